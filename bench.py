@@ -2,7 +2,7 @@
 """Headline benchmark: aggregation edges/s on the synthetic homophily sweep the north star quotes its target on
 (BASELINE.json configs[2], SURVEY.md 8(d) config C3: the `data_synthesis/4000`-equivalent set).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N worker processes (one per
@@ -23,11 +23,15 @@ A step = one pass of the hot path over that batch with all inputs resident in HB
   (4) the logits aggregation A_hat (.) (F = C, csrc/spmm_narrow.hip)
   (WDG_SWEEP_RIDE_LABELS=0 / WDG_SWEEP_FUSED_MLP=0 / WDG_SWEEP_DERIVE_COUNTS=0 restore the separate label aggregation / the
   two GEMM launches / the integer pass over the edges: 7)
-`value` = stored entries of A+I aggregated per second over the whole job (all ranks); the dominant kernel's roofline is
-measured live with HIP events on the launch stream (sampled: 50 launches over the timed region); a bounded CPU sample of the
-same workload, run the way the reference does it, is reported as `cpu_baseline` (rank 0, N=1 only).
+`value` = stored entries of A+I aggregated per second over the whole job (all ranks), `ms_per_step` = one timed step.  A plain
+run sets up, warms up, times the `--steps` steps and prints the line; everything else waits for `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (metric rows, logits, a seeded sample of the aggregated features)
+as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
 
-Beside the headline the N = 1 line carries (each can be switched off, see --help):
+With `--full` the dominant kernel's roofline is measured live with HIP events on the launch stream (sampled: 50 launches over
+the timed region), a bounded CPU sample of the same workload, run the way the reference does it, is reported as `cpu_baseline`
+(rank 0, N=1 only), the full record is written beside the line (its path: `detail`), and the N = 1 line carries (each can be
+switched off, see --help):
   secondary           the `800` set (k = 2, 100 graphs) through the same step
   sweep_full / sweep_cold   all nine scalars of the sweep job: replayed on a resident batch / every graph visited once
   sweep_whole         the sweep the reference runs (synthetic_plot.py: 6 feature bases x 28 levels x 10 samples = 1 680 jobs, nine
@@ -124,8 +128,9 @@ def launch_workers(args, argv):
     return 0
 
 
-def measure(args, k, seeds, steps, warmup, world, rank, dev):
-    """Build this rank's shard of the (k, seeds) sweep, time `steps` steps -> dict of raw measurements (every rank)."""
+def measure(args, k, seeds, steps, warmup, world, rank, dev, dump=False):
+    """Build this rank's shard of the (k, seeds) sweep, time `steps` steps -> dict of raw measurements (every rank).
+    dump: also copy what the last timed step computed to the host (`outputs`, see step_outputs)."""
     import torch
     import torch.distributed as dist
     from wdg_amd import sweep, synth
@@ -158,10 +163,12 @@ def measure(args, k, seeds, steps, warmup, world, rank, dev):
         return sorted(a.elapsed_time(b) for a, b in marks)
 
     # the aggregation launch with the MODELLED tape cut (what a one-pass sweep - sweep_cold, sweep_whole - runs with), reported beside
-    # the tuned launch the replayed headline batch uses
-    for _ in range(5):
-        batch.step()
-    untuned_ms = spmm_launch_ms(ROOFLINE_LAUNCHES)
+    # the tuned launch the replayed headline batch uses; --full only, like the rest of the roofline
+    untuned_ms = []
+    if args.full:
+        for _ in range(5):
+            batch.step()
+        untuned_ms = spmm_launch_ms(ROOFLINE_LAUNCHES)
     batch.tune()  # (replayed `steps` times: the feedback-balanced tape cut pays; ~250 untimed steps, 55 ms)
 
     def sync_all():
@@ -178,8 +185,10 @@ def measure(args, k, seeds, steps, warmup, world, rank, dev):
     # roofline figure is sampled instead of taxing every step; all steps run the same launches either way
     # (never more than every fourth step, starting at the third: a run of 20 steps is not taxed on every step, and the launch
     # right behind the synchronisation - 20-25 us of wake-up on top of the kernel - is not one of five samples)
+    # (--full only: a plain run times the steps and nothing inside them)
     stride = max(4, steps // 50)
-    ev = {s: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for s in range(min(2, steps - 1), steps, stride)}
+    ev = {s: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for s in range(min(2, steps - 1), steps, stride)} if args.full else {}
     for _ in range(warmup):
         batch.step()
     sync_all()
@@ -206,13 +215,14 @@ def measure(args, k, seeds, steps, warmup, world, rank, dev):
         total_edges = int(e.item())
     else:
         total_edges = batch.edges
+    outputs = step_outputs(batch, gathered) if dump else None
     if os.environ.get("WDG_BENCH_DUMP_LAUNCHES"):
         print("launch us by step:", " ".join(f"{s_}:{a.elapsed_time(b) * 1e3:.0f}" for s_, (a, b) in sorted(ev.items())), file=sys.stderr)
     spmm_ms = [a.elapsed_time(b) for a, b in ev.values()]
     in_region = len(spmm_ms)
     # SURVEY 8(d) asks for >= 20 launches whatever --steps is (the driver runs 20 steps: 5 samples at every fourth step): the same steps
     # go on right behind the timed region, every one with an event pair, until ROOFLINE_LAUNCHES launches have been timed
-    if in_region < ROOFLINE_LAUNCHES:
+    if args.full and in_region < ROOFLINE_LAUNCHES:
         for _ in range(3):
             batch.step()
         extra = spmm_launch_ms(ROOFLINE_LAUNCHES - in_region)
@@ -222,7 +232,40 @@ def measure(args, k, seeds, steps, warmup, world, rank, dev):
     spmm_ms.sort()
     return dict(batch=batch, mine=mine, h_levels=h_levels, elapsed=elapsed, enqueue_s=enqueue_s, total_edges=total_edges,
                 n_graphs=sum(g.shape[0] for g in gathered), spmm_ms=spmm_ms, spmm_in_region=in_region, untuned_ms=untuned_ms,
-                k=k, seeds=seeds, steps=steps)
+                k=k, seeds=seeds, steps=steps, outputs=outputs)
+
+
+DUMP_Y_ROWS = 256  # rows of every graph's aggregated features in the --dump-outputs sample (seeded, the same rows for every graph)
+DUMP_LIMIT = 64 << 20  # bytes of all --dump-outputs files together
+
+
+def step_outputs(batch, gathered):
+    """What a caller of the timed path receives from its last step, as host float32 arrays: the metric rows of every job (all
+    ranks), the GCN-2 logits of this rank's graphs and a fixed, seeded sample of the rows of its aggregated features (the whole
+    Y of the headline shard is 200 MB)."""
+    import numpy as np
+    import torch
+    out = {"results": torch.cat([g.cpu() for g in gathered]).float().numpy()}
+    if batch.gcn:
+        out["logits"] = torch.stack(batch.gcn["logits"]).cpu().float().numpy()
+    ys = batch.y
+    if ys:
+        n = min(int(y.shape[0]) for y in ys)
+        rows = np.sort(np.random.default_rng(0).choice(n, min(DUMP_Y_ROWS, n), replace=False))
+        idx = torch.from_numpy(rows).to(ys[0].device)
+        out["y_sample"] = torch.stack([y.index_select(0, idx) for y in ys]).cpu().float().numpy()
+    return out
+
+
+def write_outputs(outputs, path):
+    """--dump-outputs: one DIR/<name>.npy per array (float32), at most DUMP_LIMIT bytes in all"""
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: outputs of {total} bytes exceed the {DUMP_LIMIT}-byte limit of --dump-outputs")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def measure_full(args, dev):
@@ -816,11 +859,12 @@ def compact_line(out, detail_path=None):
     line["config"] = {"workload": _short(cfg.get("workload", ""), 200),
                       **{k: cfg[k] for k in ("graphs_per_step_per_gpu", "edges_per_step_per_gpu") if k in cfg},
                       "parallelism": _short(cfg.get("parallelism", ""), 80)}
-    rl = out.get("roofline") or {}
-    line["roofline"] = {k: _num(rl.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_traffic", "kernel",
-                                                     "avg_launch_us", "median_launch_us", "launches_timed", "launches_in_timed_region",
-                                                     "algorithmic_bytes_per_launch", "unique_bytes_per_launch", "untuned_launch_us",
-                                                     "untuned_frac") if k in rl}
+    rl = out.get("roofline")
+    if rl:
+        line["roofline"] = {k: _num(rl.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_traffic", "kernel",
+                                                         "avg_launch_us", "median_launch_us", "launches_timed", "launches_in_timed_region",
+                                                         "algorithmic_bytes_per_launch", "unique_bytes_per_launch", "untuned_launch_us",
+                                                         "untuned_frac") if k in rl}
     cb = out.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {**{k: _num(cb.get(k)) for k in ("value", "unit", "cores", "kind", "physical_cores", "value_1_thread",
@@ -889,28 +933,34 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="beside the headline also measure the roofline of its aggregation launch, the "
+                    "CPU baseline and every side block below (each can be switched off); without it a run sets up, warms up, times the "
+                    "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed "
+                    "(results: metric rows of every job; logits: GCN-2 logits; y_sample: seeded rows of the aggregated features) "
+                    "as DIR/<name>.npy, float32")
     ap.add_argument("--seeds", type=int, default=5, help="seeds per rank (x 10 homophily levels = graphs per step)")
     ap.add_argument("--nodes", type=int, default=2000)
     ap.add_argument("--feat", type=int, default=500)
     ap.add_argument("--k", type=int, default=10, help="same-class out-neighbours per node (10 = `4000` set, 2 = `800` set)")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work (0 = skip)")
-    ap.add_argument("--secondary", type=int, default=1, help="1: also time the `800` set (k=2, 10 seeds) and report it as `secondary` (N=1 only)")
-    ap.add_argument("--full-metrics", type=int, default=1, help="1: also time the whole nine-scalar sweep job batch (adds generalized edge "
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU baseline work (0 = skip)")
+    ap.add_argument("--secondary", type=int, default=1, help="--full, 1: also time the `800` set (k=2, 10 seeds) and report it as `secondary` (N=1 only)")
+    ap.add_argument("--full-metrics", type=int, default=1, help="--full, 1: also time the whole nine-scalar sweep job batch (adds generalized edge "
                     "homophily and the kernel-regression p-values, --kr-epochs epochs) and report it as `sweep_full` (N=1 only)")
     ap.add_argument("--kr-epochs", type=int, default=100)
-    ap.add_argument("--cold", type=int, default=1, help="1: also time the one-pass (cold) sweep - distinct shards from host COO to "
+    ap.add_argument("--cold", type=int, default=1, help="--full, 1: also time the one-pass (cold) sweep - distinct shards from host COO to "
                     "metric rows, everything inside the clock - and report it as `sweep_cold` (N=1 only)")
     ap.add_argument("--cold-shards", type=int, default=3)
-    ap.add_argument("--whole", type=int, default=1, help="1: also run the reference's whole sweep (6 feature bases x 28 levels x 10 samples = 1 680 "
+    ap.add_argument("--whole", type=int, default=1, help="--full, 1: also run the reference's whole sweep (6 feature bases x 28 levels x 10 samples = 1 680 "
                     "jobs, nine scalars, one pass) and report it as `sweep_whole` (N > 1: sharded over the ranks, + rank 0's one-GPU pass -> strong_speedup_vs_1gpu)")
     ap.add_argument("--whole-levels-per-shard", type=int, default=7)
-    ap.add_argument("--configs", type=int, default=1, help="1: also time BASELINE configs[0], [3], [4] as stated and the literal N = 4000 "
+    ap.add_argument("--configs", type=int, default=1, help="--full, 1: also time BASELINE configs[0], [3], [4] as stated and the literal N = 4000 "
                     "reading of configs[2] and report them as `configs` (N=1 only)")
     ap.add_argument("--config-reps", type=int, default=10)
-    ap.add_argument("--train", type=int, default=1, help="1: also time the train + eval sweep (SGC-1, GCN-2) on the shard and report it as `train` (N=1 only)")
+    ap.add_argument("--train", type=int, default=1, help="--full, 1: also time the train + eval sweep (SGC-1, GCN-2) on the shard and report it as `train` (N=1 only)")
     ap.add_argument("--train-epochs", type=int, default=30)
-    ap.add_argument("--gnb", type=int, default=1, help="1: also time the GNB classifier-based metric on a Cora-sized input, device call beside scikit-learn on the host (N=1 only)")
-    ap.add_argument("--projection", type=int, default=1, help="1: also step every rank's shard of the 50-job sweep for world sizes 2 / 4 / 8 on "
+    ap.add_argument("--gnb", type=int, default=1, help="--full, 1: also time the GNB classifier-based metric on a Cora-sized input, device call beside scikit-learn on the host (N=1 only)")
+    ap.add_argument("--projection", type=int, default=1, help="--full, 1: also step every rank's shard of the 50-job sweep for world sizes 2 / 4 / 8 on "
                     "this GPU and report the projected strong scaling as `scaling_projection` (N=1 only)")
     ap.add_argument("--projection-steps", type=int, default=100)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak", help="weak: --seeds seeds PER RANK (per-GPU work fixed); "
@@ -941,7 +991,7 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)  # RCCL
 
-    m = measure(args, args.k, args.seeds, args.steps, args.warmup, world, rank, dev)
+    m = measure(args, args.k, args.seeds, args.steps, args.warmup, world, rank, dev, dump=bool(args.dump_outputs) and rank == 0)
     if rank == 0:
         batch = m["batch"]
         out = {
@@ -966,10 +1016,14 @@ def main():
             "graphs_per_s": m["n_graphs"] * args.steps / m["elapsed"],
             "edge_features_per_s": m["total_edges"] * args.feat * args.steps / m["elapsed"],
             "host_enqueue_ms_per_step": m["enqueue_s"] / args.steps * 1e3,
-            "roofline": roofline_of(args, m),
         }
+        if args.full:
+            out["roofline"] = roofline_of(args, m)
+        if args.dump_outputs:
+            write_outputs(m["outputs"], args.dump_outputs)
     del m
-    if world == 1 and args.secondary and not (args.k == 2 and args.seeds == 10):
+    full = args.full
+    if full and world == 1 and args.secondary and not (args.k == 2 and args.seeds == 10):
         torch.cuda.empty_cache()
         steps2 = max(20, args.steps // 2)
         m2 = measure(args, 2, 10, steps2, min(args.warmup, 10), world, rank, dev)
@@ -980,40 +1034,40 @@ def main():
                             "roofline": roofline_of(args, m2)}
         del m2
     if world > 1:
-        if args.whole:  # the reference's sweep, strong-scaled over the ranks (every rank takes part; rank 0 keeps the record)
+        if full and args.whole:  # the reference's sweep, strong-scaled over the ranks (every rank takes part; rank 0 keeps the record)
             torch.cuda.empty_cache()
             whole = measure_whole(args, dev, world, rank)
             if rank == 0:
                 out["sweep_whole"] = whole
         dist.destroy_process_group()  # (before the line: RCCL writes its library path to stdout when it shuts down)
-    if world == 1 and args.full_metrics:
+    if full and world == 1 and args.full_metrics:
         out["sweep_full"] = measure_full(args, dev)
-    if world == 1 and args.cold:
+    if full and world == 1 and args.cold:
         torch.cuda.empty_cache()
         out["sweep_cold"] = measure_cold(args, dev)
-    if world == 1 and args.whole:
+    if full and world == 1 and args.whole:
         torch.cuda.empty_cache()
         out["sweep_whole"] = measure_whole(args, dev)
-    if world == 1 and args.configs:
+    if full and world == 1 and args.configs:
         torch.cuda.empty_cache()
         out["configs"] = measure_configs(args, dev)
-    if world == 1 and args.train:
+    if full and world == 1 and args.train:
         torch.cuda.empty_cache()
         out["train"] = measure_train(args, dev)
-    if world == 1 and args.gnb:
+    if full and world == 1 and args.gnb:
         torch.cuda.empty_cache()
         out["gnb"] = measure_gnb(args, dev)
-    if world == 1 and args.projection:
+    if full and world == 1 and args.projection:
         torch.cuda.empty_cache()
         out["scaling_projection"] = measure_projection(args, dev, out["ms_per_step"])
     if rank == 0:
-        if world == 1 and args.cpu_budget > 0:
+        if full and world == 1 and args.cpu_budget > 0:
             from oracle import cpu_ref
             from wdg_amd import sweep, synth
             h_levels = synth.H_LEVELS_10 if args.k == 2 else synth.H_LEVELS_10_K10
             sample = sweep.make_jobs(h_levels, [0], k=args.k, n_nodes=args.nodes)
             out["cpu_baseline"] = cpu_ref.baseline_record(sample, args.feat, args.cpu_budget)
-        print(compact_line(out, write_detail(out)), flush=True)
+        print(compact_line(out, write_detail(out) if full else None), flush=True)
 
 
 if __name__ == "__main__":

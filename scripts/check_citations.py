@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Every `path/file.py:LINE[-LINE][,LINE..]` citation in the header, the kernels, the package, the oracle and the documents must
-resolve inside the reference checkout: the file exists and every cited line number lies inside it.  Run where /root/reference is
-mounted (the build container); tests/test_abi.py runs it in the CPU suite and skips on machines without the checkout.
+resolve inside the reference checkout: the file exists and every cited line number lies inside it.  Checked against the checkout
+itself (--ref) or against the listing of its Python files and their line counts recorded in tests/golden/reference_py_lines.json
+(--listing; written from a checkout by --write-listing), which tests/test_abi.py uses in the CPU suite.
 
-usage: python scripts/check_citations.py [--ref /root/reference] [--list]
+usage: python scripts/check_citations.py (--ref CHECKOUT | --listing JSON) [--list]
+       python scripts/check_citations.py --ref CHECKOUT --write-listing JSON
 """
 import argparse
 import glob
+import json
 import os
 import re
 import sys
@@ -55,8 +58,10 @@ def citations(path):
         yield line_no, m.group(1), spans
 
 
-def check(ref, verbose=False):
-    ref_files = reference_files(ref)
+def check(ref, verbose=False, ref_files=None):
+    """ref: the checkout, or None with ref_files = {reference-relative path: line count} (a recorded listing)"""
+    if ref_files is None:
+        ref_files = reference_files(ref)
     own = own_files()
     own_base = {os.path.basename(p) for p in own}
     bad, n = [], 0
@@ -85,13 +90,18 @@ def check(ref, verbose=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default="/root/reference")
+    ap.add_argument("--ref", help="the reference checkout")
+    ap.add_argument("--listing", default=os.path.join(ROOT, "tests", "golden", "reference_py_lines.json"),
+                    help="recorded {path: line count} of the checkout's Python files (used without --ref)")
+    ap.add_argument("--write-listing", metavar="JSON", help="record the listing of --ref to this file and stop")
     ap.add_argument("--list", action="store_true")
     a = ap.parse_args()
-    if not os.path.isdir(a.ref):
-        print(f"{a.ref} is not mounted: nothing to check against")
+    if a.write_listing:
+        with open(a.write_listing, "w") as f:
+            json.dump(dict(sorted(reference_files(a.ref).items())), f, indent=0)
+            f.write("\n")
         return 0
-    n, bad = check(a.ref, a.list)
+    n, bad = check(a.ref, a.list, None if a.ref else json.load(open(a.listing)))
     for b in bad:
         print(b)
     print(f"{n} citations checked, {len(bad)} do not resolve")

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 for rep in 1 2; do
 for s in 0 1; do
-  WDG_MLP2_SPLIT=$s python bench.py --steps 200 --warmup 20 --secondary 0 --full-metrics 0 --cpu-budget 0 --cold 0 2>/dev/null | tail -1 > /tmp/ab_$s.json
+  WDG_MLP2_SPLIT=$s python bench.py --full --steps 200 --warmup 20 --secondary 0 --full-metrics 0 --cpu-budget 0 --cold 0 2>/dev/null | tail -1 > /tmp/ab_$s.json
   python - "$s" <<'PY'
 import json, sys
 d = json.loads(open(f"/tmp/ab_{sys.argv[1]}.json").read())

@@ -51,7 +51,7 @@ def main():
             line["error"] = (r.stderr or r.stdout)[-600:]
         else:
             line.update(json.loads(res[0][7:]))
-            b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "20", "--cpu-budget", "0",
+            b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "200", "--warmup", "20", "--cpu-budget", "0",
                                 "--secondary", "0", "--full-metrics", "0", "--cold", "0", "--configs", "0", "--train", "0", "--projection", "0", "--whole", "0"], env=env, capture_output=True, text=True, timeout=900)
             try:
                 j = json.loads([l for l in b.stdout.splitlines() if l.startswith("{")][-1])

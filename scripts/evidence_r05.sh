@@ -15,15 +15,15 @@ bash scripts/profile_pmc.sh r05_c2/pmc --k 2 --seeds 10 --secondary 0 --full-met
 cp gpurun_out/r05_c2/pmc/summary.txt "$C/r05_c2_pmc_summary.txt"; cp gpurun_out/r05_c2/pmc/summary.json "$C/r05_c2_pmc_summary.json"
 bash scripts/profile_pmc.sh r05_c3lit/pmc --nodes 4000 --secondary 0 --full-metrics 0 $LEAN > gpurun_out/ev5_c3lit.log 2>&1  # the literal N = 4000 shard
 cp gpurun_out/r05_c3lit/pmc/summary.txt "$C/r05_c3lit_pmc_summary.txt"; cp gpurun_out/r05_c3lit/pmc/summary.json "$C/r05_c3lit_pmc_summary.json"
-python3 bench.py > "$C/r05_bench_full.json" 2> gpurun_out/r05_bench_full.err                  # the whole default line
-python3 bench.py --steps 20 --warmup 5 > "$C/r05_bench_driver_flags.json" 2> /dev/null         # with the driver's flags
+python3 bench.py --full > "$C/r05_bench_full.json" 2> "$C/r05_bench_full.err"                 # the whole default line
+python3 bench.py --full --steps 20 --warmup 5 > "$C/r05_bench_driver_flags.json" 2> /dev/null         # with the driver's flags
 python3 scripts/bench_configs.py --out "$C/r05_configs.jsonl" > /dev/null 2> gpurun_out/r05_configs.err   # one line per BASELINE config (+ binding resource)
 { python3 scripts/dev/ablate_quad.py 10 5 0 1 4 5 2 8 12 13; N=4000 python3 scripts/dev/ablate_quad.py 10 5 0 1 4 5 2 8 12 13; } 2>&1 | grep -v amdgpu.ids > "$C/r05_quad_ablations.txt"
 build/store_shape > "$C/r05_store_shape.txt" 2>&1
 python3 scripts/dev/ab_chunked_step.py 200 2>&1 | grep -v amdgpu.ids > "$C/r05_chunked_step.txt"
 cd /tmp && export TMPDIR=/tmp
 for part in train configs whole; do                                                            # kernel statistics of the other blocks of the line
-  flags="--steps 10 --warmup 2 --secondary 0 --full-metrics 0 --cpu-budget 0 --cold 0 --configs 0 --train 0 --projection 0 --whole 0"
+  flags="--full --steps 10 --warmup 2 --secondary 0 --full-metrics 0 --cpu-budget 0 --cold 0 --configs 0 --train 0 --projection 0 --whole 0"
   flags=${flags/--$part 0/--$part 1}
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/r05_${part}_stats" -- python3 "$ROOT/bench.py" $flags > /dev/null 2>&1
   find "$ROOT/gpurun_out/r05_${part}_stats" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$C/r05_${part}_kernel_stats.csv"

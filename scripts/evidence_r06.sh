@@ -15,14 +15,14 @@ bash scripts/profile_pmc.sh r06_c2/pmc --k 2 --seeds 10 --secondary 0 --full-met
 cp gpurun_out/r06_c2/pmc/summary.txt "$C/r06_c2_pmc_summary.txt"; cp gpurun_out/r06_c2/pmc/summary.json "$C/r06_c2_pmc_summary.json"
 bash scripts/profile_pmc.sh r06_c3lit/pmc --nodes 4000 --secondary 0 --full-metrics 0 $LEAN > gpurun_out/ev6_c3lit.log 2>&1  # the literal N = 4000 shard
 cp gpurun_out/r06_c3lit/pmc/summary.txt "$C/r06_c3lit_pmc_summary.txt"; cp gpurun_out/r06_c3lit/pmc/summary.json "$C/r06_c3lit_pmc_summary.json"
-python3 bench.py > "$C/r06_bench_full_line.json" 2> gpurun_out/r06_bench_full.err              # the whole default run: the ONE compact line ..
+python3 bench.py --full > "$C/r06_bench_full_line.json" 2> "$C/r06_bench_full.err"             # the whole default run: the ONE compact line ..
 cp gpurun_out/bench_detail.json "$C/r06_bench_full_detail.json"                                # .. and the full record it points at
-python3 bench.py --steps 20 --warmup 5 > "$C/r06_bench_driver_flags_line.json" 2> /dev/null     # with the driver's flags
+python3 bench.py --full --steps 20 --warmup 5 > "$C/r06_bench_driver_flags_line.json" 2> /dev/null     # with the driver's flags
 cp gpurun_out/bench_detail.json "$C/r06_bench_driver_flags_detail.json"
 python3 scripts/bench_configs.py --out "$C/r06_configs.jsonl" > /dev/null 2> gpurun_out/r06_configs.err   # one line per BASELINE config (+ binding resource)
 cd /tmp && export TMPDIR=/tmp
 for part in train configs whole; do                                                            # kernel statistics of the other blocks of the line
-  flags="--steps 10 --warmup 2 --secondary 0 --full-metrics 0 --cpu-budget 0 --cold 0 --configs 0 --train 0 --projection 0 --whole 0 --gnb 0"
+  flags="--full --steps 10 --warmup 2 --secondary 0 --full-metrics 0 --cpu-budget 0 --cold 0 --configs 0 --train 0 --projection 0 --whole 0 --gnb 0"
   flags=${flags/--$part 0/--$part 1}
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/r06_${part}_stats" -- python3 "$ROOT/bench.py" $flags > /dev/null 2>&1
   find "$ROOT/gpurun_out/r06_${part}_stats" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$C/r06_${part}_kernel_stats.csv"

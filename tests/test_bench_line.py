@@ -66,3 +66,32 @@ def test_multi_gpu_record_keeps_the_measured_strong_speedup():
     got = strict(bench.compact_line(rec))
     assert got["sweep_whole"]["strong_speedup_vs_1gpu"] == 6.0 and got["sweep_whole"]["rows_equal_one_gpu"] is True
     assert "workload" not in got["sweep_whole"] and "cpu_baseline" not in got
+
+
+def test_plain_run_line_keeps_the_headline_keys_without_the_full_blocks():
+    """a run without --full measures no roofline, no CPU baseline and no side block: the line still carries the headline's keys
+    and no empty `roofline`"""
+    rec = {k: v for k, v in canned().items() if k in CONTRACT and k not in ("roofline", "cpu_baseline")}
+    got = strict(bench.compact_line(rec))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in got, k
+    assert got["ms_per_step"] > 0 and "roofline" not in got and "cpu_baseline" not in got and "detail" not in got
+
+
+def test_dump_outputs_are_float32_npy_files_under_the_size_limit(tmp_path):
+    import numpy as np
+    import pytest
+    outs = {"results": np.arange(12, dtype=np.float64).reshape(4, 3), "logits": np.ones((2, 5, 5), np.float32)}
+    bench.write_outputs(outs, str(tmp_path / "d"))
+    for name, a in outs.items():
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    with pytest.raises(SystemExit):
+        bench.write_outputs({"y_sample": np.zeros(bench.DUMP_LIMIT // 4 + 1, np.float32)}, str(tmp_path / "big"))
+    assert not (tmp_path / "big").exists()
+
+
+def test_help_lists_full_and_dump_outputs():
+    import subprocess
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs" in res.stdout

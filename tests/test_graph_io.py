@@ -5,10 +5,21 @@ import os
 import numpy as np
 import pytest
 
-from _golden import load
+from _golden import GOLDEN_DIR, load
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="raw dataset files live in the reference checkout")
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    """the reference's raw dataset files (tests/golden/raw_*.npz, written by make_loader_inputs.py) back on disk, at the paths
+    the reference's loaders read them from"""
+    root = tmp_path_factory.mktemp("reference")
+    for group in ("texas", "film", "cora", "citeseer", "topology"):
+        with np.load(os.path.join(GOLDEN_DIR, f"raw_{group}.npz")) as z:
+            for key in z.files:
+                path = root.joinpath(*key.split("|"))
+                path.parent.mkdir(parents=True, exist_ok=True)
+                path.write_bytes(z[key].tobytes())
+    return str(root)
 
 
 def _coo_of(golden):
@@ -25,11 +36,10 @@ def _dense_features(golden):
     return x
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["texas", "film"])
-def test_geom_gcn_converter_matches_reference_loader(name):
+def test_geom_gcn_converter_matches_reference_loader(ref, name):
     from wdg_amd import graph_io
-    d = os.path.join(REF, "new_data", name)
+    d = os.path.join(ref, "new_data", name)
     rowptr, col, x, y = graph_io.read_geom_gcn(os.path.join(d, "out1_graph_edges.txt"),
                                                os.path.join(d, "out1_node_feature_label.txt"), film=(name == "film"))
     g = load("real_" + name)
@@ -41,11 +51,10 @@ def test_geom_gcn_converter_matches_reference_loader(name):
     np.testing.assert_array_equal(x.astype(np.float32), _dense_features(g))
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["cora", "citeseer"])
-def test_planetoid_converter_matches_reference_loader(name):
+def test_planetoid_converter_matches_reference_loader(ref, name):
     from wdg_amd import graph_io
-    rowptr, col, x, y = graph_io.read_planetoid(os.path.join(REF, "data"), name)
+    rowptr, col, x, y = graph_io.read_planetoid(os.path.join(ref, "data"), name)
     g = load("real_" + name)
     rows, cols = graph_io.csr_to_coo(rowptr, col)
     want_r, want_c = _coo_of(g)
@@ -55,17 +64,16 @@ def test_planetoid_converter_matches_reference_loader(name):
     np.testing.assert_array_equal(x, _dense_features(g))
 
 
-@needs_ref
-def test_synthetic_pt_and_topology_converters():
+def test_synthetic_pt_and_topology_converters(ref):
     from wdg_amd import graph_io
-    rowptr, col, n = graph_io.read_synthetic_pt(os.path.join(REF, "data_synthesis", "800", "0.5", "adj_0.5_0.pt"))
+    rowptr, col, n = graph_io.read_synthetic_pt(os.path.join(ref, "data_synthesis", "800", "0.5", "adj_0.5_0.pt"))
     g = load("syn_800_0.5_0")
     assert n == int(g["n_nodes"])
     rows, cols = graph_io.csr_to_coo(rowptr, col)
     order = np.lexsort((g["adj_col"], g["adj_row"]))
     np.testing.assert_array_equal(rows, g["adj_row"][order])
     np.testing.assert_array_equal(cols, g["adj_col"][order])
-    rowptr, col, n = graph_io.read_edge_tsv(os.path.join(REF, "new_data", "chameleon", "out1_graph_edges.txt"))
+    rowptr, col, n = graph_io.read_edge_tsv(os.path.join(ref, "new_data", "chameleon", "out1_graph_edges.txt"))
     t = load("topo_chameleon")
     assert n == int(t["n_nodes"])
     rows, cols = graph_io.csr_to_coo(rowptr, col)
