@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cold six-scalar shards per second through sweep.run_shards at several (depth, helper thread) settings (dev tool).
+"""Cold six-scalar shards per second through sweep.run_shards, unpipelined and two deep with the helper thread (dev tool).
     python scripts/dev/time_cold_modes.py [shards]"""
 import os
 import sys
@@ -25,8 +25,7 @@ def host_inputs(first_seed):
 
 shards = [host_inputs(1000 + 5 * b) for b in range(n)]
 for nine in (False, True):
-    for depth, force in ((1, "0"), (1, "1"), (2, "0"), (2, "1")):
-        os.environ["WDG_SWEEP_BUILD_THREAD_FORCE"] = force
+    for depth in (1, 2):
         best = 1e9
         for rep in range(3):
             torch.cuda.synchronize()
@@ -34,4 +33,4 @@ for nine in (False, True):
             rows = list(sweep.run_shards(shards, n_feat=500, nine=nine, depth=depth, first_seed=1))
             torch.cuda.synchronize()
             best = min(best, time.perf_counter() - t0)
-        print(f"nine={nine} depth={depth} helper thread={force}: {n * 50 / best:8.0f} graphs/s ({best / n * 1e3:.2f} ms per shard)", flush=True)
+        print(f"nine={nine} depth={depth}: {n * 50 / best:8.0f} graphs/s ({best / n * 1e3:.2f} ms per shard)", flush=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The batched kernel-regression solver on the C3 shard's 20 000 problems (dev tool): launch time, and - A/B in two processes,
-WDG_KR_KERNEL=rank1 is round 2's solver - the per-problem hit counts written to gpurun_out/ for comparison.
+"""The batched kernel-regression solver on the C3 shard's 20 000 problems (dev tool): launch time, and the per-problem hit
+counts (written to out.npy when given, for comparison between builds).
     python scripts/dev/time_kr_batch.py [seeds] [epochs] [out.npy]"""
 import os
 import sys
@@ -33,7 +33,7 @@ torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 3
 n = sb.kr.n_jobs
 flops = n * (300 ** 3 / 3 + 2 * 300 * 300 * 8 + 2 * 200 * 300 * 8)
-print(f"kernel={os.environ.get('WDG_KR_KERNEL', 'blocked')}: {n} regressions in {ms:.2f} ms = {ms * 1e3 / n * 256:.1f} us per problem and CU, "
+print(f"{n} regressions in {ms:.2f} ms = {ms * 1e3 / n * 256:.1f} us per problem and CU, "
       f"{flops / ms * 1e-9:.1f} TFLOP/s; ridged {int(sb.kr.ridged().sum())}", flush=True)
 correct = sb.kr.correct[:n].cpu().numpy()
 print("hits: mean %.2f min %d max %d" % (correct.mean(), correct.min(), correct.max()))

@@ -33,14 +33,9 @@ def timed(reps, cold):
     return t[len(t) // 2], t[0]
 
 
-for parts in ("", "4", "5", "8"):
-    for split in ("0", "1"):
-        os.environ["WDG_MLP2_SPLIT"] = split
-        if parts:
-            os.environ["WDG_GEMM_PARTS"] = parts
-        else:
-            os.environ.pop("WDG_GEMM_PARTS", None)
-        batch.launch()
-        torch.cuda.synchronize()
-        warm, cold = timed(20, False), timed(20, True)
-        print(f"parts={parts or 'auto'} split={split}: warm median {warm[0]:.1f} us (min {warm[1]:.1f}), cold median {cold[0]:.1f} us (min {cold[1]:.1f})")
+for split in ("0", "1"):
+    os.environ["WDG_MLP2_SPLIT"] = split
+    batch.launch()
+    torch.cuda.synchronize()
+    warm, cold = timed(20, False), timed(20, True)
+    print(f"split={split}: warm median {warm[0]:.1f} us (min {warm[1]:.1f}), cold median {cold[0]:.1f} us (min {cold[1]:.1f})")

@@ -2,7 +2,8 @@
 # Everything profiles/ holds for round 4, from one box (run ON the GPU box from the repo root): bash scripts/evidence_r04.sh
 # (one rank only: the profiled process never spawns workers - scripts/profile_pmc.sh refuses --gpus > 1)
 # Needs the -DWDG_Q_PROFILE builds of scripts/dev/build_quad_variants.sh under when-do-gnns-help_amd/lib/variants/prof_{dyn,static,noadds}.so
-# (QUAD_EXTRA="-DWDG_Q_PROFILE [-DWDG_Q_STATIC_DEAL | -DWDG_Q_ABLATE_ADDS]" scripts/dev/build_quad_variants.sh "1024 1", renamed).
+# (QUAD_EXTRA="-DWDG_Q_PROFILE" scripts/dev/build_quad_variants.sh "1024 1", renamed; the static-deal and no-adds variants were
+# built from compile-time switches that the kernel no longer has).
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"

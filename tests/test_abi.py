@@ -98,15 +98,14 @@ def test_no_shipped_kernel_spills_vector_registers():
         pytest.skip("no resource reports (the library was built without the Makefile)")
     # known and bounded: the two 64-column B-resident MFMA kernels sit at the 128-register cap of a
     # 1024-thread workgroup and spill a handful of registers outside their K loop's MFMA chain
-    # ... and the kernel-regression solver parks a few registers around (not inside) the factorisation steps of a block
-    # ... and the blocked solver (48 accumulator registers + the in-wave substitution) parks 9 outside its steps: the gather, the
-    # update's operand addresses and the predictions (tests read the per-phase count with scripts in DESIGN.md 4.8); round 5's
+    # ... and the blocked kernel-regression solver (48 accumulator registers + the in-wave substitution) parks 9 outside its
+    # steps: the gather, the update's operand addresses and the predictions (tests read the per-phase count with scripts in DESIGN.md 4.8); round 5's
     # persistent form carries the previous problem's deferred predictions through the factorisation: 17; round 6: the rows' pivot
     # thresholds (19) and, in the instantiation that reads a deflation workspace, its address, the mixed-label switch and the class scales (25) -
     # measured 6.51 against 6.47 ms per 11 000 regressions (profiles/r06_kr_*)
     # ... and the several-column-block variants of the quad-row kernel (MULTI = true) hold 16 slices of accumulators per wave
     # across the blocks - a whole N = 4000 graph per item - and park 4 (pattern only) / 16 (explicit values) registers
-    allowed = {"gemm_bres_kernelILi2E": 13, "mlp2_bres_kernelILi2E": 9, "kr_solve_kernel": 16, "kr_solve_blocked_kernel": 20,
+    allowed = {"gemm_bres_kernelILi2E": 13, "mlp2_bres_kernelILi2E": 9, "kr_solve_blocked_kernel": 20,
                "spmm_quad_kernelIfLb0ELi1E": 4, "spmm_quad_kernelItLb0ELi1E": 4, "spmm_quad_kernelIfLb1ELi1E": 16,
                "spmm_quad_kernelItLb1ELi1E": 16}
     seen = 0

@@ -126,15 +126,14 @@ def test_whole_sweep_over_feature_bases_equals_stand_alone_batches():
         assert torch.equal(torch.nan_to_num(rows, nan=-7.0), torch.nan_to_num(want, nan=-7.0)), (si, bi)
 
 
-def test_table_reuse_across_wide_feature_bases_equals_stand_alone_batches(monkeypatch):
+def test_table_reuse_across_wide_feature_bases_equals_stand_alone_batches_at_every_depth(monkeypatch):
     """run_bases over several WIDE feature bases (the propagated route: label columns only in the aggregation): the bases of a shard
     share one step (step twins), a base takes over the prepared batch of an earlier base of equal sample_max (rebind_features: same
-    buffers, new features, new node-set keys) and the bases are visited out of order - every (shard, base) still gives the rows
-    of a stand-alone SweepBatch over the same inputs, bit for bit, and the same rows as the driver without any reuse
-    (WDG_SWEEP_REBIND=0 WDG_SWEEP_STEP_TWINS=0 WDG_SWEEP_PREFETCH_BUILD=0), unpipelined or with three base-shards in flight."""
+    buffers, new features, new node-set keys) and the bases are visited out of order (rows arrive in that order, tagged with their
+    base) - every (shard, base) still gives the rows of a stand-alone SweepBatch over the same inputs, bit for bit, pipelined two
+    deep, unpipelined or with three base-shards in flight."""
     from wdg_amd import sweep, synth
-    for name in ("WDG_SWEEP_REBIND", "WDG_SWEEP_STEP_TWINS", "WDG_SWEEP_PREFETCH_BUILD", "WDG_GRAM_ROUTE", "WDG_SWEEP_PROLOGUE"):
-        monkeypatch.delenv(name, raising=False)  # (this test asserts WHICH bases were rebound / twinned under the defaults)
+    monkeypatch.delenv("WDG_GRAM_ROUTE", raising=False)  # (this test asserts WHICH bases were rebound / twinned under the defaults)
     levels, samples = [0.2, 0.5, 0.8], [0, 1]
     graphs = {(h, s_): synth.regular_graph(600, 5, 4, h, s_) for h in levels for s_ in samples}
     widths = [("p1", 656, 500), ("p2", 700, 500), ("n", 97, 500), ("p3", 720, 300), ("p4", 800, 500), ("p5", 650, 300)]
@@ -148,8 +147,11 @@ def test_table_reuse_across_wide_feature_bases_equals_stand_alone_batches(monkey
     orig_rebind, orig_twin = sweep.SweepBatch.rebind_features, sweep.SweepBatch._init_step_twin
     monkeypatch.setattr(sweep.SweepBatch, "rebind_features", lambda self, *a, **k: (rebinds.append(a[1]), orig_rebind(self, *a, **k))[1])
     monkeypatch.setattr(sweep.SweepBatch, "_init_step_twin", lambda self, *a, **k: (twins.append(a[2]), orig_twin(self, *a, **k))[1])
-    got = {(si, bi): rows for si, bi, rows in sweep.run_bases(shards, bases, epochs=6, depth=2, first_seed=5)}
-    assert sorted(got) == [(si, bi) for si in range(2) for bi in range(6)]
+    order, got = [], {}
+    for si, bi, rows in sweep.run_bases(shards, bases, epochs=6, depth=2, first_seed=5):
+        order.append((si, bi))
+        got[(si, bi)] = rows
+    assert order == [(si, bi) for si in range(2) for bi in (0, 3, 1, 2, 4, 5)]  # (the visit order, shard by shard)
     assert sorted(rebinds) == [650, 650, 700, 700, 800, 800] and sorted(twins) == [720, 720]  # per shard: p2, p4, p5 rebound; p3 a twin of p1
     monkeypatch.setattr(sweep.SweepBatch, "rebind_features", orig_rebind)
     monkeypatch.setattr(sweep.SweepBatch, "_init_step_twin", orig_twin)
@@ -166,27 +168,14 @@ def test_table_reuse_across_wide_feature_bases_equals_stand_alone_batches(monkey
     for depth in (1, 3):  # (unpipelined: a batch is free again at once; three in flight: a base may find no free batch and builds its own)
         for si, bi, rows in sweep.run_bases(shards, bases, epochs=6, depth=depth, first_seed=5):
             assert torch.equal(torch.nan_to_num(rows, nan=-7.0), torch.nan_to_num(got[(si, bi)], nan=-7.0)), (depth, si, bi)
-    monkeypatch.setenv("WDG_SWEEP_PROLOGUE", "1")  # (round 6's feature prologue - a helper thread uploads the wide bases' features and
-    for si, bi, rows in sweep.run_bases(shards, bases, epochs=6, depth=2, first_seed=5):  # launches their Grams ahead - : the same rows)
-        assert torch.equal(torch.nan_to_num(rows, nan=-7.0), torch.nan_to_num(got[(si, bi)], nan=-7.0)), ("prologue", si, bi)
-    monkeypatch.delenv("WDG_SWEEP_PROLOGUE")
-    monkeypatch.setenv("WDG_SWEEP_REBIND", "0")
-    monkeypatch.setenv("WDG_SWEEP_STEP_TWINS", "0")
-    monkeypatch.setenv("WDG_SWEEP_PREFETCH_BUILD", "0")
-    order = []
-    for si, bi, rows in sweep.run_bases(shards, bases, epochs=6, depth=2, first_seed=5):
-        order.append((si, bi))
-        assert torch.equal(torch.nan_to_num(rows, nan=-7.0), torch.nan_to_num(got[(si, bi)], nan=-7.0)), (si, bi)
-    assert order == [(si, bi) for si in range(2) for bi in range(6)]  # (the caller's order without reuse)
 
 
 def test_a_graph_without_sell16_copy_in_a_wide_base_shard_falls_back_instead_of_raising(monkeypatch):
     """run_bases decided labels_only from the widths alone; one skewed graph in the shard (SELL-16 copy refused) made
-    prepare_full raise and aborted the sweep.  Now the route is decided after the build (graphs built ahead) and a labels-only
-    batch that cannot propagate falls back to the direct route over the on-demand aggregation (graphs built in place)."""
+    prepare_full raise and aborted the sweep.  Now the route is decided after the build (graphs built ahead): the shard's bases
+    aggregate at full width and take the direct route."""
     from wdg_amd import ops, sweep, synth
-    for name in ("WDG_SWEEP_REBIND", "WDG_SWEEP_STEP_TWINS", "WDG_SWEEP_PREFETCH_BUILD", "WDG_GRAM_ROUTE"):
-        monkeypatch.delenv(name, raising=False)
+    monkeypatch.delenv("WDG_GRAM_ROUTE", raising=False)
     levels, samples = [0.2, 0.5, 0.8], [0]
     jobs = sweep.make_jobs(levels, samples, k=4, n_nodes=600)
     gi = [synth.regular_graph(600, 5, 4, j.h, j.seed) for j in jobs]
@@ -198,15 +187,13 @@ def test_a_graph_without_sell16_copy_in_a_wide_base_shard_falls_back_instead_of_
         orig(self)
         self.graphs[1].quad = False  # (what ensure_quad / the batched build decide for rows that would pad beyond 4 x)
     monkeypatch.setattr(ops.GraphBatch, "finish", finish_and_refuse_one)
-    for prefetch in ("1", "0"):
-        monkeypatch.setenv("WDG_SWEEP_PREFETCH_BUILD", prefetch)
-        got = {bi: rows for _si, bi, rows in sweep.run_bases([(jobs, gi)], bases, epochs=4, depth=2, first_seed=3)}
-        assert sorted(got) == [0, 1]
-        for bi in got:
-            assert got[bi].shape == want[bi].shape and bool(torch.isfinite(got[bi][:, :7]).all())
-            # the scalars that do not depend on the kernels' route: equal to the all-quad run's to fp32 rounding
-            assert torch.allclose(got[bi][:, :7], want[bi][:, :7], rtol=2e-5, atol=1e-6), (prefetch, bi)
-            assert bool(((got[bi][:, 7:] >= 0) & (got[bi][:, 7:] <= 1)).all())
+    got = {bi: rows for _si, bi, rows in sweep.run_bases([(jobs, gi)], bases, epochs=4, depth=2, first_seed=3)}
+    assert sorted(got) == [0, 1]
+    for bi in got:
+        assert got[bi].shape == want[bi].shape and bool(torch.isfinite(got[bi][:, :7]).all())
+        # the scalars that do not depend on the kernels' route: equal to the all-quad run's to fp32 rounding
+        assert torch.allclose(got[bi][:, :7], want[bi][:, :7], rtol=2e-5, atol=1e-6), bi
+        assert bool(((got[bi][:, 7:] >= 0) & (got[bi][:, 7:] <= 1)).all())
 
 
 def test_nine_scalars_with_propagated_grams_match_the_direct_route(monkeypatch):

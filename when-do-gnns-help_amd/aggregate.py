@@ -125,14 +125,10 @@ _QUAD_COST_NS = np.array([1590, 1590, 1619, 1668, 1756, 1768, 1908, 1980, 2076, 
 
 def _quad_unit_cost(widths):
     """modelled cost of the super-units (4 slices = 64 rows each) of a graph from its slices' entries per row (summed over
-    column blocks): the measured table above, extended linearly; WDG_QUAD_ALPHA / WDG_QUAD_WMIN (entries) select the
-    two-parameter model max(width, wmin) + alpha instead (experiments)"""
+    column blocks): the measured table above, extended linearly"""
     w = widths.sum(0).astype(np.float64)
-    if "WDG_QUAD_ALPHA" in os.environ or "WDG_QUAD_WMIN" in os.environ:
-        per_slice = np.maximum(w, float(os.environ.get("WDG_QUAD_WMIN", "8"))) + float(os.environ.get("WDG_QUAD_ALPHA", "4"))
-    else:
-        per_slice = np.where(w <= _QUAD_COST_W[-1], np.interp(w, _QUAD_COST_W, _QUAD_COST_NS),
-                             _QUAD_COST_NS[-1] + 43.0 * (w - _QUAD_COST_W[-1]))
+    per_slice = np.where(w <= _QUAD_COST_W[-1], np.interp(w, _QUAD_COST_W, _QUAD_COST_NS),
+                         _QUAD_COST_NS[-1] + 43.0 * (w - _QUAD_COST_W[-1]))
     return per_slice.reshape(-1, 4).sum(1)
 
 
@@ -221,8 +217,7 @@ def _quad_segments(entries, order, n_feat, cus=256, phase_ns=None, shares=None):
         runs.append(end - pos)
         pos = end
     memo_key = (tuple(id(entries[i][0]) for i in order), tuple(runs), n_feat, cus, phase_ns, None if shares is None else tuple(shares),
-                os.environ.get("WDG_QUAD_SUBS"), os.environ.get("WDG_QUAD_PHASE_NS"), os.environ.get("WDG_QUAD_PHASE_ORDER"),
-                os.environ.get("WDG_QUAD_ALPHA"), os.environ.get("WDG_QUAD_WMIN"))
+                os.environ.get("WDG_QUAD_PHASE_NS"))
     memo = entries[order[0]][0].__dict__.setdefault("_seg_memo", {}) if order else {}
     if memo_key in memo:
         return memo[memo_key]
@@ -246,9 +241,6 @@ def _quad_segments(entries, order, n_feat, cus=256, phase_ns=None, shares=None):
         subs = min(range(1, 5), key=lambda s_: (-(-s_ * n_groups // per_xcd) / (s_ * n_groups / per_xcd), s_))
     else:
         subs = -(-per_xcd // n_groups)
-    forced = os.environ.get("WDG_QUAD_SUBS")
-    if forced:
-        subs = int(forced)
     subs = max(1, min(subs, max(1, n_units // (8 * 8))))
     if multi:  # a wave keeps at most 4 super-units (Q_MAXU = 16 slices) across the column blocks: items of <= 64 super-units
         subs = max(subs, -(-n_units // (8 * QUAD_MULTI_ITEM_SU)))
@@ -269,9 +261,10 @@ def _quad_segments(entries, order, n_feat, cus=256, phase_ns=None, shares=None):
         seg_of = np.searchsorted(cuts_a, lo, side="right") - 1          # (the LAST segment starting at or before lo: empty segments own nothing)
         grp_of = np.searchsorted(g_off, lo, side="right") - 1
         cost = cum[hi] - cum[lo]
-        if os.environ.get("WDG_QUAD_PHASE_ORDER", "1") != "0":           # (the phases of a segment run shortest first: see below)
-            perm = np.lexsort((np.arange(len(lo)), cost, seg_of))
-            lo, hi, seg_of, grp_of = lo[perm], hi[perm], seg_of[perm], grp_of[perm]
+        # the phases of a segment run shortest first: staging a slab costs 8 us while the memory system is quiet and 20 - 55 us
+        # once the launch's stores have filled the write path (scripts/dev/stamps_quad_phases.py: the later the switch, the dearer)
+        perm = np.lexsort((np.arange(len(lo)), cost, seg_of))
+        lo, hi, seg_of, grp_of = lo[perm], hi[perm], seg_of[perm], grp_of[perm]
         first = np.array([g[0] for g in groups], np.int64)
         nj = np.array([g[1] for g in groups], np.int64)
         items = list(zip(first[grp_of].tolist(), nj[grp_of].tolist(), (lo - g_off[grp_of]).tolist(), (hi - g_off[grp_of]).tolist()))
@@ -280,27 +273,17 @@ def _quad_segments(entries, order, n_feat, cus=256, phase_ns=None, shares=None):
             memo.clear()
         memo[memo_key] = (items, seg_ptr, n_seg)
         return items, seg_ptr, n_seg
+    # several column blocks: an item lies inside one job (the kernel's wave keeps that job's slices), in tape order
     items, seg_ptr = [], [0]
     for s_ in range(n_seg):
         a, b = int(cuts[s_]), int(cuts[s_ + 1])
-        seg_items = []
         while a < b:
             gi = int(np.searchsorted(g_off, a, side="right") - 1)
-            end = min(b, int(g_off[gi + 1]))
-            if multi:  # an item of a several-block table lies inside one job (the kernel's wave keeps that job's slices)
-                first_pos, nj_, _n = groups[gi]
-                jb = np.concatenate([[0], np.cumsum([entries[order[first_pos + t]][0].quad["n_su"] for t in range(nj_)])]) + int(g_off[gi])
-                end = min(end, a + QUAD_MULTI_ITEM_SU, int(jb[np.searchsorted(jb, a, side="right")]))
             first, nj, _n = groups[gi]
+            jb = np.concatenate([[0], np.cumsum([entries[order[first + t]][0].quad["n_su"] for t in range(nj)])]) + int(g_off[gi])
+            end = min(b, int(g_off[gi + 1]), a + QUAD_MULTI_ITEM_SU, int(jb[np.searchsorted(jb, a, side="right")]))
             items.append((first, nj, a - int(g_off[gi]), end - int(g_off[gi])))
-            seg_items.append((float(cum[end] - cum[a]), len(items) - 1))
             a = end
-        # the phases of a segment run shortest first: staging a slab costs 8 us while the memory system is quiet and 20 - 55 us
-        # once the launch's stores have filled the write path (scripts/dev/stamps_quad_phases.py: the later the switch, the dearer)
-        if len(seg_items) > 1 and os.environ.get("WDG_QUAD_PHASE_ORDER", "1") != "0" and not multi:
-            first_item = seg_items[0][1]
-            reordered = [items[i] for _c, i in sorted(seg_items)]
-            items[first_item:first_item + len(reordered)] = reordered
         seg_ptr.append(len(items))
     if len(memo) >= 16:
         memo.clear()

@@ -426,9 +426,6 @@ __global__ __launch_bounds__(BRES_THREADS) void mlp2_bres_kernel(const wdg_mlp2_
 // on rows spanning eight decades, 2.0e-7 against 2.7e-7 on standard normal data; scripts/dev/mlp2_split_error.py,
 // tests/test_gpu_kernels.py::test_mlp2_split_operands_are_as_accurate_as_the_fp32_chain).  Deterministic (fixed order).
 // WDG_MLP2_SPLIT=0 selects mlp2_bres_kernel, whose hidden layer is bit-identical to wdg_gemm_f32's.
-#ifndef WDG_SPLIT_ABLATE
-#define WDG_SPLIT_ABLATE 0
-#endif
 constexpr int SPLIT_KQ = 128, SPLIT_KB = SPLIT_KQ / 8;            // rows of W0 per LDS buffer, in blocks of 8: one (block, column) per thread
 constexpr int SPLIT_PIECE_WORDS = SPLIT_KB * BRES_COLS * 4;        // 32-bit words of one piece of a buffer (16 KB)
 constexpr int SPLIT_BUF_WORDS = 3 * SPLIT_PIECE_WORDS;             // a buffer: three pieces (48 KB); two buffers
@@ -582,27 +579,13 @@ __global__ __launch_bounds__(BRES_THREADS) void mlp2_split_kernel(const wdg_mlp2
                 for (int c = 0; c < 4; c += 2) {   // step 4 qu + c (+ 1): blocks 4 c .. of the buffer
                     const int base = 4 * qu + c;
                     if (base >= steps) break;
-#if WDG_SPLIT_ABLATE != 1  // (timing experiments: 1 = no A loads after the first, 2 = no products)
                     load_step(base + 1, sb);
-#else
-                    sb = sa;
-#endif
                     __builtin_amdgcn_sched_barrier(0);
-#if WDG_SPLIT_ABLATE != 2
                     split_compute<NT16>(sa, 4 * c + q, n, cur, acc);
-#else
-                    acc[0][0] += f32x4_acc{sa.a[0].x, sa.a[1].y, sa.b[0].z, sa.b[1].w};
-#endif
                     __builtin_amdgcn_sched_barrier(0);
-#if WDG_SPLIT_ABLATE != 1
                     load_step(base + 2, sa);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
-#if WDG_SPLIT_ABLATE != 2
                     if (base + 1 < steps) split_compute<NT16>(sb, 4 * c + 4 + q, n, cur, acc);
-#else
-                    acc[1][0] += f32x4_acc{sb.a[0].x, sb.a[1].y, sb.b[0].z, sb.b[1].w};
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -673,7 +656,6 @@ int bres_parts(int n_jobs, int max_M) {
         const int64_t cost = ceil_div(static_cast<int64_t>(n_jobs) * p, cus) * ceil_div(ceil_div(tiles, p), BRES_THREADS / 64);
         if (cost < best) best = cost, parts = p;
     }
-    if (const char *e = getenv("WDG_GEMM_PARTS")) parts = std::max(1, atoi(e));  // experiments
     return parts;
 }
 

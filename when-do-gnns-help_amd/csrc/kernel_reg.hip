@@ -16,15 +16,15 @@
 //   * gram_split_kernel the default since round 3 (WDG_GRAM_SPLIT=0: the two above): the same Gram with every fp32 product formed
 //                       from bf16 pieces of both operands on v_mfma_f32_32x32x16_bf16 (split_bf16.h: no input bit dropped, fp32
 //                       accumulation), gram_diag_split_kernel its diagonal by the same instruction sequence;
-//   * kr_solve_kernel   one workgroup per (graph, classifier, epoch, kernel) problem: gathers the train block K[tr, tr] from
-//                       the graph's kernel into REGISTERS (2-D cyclic over 32 x 32 threads, up to 320 x 320), factors it
-//                       (right-looking Cholesky, one LDS broadcast of the pivot column and one barrier per step), solves
-//                       for the one-hot labels, multiplies the validation rows through and counts correct arg-max
-//                       predictions.  For a symmetric positive definite block the Cholesky solution IS pinv(K) Y; when a pivot
-//                       falls to rounding level (<= n eps max K_ii / 64: a rank-deficient block, e.g. duplicate nodes) the
-//                       block is refactored once with the ridge n eps max K_ii / 8: the least-squares answer of the
-//                       pseudo-inverse to within one or two validation rows per epoch (measured against the reference's
-//                       per-epoch accuracies) - a documented deviation in the coefficients.
+//   * kr_solve_blocked_kernel
+//                       one workgroup per (graph, classifier, epoch, kernel) problem: gathers the train block K[tr, tr] from
+//                       the graph's kernel into REGISTERS (up to 320 x 320), factors it (right-looking blocked Cholesky, the
+//                       trailing update on the matrix pipe), solves for the one-hot labels, multiplies the validation rows
+//                       through and counts correct arg-max predictions.  For a symmetric positive definite block the Cholesky
+//                       solution IS pinv(K) Y; when a pivot falls to rounding level (<= n eps max K_ii / 64: a rank-deficient
+//                       block, e.g. duplicate nodes) the block is refactored once with the ridge n eps max K_ii / 8: the
+//                       least-squares answer of the pseudo-inverse to within one or two validation rows per epoch (measured
+//                       against the reference's per-epoch accuracies) - a documented deviation in the coefficients.
 #include <cstdlib>
 #include <type_traits>
 
@@ -199,9 +199,6 @@ constexpr int SG_ROW_WORDS = SGBK / 2 + 4;  // 32-bit words per LDS row: the dat
 #ifndef WDG_SGBN
 #define WDG_SGBN 64
 #endif
-#ifndef WDG_SG_ABLATE
-#define WDG_SG_ABLATE 0
-#endif
 constexpr int SGBM = 128, SGBN = WDG_SGBN, SG_NT = SGBN / 32;  // workgroup tile (a wave: 32 rows x SGBN columns).  128 x 128 tiles
                                                                 // (a third fewer row re-reads, two workgroups per CU instead of
                                                                 // three) measured 2.29 ms against 2.15 for a shard's 55 Grams
@@ -330,10 +327,7 @@ __global__ __launch_bounds__(GTHREADS) void gram_split_kernel(const wdg_gram_job
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) sg_store_quad(Bs, SG_B_WORDS, (tid + i * GTHREADS) / SG_QPR, (tid + i * GTHREADS) % SG_QPR, rb[i]);
         __syncthreads();
-#if WDG_SG_ABLATE != 1  // (timing experiments: 1 = no tile loads after the first, 2 = no products, 3 = no stores, 4 = no map)
         if (k0 + SGBK < K) load_tiles(k0 + SGBK);
-#endif
-#if WDG_SG_ABLATE != 2
 #pragma unroll
         for (int m = 0; m < SG_HALVES; ++m) {
             const u32x4_t *ap = reinterpret_cast<const u32x4_t *>(As) + (wave * 32 + li) * (SG_ROW_WORDS / 4) + 2 * m + lk;
@@ -345,7 +339,6 @@ __global__ __launch_bounds__(GTHREADS) void gram_split_kernel(const wdg_gram_job
                 acc[t] = sg_products(ah, am, al, bh, bm, bl, acc[t]);
             }
         }
-#endif
     }
     // ---- epilogue: C/D map of a 32x32 tile: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  Entries on or below the
     // diagonal are stored from the accumulators' layout (a register's 32 lanes = 128 contiguous bytes of a row); their mirrors go
@@ -371,7 +364,7 @@ __global__ __launch_bounds__(GTHREADS) void gram_split_kernel(const wdg_gram_job
                 const int gm = row0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
                 const float g = acc[t][r];
                 float kv = g * 0.5f;
-                if (which && WDG_SG_ABLATE != 4) {
+                if (which) {
                     float nu = sqrtf(norm2[gm < n ? gm : n - 1]) * dn;
                     nu = nu > 1e-8f ? nu : 1e-8f;
                     float ac = acosf(g / nu);
@@ -381,7 +374,7 @@ __global__ __launch_bounds__(GTHREADS) void gram_split_kernel(const wdg_gram_job
                     kv = (1.f / pi) * (g * (pi - ac) + sq) * 0.5f;
                 }
                 v[r] = kv;
-                if (gm < n && gn < n && gm >= gn && (WDG_SG_ABLATE != 3 || kv == 123.456f)) Kout[static_cast<int64_t>(gm) * ldk + gn] = kv;
+                if (gm < n && gn < n && gm >= gn) Kout[static_cast<int64_t>(gm) * ldk + gn] = kv;
                 T[((r & 3) + 8 * (r >> 2) + 4 * lk) * 33 + li] = kv;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -392,7 +385,7 @@ __global__ __launch_bounds__(GTHREADS) void gram_split_kernel(const wdg_gram_job
                 const int c = 2 * j + lk;  // column c of the block = row n0 + 32 t + c of the mirror, this lane its column row0 + li
                 const float kv = T[li * 33 + c];
                 const int mn = n0 + t * 32 + c, mm = row0 + li;
-                if (mm < n && mn < n && mm > mn && (WDG_SG_ABLATE != 3 || kv == 123.456f)) Kout[static_cast<int64_t>(mn) * ldk + mm] = kv;
+                if (mm < n && mn < n && mm > mn) Kout[static_cast<int64_t>(mn) * ldk + mm] = kv;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();  // (the next output overwrites the tile)
@@ -551,10 +544,10 @@ __global__ __launch_bounds__(256) void edge_gram_reduce_kernel(const wdg_edge_gr
 // utils/homophily_plot.py:286-297), a class-balanced sample of the nodes (random_disassortative_splits: per class a random
 // permutation, the first s_c members) and inside it a class-balanced train set (again per class a random permutation, the
 // first t_c); everything else of the sample validates.  Two nested uniform choices = the first t_c and the following
-// s_c - t_c members of ONE uniform random permutation of the class - which is what this kernel draws, for every (graph,
-// classifier, epoch) set of a sweep shard in one launch: key(node) = Philox4x32-10(counter = {node, set, 0, 0}, key = the
-// job's seed), the nodes sorted by (class, key, node) in LDS, roles from the rank inside the class, and an ordered compaction
-// so that the ids come out ascending like the reference's boolean masks.  Same distribution as the reference's sets, not
+// s_c - t_c members of ONE uniform random permutation of the class - which is what kr_select_kernel below draws, for every
+// (graph, classifier, epoch) set of a sweep shard in one launch: key(node) = Philox4x32-10(counter = {node, set, 0, 0}, key =
+// the job's seed), the nodes of a class ordered by (key, node), roles from the rank inside the class, and the ids written
+// ascending like the reference's boolean masks.  Same distribution as the reference's sets, not
 // the same stream (torch's CPU generator): the host routine (utils/util_funcs.kernel_regression_epoch_indices) reproduces
 // the stream and stays the path of the golden tests.  Counter-based: a set's draw depends on (seed, set index) only.
 __device__ __forceinline__ void philox_round(unsigned &c0, unsigned &c1, unsigned &c2, unsigned &c3, unsigned k0, unsigned k1) {
@@ -576,106 +569,16 @@ __device__ __forceinline__ unsigned philox4x32_10(unsigned c0, unsigned c1, unsi
     return c0;
 }
 
-constexpr int KS_THREADS = 1024, KS_MAX_CLASSES = 64;
+constexpr int KS_MAX_CLASSES = 64;
 
-__global__ __launch_bounds__(KS_THREADS) void kr_sample_kernel(const wdg_kr_sample_job *__restrict__ jobs, int n_jobs) {
-    extern __shared__ unsigned long long ks_keys[];  // [n] sort keys, then (aliased) the nodes' roles
-    __shared__ int cstart[KS_MAX_CLASSES + 1], scan_t[KS_THREADS], scan_v[KS_THREADS];
-    // which job: first_set ascending
-    int lo = 0, hi = n_jobs;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (jobs[mid].first_set <= static_cast<int>(blockIdx.x)) lo = mid;
-        else hi = mid;
-    }
-    const wdg_kr_sample_job j = jobs[lo];
-    const int set = static_cast<int>(blockIdx.x) - j.first_set;
-    if (set >= j.n_sets) return;
-    const int n = j.n, C = j.n_classes, tid = threadIdx.x;
-    const unsigned k0 = static_cast<unsigned>(j.seed), k1 = static_cast<unsigned>(j.seed >> 32);
-    for (int i = tid; i < n; i += KS_THREADS) {
-        const int c = j.labels[i];
-        const unsigned long long cls = (c >= 0 && c < C) ? static_cast<unsigned long long>(c) : 255ull;  // unlabelled: never drawn
-        ks_keys[i] = (cls << 56) | (static_cast<unsigned long long>(philox4x32_10(static_cast<unsigned>(i), static_cast<unsigned>(set), k0, k1)) << 24) |
-                     static_cast<unsigned long long>(i);
-    }
-    if (tid <= KS_MAX_CLASSES) cstart[tid] = n;
-    __syncthreads();
-    int P = 1;
-    while (P < n) P <<= 1;
-    for (int k = 2; k <= P; k <<= 1) {  // comparator network, all ascending, virtual +inf padding (any n)
-        for (int i = tid; i < n; i += KS_THREADS) {
-            const int l = i ^ (k - 1);
-            if (l > i && l < n && ks_keys[i] > ks_keys[l]) {
-                const unsigned long long t = ks_keys[i];
-                ks_keys[i] = ks_keys[l];
-                ks_keys[l] = t;
-            }
-        }
-        __syncthreads();
-        for (int jj = k >> 2; jj > 0; jj >>= 1) {
-            for (int i = tid; i < n; i += KS_THREADS) {
-                const int l = i ^ jj;
-                if (l > i && l < n && ks_keys[i] > ks_keys[l]) {
-                    const unsigned long long t = ks_keys[i];
-                    ks_keys[i] = ks_keys[l];
-                    ks_keys[l] = t;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < n; i += KS_THREADS) {  // first position of every class present
-        const int c = static_cast<int>(ks_keys[i] >> 56);
-        if (c < C && (i == 0 || static_cast<int>(ks_keys[i - 1] >> 56) != c)) cstart[c] = i;
-    }
-    __syncthreads();
-    // role of every node by its rank inside its class: 1 = train, 2 = validation, 0 = not in this epoch's sample
-    unsigned char *role = reinterpret_cast<unsigned char *>(ks_keys + n);
-    for (int i = tid; i < n; i += KS_THREADS) {
-        const unsigned long long key = ks_keys[i];
-        const int c = static_cast<int>(key >> 56), node = static_cast<int>(key & 0xffffffull);
-        unsigned char r = 0;
-        if (c < C) {
-            const int rank = i - cstart[c];
-            r = rank < j.train_per_class[c] ? 1 : (rank < j.sample_per_class[c] ? 2 : 0);
-        }
-        role[node] = r;
-    }
-    __syncthreads();
-    // ordered compaction: a thread owns a contiguous run of node ids
-    const int per = (n + KS_THREADS - 1) / KS_THREADS, a = min(n, tid * per), b = min(n, a + per);
-    int ct = 0, cv = 0;
-    for (int i = a; i < b; ++i) {
-        ct += role[i] == 1;
-        cv += role[i] == 2;
-    }
-    scan_t[tid] = ct;
-    scan_v[tid] = cv;
-    __syncthreads();
-    for (int o = 1; o < KS_THREADS; o <<= 1) {
-        const int t = tid >= o ? scan_t[tid - o] : 0, v = tid >= o ? scan_v[tid - o] : 0;
-        __syncthreads();
-        scan_t[tid] += t;
-        scan_v[tid] += v;
-        __syncthreads();
-    }
-    int pt = scan_t[tid] - ct, pv = scan_v[tid] - cv;
-    int32_t *tr = j.train_out + static_cast<int64_t>(set) * j.train_stride, *va = j.val_out + static_cast<int64_t>(set) * j.val_stride;
-    for (int i = a; i < b; ++i) {
-        if (role[i] == 1 && pt < j.train_stride) tr[pt++] = i;
-        if (role[i] == 2 && pv < j.val_stride) va[pv++] = i;
-    }
-}
-
-// Round 5: the same sets WITHOUT sorting.  The definition above needs, per node, only whether its rank inside its class is below
+// The sets WITHOUT sorting (round 5).  The definition above needs, per node, only whether its rank inside its class is below
 // t_c (train), below s_c (validation) or neither.  kr_select_kernel finds that by a radix SELECT: a histogram of the keys' top bits
 // per class (NB bins), a prefix over the bins to find the two bins in which the ranks t_c and s_c fall, and an exact rank only for
 // the few nodes of those two boundary bins (counted against the other members of the same class and bin, by a wave per such
 // node) - every other node is classified by its bin alone.  256 threads and ~25 KB of LDS per set instead of a 1024-thread
 // comparator network over 64-bit keys with ~90 barriers: several workgroups share a CU, so the launch also runs well BESIDE the
-// Gram kernels it is queued next to (the sort held whole CUs).  Bit for bit the sets of kr_sample_kernel (WDG_KR_SAMPLER_SORT=1
-// keeps that kernel; tests/test_gpu_batched_build.py compares the device's sets with a numpy restatement of the definition).
+// Gram kernels it is queued next to (a sort held whole CUs).  tests/test_gpu_batched_build.py compares the device's sets with a
+// numpy restatement of the definition.
 constexpr int KSEL_THREADS = 256, KSEL_WAVES = KSEL_THREADS / 64, KSEL_LIST = 1024;
 __device__ __forceinline__ unsigned long long ksel_composite(unsigned cls, unsigned key, int node) {
     return (static_cast<unsigned long long>(cls) << 56) | (static_cast<unsigned long long>(key) << 24) | static_cast<unsigned long long>(node);
@@ -820,256 +723,10 @@ __global__ __launch_bounds__(KSEL_THREADS) void kr_select_kernel(const wdg_kr_sa
 
 
 // ------------------------------------------------------------------------------------------------ batched kernel regression
-constexpr int KR_THREADS = 1024, KR_T = 32, KR_B = 10;  // 32 x 32 threads, 10 x 10 elements each: blocks of up to 320 x 320
-constexpr int KR_MAX_N = KR_T * KR_B, KR_MAX_C = 8;
-constexpr int KR_COL_LD = 12;  // a thread's 10 column values, padded to three ds_read_b128
-
-__global__ __launch_bounds__(KR_THREADS) void kr_solve_kernel(const wdg_kr_job *__restrict__ jobs) {
-    __shared__ float colbuf[2][KR_T * KR_COL_LD];     // the pivot column of a step, [i % 32][i / 32] (double-buffered)
-    __shared__ float rhs[KR_MAX_N * KR_MAX_C];        // one-hot labels, reduced step by step; later alpha, [i][c]
-    __shared__ float ysol[KR_MAX_N * KR_MAX_C];       // y = L^-1 B, written as the factorisation goes
-    __shared__ float dblk[KR_T * (KR_T + 1)];         // a diagonal block of L for the blocked back substitution
-    __shared__ int tr_idx[KR_MAX_N];
-    __shared__ int deficient;                         // a pivot fell to rounding level: redo on K + lambda I
-    __shared__ float part[4][256][KR_MAX_C];          // partial predictions of the validation rows
-    __shared__ float bcast[KR_MAX_C + 2];
-    __shared__ int correct;
-
-    const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)(jobs + blockIdx.x);
-    const global_ptr<const float> K = to_global(job->K);
-    const global_ptr<const int32_t> train = to_global(job->train), val = to_global(job->val), labels = to_global(job->labels);
-    const int64_t ldk = job->ldk;
-    const int nt = job->n_train, nv = job->n_val, C = job->n_classes;
-    const int tid = threadIdx.x, tc = tid & 31, trw = tid >> 5;
-    if (nt <= 0 || nt > KR_MAX_N || C <= 0 || C > KR_MAX_C) {
-        if (tid == 0 && job->correct_out) *to_global(job->correct_out) = -1;
-        if (tid == 0 && job->flags_out) *to_global(job->flags_out) = 0;
-        return;
-    }
-    for (int i = tid; i < KR_MAX_N; i += KR_THREADS) tr_idx[i] = i < nt ? train[i] : -1;
-    if (tid == 0) correct = 0;
-    __syncthreads();
-
-    // ---- gather the train block's LOWER block triangle: thread (trw, tc) holds element (trw, tc) of every 32 x 32 block
-    //      (A, B) with A >= B - 55 registers (the strictly upper parts of the diagonal blocks ride along unused); element
-    //      (i, j) = (trw + 32 A, tc + 32 B); rows / columns beyond n_train: identity
-    constexpr int KR_TRI = KR_B * (KR_B + 1) / 2;
-    float m[KR_TRI];
-#define KR_M(A, B) m[(A) * ((A) + 1) / 2 + (B)]
-    float ridge = 0.f;  // second attempt only (below)
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    for (int i = tid; i < KR_MAX_N * KR_MAX_C; i += KR_THREADS) {  // (the forward substitution below consumes it: per attempt)
-        const int row = i / KR_MAX_C, c = i % KR_MAX_C;
-        rhs[i] = (row < nt && labels[tr_idx[row]] == c) ? 1.f : 0.f;
-        ysol[i] = 0.f;
-    }
-    float dmax = 0.f;
-#pragma unroll
-    for (int a = 0; a < KR_B; ++a) {
-        const int i = trw + KR_T * a;
-        const int gi = tr_idx[i];
-#pragma unroll
-        for (int b = 0; b <= a; ++b) {
-            const int j = tc + KR_T * b;
-            const int gj = tr_idx[j];
-            KR_M(a, b) = (gi >= 0 && gj >= 0) ? K[static_cast<int64_t>(gi) * ldk + gj] : (i == j ? 1.f : 0.f);
-            if (i == j && gi >= 0) {
-                dmax = fmaxf(dmax, KR_M(a, b));
-                KR_M(a, b) += ridge;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);  // one block row's gathers (and their addresses) in flight at a time
-    }
-    for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
-    if ((tid & 63) == 0) part[0][tid >> 6][0] = dmax;
-    __syncthreads();
-    if (tid == 0) {
-        float d = 0.f;
-        for (int w = 0; w < KR_THREADS / 64; ++w) d = fmaxf(d, part[0][w][0]);
-        bcast[KR_MAX_C] = d;
-    }
-    __syncthreads();
-    // A pivot at rounding level means the block is not positive definite in fp32 (the row is a combination of earlier ones:
-    // duplicate nodes, a rank-deficient kernel).  The reference's pinv (numpy default rcond 1e-15: every singular value of an
-    // fp32 block is kept) answers such a system with the least-squares solution plus whatever its rounding-level singular
-    // values contribute; the ridge system (K + lambda I) alpha = Y approaches the least-squares part as lambda -> 0 (for a PSD
-    // kernel the validation rows annihilate the null space of the train block).  Measured against the reference's per-epoch
-    // accuracies (tests/golden/kr_epochs.npz, an fp32 emulation of this factorisation): lambda = n eps max K_ii / 8 with
-    // pivots tested against n eps max K_ii / 64 is within one validation row on the synthetic sweep graphs and within two
-    // (one epoch: four) on texas / cora; round 2's 8 n eps max K_ii was 3 - 22 rows off on the rank-deficient real kernels.
-    // The factorisation is redone ONCE on K + lambda I, pivots clamped to the test level.
-    const float drop_below = static_cast<float>(nt) * 1.1920929e-7f * bcast[KR_MAX_C] * (1.f / 64.f);
-    if (tid == 0) deficient = 0;
-    __syncthreads();
-
-    // ---- right-looking Cholesky: step k = 32 kb + kk; the owners of column k (tc == kk, their register column kb) publish
-    //      it, everyone reads the pivot, its 10 row values and its 10 column values, scales, and updates its 10 x 10 block
-    //      with the vectors masked to i > k / j > k (the finished columns of L stay untouched)
-    // (the block index of the pivot is a compile-time constant of each copy of the step - the register block is indexed
-    // statically or it would live in scratch)
-    auto chol_block = [&](auto kb_const) {
-        constexpr int kb = decltype(kb_const)::value;
-        if (kb * KR_T >= nt) return;  // (uniform; the identity padding needs no work)
-        for (int kk = 0; kk < KR_T; ++kk) {
-            const int k = kb * KR_T + kk;
-            float *cb = colbuf[k & 1];
-            if (tc == kk) {
-#pragma unroll
-                for (int a = 0; a < KR_B; ++a) cb[trw * KR_COL_LD + a] = a >= kb ? KR_M(a >= kb ? a : kb, kb) : 0.f;
-            }
-            __syncthreads();
-            float piv = cb[kk * KR_COL_LD + kb];
-            const bool low = !(piv > drop_below) && k < nt;  // (also catches NaN)
-            if (low && tid == 0) deficient = 1;
-            piv = low ? fmaxf(ridge, drop_below) : piv;
-            const float inv = 1.f / sqrtf(piv);
-            float lj[KR_B];
-#pragma unroll
-            for (int b = 0; b < KR_B; ++b) lj[b] = (tc + KR_T * b) > k ? cb[tc * KR_COL_LD + b] * inv : 0.f;
-#pragma unroll
-            for (int a = 0; a < KR_B; ++a) {
-                if (a < kb) continue;  // (static after unrolling: rows above the pivot's block are finished)
-                const float li = (trw + KR_T * a) > k ? cb[trw * KR_COL_LD + a] * inv : 0.f;
-#pragma unroll
-                for (int b = 0; b <= a; ++b)
-                    if (b >= kb) KR_M(a, b) = fmaf(-li, lj[b], KR_M(a, b));
-                if (tc == kk) {  // column k of L: l_kk = sqrt(pivot), l_ik below it
-                    const int i = trw + KR_T * a;
-                    KR_M(a, kb) = i > k ? li : (i == k ? piv * inv : KR_M(a, kb));
-                }
-            }
-            // the forward substitution L y = B rides along (column form): y_k = b_k / l_kk, b_i -= l_ik y_k for i > k.  Row k
-            // of B is final here (its last update was published by this step's barrier); eight threads per row.
-            if (k < nt) {
-                const int c = tid & (KR_MAX_C - 1);
-                const float yk = rhs[k * KR_MAX_C + c] * inv;  // (1 / l_kk = 1 / sqrt(pivot))
-                if (tid < KR_MAX_C) ysol[k * KR_MAX_C + c] = yk;
-                for (int i = k + 1 + (tid >> 3); i < nt; i += KR_THREADS / KR_MAX_C) {
-                    const float lik = cb[(i & (KR_T - 1)) * KR_COL_LD + (i >> 5)] * inv;
-                    rhs[i * KR_MAX_C + c] = fmaf(-lik, yk, rhs[i * KR_MAX_C + c]);
-                }
-            }
-        }
-    };
-#define KR_EACH_BLOCK(F)                                                                                               \
-    F(std::integral_constant<int, 0>{}); F(std::integral_constant<int, 1>{}); F(std::integral_constant<int, 2>{});     \
-    F(std::integral_constant<int, 3>{}); F(std::integral_constant<int, 4>{}); F(std::integral_constant<int, 5>{});     \
-    F(std::integral_constant<int, 6>{}); F(std::integral_constant<int, 7>{}); F(std::integral_constant<int, 8>{});     \
-    F(std::integral_constant<int, 9>{});
-#define KR_EACH_BLOCK_DOWN(F)                                                                                          \
-    F(std::integral_constant<int, 9>{}); F(std::integral_constant<int, 8>{}); F(std::integral_constant<int, 7>{});     \
-    F(std::integral_constant<int, 6>{}); F(std::integral_constant<int, 5>{}); F(std::integral_constant<int, 4>{});     \
-    F(std::integral_constant<int, 3>{}); F(std::integral_constant<int, 2>{}); F(std::integral_constant<int, 1>{});     \
-    F(std::integral_constant<int, 0>{});
-    static_assert(KR_B == 10, "KR_EACH_BLOCK lists the ten blocks");
-    KR_EACH_BLOCK(chol_block)
-    __syncthreads();
-    if (!deficient || attempt == 1) break;  // (uniform)
-    ridge = 8.f * drop_below;  // = n eps max K_ii / 8
-    __syncthreads();
-    }  // attempt
-
-    // ---- back substitution L^T alpha = y, one 32-column block at a time (30 barriers instead of two per column):
-    //      z = y_kb - sum over the blocks A > kb of L[A, kb]^T alpha_A (every thread multiplies the <= 9 elements it holds,
-    //      the 32 threads of a column are summed through LDS in a fixed order), then wave 0 solves the 32 x 32 triangle
-    //      L[kb, kb]^T alpha_kb = z by itself (lane = column, the two half-waves take four right-hand sides each).
-    float(*const zpart)[KR_T][KR_MAX_C] = reinterpret_cast<float(*)[KR_T][KR_MAX_C]>(&part[0][0][0]);  // [16 waves][32][8]
-    const int n_blocks = (nt + KR_T - 1) / KR_T;
-    auto bwd_block = [&](auto kb_const) {
-        constexpr int kb = decltype(kb_const)::value;
-        if (kb >= n_blocks) return;  // (uniform)
-        float z[KR_MAX_C];
-#pragma unroll
-        for (int c = 0; c < KR_MAX_C; ++c) z[c] = 0.f;
-#pragma unroll
-        for (int a = kb + 1; a < KR_B; ++a) {
-            if (a >= n_blocks) continue;
-            const float l = KR_M(a, kb);
-            const float *al = rhs + (trw + KR_T * a) * KR_MAX_C;  // alpha of the blocks below: already solved
-#pragma unroll
-            for (int c = 0; c < KR_MAX_C; ++c) z[c] = fmaf(l, al[c], z[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < KR_MAX_C; ++c) z[c] += __shfl_xor(z[c], 32);  // the wave's two rows
-        if ((tid & 32) == 0) {
-#pragma unroll
-            for (int c = 0; c < KR_MAX_C; ++c) zpart[tid >> 6][tc][c] = z[c];
-        }
-        dblk[trw * (KR_T + 1) + tc] = KR_M(kb, kb);
-        __syncthreads();
-        if (tid < KR_T * KR_MAX_C) {  // 256 threads: (column j, right-hand side c)
-            const int j = tid >> 3, c = tid & 7;
-            float sum = zpart[0][j][c];
-#pragma unroll
-            for (int w = 1; w < KR_THREADS / 64; ++w) sum += zpart[w][j][c];
-            ysol[(kb * KR_T + j) * KR_MAX_C + c] -= sum;
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const int j = tid & 31, c0 = (tid >> 5) * 4;
-            float zz[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) zz[c] = ysol[(kb * KR_T + j) * KR_MAX_C + c0 + c];
-            for (int k = KR_T - 1; k >= 0; --k) {
-                const float dinv = 1.f / dblk[k * (KR_T + 1) + k];
-                const float lkj = j < k ? dblk[k * (KR_T + 1) + j] : 0.f;  // row k of L = column k of L^T
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float ak = __shfl(zz[c], (tid & 32) + k) * dinv;
-                    if (j == k) zz[c] = ak;
-                    zz[c] = fmaf(-lkj, ak, zz[c]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) rhs[(kb * KR_T + j) * KR_MAX_C + c0 + c] = (kb * KR_T + j) < nt ? zz[c] : 0.f;
-        }
-        __syncthreads();
-    };
-    KR_EACH_BLOCK_DOWN(bwd_block)
-
-    // ---- predictions of the validation rows: p_v = sum_t K[val_v, train_t] alpha_t, arg-max, count the hits
-    for (int v0 = 0; v0 < nv; v0 += 256) {
-        const int v = v0 + (tid & 255), q = tid >> 8;  // four threads per validation row, a quarter of the train rows each
-        float p[KR_MAX_C];
-#pragma unroll
-        for (int c = 0; c < KR_MAX_C; ++c) p[c] = 0.f;
-        if (v < nv) {
-            const global_ptr<const float> krow = K + static_cast<int64_t>(val[v]) * ldk;
-            const int per = (nt + 3) / 4, t0 = q * per, t1 = min(nt, t0 + per);
-            for (int t = t0; t < t1; ++t) {
-                const float kv = krow[tr_idx[t]];
-#pragma unroll
-                for (int c = 0; c < KR_MAX_C; ++c) p[c] = fmaf(kv, rhs[t * KR_MAX_C + c], p[c]);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < KR_MAX_C; ++c) part[q][tid & 255][c] = p[c];
-        __syncthreads();
-        if (q == 0 && v < nv) {
-            int best = 0;
-            float bv = -3.4e38f;
-            for (int c = 0; c < C; ++c) {
-                const float s = ((part[0][tid][c] + part[1][tid][c]) + part[2][tid][c]) + part[3][tid][c];
-                if (s > bv) {  // first maximum, like torch.argmax
-                    bv = s;
-                    best = c;
-                }
-            }
-            if (best == labels[val[v]]) atomicAdd(&correct, 1);
-        }
-        __syncthreads();
-    }
-    if (tid == 0 && job->correct_out) *to_global(job->correct_out) = correct;
-    if (tid == 0 && job->flags_out) *to_global(job->flags_out) = ridge > 0.f ? 1 : 0;
-}
-
-
-// ------------------------------------------------------------------------------------------------ blocked solver (round 3)
-// The same problem as kr_solve_kernel - one workgroup of 16 waves per (kernel, train rows, validation rows) regression - as a
-// right-looking BLOCKED Cholesky with 32 x 32 blocks: the trailing update, > 90 % of the flops, runs on the fp32 matrix pipe
-// (v_mfma_f32_32x32x2_f32: an exact fp32 fma chain, fixed order -> bitwise reproducible), every solve against a diagonal block is
-// a product with that block's inverse, and a regression takes ~60 workgroup barriers instead of ~330 (kr_solve_kernel: one per
-// eliminated column).
+// One workgroup of 16 waves per (kernel, train rows, validation rows) regression, a right-looking BLOCKED Cholesky with 32 x 32
+// blocks: the trailing update, > 90 % of the flops, runs on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32: an exact fp32 fma chain,
+// fixed order -> bitwise reproducible), every solve against a diagonal block is a product with that block's inverse, and a
+// regression takes ~60 workgroup barriers instead of the ~330 of an unblocked factorisation (one per eliminated column).
 //
 //   layout   block (a, b), b <= a, of the train block lives in ONE wave's registers, TRANSPOSED in the MFMA accumulator layout:
 //            lane (i, h) = (lane & 31, lane >> 5) holds A[32 a + i][32 b + j] for the 16 columns j = jmap(h, r) = (r & 3) +
@@ -1092,8 +749,17 @@ __global__ __launch_bounds__(KR_THREADS) void kr_solve_kernel(const wdg_kr_job *
 //   then     back substitution block column by block column (the column's blocks go through LDS once more: the product with
 //            L^T sums over the lane index; alpha_kb = M^T v is a 32-term dot product per lane), predictions one wave per four
 //            validation rows.
-// Rank-deficient blocks: as in kr_solve_kernel (pivot test at n eps max K_ii / 64, one restart on K + n eps max K_ii / 8 I).
+// Rank-deficient blocks: a pivot at rounding level means the block is not positive definite in fp32 (the row is a combination
+// of earlier ones: duplicate nodes, a rank-deficient kernel).  The reference's pinv (numpy default rcond 1e-15: every singular
+// value of an fp32 block is kept) answers such a system with the least-squares solution plus whatever its rounding-level singular
+// values contribute; the ridge system (K + lambda I) alpha = Y approaches the least-squares part as lambda -> 0 (for a PSD kernel
+// the validation rows annihilate the null space of the train block).  Measured against the reference's per-epoch accuracies
+// (tests/golden/kr_epochs.npz, an fp32 emulation of the factorisation): lambda = n eps max K_ii / 8 with pivots tested against
+// n eps max K_ii / 64 is within one validation row on the synthetic sweep graphs and within two (one epoch: four) on texas / cora;
+// round 2's 8 n eps max K_ii was 3 - 22 rows off on the rank-deficient real kernels.  The factorisation is redone ONCE on
+// K + lambda I, pivots clamped to the test level.
 constexpr int K2_THREADS = 1024, K2_WAVES = 16, K2_NB = 10, K2_SLOTS = 3, K2_PS = 36;
+constexpr int KR_MAX_N = K2_NB * 32, KR_MAX_C = 8;  // train rows (320) and classes of a problem
 // the deflation workspace of a problem (wdg_kr_job.ws, filled by kr_deflate_kernel, read by the solver), as int32 words:
 //   [KRW_NT] rows to solve, [KRW_DEFLATED] != 0 when fewer than n_train, [KRW_TRAIN ..] their representatives (padded with -1),
 //   [KRW_VAL ..] n_val validation representatives, then n_val labels
@@ -1391,9 +1057,6 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
         const int64_t pldk = pj->ldk;
         const int pnt = pend_nt;
         const int g = lane >> 4, gl = lane & 15;
-#ifdef WDG_KR_ABLATION
-        if (pj->reserved & 8) return;
-#endif
         for (int u = 0; u < max_units; ++u) {
             int unit = 0;
             if (lane == 0) unit = atomicAdd(&pend_next, 1);
@@ -1478,11 +1141,6 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
     const int nt = !has_ws ? nt_in : (ws_ok ? ws[KRW_NT] : -1);
     const bool deflated = has_ws && ws_ok && ws[KRW_DEFLATED] != 0;
     const int n_mixed = (has_ws && ws_ok) ? ws[KRW_MIXED] : 0;  // (uniform) listed right-hand-side entries (duplicates with different labels)
-#ifdef WDG_KR_ABLATION  // diagnostic build only (make EXTRA=-DWDG_KR_ABLATION; scripts/dev/time_kr_batch.py): timing-only ablations
-    const int ablate = job->reserved;  // 1 no gather, 2 no factorisation, 4 no back substitution, 8 no predictions (results are wrong)
-#else
-    constexpr int ablate = 0;  // (the shipped kernel ignores the descriptor's reserved word: a stray value cannot change a result)
-#endif
     // (ldk: the deferred predictions address K by 32-bit element offsets row x ldk + column, rows and columns < ldk - a wider kernel
     // matrix is refused HERE as well as by the Python launcher, so that a C-ABI caller gets correct_out = -1, not wrong hit counts)
     if (nt_in <= 0 || nt_in > K2_NB * 32 || nt < 0 || nt > nt_in || C <= 0 || C > KR_MAX_C || ldk <= 0 || ldk >= 65536) {  // (uniform)
@@ -1560,7 +1218,7 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
             for (int r = 0; r < 16; ++r) {
                 const int j = k2_jmap(h, r), gj = tr_idx[32 * b + j];
                 const bool diag = a == b && li == j;
-                float v = (gi >= 0 && gj >= 0 && !(ablate & 1)) ? K[static_cast<int64_t>(gj) * ldk + gi] : (diag ? 1.f : 0.f);
+                float v = (gi >= 0 && gj >= 0) ? K[static_cast<int64_t>(gj) * ldk + gi] : (diag ? 1.f : 0.f);
                 if (has_ws) v *= sc[32 * a + li] * sc[32 * b + j];  // (1 for rows without duplicates: exact)
                 if (diag && gi >= 0) v += ridge;
                 t[r] = v;
@@ -1589,7 +1247,7 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
         K2_T(1);  // right-hand sides + gather
 
         // ---- the factorisation
-        for (int kb = 0; kb < ((ablate & 2) ? 0 : nb); ++kb) {
+        for (int kb = 0; kb < nb; ++kb) {
             // (lane coordinates made opaque per iteration: otherwise the compiler hoists every LDS address of the loop body -
             // dozens of loop-invariant lane-dependent offsets - out of the loop, spills them next to the 64 accumulator registers
             // and reloads each one from scratch memory, a global-memory round trip, in front of the LDS access that needs it)
@@ -1769,7 +1427,7 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
     if (nt == 0 && tid < KR_MAX_C) al[tid] = 0.f;  // (every train row dropped: no back substitution writes alpha; the predictions' masked reads hit row 0)
     K2_T(14);
     // ---- back substitution L^T alpha = z, block column by block column from the last (L_kk: still in LD)
-    for (int kb = (ablate & 4) ? -1 : nb - 1; kb >= 0; --kb) {
+    for (int kb = nb - 1; kb >= 0; --kb) {
         int li = li_, h = h_;  // (opaque per iteration: see the factorisation loop)
         asm volatile("" : "+v"(li), "+v"(h));
 #pragma unroll
@@ -1932,11 +1590,6 @@ int kernel_regress_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, bool defla
     WDG_REQUIRE(n_jobs >= 0, "kernel_regress_batched: negative size");
     if (n_jobs == 0) return WDG_OK;
     WDG_REQUIRE(jobs_dev != nullptr, "kernel_regress_batched: null job table");
-    // WDG_KR_KERNEL=rank1: round 2's solver (one barrier per eliminated column); default: the blocked solver on the matrix pipe
-    static const bool rank1 = [] {
-        const char *e = getenv("WDG_KR_KERNEL");
-        return e && e[0] == 'r';
-    }();
     // the blocked solver is persistent: one workgroup per CU (its 144 KB of LDS allow no second one) walks the problems and makes a
     // problem's predictions inside the next one's factorisation; WDG_KR_PERSIST=0: one workgroup per problem (round 3's schedule)
     static const bool persist = [] {
@@ -1949,14 +1602,13 @@ int kernel_regress_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, bool defla
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         cus = n, cus_dev = dev;
     }
-    if (rank1 && !deflated) hipLaunchKernelGGL(kr_solve_kernel, dim3(n_jobs), dim3(KR_THREADS), 0, wdg::as_stream(stream), jobs_dev);
-    else if (deflated) {
+    if (deflated) {
         hipLaunchKernelGGL(kr_deflate_kernel, dim3(static_cast<unsigned>(n_jobs)), dim3(KD_THREADS), 0, wdg::as_stream(stream), jobs_dev);
         hipLaunchKernelGGL(kr_solve_blocked_kernel<true>, dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
                            wdg::as_stream(stream), jobs_dev, n_jobs);
     } else hipLaunchKernelGGL(kr_solve_blocked_kernel<false>, dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
                               wdg::as_stream(stream), jobs_dev, n_jobs);
-    return wdg::check_launch("kr_solve_kernel");
+    return wdg::check_launch("kr_solve_blocked_kernel");
 }
 
 }  // namespace
@@ -1983,34 +1635,17 @@ int wdg_kr_sample_sets(const wdg_kr_sample_job *jobs_dev, int32_t n_jobs, int32_
     WDG_REQUIRE(jobs_dev != nullptr, "kr_sample_sets: null job table");
     WDG_REQUIRE(max_n <= 16000, "kr_sample_sets: graphs of more than 16 000 nodes draw their node sets on the host");
     hipStream_t st = wdg::as_stream(stream);
-    // WDG_KR_SAMPLER_SORT=1: round 3's kernel (a 1024-thread comparator network per set); default: the radix select, same sets
-    static const bool sort_kernel = [] {
-        const char *e = getenv("WDG_KR_SAMPLER_SORT");
-        return e && atoi(e) != 0;
-    }();
-    if (!sort_kernel) {
-        const int max_n_pad = (max_n + 63) & ~63;
-        const size_t lds_sel = static_cast<size_t>(max_n_pad) * 6 + (KSEL_HIST + KSEL_LIST) * sizeof(unsigned);
-        static thread_local int sel_dev = -1;
-        if (sel_dev != wdg::current_device()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kr_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    16000 * 6 + (KSEL_HIST + KSEL_LIST) * 4 + 512) != hipSuccess)
-                return wdg::fail(WDG_ERR_LAUNCH, "kr_sample_sets: cannot raise the dynamic LDS limit");
-            sel_dev = wdg::current_device();
-        }
-        hipLaunchKernelGGL(kr_select_kernel, dim3(static_cast<unsigned>(n_sets_total)), dim3(KSEL_THREADS), lds_sel, st, jobs_dev, n_jobs, max_n_pad);
-        return wdg::check_launch("kr_select_kernel");
-    }
-    const size_t lds = static_cast<size_t>(max_n) * 8 + ((static_cast<size_t>(max_n) + 15) & ~static_cast<size_t>(15));
-    static thread_local int configured_dev = -1;
-    if (configured_dev != wdg::current_device()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kr_sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                16000 * 9 + 16) != hipSuccess)
+    const int max_n_pad = (max_n + 63) & ~63;
+    const size_t lds_sel = static_cast<size_t>(max_n_pad) * 6 + (KSEL_HIST + KSEL_LIST) * sizeof(unsigned);
+    static thread_local int sel_dev = -1;
+    if (sel_dev != wdg::current_device()) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kr_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                16000 * 6 + (KSEL_HIST + KSEL_LIST) * 4 + 512) != hipSuccess)
             return wdg::fail(WDG_ERR_LAUNCH, "kr_sample_sets: cannot raise the dynamic LDS limit");
-        configured_dev = wdg::current_device();
+        sel_dev = wdg::current_device();
     }
-    hipLaunchKernelGGL(kr_sample_kernel, dim3(static_cast<unsigned>(n_sets_total)), dim3(KS_THREADS), lds, st, jobs_dev, n_jobs);
-    return wdg::check_launch("kr_sample_kernel");
+    hipLaunchKernelGGL(kr_select_kernel, dim3(static_cast<unsigned>(n_sets_total)), dim3(KSEL_THREADS), lds_sel, st, jobs_dev, n_jobs, max_n_pad);
+    return wdg::check_launch("kr_select_kernel");
 }
 
 size_t wdg_edge_gram_workspace_bytes(int32_t n_jobs, int32_t max_rows) {

@@ -36,8 +36,7 @@ constexpr int B_WAVES = B_THREADS / kWave;
 constexpr int B_NB = WDG_BAND_NB;  // source rows per batch; two batches are requested before the first is consumed
 constexpr int B_TEAM = 4;        // waves that sweep a hub row together
 constexpr int B_TEAMS = B_WAVES / B_TEAM;
-constexpr int B_HUB_LEN = 256;   // rows longer than this are hub rows (wdg_csr_band_plan's default; wdg_csr_band_plan_hub names it,
-                                 // WDG_BAND_HUB overrides both: experiments)
+constexpr int B_HUB_LEN = 256;   // rows longer than this are hub rows (wdg_csr_band_plan's default; wdg_csr_band_plan_hub names it)
 constexpr int B_ROW_COST = 8;    // fixed cost of a (row, band) item in entries (descriptor loads, the store)
 constexpr int B_BUCKETS = 4096;  // length buckets of the large-graph row sort
 
@@ -430,8 +429,6 @@ int band_launch(const wdg_spmm_job &j, int n_bands, int wgs_per_xcd, hipStream_t
 namespace wdg {
 
 bool band_eligible_single(const wdg_spmm_job &j) {
-    if (const char *s = getenv("WDG_SPMM_NO_BAND"))
-        if (atoi(s)) return false;
     if (!j.band_perm || !j.band_cuts || j.band_n_hub < WDG_BAND_HUB_ON_DEVICE || j.band_n_hub > j.n_rows) return false;
     if (j.n_feat < 16 || j.n_cols < 1 || !j.col) return false;
     // item indices (band x row) and byte offsets inside an X row are 32-bit
@@ -440,10 +437,6 @@ bool band_eligible_single(const wdg_spmm_job &j) {
 }
 
 int band_vec_for(int n_cols, int n_feat) {
-    if (const char *s = getenv("WDG_BAND_VEC")) {
-        const int v = atoi(s);
-        if ((v == 1 || v == 2 || v == 4) && n_feat >= v) return v;
-    }
     // 16 bytes per lane wherever the features allow it: measured on squirrel / chameleon / Cora, the bytes a wave moves per
     // instruction matter, the L2 footprint of a band (n_cols x 256 VEC bytes) does not
     int vec = 4;
@@ -455,8 +448,7 @@ int band_vec_for(int n_cols, int n_feat) {
 int band_single_f32(const wdg_spmm_job &j, hipStream_t st) {
     const int vec = band_vec_for(j.n_cols, j.n_feat);
     const int n_bands = static_cast<int>(ceil_div(j.n_feat, kWave * vec));
-    int per_cu = 2048 / B_THREADS;  // (as many as fit: the kernels use <= 64 vector registers where it matters)
-    if (const char *s = getenv("WDG_BAND_WGS")) per_cu = std::max(1, std::min(2048 / B_THREADS, atoi(s)));
+    const int per_cu = 2048 / B_THREADS;  // (as many as fit: the kernels use <= 64 vector registers where it matters)
     const int wgs_per_xcd = std::max(wdg_device_cus(), 8) / kXcds * per_cu;
     if (vec == 4) return band_launch<4>(j, n_bands, wgs_per_xcd, st);
     if (vec == 2) return band_launch<2>(j, n_bands, wgs_per_xcd, st);
@@ -497,9 +489,7 @@ int wdg_csr_band_plan_hub(const int32_t *rowptr, int32_t N, int32_t hub_len_arg,
         if (int e = wdg::exclusive_scan_i32(hist, B_BUCKETS, cursor, nullptr, scan_ws, st)) return e;
         hipLaunchKernelGGL(band_scatter, dim3(wdg::ceil_div(N, B_SORT_THREADS * B_SORT_ROWS)), dim3(B_SORT_THREADS), 0, st, rowptr, N, cursor, band_perm);
     }
-    int hub_len = hub_len_arg > 0 ? std::max(8, static_cast<int>(hub_len_arg)) : B_HUB_LEN;
-    if (const char *h = getenv("WDG_BAND_HUB"))
-        if (atoi(h) > 0) hub_len = std::max(8, atoi(h));
+    const int hub_len = hub_len_arg > 0 ? std::max(8, static_cast<int>(hub_len_arg)) : B_HUB_LEN;
     const int n_wgs = std::max(1, std::min(CUT_MAX_WGS, static_cast<int>(wdg::ceil_div(N, CUT_THREADS))));
     CutPartial *partials = reinterpret_cast<CutPartial *>(hist);     // (the bucket sort is done with both arrays by now)
     CutTargets *targets = reinterpret_cast<CutTargets *>(cursor);

@@ -294,9 +294,6 @@ constexpr int64_t N_PART_BYTES = 3 << 20;  // 3 MiB of packed sources per part: 
 extern "C" {
 
 int32_t wdg_spmm_narrow_col_bytes(int32_t n_feat, int32_t x_is_bf16, int32_t has_col_scale) {
-    if (const char *s = getenv("WDG_NARROW_TABLE32")) {  // experiments / tests: always the 32-byte fp32 table
-        if (atoi(s) != 0) return 32;
-    }
     return (n_feat <= 4 || (x_is_bf16 && !has_col_scale)) ? 16 : 32;
 }
 
@@ -362,8 +359,7 @@ static int narrow_launch(const wdg_spmm_job *j, bool bf16, const int32_t *part_p
             hipLaunchKernelGGL(narrow_pack<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float *>(j->X), j->ldx, j->col_scale, j->n_cols, j->n_feat, T);
     }
     const int cus = std::max(wdg_device_cus(), 8);
-    int per_cu = 8;
-    if (const char *s = getenv("WDG_NARROW_WGS")) per_cu = std::max(1, std::min(8, atoi(s)));
+    const int per_cu = 8;
     const dim3 grid(static_cast<unsigned>(cus / kXcds * kXcds * per_cu));
 #define WDG_NARROW_LAUNCH(V, TB) hipLaunchKernelGGL((spmm_narrow_kernel<V, TB>), grid, dim3(N_THREADS), 0, st, *j, T, part_ptr, parts, P)
     if (j->val) {

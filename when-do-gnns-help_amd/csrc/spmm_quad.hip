@@ -1035,13 +1035,9 @@ __device__ __forceinline__ void q_accw(f32x2 &a0, f32x2 &a1, const f32x4_t &v, f
 }
 __device__ __forceinline__ void q_accw(f32x2 &a0, f32x2 &, const f32x2 &v, float wv) { a0 = __builtin_elementwise_fma(f32x2{wv, wv}, v, a0); }
 #define WDG_Q_READ(J, R, V) const QV V = *(const QV __attribute__((address_space(3))) *)(slab + (q_bcast<J>(cc[R]) + loff));
-#ifndef WDG_Q_ABLATE_ADDS
 #define WDG_Q_ADD(J, R, V)                                \
     if (HAS_VAL) q_accw(a0, a1, V, q_bcastf<J>(wc[R]));   \
     else q_acc(a0, a1, V);
-#else  // (diagnostic build, scripts/dev/build_quad_variants.sh: the reads stay, their packed adds go - what the VALU costs the sweep)
-#define WDG_Q_ADD(J, R, V) asm volatile("" ::"v"(V));
-#endif
 #define WDG_Q_READ4(J, P) WDG_Q_READ(J, 0, P##0) WDG_Q_READ(J, 1, P##1) WDG_Q_READ(J, 2, P##2) WDG_Q_READ(J, 3, P##3)
 #define WDG_Q_ADD4(J, P) WDG_Q_ADD(J, 0, P##0) WDG_Q_ADD(J, 1, P##1) WDG_Q_ADD(J, 2, P##2) WDG_Q_ADD(J, 3, P##3)
 // one quad of entries, on its own (partial chunks)
@@ -1116,20 +1112,7 @@ __device__ __forceinline__ int q_ld1(global_ptr<const int32_t> base, unsigned vo
 __device__ __forceinline__ void q_st4(global_ptr<float> base, unsigned voff, f32x4_t v) {
     // (s_nop: a VALU write of the data registers right behind a store of more than 8 bytes is a hazard the compiler
     // resolves for its own stores, not for this one)
-#ifndef WDG_Q_STORE_POLICY  // (A/B of the cache policy bits of the running-sum stores: -DWDG_Q_STORE_POLICY_ID=1..4)
-#if WDG_Q_STORE_POLICY_ID == 1
-#define WDG_Q_STORE_POLICY "nt"
-#elif WDG_Q_STORE_POLICY_ID == 2
-#define WDG_Q_STORE_POLICY "sc1"
-#elif WDG_Q_STORE_POLICY_ID == 3
-#define WDG_Q_STORE_POLICY "sc0 sc1"
-#elif WDG_Q_STORE_POLICY_ID == 4
-#define WDG_Q_STORE_POLICY "nt sc1"
-#else
-#define WDG_Q_STORE_POLICY ""
-#endif
-#endif
-    asm volatile("global_store_dwordx4 %0, %1, %2 " WDG_Q_STORE_POLICY "\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(base) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(base) : "memory");
 }
 
 __device__ __forceinline__ void q_st2(global_ptr<float> base, unsigned voff, f32x2 v) {  // HALF slabs: 8 bytes per lane
@@ -1176,13 +1159,11 @@ __device__ __forceinline__ void q_units_fast(const wdg_spmm_job *jobs, const wdg
     auto next_idx = [&](bool from_counter) {
         int idx = static_idx;
         static_idx += Q_FAST_WAVES;
-#ifndef WDG_Q_STATIC_DEAL
         if (from_counter) {
             int v = 0;
             if (lane == 0) v = __hip_atomic_fetch_add((int *)next_unit, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             idx = __builtin_amdgcn_readfirstlane(v);
         }
-#endif
         return idx;
     };
 
@@ -1801,10 +1782,8 @@ int quad_single(const wdg_spmm_job &j, hipStream_t st) {
         subs = std::max(subs, need);
     }
     // many feature groups: the global deal (see the kernel) with as few segments as fill the chip about twice
-    // (WDG_QUAD_SINGLE_SEGMENTS: experiments; 0 = the per-XCD deal of rounds 2 - 5)
     {
         int glob = n_groups >= 64 ? static_cast<int>(ceil_div(2 * wdg_device_cus(), n_groups)) : 0;
-        if (const char *e = getenv("WDG_QUAD_SINGLE_SEGMENTS")) glob = atoi(e);
         if (j.q_n_blocks > 1) glob = 0;  // (several column blocks: the per-XCD deal; such graphs go to the band kernel anyway)
         if (glob > 0) {
             glob = std::min(glob, std::max(1, n_units));

@@ -371,10 +371,6 @@ class KrBatch:
             per = int(lib.wdg_kr_deflate_workspace_bytes(int(n_val.max())))
             self.ws = torch.empty(n * per, dtype=torch.uint8, device=dev)
             tab["ws"] = self.ws.data_ptr() + per * np.arange(n, dtype=np.int64)
-        # (timing-only diagnostics of the blocked solver: honoured only by a library built with -DWDG_KR_ABLATION, and never
-        # mistaken for a result - accuracy() refuses)
-        self.ablate = int(os.environ.get("WDG_KR_ABLATE", "0"))
-        tab["reserved"] = self.ablate
         self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
 
     def launch(self):
@@ -393,8 +389,6 @@ class KrBatch:
 
     def accuracy(self):
         """[n_problems] fp32 hit rate on the validation rows; raises when the kernel refused a problem (sentinel -1)"""
-        if getattr(self, "ablate", 0):
-            raise _lib.WdgError("KrBatch: WDG_KR_ABLATE is set - the launch was a timing-only ablation, its accuracies mean nothing")
         correct = self.correct[:self.n_jobs]
         if self.n_jobs and bool((correct < 0).any().item()):
             raise _lib.WdgError("wdg_kernel_regress_batched_f32 refused a problem (shape outside the solver's limits)")

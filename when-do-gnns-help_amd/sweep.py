@@ -249,15 +249,15 @@ def exchange_rows(keys, rows, n_total, device):
 
 
 def pairs_of_rank(pairs, world, rank):
-    """the adjacencies whole_sweep_rank gives `rank`: shard_pairs (sample-aware; WDG_SWEEP_SHARD=lpt: round 5's shard_jobs)"""
-    return shard_pairs(pairs, world, rank) if os.environ.get("WDG_SWEEP_SHARD", "sample") != "lpt" else shard_jobs(pairs, world, rank)
+    """the adjacencies whole_sweep_rank gives `rank`: shard_pairs (sample-aware)"""
+    return shard_pairs(pairs, world, rank)
 
 
 def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_per_shard=80, depth=2, progress=None, stats=None):
     """This rank's share of the reference's whole sweep (synthetic_plot.py:64-109), STRONG scaling: the (level, sample)
     adjacencies `pairs` (a list of Job; job.seed = the sample) are dealt to the ranks by shard_pairs (contiguous ranges of the
-    sample-major list, balanced by modelled cost; WDG_SWEEP_SHARD=lpt: round 5's shard_jobs), every rank runs all feature
-    bases over its adjacencies through run_bases (graphs built once per shard and shared by the bases) - no data-path collective.
+    sample-major list, balanced by modelled cost), every rank runs all feature bases over its adjacencies through run_bases
+    (graphs built once per shard and shared by the bases) - no data-path collective.
     graph_of(job) -> (src, dst, labels) host arrays; bases as run_bases takes them.
     -> (keys [m] int64, rows [m, 9] fp64): key = index of the pair in `pairs` x n_bases + base index, ready for exchange_rows.
     A rank keeps one shard while it holds <= max_pairs_per_shard adjacencies (fewer job tables to build), else equal shards.
@@ -279,90 +279,22 @@ def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_
 
 
 class _PrelaunchedGram:
-    """A GramBatch that has been LAUNCHED already on another stream (run_bases' feature prologue: a shard's raw-feature uploads and
-    Grams are queued before its graphs exist): the first launch() only waits for that launch's event, later ones (a replayed batch)
-    launch the table again.  Outputs as GramBatch's."""
+    """A GramBatch launched at construction (prepare_full queues the raw features' kernels before it builds the propagation's and
+    the regressions' tables): the first launch() waits for the event recorded behind that launch - free on the same stream, and
+    correct on another -, later ones (a replayed batch) launch the table again.  Outputs as GramBatch's."""
 
-    def __init__(self, gx, event=None):
-        """event: recorded behind the launch on the stream it ran on; None: it ran on the stream the batch launches on"""
-        self.gx, self.event, self.pending = gx, event, True
+    def __init__(self, gx):
+        gx.launch()
+        self.gx, self.event = gx, torch.cuda.Event()
+        self.event.record()
         self.k_linear, self.k_arccos, self.norm2, self.rep, self.row_rep = gx.k_linear, gx.k_arccos, gx.norm2, gx.rep, gx.row_rep
-
-    def launch(self):
-        if self.pending:
-            self.pending = False
-            if self.event is not None:
-                torch.cuda.current_stream().wait_event(self.event)
-                self.event = None
-        else:
-            self.gx.launch()
-
-
-class _CopiedGram:
-    """The raw-feature kernels of a prepared batch (whose job tables hold these buffers' addresses: SweepBatch.rebind_features) filled
-    by COPY from a GramBatch launched elsewhere (the feature prologue): 64 MB device to device per base and two samples instead of the
-    Gram itself on this stream.  Outputs: the batch's own buffers."""
-
-    def __init__(self, dst, src, event):
-        self.dst, self.src, self.event = dst, src, event
-        self.k_linear, self.k_arccos, self.norm2, self.rep, self.row_rep = dst.k_linear, dst.k_arccos, dst.norm2, dst.rep, dst.row_rep
 
     def launch(self):
         if self.event is not None:
             torch.cuda.current_stream().wait_event(self.event)
             self.event = None
         else:
-            self.src.launch()  # (a replay: the source table again, on this stream, then the copies)
-        for name in ("k_linear", "k_arccos", "norm2", "rep"):
-            for d, s_ in zip(getattr(self.dst, name), getattr(self.src, name)):
-                if d is not None and s_ is not None:
-                    d.copy_(s_, non_blocking=True)
-
-
-class FeaturePrologue:
-    """The raw-feature side of a shard's wide bases - the feature matrices' uploads, their Grams / arc-cosine kernels and row
-    representatives - queued on a stream of its own BEFORE the shard's graphs exist: none of it depends on a graph, and a rank's
-    share of the sweep otherwise starts with ~13 ms of host work (graph build, the first base's tables) during which the GPU has
-    nothing to do (a quarter of a rank's 51 ms at 8 ranks; scripts/dev/rank_phases.py).  items[base index] = (x {seed: device
-    tensor}, GramBatch, event) through get()."""
-
-    _POOL = None  # one helper thread per process: the uploads' host copies (150 MB per rank and pass) run beside the main thread
-
-    def __init__(self, bases, which, seeds, stream):
-        """which: the base indices, in the order they will be asked for.  The work runs on a helper thread (the copies into the page-
-        locked ring - library threads, the interpreter lock released - took 19 ms of a rank's start-up when the main thread made
-        them); get(bi) waits until base bi has been QUEUED."""
-        from concurrent.futures import ThreadPoolExecutor
-        from . import ops
-        dev = ops.require_gpu()
-        if FeaturePrologue._POOL is None:
-            FeaturePrologue._POOL = ThreadPoolExecutor(max_workers=1, thread_name_prefix="wdg-prologue")
-        device_index = torch.cuda.current_device()
-
-        def one(bi):
-            torch.cuda.set_device(device_index)
-            with torch.cuda.stream(stream):
-                _name, feats, _sm = bases[bi]
-                x = {s_: ops._h2d(np.ascontiguousarray(feats[s_], np.float32), dev) for s_ in seeds}
-                gx = ops.GramBatch([x[s_] for s_ in seeds])
-                gx.launch()
-                ev = torch.cuda.Event()
-                ev.record()
-                return x, gx, ev
-
-        self.futures = {bi: FeaturePrologue._POOL.submit(one, bi) for bi in which}
-
-    def get(self, bi):
-        f = self.futures.get(bi)
-        return None if f is None else f.result()
-
-    def drain(self):
-        """(a consumer that skipped bases - an exception, a route decided otherwise - must not leave uploads running into freed state)"""
-        for f in self.futures.values():
-            try:
-                f.result()
-            except Exception:  # noqa: BLE001  (reported where the base is asked for; here only the thread is joined)
-                pass
+            self.gx.launch()
 
 
 class _GramPair:
@@ -392,14 +324,15 @@ class SweepBatch:
         share: another SweepBatch over the SAME jobs whose graphs (CSR, SELL-16 copy, degrees, labels) this one reuses - the
         feature bases of synthetic_plot.py:64-65 aggregate different feature matrices over the same 300 adjacencies
         (BaseSweep below); feature_seed offsets the generator's feature seed per base.
-        build: "batched" (default; WDG_SWEEP_BUILD) - all graphs of the shard through ops.GraphBatch: one COO -> CSR build of
+        build: "batched" (default) - all graphs of the shard through ops.GraphBatch: one COO -> CSR build of
         their block-diagonal union, the SELL-16 copies in five launches, ONE host read-back; "per_graph" - round 2's
-        CsrGraph.from_coo + ensure_quad per graph (~20 launches and two host syncs each), kept for A/B runs and tests.
+        CsrGraph.from_coo + ensure_quad per graph (~20 launches and two host syncs each), the tests' reference.
         tune: balance the aggregation's tape cut by feedback (tune() below: ~250 extra steps) - worth it for a batch that is
         replayed many times (training, the replay benchmark); a one-pass sweep takes the modelled cut.
         graph_batch: the shard's ops.GraphBatch (A + I of every job, quad=True) when the caller has queued or finished the build
         already (run_bases builds the NEXT shard's graphs on a stream of their own while this shard's bases run).
-        x_dev: {seed: [n, n_feat] fp32 device tensor} - the feature matrices, uploaded already (run_bases' feature prologue).
+        x_dev: {seed: [n, n_feat] fp32 device tensor} - the feature matrices, uploaded already (run_bases uploads the first
+        base's while the shard's graphs are built).
         labels_only: aggregate the one-hot LABEL columns only (one 16-feature group: everything the six step scalars need); the
         feature matrices are uploaded for the kernel-regression metric, whose aggregated-feature kernels then come by propagation
         (prepare_full: K(A_hat X) = A_hat K(X) A_hat^T) - the reference's sweep over its wide feature bases (F up to 3 703) never
@@ -429,19 +362,18 @@ class SweepBatch:
         lab_col = 0 if self.labels_only else n_feat  # first label column of [X | onehot | 0]
         self.lab_col = lab_col
         # rows of [X | onehot | 0] and of Y are padded to whole 16-feature groups: every 64-byte row segment an item stores
-        # is then 64-byte aligned (one L2 write request instead of two: 220 against 225 us per launch; ..._ALIGN=4 to compare)
-        align = int(os.environ.get("WDG_SWEEP_AGG_ALIGN", "16"))
-        self.agg_feat = (lab_col + n_classes + align - 1) // align * align if ride else n_feat
+        # is then 64-byte aligned (one L2 write request instead of two: 220 against 225 us per launch with an alignment of 4)
+        self.agg_feat = (lab_col + n_classes + 15) // 16 * 16 if ride else n_feat
         self.alg_feat = lab_col + n_classes if ride else n_feat  # columns that carry data (byte accounting: no padding)
-        build = build or os.environ.get("WDG_SWEEP_BUILD", "batched")
+        build = build or "batched"
         # A STEP TWIN: with labels_only the step aggregates [onehot(labels) | 0] and nothing of the features, so its tables, its
         # outputs and its six scalars depend on the graphs and their labels only.  A batch that shares the graphs of another
         # labels-only batch (the feature bases of one shard, run_bases) shares that batch's whole step - job tables, Y, counters - and
         # uploads its feature matrices for the kernel-regression metric, nothing else; its step() launches nothing (the owner's has
-        # run on a stream this one waits for).  WDG_SWEEP_STEP_TWINS=0: every batch its own step (round 4).
+        # run on a stream this one waits for).
         self.step_owner = None
         if (share is not None and self.labels_only and getattr(share, "labels_only", False) and share.agg_feat == self.agg_feat
-                and share.symmetric == symmetric and len(share.jobs) == len(self.jobs) and os.environ.get("WDG_SWEEP_STEP_TWINS", "1") != "0"):
+                and share.symmetric == symmetric and len(share.jobs) == len(self.jobs)):
             self._init_step_twin(share.step_owner or share, inputs, n_feat, feature_seed, dev, x_dev)
             return
         feats, self.graphs, self.dinv, self.labels, self._y = {}, [], [], [], []
@@ -569,9 +501,7 @@ class SweepBatch:
 
         # GCN-2 forward (build-defined model, models.py): logits = A_hat relu((A_hat X) W0) W1, every job its own weights
         self.gcn = None
-        n_streams = int(os.environ.get("WDG_SWEEP_STREAMS", "2"))  # see step_rest
-        self.side = _side_stream(0) if n_streams >= 2 else None
-        self.side2 = _side_stream(1) if n_streams >= 3 else None
+        self.side = _side_stream(0)  # see step_rest
         self._fork = torch.cuda.Event()
         if gcn_hidden:
             gen = torch.Generator(device="cpu").manual_seed(1234)
@@ -602,7 +532,7 @@ class SweepBatch:
         ops = self.ops
         self.step_owner = owner
         for name in ("graphs", "dinv", "labels", "labels_host", "y_agg", "_y", "x_agg", "spmm", "stats", "las", "h_las", "spmm_las",
-                     "edges", "n_classes", "tiled_y", "derive_counts", "gcn", "side", "side2", "_fork", "graph_batch", "y_pool"):
+                     "edges", "n_classes", "tiled_y", "derive_counts", "gcn", "side", "_fork", "graph_batch", "y_pool"):
             if hasattr(owner, name):
                 setattr(self, name, getattr(owner, name))
         self._y_rm, self._untile_each_step, self._y_at, self._y_lazy = None, False, -1, None
@@ -743,27 +673,15 @@ class SweepBatch:
         the metric kernels use the remaining CUs meanwhile: LAS first (large workgroups, done within ~50 us), then the
         statistics kernel, whose remainder overlaps the logits aggregation (scripts/dev/step_timeline.py on a kernel trace).
         Measured per step: one stream 0.47 ms, two streams statistics-first 0.439, three streams 0.425, two streams
-        LAS-first 0.408.  WDG_SWEEP_STREAMS=1|3 for the other arrangements."""
+        LAS-first 0.408 (the arrangement taken here)."""
         main = torch.cuda.current_stream()
-        if self.gcn and self.side is not None:
-            self._fork.record(main)  # one marker on the main queue for both side streams
+        if self.gcn:
+            self._fork.record(main)
             self.side.wait_event(self._fork)
-            if self.side2 is not None:
-                self.side2.wait_event(self._fork)
-                with torch.cuda.stream(self.side):
-                    if not self.derive_counts:
-                        self.stats.launch()
-                with torch.cuda.stream(self.side2):
-                    if self.spmm_las is not None:
-                        self.spmm_las.launch()
-                    self.las.launch()
-            else:
-                with torch.cuda.stream(self.side):
-                    self._metric_chain()
+            with torch.cuda.stream(self.side):
+                self._metric_chain()
             self._gcn_chain()
             main.wait_stream(self.side)
-            if self.side2 is not None:
-                main.wait_stream(self.side2)
         else:
             self._metric_chain()
             if self.gcn:
@@ -851,7 +769,7 @@ class SweepBatch:
         st = self.stats
         if not self.jobs:  # an empty shard (more ranks than jobs): no rows, same columns
             return torch.zeros((0, STEP_METRICS), dtype=torch.float32, device=st.counters.device)
-        if not 1 <= st.c <= 32 or os.environ.get("WDG_SWEEP_SCALARS", "kernel") == "torch":
+        if not 1 <= st.c <= 32:
             return self.results_torch()
         ops = self.ops
         out = torch.empty((st.n_jobs, STEP_METRICS), dtype=torch.float32, device=st.counters.device)
@@ -889,7 +807,7 @@ class SweepBatch:
         return torch.stack([edge, node, cls, adj, li, soft_las], 1)
 
     # -- the remaining three scalars: generalized edge homophily + the kernel-regression p-values ------
-    def prepare_full(self, epochs=100, sample_max=500, seed_of=None, sampler=None, base_seed=0, sets=None, gx=None):
+    def prepare_full(self, epochs=100, sample_max=500, seed_of=None, sampler=None, base_seed=0, sets=None):
         """Set up the batched kernel-regression metric for every job: the Gram / arc-cosine kernels of the aggregated features
         (per job) and of the raw features (per feature matrix) - all nodes, once -, and, per job x classifier (kernel_reg0 /
         kernel_reg1) x epoch, the train / validation node sets; both kernels of an epoch share its node sets.
@@ -941,17 +859,10 @@ class SweepBatch:
         # graph: slower, same rows; round 5 raised here and a single hub-heavy graph aborted the whole sweep - ADVICE r05)
         x_slot = {s: J + i for i, s in enumerate(seeds)}
         if self.gram_route == "propagate":
-            # (gx: (GramBatch over self.x in seed order, event) launched already - run_bases' feature prologue)
-            if gx is None:
-                # the raw features' kernels are launched HERE, while the host goes on building the propagation's and the regressions'
-                # tables: they depend on nothing else of the batch (1.7 ms of device work for cora's two matrices that a rank's
-                # start-up otherwise leaves the GPU waiting for)
-                gx = ops.GramBatch([self.x[s] for s in seeds])
-                if os.environ.get("WDG_SWEEP_EARLY_GRAM", "1") != "0":
-                    gx.launch()
-                    gx = _PrelaunchedGram(gx)
-            else:
-                gx = _PrelaunchedGram(*gx)
+            # the raw features' kernels are launched HERE, while the host goes on building the propagation's and the regressions'
+            # tables: they depend on nothing else of the batch (1.7 ms of device work for cora's two matrices that a rank's
+            # start-up otherwise leaves the GPU waiting for)
+            gx = _PrelaunchedGram(ops.GramBatch([self.x[s] for s in seeds]))
             sym = getattr(self, "symmetric", 0)
             gy = ops.PropagatedGram([(g, d, d if sym else None, gx.k_linear[x_slot[j.seed] - J])
                                      for j, g, d in zip(self.jobs, self.graphs, self.dinv)])
@@ -1006,17 +917,8 @@ class SweepBatch:
         G = len(rep)
         self.kr_group, self.kr_rep = group, rep
         if sampler == "device":
-            # a (group, classifier) pair's key is an IDENTITY (not a position in this shard), so that the same job draws the same
-            # sets on whichever rank / in whichever batch it runs: the sample's (seed, size, label vector) - or, sets="job", the
-            # job's (seed, h, k, size), so that different jobs draw independent ones
-            def key_of(g, clf):
-                j = self.jobs[rep[g]]
-                if sets == "sample":
-                    return _mix64(base_seed, j.seed, j.n_nodes, label_crc[g], 0x5A3D, clf)
-                return _mix64(base_seed, j.seed, int(round(j.h * 1e6)), j.k, j.n_nodes, clf)
-            self.kr_sets = ops.KrSets([(self.labels[rep[g]], sizes[rep[g]][0], sizes[rep[g]][1], key_of(g, clf))
-                                       for g in range(G) for clf in (0, 1)], epochs)
             self._kr_rebind = (sets, [sizes[r_] for r_ in rep], label_crc if sets == "sample" else None)
+            self.kr_sets = self._kr_sets(base_seed)
             train, val = self.kr_sets.train, self.kr_sets.val         # [G * 2, epochs, n_train / n_val], filled by launch_full()
         else:
             self.kr_sets = None
@@ -1073,7 +975,23 @@ class SweepBatch:
         self.kr_canonical = ((u_job * 2 + u_clf) * epochs + u_epoch) * 2 + (np.arange(u_job.shape[0]) >= J * 2 * epochs)
         self._kr_index_dev = None
 
-    def rebind_features(self, feats_of_seed, n_feat, base_seed, pre=None):
+    def _kr_sets(self, base_seed, out=None):
+        """the device sampler's table of every (group, classifier) under base_seed (out: a table whose tensors it fills).  A pair's
+        key is an IDENTITY (not a position in this shard), so that the same job draws the same sets on whichever rank / in whichever
+        batch it runs: the sample's (seed, size, label vector) - or, sets="job", the job's (seed, h, k, size), so that different jobs
+        draw independent ones"""
+        mode, sizes_rep, label_crc = self._kr_rebind
+        rep = self.kr_rep
+
+        def key_of(g, clf):
+            j = self.jobs[rep[g]]
+            if mode == "sample":
+                return _mix64(base_seed, j.seed, j.n_nodes, label_crc[g], 0x5A3D, clf)
+            return _mix64(base_seed, j.seed, int(round(j.h * 1e6)), j.k, j.n_nodes, clf)
+        return self.ops.KrSets([(self.labels[rep[g]], sizes_rep[g][0], sizes_rep[g][1], key_of(g, clf))
+                                for g in range(len(rep)) for clf in (0, 1)], self.kr_epochs, out=out)
+
+    def rebind_features(self, feats_of_seed, n_feat, base_seed):
         """The NEXT FEATURE BASE on a prepared labels-only batch (run_bases: synthetic_plot.py:64-65 runs six feature bases over
         the same adjacencies): new raw feature matrices and new node-set keys, every job table kept.  The step's tables never
         held a feature address (labels_only); the raw features' kernels are written into the SAME buffers (GramBatch(out=...)),
@@ -1088,25 +1006,10 @@ class SweepBatch:
         seeds = list(self.x)
         self.n_feat = n_feat
         self._y_lazy = None
-        if pre is not None:  # (x {seed: device tensor}, GramBatch, event): uploaded and launched by the feature prologue - copied in
-            self.x = {s_: pre[0][s_] for s_ in seeds}
-            old = self.gram.feats_part
-            self.gram.feats_part = _CopiedGram(old.dst if isinstance(old, _CopiedGram) else old, pre[1], pre[2])
-        else:
-            self.x = {s_: ops._h2d(np.ascontiguousarray(feats_of_seed[s_], np.float32), dev) for s_ in seeds}
-            old = self.gram.feats_part
-            gx = ops.GramBatch([self.x[s_] for s_ in seeds], out=old.dst if isinstance(old, _CopiedGram) else old)
-            self.gram.feats_part = gx  # (same output tensors: the pair's k_linear / k_arccos / norm2 lists stay as they are)
-        mode, sizes_rep, label_crc = self._kr_rebind
-        rep = self.kr_rep
-
-        def key_of(g, clf):
-            j = self.jobs[rep[g]]
-            if mode == "sample":
-                return _mix64(base_seed, j.seed, j.n_nodes, label_crc[g], 0x5A3D, clf)
-            return _mix64(base_seed, j.seed, int(round(j.h * 1e6)), j.k, j.n_nodes, clf)
-        self.kr_sets = ops.KrSets([(self.labels[rep[g]], sizes_rep[g][0], sizes_rep[g][1], key_of(g, clf))
-                                   for g in range(len(rep)) for clf in (0, 1)], self.kr_epochs, out=self.kr_sets)
+        self.x = {s_: ops._h2d(np.ascontiguousarray(feats_of_seed[s_], np.float32), dev) for s_ in seeds}
+        # (same output tensors: the pair's k_linear / k_arccos / norm2 lists stay as they are)
+        self.gram.feats_part = ops.GramBatch([self.x[s_] for s_ in seeds], out=self.gram.feats_part)
+        self.kr_sets = self._kr_sets(base_seed, out=self.kr_sets)
 
     def kr_accuracy(self):
         """[jobs, 2 classifiers, epochs, (graph-aware, features only)] fp32 device tensor: every job's accuracies, read through
@@ -1134,20 +1037,12 @@ class SweepBatch:
         side = None
         if self.kr_sets is not None:
             # the epochs' node sets (device sampler; a host-sampled batch uploaded them in prepare_full) depend on nothing the
-            # step produces: drawn on a second stream beside the Grams (0.8 ms of LDS sorting beside 2.7 ms of MFMA tiles)
-            cur = torch.cuda.current_stream()
-            if os.environ.get("WDG_SWEEP_SIDE_STREAM", "1") != "0":
-                if getattr(self, "_side_stream", None) is None:
-                    self._side_stream = _side_stream(2)
-                side = self._side_stream
-                side.wait_stream(cur)  # (the previous batch's regressions have read the old sets)
-                with torch.cuda.stream(side):
-                    if sample_events:
-                        sample_events[0].record()
-                    self.kr_sets.launch()
-                    if sample_events:
-                        sample_events[1].record()
-            else:
+            # step produces: drawn on a second stream beside the Grams (their 2.7 ms of MFMA tiles)
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = _side_stream(2)
+            side = self._side_stream
+            side.wait_stream(torch.cuda.current_stream())  # (the previous batch's regressions have read the old sets)
+            with torch.cuda.stream(side):
                 if sample_events:
                     sample_events[0].record()
                 self.kr_sets.launch()
@@ -1289,8 +1184,6 @@ class SweepBatch:
                                              self.kr.flags.data_ptr(), self.kr.n_val.data_ptr(), n_kr, packed_dev.data_ptr(),
                                              ops.stream_handle()), "wdg_sweep_pack_f64")
         packed = packed_dev.cpu()
-        if getattr(self.kr, "ablate", 0):
-            raise WdgError("KrBatch: WDG_KR_ABLATE is set - the launch was a timing-only ablation, its accuracies mean nothing")
         if int(packed[-1].item()):
             raise WdgError("wdg_kernel_regress_batched_f32 refused a problem (shape outside the solver's limits)")
         # (rank-deficient train blocks: solved with a rounding-level ridge where the reference's pinv inverts the rounding-level
@@ -1401,10 +1294,8 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
     # the part of it that needs no interpreter.  Measured over ten 50-graph shards, best of three passes (scripts/dev/time_cold_modes.py):
     # six scalars 8 800 -> 9 700 graphs/s, nine scalars 3 360 -> 4 670.  (The shard's feature uploads moved to the helper as well:
     # 6 300 / 4 200 - its 4-MB copies hold the upload ring's lock against this thread's twenty small uploads.)
-    # WDG_SWEEP_BUILD_THREAD=0 / depth 1: everything on this thread, in place.
-    threaded = (depth > 1 and os.environ.get("WDG_SWEEP_BUILD_THREAD", "1") != "0" and os.environ.get("WDG_SWEEP_BUILD", "batched") == "batched")
-    if "WDG_SWEEP_BUILD_THREAD_FORCE" in os.environ:  # (scripts/dev/time_cold_modes.py)
-        threaded = os.environ["WDG_SWEEP_BUILD_THREAD_FORCE"] == "1"
+    # Depth 1: everything on this thread, in place.
+    threaded = depth > 1
     pool = build_stream = None
     if threaded:
         from concurrent.futures import ThreadPoolExecutor
@@ -1494,15 +1385,13 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
     # base with the same sample_max whose rows have been fetched: SweepBatch.rebind_features swaps the feature matrices and the
     # node-set keys and keeps every job table (the kernels land in the same buffers).  The bases are visited in an order that puts
     # bases of equal sample_max apart (with two base-shards in flight a batch is free again two visits later); rows carry their base
-    # index, and a batch stays on its stream.  WDG_SWEEP_REBIND=0: every base-shard builds its own tables, in the caller's order.
-    rebind_ok = os.environ.get("WDG_SWEEP_REBIND", "1") != "0"
+    # index, and a batch stays on its stream.
     # The NEXT shard's graphs are built ahead, on a stream of their own, as soon as this shard's first base is queued: the build's
     # one read-back (GraphBatch.finish) then finds its data ready.  Built in place it waited behind whatever ran on the GPU at
     # that moment - typically a regression launch that holds every CU for 5 - 9 ms - and the queue ran dry while the host stood
-    # still: a fifth of the sweep's wall clock had no kernel running.  WDG_SWEEP_PREFETCH_BUILD=0: build in place.
+    # still: a fifth of the sweep's wall clock had no kernel running.
     shards = list(shards)
-    prefetch = (os.environ.get("WDG_SWEEP_PREFETCH_BUILD", "1") != "0" and os.environ.get("WDG_SWEEP_BUILD", "batched") == "batched")
-    build_stream = _side_stream(3) if prefetch else None
+    build_stream = _side_stream(3)
     queued = {}
 
     def queue_build(si_):
@@ -1514,46 +1403,29 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
             return ops.GraphBatch([(src, dst, j.n_nodes) for j, (src, dst, _lab) in zip(jobs_, gi_)], ops.COO_ADD_SELF_LOOPS,
                                   quad=True, defer=True)
 
-    # The FEATURE PROLOGUE (round 6, WDG_SWEEP_PROLOGUE=1; OFF by default): the wide bases' feature uploads, raw-feature Grams and row
-    # representatives depend on no graph - queued, by a helper thread and on a stream of their own, before the shard's graph build is
-    # waited for, they give the GPU work during the ~13 ms in which the host builds a rank's graphs and its first base's tables.
-    # Measured at 8 ranks (scripts/dev/rank_phases.py): the device span of a rank's pass shrinks from 37.4 to 33.2 ms, but the first
-    # base's launches are queued 4 ms later (the helper's table and upload work competes with the main thread for the interpreter)
-    # - 51.0 ms per pass either way; made by the main thread itself the prologue costs 19 ms of host copies up front (65 ms).  The
-    # start-up is host-bound table building, not missing device work: kept as a switch, rows identical (tests/test_gpu_sweep.py).
-    prologue_on = os.environ.get("WDG_SWEEP_PROLOGUE", "0") not in ("0", "")
-    pro_stream = _side_stream(4) if prologue_on else None
     widths = [next(iter(feats.values())).shape[1] if feats else 0 for _name, feats, _sm in bases]
     n = 0
     for si, (jobs, graph_inputs) in enumerate(shards):
         first = first_lo = None
-        gb = None
-        if prefetch:
-            gb = queued.pop(si) if si in queued else queue_build(si)
-        pro, early = None, None
-        if jobs and (prologue_on or (prefetch and gb is not None)):
+        gb = queued.pop(si) if si in queued else queue_build(si)
+        early = None
+        if gb is not None:
             lo_guess = [propagates(w, jobs) for w in widths]  # (what `lo` below becomes when every graph has its SELL-16 copy)
-            guess = (_visit_order([(lo_guess[bi], bases[bi][2]) if lo_guess[bi] else ("own", bi) for bi in range(len(bases))])
-                     if rebind_ok else list(range(len(bases))))
-            wide = [bi for bi in guess if lo_guess[bi]]
-            if prologue_on and wide:
-                pro_stream.wait_stream(torch.cuda.current_stream())
-                pro = FeaturePrologue(bases, wide, sorted({j.seed for j in jobs}), pro_stream)
-            elif lo_guess[guess[0]]:
+            first_bi = _visit_order([(lo_guess[bi], bases[bi][2]) if lo_guess[bi] else ("own", bi) for bi in range(len(bases))])[0]
+            if lo_guess[first_bi]:
                 # the FIRST base's feature matrices go into the upload ring while the GPU builds the shard's graphs: the copies (1.2 ms
                 # of library threads for cora's two 11-MB matrices) otherwise sit between the build's read-back and the first launch
                 from . import ops
                 with torch.cuda.stream(streams[n % depth]):
-                    early = (guess[0], {s_: ops._h2d(np.ascontiguousarray(bases[guess[0]][1][s_], np.float32), ops.require_gpu())
+                    early = (first_bi, {s_: ops._h2d(np.ascontiguousarray(bases[first_bi][1][s_], np.float32), ops.require_gpu())
                                         for s_ in sorted({j.seed for j in jobs})})
-        if prefetch and gb is not None:
             with torch.cuda.stream(build_stream):
                 gb.finish()
         # (decided AFTER the graphs are built when they are built ahead: a graph without a SELL-16 copy rules the propagated route out
         # for the whole shard - its bases then aggregate at full width and take the dense Gram, as round 4 did)
         quad_ok = gb is None or all(g.quad for g in gb.graphs)
         lo = [quad_ok and propagates(w, jobs) for w in widths]
-        order = _visit_order([(lo[bi], bases[bi][2]) if lo[bi] else ("own", bi) for bi in range(len(bases))]) if rebind_ok else list(range(len(bases)))
+        order = _visit_order([(lo[bi], bases[bi][2]) if lo[bi] else ("own", bi) for bi in range(len(bases))])
         free = {}  # (sample_max, stream) -> a prepared labels-only batch whose rows have been fetched
         for bi in order:
             _name, feats, sample_max = bases[bi]
@@ -1565,27 +1437,25 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
             with torch.cuda.stream(stream):
                 width = widths[bi]
                 key = (sample_max, stream.cuda_stream)
-                sb = free.pop(key, None) if (rebind_ok and lo[bi] and jobs) else None
-                pre = pro.get(bi) if (pro is not None and lo[bi]) else None  # (x, GramBatch, event) of the prologue
+                sb = free.pop(key, None) if (lo[bi] and jobs) else None
                 x_early = early[1] if (early is not None and early[0] == bi and lo[bi] and first is None) else None  # (uploaded on this stream)
                 if sb is not None:
-                    sb.rebind_features(feats, width, first_seed + 1000 * bi, pre=pre)
+                    sb.rebind_features(feats, width, first_seed + 1000 * bi)
                 else:
                     inputs = [(src, dst, lab, feats[j.seed]) for j, (src, dst, lab) in zip(jobs, graph_inputs)]
                     sb = SweepBatch(jobs, n_feat=width, symmetric=symmetric, gcn_hidden=0, inputs=inputs,
                                     share=(first_lo or first) if lo[bi] else first, labels_only=lo[bi],
-                                    graph_batch=gb if first is None else None, x_dev=pre[0] if pre else x_early)
+                                    graph_batch=gb if first is None else None, x_dev=x_early)
                     if sb.jobs:
                         # (the node sets are keyed by the base and the job's identity, not by where the job sits: a job draws the
                         # same sets in whichever shard / on whichever rank it runs - the N-rank sweep computes the one-GPU sweep's rows)
-                        sb.prepare_full(epochs=epochs, sample_max=sample_max, base_seed=first_seed + 1000 * bi,
-                                        gx=(pre[1], pre[2]) if pre else None)
+                        sb.prepare_full(epochs=epochs, sample_max=sample_max, base_seed=first_seed + 1000 * bi)
                     sb.step()
                 if sb.jobs:
                     sb.launch_full()
             if first is None:
                 first, first_stream = sb, stream
-                if prefetch and si + 1 < len(shards):
+                if si + 1 < len(shards):
                     queued[si + 1] = queue_build(si + 1)
             if first_lo is None and sb.labels_only:
                 first_lo = sb
@@ -1593,12 +1463,10 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
             n += 1
             if len(in_flight) >= depth:
                 done = fetch()
-                if (rebind_ok and done[0] == si and done[3].labels_only and done[3].jobs and getattr(done[3], "kr_sets", None) is not None
+                if (done[0] == si and done[3].labels_only and done[3].jobs and getattr(done[3], "kr_sets", None) is not None
                         and getattr(done[3], "gram_route", None) == "propagate"):
                     free[(done[3].kr_sample_max, done[4].cuda_stream)] = done[3]
                 yield done[:3]
-        if pro is not None:
-            pro.drain()
     while in_flight:
         yield fetch()[:3]
 
