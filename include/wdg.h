@@ -710,12 +710,14 @@ int wdg_row_rep_batched(const wdg_row_rep_job *jobs_dev, int32_t n_jobs, int32_t
  *           workspace `ws` per job - does not leave EXACT duplicates to the ridge: every train / validation id is read at its representative
  *           (duplicate rows of K are then identical by construction), the train rows are deflated to one row per duplicate class with
  *           the class's mean one-hot label - the pseudo-inverse's minimum-norm answer, by a positive definite factorisation; flags bit 1 reports it.  Rows
- *           below the block's fp32 resolution (K_ii <= n eps max K_ii: all-zero rows, the arc-cosine kernel of an all-zero feature
- *           row) are dropped like exact zeros - an fp32 SVD cannot resolve their singular value either.  The deflated block is
+ *           below the block's fp32 resolution (K_ii <= n eps max K_ii / 64, the solver's own pivot test: all-zero rows, the
+ *           arc-cosine kernel of an all-zero feature row) are dropped like exact zeros - an fp32 SVD cannot resolve their singular
+ *           value either; flags bit 2 reports a drop (bit 1 is set with it).  A row above that level is solved, not dropped: a
+ *           hub-heavy kernel whose K_ii span 1e-5 of the block's maximum gets the pseudo-inverse's answer.  The deflated block is
  *           scaled by the square roots of the class sizes (pinv(P K_u P^T) = Q pinv(S K_u S) Q^T, Q = P S^-1), so that a block that is
  *           rank deficient beyond its duplicates is regularised in the full system's metric.  wdg_kernel_regress_batched_f32 itself ignores both fields.
  * `train` / `val` index rows of K; `labels` is indexed like K's rows.  Limits: ldk < 65 536 (a kernel matrix is addressed by
- * 32-bit element offsets).  The launch is persistent - one workgroup per CU walks the problems, and a problem's predictions are
+ * unsigned 32-bit element offsets: row x ldk + column < 2^32; a problem with a wider ldk answers -1 with flags 0).  The launch is persistent - one workgroup per CU walks the problems, and a problem's predictions are
  * made inside the next problem's factorisation (WDG_KR_PERSIST=0: one workgroup per problem) - which changes no result.
  */
 typedef struct wdg_kr_job {
@@ -725,7 +727,8 @@ typedef struct wdg_kr_job {
     const int32_t *labels;  /* [n] */
     int32_t *correct_out;   /* [1]: validation rows predicted right; -1 = problem refused (shape outside the limits) */
     int32_t *flags_out;     /* [1] or NULL: bit 0 = a pivot fell to rounding level and the block was refactored with the ridge;
-                               bit 1 = the train rows were deflated (duplicates merged / zero rows dropped) */
+                               bit 1 = the train rows were deflated (duplicates merged / zero rows dropped);
+                               bit 2 = (deflating entry) rows below the block's resolution were dropped */
     int64_t ldk;
     int32_t n_train, n_val, n_classes, reserved;
     const int32_t *rep;     /* [n] or NULL: row representatives of the matrix K was computed from (wdg_row_rep_batched) */

@@ -761,13 +761,14 @@ __global__ __launch_bounds__(KSEL_THREADS) void kr_select_kernel(const wdg_kr_sa
 constexpr int K2_THREADS = 1024, K2_WAVES = 16, K2_NB = 10, K2_SLOTS = 3, K2_PS = 36;
 constexpr int KR_MAX_N = K2_NB * 32, KR_MAX_C = 8;  // train rows (320) and classes of a problem
 // the deflation workspace of a problem (wdg_kr_job.ws, filled by kr_deflate_kernel, read by the solver), as int32 words:
-//   [KRW_NT] rows to solve, [KRW_DEFLATED] != 0 when fewer than n_train, [KRW_TRAIN ..] their representatives (padded with -1),
+//   [KRW_NT] rows to solve, [KRW_DEFLATED] != 0 when fewer than n_train, [KRW_DROPPED] != 0 when rows were dropped below the block's
+//   resolution (flags bit 2), [KRW_TRAIN ..] their representatives (padded with -1),
 //   [KRW_VAL ..] n_val validation representatives, then n_val labels
 //   [KRW_LAB ..] a solved row's label when all members of its duplicate class carry the same one (right-hand side: sqrt(size) in that
 //   column), -2 for a class with MIXED labels, whose non-zero right-hand-side entries are listed in [KRW_MIX ..]: [KRW_MIXED] words
 //   (row << 16 | label << 12 | members with that label); [KRW_SCALE ..] sqrt(members) of a solved row's duplicate class (fp32 bits):
 //   the solver factors M = S K S, S = diag of these
-constexpr int KRW_NT = 0, KRW_DEFLATED = 1, KRW_MIXED = 2, KRW_TRAIN = 4, KRW_LAB = KRW_TRAIN + K2_NB * 32, KRW_SCALE = KRW_LAB + K2_NB * 32,
+constexpr int KRW_NT = 0, KRW_DEFLATED = 1, KRW_MIXED = 2, KRW_DROPPED = 3, KRW_TRAIN = 4, KRW_LAB = KRW_TRAIN + K2_NB * 32, KRW_SCALE = KRW_LAB + K2_NB * 32,
               KRW_MIX = KRW_SCALE + K2_NB * 32, KRW_VAL = KRW_MIX + K2_NB * 32;
 static_assert(K2_NB * (K2_NB - 1) / 2 <= K2_WAVES * K2_SLOTS, "every block below the diagonal needs a register slot");
 
@@ -890,13 +891,13 @@ static_assert(KD_THREADS == K2_NB * 32, "one thread per train row");
 __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job *__restrict__ jobs) {
     __shared__ int d_raw[KD_THREADS], d_lab[KD_THREADS], d_first[KD_THREADS], d_slot[KD_THREADS], d_mult[KD_THREADS];
     __shared__ float rhs[KD_THREADS * KR_MAX_C];
-    __shared__ int n_keep, any_mixed;
+    __shared__ int n_keep, any_mixed, any_drop;
     const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)(jobs + blockIdx.x);
     if (job->ws == nullptr) return;  // (uniform)
     const int tid = threadIdx.x, nt_in = job->n_train, nv = job->n_val;
     const global_ptr<int32_t> ws = to_global(static_cast<int32_t *>(job->ws));
     if (nt_in <= 0 || nt_in > KD_THREADS) {  // (the solver refuses the problem by its own test; the workspace must still be sane)
-        if (tid == 0) ws[KRW_NT] = -1, ws[KRW_DEFLATED] = 0;
+        if (tid == 0) ws[KRW_NT] = -1, ws[KRW_DEFLATED] = 0, ws[KRW_DROPPED] = 0;
         return;
     }
     const global_ptr<const float> K = to_global(job->K);
@@ -904,7 +905,7 @@ __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job
                                     rep = to_global(job->rep);
     const bool has_rep = job->rep != nullptr;  // (without the maps every node is its own representative: zero rows are still dropped)
     const int64_t ldk = job->ldk;
-    if (tid == 0) n_keep = 0, any_mixed = 0;
+    if (tid == 0) n_keep = 0, any_mixed = 0, any_drop = 0;
     int r = -1, lb = -1;
     float diag = 0.f;
     if (tid < nt_in) {
@@ -912,7 +913,11 @@ __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job
         r = has_rep ? rep[g] : g, lb = labels[g];
         diag = K[static_cast<int64_t>(r) * ldk + r];
     }
-    // rows BELOW THE BLOCK'S fp32 RESOLUTION are dropped (weight 0): K_ii <= n eps max K_ii - an all-zero row of K (an isolated node's
+    // rows BELOW THE BLOCK'S fp32 RESOLUTION are dropped (weight 0): K_ii <= n eps max K_ii / 64 - the level of the solver's pivot
+    // test, so that a row the solver would factor as it is is never dropped (a hub-heavy kernel's diagonal spans 1e-5 of its maximum
+    // and more).  The two agree exactly when nothing is merged; after merges the solver tests the merged count against the diagonal
+    // of S K S (class sizes >= 1: its maximum is no smaller), so a row kept here may still meet the solver's ridge -:
+    // an all-zero row of K (an isolated node's
     // aggregated features, an all-zero feature row under the linear kernel: an exact zero singular value, which the pseudo-inverse
     // cuts), and the arc-cosine kernel's row of such a node (every entry 1.6e-9: a singular value 1e-12 of the largest, which an
     // fp32 SVD cannot resolve - the reference's pinv leaves it no weight either: measured on texas, where factoring that row
@@ -923,7 +928,7 @@ __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job
     __syncthreads();
     dmax = 0.f;
     for (int w = 0; w < KD_THREADS / 64; ++w) dmax = fmaxf(dmax, rhs[w]);
-    if (tid < nt_in && !(diag > static_cast<float>(nt_in) * 1.1920929e-7f * dmax)) r = -2;
+    if (tid < nt_in && !(diag > static_cast<float>(nt_in) * 1.1920929e-7f * dmax * (1.f / 64.f))) r = -2, any_drop = 1;
     __syncthreads();
     d_raw[tid] = r, d_lab[tid] = lb, d_mult[tid] = 0;
     for (int i = tid; i < KD_THREADS * KR_MAX_C; i += KD_THREADS) rhs[i] = 0.f;
@@ -997,7 +1002,7 @@ __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job
         ws[KRW_VAL + nv + v] = labels[g];
     }
     __syncthreads();
-    if (tid == 0) ws[KRW_NT] = kept, ws[KRW_DEFLATED] = kept != nt_in, ws[KRW_MIXED] = any_mixed;
+    if (tid == 0) ws[KRW_NT] = kept, ws[KRW_DEFLATED] = kept != nt_in, ws[KRW_MIXED] = any_mixed, ws[KRW_DROPPED] = any_drop;
 }
 
 #ifdef K2_PROFILE  // diagnostic build (make EXTRA=-DK2_PROFILE): thread 0 of workgroup 0 sums the shader clocks spent per phase
@@ -1064,7 +1069,8 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
             if (4 * unit >= pnv) break;
             const int v = 4 * unit + g, gv = pval[min(v, pnv - 1)];
             // (one uniform base + a 32-bit element offset per gather: a register per address - these loads are issued ten at a time
-            // beside the factorisation's 48 accumulator registers; the launcher refuses kernels of 2^30 elements and more)
+            // beside the factorisation's 48 accumulator registers; rows and columns are < ldk < 65 536, so row x ldk + column < 2^32:
+            // unsigned offsets past 2^31 are exact - tests/test_gpu_kr_solver.py reads rows above 32 768 at ldk = 65 535)
             const unsigned row_off = static_cast<unsigned>(gv) * static_cast<unsigned>(pldk);
             float p[KR_MAX_C];
 #pragma unroll
@@ -1509,7 +1515,9 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
     }
     // ---- this problem's predictions wait for the next problem's factorisation (or for the flush below)
     if (tid == 0) {
-        if (job->flags_out) *to_global(job->flags_out) = (ridge > 0.f ? 1 : 0) | (deflated ? 2 : 0);
+        // (bit 2 read here, not held through the factorisation: one live register more there spills)
+        const bool dropped = has_ws && ws_ok && ws[KRW_DROPPED] != 0;
+        if (job->flags_out) *to_global(job->flags_out) = (ridge > 0.f ? 1 : 0) | (deflated ? 2 : 0) | (dropped ? 4 : 0);
         pend_hits = 0;
         pend_next = 0;
     }

@@ -357,7 +357,7 @@ class KrBatch:
         if n and int(ldk.max()) >= 65536:  # (the solver's prediction gathers address a kernel matrix by 32-bit element offsets)
             raise ValueError(f"KrBatch: kernel matrices of leading dimension {int(ldk.max())}, the solver addresses up to 65 535")
         self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        self.flags = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)  # bit 0: the ridge refactorisation ran
+        self.flags = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)  # bit 0: ridge refactorisation, 1: deflated, 2: rows dropped
         self.n_val = _h2d(n_val.astype(np.float32), dev)
         tab = np.zeros(n, _KR_JOB_DTYPE)
         tab["K"], tab["train"], tab["val"], tab["labels"] = k_ptr, train_ptr, val_ptr, labels_ptr
@@ -386,6 +386,10 @@ class KrBatch:
     def deflated(self):
         """[n_problems] bool: duplicate train rows were merged / zero rows dropped before the factorisation (row representatives)"""
         return (self.flags[:self.n_jobs] & 2).bool()
+
+    def dropped(self):
+        """[n_problems] bool: train rows below the block's fp32 resolution (K_ii <= n eps max K_ii / 64) were dropped (deflating entry)"""
+        return (self.flags[:self.n_jobs] & 4).bool()
 
     def accuracy(self):
         """[n_problems] fp32 hit rate on the validation rows; raises when the kernel refused a problem (sentinel -1)"""
