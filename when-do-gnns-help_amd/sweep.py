@@ -9,7 +9,9 @@ over ranks (one process per GPU).  Jobs are independent, so the data path has no
 only the job table (broadcast from rank 0) and the per-job result rows (all_gather) through torch.distributed
 (RCCL over xGMI on a GPU node, gloo in the CPU tests).
 """
+import contextlib
 import os
+from collections import deque
 from dataclasses import dataclass
 
 import numpy as np
@@ -991,6 +993,10 @@ class SweepBatch:
         return self.ops.KrSets([(self.labels[rep[g]], sizes_rep[g][0], sizes_rep[g][1], key_of(g, clf))
                                 for g in range(len(rep)) for clf in (0, 1)], self.kr_epochs, out=out)
 
+    def rebindable(self):
+        """whether rebind_features can take this batch: prepared, labels-only, on the propagated route, with device-drawn sets"""
+        return self.labels_only and getattr(self, "gram_route", None) == "propagate" and getattr(self, "kr_sets", None) is not None
+
     def rebind_features(self, feats_of_seed, n_feat, base_seed):
         """The NEXT FEATURE BASE on a prepared labels-only batch (run_bases: synthetic_plot.py:64-65 runs six feature bases over
         the same adjacencies): new raw feature matrices and new node-set keys, every job table kept.  The step's tables never
@@ -1000,7 +1006,7 @@ class SweepBatch:
         computes (tests/test_gpu_sweep.py).  Call only when the batch's previous results have been fetched.
         feats_of_seed: {seed: [n, n_feat] fp32 host array}"""
         ops = self.ops
-        if not (self.labels_only and getattr(self, "gram_route", None) == "propagate" and self.kr_sets is not None):
+        if not self.rebindable():
             raise ValueError("rebind_features: a prepared labels-only batch on the propagated route with device-drawn sets is expected")
         dev = self.kr.correct.device
         seeds = list(self.x)
@@ -1232,14 +1238,6 @@ def welch_p_values(g_res, x_res):
     return np.where(better <= 0.5, p / 2, 1 - p / 2)
 
 
-def _count_kr(stats, sb):
-    if stats is not None:
-        stats["kr_ridged"] = stats.get("kr_ridged", 0) + getattr(sb, "kr_ridged", 0)
-        stats["kr_total"] = stats.get("kr_total", 0) + getattr(sb, "kr_total", 0)
-        stats["kr_deflated"] = stats.get("kr_deflated", 0) + getattr(sb, "kr_deflated", 0)
-        stats["kr_pinv_seconds"] = stats.get("kr_pinv_seconds", 0.0) + getattr(sb, "kr_pinv_seconds", 0.0)
-
-
 _SIDE_STREAMS = {}  # (device, handle of the stream a batch was built on, index) -> its side stream, created once per process
 
 
@@ -1265,6 +1263,54 @@ def _pipe_streams(depth):
     return _PIPE_STREAMS[key]
 
 
+class _InFlight:
+    """The in-flight batches of a pipelined sweep (run_shards, run_bases): the i-th batch pushed runs on stream i mod `depth`; once
+    `depth` are in flight the oldest one's rows are fetched - rows_of(batch) on its stream, its regression counts added to `stats`."""
+
+    def __init__(self, depth, rows_of, stats=None):
+        self.depth = max(1, int(depth))
+        self.streams, self.rows_of, self.stats = _pipe_streams(self.depth), rows_of, stats
+        self.queue, self.n = deque(), 0
+
+    @property
+    def stream(self):  # (the next batch's)
+        return self.streams[self.n % self.depth]
+
+    def push(self, tag, sb):
+        """add a batch queued on self.stream -> [(tag, batch, stream, rows)] of the batches fetched: the oldest one, or none"""
+        self.queue.append((tag, sb, self.stream))
+        self.n += 1
+        return [self.fetch()] if len(self.queue) >= self.depth else []
+
+    def fetch(self):
+        tag, sb, stream = self.queue.popleft()
+        with torch.cuda.stream(stream):
+            rows = self.rows_of(sb)
+        if self.stats is not None:
+            for name in ("kr_ridged", "kr_total", "kr_deflated", "kr_pinv_seconds"):
+                self.stats[name] = self.stats.get(name, 0) + getattr(sb, name, 0)
+        return tag, sb, stream, rows
+
+
+def _queue_graphs(jobs, graph_inputs, build_stream):
+    """queue the build of a shard's graphs (A + I, SELL-16 copies; graph_inputs[i] begins with job i's src, dst) on build_stream,
+    from any thread -> the deferred ops.GraphBatch (None for an empty shard), for _take_graphs"""
+    if not jobs:
+        return None
+    from . import ops
+    torch.cuda.set_device(build_stream.device)  # (the current device is per thread)
+    with torch.cuda.stream(build_stream):
+        return ops.GraphBatch([(g[0], g[1], j.n_nodes) for j, g in zip(jobs, graph_inputs)], ops.COO_ADD_SELF_LOOPS,
+                              quad=True, defer=True)
+
+
+def _take_graphs(gb, build_stream, stream):
+    """finish a queued graph build (its one read-back) on build_stream; `stream`, where the batch that takes it runs, waits for it"""
+    with torch.cuda.stream(build_stream):
+        gb.finish()
+    stream.wait_stream(build_stream)
+
+
 def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symmetric=0, depth=2, first_seed=0, stats=None):
     """The one-pass sweep over a sequence of shards (synthetic_plot.py:78-109: every graph visited once), PIPELINED: a generator
     of the shards' metric rows ([jobs, 6] fp32 / [jobs, 9] fp64 on the host), in order.
@@ -1276,75 +1322,42 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
     job tables: 8-11 ms per 50 graphs) thus overlaps the device part of the one before (15.6 ms with the regressions), where the
     sequential loop of bench.py's `sweep_cold` pays their sum.  depth=1 is that sequential loop.  Every shard computes the same
     bits either way (tests/test_gpu_sweep.py)."""
-    from collections import deque
-    depth = max(1, int(depth))
-    streams = _pipe_streams(depth)
-    in_flight = deque()
-
-    def fetch():
-        sb, stream = in_flight.popleft()
-        with torch.cuda.stream(stream):
-            rows = sb.full_metrics() if nine else sb.results().cpu()
-        _count_kr(stats if nine else None, sb)
-        return rows
-
+    pipe = _InFlight(depth, (lambda sb: sb.full_metrics()) if nine else (lambda sb: sb.results().cpu()), stats if nine else None)
     # The NEXT shard's graph build (host pack of the edge lists into the upload ring, upload, COO -> CSR, SELL-16 count: 2 - 3 ms of
     # mostly GIL-free library calls) runs on a HELPER THREAD and a stream of its own while this thread builds the current shard's
-    # tables: the cold path is host-bound (6.5 ms of host work per 50-graph shard against 0.2 - 9 ms on the device), and this is
-    # the part of it that needs no interpreter.  Measured over ten 50-graph shards, best of three passes (scripts/dev/time_cold_modes.py):
-    # six scalars 8 800 -> 9 700 graphs/s, nine scalars 3 360 -> 4 670.  (The shard's feature uploads moved to the helper as well:
-    # 6 300 / 4 200 - its 4-MB copies hold the upload ring's lock against this thread's twenty small uploads.)
-    # Depth 1: everything on this thread, in place.
-    threaded = depth > 1
-    pool = build_stream = None
-    if threaded:
-        from concurrent.futures import ThreadPoolExecutor
-        pool, build_stream = ThreadPoolExecutor(max_workers=1), _side_stream(3)
-        dev_index = torch.cuda.current_device()
+    # tables: the cold path is host-bound, and this is the part of it that needs no interpreter (DESIGN 5: measured, as is
+    # the loss when the feature uploads move to the helper as well).  Depth 1: everything on this thread, in place.
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=1) if pipe.depth > 1 else contextlib.nullcontext() as pool:
+        build_stream = _side_stream(3) if pool is not None else None
 
-    def queue_build(shard):
-        from . import ops
-        torch.cuda.set_device(dev_index)
-        with torch.cuda.stream(build_stream):
-            return ops.GraphBatch([(i_[0], i_[1], j.n_nodes) for j, i_ in zip(shard[0], shard[1])], ops.COO_ADD_SELF_LOOPS, quad=True, defer=True)
+        def submit(shard):  # -> the future of the shard's graphs, or None: SweepBatch builds them
+            if pool is None or shard is None or shard[1] is None:
+                return None
+            return pool.submit(_queue_graphs, shard[0], shard[1], build_stream)
 
-    def submit(shard):
-        return pool.submit(queue_build, shard) if (threaded and shard is not None and shard[0] and shard[1] is not None) else None
-
-    try:
         it = iter(shards)
         nxt = next(it, None)
         fut = submit(nxt)
         b = 0
         while nxt is not None:
-            (jobs, inputs), cur_fut = nxt, fut
+            (jobs, inputs), gb = nxt, fut.result() if fut is not None else None
             nxt = next(it, None)
-            stream = streams[b % depth]
-            gb = None
-            if cur_fut is not None:
-                gb = cur_fut.result()
-                fut = submit(nxt)  # (the helper packs the next shard while this thread builds this one's tables)
-                with torch.cuda.stream(build_stream):
-                    gb.finish()
-                stream.wait_stream(build_stream)
-            else:
-                fut = submit(nxt)
-            with torch.cuda.stream(stream):
+            fut = submit(nxt)  # (the helper packs the next shard while this thread builds this one's tables)
+            if gb is not None:
+                _take_graphs(gb, build_stream, pipe.stream)
+            with torch.cuda.stream(pipe.stream):
                 sb = SweepBatch(jobs, n_feat=n_feat, symmetric=symmetric, gcn_hidden=0, inputs=inputs, graph_batch=gb)
                 if nine and sb.jobs:
                     sb.prepare_full(epochs=epochs, sample_max=sample_max, base_seed=first_seed + b)
                 sb.step()
                 if nine and sb.jobs:
                     sb.launch_full()
-            in_flight.append((sb, stream))
+            for *_, rows in pipe.push(b, sb):
+                yield rows
             b += 1
-            if len(in_flight) >= depth:
-                yield fetch()
-        while in_flight:
-            yield fetch()
-    finally:
-        if pool is not None:
-            pool.shutdown(wait=True)
+        while pipe.queue:
+            yield pipe.fetch()[3]
 
 
 def propagates(n_feat, jobs):
@@ -1368,84 +1381,57 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
     (SweepBatch(share=...)) and aggregate their own feature matrices over them.  Base-shard b runs on HIP stream b mod `depth`
     and its rows are fetched when `depth` are in flight.  Every (shard, base) computes the rows a stand-alone SweepBatch over
     the same inputs computes (tests/test_gpu_sweep.py)."""
-    from collections import deque
-    depth = max(1, int(depth))
-    streams = _pipe_streams(depth)
-    in_flight = deque()
-
-    def fetch():
-        si, bi, sb, stream = in_flight.popleft()
-        with torch.cuda.stream(stream):
-            rows = sb.full_metrics()
-        _count_kr(stats, sb)
-        return si, bi, rows, sb, stream
-
-    # TABLE REUSE inside a shard (round 5).  Bases on the propagated route aggregate the label columns only, so (i) they share ONE
-    # step - tables, outputs, six scalars (SweepBatch step twins) - and (ii) a base can take over the prepared batch of an earlier
-    # base with the same sample_max whose rows have been fetched: SweepBatch.rebind_features swaps the feature matrices and the
-    # node-set keys and keeps every job table (the kernels land in the same buffers).  The bases are visited in an order that puts
-    # bases of equal sample_max apart (with two base-shards in flight a batch is free again two visits later); rows carry their base
-    # index, and a batch stays on its stream.
-    # The NEXT shard's graphs are built ahead, on a stream of their own, as soon as this shard's first base is queued: the build's
-    # one read-back (GraphBatch.finish) then finds its data ready.  Built in place it waited behind whatever ran on the GPU at
-    # that moment - typically a regression launch that holds every CU for 5 - 9 ms - and the queue ran dry while the host stood
-    # still: a fifth of the sweep's wall clock had no kernel running.
+    pipe = _InFlight(depth, lambda sb: sb.full_metrics(), stats)
+    # TABLE REUSE inside a shard (DESIGN 5).  Bases on the propagated route aggregate the label columns only: they share ONE step
+    # (SweepBatch step twins), and a base takes over the prepared batch of an earlier base of equal sample_max whose rows have been
+    # fetched (rebind_features: new feature matrices and node-set keys, every job table kept).  _visit_order puts bases of equal
+    # sample_max apart, so that a batch is free again two visits later; rows carry their base index, and a batch stays on its stream.
+    # The NEXT shard's graphs are built ahead, on a stream of their own, as soon as this shard's first base is queued: built in place,
+    # their one read-back waited behind whatever held the GPU - typically a regression launch - while the queue ran dry.
     shards = list(shards)
     build_stream = _side_stream(3)
-    queued = {}
-
-    def queue_build(si_):
-        jobs_, gi_ = shards[si_]
-        if not jobs_:
-            return None
-        from . import ops
-        with torch.cuda.stream(build_stream):
-            return ops.GraphBatch([(src, dst, j.n_nodes) for j, (src, dst, _lab) in zip(jobs_, gi_)], ops.COO_ADD_SELF_LOOPS,
-                                  quad=True, defer=True)
-
     widths = [next(iter(feats.values())).shape[1] if feats else 0 for _name, feats, _sm in bases]
-    n = 0
+
+    def visit_order(lo):
+        return _visit_order([(True, bases[bi][2]) if lo[bi] else ("own", bi) for bi in range(len(bases))])
+
+    ahead = _queue_graphs(*shards[0], build_stream) if shards else None
     for si, (jobs, graph_inputs) in enumerate(shards):
-        first = first_lo = None
-        gb = queued.pop(si) if si in queued else queue_build(si)
-        early = None
+        gb, ahead, x_first = ahead, None, None
+        lo = [propagates(w, jobs) for w in widths]  # (labels-only bases - if every graph gets its SELL-16 copy)
+        order = visit_order(lo)
+        if order and lo[order[0]]:
+            # the FIRST base's feature matrices go into the upload ring while the GPU builds the shard's graphs: the copies (1.2 ms
+            # of library threads for cora's two 11-MB matrices) otherwise sit between the build's read-back and the first launch
+            from . import ops
+            with torch.cuda.stream(pipe.stream):
+                x_first = {s_: ops._h2d(np.ascontiguousarray(bases[order[0]][1][s_], np.float32), ops.require_gpu())
+                           for s_ in sorted({j.seed for j in jobs})}
         if gb is not None:
-            lo_guess = [propagates(w, jobs) for w in widths]  # (what `lo` below becomes when every graph has its SELL-16 copy)
-            first_bi = _visit_order([(lo_guess[bi], bases[bi][2]) if lo_guess[bi] else ("own", bi) for bi in range(len(bases))])[0]
-            if lo_guess[first_bi]:
-                # the FIRST base's feature matrices go into the upload ring while the GPU builds the shard's graphs: the copies (1.2 ms
-                # of library threads for cora's two 11-MB matrices) otherwise sit between the build's read-back and the first launch
-                from . import ops
-                with torch.cuda.stream(streams[n % depth]):
-                    early = (first_bi, {s_: ops._h2d(np.ascontiguousarray(bases[first_bi][1][s_], np.float32), ops.require_gpu())
-                                        for s_ in sorted({j.seed for j in jobs})})
-            with torch.cuda.stream(build_stream):
-                gb.finish()
-        # (decided AFTER the graphs are built when they are built ahead: a graph without a SELL-16 copy rules the propagated route out
-        # for the whole shard - its bases then aggregate at full width and take the dense Gram, as round 4 did)
-        quad_ok = gb is None or all(g.quad for g in gb.graphs)
-        lo = [quad_ok and propagates(w, jobs) for w in widths]
-        order = _visit_order([(lo[bi], bases[bi][2]) if lo[bi] else ("own", bi) for bi in range(len(bases))])
-        free = {}  # (sample_max, stream) -> a prepared labels-only batch whose rows have been fetched
+            _take_graphs(gb, build_stream, pipe.stream)
+            # (decided AFTER the build: a graph without a SELL-16 copy rules the propagated route out for the whole shard - its
+            # bases then aggregate at full width and take the dense Gram, as round 4 did)
+            if not all(g.quad for g in gb.graphs):
+                lo, x_first = [False] * len(bases), None
+                order = visit_order(lo)
+        # the shard's first batch builds the graphs (from gb) and owns them: the later bases share them and, pipelined, wait for
+        # the owner's stream
+        owner = owner_lo = owner_stream = None
+        free = {}  # (sample_max, stream) -> a prepared batch of this shard whose rows have been fetched, for rebind_features
         for bi in order:
             _name, feats, sample_max = bases[bi]
-            stream = streams[n % depth]
-            if first is not None and depth > 1:
-                stream.wait_stream(first_stream)  # (the shared graphs are built on the first base's stream)
-            elif first is None and gb is not None:
-                stream.wait_stream(build_stream)   # (... or, built ahead, on the build stream)
+            stream = pipe.stream
+            if owner is not None and pipe.depth > 1:
+                stream.wait_stream(owner_stream)
             with torch.cuda.stream(stream):
-                width = widths[bi]
-                key = (sample_max, stream.cuda_stream)
-                sb = free.pop(key, None) if (lo[bi] and jobs) else None
-                x_early = early[1] if (early is not None and early[0] == bi and lo[bi] and first is None) else None  # (uploaded on this stream)
+                sb = free.pop((sample_max, stream.cuda_stream), None) if lo[bi] else None
                 if sb is not None:
-                    sb.rebind_features(feats, width, first_seed + 1000 * bi)
+                    sb.rebind_features(feats, widths[bi], first_seed + 1000 * bi)
                 else:
                     inputs = [(src, dst, lab, feats[j.seed]) for j, (src, dst, lab) in zip(jobs, graph_inputs)]
-                    sb = SweepBatch(jobs, n_feat=width, symmetric=symmetric, gcn_hidden=0, inputs=inputs,
-                                    share=(first_lo or first) if lo[bi] else first, labels_only=lo[bi],
-                                    graph_batch=gb if first is None else None, x_dev=x_early)
+                    sb = SweepBatch(jobs, n_feat=widths[bi], symmetric=symmetric, gcn_hidden=0, inputs=inputs,
+                                    share=(owner_lo or owner) if lo[bi] else owner, labels_only=lo[bi],
+                                    graph_batch=gb if owner is None else None, x_dev=x_first if owner is None else None)
                     if sb.jobs:
                         # (the node sets are keyed by the base and the job's identity, not by where the job sits: a job draws the
                         # same sets in whichever shard / on whichever rank it runs - the N-rank sweep computes the one-GPU sweep's rows)
@@ -1453,22 +1439,19 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
                     sb.step()
                 if sb.jobs:
                     sb.launch_full()
-            if first is None:
-                first, first_stream = sb, stream
+            if owner is None:
+                owner, owner_stream = sb, stream
                 if si + 1 < len(shards):
-                    queued[si + 1] = queue_build(si + 1)
-            if first_lo is None and sb.labels_only:
-                first_lo = sb
-            in_flight.append((si, bi, sb, stream))
-            n += 1
-            if len(in_flight) >= depth:
-                done = fetch()
-                if (done[0] == si and done[3].labels_only and done[3].jobs and getattr(done[3], "kr_sets", None) is not None
-                        and getattr(done[3], "gram_route", None) == "propagate"):
-                    free[(done[3].kr_sample_max, done[4].cuda_stream)] = done[3]
-                yield done[:3]
-    while in_flight:
-        yield fetch()[:3]
+                    ahead = _queue_graphs(*shards[si + 1], build_stream)
+            if owner_lo is None and sb.labels_only:
+                owner_lo = sb
+            for (dsi, dbi), done, done_stream, rows in pipe.push((si, bi), sb):
+                if dsi == si and done.rebindable():
+                    free[(done.kr_sample_max, done_stream.cuda_stream)] = done
+                yield dsi, dbi, rows
+    while pipe.queue:
+        (dsi, dbi), _sb, _stream, rows = pipe.fetch()
+        yield dsi, dbi, rows
 
 
 def _visit_order(keys):
