@@ -30,6 +30,6 @@ print("unreachable objects found by the collector:", n)
 types = Counter(type(o).__name__ for o in gc.garbage)
 print(types.most_common(12))
 for o in gc.garbage:
-    if type(o).__name__ in ("SweepBatch", "SpmmBatch", "GraphBatch", "PropagatedGram", "KrBatch", "CsrGraph", "function", "cell", "dict") and not isinstance(o, dict):
+    if type(o).__name__ in ("SweepBatch", "KrPlan", "SpmmBatch", "GraphBatch", "PropagatedGram", "KrBatch", "CsrGraph", "function", "cell", "dict") and not isinstance(o, dict):
         refs = [type(r).__name__ for r in gc.get_referrers(o) if r is not gc.garbage][:6]
         print(type(o).__name__, getattr(o, "__qualname__", ""), "<-", refs)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Line-level host time of SweepBatch.__init__ / prepare_full inside the whole sweep (dev tool; sys.settrace on those two frames)."""
+"""Line-level host time of SweepBatch.__init__ and of KrPlan's construction inside the whole sweep (dev tool; sys.settrace on those
+frames)."""
 import os
 import sys
 import time
@@ -24,7 +25,8 @@ sweep.whole_sweep_rank(pairs, graph_of, feats, 1, 0)
 torch.cuda.synchronize()
 acc = defaultdict(float)
 last = {}
-targets = {sweep.SweepBatch.__init__.__code__, sweep.SweepBatch.prepare_full.__code__}
+targets = {f.__code__ for f in (sweep.SweepBatch.__init__, sweep.KrPlan.__init__, sweep.KrPlan._build_grams, sweep.KrPlan._group_jobs,
+                                 sweep.KrPlan._draw_sets, sweep.KrPlan._regression_table)}
 
 
 def tracer(frame, event, arg):

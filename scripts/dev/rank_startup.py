@@ -48,18 +48,21 @@ for rep in range(3):
         inputs = [(src, dst, lab, fx[j.seed]) for j, (src, dst, lab) in zip(mine, gi)]
         if pr and bi == 0:
             pr.enable()
-        sb = sweep.SweepBatch(mine, n_feat=width, gcn_hidden=0, inputs=inputs, labels_only=True, graph_batch=gb if bi == 0 else None,
-                              share=None if bi == 0 else first)
-        mark(f"SweepBatch {name} F={width} (feature upload, step tables)")
-        sb.prepare_full(epochs=100, sample_max=sample_max, base_seed=1000 * bi)
+        if bi == 0:  # (as run_bases does: the first wide base builds the labels-only batch, a further one is a plan on it)
+            first = sweep.SweepBatch(mine, n_feat=width, gcn_hidden=0, inputs=inputs, labels_only=True, graph_batch=gb)
+            x = first.x
+            mark(f"SweepBatch {name} F={width} (feature upload, step tables)")
+        else:
+            x = {s_: sweep._upload_features(fx[s_]) for s_ in first.x}
+            mark(f"features of {name} F={width} uploaded")
+        plan = sweep.KrPlan(first, x, width, epochs=100, sample_max=sample_max, base_seed=1000 * bi)
         if pr and bi == 0:
             pr.disable()
-        mark("prepare_full (Gram / propagation / set / regression tables)")
-        sb.step()
-        sb.launch_full()
-        mark("step + launch_full queued")
+        mark("KrPlan (Gram / propagation / set / regression tables)")
         if bi == 0:
-            first = sb
+            first.step()
+        plan.launch()
+        mark("step + plan launches queued")
     mark("device done", sync=True)
     print(f"pass {rep}")
     for (_n0, a), (n1, b) in zip(marks, marks[1:]):

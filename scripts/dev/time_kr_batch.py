@@ -19,7 +19,7 @@ sb.prepare_full(epochs=epochs, sample_max=500)
 sb.step()
 sb.kr_sets.launch()
 sb.gram.launch()
-sb.ge.launch()
+sb.plan.ge.launch()
 torch.cuda.synchronize()
 for _ in range(2):
     sb.kr.launch()

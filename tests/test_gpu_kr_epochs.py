@@ -176,24 +176,24 @@ def test_batched_sweep_ridge_against_the_pseudo_inverse_at_scale():
         torch.cuda.synchronize()
         rows_dev = sb.full_metrics(ridge="device").numpy()
         acc_dev = sb.kr_acc.copy().reshape(-1)                                 # problem order [job, clf, epoch, kernel]
-        ridged = sb.kr_ridged_mask().cpu().numpy().reshape(-1)                 # (the same order: every job its own sample here)
-        deflated = sb.kr_deflated_mask().cpu().numpy().reshape(-1) & ~ridged
+        ridged = sb.plan.kr_ridged_mask().cpu().numpy().reshape(-1)                 # (the same order: every job its own sample here)
+        deflated = sb.plan.kr_deflated_mask().cpu().numpy().reshape(-1) & ~ridged
         n_val = float(sb.kr_val.shape[2])
         flagged = np.flatnonzero(ridged)
         others = rng.choice(np.flatnonzero(~ridged & ~deflated), 150, replace=False)
         defl = np.flatnonzero(deflated)
-        host_d = sb.pinv_accuracies(defl)                                      # EVERY deflated block the reference's way
+        host_d = sb.plan.pinv_accuracies(defl)                                      # EVERY deflated block the reference's way
         d_defl.append(np.abs(acc_dev[defl].astype(np.float64) - host_d) * n_val)
         n_deflated += len(defl)
         t0 = time.perf_counter()
-        host_f = sb.pinv_accuracies(flagged)                                   # the reference's way, kernels included
+        host_f = sb.plan.pinv_accuracies(flagged)                                   # the reference's way, kernels included
         t_host = time.perf_counter() - t0
-        host_o = sb.pinv_accuracies(others)
+        host_o = sb.plan.pinv_accuracies(others)
         d_ridged.append(np.abs(acc_dev[flagged].astype(np.float64) - host_f) * n_val)
         d_pd.append(np.abs(acc_dev[others].astype(np.float64) - host_o) * n_val)
         src_, host_ = (flagged, host_f) if len(flagged) else (defl, host_d)    # ~120 singular blocks: pinv on the DEVICE kernel's blocks
         some = src_[:: max(1, len(src_) // 120)]
-        d_devgram.append(np.abs(sb.pinv_accuracies(some, kernels="device").astype(np.float64) - host_[:: max(1, len(src_) // 120)]) * n_val)
+        d_devgram.append(np.abs(sb.plan.pinv_accuracies(some, kernels="device").astype(np.float64) - host_[:: max(1, len(src_) // 120)]) * n_val)
         n_regressions, n_flagged = n_regressions + ridged.size, n_flagged + len(flagged)
         rec = {"ridged": int(len(flagged)), "total": int(ridged.size), "host_seconds_flagged": t_host}
         if draw == 0:  # the patch itself: flagged blocks carry the host answer, the others the device answer; p-values follow

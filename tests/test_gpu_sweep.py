@@ -128,7 +128,7 @@ def test_whole_sweep_over_feature_bases_equals_stand_alone_batches():
 
 def test_table_reuse_across_wide_feature_bases_equals_stand_alone_batches_at_every_depth(monkeypatch):
     """run_bases over several WIDE feature bases (the propagated route: label columns only in the aggregation): the bases of a shard
-    share one step (step twins), a base takes over the prepared batch of an earlier base of equal sample_max (rebind_features: same
+    are plans on one labels-only batch (one step), a base takes over the plan of an earlier base of equal sample_max (rebind_features: same
     buffers, new features, new node-set keys) and the bases are visited out of order (rows arrive in that order, tagged with their
     base) - every (shard, base) still gives the rows of a stand-alone SweepBatch over the same inputs, bit for bit, pipelined two
     deep, unpipelined or with three base-shards in flight."""
@@ -144,17 +144,25 @@ def test_table_reuse_across_wide_feature_bases_equals_stand_alone_batches_at_eve
         jobs = sweep.make_jobs(lv, samples, k=4, n_nodes=600)
         shards.append((jobs, [graphs[(j.h, j.seed)] for j in jobs]))
     rebinds, twins = [], []
-    orig_rebind, orig_twin = sweep.SweepBatch.rebind_features, sweep.SweepBatch._init_step_twin
-    monkeypatch.setattr(sweep.SweepBatch, "rebind_features", lambda self, *a, **k: (rebinds.append(a[1]), orig_rebind(self, *a, **k))[1])
-    monkeypatch.setattr(sweep.SweepBatch, "_init_step_twin", lambda self, *a, **k: (twins.append(a[2]), orig_twin(self, *a, **k))[1])
+    orig_rebind, orig_plan = sweep.KrPlan.rebind_features, sweep.KrPlan.__init__
+    monkeypatch.setattr(sweep.KrPlan, "rebind_features", lambda self, *a, **k: (rebinds.append(a[1]), orig_rebind(self, *a, **k))[1])
+    planned = []  # the batches a plan has been built on: a further plan on one of them shares that batch's step
+
+    def plan_init(self, batch, x, n_feat, **k):
+        if any(b is batch for b in planned):
+            assert batch.labels_only
+            twins.append(n_feat)
+        planned.append(batch)
+        orig_plan(self, batch, x, n_feat, **k)
+    monkeypatch.setattr(sweep.KrPlan, "__init__", plan_init)
     order, got = [], {}
     for si, bi, rows in sweep.run_bases(shards, bases, epochs=6, depth=2, first_seed=5):
         order.append((si, bi))
         got[(si, bi)] = rows
     assert order == [(si, bi) for si in range(2) for bi in (0, 3, 1, 2, 4, 5)]  # (the visit order, shard by shard)
     assert sorted(rebinds) == [650, 650, 700, 700, 800, 800] and sorted(twins) == [720, 720]  # per shard: p2, p4, p5 rebound; p3 a twin of p1
-    monkeypatch.setattr(sweep.SweepBatch, "rebind_features", orig_rebind)
-    monkeypatch.setattr(sweep.SweepBatch, "_init_step_twin", orig_twin)
+    monkeypatch.setattr(sweep.KrPlan, "rebind_features", orig_rebind)
+    monkeypatch.setattr(sweep.KrPlan, "__init__", orig_plan)
     for (si, bi), rows in got.items():
         jobs, gi = shards[si]
         _name, feats, sample_max = bases[bi]
@@ -258,7 +266,7 @@ def test_common_sets_per_sample_share_the_raw_feature_regressions(monkeypatch):
         totals[mode] = (sb.kr.n_jobs, sb.kr_total, sb.kr_set_mode)
         if mode == "sample":
             assert sb.kr_group.tolist() == [0, 0, 0, 1, 1, 1] and sb.kr_rep.tolist() == [0, 3]
-            assert np.array_equal(sb.kr_accuracy().cpu().numpy(), accs[mode])
+            assert np.array_equal(sb.plan.kr_accuracy().cpu().numpy(), accs[mode])
             tr = sb.kr_train.cpu().numpy()
             assert tr.shape[:2] == (2 * 2, epochs) and not np.array_equal(tr[0], tr[2])  # one sequence per (sample, classifier)
     J = len(jobs)
@@ -467,7 +475,7 @@ def test_sweep_all_nine_scalars_against_golden():
     # these epochs (tests/golden/kr_epochs.npz holds 8 epochs of the same seed: the first 4 are this run's): within 2 of the
     # 200 validation rows; the p-values within what that implies for these accuracies (_golden.p_tolerance)
     from _golden import load_kr, p_tolerance
-    acc = sb.kr_accuracy().cpu().numpy().astype(np.float64)
+    acc = sb.plan.kr_accuracy().cpu().numpy().astype(np.float64)
     assert acc.shape == (len(jobs), 2, 4, 2)
     for ji, (name, r, g0) in enumerate(zip(names, rows, gold)):
         kr = load_kr(name)

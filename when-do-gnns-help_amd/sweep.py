@@ -11,6 +11,7 @@ only the job table (broadcast from rank 0) and the per-job result rows (all_gath
 """
 import contextlib
 import os
+import weakref
 from collections import deque
 from dataclasses import dataclass
 
@@ -280,6 +281,24 @@ def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_
     return torch.cat(keys), torch.cat(rows)
 
 
+def _upload_features(host):
+    """a feature matrix ([n, F] host array) -> fp32 device tensor, through the upload ring on the current stream"""
+    from . import ops
+    return ops._h2d(np.ascontiguousarray(host, np.float32), ops.require_gpu())
+
+
+def _route_propagates(n_feat, jobs, force=False):
+    """whether features of this width over these jobs take the propagated route under WDG_GRAM_ROUTE (KrPlan._build_grams): graphs
+    of one size on the quad-row kernel, and the route asked for, `auto` from F = 640 on, or `force` (a labels-only step).  The
+    caller adds what only it knows: propagates() a labels-only step's limits, the plan whether every graph got its SELL-16 copy."""
+    from . import ops
+    route = os.environ.get("WDG_GRAM_ROUTE", "auto")
+    if route not in ("auto", "direct", "propagate"):
+        raise ValueError(f"WDG_GRAM_ROUTE={route!r}")
+    return (len({j.n_nodes for j in jobs}) == 1 and not ops.quad_disabled()
+            and (force or route == "propagate" or (route == "auto" and n_feat >= 640)))
+
+
 class _PrelaunchedGram:
     """A GramBatch launched at construction (prepare_full queues the raw features' kernels before it builds the propagation's and
     the regressions' tables): the first launch() waits for the event recorded behind that launch - free on the same stream, and
@@ -336,9 +355,8 @@ class SweepBatch:
         x_dev: {seed: [n, n_feat] fp32 device tensor} - the feature matrices, uploaded already (run_bases uploads the first
         base's while the shard's graphs are built).
         labels_only: aggregate the one-hot LABEL columns only (one 16-feature group: everything the six step scalars need); the
-        feature matrices are uploaded for the kernel-regression metric, whose aggregated-feature kernels then come by propagation
-        (prepare_full: K(A_hat X) = A_hat K(X) A_hat^T) - the reference's sweep over its wide feature bases (F up to 3 703) never
-        needs A_hat X itself.  Needs gcn_hidden = 0; `y` aggregates the features on demand (the host re-solve of flagged blocks).
+        feature matrices are uploaded for the batch's KrPlan, whose aggregated-feature kernels then come by propagation (K(A_hat X) =
+        A_hat K(X) A_hat^T: the sweep over the wide feature bases never needs A_hat X itself).  Needs gcn_hidden = 0; `y` is the plan's.
 
         The aggregated features are kept TILED by 16-feature groups (ops.Tiled: y_agg[i].t is [groups, n, 16]) when everything
         that reads them inside the step can - the label columns of LAS as a strided view, the fused transform through
@@ -350,7 +368,6 @@ class SweepBatch:
         from . import ops
         self.ops = ops
         self.jobs = list(jobs)
-        self.inputs = inputs
         dev = ops.require_gpu()
         self.n_feat = n_feat
         self.symmetric = symmetric
@@ -362,42 +379,30 @@ class SweepBatch:
         ride = os.environ.get("WDG_SWEEP_RIDE_LABELS", "1") != "0" and n_classes > 0
         self.labels_only = bool(labels_only and ride and not gcn_hidden and n_classes <= 16)
         lab_col = 0 if self.labels_only else n_feat  # first label column of [X | onehot | 0]
-        self.lab_col = lab_col
         # rows of [X | onehot | 0] and of Y are padded to whole 16-feature groups: every 64-byte row segment an item stores
         # is then 64-byte aligned (one L2 write request instead of two: 220 against 225 us per launch with an alignment of 4)
         self.agg_feat = (lab_col + n_classes + 15) // 16 * 16 if ride else n_feat
         self.alg_feat = lab_col + n_classes if ride else n_feat  # columns that carry data (byte accounting: no padding)
         build = build or "batched"
-        # A STEP TWIN: with labels_only the step aggregates [onehot(labels) | 0] and nothing of the features, so its tables, its
-        # outputs and its six scalars depend on the graphs and their labels only.  A batch that shares the graphs of another
-        # labels-only batch (the feature bases of one shard, run_bases) shares that batch's whole step - job tables, Y, counters - and
-        # uploads its feature matrices for the kernel-regression metric, nothing else; its step() launches nothing (the owner's has
-        # run on a stream this one waits for).
-        self.step_owner = None
-        if (share is not None and self.labels_only and getattr(share, "labels_only", False) and share.agg_feat == self.agg_feat
-                and share.symmetric == symmetric and len(share.jobs) == len(self.jobs)):
-            self._init_step_twin(share.step_owner or share, inputs, n_feat, feature_seed, dev, x_dev)
-            return
         feats, self.graphs, self.dinv, self.labels, self._y = {}, [], [], [], []
         self.y_agg, seed_labels = [], {}
         self.tiled_y, self._y_rm, self._untile_each_step, self._y_at = False, None, False, -1
+        self.y_pool = self._class_prop = self.plan = self._graph = self._step_graph = None  # (plan: the batch's own KrPlan)
         # pass 1 (host only): every job's edge lists and labels; the graph build of the whole shard is QUEUED before the feature
         # matrices are touched, so that the GPU builds (1.8 ms of kernels per 50-graph shard) while the host copies 20 MB of features
         # into the upload ring - GraphBatch.finish(), the shard's one read-back, then finds its data ready
-        coos, labs_host, x_hosts, x_feat = [], [], [], {}
+        coos, labs_host, x_feat = [], [], {}
         for ji, j in enumerate(self.jobs):
             if inputs is not None:
-                src, dst, lab, x_host = inputs[ji]
+                src, dst, lab = inputs[ji][:3]
                 lab = np.asarray(lab)
             elif share is not None:
                 src = dst = None
-                lab, x_host = np.asarray(share.labels_host[ji]).astype(np.int64), None
+                lab = np.asarray(share.labels_host[ji]).astype(np.int64)
             else:
                 src, dst, lab = synth.regular_graph(j.n_nodes, j.n_classes, j.k, j.h, j.seed)
-                x_host = None
             coos.append((src, dst, j.n_nodes))
             labs_host.append(lab)
-            x_hosts.append(x_host)
         mode = ops.NORM_SYM if symmetric else ops.NORM_RW
         if share is None and build == "batched":
             # A + I of every graph (synthetic_plot.py:92) in one build, the degrees of all of them in one launch
@@ -405,9 +410,9 @@ class SweepBatch:
         for ji, j in enumerate(self.jobs):
             lab = labs_host[ji]
             if j.seed not in feats:
-                x_host = x_hosts[ji]
-                x = x_dev[j.seed] if x_dev is not None else ops._h2d(
-                    synth.features(j.n_nodes, n_feat, j.seed + feature_seed) if x_host is None else np.ascontiguousarray(x_host, np.float32), dev)
+                x_host = inputs[ji][3] if inputs is not None else None
+                x = x_dev[j.seed] if x_dev is not None else _upload_features(
+                    synth.features(j.n_nodes, n_feat, j.seed + feature_seed) if x_host is None else x_host)
                 if ride:
                     # [X | onehot(labels) | 0]: the label block is laid out on the host and uploaded like any other array (an
                     # index assignment `xa[arange, labels] = 1` on the device SYNCHRONISES the host with the stream - 3 ms a
@@ -460,8 +465,8 @@ class SweepBatch:
                 self.y_agg.append(torch.empty((j.n_nodes, self.agg_feat), dtype=torch.float32, device=dev))
                 self._y.append(self.y_agg[-1][:, :n_feat])  # the feature part (a view: leading dimension agg_feat)
         self.x_agg = feats                                        # what the aggregation reads: [X | onehot | 0] (labels_only: [onehot | 0])
-        self.x = x_feat if self.labels_only else {s: x[:, :n_feat] for s, x in feats.items()}  # the features proper
-        self._y_lazy = None
+        # the features proper (a labels-only batch: the matrices it was built with, for its own plan - the step never reads them)
+        self.x = x_feat if self.labels_only else {s: x[:, :n_feat] for s, x in feats.items()}
         # A + I has unit values except a doubled pre-existing loop; the generator emits no loops -> pattern only
         entries = [(g, self.x_agg[j.seed], y, d, d if symmetric else None, False)
                    for j, g, y, d in zip(self.jobs, self.graphs, self.y_agg, self.dinv)]
@@ -472,9 +477,6 @@ class SweepBatch:
         self.n_classes = n_classes
         self.stats = ops.StatsBatch(self.graphs, self.labels, n_classes)
         self.edges = sum(g.nnz for g in self.graphs)
-
-        def scale(d):
-            return d if symmetric else None
 
         # aggregation homophily (soft LAS, synthetic_plot.py:106): H = A_hat Z with one-hot Z, then W = H (H^T Y)
         self.h_las = []
@@ -491,7 +493,7 @@ class SweepBatch:
                 onehot = torch.eye(n_classes, device=dev)[lab.long()].contiguous()
                 self.h_las.append(torch.empty((j.n_nodes, n_classes), dtype=torch.float32, device=dev))
                 las_entries.append((self.graphs[len(las_entries)], onehot, self.h_las[-1]))
-            self.spmm_las = ops.SpmmBatch([(g, z, h, d, scale(d), False) for (g, z, h), d in zip(las_entries, self.dinv)])
+            self.spmm_las = ops.SpmmBatch([(g, z, h, d, d if symmetric else None, False) for (g, z, h), d in zip(las_entries, self.dinv)])
         # the integer counters of the step (edge / node / class homophily, ...) ride in the label columns as well: H = D^-1 (A + I)
         # onehot holds every node's neighbour-class counts, so the LAS launch derives them in its per-row pass and the separate
         # pass over the edges (wdg_edge_label_stats_batched, 62 us beside nothing when there is no GCN chain) leaves the step.
@@ -523,31 +525,11 @@ class SweepBatch:
                             mlp=ops.Mlp2Batch(mlp, relu=True) if fused else None,
                             gemm1=None if fused else ops.GemmBatch([(y, a, h, None) for y, a, h in zip(self._y, w0, hid)], relu=True),
                             gemm2=None if fused else ops.GemmBatch([(h, b, z, None) for h, b, z in zip(hid, w1, z2)]),
-                            spmm=ops.SpmmBatch([(g, z, o, d, scale(d), False)
+                            spmm=ops.SpmmBatch([(g, z, o, d, d if symmetric else None, False)
                                                 for g, z, o, d in zip(self.graphs, z2, out, self.dinv)]))
 
         if tune or os.environ.get("WDG_QUAD_TUNE", "") == "1":
             self.tune()
-
-    def _init_step_twin(self, owner, inputs, n_feat, feature_seed, dev, x_dev=None):
-        """the rest of __init__ for a step twin (see there): the feature matrices of this base, everything else the owner's"""
-        ops = self.ops
-        self.step_owner = owner
-        for name in ("graphs", "dinv", "labels", "labels_host", "y_agg", "_y", "x_agg", "spmm", "stats", "las", "h_las", "spmm_las",
-                     "edges", "n_classes", "tiled_y", "derive_counts", "gcn", "side", "_fork", "graph_batch", "y_pool"):
-            if hasattr(owner, name):
-                setattr(self, name, getattr(owner, name))
-        self._y_rm, self._untile_each_step, self._y_at, self._y_lazy = None, False, -1, None
-        x_feat = {}
-        for ji, j in enumerate(self.jobs):
-            if j.seed in x_feat:
-                continue
-            x_host = inputs[ji][3] if inputs is not None else None
-            x_feat[j.seed] = x_dev[j.seed] if x_dev is not None else ops._h2d(
-                synth.features(j.n_nodes, n_feat, j.seed + feature_seed) if x_host is None else np.ascontiguousarray(x_host, np.float32), dev)
-            if inputs is not None and not np.array_equal(np.asarray(inputs[ji][2]), np.asarray(owner.labels_host[ji])):
-                raise ValueError("SweepBatch(share=...): the sharing batch's labels differ from the owner's")
-        self.x = x_feat
 
     # -- the aggregated features as row-major matrices ------------------------------------------------------------
     @property
@@ -555,11 +537,10 @@ class SweepBatch:
         """list of [n, n_feat] row-major tensors, one per job (views of the aggregation's output - or, with a tiled Y, of a
         row-major copy: stable addresses, so job tables built on them stay valid; untiled here when an aggregation has run since
         the last copy, i.e. once per aggregation however often the property is read)"""
-        if self.labels_only:  # the step aggregates the label columns only: the features' aggregation on demand, once
-            if self._y_lazy is None:
-                sc = (lambda d: d) if self.symmetric else (lambda d: None)
-                self._y_lazy = [self.ops.spmm(g, self.x[j.seed], row_scale=d, col_scale=sc(d)) for j, g, d in zip(self.jobs, self.graphs, self.dinv)]
-            return self._y_lazy
+        if self.labels_only:  # the step aggregates the label columns only: the plan aggregates its features on demand
+            if self.plan is None:
+                raise AttributeError("SweepBatch.y of a labels-only batch: the features belong to its plan, call prepare_full() first")
+            return self.plan.y
         if self.tiled_y:
             if self._y_at != self.spmm.n_launches or self._y_rm is None:
                 self.untile()
@@ -660,8 +641,6 @@ class SweepBatch:
     def step(self):
         """one pass of the hot path over the batch (synthetic_plot.py:92-108 minus the kernel-regression metric):
         feature aggregation, integer edge/label pass, label aggregation + LAS, GCN-2 forward"""
-        if self.step_owner is not None:  # a step twin: the owner's step computed these outputs (same graphs, same labels)
-            return
         self.spmm.launch()        # Y = A_hat X                       (F = n_feat)   dominant kernel
         if self._untile_each_step:  # (a tiled Y and row-major readers behind the step: prepare_full's Grams, training)
             self.untile()
@@ -686,8 +665,6 @@ class SweepBatch:
             main.wait_stream(self.side)
         else:
             self._metric_chain()
-            if self.gcn:
-                self._gcn_chain()
 
     def capture_rest(self):
         """step_rest() as one hipGraph (all streams, fork / join included): replaying it replaces eight launches and the
@@ -744,23 +721,15 @@ class SweepBatch:
 
     def _class_proportions(self):
         """[jobs, C] fp32: every job's class proportions (fixed per batch; counted where the labels already are)"""
-        if getattr(self, "_class_prop", None) is None:
+        if self._class_prop is None:
             st, c = self.stats, self.stats.c
-            host = getattr(self, "labels_host", None)
-            if host is not None and len(host) == st.n_jobs:
-                memo = {}  # (the jobs of a sample share their label array: counted once per distinct array)
-
-                def count(l):
-                    if id(l) not in memo:
-                        a = np.asarray(l)
-                        memo[id(l)] = np.bincount(a[(a >= 0) & (a < c)], minlength=c)[:c]
-                    return memo[id(l)]
-                cnt = np.stack([count(l) for l in host])
-                counts = self.ops._h2d(cnt.astype(np.float32), st.counters.device)  # (never a blocking pageable copy between launches)
-            else:
-                n = st.max_rows
-                lab = torch.stack([torch.nn.functional.pad(l, (0, n - l.shape[0]), value=-1) for l in st.labels]) if st.n_jobs else torch.zeros((0, n))
-                counts = torch.stack([(lab == i).sum(1) for i in range(c)], 1).to(torch.float32)
+            memo = {}  # (the jobs of a sample share their label array: counted once per distinct array)
+            for l in self.labels_host:
+                if id(l) not in memo:
+                    a = np.asarray(l)
+                    memo[id(l)] = np.bincount(a[(a >= 0) & (a < c)], minlength=c)[:c]
+            cnt = np.stack([memo[id(l)] for l in self.labels_host])
+            counts = self.ops._h2d(cnt.astype(np.float32), st.counters.device)  # (never a blocking pageable copy between launches)
             self._class_prop = (counts / counts.sum(1, keepdim=True)).contiguous()
         return self._class_prop
 
@@ -808,103 +777,139 @@ class SweepBatch:
         soft_las = self.las.counts[:, 0].to(torch.float32) / self.las.n
         return torch.stack([edge, node, cls, adj, li, soft_las], 1)
 
-    # -- the remaining three scalars: generalized edge homophily + the kernel-regression p-values ------
+    def row_major_y(self):
+        """`y` for a job table that keeps its addresses: a tiled Y's copy is refreshed behind every aggregation from here on"""
+        self._untile_each_step = self.tiled_y
+        return self.y
+
+    # -- the remaining three scalars: the batch's own KrPlan over the features it was built with ------------------------------
     def prepare_full(self, epochs=100, sample_max=500, seed_of=None, sampler=None, base_seed=0, sets=None):
-        """Set up the batched kernel-regression metric for every job: the Gram / arc-cosine kernels of the aggregated features
-        (per job) and of the raw features (per feature matrix) - all nodes, once -, and, per job x classifier (kernel_reg0 /
-        kernel_reg1) x epoch, the train / validation node sets; both kernels of an epoch share its node sets.
-        sampler "device" (default; WDG_KR_SAMPLER): the sets of all epochs are drawn by ONE launch (ops.KrSets,
-        wdg_kr_sample_sets: Philox4x32-10 keyed by base_seed, job and classifier - the reference's distribution, a documented
-        generator) in launch_full(), inside the clock of a cold sweep.  sampler "host" (implied by seed_of): the reference's
-        own routine on torch's CPU generator seeded with seed_of(job index, classifier index) (default 1000 job + classifier) -
-        bit for bit the reference's sets (the golden tests), ~40 ms of host time per (job, classifier) at 100 epochs.
-        sets (device sampler only; WDG_SWEEP_KR_SETS): whose node sets an epoch's regressions use.
-          "job" (default, the reference's own draws: utils/homophily_metrics.py:267-283 draws per call) - independent sets per job, keyed
-                   by the job's identity: 400 regressions per job at 100 epochs.
-          "sample" - COMMON RANDOM SETS per sample (an optimisation, opt-in since round 6: a CHANGED ESTIMATOR is not a default): the jobs of a shard that share a feature matrix AND a label vector (the
-                   homophily levels of one sample, synthetic_plot.py:78-91) draw ONE sequence of sets per (sample, classifier), keyed
-                   by the sample's identity.  Every job's (X_results, G_results) pair has exactly the distribution of the reference's
-                   independent draws (both accuracies of an epoch share the epoch's sets there too, utils/homophily_metrics.py:
-                   279-297); only jobs of DIFFERENT homophily levels become correlated, which none of the reference's outputs (mean /
-                   std over the ten samples of a level, synthetic_plot.py:112-128) measures.  The raw features' regressions of such jobs
-                   are then the same problem - same kernel, same sets, same labels - and are solved ONCE per (sample, classifier,
-                   epoch) instead of once per job: 200 + 200 / (levels per shard) regressions per job instead of 400 (the whole sweep:
-                   348 000 instead of 672 000, 0.30 instead of 0.47 s on one GPU)."""
-        from .utils.util_funcs import kernel_regression_epoch_indices
-        ops = self.ops
-        dev = self.graphs[0].device if self.graphs else ops.require_gpu()
-        seeds = list(self.x)
-        J = len(self.jobs)
+        """the batch's own KrPlan (arguments: see there); launch_full(), full_metrics() and the names of _PLAN_STATE forward to it.
+        (It gets a proxy of the batch: a reference cycle would leave a finished batch's gigabytes to the cyclic collector.)"""
+        self.plan = KrPlan(weakref.proxy(self), self.x, self.n_feat, epochs=epochs, sample_max=sample_max, seed_of=seed_of,
+                           sampler=sampler, base_seed=base_seed, sets=sets)
+
+    def launch_full(self, sample_events=None):
+        """KrPlan.launch of the batch's plan (after the aggregation: on the direct route it reads Y)"""
+        self.plan.launch(sample_events)
+
+    def full_metrics(self, ridge=None):
+        """[jobs, 9] fp64: KrPlan.full_metrics of the batch's plan"""
+        return self.plan.full_metrics(ridge)
+
+    _PLAN_STATE = frozenset(("kr", "gram", "gram_route", "kr_train", "kr_val", "kr_sets", "kr_set_mode", "kr_ridged", "kr_deflated",
+                             "kr_total", "kr_pinv_seconds", "kr_acc", "kr_group", "kr_rep"))  # what callers read on the batch
+
+    def __getattr__(self, name):  # (reached only for a name the batch itself does not have)
+        if name in SweepBatch._PLAN_STATE:
+            plan = self.__dict__.get("plan")
+            if plan is None:
+                raise AttributeError(f"SweepBatch.{name} belongs to the batch's KrPlan: call prepare_full() first")
+            return vars(plan)[name]
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+
+class KrPlan:
+    """The three extra scalars of ONE FEATURE BASE over a step batch: generalized edge homophily and the two
+    kernel-regression p-values.  It reads graphs, degrees, labels and the six step scalars of `batch` (a SweepBatch; on the direct
+    route its aggregated features too) and owns the rest: the feature matrices `x` ({seed: [n, n_feat] fp32 device tensor}), the
+    Gram / propagated-Gram tables, the edge cosines, the node sets, the regression table and the index from solved problems back to
+    jobs.  SweepBatch.prepare_full builds a batch's own plan; the wide bases of a shard are SEVERAL plans on one labels-only batch
+    (run_bases), which they keep alive.
+    sampler "device" (default; WDG_KR_SAMPLER): the sets of all epochs are drawn by ONE launch (ops.KrSets: Philox4x32-10 keyed by
+    base_seed, job and classifier - the reference's distribution) in launch(), inside the clock of a cold sweep.  sampler "host"
+    (implied by seed_of): the reference's own routine on torch's CPU generator seeded with seed_of(job index, classifier index)
+    (default 1000 job + classifier) - bit for bit the reference's sets (the golden tests), ~40 ms of host time per (job, classifier).
+    sets (device sampler only; WDG_SWEEP_KR_SETS): whose node sets an epoch's regressions use.
+      "job" (default: the reference draws per call, utils/homophily_metrics.py:267-283) - independent sets per job, keyed by its identity.
+      "sample" - COMMON RANDOM SETS per sample (opt-in: a changed estimator is not a default; DESIGN 5 argues why every job keeps the
+               reference's distribution): the jobs of a shard that share a feature matrix AND a label vector (the homophily levels
+               of one sample, synthetic_plot.py:78-91) draw ONE sequence of sets per (sample, classifier), keyed by the sample's
+               identity.  Their raw features' regressions are then the same problem and are solved ONCE per (sample, classifier,
+               epoch): 200 + 200 / (levels per shard) regressions per job instead of 400."""
+
+    def __init__(self, batch, x, n_feat, epochs=100, sample_max=500, seed_of=None, sampler=None, base_seed=0, sets=None):
+        self.batch, self.ops, self.x, self.n_feat = batch, batch.ops, x, n_feat
         self.kr_epochs, self.kr_sample_max = epochs, sample_max
-        sampler = "host" if seed_of is not None else (sampler or os.environ.get("WDG_KR_SAMPLER", "device"))
-        if J == 0:  # an empty shard
-            self.gram, self.ge, self.kr_sets = ops.GramBatch([]), ops.EdgeGramBatch([]), None
-            self.kr = ops.KrBatch([], max(self.n_classes, 1))
+        self.gram_route = self.kr_set_mode = self.kr_sets = self.kr_train = self.kr_val = self.kr_group = self.kr_rep = None
+        self.kr_index = self.kr_canonical = self._x_slot = self._n_tr = self._n_va = self._kr_rebind = None
+        # filled later (the sampler's stream at the first launch(): _side_stream is keyed by the stream that is current THEN)
+        self._kr_index_dev = self._side_stream = self._y_lazy = self.kr_acc = None
+        self.kr_ridged, self.kr_deflated, self.kr_total, self.kr_pinv_seconds = 0, 0, 0, 0.0
+        if not batch.jobs:  # an empty shard
+            self.gram, self.ge = self.ops.GramBatch([]), self.ops.EdgeGramBatch([])
+            self.kr = self.ops.KrBatch([], max(batch.n_classes, 1))
             return
-        if self.n_classes > ops.KrBatch.MAX_CLASSES:
-            raise ValueError(f"SweepBatch.prepare_full: {self.n_classes} classes, the device solver holds {ops.KrBatch.MAX_CLASSES}; "
+        if batch.n_classes > self.ops.KrBatch.MAX_CLASSES:
+            raise ValueError(f"KrPlan: {batch.n_classes} classes, the device solver holds {self.ops.KrBatch.MAX_CLASSES}; "
                              "use utils.homophily_metrics.classifier_based_performance_metric (host path) per graph")
-        # kernels: [aggregated features of every job] + [raw features of every feature matrix], linear and arc-cosine.
-        # Two routes to the aggregated features' kernels (WDG_GRAM_ROUTE=direct|propagate|auto):
-        #   direct     the Gram of Y = A_hat X, one dense n x n x F product per job (ops.GramBatch over Y);
-        #   propagate  K_linear(Y) = A_hat K_linear(X) A_hat^T: two aggregations with n "features" over the raw features' half Gram
-        #              (ops.PropagatedGram) - 2 nnz n flops each instead of n^2 F; auto takes it from F = 640 on (the reference's
-        #              bases: every one but pubmed), where the dense product costs 2 - 7 x the propagation (round 5).
-        route = os.environ.get("WDG_GRAM_ROUTE", "auto")
-        if route not in ("auto", "direct", "propagate"):
-            raise ValueError(f"WDG_GRAM_ROUTE={route!r}")
-        nodes = {j.n_nodes for j in self.jobs}
-        can = len(nodes) == 1 and not ops.quad_disabled() and all(g.ensure_quad() for g in self.graphs)
-        self.gram_route = "propagate" if can and (route == "propagate" or (route == "auto" and self.n_feat >= 640) or self.labels_only) else "direct"
-        # (a labels-only batch whose graphs cannot take the propagated route - one graph of the shard without a SELL-16 copy: padding
-        # beyond 4 x, graphs.py ensure_quad - falls back to the direct route over `y`, the features' aggregation made on demand graph by
-        # graph: slower, same rows; round 5 raised here and a single hub-heavy graph aborted the whole sweep - ADVICE r05)
-        x_slot = {s: J + i for i, s in enumerate(seeds)}
+        sampler = "host" if seed_of is not None else (sampler or os.environ.get("WDG_KR_SAMPLER", "device"))
+        self.gram, self.ge = self._build_grams()
+        self._group_jobs(sets, sampler)
+        self.kr_train, self.kr_val = self._draw_sets(sampler, seed_of, base_seed)
+        self.kr = self._regression_table()
+
+    def _build_grams(self):
+        """-> (gram, ge): the kernels [aggregated features of every job] + [raw features of every feature matrix], linear and
+        arc-cosine, and the edge cosines over the raw features'; sets gram_route and every job's slot of raw-features kernel.
+        Two routes to the aggregated features' kernels (WDG_GRAM_ROUTE=direct|propagate|auto):
+          direct     the Gram of Y = A_hat X, one dense n x n x F product per job (ops.GramBatch over Y);
+          propagate  K_linear(Y) = A_hat K_linear(X) A_hat^T: two aggregations with n "features" over the raw features' half Gram
+                     (ops.PropagatedGram) - 2 nnz n flops each instead of n^2 F; auto takes it from F = 640 on (_route_propagates).
+        A labels-only batch with a graph that has no SELL-16 copy (graphs.py ensure_quad) falls back to the direct route over `y`."""
+        ops, batch, seeds = self.ops, self.batch, list(self.x)
+        J = len(batch.jobs)
+        wanted = _route_propagates(self.n_feat, batch.jobs, force=batch.labels_only)
+        self.gram_route = "propagate" if wanted and all(g.ensure_quad() for g in batch.graphs) else "direct"
+        self._x_slot = x_slot = J + np.array([seeds.index(j.seed) for j in batch.jobs], np.int64)
         if self.gram_route == "propagate":
             # the raw features' kernels are launched HERE, while the host goes on building the propagation's and the regressions'
             # tables: they depend on nothing else of the batch (1.7 ms of device work for cora's two matrices that a rank's
             # start-up otherwise leaves the GPU waiting for)
             gx = _PrelaunchedGram(ops.GramBatch([self.x[s] for s in seeds]))
-            sym = getattr(self, "symmetric", 0)
-            gy = ops.PropagatedGram([(g, d, d if sym else None, gx.k_linear[x_slot[j.seed] - J])
-                                     for j, g, d in zip(self.jobs, self.graphs, self.dinv)])
-            self.gram = _GramPair(gy, gx)
+            gy = ops.PropagatedGram([(g, d, d if batch.symmetric else None, gx.k_linear[sl - J])
+                                     for g, d, sl in zip(batch.graphs, batch.dinv, x_slot)])
+            gram = _GramPair(gy, gx)
         else:
-            if self.labels_only:
+            if batch.labels_only:
                 ys = self.y  # (aggregated on demand, row-major; the step's tables hold the label columns only)
-            elif self.tiled_y and ops.GramBatch.tiled_ok():  # the Gram kernels read the tiled aggregation output as it is
-                ys = [ya.columns(self.n_feat) for ya in self.y_agg]
+            elif batch.tiled_y and ops.GramBatch.tiled_ok():  # the Gram kernels read the tiled aggregation output as it is
+                ys = [ya.columns(self.n_feat) for ya in batch.y_agg]
             else:  # row-major: with a tiled Y the copy, refreshed behind every aggregation from here on
-                ys = self.y
-                self._untile_each_step = self.tiled_y
-            self.gram = ops.GramBatch([ys[i] for i in range(J)] + [self.x[s] for s in seeds])
-        self.ge = ops.EdgeGramBatch([(g, self.gram.k_linear[x_slot[j.seed]], self.gram.norm2[x_slot[j.seed]])
-                                     for j, g in zip(self.jobs, self.graphs)])
-        # (the jobs of a sweep share a handful of label vectors - a sample's levels carry equal labels in separate arrays: a job's
-        # vector is first compared with the distinct ones met so far (np.array_equal: 2 us) and its bytes taken only for a new one -
-        # 35 x 2 `tobytes` of 16 KB were 1 ms of a rank's start-up)
+                ys = batch.row_major_y()
+            gram = ops.GramBatch([ys[i] for i in range(J)] + [self.x[s] for s in seeds])
+        return gram, ops.EdgeGramBatch([(g, gram.k_linear[sl], gram.norm2[sl]) for g, sl in zip(batch.graphs, x_slot)])
+
+    def _group_jobs(self, sets, sampler):
+        """the distinct label vectors, the jobs' split sizes and the groups of jobs that use one sequence of node sets (kr_group[job]
+        -> group, kr_rep[group] -> its first job; sets="job": every job its own); sets kr_set_mode and what _kr_sets keys a group by"""
+        batch = self.batch
+        # (a sample's levels carry equal labels in separate arrays: a job's vector is first compared with the distinct ones met so
+        # far - np.array_equal: 2 us - and its bytes taken only for a new one)
         distinct = []  # (array as int64, its bytes, per-class sizes)
         which = []
-        for lab in self.labels_host:
+        for lab in batch.labels_host:
             la = np.asarray(lab)
             k = next((i for i, (a, _b, _s) in enumerate(distinct) if a.shape == la.shape and np.array_equal(a, la)), -1)
             if k < 0:
                 a64 = np.ascontiguousarray(la, dtype=np.int64)
-                distinct.append((a64, a64.tobytes(), ops.kr_split_sizes(la, sample_max)))
+                distinct.append((a64, a64.tobytes(), self.ops.kr_split_sizes(la, self.kr_sample_max)))
                 k = len(distinct) - 1
             which.append(k)
         sizes = [distinct[k][2] for k in which]
+        self._n_tr = np.array([int(t.sum()) for _s, t in sizes], np.int64)
+        self._n_va = np.array([int(s_.sum() - t.sum()) for s_, t in sizes], np.int64)
         sets = sets or os.environ.get("WDG_SWEEP_KR_SETS", "job")
         if sets not in ("sample", "job"):
             raise ValueError(f"prepare_full: sets={sets!r} (sample | job)")
         if sampler != "device":
             sets = "job"  # (the reference's host routine draws per call)
         self.kr_set_mode = sets
-        # group[ji]: the set sequence job ji uses; rep[g]: the first job of group g
+        label_crc = None
         if sets == "sample":
             import zlib
             index, group, rep, label_crc = {}, [], [], []
-            for ji, j in enumerate(self.jobs):
+            for ji, j in enumerate(batch.jobs):
                 # (the label vector enters by VALUE - its int64 bytes' CRC -: the same job given int32 or int64 labels, or equal labels in
                 # another array, draws the same sets - ADVICE r05)
                 key = (j.seed, j.n_nodes, which[ji])
@@ -915,35 +920,41 @@ class SweepBatch:
                 group.append(index[key])
             group, rep = np.asarray(group, np.int64), np.asarray(rep, np.int64)
         else:
-            group = rep = np.arange(J, dtype=np.int64)
-        G = len(rep)
+            group = rep = np.arange(len(batch.jobs), dtype=np.int64)
         self.kr_group, self.kr_rep = group, rep
+        self._kr_rebind = ([sizes[r_] for r_ in rep], label_crc)  # per group: its split sizes, its label CRC (sets="sample")
+
+    def _draw_sets(self, sampler, seed_of, base_seed):
+        """-> (train, val) device tensors [G * 2, epochs, n_train / n_val]: row kr_group[job] * 2 + classifier holds a job's sets.
+        sampler "device": the sampler's table (kr_sets), filled by launch(); else the reference's routine on the host, uploaded here"""
+        batch, epochs = self.batch, self.kr_epochs
         if sampler == "device":
-            self._kr_rebind = (sets, [sizes[r_] for r_ in rep], label_crc if sets == "sample" else None)
             self.kr_sets = self._kr_sets(base_seed)
-            train, val = self.kr_sets.train, self.kr_sets.val         # [G * 2, epochs, n_train / n_val], filled by launch_full()
-        else:
-            self.kr_sets = None
-            seed_of = seed_of or (lambda ji, clf: 1000 * ji + clf)
-            nt = max([int(t.sum()) for _s, t in sizes], default=1)
-            nv = max([int(s_.sum() - t.sum()) for s_, t in sizes], default=1)
-            train_h, val_h = np.zeros((J * 2, epochs, max(nt, 1)), np.int32), np.zeros((J * 2, epochs, max(nv, 1)), np.int32)
-            rng_state = torch.get_rng_state()
-            for ji, lab in enumerate(self.labels_host):
-                lab_t = torch.from_numpy(np.asarray(lab)).long()
-                for clf in (0, 1):
-                    torch.manual_seed(seed_of(ji, clf))
-                    for e, (tr, va) in enumerate(kernel_regression_epoch_indices(lab_t, sample_max, epochs)):
-                        train_h[2 * ji + clf, e, :tr.shape[0]] = tr.numpy()
-                        val_h[2 * ji + clf, e, :va.shape[0]] = va.numpy()
-            torch.set_rng_state(rng_state)
-            train, val = ops._h2d(train_h, dev), ops._h2d(val_h, dev)
-        self.kr_train, self.kr_val = train, val  # [G * 2, epochs, .]: row kr_group[job] * 2 + classifier holds a job's sets
-        # the table of the regressions that are SOLVED, described by arithmetic on base addresses:
-        #   u = (job * 2 + classifier) * epochs + epoch                      the aggregated features' kernel of every job, then
-        #   u = J * 2 * epochs + (group * 2 + classifier) * epochs + epoch   the raw features' kernel of every group (sets="job":
-        #                                                                    a group is a job)
-        # kr_index[job, classifier, epoch, (0 aggregated | 1 raw)] -> u is what kr_accuracy() / full_metrics() read through
+            return self.kr_sets.train, self.kr_sets.val
+        from .utils.util_funcs import kernel_regression_epoch_indices
+        seed_of = seed_of or (lambda ji, clf: 1000 * ji + clf)
+        J, nt, nv = len(batch.jobs), int(self._n_tr.max()), int(self._n_va.max())
+        train_h, val_h = np.zeros((J * 2, epochs, max(nt, 1)), np.int32), np.zeros((J * 2, epochs, max(nv, 1)), np.int32)
+        rng_state = torch.get_rng_state()
+        for ji, lab in enumerate(batch.labels_host):
+            lab_t = torch.from_numpy(np.asarray(lab)).long()
+            for clf in (0, 1):
+                torch.manual_seed(seed_of(ji, clf))
+                for e, (tr, va) in enumerate(kernel_regression_epoch_indices(lab_t, self.kr_sample_max, epochs)):
+                    train_h[2 * ji + clf, e, :tr.shape[0]] = tr.numpy()
+                    val_h[2 * ji + clf, e, :va.shape[0]] = va.numpy()
+        torch.set_rng_state(rng_state)
+        dev = batch.graphs[0].device
+        return self.ops._h2d(train_h, dev), self.ops._h2d(val_h, dev)
+
+    def _regression_table(self):
+        """the table of the regressions that are SOLVED (-> ops.KrBatch), described by arithmetic on base addresses:
+          u = (job * 2 + classifier) * epochs + epoch                      the aggregated features' kernel of every job, then
+          u = J * 2 * epochs + (group * 2 + classifier) * epochs + epoch   the raw features' kernel of every group (sets="job":
+                                                                           a group is a job)
+        kr_index[job, classifier, epoch, (0 aggregated | 1 raw)] -> u is what kr_accuracy() / full_metrics() read through"""
+        batch, epochs, group, rep, train, val = self.batch, self.kr_epochs, self.kr_group, self.kr_rep, self.kr_train, self.kr_val
+        J, G = len(batch.jobs), len(rep)
         e_ = np.arange(epochs, dtype=np.int64)
         jc = np.arange(J * 2, dtype=np.int64)                        # job * 2 + classifier
         gc = np.arange(G * 2, dtype=np.int64)                        # group * 2 + classifier
@@ -955,19 +966,12 @@ class SweepBatch:
         u_epoch = np.concatenate([np.tile(e_, J * 2), np.tile(e_, G * 2)])          # its epoch
         k_lin = np.array([k.data_ptr() for k in self.gram.k_linear], np.int64)
         k_arc = np.array([k.data_ptr() for k in self.gram.k_arccos], np.int64)
-        xs = np.array([x_slot[j.seed] for j in self.jobs], np.int64)
-        u_slot = np.concatenate([np.repeat(jc // 2, epochs), np.repeat(xs[rep[gc // 2]], epochs)])  # and its kernel matrix
+        u_slot = np.concatenate([np.repeat(jc // 2, epochs), np.repeat(self._x_slot[rep[gc // 2]], epochs)])  # and its kernel matrix
         k_ptr = np.where(u_clf == 0, k_lin[u_slot], k_arc[u_slot])
-        n_nodes = np.array([j.n_nodes for j in self.jobs], np.int64)
-        n_tr = np.array([int(t.sum()) for _s, t in sizes], np.int64)
-        n_va = np.array([int(s_.sum() - t.sum()) for s_, t in sizes], np.int64)
-        lab_ptr = np.array([l.data_ptr() for l in self.labels], np.int64)
+        n_nodes = np.array([j.n_nodes for j in batch.jobs], np.int64)
+        lab_ptr = np.array([l.data_ptr() for l in batch.labels], np.int64)
         # (the row representatives of the matrix a kernel was computed from: duplicate nodes are deflated, not regularised - DESIGN 4.8)
         rep_of_slot = np.array([0 if r is None else r.data_ptr() for r in self.gram.rep], np.int64)
-        self.kr = ops.KrBatch.from_arrays(
-            k_ptr, n_nodes[u_job], train.data_ptr() + 4 * (u_row * epochs + u_epoch) * train.shape[2],
-            val.data_ptr() + 4 * (u_row * epochs + u_epoch) * val.shape[2], lab_ptr[u_job], n_tr[u_job], n_va[u_job], self.n_classes,
-            keep=(train, val, self.gram), rep_ptr=rep_of_slot[u_slot])
         idx = np.empty((J, 2, epochs, 2), np.int64)
         idx[..., 0] = (jc[:, None] * epochs + e_[None, :]).reshape(J, 2, epochs)
         idx[..., 1] = (J * 2 * epochs + row_g[:, None] * epochs + e_[None, :]).reshape(J, 2, epochs)
@@ -975,76 +979,86 @@ class SweepBatch:
         # a solved problem's name in the per-job enumeration p = ((job * 2 + classifier) * epochs + epoch) * 2 + which (what
         # pinv_accuracies takes): the group's first job stands for a shared raw-features problem
         self.kr_canonical = ((u_job * 2 + u_clf) * epochs + u_epoch) * 2 + (np.arange(u_job.shape[0]) >= J * 2 * epochs)
-        self._kr_index_dev = None
+        return self.ops.KrBatch.from_arrays(
+            k_ptr, n_nodes[u_job], train.data_ptr() + 4 * (u_row * epochs + u_epoch) * train.shape[2],
+            val.data_ptr() + 4 * (u_row * epochs + u_epoch) * val.shape[2], lab_ptr[u_job], self._n_tr[u_job], self._n_va[u_job],
+            batch.n_classes, keep=(train, val, self.gram), rep_ptr=rep_of_slot[u_slot])
 
     def _kr_sets(self, base_seed, out=None):
         """the device sampler's table of every (group, classifier) under base_seed (out: a table whose tensors it fills).  A pair's
         key is an IDENTITY (not a position in this shard), so that the same job draws the same sets on whichever rank / in whichever
         batch it runs: the sample's (seed, size, label vector) - or, sets="job", the job's (seed, h, k, size), so that different jobs
         draw independent ones"""
-        mode, sizes_rep, label_crc = self._kr_rebind
-        rep = self.kr_rep
+        (sizes_rep, label_crc), jobs, labels, rep = self._kr_rebind, self.batch.jobs, self.batch.labels, self.kr_rep
 
         def key_of(g, clf):
-            j = self.jobs[rep[g]]
-            if mode == "sample":
+            j = jobs[rep[g]]
+            if self.kr_set_mode == "sample":
                 return _mix64(base_seed, j.seed, j.n_nodes, label_crc[g], 0x5A3D, clf)
             return _mix64(base_seed, j.seed, int(round(j.h * 1e6)), j.k, j.n_nodes, clf)
-        return self.ops.KrSets([(self.labels[rep[g]], sizes_rep[g][0], sizes_rep[g][1], key_of(g, clf))
+        return self.ops.KrSets([(labels[rep[g]], sizes_rep[g][0], sizes_rep[g][1], key_of(g, clf))
                                 for g in range(len(rep)) for clf in (0, 1)], self.kr_epochs, out=out)
 
+    @property
+    def y(self):
+        """the aggregated features, row-major [n, n_feat] per job: the batch's - or, over a labels-only step, this plan's own
+        aggregation, made on demand, once (the direct route's fallback; the host re-solve of flagged blocks)"""
+        batch = self.batch
+        if not batch.labels_only:
+            return batch.y
+        if self._y_lazy is None:
+            self._y_lazy = [self.ops.spmm(g, self.x[j.seed], row_scale=d, col_scale=d if batch.symmetric else None)
+                            for j, g, d in zip(batch.jobs, batch.graphs, batch.dinv)]
+        return self._y_lazy
+
     def rebindable(self):
-        """whether rebind_features can take this batch: prepared, labels-only, on the propagated route, with device-drawn sets"""
-        return self.labels_only and getattr(self, "gram_route", None) == "propagate" and getattr(self, "kr_sets", None) is not None
+        """whether rebind_features can take this plan: over a labels-only step, on the propagated route, with device-drawn sets"""
+        return self.batch.labels_only and self.gram_route == "propagate" and self.kr_sets is not None
 
     def rebind_features(self, feats_of_seed, n_feat, base_seed):
-        """The NEXT FEATURE BASE on a prepared labels-only batch (run_bases: synthetic_plot.py:64-65 runs six feature bases over
-        the same adjacencies): new raw feature matrices and new node-set keys, every job table kept.  The step's tables never
-        held a feature address (labels_only); the raw features' kernels are written into the SAME buffers (GramBatch(out=...)),
-        so the propagation's, the edge cosines' and the regressions' tables stay valid; the node sets are drawn into the same
-        tensors under the new base's keys.  Computes what a fresh SweepBatch + prepare_full(base_seed=...) over the same inputs
-        computes (tests/test_gpu_sweep.py).  Call only when the batch's previous results have been fetched.
+        """The NEXT FEATURE BASE on this plan (run_bases): new raw feature matrices and new node-set keys, every job table kept.  The
+        raw features' kernels are written into the SAME buffers (GramBatch(out=...)), so the propagation's, the edge cosines' and the
+        regressions' tables stay valid; the node sets are drawn into the same tensors under the new base's keys.  Computes what a
+        fresh plan (base_seed=...) over the same inputs computes (tests/test_gpu_sweep.py).  Call only when the previous results have been fetched.
         feats_of_seed: {seed: [n, n_feat] fp32 host array}"""
-        ops = self.ops
         if not self.rebindable():
-            raise ValueError("rebind_features: a prepared labels-only batch on the propagated route with device-drawn sets is expected")
-        dev = self.kr.correct.device
+            raise ValueError("rebind_features: a plan over a labels-only step on the propagated route with device-drawn sets is expected")
         seeds = list(self.x)
         self.n_feat = n_feat
         self._y_lazy = None
-        self.x = {s_: ops._h2d(np.ascontiguousarray(feats_of_seed[s_], np.float32), dev) for s_ in seeds}
+        self.x = {s_: _upload_features(feats_of_seed[s_]) for s_ in seeds}
         # (same output tensors: the pair's k_linear / k_arccos / norm2 lists stay as they are)
-        self.gram.feats_part = ops.GramBatch([self.x[s_] for s_ in seeds], out=self.gram.feats_part)
+        self.gram.feats_part = self.ops.GramBatch([self.x[s_] for s_ in seeds], out=self.gram.feats_part)
         self.kr_sets = self._kr_sets(base_seed, out=self.kr_sets)
 
-    def kr_accuracy(self):
-        """[jobs, 2 classifiers, epochs, (graph-aware, features only)] fp32 device tensor: every job's accuracies, read through
-        kr_index from the regressions that were solved (shared raw-features problems appear once per job of their group)"""
+    def _through_index(self, per_problem):
+        """a [solved problems] device tensor of the solver -> [jobs, 2 classifiers, epochs, (graph-aware, features only)] through
+        kr_index (a shared raw-features problem appears once per job of its group); the index is uploaded on first use"""
         if self._kr_index_dev is None:
             self._kr_index_dev = self.ops._h2d(self.kr_index.reshape(-1), self.kr.correct.device)
-        return self.kr.accuracy()[self._kr_index_dev].reshape(self.kr_index.shape)
+        return per_problem[self._kr_index_dev].reshape(self.kr_index.shape)
+
+    def kr_accuracy(self):
+        """[jobs, 2, epochs, 2] fp32 device tensor: every job's accuracies, from the regressions that were solved"""
+        return self._through_index(self.kr.accuracy())
 
     def kr_ridged_mask(self):
-        """[jobs, 2, epochs, 2] bool device tensor: KrBatch.ridged() through kr_index"""
-        if self._kr_index_dev is None:
-            self._kr_index_dev = self.ops._h2d(self.kr_index.reshape(-1), self.kr.correct.device)
-        return self.kr.ridged()[self._kr_index_dev].reshape(self.kr_index.shape)
+        """[jobs, 2, epochs, 2] bool device tensor: KrBatch.ridged()"""
+        return self._through_index(self.kr.ridged())
 
     def kr_deflated_mask(self):
-        """[jobs, 2, epochs, 2] bool device tensor: KrBatch.deflated() (duplicate train rows merged / zero rows dropped) through kr_index"""
-        if self._kr_index_dev is None:
-            self._kr_index_dev = self.ops._h2d(self.kr_index.reshape(-1), self.kr.correct.device)
-        return self.kr.deflated()[self._kr_index_dev].reshape(self.kr_index.shape)
+        """[jobs, 2, epochs, 2] bool device tensor: KrBatch.deflated() (duplicate train rows merged / zero rows dropped)"""
+        return self._through_index(self.kr.deflated())
 
-    def launch_full(self, sample_events=None):
+    def launch(self, sample_events=None):
         """the launches of the three extra scalars (after the aggregation: they read Y): Gram + maps, edge cosines, regressions
         (sample_events: an optional pair of torch events recorded around the node-set sampler on the stream it runs on -
         bench.py's `sample_ms`; nothing is recorded when the sets were drawn on the host)"""
         side = None
         if self.kr_sets is not None:
-            # the epochs' node sets (device sampler; a host-sampled batch uploaded them in prepare_full) depend on nothing the
+            # the epochs' node sets (device sampler; a host-sampled plan uploaded them at construction) depend on nothing the
             # step produces: drawn on a second stream beside the Grams (their 2.7 ms of MFMA tiles)
-            if getattr(self, "_side_stream", None) is None:
+            if self._side_stream is None:
                 self._side_stream = _side_stream(2)
             side = self._side_stream
             side.wait_stream(torch.cuda.current_stream())  # (the previous batch's regressions have read the old sets)
@@ -1067,15 +1081,13 @@ class SweepBatch:
         kernels "host" (default): the epoch's kernel computed the reference's way too - the features of the epoch's sample
                  gathered from the device, their Gram by the host's fp32 GEMM, the arc-cosine map of utils/homophily_metrics.py:
                  232-257 in numpy - i.e. exactly what WDG_KR_SOLVER=host computes for that epoch.  This matters on rank-deficient
-                 blocks: duplicate nodes give bit-identical rows in a GEMM's Gram, so their null direction is exact and pinv's
-                 inverted rounding-level singular value multiplies an exact zero; the device Gram (products from bf16 pieces,
-                 operand roles not symmetric) leaves such rows a last bit apart, and pinv then amplifies that bit by 1e7 - measured on
-                 the golden epochs (profiles/r05_kr_three_way.txt): up to 28 validation rows from the reference on linear feature
-                 kernels with the device Gram, where the device solver's own ridge answer is within 0 - 1.
+                 blocks: duplicate nodes give bit-identical rows in a GEMM's Gram (an exact null direction), while the device Gram
+                 leaves them a last bit apart, which pinv amplifies by 1e7 - up to 28 validation rows from the reference on the
+                 golden epochs (profiles/r05_kr_three_way.txt).
                  "device": the blocks gathered from the device kernels (one gather and one copy per kernel matrix).
         The pseudo-inverses run on a pool of host threads with one BLAS thread each.
         problems: 1-D array of problem indices p = ((job * 2 + classifier) * epochs + epoch) * 2 + (0 aggregated | 1 raw features).
-        -> fp32 accuracies, one per listed problem.  Needs the node sets on the device (after launch_full())."""
+        -> fp32 accuracies, one per listed problem.  Needs the node sets on the device (after launch())."""
         from concurrent.futures import ThreadPoolExecutor
         problems = np.asarray(problems, np.int64).reshape(-1)
         out = np.zeros(problems.shape[0], np.float32)
@@ -1087,21 +1099,17 @@ class SweepBatch:
         pair, epoch, which = problems // (2 * E), (problems // 2) % E, problems % 2
         ji, clf = pair // 2, pair % 2
         seeds = list(self.x)
-        x_slot = {s_: len(self.jobs) + i for i, s_ in enumerate(seeds)}
-        slot = np.where(which == 0, ji, np.array([x_slot[j.seed] for j in self.jobs], np.int64)[ji])
-        sizes = [self.ops.kr_split_sizes(lab, self.kr_sample_max) for lab in self.labels_host]
-        n_tr = np.array([int(t.sum()) for _s, t in sizes], np.int64)
-        n_va = np.array([int(s_.sum() - t.sum()) for s_, t in sizes], np.int64)
-        c = self.n_classes
+        slot = np.where(which == 0, ji, self._x_slot[ji])
+        c = self.batch.n_classes
         ys = self.y if kernels == "host" else None  # (row-major aggregated features; a tiled Y is copied out once)
         work = []  # host: (position, H of the sample [train rows first], n_train, classifier, labels train, labels val); device: (position, K_tt, K_vt, ...)
         for key in sorted(set(zip(slot.tolist(), clf.tolist(), ji.tolist()))):
             sl, cl, jb = key
             sel = np.flatnonzero((slot == sl) & (clf == cl) & (ji == jb))
             rows_t = torch.from_numpy((int(self.kr_group[jb]) * 2 + cl) * np.ones_like(sel))  # (the sets row of (job, classifier))
-            tr = self.kr_train[rows_t, torch.from_numpy(epoch[sel])][:, :n_tr[jb]].long()  # [m, n_train] node ids
-            va = self.kr_val[rows_t, torch.from_numpy(epoch[sel])][:, :n_va[jb]].long()
-            lab = np.asarray(self.labels_host[jb]).astype(np.int64)
+            tr = self.kr_train[rows_t, torch.from_numpy(epoch[sel])][:, :self._n_tr[jb]].long()  # [m, n_train] node ids
+            va = self.kr_val[rows_t, torch.from_numpy(epoch[sel])][:, :self._n_va[jb]].long()
+            lab = np.asarray(self.batch.labels_host[jb]).astype(np.int64)
             tr_h, va_h = tr.cpu().numpy(), va.cpu().numpy()
             if kernels == "device":
                 kern = (self.gram.k_linear if cl == 0 else self.gram.k_arccos)[sl]
@@ -1110,13 +1118,13 @@ class SweepBatch:
                 for m_, pos in enumerate(sel):
                     work.append((int(pos), k_tt[m_], k_vt[m_], None, cl, lab[tr_h[m_]], lab[va_h[m_]]))
             else:
-                h = ys[jb] if sl < len(self.jobs) else self.x[seeds[sl - len(self.jobs)]]
+                h = ys[jb] if sl < len(self.batch.jobs) else self.x[seeds[sl - len(self.batch.jobs)]]
                 both = torch.cat([tr, va], 1)                                            # [m, n_train + n_val]
                 step = max(1, (64 << 20) // max(1, both.shape[1] * h.shape[1] * 4))       # <= 64 MB per copy
                 for a in range(0, both.shape[0], step):
                     hs = h[both[a:a + step].reshape(-1)].reshape(-1, both.shape[1], h.shape[1]).cpu().numpy()
                     for m_ in range(hs.shape[0]):
-                        work.append((int(sel[a + m_]), hs[m_], None, int(n_tr[jb]), cl, lab[tr_h[a + m_]], lab[va_h[a + m_]]))
+                        work.append((int(sel[a + m_]), hs[m_], None, int(self._n_tr[jb]), cl, lab[tr_h[a + m_]], lab[va_h[a + m_]]))
         eye = np.eye(c, dtype=np.float32)
         eps, pi = np.float32(1e-8), np.float32(np.pi)
 
@@ -1163,26 +1171,22 @@ class SweepBatch:
         over the epochs' accuracies (scipy on the host for the t distribution, as in the reference).
         ridge: what to do with the train blocks the device solver flags as rank deficient at fp32 rounding level
           "device" (default; WDG_SWEEP_KR_RIDGE) - keep the solver's ridge answers (counted in kr_ridged / kr_total, announced once
-                   per shard).  Measured against what the REFERENCE computed in the same epochs (golden fixtures, profiles/
-                   r05_kr_three_way.txt): within 0 - 2 validation rows on every synthetic-sweep fixture (flagged: the raw pubmed
-                   features' kernels, which hold duplicate rows), within 4 on cora's raw-adjacency kernels;
-          "pinv"   - solve exactly those blocks again the reference's way (pinv_accuracies: the epoch's sample gathered from the
-                   device, its kernel by the host's fp32 GEMM + the arc-cosine map, np.linalg.pinv on host threads) and patch their
-                   accuracies before the t-tests: the reference-equal answer on the sweep path, at ~8 ms of one host core per flagged
-                   block (kr_pinv_seconds).  Nothing is flagged on the synthetic feature bases of bench.py (0 of 672 000); the
-                   pubmed-sample fixtures flag 39 %."""
+                   per shard with how far they lie from what the REFERENCE computed in the same epochs: the warning below);
+          "pinv"   - solve exactly those blocks again the reference's way (pinv_accuracies) and patch their accuracies before the
+                   t-tests: the reference-equal answer on the sweep path, at ~8 ms of one host core per flagged block
+                   (kr_pinv_seconds).  Nothing is flagged on the synthetic feature bases of bench.py; the pubmed-sample fixtures flag 39 %."""
         ridge = ridge or os.environ.get("WDG_SWEEP_KR_RIDGE", "device")
         if ridge not in ("device", "pinv"):
             raise ValueError(f"full_metrics: ridge={ridge!r} (device | pinv)")
         self.kr_ridged = self.kr_deflated = self.kr_total = 0
         self.kr_pinv_seconds = 0.0
-        if not self.jobs:
+        if not self.batch.jobs:
             return torch.zeros((0, len(METRIC_NAMES)), dtype=torch.float64)
-        nj = len(self.jobs)
+        nj = len(self.batch.jobs)
         # one copy back: the step's scalars, the edge cosine means, the 4 x epochs accuracies of every job and the count of
         # train blocks the solver had to regularise
         # (one launch - wdg_sweep_pack_f64 - instead of a dozen library launches queued behind the regressions, then the one copy)
-        res = self.results().contiguous()
+        res = self.batch.results().contiguous()
         n_kr = int(self.kr.n_jobs)
         packed_dev = torch.empty(res.numel() + nj + n_kr + 3, dtype=torch.float64, device=res.device)
         ops = self.ops
@@ -1200,7 +1204,7 @@ class SweepBatch:
         n_base = packed.numel() - nj - self.kr.n_jobs
         base = packed[:n_base].reshape(nj, -1)
         ge = packed[n_base:n_base + nj]
-        acc = packed[n_base + nj:].numpy().astype(np.float32)  # the solved problems, in table order (prepare_full)
+        acc = packed[n_base + nj:].numpy().astype(np.float32)  # the solved problems, in table order (_regression_table)
         if self.kr_ridged and ridge == "pinv":
             import time
             t0 = time.perf_counter()
@@ -1264,8 +1268,9 @@ def _pipe_streams(depth):
 
 
 class _InFlight:
-    """The in-flight batches of a pipelined sweep (run_shards, run_bases): the i-th batch pushed runs on stream i mod `depth`; once
-    `depth` are in flight the oldest one's rows are fetched - rows_of(batch) on its stream, its regression counts added to `stats`."""
+    """The in-flight batches of a pipelined sweep (run_shards: SweepBatch; run_bases: KrPlan): the i-th one pushed runs on stream
+    i mod `depth`; once `depth` are in flight the oldest one's rows are fetched - rows_of(it) on its stream, its regression counts
+    (a plan's, or a batch's own plan's) added to `stats`."""
 
     def __init__(self, depth, rows_of, stats=None):
         self.depth = max(1, int(depth))
@@ -1287,8 +1292,9 @@ class _InFlight:
         with torch.cuda.stream(stream):
             rows = self.rows_of(sb)
         if self.stats is not None:
-            for name in ("kr_ridged", "kr_total", "kr_deflated", "kr_pinv_seconds"):
-                self.stats[name] = self.stats.get(name, 0) + getattr(sb, name, 0)
+            for name, n in (("kr_ridged", sb.kr_ridged), ("kr_total", sb.kr_total), ("kr_deflated", sb.kr_deflated),
+                            ("kr_pinv_seconds", sb.kr_pinv_seconds)):
+                self.stats[name] = self.stats.get(name, 0) + n
         return tag, sb, stream, rows
 
 
@@ -1348,7 +1354,7 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
                 _take_graphs(gb, build_stream, pipe.stream)
             with torch.cuda.stream(pipe.stream):
                 sb = SweepBatch(jobs, n_feat=n_feat, symmetric=symmetric, gcn_hidden=0, inputs=inputs, graph_batch=gb)
-                if nine and sb.jobs:
+                if nine:
                     sb.prepare_full(epochs=epochs, sample_max=sample_max, base_seed=first_seed + b)
                 sb.step()
                 if nine and sb.jobs:
@@ -1361,12 +1367,10 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
 
 
 def propagates(n_feat, jobs):
-    """whether prepare_full takes the propagated route for the aggregated features' kernels of these jobs on its own (WDG_GRAM_ROUTE,
-    width, graphs of one size that fit the quad-row kernel's one-block slabs): the sweep driver then aggregates the label columns only"""
-    route = os.environ.get("WDG_GRAM_ROUTE", "auto")
-    one_size = len({j.n_nodes for j in jobs}) == 1 and all(j.n_nodes <= 5056 for j in jobs)
-    return bool(jobs) and one_size and os.environ.get("WDG_SPMM_NO_QUAD", "0") in ("", "0") and (
-        route == "propagate" or (route == "auto" and n_feat >= 640)) and os.environ.get("WDG_SWEEP_RIDE_LABELS", "1") != "0"
+    """whether a plan takes the propagated route for these jobs on its own (_route_propagates; graphs that fit the quad-row kernel's
+    one-block slabs, label columns that ride): the sweep driver then aggregates the label columns only"""
+    return (bool(jobs) and _route_propagates(n_feat, jobs) and all(j.n_nodes <= 5056 for j in jobs)
+            and os.environ.get("WDG_SWEEP_RIDE_LABELS", "1") != "0")
 
 
 def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, stats=None):
@@ -1377,15 +1381,14 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
             (homophily level, sample) pair: `job.seed` = the sample);
     bases:  list of (name, features, sample_max) - features[seed] = [n, F_base] fp32 host array of that base's sample `seed`
             (synthetic_plot.py:81-82), sample_max as synthetic_plot.py:66 (300 for chameleon / film, else 500).
-    A shard's graphs (CSR, SELL-16 copy, degrees, labels) are built ONCE, by its first base; the other bases' batches share them
-    (SweepBatch(share=...)) and aggregate their own feature matrices over them.  Base-shard b runs on HIP stream b mod `depth`
-    and its rows are fetched when `depth` are in flight.  Every (shard, base) computes the rows a stand-alone SweepBatch over
-    the same inputs computes (tests/test_gpu_sweep.py)."""
-    pipe = _InFlight(depth, lambda sb: sb.full_metrics(), stats)
-    # TABLE REUSE inside a shard (DESIGN 5).  Bases on the propagated route aggregate the label columns only: they share ONE step
-    # (SweepBatch step twins), and a base takes over the prepared batch of an earlier base of equal sample_max whose rows have been
-    # fetched (rebind_features: new feature matrices and node-set keys, every job table kept).  _visit_order puts bases of equal
-    # sample_max apart, so that a batch is free again two visits later; rows carry their base index, and a batch stays on its stream.
+    A shard's graphs (CSR, SELL-16 copy, degrees, labels) are built ONCE, by its first base; a narrow base has a batch of its own
+    that shares them (SweepBatch(share=...)) and aggregates its feature matrices over them, the wide bases are plans on ONE
+    labels-only batch.  Base-shard b runs on HIP stream b mod `depth` and its rows are fetched when `depth` are in flight.  Every
+    (shard, base) computes the rows a stand-alone SweepBatch over the same inputs computes (tests/test_gpu_sweep.py)."""
+    pipe = _InFlight(depth, lambda plan: plan.full_metrics(), stats)
+    # TABLE REUSE inside a shard (DESIGN 5).  Bases on the propagated route are KrPlans on ONE labels-only batch, whose step runs
+    # once, and a base takes over the plan of an earlier base of equal sample_max whose rows have been fetched (rebind_features).
+    # _visit_order puts bases of equal sample_max apart, so that a plan is free again two visits later; a plan stays on its stream.
     # The NEXT shard's graphs are built ahead, on a stream of their own, as soon as this shard's first base is queued: built in place,
     # their one read-back waited behind whatever held the GPU - typically a regression launch - while the queue ran dry.
     shards = list(shards)
@@ -1403,10 +1406,8 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
         if order and lo[order[0]]:
             # the FIRST base's feature matrices go into the upload ring while the GPU builds the shard's graphs: the copies (1.2 ms
             # of library threads for cora's two 11-MB matrices) otherwise sit between the build's read-back and the first launch
-            from . import ops
             with torch.cuda.stream(pipe.stream):
-                x_first = {s_: ops._h2d(np.ascontiguousarray(bases[order[0]][1][s_], np.float32), ops.require_gpu())
-                           for s_ in sorted({j.seed for j in jobs})}
+                x_first = {s_: _upload_features(bases[order[0]][1][s_]) for s_ in sorted({j.seed for j in jobs})}
         if gb is not None:
             _take_graphs(gb, build_stream, pipe.stream)
             # (decided AFTER the build: a graph without a SELL-16 copy rules the propagated route out for the whole shard - its
@@ -1414,38 +1415,36 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
             if not all(g.quad for g in gb.graphs):
                 lo, x_first = [False] * len(bases), None
                 order = visit_order(lo)
-        # the shard's first batch builds the graphs (from gb) and owns them: the later bases share them and, pipelined, wait for
-        # the owner's stream
+        # the shard's first batch builds the graphs (from gb) and owns them: the later bases share them and wait for its stream
         owner = owner_lo = owner_stream = None
-        free = {}  # (sample_max, stream) -> a prepared batch of this shard whose rows have been fetched, for rebind_features
+        free = {}  # (sample_max, stream) -> a plan of this shard whose rows have been fetched, for rebind_features
         for bi in order:
             _name, feats, sample_max = bases[bi]
-            stream = pipe.stream
-            if owner is not None and pipe.depth > 1:
+            stream, first = pipe.stream, owner is None
+            if not first and pipe.depth > 1:
                 stream.wait_stream(owner_stream)
             with torch.cuda.stream(stream):
-                sb = free.pop((sample_max, stream.cuda_stream), None) if lo[bi] else None
-                if sb is not None:
-                    sb.rebind_features(feats, widths[bi], first_seed + 1000 * bi)
+                plan = free.pop((sample_max, stream.cuda_stream), None) if lo[bi] else None
+                kr = dict(epochs=epochs, sample_max=sample_max, base_seed=first_seed + 1000 * bi)
+                if plan is not None:
+                    plan.rebind_features(feats, widths[bi], kr["base_seed"])
+                elif lo[bi] and owner_lo is not None:  # a further plan on the labels-only batch: its step has been queued
+                    plan = KrPlan(owner_lo, {s_: _upload_features(feats[s_]) for s_ in owner_lo.x}, widths[bi], **kr)
                 else:
                     inputs = [(src, dst, lab, feats[j.seed]) for j, (src, dst, lab) in zip(jobs, graph_inputs)]
-                    sb = SweepBatch(jobs, n_feat=widths[bi], symmetric=symmetric, gcn_hidden=0, inputs=inputs,
-                                    share=(owner_lo or owner) if lo[bi] else owner, labels_only=lo[bi],
-                                    graph_batch=gb if owner is None else None, x_dev=x_first if owner is None else None)
-                    if sb.jobs:
-                        # (the node sets are keyed by the base and the job's identity, not by where the job sits: a job draws the
-                        # same sets in whichever shard / on whichever rank it runs - the N-rank sweep computes the one-GPU sweep's rows)
-                        sb.prepare_full(epochs=epochs, sample_max=sample_max, base_seed=first_seed + 1000 * bi)
+                    sb = SweepBatch(jobs, n_feat=widths[bi], symmetric=symmetric, gcn_hidden=0, inputs=inputs, share=owner,
+                                    labels_only=lo[bi], graph_batch=gb if first else None, x_dev=x_first if first else None)
+                    plan = KrPlan(sb, sb.x, widths[bi], **kr)  # (the in-flight plan keeps its batch alive, not the other way round)
                     sb.step()
-                if sb.jobs:
-                    sb.launch_full()
-            if owner is None:
-                owner, owner_stream = sb, stream
-                if si + 1 < len(shards):
-                    ahead = _queue_graphs(*shards[si + 1], build_stream)
-            if owner_lo is None and sb.labels_only:
-                owner_lo = sb
-            for (dsi, dbi), done, done_stream, rows in pipe.push((si, bi), sb):
+                    if first:
+                        owner, owner_stream = sb, stream
+                    if sb.labels_only:
+                        owner_lo = sb
+                if jobs:
+                    plan.launch()
+            if first and si + 1 < len(shards):
+                ahead = _queue_graphs(*shards[si + 1], build_stream)
+            for (dsi, dbi), done, done_stream, rows in pipe.push((si, bi), plan):
                 if dsi == si and done.rebindable():
                     free[(done.kr_sample_max, done_stream.cuda_stream)] = done
                 yield dsi, dbi, rows
