@@ -431,29 +431,30 @@ constexpr int SPLIT_PIECE_WORDS = SPLIT_KB * BRES_COLS * 4;        // 32-bit wor
 constexpr int SPLIT_BUF_WORDS = 3 * SPLIT_PIECE_WORDS;             // a buffer: three pieces (48 KB); two buffers
 static_assert(SPLIT_KB * BRES_COLS == BRES_THREADS, "one (k block, column) pair of a buffer per thread");
 
-// the thread's eight rows (k0 + 8 (tid / 64) + 0..7, column tid % 64) of W0: requested / split and written to a buffer
-__device__ __forceinline__ void split_load_w(global_ptr<const float> W0, int64_t ldw0, int K, int H, int k0, float (&w)[8]) {
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));  // (opaque per call: the eight row addresses are computed here, not hoisted out of the loops and spilled)
-    const int col = tid % BRES_COLS, kb = tid / BRES_COLS;
-    if (k0 + SPLIT_KQ <= K && H == BRES_COLS) {  // (uniform) a whole quarter of a full-width W0: eight loads off one pointer
-        const global_ptr<const float> p = W0 + static_cast<int64_t>(k0 + 8 * kb) * ldw0 + col;
+// the thread's eight rows (k0 + 8 (tid / 64) + 0..7, column tid % 64) of W0: requested / split and written to a buffer.
+// The request is eight unconditional loads whatever k0, K and H are: the rows are the wave's (scalar offsets, pulled back to
+// row K - 1), the column is pulled back to H - 1, and what lies outside W0 is zeroed when the values are written (behind a pin:
+// a load that only feeds a select is sunk under the select's condition and waited for on the spot, eight round trips in a row).
+// Nothing in the K loop is a conditional memory operation, so the compiler's vmcnt waits there stay counted.
+__device__ __forceinline__ void split_load_w(global_ptr<const float> W0, int64_t ldw0, int K, int H, int k0, int wave, int lane, float (&w)[8]) {
+    unsigned at = static_cast<unsigned>(min(lane, H - 1)) * 4u;  // the lane's byte offset in a row; the row addresses are scalar
+    asm volatile("" : "+v"(at));  // (opaque per call: the eight addresses are formed here, not hoisted out of the loops and held or spilled)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) w[j] = p[j * ldw0];
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {  // (unconditional loads from clamped addresses, zeroed afterwards: no branch per load)
-        const int k = k0 + 8 * kb + j;
-        const float v = W0[static_cast<int64_t>(min(k, K - 1)) * ldw0 + min(col, H - 1)];
-        w[j] = (k < K && col < H) ? v : 0.f;
+    for (int j = 0; j < 8; ++j) {
+        const global_ptr<const float> row = W0 + static_cast<int64_t>(min(k0 + 8 * wave + j, K - 1)) * ldw0;
+        w[j] = *(global_ptr<const float>)((global_ptr<const char>)row + at);
     }
 }
-__device__ __forceinline__ void split_write_w(const float (&w)[8], unsigned *buf) {
+__device__ __forceinline__ void split_write_w(float (&w)[8], int K, int H, int k0, int wave, int lane, unsigned *buf) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        asm volatile("" : "+v"(w[j]));
+        w[j] = (k0 + 8 * wave + j < K && lane < H) ? w[j] : 0.f;
+    }
     unsigned h[4], m[4], l[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) split_pair(w[2 * j], w[2 * j + 1], h[j], m[j], l[j]);
-    u32x4_t *dst = reinterpret_cast<u32x4_t *>(buf) + threadIdx.x;
+    u32x4_t *dst = reinterpret_cast<u32x4_t *>(buf) + wave * BRES_COLS + lane;
     dst[0] = u32x4_t{h[0], h[1], h[2], h[3]};
     dst[SPLIT_PIECE_WORDS / 4] = u32x4_t{m[0], m[1], m[2], m[3]};
     dst[2 * (SPLIT_PIECE_WORDS / 4)] = u32x4_t{l[0], l[1], l[2], l[3]};
@@ -510,7 +511,8 @@ __global__ __launch_bounds__(BRES_THREADS) void mlp2_split_kernel(const wdg_mlp2
     const int64_t lda = job->lda, ldw0 = job->ldw0, ldw1 = job->ldw1, ldz = job->ldz;
     const int64_t ags = job->a_group_stride > 0 ? job->a_group_stride : 16;  // floats between consecutive 16-column groups of a row of A
     const int M = job->M, K = job->K, H = job->H, C = job->C, act = job->act;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 15, q = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (scalar: W0's rows and `have` below are the wave's)
+    const int lane = threadIdx.x & 63, n = lane & 15, q = lane >> 4;
     if (M <= 0 || H <= 0 || C <= 0) return;
     unsigned *const Ws = reinterpret_cast<unsigned *>(Bres);
     float *const w1s = Bres + 2 * SPLIT_BUF_WORDS;
@@ -524,81 +526,104 @@ __global__ __launch_bounds__(BRES_THREADS) void mlp2_split_kernel(const wdg_mlp2
     const int tiles = (M + 31) / 32, per_part = (tiles + n_parts - 1) / n_parts;
     const int t_first = part * per_part, t_end = min((part + 1) * per_part, tiles);
     const bool relu = act == WDG_ACT_RELU;
-    const int steps = (K + 31) / 32, quarters = (K + SPLIT_KQ - 1) / SPLIT_KQ;
+    // K = 32 whole + (0 | 4 .. 28): the K loop runs the WHOLE steps, the one partial step is taken behind it
+    const int whole = K / 32, quarters = (K + SPLIT_KQ - 1) / SPLIT_KQ;
+    const unsigned *const last = Ws + ((quarters - 1) & 1) * SPLIT_BUF_WORDS;
     for (int t0 = t_first; t0 < t_end; t0 += BRES_THREADS / 64) {  // (uniform: a round of up to sixteen tiles, one per wave)
         const int tile = t0 + wave;
-        const bool have = tile < t_end;
+        float w[8];
+        // W0 passes through LDS in quarters of 128 rows, double-buffered: the rows of quarter q + 1 are requested before the MFMAs of
+        // quarter q and split + written after them, one barrier per quarter and one behind the last (nobody reads a buffer any more)
+        split_load_w(W0, ldw0, K, H, 0, wave, lane, w);
+        if (tile >= t_end) {  // a wave without a tile only carries its rows of W0
+            split_write_w(w, K, H, 0, wave, lane, Ws);
+            __syncthreads();
+            for (int qu = 1; qu < quarters; ++qu) {
+                split_load_w(W0, ldw0, K, H, qu * SPLIT_KQ, wave, lane, w);
+                split_write_w(w, K, H, qu * SPLIT_KQ, wave, lane, Ws + (qu & 1) * SPLIT_BUF_WORDS);
+                __syncthreads();
+            }
+            __syncthreads();
+            continue;
+        }
         global_ptr<const float> a_row[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int gm = tile * 32 + 16 * s + n;
             // (k = 32 st + 8 q + 0..7 of the lane's row: row-major at row lda + k; A tiled by 16-column groups - what the quad-row
             // aggregation writes with y_group_stride - at (k / 16) ags + row lda + k % 16, i.e. plane 2 st + q / 2, position 8 (q & 1))
-            a_row[s] = A + static_cast<int64_t>(have && gm < M ? gm : M - 1) * lda + (q >> 1) * ags + (q & 1) * 8;
+            a_row[s] = A + static_cast<int64_t>(gm < M ? gm : M - 1) * lda + (q >> 1) * ags + (q & 1) * 8;
         }
         f32x4_acc acc[2][NT16];
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int T = 0; T < NT16; ++T) acc[s][T] = f32x4_acc{0.f, 0.f, 0.f, 0.f};
-        auto load_step = [&](int st, SplitStep &dst) {  // k = 32 st + 8 q + 0..7 of both rows
-            st = min(st, steps - 1);
-            if (32 * st + 32 <= K) {  // (uniform) a whole step: plain loads off the lane's row pointers
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    dst.a[s] = *(const global_ptr<const f32x4_t>)(a_row[s] + 2 * ags * st);
-                    dst.b[s] = *(const global_ptr<const f32x4_t>)(a_row[s] + 2 * ags * st + 4);
-                }
-                return;
-            }
-            const int k = 32 * st + 8 * q;  // the last, partial step: addresses pulled back inside the row, values past K zeroed
-            const f32x4_t zero{0.f, 0.f, 0.f, 0.f};
+        // k = 32 st + 8 q + 0..7 of both rows, a whole step: plain loads off the lane's row pointers.  Steps past the last whole
+        // one re-request it (a load nobody uses, in place of a branch around the request)
+        auto load_step = [&](int st, SplitStep &dst) {
+            st = min(st, whole - 1);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const global_ptr<const float> row0 = a_row[s] - ((q >> 1) * ags + (q & 1) * 8);  // (the row's k = 0)
-                const int ka = min(k, K - 4), kb = min(k + 4, K - 4);
-                const f32x4_t va = *(const global_ptr<const f32x4_t>)(row0 + (ka >> 4) * ags + (ka & 15));
-                const f32x4_t vb = *(const global_ptr<const f32x4_t>)(row0 + (kb >> 4) * ags + (kb & 15));
-                dst.a[s] = k < K ? va : zero;
-                dst.b[s] = k + 4 < K ? vb : zero;
+                dst.a[s] = *(const global_ptr<const f32x4_t>)(a_row[s] + 2 * ags * st);
+                dst.b[s] = *(const global_ptr<const f32x4_t>)(a_row[s] + 2 * ags * st + 4);
             }
         };
         SplitStep sa, sb;
-        float w[8];
-        load_step(0, sa);
-        split_load_w(W0, ldw0, K, H, 0, w);     // (the previous round's last barrier: nobody reads buffer 0 any more)
-        split_write_w(w, Ws);
+        if (whole > 0) load_step(0, sa);
+        split_write_w(w, K, H, 0, wave, lane, Ws);
         __syncthreads();
-        // W0 passes through LDS in quarters of 128 rows, double-buffered: the rows of quarter q + 1 are requested before the MFMAs of
-        // quarter q and split + written after them, one barrier per quarter; the A steps run one ahead straight through
-        for (int qu = 0; qu < quarters; ++qu) {
-            const unsigned *cur = Ws + (qu & 1) * SPLIT_BUF_WORDS;
-            if (qu + 1 < quarters) split_load_w(W0, ldw0, K, H, (qu + 1) * SPLIT_KQ, w);
-            if (have) {
+        // the A steps run one ahead straight through the quarters: every block requests the next step's four loads and then splits
+        // and multiplies the step it holds, which needs the FOUR requests behind it in flight and nothing else (vmcnt(4); scripts/check_mlp2_isa.py)
+        if (whole > 0) {
+            for (int qu = 0;; ++qu) {
+                const unsigned *cur = Ws + (qu & 1) * SPLIT_BUF_WORDS;
+                split_load_w(W0, ldw0, K, H, (qu + 1) * SPLIT_KQ, wave, lane, w);
 #pragma unroll
                 for (int c = 0; c < 4; c += 2) {   // step 4 qu + c (+ 1): blocks 4 c .. of the buffer
                     const int base = 4 * qu + c;
-                    if (base >= steps) break;
                     load_step(base + 1, sb);
                     __builtin_amdgcn_sched_barrier(0);
-                    split_compute<NT16>(sa, 4 * c + q, n, cur, acc);
+                    if (base < whole) split_compute<NT16>(sa, 4 * c + q, n, cur, acc);
                     __builtin_amdgcn_sched_barrier(0);
                     load_step(base + 2, sa);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (base + 1 < steps) split_compute<NT16>(sb, 4 * c + 4 + q, n, cur, acc);
+                    if (base + 1 < whole) split_compute<NT16>(sb, 4 * c + 4 + q, n, cur, acc);
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                if (qu + 1 == quarters) break;
+                split_write_w(w, K, H, (qu + 1) * SPLIT_KQ, wave, lane, Ws + ((qu + 1) & 1) * SPLIT_BUF_WORDS);
+                __syncthreads();
             }
-            if (qu + 1 < quarters) split_write_w(w, Ws + ((qu + 1) & 1) * SPLIT_BUF_WORDS);
-            __syncthreads();
         }
-        if (!have) continue;
-
+        if (32 * whole < K) {  // the partial step: addresses pulled back inside the row, values past K zeroed
+            int qo = q;  // (opaque per tile: the tile-invariant offsets below are computed here, not hoisted out of the round loop and spilled)
+            asm volatile("" : "+v"(qo));
+            const int k = 32 * whole + 8 * qo;
+            const f32x4_t zero{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const global_ptr<const float> row0 = a_row[s] - ((qo >> 1) * ags + (qo & 1) * 8);  // (the row's k = 0)
+                const int ka = min(k, K - 4), kb = min(k + 4, K - 4);
+                const f32x4_t va = *(const global_ptr<const f32x4_t>)(row0 + (ka >> 4) * ags + (ka & 15));
+                const f32x4_t vb = *(const global_ptr<const f32x4_t>)(row0 + (kb >> 4) * ags + (kb & 15));
+                sb.a[s] = k < K ? va : zero;
+                sb.b[s] = k + 4 < K ? vb : zero;
+            }
+            split_compute<NT16>(sb, 4 * (whole & 3) + q, n, last, acc);
+        }
+        // b1: lane c holds b1[c], requested here and read (v_readlane) behind the second product - no load, and so no wait, inside
+        // the store sequence (a wait for a load there also waits for the store before it: one counter)
         int lds_off = q * 4;  // (opaque per tile: keeps the tile-invariant W1 / b0 reads from being hoisted and spilled)
         asm volatile("" : "+v"(lds_off));
+        int b1_at = n & (MLP2_MAX_C - 1);
+        asm volatile("" : "+v"(b1_at));
+        float b1v = 0.f;
+        if (b1) b1v = b1[static_cast<unsigned>(min(b1_at, C - 1))];
+        float zs[2][MLP2_MAX_C];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            float z[MLP2_MAX_C];
+            float (&z)[MLP2_MAX_C] = zs[s];
 #pragma unroll
             for (int c = 0; c < MLP2_MAX_C; ++c) z[c] = 0.f;
 #pragma unroll
@@ -623,14 +648,19 @@ __global__ __launch_bounds__(BRES_THREADS) void mlp2_split_kernel(const wdg_mlp2
                 z[c] += __shfl_xor(z[c], 16);
                 z[c] += __shfl_xor(z[c], 32);
             }
+        }
+        asm volatile("" : "+v"(b1v));  // the one wait for b1 lands here, in front of all stores
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
             const int gm = tile * 32 + 16 * s + n;
             if (q == 0 && gm < M) {
                 const global_ptr<float> zp = Z + static_cast<int64_t>(gm) * ldz;
 #pragma unroll
                 for (int c = 0; c < MLP2_MAX_C; ++c)
-                    if (c < C) zp[c] = z[c] + (b1 ? b1[c] : 0.f);
+                    if (c < C) zp[c] = zs[s][c] + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b1v), c));
             }
         }
+        __syncthreads();  // (the round's last: the partial step above read the last buffer)
     }
 }
 
