@@ -4,8 +4,10 @@ CSRC     := $(PKG)/csrc
 HIPCC    ?= /opt/rocm/bin/hipcc
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-value $(if $(STAMPS),-DWDG_STAMPS,) $(if $(DEPTH),-DWDG_PREFETCH_DEPTH=$(DEPTH),) $(EXTRA)
 SRCS     := $(wildcard $(CSRC)/*.hip)
-# per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution must unroll completely (their register indices and
-# branch conditions are compile-time only then) - with the default budget the compiler peels 11 steps and rolls the rest
+LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
+# per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and
+# nothing else) must unroll completely (their register indices and branch conditions are compile-time only then) - with the
+# default budget the compiler peels 11 steps and rolls the rest
 FLAGS_kernel_reg := -mllvm -pragma-unroll-threshold=200000
 # gnb.hip reproduces numpy's fp32 sums bit for bit: no multiply-add may be fused (its source says so as well: #pragma clang fp contract(off))
 FLAGS_gnb := -ffp-contract=off
@@ -16,7 +18,7 @@ all: $(LIB) oracle
 
 $(LIB): $(OBJS)
 	@mkdir -p $(dir $@)
-	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(OBJS)
+	$(HIPCC) $(LINKFLAGS) -o $@ $(OBJS)
 
 # (the compiler's per-kernel resource report - registers, spills, scratch - is kept beside the object: tests/test_abi.py
 # checks that no shipped kernel spills vector registers)
@@ -24,6 +26,21 @@ build/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/wdg.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> build/$*.rsrc || (cat build/$*.rsrc; exit 1)
 	@grep -E "warning:|error:" build/$*.rsrc || true
+
+# This file is the one place that knows how a unit is compiled.  Whatever else compiles one asks here:
+#   make -s hipcc-line UNIT=spmm_quad      prints the compiler and the unit's options (tests/_device_code.py generates the device
+#                                          code the ISA checks read with exactly this line + -S --cuda-device-only)
+#   make variant UNIT=kernel_reg NAME=kr_prof VFLAGS=-DK2_PROFILE      (dev tools: scripts/dev/build_*_variant*.sh)
+#                                          lib/variants/libwdg_hip_$(NAME).so = the shipped objects, UNIT's replaced by one compiled
+#                                          with the unit's options + VFLAGS
+hipcc-line:
+	@echo $(HIPCC) $(HIPFLAGS) $(FLAGS_$(UNIT))
+
+variant: $(OBJS)
+	@mkdir -p build/variants $(PKG)/lib/variants
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_$(UNIT)) $(VFLAGS) -c $(CSRC)/$(UNIT).hip -o build/variants/$(UNIT)_$(NAME).o 2> build/variants/$(NAME).log
+	$(HIPCC) $(LINKFLAGS) -o $(PKG)/lib/variants/libwdg_hip_$(NAME).so $(filter-out build/$(UNIT).o,$(OBJS)) build/variants/$(UNIT)_$(NAME).o
+	@echo built $(PKG)/lib/variants/libwdg_hip_$(NAME).so
 
 oracle: oracle/_build/libwdg_oracle.so
 
@@ -34,4 +51,4 @@ oracle/_build/libwdg_oracle.so: oracle/wdg_oracle.c
 clean:
 	rm -rf build $(LIB) oracle/_build
 
-.PHONY: all oracle clean
+.PHONY: all oracle clean hipcc-line variant

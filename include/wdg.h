@@ -238,7 +238,7 @@ int wdg_spmm_plan(int32_t n_jobs, int32_t max_rows, int32_t max_cols, int32_t n_
                   int *threads_out);
 
 /*
- * CSR -> SELL-16 (the index layout of the quad-row kernel, csrc/spmm_quad.hip): rows sorted by length (q_perm[slot] = row),
+ * CSR -> SELL-16 (the index layout of the quad-row kernel, csrc/sell16.h; built by csrc/sell16.hip): rows sorted by length (q_perm[slot] = row),
  * slices of 16 slots, columns cut into ceil(n_cols / B) blocks of B = wdg_sell16_block_cols(n_cols) <= 2528 (what one
  * 16-feature slab of X occupies in LDS), entries in chunks of 16 per row.  Inside a (row, block) segment the entries are
  * stored in a bank-aware order (the four rows an LDS service group reads together get columns of different classes mod 4),

@@ -12,10 +12,11 @@ arrived.  The results are the same either way, so only the gener
   (b) no `s_waitcnt vmcnt` between the first and the last store of Z (a wait there also waits for the store before it);
   (c) no `scratch_` instruction.
 
-Used by tests/test_mlp2_isa.py.  By hand:
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Iwhen-do-gnns-help_amd/csrc --cuda-device-only -S \\
-          when-do-gnns-help_amd/csrc/gemm.hip -o gemm.s && python scripts/check_mlp2_isa.py gemm.s
-(`python scripts/check_mlp2_isa.py kernel_reg.s gram_split_kernel` reports (a) and (c) for another kernel of the same scheme.)
+Used by tests/test_mlp2_isa.py.  By hand (the compiler and the unit's flags as the Makefile hands them out):
+    $(make -s hipcc-line UNIT=gemm) --cuda-device-only -S when-do-gnns-help_amd/csrc/gemm.hip -o gemm.s && \\
+          python scripts/check_mlp2_isa.py gemm.s
+(`python scripts/check_mlp2_isa.py gram.s gram_split_kernel`, on csrc/gram.hip's code, reports (a) and (c) for another kernel of the
+same scheme.)
 """
 import re
 import sys

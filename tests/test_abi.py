@@ -8,6 +8,8 @@ import subprocess
 import pytest
 import torch
 
+from _device_code import device_code
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -126,24 +128,13 @@ def test_no_shipped_kernel_spills_vector_registers():
     assert seen >= 20
 
 
-def _quad_device_code(tmp_path, *flags):
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    import subprocess
-    out = tmp_path / "quad.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{ROOT}/when-do-gnns-help_amd/csrc", "-S",
-                    "--cuda-device-only", *flags, "-o", str(out), f"{ROOT}/when-do-gnns-help_amd/csrc/spmm_quad.hip"], check=True, capture_output=True)
-    return out.read_text()
-
-
 def test_quad_row_fast_loop_keeps_its_memory_operations_to_itself(tmp_path):
     """csrc/spmm_quad.hip issues the loads and stores of its pipelined loop from inline asm and waits for them with hand-counted
     `s_waitcnt vmcnt(n)`: that is only right while the COMPILER puts no memory operation of its own between them (its wait
     insertion does not see the asm ones, and a spill reload or a conditional global access would shift the counts) and never
     touches a register whose asm load is still in flight (scripts/check_quad_isa.py: a dataflow over the generated code).
     The device code of the shipped flags is generated here and checked."""
-    text = _quad_device_code(tmp_path)
+    text = device_code("spmm_quad", tmp_path)
     import importlib.util
     spec = importlib.util.spec_from_file_location("check_quad_isa", os.path.join(ROOT, "scripts", "check_quad_isa.py"))
     chk = importlib.util.module_from_spec(spec)
@@ -190,9 +181,9 @@ def test_quad_isa_check_sees_a_register_rotation(tmp_path):
     spec = importlib.util.spec_from_file_location("check_quad_isa", os.path.join(ROOT, "scripts", "check_quad_isa.py"))
     chk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(chk)
-    good = chk.check_kernel(_quad_device_code(tmp_path, "-DWDG_Q_FAST_THREADS=768", "-DWDG_Q_DEPTH=2"), "IfLb0ELi0E")
+    good = chk.check_kernel(device_code("spmm_quad", tmp_path, "-DWDG_Q_FAST_THREADS=768", "-DWDG_Q_DEPTH=2"), "IfLb0ELi0E")
     assert good["depth"] == 2 and good["in_flight"] == 19 and not good["violations"], good
-    bad = chk.check_kernel(_quad_device_code(tmp_path, "-DWDG_Q_FAST_THREADS=768", "-DWDG_Q_DEPTH=2", "-DWDG_Q_EXPERIMENT_PLAIN_COPIES"), "IfLb0ELi0E")
+    bad = chk.check_kernel(device_code("spmm_quad", tmp_path, "-DWDG_Q_FAST_THREADS=768", "-DWDG_Q_DEPTH=2", "-DWDG_Q_EXPERIMENT_PLAIN_COPIES"), "IfLb0ELi0E")
     assert bad["violations"], "the checker missed the rotation of registers whose loads are in flight"
 
 

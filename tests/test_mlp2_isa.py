@@ -3,9 +3,8 @@ stay counted - the next step's loads in flight while the held step is split and 
 back to back (scripts/check_mlp2_isa.py).  The kernel computes the same bits either way: only its code shows it."""
 import importlib.util
 import os
-import subprocess
 
-import pytest
+from _device_code import device_code
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ("mlp2_split_kernelILi1E", "mlp2_split_kernelILi2E")
@@ -18,20 +17,10 @@ def _checker():
     return chk
 
 
-def _gemm_device_code(tmp_path):
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = tmp_path / "gemm.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{ROOT}/when-do-gnns-help_amd/csrc", "-S",
-                    "--cuda-device-only", "-o", str(out), f"{ROOT}/when-do-gnns-help_amd/csrc/gemm.hip"], check=True, capture_output=True)
-    return out.read_text()
-
-
 def test_mlp2_split_loop_keeps_its_prefetch_in_flight(tmp_path):
     """both instantiations, as shipped: (a) between a step's four A loads and the end of the MFMAs behind them no wait asks for
     fewer than four requests in flight, (b) no vmcnt wait between the first and the last store of Z, (c) no scratch"""
-    chk, text = _checker(), _gemm_device_code(tmp_path)
+    chk, text = _checker(), device_code("gemm", tmp_path)
     for name in KERNELS:
         res = chk.check_kernel(text, name)
         assert res["loops"] == 1 and res["groups"] == 4, (name, res)  # the quarter loop: four steps, each behind a group of four loads

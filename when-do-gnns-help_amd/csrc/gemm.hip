@@ -24,8 +24,6 @@ namespace {
 
 using namespace wdg;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int BM = 128, BK = 16, THREADS = 256;
 constexpr int LDA_S = BK + 1;  // As[m][k], odd stride -> lanes m=0..31 hit distinct banks
 

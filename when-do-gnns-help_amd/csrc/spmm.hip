@@ -23,15 +23,6 @@
 #include "wdg_common.h"
 #include "spmm_job_view.h"
 
-namespace wdg {
-// quad-row family (spmm_quad.hip), band kernel (spmm_band.hip)
-bool quad_eligible_single(const wdg_spmm_job &j);
-bool band_eligible_single(const wdg_spmm_job &j);
-int band_single_f32(const wdg_spmm_job &j, hipStream_t st);
-int quad_single_f32(const wdg_spmm_job &j, hipStream_t st);
-int quad_single_bf16(const wdg_spmm_job &j, hipStream_t st);
-}  // namespace wdg
-
 namespace {
 
 using namespace wdg;

@@ -18,13 +18,6 @@
 
 #include "wdg_common.h"
 
-namespace wdg {
-int exclusive_scan_i32(const int32_t *in, int64_t n, int32_t *out, int64_t *total64, void *ws, hipStream_t st);
-size_t exclusive_scan_ws_bytes(int64_t n);
-int sort_rows_by_length_small(const int32_t *rowptr, int32_t N, int32_t *perm, hipStream_t st);  // spmm_quad.hip, N <= 16384
-int sort_rows_small_limit();
-}  // namespace wdg
-
 namespace {
 using namespace wdg;
 

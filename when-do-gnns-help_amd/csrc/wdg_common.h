@@ -16,6 +16,20 @@ constexpr int kLdsBytes = 160 * 1024;
 char *error_buffer();           // thread-local, 256 bytes
 int fail(int code, const char *fmt, ...);
 
+// What one unit defines and another calls (the defining unit sees the declaration too):
+// graph_build.hip: exclusive scan of int32 counts on a stream, and the workspace it needs
+int exclusive_scan_i32(const int32_t *in, int64_t n, int32_t *out, int64_t *total64, void *ws, hipStream_t st);
+size_t exclusive_scan_ws_bytes(int64_t n);
+// sell16.hip: perm = rows by length, longest first (N <= sort_rows_small_limit() = 16384; more rows: the identity)
+int sort_rows_by_length_small(const int32_t *rowptr, int32_t N, int32_t *perm, hipStream_t st);
+int sort_rows_small_limit();
+// spmm_quad.hip, spmm_band.hip: the single-graph entries of the quad-row family and of the band kernel (wdg_spmm_csr_* picks)
+bool quad_eligible_single(const wdg_spmm_job &j);
+int quad_single_f32(const wdg_spmm_job &j, hipStream_t st);
+int quad_single_bf16(const wdg_spmm_job &j, hipStream_t st);
+bool band_eligible_single(const wdg_spmm_job &j);
+int band_single_f32(const wdg_spmm_job &j, hipStream_t st);
+
 inline hipStream_t as_stream(wdg_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int check_launch(const char *what) {
@@ -62,6 +76,7 @@ __device__ __forceinline__ desc_ptr<J> descriptor(const J *jobs, const J &inline
     return jobs ? (desc_ptr<J>)(jobs + id) : (desc_ptr<J>)(&inline_job);
 }
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // the accumulator of a 32x32 MFMA
 __device__ __forceinline__ float4 load_f32x4(global_ptr<const float> p) {
     const f32x4_t v = *(global_ptr<const f32x4_t>)p;
     return make_float4(v.x, v.y, v.z, v.w);

@@ -94,7 +94,7 @@ class CsrGraph:
         # 21 us against 105, a 4000-node sweep graph 17 against 42 - a slab per feature group is worth staging for a batch)
         return n_feat >= 64 and (self.n_cols > self.QUAD_SLAB_COLS or self.band["n_long"] > 0)  # (n_long: rows of more than 128 entries)
 
-    QUAD_MAX_BLOCKS = 4  # column blocks of <= 2528 columns the quad-row kernel sweeps (csrc/spmm_quad.hip)
+    QUAD_MAX_BLOCKS = 4  # column blocks of <= 2528 columns the quad-row kernel sweeps (Q_MAX_BLOCKS of csrc/sell16.h)
 
     def ensure_quad(self, max_padding=4.0):
         """Build the SELL-16 copy (wdg_csr_to_sell16_*) that the quad-row SpMM consumes.  One-time per graph; False for

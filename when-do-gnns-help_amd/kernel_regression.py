@@ -104,7 +104,7 @@ class GramBatch:
 
     @staticmethod
     def tiled_ok():
-        """the launcher's own rule (csrc/kernel_reg.hip, wdg_gram_map_batched_f32): split-operand kernels unless WDG_GRAM_SPLIT=0"""
+        """the launcher's own rule (csrc/gram.hip, wdg_gram_map_batched_f32): split-operand kernels unless WDG_GRAM_SPLIT=0"""
         e = os.environ.get("WDG_GRAM_SPLIT")
         try:
             return True if e is None else int(e) != 0
