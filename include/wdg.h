@@ -607,6 +607,13 @@ int wdg_mlp2_batched_flags_f32(const wdg_mlp2_job *jobs_dev, int32_t n_jobs, int
  *   K_linear = G / 2                                                           (n_layers = 0)
  *   K_arccos = (G (pi - acos(G / nu)) + sqrt(nu^2 - G^2)) / (2 pi),  nu = max(|a_i| |a_j|, 1e-8), NaN -> 0   (n_layers = 1)
  * with |a_i|^2 = G_ii, the Gram's own diagonal bit for bit (norm2 [n] is scratch the call fills).  G is symmetric bit for bit.
+ * Symmetric does not mean that bit-identical ROWS of A give bit-identical rows of K: the split-operand kernels compute the entries
+ * on or below the diagonal and mirror them, and their piece products are not symmetric in the two operands, so for duplicates
+ * d1 < j < d2 the entries K[d1][j] (a mirror) and K[d2][j] may differ in the last bit (equal where both lie on the same side of the
+ * diagonal; the chain's products commute: equal everywhere).  The solver reads every id at its representative and does not care.
+ * The map inherits the reference's jump at cos = -1: acos of a quotient that rounding pushed below -1 is NaN, NaN -> 0, and the entry
+ * of two exactly antiparallel rows is either about 0 or about G / 2, decided by the last bit of G / nu (at cos = +1 both branches
+ * agree).  The features of this domain are non-negative, where no cosine is negative.
  * Its fp32 products are formed from three bf16 pieces per operand on the bf16 matrix pipe, fp32 accumulation (no input bit
  * dropped; against fp64 within a small factor of the k-ordered fp32 chain's error, usually below it); WDG_GRAM_SPLIT=0 in the
  * environment selects that chain (then G is bit-identical to wdg_gemm_f32 with transb).

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from _golden import REAL, SYN, dense_features, load
+from _gram_ref import arccos_map32
 
 pytestmark = pytest.mark.gpu
 
@@ -1221,19 +1222,6 @@ def test_gram_matches_oracle(ops, oracle):
 
 
 # --------------------------------------------------------------------------------------------- kernel-regression metric
-def _arccos_map(g, n_layers):
-    """the reference's map (utils/homophily_metrics.py:236-244) in numpy fp32"""
-    if n_layers != 1:
-        return g / 2
-    d = np.sqrt(np.diag(g))
-    nu = d[:, None] * d[None, :]
-    nu = np.where(nu > 1e-8, nu, np.float32(1e-8))
-    with np.errstate(invalid="ignore"):
-        ac = np.nan_to_num(np.arccos(g / nu), nan=0.0)
-        sq = np.nan_to_num(np.sqrt(nu * nu - g * g), nan=0.0)
-    return (np.float32(1 / np.pi) * (g * (np.float32(np.pi) - ac) + sq) / 2).astype(np.float32)
-
-
 @pytest.mark.parametrize("split", ["0", "1"])
 def test_gram_map_fused_epilogue(ops, oracle, split, monkeypatch):
     """wdg_gram_map_batched_f32: K = map(A A^T) for all rows, linear and arc-cosine in one launch.  split = 0: the Gram part is the
@@ -1261,7 +1249,7 @@ def test_gram_map_fused_epilogue(ops, oracle, split, monkeypatch):
             g = 2.0 * _np(kl)  # (exact doubling: the map below is checked on the kernel's own Gram)
             assert np.array_equal(_np(n2), np.diag(g))  # the norms the map uses = the Gram's diagonal, same bits
         assert torch.equal(kl, kl.T) and torch.equal(ka, ka.T)  # (entries above the diagonal are written mirrored, not computed)
-        want = _arccos_map(g, 1)
+        want = arccos_map32(g, np.diag(g))
         np.testing.assert_allclose(_np(ka), want, rtol=2e-5, atol=2e-6 * max(float(np.abs(want).max()), 1e-30))
     only = ops.GramBatch(dev[:1], linear=False)
     only.launch()
@@ -1337,7 +1325,7 @@ def test_propagated_gram_equals_the_gram_of_the_aggregated_features(ops, symmetr
         assert torch.equal(prop.k_linear[i], prop.k_linear[i].T) and torch.equal(prop.k_arccos[i], prop.k_arccos[i].T)
         assert np.array_equal(_np(prop.norm2[i]), 2.0 * np.diag(b))       # G_ii from the propagated Gram's own diagonal, same bits
         np.testing.assert_allclose(_np(prop.norm2[i]), _np(direct.norm2[i]), rtol=2e-5)
-        want = _arccos_map(2.0 * b, 1)                                    # the map on the kernel's own Gram (numpy's fp32 map)
+        want = arccos_map32(2.0 * b, 2.0 * np.diag(b))                    # the map on the kernel's own Gram (numpy's fp32 map)
         np.testing.assert_allclose(_np(prop.k_arccos[i]), want, rtol=2e-5, atol=2e-6 * max(float(np.abs(want).max()), 1e-30))
         np.testing.assert_allclose(_np(prop.k_arccos[i]), _np(direct.k_arccos[i]), rtol=0, atol=3e-4 * float(np.abs(want).max()))
         assert np.allclose(np.diag(_np(prop.k_arccos[i])), np.diag(b), rtol=5e-4)  # K_arccos(i, i) = G_ii / 2 up to acos near 1
