@@ -9,6 +9,8 @@ LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # nothing else) must unroll completely (their register indices and branch conditions are compile-time only then) - with the
 # default budget the compiler peels 11 steps and rolls the rest
 FLAGS_kernel_reg := -mllvm -pragma-unroll-threshold=200000
+# (kernel_reg_large.hip factors its diagonal blocks with the same routine, csrc/kr_blocks.h)
+FLAGS_kernel_reg_large := -mllvm -pragma-unroll-threshold=200000
 # gnb.hip reproduces numpy's fp32 sums bit for bit: no multiply-add may be fused (its source says so as well: #pragma clang fp contract(off))
 FLAGS_gnb := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))

@@ -753,6 +753,33 @@ int wdg_kernel_regress_deflated_batched_f32(const wdg_kr_job *jobs_dev, int32_t 
 int32_t wdg_kernel_regress_max_train(void);
 
 /*
+ * The same regression for train blocks of 1 .. wdg_kernel_regress_large_max_train() = 1024 rows (n_classes <= 8, ldk < 65 536): the
+ * Cholesky factor lives in device memory instead of registers - packed 32 x 32 blocks of the lower triangle in a LAUNCH-LEVEL
+ * scratch buffer that the caller allocates, one 2.1-MiB slice (528 blocks x 4 KiB) per resident workgroup:
+ * wdg_kr_large_scratch_bytes() = CUs x 2.1 MiB, whatever the length of the table (a shorter buffer runs fewer workgroups; less
+ * than one slice is an error).  One workgroup per problem, persistent over the table; left-looking by block column on the fp32
+ * matrix pipe; every sum in a fixed order that depends on the problem alone (a relaunch is bit-identical, and no result depends
+ * on the workgroup that took the problem).  The numerical contract is wdg_kernel_regress_batched_f32's: pivots tested against
+ * n eps max K_ii / 64, one refactorisation with the ridge n eps max K_ii / 8 (flags bit 0), -1 for shapes out of range.
+ * Per job: ws != NULL - the deflating pre-pass runs first (row representatives `rep`, NULL = every node its own; scaled block
+ * S K S, mean one-hot right-hand sides, the drop rule, flags bits 1 and 2: exactly wdg_kernel_regress_deflated_batched_f32's
+ * semantics, above), ws = wdg_kr_large_workspace_bytes(n_train, n_val) bytes (16-byte aligned) of the job's own;
+ * ws == NULL and rep == NULL - the block is solved as it is; ws == NULL with rep != NULL answers -1.
+ * The caller allocates everything; no hidden synchronisation, no allocation.  Two launches, one call.
+ * replaces: `K_val_train @ (np.linalg.pinv(K_train_train) @ label_onehot[idx_train])`, `.argmax(1).eq(labels[idx_val])`
+ *           utils/homophily_metrics.py:283-297 (utils/homophily_plot.py:296-310) for `--sample_max` (homophily_tests.py:54)
+ *           above 533, where an epoch's train block has more than 320 rows.
+ */
+/* replaces: the limit on utils/homophily_metrics.py:283-297 that this entry holds (train rows of one regression) */
+int32_t wdg_kernel_regress_large_max_train(void);
+/* replaces: nothing of its own - the factor storage of utils/homophily_metrics.py:291-297's pinv, owned by the launch */
+size_t wdg_kr_large_scratch_bytes(void);
+/* replaces: nothing of its own - the per-job workspace of the deflating pre-pass (utils/homophily_metrics.py:291-297 on singular blocks) */
+size_t wdg_kr_large_workspace_bytes(int32_t n_train, int32_t n_val);
+/* replaces: utils/homophily_metrics.py:283-297, utils/homophily_plot.py:296-310 (see above) */
+int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream);
+
+/*
  * The node sets of the epochs, drawn on the device: per (graph, classifier, epoch) set a class-balanced sample of the nodes
  * and, inside it, the class-balanced train rows; the rest of the sample validates.
  * replaces: the two random_disassortative_splits calls per epoch of classifier_based_performance_metric

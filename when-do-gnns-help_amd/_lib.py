@@ -146,6 +146,10 @@ SIGNATURES = {
     "wdg_sweep_pack_f64": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "wdg_kr_deflate_workspace_bytes": (c_size_t, [c_int32]),
     "wdg_kernel_regress_deflated_batched_f32": (c_int, [c_void_p, c_int32, c_void_p]),
+    "wdg_kernel_regress_large_max_train": (c_int32, []),
+    "wdg_kr_large_scratch_bytes": (c_size_t, []),
+    "wdg_kr_large_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "wdg_kernel_regress_large_batched_f32": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "wdg_kr_sample_sets": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
 }
 

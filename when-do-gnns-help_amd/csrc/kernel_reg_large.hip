@@ -1,0 +1,579 @@
+// Kernel-regression metric on the device, train blocks of up to 1024 rows: a second batched Cholesky solver beside
+// csrc/kernel_reg.hip, whose register-resident factor ends at 320 rows.  Here the factor lives in DEVICE MEMORY: a 1024-row lower
+// triangle is 2 MiB of fp32, more than a CU's register file.
+//
+// replaces: the kernel-regression branch of classifier_based_performance_metric (utils/homophily_metrics.py:283-297,
+//           utils/homophily_plot.py:296-310: `K_val_train @ (np.linalg.pinv(K_train_train) @ onehot[idx_train])`, argmax, accuracy)
+//           for `--sample_max` above 533 (homophily_tests.py:54), where an epoch's train block outgrows the register solver.
+//
+//   * kr_large_deflate_kernel  the deflation pre-pass of kernel_reg.hip, one thread per train row, for 1024 rows, persistent over the table;
+//   * kr_large_solve_kernel    one workgroup of 8 waves per problem, persistent over the job table.
+//
+//   storage  the factor as packed 32 x 32 blocks of the lower triangle (block (a, b), b <= a, at (a (a + 1) / 2 + b) x 4 KiB, row-major,
+//            stride 32) in a launch-level scratch buffer: slice blockIdx.x belongs to the RESIDENT WORKGROUP, not to the job - 528 blocks
+//            = 2.1 MiB per workgroup, one workgroup per CU, however long the table is.  A workgroup only reads what it wrote itself
+//            while it worked on the same problem (its waves share the CU's vector L1; a barrier orders the accesses).  The diagonal
+//            block's place holds M = L_kk^-1 (all that the substitutions need of it).
+//   column   LEFT-LOOKING by block column kb.  The wave that owns block (a, kb) gathers K[tr, tr] for it straight from the Gram (the
+//            symmetric read of kernel_reg.hip: K_tt is never materialised), subtracts sum_j L(a, j) L(kb, j)^T, j ascending, on
+//            v_mfma_f32_32x32x2_f32 - the accumulator stays in registers, the block is written once.  The row panel L(kb, .), which all
+//            of the column's waves read, is staged in LDS in parts of 8 blocks (stride 36: conflict-free; a whole 31-block panel
+//            would be 143 KiB); L(a, .), private to the wave, streams from the L2.  Wave 0 owns the diagonal block alone and
+//            factors + inverts it with the register solver's one-wave routine (k2_factor_invert, kr_blocks.h) as soon as its own
+//            sum is through; waves 1 .. 7 are dealt the blocks below it round-robin (up to 5 each: 80 accumulator registers).
+//            Then the panel: X = A M^T on the matrix pipe (A back from the wave's own scratch block as an MFMA operand), and the
+//            right-hand sides inside the same step: z_kb = M y_kb (wave 0), y_a -= L(a, kb) z_kb (the block's wave).
+//   then     back substitution block column by block column (each wave sums its blocks a = kb + 1 + wave, + 8, .. ascending, wave
+//            0 subtracts the eight partial sums in wave order: alpha_kb = M^T v), predictions K[val, train] alpha four validation
+//            rows per wave at a time, arg-max by first maximum, one hit count per problem.
+// Every sum has a fixed order that depends on the problem alone - not on the workgroup that took it, not on the table: a relaunch
+// is bit-identical.  The numerical contract is the register solver's: pivots tested against n eps max K_ii / 64, ONE refactorisation
+// on K + (n eps max K_ii / 8) I (flags bit 0), the deflated block scaled by the square roots of the class sizes (bits 1 and 2),
+// ldk < 65 536, the sentinel -1 for shapes out of range.
+#include "wdg_common.h"
+#include "kr_blocks.h"
+
+namespace {
+
+using namespace wdg;
+
+constexpr int KL_THREADS = 512, KL_WAVES = 8, KL_NB = 32, KL_MAX_N = KL_NB * 32, KL_MAX_C = 8;
+constexpr int KL_SLOTS = 5;                         // blocks of one column a wave holds: ceil((KL_NB - 1) / (KL_WAVES - 1))
+constexpr int KL_CH = 8;                            // blocks of the row panel staged in LDS at a time
+constexpr int KL_BLOCKS = KL_NB * (KL_NB + 1) / 2;  // 528 blocks of the lower triangle
+constexpr size_t KL_WG_BYTES = static_cast<size_t>(KL_BLOCKS) * 4096;
+static_assert((KL_NB - 1 + KL_WAVES - 2) / (KL_WAVES - 1) <= KL_SLOTS, "every block of a column needs a register slot");
+
+// the deflation workspace of a problem (wdg_kr_job.ws), as int32 words - kernel_reg.hip's layout with the four per-row arrays sized
+// by the problem's OWN train rows, P = n_train rounded up to 32: [0] rows to solve, [1] != 0 when fewer than n_train, [2] listed
+// mixed-label entries, [3] != 0 when rows were dropped, [4 ..] representatives (padded with -1), [4 + P ..] labels (-2: mixed),
+// [4 + 2 P ..] sqrt(members) (fp32 bits), [4 + 3 P ..] the mixed list (row << 16 | label << 12 | members with that label),
+// [4 + 4 P ..] n_val validation representatives, then n_val labels
+constexpr int KLW_NT = 0, KLW_DEFLATED = 1, KLW_MIXED = 2, KLW_DROPPED = 3, KLW_TRAIN = 4;
+__host__ __device__ constexpr int klw_pad(int n_train) { return (n_train + 31) & ~31; }
+
+// Deflation pre-pass: kernel_reg.hip's kr_deflate_kernel (its comment holds the algebra and the drop rule) for up to 1024 train rows
+constexpr int KLD_THREADS = KL_MAX_N;
+__device__ void kl_deflate_one(const wdg_kr_job *__restrict__ job_ptr) {
+    __shared__ int d_raw[KLD_THREADS], d_lab[KLD_THREADS], d_first[KLD_THREADS], d_slot[KLD_THREADS], d_mult[KLD_THREADS];
+    __shared__ float rhs[KLD_THREADS * KL_MAX_C];
+    __shared__ int n_keep, any_mixed, any_drop;
+    const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)job_ptr;
+    if (job->ws == nullptr) return;  // (uniform) solved as it is
+    const int tid = threadIdx.x, nt_in = job->n_train, nv = job->n_val;
+    const global_ptr<int32_t> ws = to_global(static_cast<int32_t *>(job->ws));
+    if (nt_in <= 0 || nt_in > KLD_THREADS) {  // (the solver refuses the problem by its own test; the workspace must still be sane)
+        if (tid == 0) ws[KLW_NT] = -1, ws[KLW_DEFLATED] = 0, ws[KLW_MIXED] = 0, ws[KLW_DROPPED] = 0;
+        return;
+    }
+    const int P = klw_pad(nt_in), W_LAB = KLW_TRAIN + P, W_SCALE = W_LAB + P, W_MIX = W_SCALE + P, W_VAL = W_MIX + P;
+    const global_ptr<const float> K = to_global(job->K);
+    const global_ptr<const int32_t> train = to_global(job->train), val = to_global(job->val), labels = to_global(job->labels),
+                                    rep = to_global(job->rep);
+    const bool has_rep = job->rep != nullptr;  // (without the maps every node is its own representative: zero rows are still dropped)
+    const int64_t ldk = job->ldk;
+    if (tid == 0) n_keep = 0, any_mixed = 0, any_drop = 0;
+    int r = -1, lb = -1;
+    float diag = 0.f;
+    if (tid < nt_in) {
+        const int g = train[tid];
+        r = has_rep ? rep[g] : g, lb = labels[g];
+        diag = K[static_cast<int64_t>(r) * ldk + r];
+    }
+    // rows below the block's fp32 resolution are dropped: K_ii <= n eps max K_ii / 64, the level of the solver's pivot test
+    float dmax = diag == diag ? diag : 0.f;
+    for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
+    if ((tid & 63) == 0) rhs[tid >> 6] = dmax;  // (rhs doubles as the waves' maxima; zeroed below)
+    __syncthreads();
+    dmax = 0.f;
+    for (int w = 0; w < KLD_THREADS / 64; ++w) dmax = fmaxf(dmax, rhs[w]);
+    if (tid < nt_in && !(diag > static_cast<float>(nt_in) * 1.1920929e-7f * dmax * (1.f / 64.f))) r = -2, any_drop = 1;
+    __syncthreads();
+    d_raw[tid] = r, d_lab[tid] = lb, d_mult[tid] = 0;
+    for (int i = tid; i < KLD_THREADS * KL_MAX_C; i += KLD_THREADS) rhs[i] = 0.f;
+    __syncthreads();
+    int first = r < 0 ? -1 : tid;  // the first train row with this representative
+    if (r >= 0)
+        for (int j0 = 0; j0 < tid && first == tid; j0 += 8) {
+            int v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = d_raw[min(j0 + e, KLD_THREADS - 1)];
+#pragma unroll
+            for (int e = 7; e >= 0; --e)
+                if (v[e] == r && j0 + e < tid) first = j0 + e;  // (descending: the smallest match stays)
+        }
+    d_first[tid] = first;
+    // a kept row's slot = the kept rows before it: ballot prefix inside a wave + the earlier waves' counts
+    const bool keep = first == tid;
+    const unsigned long long kmask = __ballot(keep);
+    const int lane = tid & 63, wv = tid >> 6;
+    if (lane == 0) d_mult[wv] = __popcll(kmask);  // (d_mult doubles as the per-wave counts until the barrier; zeroed again below)
+    __syncthreads();
+    int slot = -1;
+    if (keep) {
+        slot = __popcll(kmask & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wv; ++w) slot += d_mult[w];
+        d_slot[tid] = slot;
+    }
+    if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < KLD_THREADS / 64; ++w) total += d_mult[w];
+        n_keep = total;
+    }
+    __syncthreads();
+    if (tid < KLD_THREADS / 64) d_mult[tid] = 0;
+    __syncthreads();
+    if (first >= 0 && first != tid) slot = d_slot[first];
+    __syncthreads();                       // (every read of d_slot / d_first as a map precedes the compaction below)
+    if (first == tid) d_first[slot] = r;  // (d_first is free now: the kept representatives, compact)
+    if (slot >= 0) {                       // (counts of small integers: exact in any order)
+        atomicAdd(&d_mult[slot], 1);
+        if (lb >= 0 && lb < KL_MAX_C) atomicAdd(&rhs[slot * KL_MAX_C + lb], 1.f);
+    }
+    __syncthreads();
+    const int kept = n_keep;
+    if (tid < P) ws[KLW_TRAIN + tid] = tid < kept ? d_first[tid] : -1;
+    // slot `tid`: pure (every member one label -> that label; members without a label in range -> -1: a zero row) or mixed
+    int pure = -1;
+    bool mixed = false;
+    if (tid < kept) {
+        const float m = static_cast<float>(d_mult[tid]);
+        int nz = 0;
+        for (int c = 0; c < KL_MAX_C; ++c) {
+            const float cnt = rhs[tid * KL_MAX_C + c];
+            if (cnt != 0.f) ++nz, pure = c;
+            if (cnt != 0.f && cnt != m) mixed = true;
+        }
+        mixed |= nz > 1;
+        if (mixed) {  // (a (row, label) pair per train row at most: the list never outgrows its P words)
+            pure = -2;
+            for (int c = 0; c < KL_MAX_C; ++c) {
+                const int cnt = static_cast<int>(rhs[tid * KL_MAX_C + c]);
+                if (cnt > 0) ws[W_MIX + atomicAdd(&any_mixed, 1)] = (tid << 16) | (c << 12) | cnt;
+            }
+        }
+    }
+    if (tid < P) {
+        ws[W_LAB + tid] = pure;
+        ws[W_SCALE + tid] = __builtin_bit_cast(int, tid < kept ? sqrtf(static_cast<float>(d_mult[tid])) : 1.f);
+    }
+    for (int v = tid; v < nv; v += KLD_THREADS) {
+        const int g = val[v];
+        ws[W_VAL + v] = has_rep ? rep[g] : g;
+        ws[W_VAL + nv + v] = labels[g];
+    }
+    __syncthreads();
+    if (tid == 0) ws[KLW_NT] = kept, ws[KLW_DEFLATED] = kept != nt_in, ws[KLW_MIXED] = any_mixed, ws[KLW_DROPPED] = any_drop;
+}
+
+// persistent over the job table like the solver: a table without workspaces costs two workgroups per CU that read its ws
+// pointers, not a workgroup per problem
+__global__ __launch_bounds__(KLD_THREADS) void kr_large_deflate_kernel(const wdg_kr_job *__restrict__ jobs, int n_jobs) {
+    for (int prob = blockIdx.x; prob < n_jobs; prob += gridDim.x) {
+        kl_deflate_one(jobs + prob);
+        __syncthreads();  // (the next problem's pass overwrites the shared arrays)
+    }
+}
+
+__device__ __forceinline__ int kl_blk(int a, int b) { return a * (a + 1) / 2 + b; }  // b <= a
+
+__global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr_job *__restrict__ jobs, int n_jobs, float *scratch_all) {
+    __shared__ float RP[KL_CH * 32 * K2_PS];           // a part of the row panel L(kb, j0 .. j0 + 7), row-major, stride 36
+    __shared__ float LD[32 * K2_PS];                   // the diagonal block: A_kk -> M = L_kk^-1 (k2_factor_invert)
+    __shared__ float LT[32 * K2_PS];                   // k2_factor_invert's column buffer
+    __shared__ float zs[KL_MAX_N * KL_MAX_C];          // right-hand sides -> z = L^-1 Y (block by block) -> v of the back substitution
+    __shared__ float al[KL_MAX_N * KL_MAX_C];          // alpha
+    __shared__ float part[KL_WAVES][32][KL_MAX_C];     // per-wave partial sums (back substitution)
+    __shared__ int tr_idx[KL_MAX_N];                   // the train rows' ids as solved
+    __shared__ float sc[KL_MAX_N];                     // sqrt(size) of a solved row's duplicate class (1 without a workspace)
+    __shared__ float red[KL_WAVES];
+    __shared__ int deficient, hits;
+
+    // (the wave index as a SCALAR: the branches on it are then scalar branches, and what one side holds in registers - the column's
+    // accumulators - is not live through the other - the diagonal block's factorisation)
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li_ = lane & 31, h_ = lane >> 5;
+    const global_ptr<float> S = to_global(scratch_all) + static_cast<size_t>(blockIdx.x) * (KL_BLOCKS * 1024);  // this workgroup's factor
+    for (int prob = blockIdx.x; prob < n_jobs; prob += gridDim.x) {
+        const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)(jobs + prob);
+        const global_ptr<const float> K = to_global(job->K);
+        const global_ptr<const int32_t> train = to_global(job->train), val = to_global(job->val), labels = to_global(job->labels);
+        const global_ptr<const int32_t> ws = to_global(static_cast<const int32_t *>(job->ws));
+        const int64_t ldk = job->ldk;
+        const int nt_in = job->n_train, nv = job->n_val, C = job->n_classes;
+        const bool has_ws = job->ws != nullptr;  // (uniform) the pre-pass has run on this job
+        bool refuse = nt_in <= 0 || nt_in > KL_MAX_N || C <= 0 || C > KL_MAX_C || ldk <= 0 || ldk >= 65536 ||
+                      (!has_ws && job->rep != nullptr);  // (representatives without a workspace: not solved as if there were none)
+        int nt = nt_in;
+        if (!refuse && has_ws) {
+            nt = ws[KLW_NT];
+            refuse = nt < 0 || nt > nt_in;
+        }
+        if (refuse) {  // (uniform)
+            if (tid == 0 && job->correct_out) *to_global(job->correct_out) = -1;
+            if (tid == 0 && job->flags_out) *to_global(job->flags_out) = 0;
+            continue;
+        }
+        const int P = klw_pad(nt_in), W_LAB = KLW_TRAIN + P, W_SCALE = W_LAB + P, W_MIX = W_SCALE + P, W_VAL = W_MIX + P;
+        const bool deflated = has_ws && ws[KLW_DEFLATED] != 0;
+        const bool dropped = has_ws && ws[KLW_DROPPED] != 0;
+        const int n_mixed = has_ws ? ws[KLW_MIXED] : 0;
+        const int nb = (nt + 31) >> 5;
+        for (int i = tid; i < nb * 32; i += KL_THREADS) {
+            tr_idx[i] = i < nt ? (has_ws ? ws[KLW_TRAIN + i] : train[i]) : -1;
+            sc[i] = (has_ws && i < nt) ? __builtin_bit_cast(float, ws[W_SCALE + i]) : 1.f;
+        }
+        if (tid == 0) hits = 0;
+        __syncthreads();
+        // max K_ii of the solved rows (the scale of the pivot test)
+        float dmax = 0.f;
+        for (int t = tid; t < nt; t += KL_THREADS) dmax = fmaxf(dmax, K[static_cast<int64_t>(tr_idx[t]) * ldk + tr_idx[t]] * (sc[t] * sc[t]));
+        for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
+        if (lane == 0) red[wave] = dmax;
+        __syncthreads();
+        dmax = 0.f;
+#pragma unroll
+        for (int w = 0; w < KL_WAVES; ++w) dmax = fmaxf(dmax, red[w]);
+        const float drop_below = static_cast<float>(nt) * 1.1920929e-7f * dmax * (1.f / 64.f);
+        float ridge = 0.f;
+
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            // ---- right-hand sides
+            for (int i = tid; i < nb * 32 * KL_MAX_C; i += KL_THREADS) {
+                const int row = i / KL_MAX_C, c = i % KL_MAX_C;
+                float v = 0.f;
+                if (row < nt) {
+                    const int lb = has_ws ? ws[W_LAB + row] : labels[tr_idx[row]];
+                    v = lb == c ? sc[row] : 0.f;
+                    if (lb == -2 && has_ws)  // (rare) a class of duplicates with different labels: its label counts over sqrt(size)
+                        for (int e = 0; e < n_mixed; ++e) {
+                            const int w = ws[W_MIX + e];
+                            if ((w >> 12) == ((row << 4) | c)) v = static_cast<float>(w & 0xfff) / sc[row];
+                        }
+                }
+                zs[i] = v;
+            }
+            if (tid == 0) deficient = 0;
+            __syncthreads();
+            // lane (i, h): A[32 a + i][32 b + jmap(h, r)] = K[tr[32 b + j]][tr[32 a + i]] (K is symmetric: per register a wave-uniform
+            // row per lane half, 32 columns)
+            auto gather_block = [&](int a, int b, f32x16 &t) {
+                int li = li_, h = h_;
+                asm volatile("" : "+v"(li), "+v"(h));
+                const int gi = tr_idx[32 * a + li];
+                const float si = sc[32 * a + li];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int j = k2_jmap(h, r), gj = tr_idx[32 * b + j];
+                    const bool diag = a == b && li == j;
+                    float v = (gi >= 0 && gj >= 0) ? K[static_cast<int64_t>(gj) * ldk + gi] : (diag ? 1.f : 0.f);
+                    v *= si * sc[32 * b + j];  // (1 for rows without duplicates: exact)
+                    if (diag && gi >= 0) v += ridge;
+                    t[r] = v;
+                }
+            };
+
+            // ---- the factorisation, left-looking by block column
+            for (int kb = 0; kb < nb; ++kb) {
+                int li = li_, h = h_;  // (opaque per iteration: the loop's lane-dependent addresses are not hoisted out of it)
+                asm volatile("" : "+v"(li), "+v"(h));
+                // this wave's blocks of the column: wave 0 the diagonal block, waves 1 .. 7 the blocks below it round-robin
+                int sa[KL_SLOTS];
+                f32x16 acc[KL_SLOTS];
+#pragma unroll
+                for (int s = 0; s < KL_SLOTS; ++s) {
+                    const int i = wave == 0 ? (s == 0 ? 0 : nb) : wave + (KL_WAVES - 1) * s;
+                    sa[s] = __builtin_amdgcn_readfirstlane(kb + i < nb ? kb + i : -1);
+                    if (sa[s] >= 0) gather_block(sa[s], kb, acc[s]);
+                    else
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+                }
+                for (int j0 = 0; j0 < kb; j0 += KL_CH) {
+                    const int cnt = min(KL_CH, kb - j0);
+                    for (int e = tid; e < cnt * 256; e += KL_THREADS) {  // L(kb, j0 + c) -> RP[c]
+                        const int c = e >> 8, row = (e >> 3) & 31, q = e & 7;
+                        const f32x4_t v = *(global_ptr<const f32x4_t>)(S + kl_blk(kb, j0 + c) * 1024 + row * 32 + 4 * q);
+                        *reinterpret_cast<float4 *>(&RP[(c * 32 + row) * K2_PS + 4 * q]) = make_float4(v.x, v.y, v.z, v.w);
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int s = 0; s < KL_SLOTS; ++s) {
+                        if (sa[s] < 0) continue;  // (wave-uniform)
+                        for (int c = 0; c < cnt; ++c) {
+                            const global_ptr<const float> pa = S + kl_blk(sa[s], j0 + c) * 1024 + li * 32 + 4 * h;
+                            const float *pb = &RP[(c * 32 + li) * K2_PS + 4 * h];
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                const f32x4_t va = *(global_ptr<const f32x4_t>)(pa + 8 * q);
+                                const float4 vb = *reinterpret_cast<const float4 *>(pb + 8 * q);
+                                acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(-vb.x, va.x, acc[s], 0, 0, 0);
+                                acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(-vb.y, va.y, acc[s], 0, 0, 0);
+                                acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(-vb.z, va.z, acc[s], 0, 0, 0);
+                                acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(-vb.w, va.w, acc[s], 0, 0, 0);
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+                if (wave == 0) {
+                    // the diagonal block: factored and inverted in one pass (LD holds M = L_kk^-1 afterwards), M -> its scratch block,
+                    // z_kb = M y_kb (the lane halves split k, one cross-half add)
+                    k2_store_block(acc[0], LD, li, h);
+                    if (k2_factor_invert(LD, LT, li, h, nt - 32 * kb, drop_below, ridge) && lane == 0) deficient = 1;
+                    const float *mrow = &LD[li * K2_PS + 4 * h];
+                    const global_ptr<float> md = S + kl_blk(kb, kb) * 1024 + li * 32 + 4 * h;
+                    float sum[KL_MAX_C];
+#pragma unroll
+                    for (int c = 0; c < KL_MAX_C; ++c) sum[c] = 0.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 m = *reinterpret_cast<const float4 *>(mrow + 8 * q);
+                        *(global_ptr<f32x4_t>)(md + 8 * q) = f32x4_t{m.x, m.y, m.z, m.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float *y = &zs[(32 * kb + 8 * q + 4 * h + e) * KL_MAX_C];
+                            const float4 y0 = *reinterpret_cast<const float4 *>(y), y1 = *reinterpret_cast<const float4 *>(y + 4);
+                            const float l = e == 0 ? m.x : e == 1 ? m.y : e == 2 ? m.z : m.w;
+                            sum[0] = fmaf(l, y0.x, sum[0]), sum[1] = fmaf(l, y0.y, sum[1]), sum[2] = fmaf(l, y0.z, sum[2]), sum[3] = fmaf(l, y0.w, sum[3]);
+                            sum[4] = fmaf(l, y1.x, sum[4]), sum[5] = fmaf(l, y1.y, sum[5]), sum[6] = fmaf(l, y1.z, sum[6]), sum[7] = fmaf(l, y1.w, sum[7]);
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < KL_MAX_C; ++c) sum[c] += __shfl_xor(sum[c], 32);
+                    if (h == 0) {  // (every read of y above precedes these writes: they depend on all of them)
+                        *reinterpret_cast<float4 *>(&zs[(32 * kb + li) * KL_MAX_C]) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+                        *reinterpret_cast<float4 *>(&zs[(32 * kb + li) * KL_MAX_C + 4]) = make_float4(sum[4], sum[5], sum[6], sum[7]);
+                    }
+                } else {
+                    // A(a, kb), updated, -> its scratch block: it comes back below as an MFMA operand (row li, the k index in the registers)
+#pragma unroll
+                    for (int s = 0; s < KL_SLOTS; ++s) {
+                        if (sa[s] < 0) continue;
+                        const global_ptr<float> pd = S + kl_blk(sa[s], kb) * 1024 + li * 32 + 4 * h;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            *(global_ptr<f32x4_t>)(pd + 8 * q) = f32x4_t{acc[s][4 * q], acc[s][4 * q + 1], acc[s][4 * q + 2], acc[s][4 * q + 3]};
+                    }
+                }
+                __syncthreads();
+                if (deficient && attempt == 0) break;  // (uniform) restart on K + ridge I
+                // the panel: X L_kk^T = A  <=>  X = A M^T, 16 MFMAs per block; y_a -= X z_kb
+                if (wave != 0) {
+#pragma unroll 1
+                    for (int s = 0; s < KL_SLOTS; ++s) {
+                        const int a = sa[s];
+                        if (a < 0) continue;
+                        f32x16 t;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) t[r] = 0.f;
+                        const global_ptr<float> pa = S + kl_blk(a, kb) * 1024 + li * 32 + 4 * h;
+                        const float *pm = &LD[li * K2_PS + 4 * h];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const f32x4_t va = *(global_ptr<const f32x4_t>)(pa + 8 * q);
+                            const float4 vm = *reinterpret_cast<const float4 *>(pm + 8 * q);
+                            t = __builtin_amdgcn_mfma_f32_32x32x2f32(vm.x, va.x, t, 0, 0, 0);
+                            t = __builtin_amdgcn_mfma_f32_32x32x2f32(vm.y, va.y, t, 0, 0, 0);
+                            t = __builtin_amdgcn_mfma_f32_32x32x2f32(vm.z, va.z, t, 0, 0, 0);
+                            t = __builtin_amdgcn_mfma_f32_32x32x2f32(vm.w, va.w, t, 0, 0, 0);
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)  // L(a, kb), final (the stores depend on every load above through the products)
+                            *(global_ptr<f32x4_t>)(pa + 8 * q) = f32x4_t{t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]};
+                        float sum[KL_MAX_C];
+#pragma unroll
+                        for (int c = 0; c < KL_MAX_C; ++c) sum[c] = 0.f;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const float *z = &zs[(32 * kb + k2_jmap(h, r)) * KL_MAX_C];
+                            const float4 z0 = *reinterpret_cast<const float4 *>(z), z1 = *reinterpret_cast<const float4 *>(z + 4);
+                            const float l = t[r];
+                            sum[0] = fmaf(l, z0.x, sum[0]), sum[1] = fmaf(l, z0.y, sum[1]), sum[2] = fmaf(l, z0.z, sum[2]), sum[3] = fmaf(l, z0.w, sum[3]);
+                            sum[4] = fmaf(l, z1.x, sum[4]), sum[5] = fmaf(l, z1.y, sum[5]), sum[6] = fmaf(l, z1.z, sum[6]), sum[7] = fmaf(l, z1.w, sum[7]);
+                        }
+#pragma unroll
+                        for (int c = 0; c < KL_MAX_C; ++c) sum[c] += __shfl_xor(sum[c], 32);
+                        if (h == 0) {
+                            float *y = &zs[(32 * a + li) * KL_MAX_C];
+#pragma unroll
+                            for (int c = 0; c < KL_MAX_C; ++c) y[c] -= sum[c];
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            __syncthreads();
+            if (!deficient || attempt == 1) break;  // (uniform)
+            ridge = 8.f * drop_below;                // = n eps max K_ii / 8
+            __syncthreads();
+        }
+
+        if (nt == 0 && tid < KL_MAX_C) al[tid] = 0.f;  // (every train row dropped: the predictions' masked reads hit row 0)
+        // ---- back substitution L^T alpha = z, block column by block column from the last
+        for (int kb = nb - 1; kb >= 0; --kb) {
+            int li = li_, h = h_;
+            asm volatile("" : "+v"(li), "+v"(h));
+            {  // lane (j, h) sums L(a, kb)[i][j] alpha_a[i][.] over the 16 rows i of its half, this wave's blocks a ascending
+                float sum[KL_MAX_C];
+#pragma unroll
+                for (int c = 0; c < KL_MAX_C; ++c) sum[c] = 0.f;
+                for (int a = kb + 1 + wave; a < nb; a += KL_WAVES) {
+                    const global_ptr<const float> pl = S + kl_blk(a, kb) * 1024 + (16 * h) * 32 + li;
+#pragma unroll 4
+                    for (int ii = 0; ii < 16; ++ii) {
+                        const float l = pl[ii * 32];
+                        const float *av = &al[(32 * a + 16 * h + ii) * KL_MAX_C];
+                        const float4 a0 = *reinterpret_cast<const float4 *>(av), a1 = *reinterpret_cast<const float4 *>(av + 4);
+                        sum[0] = fmaf(l, a0.x, sum[0]), sum[1] = fmaf(l, a0.y, sum[1]), sum[2] = fmaf(l, a0.z, sum[2]), sum[3] = fmaf(l, a0.w, sum[3]);
+                        sum[4] = fmaf(l, a1.x, sum[4]), sum[5] = fmaf(l, a1.y, sum[5]), sum[6] = fmaf(l, a1.z, sum[6]), sum[7] = fmaf(l, a1.w, sum[7]);
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < KL_MAX_C; ++c) sum[c] += __shfl_xor(sum[c], 32);
+                if (h == 0) {
+#pragma unroll
+                    for (int c = 0; c < KL_MAX_C; ++c) part[wave][li][c] = sum[c];
+                }
+            }
+            __syncthreads();
+            if (wave == 0) {  // alpha_kb = M^T (z_kb - the waves' sums, in wave order)
+                float v[KL_MAX_C];
+                {
+                    const float4 r0 = *reinterpret_cast<const float4 *>(&zs[(32 * kb + li) * KL_MAX_C]), r1 = *reinterpret_cast<const float4 *>(&zs[(32 * kb + li) * KL_MAX_C + 4]);
+                    v[0] = r0.x, v[1] = r0.y, v[2] = r0.z, v[3] = r0.w, v[4] = r1.x, v[5] = r1.y, v[6] = r1.z, v[7] = r1.w;
+                }
+#pragma unroll
+                for (int w = 0; w < KL_WAVES; ++w) {
+                    const float4 p0 = *reinterpret_cast<const float4 *>(&part[w][li][0]), p1 = *reinterpret_cast<const float4 *>(&part[w][li][4]);
+                    v[0] -= p0.x, v[1] -= p0.y, v[2] -= p0.z, v[3] -= p0.w, v[4] -= p1.x, v[5] -= p1.y, v[6] -= p1.z, v[7] -= p1.w;
+                }
+                // v goes through the block's z slot so that every lane can read every row of it (one wave: its LDS operations are
+                // carried out in issue order); alpha_kb[i] = sum_j M[j][i] v[j], the lane halves split j
+                if (h == 0) {
+                    *reinterpret_cast<float4 *>(&zs[(32 * kb + li) * KL_MAX_C]) = make_float4(v[0], v[1], v[2], v[3]);
+                    *reinterpret_cast<float4 *>(&zs[(32 * kb + li) * KL_MAX_C + 4]) = make_float4(v[4], v[5], v[6], v[7]);
+                }
+                const global_ptr<const float> pm = S + kl_blk(kb, kb) * 1024 + (16 * h) * 32 + li;
+                float sum[KL_MAX_C];
+#pragma unroll
+                for (int c = 0; c < KL_MAX_C; ++c) sum[c] = 0.f;
+#pragma unroll 4
+                for (int jj = 0; jj < 16; ++jj) {
+                    const float m = pm[jj * 32];
+                    const float *vj = &zs[(32 * kb + 16 * h + jj) * KL_MAX_C];
+                    const float4 v0 = *reinterpret_cast<const float4 *>(vj), v1 = *reinterpret_cast<const float4 *>(vj + 4);
+                    sum[0] = fmaf(m, v0.x, sum[0]), sum[1] = fmaf(m, v0.y, sum[1]), sum[2] = fmaf(m, v0.z, sum[2]), sum[3] = fmaf(m, v0.w, sum[3]);
+                    sum[4] = fmaf(m, v1.x, sum[4]), sum[5] = fmaf(m, v1.y, sum[5]), sum[6] = fmaf(m, v1.z, sum[6]), sum[7] = fmaf(m, v1.w, sum[7]);
+                }
+#pragma unroll
+                for (int c = 0; c < KL_MAX_C; ++c) sum[c] += __shfl_xor(sum[c], 32);
+                if (h == 0) {
+                    const bool real = 32 * kb + li < nt;
+                    *reinterpret_cast<float4 *>(&al[(32 * kb + li) * KL_MAX_C]) = real ? make_float4(sum[0], sum[1], sum[2], sum[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    *reinterpret_cast<float4 *>(&al[(32 * kb + li) * KL_MAX_C + 4]) = real ? make_float4(sum[4], sum[5], sum[6], sum[7]) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+            __syncthreads();
+        }
+        // a class's weight as the predictions apply it: sqrt(size) x the scaled system's solution
+        if (deflated) {
+            for (int i = tid; i < nt * KL_MAX_C; i += KL_THREADS) al[i] *= sc[i / KL_MAX_C];
+        }
+        __syncthreads();
+
+        // ---- predictions: units of four validation rows dealt to the waves in turn, sixteen lanes per row; the lanes of a row split
+        //      the train rows (t = lane + 16 k, k ascending), a row's sum: its lanes' partial sums added by a four-step butterfly
+        {
+            const global_ptr<const int32_t> pval = has_ws ? ws + W_VAL : val;
+            const int g = lane >> 4, gl = lane & 15;
+            for (int unit = wave; 4 * unit < nv; unit += KL_WAVES) {
+                const int v = 4 * unit + g, vv = min(v, nv - 1), gv = pval[vv];
+                const global_ptr<const float> krow = K + static_cast<int64_t>(gv) * ldk;
+                float p[KL_MAX_C];
+#pragma unroll
+                for (int c = 0; c < KL_MAX_C; ++c) p[c] = 0.f;
+                for (int t0 = 0; t0 < nt; t0 += 16 * 8) {
+                    float kv[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int t = t0 + gl + 16 * k;
+                        const bool ok = t < nt;
+                        kv[k] = ok ? krow[tr_idx[ok ? t : 0]] : 0.f;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int t = t0 + gl + 16 * k;
+                        const int ta = t < nt ? t : 0;  // (kv is 0 there)
+                        const float4 a0 = *reinterpret_cast<const float4 *>(&al[ta * KL_MAX_C]), a1 = *reinterpret_cast<const float4 *>(&al[ta * KL_MAX_C + 4]);
+                        p[0] = fmaf(kv[k], a0.x, p[0]), p[1] = fmaf(kv[k], a0.y, p[1]), p[2] = fmaf(kv[k], a0.z, p[2]), p[3] = fmaf(kv[k], a0.w, p[3]);
+                        p[4] = fmaf(kv[k], a1.x, p[4]), p[5] = fmaf(kv[k], a1.y, p[5]), p[6] = fmaf(kv[k], a1.z, p[6]), p[7] = fmaf(kv[k], a1.w, p[7]);
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < KL_MAX_C; ++c)
+                    for (int o = 8; o > 0; o >>= 1) p[c] += __shfl_xor(p[c], o);  // (inside the row's 16 lanes: every lane ends with the sum)
+                int best = 0;
+                float bv = -3.4e38f;
+                for (int c = 0; c < C; ++c)
+                    if (p[c] > bv) {  // first maximum, like torch.argmax
+                        bv = p[c];
+                        best = c;
+                    }
+                const int want = has_ws ? ws[W_VAL + nv + vv] : labels[gv];
+                const unsigned long long hit = __ballot(gl == 0 && v < nv && best == want);
+                if (lane == 0 && hit) atomicAdd(&hits, __popcll(hit));
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            if (job->correct_out) *to_global(job->correct_out) = hits;
+            if (job->flags_out) *to_global(job->flags_out) = (ridge > 0.f ? 1 : 0) | (deflated ? 2 : 0) | (dropped ? 4 : 0);
+        }
+        __syncthreads();  // (the next problem's setup overwrites tr_idx, sc and hits)
+    }
+}
+
+int device_cus() {
+    static thread_local int cus = 0, cus_dev = -1;
+    if (cus_dev != wdg::current_device()) {
+        int dev = wdg::current_device(), n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n, cus_dev = dev;
+    }
+    return cus;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t wdg_kernel_regress_large_max_train(void) { return KL_MAX_N; }
+
+size_t wdg_kr_large_scratch_bytes(void) { return static_cast<size_t>(device_cus()) * KL_WG_BYTES; }
+
+size_t wdg_kr_large_workspace_bytes(int32_t n_train, int32_t n_val) {
+    const int p = klw_pad(n_train < 0 ? 0 : (n_train > KL_MAX_N ? KL_MAX_N : n_train));
+    return (static_cast<size_t>(KLW_TRAIN + 4 * p + 2 * (n_val > 0 ? n_val : 0)) * 4 + 255) & ~static_cast<size_t>(255);
+}
+
+int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream) {
+    WDG_REQUIRE(n_jobs >= 0, "kernel_regress_large_batched: negative size");
+    if (n_jobs == 0) return WDG_OK;
+    WDG_REQUIRE(jobs_dev != nullptr, "kernel_regress_large_batched: null job table");
+    WDG_REQUIRE(scratch != nullptr && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "kernel_regress_large_batched: the scratch buffer must be 16-byte aligned");
+    // one resident workgroup per CU (its 125 KB of LDS allow no second one) and per 2.1-MiB slice of the scratch buffer
+    const size_t slices = scratch_bytes / KL_WG_BYTES;
+    WDG_REQUIRE(slices >= 1, "kernel_regress_large_batched: %zu bytes of scratch, one workgroup needs %zu (wdg_kr_large_scratch_bytes)",
+                scratch_bytes, KL_WG_BYTES);
+    int wgs = device_cus();
+    if (n_jobs < wgs) wgs = n_jobs;
+    if (slices < static_cast<size_t>(wgs)) wgs = static_cast<int>(slices);
+    const int dwgs = n_jobs < 2 * device_cus() ? n_jobs : 2 * device_cus();
+    hipLaunchKernelGGL(kr_large_deflate_kernel, dim3(static_cast<unsigned>(dwgs)), dim3(KLD_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs);
+    if (const int rc = wdg::check_launch("kr_large_deflate_kernel")) return rc;
+    hipLaunchKernelGGL(kr_large_solve_kernel, dim3(static_cast<unsigned>(wgs)), dim3(KL_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs,
+                       static_cast<float *>(scratch));
+    return wdg::check_launch("kr_large_solve_kernel");
+}
+
+}  // extern "C"

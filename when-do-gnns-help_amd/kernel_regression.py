@@ -316,18 +316,46 @@ _KR_JOB_DTYPE = np.dtype([("K", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labe
 assert _KR_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.KrJob)
 
 
+_KR_LARGE_SCRATCH = {}  # (device, stream) -> the large solver's factor storage: launches on one stream run in order and share it
+
+
+def _kr_large_scratch(dev):
+    """the launch-level factor storage of wdg_kernel_regress_large_batched_f32 (CUs x 2.1 MiB: 540 MB on 256 CUs), one per device
+    and stream.  It is kept for the life of the process (a sweep launches a table per shard on the same few streams: the pipelining
+    streams of sweep.py are created once); release_kr_large_scratch() gives it back.  The key is the raw stream handle: a handle
+    the runtime hands out again after a stream was destroyed finds the old buffer, which is harmless - the destroyed stream's
+    launches have completed, and the new stream's run in order."""
+    key = (torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
+    if key not in _KR_LARGE_SCRATCH:
+        _KR_LARGE_SCRATCH[key] = torch.empty(int(lib.wdg_kr_large_scratch_bytes()), dtype=torch.uint8, device=dev)
+    return _KR_LARGE_SCRATCH[key]
+
+
+def release_kr_large_scratch():
+    """drop the large solver's cached factor storage (every device and stream); call it when no KrBatch on the large route is in
+    flight or will be launched again - a live table keeps its own reference until then"""
+    _KR_LARGE_SCRATCH.clear()
+
+
 class KrBatch:
-    """Job table for wdg_kernel_regress_batched_f32: many (kernel, train rows, validation rows) problems in one launch."""
+    """Job table for the batched kernel-regression solvers: many (kernel, train rows, validation rows) problems in one launch -
+    wdg_kernel_regress_batched_f32 (train blocks of up to 320 rows, register-resident) or, for a table that holds a larger block,
+    wdg_kernel_regress_large_batched_f32 (up to 1024 rows, the factor in device memory)."""
 
-    MAX_TRAIN = 320
+    MAX_TRAIN = 320         # the register-resident solver (csrc/kernel_reg.hip)
+    MAX_TRAIN_LARGE = 1024  # the solver whose factor lives in device memory (csrc/kernel_reg_large.hip)
     MAX_CLASSES = 8  # KR_MAX_C of csrc/kernel_reg.hip: the right-hand sides a problem's workgroup carries
+    ROUTES = ("auto", "registers", "large")
 
-    def __init__(self, problems, n_classes):
+    def __init__(self, problems, n_classes, route="auto"):
         """problems: list of (K [n, n] fp32 device, train int32 device [nt], val int32 device [nv], labels int32 device [n]
         [, rep int32 device [n] | None: the row representatives of the matrix K was computed from - GramBatch.rep[i]; the solver
         then deflates duplicate nodes instead of regularising the block])
-        -> self.correct [n_problems] int32 after launch().  Shapes the solver does not hold (more than 8 classes, more than
-        320 or fewer than 1 train rows) raise here: the kernel would answer them with the sentinel -1, and an accuracy of
+        route: "auto" - the register solver when every train block has at most 320 rows, else the WHOLE table through the large
+        solver (it holds any size from 1 up: still one launch); "registers" / "large" name the solver (tests push small problems
+        through the large one).
+        -> self.correct [n_problems] int32 after launch().  Shapes the chosen solver does not hold (more than 8 classes, more than
+        320 / 1024 or fewer than 1 train rows) raise here: the kernel would answer them with the sentinel -1, and an accuracy of
         -1 / n_val fed to the t-test is a silently wrong p-value (callers with such label sets take the host path)."""
         self.keep = problems
         n = len(problems)
@@ -335,25 +363,30 @@ class KrBatch:
         self._build(col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0])), col(lambda p_: p_[1].data_ptr()),
                     col(lambda p_: p_[2].data_ptr()), col(lambda p_: p_[3].data_ptr()), col(lambda p_: p_[1].shape[0]),
                     col(lambda p_: p_[2].shape[0]), n_classes,
-                    col(lambda p_: p_[4].data_ptr() if len(p_) > 4 and p_[4] is not None else 0))
+                    col(lambda p_: p_[4].data_ptr() if len(p_) > 4 and p_[4] is not None else 0), route=route)
 
     @classmethod
-    def from_arrays(cls, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, keep=None, rep_ptr=None):
+    def from_arrays(cls, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, keep=None, rep_ptr=None, route="auto"):
         """the same table from per-problem numpy columns (device addresses and sizes): a sweep shard's 20 000 problems are
         described by arithmetic on a few base pointers, not by 20 000 tensor objects"""
         self = cls.__new__(cls)
         self.keep = keep
         self._build(*(np.asarray(a, np.int64) for a in (k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val)), n_classes,
-                    None if rep_ptr is None else np.asarray(rep_ptr, np.int64))
+                    None if rep_ptr is None else np.asarray(rep_ptr, np.int64), route=route)
         return self
 
-    def _build(self, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, rep_ptr=None):
+    def _build(self, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, rep_ptr=None, route="auto"):
         dev = require_gpu()
         n = self.n_jobs = int(k_ptr.shape[0])
+        if route not in self.ROUTES:
+            raise ValueError(f"KrBatch: unknown route {route!r} (one of {', '.join(self.ROUTES)})")
         if n and not 1 <= int(n_classes) <= self.MAX_CLASSES:
             raise ValueError(f"KrBatch: {n_classes} classes, the solver holds 1..{self.MAX_CLASSES}")
-        if n and not (1 <= int(n_train.min()) and int(n_train.max()) <= self.MAX_TRAIN):
-            raise ValueError(f"KrBatch: {int(n_train.min())}..{int(n_train.max())} train rows, the solver holds blocks of 1..{self.MAX_TRAIN}")
+        self.large = route == "large" or (route == "auto" and bool(n) and int(n_train.max()) > self.MAX_TRAIN)
+        limit = self.MAX_TRAIN_LARGE if self.large else self.MAX_TRAIN
+        if n and not (1 <= int(n_train.min()) and int(n_train.max()) <= limit):
+            raise ValueError(f"KrBatch: {int(n_train.min())}..{int(n_train.max())} train rows, the solver holds blocks of 1..{limit}"
+                             + ("" if self.large else f" (route {route!r}; the large solver holds 1..{self.MAX_TRAIN_LARGE})"))
         if n and int(ldk.max()) >= 65536:  # (the solver's prediction gathers address a kernel matrix by 32-bit element offsets)
             raise ValueError(f"KrBatch: kernel matrices of leading dimension {int(ldk.max())}, the solver addresses up to 65 535")
         self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
@@ -368,13 +401,23 @@ class KrBatch:
         self.ws = None
         tab["rep"] = 0 if rep_ptr is None else rep_ptr
         if n and bool((tab["rep"] != 0).any()):
-            per = int(lib.wdg_kr_deflate_workspace_bytes(int(n_val.max())))
+            per = int(lib.wdg_kr_large_workspace_bytes(int(n_train.max()), int(n_val.max())) if self.large
+                      else lib.wdg_kr_deflate_workspace_bytes(int(n_val.max())))
             self.ws = torch.empty(n * per, dtype=torch.uint8, device=dev)
             tab["ws"] = self.ws.data_ptr() + per * np.arange(n, dtype=np.int64)
+        # (large) the factor storage belongs to the launch, not to the table: CUs x 2.1 MiB shared, in stream order, by the tables
+        # launched on one stream - taken here for the stream that is current now, and by launch() for the one current then
+        self.scratch = _kr_large_scratch(dev) if (self.large and n) else None
         self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
 
     def launch(self):
-        if self.ws is not None:
+        if self.large:
+            if self.n_jobs:
+                self.scratch = _kr_large_scratch(self.correct.device)
+            check(lib.wdg_kernel_regress_large_batched_f32(_ptr(self.table), self.n_jobs, _ptr(self.scratch),
+                                                           self.scratch.numel() if self.n_jobs else 0, stream_handle()),
+                  "wdg_kernel_regress_large_batched_f32")
+        elif self.ws is not None:
             check(lib.wdg_kernel_regress_deflated_batched_f32(_ptr(self.table), self.n_jobs, stream_handle()), "wdg_kernel_regress_deflated_batched_f32")
         else:
             check(lib.wdg_kernel_regress_batched_f32(_ptr(self.table), self.n_jobs, stream_handle()), "wdg_kernel_regress_batched_f32")

@@ -1170,12 +1170,18 @@ class KrPlan:
         """[jobs, 9] fp64: results() + ge_homo + the p-values KR_L (kernel_reg0) and KR_NL (kernel_reg1) of the Welch t-test
         over the epochs' accuracies (scipy on the host for the t distribution, as in the reference).
         ridge: what to do with the train blocks the device solver flags as rank deficient at fp32 rounding level
-          "device" (default; WDG_SWEEP_KR_RIDGE) - keep the solver's ridge answers (counted in kr_ridged / kr_total, announced once
-                   per shard with how far they lie from what the REFERENCE computed in the same epochs: the warning below);
+          "device" - keep the solver's ridge answers (counted in kr_ridged / kr_total, announced once per shard with how far they
+                   lie from what the REFERENCE computed in the same epochs: the warning below);
           "pinv"   - solve exactly those blocks again the reference's way (pinv_accuracies) and patch their accuracies before the
-                   t-tests: the reference-equal answer on the sweep path, at ~8 ms of one host core per flagged block
-                   (kr_pinv_seconds).  Nothing is flagged on the synthetic feature bases of bench.py; the pubmed-sample fixtures flag 39 %."""
-        ridge = ridge or os.environ.get("WDG_SWEEP_KR_RIDGE", "device")
+                   t-tests: the reference-equal answer on the sweep path, at ~8 ms of one host core per flagged 300-row block
+                   (kr_pinv_seconds).  Nothing is flagged on the synthetic feature bases of bench.py; the pubmed-sample fixtures flag 39 %.
+        The default (None -> WDG_SWEEP_KR_RIDGE when set) depends on the plan's solver: "device" for tables of up to 320 train rows,
+        whose flagged blocks are a few duplicate rows short of full rank and land within 2 - 4 validation rows of the reference;
+        "pinv" for a table on the large solver (KrBatch.large).  With more train rows than features (600 rows of 500 features:
+        EVERY linear-kernel block, short of full rank by 100 dimensions) the ridge answer and the reference's pinv, which inverts
+        that block's rounding-level singular values, are different estimators: measured up to 89 of 400 validation rows apart,
+        3 of 24 blocks within 2.  Such a sweep is reference-equal by default and pays the host for it."""
+        ridge = ridge or os.environ.get("WDG_SWEEP_KR_RIDGE") or ("pinv" if self.kr.large else "device")
         if ridge not in ("device", "pinv"):
             raise ValueError(f"full_metrics: ridge={ridge!r} (device | pinv)")
         self.kr_ridged = self.kr_deflated = self.kr_total = 0
@@ -1213,9 +1219,13 @@ class KrPlan:
             self.kr_pinv_seconds = time.perf_counter() - t0
         elif self.kr_ridged and os.environ.get("WDG_KR_QUIET", "0") in ("", "0"):
             import warnings
+            how_far = ("with more than 320 train rows that is NOT close to the reference where a block has fewer features than train rows: "
+                       "up to 89 of 400 validation rows from what the reference's pinv computed in the same epochs (DESIGN 4.8)"
+                       if self.kr.large else
+                       "within 0 - 2 validation rows of what the reference computed in the same epochs on the synthetic-sweep fixtures, "
+                       "4 on cora (profiles/r05_kr_three_way.txt)")
             warnings.warn(f"kernel regression: {self.kr_ridged} of {self.kr.n_jobs} train blocks of this shard were rank-deficient at fp32 "
-                          "rounding level and keep the device solver's ridge answers: within 0 - 2 validation rows of what the reference "
-                          "computed in the same epochs on the synthetic-sweep fixtures, 4 on cora (profiles/r05_kr_three_way.txt); "
+                          f"rounding level and keep the device solver's ridge answers: {how_far}; "
                           "full_metrics(ridge='pinv') / WDG_SWEEP_KR_RIDGE=pinv solves them again the reference's way on the host", stacklevel=2)
         acc = acc[self.kr_index]  # -> every job's accuracies (a shared raw-features problem is read by each job of its group)
         self.kr_acc = acc  # [job, classifier, epoch, (graph-aware, features only)]: diagnostics / tests

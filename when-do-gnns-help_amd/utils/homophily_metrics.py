@@ -244,8 +244,9 @@ LAST_KR_RIDGED = 0
 
 def _kernel_regression_on_device(features, adj, labels, sample_max, base_classifier, epochs):
     """the kernel-regression branch of classifier_based_performance_metric entirely on the GPU -> (p_value, seconds), or
-    None when the solver does not hold the problem: a train block of more than 320 rows or more than 8 classes (Coauthor_CS
-    15, Amazon_Computers 10, WikiCS 10: the caller then takes the reference's host path)"""
+    None when the solvers do not hold the problem: a train block of more than 1024 rows (KrBatch.MAX_TRAIN_LARGE; up to 320 rows
+    the register-resident solver runs, above that the one whose factor lives in device memory - KrBatch picks) or more than 8
+    classes (Coauthor_CS 15, Amazon_Computers 10, WikiCS 10: the caller then takes the reference's host path)"""
     from .util_funcs import kernel_regression_epoch_indices
     t_time = time.time()
     g = _graph(adj)
@@ -259,7 +260,7 @@ def _kernel_regression_on_device(features, adj, labels, sample_max, base_classif
         return None  # (before the node sets are drawn: the host path draws them itself, from the same generator state)
     rng_state = torch.get_rng_state()
     node_sets = kernel_regression_epoch_indices(labels, sample_max, epochs)  # (the generator is consumed as in the reference)
-    if not 1 <= min(tr.shape[0] for tr, _ in node_sets) or max(tr.shape[0] for tr, _ in node_sets) > ops.KrBatch.MAX_TRAIN:
+    if not 1 <= min(tr.shape[0] for tr, _ in node_sets) or max(tr.shape[0] for tr, _ in node_sets) > ops.KrBatch.MAX_TRAIN_LARGE:
         torch.set_rng_state(rng_state)  # the host path redraws the same sets
         return None
     h_agg = ops.spmm(g, features)
@@ -363,12 +364,13 @@ def classifier_based_performance_metric(features, adj, labels, sample_max, base_
     base_classifier 'gnb' (round 6): all epochs' Gaussian-naive-Bayes fits and predictions in one call of wdg_gnb_batched_f32
     (_gnb_on_device; scikit-learn's statistics bit for bit); WDG_GNB_SOLVER=host / solver="host" runs sklearn like the reference.
 
-    solver="device" (the default for the kernel-regression classifiers when a train block fits the solver: <= 320 rows;
+    solver="device" (the default for the kernel-regression classifiers when a train block fits a solver: <= 1024 rows;
     WDG_KR_SOLVER=host restores the reference's host path) keeps the metric on the GPU: the kernels of
     ALL nodes are computed once per call (the map is elementwise, so an epoch's kernel is a sub-block; graphs of more than
     16 384 nodes: the Gram of each epoch's sample instead), every epoch's node sets are drawn first - same generator, same
-    order as the reference -, and all 2 x epochs regressions run in ONE launch of the register-resident Cholesky solver
-    (wdg_kernel_regress_batched_f32).  For a positive definite train block the Cholesky solution is the pseudo-inverse's;
+    order as the reference -, and all 2 x epochs regressions run in ONE launch of a batched Cholesky solver: the register-resident
+    one up to 320 train rows (wdg_kernel_regress_batched_f32), above that - `sample_max` beyond 533 - the one whose factor lives in
+    device memory (wdg_kernel_regress_large_batched_f32).  For a positive definite train block the Cholesky solution is the pseudo-inverse's;
     per-epoch accuracies match the host path to a few validation nodes on well-conditioned kernels
     (tests/test_gpu_api.py); a rank-deficient block is refactored with a ridge at rounding level (include/wdg.h)."""
     solver = solver or os.environ.get("WDG_KR_SOLVER", "device")
