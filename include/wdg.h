@@ -461,6 +461,64 @@ size_t wdg_gnb_workspace_bytes(int32_t n_feat, int32_t n_classes);
 int wdg_gnb_batched_f32(const wdg_gnb_job *jobs_dev, int32_t n_jobs, int32_t max_feat, int32_t max_val, int32_t max_classes,
                         wdg_stream_t stream);
 
+/* ------------------------------------------------------------------ support vector classifiers (the svm_* base classifiers) */
+/*
+ * Batched C-SVC over a precomputed Gram: per problem, fit a one-vs-one support vector classifier on the train rows and predict the
+ * validation rows - the svm_rbf / svm_poly / svm_linear branches of the classifier-based performance metric, every (epoch, feature
+ * matrix) problem of a call in one call here (two launches: the solver, a wave per pair of classes; the predictor).
+ * The arithmetic is libsvm's C-SVC as scikit-learn calls it (tol 1e-3, no class weights), restated in tests/_svm_ref.py:
+ *   kernel entry  from G = 2 G_half: linear G_ij; poly (gamma G_ij)^degree (coef0 = 0); rbf exp(-gamma (G_ii + G_jj - 2 G_ij)) with
+ *                 G_ii = norm2[i]; evaluated in fp64 and rounded to fp32 for the solver (libsvm's kernel cache), fp64 diagonal,
+ *                 gradient and alphas; gamma <= 0: scikit-learn's 'scale', 1 / (F var) over all elements of the train rows, formed in
+ *                 fp64 from row_sum and norm2;
+ *   pair (p, q)   p < q among the classes present in the train rows: the train rows of p as +1, then those of q as -1, in the order
+ *                 of `train` (ascending ids, as boolean masks give them);
+ *   solver        SMO with second-order working-set selection (the LAST maximiser / minimiser wins a tie), libsvm's box clipping,
+ *                 stop at Gmax + Gmax2 < 1e-3 or after max_iter iterations of a pair (flag bit 0); no shrinking;
+ *   rho           mean of y G over the free alphas, without any the midpoint of the two bounds;
+ *   prediction    dec = sum_t alpha_t y_t K(v, t) - rho per pair in fp64 (unrounded kernel entries); > 0 votes p, otherwise q; the
+ *                 first class with the most votes.
+ * dec: [n_val, n_classes (n_classes - 1) / 2] fp64; a row's first P (P - 1) / 2 entries are the pairs of the P PRESENT classes in
+ * libsvm's order (0,1), (0,2) .. (P-2,P-1) over the present classes in ascending order, the rest is not written.
+ * info: {iterations of all pairs, the largest count of a pair, support vectors, flags}; flags bit 0: a pair stopped at max_iter
+ * before it converged; bit 1: fewer than two classes among the train rows - nothing is predicted, correct = 0.
+ * Limits: n_train <= 1024, n_classes <= 16, n_jobs <= 65535; labels in [0, n_classes).  ws: wdg_svm_workspace_bytes(n_train,
+ * n_classes) bytes per problem, 256-byte aligned (the solver leaves the coefficient table there: (n_classes - 1) n_train fp64
+ * coefficients, a rho and an iteration count per pair).
+ * replaces: `svm.SVC(kernel=.., ..).fit(X[idx_train], labels_sample[idx_train])` / `.predict(X[idx_val])` for X and X_agg and the two
+ *           accuracies (utils/homophily_metrics.py:313-333, utils/homophily_plot.py:334-354) inside the epoch loop of
+ *           classifier_based_performance_metric (utils/homophily_metrics.py:260-349).
+ */
+#define WDG_SVM_LINEAR 0
+#define WDG_SVM_POLY 1
+#define WDG_SVM_RBF 2
+#define WDG_SVM_FLAG_MAX_ITER 1
+#define WDG_SVM_FLAG_ONE_CLASS 2
+typedef struct {
+    const float *G_half;     /* [n, n] fp32, leading dimension ldk: K_linear of wdg_gram_map_batched_f32 = G / 2 exactly */
+    const float *norm2;      /* [n] the Gram's diagonal G_ii */
+    const double *row_sum;   /* [n] sum of every feature row in fp64 (NULL: allowed unless gamma <= 0 with a poly / rbf kernel) */
+    const int32_t *train;    /* [n_train] row ids, ascending */
+    const int32_t *val;      /* [n_val] row ids */
+    const int32_t *labels;   /* [n] class of every row */
+    void *ws;                /* wdg_svm_workspace_bytes(n_train, n_classes) bytes */
+    int32_t *correct;        /* out: hits among the validation rows */
+    int32_t *pred;           /* out [n_val]: predicted class (NULL: not wanted) */
+    double *dec;             /* out [n_val, n_classes (n_classes - 1) / 2]: pairwise decision values (NULL: not wanted) */
+    int32_t *info;           /* out [4]: total iterations, largest iteration count of a pair, support vectors, flags */
+    int64_t ldk;
+    double C;                /* box constraint */
+    double gamma;            /* <= 0: 'scale' */
+    int32_t kernel, degree;  /* WDG_SVM_LINEAR / _POLY / _RBF; degree of the polynomial */
+    int32_t max_iter;        /* iteration cap per pair */
+    int32_t n_train, n_val, n_classes;
+    int32_t F;               /* features per row (for gamma = 'scale') */
+    int32_t reserved;
+} wdg_svm_job;
+size_t wdg_svm_workspace_bytes(int32_t n_train, int32_t n_classes);
+int wdg_svm_batched_f32(const wdg_svm_job *jobs_dev, int32_t n_jobs, int32_t max_train, int32_t max_val, int32_t max_classes,
+                        wdg_stream_t stream);
+
 /* ------------------------------------------------------------------ per-edge cosine (SDDMM) */
 /*
  * out[i] = cos(x_u, x_v) for stored entry e_i = (u, v) (e_i = entries[i], or i when entries == NULL); NaN -> 0;

@@ -143,6 +143,8 @@ SIGNATURES = {
     "wdg_row_rep_batched": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_gnb_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_gnb_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_svm_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "wdg_svm_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_sweep_pack_f64": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "wdg_kr_deflate_workspace_bytes": (c_size_t, [c_int32]),
     "wdg_kernel_regress_deflated_batched_f32": (c_int, [c_void_p, c_int32, c_void_p]),
@@ -195,6 +197,15 @@ class GnbJob(ctypes.Structure):
     """mirror of `wdg_gnb_job` (include/wdg.h)"""
     _fields_ = [("X", c_void_p), ("train", c_void_p), ("val", c_void_p), ("labels", c_void_p), ("ws", c_void_p), ("correct", c_void_p),
                 ("pred", c_void_p), ("ldx", c_int64), ("n_train", c_int32), ("n_val", c_int32), ("F", c_int32), ("n_classes", c_int32)]
+
+
+class SvmJob(ctypes.Structure):
+    """mirror of `wdg_svm_job` (include/wdg.h)"""
+    _fields_ = [("G_half", c_void_p), ("norm2", c_void_p), ("row_sum", c_void_p), ("train", c_void_p), ("val", c_void_p),
+                ("labels", c_void_p), ("ws", c_void_p), ("correct", c_void_p), ("pred", c_void_p), ("dec", c_void_p), ("info", c_void_p),
+                ("ldk", c_int64), ("C", ctypes.c_double), ("gamma", ctypes.c_double), ("kernel", c_int32), ("degree", c_int32),
+                ("max_iter", c_int32), ("n_train", c_int32), ("n_val", c_int32), ("n_classes", c_int32), ("F", c_int32),
+                ("reserved", c_int32)]
 
 
 class KrSampleJob(ctypes.Structure):

@@ -506,3 +506,109 @@ class GnbBatch:
         hits = self.correct[:self.n_jobs].cpu().numpy().astype(np.float32)
         with np.errstate(invalid="ignore", divide="ignore"):
             return hits / self.n_val.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------- support vector classifiers (svm_*)
+_SVM_JOB_DTYPE = np.dtype([("G_half", "<u8"), ("norm2", "<u8"), ("row_sum", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labels", "<u8"),
+                           ("ws", "<u8"), ("correct", "<u8"), ("pred", "<u8"), ("dec", "<u8"), ("info", "<u8"), ("ldk", "<i8"),
+                           ("C", "<f8"), ("gamma", "<f8"), ("kernel", "<i4"), ("degree", "<i4"), ("max_iter", "<i4"), ("n_train", "<i4"),
+                           ("n_val", "<i4"), ("n_classes", "<i4"), ("F", "<i4"), ("reserved", "<i4")])
+assert _SVM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.SvmJob)
+
+
+class SvmBatch:
+    """Job table for wdg_svm_batched_f32: many (Gram, train rows, validation rows) one-vs-one C-SVC problems in one call - the svm_rbf /
+    svm_poly / svm_linear branches of classifier_based_performance_metric (utils/homophily_metrics.py:313-333), libsvm's arithmetic as
+    scikit-learn calls it (csrc/svm.hip; tests/_svm_ref.py restates it)."""
+
+    MAX_CLASSES = 16
+    MAX_TRAIN = 1024
+    KERNELS = {"linear": 0, "poly": 1, "rbf": 2}
+    FLAG_MAX_ITER, FLAG_ONE_CLASS = 1, 2
+
+    def __init__(self, problems, n_classes, kernel, C, gamma, degree=3, want_pred=False, want_dec=False, max_iter=None):
+        """problems: list of (G_half [n, n] fp32 device (K_linear of GramBatch; unit inner stride, any leading dimension), norm2 [n]
+        fp32 device (GramBatch.norm2), row_sum [n] fp64 device or None (the feature rows' sums: needed for gamma 'scale'), train int32
+        device [nt] ascending, val int32 device [nv], labels int32 device [n], F = features per row)
+        kernel: 'linear' | 'poly' (coef0 = 0) | 'rbf';  gamma: a positive number, or 'scale' / None for 1 / (F var of the train rows)
+        max_iter: iteration cap per pair of classes (None: 1000 x the problem's train rows)
+        -> after launch(): self.correct [n_problems] int32, self.info [n_problems, 4] int32 (iterations, largest count of a pair,
+        support vectors, flags); want_pred: self.pred[i] int32 [nv]; want_dec: self.dec[i] fp64 [nv, n_classes (n_classes - 1) / 2]
+        (the pairs of the PRESENT classes first, in libsvm's order; a positive value votes for the lower class).
+        Raises ValueError for what the kernel does not hold: more than 16 classes, more than 1024 train rows, no train rows, another
+        dtype than fp32."""
+        dev = require_gpu()
+        self.keep = problems
+        n = self.n_jobs = len(problems)
+        self.n_classes = int(n_classes)
+        if kernel not in self.KERNELS:
+            raise ValueError(f"SvmBatch: unknown kernel {kernel!r}")
+        if n and not 1 <= self.n_classes <= self.MAX_CLASSES:
+            raise ValueError(f"SvmBatch: {n_classes} classes, the kernel holds 1..{self.MAX_CLASSES}")
+        scale = gamma is None or gamma == "scale"
+        if not scale and not float(gamma) > 0:
+            raise ValueError("SvmBatch: gamma must be positive or 'scale'")
+        if not float(C) > 0:
+            raise ValueError("SvmBatch: C must be positive")
+        for g, n2, rs, tr, va, lab, feat in problems:
+            if g.dim() != 2 or g.dtype != torch.float32 or g.stride(1) != 1 or not g.is_cuda or g.shape[0] != g.shape[1]:
+                raise ValueError("SvmBatch: G_half must be a square row-major fp32 device matrix")
+            if n2.dtype != torch.float32 or n2.shape[0] != g.shape[0] or not n2.is_contiguous():
+                raise ValueError("SvmBatch: norm2 must be fp32 [n]")
+            if rs is not None and (rs.dtype != torch.float64 or rs.shape[0] != g.shape[0] or not rs.is_contiguous()):
+                raise ValueError("SvmBatch: row_sum must be fp64 [n]")
+            if rs is None and scale and kernel != "linear":
+                raise ValueError("SvmBatch: gamma 'scale' needs the rows' sums")
+            if tr.dtype != torch.int32 or va.dtype != torch.int32 or lab.dtype != torch.int32:
+                raise ValueError("SvmBatch: int32 node ids and labels expected")
+            if not 1 <= tr.shape[0] <= self.MAX_TRAIN:
+                raise ValueError(f"SvmBatch: {tr.shape[0]} train rows, the solver holds 1..{self.MAX_TRAIN}")
+            if lab.shape[0] != g.shape[0] or int(feat) < 1:
+                raise ValueError("SvmBatch: one label per row of the Gram and at least one feature")
+        col = lambda f: np.fromiter((f(p_) for p_ in problems), np.int64, n)  # noqa: E731
+        n_train, n_val = col(lambda p_: p_[3].shape[0]), col(lambda p_: p_[4].shape[0])
+        self.max_train, self.max_val, self.n_val = int(n_train.max(initial=0)), int(n_val.max(initial=0)), n_val
+        self.n_pairs = self.n_classes * (self.n_classes - 1) // 2
+        self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        self.info = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
+        ws_each = np.array([int(lib.wdg_svm_workspace_bytes(int(t), self.n_classes)) for t in n_train], np.int64)
+        ws_off = np.concatenate([[0], np.cumsum(ws_each)]).astype(np.int64)
+        self.ws = torch.empty(max(int(ws_off[-1]), 256), dtype=torch.uint8, device=dev)
+        self.pred = self.dec = None
+        tab = np.zeros(n, _SVM_JOB_DTYPE)
+        tab["G_half"], tab["ldk"] = col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0]))
+        tab["norm2"], tab["row_sum"] = col(lambda p_: p_[1].data_ptr()), col(lambda p_: 0 if p_[2] is None else p_[2].data_ptr())
+        tab["train"], tab["val"], tab["labels"] = col(lambda p_: p_[3].data_ptr()), col(lambda p_: p_[4].data_ptr()), col(lambda p_: p_[5].data_ptr())
+        tab["ws"] = self.ws.data_ptr() + ws_off[:-1]
+        tab["correct"] = self.correct.data_ptr() + 4 * np.arange(n, dtype=np.int64)
+        tab["info"] = self.info.data_ptr() + 16 * np.arange(n, dtype=np.int64)
+        v_off = np.concatenate([[0], np.cumsum(n_val)]).astype(np.int64)
+        if want_pred:
+            pool = torch.full((max(int(v_off[-1]), 1),), -1, dtype=torch.int32, device=dev)
+            self.pred = [pool[int(v_off[i]):int(v_off[i + 1])] for i in range(n)]
+            tab["pred"] = pool.data_ptr() + 4 * v_off[:-1]
+        if want_dec:
+            w = max(self.n_pairs, 1)
+            pool = torch.zeros((max(int(v_off[-1]), 1), w), dtype=torch.float64, device=dev)
+            self.dec = [pool[int(v_off[i]):int(v_off[i + 1])] for i in range(n)]
+            tab["dec"] = pool.data_ptr() + 8 * w * v_off[:-1]
+        tab["C"], tab["gamma"] = float(C), 0.0 if scale else float(gamma)
+        tab["kernel"], tab["degree"] = self.KERNELS[kernel], int(degree)
+        tab["max_iter"] = np.minimum(1000 * n_train, 2 ** 31 - 1) if max_iter is None else int(max_iter)
+        tab["n_train"], tab["n_val"], tab["n_classes"], tab["F"] = n_train, n_val, self.n_classes, col(lambda p_: int(p_[6]))
+        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self):
+        check(lib.wdg_svm_batched_f32(_ptr(self.table), self.n_jobs, self.max_train, self.max_val, self.n_classes, stream_handle()),
+              "wdg_svm_batched_f32")
+
+    def flags(self):
+        """[n_problems] int32 (host): bit 0 a pair stopped at max_iter, bit 1 fewer than two classes among the train rows"""
+        return self.info[:self.n_jobs, 3].cpu().numpy()
+
+    def accuracy(self):
+        """[n_problems] float32 (host): hits / validation rows, as `torch.mean(pred.eq(labels[idx_val]).float())` gives them
+        (utils/homophily_metrics.py:328-329); NaN for a problem without validation rows"""
+        hits = self.correct[:self.n_jobs].cpu().numpy().astype(np.float32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return hits / self.n_val.astype(np.float32)

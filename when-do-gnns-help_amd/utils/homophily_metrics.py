@@ -353,6 +353,90 @@ def _gnb_on_device(features, adj, labels, sample_max, epochs):
     return p, time.time() - t_time
 
 
+LAST_SVM_ACCURACIES = None  # [epoch, (graph-aware, features only)] of the last device SVM call: diagnostics / tests
+LAST_SVM_INFO = None        # [2 x epochs, 4] int32: iterations, largest count of a pair, support vectors, flags
+# the reference's parameters (utils/homophily_metrics.py:316-324); gamma None = scikit-learn's default 'scale'
+SVM_PARAMS = {'svm_rbf': dict(kernel='rbf', gamma=0.5, C=0.1, degree=3), 'svm_poly': dict(kernel='poly', gamma=None, C=1.0, degree=3),
+              'svm_linear': dict(kernel='linear', gamma=None, C=1.0, degree=3)}
+
+
+def _linear_gram(a):
+    """(G / 2, diag G, fp64 row sums) of a feature matrix: what ops.SvmBatch reads"""
+    a = a.contiguous()
+    gb = ops.GramBatch([a], linear=True, arccos=False)
+    gb.row_rep = None  # (the duplicate-row maps serve the regression solver only)
+    gb.launch()
+    return gb.k_linear[0], gb.norm2[0], a.sum(dim=1, dtype=torch.float64)
+
+
+def _svm_on_device(features, adj, labels, sample_max, base_classifier, epochs):
+    """the svm_rbf / svm_poly / svm_linear branches of classifier_based_performance_metric (utils/homophily_metrics.py:313-333) on
+    the GPU -> (p_value, seconds), or None when the solver does not hold the problem (more than 16 classes, a train block of more
+    than 1024 rows: the caller then runs scikit-learn on the host like the reference).  The epochs' node sets are drawn first - same
+    generator, same order as the reference -, the aggregation and the Gram of all nodes are computed once per call (graphs of more
+    than 16 384 nodes: the Gram of each epoch's sample), then all 2 x epochs fits and predictions run in ONE call of
+    wdg_svm_batched_f32 (csrc/svm.hip: libsvm's solver as scikit-learn calls it, a wave per pair of classes).  A problem whose
+    solver stopped at its iteration cap (1000 x train rows per pair) is solved again with scikit-learn on the host, with a warning;
+    a train block with a single class raises like scikit-learn."""
+    from .util_funcs import kernel_regression_epoch_indices
+    global LAST_SVM_ACCURACIES, LAST_SVM_INFO
+    t_time = time.time()
+    g = _graph(adj)
+    dev = g.device
+    features = features.to(dev, torch.float32).contiguous()
+    labels = labels.to(dev).flatten()
+    lab32 = labels.to(torch.int32)
+    n_cls = int(labels.max().item()) + 1
+    if n_cls > ops.SvmBatch.MAX_CLASSES or int(labels.min().item()) < 0 or features.shape[1] < 1:
+        return None  # (before the node sets are drawn: the host path draws them itself, from the same generator state)
+    rng_state = torch.get_rng_state()
+    node_sets = kernel_regression_epoch_indices(labels, sample_max, epochs)  # (the generator is consumed as in the reference)
+    if not 1 <= min(tr.shape[0] for tr, _ in node_sets) or max(tr.shape[0] for tr, _ in node_sets) > ops.SvmBatch.MAX_TRAIN:
+        torch.set_rng_state(rng_state)  # the host path redraws the same sets
+        return None
+    prm = SVM_PARAMS[base_classifier]
+    h_agg = ops.spmm(g, features)
+    n_feat = features.shape[1]
+    problems = []
+    if labels.shape[0] <= FULL_KERNEL_MAX_NODES:
+        gram_g, gram_x = _linear_gram(h_agg), _linear_gram(features)
+        for tr, va in node_sets:
+            tr, va = tr.to(dev, torch.int32), va.to(dev, torch.int32)
+            problems += [(*gram_g, tr, va, lab32, n_feat), (*gram_x, tr, va, lab32, n_feat)]
+    else:  # Grams of each epoch's sample only (rows: train first, then validation - both ascending)
+        for tr, va in node_sets:
+            rows = torch.cat([tr, va]).to(dev)
+            lt = torch.arange(tr.shape[0], dtype=torch.int32, device=dev)
+            lv = torch.arange(tr.shape[0], rows.shape[0], dtype=torch.int32, device=dev)
+            problems += [(*_linear_gram(h_agg[rows]), lt, lv, lab32[rows], n_feat), (*_linear_gram(features[rows]), lt, lv, lab32[rows], n_feat)]
+    sb = ops.SvmBatch(problems, n_cls, prm['kernel'], prm['C'], prm['gamma'], degree=prm['degree'])
+    sb.launch()
+    acc = torch.from_numpy(sb.accuracy()).reshape(-1)
+    flags = sb.flags()
+    LAST_SVM_INFO = sb.info[:sb.n_jobs].cpu()
+    if (flags & ops.SvmBatch.FLAG_ONE_CLASS).any():
+        raise ValueError("The number of classes has to be greater than one; got 1 class")  # (scikit-learn's message)
+    capped = np.nonzero(flags & ops.SvmBatch.FLAG_MAX_ITER)[0]
+    if capped.shape[0]:
+        import warnings
+        from sklearn import svm
+        warnings.warn(f"{base_classifier}: {capped.shape[0]} of {len(problems)} problems reached the device solver's iteration cap; "
+                      "they were solved again with scikit-learn on the host", stacklevel=3)
+        lab_cpu = labels.cpu()
+        for i in capped.tolist():
+            tr, va = node_sets[i // 2]
+            x = (h_agg if i % 2 == 0 else features)
+            model = svm.SVC(kernel=prm['kernel'], C=prm['C'], degree=prm['degree'], gamma='scale' if prm['gamma'] is None else prm['gamma'])
+            model.fit(x[tr.to(dev)].cpu(), lab_cpu[tr])
+            acc[i] = torch.mean(torch.tensor(model.predict(x[va.to(dev)].cpu())).eq(lab_cpu[va]).float())
+    acc = acc.reshape(epochs, 2)
+    LAST_SVM_ACCURACIES = acc.clone()
+    G_results, X_results = acc[:, 0], acc[:, 1]
+    _, p = ttest_ind(X_results, G_results, axis=0, equal_var=False, nan_policy='propagate')
+    p = p / 2 if torch.mean((G_results > X_results).float()) <= 0.5 else 1 - p / 2
+    return p, time.time() - t_time
+
+
 def classifier_based_performance_metric(features, adj, labels, sample_max, base_classifier='kernel_reg1', epochs=100,
                                         solver=None):
     """Classifier-based performance metric -> (p_value, seconds).  reference: utils/homophily_metrics.py:260-349.
@@ -360,7 +444,12 @@ def classifier_based_performance_metric(features, adj, labels, sample_max, base_
     GPU: the aggregation A X (hoisted out of the epoch loop - it is loop invariant), the sampled
     Gram products and the arc-cosine map (hoisted too when nnodes <= sample_max: the sample is then every node).
     Host, exactly as in the reference: split sampling from torch's CPU generator, `np.linalg.pinv` (the reference
-    moves the kernels to the CPU for it, :286-290), sklearn SVM, scipy's Welch t-test.
+    moves the kernels to the CPU for it, :286-290), scipy's Welch t-test.
+    base_classifier 'svm_rbf' / 'svm_poly' / 'svm_linear': all epochs' one-vs-one support vector fits and predictions in one call of
+    wdg_svm_batched_f32 over the linear Gram of all nodes (_svm_on_device; libsvm's solver as scikit-learn calls it, restated in
+    tests/_svm_ref.py: decision values agree with scikit-learn's within its own stopping tolerance, so a validation row can differ
+    only where a decision value is that close to zero); WDG_SVM_SOLVER=host / solver="host" runs sklearn like the reference, as do
+    more than 16 classes or more than 1024 train rows.
     base_classifier 'gnb' (round 6): all epochs' Gaussian-naive-Bayes fits and predictions in one call of wdg_gnb_batched_f32
     (_gnb_on_device; scikit-learn's statistics bit for bit); WDG_GNB_SOLVER=host / solver="host" runs sklearn like the reference.
 
@@ -383,6 +472,10 @@ def classifier_based_performance_metric(features, adj, labels, sample_max, base_
         solver = "host"  # (a train block larger than the solver holds)
     if base_classifier == 'gnb' and solver == "device" and os.environ.get("WDG_GNB_SOLVER", "device") != "host":
         res = _gnb_on_device(features, adj, labels, sample_max, epochs)
+        if res is not None:
+            return res
+    if base_classifier in SVM_PARAMS and solver == "device" and os.environ.get("WDG_SVM_SOLVER", "device") != "host":
+        res = _svm_on_device(features, adj, labels, sample_max, base_classifier, epochs)
         if res is not None:
             return res
     from sklearn import svm
