@@ -5,7 +5,8 @@
 // replaces: the kernel-regression branch of classifier_based_performance_metric (utils/homophily_metrics.py:283-297,
 //           utils/homophily_plot.py:296-310: `K_val_train @ (np.linalg.pinv(K_train_train) @ onehot[idx_train])`, argmax, accuracy).
 //
-//   * kr_deflate_kernel the deflation pre-pass: one row per duplicate class of the train rows (below);
+//   * kr_deflate_kernel the deflation pre-pass: one row per duplicate class of the train rows (csrc/kr_deflate.h: the routine
+//                       and the layout of the workspace it fills, shared with csrc/kernel_reg_large.hip);
 //   * kr_solve_blocked_kernel
 //                       one workgroup per (graph, classifier, epoch, kernel) problem: gathers the train block K[tr, tr] from
 //                       the graph's kernel into REGISTERS (up to 320 x 320), factors it (right-looking blocked Cholesky, the
@@ -19,6 +20,7 @@
 
 #include "wdg_common.h"
 #include "kr_blocks.h"
+#include "kr_deflate.h"
 
 namespace {
 
@@ -61,148 +63,16 @@ using namespace wdg;
 // round 2's 8 n eps max K_ii was 3 - 22 rows off on the rank-deficient real kernels.  The factorisation is redone ONCE on
 // K + lambda I, pivots clamped to the test level.
 constexpr int K2_THREADS = 1024, K2_WAVES = 16, K2_NB = 10, K2_SLOTS = 3;  // (K2_PS, the image stride: kr_blocks.h)
-constexpr int KR_MAX_N = K2_NB * 32, KR_MAX_C = 8;  // train rows (320) and classes of a problem
-// the deflation workspace of a problem (wdg_kr_job.ws, filled by kr_deflate_kernel, read by the solver), as int32 words:
-//   [KRW_NT] rows to solve, [KRW_DEFLATED] != 0 when fewer than n_train, [KRW_DROPPED] != 0 when rows were dropped below the block's
-//   resolution (flags bit 2), [KRW_TRAIN ..] their representatives (padded with -1),
-//   [KRW_VAL ..] n_val validation representatives, then n_val labels
-//   [KRW_LAB ..] a solved row's label when all members of its duplicate class carry the same one (right-hand side: sqrt(size) in that
-//   column), -2 for a class with MIXED labels, whose non-zero right-hand-side entries are listed in [KRW_MIX ..]: [KRW_MIXED] words
-//   (row << 16 | label << 12 | members with that label); [KRW_SCALE ..] sqrt(members) of a solved row's duplicate class (fp32 bits):
-//   the solver factors M = S K S, S = diag of these
-constexpr int KRW_NT = 0, KRW_DEFLATED = 1, KRW_MIXED = 2, KRW_DROPPED = 3, KRW_TRAIN = 4, KRW_LAB = KRW_TRAIN + K2_NB * 32, KRW_SCALE = KRW_LAB + K2_NB * 32,
-              KRW_MIX = KRW_SCALE + K2_NB * 32, KRW_VAL = KRW_MIX + K2_NB * 32;
+constexpr int KR_MAX_N = K2_NB * 32;  // train rows of a problem (320; its classes, KR_MAX_C: kr_deflate.h)
+// the deflation workspace of a problem (wdg_kr_job.ws; kr_deflate.h holds the layout) at this solver's fixed stride of KR_MAX_N words
+constexpr krw_offsets KRW(KR_MAX_N);
+constexpr int KRW_LAB = KRW.lab, KRW_SCALE = KRW.scale, KRW_MIX = KRW.mix, KRW_VAL = KRW.val;
 static_assert(K2_NB * (K2_NB - 1) / 2 <= K2_WAVES * K2_SLOTS, "every block below the diagonal needs a register slot");
 
-// Deflation pre-pass (one workgroup per problem): with the row representatives of the matrix K was computed from (wdg_kr_job.rep,
-// csrc/row_rep.hip) every id is taken at its representative - duplicate rows of K are then identical by construction -, the train
-// rows are DEFLATED to one row per duplicate class with the class's mean one-hot label as right-hand side, and rows whose K_ii is
-// exactly 0 (all-zero feature rows under the linear kernel) are dropped.  That is the answer of the reference's
-// `np.linalg.pinv(K_train_train) @ label_onehot[idx_train]` (utils/homophily_metrics.py:291-297) on an exactly singular block: the
-// minimum-norm solution shares a class's weight among its members, K[v, members] sums it up again.  With P the members-to-class
-// incidence matrix and D = P^T P (the class sizes), K_tt = P K_u P^T = Q (D^1/2 K_u D^1/2) Q^T with Q = P D^-1/2 orthonormal, so
-// pinv(K_tt) = Q pinv(M) Q^T, M = S K_u S, S = D^1/2: the solver factors the SCALED block M with right-hand sides S^-1 P^T Y (a
-// class's label counts over sqrt(size)) and multiplies the solution by S - for a regular K_u the same as K_u^-1 (mean label), and
-// for a K_u that is rank deficient beyond its duplicates (texas: aggregated rows that are sums of others) the regularised answer
-// keeps the full system's metric (the unscaled form was up to 26 validation rows from the reference there).  The solver reads the
-// result from the problem's workspace and factors a positive definite block where round 5 added a rounding-level ridge.
-constexpr int KD_THREADS = 320;
-static_assert(KD_THREADS == K2_NB * 32, "one thread per train row");
+// Deflation pre-pass (kr_deflate.h), one workgroup per problem, one thread per train row
+constexpr int KD_THREADS = KR_MAX_N;
 __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job *__restrict__ jobs) {
-    __shared__ int d_raw[KD_THREADS], d_lab[KD_THREADS], d_first[KD_THREADS], d_slot[KD_THREADS], d_mult[KD_THREADS];
-    __shared__ float rhs[KD_THREADS * KR_MAX_C];
-    __shared__ int n_keep, any_mixed, any_drop;
-    const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)(jobs + blockIdx.x);
-    if (job->ws == nullptr) return;  // (uniform)
-    const int tid = threadIdx.x, nt_in = job->n_train, nv = job->n_val;
-    const global_ptr<int32_t> ws = to_global(static_cast<int32_t *>(job->ws));
-    if (nt_in <= 0 || nt_in > KD_THREADS) {  // (the solver refuses the problem by its own test; the workspace must still be sane)
-        if (tid == 0) ws[KRW_NT] = -1, ws[KRW_DEFLATED] = 0, ws[KRW_DROPPED] = 0;
-        return;
-    }
-    const global_ptr<const float> K = to_global(job->K);
-    const global_ptr<const int32_t> train = to_global(job->train), val = to_global(job->val), labels = to_global(job->labels),
-                                    rep = to_global(job->rep);
-    const bool has_rep = job->rep != nullptr;  // (without the maps every node is its own representative: zero rows are still dropped)
-    const int64_t ldk = job->ldk;
-    if (tid == 0) n_keep = 0, any_mixed = 0, any_drop = 0;
-    int r = -1, lb = -1;
-    float diag = 0.f;
-    if (tid < nt_in) {
-        const int g = train[tid];
-        r = has_rep ? rep[g] : g, lb = labels[g];
-        diag = K[static_cast<int64_t>(r) * ldk + r];
-    }
-    // rows BELOW THE BLOCK'S fp32 RESOLUTION are dropped (weight 0): K_ii <= n eps max K_ii / 64 - the level of the solver's pivot
-    // test, so that a row the solver would factor as it is is never dropped (a hub-heavy kernel's diagonal spans 1e-5 of its maximum
-    // and more).  The two agree exactly when nothing is merged; after merges the solver tests the merged count against the diagonal
-    // of S K S (class sizes >= 1: its maximum is no smaller), so a row kept here may still meet the solver's ridge -:
-    // an all-zero row of K (an isolated node's
-    // aggregated features, an all-zero feature row under the linear kernel: an exact zero singular value, which the pseudo-inverse
-    // cuts), and the arc-cosine kernel's row of such a node (every entry 1.6e-9: a singular value 1e-12 of the largest, which an
-    // fp32 SVD cannot resolve - the reference's pinv leaves it no weight either: measured on texas, where factoring that row
-    // exactly, as an fp64 pseudo-inverse would, moved an epoch 24 validation rows away from the reference's)
-    float dmax = diag == diag ? diag : 0.f;
-    for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
-    if ((tid & 63) == 0) rhs[tid >> 6] = dmax;  // (rhs doubles as the waves' maxima; zeroed below)
-    __syncthreads();
-    dmax = 0.f;
-    for (int w = 0; w < KD_THREADS / 64; ++w) dmax = fmaxf(dmax, rhs[w]);
-    if (tid < nt_in && !(diag > static_cast<float>(nt_in) * 1.1920929e-7f * dmax * (1.f / 64.f))) r = -2, any_drop = 1;
-    __syncthreads();
-    d_raw[tid] = r, d_lab[tid] = lb, d_mult[tid] = 0;
-    for (int i = tid; i < KD_THREADS * KR_MAX_C; i += KD_THREADS) rhs[i] = 0.f;
-    __syncthreads();
-    int first = r < 0 ? -1 : tid;  // the first train row with this representative
-    if (r >= 0)  // (eight ids per step, tested together: a one-at-a-time loop with an early exit waits for every LDS read)
-        for (int j0 = 0; j0 < tid && first == tid; j0 += 8) {
-            int v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = d_raw[min(j0 + e, KD_THREADS - 1)];
-#pragma unroll
-            for (int e = 7; e >= 0; --e)
-                if (v[e] == r && j0 + e < tid) first = j0 + e;  // (descending: the smallest match stays)
-        }
-    d_first[tid] = first;
-    // a kept row's slot = the kept rows before it (train ids ascend: so do the slots' rows): ballot prefix inside a wave + the
-    // earlier waves' counts
-    const bool keep = first == tid;
-    const unsigned long long kmask = __ballot(keep);
-    const int lane = tid & 63, wv = tid >> 6;
-    if (lane == 0) d_mult[wv] = __popcll(kmask);  // (d_mult doubles as the per-wave counts until the barrier; zeroed again below)
-    __syncthreads();
-    int slot = -1;
-    if (keep) {
-        slot = __popcll(kmask & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wv; ++w) slot += d_mult[w];
-        d_slot[tid] = slot;
-    }
-    if (tid == 0) {
-        int total = 0;
-        for (int w = 0; w < KD_THREADS / 64; ++w) total += d_mult[w];
-        n_keep = total;
-    }
-    __syncthreads();
-    if (tid < KD_THREADS / 64) d_mult[tid] = 0;
-    __syncthreads();
-    if (first >= 0 && first != tid) slot = d_slot[first];
-    if (first == tid) d_first[slot] = r;  // (d_first is free now: the kept representatives, compact)
-    if (slot >= 0) {  // (counts of small integers: exact in any order)
-        atomicAdd(&d_mult[slot], 1);
-        if (lb >= 0 && lb < KR_MAX_C) atomicAdd(&rhs[slot * KR_MAX_C + lb], 1.f);
-    }
-    __syncthreads();
-    const int kept = n_keep;
-    ws[KRW_TRAIN + tid] = tid < kept ? d_first[tid] : -1;
-    // slot `tid`: pure (every member one label -> that label; members without a label in range -> -1: a zero row) or mixed
-    int pure = -1;
-    bool mixed = false;
-    if (tid < kept) {
-        const float m = static_cast<float>(d_mult[tid]);
-        int nz = 0;
-        for (int c = 0; c < KR_MAX_C; ++c) {
-            const float cnt = rhs[tid * KR_MAX_C + c];
-            if (cnt != 0.f) ++nz, pure = c;
-            if (cnt != 0.f && cnt != m) mixed = true;
-        }
-        mixed |= nz > 1;
-        if (mixed) {  // (a (row, label) pair per train row at most: the list never outgrows its K2_NB * 32 words)
-            pure = -2;
-            for (int c = 0; c < KR_MAX_C; ++c) {
-                const int cnt = static_cast<int>(rhs[tid * KR_MAX_C + c]);
-                if (cnt > 0) ws[KRW_MIX + atomicAdd(&any_mixed, 1)] = (tid << 16) | (c << 12) | cnt;
-            }
-        }
-    }
-    ws[KRW_LAB + tid] = pure;
-    ws[KRW_SCALE + tid] = __builtin_bit_cast(int, tid < kept ? sqrtf(static_cast<float>(d_mult[tid])) : 1.f);
-    for (int v = tid; v < nv; v += KD_THREADS) {
-        const int g = val[v];
-        ws[KRW_VAL + v] = has_rep ? rep[g] : g;
-        ws[KRW_VAL + nv + v] = labels[g];
-    }
-    __syncthreads();
-    if (tid == 0) ws[KRW_NT] = kept, ws[KRW_DEFLATED] = kept != nt_in, ws[KRW_MIXED] = any_mixed, ws[KRW_DROPPED] = any_drop;
+    kr_deflate_one<KD_THREADS>(jobs + blockIdx.x, KR_MAX_N);
 }
 
 #ifdef K2_PROFILE  // diagnostic build (make EXTRA=-DK2_PROFILE): thread 0 of workgroup 0 sums the shader clocks spent per phase
@@ -746,14 +616,10 @@ int kernel_regress_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, bool defla
         const char *e = getenv("WDG_KR_PERSIST");
         return !(e && atoi(e) == 0 && e[0] != '\0');
     }();
-    static thread_local int cus = 0, cus_dev = -1;
-    if (cus_dev != wdg::current_device()) {
-        int dev = wdg::current_device(), n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n, cus_dev = dev;
-    }
+    const int cus = wdg::device_cus();
     if (deflated) {
         hipLaunchKernelGGL(kr_deflate_kernel, dim3(static_cast<unsigned>(n_jobs)), dim3(KD_THREADS), 0, wdg::as_stream(stream), jobs_dev);
+        if (const int rc = wdg::check_launch("kr_deflate_kernel")) return rc;
         hipLaunchKernelGGL(kr_solve_blocked_kernel<true>, dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
                            wdg::as_stream(stream), jobs_dev, n_jobs);
     } else hipLaunchKernelGGL(kr_solve_blocked_kernel<false>, dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
@@ -775,8 +641,6 @@ int wdg_kernel_regress_deflated_batched_f32(const wdg_kr_job *jobs_dev, int32_t 
 
 int32_t wdg_kernel_regress_max_train(void) { return KR_MAX_N; }
 
-size_t wdg_kr_deflate_workspace_bytes(int32_t n_val) {
-    return (static_cast<size_t>(KRW_VAL + 2 * (n_val > 0 ? n_val : 0)) * 4 + 255) & ~static_cast<size_t>(255);
-}
+size_t wdg_kr_deflate_workspace_bytes(int32_t n_val) { return krw_bytes(KR_MAX_N, n_val); }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 //           utils/homophily_plot.py:296-310: `K_val_train @ (np.linalg.pinv(K_train_train) @ onehot[idx_train])`, argmax, accuracy)
 //           for `--sample_max` above 533 (homophily_tests.py:54), where an epoch's train block outgrows the register solver.
 //
-//   * kr_large_deflate_kernel  the deflation pre-pass of kernel_reg.hip, one thread per train row, for 1024 rows, persistent over the table;
+//   * kr_large_deflate_kernel  the deflation pre-pass (csrc/kr_deflate.h) for up to 1024 train rows, persistent over the table;
 //   * kr_large_solve_kernel    one workgroup of 8 waves per problem, persistent over the job table.
 //
 //   storage  the factor as packed 32 x 32 blocks of the lower triangle (block (a, b), b <= a, at (a (a + 1) / 2 + b) x 4 KiB, row-major,
@@ -32,145 +32,26 @@
 // ldk < 65 536, the sentinel -1 for shapes out of range.
 #include "wdg_common.h"
 #include "kr_blocks.h"
+#include "kr_deflate.h"
 
 namespace {
 
 using namespace wdg;
 
-constexpr int KL_THREADS = 512, KL_WAVES = 8, KL_NB = 32, KL_MAX_N = KL_NB * 32, KL_MAX_C = 8;
+constexpr int KL_THREADS = 512, KL_WAVES = 8, KL_NB = 32, KL_MAX_N = KL_NB * 32, KL_MAX_C = KR_MAX_C;
 constexpr int KL_SLOTS = 5;                         // blocks of one column a wave holds: ceil((KL_NB - 1) / (KL_WAVES - 1))
 constexpr int KL_CH = 8;                            // blocks of the row panel staged in LDS at a time
 constexpr int KL_BLOCKS = KL_NB * (KL_NB + 1) / 2;  // 528 blocks of the lower triangle
 constexpr size_t KL_WG_BYTES = static_cast<size_t>(KL_BLOCKS) * 4096;
 static_assert((KL_NB - 1 + KL_WAVES - 2) / (KL_WAVES - 1) <= KL_SLOTS, "every block of a column needs a register slot");
 
-// the deflation workspace of a problem (wdg_kr_job.ws), as int32 words - kernel_reg.hip's layout with the four per-row arrays sized
-// by the problem's OWN train rows, P = n_train rounded up to 32: [0] rows to solve, [1] != 0 when fewer than n_train, [2] listed
-// mixed-label entries, [3] != 0 when rows were dropped, [4 ..] representatives (padded with -1), [4 + P ..] labels (-2: mixed),
-// [4 + 2 P ..] sqrt(members) (fp32 bits), [4 + 3 P ..] the mixed list (row << 16 | label << 12 | members with that label),
-// [4 + 4 P ..] n_val validation representatives, then n_val labels
-constexpr int KLW_NT = 0, KLW_DEFLATED = 1, KLW_MIXED = 2, KLW_DROPPED = 3, KLW_TRAIN = 4;
-__host__ __device__ constexpr int klw_pad(int n_train) { return (n_train + 31) & ~31; }
-
-// Deflation pre-pass: kernel_reg.hip's kr_deflate_kernel (its comment holds the algebra and the drop rule) for up to 1024 train rows
+// Deflation pre-pass (kr_deflate.h: the routine and the layout of the workspace, whose four per-row arrays take P = the problem's OWN
+// train rows rounded up to 32 words each here), one thread per train row.  Persistent over the job table like the solver: a table
+// without workspaces costs two workgroups per CU that read its ws pointers, not a workgroup per problem
 constexpr int KLD_THREADS = KL_MAX_N;
-__device__ void kl_deflate_one(const wdg_kr_job *__restrict__ job_ptr) {
-    __shared__ int d_raw[KLD_THREADS], d_lab[KLD_THREADS], d_first[KLD_THREADS], d_slot[KLD_THREADS], d_mult[KLD_THREADS];
-    __shared__ float rhs[KLD_THREADS * KL_MAX_C];
-    __shared__ int n_keep, any_mixed, any_drop;
-    const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)job_ptr;
-    if (job->ws == nullptr) return;  // (uniform) solved as it is
-    const int tid = threadIdx.x, nt_in = job->n_train, nv = job->n_val;
-    const global_ptr<int32_t> ws = to_global(static_cast<int32_t *>(job->ws));
-    if (nt_in <= 0 || nt_in > KLD_THREADS) {  // (the solver refuses the problem by its own test; the workspace must still be sane)
-        if (tid == 0) ws[KLW_NT] = -1, ws[KLW_DEFLATED] = 0, ws[KLW_MIXED] = 0, ws[KLW_DROPPED] = 0;
-        return;
-    }
-    const int P = klw_pad(nt_in), W_LAB = KLW_TRAIN + P, W_SCALE = W_LAB + P, W_MIX = W_SCALE + P, W_VAL = W_MIX + P;
-    const global_ptr<const float> K = to_global(job->K);
-    const global_ptr<const int32_t> train = to_global(job->train), val = to_global(job->val), labels = to_global(job->labels),
-                                    rep = to_global(job->rep);
-    const bool has_rep = job->rep != nullptr;  // (without the maps every node is its own representative: zero rows are still dropped)
-    const int64_t ldk = job->ldk;
-    if (tid == 0) n_keep = 0, any_mixed = 0, any_drop = 0;
-    int r = -1, lb = -1;
-    float diag = 0.f;
-    if (tid < nt_in) {
-        const int g = train[tid];
-        r = has_rep ? rep[g] : g, lb = labels[g];
-        diag = K[static_cast<int64_t>(r) * ldk + r];
-    }
-    // rows below the block's fp32 resolution are dropped: K_ii <= n eps max K_ii / 64, the level of the solver's pivot test
-    float dmax = diag == diag ? diag : 0.f;
-    for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
-    if ((tid & 63) == 0) rhs[tid >> 6] = dmax;  // (rhs doubles as the waves' maxima; zeroed below)
-    __syncthreads();
-    dmax = 0.f;
-    for (int w = 0; w < KLD_THREADS / 64; ++w) dmax = fmaxf(dmax, rhs[w]);
-    if (tid < nt_in && !(diag > static_cast<float>(nt_in) * 1.1920929e-7f * dmax * (1.f / 64.f))) r = -2, any_drop = 1;
-    __syncthreads();
-    d_raw[tid] = r, d_lab[tid] = lb, d_mult[tid] = 0;
-    for (int i = tid; i < KLD_THREADS * KL_MAX_C; i += KLD_THREADS) rhs[i] = 0.f;
-    __syncthreads();
-    int first = r < 0 ? -1 : tid;  // the first train row with this representative
-    if (r >= 0)
-        for (int j0 = 0; j0 < tid && first == tid; j0 += 8) {
-            int v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = d_raw[min(j0 + e, KLD_THREADS - 1)];
-#pragma unroll
-            for (int e = 7; e >= 0; --e)
-                if (v[e] == r && j0 + e < tid) first = j0 + e;  // (descending: the smallest match stays)
-        }
-    d_first[tid] = first;
-    // a kept row's slot = the kept rows before it: ballot prefix inside a wave + the earlier waves' counts
-    const bool keep = first == tid;
-    const unsigned long long kmask = __ballot(keep);
-    const int lane = tid & 63, wv = tid >> 6;
-    if (lane == 0) d_mult[wv] = __popcll(kmask);  // (d_mult doubles as the per-wave counts until the barrier; zeroed again below)
-    __syncthreads();
-    int slot = -1;
-    if (keep) {
-        slot = __popcll(kmask & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wv; ++w) slot += d_mult[w];
-        d_slot[tid] = slot;
-    }
-    if (tid == 0) {
-        int total = 0;
-        for (int w = 0; w < KLD_THREADS / 64; ++w) total += d_mult[w];
-        n_keep = total;
-    }
-    __syncthreads();
-    if (tid < KLD_THREADS / 64) d_mult[tid] = 0;
-    __syncthreads();
-    if (first >= 0 && first != tid) slot = d_slot[first];
-    __syncthreads();                       // (every read of d_slot / d_first as a map precedes the compaction below)
-    if (first == tid) d_first[slot] = r;  // (d_first is free now: the kept representatives, compact)
-    if (slot >= 0) {                       // (counts of small integers: exact in any order)
-        atomicAdd(&d_mult[slot], 1);
-        if (lb >= 0 && lb < KL_MAX_C) atomicAdd(&rhs[slot * KL_MAX_C + lb], 1.f);
-    }
-    __syncthreads();
-    const int kept = n_keep;
-    if (tid < P) ws[KLW_TRAIN + tid] = tid < kept ? d_first[tid] : -1;
-    // slot `tid`: pure (every member one label -> that label; members without a label in range -> -1: a zero row) or mixed
-    int pure = -1;
-    bool mixed = false;
-    if (tid < kept) {
-        const float m = static_cast<float>(d_mult[tid]);
-        int nz = 0;
-        for (int c = 0; c < KL_MAX_C; ++c) {
-            const float cnt = rhs[tid * KL_MAX_C + c];
-            if (cnt != 0.f) ++nz, pure = c;
-            if (cnt != 0.f && cnt != m) mixed = true;
-        }
-        mixed |= nz > 1;
-        if (mixed) {  // (a (row, label) pair per train row at most: the list never outgrows its P words)
-            pure = -2;
-            for (int c = 0; c < KL_MAX_C; ++c) {
-                const int cnt = static_cast<int>(rhs[tid * KL_MAX_C + c]);
-                if (cnt > 0) ws[W_MIX + atomicAdd(&any_mixed, 1)] = (tid << 16) | (c << 12) | cnt;
-            }
-        }
-    }
-    if (tid < P) {
-        ws[W_LAB + tid] = pure;
-        ws[W_SCALE + tid] = __builtin_bit_cast(int, tid < kept ? sqrtf(static_cast<float>(d_mult[tid])) : 1.f);
-    }
-    for (int v = tid; v < nv; v += KLD_THREADS) {
-        const int g = val[v];
-        ws[W_VAL + v] = has_rep ? rep[g] : g;
-        ws[W_VAL + nv + v] = labels[g];
-    }
-    __syncthreads();
-    if (tid == 0) ws[KLW_NT] = kept, ws[KLW_DEFLATED] = kept != nt_in, ws[KLW_MIXED] = any_mixed, ws[KLW_DROPPED] = any_drop;
-}
-
-// persistent over the job table like the solver: a table without workspaces costs two workgroups per CU that read its ws
-// pointers, not a workgroup per problem
 __global__ __launch_bounds__(KLD_THREADS) void kr_large_deflate_kernel(const wdg_kr_job *__restrict__ jobs, int n_jobs) {
     for (int prob = blockIdx.x; prob < n_jobs; prob += gridDim.x) {
-        kl_deflate_one(jobs + prob);
+        kr_deflate_one<KLD_THREADS>(jobs + prob, krw_pad(((desc_ptr<wdg_kr_job>)(jobs + prob))->n_train));
         __syncthreads();  // (the next problem's pass overwrites the shared arrays)
     }
 }
@@ -205,7 +86,7 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
                       (!has_ws && job->rep != nullptr);  // (representatives without a workspace: not solved as if there were none)
         int nt = nt_in;
         if (!refuse && has_ws) {
-            nt = ws[KLW_NT];
+            nt = ws[KRW_NT];
             refuse = nt < 0 || nt > nt_in;
         }
         if (refuse) {  // (uniform)
@@ -213,14 +94,14 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
             if (tid == 0 && job->flags_out) *to_global(job->flags_out) = 0;
             continue;
         }
-        const int P = klw_pad(nt_in), W_LAB = KLW_TRAIN + P, W_SCALE = W_LAB + P, W_MIX = W_SCALE + P, W_VAL = W_MIX + P;
-        const bool deflated = has_ws && ws[KLW_DEFLATED] != 0;
-        const bool dropped = has_ws && ws[KLW_DROPPED] != 0;
-        const int n_mixed = has_ws ? ws[KLW_MIXED] : 0;
+        const krw_offsets W(krw_pad(nt_in));
+        const bool deflated = has_ws && ws[KRW_DEFLATED] != 0;
+        const bool dropped = has_ws && ws[KRW_DROPPED] != 0;
+        const int n_mixed = has_ws ? ws[KRW_MIXED] : 0;
         const int nb = (nt + 31) >> 5;
         for (int i = tid; i < nb * 32; i += KL_THREADS) {
-            tr_idx[i] = i < nt ? (has_ws ? ws[KLW_TRAIN + i] : train[i]) : -1;
-            sc[i] = (has_ws && i < nt) ? __builtin_bit_cast(float, ws[W_SCALE + i]) : 1.f;
+            tr_idx[i] = i < nt ? (has_ws ? ws[KRW_TRAIN + i] : train[i]) : -1;
+            sc[i] = (has_ws && i < nt) ? __builtin_bit_cast(float, ws[W.scale + i]) : 1.f;
         }
         if (tid == 0) hits = 0;
         __syncthreads();
@@ -242,11 +123,11 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
                 const int row = i / KL_MAX_C, c = i % KL_MAX_C;
                 float v = 0.f;
                 if (row < nt) {
-                    const int lb = has_ws ? ws[W_LAB + row] : labels[tr_idx[row]];
+                    const int lb = has_ws ? ws[W.lab + row] : labels[tr_idx[row]];
                     v = lb == c ? sc[row] : 0.f;
                     if (lb == -2 && has_ws)  // (rare) a class of duplicates with different labels: its label counts over sqrt(size)
                         for (int e = 0; e < n_mixed; ++e) {
-                            const int w = ws[W_MIX + e];
+                            const int w = ws[W.mix + e];
                             if ((w >> 12) == ((row << 4) | c)) v = static_cast<float>(w & 0xfff) / sc[row];
                         }
                 }
@@ -484,7 +365,7 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
         // ---- predictions: units of four validation rows dealt to the waves in turn, sixteen lanes per row; the lanes of a row split
         //      the train rows (t = lane + 16 k, k ascending), a row's sum: its lanes' partial sums added by a four-step butterfly
         {
-            const global_ptr<const int32_t> pval = has_ws ? ws + W_VAL : val;
+            const global_ptr<const int32_t> pval = has_ws ? ws + W.val : val;
             const int g = lane >> 4, gl = lane & 15;
             for (int unit = wave; 4 * unit < nv; unit += KL_WAVES) {
                 const int v = 4 * unit + g, vv = min(v, nv - 1), gv = pval[vv];
@@ -519,7 +400,7 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
                         bv = p[c];
                         best = c;
                     }
-                const int want = has_ws ? ws[W_VAL + nv + vv] : labels[gv];
+                const int want = has_ws ? ws[W.val + nv + vv] : labels[gv];
                 const unsigned long long hit = __ballot(gl == 0 && v < nv && best == want);
                 if (lane == 0 && hit) atomicAdd(&hits, __popcll(hit));
             }
@@ -533,27 +414,16 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
     }
 }
 
-int device_cus() {
-    static thread_local int cus = 0, cus_dev = -1;
-    if (cus_dev != wdg::current_device()) {
-        int dev = wdg::current_device(), n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n, cus_dev = dev;
-    }
-    return cus;
-}
-
 }  // namespace
 
 extern "C" {
 
 int32_t wdg_kernel_regress_large_max_train(void) { return KL_MAX_N; }
 
-size_t wdg_kr_large_scratch_bytes(void) { return static_cast<size_t>(device_cus()) * KL_WG_BYTES; }
+size_t wdg_kr_large_scratch_bytes(void) { return static_cast<size_t>(wdg::device_cus()) * KL_WG_BYTES; }
 
 size_t wdg_kr_large_workspace_bytes(int32_t n_train, int32_t n_val) {
-    const int p = klw_pad(n_train < 0 ? 0 : (n_train > KL_MAX_N ? KL_MAX_N : n_train));
-    return (static_cast<size_t>(KLW_TRAIN + 4 * p + 2 * (n_val > 0 ? n_val : 0)) * 4 + 255) & ~static_cast<size_t>(255);
+    return krw_bytes(krw_pad(n_train < 0 ? 0 : (n_train > KL_MAX_N ? KL_MAX_N : n_train)), n_val);
 }
 
 int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream) {
@@ -565,10 +435,10 @@ int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_j
     const size_t slices = scratch_bytes / KL_WG_BYTES;
     WDG_REQUIRE(slices >= 1, "kernel_regress_large_batched: %zu bytes of scratch, one workgroup needs %zu (wdg_kr_large_scratch_bytes)",
                 scratch_bytes, KL_WG_BYTES);
-    int wgs = device_cus();
+    int wgs = wdg::device_cus();
     if (n_jobs < wgs) wgs = n_jobs;
     if (slices < static_cast<size_t>(wgs)) wgs = static_cast<int>(slices);
-    const int dwgs = n_jobs < 2 * device_cus() ? n_jobs : 2 * device_cus();
+    const int dwgs = n_jobs < 2 * wdg::device_cus() ? n_jobs : 2 * wdg::device_cus();
     hipLaunchKernelGGL(kr_large_deflate_kernel, dim3(static_cast<unsigned>(dwgs)), dim3(KLD_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs);
     if (const int rc = wdg::check_launch("kr_large_deflate_kernel")) return rc;
     hipLaunchKernelGGL(kr_large_solve_kernel, dim3(static_cast<unsigned>(wgs)), dim3(KL_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs,

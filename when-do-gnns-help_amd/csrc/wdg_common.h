@@ -47,6 +47,9 @@ inline int current_device() {
     (void)hipGetDevice(&dev);
     return dev;
 }
+// wdg_common.hip: the compute units of the calling thread's current device, queried once per device (256 when the query fails) -
+// what a persistent launcher sizes its grid by
+int device_cus();
 
 // Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Map a launch's linear block id
 // to a work item so that each XCD walks a CONTIGUOUS range of items: neighbouring items (adjacent feature

@@ -16,6 +16,16 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+int device_cus() {
+    static thread_local int cus = 0, cus_dev = -1;
+    if (cus_dev != current_device()) {
+        int dev = current_device(), n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n, cus_dev = dev;
+    }
+    return cus;
+}
+
 }  // namespace wdg
 
 extern "C" {

@@ -442,6 +442,25 @@ class KrBatch:
         return correct.to(torch.float32) / self.n_val
 
 
+# ------------------------------------------------------------------------------------------- what the GNB and SVM tables share
+def _pooled(counts, dtype, dev, fill=None, width=None, floor=1):
+    """One allocation for every job's `counts[i]` rows (of `width` elements each, when given) -> (pool, the jobs' views of it, the
+    views' device addresses [n] int64).  fill None: uninitialised; the pool holds at least `floor` rows (a table without jobs)."""
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    shape = (max(int(off[-1]), floor),) + (() if width is None else (width,))
+    pool = torch.empty(shape, dtype=dtype, device=dev) if fill is None else torch.full(shape, fill, dtype=dtype, device=dev)
+    views = [pool[int(off[i]):int(off[i + 1])] for i in range(len(counts))]
+    return pool, views, pool.data_ptr() + pool.element_size() * (width or 1) * off[:-1]
+
+
+def _host_hit_rate(correct, n_val):
+    """[n_problems] float32 (host): hits / validation rows, as `torch.mean(pred.eq(labels[idx_val]).float())` gives them
+    (utils/homophily_metrics.py:311-312, :328-329); NaN for a problem without validation rows"""
+    hits = correct.cpu().numpy().astype(np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return hits / n_val.astype(np.float32)
+
+
 # ------------------------------------------------------------------------------------------- Gaussian naive Bayes (the GNB classifier)
 _GNB_JOB_DTYPE = np.dtype([("X", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labels", "<u8"), ("ws", "<u8"), ("correct", "<u8"),
                            ("pred", "<u8"), ("ldx", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("F", "<i4"), ("n_classes", "<i4")])
@@ -479,20 +498,15 @@ class GnbBatch:
         self.max_feat, self.max_val = int(feats.max(initial=0)), int(n_val.max(initial=0))
         self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         self.n_val = n_val
-        ws_each = np.array([int(lib.wdg_gnb_workspace_bytes(int(f), self.n_classes)) for f in feats], np.int64)
-        ws_off = np.concatenate([[0], np.cumsum(ws_each)]).astype(np.int64)
-        self.ws = torch.empty(max(int(ws_off[-1]), 256), dtype=torch.uint8, device=dev)
+        self.ws, _, ws_ptr = _pooled([int(lib.wdg_gnb_workspace_bytes(int(f), self.n_classes)) for f in feats], torch.uint8, dev, floor=256)
         self.pred = None
         tab = np.zeros(n, _GNB_JOB_DTYPE)
         tab["X"], tab["ldx"] = col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0]))
         tab["train"], tab["val"], tab["labels"] = col(lambda p_: p_[1].data_ptr()), col(lambda p_: p_[2].data_ptr()), col(lambda p_: p_[3].data_ptr())
-        tab["ws"] = self.ws.data_ptr() + ws_off[:-1]
+        tab["ws"] = ws_ptr
         tab["correct"] = self.correct.data_ptr() + 4 * np.arange(n, dtype=np.int64)
         if want_pred:
-            v_off = np.concatenate([[0], np.cumsum(n_val)]).astype(np.int64)
-            pool = torch.full((max(int(v_off[-1]), 1),), -1, dtype=torch.int32, device=dev)
-            self.pred = [pool[int(v_off[i]):int(v_off[i + 1])] for i in range(n)]
-            tab["pred"] = pool.data_ptr() + 4 * v_off[:-1]
+            _, self.pred, tab["pred"] = _pooled(n_val, torch.int32, dev, fill=-1)
         tab["n_train"], tab["n_val"], tab["F"], tab["n_classes"] = col(lambda p_: p_[1].shape[0]), n_val, feats, self.n_classes
         self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
 
@@ -501,11 +515,8 @@ class GnbBatch:
               "wdg_gnb_batched_f32")
 
     def accuracy(self):
-        """[n_problems] float32 (host): hits / validation rows, as `torch.mean(pred.eq(labels[idx_val]).float())` gives them
-        (utils/homophily_metrics.py:311-312); NaN for a problem without validation rows"""
-        hits = self.correct[:self.n_jobs].cpu().numpy().astype(np.float32)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return hits / self.n_val.astype(np.float32)
+        """[n_problems] float32 (host): hits / validation rows (_host_hit_rate)"""
+        return _host_hit_rate(self.correct[:self.n_jobs], self.n_val)
 
 
 # ------------------------------------------------------------------------------------------- support vector classifiers (svm_*)
@@ -571,27 +582,19 @@ class SvmBatch:
         self.n_pairs = self.n_classes * (self.n_classes - 1) // 2
         self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         self.info = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
-        ws_each = np.array([int(lib.wdg_svm_workspace_bytes(int(t), self.n_classes)) for t in n_train], np.int64)
-        ws_off = np.concatenate([[0], np.cumsum(ws_each)]).astype(np.int64)
-        self.ws = torch.empty(max(int(ws_off[-1]), 256), dtype=torch.uint8, device=dev)
+        self.ws, _, ws_ptr = _pooled([int(lib.wdg_svm_workspace_bytes(int(t), self.n_classes)) for t in n_train], torch.uint8, dev, floor=256)
         self.pred = self.dec = None
         tab = np.zeros(n, _SVM_JOB_DTYPE)
         tab["G_half"], tab["ldk"] = col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0]))
         tab["norm2"], tab["row_sum"] = col(lambda p_: p_[1].data_ptr()), col(lambda p_: 0 if p_[2] is None else p_[2].data_ptr())
         tab["train"], tab["val"], tab["labels"] = col(lambda p_: p_[3].data_ptr()), col(lambda p_: p_[4].data_ptr()), col(lambda p_: p_[5].data_ptr())
-        tab["ws"] = self.ws.data_ptr() + ws_off[:-1]
+        tab["ws"] = ws_ptr
         tab["correct"] = self.correct.data_ptr() + 4 * np.arange(n, dtype=np.int64)
         tab["info"] = self.info.data_ptr() + 16 * np.arange(n, dtype=np.int64)
-        v_off = np.concatenate([[0], np.cumsum(n_val)]).astype(np.int64)
         if want_pred:
-            pool = torch.full((max(int(v_off[-1]), 1),), -1, dtype=torch.int32, device=dev)
-            self.pred = [pool[int(v_off[i]):int(v_off[i + 1])] for i in range(n)]
-            tab["pred"] = pool.data_ptr() + 4 * v_off[:-1]
+            _, self.pred, tab["pred"] = _pooled(n_val, torch.int32, dev, fill=-1)
         if want_dec:
-            w = max(self.n_pairs, 1)
-            pool = torch.zeros((max(int(v_off[-1]), 1), w), dtype=torch.float64, device=dev)
-            self.dec = [pool[int(v_off[i]):int(v_off[i + 1])] for i in range(n)]
-            tab["dec"] = pool.data_ptr() + 8 * w * v_off[:-1]
+            _, self.dec, tab["dec"] = _pooled(n_val, torch.float64, dev, fill=0.0, width=max(self.n_pairs, 1))
         tab["C"], tab["gamma"] = float(C), 0.0 if scale else float(gamma)
         tab["kernel"], tab["degree"] = self.KERNELS[kernel], int(degree)
         tab["max_iter"] = np.minimum(1000 * n_train, 2 ** 31 - 1) if max_iter is None else int(max_iter)
@@ -607,8 +610,5 @@ class SvmBatch:
         return self.info[:self.n_jobs, 3].cpu().numpy()
 
     def accuracy(self):
-        """[n_problems] float32 (host): hits / validation rows, as `torch.mean(pred.eq(labels[idx_val]).float())` gives them
-        (utils/homophily_metrics.py:328-329); NaN for a problem without validation rows"""
-        hits = self.correct[:self.n_jobs].cpu().numpy().astype(np.float32)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return hits / self.n_val.astype(np.float32)
+        """[n_problems] float32 (host): hits / validation rows (_host_hit_rate)"""
+        return _host_hit_rate(self.correct[:self.n_jobs], self.n_val)

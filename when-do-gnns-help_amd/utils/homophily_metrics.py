@@ -238,6 +238,52 @@ def gntk_homophily_(features, adj, sample, n_layers):
 
 
 FULL_KERNEL_MAX_NODES = 16384  # n x n fp32 kernels of all nodes: 1 GiB each at this size
+
+
+# What the device routes of classifier_based_performance_metric share.  Each route gates on ITS limits between the first two pieces -
+# before the node sets are drawn: a route that refuses hands the host path the generator where the reference would find it.
+def _device_inputs(features, adj, labels):
+    """-> (graph, device, features fp32 [n, F], labels [n], the labels as int32, classes counted as max label + 1)"""
+    g = _graph(adj)
+    dev = g.device
+    features = features.to(dev, torch.float32).contiguous()
+    labels = labels.to(dev).flatten()
+    return g, dev, features, labels, labels.to(torch.int32), int(labels.max().item()) + 1
+
+
+def _epoch_node_sets(labels, sample_max, epochs, train_limit=None):
+    """every epoch's (train ids, validation ids), drawn first - same generator, same order as the reference.  With a `train_limit`:
+    None when an epoch's train block lies outside 1..train_limit, and the generator is put back (the host path redraws the same sets)"""
+    from .util_funcs import kernel_regression_epoch_indices
+    rng_state = torch.get_rng_state() if train_limit is not None else None
+    node_sets = kernel_regression_epoch_indices(labels, sample_max, epochs)  # (the generator is consumed as in the reference)
+    if train_limit is not None and not (1 <= min(tr.shape[0] for tr, _ in node_sets) and max(tr.shape[0] for tr, _ in node_sets) <= train_limit):
+        torch.set_rng_state(rng_state)
+        return None
+    return node_sets
+
+
+def _epoch_blocks(node_sets, lab32, dev, whole):
+    """per epoch: (rows, train ids, validation ids, labels) as a device problem takes them.  `whole`: rows is None - the ids are the
+    graph's own, into operands computed once for all nodes.  Otherwise rows = the epoch's sample on the device (train first, then
+    validation - both ascending) - the caller computes its operands at these rows -, with local ids and the rows' labels"""
+    for tr, va in node_sets:
+        if whole:
+            yield None, tr.to(dev, torch.int32), va.to(dev, torch.int32), lab32
+        else:
+            rows = torch.cat([tr, va]).to(dev)
+            yield (rows, torch.arange(tr.shape[0], dtype=torch.int32, device=dev),
+                   torch.arange(tr.shape[0], rows.shape[0], dtype=torch.int32, device=dev), lab32[rows])
+
+
+def _welch_p(acc):
+    """[epochs, (graph-aware, features only)] accuracies (host) -> the metric's p-value: Welch's t-test, halved towards the side the
+    epochs favour (utils/homophily_metrics.py:340-347; the reference's mean(diff_results) is mean(G > X))"""
+    G_results, X_results = acc[:, 0], acc[:, 1]
+    _, p = ttest_ind(X_results, G_results, axis=0, equal_var=False, nan_policy='propagate')
+    return p / 2 if torch.mean((G_results > X_results).float()) <= 0.5 else 1 - p / 2
+
+
 LAST_KR_ACCURACIES = None
 LAST_KR_RIDGED = 0
 
@@ -247,36 +293,23 @@ def _kernel_regression_on_device(features, adj, labels, sample_max, base_classif
     None when the solvers do not hold the problem: a train block of more than 1024 rows (KrBatch.MAX_TRAIN_LARGE; up to 320 rows
     the register-resident solver runs, above that the one whose factor lives in device memory - KrBatch picks) or more than 8
     classes (Coauthor_CS 15, Amazon_Computers 10, WikiCS 10: the caller then takes the reference's host path)"""
-    from .util_funcs import kernel_regression_epoch_indices
     t_time = time.time()
-    g = _graph(adj)
-    dev = g.device
-    features = features.to(dev, torch.float32)
-    labels = labels.to(dev).flatten()
-    lab32 = labels.to(torch.int32)
-    n_cls = int(labels.max().item()) + 1
+    g, dev, features, labels, lab32, n_cls = _device_inputs(features, adj, labels)
     n_layers = 0 if base_classifier == 'kernel_reg0' else 1
     if n_cls > ops.KrBatch.MAX_CLASSES:
-        return None  # (before the node sets are drawn: the host path draws them itself, from the same generator state)
-    rng_state = torch.get_rng_state()
-    node_sets = kernel_regression_epoch_indices(labels, sample_max, epochs)  # (the generator is consumed as in the reference)
-    if not 1 <= min(tr.shape[0] for tr, _ in node_sets) or max(tr.shape[0] for tr, _ in node_sets) > ops.KrBatch.MAX_TRAIN_LARGE:
-        torch.set_rng_state(rng_state)  # the host path redraws the same sets
+        return None
+    node_sets = _epoch_node_sets(labels, sample_max, epochs, ops.KrBatch.MAX_TRAIN_LARGE)
+    if node_sets is None:
         return None
     h_agg = ops.spmm(g, features)
-    problems = []
-    if labels.shape[0] <= FULL_KERNEL_MAX_NODES:
+    whole = labels.shape[0] <= FULL_KERNEL_MAX_NODES  # else: kernels of each epoch's sample only
+    if whole:
         (k_g, rep_g), (k_x, rep_x) = _gram_kernel_rep(h_agg, n_layers), _gram_kernel_rep(features, n_layers)
-        for tr, va in node_sets:
-            tr, va = tr.to(dev, torch.int32), va.to(dev, torch.int32)
-            problems += [(k_g, tr, va, lab32, rep_g), (k_x, tr, va, lab32, rep_x)]
-    else:  # kernels of each epoch's sample only (rows: train first, then validation)
-        for tr, va in node_sets:
-            rows = torch.cat([tr, va]).to(dev)
+    problems = []
+    for rows, tr, va, lab in _epoch_blocks(node_sets, lab32, dev, whole):
+        if rows is not None:
             (k_g, rep_g), (k_x, rep_x) = _gram_kernel_rep(h_agg[rows], n_layers), _gram_kernel_rep(features[rows], n_layers)
-            lt = torch.arange(tr.shape[0], dtype=torch.int32, device=dev)
-            lv = torch.arange(tr.shape[0], rows.shape[0], dtype=torch.int32, device=dev)
-            problems += [(k_g, lt, lv, lab32[rows], rep_g), (k_x, lt, lv, lab32[rows], rep_x)]
+        problems += [(k_g, tr, va, lab, rep_g), (k_x, tr, va, lab, rep_x)]
     kb = ops.KrBatch(problems, n_cls)
     kb.launch()
     acc = kb.accuracy().cpu().reshape(-1)
@@ -311,10 +344,7 @@ def _kernel_regression_on_device(features, adj, labels, sample_max, base_classif
                          "solved with a ridge on the device (WDG_KR_RIDGE=device): their accuracies can differ from the reference's "
                          "pseudo-inverse by a few validation rows") + " (WDG_KR_SOLVER=host runs the whole metric on the reference's host path)",
                       stacklevel=3)
-    G_results, X_results = acc[:, 0], acc[:, 1]
-    _, p = ttest_ind(X_results, G_results, axis=0, equal_var=False, nan_policy='propagate')
-    p = p / 2 if torch.mean((G_results > X_results).float()) <= 0.5 else 1 - p / 2
-    return p, time.time() - t_time
+    return _welch_p(acc), time.time() - t_time
 
 
 LAST_GNB_ACCURACIES = None  # [epoch, (graph-aware, features only)] of the last device GNB call: diagnostics / tests
@@ -326,31 +356,21 @@ def _gnb_on_device(features, adj, labels, sample_max, epochs):
     reference).  The epochs' node sets are drawn first - same generator, same order as the reference -, then every epoch's two fits
     and predictions (aggregated features, raw features) run in ONE call of wdg_gnb_batched_f32, whose statistics are scikit-learn's
     bit for bit (csrc/gnb.hip; tests/test_gpu_gnb.py checks kernel and scikit-learn against each other)."""
-    from .util_funcs import kernel_regression_epoch_indices
     global LAST_GNB_ACCURACIES
     t_time = time.time()
-    g = _graph(adj)
-    dev = g.device
-    features = features.to(dev, torch.float32).contiguous()
-    labels = labels.to(dev).flatten()
-    lab32 = labels.to(torch.int32)
-    n_cls = int(labels.max().item()) + 1
+    g, dev, features, labels, lab32, n_cls = _device_inputs(features, adj, labels)
     if n_cls > ops.GnbBatch.MAX_CLASSES or int(labels.min().item()) < 0 or features.shape[1] < 1:
-        return None  # (before the node sets are drawn: the host path draws them itself, from the same generator state)
-    node_sets = kernel_regression_epoch_indices(labels, sample_max, epochs)  # (the generator is consumed as in the reference)
+        return None
+    node_sets = _epoch_node_sets(labels, sample_max, epochs)  # (no limit on the train rows: nothing is refused after the draw)
     h_agg = ops.spmm(g, features)
     problems = []
-    for tr, va in node_sets:
-        tr, va = tr.to(dev, torch.int32), va.to(dev, torch.int32)
-        problems += [(h_agg, tr, va, lab32), (features, tr, va, lab32)]
+    for _rows, tr, va, lab in _epoch_blocks(node_sets, lab32, dev, True):
+        problems += [(h_agg, tr, va, lab), (features, tr, va, lab)]
     gb = ops.GnbBatch(problems, n_cls)
     gb.launch()
     acc = torch.from_numpy(gb.accuracy()).reshape(epochs, 2)
     LAST_GNB_ACCURACIES = acc.clone()
-    G_results, X_results = acc[:, 0], acc[:, 1]
-    _, p = ttest_ind(X_results, G_results, axis=0, equal_var=False, nan_policy='propagate')
-    p = p / 2 if torch.mean((G_results > X_results).float()) <= 0.5 else 1 - p / 2
-    return p, time.time() - t_time
+    return _welch_p(acc), time.time() - t_time
 
 
 LAST_SVM_ACCURACIES = None  # [epoch, (graph-aware, features only)] of the last device SVM call: diagnostics / tests
@@ -378,37 +398,25 @@ def _svm_on_device(features, adj, labels, sample_max, base_classifier, epochs):
     wdg_svm_batched_f32 (csrc/svm.hip: libsvm's solver as scikit-learn calls it, a wave per pair of classes).  A problem whose
     solver stopped at its iteration cap (1000 x train rows per pair) is solved again with scikit-learn on the host, with a warning;
     a train block with a single class raises like scikit-learn."""
-    from .util_funcs import kernel_regression_epoch_indices
     global LAST_SVM_ACCURACIES, LAST_SVM_INFO
     t_time = time.time()
-    g = _graph(adj)
-    dev = g.device
-    features = features.to(dev, torch.float32).contiguous()
-    labels = labels.to(dev).flatten()
-    lab32 = labels.to(torch.int32)
-    n_cls = int(labels.max().item()) + 1
+    g, dev, features, labels, lab32, n_cls = _device_inputs(features, adj, labels)
     if n_cls > ops.SvmBatch.MAX_CLASSES or int(labels.min().item()) < 0 or features.shape[1] < 1:
-        return None  # (before the node sets are drawn: the host path draws them itself, from the same generator state)
-    rng_state = torch.get_rng_state()
-    node_sets = kernel_regression_epoch_indices(labels, sample_max, epochs)  # (the generator is consumed as in the reference)
-    if not 1 <= min(tr.shape[0] for tr, _ in node_sets) or max(tr.shape[0] for tr, _ in node_sets) > ops.SvmBatch.MAX_TRAIN:
-        torch.set_rng_state(rng_state)  # the host path redraws the same sets
+        return None
+    node_sets = _epoch_node_sets(labels, sample_max, epochs, ops.SvmBatch.MAX_TRAIN)
+    if node_sets is None:
         return None
     prm = SVM_PARAMS[base_classifier]
     h_agg = ops.spmm(g, features)
     n_feat = features.shape[1]
-    problems = []
-    if labels.shape[0] <= FULL_KERNEL_MAX_NODES:
+    whole = labels.shape[0] <= FULL_KERNEL_MAX_NODES  # else: Grams of each epoch's sample only
+    if whole:
         gram_g, gram_x = _linear_gram(h_agg), _linear_gram(features)
-        for tr, va in node_sets:
-            tr, va = tr.to(dev, torch.int32), va.to(dev, torch.int32)
-            problems += [(*gram_g, tr, va, lab32, n_feat), (*gram_x, tr, va, lab32, n_feat)]
-    else:  # Grams of each epoch's sample only (rows: train first, then validation - both ascending)
-        for tr, va in node_sets:
-            rows = torch.cat([tr, va]).to(dev)
-            lt = torch.arange(tr.shape[0], dtype=torch.int32, device=dev)
-            lv = torch.arange(tr.shape[0], rows.shape[0], dtype=torch.int32, device=dev)
-            problems += [(*_linear_gram(h_agg[rows]), lt, lv, lab32[rows], n_feat), (*_linear_gram(features[rows]), lt, lv, lab32[rows], n_feat)]
+    problems = []
+    for rows, tr, va, lab in _epoch_blocks(node_sets, lab32, dev, whole):
+        if rows is not None:
+            gram_g, gram_x = _linear_gram(h_agg[rows]), _linear_gram(features[rows])
+        problems += [(*gram_g, tr, va, lab, n_feat), (*gram_x, tr, va, lab, n_feat)]
     sb = ops.SvmBatch(problems, n_cls, prm['kernel'], prm['C'], prm['gamma'], degree=prm['degree'])
     sb.launch()
     acc = torch.from_numpy(sb.accuracy()).reshape(-1)
@@ -431,10 +439,7 @@ def _svm_on_device(features, adj, labels, sample_max, base_classifier, epochs):
             acc[i] = torch.mean(torch.tensor(model.predict(x[va.to(dev)].cpu())).eq(lab_cpu[va]).float())
     acc = acc.reshape(epochs, 2)
     LAST_SVM_ACCURACIES = acc.clone()
-    G_results, X_results = acc[:, 0], acc[:, 1]
-    _, p = ttest_ind(X_results, G_results, axis=0, equal_var=False, nan_policy='propagate')
-    p = p / 2 if torch.mean((G_results > X_results).float()) <= 0.5 else 1 - p / 2
-    return p, time.time() - t_time
+    return _welch_p(acc), time.time() - t_time
 
 
 def classifier_based_performance_metric(features, adj, labels, sample_max, base_classifier='kernel_reg1', epochs=100,
@@ -488,7 +493,7 @@ def classifier_based_performance_metric(features, adj, labels, sample_max, base_
     nnodes = labels.shape[0]
     if labels.dim() > 1:
         labels = labels.flatten()
-    G_results, X_results, diff_results = torch.zeros(epochs), torch.zeros(epochs), torch.zeros(epochs)
+    G_results, X_results = torch.zeros(epochs), torch.zeros(epochs)
     t_time = time.time()
     h_agg = ops.spmm(g, features)
     n_cls = int(labels.max().item()) + 1
@@ -542,9 +547,6 @@ def classifier_based_performance_metric(features, adj, labels, sample_max, base_
             X_pred, G_pred = torch.tensor(x_model.predict(X[idx_val])), torch.tensor(g_model.predict(X_agg[idx_val]))
             acc_g = torch.mean(G_pred.eq(labels_sample[idx_val]).float())
             acc_x = torch.mean(X_pred.eq(labels_sample[idx_val]).float())
-        diff_results[j] = (acc_g > acc_x)
         G_results[j], X_results[j] = acc_g, acc_x
 
-    _, p = ttest_ind(X_results.detach().cpu(), G_results.detach().cpu(), axis=0, equal_var=False, nan_policy='propagate')
-    p = p / 2 if torch.mean(diff_results) <= 0.5 else 1 - p / 2
-    return p, time.time() - t_time
+    return _welch_p(torch.stack([G_results, X_results], 1)), time.time() - t_time
