@@ -144,6 +144,46 @@ int wdg_row_l1_normalise_f32(const float *X, int64_t ldx, float *Y, int64_t ldy,
 int wdg_unpack_bits_f32(const uint32_t *words, int64_t ldw, int32_t N, int32_t F, int normalise, float *out, int64_t ldo,
                         wdg_stream_t stream);
 
+/*
+ * A LIST of compact feature matrices -> dense fp32 rows in one launch: sparse rows (CSR) or the container's bit-packed words,
+ * optionally with the row-L1 scaling of wdg_row_l1_normalise_f32 fused (csrc/features.hip).
+ * replaces: th.FloatTensor(features) / .todense() utils/util_funcs.py:339; preprocess_features utils/util_funcs.py:39-46;
+ *           f.normalize homophily_tests.py:94 - for feature matrices that are mostly zeros, without a dense host copy.
+ * For every job, every element of out[0:n_rows, 0:n_feat] is written (zeros included: no memset first) and nothing outside it:
+ * columns n_feat .. ldo - 1 keep what they held, so a job may expand straight into a wider operand.  ldo and n_feat need not be
+ * multiples of 4.
+ *   kind WDG_FEAT_CSR:  rowptr int32 [n_rows + 1], col int32 [nnz], val fp32 [nnz] or NULL (= 1.0).  Columns sorted and unique
+ *        within a row.  An entry whose column is not in [0, n_feat) is skipped - never stored through, left out of the row sum.
+ *   kind WDG_FEAT_BITS: words uint32 [n_rows, ldw], bit j of word w = feature 32 w + j (graph_io.py); bits past n_feat are padding.
+ *   normalise WDG_FEAT_NORM_SUM: wdg_row_l1_normalise_f32(use_abs = 0) of the expanded matrix - the row sum in fp64, s = (float)sum,
+ *        r = 1.0f / s, inf -> 0, y = r * x;  WDG_FEAT_NORM_ABS: use_abs = 1 - s over |x|, y = x / fmaxf(s, 1e-12f).
+ *        Bit-identical to that call where the fp64 row sum is exact in any order (0/1 features, fixed-point values), to fp64
+ *        rounding of the sum otherwise (the entries are summed in another order).  Zeros are +0 also in a row of negative sum,
+ *        where the dense call gives -0 (they compare equal).  WDG_FEAT_BITS equals wdg_unpack_bits_f32 bit for bit, either way.
+ * max_rows / max_feat: the largest n_rows / n_feat of the table (0: nothing to do).  Any number of jobs (launched 65535 at a time).
+ * wdg_features_image_floats: the floats of one row image of the CSR path - a wider row is written in several windows.
+ */
+#define WDG_FEAT_CSR 0
+#define WDG_FEAT_BITS 1
+#define WDG_FEAT_NORM_NONE 0
+#define WDG_FEAT_NORM_SUM 1
+#define WDG_FEAT_NORM_ABS 2
+typedef struct wdg_feat_job {
+    const int32_t *rowptr;  /* WDG_FEAT_CSR: [n_rows + 1] */
+    const int32_t *col;     /* WDG_FEAT_CSR: [nnz] */
+    const float *val;       /* WDG_FEAT_CSR: [nnz] or NULL = 1.0 */
+    const uint32_t *words;  /* WDG_FEAT_BITS: [n_rows, ldw] */
+    float *out;             /* [n_rows, ldo] */
+    int64_t ldw;            /* words between consecutive rows, >= ceil(n_feat / 32) */
+    int64_t ldo;            /* elements between consecutive output rows, >= n_feat */
+    int32_t n_rows, n_feat;
+    int32_t kind;           /* WDG_FEAT_CSR | WDG_FEAT_BITS */
+    int32_t normalise;      /* WDG_FEAT_NORM_* */
+} wdg_feat_job;
+int32_t wdg_features_image_floats(void);
+int wdg_features_expand_batched_f32(const wdg_feat_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat,
+                                    wdg_stream_t stream);
+
 /* ------------------------------------------------------------------ aggregation (SpMM) */
 /*
  * One aggregation problem:  Y[i,:] = row_scale[i] * sum_p val[p] * col_scale[col[p]] * X[col[p],:]

@@ -79,6 +79,8 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "wdg_row_l1_normalise_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p]),
     "wdg_unpack_bits_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p, c_int64, c_void_p]),
+    "wdg_features_image_floats": (c_int32, []),
+    "wdg_features_expand_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_spmm_csr_f32": (c_int, [ctypes.POINTER(SpmmJob), c_void_p]),
     "wdg_spmm_csr_bf16": (c_int, [ctypes.POINTER(SpmmJob), c_void_p]),
     "wdg_spmm_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int, c_void_p]),
@@ -154,6 +156,13 @@ SIGNATURES = {
     "wdg_kernel_regress_large_batched_f32": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "wdg_kr_sample_sets": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
 }
+
+
+class FeatJob(ctypes.Structure):
+    """mirror of `wdg_feat_job` (include/wdg.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("val", c_void_p), ("words", c_void_p), ("out", c_void_p),
+                ("ldw", c_int64), ("ldo", c_int64), ("n_rows", c_int32), ("n_feat", c_int32), ("kind", c_int32),
+                ("normalise", c_int32)]
 
 
 class Sell16Job(ctypes.Structure):

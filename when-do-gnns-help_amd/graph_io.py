@@ -11,9 +11,12 @@ without networkx, so that a dataset can be converted once where the raw files li
         i32 rowptr[n+1], i32 col[nnz]            CSR pattern, rows sorted by column (binary adjacency)
         i32 labels[n]
         features: kind 0 = none; 1 = fp32 dense [n, n_feat];
-                  2 = bit-packed binary [n, ceil(n_feat / 32)] u32 words, bit j of word w = feature 32 w + j
-Binary bag-of-words features (cora, citeseer, texas, film, ...) shrink 32x; `load_device` unpacks them on the GPU
-(`wdg_unpack_bits_f32`, optionally fused with the row-L1 normalisation of `preprocess_features`,
+                  2 = bit-packed binary [n, ceil(n_feat / 32)] u32 words, bit j of word w = feature 32 w + j;
+                  3 = CSR fp32: i64 nnz_feat, i32 rowptr[n+1], i32 col[nnz_feat], f32 val[nnz_feat] - rows sorted by column,
+                      no duplicates, no stored zeros (written only on request: save_graph(..., pack="csr"))
+Binary bag-of-words features (cora, citeseer, texas, film, ...) shrink 32x; sparse real-valued ones (pubmed's TF-IDF rows are
+10 % dense after `preprocess_features`) take kind 3.  `load_device` uploads kinds 2 and 3 compact and expands them on the GPU
+(`wdg_features_expand_batched_f32`, optionally fused with the row-L1 normalisation of `preprocess_features`,
 `utils/util_funcs.py:39-46`).
 """
 import os
@@ -24,7 +27,7 @@ import numpy as np
 
 MAGIC = b"WDGG"
 VERSION = 1
-FEAT_NONE, FEAT_F32, FEAT_BITS = 0, 1, 2
+FEAT_NONE, FEAT_F32, FEAT_BITS, FEAT_CSR = 0, 1, 2, 3
 
 
 # ------------------------------------------------------------------------------------------------ helpers
@@ -157,13 +160,27 @@ def unpack_bits(words, n_feat):
 
 
 def save_graph(path, rowptr, col, labels, features=None, n_classes=None, pack=None):
-    """Write the container.  `pack=None` bit-packs the features when every entry is 0 or 1."""
+    """Write the container.  `pack=None` bit-packs the features when every entry is 0 or 1 (True / False force the choice);
+    `pack="csr"` stores them as CSR fp32 (kind 3) - `features` may then be a dense array, an ops.SparseFeatures or a scipy matrix."""
     rowptr, col = np.asarray(rowptr, "<i4"), np.asarray(col, "<i4")
     labels = np.asarray(labels, "<i4")
     n = len(rowptr) - 1
     assert labels.shape == (n,) and rowptr[-1] == len(col)
     kind, n_feat, payload = FEAT_NONE, 0, b""
-    if features is not None:
+    if isinstance(pack, str) and pack != "csr":
+        raise ValueError(f"save_graph: pack={pack!r} (None, True, False or 'csr')")
+    if features is not None and isinstance(pack, str):
+        from .sparse_features import SparseFeatures, as_compact
+        sf = as_compact(features)
+        if sf is None:
+            sf = SparseFeatures.from_dense(features, kind="csr")
+        elif sf.kind != "csr":
+            sf = SparseFeatures.from_dense(sf.toarray(), kind="csr")
+        assert sf.shape[0] == n
+        n_feat, kind = sf.shape[1], FEAT_CSR
+        val = np.ones(sf.col.shape[0], "<f4") if sf.val is None else sf.val.astype("<f4")
+        payload = struct.pack("<q", sf.col.shape[0]) + sf.rowptr.astype("<i4").tobytes() + sf.col.astype("<i4").tobytes() + val.tobytes()
+    elif features is not None:
         features = np.asarray(features)
         n_feat = features.shape[1]
         if pack is None:
@@ -179,7 +196,8 @@ def save_graph(path, rowptr, col, labels, features=None, n_classes=None, pack=No
 
 
 def load_graph(path, unpack=True):
-    """-> dict(rowptr, col, labels, features | feature_words, n_nodes, n_feat, n_classes, feature_kind); host arrays."""
+    """-> dict(rowptr, col, labels, features | feature_words | feature_csr, n_nodes, n_feat, n_classes, feature_kind); host arrays.
+    feature_csr = (rowptr, col, val) of a kind-3 container; `unpack` adds the dense `features` of kinds 2 and 3."""
     with open(path, "rb") as f:
         blob = f.read()
     if blob[:4] != MAGIC:
@@ -199,15 +217,26 @@ def load_graph(path, unpack=True):
         out["feature_words"] = words
         if unpack:
             out["features"] = unpack_bits(words, n_feat)
+    elif kind == FEAT_CSR:
+        (nnz_feat,) = struct.unpack_from("<q", blob, off); off += 8
+        if not 0 <= nnz_feat <= (len(blob) - off - 4 * (n + 1)) // 8:
+            raise ValueError(f"{path}: {nnz_feat} feature entries do not fit the file")
+        f_rowptr = np.frombuffer(blob, "<i4", n + 1, off); off += 4 * (n + 1)
+        f_col = np.frombuffer(blob, "<i4", nnz_feat, off); off += 4 * nnz_feat
+        f_val = np.frombuffer(blob, "<f4", nnz_feat, off)
+        out["feature_csr"] = (f_rowptr, f_col, f_val)
+        if unpack:
+            from .sparse_features import SparseFeatures
+            out["features"] = SparseFeatures.from_csr(f_rowptr, f_col, f_val, (n, n_feat)).toarray()
     elif kind != FEAT_NONE:
         raise ValueError(f"{path}: unknown feature kind {kind}")
     return out
 
 
 def load_device(path, row_normalise=False):
-    """Container -> (ops.CsrGraph, features fp32 on the GPU | None, labels int64 on the GPU).  Bit-packed features are
-    uploaded packed and expanded by `wdg_unpack_bits_f32`; `row_normalise` fuses `preprocess_features`' row-L1 scaling
-    (rows summing to 0 stay 0: the reference's inf -> 0 guard)."""
+    """Container -> (ops.CsrGraph, features fp32 on the GPU | None, labels int64 on the GPU).  Bit-packed and CSR features are
+    uploaded compact and expanded by `wdg_features_expand_batched_f32`; `row_normalise` fuses `preprocess_features`' row-L1
+    scaling (rows summing to 0 stay 0: the reference's inf -> 0 guard)."""
     import torch
 
     from . import ops
@@ -217,9 +246,11 @@ def load_device(path, row_normalise=False):
                          g["n_nodes"], g["n_nodes"])
     labels = torch.from_numpy(g["labels"].astype(np.int64)).to(dev)
     feats = None
+    normalise = "sum" if row_normalise else None
     if g["feature_kind"] == FEAT_BITS:
-        words = torch.from_numpy(g["feature_words"].astype(np.int32)).to(dev)  # same bits, torch has no uint32 arithmetic
-        feats = ops.unpack_bits(words, g["n_feat"], row_normalise=row_normalise)
+        feats = ops.expand_features([ops.SparseFeatures.from_bits(g["feature_words"], g["n_feat"], normalise)])[0]
+    elif g["feature_kind"] == FEAT_CSR:  # (validated again: a file is outside input)
+        feats = ops.expand_features([ops.SparseFeatures.from_csr(*g["feature_csr"], (g["n_nodes"], g["n_feat"]), normalise)])[0]
     elif g["feature_kind"] == FEAT_F32:
         feats = torch.from_numpy(g["features"].copy()).to(dev)
         if row_normalise:

@@ -282,9 +282,23 @@ def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_
 
 
 def _upload_features(host):
-    """a feature matrix ([n, F] host array) -> fp32 device tensor, through the upload ring on the current stream"""
+    """a feature matrix ([n, F] host array) -> fp32 device tensor, through the upload ring on the current stream.  An
+    ops.SparseFeatures (or a scipy sparse matrix) travels compact and is expanded on the device (csrc/features.hip)."""
     from . import ops
+    compact = ops.as_compact(host)
+    if compact is not None:
+        return ops.expand_features([compact])[0]
     return ops._h2d(np.ascontiguousarray(host, np.float32), ops.require_gpu())
+
+
+def _upload_features_of(feats, seeds):
+    """{seed: _upload_features(feats[seed])} - the compact matrices among them share one pooled upload and ONE expand launch"""
+    from . import ops
+    seeds = list(seeds)
+    compact = {s_: ops.as_compact(feats[s_]) for s_ in seeds}
+    packed = [s_ for s_ in seeds if compact[s_] is not None]
+    expanded = dict(zip(packed, ops.expand_features([compact[s_] for s_ in packed]))) if packed else {}
+    return {s_: expanded[s_] if s_ in expanded else _upload_features(feats[s_]) for s_ in seeds}
 
 
 def _route_propagates(n_feat, jobs, force=False):
@@ -411,7 +425,9 @@ class SweepBatch:
             lab = labs_host[ji]
             if j.seed not in feats:
                 x_host = inputs[ji][3] if inputs is not None else None
-                x = x_dev[j.seed] if x_dev is not None else _upload_features(
+                # (a compact matrix is expanded straight into the left block of [X | onehot | 0] below: the same values, one copy less)
+                direct = ops.as_compact(x_host) if x_dev is None and ride and not self.labels_only else None
+                x = x_dev[j.seed] if x_dev is not None else None if direct is not None else _upload_features(
                     synth.features(j.n_nodes, n_feat, j.seed + feature_seed) if x_host is None else x_host)
                 if ride:
                     # [X | onehot(labels) | 0]: the label block is laid out on the host and uploaded like any other array (an
@@ -425,7 +441,12 @@ class SweepBatch:
                         xa = ops._h2d(tail, dev)
                     else:
                         xa = torch.empty((j.n_nodes, self.agg_feat), dtype=torch.float32, device=dev)
-                        xa[:, :n_feat] = x
+                        if direct is not None:
+                            if direct.shape != (j.n_nodes, n_feat):
+                                raise ValueError(f"SweepBatch: features of shape {direct.shape} for {j.n_nodes} nodes and n_feat = {n_feat}")
+                            ops.expand_features([direct], outs=[(xa, self.agg_feat)])
+                        else:
+                            xa[:, :n_feat] = x
                         xa[:, lab_col:] = ops._h2d(tail, dev)
                     x = xa
                 feats[j.seed], seed_labels[j.seed] = x, lab
@@ -1020,13 +1041,13 @@ class KrPlan:
         raw features' kernels are written into the SAME buffers (GramBatch(out=...)), so the propagation's, the edge cosines' and the
         regressions' tables stay valid; the node sets are drawn into the same tensors under the new base's keys.  Computes what a
         fresh plan (base_seed=...) over the same inputs computes (tests/test_gpu_sweep.py).  Call only when the previous results have been fetched.
-        feats_of_seed: {seed: [n, n_feat] fp32 host array}"""
+        feats_of_seed: {seed: [n, n_feat] fp32 host array, ops.SparseFeatures or scipy sparse matrix}"""
         if not self.rebindable():
             raise ValueError("rebind_features: a plan over a labels-only step on the propagated route with device-drawn sets is expected")
         seeds = list(self.x)
         self.n_feat = n_feat
         self._y_lazy = None
-        self.x = {s_: _upload_features(feats_of_seed[s_]) for s_ in seeds}
+        self.x = _upload_features_of(feats_of_seed, seeds)
         # (same output tensors: the pair's k_linear / k_arccos / norm2 lists stay as they are)
         self.gram.feats_part = self.ops.GramBatch([self.x[s_] for s_ in seeds], out=self.gram.feats_part)
         self.kr_sets = self._kr_sets(base_seed, out=self.kr_sets)
@@ -1389,7 +1410,8 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
 
     shards: list of (jobs, graph_inputs) - graph_inputs[i] = (src, dst, labels) host arrays of job i (an adjacency belongs to a
             (homophily level, sample) pair: `job.seed` = the sample);
-    bases:  list of (name, features, sample_max) - features[seed] = [n, F_base] fp32 host array of that base's sample `seed`
+    bases:  list of (name, features, sample_max) - features[seed] = [n, F_base] fp32 host array of that base's sample `seed`, or
+            the same matrix compact: an ops.SparseFeatures / a scipy sparse matrix (uploaded as such, expanded on the device)
             (synthetic_plot.py:81-82), sample_max as synthetic_plot.py:66 (300 for chameleon / film, else 500).
     A shard's graphs (CSR, SELL-16 copy, degrees, labels) are built ONCE, by its first base; a narrow base has a batch of its own
     that shares them (SweepBatch(share=...)) and aggregates its feature matrices over them, the wide bases are plans on ONE
@@ -1417,7 +1439,7 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
             # the FIRST base's feature matrices go into the upload ring while the GPU builds the shard's graphs: the copies (1.2 ms
             # of library threads for cora's two 11-MB matrices) otherwise sit between the build's read-back and the first launch
             with torch.cuda.stream(pipe.stream):
-                x_first = {s_: _upload_features(bases[order[0]][1][s_]) for s_ in sorted({j.seed for j in jobs})}
+                x_first = _upload_features_of(bases[order[0]][1], sorted({j.seed for j in jobs}))
         if gb is not None:
             _take_graphs(gb, build_stream, pipe.stream)
             # (decided AFTER the build: a graph without a SELL-16 copy rules the propagated route out for the whole shard - its
@@ -1439,7 +1461,7 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
                 if plan is not None:
                     plan.rebind_features(feats, widths[bi], kr["base_seed"])
                 elif lo[bi] and owner_lo is not None:  # a further plan on the labels-only batch: its step has been queued
-                    plan = KrPlan(owner_lo, {s_: _upload_features(feats[s_]) for s_ in owner_lo.x}, widths[bi], **kr)
+                    plan = KrPlan(owner_lo, _upload_features_of(feats, owner_lo.x), widths[bi], **kr)
                 else:
                     inputs = [(src, dst, lab, feats[j.seed]) for j, (src, dst, lab) in zip(jobs, graph_inputs)]
                     sb = SweepBatch(jobs, n_feat=widths[bi], symmetric=symmetric, gcn_hidden=0, inputs=inputs, share=owner,

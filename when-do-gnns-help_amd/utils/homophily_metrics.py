@@ -138,9 +138,19 @@ def label_informativeness(A, label):
 
 
 # ------------------------------------------------------------------------------------------- generalised edge homophily
+def _device_features(features, dev):
+    """a feature matrix -> fp32 [n, F] on `dev`: a tensor is moved; an ops.SparseFeatures (or a scipy sparse matrix, what the
+    reference's Planetoid loader returns) is uploaded compact and expanded on the device (csrc/features.hip)"""
+    compact = ops.as_compact(features)
+    if compact is None:
+        return features.to(dev, torch.float32)
+    with torch.cuda.device(dev):
+        return ops.expand_features([compact])[0]
+
+
 def _edge_cosine_sum(g, features, entries=None):
     """sum over stored non-loop entries (or the listed entry ids) of cos(x_u, x_v); NaN -> 0."""
-    x = features.to(g.device, torch.float32)
+    x = _device_features(features, g.device)
     if entries is not None:  # sampled entries: loops are kept, as the reference's sampling branch does
         sim = ops.edge_cosine(g, x, entries=entries, skip_self=False)
         return sim.double().sum().float(), torch.tensor(sim.shape[0], device=g.device), sim
@@ -178,7 +188,7 @@ def similarity(features, adj, label, hard=None, LP=1, ifsum=1, idx_train=None):
     g = _graph(adj)
     dev = g.device
     label = label.to(dev)
-    h = ops.spmm(g, features.to(dev))
+    h = ops.spmm(g, features.to(dev) if ops.as_compact(features) is None else _device_features(features, dev))
     labels_all = torch.argmax(label, 1)
     rows = None
     if idx_train is not None:
@@ -246,7 +256,7 @@ def _device_inputs(features, adj, labels):
     """-> (graph, device, features fp32 [n, F], labels [n], the labels as int32, classes counted as max label + 1)"""
     g = _graph(adj)
     dev = g.device
-    features = features.to(dev, torch.float32).contiguous()
+    features = _device_features(features, dev).contiguous()
     labels = labels.to(dev).flatten()
     return g, dev, features, labels, labels.to(torch.int32), int(labels.max().item()) + 1
 
