@@ -11,6 +11,8 @@ LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 FLAGS_kernel_reg := -mllvm -pragma-unroll-threshold=200000
 # (kernel_reg_large.hip factors its diagonal blocks with the same routine, csrc/kr_blocks.h)
 FLAGS_kernel_reg_large := -mllvm -pragma-unroll-threshold=200000
+# (kernel_reg_large_windows.hip IS kernel_reg_large.hip, compiled in its class-window form)
+FLAGS_kernel_reg_large_windows := $(FLAGS_kernel_reg_large)
 # gnb.hip reproduces numpy's fp32 sums bit for bit: no multiply-add may be fused (its source says so as well: #pragma clang fp contract(off))
 FLAGS_gnb := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
@@ -24,6 +26,7 @@ $(LIB): $(OBJS)
 
 # (the compiler's per-kernel resource report - registers, spills, scratch - is kept beside the object: tests/test_abi.py
 # checks that no shipped kernel spills vector registers)
+build/kernel_reg_large_windows.o: $(CSRC)/kernel_reg_large.hip
 build/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/wdg.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> build/$*.rsrc || (cat build/$*.rsrc; exit 1)

@@ -803,7 +803,8 @@ int wdg_row_rep_batched(const wdg_row_rep_job *jobs_dev, int32_t n_jobs, int32_t
 
 /*
  * Batched kernel regression: for every job, alpha = K[train, train]^-1 onehot(labels[train]) by a register-resident Cholesky
- * factorisation (n_train <= wdg_kernel_regress_max_train() = 320, n_classes <= 8), predictions K[val, train] alpha, and
+ * factorisation (n_train <= wdg_kernel_regress_max_train() = 320; a job carries the right-hand sides of at most 8 classes - n_classes <= 8,
+ * or one CLASS WINDOW of a problem of up to 16 classes, below), predictions K[val, train] alpha, and
  * *correct_out = #{v in val : argmax_c prediction == labels[v]} (first maximum, like torch.argmax); -1 for shapes out of range.
  * replaces: `K_val_train @ (np.linalg.pinv(K_train_train) @ label_onehot[idx_train])`, `.argmax(1).eq(labels[idx_val])`
  *           utils/homophily_metrics.py:283-297 (utils/homophily_plot.py:296-310), once per (graph, classifier, epoch,
@@ -825,6 +826,10 @@ int wdg_row_rep_batched(const wdg_row_rep_job *jobs_dev, int32_t n_jobs, int32_t
  * unsigned 32-bit element offsets: row x ldk + column < 2^32; a problem with a wider ldk answers -1 with flags 0).  The launch is persistent - one workgroup per CU walks the problems, and a problem's predictions are
  * made inside the next problem's factorisation (WDG_KR_PERSIST=0: one workgroup per problem) - which changes no result.
  */
+typedef struct wdg_kr_row_best {
+    float value;            /* the first maximum over the window's classes; -3.4e38 when no prediction exceeds that (NaN never wins) */
+    int32_t cls;            /* its class, as an ABSOLUTE class id (class_base + column); class_base when nothing won */
+} wdg_kr_row_best;
 typedef struct wdg_kr_job {
     const float *K;         /* [n, n] kernel of all nodes (a wdg_gram_map_batched_f32 output), leading dimension ldk */
     const int32_t *train;   /* [n_train] */
@@ -835,10 +840,13 @@ typedef struct wdg_kr_job {
                                bit 1 = the train rows were deflated (duplicates merged / zero rows dropped);
                                bit 2 = (deflating entry) rows below the block's resolution were dropped */
     int64_t ldk;
-    int32_t n_train, n_val, n_classes, reserved;
+    int32_t n_train, n_val, n_classes; /* n_classes: the PROBLEM's classes (also of a window job) */
+    int32_t class_base;     /* the first class of the job's window: 0 for the entries without class windows (they do not read it) */
     const int32_t *rep;     /* [n] or NULL: row representatives of the matrix K was computed from (wdg_row_rep_batched) */
     void *ws;               /* NULL, or wdg_kr_deflate_workspace_bytes(n_val) bytes (16-byte aligned) of the problem's own
                                (wdg_kernel_regress_deflated_batched_f32) */
+    wdg_kr_row_best *rows_out; /* [n_val] or NULL (not wanted): per validation row, in `val` order, the largest prediction among the
+                               window's classes and its class (the window entries; the entries without class windows do not read it) */
 } wdg_kr_job;
 /* The same regression for a table whose EVERY job carries a workspace `ws` (and, where the matrix has them, the row representatives
  * `rep`; NULL = every node its own): a pre-pass writes per problem the train rows to solve (one representative per class of duplicate
@@ -851,7 +859,46 @@ int wdg_kernel_regress_deflated_batched_f32(const wdg_kr_job *jobs_dev, int32_t 
 int32_t wdg_kernel_regress_max_train(void);
 
 /*
- * The same regression for train blocks of 1 .. wdg_kernel_regress_large_max_train() = 1024 rows (n_classes <= 8, ldk < 65 536): the
+ * CLASS WINDOWS: problems of 9 .. 16 classes.  A regression's class columns are independent - the factorisation, the pivot test,
+ * the ridge and the deflation do not see the right-hand sides -, and a solver workgroup has room for 8 of them.  A problem of C
+ * classes, C <= 16, is therefore solved as ceil(C / 8) WINDOW JOBS over the same kernel, node sets and labels: window job w has
+ * class_base = 8 w, n_classes = C (the problem's total) and carries the right-hand sides of classes class_base ..
+ * min(class_base + 8, C) - 1; its rows_out receives, per validation row, the first maximum over those classes (value, absolute class id) -
+ * the arg-max rule of the plain entries: the value starts at -3.4e38, a strictly greater prediction replaces it, NaN never wins -,
+ * its correct_out the hits of the window alone and its flags_out the flags word.  The deflation pre-pass judges a duplicate class's
+ * labels (pure / mixed / none in range) over all 16 classes, so a problem's workspace does not depend on the window; every window
+ * job carries a workspace of its own all the same.  wdg_kr_combine_windows_batched then takes, per problem and validation row,
+ * the first maximum over the problem's windows in window order and counts the hits.
+ * A window job is refused (correct_out -1, flags_out 0, rows_out untouched, the table's other jobs unaffected) when n_classes > 16,
+ * class_base is not a multiple of 8 or >= n_classes, or n_classes > 8 without rows_out; the limits of the plain entries hold as well.
+ * A job with class_base 0, n_classes <= 8 and no rows_out is answered exactly as the plain entry answers it.
+ * deflate != 0: wdg_kernel_regress_deflated_batched_f32's pre-pass and solver (every job carries `ws`), else wdg_kernel_regress_batched_f32's.
+ * The plain entries above run their own, unchanged kernels: tables with window jobs go through the entries below.
+ * replaces: `K_val_train @ (np.linalg.pinv(K_train_train) @ label_onehot[idx_train])` utils/homophily_metrics.py:283-297
+ *           (utils/homophily_plot.py:296-310) for the datasets of more than 8 classes that the reference's loaders name
+ *           (utils/util_funcs.py:134,138), a window of 8 class columns per job.
+ */
+int wdg_kernel_regress_windows_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, int32_t deflate, wdg_stream_t stream);
+/* The combine pass of a table of window jobs: per problem, for every validation row v the first maximum over rows[w * row_stride + v],
+ * w = 0 .. n_windows - 1 in window order (a strictly greater value replaces; start -3.4e38, class 0; NaN never wins), compared with
+ * labels[val[v]]; *correct_out = the hits, or -1 when a window job refused (win_correct[w] < 0) or n_windows is outside 1 .. 2;
+ * *flags_out = the OR of win_flags[w].  One launch for the whole table; it only enqueues.
+ * replaces: `.argmax(1)` / accuracy of utils/homophily_metrics.py:283-297 over the class columns that the window jobs hold apart. */
+typedef struct wdg_kr_combine_job {
+    const wdg_kr_row_best *rows; /* [n_windows, row_stride]: the window jobs' rows_out */
+    const int32_t *win_correct;  /* [n_windows]: the window jobs' correct_out */
+    const int32_t *win_flags;    /* [n_windows] or NULL: the window jobs' flags_out */
+    const int32_t *val;          /* [n_val] */
+    const int32_t *labels;       /* [n] */
+    int32_t *correct_out;        /* [1] */
+    int32_t *flags_out;          /* [1] or NULL */
+    int64_t row_stride;
+    int32_t n_val, n_windows;
+} wdg_kr_combine_job;
+int wdg_kr_combine_windows_batched(const wdg_kr_combine_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream);
+
+/*
+ * The same regression for train blocks of 1 .. wdg_kernel_regress_large_max_train() = 1024 rows (8 class columns per job as above, ldk < 65 536): the
  * Cholesky factor lives in device memory instead of registers - packed 32 x 32 blocks of the lower triangle in a LAUNCH-LEVEL
  * scratch buffer that the caller allocates, one 2.1-MiB slice (528 blocks x 4 KiB) per resident workgroup:
  * wdg_kr_large_scratch_bytes() = CUs x 2.1 MiB, whatever the length of the table (a shorter buffer runs fewer workgroups; less
@@ -876,6 +923,11 @@ size_t wdg_kr_large_scratch_bytes(void);
 size_t wdg_kr_large_workspace_bytes(int32_t n_train, int32_t n_val);
 /* replaces: utils/homophily_metrics.py:283-297, utils/homophily_plot.py:296-310 (see above) */
 int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream);
+/* The large solver for a table of window jobs (class windows, above: class_base, rows_out, the same refusals); otherwise
+ * wdg_kernel_regress_large_batched_f32's contract, scratch included.
+ * replaces: utils/homophily_metrics.py:283-297, utils/homophily_plot.py:296-310 for more than 8 classes (utils/util_funcs.py:134,138)
+ *           and train blocks of more than 320 rows */
+int wdg_kernel_regress_large_windows_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream);
 
 /*
  * The node sets of the epochs, drawn on the device: per (graph, classifier, epoch) set a class-balanced sample of the nodes

@@ -155,6 +155,9 @@ SIGNATURES = {
     "wdg_kr_large_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_kernel_regress_large_batched_f32": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "wdg_kr_sample_sets": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_kernel_regress_windows_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_kernel_regress_large_windows_batched_f32": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    "wdg_kr_combine_windows_batched": (c_int, [c_void_p, c_int32, c_void_p]),
 }
 
 
@@ -192,8 +195,19 @@ class EdgeGramJob(ctypes.Structure):
 class KrJob(ctypes.Structure):
     """mirror of `wdg_kr_job` (include/wdg.h)"""
     _fields_ = [("K", c_void_p), ("train", c_void_p), ("val", c_void_p), ("labels", c_void_p), ("correct_out", c_void_p),
-                ("flags_out", c_void_p), ("ldk", c_int64), ("n_train", c_int32), ("n_val", c_int32), ("n_classes", c_int32), ("reserved", c_int32),
-                ("rep", c_void_p), ("ws", c_void_p)]
+                ("flags_out", c_void_p), ("ldk", c_int64), ("n_train", c_int32), ("n_val", c_int32), ("n_classes", c_int32), ("class_base", c_int32),
+                ("rep", c_void_p), ("ws", c_void_p), ("rows_out", c_void_p)]
+
+
+class KrRowBest(ctypes.Structure):
+    """mirror of `wdg_kr_row_best` (include/wdg.h)"""
+    _fields_ = [("value", ctypes.c_float), ("cls", c_int32)]
+
+
+class KrCombineJob(ctypes.Structure):
+    """mirror of `wdg_kr_combine_job` (include/wdg.h)"""
+    _fields_ = [("rows", c_void_p), ("win_correct", c_void_p), ("win_flags", c_void_p), ("val", c_void_p), ("labels", c_void_p),
+                ("correct_out", c_void_p), ("flags_out", c_void_p), ("row_stride", c_int64), ("n_val", c_int32), ("n_windows", c_int32)]
 
 
 class RowRepJob(ctypes.Structure):

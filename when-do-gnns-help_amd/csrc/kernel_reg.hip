@@ -97,7 +97,10 @@ __global__ __launch_bounds__(KD_THREADS) void kr_deflate_kernel(const wdg_kr_job
 // (WDG_KR_PERSIST=0) every problem is a last problem: round 3's schedule.  Hit counts do not depend on the schedule.
 // WS: every job of the table carries a deflation workspace (kr_deflate_kernel has run): the train rows to solve, their labels /
 // right-hand sides and the validation rows' representatives and labels are read from it, and the pivot test is per row.
-template <bool WS>
+// WIN: the table holds CLASS-WINDOW jobs (include/wdg.h): a job carries the right-hand sides of classes class_base .. class_base + 7 of
+// a problem of up to KR_ALL_C classes and leaves every validation row's best (value, class) of its window in rows_out - an
+// instantiation of its own, launched only by the window entry: the plain entries' code reads neither field.
+template <bool WS, bool WIN>
 __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_kr_job *__restrict__ jobs, int n_jobs) {
     __shared__ float P[(K2_NB - 1) * 32 * K2_PS];      // the step's panel L[a, kb], a > kb: [a - kb - 1][row][k], stride 36
     __shared__ float LD[K2_NB * 32 * K2_PS];           // the diagonal blocks L_kk, row-major (kept: the back substitution reads them)
@@ -123,7 +126,9 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
     int pend_nt = 0;  // (uniform) the pending problem's train rows as solved (fewer than n_train after deflation)
     auto predict_units = [&](const desc_ptr<wdg_kr_job> pj, const int *tidx, int max_units) {
         const global_ptr<const float> pK = to_global(pj->K);
-        const int pnv = pj->n_val, pC = pj->n_classes;
+        const int pnv = pj->n_val;
+        const int pcb = WIN ? pj->class_base : 0;                         // (uniform) the window's first class
+        const int pC = WIN ? min(KR_MAX_C, pj->n_classes - pcb) : pj->n_classes;  // the columns that hold classes
         // with a deflation workspace (wdg_kr_deflate_batched) a validation row's kernel row (its representative) and its label come
         // from two arrays indexed by v - no id -> label chain; without: val[v] and labels[val[v]]
         constexpr bool pws = WS;
@@ -179,6 +184,11 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
                     bv = p[c];
                     best = c;
                 }
+            if constexpr (WIN) {  // the row's best of this window, for the combine pass (the pointer is read here: no register held for it)
+                const global_ptr<i32x2_t> prow = to_global(reinterpret_cast<i32x2_t *>(pj->rows_out));  // (value, class): one 8-byte store
+                best += pcb;
+                if (pj->rows_out != nullptr && gl == 0 && v < pnv) prow[v] = i32x2_t{__builtin_bit_cast(int, bv), best};
+            }
             const unsigned long long hit = __ballot(gl == 0 && v < pnv && best == plabels[pws ? min(v, pnv - 1) : gv]);
             if (lane == 0 && hit) atomicAdd(&pend_hits, __popcll(hit));
         }
@@ -219,7 +229,11 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
     const int n_mixed = (has_ws && ws_ok) ? ws[KRW_MIXED] : 0;  // (uniform) listed right-hand-side entries (duplicates with different labels)
     // (ldk: the deferred predictions address K by 32-bit element offsets row x ldk + column, rows and columns < ldk - a wider kernel
     // matrix is refused HERE as well as by the Python launcher, so that a C-ABI caller gets correct_out = -1, not wrong hit counts)
-    if (nt_in <= 0 || nt_in > K2_NB * 32 || nt < 0 || nt > nt_in || C <= 0 || C > KR_MAX_C || ldk <= 0 || ldk >= 65536) {  // (uniform)
+    const int cb = WIN ? job->class_base : 0;  // (uniform) the window's first class
+    bool bad_window = false;
+    if constexpr (WIN) bad_window = cb < 0 || (cb & (KR_MAX_C - 1)) != 0 || cb >= C || (C > KR_MAX_C && job->rows_out == nullptr);
+    if (nt_in <= 0 || nt_in > K2_NB * 32 || nt < 0 || nt > nt_in || C <= 0 || C > (WIN ? KR_ALL_C : KR_MAX_C) || bad_window || ldk <= 0 ||
+        ldk >= 65536) {  // (uniform)
         if (tid == 0 && job->correct_out) *to_global(job->correct_out) = -1;
         if (tid == 0 && job->flags_out) *to_global(job->flags_out) = 0;
         continue;
@@ -275,11 +289,11 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
             float v = 0.f;
             if (row < nt) {
                 const int lb = has_ws ? ws[KRW_LAB + row] : labels[tr_idx[row]];
-                v = lb == c ? (has_ws ? sc[row] : 1.f) : 0.f;
+                v = lb - cb == c ? (has_ws ? sc[row] : 1.f) : 0.f;  // (lb -1 / -2: never a column of any window)
                 if (has_ws && lb == -2)  // (rare) a class of duplicates with different labels: its label counts over sqrt(size)
                     for (int e = 0; e < n_mixed; ++e) {
                         const int w = ws[KRW_MIX + e];
-                        if ((w >> 12) == ((row << 4) | c)) v = static_cast<float>(w & 0xfff) / sc[row];
+                        if ((w >> 12) == ((row << 4) | (c + cb))) v = static_cast<float>(w & 0xfff) / sc[row];
                     }
             }
             zs[i] = v;
@@ -606,6 +620,7 @@ __global__ __launch_bounds__(K2_THREADS) void kr_solve_blocked_kernel(const wdg_
 #endif
 }
 
+template <bool WIN>
 int kernel_regress_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, bool deflated, wdg_stream_t stream) {
     WDG_REQUIRE(n_jobs >= 0, "kernel_regress_batched: negative size");
     if (n_jobs == 0) return WDG_OK;
@@ -620,9 +635,9 @@ int kernel_regress_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, bool defla
     if (deflated) {
         hipLaunchKernelGGL(kr_deflate_kernel, dim3(static_cast<unsigned>(n_jobs)), dim3(KD_THREADS), 0, wdg::as_stream(stream), jobs_dev);
         if (const int rc = wdg::check_launch("kr_deflate_kernel")) return rc;
-        hipLaunchKernelGGL(kr_solve_blocked_kernel<true>, dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(kr_solve_blocked_kernel<true, WIN>), dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
                            wdg::as_stream(stream), jobs_dev, n_jobs);
-    } else hipLaunchKernelGGL(kr_solve_blocked_kernel<false>, dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
+    } else hipLaunchKernelGGL(HIP_KERNEL_NAME(kr_solve_blocked_kernel<false, WIN>), dim3(persist ? (n_jobs < cus ? n_jobs : cus) : n_jobs), dim3(K2_THREADS), 0,
                               wdg::as_stream(stream), jobs_dev, n_jobs);
     return wdg::check_launch("kr_solve_blocked_kernel");
 }
@@ -632,11 +647,15 @@ int kernel_regress_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, bool defla
 extern "C" {
 
 int wdg_kernel_regress_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream) {
-    return kernel_regress_launch(jobs_dev, n_jobs, false, stream);
+    return kernel_regress_launch<false>(jobs_dev, n_jobs, false, stream);
 }
 
 int wdg_kernel_regress_deflated_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream) {
-    return kernel_regress_launch(jobs_dev, n_jobs, true, stream);
+    return kernel_regress_launch<false>(jobs_dev, n_jobs, true, stream);
+}
+
+int wdg_kernel_regress_windows_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, int32_t deflate, wdg_stream_t stream) {
+    return kernel_regress_launch<true>(jobs_dev, n_jobs, deflate != 0, stream);
 }
 
 int32_t wdg_kernel_regress_max_train(void) { return KR_MAX_N; }

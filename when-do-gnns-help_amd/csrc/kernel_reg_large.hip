@@ -58,6 +58,16 @@ __global__ __launch_bounds__(KLD_THREADS) void kr_large_deflate_kernel(const wdg
 
 __device__ __forceinline__ int kl_blk(int a, int b) { return a * (a + 1) / 2 + b; }  // b <= a
 
+// WIN: the table holds CLASS-WINDOW jobs (include/wdg.h; the register solver's form of the same name): an instantiation of its own,
+// launched only by the window entry - and compiled in a unit of its own (csrc/kernel_reg_large_windows.hip includes this file with
+// KL_WINDOWS_UNIT defined): a second instantiation in THIS unit changes the code generated for the first (its register allocation:
+// 6 780 -> 6 871 instructions, measured with a copy of the kernel that differed in nothing but the template argument)
+#ifdef KL_WINDOWS_UNIT
+constexpr bool KL_WIN = true;
+#else
+constexpr bool KL_WIN = false;
+#endif
+template <bool WIN>
 __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr_job *__restrict__ jobs, int n_jobs, float *scratch_all) {
     __shared__ float RP[KL_CH * 32 * K2_PS];           // a part of the row panel L(kb, j0 .. j0 + 7), row-major, stride 36
     __shared__ float LD[32 * K2_PS];                   // the diagonal block: A_kk -> M = L_kk^-1 (k2_factor_invert)
@@ -82,7 +92,9 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
         const int64_t ldk = job->ldk;
         const int nt_in = job->n_train, nv = job->n_val, C = job->n_classes;
         const bool has_ws = job->ws != nullptr;  // (uniform) the pre-pass has run on this job
-        bool refuse = nt_in <= 0 || nt_in > KL_MAX_N || C <= 0 || C > KL_MAX_C || ldk <= 0 || ldk >= 65536 ||
+        const int cb = WIN ? job->class_base : 0;  // (uniform) the window's first class
+        bool refuse = nt_in <= 0 || nt_in > KL_MAX_N || C <= 0 || C > (WIN ? KR_ALL_C : KL_MAX_C) || ldk <= 0 || ldk >= 65536 ||
+                      (WIN && (cb < 0 || (cb & (KL_MAX_C - 1)) != 0 || cb >= C || (C > KL_MAX_C && job->rows_out == nullptr))) ||
                       (!has_ws && job->rep != nullptr);  // (representatives without a workspace: not solved as if there were none)
         int nt = nt_in;
         if (!refuse && has_ws) {
@@ -124,11 +136,11 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
                 float v = 0.f;
                 if (row < nt) {
                     const int lb = has_ws ? ws[W.lab + row] : labels[tr_idx[row]];
-                    v = lb == c ? sc[row] : 0.f;
+                    v = lb - cb == c ? sc[row] : 0.f;  // (lb -1 / -2: never a column of any window)
                     if (lb == -2 && has_ws)  // (rare) a class of duplicates with different labels: its label counts over sqrt(size)
                         for (int e = 0; e < n_mixed; ++e) {
                             const int w = ws[W.mix + e];
-                            if ((w >> 12) == ((row << 4) | c)) v = static_cast<float>(w & 0xfff) / sc[row];
+                            if ((w >> 12) == ((row << 4) | (c + cb))) v = static_cast<float>(w & 0xfff) / sc[row];
                         }
                 }
                 zs[i] = v;
@@ -395,11 +407,17 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
                     for (int o = 8; o > 0; o >>= 1) p[c] += __shfl_xor(p[c], o);  // (inside the row's 16 lanes: every lane ends with the sum)
                 int best = 0;
                 float bv = -3.4e38f;
-                for (int c = 0; c < C; ++c)
+                const int Cw = WIN ? min(KL_MAX_C, C - cb) : C;  // the columns that hold classes
+                for (int c = 0; c < Cw; ++c)
                     if (p[c] > bv) {  // first maximum, like torch.argmax
                         bv = p[c];
                         best = c;
                     }
+                if constexpr (WIN) {  // the row's best of this window, for the combine pass
+                    const global_ptr<i32x2_t> prow = to_global(reinterpret_cast<i32x2_t *>(job->rows_out));  // (value, class): one 8-byte store
+                    best += cb;
+                    if (job->rows_out != nullptr && gl == 0 && v < nv) prow[v] = i32x2_t{__builtin_bit_cast(int, bv), best};
+                }
                 const int want = has_ws ? ws[W.val + nv + vv] : labels[gv];
                 const unsigned long long hit = __ballot(gl == 0 && v < nv && best == want);
                 if (lane == 0 && hit) atomicAdd(&hits, __popcll(hit));
@@ -416,6 +434,7 @@ __global__ __launch_bounds__(KL_THREADS) void kr_large_solve_kernel(const wdg_kr
 
 }  // namespace
 
+#ifndef KL_WINDOWS_UNIT
 extern "C" {
 
 int32_t wdg_kernel_regress_large_max_train(void) { return KL_MAX_N; }
@@ -426,7 +445,13 @@ size_t wdg_kr_large_workspace_bytes(int32_t n_train, int32_t n_val) {
     return krw_bytes(krw_pad(n_train < 0 ? 0 : (n_train > KL_MAX_N ? KL_MAX_N : n_train)), n_val);
 }
 
-int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream) {
+}  // extern "C"
+#endif
+
+namespace {
+
+template <bool WIN>
+int kernel_regress_large_launch(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream) {
     WDG_REQUIRE(n_jobs >= 0, "kernel_regress_large_batched: negative size");
     if (n_jobs == 0) return WDG_OK;
     WDG_REQUIRE(jobs_dev != nullptr, "kernel_regress_large_batched: null job table");
@@ -441,9 +466,23 @@ int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_j
     const int dwgs = n_jobs < 2 * wdg::device_cus() ? n_jobs : 2 * wdg::device_cus();
     hipLaunchKernelGGL(kr_large_deflate_kernel, dim3(static_cast<unsigned>(dwgs)), dim3(KLD_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs);
     if (const int rc = wdg::check_launch("kr_large_deflate_kernel")) return rc;
-    hipLaunchKernelGGL(kr_large_solve_kernel, dim3(static_cast<unsigned>(wgs)), dim3(KL_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs,
+    hipLaunchKernelGGL(kr_large_solve_kernel<WIN>, dim3(static_cast<unsigned>(wgs)), dim3(KL_THREADS), 0, wdg::as_stream(stream), jobs_dev, n_jobs,
                        static_cast<float *>(scratch));
     return wdg::check_launch("kr_large_solve_kernel");
 }
+
+}  // namespace
+
+extern "C" {
+
+#ifndef KL_WINDOWS_UNIT
+int wdg_kernel_regress_large_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream) {
+    return kernel_regress_large_launch<KL_WIN>(jobs_dev, n_jobs, scratch, scratch_bytes, stream);
+}
+#else
+int wdg_kernel_regress_large_windows_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, void *scratch, size_t scratch_bytes, wdg_stream_t stream) {
+    return kernel_regress_large_launch<KL_WIN>(jobs_dev, n_jobs, scratch, scratch_bytes, stream);
+}
+#endif
 
 }  // extern "C"

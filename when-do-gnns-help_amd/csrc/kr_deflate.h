@@ -8,7 +8,10 @@ namespace {
 
 using namespace wdg;
 
-constexpr int KR_MAX_C = 8;  // classes of a problem: the right-hand sides a solver's workgroup carries
+constexpr int KR_MAX_C = 8;  // the right-hand sides a solver's workgroup carries: a problem's classes, or one class window of them
+typedef int i32x2_t __attribute__((ext_vector_type(2)));  // a wdg_kr_row_best as one 8-byte store: (value bits, class)
+static_assert(sizeof(wdg_kr_row_best) == 8, "a row's (value, class) pair is stored as one 8-byte vector");
+constexpr int KR_ALL_C = 16;  // classes of a problem solved in class windows (wdg_kr_job.class_base): what the pre-pass judges labels over
 
 // The deflation workspace of a problem (wdg_kr_job.ws: filled by the pre-pass, read by the solver), as int32 words.  Four header
 // words, then four per-row arrays of P words each, then the validation rows (krw_bytes in all).  P is the register solver's 320
@@ -19,7 +22,8 @@ constexpr int KR_MAX_C = 8;  // classes of a problem: the right-hand sides a sol
 //   [KRW_DROPPED]    != 0 when rows were dropped below the block's resolution (flags bit 2);
 //   [KRW_TRAIN ..]   the solved rows' representatives, padded with -1 up to P;
 //   [W.lab ..]       a solved row's label when all members of its duplicate class carry the same one (right-hand side: sqrt(size) in
-//                    that column), -1 when none carries a label in range (a zero row), -2 for a class with MIXED labels, whose
+//                    that column), -1 when none carries a label in range (0 .. KR_ALL_C - 1: ALL classes, whatever the window of
+//                    the job - a problem's workspace is the same for each of its window jobs; a zero row), -2 for a class with MIXED labels, whose
 //                    non-zero right-hand-side entries are listed in [W.mix ..];
 //   [W.scale ..]     sqrt(members) of a solved row's duplicate class (fp32 bits): the solver factors M = S K S, S = diag of these;
 //   [W.mix ..]       the mixed list: row << 16 | label << 12 | members with that label (a pair per train row at most: <= P words);
@@ -55,7 +59,10 @@ template <int THREADS>
 __device__ __forceinline__ void kr_deflate_one(const wdg_kr_job *__restrict__ job_ptr, int P) {
     static_assert(THREADS % 64 == 0, "whole waves");
     __shared__ int d_raw[THREADS], d_first[THREADS], d_slot[THREADS], d_mult[THREADS];
-    __shared__ float rhs[THREADS * KR_MAX_C];
+    // a slot's label counts over all KR_ALL_C classes, two 16-bit counts per word (a count is at most THREADS <= 4095, the mixed
+    // list's own cap: no carry into the neighbour) - fp32 counts of 16 classes would be 64 KB at 1024 threads
+    __shared__ unsigned cnt2[THREADS * (KR_ALL_C / 2)];
+    __shared__ float wmax[THREADS / 64];
     __shared__ int n_keep, any_mixed, any_drop;
     const desc_ptr<wdg_kr_job> job = (desc_ptr<wdg_kr_job>)job_ptr;
     if (job->ws == nullptr) return;  // (uniform)
@@ -90,14 +97,14 @@ __device__ __forceinline__ void kr_deflate_one(const wdg_kr_job *__restrict__ jo
     // from the reference's)
     float dmax = diag == diag ? diag : 0.f;
     for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o));
-    if ((tid & 63) == 0) rhs[tid >> 6] = dmax;  // (rhs doubles as the waves' maxima; zeroed below)
+    if ((tid & 63) == 0) wmax[tid >> 6] = dmax;
     __syncthreads();
     dmax = 0.f;
-    for (int w = 0; w < THREADS / 64; ++w) dmax = fmaxf(dmax, rhs[w]);
+    for (int w = 0; w < THREADS / 64; ++w) dmax = fmaxf(dmax, wmax[w]);
     if (tid < nt_in && !(diag > static_cast<float>(nt_in) * 1.1920929e-7f * dmax * (1.f / 64.f))) r = -2, any_drop = 1;
     __syncthreads();
     d_raw[tid] = r, d_mult[tid] = 0;
-    for (int i = tid; i < THREADS * KR_MAX_C; i += THREADS) rhs[i] = 0.f;
+    for (int i = tid; i < THREADS * (KR_ALL_C / 2); i += THREADS) cnt2[i] = 0u;
     __syncthreads();
     int first = r < 0 ? -1 : tid;  // the first train row with this representative
     if (r >= 0)  // (eight ids per step, tested together: a one-at-a-time loop with an early exit waits for every LDS read)
@@ -136,7 +143,7 @@ __device__ __forceinline__ void kr_deflate_one(const wdg_kr_job *__restrict__ jo
     if (first == tid) d_first[slot] = r;  // the kept representatives, compact
     if (slot >= 0) {                      // (counts of small integers: exact in any order)
         atomicAdd(&d_mult[slot], 1);
-        if (lb >= 0 && lb < KR_MAX_C) atomicAdd(&rhs[slot * KR_MAX_C + lb], 1.f);
+        if (lb >= 0 && lb < KR_ALL_C) atomicAdd(&cnt2[slot * (KR_ALL_C / 2) + (lb >> 1)], 1u << (16 * (lb & 1)));
     }
     __syncthreads();
     const int kept = n_keep;
@@ -145,18 +152,18 @@ __device__ __forceinline__ void kr_deflate_one(const wdg_kr_job *__restrict__ jo
     int pure = -1;
     bool mixed = false;
     if (tid < kept) {
-        const float m = static_cast<float>(d_mult[tid]);
+        const int m = d_mult[tid];
         int nz = 0;
-        for (int c = 0; c < KR_MAX_C; ++c) {
-            const float cnt = rhs[tid * KR_MAX_C + c];
-            if (cnt != 0.f) ++nz, pure = c;
-            if (cnt != 0.f && cnt != m) mixed = true;
+        for (int c = 0; c < KR_ALL_C; ++c) {
+            const int cnt = static_cast<int>((cnt2[tid * (KR_ALL_C / 2) + (c >> 1)] >> (16 * (c & 1))) & 0xffffu);
+            if (cnt != 0) ++nz, pure = c;
+            if (cnt != 0 && cnt != m) mixed = true;
         }
         mixed |= nz > 1;
         if (mixed) {  // (a (row, label) pair per train row at most: the list never outgrows its P words)
             pure = -2;
-            for (int c = 0; c < KR_MAX_C; ++c) {
-                const int cnt = static_cast<int>(rhs[tid * KR_MAX_C + c]);
+            for (int c = 0; c < KR_ALL_C; ++c) {
+                const int cnt = static_cast<int>((cnt2[tid * (KR_ALL_C / 2) + (c >> 1)] >> (16 * (c & 1))) & 0xffffu);
                 if (cnt > 0) ws[W.mix + atomicAdd(&any_mixed, 1)] = (tid << 16) | (c << 12) | cnt;
             }
         }

@@ -67,7 +67,7 @@ def load_npz_graph(path):
     return adj, feats, torch.from_numpy(z["labels"].astype(np.int64))
 
 
-def run(dataset_path, homophily_metric, symmetric=0, sample_max=500, base_classifier='kernel_reg1'):
+def run(dataset_path, homophily_metric, symmetric=0, sample_max=500, base_classifier='kernel_reg1', kr_class_windows=None):
     device = torch.device("cuda:0")
     adj_raw, features_raw, labels_raw = load_npz_graph(dataset_path)
     nnodes = labels_raw.shape[0]
@@ -100,7 +100,8 @@ def run(dataset_path, homophily_metric, symmetric=0, sample_max=500, base_classi
             las[i] = 2 * float(hm.similarity(label_onehot, adj_raw, label_onehot, hard=is_hard, LP=1, idx_train=idx_train)) - 1
         return METRIC_LIST[homophily_metric](las)
     base = homophily_metric.partition("_based")[0]
-    return METRIC_LIST[homophily_metric](features_raw, adj_raw, labels_raw, sample_max, base_classifier=base, epochs=100)
+    return METRIC_LIST[homophily_metric](features_raw, adj_raw, labels_raw, sample_max, base_classifier=base, epochs=100,
+                                        class_windows=kr_class_windows)
 
 
 def main(argv=None):
@@ -113,10 +114,13 @@ def main(argv=None):
     p.add_argument('--sample_max', type=float, default=500, help='maxinum number of samples used in gntk')
     p.add_argument('--base_classifier', type=str, default='kernel_reg1', choices=BASE_CLASSIFIERS)
     p.add_argument('--homophily_metric', required=True, choices=list(METRIC_LIST.keys()))
+    p.add_argument('--kr_class_windows', action='store_true', default=None,
+                   help='kernel-regression classifiers: keep graphs of 9 .. 16 classes on the device (two class windows of 8 per regression\n'
+                        'and a combine pass) instead of the host path (default: $WDG_KR_CLASS_WINDOWS, off)')
     args = p.parse_args(argv)
     path = (args.dataset_name if args.dataset_name.endswith((".npz", ".wdgg"))
             else os.path.join(args.data_dir, f"real_{args.dataset_name}.npz"))
-    lvl = run(path, args.homophily_metric, args.symmetric, args.sample_max, args.base_classifier)
+    lvl = run(path, args.homophily_metric, args.symmetric, args.sample_max, args.base_classifier, args.kr_class_windows)
     if isinstance(lvl, tuple):
         lvl = lvl[0]
     print(f"The Homophily level of given dataset {args.dataset_name} is {lvl} using metric {args.homophily_metric}")

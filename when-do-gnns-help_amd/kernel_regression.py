@@ -312,8 +312,39 @@ class KrSets:
 
 
 _KR_JOB_DTYPE = np.dtype([("K", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labels", "<u8"), ("correct_out", "<u8"), ("flags_out", "<u8"),
-                          ("ldk", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("n_classes", "<i4"), ("reserved", "<i4"), ("rep", "<u8"), ("ws", "<u8")])
+                          ("ldk", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("n_classes", "<i4"), ("class_base", "<i4"), ("rep", "<u8"), ("ws", "<u8"),
+                          ("rows_out", "<u8")])
 assert _KR_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.KrJob)
+_KR_COMBINE_JOB_DTYPE = np.dtype([("rows", "<u8"), ("win_correct", "<u8"), ("win_flags", "<u8"), ("val", "<u8"), ("labels", "<u8"),
+                                  ("correct_out", "<u8"), ("flags_out", "<u8"), ("row_stride", "<i8"), ("n_val", "<i4"), ("n_windows", "<i4")])
+assert _KR_COMBINE_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.KrCombineJob)
+KR_WINDOW = 8  # class columns of a window job (KR_MAX_C of csrc/kr_deflate.h)
+
+
+def kr_class_window_tables(tab, n_classes, rows_ptr, row_stride, win_correct_ptr, win_flags_ptr, ws_ptr=0, ws_bytes=0):
+    """Pure table arithmetic (numpy, no GPU): the per-problem job table `tab` (_KR_JOB_DTYPE, class_base 0) of problems of
+    `n_classes` classes -> (window table, combine table).  Problem p becomes W = ceil(n_classes / 8) consecutive window jobs
+    (problem-major: the windows of a problem follow each other, as its epochs' problems do - they read the same kernel); window job
+    j = W p + w has class_base 8 w, n_classes unchanged (the problem's total), correct_out / flags_out = word j of the window-level
+    arrays at win_correct_ptr / win_flags_ptr, rows_out = row j of the [jobs, row_stride] array of (value, class) pairs at rows_ptr,
+    and - where the problem carries a workspace - ws = slice j of the pool at ws_ptr (ws_bytes each).  The combine table
+    (_KR_COMBINE_JOB_DTYPE) has one row per problem, with the problem's own correct_out / flags_out."""
+    n = int(tab.shape[0])
+    n_win = (int(n_classes) + KR_WINDOW - 1) // KR_WINDOW
+    win = np.repeat(tab, n_win)
+    j = np.arange(n * n_win, dtype=np.int64)
+    win["class_base"] = KR_WINDOW * (j % n_win)
+    win["correct_out"] = win_correct_ptr + 4 * j
+    win["flags_out"] = win_flags_ptr + 4 * j
+    win["rows_out"] = rows_ptr + 8 * row_stride * j
+    win["ws"] = np.where(win["ws"] != 0, ws_ptr + ws_bytes * j, 0).astype(np.uint64)
+    comb = np.zeros(n, _KR_COMBINE_JOB_DTYPE)
+    first = n_win * np.arange(n, dtype=np.int64)
+    comb["rows"] = rows_ptr + 8 * row_stride * first
+    comb["win_correct"], comb["win_flags"] = win_correct_ptr + 4 * first, win_flags_ptr + 4 * first
+    comb["val"], comb["labels"], comb["correct_out"], comb["flags_out"] = tab["val"], tab["labels"], tab["correct_out"], tab["flags_out"]
+    comb["row_stride"], comb["n_val"], comb["n_windows"] = row_stride, tab["n_val"], n_win
+    return win, comb
 
 
 _KR_LARGE_SCRATCH = {}  # (device, stream) -> the large solver's factor storage: launches on one stream run in order and share it
@@ -345,15 +376,20 @@ class KrBatch:
     MAX_TRAIN = 320         # the register-resident solver (csrc/kernel_reg.hip)
     MAX_TRAIN_LARGE = 1024  # the solver whose factor lives in device memory (csrc/kernel_reg_large.hip)
     MAX_CLASSES = 8  # KR_MAX_C of csrc/kernel_reg.hip: the right-hand sides a problem's workgroup carries
+    MAX_CLASSES_WINDOWED = 16  # with class_windows=True: two window jobs of 8 class columns each + the combine pass (include/wdg.h)
     ROUTES = ("auto", "registers", "large")
 
-    def __init__(self, problems, n_classes, route="auto"):
+    def __init__(self, problems, n_classes, route="auto", class_windows=False):
         """problems: list of (K [n, n] fp32 device, train int32 device [nt], val int32 device [nv], labels int32 device [n]
         [, rep int32 device [n] | None: the row representatives of the matrix K was computed from - GramBatch.rep[i]; the solver
         then deflates duplicate nodes instead of regularising the block])
         route: "auto" - the register solver when every train block has at most 320 rows, else the WHOLE table through the large
         solver (it holds any size from 1 up: still one launch); "registers" / "large" name the solver (tests push small problems
         through the large one).
+        class_windows: True - a table of 9 .. 16 classes is solved as window jobs of 8 class columns each (self.table then holds
+        ceil(n_classes / 8) rows per problem, problem-major) plus a combine pass (self.combine_table); launch() enqueues both, and
+        every per-problem interface (correct, flags, ridged(), deflated(), dropped(), accuracy()) stays per problem, in problem
+        order.  Up to 8 classes, and without the argument, nothing changes: one row per problem, more than 8 classes raise.
         -> self.correct [n_problems] int32 after launch().  Shapes the chosen solver does not hold (more than 8 classes, more than
         320 / 1024 or fewer than 1 train rows) raise here: the kernel would answer them with the sentinel -1, and an accuracy of
         -1 / n_val fed to the t-test is a silently wrong p-value (callers with such label sets take the host path)."""
@@ -363,25 +399,30 @@ class KrBatch:
         self._build(col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0])), col(lambda p_: p_[1].data_ptr()),
                     col(lambda p_: p_[2].data_ptr()), col(lambda p_: p_[3].data_ptr()), col(lambda p_: p_[1].shape[0]),
                     col(lambda p_: p_[2].shape[0]), n_classes,
-                    col(lambda p_: p_[4].data_ptr() if len(p_) > 4 and p_[4] is not None else 0), route=route)
+                    col(lambda p_: p_[4].data_ptr() if len(p_) > 4 and p_[4] is not None else 0), route=route, class_windows=class_windows)
 
     @classmethod
-    def from_arrays(cls, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, keep=None, rep_ptr=None, route="auto"):
+    def from_arrays(cls, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, keep=None, rep_ptr=None, route="auto",
+                    class_windows=False):
         """the same table from per-problem numpy columns (device addresses and sizes): a sweep shard's 20 000 problems are
         described by arithmetic on a few base pointers, not by 20 000 tensor objects"""
         self = cls.__new__(cls)
         self.keep = keep
         self._build(*(np.asarray(a, np.int64) for a in (k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val)), n_classes,
-                    None if rep_ptr is None else np.asarray(rep_ptr, np.int64), route=route)
+                    None if rep_ptr is None else np.asarray(rep_ptr, np.int64), route=route, class_windows=class_windows)
         return self
 
-    def _build(self, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, rep_ptr=None, route="auto"):
+    def _build(self, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, rep_ptr=None, route="auto", class_windows=False):
         dev = require_gpu()
         n = self.n_jobs = int(k_ptr.shape[0])
         if route not in self.ROUTES:
             raise ValueError(f"KrBatch: unknown route {route!r} (one of {', '.join(self.ROUTES)})")
-        if n and not 1 <= int(n_classes) <= self.MAX_CLASSES:
-            raise ValueError(f"KrBatch: {n_classes} classes, the solver holds 1..{self.MAX_CLASSES}")
+        max_classes = self.MAX_CLASSES_WINDOWED if class_windows else self.MAX_CLASSES
+        if n and not 1 <= int(n_classes) <= max_classes:
+            raise ValueError(f"KrBatch: {n_classes} classes, the solver holds 1..{max_classes}"
+                             + ("" if class_windows else f" (class_windows=True: 1..{self.MAX_CLASSES_WINDOWED})"))
+        self.windowed = bool(class_windows) and int(n_classes) > self.MAX_CLASSES  # window jobs + combine pass
+        n_win = (int(n_classes) + KR_WINDOW - 1) // KR_WINDOW if self.windowed else 1
         self.large = route == "large" or (route == "auto" and bool(n) and int(n_train.max()) > self.MAX_TRAIN)
         limit = self.MAX_TRAIN_LARGE if self.large else self.MAX_TRAIN
         if n and not (1 <= int(n_train.min()) and int(n_train.max()) <= limit):
@@ -403,15 +444,36 @@ class KrBatch:
         if n and bool((tab["rep"] != 0).any()):
             per = int(lib.wdg_kr_large_workspace_bytes(int(n_train.max()), int(n_val.max())) if self.large
                       else lib.wdg_kr_deflate_workspace_bytes(int(n_val.max())))
-            self.ws = torch.empty(n * per, dtype=torch.uint8, device=dev)
+            self.ws = torch.empty(n * n_win * per, dtype=torch.uint8, device=dev)  # (windowed: a workspace per window job)
             tab["ws"] = self.ws.data_ptr() + per * np.arange(n, dtype=np.int64)
         # (large) the factor storage belongs to the launch, not to the table: CUs x 2.1 MiB shared, in stream order, by the tables
         # launched on one stream - taken here for the stream that is current now, and by launch() for the one current then
         self.scratch = _kr_large_scratch(dev) if (self.large and n) else None
+        self.n_table_jobs = n * n_win  # rows of self.table: the window jobs of a windowed table, else the problems
+        self.combine_table = None
+        if self.windowed and n:
+            row_stride = max(int(n_val.max()), 1)
+            self.win_correct = torch.zeros(n * n_win, dtype=torch.int32, device=dev)  # the window jobs' own hit counts and flags
+            self.win_flags = torch.zeros(n * n_win, dtype=torch.int32, device=dev)
+            self.rows = torch.zeros((n * n_win, row_stride, 2), dtype=torch.int32, device=dev)  # wdg_kr_row_best per window job and row
+            tab, comb = kr_class_window_tables(tab, n_classes, self.rows.data_ptr(), row_stride, self.win_correct.data_ptr(),
+                                               self.win_flags.data_ptr(), 0 if self.ws is None else self.ws.data_ptr(),
+                                               0 if self.ws is None else per)
+            self.combine_table = _h2d(comb.view(np.uint8), dev)
         self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
 
     def launch(self):
-        if self.large:
+        if self.windowed and self.n_jobs:
+            if self.large:
+                self.scratch = _kr_large_scratch(self.correct.device)
+                check(lib.wdg_kernel_regress_large_windows_batched_f32(_ptr(self.table), self.n_table_jobs, _ptr(self.scratch),
+                                                                       self.scratch.numel(), stream_handle()),
+                      "wdg_kernel_regress_large_windows_batched_f32")
+            else:
+                check(lib.wdg_kernel_regress_windows_batched_f32(_ptr(self.table), self.n_table_jobs, int(self.ws is not None), stream_handle()),
+                      "wdg_kernel_regress_windows_batched_f32")
+            check(lib.wdg_kr_combine_windows_batched(_ptr(self.combine_table), self.n_jobs, stream_handle()), "wdg_kr_combine_windows_batched")
+        elif self.large:
             if self.n_jobs:
                 self.scratch = _kr_large_scratch(self.correct.device)
             check(lib.wdg_kernel_regress_large_batched_f32(_ptr(self.table), self.n_jobs, _ptr(self.scratch),

@@ -849,6 +849,8 @@ class KrPlan:
                identity.  Their raw features' regressions are then the same problem and are solved ONCE per (sample, classifier,
                epoch): 200 + 200 / (levels per shard) regressions per job instead of 400."""
 
+    MAX_CLASSES = 8  # the plan's own limit: its tables (regressions, node sets, index) were not examined for class windows (KrBatch.MAX_CLASSES_WINDOWED)
+
     def __init__(self, batch, x, n_feat, epochs=100, sample_max=500, seed_of=None, sampler=None, base_seed=0, sets=None):
         self.batch, self.ops, self.x, self.n_feat = batch, batch.ops, x, n_feat
         self.kr_epochs, self.kr_sample_max = epochs, sample_max
@@ -861,8 +863,8 @@ class KrPlan:
             self.gram, self.ge = self.ops.GramBatch([]), self.ops.EdgeGramBatch([])
             self.kr = self.ops.KrBatch([], max(batch.n_classes, 1))
             return
-        if batch.n_classes > self.ops.KrBatch.MAX_CLASSES:
-            raise ValueError(f"KrPlan: {batch.n_classes} classes, the device solver holds {self.ops.KrBatch.MAX_CLASSES}; "
+        if batch.n_classes > self.MAX_CLASSES:
+            raise ValueError(f"KrPlan: {batch.n_classes} classes, the device solver holds {self.MAX_CLASSES}; "
                              "use utils.homophily_metrics.classifier_based_performance_metric (host path) per graph")
         sampler = "host" if seed_of is not None else (sampler or os.environ.get("WDG_KR_SAMPLER", "device"))
         self.gram, self.ge = self._build_grams()

@@ -298,15 +298,25 @@ LAST_KR_ACCURACIES = None
 LAST_KR_RIDGED = 0
 
 
-def _kernel_regression_on_device(features, adj, labels, sample_max, base_classifier, epochs):
+def _class_windows_enabled(class_windows):
+    """the class-window switch of the kernel-regression classifiers: the argument, or (None) WDG_KR_CLASS_WINDOWS - default off"""
+    if class_windows is None:
+        return os.environ.get("WDG_KR_CLASS_WINDOWS", "0") not in ("", "0")
+    return bool(class_windows)
+
+
+def _kernel_regression_on_device(features, adj, labels, sample_max, base_classifier, epochs, class_windows=None):
     """the kernel-regression branch of classifier_based_performance_metric entirely on the GPU -> (p_value, seconds), or
     None when the solvers do not hold the problem: a train block of more than 1024 rows (KrBatch.MAX_TRAIN_LARGE; up to 320 rows
     the register-resident solver runs, above that the one whose factor lives in device memory - KrBatch picks) or more than 8
-    classes (Coauthor_CS 15, Amazon_Computers 10, WikiCS 10: the caller then takes the reference's host path)"""
+    classes (Coauthor_CS 15, Amazon_Computers 10, WikiCS 10: the caller then takes the reference's host path) - with
+    class_windows (None: WDG_KR_CLASS_WINDOWS, default off) more than 16: 9 .. 16 classes are then solved as two class windows
+    per regression and a combine pass (KrBatch(class_windows=True))"""
     t_time = time.time()
     g, dev, features, labels, lab32, n_cls = _device_inputs(features, adj, labels)
     n_layers = 0 if base_classifier == 'kernel_reg0' else 1
-    if n_cls > ops.KrBatch.MAX_CLASSES:
+    class_windows = _class_windows_enabled(class_windows)
+    if n_cls > (ops.KrBatch.MAX_CLASSES_WINDOWED if class_windows else ops.KrBatch.MAX_CLASSES):
         return None
     node_sets = _epoch_node_sets(labels, sample_max, epochs, ops.KrBatch.MAX_TRAIN_LARGE)
     if node_sets is None:
@@ -320,7 +330,7 @@ def _kernel_regression_on_device(features, adj, labels, sample_max, base_classif
         if rows is not None:
             (k_g, rep_g), (k_x, rep_x) = _gram_kernel_rep(h_agg[rows], n_layers), _gram_kernel_rep(features[rows], n_layers)
         problems += [(k_g, tr, va, lab, rep_g), (k_x, tr, va, lab, rep_x)]
-    kb = ops.KrBatch(problems, n_cls)
+    kb = ops.KrBatch(problems, n_cls, class_windows=class_windows)
     kb.launch()
     acc = kb.accuracy().cpu().reshape(-1)
     global LAST_KR_ACCURACIES, LAST_KR_RIDGED
@@ -453,7 +463,7 @@ def _svm_on_device(features, adj, labels, sample_max, base_classifier, epochs):
 
 
 def classifier_based_performance_metric(features, adj, labels, sample_max, base_classifier='kernel_reg1', epochs=100,
-                                        solver=None):
+                                        solver=None, class_windows=None):
     """Classifier-based performance metric -> (p_value, seconds).  reference: utils/homophily_metrics.py:260-349.
 
     GPU: the aggregation A X (hoisted out of the epoch loop - it is loop invariant), the sampled
@@ -476,12 +486,14 @@ def classifier_based_performance_metric(features, adj, labels, sample_max, base_
     one up to 320 train rows (wdg_kernel_regress_batched_f32), above that - `sample_max` beyond 533 - the one whose factor lives in
     device memory (wdg_kernel_regress_large_batched_f32).  For a positive definite train block the Cholesky solution is the pseudo-inverse's;
     per-epoch accuracies match the host path to a few validation nodes on well-conditioned kernels
-    (tests/test_gpu_api.py); a rank-deficient block is refactored with a ridge at rounding level (include/wdg.h)."""
+    (tests/test_gpu_api.py); a rank-deficient block is refactored with a ridge at rounding level (include/wdg.h).
+    More than 8 classes take the host path unless class_windows is on (None: WDG_KR_CLASS_WINDOWS, default off): 9 .. 16 classes
+    then stay on the device, two class windows of 8 per regression and a combine pass."""
     solver = solver or os.environ.get("WDG_KR_SOLVER", "device")
     if solver not in ("host", "device"):
         raise ValueError(f"unknown solver {solver!r}")
     if base_classifier in {'kernel_reg0', 'kernel_reg1'} and solver == "device":
-        res = _kernel_regression_on_device(features, adj, labels, sample_max, base_classifier, epochs)
+        res = _kernel_regression_on_device(features, adj, labels, sample_max, base_classifier, epochs, class_windows)
         if res is not None:
             return res
         solver = "host"  # (a train block larger than the solver holds)
