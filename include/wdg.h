@@ -954,6 +954,39 @@ typedef struct wdg_kr_sample_job {
 int wdg_kr_sample_sets(const wdg_kr_sample_job *jobs_dev, int32_t n_jobs, int32_t n_sets_total, int32_t max_n, wdg_stream_t stream);
 int wdg_kernel_regress_batched_f32(const wdg_kr_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream);
 
+/*
+ * Every epoch of many multinomial logistic heads, logits = M W, in one call: one workgroup trains one model for all `epochs` epochs
+ * (cross-entropy over the train rows, torch's Adam with the L2 term in the gradient, model selection on the validation hits), no
+ * host in the loop and nothing between workgroups.
+ * replaces: the training loops behind the SGC-1 and MLP-1 accuracy tables, gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249 (the
+ *           loop itself lives upstream of the reference): M = A_hat X for SGC-1, M = X for MLP-1.  The arithmetic restates the
+ *           epoch of sweep.TrainBatch (kind "sgc" / "mlp1": two batched GEMM launches + ~15 PyTorch launches per epoch).
+ * For epoch e = 0 .. epochs - 1, Adam step t = step0 + e + 1:
+ *   Z = M[train] W;  G = (softmax(Z) - onehot(labels[train])) / n_train (fp32, maximum subtracted);  g = M[train]^T G + weight_decay W;
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  W -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps);
+ *   with the new W: pred = argmax(M W) (first maximum), the hits on `val` and on `test`;
+ *   if val hits > best[0] (strict): best = (val hits, test hits, step0 + e).
+ * W, m, v and best are read and written, so a call of a + b epochs and two calls of a, then b epochs (step0 = a) are the same
+ * computation, bit for bit; every sum has a fixed order that depends on the job's own shape alone (no floating-point atomics: two
+ * runs are bit-identical, and a job's result does not depend on the table it is in).
+ * Limits: 1 <= C <= 8, 1 <= F <= 4096 (max_F / max_C: the table's largest; outside: WDG_ERR_UNSUPPORTED), n_train >= 1, n_val >= 1,
+ * n_test >= 0, ldm >= F (a job outside them is left untouched); labels outside 0 .. C-1 match no class.  n_jobs == 0 or
+ * epochs == 0: nothing is launched.  Jobs run in the kernel instantiation their own (F, C) names: the call enqueues one launch per
+ * instantiation that max_F / max_C admit, a workgroup per job in each, and only the owning one works.
+ */
+typedef struct wdg_head_train_job {
+    const float *M;          /* [n, F] fp32 row-major, leading dimension ldm */
+    const int32_t *labels;   /* [n] class of every row, 0 .. C-1 */
+    const int32_t *train, *val, *test;   /* row ids */
+    float *W, *m, *v;        /* [F, C] in/out: weights, Adam first / second moment */
+    int32_t *best;           /* in/out [3]: validation hits of the best epoch (-1: none yet), test hits at it, its epoch index */
+    int64_t ldm;
+    int32_t n_train, n_val, n_test, F, C, reserved;
+} wdg_head_train_job;
+int wdg_head_train_batched_f32(const wdg_head_train_job *jobs_dev, int32_t n_jobs, int32_t max_F, int32_t max_C,
+                               int32_t epochs, int32_t step0, float lr, float weight_decay,
+                               float beta1, float beta2, float eps, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

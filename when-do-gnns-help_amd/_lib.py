@@ -158,6 +158,8 @@ SIGNATURES = {
     "wdg_kernel_regress_windows_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_kernel_regress_large_windows_batched_f32": (c_int, [c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
     "wdg_kr_combine_windows_batched": (c_int, [c_void_p, c_int32, c_void_p]),
+    "wdg_head_train_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p]),
 }
 
 
@@ -256,6 +258,13 @@ class Mlp2Job(ctypes.Structure):
                 ("lda", c_int64), ("ldw0", c_int64), ("ldw1", c_int64), ("ldz", c_int64),
                 ("M", c_int32), ("K", c_int32), ("H", c_int32), ("C", c_int32), ("act", c_int32), ("reserved", c_int32),
                 ("a_group_stride", c_int64)]
+
+
+class HeadTrainJob(ctypes.Structure):
+    """mirror of `wdg_head_train_job` (include/wdg.h)"""
+    _fields_ = [("M", c_void_p), ("labels", c_void_p), ("train", c_void_p), ("val", c_void_p), ("test", c_void_p),
+                ("W", c_void_p), ("m", c_void_p), ("v", c_void_p), ("best", c_void_p), ("ldm", c_int64),
+                ("n_train", c_int32), ("n_val", c_int32), ("n_test", c_int32), ("F", c_int32), ("C", c_int32), ("reserved", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

@@ -5,6 +5,8 @@ ACM-GNN code (`README.md:79-87`) - so the architecture is defined here, followin
 ("GCN" with random-walk A_hat, "SGC" one step):
     SGC-1 : logits = (A_hat X) W                     (aggregation computed once and cached)
     GCN-2 : logits = A_hat relu(A_hat (X W0)) W1     (transform-then-aggregate: hidden << F), bias-free layers
+and their graph-agnostic twins on the same features, the baselines the table compares them with:
+    MLP-1 : logits = X W                             MLP-2 : logits = relu(X W0) W1
 Forward AND backward run on csrc/spmm*.hip (A_hat^T for the backward pass is the transposed CSR: the synthetic
 graphs are directed) and csrc/gemm.hip (exact-fp32 MFMA).  PyTorch supplies autograd bookkeeping, dropout,
 log-softmax / NLL on [N, C] logits and Adam.
@@ -109,6 +111,36 @@ class GCN2(torch.nn.Module):
         h = torch.relu(adj.matmul(_Linear.apply(x, self.w0, False)))
         h = torch.nn.functional.dropout(h, self.dropout, self.training)
         return adj.matmul(_Linear.apply(h, self.w1, False))
+
+
+class MLP1(torch.nn.Module):
+    """logits = X W: SGC-1 without its aggregation, the graph-agnostic baseline SGC-1 is compared with (gnns_on_syn.py:109-154
+    beside gnns_on_syn.py:213-249).  `adj` is accepted, so that the training loops take it like a GNN, and ignored."""
+
+    def __init__(self, nfeat, nclass):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(nfeat, nclass))
+        torch.nn.init.xavier_uniform_(self.weight)
+
+    def forward(self, adj, x):
+        return _Linear.apply(x, self.weight, False)
+
+
+class MLP2(torch.nn.Module):
+    """logits = relu(X W0) W1: GCN-2 without its two aggregations, bias-free like it; `adj` is accepted and ignored."""
+
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5):
+        super().__init__()
+        self.w0 = torch.nn.Parameter(torch.empty(nfeat, nhid))
+        self.w1 = torch.nn.Parameter(torch.empty(nhid, nclass))
+        torch.nn.init.xavier_uniform_(self.w0)
+        torch.nn.init.xavier_uniform_(self.w1)
+        self.dropout = dropout
+
+    def forward(self, adj, x):
+        h = _Linear.apply(x, self.w0, True)
+        h = torch.nn.functional.dropout(h, self.dropout, self.training)
+        return _Linear.apply(h, self.w1, False)
 
 
 def graphed_inference(model, adj, x, **forward_kwargs):

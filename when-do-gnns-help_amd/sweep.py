@@ -1546,12 +1546,24 @@ class TrainBatch:
 
         kind "sgc":  logits_j = (A_hat_j X) W_j                    (the aggregation Y_j is computed once)
         kind "gcn":  logits_j = A_hat_j relu(A_hat_j (X W0_j)) W1_j   (hidden 64)
-    Per-graph reference with identical arithmetic: models.train_eval_graphed."""
+        kind "mlp1": logits_j = X W_j                              (SGC-1's graph-agnostic twin: the "sgc" epoch on X, no aggregation)
+        kind "mlp2": logits_j = relu(X W0_j) W1_j                  (GCN-2's twin: the "gcn" epoch without its four aggregations)
+    (the baselines the reference's sweep plots the GNNs against: gnns_on_syn.py:109-154 SGC-1 / MLP-1, gnns_on_syn.py:213-249 GCN / MLP-2)
+    Per-graph reference with identical arithmetic: models.train_eval_graphed (models.SGC1 / GCN2 / MLP1 / MLP2).
+    run(whole_run=True) trains the two linear heads ("sgc", "mlp1") with every epoch inside one launch (ops.HeadTrainBatch)."""
+
+    # run(whole_run=True): one launch is kept near this many seconds.  A workgroup of csrc/head_train.hip reads its rows of M at about
+    # HEAD_BYTES_PER_S (measured, DESIGN 4.13 / profiles/head_train_timing.json: bound by a step's chain of latencies, not by bandwidth) and HEAD_RESIDENT of them
+    # run at a time; the default epochs_per_launch follows from the two.
+    HEAD_LAUNCH_S, HEAD_BYTES_PER_S, HEAD_RESIDENT = 0.2, 3.6e9, 256
 
     def __init__(self, sb, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, train_frac=0.6, seed=0):
         from .utils.util_funcs import random_disassortative_splits
         ops = sb.ops
         self.sb, self.kind = sb, kind
+        self.lr, self.weight_decay = lr, weight_decay
+        self._head = None  # (run(whole_run=True): the ops.HeadTrainBatch over this batch's models, and the Adam steps it has taken)
+        self._head_step = 0
         jobs = sb.jobs
         J = len(jobs)
         n, c, f = jobs[0].n_nodes, sb.n_classes, sb.n_feat
@@ -1585,10 +1597,14 @@ class TrainBatch:
         def bwd_spmm(xs, ys):
             return ops.SpmmBatch([(gt, x, y, None, d, False) for gt, x, y, d in zip(graphs_t, xs, ys, rs)])
 
-        if kind == "sgc":
-            sb.spmm.launch()  # Y_j = A_hat_j X, once
-            torch.cuda.synchronize()
-            ys = sb.y  # (row-major; a tiled Y is copied out here, once: the aggregation above is the only one)
+        if kind in ("sgc", "mlp1"):
+            if kind == "sgc":
+                sb.spmm.launch()  # Y_j = A_hat_j X, once
+                torch.cuda.synchronize()
+                ys = sb.y  # (row-major; a tiled Y is copied out here, once: the aggregation above is the only one)
+            else:
+                ys = [sb.x[j.seed] for j in jobs]  # the features themselves: nothing is aggregated
+            self.ys = ys
             self.yt = torch.stack([y.t().contiguous() for y in ys])  # [J, F, n] for dW = Y^T dlogits
             self.w = torch.nn.Parameter(xavier(J, f, c))
             self.w.grad = torch.zeros_like(self.w)
@@ -1614,6 +1630,20 @@ class TrainBatch:
                         ops.GemmBatch([(self.dz[j], self.w1t[j], self.dhid[j], None) for j in range(J)]),       # dH = dZ W1^T
                         bwd_spmm(self.dhid, self.dp),                                                    # dP = A_hat^T (dH * mask)
                         ops.GemmBatch([(xt[jobs[j].seed], self.dp[j], self.w0.grad[j], None) for j in range(J)])]  # dW0 = X^T dP
+        elif kind == "mlp2":
+            xt = {s: x.t().contiguous() for s, x in sb.x.items()}  # X^T per seed, for dW0 = X^T dH
+            self.w0 = torch.nn.Parameter(xavier(J, f, hidden))
+            self.w1 = torch.nn.Parameter(xavier(J, hidden, c))
+            self.w0.grad, self.w1.grad = torch.zeros_like(self.w0), torch.zeros_like(self.w1)
+            self.params = [self.w0, self.w1]
+            z = lambda *s: torch.empty((J,) + s, device=dev)  # noqa: E731
+            self.hid, self.hid_t, self.dhid, self.w1t = z(n, hidden), z(hidden, n), z(n, hidden), z(c, hidden)
+            xs = [sb.x[j.seed] for j in jobs]
+            self.fwd = [ops.GemmBatch([(xs[j], self.w0.data[j], self.hid[j], None) for j in range(J)]),         # P = X W0 (relu below)
+                        ops.GemmBatch([(self.hid[j], self.w1.data[j], self.logits[j], None) for j in range(J)])]  # Z = H W1
+            self.bwd = [ops.GemmBatch([(self.hid_t[j], self.dlogits[j], self.w1.grad[j], None) for j in range(J)]),  # dW1 = H^T dZ
+                        ops.GemmBatch([(self.dlogits[j], self.w1t[j], self.dhid[j], None) for j in range(J)]),       # dH = dZ W1^T
+                        ops.GemmBatch([(xt[jobs[j].seed], self.dhid[j], self.w0.grad[j], None) for j in range(J)])]  # dW0 = X^T (dH * mask)
         else:
             raise ValueError(f"unknown model kind {kind!r}")
         self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True)
@@ -1623,8 +1653,12 @@ class TrainBatch:
 
     # -- one epoch ---------------------------------------------------------------------------------------------
     def _forward(self):
-        if self.kind == "sgc":
+        if self.kind in ("sgc", "mlp1"):
             self.fwd[0].launch()
+        elif self.kind == "mlp2":
+            self.fwd[0].launch()
+            self.hid.clamp_(min=0)  # relu
+            self.fwd[1].launch()
         else:
             self.fwd[0].launch()
             self.fwd[1].launch()
@@ -1640,8 +1674,15 @@ class TrainBatch:
             sm.scatter_add_(2, self.y_tr.unsqueeze(-1), torch.full_like(sm[..., :1], -1.0))
             self.dlogits.zero_()
             self.dlogits.scatter_(1, self.tr.unsqueeze(-1).expand(-1, -1, self.c), sm / self.tr.shape[1])
-            if self.kind == "sgc":
+            if self.kind in ("sgc", "mlp1"):
                 self.bwd[0].launch()
+            elif self.kind == "mlp2":
+                self.hid_t.copy_(self.hid.transpose(1, 2))
+                self.bwd[0].launch()
+                self.w1t.copy_(self.w1.data.transpose(1, 2))
+                self.bwd[1].launch()
+                self.dhid.mul_(self.hid > 0)
+                self.bwd[2].launch()
             else:
                 self.bwd[0].launch()
                 self.hid_t.copy_(self.hid.transpose(1, 2))
@@ -1698,9 +1739,44 @@ class TrainBatch:
                 p.copy_(s)
         return self.graph.replay
 
-    def run(self, epochs=200, capture=True):
-        """-> dict(val_acc [J], test_acc [J], seconds, graphs_per_s): train + evaluate every model for `epochs` epochs."""
+    def _run_whole(self, epochs, epochs_per_launch):
+        """every epoch inside csrc/head_train.hip: one workgroup per model, `epochs_per_launch` epochs per call"""
         import time
+        if self.kind not in ("sgc", "mlp1"):
+            raise ValueError(f"TrainBatch.run(whole_run=True) trains the linear heads (kind 'sgc' / 'mlp1'), not {self.kind!r}")
+        if self._head is None:
+            i32 = lambda t: t.to(torch.int32).contiguous()  # noqa: E731
+            self._head_sets = [i32(t) for t in (self.labels, self.tr, self.va, self.te)]
+            lab, tr, va, te = self._head_sets
+            self._head = self.sb.ops.HeadTrainBatch([(self.ys[j], lab[j], tr[j], va[j], te[j], self.w.data[j]) for j in range(self.J)],
+                                                    self.c, lr=self.lr, weight_decay=self.weight_decay)
+        if epochs_per_launch is None:  # a launch near HEAD_LAUNCH_S: rounds of resident workgroups x an epoch's bytes at the measured rate
+            rounds = -(-self.J // self.HEAD_RESIDENT)
+            epochs_per_launch = int(self.HEAD_LAUNCH_S * self.HEAD_BYTES_PER_S / (rounds * self.n * self.f * 4.0))
+        per = max(1, int(epochs_per_launch))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for done in range(0, epochs, per):
+            self._head.launch(min(per, epochs - done), step0=self._head_step + done)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        self._head_step += epochs
+        best = self._head.best
+        none = best[:, 0] < 0
+        self.best_val.copy_(torch.where(none, torch.full_like(self.best_val, -1.0), best[:, 0].float() / self.va.shape[1]))
+        self.best_test.copy_(torch.where(none, torch.zeros_like(self.best_test), best[:, 1].float() / max(1, self.te.shape[1])))
+        return dict(val_acc=self.best_val.cpu(), test_acc=self.best_test.cpu(), seconds=dt, graphs_per_s=self.J / dt, epochs=epochs,
+                    epochs_per_launch=per, best_epoch=best[:, 2].cpu())
+
+    def run(self, epochs=200, capture=True, whole_run=False, epochs_per_launch=None):
+        """-> dict(val_acc [J], test_acc [J], seconds, graphs_per_s): train + evaluate every model for `epochs` epochs.
+        whole_run (kinds "sgc" / "mlp1" only; opt-in): the epochs run inside wdg_head_train_batched_f32 - a workgroup per model, Adam
+        moments of its own, the same splits, labels and self.w - in launches of `epochs_per_launch` epochs (default: what keeps a
+        launch near HEAD_LAUNCH_S); the accuracies come from its integer hits.  Same arithmetic in another summation order: weights
+        within fp32 rounding of the default path's, not bit for bit."""
+        import time
+        if whole_run:
+            return self._run_whole(epochs, epochs_per_launch)
         step = self.capture() if capture else self.epoch
         with torch.no_grad():
             self._forward()  # logits of the initial weights
