@@ -577,6 +577,8 @@ int wdg_edge_cosine_f32(const int32_t *rowptr, const int32_t *col, const int32_t
  * Then counts: count_out[0] = #{i : soft LAS ratio >= 1}, count_out[1] = #{i : argmax_c W[i,c] == y_i}.
  * replaces: utils/homophily_metrics.py:192-206,216-220,226; utils/homophily_plot.py:196-226,232.
  * `labels` is indexed by node id (full length); `rows` (int32[n], may be NULL = identity) selects the sample.
+ * A selected row whose label lies outside [0, C) belongs to no class: it adds to no column of W, still counts in n, and is
+ * never a hit of either count.
  * workspace: wdg_las_workspace_bytes(n, F, C).
  */
 size_t wdg_las_workspace_bytes(int32_t n, int32_t F, int32_t C);
@@ -584,7 +586,8 @@ int wdg_las_f32(const float *H, int64_t ldh, const int32_t *labels, const int32_
                 int32_t C, double *W_out, int64_t *count_out, void *workspace, size_t workspace_bytes,
                 wdg_stream_t stream);
 
-/* Many problems in one launch (every graph of a sweep batch); count_out is reset by the call itself. */
+/* Many problems in one launch (every graph of a sweep batch); count_out is reset by the call itself - a job with n == 0
+ * inside a non-empty table gets {0, 0} as well (its H, labels, W_out and workspace are not touched). */
 typedef struct wdg_las_job {
     const float *H;
     const int32_t *labels;

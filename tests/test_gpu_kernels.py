@@ -1528,10 +1528,14 @@ def test_fuzz_build_stats_las_gemm(ops, oracle, seed):
     cnt, n_used, w = ops.las(torch.from_numpy(h), torch.from_numpy(lab), cl, want_weights=True)
     wref = oracle.las_weights(h, lab, cl, f64=True)
     np.testing.assert_array_equal(_np(w), wref)
+    assert n_used == nl
+    assert _np(cnt).tolist() == [round(oracle.las_from_weights(wref, lab) * nl), round(oracle.las_from_weights(wref, lab, hard=1) * nl)]
     rows = np.sort(rng.choice(nl, max(1, nl // 3), replace=False))
     cnt_s, n_s, w_s = ops.las(torch.from_numpy(h), torch.from_numpy(lab), cl, rows=torch.from_numpy(rows), want_weights=True)
-    np.testing.assert_array_equal(_np(w_s), oracle.las_weights(h[rows], lab[rows], cl, f64=True))
+    wref_s = oracle.las_weights(h[rows], lab[rows], cl, f64=True)
+    np.testing.assert_array_equal(_np(w_s), wref_s)
     assert n_s == len(rows)
+    assert _np(cnt_s).tolist() == [round(oracle.las_from_weights(wref_s, lab[rows]) * n_s), round(oracle.las_from_weights(wref_s, lab[rows], hard=1) * n_s)]
     # ---- GEMM
     m, kk, nn = int(rng.choice([1, 31, 32, 33, 127, 128, 129, 700])), int(rng.choice([1, 2, 15, 16, 17, 100, 500])), int(rng.choice([1, 5, 31, 32, 33, 64, 65, 100]))
     a = rng.standard_normal((m, kk + 3)).astype(np.float32)[:, :kk]  # non-contiguous leading dimension

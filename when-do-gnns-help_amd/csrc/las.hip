@@ -106,10 +106,13 @@ __global__ __launch_bounds__(64) void las_middle_partial(const wdg_las_job *__re
 __global__ void las_middle_reduce(const wdg_las_job *__restrict__ jobs, const wdg_las_job inline_job) {
     const LasView job = las_view(jobs, inline_job, blockIdx.z);
     const int n = job.n, F = job.F, C = job.C;
-    if (n <= 0 || C <= 0) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n <= 0 || C <= 0) {  // an empty job of a non-empty table: nothing to reduce, but its counters are reset all the same
+        if (i < 2) job.count_out[i] = 0;
+        return;
+    }
     const int n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
     const LasWsView ws = job_ws(job);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < C * F) {
         double acc = 0.0;
         for (int t = 0; t < n_tiles; ++t) acc += ws.partial[static_cast<int64_t>(t) * C * F + i];
@@ -285,7 +288,10 @@ __global__ __launch_bounds__(FUSED_THREADS) void las_small_fused(const wdg_las_j
     __shared__ int st_tot[6];
     const LasView job = las_view(jobs, inline_job, blockIdx.x);
     const int n = job.n, F = job.F, C = job.C;
-    if (n <= 0 || C <= 0) return;
+    if (n <= 0 || C <= 0) {  // an empty job of a non-empty table: no row to decide, both counts are 0
+        if (threadIdx.x < 2) job.count_out[threadIdx.x] = 0;
+        return;
+    }
     const int n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double *M = partial + static_cast<size_t>(n_tiles) * C * F;
