@@ -990,6 +990,58 @@ int wdg_head_train_batched_f32(const wdg_head_train_job *jobs_dev, int32_t n_job
                                int32_t epochs, int32_t step0, float lr, float weight_decay,
                                float beta1, float beta2, float eps, wdg_stream_t stream);
 
+/*
+ * The sweep's synthetic graphs, generated on the device: every graph of a shard in ONE launch, written as sorted CSR - nothing is
+ * uploaded and nothing is sorted.  The family is the one of the reference's pre-generated files (verified on them: N nodes in C
+ * equal contiguous classes, every row exactly d = int(k / h) out-neighbours of which exactly k lie in the row's own class, no
+ * self loops, no duplicates, the draws uniform without replacement inside the class and outside it).  Same DISTRIBUTION as the
+ * reference's files, a documented stream of its own (the position wdg_kr_sample_sets takes for the node sets).
+ * replaces: the loads of the adjacency, label and degree files, synthetic_plot.py:84-90 (the generator that wrote them is not in
+ *           the reference).
+ *
+ * The definition, for a graph (n, C = n_classes, k, d, seed) with m = n / C:
+ *   key(i, j) = word j & 3 of the four output words of Philox4x32-10 with counter {i, j >> 2, 0, 0} and key {seed low, seed high}
+ *               (one Philox block serves four candidate columns);
+ *   row i, of class c = i / m, holds
+ *     - the k columns j of [c m, (c + 1) m), j != i, with the smallest (key(i, j), j), and
+ *     - the d - k columns j outside [c m, (c + 1) m) with the smallest (key(i, j), j),
+ *     - with WDG_SYNTH_SELF_LOOPS also column i (the A + I the sweep aggregates over),
+ *   written ascending; every stored value is 1; labels[i] = i / m.
+ * Outputs of job g: rowptr [n + 1] (local: rowptr[i] = i D, D = d or d + 1 with loops), col / val [n D], labels [n]; and, when
+ * rowptr_union != NULL, rowptr_union[i] = nnz_base + i D for i = 0 .. n (the graph's rows inside the row pointer of a shard's
+ * block-diagonal union; neighbouring graphs write the shared entry with the same value).
+ * The table is given twice: jobs_host, which the entry validates BEFORE anything is launched, and the same bytes on the device.
+ * Refused (WDG_ERR_INVALID): a null table with n_jobs > 0, more than 65535 jobs, n outside 1 .. 16384 (the cap of a batched
+ * SELL-16 copy), C not dividing n, k outside 1 .. m - 1, d < k, d - k > n - m, unknown flags, a null output.  n_jobs == 0: nothing.
+ */
+#define WDG_SYNTH_SELF_LOOPS 1
+typedef struct wdg_synth_job {
+    int32_t *rowptr;        /* out [n + 1] */
+    int32_t *col;           /* out [n D] */
+    float *val;             /* out [n D]: ones */
+    int32_t *labels;        /* out [n] */
+    int32_t *rowptr_union;  /* out [n + 1] or NULL: nnz_base + rowptr */
+    uint64_t seed;
+    int32_t n, n_classes, k, d, flags, nnz_base;
+} wdg_synth_job;
+int wdg_synth_regular_batched(const wdg_synth_job *jobs_host, const wdg_synth_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream);
+
+/*
+ * The rows of a base dataset behind a synthetic graph's features: node i of class c = i / (n / n_classes) takes member number
+ * (u |class c|) >> 32 of the ASCENDING list of the base rows labelled c, u = the first output word of Philox4x32-10 with counter
+ * {i, 0, 0, 0} and key {seed low, seed high} - per class a draw WITH replacement, as in the reference's feature files (which is
+ * why they hold duplicate rows).  The multiply-shift favours some members by at most |class c| / 2^32 in relative terms (the
+ * 2^32 values of u do not divide evenly among |class c| members): 1e-6 for a class of 4 000 rows.
+ * replaces: the loads of the pre-sampled feature files, synthetic_plot.py:81-82 (the sampler that wrote them is not in the reference).
+ * rows_out [n] int32; workspace: wdg_synth_feature_rows_workspace_bytes(n_base, n_classes) bytes, whose LAST n_classes int32 words
+ * hold |class c| afterwards - a class without base rows leaves its nodes' entries unwritten: the caller checks the counts.
+ */
+/* replaces: nothing of its own - the member lists of the draw above (synthetic_plot.py:81-82) */
+size_t wdg_synth_feature_rows_workspace_bytes(int32_t n_base, int32_t n_classes);
+/* replaces: synthetic_plot.py:81-82 (see above) */
+int wdg_synth_feature_rows(const int32_t *base_labels, int32_t n_base, int32_t n, int32_t n_classes, uint64_t seed, int32_t *rows_out,
+                           void *workspace, size_t workspace_bytes, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,9 @@ SIGNATURES = {
     "wdg_kr_combine_windows_batched": (c_int, [c_void_p, c_int32, c_void_p]),
     "wdg_head_train_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, ctypes.c_float,
                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p]),
+    "wdg_synth_regular_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -238,6 +241,13 @@ class KrSampleJob(ctypes.Structure):
     _fields_ = [("labels", c_void_p), ("sample_per_class", c_void_p), ("train_per_class", c_void_p), ("train_out", c_void_p),
                 ("val_out", c_void_p), ("seed", ctypes.c_uint64), ("n", c_int32), ("n_classes", c_int32), ("n_sets", c_int32),
                 ("first_set", c_int32), ("train_stride", c_int32), ("val_stride", c_int32)]
+
+
+class SynthJob(ctypes.Structure):
+    """mirror of `wdg_synth_job` (include/wdg.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("val", c_void_p), ("labels", c_void_p), ("rowptr_union", c_void_p),
+                ("seed", ctypes.c_uint64), ("n", c_int32), ("n_classes", c_int32), ("k", c_int32), ("d", c_int32), ("flags", c_int32),
+                ("nnz_base", c_int32)]
 
 
 class LasJob(ctypes.Structure):

@@ -3,6 +3,7 @@
 //
 // replaces: random_disassortative_splits + the per-class train draw inside classifier_based_performance_metric
 //           (utils/homophily_metrics.py:267-281, utils/homophily_plot.py:286-297) - same distribution, not the same stream.
+#include "philox.h"
 #include "wdg_common.h"
 
 namespace {
@@ -20,24 +21,7 @@ using namespace wdg;
 // ascending like the reference's boolean masks.  Same distribution as the reference's sets, not
 // the same stream (torch's CPU generator): the host routine (utils/util_funcs.kernel_regression_epoch_indices) reproduces
 // the stream and stays the path of the golden tests.  Counter-based: a set's draw depends on (seed, set index) only.
-__device__ __forceinline__ void philox_round(unsigned &c0, unsigned &c1, unsigned &c2, unsigned &c3, unsigned k0, unsigned k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = static_cast<unsigned>(p1 >> 32) ^ c1 ^ k0, n2 = static_cast<unsigned>(p0 >> 32) ^ c3 ^ k1;
-    c1 = static_cast<unsigned>(p1);
-    c3 = static_cast<unsigned>(p0);
-    c0 = n0;
-    c2 = n2;
-}
-__device__ __forceinline__ unsigned philox4x32_10(unsigned c0, unsigned c1, unsigned k0, unsigned k1) {
-    unsigned c2 = 0, c3 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
+// (the generator itself: csrc/philox.h, shared with synth.hip)
 
 constexpr int KS_MAX_CLASSES = 64;
 

@@ -371,8 +371,28 @@ class GraphBatch:
                     _ptr(self.val), c_void_p(info.data_ptr() + 8), _ptr(ws), ws_bytes, st), "wdg_coo_to_csr_i32")
         # per-graph buffers of the SELL-16 build, pooled; the job table's rowptr / col / val are filled in by the split kernel
         self.rowptr_pool = torch.zeros(self.n_total + G, dtype=torch.int32, device=dev)  # (zeros: a graph of no nodes keeps rowptr = [0])
+        quad, jobs, pools = self._sell16_pools(ns, quad, dev)
+        table = _table(jobs) if quad and G else None
+        check(lib.wdg_csr_split_blockdiag(_ptr(self.rowptr), _ptr(self.col), _ptr(self.val), _ptr(node_ptr), G, self.n_total,
+                                          _ptr(self.rowptr_pool), c_void_p(info.data_ptr() + 16), _ptr(table), st),
+              "wdg_csr_split_blockdiag")
+        if quad:
+            check(lib.wdg_csr_to_sell16_count_batched(_ptr(table), G, max(ns), max(ns), st), "wdg_csr_to_sell16_count_batched")
+        info[0:1].copy_(bad[0:1])
+        self._set_pending(G, ns, quad, quad_values, max_padding, info, jobs, dev, node_ptr_h, st, pools,
+                          keep=(src, dst, val, ws, node_ptr, edge_ptr, bad, table))
+        if not defer:
+            self.finish()
+
+    @staticmethod
+    def _sell16_pools(ns, quad, dev):
+        """the per-graph buffers of the batched SELL-16 build, pooled -> (quad: whether the shard gets SELL-16 copies, the host job
+        table with q_perm / q_ext / q_rows / workspace and the sizes set, the pools and their offsets).  The table's rowptr / col /
+        val belong to the caller (the split kernel fills them in on the device, the generator's caller on the host)."""
+        G = len(ns)
         quad = quad and not quad_disabled() and G > 0
         jobs = (_lib.Sell16Job * max(G, 1))()
+        pools = {}
         if quad:
             n_blocks = [(max(n, 1) + lib.wdg_sell16_block_cols(n) - 1) // lib.wdg_sell16_block_cols(n) for n in ns]
             quad = max(n_blocks) <= CsrGraph.QUAD_MAX_BLOCKS and max(ns) <= 16384
@@ -394,23 +414,17 @@ class GraphBatch:
                 job.q_perm, job.q_ext = perm.data_ptr() + 4 * int(perm_off[g_]), ext.data_ptr() + 4 * int(ext_off[g_])
                 job.q_rows, job.workspace = rows.data_ptr() + 4 * int(rows_off[g_]), qws.data_ptr() + int(ws_off[g_])
                 job.n_rows = job.n_cols = ns[g_]
-            table = _table(jobs) if G else None
-        else:
-            table = None
-        check(lib.wdg_csr_split_blockdiag(_ptr(self.rowptr), _ptr(self.col), _ptr(self.val), _ptr(node_ptr), G, self.n_total,
-                                          _ptr(self.rowptr_pool), c_void_p(info.data_ptr() + 16), _ptr(table), st),
-              "wdg_csr_split_blockdiag")
-        if quad:
-            check(lib.wdg_csr_to_sell16_count_batched(_ptr(table), G, max(ns), max(ns), st), "wdg_csr_to_sell16_count_batched")
-        info[0:1].copy_(bad[0:1])
+            pools = dict(ext=ext, rows=rows, perm=perm, qws=qws, ext_off=ext_off, rows_off=rows_off, perm_off=perm_off,
+                         ext_len=ext_len, perm_len=perm_len, n_blocks=n_blocks)
+        return quad, jobs, pools
+
+    def _set_pending(self, G, ns, quad, quad_values, max_padding, info, jobs, dev, node_ptr_h, st, pools, keep, info_host=None):
+        """what finish() needs: the shard's sizes, the info block ([bad, nnz of the union, nnz per graph ...]: a device tensor the
+        read-back fetches - or info_host, the same numbers when the host knows them already) and the SELL-16 pools"""
         self._pending = dict(G=G, ns=ns, quad=quad, quad_values=quad_values, max_padding=max_padding, info=info, jobs=jobs, dev=dev,
-                             node_ptr_h=node_ptr_h, st=st, keep=(src, dst, val, ws, node_ptr, edge_ptr, bad, table))
-        if quad:
-            self._pending.update(ext=ext, rows=rows, perm=perm, qws=qws, ext_off=ext_off, rows_off=rows_off, perm_off=perm_off,
-                                 ext_len=ext_len, perm_len=perm_len, n_blocks=n_blocks)
+                             node_ptr_h=node_ptr_h, st=st, keep=keep, info_host=info_host)
+        self._pending.update(pools)
         self.graphs = None
-        if not defer:
-            self.finish()
 
     def finish(self):
         """the second half of the build: the shard's ONE host read-back, the per-graph views, the SELL-16 fill"""
@@ -424,7 +438,11 @@ class GraphBatch:
                 pd[k] for k in ("ext", "rows", "perm", "qws", "ext_off", "rows_off", "perm_off", "ext_len", "perm_len", "n_blocks"))
         # ---- the shard's ONE host read-back: the info block and, behind it in the same buffer, the pool of extents (64 KB for 50
         #      graphs: the widths price the aggregation's tape cut, the tails size the index arrays) - one blocking copy
-        if quad:
+        if pd["info_host"] is not None:  # (a generated shard: the sizes are host arithmetic, the read-back fetches the extents alone)
+            info_h = pd["info_host"]
+            if quad:
+                ext_h = ext.cpu().numpy()
+        elif quad:
             both = torch.cat([info.view(torch.int32), ext]).cpu().numpy()
             info_h, ext_h = both[:2 * info.numel()].view(np.int64), both[2 * info.numel():]
         else:
@@ -477,6 +495,66 @@ class GraphBatch:
                            block_cols=int(lib.wdg_sell16_block_cols(ns[g_])), n_blocks=n_blocks[g_], n_entries=n_entries,
                            n_su=n_entries // 4, split=split, widths=widths, chunks=chunks_g[g_], n_slices=n_entries,
                            half=lib.wdg_sell16_row_bytes(ns[g_]) == 32)
+
+    @classmethod
+    def generated(cls, specs, flags=0, quad=True, quad_values=False, max_padding=4.0, defer=False):
+        """A shard of synthetic regular graphs GENERATED on the device (wdg_synth_regular_batched: the definition is in
+        include/wdg.h) - the object GraphBatch(coos, flags) yields for the same graphs, bit for bit (tests/test_gpu_synth.py), without
+        a COO pack, an upload, the COO -> CSR build or the split kernel: the generator writes every graph's sorted rows straight into
+        the shard's CSR arrays, and row pointers and sizes are host arithmetic.  The SELL-16 tail and the one read-back (of the
+        extents) are __init__'s.
+        specs: list of (n, n_classes, k, d, seed) - d = the out-degree, int(k / h); seed: 64 bits.
+        flags: 0 or COO_ADD_SELF_LOOPS (A + I: column i in its sorted place).
+        .labels: list of int32 device views, labels[g][i] = i // (n / n_classes)."""
+        if flags not in (0, COO_ADD_SELF_LOOPS):
+            raise ValueError(f"GraphBatch.generated: flags = {flags} (0 or COO_ADD_SELF_LOOPS: the generator emits a coalesced pattern)")
+        dev = require_gpu()
+        self = cls.__new__(cls)
+        G = len(specs)
+        self.flags = flags
+        loops = 1 if flags & COO_ADD_SELF_LOOPS else 0
+        ns = [int(s_[0]) for s_ in specs]
+        nnz = [int(s_[0]) * (int(s_[3]) + loops) for s_ in specs]
+        node_ptr_h = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        base = np.concatenate([[0], np.cumsum(nnz)]).astype(np.int64)
+        self.n_total, nnz_total = int(node_ptr_h[-1]), int(base[-1])
+        if self.n_total >= (1 << 31) - 1 or nnz_total >= (1 << 31) - 1:
+            raise ValueError("GraphBatch.generated: more than 2^31 nodes or entries in one shard")
+        st = stream_handle()
+        self.rowptr = torch.zeros(self.n_total + 1, dtype=torch.int32, device=dev)
+        self.col = torch.empty(nnz_total, dtype=torch.int32, device=dev)
+        self.val = torch.empty(nnz_total, dtype=torch.float32, device=dev)
+        self.rowptr_pool = torch.zeros(self.n_total + G, dtype=torch.int32, device=dev)
+        label_pool = torch.empty(self.n_total, dtype=torch.int32, device=dev)
+        self.labels = [label_pool[int(node_ptr_h[g_]):int(node_ptr_h[g_ + 1])] for g_ in range(G)]
+        quad, jobs, pools = cls._sell16_pools(ns, quad, dev)
+        synth_jobs = (_lib.SynthJob * max(G, 1))()
+        for g_, (n, n_classes, k, d, seed) in enumerate(specs):
+            sj, o = synth_jobs[g_], int(node_ptr_h[g_]) + g_
+            sj.rowptr = self.rowptr_pool.data_ptr() + 4 * o
+            sj.col, sj.val = self.col.data_ptr() + 4 * int(base[g_]), self.val.data_ptr() + 4 * int(base[g_])
+            sj.labels, sj.rowptr_union = label_pool.data_ptr() + 4 * int(node_ptr_h[g_]), self.rowptr.data_ptr() + 4 * int(node_ptr_h[g_])
+            sj.seed, sj.n, sj.n_classes, sj.k, sj.d = int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(n_classes), int(k), int(d)
+            sj.flags, sj.nnz_base = loops, int(base[g_])  # (WDG_SYNTH_SELF_LOOPS == 1)
+            jobs[g_].rowptr, jobs[g_].col, jobs[g_].val = sj.rowptr, sj.col, sj.val
+        self._synth = (synth_jobs, _table(synth_jobs) if G else None, G)
+        self.regenerate()
+        table = _table(jobs) if quad else None
+        if quad:
+            check(lib.wdg_csr_to_sell16_count_batched(_ptr(table), G, max(ns), max(ns), st), "wdg_csr_to_sell16_count_batched")
+        info_host = np.concatenate([[0, nnz_total], nnz]).astype(np.int64)
+        self._set_pending(G, ns, quad, quad_values, max_padding, None, jobs, dev, node_ptr_h, st, pools,
+                          keep=(table, label_pool), info_host=info_host)
+        if not defer:
+            self.finish()
+        return self
+
+    def regenerate(self):
+        """launch the generator of a generated batch (again) on the current stream: counter-based, so the same bits into the same
+        arrays - the one launch `generated` makes, on its own for whoever wants to time it"""
+        synth_jobs, synth_table, G = self._synth
+        check(lib.wdg_synth_regular_batched(ctypes.cast(synth_jobs, c_void_p), _ptr(synth_table), G, stream_handle()),
+              "wdg_synth_regular_batched")
 
     def degree_norm(self, mode=NORM_RW, prec=PREC_F32, use_values=True):
         """-> list (one dict per graph, like ops.degree_norm) of views into the union's arrays: one launch for the shard"""

@@ -5,7 +5,9 @@ gfx950 kernel in csrc/.  Nothing here runs on the CPU, and nothing falls back.
 
 This module is the one namespace callers use (`from wdg_amd import ops`); the code lives in
   _rt.py                flag values of include/wdg.h, pointer helpers, the page-locked upload arena
-  graphs.py             CsrGraph (+ its one-time plans), GraphBatch (a shard's graphs in one build), normalisations
+  graphs.py             CsrGraph (+ its one-time plans), GraphBatch (a shard's graphs in one build, or GENERATED on the device:
+                        GraphBatch.generated), normalisations
+  synth.py              regular_graph_device, sample_feature_rows (the device generators; the numpy generators live there too)
   aggregate.py          spmm, SpmmBatch (the quad-row kernel's tape and its cost cut), spmm_plan
   stats.py              edge / label statistics, LAS, per-edge cosine, their job tables
   gemm.py               gemm, gemm_skinny, GemmBatch, Mlp2Batch
@@ -34,6 +36,7 @@ from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
 from .train import HeadTrainBatch  # noqa: F401
+from .synth import regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, expand_features, feature_image_floats, FeatureExpand, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
     deflation_enabled, EdgeGramBatch, GnbBatch, GramBatch, kr_split_sizes, KrBatch, KrSets, PropagatedGram, RowRepBatch, SvmBatch, _KR_JOB_DTYPE,

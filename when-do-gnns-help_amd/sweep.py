@@ -58,6 +58,30 @@ def make_jobs(h_levels, seeds, k=2, n_nodes=2000, n_classes=5):
     return [Job(float(h), int(s), k, n_nodes, n_classes) for s in seeds for h in h_levels]
 
 
+SYNTH_TAG = 0x53594E  # the last word of a device-generated graph's seed
+
+
+def synth_seed(j):
+    """the 64-bit seed of job j's device-generated graph (include/wdg.h, wdg_synth_regular_batched)"""
+    return _mix64(j.seed, int(round(1000 * j.h)), j.n_nodes, j.k, SYNTH_TAG)
+
+
+def synth_specs(jobs):
+    """jobs -> the (n, n_classes, k, d, seed) list ops.GraphBatch.generated takes"""
+    return [(j.n_nodes, j.n_classes, j.k, synth.out_degree(j.k, j.h), synth_seed(j)) for j in jobs]
+
+
+def _generated_labels(j):
+    """the generator's labels, on the host: contiguous classes of n / C nodes"""
+    return np.arange(j.n_nodes, dtype=np.int64) // (j.n_nodes // j.n_classes)
+
+
+def _check_generate(generate):
+    if generate not in ("host", "device"):
+        raise ValueError(f"generate={generate!r}: 'host' or 'device'")
+    return generate == "device"
+
+
 # what a job costs a GPU, in units of one stored entry of A + I: the aggregation's measured price per 16-row slice is flat
 # (~1.6 us: the slice's 2-KB rows of Y) plus ~43 ns per entry of width (ops._QUAD_COST_*: 1 200 + 38.5 w ns fits the table),
 # i.e. w + 31 entries' worth per row; the feature transform and the metric kernels are per-node work as well
@@ -256,7 +280,8 @@ def pairs_of_rank(pairs, world, rank):
     return shard_pairs(pairs, world, rank)
 
 
-def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_per_shard=80, depth=2, progress=None, stats=None):
+def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_per_shard=80, depth=2, progress=None, stats=None,
+                     generate="host"):
     """This rank's share of the reference's whole sweep (synthetic_plot.py:64-109), STRONG scaling: the (level, sample)
     adjacencies `pairs` (a list of Job; job.seed = the sample) are dealt to the ranks by shard_pairs (contiguous ranges of the
     sample-major list, balanced by modelled cost), every rank runs all feature bases over its adjacencies through run_bases
@@ -264,14 +289,16 @@ def whole_sweep_rank(pairs, graph_of, bases, world, rank, epochs=100, max_pairs_
     graph_of(job) -> (src, dst, labels) host arrays; bases as run_bases takes them.
     -> (keys [m] int64, rows [m, 9] fp64): key = index of the pair in `pairs` x n_bases + base index, ready for exchange_rows.
     A rank keeps one shard while it holds <= max_pairs_per_shard adjacencies (fewer job tables to build), else equal shards.
-    progress(shard index, base index, rows): called as every base-shard's rows arrive on the host (bench.py's per-base clock)."""
+    progress(shard index, base index, rows): called as every base-shard's rows arrive on the host (bench.py's per-base clock).
+    generate="device": graph_of is not called (None will do) - run_bases draws the adjacencies with the device generator."""
+    device_graphs = _check_generate(generate)
     mine = pairs_of_rank(pairs, world, rank)
     index = {j: i for i, j in enumerate(pairs)}
     n_shards = max(1, -(-len(mine) // max_pairs_per_shard))
     per = max(1, -(-len(mine) // n_shards))
-    shards = [(mine[a:a + per], [graph_of(j) for j in mine[a:a + per]]) for a in range(0, len(mine), per)]
+    shards = [(mine[a:a + per], None if device_graphs else [graph_of(j) for j in mine[a:a + per]]) for a in range(0, len(mine), per)]
     keys, rows = [], []
-    for si, bi, r in run_bases(shards, bases, epochs=epochs, depth=depth, stats=stats):
+    for si, bi, r in run_bases(shards, bases, epochs=epochs, depth=depth, stats=stats, generate=generate):
         keys.append(torch.tensor([index[j] * len(bases) + bi for j in shards[si][0]], dtype=torch.int64))
         rows.append(r)
         if progress is not None:
@@ -352,7 +379,7 @@ class SweepBatch:
     """All jobs of this rank, resident in HBM, with prebuilt job tables (one launch per stage per step)."""
 
     def __init__(self, jobs, n_feat=500, symmetric=0, gcn_hidden=64, inputs=None, share=None, feature_seed=0, tune=False,
-                 build=None, labels_only=False, graph_batch=None, x_dev=None):
+                 build=None, labels_only=False, graph_batch=None, x_dev=None, generate="host"):
         """jobs: list of Job (graph + features come from the generator of synth.py) - or, with `inputs`, a list of the same
         length of (src, dst, labels, features [n, n_feat] fp32 numpy) tuples to run instead (real / fixture graphs; jobs that
         share a feature matrix must pass the same array object and carry the same `seed`).
@@ -366,6 +393,10 @@ class SweepBatch:
         replayed many times (training, the replay benchmark); a one-pass sweep takes the modelled cut.
         graph_batch: the shard's ops.GraphBatch (A + I of every job, quad=True) when the caller has queued or finished the build
         already (run_bases builds the NEXT shard's graphs on a stream of their own while this shard's bases run).
+        generate: "host" (default) - the jobs' graphs come from synth.regular_graph (numpy) and go through the COO build; "device" -
+        from ops.GraphBatch.generated over synth_specs(jobs): the same family drawn by the device generator of include/wdg.h (its
+        own stream: other graphs than the host generator's, the same distribution), nothing per edge on the host.  Not together
+        with `inputs`, `share` or build="per_graph"; graph_batch may carry the generated batch.
         x_dev: {seed: [n, n_feat] fp32 device tensor} - the feature matrices, uploaded already (run_bases uploads the first
         base's while the shard's graphs are built).
         labels_only: aggregate the one-hot LABEL columns only (one 16-feature group: everything the six step scalars need); the
@@ -380,6 +411,10 @@ class SweepBatch:
         kernels read row-major operands on the chain variants, refreshes it after every aggregation; TrainBatch("sgc") aggregates
         ONCE and builds its tables on that copy.  WDG_SWEEP_TILED_Y=0: row-major, as in rounds 1 - 3."""
         from . import ops
+        device_graphs = _check_generate(generate)
+        if device_graphs and (inputs is not None or share is not None or build == "per_graph"):
+            raise ValueError("SweepBatch: generate='device' draws the jobs' own graphs in one batched build: not with inputs, share or "
+                             "build='per_graph'")
         self.ops = ops
         self.jobs = list(jobs)
         dev = ops.require_gpu()
@@ -413,6 +448,9 @@ class SweepBatch:
             elif share is not None:
                 src = dst = None
                 lab = np.asarray(share.labels_host[ji]).astype(np.int64)
+            elif device_graphs:
+                src = dst = None
+                lab = _generated_labels(j)
             else:
                 src, dst, lab = synth.regular_graph(j.n_nodes, j.n_classes, j.k, j.h, j.seed)
             coos.append((src, dst, j.n_nodes))
@@ -420,7 +458,12 @@ class SweepBatch:
         mode = ops.NORM_SYM if symmetric else ops.NORM_RW
         if share is None and build == "batched":
             # A + I of every graph (synthetic_plot.py:92) in one build, the degrees of all of them in one launch
-            self.graph_batch = graph_batch if graph_batch is not None else ops.GraphBatch(coos, ops.COO_ADD_SELF_LOOPS, quad=True, defer=True)
+            if graph_batch is not None:
+                self.graph_batch = graph_batch
+            elif device_graphs:
+                self.graph_batch = ops.GraphBatch.generated(synth_specs(self.jobs), ops.COO_ADD_SELF_LOOPS, quad=True, defer=True)
+            else:
+                self.graph_batch = ops.GraphBatch(coos, ops.COO_ADD_SELF_LOOPS, quad=True, defer=True)
         for ji, j in enumerate(self.jobs):
             lab = labs_host[ji]
             if j.seed not in feats:
@@ -1331,14 +1374,17 @@ class _InFlight:
         return tag, sb, stream, rows
 
 
-def _queue_graphs(jobs, graph_inputs, build_stream):
-    """queue the build of a shard's graphs (A + I, SELL-16 copies; graph_inputs[i] begins with job i's src, dst) on build_stream,
-    from any thread -> the deferred ops.GraphBatch (None for an empty shard), for _take_graphs"""
+def _queue_graphs(jobs, graph_inputs, build_stream, generate="host"):
+    """queue the build of a shard's graphs (A + I, SELL-16 copies; graph_inputs[i] begins with job i's src, dst - or, with
+    generate="device", nothing: the device generator draws them) on build_stream, from any thread -> the deferred ops.GraphBatch
+    (None for an empty shard), for _take_graphs"""
     if not jobs:
         return None
     from . import ops
     torch.cuda.set_device(build_stream.device)  # (the current device is per thread)
     with torch.cuda.stream(build_stream):
+        if generate == "device":
+            return ops.GraphBatch.generated(synth_specs(jobs), ops.COO_ADD_SELF_LOOPS, quad=True, defer=True)
         return ops.GraphBatch([(g[0], g[1], j.n_nodes) for j, g in zip(jobs, graph_inputs)], ops.COO_ADD_SELF_LOOPS,
                               quad=True, defer=True)
 
@@ -1350,7 +1396,8 @@ def _take_graphs(gb, build_stream, stream):
     stream.wait_stream(build_stream)
 
 
-def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symmetric=0, depth=2, first_seed=0, stats=None):
+def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symmetric=0, depth=2, first_seed=0, stats=None,
+               generate="host"):
     """The one-pass sweep over a sequence of shards (synthetic_plot.py:78-109: every graph visited once), PIPELINED: a generator
     of the shards' metric rows ([jobs, 6] fp32 / [jobs, 9] fp64 on the host), in order.
 
@@ -1360,7 +1407,10 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
     b + 1 and fetches shard b's rows only when `depth` shards are in flight.  The host part of a shard (concatenation, uploads,
     job tables: 8-11 ms per 50 graphs) thus overlaps the device part of the one before (15.6 ms with the regressions), where the
     sequential loop of bench.py's `sweep_cold` pays their sum.  depth=1 is that sequential loop.  Every shard computes the same
-    bits either way (tests/test_gpu_sweep.py)."""
+    bits either way (tests/test_gpu_sweep.py).
+    generate="device": every shard is (jobs, None) and its graphs come from the device generator (SweepBatch(generate="device"));
+    the next shard's are generated ahead on the build stream, in place of the host pack and the COO build."""
+    device_graphs = _check_generate(generate)
     pipe = _InFlight(depth, (lambda sb: sb.full_metrics()) if nine else (lambda sb: sb.results().cpu()), stats if nine else None)
     # The NEXT shard's graph build (host pack of the edge lists into the upload ring, upload, COO -> CSR, SELL-16 count: 2 - 3 ms of
     # mostly GIL-free library calls) runs on a HELPER THREAD and a stream of its own while this thread builds the current shard's
@@ -1371,9 +1421,11 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
         build_stream = _side_stream(3) if pool is not None else None
 
         def submit(shard):  # -> the future of the shard's graphs, or None: SweepBatch builds them
-            if pool is None or shard is None or shard[1] is None:
+            if device_graphs and shard is not None and shard[1] is not None:
+                raise ValueError("run_shards: generate='device' takes shards of (jobs, None)")
+            if pool is None or shard is None or (shard[1] is None and not device_graphs):
                 return None
-            return pool.submit(_queue_graphs, shard[0], shard[1], build_stream)
+            return pool.submit(_queue_graphs, shard[0], shard[1], build_stream, generate)
 
         it = iter(shards)
         nxt = next(it, None)
@@ -1386,7 +1438,7 @@ def run_shards(shards, n_feat=500, nine=False, epochs=100, sample_max=500, symme
             if gb is not None:
                 _take_graphs(gb, build_stream, pipe.stream)
             with torch.cuda.stream(pipe.stream):
-                sb = SweepBatch(jobs, n_feat=n_feat, symmetric=symmetric, gcn_hidden=0, inputs=inputs, graph_batch=gb)
+                sb = SweepBatch(jobs, n_feat=n_feat, symmetric=symmetric, gcn_hidden=0, inputs=inputs, graph_batch=gb, generate=generate)
                 if nine:
                     sb.prepare_full(epochs=epochs, sample_max=sample_max, base_seed=first_seed + b)
                 sb.step()
@@ -1406,7 +1458,7 @@ def propagates(n_feat, jobs):
             and os.environ.get("WDG_SWEEP_RIDE_LABELS", "1") != "0")
 
 
-def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, stats=None):
+def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, stats=None, generate="host"):
     """The reference's WHOLE sweep (synthetic_plot.py:64-109: 6 feature bases x 30 homophily levels x 10 samples = 1 800 jobs, nine
     scalars each), one pass, PIPELINED like run_shards: a generator of (shard index, base index, rows [jobs, 9] fp64 on the host).
 
@@ -1418,7 +1470,10 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
     A shard's graphs (CSR, SELL-16 copy, degrees, labels) are built ONCE, by its first base; a narrow base has a batch of its own
     that shares them (SweepBatch(share=...)) and aggregates its feature matrices over them, the wide bases are plans on ONE
     labels-only batch.  Base-shard b runs on HIP stream b mod `depth` and its rows are fetched when `depth` are in flight.  Every
-    (shard, base) computes the rows a stand-alone SweepBatch over the same inputs computes (tests/test_gpu_sweep.py)."""
+    (shard, base) computes the rows a stand-alone SweepBatch over the same inputs computes (tests/test_gpu_sweep.py).
+    generate="device": graph_inputs is None for every shard - the graphs come from the device generator (ops.GraphBatch.generated
+    over synth_specs(jobs)), built ahead on the build stream like the host-supplied ones; labels are the generator's."""
+    device_graphs = _check_generate(generate)
     pipe = _InFlight(depth, lambda plan: plan.full_metrics(), stats)
     # TABLE REUSE inside a shard (DESIGN 5).  Bases on the propagated route are KrPlans on ONE labels-only batch, whose step runs
     # once, and a base takes over the plan of an earlier base of equal sample_max whose rows have been fetched (rebind_features).
@@ -1432,8 +1487,12 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
     def visit_order(lo):
         return _visit_order([(True, bases[bi][2]) if lo[bi] else ("own", bi) for bi in range(len(bases))])
 
-    ahead = _queue_graphs(*shards[0], build_stream) if shards else None
+    if device_graphs and any(gi is not None for _jobs, gi in shards):
+        raise ValueError("run_bases: generate='device' takes shards of (jobs, None)")
+    ahead = _queue_graphs(*shards[0], build_stream, generate) if shards else None
     for si, (jobs, graph_inputs) in enumerate(shards):
+        if device_graphs:  # (the batches take the generated graphs through graph_batch=; src / dst are never read)
+            graph_inputs = [(None, None, _generated_labels(j)) for j in jobs]
         gb, ahead, x_first = ahead, None, None
         lo = [propagates(w, jobs) for w in widths]  # (labels-only bases - if every graph gets its SELL-16 copy)
         order = visit_order(lo)
@@ -1477,7 +1536,7 @@ def run_bases(shards, bases, epochs=100, symmetric=0, depth=2, first_seed=0, sta
                 if jobs:
                     plan.launch()
             if first and si + 1 < len(shards):
-                ahead = _queue_graphs(*shards[si + 1], build_stream)
+                ahead = _queue_graphs(*shards[si + 1], build_stream, generate)
             for (dsi, dbi), done, done_stream, rows in pipe.push((si, bi), plan):
                 if dsi == si and done.rebindable():
                     free[(done.kr_sample_max, done_stream.cuda_stream)] = done

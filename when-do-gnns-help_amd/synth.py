@@ -9,6 +9,7 @@ verified on those files, is restated here so that benchmarks and tests need no d
   * `data_synthesis/800` is k=2, `data_synthesis/4000` is k=10 (the directory name is k * 400, synthetic_plot.py:22);
   * features: dense fp32 [N,F], ~10 % non-zeros, rows L1-normalised (pubmed-sample statistics).
 Host-side numpy (numpy PCG64 seeded by (seed, h)); the graphs are inputs, not part of the timed hot path.
+regular_graph_device / sample_feature_rows at the end draw the same family, and the rows behind its features, on the device.
 """
 import numpy as np
 
@@ -99,3 +100,42 @@ def random_graph(n, n_edges, seed, power_law=False):
         src = rng.integers(0, n, n_edges)
     dst = rng.integers(0, n, n_edges)
     return src.astype(np.int64), dst.astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------- the device generators
+def regular_graph_device(n, n_classes, k, h, seed, self_loops=False):
+    """One graph of regular_graph's family drawn ON THE DEVICE (wdg_synth_regular_batched; the definition is in include/wdg.h:
+    the same distribution as regular_graph, a Philox stream of its own) -> (rowptr int32 [n + 1], col int32 [n d], labels int32 [n])
+    device tensors, rows sorted by column, d = int(k / h) (+ 1 with self_loops: column i in row i).  `seed`: 64 bits, used as is.
+    A shard of them, with SELL-16 copies and degrees: ops.GraphBatch.generated."""
+    from . import ops
+    gb = ops.GraphBatch.generated([(n, n_classes, k, out_degree(k, h), seed)], ops.COO_ADD_SELF_LOOPS if self_loops else 0, quad=False)
+    return gb.graphs[0].rowptr, gb.graphs[0].col, gb.labels[0]
+
+
+def sample_feature_rows(base_labels_dev, n, n_classes, seed):
+    """The reference's synthetic features are rows of a base dataset sampled per class WITH replacement (hence the duplicate rows of
+    its files).  -> int32 [n] device tensor of base-row indices: node i of class c = i // (n / n_classes) takes member number
+    (u |class c|) >> 32 of the ascending list of base rows labelled c, u = the first word of Philox4x32-10(counter {i, 0, 0, 0},
+    key seed) (wdg_synth_feature_rows).  The multiply-shift is biased by at most |class c| / 2^32 (relative): the 2^32 values of u
+    do not divide evenly among the members.  The gather itself is torch.index_select(base_features_dev, 0, rows.long()) on a base
+    matrix uploaded (or expanded) once.  A class without base rows raises ValueError (one read-back of the class sizes)."""
+    import torch
+
+    from . import ops
+    dev = ops.require_gpu()
+    n, n_classes = int(n), int(n_classes)
+    if n_classes <= 0 or n % n_classes:
+        raise ValueError(f"sample_feature_rows: {n_classes} classes do not divide {n} nodes")
+    lab = ops._dev(base_labels_dev, torch.int32, dev)
+    n_base = int(lab.shape[0])
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    ws_bytes = int(ops.lib.wdg_synth_feature_rows_workspace_bytes(n_base, n_classes))
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.int32, device=dev)
+    ops.check(ops.lib.wdg_synth_feature_rows(ops._ptr(lab), n_base, n, n_classes, int(seed) & 0xFFFFFFFFFFFFFFFF, ops._ptr(out), ops._ptr(ws),
+                                             ws_bytes, ops.stream_handle()), "wdg_synth_feature_rows")
+    if n:
+        counts = ws[n_base * n_classes:n_base * n_classes + n_classes].cpu().numpy()
+        if (counts == 0).any():
+            raise ValueError(f"sample_feature_rows: class {int(np.flatnonzero(counts == 0)[0])} has no base rows")
+    return out
