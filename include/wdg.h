@@ -991,6 +991,46 @@ int wdg_head_train_batched_f32(const wdg_head_train_job *jobs_dev, int32_t n_job
                                float beta1, float beta2, float eps, wdg_stream_t stream);
 
 /*
+ * ReLU + inverted dropout of the hidden layer of many two-layer models in one launch, IN PLACE, with the transposed copy the
+ * backward GEMM reads (dW1 = H^T dZ) written in the same pass.  The mask is not stored: it is a function of the element's
+ * position and of (seed, stream, step) through Philox4x32-10 (counter {c0, c1, 0, 0}, key {k0, k1}: the generator of
+ * wdg_kr_sample_sets and wdg_synth_regular_batched), so two runs, an eager and a captured run, and a batched and a per-graph run of
+ * the same model draw the same bits.
+ * replaces: the hidden layer's ReLU + dropout of the training loops behind the GCN and MLP-2 accuracy tables, gnns_on_syn.py:213-249
+ *           (beside the one-layer tables gnns_on_syn.py:109-154; the loop itself lives upstream of the reference, which has no
+ *           model code).  In sweep.TrainBatch it stands in for the epoch's `hid.clamp_(min=0)` and `hid_t.copy_(hid^T)`.
+ * The definition, for element (r, c) of job j (rows x cols, groups_per_row = ceil(cols / 4)):
+ *   g = r * groups_per_row + (c >> 2)                                   (one Philox block serves four adjacent columns)
+ *   w = the four output words of Philox4x32-10 with counter {g, *step_dev, 0, 0} and key {seed, jobs[j].stream}
+ *   kept = w[c & 3] >= drop_threshold
+ *   out = h * scale (ONE fp32 multiply) if kept and h > 0;  h itself if h is a NaN (a diverged run is not hidden);  +0.0f otherwise
+ *   h[r][c] = out, and ht[c][r] = out when ht != NULL.
+ * The host passes drop_threshold = (uint32_t) floor(p * 2^32), computed in fp64, and scale = (float) (1 / (1 - p)) for a drop
+ * probability 0 <= p < 1; p = 0 is (0, 1.0f): every element is kept and the call is a plain ReLU.
+ * *step_dev is read from DEVICE memory by the kernel: a captured hipGraph that holds this launch and an increment of the word
+ * draws a fresh mask on every replay.
+ * The backward pass needs no generator and no stored mask: a result is positive exactly where the unit was positive AND kept, so
+ *   dH = (H_out > 0) ? dH * scale : 0.
+ * Deterministic, no atomics; an element depends on its own input and position only: a job's result does not depend on the table
+ * it is in.  h and ht of a job must not overlap.
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, a NULL step_dev, a scale that is
+ * not a number, max_rows * ceil(max_cols / 4) >= 2^32 (g is a 32-bit counter word), more than 65535 jobs (a job per grid z),
+ * more than 64 * 65535 columns (a 64-column tile per grid y).  n_jobs == 0: WDG_OK, nothing is launched.  A job of 0 rows or 0
+ * columns is skipped; rows and columns beyond max_rows / max_cols (the table's largest) are left untouched.
+ */
+typedef struct wdg_dropout_job {
+    float *h;          /* [rows, cols], leading dimension ld; pre-activation in, relu + dropout out, IN PLACE */
+    float *ht;         /* NULL, or [cols, rows], leading dimension ld_t: receives the transposed result */
+    int64_t ld, ld_t;
+    int32_t rows, cols;
+    uint32_t stream;   /* generator stream of this job (TrainBatch: the job's index in the batch) */
+} wdg_dropout_job;
+
+int wdg_relu_dropout_batched_f32(const wdg_dropout_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
+                                 uint32_t drop_threshold, float scale, uint32_t seed, const uint32_t *step_dev,
+                                 wdg_stream_t stream);
+
+/*
  * The sweep's synthetic graphs, generated on the device: every graph of a shard in ONE launch, written as sorted CSR - nothing is
  * uploaded and nothing is sorted.  The family is the one of the reference's pre-generated files (verified on them: N nodes in C
  * equal contiguous classes, every row exactly d = int(k / h) out-neighbours of which exactly k lie in the row's own class, no

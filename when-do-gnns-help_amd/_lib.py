@@ -160,6 +160,7 @@ SIGNATURES = {
     "wdg_kr_combine_windows_batched": (c_int, [c_void_p, c_int32, c_void_p]),
     "wdg_head_train_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, ctypes.c_float,
                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p]),
+    "wdg_relu_dropout_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_uint32, ctypes.c_float, c_uint32, c_void_p, c_void_p]),
     "wdg_synth_regular_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -275,6 +276,12 @@ class HeadTrainJob(ctypes.Structure):
     _fields_ = [("M", c_void_p), ("labels", c_void_p), ("train", c_void_p), ("val", c_void_p), ("test", c_void_p),
                 ("W", c_void_p), ("m", c_void_p), ("v", c_void_p), ("best", c_void_p), ("ldm", c_int64),
                 ("n_train", c_int32), ("n_val", c_int32), ("n_test", c_int32), ("F", c_int32), ("C", c_int32), ("reserved", c_int32)]
+
+
+class DropoutJob(ctypes.Structure):
+    """mirror of `wdg_dropout_job` (include/wdg.h)"""
+    _fields_ = [("h", c_void_p), ("ht", c_void_p), ("ld", c_int64), ("ld_t", c_int64), ("rows", c_int32), ("cols", c_int32),
+                ("stream", c_uint32)]
 
 
 if not os.path.exists(LIB_PATH):

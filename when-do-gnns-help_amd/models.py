@@ -9,7 +9,8 @@ and their graph-agnostic twins on the same features, the baselines the table com
     MLP-1 : logits = X W                             MLP-2 : logits = relu(X W0) W1
 Forward AND backward run on csrc/spmm*.hip (A_hat^T for the backward pass is the transposed CSR: the synthetic
 graphs are directed) and csrc/gemm.hip (exact-fp32 MFMA).  PyTorch supplies autograd bookkeeping, dropout,
-log-softmax / NLL on [N, C] logits and Adam.
+log-softmax / NLL on [N, C] logits and Adam.  With a `DeviceDropout` the hidden layer's ReLU + dropout runs on csrc/dropout.hip
+instead: a counter-based mask that sweep.TrainBatch draws identically for the same (seed, stream, step).
 """
 import torch
 
@@ -65,6 +66,56 @@ class _Linear(torch.autograd.Function):
         return gx, gw, None
 
 
+class DeviceDropout:
+    """The generator identity of one dropout layer on the device: (seed, stream) and a step word in DEVICE memory that starts at 0 and
+    advances by one per training forward pass - the masks of wdg_relu_dropout_batched_f32 (include/wdg.h), which sweep.TrainBatch(
+    dropout=p, dropout_seed=seed) draws for its job number `stream`.  One instance per dropout layer."""
+
+    def __init__(self, seed, stream=0):
+        self.seed, self.stream = int(seed), int(stream)
+        self.step = torch.zeros(1, dtype=torch.int32, device=ops.require_gpu())
+        self._tables = {}  # (rows, cols, p) -> (work buffer, the one-job table over it): built on first use, before any capture
+
+    def relu_dropout(self, pre, p, training):
+        """dropout(relu(pre)): in training mode with p > 0 through the kernel (and the step word advances, on the device: a captured
+        forward draws a fresh mask per replay); otherwise torch.relu(pre)"""
+        if training and p > 0:
+            return _ReluDropout.apply(pre, self, float(p))
+        return torch.relu(pre)
+
+    def _table(self, rows, cols, p):
+        key = (rows, cols, p)
+        if key not in self._tables:
+            buf = torch.empty((rows, cols), dtype=torch.float32, device=self.step.device)
+            self._tables[key] = (buf, ops.DropoutBatch([(buf, None, self.stream)], p, self.seed))
+        return self._tables[key]
+
+
+class _ReluDropout(torch.autograd.Function):
+    """y = dropout(relu(x)) on wdg_relu_dropout_batched_f32 (a one-job table); the backward pass reads the mask off y:
+    a result is positive exactly where the unit was positive and kept."""
+
+    @staticmethod
+    def forward(ctx, x, rng, p):
+        buf, table = rng._table(x.shape[0], x.shape[1], p)
+        buf.copy_(x)
+        table.launch(rng.step)
+        rng.step.add_(1)
+        y = buf.clone()
+        ctx.save_for_backward(y)
+        ctx.scale = table.scale
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, = ctx.saved_tensors
+        return torch.where(y > 0, gy * ctx.scale, 0.0), None, None
+
+
+def _dropout_rngs(model):
+    return [m.dropout_rng for m in model.modules() if getattr(m, "dropout_rng", None) is not None]
+
+
 class SGC1(torch.nn.Module):
     """logits = (A_hat X) W.  Training caches A_hat X (loop invariant: one wide aggregation for the whole run) and learns W on it;
     a forward pass WITHOUT that cache in eval mode (one-shot inference on a graph: BASELINE configs[0], [3], [4]) takes the
@@ -99,17 +150,23 @@ class SGC1(torch.nn.Module):
 
 
 class GCN2(torch.nn.Module):
-    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5):
+    """dropout_rng: None - torch's dropout (its own generator) - or a DeviceDropout: the hidden layer's ReLU + dropout on
+    csrc/dropout.hip, masks reproducible from (seed, stream, step)"""
+
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
         super().__init__()
         self.w0 = torch.nn.Parameter(torch.empty(nfeat, nhid))
         self.w1 = torch.nn.Parameter(torch.empty(nhid, nclass))
         torch.nn.init.xavier_uniform_(self.w0)
         torch.nn.init.xavier_uniform_(self.w1)
-        self.dropout = dropout
+        self.dropout, self.dropout_rng = dropout, dropout_rng
 
     def forward(self, adj, x):
-        h = torch.relu(adj.matmul(_Linear.apply(x, self.w0, False)))
-        h = torch.nn.functional.dropout(h, self.dropout, self.training)
+        if self.dropout_rng is not None:
+            h = self.dropout_rng.relu_dropout(adj.matmul(_Linear.apply(x, self.w0, False)), self.dropout, self.training)
+        else:
+            h = torch.relu(adj.matmul(_Linear.apply(x, self.w0, False)))
+            h = torch.nn.functional.dropout(h, self.dropout, self.training)
         return adj.matmul(_Linear.apply(h, self.w1, False))
 
 
@@ -127,19 +184,23 @@ class MLP1(torch.nn.Module):
 
 
 class MLP2(torch.nn.Module):
-    """logits = relu(X W0) W1: GCN-2 without its two aggregations, bias-free like it; `adj` is accepted and ignored."""
+    """logits = relu(X W0) W1: GCN-2 without its two aggregations, bias-free like it; `adj` is accepted and ignored.
+    dropout_rng: as for GCN2."""
 
-    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5):
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
         super().__init__()
         self.w0 = torch.nn.Parameter(torch.empty(nfeat, nhid))
         self.w1 = torch.nn.Parameter(torch.empty(nhid, nclass))
         torch.nn.init.xavier_uniform_(self.w0)
         torch.nn.init.xavier_uniform_(self.w1)
-        self.dropout = dropout
+        self.dropout, self.dropout_rng = dropout, dropout_rng
 
     def forward(self, adj, x):
-        h = _Linear.apply(x, self.w0, True)
-        h = torch.nn.functional.dropout(h, self.dropout, self.training)
+        if self.dropout_rng is not None:
+            h = self.dropout_rng.relu_dropout(_Linear.apply(x, self.w0, False), self.dropout, self.training)
+        else:
+            h = _Linear.apply(x, self.w0, True)
+            h = torch.nn.functional.dropout(h, self.dropout, self.training)
         return _Linear.apply(h, self.w1, False)
 
 
@@ -241,6 +302,7 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
     g_train = g_eval = None
     if capture:
         saved = [p.detach().clone() for p in model.parameters()]
+        saved_steps = [(r, r.step.clone()) for r in _dropout_rngs(model)]  # (DeviceDropout: the warm-up's masks are drawn again)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # warm-up off the capture stream: lazy state (Adam moments, SELL copies, kernel attributes)
@@ -257,6 +319,8 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
                     if torch.is_tensor(v):
                         v.zero_()
             best_val.fill_(-1.0); best_test.zero_(); best_epoch.zero_(); epoch.zero_()
+            for r, s0 in saved_steps:
+                r.step.copy_(s0)
         g_train, g_eval = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_train):
             train_step()

@@ -1609,17 +1609,31 @@ class TrainBatch:
         kind "mlp2": logits_j = relu(X W0_j) W1_j                  (GCN-2's twin: the "gcn" epoch without its four aggregations)
     (the baselines the reference's sweep plots the GNNs against: gnns_on_syn.py:109-154 SGC-1 / MLP-1, gnns_on_syn.py:213-249 GCN / MLP-2)
     Per-graph reference with identical arithmetic: models.train_eval_graphed (models.SGC1 / GCN2 / MLP1 / MLP2).
-    run(whole_run=True) trains the two linear heads ("sgc", "mlp1") with every epoch inside one launch (ops.HeadTrainBatch)."""
+    run(whole_run=True) trains the two linear heads ("sgc", "mlp1") with every epoch inside one launch (ops.HeadTrainBatch).
+
+    dropout = p > 0 (kinds "gcn" / "mlp2": the models as models.GCN2 / MLP2 define them) drops hidden units while training.  The
+    evaluation's forward pass is then no longer the next epoch's training forward pass, and an epoch becomes
+        training forward (ops.DropoutBatch in place of the ReLU: hid and hid_t in one launch) -> cross-entropy gradient of THESE logits
+        -> backward with dhid = where(hid > 0, dhid * scale, 0) -> Adam -> clean evaluation forward -> model selection.
+    The masks are those of wdg_relu_dropout_batched_f32 (include/wdg.h) with seed `dropout_seed` (default: `seed`), job j's stream
+    = j and a step word in device memory that advances once per training forward, inside the captured epoch: the per-graph
+    reference is models.GCN2 / MLP2(dropout_rng=models.DeviceDropout(dropout_seed, stream=j)).  dropout = 0: the epoch above, unchanged."""
 
     # run(whole_run=True): one launch is kept near this many seconds.  A workgroup of csrc/head_train.hip reads its rows of M at about
     # HEAD_BYTES_PER_S (measured, DESIGN 4.13 / profiles/head_train_timing.json: bound by a step's chain of latencies, not by bandwidth) and HEAD_RESIDENT of them
     # run at a time; the default epochs_per_launch follows from the two.
     HEAD_LAUNCH_S, HEAD_BYTES_PER_S, HEAD_RESIDENT = 0.2, 3.6e9, 256
 
-    def __init__(self, sb, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, train_frac=0.6, seed=0):
+    def __init__(self, sb, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, train_frac=0.6, seed=0, dropout=0.0, dropout_seed=None):
         from .utils.util_funcs import random_disassortative_splits
         ops = sb.ops
         self.sb, self.kind = sb, kind
+        self.dropout = float(dropout)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"TrainBatch: a drop probability in [0, 1) expected, got {dropout!r}")
+        if self.dropout > 0 and kind in ("sgc", "mlp1"):
+            raise ValueError(f"TrainBatch: kind {kind!r} has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2')")
+        self.drop = None  # (dropout > 0: the ops.DropoutBatch over hid / hid_t, and its step word)
         self.lr, self.weight_decay = lr, weight_decay
         self._head = None  # (run(whole_run=True): the ops.HeadTrainBatch over this batch's models, and the Adam steps it has taken)
         self._head_step = 0
@@ -1705,6 +1719,13 @@ class TrainBatch:
                         ops.GemmBatch([(xt[jobs[j].seed], self.dhid[j], self.w0.grad[j], None) for j in range(J)])]  # dW0 = X^T (dH * mask)
         else:
             raise ValueError(f"unknown model kind {kind!r}")
+        if self.dropout > 0:
+            self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)  # advances once per training forward, on the device
+            self.drop = ops.DropoutBatch([(self.hid[j], self.hid_t[j], j) for j in range(J)], self.dropout, seed if dropout_seed is None else dropout_seed)
+            # _loss_gradient_as_autograd(): where the train rows' label entries sit in a model's flattened [n, c] logits, and what
+            # nll_loss's backward puts there for a mean over the train rows
+            self._label_pos = self.tr * c + self.y_tr
+            self._neg_inv_ntr = (-(torch.ones((), device=dev) / float(self.tr.shape[1]))).expand(J, self.tr.shape[1])
         self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True)
         self.best_val = torch.full((J,), -1.0, device=dev)
         self.best_test = torch.zeros(J, device=dev)
@@ -1725,9 +1746,63 @@ class TrainBatch:
             self.fwd[2].launch()
             self.fwd[3].launch()
 
+    def _train_forward(self):
+        """_forward() in training mode (dropout > 0): one launch writes dropout(relu(.)) into hid AND its transpose into hid_t, with
+        the masks of the current step; the step word advances"""
+        if self.kind == "mlp2":
+            self.fwd[0].launch()
+        else:
+            self.fwd[0].launch()
+            self.fwd[1].launch()
+        self.drop.launch(self.drop_step)
+        self.drop_step.add_(1)
+        if self.kind == "mlp2":
+            self.fwd[1].launch()
+        else:
+            self.fwd[2].launch()
+            self.fwd[3].launch()
+
+    def _backward_dropped(self):
+        """the backward launches behind dlogits for the logits of _train_forward(): hid_t is there already, and a unit passes its
+        gradient on (scaled) exactly where its output is positive - it was positive and kept"""
+        scale = self.drop.scale
+        if self.kind == "mlp2":
+            self.bwd[0].launch()
+            self.w1t.copy_(self.w1.data.transpose(1, 2))
+            self.bwd[1].launch()
+            self.dhid.copy_(torch.where(self.hid > 0, self.dhid * scale, 0.0))
+            self.bwd[2].launch()
+        else:
+            self.bwd[0].launch()
+            self.bwd[1].launch()
+            self.w1t.copy_(self.w1.data.transpose(1, 2))
+            self.bwd[2].launch()
+            self.dhid.copy_(torch.where(self.hid > 0, self.dhid * scale, 0.0))
+            self.bwd[3].launch()
+            self.bwd[4].launch()
+
+    def _loss_gradient_as_autograd(self):
+        """dlogits of mean NLL over the train rows by the calls autograd makes for nll_loss(log_softmax(logits)[train], labels) in
+        models.train_eval_graphed: -1 / n_train at the label entries of the train rows, then log_softmax's own backward.  The
+        dropout-free step's (softmax - onehot) / n_train is the same quantity rounded differently in one entry of three; behind
+        bitwise equal logits, gradients that differ in the last bit are what Adam's eps amplifies where a gradient cancels its
+        weight decay, so the dropout epoch - whose masks the per-graph models draw bit for bit - takes autograd's bits."""
+        self.dlogits.zero_()
+        self.dlogits.view(self.J, -1).scatter_(1, self._label_pos, self._neg_inv_ntr)  # what nll_loss's backward hands log_softmax's
+        with torch.enable_grad():  # (the public route to log_softmax's backward kernel: no private operator is named)
+            logits = self.logits.detach().requires_grad_(True)
+            out = torch.log_softmax(logits, 2)
+        self.dlogits.copy_(torch.autograd.grad(out, logits, grad_outputs=self.dlogits)[0])
+
     def train_step(self):
-        # (the forward pass of these weights has been run already: by the previous epoch's evaluation, or by run())
+        # (dropout == 0: the forward pass of these weights has been run already: by the previous epoch's evaluation, or by run())
         with torch.no_grad():
+            if self.drop is not None:
+                self._train_forward()
+                self._loss_gradient_as_autograd()
+                self._backward_dropped()
+                self.opt.step()
+                return
             # d(mean NLL over the training rows) / dlogits = (softmax - onehot) / n_train on those rows, 0 elsewhere
             sm = torch.softmax(self.logits.gather(1, self.tr.unsqueeze(-1).expand(-1, -1, self.c)), 2)
             sm.scatter_add_(2, self.y_tr.unsqueeze(-1), torch.full_like(sm[..., :1], -1.0))
@@ -1764,14 +1839,16 @@ class TrainBatch:
             self.best_val.copy_(torch.where(better, v, self.best_val))
 
     def epoch(self):
-        """gradient of the current logits -> Adam step -> forward with the new weights -> evaluation.  The evaluation's
-        forward pass is the next epoch's training forward pass (no dropout: the two would be identical)."""
+        """gradient of the current logits -> Adam step -> forward with the new weights -> evaluation.  Without dropout the
+        evaluation's forward pass is the next epoch's training forward pass (the two would be identical); with dropout > 0
+        train_step() starts with a training forward pass of its own."""
         self.train_step()
         self.eval_step()
 
     def capture(self):
         """Capture one epoch as a hipGraph (after a warm-up whose effects are rewound); returns the replay callable."""
         saved = [p.detach().clone() for p in self.params]
+        saved_step = None if self.drop is None else self.drop_step.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -1790,6 +1867,8 @@ class TrainBatch:
                         v.zero_()
             self.best_val.fill_(-1.0)
             self.best_test.zero_()
+            if self.drop is not None:  # the warm-up's training forwards advanced the step word: the replays draw its masks again
+                self.drop_step.copy_(saved_step)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.epoch()
@@ -1832,9 +1911,11 @@ class TrainBatch:
         whole_run (kinds "sgc" / "mlp1" only; opt-in): the epochs run inside wdg_head_train_batched_f32 - a workgroup per model, Adam
         moments of its own, the same splits, labels and self.w - in launches of `epochs_per_launch` epochs (default: what keeps a
         launch near HEAD_LAUNCH_S); the accuracies come from its integer hits.  Same arithmetic in another summation order: weights
-        within fp32 rounding of the default path's, not bit for bit."""
+        within fp32 rounding of the default path's, not bit for bit.  With dropout > 0 whole_run raises ValueError."""
         import time
         if whole_run:
+            if self.drop is not None:
+                raise ValueError("TrainBatch.run(whole_run=True) has no dropout: the heads it trains have no hidden layer")
             return self._run_whole(epochs, epochs_per_launch)
         step = self.capture() if capture else self.epoch
         with torch.no_grad():

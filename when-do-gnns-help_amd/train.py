@@ -1,6 +1,8 @@
-"""Whole training runs on the device: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the
-models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip."""
+"""Training on the device: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the
+models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip, and the hidden layer's
+ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -13,6 +15,9 @@ _HEAD_JOB_DTYPE = np.dtype([("M", "<u8"), ("labels", "<u8"), ("train", "<u8"), (
                             ("v", "<u8"), ("best", "<u8"), ("ldm", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("n_test", "<i4"),
                             ("F", "<i4"), ("C", "<i4"), ("reserved", "<i4")])
 assert _HEAD_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.HeadTrainJob)
+_DROPOUT_JOB_DTYPE = np.dtype([("h", "<u8"), ("ht", "<u8"), ("ld", "<i8"), ("ld_t", "<i8"), ("rows", "<i4"), ("cols", "<i4"),
+                               ("stream", "<u4"), ("tail_padding", "<u4")])
+assert _DROPOUT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.DropoutJob)
 
 
 class HeadTrainBatch:
@@ -82,3 +87,63 @@ class HeadTrainBatch:
         self._moments.zero_()
         self.best.zero_()
         self.best[:, 0] = -1
+
+
+def dropout_constants(p):
+    """-> (drop_threshold, scale) of wdg_relu_dropout_batched_f32 for a drop probability 0 <= p < 1: floor(p 2^32) computed in fp64
+    and (float)(1 / (1 - p)); p = 0 gives (0, 1.0): a plain ReLU"""
+    p = float(p)
+    if not 0.0 <= p < 1.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"dropout: a drop probability in [0, 1) expected, got {p!r}")
+    return int(math.floor(p * 4294967296.0)), float(np.float32(1.0 / (1.0 - p)))
+
+
+class DropoutBatch:
+    """Job table for wdg_relu_dropout_batched_f32 (csrc/dropout.hip): h <- dropout(relu(h)) IN PLACE for every entry, and its
+    transpose into ht where one is given, in one launch.  The mask of element (r, c) is a function of (seed, the entry's stream,
+    the step word, r, c) alone (include/wdg.h states it; tests/_dropout_ref.py restates it in numpy): nothing is stored, and the
+    backward pass is dH = where(h_out > 0, dH * self.scale, 0)."""
+
+    def __init__(self, entries, p, seed):
+        """entries: list of (h [rows, cols] fp32 device with unit inner stride; ht None or [cols, rows] fp32 device with unit inner
+        stride, not overlapping h; stream: the entry's generator stream, 0 .. 2^32 - 1).  p: drop probability in [0, 1).
+        seed: 0 .. 2^32 - 1."""
+        self.p = float(p)
+        self.threshold, self.scale = dropout_constants(p)
+        self.seed = int(seed)
+        if not 0 <= self.seed < 1 << 32:
+            raise ValueError(f"DropoutBatch: a seed of 32 bits expected, got {seed!r}")
+        dev = require_gpu()
+        self.keep = entries
+        n = self.n_jobs = len(entries)
+        for h, ht, stream in entries:
+            if h.dim() != 2 or h.dtype != torch.float32 or not h.is_cuda:
+                raise ValueError("DropoutBatch: h must be a 2-D fp32 device matrix")
+            if h.shape[1] > 1 and h.stride(1) != 1:
+                raise ValueError("DropoutBatch: the rows of h must be contiguous (unit inner stride)")
+            if h.shape[0] > 1 and h.stride(0) < h.shape[1]:
+                raise ValueError("DropoutBatch: the rows of h overlap")
+            if ht is not None:
+                if ht.dim() != 2 or tuple(ht.shape) != (h.shape[1], h.shape[0]):
+                    raise ValueError(f"DropoutBatch: ht must be [cols, rows] = {(h.shape[1], h.shape[0])}, got {tuple(ht.shape)}")
+                if ht.dtype != torch.float32 or not ht.is_cuda or (ht.shape[1] > 1 and ht.stride(1) != 1) or (ht.shape[0] > 1 and ht.stride(0) < ht.shape[1]):
+                    raise ValueError("DropoutBatch: ht must be an fp32 device matrix with contiguous rows")
+            if not 0 <= int(stream) < 1 << 32:
+                raise ValueError(f"DropoutBatch: a stream of 32 bits expected, got {stream!r}")
+        col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
+        tab = np.zeros(n, _DROPOUT_JOB_DTYPE)
+        tab["h"], tab["ld"] = col(lambda e: e[0].data_ptr()), col(lambda e: _ld(e[0]))
+        tab["ht"] = col(lambda e: 0 if e[1] is None else e[1].data_ptr())
+        tab["ld_t"] = col(lambda e: 0 if e[1] is None else _ld(e[1]))
+        tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
+        tab["stream"] = col(lambda e: int(e[2]))
+        self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
+        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self, step):
+        """step: a one-element int32 DEVICE tensor whose bits are the uint32 step - the kernel reads it when it runs, so a captured
+        launch followed by a captured `step.add_(1)` draws a fresh mask on every replay"""
+        if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
+            raise ValueError("DropoutBatch.launch: a one-element int32 device tensor expected")
+        check(lib.wdg_relu_dropout_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.threshold, self.scale,
+                                               self.seed, _ptr(step), stream_handle()), "wdg_relu_dropout_batched_f32")
