@@ -1082,6 +1082,60 @@ size_t wdg_synth_feature_rows_workspace_bytes(int32_t n_base, int32_t n_classes)
 int wdg_synth_feature_rows(const int32_t *base_labels, int32_t n_base, int32_t n, int32_t n_classes, uint64_t seed, int32_t *rows_out,
                            void *workspace, size_t workspace_bytes, wdg_stream_t stream);
 
+/*
+ * The channel mix of an ACM layer (adaptive channel mixing: a low-pass, a high-pass and an identity channel weighted per node)
+ * for many models in one launch, and its backward pass.  The reference's loader returns the high-pass operator g_high = I - A_hat
+ * beside the low-pass one and its accuracy tables name "mf-" models, but it ships no model code: the layer is DEFINED here
+ *  and is not claimed to reproduce those tables.
+ * replaces: the use of g_high = I - A_hat, utils/util_funcs.py:198-204, in the model family behind the "mf-GCN" / "mf-SGC" tables,
+ *           gnns_on_syn.py:58-104 and gnns_on_syn.py:159-206 (models that live upstream of the reference).
+ * The definition, for row r of a job (rows x cols, 1 <= cols <= 256), T = 3, relu = flags & WDG_ACM_RELU:
+ *   P_L = low[r,:]    P_H = high[r,:] - high_agg[r,:]  (high_agg == NULL: P_H = high[r,:])    P_I = ident[r,:]
+ *   H_c = relu ? (P_c <= 0 ? 0 : P_c) : P_c                                    (a NaN stays a NaN)
+ *   s_c = 1 / (1 + exp(-sum_k H_c[k] att[c][k]))                                 c in {L, H, I} = {0, 1, 2}
+ *   z_c = sum_j (s_j / T) wmix[j][c]     alpha = softmax(z) with the maximum subtracted
+ *   out[r][k] = 3 (alpha_L H_L[k] + alpha_H H_H[k] + alpha_I H_I[k]),  out_t[k][r] = out[r][k] when out_t != NULL
+ *   aux[r][0..7] = alpha_L alpha_H alpha_I s_L s_H s_I 0 0
+ * One pass: the subtraction, the row sums, the sigmoids, the 3 x 3 product, the softmax and the combination stay in registers.
+ * The backward pass reads the same inputs, aux and d_out (g = d_out[r,:]) and writes
+ *   dalpha_c = 3 sum_k g[k] H_c[k]      dz_c = alpha_c (dalpha_c - sum_j alpha_j dalpha_j)
+ *   ds_j = (1 / T) sum_c wmix[j][c] dz_c      du_c = ds_c s_c (1 - s_c)
+ *   dP_c[k] = (3 alpha_c g[k] + du_c att[c][k]) * (relu ? H_c[k] > 0 : 1)  ->  d_low = dP_L, d_high = dP_H, d_ident = dP_I
+ *   d_att[c][k] = sum_r du_c H_c[k]      d_wmix[j][c] = sum_r (s_j / T) dz_c
+ * (the caller forms d(high_agg) = -d_high).  The sums over rows are bitwise reproducible - no float atomics: the workgroup of
+ * rows [64 b, 64 b + 64) adds its rows in a fixed order and stores one vector of 3 cols + 9 floats at partials + b (3 cols + 9);
+ * a second launch inside the entry adds the blocks in block order.  partials holds ceil(rows / 64) (3 cols + 9) floats.
+ * Every matrix has its own leading dimension (column slices of a wider GEMM or aggregation output are passed in place); att is
+ * [3, cols] and wmix [3, 3], contiguous; aux is [rows, 8], contiguous.  Outputs must not overlap inputs or each other.
+ * An element of out depends on its own row alone and a job's sums on the job alone: a job answers in a table what it answers alone.
+ * Refused before any launch (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs (a job per
+ * grid z), max_cols > 256.  n_jobs == 0: WDG_OK, nothing is launched.  A job of 0 rows writes nothing forward and zero sums
+ * backward; rows beyond max_rows (the table's largest) are left untouched, and a job of more than max_cols columns is skipped.
+ */
+#define WDG_ACM_RELU 1
+#define WDG_ACM_MAX_COLS 256
+typedef struct wdg_acm_mix_job {
+    const float *low;       /* [rows, cols]: A_hat (M W_L) */
+    const float *high;      /* [rows, cols]: M W_H */
+    const float *high_agg;  /* [rows, cols]: A_hat (M W_H), or NULL */
+    const float *ident;     /* [rows, cols]: M W_I */
+    const float *att;       /* [3, cols] */
+    const float *wmix;      /* [3, 3] */
+    float *out;             /* forward out [rows, cols] */
+    float *out_t;           /* forward out [cols, rows], or NULL */
+    float *aux;             /* [rows, 8]: forward out, backward in */
+    const float *d_out;     /* backward in [rows, cols] */
+    float *d_low, *d_high, *d_ident; /* backward out [rows, cols] */
+    float *d_att;           /* backward out [3, cols] */
+    float *d_wmix;          /* backward out [3, 3] */
+    float *partials;        /* backward workspace: ceil(rows / 64) * (3 cols + 9) floats */
+    int64_t ld_low, ld_high, ld_high_agg, ld_ident, ld_out, ld_out_t, ld_d_out, ld_d_low, ld_d_high, ld_d_ident;
+    int32_t rows, cols, flags, reserved;
+} wdg_acm_mix_job;
+int wdg_acm_mix_batched_f32(const wdg_acm_mix_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols, wdg_stream_t stream);
+int wdg_acm_mix_backward_batched_f32(const wdg_acm_mix_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
+                                     wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,8 @@ SIGNATURES = {
                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p]),
     "wdg_relu_dropout_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_uint32, ctypes.c_float, c_uint32, c_void_p, c_void_p]),
     "wdg_synth_regular_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "wdg_acm_mix_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_acm_mix_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -282,6 +284,15 @@ class DropoutJob(ctypes.Structure):
     """mirror of `wdg_dropout_job` (include/wdg.h)"""
     _fields_ = [("h", c_void_p), ("ht", c_void_p), ("ld", c_int64), ("ld_t", c_int64), ("rows", c_int32), ("cols", c_int32),
                 ("stream", c_uint32)]
+
+
+class AcmMixJob(ctypes.Structure):
+    """mirror of `wdg_acm_mix_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("low", "high", "high_agg", "ident", "att", "wmix", "out", "out_t", "aux", "d_out", "d_low",
+                                              "d_high", "d_ident", "d_att", "d_wmix", "partials")] + \
+               [(name, c_int64) for name in ("ld_low", "ld_high", "ld_high_agg", "ld_ident", "ld_out", "ld_out_t", "ld_d_out", "ld_d_low",
+                                             "ld_d_high", "ld_d_ident")] + \
+               [("rows", c_int32), ("cols", c_int32), ("flags", c_int32), ("reserved", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

@@ -11,6 +11,12 @@ Forward AND backward run on csrc/spmm*.hip (A_hat^T for the backward pass is the
 graphs are directed) and csrc/gemm.hip (exact-fp32 MFMA).  PyTorch supplies autograd bookkeeping, dropout,
 log-softmax / NLL on [N, C] logits and Adam.  With a `DeviceDropout` the hidden layer's ReLU + dropout runs on csrc/dropout.hip
 instead: a counter-based mask that sweep.TrainBatch draws identically for the same (seed, stream, step).
+
+ACM-SGC-1 / ACM-GCN-2 (`ACMSGC1`, `ACMGCN2`) answer the reference's finding that a low-pass GNN falls below its MLP twin
+in the middle of the homophily range: every layer mixes a low-pass channel A_hat (M W_L), a high-pass channel (I - A_hat) (M W_H) -
+the g_high its loader returns, utils/util_funcs.py:198-204 - and an identity channel M W_I with per-node weights.  The mix and its
+backward pass run on csrc/acm_mix.hip; the layer is defined by this project (the reference names "mf-" models in
+gnns_on_syn.py:58-104 and gnns_on_syn.py:159-206 but ships none) and is not claimed to reproduce those tables.
 """
 import torch
 
@@ -202,6 +208,130 @@ class MLP2(torch.nn.Module):
             h = _Linear.apply(x, self.w0, True)
             h = torch.nn.functional.dropout(h, self.dropout, self.training)
         return _Linear.apply(h, self.w1, False)
+
+
+class _AcmMixer:
+    """The channel mix of one ACM layer on a one-job ops.AcmMixBatch: work buffers and the table over them per (rows, cols), built on
+    first use - before any capture - so that a captured forward / backward addresses the same memory on every replay.
+    What it requires: the buffers (aux among them) hold ONE forward pass, the latest.  A backward pass must either follow its own
+    forward pass with no other forward pass of this layer between them, or run eagerly: `version` counts forward passes on the host
+    and an eager backward pass that finds another forward pass in between runs its own again from the saved operands.  The counter
+    does not advance while a hipGraph replays, so inside a captured region a backward pass must follow its own forward pass there
+    (models.train_eval_graphed: forward, backward, Adam in one graph, the evaluation forward in another)."""
+
+    def __init__(self, relu):
+        self.relu = bool(relu)
+        self._tables = {}
+        self.version = 0  # forward passes so far: a backward pass whose forward is not the latest one runs it again (aux is the table's)
+
+    def table(self, rows, cols, dev):
+        key = (rows, cols)
+        if key not in self._tables:
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            b = dict(inp=z(4, rows, cols), att=z(3, cols), wmix=z(3, 3), out=z(rows, cols), d_out=z(rows, cols), d=z(3, rows, cols),
+                     d_att=z(3, cols), d_wmix=z(3, 3))
+            entry = dict(low=b["inp"][0], high=b["inp"][1], high_agg=b["inp"][2], ident=b["inp"][3], att=b["att"], wmix=b["wmix"], out=b["out"],
+                         d_out=b["d_out"], d_low=b["d"][0], d_high=b["d"][1], d_ident=b["d"][2], d_att=b["d_att"], d_wmix=b["d_wmix"])
+            self._tables[key] = (b, ops.AcmMixBatch([entry], self.relu))
+        return self._tables[key]
+
+    def run(self, inputs):
+        low, high, high_agg, ident, att, wmix = inputs
+        b, table = self.table(low.shape[0], low.shape[1], low.device)
+        for i, t in enumerate((low, high, high_agg, ident)):
+            b["inp"][i].copy_(t)
+        b["att"].copy_(att)
+        b["wmix"].copy_(wmix)
+        table.launch()
+        self.version += 1
+        return b, table
+
+    def __call__(self, low, high, high_agg, ident, att, wmix):
+        return _AcmMix.apply(low, high, high_agg, ident, att, wmix, self)
+
+
+class _AcmMix(torch.autograd.Function):
+    """out = 3 sum_c alpha_c H_c (include/wdg.h: wdg_acm_mix_batched_f32) and its backward pass, both on csrc/acm_mix.hip"""
+
+    @staticmethod
+    def forward(ctx, low, high, high_agg, ident, att, wmix, mixer):
+        b, _ = mixer.run((low, high, high_agg, ident, att, wmix))
+        ctx.save_for_backward(low, high, high_agg, ident, att, wmix)
+        ctx.mixer, ctx.version = mixer, mixer.version
+        return b["out"].clone()
+
+    @staticmethod
+    def backward(ctx, gy):
+        mixer = ctx.mixer
+        if mixer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
+            b, table = mixer.run(ctx.saved_tensors)
+        else:
+            b, table = mixer.table(gy.shape[0], gy.shape[1], gy.device)
+        b["d_out"].copy_(gy)
+        table.launch_backward()
+        d = b["d"].clone()
+        return d[0], d[1], -d[1], d[2], b["d_att"].clone(), b["d_wmix"].clone(), None
+
+
+def _acm_parameters(nfeat, width):
+    """the parameters of one ACM layer in the documented draw order: W_L, W_H, W_I (xavier_uniform, [nfeat, width] each), the attention
+    vectors a_L a_H a_I ([3, width], uniform in +- 1 / sqrt(width)), Wmix ([3, 3], uniform in +- 1 / sqrt(3)) ->
+    (weight [nfeat, 3 width] = [W_L | W_H | W_I], att, wmix)"""
+    if not 1 <= width <= ops.AcmMixBatch.MAX_COLS:
+        raise ValueError(f"an ACM layer of width {width}: the mix kernel holds 1..{ops.AcmMixBatch.MAX_COLS} (256) columns")
+    ws = [torch.nn.init.xavier_uniform_(torch.empty(nfeat, width)) for _ in range(3)]
+    att = (torch.rand(3, width) * 2 - 1) / width ** 0.5
+    wmix = (torch.rand(3, 3) * 2 - 1) / 3 ** 0.5
+    return torch.nn.Parameter(torch.cat(ws, 1)), torch.nn.Parameter(att), torch.nn.Parameter(wmix)
+
+
+class ACMSGC1(torch.nn.Module):
+    """ACM-SGC-1: logits = mix(A_hat (X W_L), X W_H - A_hat (X W_H), X W_I), one ACM layer of width C without activation.
+    Like SGC1 it caches Y = A_hat X (loop invariant) and computes low = Y W_L, high_agg = Y W_H, so that an epoch has no aggregation:
+    [low | high_agg] = Y [W_L | W_H] and [high | ident] = X [W_H | W_I] are one product each."""
+
+    def __init__(self, nfeat, nclass):
+        super().__init__()
+        self.weight, self.att, self.wmix = _acm_parameters(nfeat, nclass)
+        self.nclass = nclass
+        self._mix = _AcmMixer(relu=False)
+        self._cache = None
+
+    aggregate_once = SGC1.aggregate_once
+
+    def forward(self, adj, x):
+        c = self.nclass
+        ya = _Linear.apply(self.aggregate_once(adj, x), self.weight[:, :2 * c], False)  # [low | high_agg]
+        xb = _Linear.apply(x, self.weight[:, c:], False)                                 # [high | ident]
+        return self._mix(ya[:, :c], xb[:, :c], ya[:, c:], xb[:, c:], self.att, self.wmix)
+
+
+class ACMGCN2(torch.nn.Module):
+    """ACM-GCN-2: layer 1 (F -> nhid, activation on) -> dropout(relu(.)) -> layer 2 (nhid -> C, no activation); bias-free, A_hat the
+    random-walk normalisation as for GCN2.  A layer is one product M [W_L | W_H | W_I], one aggregation of its first two
+    column blocks and the mix.  dropout_rng: as for GCN2 (layer 1's output is non-negative: relu + dropout apply as they stand)."""
+
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
+        super().__init__()
+        self.w0, self.att0, self.wmix0 = _acm_parameters(nfeat, nhid)
+        self.w1, self.att1, self.wmix1 = _acm_parameters(nhid, nclass)
+        self.nhid, self.nclass = nhid, nclass
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._mix0, self._mix1 = _AcmMixer(relu=True), _AcmMixer(relu=False)
+
+    @staticmethod
+    def _layer(adj, m, w, att, wmix, width, mix):
+        mw = _Linear.apply(m, w, False)             # [M W_L | M W_H | M W_I]
+        ag = adj.matmul(mw[:, :2 * width])         # A_hat of the first two blocks
+        return mix(ag[:, :width], mw[:, width:2 * width], ag[:, width:], mw[:, 2 * width:], att, wmix)
+
+    def forward(self, adj, x):
+        o = self._layer(adj, x, self.w0, self.att0, self.wmix0, self.nhid, self._mix0)
+        if self.dropout_rng is not None:
+            h = self.dropout_rng.relu_dropout(o, self.dropout, self.training)
+        else:
+            h = torch.nn.functional.dropout(torch.relu(o), self.dropout, self.training)
+        return self._layer(adj, h, self.w1, self.att1, self.wmix1, self.nclass, self._mix1)
 
 
 def graphed_inference(model, adj, x, **forward_kwargs):

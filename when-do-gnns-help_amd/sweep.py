@@ -1608,6 +1608,11 @@ class TrainBatch:
         kind "mlp1": logits_j = X W_j                              (SGC-1's graph-agnostic twin: the "sgc" epoch on X, no aggregation)
         kind "mlp2": logits_j = relu(X W0_j) W1_j                  (GCN-2's twin: the "gcn" epoch without its four aggregations)
     (the baselines the reference's sweep plots the GNNs against: gnns_on_syn.py:109-154 SGC-1 / MLP-1, gnns_on_syn.py:213-249 GCN / MLP-2)
+        kind "acm_sgc": logits_j = mix(Y_j W_L, X W_H - Y_j W_H, X W_I)       (ACM-SGC-1, models.ACMSGC1: Y_j = A_hat_j X computed once)
+        kind "acm_gcn": two ACM layers, dropout(relu(.)) between them         (ACM-GCN-2, models.ACMGCN2)
+    (opt-in: a low-pass, a high-pass - the g_high = I - A_hat of utils/util_funcs.py:198-204 - and an identity channel mixed per node
+    on csrc/acm_mix.hip, ops.AcmMixBatch; their loss gradient is always _loss_gradient_as_autograd()'s, `dropout` applies to "acm_gcn"
+    alone and whole_run to neither; the four kinds above keep their code paths)
     Per-graph reference with identical arithmetic: models.train_eval_graphed (models.SGC1 / GCN2 / MLP1 / MLP2).
     run(whole_run=True) trains the two linear heads ("sgc", "mlp1") with every epoch inside one launch (ops.HeadTrainBatch).
 
@@ -1623,6 +1628,7 @@ class TrainBatch:
     # HEAD_BYTES_PER_S (measured, DESIGN 4.13 / profiles/head_train_timing.json: bound by a step's chain of latencies, not by bandwidth) and HEAD_RESIDENT of them
     # run at a time; the default epochs_per_launch follows from the two.
     HEAD_LAUNCH_S, HEAD_BYTES_PER_S, HEAD_RESIDENT = 0.2, 3.6e9, 256
+    ACM_KINDS = ("acm_sgc", "acm_gcn")
 
     def __init__(self, sb, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, train_frac=0.6, seed=0, dropout=0.0, dropout_seed=None):
         from .utils.util_funcs import random_disassortative_splits
@@ -1633,6 +1639,8 @@ class TrainBatch:
             raise ValueError(f"TrainBatch: a drop probability in [0, 1) expected, got {dropout!r}")
         if self.dropout > 0 and kind in ("sgc", "mlp1"):
             raise ValueError(f"TrainBatch: kind {kind!r} has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2')")
+        if self.dropout > 0 and kind == "acm_sgc":
+            raise ValueError("TrainBatch: kind 'acm_sgc' has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2' / 'acm_gcn')")
         self.drop = None  # (dropout > 0: the ops.DropoutBatch over hid / hid_t, and its step word)
         self.lr, self.weight_decay = lr, weight_decay
         self._head = None  # (run(whole_run=True): the ops.HeadTrainBatch over this batch's models, and the Adam steps it has taken)
@@ -1717,11 +1725,14 @@ class TrainBatch:
             self.bwd = [ops.GemmBatch([(self.hid_t[j], self.dlogits[j], self.w1.grad[j], None) for j in range(J)]),  # dW1 = H^T dZ
                         ops.GemmBatch([(self.dlogits[j], self.w1t[j], self.dhid[j], None) for j in range(J)]),       # dH = dZ W1^T
                         ops.GemmBatch([(xt[jobs[j].seed], self.dhid[j], self.w0.grad[j], None) for j in range(J)])]  # dW0 = X^T (dH * mask)
+        elif kind in self.ACM_KINDS:
+            self._build_acm(xavier, gen, fwd_spmm, bwd_spmm)
         else:
             raise ValueError(f"unknown model kind {kind!r}")
         if self.dropout > 0:
             self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)  # advances once per training forward, on the device
             self.drop = ops.DropoutBatch([(self.hid[j], self.hid_t[j], j) for j in range(J)], self.dropout, seed if dropout_seed is None else dropout_seed)
+        if self.dropout > 0 or kind in self.ACM_KINDS:
             # _loss_gradient_as_autograd(): where the train rows' label entries sit in a model's flattened [n, c] logits, and what
             # nll_loss's backward puts there for a mean over the train rows
             self._label_pos = self.tr * c + self.y_tr
@@ -1731,8 +1742,132 @@ class TrainBatch:
         self.best_test = torch.zeros(J, device=dev)
         self.graph = None
 
+    # -- ACM-SGC-1 / ACM-GCN-2 -----------------------------------------------------------------------------------
+    def _build_acm(self, xavier, gen, fwd_spmm, bwd_spmm):
+        """parameters, buffers and launch tables of the kinds "acm_sgc" / "acm_gcn".  The draw order per layer is fixed: W_L, W_H, W_I
+        (xavier_uniform per [Fin, width] matrix, all models of the shard at once), the attention vectors [3, width] uniform in
+        +- 1 / sqrt(width), Wmix [3, 3] uniform in +- 1 / sqrt(3) - layer 1 before layer 2; a layer's three matrices are stored side by
+        side, W = [W_L | W_H | W_I], so that one product M W serves the three channels and column slices of it go to the kernels in place
+        (models.ACMSGC1 / ACMGCN2 hold their parameters the same way and draw them in the same order, but per model and from torch's
+        global generator, where the batch draws every model's matrix in one call from its own seeded generator: no seed reproduces
+        model j on the per-graph side.  The two start equal by COPYING model j's slices of self.params into the per-graph model.)"""
+        sb, ops, J, n, c, f, hidden = self.sb, self.sb.ops, self.J, self.n, self.c, self.f, self.h
+        jobs, dev = sb.jobs, self.logits.device
+        z = lambda *s: torch.zeros((J,) + s, device=dev)  # noqa: E731
+
+        def layer_parameters(fin, width):
+            w = torch.cat([xavier(J, fin, width) for _ in range(3)], 2)
+            att = (((torch.rand((J, 3, width), generator=gen) * 2 - 1) / width ** 0.5)).to(dev)
+            wmix = (((torch.rand((J, 3, 3), generator=gen) * 2 - 1) / 3 ** 0.5)).to(dev)
+            out = [torch.nn.Parameter(t) for t in (w, att, wmix)]
+            for p in out:
+                p.grad = torch.zeros_like(p)
+            return out
+
+        xs = [sb.x[j.seed] for j in jobs]
+        xt = {s: x.t().contiguous() for s, x in sb.x.items()}
+        if self.kind == "acm_sgc":
+            sb.spmm.launch()  # Y_j = A_hat_j X, once
+            torch.cuda.synchronize()
+            self.ys = ys = sb.y
+            self.yt = torch.stack([y.t().contiguous() for y in ys])
+            self.w, self.att, self.wmix = self.params = layer_parameters(f, c)
+            self.ya, self.xb = z(n, 2 * c), z(n, 2 * c)        # [low | high_agg] = Y [W_L | W_H],  [high | ident] = X [W_H | W_I]
+            self.dya, self.dxb = z(n, 2 * c), z(n, 2 * c)      # [d_low | -d_high],  [d_high | d_ident]
+            self.gwa, self.gwb = z(f, 2 * c), z(f, 2 * c)
+            self.mix = [ops.AcmMixBatch([dict(low=self.ya[j][:, :c], high=self.xb[j][:, :c], high_agg=self.ya[j][:, c:], ident=self.xb[j][:, c:],
+                                              att=self.att.data[j], wmix=self.wmix.data[j], out=self.logits[j], d_out=self.dlogits[j],
+                                              d_low=self.dya[j][:, :c], d_high=self.dxb[j][:, :c], d_ident=self.dxb[j][:, c:],
+                                              d_att=self.att.grad[j], d_wmix=self.wmix.grad[j]) for j in range(J)], relu=False)]
+            self.fwd = [ops.GemmBatch([(ys[j], self.w.data[j][:, :2 * c], self.ya[j], None) for j in range(J)]),
+                        ops.GemmBatch([(xs[j], self.w.data[j][:, c:], self.xb[j], None) for j in range(J)])]
+            self.bwd = [ops.GemmBatch([(self.yt[j], self.dya[j], self.gwa[j], None) for j in range(J)]),            # Y^T [d_low | -d_high]
+                        ops.GemmBatch([(xt[jobs[j].seed], self.dxb[j], self.gwb[j], None) for j in range(J)])]     # X^T [d_high | d_ident]
+        else:
+            h = hidden
+            self.w0, self.att0, self.wmix0 = l0 = layer_parameters(f, h)
+            self.w1, self.att1, self.wmix1 = l1 = layer_parameters(h, c)
+            self.params = l0 + l1
+            self.xw, self.ag1, self.hid, self.hid_t = z(n, 3 * h), z(n, 2 * h), z(n, h), z(h, n)
+            self.hw, self.ag2 = z(n, 3 * c), z(n, 2 * c)
+            self.dg2, self.t2, self.dhw, self.dhid, self.w1t = z(n, 2 * c), z(n, 2 * c), z(n, 3 * c), z(n, h), z(3 * c, h)
+            self.dg1, self.t1, self.dxw = z(n, 2 * h), z(n, 2 * h), z(n, 3 * h)
+            with_t = self.dropout == 0  # (dropout > 0: ops.DropoutBatch writes hid_t with the masked hid)
+            self.mix = [ops.AcmMixBatch([dict(low=self.ag1[j][:, :h], high=self.xw[j][:, h:2 * h], high_agg=self.ag1[j][:, h:], ident=self.xw[j][:, 2 * h:],
+                                              att=self.att0.data[j], wmix=self.wmix0.data[j], out=self.hid[j], out_t=self.hid_t[j] if with_t else None,
+                                              d_out=self.dhid[j], d_low=self.dg1[j][:, :h], d_high=self.dg1[j][:, h:], d_ident=self.dxw[j][:, 2 * h:],
+                                              d_att=self.att0.grad[j], d_wmix=self.wmix0.grad[j]) for j in range(J)], relu=True),
+                        ops.AcmMixBatch([dict(low=self.ag2[j][:, :c], high=self.hw[j][:, c:2 * c], high_agg=self.ag2[j][:, c:], ident=self.hw[j][:, 2 * c:],
+                                              att=self.att1.data[j], wmix=self.wmix1.data[j], out=self.logits[j], d_out=self.dlogits[j],
+                                              d_low=self.dg2[j][:, :c], d_high=self.dg2[j][:, c:], d_ident=self.dhw[j][:, 2 * c:],
+                                              d_att=self.att1.grad[j], d_wmix=self.wmix1.grad[j]) for j in range(J)], relu=False)]
+            self.fwd = [ops.GemmBatch([(xs[j], self.w0.data[j], self.xw[j], None) for j in range(J)]),          # X [W_L | W_H | W_I]
+                        fwd_spmm([self.xw[j][:, :2 * h] for j in range(J)], self.ag1),                           # A_hat of the first two blocks
+                        ops.GemmBatch([(self.hid[j], self.w1.data[j], self.hw[j], None) for j in range(J)]),
+                        fwd_spmm([self.hw[j][:, :2 * c] for j in range(J)], self.ag2)]
+            self.bwd = [bwd_spmm(self.dg2, self.t2),                                                             # A_hat^T [d_low | d_high]
+                        ops.GemmBatch([(self.hid_t[j], self.dhw[j], self.w1.grad[j], None) for j in range(J)]),  # dW1 = H^T d(H W1)
+                        ops.GemmBatch([(self.dhw[j], self.w1t[j], self.dhid[j], None) for j in range(J)]),       # dH = d(H W1) W1^T
+                        bwd_spmm(self.dg1, self.t1),
+                        ops.GemmBatch([(xt[jobs[j].seed], self.dxw[j], self.w0.grad[j], None) for j in range(J)])]  # dW0 = X^T d(X W0)
+
+    def _acm_forward(self, train):
+        """every stage one batched launch; train (dropout > 0 only): layer 1's output goes through ops.DropoutBatch - relu + mask into
+        hid and hid_t - and the step word advances"""
+        if self.kind == "acm_sgc":
+            self.fwd[0].launch()
+            self.fwd[1].launch()
+            self.mix[0].launch()
+            return
+        self.fwd[0].launch()
+        self.fwd[1].launch()
+        self.mix[0].launch()  # hid (>= 0: the channels are, and the weights are a softmax's); hid_t as well when there is no dropout
+        if train:
+            self.drop.launch(self.drop_step)
+            self.drop_step.add_(1)
+        self.fwd[2].launch()
+        self.fwd[3].launch()
+        self.mix[1].launch()
+
+    @staticmethod
+    def _acm_operand_gradient(d_pair, t_pair, d_full, width):
+        """d(M W) = [A_hat^T dP_L | dP_H - A_hat^T dP_H | dP_I] from d_pair = [dP_L | dP_H] and t_pair = A_hat^T d_pair (the kernel has
+        written dP_I into the third block of d_full already)"""
+        d_full[..., :width].copy_(t_pair[..., :width])
+        torch.sub(d_pair[..., width:], t_pair[..., width:], out=d_full[..., width:2 * width])
+
+    def _acm_backward(self):
+        """the backward launches behind dlogits for the logits of the last _acm_forward()"""
+        c, h = self.c, self.h
+        if self.kind == "acm_sgc":
+            self.mix[0].launch_backward()
+            torch.neg(self.dxb[..., :c], out=self.dya[..., c:])  # d(high_agg) = -d_high
+            self.bwd[0].launch()
+            self.bwd[1].launch()
+            g = self.w.grad  # dW = [Y^T d_low | X^T d_high - Y^T d_high | X^T d_ident]
+            g[..., :c].copy_(self.gwa[..., :c])
+            torch.add(self.gwa[..., c:], self.gwb[..., :c], out=g[..., c:2 * c])
+            g[..., 2 * c:].copy_(self.gwb[..., c:])
+            return
+        self.mix[1].launch_backward()
+        self.bwd[0].launch()
+        self._acm_operand_gradient(self.dg2, self.t2, self.dhw, c)
+        self.bwd[1].launch()
+        self.w1t.copy_(self.w1.data.transpose(1, 2))
+        self.bwd[2].launch()
+        if self.drop is not None:
+            self.dhid.copy_(torch.where(self.hid > 0, self.dhid * self.drop.scale, 0.0))
+        else:
+            self.dhid.mul_(self.hid > 0)
+        self.mix[0].launch_backward()
+        self.bwd[3].launch()
+        self._acm_operand_gradient(self.dg1, self.t1, self.dxw, h)
+        self.bwd[4].launch()
+
     # -- one epoch ---------------------------------------------------------------------------------------------
     def _forward(self):
+        if self.kind in self.ACM_KINDS:
+            return self._acm_forward(train=False)
         if self.kind in ("sgc", "mlp1"):
             self.fwd[0].launch()
         elif self.kind == "mlp2":
@@ -1797,6 +1932,13 @@ class TrainBatch:
     def train_step(self):
         # (dropout == 0: the forward pass of these weights has been run already: by the previous epoch's evaluation, or by run())
         with torch.no_grad():
+            if self.kind in self.ACM_KINDS:
+                if self.drop is not None:
+                    self._acm_forward(train=True)
+                self._loss_gradient_as_autograd()
+                self._acm_backward()
+                self.opt.step()
+                return
             if self.drop is not None:
                 self._train_forward()
                 self._loss_gradient_as_autograd()

@@ -1,6 +1,7 @@
 """Training on the device: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the
 models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip, and the hidden layer's
-ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip."""
+ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip, and the channel mix of many ACM layers
+(ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip."""
 import ctypes
 import math
 
@@ -18,6 +19,9 @@ assert _HEAD_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.HeadTrainJob)
 _DROPOUT_JOB_DTYPE = np.dtype([("h", "<u8"), ("ht", "<u8"), ("ld", "<i8"), ("ld_t", "<i8"), ("rows", "<i4"), ("cols", "<i4"),
                                ("stream", "<u4"), ("tail_padding", "<u4")])
 assert _DROPOUT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.DropoutJob)
+_ACM_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
+                           for name, ctype in _lib.AcmMixJob._fields_])
+assert _ACM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.AcmMixJob)
 
 
 class HeadTrainBatch:
@@ -147,3 +151,118 @@ class DropoutBatch:
             raise ValueError("DropoutBatch.launch: a one-element int32 device tensor expected")
         check(lib.wdg_relu_dropout_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.threshold, self.scale,
                                                self.seed, _ptr(step), stream_handle()), "wdg_relu_dropout_batched_f32")
+
+
+def _views_may_overlap(a, b):
+    """whether two 2-D views with unit inner stride may share a byte.  Exact when their byte spans are disjoint and for views of
+    one row pitch (column slices of one wider matrix: they share nothing when their column ranges are disjoint inside the pitch);
+    other views whose spans intersect are reported as overlapping."""
+    def span(t):
+        r, c = t.shape
+        return t.data_ptr(), ((r - 1) * t.stride(0) + c) * 4 if r and c else 0
+    (pa, na), (pb, nb) = span(a), span(b)
+    if na == 0 or nb == 0 or pa + na <= pb or pb + nb <= pa:
+        return False
+    if a.shape[0] > 1 and b.shape[0] > 1 and a.stride(0) == b.stride(0):
+        pitch, wa, wb = a.stride(0) * 4, a.shape[1] * 4, b.shape[1] * 4
+        delta = (pb - pa) % pitch
+        return delta < wa or delta + wb > pitch
+    return True
+
+
+class AcmMixBatch:
+    """Job table for wdg_acm_mix_batched_f32 / wdg_acm_mix_backward_batched_f32 (csrc/acm_mix.hip): the channel mix of one ACM layer
+    per entry - out = 3 sum_c alpha_c H_c over the channels H_L = act(low), H_H = act(high - high_agg), H_I = act(ident), with
+    alpha = softmax((sigmoid(H_c . att_c) / 3) wmix) per row (include/wdg.h states it; tests/_acm_ref.py restates it in numpy) - and
+    its backward pass, a whole table per launch.  The table owns aux (alpha and the sigmoids of every row: written forward, read
+    backward) and the partial sums of the parameter gradients."""
+
+    MAX_COLS, MAX_JOBS, TILE = 256, 65535, 64
+
+    def __init__(self, entries, relu):
+        """entries: list of dicts of fp32 device tensors -
+             low, high, ident [rows, cols] (unit inner stride, any leading dimension: column slices of a wider matrix are fine),
+             high_agg [rows, cols] or None, att [3, cols] and wmix [3, 3] (contiguous), out [rows, cols], out_t None or [cols, rows];
+           and, for launch_backward(): d_out, d_low, d_high, d_ident [rows, cols], d_att [3, cols], d_wmix [3, 3] (contiguous)
+           - all six or none.  relu: the activation flag of every entry (one bool, or one per entry).
+        Raises for what the kernel does not take: cols outside 1..256, other dtypes, shapes or strides, more than 65535 entries, an
+        output that overlaps an input or another output of its entry."""
+        self.keep = entries
+        n = self.n_jobs = len(entries)
+        if n > self.MAX_JOBS:
+            raise ValueError(f"AcmMixBatch: {n} entries; one launch takes {self.MAX_JOBS}")
+        flags = [bool(relu)] * n if np.ndim(relu) == 0 else [bool(f) for f in relu]
+        if len(flags) != n:
+            raise ValueError("AcmMixBatch: one activation flag per entry")
+        mats = ("low", "high", "high_agg", "ident", "out", "d_out", "d_low", "d_high", "d_ident")
+        grads = ("d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
+        self.has_backward = n > 0
+        for e in entries:
+            unknown = set(e) - set(mats) - {"att", "wmix", "out_t", "d_att", "d_wmix"}
+            if unknown:
+                raise ValueError(f"AcmMixBatch: unknown keys {sorted(unknown)}")
+            if any(e.get(k) is None for k in ("low", "high", "ident", "att", "wmix", "out")):
+                raise ValueError("AcmMixBatch: low, high, ident, att, wmix and out are required")
+            rows, cols = e["low"].shape if isinstance(e["low"], torch.Tensor) and e["low"].dim() == 2 else (-1, -1)
+            if not 1 <= cols <= self.MAX_COLS:
+                raise ValueError(f"AcmMixBatch: a layer of {cols} columns; the kernel holds 1..{self.MAX_COLS}")
+            given = [k for k in grads if e.get(k) is not None]
+            if given and len(given) != len(grads):
+                raise ValueError("AcmMixBatch: d_out, d_low, d_high, d_ident, d_att and d_wmix come together or not at all")
+            self.has_backward = self.has_backward and bool(given)
+            for k in mats:
+                t = e.get(k)
+                if t is None:
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (rows, cols):
+                    raise ValueError(f"AcmMixBatch: {k} must be a [{rows}, {cols}] fp32 device matrix")
+                if (cols > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < cols):
+                    raise ValueError(f"AcmMixBatch: the rows of {k} must be contiguous and must not overlap")
+            for k, shape in (("att", (3, cols)), ("wmix", (3, 3)), ("d_att", (3, cols)), ("d_wmix", (3, 3))):
+                t = e.get(k)
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
+                                      or tuple(t.shape) != shape or not t.is_contiguous()):
+                    raise ValueError(f"AcmMixBatch: {k} must be a contiguous {list(shape)} fp32 device tensor")
+            t = e.get("out_t")
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (cols, rows)
+                                  or (rows > 1 and t.stride(1) != 1) or (cols > 1 and t.stride(0) < rows)):
+                raise ValueError(f"AcmMixBatch: out_t must be a [{cols}, {rows}] fp32 device matrix with contiguous rows")
+            outputs = ("out", "out_t", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
+            given = [(k, t) for k, t in e.items() if t is not None]
+            for i, (ka, ta) in enumerate(given):
+                for kb, tb in given[i + 1:]:
+                    if (ka in outputs or kb in outputs) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"AcmMixBatch: {ka} and {kb} overlap; an output must not overlap an input or another output")
+        dev = require_gpu()  # (after the checks that need no device)
+        rows = np.fromiter((e["low"].shape[0] for e in entries), np.int64, n)
+        cols = np.fromiter((e["low"].shape[1] for e in entries), np.int64, n)
+        self.max_rows, self.max_cols = int(rows.max(initial=0)), int(cols.max(initial=0))
+        self.aux = torch.zeros((max(int(rows.sum()), 1), 8), dtype=torch.float32, device=dev)
+        row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        plen = -(-rows // self.TILE) * (3 * cols + 9)
+        part_off = np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)
+        self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
+        tab = np.zeros(n, _ACM_JOB_DTYPE)
+        for i, e in enumerate(entries):
+            for k in ("low", "high", "high_agg", "ident", "att", "wmix", "out", "out_t", "d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix"):
+                t = e.get(k)
+                tab[k][i] = 0 if t is None else t.data_ptr()
+                if "ld_" + k in _ACM_JOB_DTYPE.names:
+                    tab["ld_" + k][i] = 0 if t is None else _ld(t)
+        tab["aux"] = self.aux.data_ptr() + 32 * row_off[:-1]
+        if self.has_backward:
+            tab["partials"] = self.partials.data_ptr() + 4 * part_off[:-1]
+        tab["rows"], tab["cols"], tab["flags"] = rows, cols, np.asarray(flags, np.int64)
+        self.aux_of = [self.aux[row_off[i]:row_off[i + 1]] for i in range(n)]  # [rows, 8] per entry: alpha_L alpha_H alpha_I s_L s_H s_I 0 0
+        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self):
+        """out (and out_t, aux) of every entry"""
+        check(lib.wdg_acm_mix_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()), "wdg_acm_mix_batched_f32")
+
+    def launch_backward(self):
+        """d_low, d_high, d_ident, d_att, d_wmix of every entry from d_out, the inputs and the aux of the last launch()"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError("AcmMixBatch.launch_backward: the table was built without gradient tensors")
+        check(lib.wdg_acm_mix_backward_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()),
+              "wdg_acm_mix_backward_batched_f32")
