@@ -1136,6 +1136,54 @@ int wdg_acm_mix_batched_f32(const wdg_acm_mix_job *jobs_dev, int32_t n_jobs, int
 int wdg_acm_mix_backward_batched_f32(const wdg_acm_mix_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
                                      wdg_stream_t stream);
 
+/*
+ * The tail of a training epoch for many models whose logits are STACKED along the feature axis - all splits ("replicas") of one
+ * graph share A_hat, X and the labels, so their logits are column blocks of one [n, R cs] matrix: the cross-entropy gradient of
+ * every replica's train rows, its validation and test hits and its model selection, in one pass.  A job is one graph's stacked
+ * logits; n, R, C and cs are the job's own (a ragged table).
+ * replaces: the accuracy of utils/util_funcs.py:393 and the loss / accuracy bookkeeping of the training loops behind the accuracy
+ *           tables gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249 (the loop itself lives upstream of the reference).  It stands
+ *           in for the softmax / scatter / argmax / gather / where launches of sweep.TrainBatch.train_step and eval_step.
+ * The definition, for row i and replica r of a job, with z_k = logits[i][r cs + k], k = 0 .. C - 1; all arithmetic in fp32, in this
+ * order (tests/_xent_ref.py restates it in numpy):
+ *   WDG_XENT_GRAD:
+ *     split[i][r] == 1:  m = max_k z_k;  e_k = exp(z_k - m);  s = e_0 + e_1 + ... + e_{C-1} (in that order);
+ *                        dlogits[i][r cs + k] = (e_k / s - [k == labels[i]]) * inv_n_train[r]
+ *     otherwise:         dlogits[i][r cs + k] = +0.0f
+ *     the padding columns C .. cs - 1 of every replica are written +0.0f (the backward aggregation reads whole rows); the padding
+ *     columns of logits are never read; nothing beyond column R cs of a row is read or written.  A label outside 0 .. C - 1 matches no
+ *     class (the rule of wdg_head_train_batched_f32).  A NaN among the z's makes all C gradients NaN: a diverged run is not hidden.
+ *   WDG_XENT_EVAL:
+ *     pred = the first k with z_k == m; a row with a NaN among its z's has no prediction.  A row with split code 2 (validation) or 3
+ *     (test) is a hit when pred == labels[i].  After ALL rows are counted, for every r:
+ *       if hits[r][0] > best[r][0] (strict):  best[r] = (hits[r][0], hits[r][1], *step_dev);      then hits[r] = (0, 0).
+ *     *step_dev is read from DEVICE memory when the kernel runs: a captured epoch that also increments the word records the right
+ *     step on every replay.  The selection is a second small launch inside the same call.
+ * Deterministic: the hits are integer sums (per workgroup in LDS, then one integer add per workgroup and counter), there is no
+ * floating-point atomic, two runs are bit-identical, and a replica's outputs do not depend on which other replicas or jobs are in
+ * the table.
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, flags outside 1 .. 3, a NULL step_dev
+ * with WDG_XENT_EVAL, more than 65535 jobs (a job per grid z).  max_cols names the table's largest C: more than 16 classes (the class
+ * limit of wdg_gnb_batched_f32) is WDG_ERR_UNSUPPORTED.  n_jobs == 0: WDG_OK, nothing is launched.  A job with n == 0 or R == 0 is
+ * skipped, and so is one whose own C lies outside 1 .. 16 or whose cs < C; rows beyond max_rows (the table's largest n) are left untouched.
+ */
+#define WDG_XENT_GRAD 1
+#define WDG_XENT_EVAL 2
+typedef struct wdg_xent_job {
+    const float *logits;      /* [n, R*cs] fp32, leading dimension ld_logits; replica r's classes are columns r*cs .. r*cs + C-1 */
+    float *dlogits;           /* [n, R*cs], leading dimension ld_dlogits (flag GRAD) */
+    const int32_t *labels;    /* [n], shared by the replicas */
+    const uint8_t *split;     /* [n, R] row-major: 0 unused, 1 train, 2 validation, 3 test */
+    const float *inv_n_train; /* [R]: (float)(1 / n_train_r), computed by the host */
+    int32_t *hits;            /* [R, 2] work space, zero before the first call; left zero by every EVAL call */
+    int32_t *best;            /* [R, 3] in/out: validation hits of the best epoch (-1: none yet), test hits at it, its step */
+    int64_t ld_logits, ld_dlogits;
+    int32_t n, R, C, cs;
+} wdg_xent_job;
+int wdg_xent_eval_batched_f32(const wdg_xent_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
+                              int32_t flags /* WDG_XENT_GRAD = 1, WDG_XENT_EVAL = 2, or both */,
+                              const int32_t *step_dev, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,7 @@ SIGNATURES = {
     "wdg_synth_regular_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "wdg_acm_mix_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_acm_mix_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_xent_eval_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -293,6 +294,12 @@ class AcmMixJob(ctypes.Structure):
                [(name, c_int64) for name in ("ld_low", "ld_high", "ld_high_agg", "ld_ident", "ld_out", "ld_out_t", "ld_d_out", "ld_d_low",
                                              "ld_d_high", "ld_d_ident")] + \
                [("rows", c_int32), ("cols", c_int32), ("flags", c_int32), ("reserved", c_int32)]
+
+
+class XentJob(ctypes.Structure):
+    """mirror of `wdg_xent_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("logits", "dlogits", "labels", "split", "inv_n_train", "hits", "best")] + \
+               [("ld_logits", c_int64), ("ld_dlogits", c_int64), ("n", c_int32), ("R", c_int32), ("C", c_int32), ("cs", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

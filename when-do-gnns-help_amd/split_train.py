@@ -1,0 +1,341 @@
+"""All splits of ONE graph trained as a single stacked run (SplitTrainBatch).
+
+The real-graph experiments train one graph over ten 60/20/20 splits (the reference ships ten fixed splits per dataset and compares
+its metrics with the accuracies trained on them); sweep.TrainBatch trains one model per GRAPH and wants equal node counts and
+balanced classes, so those runs went one split at a time through models.train_eval_graphed.  The R replicas share A_hat, X and
+the labels - only the weights and the row masks differ - so they are stacked along the feature axis here:
+    A_hat [H_1 | ... | H_R]   one aggregation of R hidden (or R cs) columns instead of R narrow ones: the graph is walked once
+    X [W0_1 | ... | W0_R]     one first-layer product
+and the per-replica products (H_r W1_r, H_r^T dZ_r, dZ_r W1_r^T) are column-block entries of ops.GemmBatch tables.  The epoch's tail
+- cross-entropy gradient, validation / test hits, model selection, with per-replica masks of unequal size - is one kernel,
+csrc/xent_eval.hip (ops.XentEvalBatch).  PyTorch supplies the parameters' memory, the backward ReLU mask and one Adam over the
+stacked parameters (element-wise: stacking changes nothing).
+
+Stacked layout (cs = C rounded up to a multiple of 4; replica r owns hidden columns r hidden .. and class columns r cs .. r cs + C - 1):
+    kinds "gcn" / "mlp2":  w0 [F, R hidden], w1 [R, hidden, cs]        kinds "sgc" / "mlp1":  w [F, R cs]
+The padding columns of the weights start at zero and stay zero: their gradient is zero, and weight decay of zero is zero."""
+import time
+
+import numpy as np
+import torch
+
+from ._lib import require_gpu
+from ._rt import _dev
+from .aggregate import spmm
+from .gemm import GemmBatch, gemm
+from .train import XENT_EVAL, XENT_GRAD, DropoutBatch, XentEvalBatch
+
+MAX_CLASSES = XentEvalBatch.MAX_C
+
+
+def masks_from_indices(n, splits):
+    """splits: a list of (train, valid, test) index arrays, one triple per replica -> bool [R, 3, n]"""
+    masks = np.zeros((len(splits), 3, n), bool)
+    for r, triple in enumerate(splits):
+        if len(triple) != 3:
+            raise ValueError("masks_from_indices: a (train, valid, test) triple per replica expected")
+        for k, idx in enumerate(triple):
+            idx = np.asarray(idx, np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= n):
+                raise ValueError(f"masks_from_indices: an index outside 0..{n - 1}")
+            masks[r, k, idx] = True
+    return masks
+
+
+def random_masks(labels, R, seed, train_frac=0.6):
+    """R draws of utils.util_funcs.random_disassortative_splits (class-balanced train rows, 20 % validation, the rest test) from
+    torch's CPU generator seeded with `seed` (the caller's generator state is put back) -> bool [R, 3, n]"""
+    from .utils.util_funcs import random_disassortative_splits
+    labels = torch.as_tensor(np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)).long()
+    c = int(labels.max()) + 1
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(seed))
+        draws = [random_disassortative_splits(labels, c, train_frac) for _ in range(int(R))]
+    return np.stack([np.stack([m.cpu().numpy().astype(bool) for m in d]) for d in draws])
+
+
+def replica_seed(seed, r):
+    """the seed of replica r's CPU generator: a replica's initial weights depend on (seed, r) alone, not on R.  Kept inside 31 bits:
+    torch's CPU generator (mt19937) is seeded by the low 32 bits of what it is given."""
+    return (int(seed) * 1000003 + int(r)) & 0x7FFFFFFF
+
+
+def xavier(fan_in, fan_out, gen):
+    """[fan_in, fan_out] fp32, uniform in +-sqrt(6 / (fan_in + fan_out)), from a seeded CPU generator (sweep.TrainBatch's rule)"""
+    bound = (6.0 / (fan_in + fan_out)) ** 0.5
+    return (torch.rand((fan_in, fan_out), generator=gen) * 2 - 1) * bound
+
+
+class SplitTrainBatch:
+    """Train + evaluate R replicas of one model on one graph, one per split, as a single stacked run.
+
+        kind "sgc":  logits_r = (A_hat X) W_r                        (the aggregation is computed once)
+        kind "gcn":  logits_r = A_hat relu(A_hat (X W0_r)) W1_r
+        kind "mlp1": logits_r = X W_r                                kind "mlp2": logits_r = relu(X W0_r) W1_r
+    bias-free, as in sweep.TrainBatch; the per-replica reference is replica_model(r): a models.SGC1 / GCN2 / MLP1 / MLP2.
+
+    An epoch has the meaning of TrainBatch's: gradient of the train loss -> Adam (the L2 term in the gradient) -> a clean forward pass
+    -> evaluation and model selection; a step word in device memory advances at its end.  Without dropout the clean forward pass is
+    the next epoch's training forward pass.  dropout = p > 0 (kinds "gcn" / "mlp2") starts the epoch with a training forward pass
+    whose masks are those of wdg_relu_dropout_batched_f32 with seed `dropout_seed` (default: `seed`), replica r's stream = r and the
+    step word: what models.DeviceDropout(dropout_seed, stream=r) draws.
+
+    adj: whatever models.NormAdj takes, or a NormAdj (then `symmetric` is the NormAdj's own); None for the MLP kinds.
+    x [n, F] fp32 (host or device), labels [n] integers, masks bool [R, 3, n] (train, validation, test; sizes may differ between
+    replicas, classes may be unbalanced).  Raises ValueError for a replica without a train or a validation row, overlapping sets, a
+    split row whose label lies outside 0 .. C - 1, more than 16 classes, dropout with a kind that has no hidden layer."""
+
+    KINDS = ("sgc", "gcn", "mlp1", "mlp2")
+
+    def __init__(self, adj, x, labels, masks, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
+                 dropout_seed=None):
+        if kind not in self.KINDS:
+            raise ValueError(f"SplitTrainBatch: unknown model kind {kind!r} (one of {self.KINDS}; the ACM kinds are sweep.TrainBatch's)")
+        self.kind, self.dropout = kind, float(dropout)
+        self.two_layer = kind in ("gcn", "mlp2")
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"SplitTrainBatch: a drop probability in [0, 1) expected, got {dropout!r}")
+        if self.dropout > 0 and not self.two_layer:
+            raise ValueError(f"SplitTrainBatch: kind {kind!r} has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2')")
+        labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
+        n = labels_np.shape[0]
+        masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+        if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[2] != n or masks.shape[0] < 1:
+            raise ValueError(f"SplitTrainBatch: masks must be a bool array [R, 3, n = {n}], got {masks.dtype} {tuple(masks.shape)}")
+        R = masks.shape[0]
+        c = int(labels_np.max()) + 1 if n else 0
+        if not 1 <= c <= MAX_CLASSES:
+            raise ValueError(f"SplitTrainBatch: {c} classes; the loss kernel holds 1..{MAX_CLASSES}")
+        if (masks.sum(1) > 1).any():
+            raise ValueError("SplitTrainBatch: the train, validation and test rows of a replica overlap")
+        counts = masks.sum(2)  # [R, 3]
+        if (counts[:, 0] < 1).any() or (counts[:, 1] < 1).any():
+            raise ValueError("SplitTrainBatch: every replica needs at least one train row and one validation row")
+        if (labels_np[masks.any((0, 1))] < 0).any():
+            raise ValueError(f"SplitTrainBatch: a row of a split carries a label outside 0..{c - 1}")
+        dev = require_gpu()  # (after the checks that need no device)
+        from . import models
+        if kind in ("sgc", "gcn"):
+            self.adj = adj if isinstance(adj, models.NormAdj) else models.NormAdj(adj, symmetric=symmetric)
+            if self.adj.n != n:
+                raise ValueError(f"SplitTrainBatch: the graph has {self.adj.n} nodes, labels has {n}")
+        else:
+            self.adj = adj if isinstance(adj, models.NormAdj) or adj is None else models.NormAdj(adj, symmetric=symmetric)
+        x = _dev(x, torch.float32, dev)
+        if x.dim() != 2 or x.shape[0] != n:
+            raise ValueError(f"SplitTrainBatch: x must be [n = {n}, F]")
+        f, h = x.shape[1], int(hidden)
+        cs = -(-c // 4) * 4
+        self.x, self.n, self.R, self.c, self.cs, self.f, self.h = x, n, R, c, cs, f, h
+        self.lr, self.weight_decay, self.seed = lr, weight_decay, int(seed)
+        self.dropout_seed = self.seed if dropout_seed is None else int(dropout_seed)
+        self.n_train, self.n_val, self.n_test = (counts[:, k].copy() for k in range(3))
+        self.labels = torch.from_numpy(labels_np.astype(np.int32)).to(dev)
+        codes = (masks[:, 0] * 1 + masks[:, 1] * 2 + masks[:, 2] * 3).astype(np.uint8)  # [R, n]
+        self.split = torch.from_numpy(np.ascontiguousarray(codes.T)).to(dev)  # [n, R]
+        self.inv_n_train = torch.from_numpy((1.0 / counts[:, 0].astype(np.float64)).astype(np.float32)).to(dev)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)  # epochs done; the dropout masks' step word as well
+
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        self.logits, self.dlogits = z(n, R * cs), z(n, R * cs)
+        blk = lambda t, r, w: t[:, r * w:(r + 1) * w]  # noqa: E731  (replica r's column block of a stacked matrix)
+        if self.two_layer:
+            w0, w1 = z(f, R * h), z(R, h, cs)
+            for r in range(R):
+                gen = torch.Generator(device="cpu").manual_seed(replica_seed(seed, r))
+                blk(w0, r, h).copy_(xavier(f, h, gen))
+                w1[r, :, :c].copy_(xavier(h, c, gen))
+            self.w0, self.w1 = torch.nn.Parameter(w0), torch.nn.Parameter(w1)
+            self.w0.grad, self.w1.grad = torch.zeros_like(w0), torch.zeros_like(w1)
+            self.params = [self.w0, self.w1]
+            self.xt = x.t().contiguous()  # for dW0 = X^T dP
+            self.hid, self.hid_t, self.dhid, self.w1t = z(n, R * h), z(R * h, n), z(n, R * h), z(R, cs, h)
+            if kind == "gcn":
+                self.p, self.z, self.dz, self.dp = z(n, R * h), z(n, R * cs), z(n, R * cs), z(n, R * h)
+            head_out = self.z if kind == "gcn" else self.logits     # Z_r = H_r W1_r: aggregated afterwards ("gcn") or the logits ("mlp2")
+            head_grad = self.dz if kind == "gcn" else self.dlogits  # dZ_r
+            self.head = GemmBatch([(blk(self.hid, r, h), self.w1.data[r], blk(head_out, r, cs), None) for r in range(R)])
+            self.d_w1 = GemmBatch([(self.hid_t[r * h:(r + 1) * h], blk(head_grad, r, cs), self.w1.grad[r], None) for r in range(R)])  # H_r^T dZ_r
+            self.d_hid = GemmBatch([(blk(head_grad, r, cs), self.w1t[r], blk(self.dhid, r, h), None) for r in range(R)])               # dZ_r W1_r^T
+            units = [(blk(self.hid, r, h), self.hid_t[r * h:(r + 1) * h], r) for r in range(R)]
+            if self.dropout > 0:
+                self.drop = DropoutBatch(units, self.dropout, self.dropout_seed)
+                self.relu = DropoutBatch([(u, None, r) for u, _, r in units], 0.0, self.dropout_seed)  # the clean pass: no transposed copy is read
+            else:
+                self.drop = self.relu = DropoutBatch(units, 0.0, self.dropout_seed)  # p = 0: a plain ReLU plus the transposed copy
+        else:
+            w = z(f, R * cs)
+            for r in range(R):
+                gen = torch.Generator(device="cpu").manual_seed(replica_seed(seed, r))
+                w[:, r * cs:r * cs + c].copy_(xavier(f, c, gen))
+            self.w = torch.nn.Parameter(w)
+            self.w.grad = torch.zeros_like(w)
+            self.params = [self.w]
+            self.drop = None
+            if kind == "sgc":
+                a = self.adj
+                self.y = spmm(a.graph, x, row_scale=a.row_scale, col_scale=a.col_scale)  # Y = A_hat X, once
+            else:
+                self.y = x
+            self.yt = self.y.t().contiguous()  # for dW = Y^T dlogits
+        self.xent = XentEvalBatch([dict(logits=self.logits, dlogits=self.dlogits, labels=self.labels, split=self.split,
+                                        inv_n_train=self.inv_n_train, C=c, cs=cs)])
+        self.best = self.xent.best_of[0]  # [R, 3] int32: validation hits of the best epoch (-1: none yet), test hits at it, its epoch
+        # torch's fused Adam: its kernel forms the bias corrections 1 - beta^t in double precision.  The unfused capturable path forms
+        # them in fp32 tensors - 1 - 0.999^t cancels to a relative error of 1e-5 - and twelve epochs end 9e-7 from a float64 run where
+        # this form ends 1e-7 from it (measured: tests/test_gpu_split_train.py).  Both keep the step count on the device: capturable.
+        self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True, fused=True)
+        self.graph = None
+
+    # -- the stacked products ----------------------------------------------------------------------------------
+    def _aggregate(self, src, out):
+        a = self.adj
+        spmm(a.graph, src, row_scale=a.row_scale, col_scale=a.col_scale, out=out)
+
+    def _aggregate_t(self, src, out):
+        a = self.adj  # (R A C)^T = C A^T R
+        spmm(a.graph_t, src, row_scale=a.col_scale, col_scale=a.row_scale, out=out)
+
+    def forward(self, train=False):
+        """the logits of the current weights into self.logits; train=True (dropout > 0): with the dropout masks of the current step
+        word.  The hidden layer's launch also leaves hid^T in hid_t, which the backward pass reads."""
+        with torch.no_grad():
+            if not self.two_layer:
+                gemm(self.y, self.w.data, out=self.logits)
+                return
+            unit = self.drop if (train or self.dropout == 0) else self.relu
+            if self.kind == "gcn":
+                gemm(self.x, self.w0.data, out=self.p)     # P = X [W0_1 | ... | W0_R]
+                self._aggregate(self.p, self.hid)           # A_hat P
+                unit.launch(self.step)                      # relu (+ dropout), hid^T
+                self.head.launch()                          # Z_r = H_r W1_r
+                self._aggregate(self.z, self.logits)        # logits = A_hat Z
+            else:
+                gemm(self.x, self.w0.data, out=self.hid)
+                unit.launch(self.step)
+                self.head.launch()
+
+    def _backward(self):
+        """the weight gradients behind self.dlogits, for the forward pass that produced self.logits"""
+        with torch.no_grad():
+            if not self.two_layer:
+                gemm(self.yt, self.dlogits, out=self.w.grad)  # dW = Y^T dlogits
+                return
+            if self.kind == "gcn":
+                self._aggregate_t(self.dlogits, self.dz)      # dZ = A_hat^T dlogits
+            self.d_w1.launch()
+            self.w1t.copy_(self.w1.data.transpose(1, 2))
+            self.d_hid.launch()
+            # a unit passes its gradient on (scaled) exactly where its output is positive: it was positive and kept
+            self.dhid.copy_(torch.where(self.hid > 0, self.dhid * self.drop.scale, 0.0))
+            if self.kind == "gcn":
+                self._aggregate_t(self.dhid, self.dp)         # dP = A_hat^T dH
+                gemm(self.xt, self.dp, out=self.w0.grad)      # dW0 = X^T dP
+            else:
+                gemm(self.xt, self.dhid, out=self.w0.grad)
+
+    def gradients(self):
+        """the gradients of every replica's mean train loss at the current weights into the parameters' .grad (no weight decay, no
+        Adam step): a training forward pass when dropout > 0 - else the logits of the last forward() are used - the loss kernel, the
+        backward products"""
+        if self.dropout > 0:
+            self.forward(train=True)
+        self.xent.launch(XENT_GRAD)
+        self._backward()
+
+    def train_step(self):
+        # (dropout == 0: the forward pass of these weights has been run already: by the previous epoch's evaluation, or by run())
+        self.gradients()
+        self.opt.step()
+
+    def eval_step(self):
+        self.forward(train=False)
+        self.xent.launch(XENT_EVAL, self.step)
+        self.step.add_(1)
+
+    def epoch(self):
+        """one epoch, eager (run() and capture() call forward() once before the first epoch of a run without dropout)"""
+        self.train_step()
+        self.eval_step()
+
+    def capture(self):
+        """Capture one epoch as a hipGraph (after a warm-up whose effects are rewound); returns the replay callable."""
+        saved = [p.detach().clone() for p in self.params]
+        saved_step, saved_best = self.step.clone(), self.xent.best.clone()
+        saved_state = [{k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for st in self.opt.state.values()]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self.forward()
+            for _ in range(2):
+                self.epoch()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+
+        def rewind():
+            with torch.no_grad():
+                for p, s in zip(self.params, saved):
+                    p.copy_(s)
+                for i, st in enumerate(self.opt.state.values()):
+                    for k, v in st.items():
+                        if torch.is_tensor(v):
+                            if i < len(saved_state) and k in saved_state[i]:
+                                v.copy_(saved_state[i][k])
+                            else:
+                                v.zero_()
+                self.step.copy_(saved_step)
+                self.xent.best.copy_(saved_best)
+
+        rewind()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.epoch()
+        rewind()  # (capturing does not execute: explicit all the same)
+        return self.graph.replay
+
+    def run(self, epochs=200, capture=True):
+        """-> dict(val_acc [R], test_acc [R], best_epoch [R], seconds, replicas_per_s): `epochs` more epochs of every replica"""
+        step = (self.graph.replay if self.graph is not None else self.capture()) if capture else self.epoch
+        self.forward()  # logits of the current weights
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(epochs):
+            step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        best = self.best.cpu().numpy()
+        none = best[:, 0] < 0
+        return dict(val_acc=torch.from_numpy(np.where(none, -1.0, best[:, 0] / self.n_val)),
+                    test_acc=torch.from_numpy(np.where(none, 0.0, best[:, 1] / np.maximum(self.n_test, 1))),
+                    best_epoch=torch.from_numpy(best[:, 2].astype(np.int64)), seconds=dt, replicas_per_s=self.R / dt, epochs=epochs)
+
+    # -- one replica ---------------------------------------------------------------------------------------------
+    def weights_of(self, r, grad=False):
+        """replica r's weights (or their gradients) as views without the padding columns: (W,) or (W0, W1)"""
+        c, cs, h = self.c, self.cs, self.h
+        pick = (lambda p: p.grad) if grad else (lambda p: p.data)
+        if self.two_layer:
+            return pick(self.w0)[:, r * h:(r + 1) * h], pick(self.w1)[r, :, :c]
+        return (pick(self.w)[:, r * cs:r * cs + c],)
+
+    def logits_of(self, r):
+        return self.logits[:, r * self.cs:r * self.cs + self.c]
+
+    def replica_model(self, r):
+        """a models.SGC1 / GCN2 / MLP1 / MLP2 on the device holding replica r's CURRENT weights (copies); with dropout > 0 its hidden
+        layer draws from models.DeviceDropout(dropout_seed, stream=r), whose step word starts at 0"""
+        from . import models
+        if not 0 <= r < self.R:
+            raise ValueError(f"SplitTrainBatch.replica_model: replica {r} of {self.R}")
+        with torch.random.fork_rng(devices=[]):  # (the constructors draw an initialisation that is overwritten below)
+            if self.two_layer:
+                rng = models.DeviceDropout(self.dropout_seed, stream=r) if self.dropout > 0 else None
+                cls = models.GCN2 if self.kind == "gcn" else models.MLP2
+                model = cls(self.f, self.c, nhid=self.h, dropout=self.dropout, dropout_rng=rng)
+            else:
+                model = (models.SGC1 if self.kind == "sgc" else models.MLP1)(self.f, self.c)
+        model = model.to(self.x.device)
+        with torch.no_grad():
+            for p, w in zip(model.parameters(), self.weights_of(r)):
+                p.copy_(w)
+        return model

@@ -1,7 +1,8 @@
 """Training on the device: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the
 models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip, and the hidden layer's
 ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip, and the channel mix of many ACM layers
-(ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip."""
+(ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip,
+and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip."""
 import ctypes
 import math
 
@@ -22,6 +23,10 @@ assert _DROPOUT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.DropoutJob)
 _ACM_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
                            for name, ctype in _lib.AcmMixJob._fields_])
 assert _ACM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.AcmMixJob)
+_XENT_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
+                            for name, ctype in _lib.XentJob._fields_])
+assert _XENT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.XentJob)
+XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
 
 
 class HeadTrainBatch:
@@ -266,3 +271,100 @@ class AcmMixBatch:
             raise ValueError("AcmMixBatch.launch_backward: the table was built without gradient tensors")
         check(lib.wdg_acm_mix_backward_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()),
               "wdg_acm_mix_backward_batched_f32")
+
+
+class XentEvalBatch:
+    """Job table for wdg_xent_eval_batched_f32 (csrc/xent_eval.hip): the tail of an epoch for models whose logits are stacked along
+    the feature axis - replica r of an entry owns columns r cs .. r cs + C - 1 of its [n, R cs] logits.  launch(XENT_GRAD) writes the
+    cross-entropy gradient of every replica's train rows (+0 elsewhere and in the padding columns); launch(XENT_EVAL) counts every
+    replica's validation and test hits and keeps the best (include/wdg.h states both; tests/_xent_ref.py restates them in numpy).
+    The table owns self.hits and self.best (one [R, 2] / [R, 3] int32 view per entry in hits_of / best_of)."""
+
+    MAX_C, MAX_JOBS = 16, 65535
+
+    def __init__(self, entries):
+        """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), dlogits the same or
+        None (then launch(XENT_GRAD) is refused), labels [n] int32 device, split [n, R] uint8 device contiguous (0 unused, 1 train,
+        2 validation, 3 test), inv_n_train [R] fp32 device, C, cs (default: C).  R is split's second dimension.
+        Raises ValueError for other shapes, dtypes or strides, C outside 1 .. 16, cs < C, R cs beyond a row, more than 65535 entries."""
+        self.keep = entries
+        n_jobs = self.n_jobs = len(entries)
+        if n_jobs > self.MAX_JOBS:
+            raise ValueError(f"XentEvalBatch: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
+        self.has_grad = n_jobs > 0
+        shapes = []
+        for e in entries:
+            unknown = set(e) - {"logits", "dlogits", "labels", "split", "inv_n_train", "C", "cs"}
+            if unknown:
+                raise ValueError(f"XentEvalBatch: unknown keys {sorted(unknown)}")
+            logits, split = e.get("logits"), e.get("split")
+            if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+                raise ValueError("XentEvalBatch: logits must be a 2-D fp32 device matrix")
+            if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
+                raise ValueError("XentEvalBatch: split must be a contiguous [n, R] uint8 device matrix")
+            n, r = split.shape
+            c = int(e.get("C", 0))
+            cs = int(e.get("cs", c))
+            if not 1 <= c <= self.MAX_C:
+                raise ValueError(f"XentEvalBatch: {c} classes; the kernel holds 1..{self.MAX_C}")
+            if cs < c:
+                raise ValueError(f"XentEvalBatch: a replica stride of {cs} columns is narrower than its {c} classes")
+            if logits.shape[0] != n:
+                raise ValueError("XentEvalBatch: one row of split per row of logits")
+            for name in ("logits", "dlogits"):
+                t = e.get(name)
+                if t is None and name == "dlogits":
+                    self.has_grad = False
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != n:
+                    raise ValueError(f"XentEvalBatch: {name} must be an [n, >= R cs] fp32 device matrix")
+                if t.shape[1] > 1 and t.stride(1) != 1:
+                    raise ValueError(f"XentEvalBatch: the rows of {name} must be contiguous (unit inner stride)")
+                if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
+                    raise ValueError(f"XentEvalBatch: {r} replicas of {cs} columns do not fit a row of {name} ({t.shape[1]} columns, leading dimension {_ld(t)})")
+            lab, inv = e.get("labels"), e.get("inv_n_train")
+            if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
+                raise ValueError("XentEvalBatch: labels must be a contiguous [n] int32 device vector")
+            if not isinstance(inv, torch.Tensor) or inv.dtype != torch.float32 or not inv.is_cuda or not inv.is_contiguous() or tuple(inv.shape) != (r,):
+                raise ValueError("XentEvalBatch: inv_n_train must be a contiguous [R] fp32 device vector")
+            shapes.append((n, r, c, cs))
+        dev = require_gpu()  # (after the checks that need no device)
+        reps = np.fromiter((s_[1] for s_ in shapes), np.int64, n_jobs)
+        off = np.concatenate([[0], np.cumsum(reps)]).astype(np.int64)
+        total = max(int(off[-1]), 1)
+        self.hits = torch.zeros((total, 2), dtype=torch.int32, device=dev)
+        self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
+        self.best[:, 0] = -1
+        self.hits_of = [self.hits[off[i]:off[i + 1]] for i in range(n_jobs)]
+        self.best_of = [self.best[off[i]:off[i + 1]] for i in range(n_jobs)]
+        tab = np.zeros(n_jobs, _XENT_JOB_DTYPE)
+        for i, e in enumerate(entries):
+            for k in ("logits", "dlogits", "labels", "split", "inv_n_train"):
+                tab[k][i] = 0 if e.get(k) is None else e[k].data_ptr()
+            tab["ld_logits"][i] = _ld(e["logits"])
+            tab["ld_dlogits"][i] = 0 if e.get("dlogits") is None else _ld(e["dlogits"])
+        tab["hits"] = self.hits.data_ptr() + 8 * off[:-1]
+        tab["best"] = self.best.data_ptr() + 12 * off[:-1]
+        for k, name in enumerate(("n", "R", "C", "cs")):
+            tab[name] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
+        self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
+        self.table = _h2d(tab.view(np.uint8), dev) if n_jobs else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self, flags, step=None):
+        """flags: XENT_GRAD, XENT_EVAL or both.  step (needed with XENT_EVAL): a one-element int32 DEVICE tensor - the kernel reads it
+        when it runs, so a captured launch beside a captured `step.add_(1)` records the right step on every replay"""
+        flags = int(flags)
+        if not 1 <= flags <= 3:
+            raise ValueError(f"XentEvalBatch.launch: flags {flags}; XENT_GRAD, XENT_EVAL or both")
+        if flags & XENT_GRAD and not self.has_grad and self.n_jobs:
+            raise ValueError("XentEvalBatch.launch: the table was built without dlogits")
+        if flags & XENT_EVAL and (not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda):
+            raise ValueError("XentEvalBatch.launch: a one-element int32 device tensor expected as the step word")
+        check(lib.wdg_xent_eval_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, flags,
+                                            _ptr(step if flags & XENT_EVAL else None), stream_handle()), "wdg_xent_eval_batched_f32")
+
+    def reset(self):
+        """the running best back to "none yet" (the counters are zero between calls)"""
+        self.hits.zero_()
+        self.best.zero_()
+        self.best[:, 0] = -1
