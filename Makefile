@@ -15,6 +15,8 @@ FLAGS_kernel_reg_large := -mllvm -pragma-unroll-threshold=200000
 FLAGS_kernel_reg_large_windows := $(FLAGS_kernel_reg_large)
 # gnb.hip reproduces numpy's fp32 sums bit for bit: no multiply-add may be fused (its source says so as well: #pragma clang fp contract(off))
 FLAGS_gnb := -ffp-contract=off
+# adam.hip's step is restated in numpy bit for bit: every multiply and add is its own rounded operation (the source says so as well)
+FLAGS_adam := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB      := $(PKG)/lib/libwdg_hip.so
 

@@ -1184,6 +1184,54 @@ int wdg_xent_eval_batched_f32(const wdg_xent_job *jobs_dev, int32_t n_jobs, int3
                               int32_t flags /* WDG_XENT_GRAD = 1, WDG_XENT_EVAL = 2, or both */,
                               const int32_t *step_dev, wdg_stream_t stream);
 
+/*
+ * The Adam step of every parameter tensor of a stacked run (split_train.SplitTrainBatch: the replicas of one model are column blocks
+ * of w0 [F, R hidden] and w [F, R cs] and row blocks of w1 [R hidden, cs]) in ONE launch, with the learning rate and the weight decay
+ * of every replica read from device memory - a torch parameter group has one of each per tensor - and the step count read from the
+ * run's step word.  A job is one parameter TENSOR, not one replica: a run is one, two or three jobs however many replicas it holds,
+ * and every access is as wide as the tensor.
+ * replaces: the optimiser step (torch.optim.Adam, the L2 term in the gradient) of the training loops behind the accuracy tables
+ *           gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249 (the loop itself lives upstream of the reference, which has no model
+ *           code).  In SplitTrainBatch(optimizer="device") it stands in for torch's fused Adam over the stacked parameters.
+ * Segments: element (r, c) of a job belongs to segment s = (r / seg_rows) * ceil(cols / seg_cols) + c / seg_cols (integer divisions;
+ * the last segment of a row or of the tensor may be ragged), and hyper[2 s], hyper[2 s + 1] are its lr and weight_decay.
+ *   w0 / w: seg_rows = rows, seg_cols = hidden or cs (a replica = a column block);  w1: seg_rows = hidden, seg_cols = cols (a row block).
+ * The definition, for t = *step_dev + 1 (the word wdg_xent_eval_batched_f32 records and wdg_relu_dropout_batched_f32 draws its masks
+ * from: read from DEVICE memory when the kernel runs, so a captured epoch that increments the word steps correctly on every replay);
+ * every operation below is ONE correctly rounded fp32 operation unless it says double, in this order, nothing fused
+ * (csrc/adam.hip is compiled with contraction off; tests/_adam_ref.py restates the bits in numpy):
+ *   ipow(b, t) = b^t by square and multiply in double (csrc/ipow.h: r = 1; while t: if t & 1: r *= b; b *= b; t >>= 1)
+ *   step_size = (float) ((double) lr / (1.0 - ipow((double) beta1, t)))        bc2_sqrt = (float) sqrt(1.0 - ipow((double) beta2, t))
+ *   g1 = g + weight_decay * p
+ *   m  = beta1 * m + (1 - beta1) * g1                    (1 - beta1, 1 - beta2: fp32 subtractions)
+ *   v  = beta2 * v + ((1 - beta2) * g1) * g1
+ *   p  = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps))
+ * - wdg_head_train_batched_f32's step with the multiply-adds written out.  An element depends on its own four inputs, its segment's
+ * two numbers and t: a job's result does not depend on the table it is in, there are no atomics, and two launches from the same
+ * inputs give the same bits.  A NaN gradient makes that element's p, m and v NaN and no other element's.  g = 0 with p = 0 leaves
+ * p, m and v at +0.0f for eps > 0 (the padding columns of a stacked run stay zero).  lr = 0 leaves p unchanged (while the quotient is
+ * finite) and still advances m and v.
+ * p, m and v of a job must not overlap each other or g, and no two jobs may share an element (the front end checks the first).
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, a NULL step_dev, a beta outside
+ * [0, 1), an eps that is not a number, more than 65535 jobs (a job per grid z), more than 64 * 65535 columns (a tile per grid y).
+ * The table lives in device memory, so what is wrong inside a job - seg_rows < 1 or seg_cols < 1 on a non-empty job, ld or ld_s
+ * below cols, a NULL pointer - is refused by wdg_adam_check_jobs on the HOST copy of the table (ops.AdamBatch calls it before it
+ * uploads; no HIP call either); a launch leaves such a job untouched.  n_jobs == 0: WDG_OK, nothing is launched.  A job of 0 rows or
+ * 0 columns is skipped; rows beyond max_rows (the table's largest) are left untouched, and so is a job of more than max_cols columns.
+ */
+typedef struct wdg_adam_job {
+    float *p;            /* [rows, cols], leading dimension ld: a parameter, updated IN PLACE */
+    const float *g;      /* [rows, cols], leading dimension ld: its gradient */
+    float *m, *v;        /* [rows, cols], leading dimension ld_s: first / second moment, in/out */
+    const float *hyper;  /* device, [segments, 2]: lr, weight_decay of a segment */
+    int64_t ld, ld_s;
+    int32_t rows, cols, seg_rows, seg_cols;
+} wdg_adam_job;
+int wdg_adam_batched_f32(const wdg_adam_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
+                         float beta1, float beta2, float eps, const int32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the optimiser step above (gnns_on_syn.py:109-154), on the host's table */
+int wdg_adam_check_jobs(const wdg_adam_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

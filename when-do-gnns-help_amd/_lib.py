@@ -165,6 +165,8 @@ SIGNATURES = {
     "wdg_acm_mix_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_acm_mix_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_xent_eval_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "wdg_adam_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
+    "wdg_adam_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -300,6 +302,12 @@ class XentJob(ctypes.Structure):
     """mirror of `wdg_xent_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("logits", "dlogits", "labels", "split", "inv_n_train", "hits", "best")] + \
                [("ld_logits", c_int64), ("ld_dlogits", c_int64), ("n", c_int32), ("R", c_int32), ("C", c_int32), ("cs", c_int32)]
+
+
+class AdamJob(ctypes.Structure):
+    """mirror of `wdg_adam_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("p", "g", "m", "v", "hyper")] + \
+               [("ld", c_int64), ("ld_s", c_int64), ("rows", c_int32), ("cols", c_int32), ("seg_rows", c_int32), ("seg_cols", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

@@ -16,6 +16,7 @@
 // One pass over M per epoch: pass p walks train | val | test once with W_p - the gradient of epoch p over the train rows, the hits of
 // epoch p - 1 over the others - pass 0 stops after the train rows and pass `epochs` starts at the first step that holds another row.
 // Steps are aligned to the start of the row list in every pass, so a call of a + b epochs and calls of a, then b epochs do the same sums.
+#include "ipow.h"  // b^t in fp64 by squaring: a function of t alone (a call that starts at step0 gets the bits of one that ran through it)
 #include "wdg_common.h"
 
 namespace {
@@ -28,14 +29,6 @@ constexpr int HT_MAX_F = 4096, HT_MAX_C = 8;
 __host__ __device__ constexpr int ht_cfg(int F) { return F <= 256 ? 0 : F <= 512 ? 1 : F <= 1024 ? 2 : F <= 2048 ? 3 : 4; }
 __host__ __device__ constexpr int ht_cfg_max_f(int cfg) { return 256 << cfg; }
 __host__ __device__ constexpr int ht_cp(int C) { return C <= 2 ? 2 : C <= 4 ? 4 : 8; }
-
-// b^t in fp64 by squaring: a function of t alone (a call that starts at step0 gets the bits of one that ran through it)
-__device__ __forceinline__ double ht_ipow(double b, int t) {
-    double r = 1.0;
-    for (; t > 0; t >>= 1, b *= b)
-        if (t & 1) r *= b;
-    return r;
-}
 
 // v[0 .. P) of every lane -> the sum over the 64 lanes of value (lane >> (6 - log2 P)), in every lane of that group
 template <int K, int P>
@@ -206,8 +199,8 @@ __global__ __launch_bounds__(T) void head_train_kernel(const wdg_head_train_job 
         }
         if (do_train) {  // torch.optim.Adam, step step0 + p + 1: the L2 term goes into the gradient
             const int step = step0 + p + 1;
-            const float step_size = static_cast<float>(static_cast<double>(lr) / (1.0 - ht_ipow(static_cast<double>(beta1), step)));
-            const float bc2_sqrt = static_cast<float>(sqrt(1.0 - ht_ipow(static_cast<double>(beta2), step)));
+            const float step_size = static_cast<float>(static_cast<double>(lr) / (1.0 - ipow_f64(static_cast<double>(beta1), step)));
+            const float bc2_sqrt = static_cast<float>(sqrt(1.0 - ipow_f64(static_cast<double>(beta2), step)));
 #pragma unroll
             for (int k = 0; k < FPT; ++k) {
                 const int f = t + k * T;

@@ -13,7 +13,13 @@ stacked parameters (element-wise: stacking changes nothing).
 
 Stacked layout (cs = C rounded up to a multiple of 4; replica r owns hidden columns r hidden .. and class columns r cs .. r cs + C - 1):
     kinds "gcn" / "mlp2":  w0 [F, R hidden], w1 [R, hidden, cs]        kinds "sgc" / "mlp1":  w [F, R cs]
-The padding columns of the weights start at zero and stay zero: their gradient is zero, and weight decay of zero is zero."""
+The padding columns of the weights start at zero and stay zero: their gradient is zero, and weight decay of zero is zero.
+
+A hyperparameter GRID over the splits is the same stacked run with more replicas: optimizer="device" steps with ops.AdamBatch
+(csrc/adam.hip: lr and weight_decay of every replica in device memory), the dropout stage runs one DropoutBatch per distinct drop
+probability, and replica_ids names the split a replica belongs to, so that every setting starts split s from the same weights and
+draws the same masks (common random numbers).  grid_search() cuts a grid into chunks of whole settings and select_settings() picks
+a setting per split on the validation hits."""
 import time
 
 import numpy as np
@@ -23,7 +29,7 @@ from ._lib import require_gpu
 from ._rt import _dev
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
-from .train import XENT_EVAL, XENT_GRAD, DropoutBatch, XentEvalBatch
+from .train import XENT_EVAL, XENT_GRAD, AdamBatch, DropoutBatch, XentEvalBatch, dropout_constants
 
 MAX_CLASSES = XentEvalBatch.MAX_C
 
@@ -83,19 +89,36 @@ class SplitTrainBatch:
     adj: whatever models.NormAdj takes, or a NormAdj (then `symmetric` is the NormAdj's own); None for the MLP kinds.
     x [n, F] fp32 (host or device), labels [n] integers, masks bool [R, 3, n] (train, validation, test; sizes may differ between
     replicas, classes may be unbalanced).  Raises ValueError for a replica without a train or a validation row, overlapping sets, a
-    split row whose label lies outside 0 .. C - 1, more than 16 classes, dropout with a kind that has no hidden layer."""
+    split row whose label lies outside 0 .. C - 1, more than 16 classes, dropout with a kind that has no hidden layer.
+
+    optimizer="torch" (the default): one fused torch Adam over the stacked parameters - one lr, one weight_decay, one dropout.
+    optimizer="device": the step is ops.AdamBatch's (csrc/adam.hip) on self.step, and lr, weight_decay and dropout may each be a
+    sequence of R values, one per replica (self.lrs, self.weight_decays, self.dropouts: [R]); a sequence with optimizer="torch" is
+    refused - a torch parameter group has one rate per tensor.  With a dropout sequence the replicas are grouped by drop probability,
+    ascending, one DropoutBatch per group (self.drops); self.dropout is then the largest of them.
+    replica_ids: R non-negative integers that stand for r in replica_seed(seed, r) and as the dropout stream (default: range(R)).
+    Replicas with one id start from the same weights and, with one drop probability, draw the same masks."""
 
     KINDS = ("sgc", "gcn", "mlp1", "mlp2")
+    OPTIMIZERS = ("torch", "device")
 
     def __init__(self, adj, x, labels, masks, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
-                 dropout_seed=None):
+                 dropout_seed=None, *, optimizer="torch", replica_ids=None):
         if kind not in self.KINDS:
             raise ValueError(f"SplitTrainBatch: unknown model kind {kind!r} (one of {self.KINDS}; the ACM kinds are sweep.TrainBatch's)")
-        self.kind, self.dropout = kind, float(dropout)
+        if optimizer not in self.OPTIMIZERS:
+            raise ValueError(f"SplitTrainBatch: unknown optimizer {optimizer!r} (one of {self.OPTIMIZERS})")
+        self.kind, self.optimizer = kind, optimizer
         self.two_layer = kind in ("gcn", "mlp2")
-        if not 0.0 <= self.dropout < 1.0:
+        per_replica = {name: np.ndim(val) > 0 for name, val in (("lr", lr), ("weight_decay", weight_decay), ("dropout", dropout))}
+        if optimizer != "device" and any(per_replica.values()):
+            raise ValueError("SplitTrainBatch: %s given per replica: a sequence requires optimizer=\"device\" (torch's Adam has one rate "
+                             "per tensor, and a replica is a column block of one)" % ", ".join(k for k, v in per_replica.items() if v))
+        drops = np.asarray(dropout, np.float64).reshape(-1)
+        self.dropout = float(drops.max(initial=0.0)) if per_replica["dropout"] else float(dropout)
+        if not bool(((drops >= 0.0) & (drops < 1.0)).all()):  # (a NaN fails both comparisons)
             raise ValueError(f"SplitTrainBatch: a drop probability in [0, 1) expected, got {dropout!r}")
-        if self.dropout > 0 and not self.two_layer:
+        if (self.dropout > 0 or per_replica["dropout"]) and not self.two_layer:
             raise ValueError(f"SplitTrainBatch: kind {kind!r} has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2')")
         labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
         n = labels_np.shape[0]
@@ -103,6 +126,16 @@ class SplitTrainBatch:
         if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[2] != n or masks.shape[0] < 1:
             raise ValueError(f"SplitTrainBatch: masks must be a bool array [R, 3, n = {n}], got {masks.dtype} {tuple(masks.shape)}")
         R = masks.shape[0]
+        spread = lambda val, name: self._per_replica(val, R, name)  # noqa: E731
+        self.lrs, self.weight_decays, self.dropouts = spread(lr, "lr"), spread(weight_decay, "weight_decay"), spread(dropout, "dropout")
+        if replica_ids is None:
+            ids = np.arange(R, dtype=np.int64)
+        else:
+            ids = np.asarray(replica_ids)
+            if ids.shape != (R,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids >= 1 << 32).any():
+                raise ValueError(f"SplitTrainBatch: replica_ids must be {R} non-negative integers (of 32 bits: they are dropout streams)")
+            ids = ids.astype(np.int64)
+        self.replica_ids = ids
         c = int(labels_np.max()) + 1 if n else 0
         if not 1 <= c <= MAX_CLASSES:
             raise ValueError(f"SplitTrainBatch: {c} classes; the loss kernel holds 1..{MAX_CLASSES}")
@@ -142,7 +175,7 @@ class SplitTrainBatch:
         if self.two_layer:
             w0, w1 = z(f, R * h), z(R, h, cs)
             for r in range(R):
-                gen = torch.Generator(device="cpu").manual_seed(replica_seed(seed, r))
+                gen = torch.Generator(device="cpu").manual_seed(replica_seed(seed, ids[r]))
                 blk(w0, r, h).copy_(xavier(f, h, gen))
                 w1[r, :, :c].copy_(xavier(h, c, gen))
             self.w0, self.w1 = torch.nn.Parameter(w0), torch.nn.Parameter(w1)
@@ -157,21 +190,28 @@ class SplitTrainBatch:
             self.head = GemmBatch([(blk(self.hid, r, h), self.w1.data[r], blk(head_out, r, cs), None) for r in range(R)])
             self.d_w1 = GemmBatch([(self.hid_t[r * h:(r + 1) * h], blk(head_grad, r, cs), self.w1.grad[r], None) for r in range(R)])  # H_r^T dZ_r
             self.d_hid = GemmBatch([(blk(head_grad, r, cs), self.w1t[r], blk(self.dhid, r, h), None) for r in range(R)])               # dZ_r W1_r^T
-            units = [(blk(self.hid, r, h), self.hid_t[r * h:(r + 1) * h], r) for r in range(R)]
+            units = [(blk(self.hid, r, h), self.hid_t[r * h:(r + 1) * h], int(ids[r])) for r in range(R)]
             if self.dropout > 0:
-                self.drop = DropoutBatch(units, self.dropout, self.dropout_seed)
+                # one launch per distinct drop probability, ascending (a scalar dropout: one group, as ever)
+                self.drops = [DropoutBatch([units[r] for r in np.nonzero(self.dropouts == p)[0]], float(p), self.dropout_seed)
+                              for p in np.unique(self.dropouts)]
                 self.relu = DropoutBatch([(u, None, r) for u, _, r in units], 0.0, self.dropout_seed)  # the clean pass: no transposed copy is read
             else:
-                self.drop = self.relu = DropoutBatch(units, 0.0, self.dropout_seed)  # p = 0: a plain ReLU plus the transposed copy
+                self.relu = DropoutBatch(units, 0.0, self.dropout_seed)  # p = 0: a plain ReLU plus the transposed copy
+                self.drops = [self.relu]
+            self.drop = self.drops[0] if len(self.drops) == 1 else None
+            # the backward rule's scale per hidden column, for a run whose replicas do not share one
+            self.hid_scale = None if self.drop is not None else torch.from_numpy(np.repeat(
+                np.array([dropout_constants(p)[1] for p in self.dropouts], np.float32), h)).to(dev)
         else:
             w = z(f, R * cs)
             for r in range(R):
-                gen = torch.Generator(device="cpu").manual_seed(replica_seed(seed, r))
+                gen = torch.Generator(device="cpu").manual_seed(replica_seed(seed, ids[r]))
                 w[:, r * cs:r * cs + c].copy_(xavier(f, c, gen))
             self.w = torch.nn.Parameter(w)
             self.w.grad = torch.zeros_like(w)
             self.params = [self.w]
-            self.drop = None
+            self.drop, self.drops = None, []
             if kind == "sgc":
                 a = self.adj
                 self.y = spmm(a.graph, x, row_scale=a.row_scale, col_scale=a.col_scale)  # Y = A_hat X, once
@@ -184,8 +224,35 @@ class SplitTrainBatch:
         # torch's fused Adam: its kernel forms the bias corrections 1 - beta^t in double precision.  The unfused capturable path forms
         # them in fp32 tensors - 1 - 0.999^t cancels to a relative error of 1e-5 - and twelve epochs end 9e-7 from a float64 run where
         # this form ends 1e-7 from it (measured: tests/test_gpu_split_train.py).  Both keep the step count on the device: capturable.
-        self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True, fused=True)
+        if optimizer == "torch":
+            self.opt, self.adam = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True, fused=True), None
+        else:
+            # ops.AdamBatch: one job per parameter tensor, a replica = a segment (a column block of w0 / w, a row block of w1)
+            hyper = np.stack([self.lrs, self.weight_decays], 1).astype(np.float32)
+            if self.two_layer:
+                entries = [(self.w0.data, self.w0.grad, f, h, hyper), (self.w1.data.view(R * h, cs), self.w1.grad.view(R * h, cs), h, cs, hyper)]
+            else:
+                entries = [(self.w.data, self.w.grad, f, cs, hyper)]
+            self.opt, self.adam = None, AdamBatch(entries)
         self.graph = None
+
+    @staticmethod
+    def _per_replica(val, R, name):
+        """a number or a sequence of R numbers -> float64 [R]"""
+        a = np.asarray(val, np.float64)
+        if a.ndim == 0:
+            return np.full(R, float(a))
+        if a.shape != (R,):
+            raise ValueError(f"SplitTrainBatch: {name} must be a number or one value per replica ({R}), got shape {tuple(a.shape)}")
+        return a.copy()
+
+    def set_hyper(self, lr, weight_decay):
+        """optimizer="device": new learning rates and weight decays (a number, or one per replica) for the NEXT steps, written into
+        the device table the captured step reads - no new capture"""
+        if self.adam is None:
+            raise ValueError("SplitTrainBatch.set_hyper: the run steps with torch's Adam (optimizer=\"torch\")")
+        self.lrs, self.weight_decays = self._per_replica(lr, self.R, "lr"), self._per_replica(weight_decay, self.R, "weight_decay")
+        self.adam.set_hyper(self.lrs, self.weight_decays)
 
     # -- the stacked products ----------------------------------------------------------------------------------
     def _aggregate(self, src, out):
@@ -203,16 +270,18 @@ class SplitTrainBatch:
             if not self.two_layer:
                 gemm(self.y, self.w.data, out=self.logits)
                 return
-            unit = self.drop if (train or self.dropout == 0) else self.relu
+            units = self.drops if (train or self.dropout == 0) else [self.relu]
             if self.kind == "gcn":
                 gemm(self.x, self.w0.data, out=self.p)     # P = X [W0_1 | ... | W0_R]
                 self._aggregate(self.p, self.hid)           # A_hat P
-                unit.launch(self.step)                      # relu (+ dropout), hid^T
+                for unit in units:
+                    unit.launch(self.step)                  # relu (+ dropout), hid^T
                 self.head.launch()                          # Z_r = H_r W1_r
                 self._aggregate(self.z, self.logits)        # logits = A_hat Z
             else:
                 gemm(self.x, self.w0.data, out=self.hid)
-                unit.launch(self.step)
+                for unit in units:
+                    unit.launch(self.step)
                 self.head.launch()
 
     def _backward(self):
@@ -227,7 +296,8 @@ class SplitTrainBatch:
             self.w1t.copy_(self.w1.data.transpose(1, 2))
             self.d_hid.launch()
             # a unit passes its gradient on (scaled) exactly where its output is positive: it was positive and kept
-            self.dhid.copy_(torch.where(self.hid > 0, self.dhid * self.drop.scale, 0.0))
+            scale = self.drop.scale if self.drop is not None else self.hid_scale  # (one number, or a [R hidden] row of per-replica scales)
+            self.dhid.copy_(torch.where(self.hid > 0, self.dhid * scale, 0.0))
             if self.kind == "gcn":
                 self._aggregate_t(self.dhid, self.dp)         # dP = A_hat^T dH
                 gemm(self.xt, self.dp, out=self.w0.grad)      # dW0 = X^T dP
@@ -246,7 +316,10 @@ class SplitTrainBatch:
     def train_step(self):
         # (dropout == 0: the forward pass of these weights has been run already: by the previous epoch's evaluation, or by run())
         self.gradients()
-        self.opt.step()
+        if self.adam is None:
+            self.opt.step()
+        else:
+            self.adam.launch(self.step)  # t = step word + 1, read on the device
 
     def eval_step(self):
         self.forward(train=False)
@@ -262,7 +335,8 @@ class SplitTrainBatch:
         """Capture one epoch as a hipGraph (after a warm-up whose effects are rewound); returns the replay callable."""
         saved = [p.detach().clone() for p in self.params]
         saved_step, saved_best = self.step.clone(), self.xent.best.clone()
-        saved_state = [{k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for st in self.opt.state.values()]
+        saved_state = [{k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for st in self.opt.state.values()] if self.adam is None else []
+        saved_moments = None if self.adam is None else self.adam.moments.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -276,7 +350,9 @@ class SplitTrainBatch:
             with torch.no_grad():
                 for p, s in zip(self.params, saved):
                     p.copy_(s)
-                for i, st in enumerate(self.opt.state.values()):
+                if self.adam is not None:
+                    self.adam.moments.copy_(saved_moments)
+                for i, st in enumerate(self.opt.state.values() if self.adam is None else ()):
                     for k, v in st.items():
                         if torch.is_tensor(v):
                             if i < len(saved_state) and k in saved_state[i]:
@@ -323,15 +399,17 @@ class SplitTrainBatch:
 
     def replica_model(self, r):
         """a models.SGC1 / GCN2 / MLP1 / MLP2 on the device holding replica r's CURRENT weights (copies); with dropout > 0 its hidden
-        layer draws from models.DeviceDropout(dropout_seed, stream=r), whose step word starts at 0"""
+        layer draws from models.DeviceDropout(dropout_seed, stream=replica_ids[r]) with replica r's own drop probability; its step
+        word starts at 0"""
         from . import models
         if not 0 <= r < self.R:
             raise ValueError(f"SplitTrainBatch.replica_model: replica {r} of {self.R}")
         with torch.random.fork_rng(devices=[]):  # (the constructors draw an initialisation that is overwritten below)
             if self.two_layer:
-                rng = models.DeviceDropout(self.dropout_seed, stream=r) if self.dropout > 0 else None
+                p = float(self.dropouts[r])
+                rng = models.DeviceDropout(self.dropout_seed, stream=int(self.replica_ids[r])) if p > 0 else None
                 cls = models.GCN2 if self.kind == "gcn" else models.MLP2
-                model = cls(self.f, self.c, nhid=self.h, dropout=self.dropout, dropout_rng=rng)
+                model = cls(self.f, self.c, nhid=self.h, dropout=p, dropout_rng=rng)
             else:
                 model = (models.SGC1 if self.kind == "sgc" else models.MLP1)(self.f, self.c)
         model = model.to(self.x.device)
@@ -339,3 +417,115 @@ class SplitTrainBatch:
             for p, w in zip(model.parameters(), self.weights_of(r)):
                 p.copy_(w)
         return model
+
+
+# -- a hyperparameter grid over the splits ------------------------------------------------------------------------------------
+# buffers of hidden width [n, R hidden] a stacked run holds (the class-width ones, [n, R cs], for the one-layer kinds)
+_WIDE_BUFFERS = {"gcn": 5, "mlp2": 3, "sgc": 2, "mlp1": 2}  # gcn: p, hid, hid_t, dhid, dp; mlp2: hid, hid_t, dhid; else logits, dlogits
+ACTIVATION_BUDGET_BYTES = 1 << 30
+
+
+def default_max_replicas(n, width, kind, n_splits, budget_bytes=ACTIVATION_BUDGET_BYTES):
+    """the most replicas of one chunk: the largest number of WHOLE settings (n_splits replicas each) whose activation footprint
+    n * R * width * 4 bytes * (the kind's buffers of that width) stays within budget_bytes - never less than one setting"""
+    per_replica = max(int(n) * int(width) * 4 * _WIDE_BUFFERS[kind], 1)
+    return max(int(budget_bytes // per_replica) // int(n_splits), 1) * int(n_splits)
+
+
+def chunk_settings(n_settings, n_splits, max_replicas):
+    """-> [(g0, g1), ...]: consecutive ranges of settings, in order, each of at most max_replicas // n_splits settings (whole settings
+    only: every chunk trains all splits of its settings).  max_replicas < n_splits - not even one setting fits - is refused."""
+    n_settings, n_splits, max_replicas = int(n_settings), int(n_splits), int(max_replicas)
+    if n_settings < 1 or n_splits < 1:
+        raise ValueError(f"grid_search: {n_settings} settings over {n_splits} splits; at least one of each expected")
+    if max_replicas < n_splits:
+        raise ValueError(f"grid_search: max_replicas = {max_replicas} holds less than one setting ({n_splits} splits)")
+    per = max_replicas // n_splits
+    return [(g0, min(g0 + per, n_settings)) for g0 in range(0, n_settings, per)]
+
+
+def select_settings(best, n_val, n_test):
+    """Model selection over a grid, in numpy alone.  best: int [G, S, 3] - per (setting, split) the validation hits of the best epoch
+    (-1: the replica never had a best epoch), the test hits at it, its epoch; n_val, n_test: [S] row counts.
+    For every split the setting with the most validation hits is picked, the LOWEST setting index among equals; a replica without a
+    best epoch never wins against one that has one (a split where no setting has one picks setting 0 with test accuracy 0).
+    -> dict(setting [S], val_acc [S], test_acc [S], best_epoch [S] at the picked setting; test_mean, test_std: mean and SAMPLE
+    deviation (ddof = 1; 0 for a single split) of test_acc over the splits; mean_val_acc [G]: the settings' mean validation accuracy
+    over the splits (a replica without a best epoch counts 0), best_mean_setting: its argmax (lowest index among equals), and
+    best_mean_test_mean / best_mean_test_std: that one setting's test accuracy over the splits)."""
+    best = np.asarray(best)
+    if best.ndim != 3 or best.shape[2] != 3 or best.shape[0] < 1 or best.shape[1] < 1 or best.dtype.kind not in "iu":
+        raise ValueError(f"select_settings: an integer [G, S, 3] table expected, got {best.dtype} {tuple(best.shape)}")
+    G, S = best.shape[:2]
+    n_val, n_test = np.asarray(n_val, np.int64).reshape(-1), np.asarray(n_test, np.int64).reshape(-1)
+    if n_val.shape != (S,) or n_test.shape != (S,) or (n_val < 1).any() or (n_test < 0).any():
+        raise ValueError(f"select_settings: one validation and one test row count per split ({S}) expected")
+    hits = best[:, :, 0].astype(np.int64)
+    pick = hits.argmax(0)  # (numpy's argmax: the first maximum = the lowest setting index; -1 loses to every count >= 0)
+    cols = np.arange(S)
+    none = hits[pick, cols] < 0
+    test_all = np.where(hits < 0, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :])
+    val_all = np.where(hits < 0, 0.0, hits / n_val[None, :])
+    test_acc = test_all[pick, cols]
+    dev = lambda a: float(a.std(ddof=1)) if a.size > 1 else 0.0  # noqa: E731
+    mean_val = val_all.mean(1)
+    g_best = int(mean_val.argmax())
+    return dict(setting=pick.astype(np.int64), val_acc=np.where(none, -1.0, val_all[pick, cols]), test_acc=test_acc,
+                best_epoch=best[pick, cols, 2].astype(np.int64), test_mean=float(test_acc.mean()), test_std=dev(test_acc),
+                mean_val_acc=mean_val, best_mean_setting=g_best, best_mean_test_mean=float(test_all[g_best].mean()),
+                best_mean_test_std=dev(test_all[g_best]))
+
+
+def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, seed=0, max_replicas=None, symmetric=0, capture=True):
+    """A hyperparameter grid over all splits of one graph, as stacked runs.  grid: a list of G dicts with the keys lr, weight_decay and
+    dropout; masks: bool [S, 3, n].  Replica (g, s) - setting g on split s - sits at position g S + s (setting-major) with
+    replica_ids = s: every setting starts split s from the same weights and draws the same dropout masks (common random numbers).
+    The G S replicas are cut into chunks of WHOLE settings with at most max_replicas replicas each, trained one after the other as one
+    SplitTrainBatch(optimizer="device") per chunk; one models.NormAdj, one device copy of x and one label vector serve all chunks.
+    max_replicas (default: default_max_replicas) bounds the ACTIVATION memory of a chunk - n * R * hidden * 4 bytes for each of the
+    kind's hidden-width buffers (five for "gcn": p, hid, hid^T, dhid, dp; the class-width logits / dlogits for the one-layer kinds) -
+    to ACTIVATION_BUDGET_BYTES = 1 GiB; the weights and the Adam moments (F R hidden floats, three times) are not counted.  It must
+    hold at least one setting: max_replicas < S is refused.
+    -> dict(val_acc, test_acc [G, S] float64 (-1 / 0 for a replica without a best epoch), best_epoch [G, S], best [G, S, 3] int
+    (validation hits, test hits, epoch), n_val, n_test [S], chunks [(g0, g1), ...], seconds, selection = select_settings(best, n_val,
+    n_test): the per-split pick, its test accuracy's mean and sample deviation, and the setting of the best mean validation accuracy)."""
+    grid = list(grid)
+    for g in grid:
+        if not isinstance(g, dict) or set(g) != {"lr", "weight_decay", "dropout"}:
+            raise ValueError("grid_search: every setting is a dict with exactly the keys lr, weight_decay and dropout")
+    if kind not in SplitTrainBatch.KINDS:
+        raise ValueError(f"grid_search: unknown model kind {kind!r} (one of {SplitTrainBatch.KINDS})")
+    masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+    if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[0] < 1:
+        raise ValueError(f"grid_search: masks must be a bool array [S, 3, n], got {masks.dtype} {tuple(masks.shape)}")
+    S, n = masks.shape[0], masks.shape[2]
+    two_layer = kind in ("gcn", "mlp2")
+    if not two_layer and any(float(g["dropout"]) != 0.0 for g in grid):
+        raise ValueError(f"grid_search: kind {kind!r} has no hidden layer to drop units of: every setting's dropout must be 0")
+    labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+    cs = -(-(int(labels_np.max()) + 1 if labels_np.size else 1) // 4) * 4
+    if max_replicas is None:
+        max_replicas = default_max_replicas(n, int(hidden) if two_layer else cs, kind, S)
+    chunks = chunk_settings(len(grid), S, max_replicas)
+    dev = require_gpu()  # (after the checks that need no device)
+    from . import models
+    if kind in ("sgc", "gcn") and not isinstance(adj, models.NormAdj):
+        adj = models.NormAdj(adj, symmetric=symmetric)
+    x = _dev(x, torch.float32, dev)
+    labels_dev = torch.as_tensor(labels_np.astype(np.int64))
+    best = np.zeros((len(grid), S, 3), np.int64)
+    seconds = 0.0
+    for g0, g1 in chunks:
+        part = grid[g0:g1]
+        spread = lambda key: np.repeat(np.array([float(g[key]) for g in part]), S)  # noqa: E731  (setting-major)
+        kw = dict(dropout=spread("dropout")) if two_layer else {}
+        stb = SplitTrainBatch(adj, x, labels_dev, np.tile(masks, (g1 - g0, 1, 1)), kind=kind, hidden=hidden, lr=spread("lr"),
+                              weight_decay=spread("weight_decay"), seed=seed, optimizer="device", replica_ids=np.tile(np.arange(S), g1 - g0), **kw)
+        seconds += stb.run(epochs=epochs, capture=capture)["seconds"]
+        best[g0:g1] = stb.best.cpu().numpy().reshape(g1 - g0, S, 3)
+        del stb
+    n_val, n_test = masks[:, 1].sum(1).astype(np.int64), masks[:, 2].sum(1).astype(np.int64)
+    none = best[:, :, 0] < 0
+    return dict(val_acc=np.where(none, -1.0, best[:, :, 0] / n_val[None, :]), test_acc=np.where(none, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :]),
+                best_epoch=best[:, :, 2].copy(), best=best, n_val=n_val, n_test=n_test, chunks=chunks, seconds=seconds,
+                selection=select_settings(best, n_val, n_test))

@@ -2,7 +2,8 @@
 models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip, and the hidden layer's
 ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip, and the channel mix of many ACM layers
 (ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip,
-and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip."""
+and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip,
+and the Adam step of the stacked parameters with every replica's own learning rate and weight decay, csrc/adam.hip."""
 import ctypes
 import math
 
@@ -26,6 +27,9 @@ assert _ACM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.AcmMixJob)
 _XENT_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
                             for name, ctype in _lib.XentJob._fields_])
 assert _XENT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.XentJob)
+_ADAM_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
+                            for name, ctype in _lib.AdamJob._fields_])
+assert _ADAM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.AdamJob)
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
 
 
@@ -368,3 +372,107 @@ class XentEvalBatch:
         self.hits.zero_()
         self.best.zero_()
         self.best[:, 0] = -1
+
+
+class AdamBatch:
+    """Job table for wdg_adam_batched_f32 (csrc/adam.hip): the Adam step (the L2 term in the gradient, torch.optim.Adam's rule) of every
+    parameter tensor of a stacked run in one launch, with the learning rate and the weight decay of every SEGMENT of a tensor - a
+    replica's column or row block - in device memory (include/wdg.h states the arithmetic and the segment rule; tests/_adam_ref.py
+    restates both in numpy, bit for bit).  The table owns the moments (self.m[i], self.v[i]: zeros, contiguous; self.moments holds
+    all of them, so a run is rewound by copying or zeroing one tensor) and the hyperparameter table (self.hyper_of[i]: [segments, 2])."""
+
+    MAX_JOBS = 65535
+
+    def __init__(self, entries, betas=(0.9, 0.999), eps=1e-8):
+        """entries: list of (param, grad, seg_rows, seg_cols, hyper) - param and grad [rows, cols] fp32 device views with unit inner
+        stride and ONE leading dimension (a parameter's .data and its .grad; w1 [R, hidden, cs] is passed as its [R hidden, cs] view),
+        param updated IN PLACE; element (r, c) belongs to segment (r // seg_rows) * ceil(cols / seg_cols) + c // seg_cols; hyper:
+        [segments, 2] (lr, weight_decay) as a host array or a tensor - it is COPIED into the table's own device memory (set_hyper
+        rewrites it).  Raises ValueError for other dtypes, shapes or strides, param and grad that overlap, seg_rows or seg_cols
+        below 1, a hyper of another shape, betas outside [0, 1), an eps that is not a number, more than 65535 entries."""
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if not all(0.0 <= b < 1.0 for b in self.betas) or self.eps != self.eps:
+            raise ValueError(f"AdamBatch: betas in [0, 1) and an eps that is a number expected, got {betas!r}, {eps!r}")
+        self.keep = entries
+        n = self.n_jobs = len(entries)
+        if n > self.MAX_JOBS:
+            raise ValueError(f"AdamBatch: {n} entries; one launch takes {self.MAX_JOBS}")
+        hypers, self.segments = [], []
+        for e in entries:
+            if len(e) != 5:
+                raise ValueError("AdamBatch: an entry is (param, grad, seg_rows, seg_cols, hyper)")
+            p, g, seg_rows, seg_cols, hyper = e
+            for name, t in (("param", p), ("grad", g)):
+                if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda:
+                    raise ValueError(f"AdamBatch: {name} must be a 2-D fp32 device matrix")
+                if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+                    raise ValueError(f"AdamBatch: the rows of {name} must be contiguous and must not overlap")
+            if p.shape != g.shape or (p.shape[0] > 1 and _ld(p) != _ld(g)):
+                raise ValueError("AdamBatch: param and grad must have one shape and one leading dimension")
+            if _views_may_overlap(p, g):
+                raise ValueError("AdamBatch: param and grad overlap")
+            rows, cols = p.shape
+            seg_rows, seg_cols = int(seg_rows), int(seg_cols)
+            if rows and cols and (seg_rows < 1 or seg_cols < 1):
+                raise ValueError(f"AdamBatch: segments of {seg_rows} x {seg_cols}; at least 1 x 1 expected")
+            segs = (-(-rows // seg_rows)) * (-(-cols // seg_cols)) if rows and cols else 0
+            h = np.asarray(hyper.detach().cpu() if isinstance(hyper, torch.Tensor) else hyper, dtype=np.float32)
+            if h.shape != (segs, 2):
+                raise ValueError(f"AdamBatch: hyper must be [segments = {segs}, 2] (lr, weight_decay), got {tuple(h.shape)}")
+            hypers.append(h)
+            self.segments.append(segs)
+        dev = require_gpu()  # (after the checks that need no device)
+        # the moments: every tensor's block starts at a multiple of four floats (16-byte accesses where its width allows)
+        sizes = np.fromiter((-(-e[0].numel() // 4) * 4 for e in entries), np.int64, n)
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = max(int(offs[-1]), 4)
+        self.moments = torch.zeros((2, total), dtype=torch.float32, device=dev)
+        self.m = [self.moments[0, offs[i]:offs[i] + entries[i][0].numel()].view(entries[i][0].shape) for i in range(n)]
+        self.v = [self.moments[1, offs[i]:offs[i] + entries[i][0].numel()].view(entries[i][0].shape) for i in range(n)]
+        hoff = np.concatenate([[0], np.cumsum(self.segments)]).astype(np.int64)
+        self.hyper = torch.zeros((max(int(hoff[-1]), 1), 2), dtype=torch.float32, device=dev)
+        if hoff[-1]:
+            self.hyper[:int(hoff[-1])].copy_(torch.from_numpy(np.concatenate(hypers, 0)))
+        self.hyper_of = [self.hyper[hoff[i]:hoff[i + 1]] for i in range(n)]
+        col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
+        tab = np.zeros(n, _ADAM_JOB_DTYPE)
+        tab["p"], tab["g"], tab["ld"] = col(lambda e: e[0].data_ptr()), col(lambda e: e[1].data_ptr()), col(lambda e: max(_ld(e[0]), e[0].shape[1]))
+        tab["m"] = self.moments.data_ptr() + 4 * offs[:-1]
+        tab["v"] = self.moments.data_ptr() + 4 * (offs[:-1] + total)
+        tab["hyper"] = self.hyper.data_ptr() + 8 * hoff[:-1]
+        tab["ld_s"] = col(lambda e: e[0].shape[1])
+        tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
+        tab["seg_rows"], tab["seg_cols"] = col(lambda e: int(e[2])), col(lambda e: int(e[3]))
+        self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
+        host = np.ascontiguousarray(tab)
+        check(lib.wdg_adam_check_jobs(ctypes.c_void_p(host.ctypes.data), n), "wdg_adam_check_jobs")
+        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self, step):
+        """one Adam step, t = step + 1.  step: a one-element int32 DEVICE tensor, read by the kernel when it runs (the word DropoutBatch
+        and XentEvalBatch read): a captured launch beside a captured `step.add_(1)` takes the right step on every replay"""
+        if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
+            raise ValueError("AdamBatch.launch: a one-element int32 device tensor expected as the step word")
+        check(lib.wdg_adam_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.betas[0], self.betas[1], self.eps,
+                                       _ptr(step), stream_handle()), "wdg_adam_batched_f32")
+
+    def set_hyper(self, lr, weight_decay, entry=None):
+        """rewrite the device table IN PLACE (the captured launch reads it on its next replay: a rate changes between replays without a
+        new capture).  lr, weight_decay: a number (every segment) or a sequence with one value per segment of the entries it is written
+        to; entry: None = every entry, or an index"""
+        for i in (range(self.n_jobs) if entry is None else [int(entry)]):
+            segs = self.segments[i]
+            cols = []
+            for name, val in (("lr", lr), ("weight_decay", weight_decay)):
+                a = np.asarray(val, dtype=np.float32)
+                if a.ndim == 0:
+                    a = np.full(segs, a, np.float32)
+                if a.shape != (segs,):
+                    raise ValueError(f"AdamBatch.set_hyper: {name} must be a number or one value per segment ({segs}) of entry {i}, got shape {tuple(a.shape)}")
+                cols.append(a)
+            if segs:
+                self.hyper_of[i].copy_(torch.from_numpy(np.stack(cols, 1)))
+
+    def reset(self):
+        """the moments back to zero (the parameters and the step word are the caller's)"""
+        self.moments.zero_()
