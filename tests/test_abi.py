@@ -91,6 +91,28 @@ def test_struct_layout_matches_header(tmp_path):
             assert got[(cname, fname)] == getattr(mirror, fname).offset, (cname, fname)
 
 
+DERIVED_RECORDS = [("train", "_HEAD_JOB_DTYPE", "HeadTrainJob"), ("train", "_DROPOUT_JOB_DTYPE", "DropoutJob"), ("train", "_ACM_JOB_DTYPE", "AcmMixJob"),
+                   ("train", "_XENT_JOB_DTYPE", "XentJob"), ("train", "_ADAM_JOB_DTYPE", "AdamJob"),
+                   ("kernel_regression", "_KR_SAMPLE_DTYPE", "KrSampleJob"), ("kernel_regression", "_KR_JOB_DTYPE", "KrJob"),
+                   ("kernel_regression", "_KR_COMBINE_JOB_DTYPE", "KrCombineJob"), ("kernel_regression", "_GNB_JOB_DTYPE", "GnbJob"),
+                   ("kernel_regression", "_SVM_JOB_DTYPE", "SvmJob")]
+
+
+@pytest.mark.parametrize("module,record,struct", DERIVED_RECORDS)
+def test_a_job_tables_record_type_is_its_structs_layout(module, record, struct):
+    """the numpy record type a front-end module fills its job table through has the size of the ctypes mirror of include/wdg.h, and
+    every field of the mirror under its own name, at its own offset and of its own width (the mirrors themselves are checked
+    against the header: test_struct_layout_matches_header and the layout tests of the newer structs)"""
+    import importlib
+    import wdg_amd._lib as L
+    dtype, st = getattr(importlib.import_module("wdg_amd." + module), record), getattr(L, struct)
+    assert dtype.itemsize == ctypes.sizeof(st)
+    assert list(dtype.names) == [name for name, _ in st._fields_]
+    for name, ctype in st._fields_:
+        assert dtype.fields[name][1] == getattr(st, name).offset, name
+        assert dtype.fields[name][0].itemsize == ctypes.sizeof(ctype), name
+
+
 def test_no_shipped_kernel_spills_vector_registers():
     """the compiler's resource report of every translation unit (build/*.rsrc, written by the Makefile): no kernel of the
     library may spill VGPRs to scratch (a spill inside the aggregation loops also breaks their hand-counted vmcnt waits)"""

@@ -81,7 +81,7 @@ def test_dropout_job_layout_matches_header(tmp_path):
     assert got["size"] == ctypes.sizeof(L.DropoutJob) == train._DROPOUT_JOB_DTYPE.itemsize
     for fname, _ in L.DropoutJob._fields_:
         assert got[fname] == getattr(L.DropoutJob, fname).offset == train._DROPOUT_JOB_DTYPE.fields[fname][1], fname
-    assert [f for f, _ in L.DropoutJob._fields_] == list(train._DROPOUT_JOB_DTYPE.names)[:-1]  # (the record names the tail padding)
+    assert [f for f, _ in L.DropoutJob._fields_] == list(train._DROPOUT_JOB_DTYPE.names)  # (the tail padding is in the itemsize, unnamed)
 
 
 def test_argument_refusals_need_no_gpu():

@@ -239,3 +239,36 @@ def _table(arr):
 # flags of wdg_spmm_batched_f32 / wdg_spmm_quad_batched_f32 and of the GEMM tables (include/wdg.h)
 SPMM_ANY_VAL, SPMM_DMA_OK, SPMM_SMALL_OFFSETS, SPMM_ANY_COL_SCALE, SPMM_HALF_SLAB = 2, 4, 8, 16, 32
 GEMM_A_VEC4 = 1
+
+
+def snapshot(tensors):
+    """copies of `tensors` now -> the callable that copies them back in place"""
+    tensors = list(tensors)
+    saved = [t.detach().clone() for t in tensors]
+
+    def restore():
+        with torch.no_grad():
+            for t, s in zip(tensors, saved):
+                t.copy_(s)
+    return restore
+
+
+def capture_graphs(steps, warm_up, rewind):
+    """Each callable of `steps` captured as a hipGraph of its own -> the list of torch.cuda.CUDAGraph.  warm_up() runs first, on a side
+    stream that waits for and is waited for by the current one (lazy state - Adam moments, SELL copies, kernel attributes - must
+    exist before anything is captured); rewind() then puts the state back IN PLACE (the graphs address these very tensors), and
+    once more after the captures (capturing does not execute: explicit all the same)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        warm_up()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    rewind()
+    graphs = []
+    for step in steps:
+        graphs.append(torch.cuda.CUDAGraph())
+        with torch.cuda.graph(graphs[-1]):
+            step()
+    rewind()
+    return graphs

@@ -1,6 +1,5 @@
 """The kernel-regression metric on the device (reference: utils/homophily_metrics.py:190-349): batched Grams with the fused
 arc-cosine map, the generalized edge homophily gathered from a Gram, the device sampler of the node sets and the batched solver."""
-import ctypes
 import os
 
 import numpy as np
@@ -243,10 +242,7 @@ def kr_split_sizes(labels, sample_max):
     return s_c.astype(np.int32), t_c.astype(np.int32)
 
 
-_KR_SAMPLE_DTYPE = np.dtype([("labels", "<u8"), ("sample_per_class", "<u8"), ("train_per_class", "<u8"), ("train_out", "<u8"), ("val_out", "<u8"),
-                             ("seed", "<u8"), ("n", "<i4"), ("n_classes", "<i4"), ("n_sets", "<i4"), ("first_set", "<i4"), ("train_stride", "<i4"),
-                             ("val_stride", "<i4")])
-assert _KR_SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.KrSampleJob)
+_KR_SAMPLE_DTYPE = np.dtype(_lib.KrSampleJob)  # the record type of the ctypes mirror: its names, offsets and size
 
 
 class KrSets:
@@ -311,13 +307,8 @@ class KrSets:
               "wdg_kr_sample_sets")
 
 
-_KR_JOB_DTYPE = np.dtype([("K", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labels", "<u8"), ("correct_out", "<u8"), ("flags_out", "<u8"),
-                          ("ldk", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("n_classes", "<i4"), ("class_base", "<i4"), ("rep", "<u8"), ("ws", "<u8"),
-                          ("rows_out", "<u8")])
-assert _KR_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.KrJob)
-_KR_COMBINE_JOB_DTYPE = np.dtype([("rows", "<u8"), ("win_correct", "<u8"), ("win_flags", "<u8"), ("val", "<u8"), ("labels", "<u8"),
-                                  ("correct_out", "<u8"), ("flags_out", "<u8"), ("row_stride", "<i8"), ("n_val", "<i4"), ("n_windows", "<i4")])
-assert _KR_COMBINE_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.KrCombineJob)
+_KR_JOB_DTYPE = np.dtype(_lib.KrJob)
+_KR_COMBINE_JOB_DTYPE = np.dtype(_lib.KrCombineJob)
 KR_WINDOW = 8  # class columns of a window job (KR_MAX_C of csrc/kr_deflate.h)
 
 
@@ -524,9 +515,7 @@ def _host_hit_rate(correct, n_val):
 
 
 # ------------------------------------------------------------------------------------------- Gaussian naive Bayes (the GNB classifier)
-_GNB_JOB_DTYPE = np.dtype([("X", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labels", "<u8"), ("ws", "<u8"), ("correct", "<u8"),
-                           ("pred", "<u8"), ("ldx", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("F", "<i4"), ("n_classes", "<i4")])
-assert _GNB_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.GnbJob)
+_GNB_JOB_DTYPE = np.dtype(_lib.GnbJob)
 
 
 class GnbBatch:
@@ -582,11 +571,7 @@ class GnbBatch:
 
 
 # ------------------------------------------------------------------------------------------- support vector classifiers (svm_*)
-_SVM_JOB_DTYPE = np.dtype([("G_half", "<u8"), ("norm2", "<u8"), ("row_sum", "<u8"), ("train", "<u8"), ("val", "<u8"), ("labels", "<u8"),
-                           ("ws", "<u8"), ("correct", "<u8"), ("pred", "<u8"), ("dec", "<u8"), ("info", "<u8"), ("ldk", "<i8"),
-                           ("C", "<f8"), ("gamma", "<f8"), ("kernel", "<i4"), ("degree", "<i4"), ("max_iter", "<i4"), ("n_train", "<i4"),
-                           ("n_val", "<i4"), ("n_classes", "<i4"), ("F", "<i4"), ("reserved", "<i4")])
-assert _SVM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.SvmJob)
+_SVM_JOB_DTYPE = np.dtype(_lib.SvmJob)
 
 
 class SvmBatch:

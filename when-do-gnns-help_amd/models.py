@@ -21,6 +21,7 @@ gnns_on_syn.py:58-104 and gnns_on_syn.py:159-206 but ships none) and is not clai
 import torch
 
 from . import ops
+from ._rt import capture_graphs, snapshot
 from .ops import CsrGraph
 from .utils.util_funcs import accuracy, random_disassortative_splits
 
@@ -431,34 +432,23 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
         p.grad = torch.zeros_like(p)
     g_train = g_eval = None
     if capture:
-        saved = [p.detach().clone() for p in model.parameters()]
-        saved_steps = [(r, r.step.clone()) for r in _dropout_rngs(model)]  # (DeviceDropout: the warm-up's masks are drawn again)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up off the capture stream: lazy state (Adam moments, SELL copies, kernel attributes)
+        # (DeviceDropout: the warm-up's masks are drawn again)
+        restore = snapshot(list(model.parameters()) + [r.step for r in _dropout_rngs(model)])
+
+        def warm_up():
             for _ in range(2):
                 train_step()
                 eval_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        with torch.no_grad():  # rewind to the initial state, in place (the graphs will address these very tensors)
-            for p, s in zip(model.parameters(), saved):
-                p.copy_(s)
+
+        def rewind():
+            restore()
             for st in opt.state.values():
                 for v in st.values():
                     if torch.is_tensor(v):
                         v.zero_()
             best_val.fill_(-1.0); best_test.zero_(); best_epoch.zero_(); epoch.zero_()
-            for r, s0 in saved_steps:
-                r.step.copy_(s0)
-        g_train, g_eval = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_train):
-            train_step()
-        with torch.cuda.graph(g_eval):
-            eval_step()
-        with torch.no_grad():  # capturing does not execute: state is still the initial one, but make that explicit
-            for p, s in zip(model.parameters(), saved):
-                p.copy_(s)
+
+        g_train, g_eval = capture_graphs([train_step, eval_step], warm_up, rewind)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(epochs):

@@ -4,7 +4,8 @@ PyTorch is plumbing here (device memory, the current HIP stream); every computat
 gfx950 kernel in csrc/.  Nothing here runs on the CPU, and nothing falls back.
 
 This module is the one namespace callers use (`from wdg_amd import ops`); the code lives in
-  _rt.py                flag values of include/wdg.h, pointer helpers, the page-locked upload arena
+  _rt.py                flag values of include/wdg.h, pointer helpers, the page-locked upload arena, the hipGraph capture harness
+                        (capture_graphs, snapshot: TrainBatch, SplitTrainBatch and models.train_eval_graphed call it)
   graphs.py             CsrGraph (+ its one-time plans), GraphBatch (a shard's graphs in one build, or GENERATED on the device:
                         GraphBatch.generated), normalisations
   synth.py              regular_graph_device, sample_feature_rows (the device generators; the numpy generators live there too)
@@ -19,6 +20,7 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
   split_train.py        SplitTrainBatch (all splits of ONE graph trained as a single stacked run; reached as ops.SplitTrainBatch;
                         optimizer="device": per-replica lr / weight_decay / dropout), grid_search (a hyperparameter grid over all
                         splits as stacked chunks), select_settings
+  train_batch.py        TrainBatch (one model per graph of a shard, trained for all graphs at once; reached as sweep.TrainBatch)
   sparse_features.py    SparseFeatures (compact feature matrices on the host), expand_features / FeatureExpand (one launch for a list of them)
   kernel_regression.py  GramBatch, PropagatedGram, RowRepBatch, EdgeGramBatch, KrSets, KrBatch, GnbBatch, SvmBatch
 (module-level switches - aggregate.ABLATE_BITS, aggregate.NARROW_MIN_ENTRIES - are set on the module that owns them)."""

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ._lib import require_gpu
-from ._rt import _dev
+from ._rt import _dev, capture_graphs, snapshot
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
 from .train import XENT_EVAL, XENT_GRAD, AdamBatch, DropoutBatch, XentEvalBatch, dropout_constants
@@ -333,40 +333,23 @@ class SplitTrainBatch:
 
     def capture(self):
         """Capture one epoch as a hipGraph (after a warm-up whose effects are rewound); returns the replay callable."""
-        saved = [p.detach().clone() for p in self.params]
-        saved_step, saved_best = self.step.clone(), self.xent.best.clone()
-        saved_state = [{k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for st in self.opt.state.values()] if self.adam is None else []
-        saved_moments = None if self.adam is None else self.adam.moments.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        # torch's Adam: the state it has is restored, the state the warm-up creates starts from zero
+        state = [] if self.adam is not None else [v for st in self.opt.state.values() for v in st.values() if torch.is_tensor(v)]
+        restore = snapshot(self.params + [self.step, self.xent.best] + ([self.adam.moments] if self.adam is not None else state))
+
+        def warm_up():
             self.forward()
             for _ in range(2):
                 self.epoch()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
 
         def rewind():
-            with torch.no_grad():
-                for p, s in zip(self.params, saved):
-                    p.copy_(s)
-                if self.adam is not None:
-                    self.adam.moments.copy_(saved_moments)
-                for i, st in enumerate(self.opt.state.values() if self.adam is None else ()):
-                    for k, v in st.items():
-                        if torch.is_tensor(v):
-                            if i < len(saved_state) and k in saved_state[i]:
-                                v.copy_(saved_state[i][k])
-                            else:
-                                v.zero_()
-                self.step.copy_(saved_step)
-                self.xent.best.copy_(saved_best)
+            for st in (self.opt.state.values() if self.adam is None else ()):
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+            restore()
 
-        rewind()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.epoch()
-        rewind()  # (capturing does not execute: explicit all the same)
+        self.graph, = capture_graphs([self.epoch], warm_up, rewind)
         return self.graph.replay
 
     def run(self, epochs=200, capture=True):

@@ -14,23 +14,29 @@ from . import _lib
 from ._lib import check, lib, require_gpu, stream_handle
 from ._rt import _h2d, _ld, _ptr
 
-_HEAD_JOB_DTYPE = np.dtype([("M", "<u8"), ("labels", "<u8"), ("train", "<u8"), ("val", "<u8"), ("test", "<u8"), ("W", "<u8"), ("m", "<u8"),
-                            ("v", "<u8"), ("best", "<u8"), ("ldm", "<i8"), ("n_train", "<i4"), ("n_val", "<i4"), ("n_test", "<i4"),
-                            ("F", "<i4"), ("C", "<i4"), ("reserved", "<i4")])
-assert _HEAD_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.HeadTrainJob)
-_DROPOUT_JOB_DTYPE = np.dtype([("h", "<u8"), ("ht", "<u8"), ("ld", "<i8"), ("ld_t", "<i8"), ("rows", "<i4"), ("cols", "<i4"),
-                               ("stream", "<u4"), ("tail_padding", "<u4")])
-assert _DROPOUT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.DropoutJob)
-_ACM_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
-                           for name, ctype in _lib.AcmMixJob._fields_])
-assert _ACM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.AcmMixJob)
-_XENT_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
-                            for name, ctype in _lib.XentJob._fields_])
-assert _XENT_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.XentJob)
-_ADAM_JOB_DTYPE = np.dtype([(name, "<u8" if ctype is ctypes.c_void_p else "<i8" if ctype is ctypes.c_int64 else "<i4")
-                            for name, ctype in _lib.AdamJob._fields_])
-assert _ADAM_JOB_DTYPE.itemsize == ctypes.sizeof(_lib.AdamJob)
+# the record types of the job tables: those of the ctypes mirrors of include/wdg.h (names, offsets and size; tests/test_abi*.py check
+# the mirrors against the header)
+_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE = (
+    np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob))
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
+
+
+def _check_matrix(table, name, t, shape=None):
+    """ValueError (naming the table and the operand) unless t is a 2-D fp32 device matrix - of `shape`, where one is given (None = any
+    size in that dimension) - whose rows are contiguous and do not overlap; any leading dimension"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (
+            shape is not None and any(want is not None and want != got for want, got in zip(shape, t.shape))):
+        what = "2-D" if shape is None else "[" + ", ".join("any" if d is None else str(d) for d in shape) + "]"
+        raise ValueError(f"{table}: {name} must be a {what} fp32 device matrix")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{table}: the rows of {name} must be contiguous (unit inner stride) and must not overlap")
+
+
+def _step_word(where, step):
+    """-> the pointer of a launch's step word: a one-element int32 DEVICE tensor, read by the kernel when it runs"""
+    if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
+        raise ValueError(f"{where}: a one-element int32 device tensor expected as the step word")
+    return _ptr(step)
 
 
 class HeadTrainBatch:
@@ -130,17 +136,9 @@ class DropoutBatch:
         self.keep = entries
         n = self.n_jobs = len(entries)
         for h, ht, stream in entries:
-            if h.dim() != 2 or h.dtype != torch.float32 or not h.is_cuda:
-                raise ValueError("DropoutBatch: h must be a 2-D fp32 device matrix")
-            if h.shape[1] > 1 and h.stride(1) != 1:
-                raise ValueError("DropoutBatch: the rows of h must be contiguous (unit inner stride)")
-            if h.shape[0] > 1 and h.stride(0) < h.shape[1]:
-                raise ValueError("DropoutBatch: the rows of h overlap")
+            _check_matrix("DropoutBatch", "h", h)
             if ht is not None:
-                if ht.dim() != 2 or tuple(ht.shape) != (h.shape[1], h.shape[0]):
-                    raise ValueError(f"DropoutBatch: ht must be [cols, rows] = {(h.shape[1], h.shape[0])}, got {tuple(ht.shape)}")
-                if ht.dtype != torch.float32 or not ht.is_cuda or (ht.shape[1] > 1 and ht.stride(1) != 1) or (ht.shape[0] > 1 and ht.stride(0) < ht.shape[1]):
-                    raise ValueError("DropoutBatch: ht must be an fp32 device matrix with contiguous rows")
+                _check_matrix("DropoutBatch", "ht", ht, (h.shape[1], h.shape[0]))
             if not 0 <= int(stream) < 1 << 32:
                 raise ValueError(f"DropoutBatch: a stream of 32 bits expected, got {stream!r}")
         col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
@@ -156,10 +154,8 @@ class DropoutBatch:
     def launch(self, step):
         """step: a one-element int32 DEVICE tensor whose bits are the uint32 step - the kernel reads it when it runs, so a captured
         launch followed by a captured `step.add_(1)` draws a fresh mask on every replay"""
-        if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
-            raise ValueError("DropoutBatch.launch: a one-element int32 device tensor expected")
         check(lib.wdg_relu_dropout_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.threshold, self.scale,
-                                               self.seed, _ptr(step), stream_handle()), "wdg_relu_dropout_batched_f32")
+                                               self.seed, _step_word("DropoutBatch.launch", step), stream_handle()), "wdg_relu_dropout_batched_f32")
 
 
 def _views_may_overlap(a, b):
@@ -220,22 +216,15 @@ class AcmMixBatch:
                 raise ValueError("AcmMixBatch: d_out, d_low, d_high, d_ident, d_att and d_wmix come together or not at all")
             self.has_backward = self.has_backward and bool(given)
             for k in mats:
-                t = e.get(k)
-                if t is None:
-                    continue
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (rows, cols):
-                    raise ValueError(f"AcmMixBatch: {k} must be a [{rows}, {cols}] fp32 device matrix")
-                if (cols > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < cols):
-                    raise ValueError(f"AcmMixBatch: the rows of {k} must be contiguous and must not overlap")
+                if e.get(k) is not None:
+                    _check_matrix("AcmMixBatch", k, e[k], (rows, cols))
             for k, shape in (("att", (3, cols)), ("wmix", (3, 3)), ("d_att", (3, cols)), ("d_wmix", (3, 3))):
                 t = e.get(k)
                 if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
                                       or tuple(t.shape) != shape or not t.is_contiguous()):
                     raise ValueError(f"AcmMixBatch: {k} must be a contiguous {list(shape)} fp32 device tensor")
-            t = e.get("out_t")
-            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (cols, rows)
-                                  or (rows > 1 and t.stride(1) != 1) or (cols > 1 and t.stride(0) < rows)):
-                raise ValueError(f"AcmMixBatch: out_t must be a [{cols}, {rows}] fp32 device matrix with contiguous rows")
+            if e.get("out_t") is not None:
+                _check_matrix("AcmMixBatch", "out_t", e["out_t"], (cols, rows))
             outputs = ("out", "out_t", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
             given = [(k, t) for k, t in e.items() if t is not None]
             for i, (ka, ta) in enumerate(given):
@@ -301,9 +290,7 @@ class XentEvalBatch:
             unknown = set(e) - {"logits", "dlogits", "labels", "split", "inv_n_train", "C", "cs"}
             if unknown:
                 raise ValueError(f"XentEvalBatch: unknown keys {sorted(unknown)}")
-            logits, split = e.get("logits"), e.get("split")
-            if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_cuda:
-                raise ValueError("XentEvalBatch: logits must be a 2-D fp32 device matrix")
+            split = e.get("split")
             if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
                 raise ValueError("XentEvalBatch: split must be a contiguous [n, R] uint8 device matrix")
             n, r = split.shape
@@ -313,17 +300,12 @@ class XentEvalBatch:
                 raise ValueError(f"XentEvalBatch: {c} classes; the kernel holds 1..{self.MAX_C}")
             if cs < c:
                 raise ValueError(f"XentEvalBatch: a replica stride of {cs} columns is narrower than its {c} classes")
-            if logits.shape[0] != n:
-                raise ValueError("XentEvalBatch: one row of split per row of logits")
             for name in ("logits", "dlogits"):
                 t = e.get(name)
                 if t is None and name == "dlogits":
                     self.has_grad = False
                     continue
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.shape[0] != n:
-                    raise ValueError(f"XentEvalBatch: {name} must be an [n, >= R cs] fp32 device matrix")
-                if t.shape[1] > 1 and t.stride(1) != 1:
-                    raise ValueError(f"XentEvalBatch: the rows of {name} must be contiguous (unit inner stride)")
+                _check_matrix("XentEvalBatch", name, t, (n, None))  # (one row of split per row)
                 if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
                     raise ValueError(f"XentEvalBatch: {r} replicas of {cs} columns do not fit a row of {name} ({t.shape[1]} columns, leading dimension {_ld(t)})")
             lab, inv = e.get("labels"), e.get("inv_n_train")
@@ -362,10 +344,9 @@ class XentEvalBatch:
             raise ValueError(f"XentEvalBatch.launch: flags {flags}; XENT_GRAD, XENT_EVAL or both")
         if flags & XENT_GRAD and not self.has_grad and self.n_jobs:
             raise ValueError("XentEvalBatch.launch: the table was built without dlogits")
-        if flags & XENT_EVAL and (not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda):
-            raise ValueError("XentEvalBatch.launch: a one-element int32 device tensor expected as the step word")
-        check(lib.wdg_xent_eval_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, flags,
-                                            _ptr(step if flags & XENT_EVAL else None), stream_handle()), "wdg_xent_eval_batched_f32")
+        word = _step_word("XentEvalBatch.launch", step) if flags & XENT_EVAL else _ptr(None)
+        check(lib.wdg_xent_eval_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, flags, word, stream_handle()),
+              "wdg_xent_eval_batched_f32")
 
     def reset(self):
         """the running best back to "none yet" (the counters are zero between calls)"""
@@ -402,11 +383,8 @@ class AdamBatch:
             if len(e) != 5:
                 raise ValueError("AdamBatch: an entry is (param, grad, seg_rows, seg_cols, hyper)")
             p, g, seg_rows, seg_cols, hyper = e
-            for name, t in (("param", p), ("grad", g)):
-                if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda:
-                    raise ValueError(f"AdamBatch: {name} must be a 2-D fp32 device matrix")
-                if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-                    raise ValueError(f"AdamBatch: the rows of {name} must be contiguous and must not overlap")
+            _check_matrix("AdamBatch", "param", p)
+            _check_matrix("AdamBatch", "grad", g)
             if p.shape != g.shape or (p.shape[0] > 1 and _ld(p) != _ld(g)):
                 raise ValueError("AdamBatch: param and grad must have one shape and one leading dimension")
             if _views_may_overlap(p, g):
@@ -451,10 +429,8 @@ class AdamBatch:
     def launch(self, step):
         """one Adam step, t = step + 1.  step: a one-element int32 DEVICE tensor, read by the kernel when it runs (the word DropoutBatch
         and XentEvalBatch read): a captured launch beside a captured `step.add_(1)` takes the right step on every replay"""
-        if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
-            raise ValueError("AdamBatch.launch: a one-element int32 device tensor expected as the step word")
         check(lib.wdg_adam_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.betas[0], self.betas[1], self.eps,
-                                       _ptr(step), stream_handle()), "wdg_adam_batched_f32")
+                                       _step_word("AdamBatch.launch", step), stream_handle()), "wdg_adam_batched_f32")
 
     def set_hyper(self, lr, weight_decay, entry=None):
         """rewrite the device table IN PLACE (the captured launch reads it on its next replay: a rate changes between replays without a
