@@ -17,6 +17,8 @@ FLAGS_kernel_reg_large_windows := $(FLAGS_kernel_reg_large)
 FLAGS_gnb := -ffp-contract=off
 # adam.hip's step is restated in numpy bit for bit: every multiply and add is its own rounded operation (the source says so as well)
 FLAGS_adam := -ffp-contract=off
+# acm_mix_packed.hip computes a replica's bits exactly as acm_mix.hip computes a job's: every multiply-add is written out (the source says so as well)
+FLAGS_acm_mix_packed := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB      := $(PKG)/lib/libwdg_hip.so
 

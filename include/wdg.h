@@ -1137,6 +1137,53 @@ int wdg_acm_mix_backward_batched_f32(const wdg_acm_mix_job *jobs_dev, int32_t n_
                                      wdg_stream_t stream);
 
 /*
+ * The same channel mix for STACKED narrow layers (csrc/acm_mix_packed.hip): a job is one layer of `reps` replicas - the splits of
+ * one graph trained as one run - of `cols` real columns each, `stride` in {4, 8, 16} floats between replicas, 1 <= cols <= stride,
+ * rows >= 0.  Replica p occupies columns p stride .. p stride + cols - 1 of every operand; 1, 2 or 4 adjacent lanes are one replica,
+ * so one pass over the rows serves all replicas (wdg_acm_mix_batched_f32 gives the 16 lanes of a row to ONE job).
+ * replaces: the use of g_high = I - A_hat, utils/util_funcs.py:198-204, in the model family behind the "mf-GCN" / "mf-SGC" tables,
+ *           gnns_on_syn.py:58-104 and gnns_on_syn.py:159-206 (models that live upstream of the reference).
+ * The arithmetic of replica p is the definition above, forward and backward, on its column slices, with att [reps, 3, stride] and
+ * wmix [reps, 9] - and its BITS are those of a one-job wdg_acm_mix_batched_f32 / wdg_acm_mix_backward_batched_f32 launch on those
+ * slices (the same ownership, the same orders of addition; tests/test_gpu_acm_packed.py compares with ==).
+ *   low, high, high_agg (NULL: P_H = high), ident, out, d_out, d_low, d_high, d_ident: [rows, reps stride], each with its own
+ *   leading dimension;  aux [rows, reps, 8];  d_att [reps, 3, stride];  d_wmix [reps, 9];
+ *   partials: ceil(rows / 64) * reps * (3 stride + 12) floats (one vector per 64-row block and replica; no float atomics - a second
+ *   launch inside the entry adds the blocks in block order).  There is no transposed output.  flags bit 0 (WDG_ACM_RELU): the whole job.
+ * Padding columns (cols .. stride - 1 of a replica) count as +0 on input whatever memory holds, and are WRITTEN +0.0f in out, d_low,
+ * d_high, d_ident and d_att (aggregations and the loss kernel downstream read whole rows).
+ * Preconditions: 16-byte aligned low, high, high_agg, ident, out, att, aux, d_out, d_low, d_high, d_ident, d_att, partials; leading
+ * dimensions that are multiples of 4 and at least reps stride.  The gradient arrays (d_out .. d_wmix, partials) come together or
+ * not at all.  Outputs must not overlap inputs or each other.
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs (a job per
+ * grid z), max_width (the table's largest reps stride) above 64 * 65535.  n_jobs == 0: WDG_OK, nothing is launched.  The table lives
+ * in device memory, so what is wrong inside a job - a stride outside {4, 8, 16}, cols outside 1 .. stride, reps < 1, rows < 0, a
+ * misaligned pointer or leading dimension, a leading dimension below reps stride, a NULL required pointer - is refused by
+ * wdg_acm_mix_packed_check_jobs on the HOST copy of the table (no HIP call either); a launch leaves such a job untouched.  A job of
+ * 0 rows writes nothing forward and zero sums backward, and its [rows, .] arrays and partials may be NULL (att, wmix and, backward,
+ * d_att and d_wmix may not); rows beyond max_rows and columns beyond max_width are left untouched.
+ */
+typedef struct wdg_acm_packed_job {
+    const float *low, *high, *high_agg, *ident; /* [rows, reps stride] */
+    const float *att;       /* [reps, 3, stride] */
+    const float *wmix;      /* [reps, 9] */
+    float *out;             /* forward out [rows, reps stride] */
+    float *aux;             /* [rows, reps, 8]: forward out, backward in */
+    const float *d_out;     /* backward in [rows, reps stride] */
+    float *d_low, *d_high, *d_ident; /* backward out [rows, reps stride] */
+    float *d_att;           /* backward out [reps, 3, stride] */
+    float *d_wmix;          /* backward out [reps, 9] */
+    float *partials;        /* backward workspace: ceil(rows / 64) * reps * (3 stride + 12) floats */
+    int64_t ld_low, ld_high, ld_high_agg, ld_ident, ld_out, ld_d_out, ld_d_low, ld_d_high, ld_d_ident;
+    int32_t rows, reps, cols, stride, flags, reserved;
+} wdg_acm_packed_job;
+int wdg_acm_mix_packed_f32(const wdg_acm_packed_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int64_t max_width, wdg_stream_t stream);
+int wdg_acm_mix_packed_backward_f32(const wdg_acm_packed_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int64_t max_width,
+                                    wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the packed channel mix above (utils/util_funcs.py:198-204), on the host's table */
+int wdg_acm_mix_packed_check_jobs(const wdg_acm_packed_job *jobs_host, int32_t n_jobs);
+
+/*
  * The tail of a training epoch for many models whose logits are STACKED along the feature axis - all splits ("replicas") of one
  * graph share A_hat, X and the labels, so their logits are column blocks of one [n, R cs] matrix: the cross-entropy gradient of
  * every replica's train rows, its validation and test hits and its model selection, in one pass.  A job is one graph's stacked

@@ -164,6 +164,9 @@ SIGNATURES = {
     "wdg_synth_regular_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "wdg_acm_mix_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_acm_mix_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_acm_mix_packed_f32": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p]),
+    "wdg_acm_mix_packed_backward_f32": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_void_p]),
+    "wdg_acm_mix_packed_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_xent_eval_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "wdg_adam_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
     "wdg_adam_check_jobs": (c_int, [c_void_p, c_int32]),
@@ -296,6 +299,15 @@ class AcmMixJob(ctypes.Structure):
                [(name, c_int64) for name in ("ld_low", "ld_high", "ld_high_agg", "ld_ident", "ld_out", "ld_out_t", "ld_d_out", "ld_d_low",
                                              "ld_d_high", "ld_d_ident")] + \
                [("rows", c_int32), ("cols", c_int32), ("flags", c_int32), ("reserved", c_int32)]
+
+
+class AcmPackedJob(ctypes.Structure):
+    """mirror of `wdg_acm_packed_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("low", "high", "high_agg", "ident", "att", "wmix", "out", "aux", "d_out", "d_low", "d_high",
+                                              "d_ident", "d_att", "d_wmix", "partials")] + \
+               [(name, c_int64) for name in ("ld_low", "ld_high", "ld_high_agg", "ld_ident", "ld_out", "ld_d_out", "ld_d_low", "ld_d_high",
+                                             "ld_d_ident")] + \
+               [("rows", c_int32), ("reps", c_int32), ("cols", c_int32), ("stride", c_int32), ("flags", c_int32), ("reserved", c_int32)]
 
 
 class XentJob(ctypes.Structure):

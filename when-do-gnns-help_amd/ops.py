@@ -14,12 +14,15 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
   gemm.py               gemm, gemm_skinny, GemmBatch, Mlp2Batch
   train.py              HeadTrainBatch (every epoch of many logistic heads in one launch), DropoutBatch (ReLU + counter-based
                         dropout of many hidden layers in one launch), AcmMixBatch (the channel mix of many ACM layers, forward and backward),
+                        AcmMixPackedBatch (the same mix for stacked class-width layers: 1, 2 or 4 lanes per replica),
                         XentEvalBatch (cross-entropy gradient, hits and model selection of many models with stacked logits),
                         AdamBatch (the Adam step of a stacked run's parameter tensors in one launch: a learning rate and a weight
                         decay per replica in device memory, the step count read from the run's step word)
   split_train.py        SplitTrainBatch (all splits of ONE graph trained as a single stacked run; reached as ops.SplitTrainBatch;
                         optimizer="device": per-replica lr / weight_decay / dropout), grid_search (a hyperparameter grid over all
                         splits as stacked chunks), select_settings
+  acm_split_train.py    AcmSplitTrainBatch (all splits of ONE graph trained as a single stacked run of ACM-SGC-1 / ACM-GCN-2 models, in a
+                        channel-major layout; reached as ops.AcmSplitTrainBatch)
   train_batch.py        TrainBatch (one model per graph of a shard, trained for all graphs at once; reached as sweep.TrainBatch)
   sparse_features.py    SparseFeatures (compact feature matrices on the host), expand_features / FeatureExpand (one launch for a list of them)
   kernel_regression.py  GramBatch, PropagatedGram, RowRepBatch, EdgeGramBatch, KrSets, KrBatch, GnbBatch, SvmBatch
@@ -44,10 +47,11 @@ from .stats import (  # noqa: F401
 from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
-from .train import dropout_constants, AcmMixBatch, AdamBatch, DropoutBatch, HeadTrainBatch, XentEvalBatch, XENT_EVAL, XENT_GRAD  # noqa: F401
+from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, DropoutBatch, HeadTrainBatch, XentEvalBatch, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .synth import regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, expand_features, feature_image_floats, FeatureExpand, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
     deflation_enabled, EdgeGramBatch, GnbBatch, GramBatch, kr_split_sizes, KrBatch, KrSets, PropagatedGram, RowRepBatch, SvmBatch, _KR_JOB_DTYPE,
 )
 from .split_train import grid_search, masks_from_indices, random_masks, select_settings, SplitTrainBatch  # noqa: E402,F401  (last: it builds on the modules above)
+from .acm_split_train import AcmSplitTrainBatch  # noqa: E402,F401

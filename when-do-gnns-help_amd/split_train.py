@@ -72,6 +72,41 @@ def xavier(fan_in, fan_out, gen):
     return (torch.rand((fan_in, fan_out), generator=gen) * 2 - 1) * bound
 
 
+# the checks of a stacked run's labels, masks and replica ids (`who` names the class in the messages: acm_split_train shares them)
+def _labels_and_masks(who, labels, masks):
+    """-> (labels int64 [n], masks bool [R, 3, n]) as numpy arrays"""
+    labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
+    n = labels_np.shape[0]
+    masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+    if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[2] != n or masks.shape[0] < 1:
+        raise ValueError(f"{who}: masks must be a bool array [R, 3, n = {n}], got {masks.dtype} {tuple(masks.shape)}")
+    return labels_np, masks
+
+
+def _replica_ids(who, replica_ids, R):
+    if replica_ids is None:
+        return np.arange(R, dtype=np.int64)
+    ids = np.asarray(replica_ids)
+    if ids.shape != (R,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids >= 1 << 32).any():
+        raise ValueError(f"{who}: replica_ids must be {R} non-negative integers (of 32 bits: they are dropout streams)")
+    return ids.astype(np.int64)
+
+
+def _classes_and_counts(who, labels_np, masks):
+    """-> (C, counts [R, 3] of train, validation and test rows)"""
+    c = int(labels_np.max()) + 1 if labels_np.shape[0] else 0
+    if not 1 <= c <= MAX_CLASSES:
+        raise ValueError(f"{who}: {c} classes; the loss kernel holds 1..{MAX_CLASSES}")
+    if (masks.sum(1) > 1).any():
+        raise ValueError(f"{who}: the train, validation and test rows of a replica overlap")
+    counts = masks.sum(2)  # [R, 3]
+    if (counts[:, 0] < 1).any() or (counts[:, 1] < 1).any():
+        raise ValueError(f"{who}: every replica needs at least one train row and one validation row")
+    if (labels_np[masks.any((0, 1))] < 0).any():
+        raise ValueError(f"{who}: a row of a split carries a label outside 0..{c - 1}")
+    return c, counts
+
+
 class SplitTrainBatch:
     """Train + evaluate R replicas of one model on one graph, one per split, as a single stacked run.
 
@@ -79,6 +114,7 @@ class SplitTrainBatch:
         kind "gcn":  logits_r = A_hat relu(A_hat (X W0_r)) W1_r
         kind "mlp1": logits_r = X W_r                                kind "mlp2": logits_r = relu(X W0_r) W1_r
     bias-free, as in sweep.TrainBatch; the per-replica reference is replica_model(r): a models.SGC1 / GCN2 / MLP1 / MLP2.
+    (The ACM kinds "acm_sgc" / "acm_gcn" are stacked over the splits by acm_split_train.AcmSplitTrainBatch, in a layout of their own.)
 
     An epoch has the meaning of TrainBatch's: gradient of the train loss -> Adam (the L2 term in the gradient) -> a clean forward pass
     -> evaluation and model selection; a step word in device memory advances at its end.  Without dropout the clean forward pass is
@@ -120,32 +156,12 @@ class SplitTrainBatch:
             raise ValueError(f"SplitTrainBatch: a drop probability in [0, 1) expected, got {dropout!r}")
         if (self.dropout > 0 or per_replica["dropout"]) and not self.two_layer:
             raise ValueError(f"SplitTrainBatch: kind {kind!r} has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2')")
-        labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
-        n = labels_np.shape[0]
-        masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
-        if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[2] != n or masks.shape[0] < 1:
-            raise ValueError(f"SplitTrainBatch: masks must be a bool array [R, 3, n = {n}], got {masks.dtype} {tuple(masks.shape)}")
-        R = masks.shape[0]
+        labels_np, masks = _labels_and_masks("SplitTrainBatch", labels, masks)
+        n, R = labels_np.shape[0], masks.shape[0]
         spread = lambda val, name: self._per_replica(val, R, name)  # noqa: E731
         self.lrs, self.weight_decays, self.dropouts = spread(lr, "lr"), spread(weight_decay, "weight_decay"), spread(dropout, "dropout")
-        if replica_ids is None:
-            ids = np.arange(R, dtype=np.int64)
-        else:
-            ids = np.asarray(replica_ids)
-            if ids.shape != (R,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids >= 1 << 32).any():
-                raise ValueError(f"SplitTrainBatch: replica_ids must be {R} non-negative integers (of 32 bits: they are dropout streams)")
-            ids = ids.astype(np.int64)
-        self.replica_ids = ids
-        c = int(labels_np.max()) + 1 if n else 0
-        if not 1 <= c <= MAX_CLASSES:
-            raise ValueError(f"SplitTrainBatch: {c} classes; the loss kernel holds 1..{MAX_CLASSES}")
-        if (masks.sum(1) > 1).any():
-            raise ValueError("SplitTrainBatch: the train, validation and test rows of a replica overlap")
-        counts = masks.sum(2)  # [R, 3]
-        if (counts[:, 0] < 1).any() or (counts[:, 1] < 1).any():
-            raise ValueError("SplitTrainBatch: every replica needs at least one train row and one validation row")
-        if (labels_np[masks.any((0, 1))] < 0).any():
-            raise ValueError(f"SplitTrainBatch: a row of a split carries a label outside 0..{c - 1}")
+        self.replica_ids = ids = _replica_ids("SplitTrainBatch", replica_ids, R)
+        c, counts = _classes_and_counts("SplitTrainBatch", labels_np, masks)
         dev = require_gpu()  # (after the checks that need no device)
         from . import models
         if kind in ("sgc", "gcn"):
@@ -162,12 +178,7 @@ class SplitTrainBatch:
         self.x, self.n, self.R, self.c, self.cs, self.f, self.h = x, n, R, c, cs, f, h
         self.lr, self.weight_decay, self.seed = lr, weight_decay, int(seed)
         self.dropout_seed = self.seed if dropout_seed is None else int(dropout_seed)
-        self.n_train, self.n_val, self.n_test = (counts[:, k].copy() for k in range(3))
-        self.labels = torch.from_numpy(labels_np.astype(np.int32)).to(dev)
-        codes = (masks[:, 0] * 1 + masks[:, 1] * 2 + masks[:, 2] * 3).astype(np.uint8)  # [R, n]
-        self.split = torch.from_numpy(np.ascontiguousarray(codes.T)).to(dev)  # [n, R]
-        self.inv_n_train = torch.from_numpy((1.0 / counts[:, 0].astype(np.float64)).astype(np.float32)).to(dev)
-        self.step = torch.zeros(1, dtype=torch.int32, device=dev)  # epochs done; the dropout masks' step word as well
+        self._stage_splits(labels_np, masks, counts, dev)
 
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
         self.logits, self.dlogits = z(n, R * cs), z(n, R * cs)
@@ -235,6 +246,15 @@ class SplitTrainBatch:
                 entries = [(self.w.data, self.w.grad, f, cs, hyper)]
             self.opt, self.adam = None, AdamBatch(entries)
         self.graph = None
+
+    def _stage_splits(self, labels_np, masks, counts, dev):
+        """what the loss kernel reads of the splits, and the run's step word, on the device"""
+        self.n_train, self.n_val, self.n_test = (counts[:, k].copy() for k in range(3))
+        self.labels = torch.from_numpy(labels_np.astype(np.int32)).to(dev)
+        codes = (masks[:, 0] * 1 + masks[:, 1] * 2 + masks[:, 2] * 3).astype(np.uint8)  # [R, n]
+        self.split = torch.from_numpy(np.ascontiguousarray(codes.T)).to(dev)  # [n, R]
+        self.inv_n_train = torch.from_numpy((1.0 / counts[:, 0].astype(np.float64)).astype(np.float32)).to(dev)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)  # epochs done; the dropout masks' step word as well
 
     @staticmethod
     def _per_replica(val, R, name):

@@ -1,7 +1,8 @@
 """Training on the device: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the
 models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip, and the hidden layer's
 ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip, and the channel mix of many ACM layers
-(ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip,
+(ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip
+(and, for the stacked class-width layers of acm_split_train, several replicas per 16 lanes: csrc/acm_mix_packed.hip),
 and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip,
 and the Adam step of the stacked parameters with every replica's own learning rate and weight decay, csrc/adam.hip."""
 import ctypes
@@ -16,8 +17,8 @@ from ._rt import _h2d, _ld, _ptr
 
 # the record types of the job tables: those of the ctypes mirrors of include/wdg.h (names, offsets and size; tests/test_abi*.py check
 # the mirrors against the header)
-_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE = (
-    np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob))
+_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE, _ACM_PACKED_JOB_DTYPE = (
+    np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob, _lib.AcmPackedJob))
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
 
 
@@ -264,6 +265,112 @@ class AcmMixBatch:
             raise ValueError("AcmMixBatch.launch_backward: the table was built without gradient tensors")
         check(lib.wdg_acm_mix_backward_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()),
               "wdg_acm_mix_backward_batched_f32")
+
+
+class AcmMixPackedBatch:
+    """Job table for wdg_acm_mix_packed_f32 / wdg_acm_mix_packed_backward_f32 (csrc/acm_mix_packed.hip): the channel mix of AcmMixBatch
+    for STACKED narrow layers - an entry is one [rows, reps stride] layer of `reps` replicas of `cols` real columns each, stride 4, 8
+    or 16 floats between replicas; replica p owns columns p stride .. p stride + cols - 1 of every operand.  A replica's results are,
+    bit for bit, those of a one-entry AcmMixBatch on its column slices; the padding columns of out, d_low, d_high, d_ident and d_att
+    are written +0 and those of the inputs are never used.  The table owns aux ([rows, reps, 8] per entry in aux_of) and the
+    partial sums of the parameter gradients."""
+
+    STRIDES, MAX_JOBS, TILE = (4, 8, 16), 65535, 64
+
+    def __init__(self, entries, relu):
+        """entries: list of dicts - cols (int), att [reps, 3, stride] and wmix [reps, 3, 3] or [reps, 9] (fp32 device, contiguous: reps
+           and stride are att's), low, high, ident, out [rows, reps stride] fp32 device (unit inner stride, any leading dimension that
+           is a multiple of 4: column ranges of a wider matrix are fine), high_agg the same or None;
+           and, for launch_backward(): d_out, d_low, d_high, d_ident [rows, reps stride], d_att like att, d_wmix like wmix - all six or none.
+           Every tensor starts at a 16-byte boundary.  relu: the activation flag of every entry (one bool, or one per entry).
+        Raises ValueError for a stride outside {4, 8, 16}, cols outside 1..stride, other dtypes, shapes or strides, misaligned
+        tensors, more than 65535 entries, an output that overlaps an input or another output of its entry."""
+        name = "AcmMixPackedBatch"
+        self.keep = entries
+        n = self.n_jobs = len(entries)
+        if n > self.MAX_JOBS:
+            raise ValueError(f"{name}: {n} entries; one launch takes {self.MAX_JOBS}")
+        flags = [bool(relu)] * n if np.ndim(relu) == 0 else [bool(f) for f in relu]
+        if len(flags) != n:
+            raise ValueError(f"{name}: one activation flag per entry")
+        mats = ("low", "high", "high_agg", "ident", "out", "d_out", "d_low", "d_high", "d_ident")
+        grads = ("d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
+        self.has_backward = n > 0
+        shapes = []
+        for e in entries:
+            unknown = set(e) - set(mats) - {"att", "wmix", "d_att", "d_wmix", "cols"}
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            if any(e.get(k) is None for k in ("low", "high", "ident", "att", "wmix", "out", "cols")):
+                raise ValueError(f"{name}: cols, low, high, ident, att, wmix and out are required")
+            att = e["att"]
+            if not isinstance(att, torch.Tensor) or att.dim() != 3 or att.shape[1] != 3 or att.shape[0] < 1:
+                raise ValueError(f"{name}: att must be a [reps >= 1, 3, stride] tensor")
+            reps, stride, cols = att.shape[0], att.shape[2], int(e["cols"])
+            if stride not in self.STRIDES:
+                raise ValueError(f"{name}: a replica stride of {stride} floats; the kernel takes 4, 8 or 16")
+            if not 1 <= cols <= stride:
+                raise ValueError(f"{name}: {cols} columns in a replica stride of {stride}; 1..{stride} expected")
+            rows = e["low"].shape[0] if isinstance(e["low"], torch.Tensor) and e["low"].dim() == 2 else -1
+            given = [k for k in grads if e.get(k) is not None]
+            if given and len(given) != len(grads):
+                raise ValueError(f"{name}: d_out, d_low, d_high, d_ident, d_att and d_wmix come together or not at all")
+            self.has_backward = self.has_backward and bool(given)
+            for k in mats:
+                if e.get(k) is not None:
+                    _check_matrix(name, k, e[k], (rows, reps * stride))
+                    if e[k].data_ptr() % 16 or (rows > 1 and _ld(e[k]) % 4):
+                        raise ValueError(f"{name}: {k} must start at a 16-byte boundary and have a leading dimension that is a multiple of 4")
+            for k, ok in (("att", ((reps, 3, stride),)), ("wmix", ((reps, 3, 3), (reps, 9))), ("d_att", ((reps, 3, stride),)),
+                          ("d_wmix", ((reps, 3, 3), (reps, 9)))):
+                t = e.get(k)
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
+                                      or tuple(t.shape) not in ok or not t.is_contiguous()):
+                    raise ValueError(f"{name}: {k} must be a contiguous {list(ok[0])} fp32 device tensor")
+                if t is not None and k in ("att", "d_att") and t.data_ptr() % 16:
+                    raise ValueError(f"{name}: {k} must start at a 16-byte boundary")
+            outputs = ("out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
+            given = [(k, t.reshape(t.shape[0], -1) if t.dim() == 3 else t) for k, t in e.items() if isinstance(t, torch.Tensor)]
+            for i, (ka, ta) in enumerate(given):
+                for kb, tb in given[i + 1:]:
+                    if (ka in outputs or kb in outputs) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
+            shapes.append((rows, reps, cols, stride))
+        dev = require_gpu()  # (after the checks that need no device)
+        rows, reps, cols, stride = (np.fromiter((s_[k] for s_ in shapes), np.int64, n) for k in range(4))
+        self.max_rows, self.max_width = int(rows.max(initial=0)), int((reps * stride).max(initial=0))
+        aux_len = rows * reps * 8
+        aux_off = np.concatenate([[0], np.cumsum(aux_len)]).astype(np.int64)
+        self.aux = torch.zeros(max(int(aux_off[-1]), 1), dtype=torch.float32, device=dev)
+        plen = -(-rows // self.TILE) * reps * (3 * stride + 12)
+        part_off = np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)
+        self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
+        tab = np.zeros(n, _ACM_PACKED_JOB_DTYPE)
+        for i, e in enumerate(entries):
+            for k in ("low", "high", "high_agg", "ident", "att", "wmix", "out", "d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix"):
+                t = e.get(k)
+                tab[k][i] = 0 if t is None else t.data_ptr()
+                if "ld_" + k in _ACM_PACKED_JOB_DTYPE.names:
+                    tab["ld_" + k][i] = 0 if t is None else max(_ld(t), t.shape[1])
+        tab["aux"] = self.aux.data_ptr() + 4 * aux_off[:-1]
+        if self.has_backward:
+            tab["partials"] = self.partials.data_ptr() + 4 * part_off[:-1]
+        tab["rows"], tab["reps"], tab["cols"], tab["stride"], tab["flags"] = rows, reps, cols, stride, np.asarray(flags, np.int64)
+        self.aux_of = [self.aux[aux_off[i]:aux_off[i + 1]].view(int(rows[i]), int(reps[i]), 8) for i in range(n)]
+        host = np.ascontiguousarray(tab)
+        check(lib.wdg_acm_mix_packed_check_jobs(ctypes.c_void_p(host.ctypes.data), n), "wdg_acm_mix_packed_check_jobs")
+        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self):
+        """out and aux of every entry"""
+        check(lib.wdg_acm_mix_packed_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_width, stream_handle()), "wdg_acm_mix_packed_f32")
+
+    def launch_backward(self):
+        """d_low, d_high, d_ident, d_att, d_wmix of every entry from d_out, the inputs and the aux of the last launch()"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError("AcmMixPackedBatch.launch_backward: the table was built without gradient tensors")
+        check(lib.wdg_acm_mix_packed_backward_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_width, stream_handle()),
+              "wdg_acm_mix_packed_backward_f32")
 
 
 class XentEvalBatch:
