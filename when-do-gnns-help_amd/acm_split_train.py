@@ -19,12 +19,10 @@ the result dictionary are SplitTrainBatch's."""
 import numpy as np
 import torch
 
-from ._lib import require_gpu
-from ._rt import _dev
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
-from .split_train import SplitTrainBatch, _classes_and_counts, _labels_and_masks, _replica_ids, replica_seed, xavier
-from .train import AcmMixBatch, AcmMixPackedBatch, DropoutBatch, XentEvalBatch, dropout_constants
+from .split_train import SplitTrainBatch, replica_seed, xavier
+from .train import AcmMixBatch, AcmMixPackedBatch, DropoutBatch, acm_operand_gradient, acm_sgc_weight_gradient, dropout_constants
 
 
 def class_stride(c):
@@ -80,25 +78,8 @@ class AcmSplitTrainBatch(SplitTrainBatch):
         h = int(hidden)
         if self.two_layer and not 1 <= h <= self.MAX_HIDDEN:
             raise ValueError(f"{who}: a hidden layer of {h} units; the channel mix holds a row of 1..{self.MAX_HIDDEN}")
-        labels_np, masks = _labels_and_masks(who, labels, masks)
-        n, R = labels_np.shape[0], masks.shape[0]
-        self.lrs, self.weight_decays, self.dropouts = (np.full(R, float(v)) for v in (lr, weight_decay, dropout))
-        self.replica_ids = ids = _replica_ids(who, replica_ids, R)
-        c, counts = _classes_and_counts(who, labels_np, masks)
-        cs = class_stride(c)
-        dev = require_gpu()  # (after the checks that need no device)
-        from . import models
-        self.adj = adj if isinstance(adj, models.NormAdj) else models.NormAdj(adj, symmetric=symmetric)
-        if self.adj.n != n:
-            raise ValueError(f"{who}: the graph has {self.adj.n} nodes, labels has {n}")
-        x = _dev(x, torch.float32, dev)
-        if x.dim() != 2 or x.shape[0] != n:
-            raise ValueError(f"{who}: x must be [n = {n}, F]")
-        f = x.shape[1]
-        self.x, self.n, self.R, self.c, self.cs, self.f, self.h = x, n, R, c, cs, f, h
-        self.lr, self.weight_decay, self.seed = lr, weight_decay, int(seed)
-        self.dropout_seed = self.seed if dropout_seed is None else int(dropout_seed)
-        self._stage_splits(labels_np, masks, counts, dev)
+        dev = self._prologue(who, adj, x, labels, masks, h, lr, weight_decay, symmetric, seed, dropout, dropout_seed, replica_ids, needs_graph=True)
+        x, n, R, c, cs, f, ids = self.x, self.n, self.R, self.c, self.cs, self.f, self.replica_ids
 
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
         wc, wh = R * cs, R * h  # a channel's columns of a class-width / hidden-width layer
@@ -180,12 +161,9 @@ class AcmSplitTrainBatch(SplitTrainBatch):
                 self.relu = DropoutBatch(units, 0.0, self.dropout_seed)  # p = 0: a plain ReLU plus the transposed copy
                 self.drops = [self.relu]
             self.drop, self.hid_scale = self.drops[0], None
-        self.xent = XentEvalBatch([dict(logits=self.logits, dlogits=self.dlogits, labels=self.labels, split=self.split,
-                                        inv_n_train=self.inv_n_train, C=c, cs=cs)])
-        self.best = self.xent.best_of[0]  # [R, 3] int32: validation hits of the best epoch (-1: none yet), test hits at it, its epoch
-        # (torch's fused Adam, for SplitTrainBatch's reason: its bias corrections are formed in double precision, and it is capturable)
-        self.opt, self.adam = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True, fused=True), None
-        self.graph = None
+        self._epilogue()  # (optimizer "torch": the fused Adam, for SplitTrainBatch's reason)
+
+    _class_stride = staticmethod(class_stride)
 
     def set_hyper(self, lr, weight_decay):
         raise ValueError("AcmSplitTrainBatch.set_hyper: the run steps with torch's Adam (one rate per tensor)")
@@ -209,13 +187,6 @@ class AcmSplitTrainBatch(SplitTrainBatch):
             self._aggregate(self.hw[:, :2 * wc], self.ag2)
             self.mix.launch()                                   # layer 2's mix of all replicas: the logits
 
-    @staticmethod
-    def _operand_gradient(d_pair, t_pair, d_full, width):
-        """d(M W) = [A_hat^T dP_L | dP_H - A_hat^T dP_H | dP_I] from d_pair = [dP_L | dP_H] and t_pair = A_hat^T d_pair (the kernel has
-        written dP_I into the third channel of d_full already)"""
-        d_full[:, :width].copy_(t_pair[:, :width])
-        torch.sub(d_pair[:, width:], t_pair[:, width:], out=d_full[:, width:2 * width])
-
     def _backward(self):
         """the parameter gradients behind self.dlogits, for the forward pass that produced self.logits"""
         with torch.no_grad():
@@ -225,13 +196,10 @@ class AcmSplitTrainBatch(SplitTrainBatch):
             if not self.two_layer:
                 torch.neg(self.dxb[:, :wc], out=self.dya[:, wc:])  # d(high_agg) = -d_high
                 self.bwd.launch()
-                g = self.w.grad  # dW = [Y^T d_low | X^T d_high - Y^T d_high | X^T d_ident]
-                g[:, :wc].copy_(self.gwa[:, :wc])
-                torch.add(self.gwa[:, wc:], self.gwb[:, :wc], out=g[:, wc:2 * wc])
-                g[:, 2 * wc:].copy_(self.gwb[:, wc:])
+                acm_sgc_weight_gradient(self.w.grad, self.gwa, self.gwb, wc)
                 return
             self._aggregate_t(self.dg2, self.t2)
-            self._operand_gradient(self.dg2, self.t2, self.dhw, wc)
+            acm_operand_gradient(self.dg2, self.t2, self.dhw, wc)
             self.d_w1.launch()
             # d(H_r W1_r) of a replica side by side: [n, R, 3 cs] from the channel-major [n, 3, R, cs]
             self.dhw_r.view(-1, R, 3, cs).copy_(self.dhw.view(-1, 3, R, cs).transpose(1, 2))
@@ -241,7 +209,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
             self.dhid.copy_(torch.where(self.hid > 0, self.dhid * self.drop.scale, 0.0))
             self.mix0.launch_backward()
             self._aggregate_t(self.dg1, self.t1)
-            self._operand_gradient(self.dg1, self.t1, self.dxw, wh)
+            acm_operand_gradient(self.dg1, self.t1, self.dxw, wh)
             gemm(self.xt, self.dxw, out=self.w0.grad)           # dW0 = X^T d(X W0)
 
     # -- one replica ---------------------------------------------------------------------------------------------
@@ -260,20 +228,6 @@ class AcmSplitTrainBatch(SplitTrainBatch):
         return (self._first_layer_block(pick(self.w0), r, h, h), pick(self.att0)[r], pick(self.wmix0)[r],
                 w1, pick(self.att1)[r, :, :c], pick(self.wmix1)[r])
 
-    def replica_model(self, r):
-        """a models.ACMSGC1 / ACMGCN2 on the device holding replica r's CURRENT parameters (copies); with dropout > 0 its hidden layer
-        draws from models.DeviceDropout(dropout_seed, stream=replica_ids[r]); its step word starts at 0"""
-        from . import models
-        if not 0 <= r < self.R:
-            raise ValueError(f"AcmSplitTrainBatch.replica_model: replica {r} of {self.R}")
-        with torch.random.fork_rng(devices=[]):  # (the constructors draw an initialisation that is overwritten below)
-            if self.two_layer:
-                rng = models.DeviceDropout(self.dropout_seed, stream=int(self.replica_ids[r])) if self.dropout > 0 else None
-                model = models.ACMGCN2(self.f, self.c, nhid=self.h, dropout=self.dropout, dropout_rng=rng)
-            else:
-                model = models.ACMSGC1(self.f, self.c)
-        model = model.to(self.x.device)
-        with torch.no_grad():
-            for p, w in zip(model.parameters(), self.weights_of(r)):
-                p.copy_(w)
-        return model
+    def _empty_model(self, models, p, rng):
+        """replica_model()'s module: a models.ACMGCN2 / ACMSGC1"""
+        return models.ACMGCN2(self.f, self.c, nhid=self.h, dropout=p, dropout_rng=rng) if self.two_layer else models.ACMSGC1(self.f, self.c)

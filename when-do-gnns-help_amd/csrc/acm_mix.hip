@@ -16,6 +16,7 @@
 // 16 row slots are added in order through LDS, the workgroup stores one vector per 64-row block, and acm_mix_reduce_kernel adds
 // the blocks in block order (the store-and-sum form).
 #include "wdg_common.h"
+#include "acm_mix_row.h"  // the arithmetic of a row after its row sums, shared with acm_mix_packed.hip
 
 #pragma clang fp contract(off)  // every multiply-add below is written out (fmaf or two operations): the same bits in every instantiation
 
@@ -23,9 +24,8 @@ namespace {
 
 using namespace wdg;
 
-constexpr int AM_TILE = 64, AM_THREADS = 256, AM_SLOTS = 16, AM_ROWS_PER_THREAD = 4;
-constexpr int AM_MAX_JOBS = 65535;  // gridDim.z: a job per z
-constexpr float AM_INV_T = 1.0f / 3.0f;
+constexpr int AM_TILE = acm::TILE, AM_THREADS = acm::THREADS, AM_SLOTS = acm::SLOTS, AM_ROWS_PER_THREAD = acm::ROWS_PER_THREAD;
+constexpr int AM_MAX_JOBS = acm::MAX_JOBS;  // gridDim.z: a job per z
 
 struct am_mat {  // one [rows, cols] operand of a job
     global_ptr<const float> p;
@@ -33,7 +33,7 @@ struct am_mat {  // one [rows, cols] operand of a job
     bool vec;  // 16-byte rows: pointer and leading dimension
 };
 __device__ __forceinline__ am_mat am_operand(const float *p, const int64_t ld) {
-    return am_mat{to_global(p), ld, ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0};
+    return am_mat{to_global(p), ld, acm::rows_aligned16(p, ld)};
 }
 // four adjacent columns c .. c + 3 of row r; columns at or past `cols` read as +0
 __device__ __forceinline__ void am_load4(const am_mat &m, const int r, const int c, const int cols, float (&v)[4]) {
@@ -52,7 +52,7 @@ __device__ __forceinline__ void am_load4(const am_mat &m, const int r, const int
 __device__ __forceinline__ void am_store4(float *base, const int64_t ld, const int r, const int c, const int cols, const float (&v)[4]) {
     if (c >= cols) return;
     const global_ptr<float> p = to_global(base) + static_cast<int64_t>(r) * ld + c;
-    if (((reinterpret_cast<uintptr_t>(base) | static_cast<uintptr_t>(ld * 4)) & 15) == 0 && c + 3 < cols) {
+    if (acm::rows_aligned16(base, ld) && c + 3 < cols) {
         store_f32x4(p, make_float4(v[0], v[1], v[2], v[3]));
     } else {
 #pragma unroll
@@ -68,7 +68,6 @@ __device__ __forceinline__ float am_row_sum(float v) {
     v = v + __shfl_xor(v, 8, 16);
     return v;
 }
-__device__ __forceinline__ float am_relu(const float p) { return p <= 0.f ? 0.f : p; }  // (a NaN fails the comparison and stays)
 
 // the three channels of row r, columns 4 gq + 64 q .. + 3, activation applied: h[c][q][k]
 template <int CH>
@@ -90,7 +89,7 @@ __device__ __forceinline__ void am_channels(const am_mat &low, const am_mat &hig
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) h[ch][q][k] = am_relu(h[ch][q][k]);
+                for (int k = 0; k < 4; ++k) h[ch][q][k] = acm::relu(h[ch][q][k]);
         }
     }
 }
@@ -140,29 +139,20 @@ __global__ __launch_bounds__(AM_THREADS) void acm_mix_kernel(const wdg_acm_mix_j
 #pragma unroll
         for (int q = 0; q < CH; ++q) o[m][q][0] = o[m][q][1] = o[m][q][2] = o[m][q][3] = 0.f;
         if (r >= rows) continue;  // (the 16 lanes of a row together)
-        float h[3][CH][4], s[3], z[3], al[3];
+        float h[3][CH][4], dot[3], s[3], al[3];
         am_channels<CH>(low, high, agg, has_agg, ident, r, gq, cols, relu, h);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] = 1.0f / (1.0f + expf(-am_row_sum(am_dot<CH>(h[c], att[c]))));
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            z[c] = fmaf(s[2] * AM_INV_T, wm[6 + c], fmaf(s[1] * AM_INV_T, wm[3 + c], (s[0] * AM_INV_T) * wm[c]));
-        const float zmax = fmaxf(fmaxf(z[0], z[1]), z[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) al[c] = expf(z[c] - zmax);
-        const float den = (al[0] + al[1]) + al[2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) al[c] = al[c] / den;
+        for (int c = 0; c < 3; ++c) dot[c] = am_row_sum(am_dot<CH>(h[c], att[c]));
+        acm::alpha(dot, wm, s, al);
 #pragma unroll
         for (int q = 0; q < CH; ++q) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                o[m][q][k] = 3.0f * fmaf(al[2], h[2][q][k], fmaf(al[1], h[1][q][k], al[0] * h[0][q][k]));
+            for (int k = 0; k < 4; ++k) o[m][q][k] = acm::mix(al, h[0][q][k], h[1][q][k], h[2][q][k]);
             am_store4(job->out, job->ld_out, r, 64 * q + 4 * gq, cols, o[m][q]);
         }
-        if (gq < 8) {  // aux[r] = alpha_L alpha_H alpha_I s_L s_H s_I 0 0: a lane per word
+        if (gq < acm::AUX_WORDS) {  // aux[r] = alpha_L alpha_H alpha_I s_L s_H s_I 0 0: a lane per word
             const float w = gq == 0 ? al[0] : gq == 1 ? al[1] : gq == 2 ? al[2] : gq == 3 ? s[0] : gq == 4 ? s[1] : gq == 5 ? s[2] : 0.f;
-            aux[static_cast<int64_t>(r) * 8 + gq] = w;
+            aux[static_cast<int64_t>(r) * acm::AUX_WORDS + gq] = w;
         }
     }
     if (!transposed) return;  // (uniform)
@@ -219,24 +209,18 @@ __global__ __launch_bounds__(AM_THREADS) void acm_mix_backward_kernel(const wdg_
     for (int m = 0; m < AM_ROWS_PER_THREAD; ++m) {
         const int r = r0 + slot + AM_SLOTS * m;
         if (r >= rows) continue;  // (the 16 lanes of a row together)
-        float h[3][CH][4], g[CH][4], al[3], s[3], dal[3], dz[3], du[3];
+        float h[3][CH][4], g[CH][4], al[3], s[3], dal[3], du[3];
         am_channels<CH>(low, high, agg, has_agg, ident, r, gq, cols, relu, h);
 #pragma unroll
         for (int q = 0; q < CH; ++q) am_load4(dout, r, 64 * q + 4 * gq, cols, g[q]);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) al[c] = aux[static_cast<int64_t>(r) * 8 + c], s[c] = aux[static_cast<int64_t>(r) * 8 + 3 + c];
+        for (int c = 0; c < 3; ++c) {
+            al[c] = aux[static_cast<int64_t>(r) * acm::AUX_WORDS + acm::AUX_ALPHA + c];
+            s[c] = aux[static_cast<int64_t>(r) * acm::AUX_WORDS + acm::AUX_S + c];
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) dal[c] = 3.0f * am_row_sum(am_dot<CH>(g, h[c]));
-        const float mean = fmaf(al[2], dal[2], fmaf(al[1], dal[1], al[0] * dal[0]));
-#pragma unroll
-        for (int c = 0; c < 3; ++c) dz[c] = al[c] * (dal[c] - mean);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float ds = AM_INV_T * fmaf(wm[3 * j + 2], dz[2], fmaf(wm[3 * j + 1], dz[1], wm[3 * j] * dz[0]));
-            du[j] = (ds * s[j]) * (1.0f - s[j]);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dw[3 * j + c] = fmaf(s[j] * AM_INV_T, dz[c], dw[3 * j + c]);
-        }
+        acm::scores_backward(al, s, dal, wm, du, dw);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float a3 = 3.0f * al[c];
@@ -244,11 +228,7 @@ __global__ __launch_bounds__(AM_THREADS) void acm_mix_backward_kernel(const wdg_
             for (int q = 0; q < CH; ++q) {
                 float dp[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    da[c][q][k] = fmaf(du[c], h[c][q][k], da[c][q][k]);
-                    dp[k] = fmaf(a3, g[q][k], du[c] * att[c][q][k]);
-                    if (relu && !(h[c][q][k] > 0.f) && h[c][q][k] == h[c][q][k]) dp[k] = 0.f;  // (a NaN unit keeps its NaN gradient)
-                }
+                for (int k = 0; k < 4; ++k) dp[k] = acm::input_gradient(a3, g[q][k], du[c], att[c][q][k], h[c][q][k], relu, da[c][q][k]);
                 am_store4(d_mat[c], d_ld[c], r, 64 * q + 4 * gq, cols, dp);
             }
         }

@@ -19,6 +19,7 @@
 // Every access to a matrix, to att / d_att, aux and the partial sums is a 16-byte one (the preconditions: 16-byte aligned pointers,
 // leading dimensions that are multiples of 4); wmix / d_wmix are [reps, 9] and are read and written word by word.
 #include "wdg_common.h"
+#include "acm_mix_row.h"  // the arithmetic of a row after its row sums, shared with acm_mix.hip: one text, so one set of bits
 
 #pragma clang fp contract(off)  // every multiply-add below is written out (fmaf or two operations): acm_mix.hip's bits
 
@@ -26,17 +27,12 @@ namespace {
 
 using namespace wdg;
 
-constexpr int AP_TILE = 64, AP_THREADS = 256, AP_SLOTS = 16, AP_ROWS_PER_THREAD = 4;
-constexpr int AP_MAX_JOBS = 65535;               // gridDim.z: a job per z
+constexpr int AP_TILE = acm::TILE, AP_THREADS = acm::THREADS, AP_SLOTS = acm::SLOTS, AP_ROWS_PER_THREAD = acm::ROWS_PER_THREAD;
+constexpr int AP_MAX_JOBS = acm::MAX_JOBS;       // gridDim.z: a job per z
 constexpr int64_t AP_MAX_WIDTH = 64LL * 65535;   // gridDim.y: a 64-column block per y
-constexpr float AP_INV_T = 1.0f / 3.0f;
 constexpr int AP_RED_DW = 3 * AP_TILE;           // a row slot's sums in LDS: d_att [3][64], then 12 words of d_wmix per replica
 
 __host__ __device__ constexpr int ap_partial_len(const int stride) { return 3 * stride + 12; }  // d_att [3, stride], d_wmix [9], 3 unused
-
-__host__ __device__ inline bool ap_aligned(const void *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
 
 // what makes a job malformed (the kernels skip such a job; wdg_acm_mix_packed_check_jobs says which rule it breaks)
 template <typename J>
@@ -52,8 +48,8 @@ __host__ __device__ inline const char *ap_defect(const J job, const bool backwar
     if (!job->att || !job->wmix || (!empty && (!job->low || !job->high || !job->ident || !job->out || !job->aux))) return "a null required pointer";
     if (job->ld_low < width || job->ld_high < width || job->ld_ident < width || job->ld_out < width || (job->high_agg && job->ld_high_agg < width))
         return "a leading dimension below reps * stride";
-    if (!ap_aligned(job->low, job->ld_low) || !ap_aligned(job->high, job->ld_high) || !ap_aligned(job->ident, job->ld_ident) ||
-        !ap_aligned(job->out, job->ld_out) || (job->high_agg && !ap_aligned(job->high_agg, job->ld_high_agg)) || !ap_aligned(job->att, 0) || !ap_aligned(job->aux, 0))
+    if (!acm::rows_aligned16(job->low, job->ld_low) || !acm::rows_aligned16(job->high, job->ld_high) || !acm::rows_aligned16(job->ident, job->ld_ident) ||
+        !acm::rows_aligned16(job->out, job->ld_out) || (job->high_agg && !acm::rows_aligned16(job->high_agg, job->ld_high_agg)) || !acm::rows_aligned16(job->att, 0) || !acm::rows_aligned16(job->aux, 0))
         return "a pointer that is not 16-byte aligned or a leading dimension that is no multiple of 4";
     const bool any = job->d_out || job->d_low || job->d_high || job->d_ident || job->d_att || job->d_wmix || job->partials;
     if (!backward && !any) return nullptr;
@@ -61,8 +57,8 @@ __host__ __device__ inline const char *ap_defect(const J job, const bool backwar
         return "a null required pointer (the gradient arrays come together)";
     if (job->ld_d_out < width || job->ld_d_low < width || job->ld_d_high < width || job->ld_d_ident < width)
         return "a leading dimension below reps * stride";
-    if (!ap_aligned(job->d_out, job->ld_d_out) || !ap_aligned(job->d_low, job->ld_d_low) || !ap_aligned(job->d_high, job->ld_d_high) ||
-        !ap_aligned(job->d_ident, job->ld_d_ident) || !ap_aligned(job->d_att, 0) || !ap_aligned(job->partials, 0))
+    if (!acm::rows_aligned16(job->d_out, job->ld_d_out) || !acm::rows_aligned16(job->d_low, job->ld_d_low) || !acm::rows_aligned16(job->d_high, job->ld_d_high) ||
+        !acm::rows_aligned16(job->d_ident, job->ld_d_ident) || !acm::rows_aligned16(job->d_att, 0) || !acm::rows_aligned16(job->partials, 0))
         return "a pointer that is not 16-byte aligned or a leading dimension that is no multiple of 4";
     return nullptr;
 }
@@ -78,7 +74,6 @@ __device__ __forceinline__ float ap_seg_sum(float v, const int stride) {
     if (stride >= 16) v = v + __shfl_xor(v, 2, 16);
     return v + 0.f;  // am_row_sum's remaining steps add lanes that hold +0
 }
-__device__ __forceinline__ float ap_relu(const float p) { return p <= 0.f ? 0.f : p; }  // (a NaN fails the comparison and stays)
 __device__ __forceinline__ float ap_dot(const float (&x)[4], const float (&y)[4]) {
     float acc = 0.f;
 #pragma unroll
@@ -110,7 +105,7 @@ __device__ __forceinline__ void ap_channels(const ap_operands &o, const int r, c
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) h[ch][k] = ap_relu(h[ch][k]);
+            for (int k = 0; k < 4; ++k) h[ch][k] = acm::relu(h[ch][k]);
     }
 }
 
@@ -137,25 +132,17 @@ __global__ __launch_bounds__(AP_THREADS) void acm_packed_kernel(const wdg_acm_pa
     for (int m = 0; m < AP_ROWS_PER_THREAD; ++m) {
         const int r = r0 + slot + AP_SLOTS * m;
         if (r >= rows) continue;  // (the 16 lanes of a row together)
-        float h[3][4], s[3], z[3], al[3], o[4];
+        float h[3][4], dot[3], s[3], al[3], o[4];
         ap_channels(ops, r, c0, real, h);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] = 1.0f / (1.0f + expf(-ap_seg_sum(ap_dot(h[c], att[c]), stride)));
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            z[c] = fmaf(s[2] * AP_INV_T, wm[6 + c], fmaf(s[1] * AP_INV_T, wm[3 + c], (s[0] * AP_INV_T) * wm[c]));
-        const float zmax = fmaxf(fmaxf(z[0], z[1]), z[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) al[c] = expf(z[c] - zmax);
-        const float den = (al[0] + al[1]) + al[2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) al[c] = al[c] / den;
+        for (int c = 0; c < 3; ++c) dot[c] = ap_seg_sum(ap_dot(h[c], att[c]), stride);
+        acm::alpha(dot, wm, s, al);
 #pragma unroll
         for (int k = 0; k < 4; ++k)  // (a padding column is WRITTEN +0: a NaN alpha does not reach it)
-            o[k] = k < real ? 3.0f * fmaf(al[2], h[2][k], fmaf(al[1], h[1][k], al[0] * h[0][k])) : 0.f;
+            o[k] = k < real ? acm::mix(al, h[0][k], h[1][k], h[2][k]) : 0.f;
         store_f32x4(out + (static_cast<int64_t>(r) * ld_out + c0), make_float4(o[0], o[1], o[2], o[3]));
         if (cr == 0) {  // aux[r][rep] = alpha_L alpha_H alpha_I s_L s_H s_I 0 0: the replica's first lane
-            const global_ptr<float> a = aux + (static_cast<int64_t>(r) * reps + rep) * 8;
+            const global_ptr<float> a = aux + (static_cast<int64_t>(r) * reps + rep) * acm::AUX_WORDS;
             store_f32x4(a, make_float4(al[0], al[1], al[2], s[0]));
             store_f32x4(a + 4, make_float4(s[1], s[2], 0.f, 0.f));
         }
@@ -194,34 +181,23 @@ __global__ __launch_bounds__(AP_THREADS) void acm_packed_backward_kernel(const w
         for (int m = 0; m < AP_ROWS_PER_THREAD; ++m) {
             const int r = r0 + slot + AP_SLOTS * m;
             if (r >= rows) continue;  // (the 16 lanes of a row together)
-            float h[3][4], g[4], al[3], s[3], dal[3], dz[3], du[3];
+            float h[3][4], g[4], al[3], s[3], dal[3], du[3];
             ap_channels(ops, r, c0, real, h);
             ap_load4(dout, static_cast<int64_t>(r) * ld_dout + c0, real, g);
-            const global_ptr<const float> a = aux + (static_cast<int64_t>(r) * reps + rep) * 8;
+            const global_ptr<const float> a = aux + (static_cast<int64_t>(r) * reps + rep) * acm::AUX_WORDS;
             const float4 a0 = load_f32x4(a), a1 = load_f32x4(a + 4);
             al[0] = a0.x, al[1] = a0.y, al[2] = a0.z, s[0] = a0.w, s[1] = a1.x, s[2] = a1.y;
 #pragma unroll
             for (int c = 0; c < 3; ++c) dal[c] = 3.0f * ap_seg_sum(ap_dot(g, h[c]), stride);
-            const float mean = fmaf(al[2], dal[2], fmaf(al[1], dal[1], al[0] * dal[0]));
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dz[c] = al[c] * (dal[c] - mean);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float ds = AP_INV_T * fmaf(wm[3 * j + 2], dz[2], fmaf(wm[3 * j + 1], dz[1], wm[3 * j] * dz[0]));
-                du[j] = (ds * s[j]) * (1.0f - s[j]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) dw[3 * j + c] = fmaf(s[j] * AP_INV_T, dz[c], dw[3 * j + c]);
-            }
+            acm::scores_backward(al, s, dal, wm, du, dw);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float a3 = 3.0f * al[c];
                 float dp[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    da[c][k] = fmaf(du[c], h[c][k], da[c][k]);
-                    dp[k] = fmaf(a3, g[k], du[c] * att[c][k]);
-                    if (ops.relu && !(h[c][k] > 0.f) && h[c][k] == h[c][k]) dp[k] = 0.f;  // (a NaN unit keeps its NaN gradient)
-                    if (k >= real) dp[k] = 0.f;                                           // (a padding column is WRITTEN +0)
+                    dp[k] = acm::input_gradient(a3, g[k], du[c], att[c][k], h[c][k], ops.relu, da[c][k]);
+                    if (k >= real) dp[k] = 0.f;  // (a padding column is WRITTEN +0)
                 }
                 store_f32x4(d_mat[c] + (static_cast<int64_t>(r) * d_ld[c] + c0), make_float4(dp[0], dp[1], dp[2], dp[3]));
             }

@@ -156,29 +156,9 @@ class SplitTrainBatch:
             raise ValueError(f"SplitTrainBatch: a drop probability in [0, 1) expected, got {dropout!r}")
         if (self.dropout > 0 or per_replica["dropout"]) and not self.two_layer:
             raise ValueError(f"SplitTrainBatch: kind {kind!r} has no hidden layer to drop units of (dropout applies to 'gcn' / 'mlp2')")
-        labels_np, masks = _labels_and_masks("SplitTrainBatch", labels, masks)
-        n, R = labels_np.shape[0], masks.shape[0]
-        spread = lambda val, name: self._per_replica(val, R, name)  # noqa: E731
-        self.lrs, self.weight_decays, self.dropouts = spread(lr, "lr"), spread(weight_decay, "weight_decay"), spread(dropout, "dropout")
-        self.replica_ids = ids = _replica_ids("SplitTrainBatch", replica_ids, R)
-        c, counts = _classes_and_counts("SplitTrainBatch", labels_np, masks)
-        dev = require_gpu()  # (after the checks that need no device)
-        from . import models
-        if kind in ("sgc", "gcn"):
-            self.adj = adj if isinstance(adj, models.NormAdj) else models.NormAdj(adj, symmetric=symmetric)
-            if self.adj.n != n:
-                raise ValueError(f"SplitTrainBatch: the graph has {self.adj.n} nodes, labels has {n}")
-        else:
-            self.adj = adj if isinstance(adj, models.NormAdj) or adj is None else models.NormAdj(adj, symmetric=symmetric)
-        x = _dev(x, torch.float32, dev)
-        if x.dim() != 2 or x.shape[0] != n:
-            raise ValueError(f"SplitTrainBatch: x must be [n = {n}, F]")
-        f, h = x.shape[1], int(hidden)
-        cs = -(-c // 4) * 4
-        self.x, self.n, self.R, self.c, self.cs, self.f, self.h = x, n, R, c, cs, f, h
-        self.lr, self.weight_decay, self.seed = lr, weight_decay, int(seed)
-        self.dropout_seed = self.seed if dropout_seed is None else int(dropout_seed)
-        self._stage_splits(labels_np, masks, counts, dev)
+        dev = self._prologue("SplitTrainBatch", adj, x, labels, masks, hidden, lr, weight_decay, symmetric, seed, dropout, dropout_seed, replica_ids,
+                             needs_graph=kind in ("sgc", "gcn"))
+        x, n, R, c, cs, f, h, ids = self.x, self.n, self.R, self.c, self.cs, self.f, self.h, self.replica_ids
 
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
         self.logits, self.dlogits = z(n, R * cs), z(n, R * cs)
@@ -229,16 +209,50 @@ class SplitTrainBatch:
             else:
                 self.y = x
             self.yt = self.y.t().contiguous()  # for dW = Y^T dlogits
+        self._epilogue()
+
+    # -- the constructor's steps that every stacked run shares (acm_split_train.AcmSplitTrainBatch builds its own layout between them) --
+    def _prologue(self, who, adj, x, labels, masks, hidden, lr, weight_decay, symmetric, seed, dropout, dropout_seed, replica_ids, needs_graph):
+        """the checks of labels, masks, replica ids and classes (`who` names the class in the messages), then - on the device - the
+        graph (needs_graph: required; else optional), x, the run's scalars and the staged splits -> the device"""
+        labels_np, masks = _labels_and_masks(who, labels, masks)
+        n, R = labels_np.shape[0], masks.shape[0]
+        spread = lambda val, name: self._per_replica(val, R, name)  # noqa: E731
+        self.lrs, self.weight_decays, self.dropouts = spread(lr, "lr"), spread(weight_decay, "weight_decay"), spread(dropout, "dropout")
+        self.replica_ids = _replica_ids(who, replica_ids, R)
+        c, counts = _classes_and_counts(who, labels_np, masks)
+        dev = require_gpu()  # (after the checks that need no device)
+        from . import models
+        self.adj = adj if isinstance(adj, models.NormAdj) or (adj is None and not needs_graph) else models.NormAdj(adj, symmetric=symmetric)
+        if needs_graph and self.adj.n != n:
+            raise ValueError(f"{who}: the graph has {self.adj.n} nodes, labels has {n}")
+        x = _dev(x, torch.float32, dev)
+        if x.dim() != 2 or x.shape[0] != n:
+            raise ValueError(f"{who}: x must be [n = {n}, F]")
+        self.x, self.n, self.R, self.c, self.cs, self.f, self.h = x, n, R, c, self._class_stride(c), x.shape[1], int(hidden)
+        self.lr, self.weight_decay, self.seed = lr, weight_decay, int(seed)
+        self.dropout_seed = self.seed if dropout_seed is None else int(dropout_seed)
+        self._stage_splits(labels_np, masks, counts, dev)
+        return dev
+
+    @staticmethod
+    def _class_stride(c):
+        """the columns between the replicas of a class-width matrix: c rounded up to a multiple of 4"""
+        return -(-c // 4) * 4
+
+    def _epilogue(self):
+        """the loss kernel's table over the stacked logits, the running best, the optimizer over self.params; no captured epoch yet"""
         self.xent = XentEvalBatch([dict(logits=self.logits, dlogits=self.dlogits, labels=self.labels, split=self.split,
-                                        inv_n_train=self.inv_n_train, C=c, cs=cs)])
+                                        inv_n_train=self.inv_n_train, C=self.c, cs=self.cs)])
         self.best = self.xent.best_of[0]  # [R, 3] int32: validation hits of the best epoch (-1: none yet), test hits at it, its epoch
         # torch's fused Adam: its kernel forms the bias corrections 1 - beta^t in double precision.  The unfused capturable path forms
         # them in fp32 tensors - 1 - 0.999^t cancels to a relative error of 1e-5 - and twelve epochs end 9e-7 from a float64 run where
         # this form ends 1e-7 from it (measured: tests/test_gpu_split_train.py).  Both keep the step count on the device: capturable.
-        if optimizer == "torch":
-            self.opt, self.adam = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True, fused=True), None
+        if self.optimizer == "torch":
+            self.opt, self.adam = torch.optim.Adam(self.params, lr=self.lr, weight_decay=self.weight_decay, capturable=True, fused=True), None
         else:
             # ops.AdamBatch: one job per parameter tensor, a replica = a segment (a column block of w0 / w, a row block of w1)
+            R, f, h, cs = self.R, self.f, self.h, self.cs
             hyper = np.stack([self.lrs, self.weight_decays], 1).astype(np.float32)
             if self.two_layer:
                 entries = [(self.w0.data, self.w0.grad, f, h, hyper), (self.w1.data.view(R * h, cs), self.w1.grad.view(R * h, cs), h, cs, hyper)]
@@ -400,21 +414,23 @@ class SplitTrainBatch:
     def logits_of(self, r):
         return self.logits[:, r * self.cs:r * self.cs + self.c]
 
+    def _empty_model(self, models, p, rng):
+        """the per-replica reference module of this kind, freshly initialised: drop probability p, dropout generator rng (or None)"""
+        if self.two_layer:
+            return (models.GCN2 if self.kind == "gcn" else models.MLP2)(self.f, self.c, nhid=self.h, dropout=p, dropout_rng=rng)
+        return (models.SGC1 if self.kind == "sgc" else models.MLP1)(self.f, self.c)
+
     def replica_model(self, r):
-        """a models.SGC1 / GCN2 / MLP1 / MLP2 on the device holding replica r's CURRENT weights (copies); with dropout > 0 its hidden
-        layer draws from models.DeviceDropout(dropout_seed, stream=replica_ids[r]) with replica r's own drop probability; its step
-        word starts at 0"""
+        """the per-replica reference (a models.SGC1 / GCN2 / MLP1 / MLP2; a subclass: its own) on the device holding replica r's CURRENT
+        parameters (copies); with dropout > 0 its hidden layer draws from models.DeviceDropout(dropout_seed, stream=replica_ids[r]) with
+        replica r's own drop probability; its step word starts at 0"""
         from . import models
         if not 0 <= r < self.R:
-            raise ValueError(f"SplitTrainBatch.replica_model: replica {r} of {self.R}")
-        with torch.random.fork_rng(devices=[]):  # (the constructors draw an initialisation that is overwritten below)
-            if self.two_layer:
-                p = float(self.dropouts[r])
-                rng = models.DeviceDropout(self.dropout_seed, stream=int(self.replica_ids[r])) if p > 0 else None
-                cls = models.GCN2 if self.kind == "gcn" else models.MLP2
-                model = cls(self.f, self.c, nhid=self.h, dropout=p, dropout_rng=rng)
-            else:
-                model = (models.SGC1 if self.kind == "sgc" else models.MLP1)(self.f, self.c)
+            raise ValueError(f"{type(self).__name__}.replica_model: replica {r} of {self.R}")
+        p = float(self.dropouts[r])
+        with torch.random.fork_rng(devices=[]):  # (the constructor draws an initialisation that is overwritten below)
+            rng = models.DeviceDropout(self.dropout_seed, stream=int(self.replica_ids[r])) if self.two_layer and p > 0 else None
+            model = self._empty_model(models, p, rng)
         model = model.to(self.x.device)
         with torch.no_grad():
             for p, w in zip(model.parameters(), self.weights_of(r)):
@@ -506,7 +522,7 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     if not two_layer and any(float(g["dropout"]) != 0.0 for g in grid):
         raise ValueError(f"grid_search: kind {kind!r} has no hidden layer to drop units of: every setting's dropout must be 0")
     labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
-    cs = -(-(int(labels_np.max()) + 1 if labels_np.size else 1) // 4) * 4
+    cs = SplitTrainBatch._class_stride(int(labels_np.max()) + 1 if labels_np.size else 1)
     if max_replicas is None:
         max_replicas = default_max_replicas(n, int(hidden) if two_layer else cs, kind, S)
     chunks = chunk_settings(len(grid), S, max_replicas)

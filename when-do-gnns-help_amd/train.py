@@ -176,14 +176,114 @@ def _views_may_overlap(a, b):
     return True
 
 
-class AcmMixBatch:
+class _AcmMixTable:
+    """What the job tables of the two channel-mix kernels share: the activation flags, the key checks, the "all six gradient tensors or
+    none" rule, the overlap check, the pointer / leading-dimension fill, aux and the partial sums of the parameter gradients (owned by
+    the table, one slice per entry) and the two launches.  A subclass states its record type and entry points, its keys and, in
+    _shape(), its shape rules; _check_alignment() and _check_jobs() are there for the kernel that has such rules."""
+
+    MAX_JOBS, TILE = 65535, 64
+    _MATS = ("low", "high", "high_agg", "ident", "out", "d_out", "d_low", "d_high", "d_ident")
+    _VECS = ("att", "wmix", "d_att", "d_wmix")
+    _GRADS = ("d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
+    _OUTPUTS = ("out", "out_t", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
+    # of a subclass: _DTYPE, _FORWARD, _BACKWARD (the record type and the entry points), _EXTRA (its keys besides _MATS and _VECS),
+    # _REQUIRED (in the order of the message)
+
+    def __init__(self, entries, relu):
+        name = type(self).__name__
+        self.keep = entries
+        n = self.n_jobs = len(entries)
+        if n > self.MAX_JOBS:
+            raise ValueError(f"{name}: {n} entries; one launch takes {self.MAX_JOBS}")
+        flags = [bool(relu)] * n if np.ndim(relu) == 0 else [bool(f) for f in relu]
+        if len(flags) != n:
+            raise ValueError(f"{name}: one activation flag per entry")
+        self.has_backward = n > 0
+        shapes = []
+        for e in entries:
+            unknown = set(e) - set(self._MATS) - set(self._VECS) - set(self._EXTRA)
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            if any(e.get(k) is None for k in self._REQUIRED):
+                raise ValueError(f"{name}: {', '.join(self._REQUIRED[:-1])} and {self._REQUIRED[-1]} are required")
+            rows, width, vec_shapes, fields, aux_shape, part_len = self._shape(e)
+            given = [k for k in self._GRADS if e.get(k) is not None]
+            if given and len(given) != len(self._GRADS):
+                raise ValueError(f"{name}: d_out, d_low, d_high, d_ident, d_att and d_wmix come together or not at all")
+            self.has_backward = self.has_backward and bool(given)
+            for k in self._MATS:
+                if e.get(k) is not None:
+                    _check_matrix(name, k, e[k], (rows, width))
+                    self._check_alignment(k, e[k], rows)
+            for k in self._VECS:
+                t, ok = e.get(k), vec_shapes[k[2:] if k.startswith("d_") else k]
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
+                                      or tuple(t.shape) not in ok or not t.is_contiguous()):
+                    raise ValueError(f"{name}: {k} must be a contiguous {list(ok[0])} fp32 device tensor")
+                if t is not None:
+                    self._check_alignment(k, t, rows)
+            if e.get("out_t") is not None:
+                _check_matrix(name, "out_t", e["out_t"], (width, rows))
+            given = [(k, t.reshape(t.shape[0], -1) if t.dim() == 3 else t) for k, t in e.items() if isinstance(t, torch.Tensor)]
+            for i, (ka, ta) in enumerate(given):
+                for kb, tb in given[i + 1:]:
+                    if (ka in self._OUTPUTS or kb in self._OUTPUTS) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
+            shapes.append((fields, width, aux_shape, -(-rows // self.TILE) * part_len))
+        dev = require_gpu()  # (after the checks that need no device)
+        offsets = lambda lens: np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n))]).astype(np.int64)  # noqa: E731
+        aux_off, part_off = offsets(int(np.prod(s_[2])) for s_ in shapes), offsets(s_[3] for s_ in shapes)
+        self.aux = torch.zeros(max(int(aux_off[-1]), 1), dtype=torch.float32, device=dev)
+        self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
+        tab = np.zeros(n, self._DTYPE)
+        for i, e in enumerate(entries):
+            for k in self._MATS + self._VECS + ("out_t",):
+                if k in self._DTYPE.names:
+                    t = e.get(k)
+                    tab[k][i] = 0 if t is None else t.data_ptr()
+                    if "ld_" + k in self._DTYPE.names:
+                        tab["ld_" + k][i] = 0 if t is None else _ld(t)
+            for k, v in shapes[i][0].items():
+                tab[k][i] = v
+        tab["aux"] = self.aux.data_ptr() + 4 * aux_off[:-1]
+        if self.has_backward:
+            tab["partials"] = self.partials.data_ptr() + 4 * part_off[:-1]
+        tab["flags"] = np.asarray(flags, np.int64)
+        self.max_rows = int(tab["rows"].max(initial=0))
+        self._widest = max((s_[1] for s_ in shapes), default=0)
+        self.aux_of = [self.aux[aux_off[i]:aux_off[i + 1]].view(shapes[i][2]) for i in range(n)]
+        host = np.ascontiguousarray(tab)
+        self._check_jobs(host)
+        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def _check_alignment(self, k, t, rows):
+        """(the kernel that takes any alignment)"""
+
+    def _check_jobs(self, host):
+        """(the kernel without a host-side check of its records)"""
+
+    def launch(self):
+        """out (and out_t, aux) of every entry"""
+        check(getattr(lib, self._FORWARD)(_ptr(self.table), self.n_jobs, self.max_rows, self._widest, stream_handle()), self._FORWARD)
+
+    def launch_backward(self):
+        """d_low, d_high, d_ident, d_att, d_wmix of every entry from d_out, the inputs and the aux of the last launch()"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError(f"{type(self).__name__}.launch_backward: the table was built without gradient tensors")
+        check(getattr(lib, self._BACKWARD)(_ptr(self.table), self.n_jobs, self.max_rows, self._widest, stream_handle()), self._BACKWARD)
+
+
+class AcmMixBatch(_AcmMixTable):
     """Job table for wdg_acm_mix_batched_f32 / wdg_acm_mix_backward_batched_f32 (csrc/acm_mix.hip): the channel mix of one ACM layer
     per entry - out = 3 sum_c alpha_c H_c over the channels H_L = act(low), H_H = act(high - high_agg), H_I = act(ident), with
     alpha = softmax((sigmoid(H_c . att_c) / 3) wmix) per row (include/wdg.h states it; tests/_acm_ref.py restates it in numpy) - and
     its backward pass, a whole table per launch.  The table owns aux (alpha and the sigmoids of every row: written forward, read
-    backward) and the partial sums of the parameter gradients."""
+    backward; [rows, 8] per entry in aux_of: alpha_L alpha_H alpha_I s_L s_H s_I 0 0) and the partial sums of the parameter gradients."""
 
-    MAX_COLS, MAX_JOBS, TILE = 256, 65535, 64
+    MAX_COLS = 256
+    _DTYPE, _FORWARD, _BACKWARD = _ACM_JOB_DTYPE, "wdg_acm_mix_batched_f32", "wdg_acm_mix_backward_batched_f32"
+    _EXTRA, _REQUIRED = ("out_t",), ("low", "high", "ident", "att", "wmix", "out")
 
     def __init__(self, entries, relu):
         """entries: list of dicts of fp32 device tensors -
@@ -193,81 +293,17 @@ class AcmMixBatch:
            - all six or none.  relu: the activation flag of every entry (one bool, or one per entry).
         Raises for what the kernel does not take: cols outside 1..256, other dtypes, shapes or strides, more than 65535 entries, an
         output that overlaps an input or another output of its entry."""
-        self.keep = entries
-        n = self.n_jobs = len(entries)
-        if n > self.MAX_JOBS:
-            raise ValueError(f"AcmMixBatch: {n} entries; one launch takes {self.MAX_JOBS}")
-        flags = [bool(relu)] * n if np.ndim(relu) == 0 else [bool(f) for f in relu]
-        if len(flags) != n:
-            raise ValueError("AcmMixBatch: one activation flag per entry")
-        mats = ("low", "high", "high_agg", "ident", "out", "d_out", "d_low", "d_high", "d_ident")
-        grads = ("d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
-        self.has_backward = n > 0
-        for e in entries:
-            unknown = set(e) - set(mats) - {"att", "wmix", "out_t", "d_att", "d_wmix"}
-            if unknown:
-                raise ValueError(f"AcmMixBatch: unknown keys {sorted(unknown)}")
-            if any(e.get(k) is None for k in ("low", "high", "ident", "att", "wmix", "out")):
-                raise ValueError("AcmMixBatch: low, high, ident, att, wmix and out are required")
-            rows, cols = e["low"].shape if isinstance(e["low"], torch.Tensor) and e["low"].dim() == 2 else (-1, -1)
-            if not 1 <= cols <= self.MAX_COLS:
-                raise ValueError(f"AcmMixBatch: a layer of {cols} columns; the kernel holds 1..{self.MAX_COLS}")
-            given = [k for k in grads if e.get(k) is not None]
-            if given and len(given) != len(grads):
-                raise ValueError("AcmMixBatch: d_out, d_low, d_high, d_ident, d_att and d_wmix come together or not at all")
-            self.has_backward = self.has_backward and bool(given)
-            for k in mats:
-                if e.get(k) is not None:
-                    _check_matrix("AcmMixBatch", k, e[k], (rows, cols))
-            for k, shape in (("att", (3, cols)), ("wmix", (3, 3)), ("d_att", (3, cols)), ("d_wmix", (3, 3))):
-                t = e.get(k)
-                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
-                                      or tuple(t.shape) != shape or not t.is_contiguous()):
-                    raise ValueError(f"AcmMixBatch: {k} must be a contiguous {list(shape)} fp32 device tensor")
-            if e.get("out_t") is not None:
-                _check_matrix("AcmMixBatch", "out_t", e["out_t"], (cols, rows))
-            outputs = ("out", "out_t", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
-            given = [(k, t) for k, t in e.items() if t is not None]
-            for i, (ka, ta) in enumerate(given):
-                for kb, tb in given[i + 1:]:
-                    if (ka in outputs or kb in outputs) and _views_may_overlap(ta, tb):
-                        raise ValueError(f"AcmMixBatch: {ka} and {kb} overlap; an output must not overlap an input or another output")
-        dev = require_gpu()  # (after the checks that need no device)
-        rows = np.fromiter((e["low"].shape[0] for e in entries), np.int64, n)
-        cols = np.fromiter((e["low"].shape[1] for e in entries), np.int64, n)
-        self.max_rows, self.max_cols = int(rows.max(initial=0)), int(cols.max(initial=0))
-        self.aux = torch.zeros((max(int(rows.sum()), 1), 8), dtype=torch.float32, device=dev)
-        row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-        plen = -(-rows // self.TILE) * (3 * cols + 9)
-        part_off = np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)
-        self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
-        tab = np.zeros(n, _ACM_JOB_DTYPE)
-        for i, e in enumerate(entries):
-            for k in ("low", "high", "high_agg", "ident", "att", "wmix", "out", "out_t", "d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix"):
-                t = e.get(k)
-                tab[k][i] = 0 if t is None else t.data_ptr()
-                if "ld_" + k in _ACM_JOB_DTYPE.names:
-                    tab["ld_" + k][i] = 0 if t is None else _ld(t)
-        tab["aux"] = self.aux.data_ptr() + 32 * row_off[:-1]
-        if self.has_backward:
-            tab["partials"] = self.partials.data_ptr() + 4 * part_off[:-1]
-        tab["rows"], tab["cols"], tab["flags"] = rows, cols, np.asarray(flags, np.int64)
-        self.aux_of = [self.aux[row_off[i]:row_off[i + 1]] for i in range(n)]  # [rows, 8] per entry: alpha_L alpha_H alpha_I s_L s_H s_I 0 0
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        super().__init__(entries, relu)
+        self.max_cols = self._widest
 
-    def launch(self):
-        """out (and out_t, aux) of every entry"""
-        check(lib.wdg_acm_mix_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()), "wdg_acm_mix_batched_f32")
-
-    def launch_backward(self):
-        """d_low, d_high, d_ident, d_att, d_wmix of every entry from d_out, the inputs and the aux of the last launch()"""
-        if not self.has_backward and self.n_jobs:
-            raise ValueError("AcmMixBatch.launch_backward: the table was built without gradient tensors")
-        check(lib.wdg_acm_mix_backward_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()),
-              "wdg_acm_mix_backward_batched_f32")
+    def _shape(self, e):
+        rows, cols = e["low"].shape if isinstance(e["low"], torch.Tensor) and e["low"].dim() == 2 else (-1, -1)
+        if not 1 <= cols <= self.MAX_COLS:
+            raise ValueError(f"AcmMixBatch: a layer of {cols} columns; the kernel holds 1..{self.MAX_COLS}")
+        return rows, cols, {"att": ((3, cols),), "wmix": ((3, 3),)}, dict(rows=rows, cols=cols), (rows, 8), 3 * cols + 9
 
 
-class AcmMixPackedBatch:
+class AcmMixPackedBatch(_AcmMixTable):
     """Job table for wdg_acm_mix_packed_f32 / wdg_acm_mix_packed_backward_f32 (csrc/acm_mix_packed.hip): the channel mix of AcmMixBatch
     for STACKED narrow layers - an entry is one [rows, reps stride] layer of `reps` replicas of `cols` real columns each, stride 4, 8
     or 16 floats between replicas; replica p owns columns p stride .. p stride + cols - 1 of every operand.  A replica's results are,
@@ -275,7 +311,9 @@ class AcmMixPackedBatch:
     are written +0 and those of the inputs are never used.  The table owns aux ([rows, reps, 8] per entry in aux_of) and the
     partial sums of the parameter gradients."""
 
-    STRIDES, MAX_JOBS, TILE = (4, 8, 16), 65535, 64
+    STRIDES = (4, 8, 16)
+    _DTYPE, _FORWARD, _BACKWARD = _ACM_PACKED_JOB_DTYPE, "wdg_acm_mix_packed_f32", "wdg_acm_mix_packed_backward_f32"
+    _EXTRA, _REQUIRED = ("cols",), ("cols", "low", "high", "ident", "att", "wmix", "out")
 
     def __init__(self, entries, relu):
         """entries: list of dicts - cols (int), att [reps, 3, stride] and wmix [reps, 3, 3] or [reps, 9] (fp32 device, contiguous: reps
@@ -285,92 +323,45 @@ class AcmMixPackedBatch:
            Every tensor starts at a 16-byte boundary.  relu: the activation flag of every entry (one bool, or one per entry).
         Raises ValueError for a stride outside {4, 8, 16}, cols outside 1..stride, other dtypes, shapes or strides, misaligned
         tensors, more than 65535 entries, an output that overlaps an input or another output of its entry."""
-        name = "AcmMixPackedBatch"
-        self.keep = entries
-        n = self.n_jobs = len(entries)
-        if n > self.MAX_JOBS:
-            raise ValueError(f"{name}: {n} entries; one launch takes {self.MAX_JOBS}")
-        flags = [bool(relu)] * n if np.ndim(relu) == 0 else [bool(f) for f in relu]
-        if len(flags) != n:
-            raise ValueError(f"{name}: one activation flag per entry")
-        mats = ("low", "high", "high_agg", "ident", "out", "d_out", "d_low", "d_high", "d_ident")
-        grads = ("d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
-        self.has_backward = n > 0
-        shapes = []
-        for e in entries:
-            unknown = set(e) - set(mats) - {"att", "wmix", "d_att", "d_wmix", "cols"}
-            if unknown:
-                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
-            if any(e.get(k) is None for k in ("low", "high", "ident", "att", "wmix", "out", "cols")):
-                raise ValueError(f"{name}: cols, low, high, ident, att, wmix and out are required")
-            att = e["att"]
-            if not isinstance(att, torch.Tensor) or att.dim() != 3 or att.shape[1] != 3 or att.shape[0] < 1:
-                raise ValueError(f"{name}: att must be a [reps >= 1, 3, stride] tensor")
-            reps, stride, cols = att.shape[0], att.shape[2], int(e["cols"])
-            if stride not in self.STRIDES:
-                raise ValueError(f"{name}: a replica stride of {stride} floats; the kernel takes 4, 8 or 16")
-            if not 1 <= cols <= stride:
-                raise ValueError(f"{name}: {cols} columns in a replica stride of {stride}; 1..{stride} expected")
-            rows = e["low"].shape[0] if isinstance(e["low"], torch.Tensor) and e["low"].dim() == 2 else -1
-            given = [k for k in grads if e.get(k) is not None]
-            if given and len(given) != len(grads):
-                raise ValueError(f"{name}: d_out, d_low, d_high, d_ident, d_att and d_wmix come together or not at all")
-            self.has_backward = self.has_backward and bool(given)
-            for k in mats:
-                if e.get(k) is not None:
-                    _check_matrix(name, k, e[k], (rows, reps * stride))
-                    if e[k].data_ptr() % 16 or (rows > 1 and _ld(e[k]) % 4):
-                        raise ValueError(f"{name}: {k} must start at a 16-byte boundary and have a leading dimension that is a multiple of 4")
-            for k, ok in (("att", ((reps, 3, stride),)), ("wmix", ((reps, 3, 3), (reps, 9))), ("d_att", ((reps, 3, stride),)),
-                          ("d_wmix", ((reps, 3, 3), (reps, 9)))):
-                t = e.get(k)
-                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
-                                      or tuple(t.shape) not in ok or not t.is_contiguous()):
-                    raise ValueError(f"{name}: {k} must be a contiguous {list(ok[0])} fp32 device tensor")
-                if t is not None and k in ("att", "d_att") and t.data_ptr() % 16:
-                    raise ValueError(f"{name}: {k} must start at a 16-byte boundary")
-            outputs = ("out", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
-            given = [(k, t.reshape(t.shape[0], -1) if t.dim() == 3 else t) for k, t in e.items() if isinstance(t, torch.Tensor)]
-            for i, (ka, ta) in enumerate(given):
-                for kb, tb in given[i + 1:]:
-                    if (ka in outputs or kb in outputs) and _views_may_overlap(ta, tb):
-                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
-            shapes.append((rows, reps, cols, stride))
-        dev = require_gpu()  # (after the checks that need no device)
-        rows, reps, cols, stride = (np.fromiter((s_[k] for s_ in shapes), np.int64, n) for k in range(4))
-        self.max_rows, self.max_width = int(rows.max(initial=0)), int((reps * stride).max(initial=0))
-        aux_len = rows * reps * 8
-        aux_off = np.concatenate([[0], np.cumsum(aux_len)]).astype(np.int64)
-        self.aux = torch.zeros(max(int(aux_off[-1]), 1), dtype=torch.float32, device=dev)
-        plen = -(-rows // self.TILE) * reps * (3 * stride + 12)
-        part_off = np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)
-        self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
-        tab = np.zeros(n, _ACM_PACKED_JOB_DTYPE)
-        for i, e in enumerate(entries):
-            for k in ("low", "high", "high_agg", "ident", "att", "wmix", "out", "d_out", "d_low", "d_high", "d_ident", "d_att", "d_wmix"):
-                t = e.get(k)
-                tab[k][i] = 0 if t is None else t.data_ptr()
-                if "ld_" + k in _ACM_PACKED_JOB_DTYPE.names:
-                    tab["ld_" + k][i] = 0 if t is None else max(_ld(t), t.shape[1])
-        tab["aux"] = self.aux.data_ptr() + 4 * aux_off[:-1]
-        if self.has_backward:
-            tab["partials"] = self.partials.data_ptr() + 4 * part_off[:-1]
-        tab["rows"], tab["reps"], tab["cols"], tab["stride"], tab["flags"] = rows, reps, cols, stride, np.asarray(flags, np.int64)
-        self.aux_of = [self.aux[aux_off[i]:aux_off[i + 1]].view(int(rows[i]), int(reps[i]), 8) for i in range(n)]
-        host = np.ascontiguousarray(tab)
-        check(lib.wdg_acm_mix_packed_check_jobs(ctypes.c_void_p(host.ctypes.data), n), "wdg_acm_mix_packed_check_jobs")
-        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        super().__init__(entries, relu)
+        self.max_width = self._widest
 
-    def launch(self):
-        """out and aux of every entry"""
-        check(lib.wdg_acm_mix_packed_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_width, stream_handle()), "wdg_acm_mix_packed_f32")
+    def _shape(self, e):
+        name, att = "AcmMixPackedBatch", e["att"]
+        if not isinstance(att, torch.Tensor) or att.dim() != 3 or att.shape[1] != 3 or att.shape[0] < 1:
+            raise ValueError(f"{name}: att must be a [reps >= 1, 3, stride] tensor")
+        reps, stride, cols = att.shape[0], att.shape[2], int(e["cols"])
+        if stride not in self.STRIDES:
+            raise ValueError(f"{name}: a replica stride of {stride} floats; the kernel takes 4, 8 or 16")
+        if not 1 <= cols <= stride:
+            raise ValueError(f"{name}: {cols} columns in a replica stride of {stride}; 1..{stride} expected")
+        rows = e["low"].shape[0] if isinstance(e["low"], torch.Tensor) and e["low"].dim() == 2 else -1
+        return (rows, reps * stride, {"att": ((reps, 3, stride),), "wmix": ((reps, 3, 3), (reps, 9))},
+                dict(rows=rows, reps=reps, cols=cols, stride=stride), (rows, reps, 8), reps * (3 * stride + 12))
 
-    def launch_backward(self):
-        """d_low, d_high, d_ident, d_att, d_wmix of every entry from d_out, the inputs and the aux of the last launch()"""
-        if not self.has_backward and self.n_jobs:
-            raise ValueError("AcmMixPackedBatch.launch_backward: the table was built without gradient tensors")
-        check(lib.wdg_acm_mix_packed_backward_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_width, stream_handle()),
-              "wdg_acm_mix_packed_backward_f32")
+    def _check_alignment(self, k, t, rows):
+        if k in self._MATS and (t.data_ptr() % 16 or (rows > 1 and _ld(t) % 4)):
+            raise ValueError(f"AcmMixPackedBatch: {k} must start at a 16-byte boundary and have a leading dimension that is a multiple of 4")
+        if k in ("att", "d_att") and t.data_ptr() % 16:
+            raise ValueError(f"AcmMixPackedBatch: {k} must start at a 16-byte boundary")
+
+    def _check_jobs(self, host):
+        check(lib.wdg_acm_mix_packed_check_jobs(ctypes.c_void_p(host.ctypes.data), self.n_jobs), "wdg_acm_mix_packed_check_jobs")
+
+
+def acm_operand_gradient(d_pair, t_pair, d_full, width):
+    """d(M W) = [A_hat^T dP_L | dP_H - A_hat^T dP_H | dP_I] from d_pair = [dP_L | dP_H] and t_pair = A_hat^T d_pair (the kernel has
+    written dP_I into the third channel of d_full already); [n, .] matrices, or [J, n, .] stacks of them"""
+    d_full[..., :width].copy_(t_pair[..., :width])
+    torch.sub(d_pair[..., width:], t_pair[..., width:], out=d_full[..., width:2 * width])
+
+
+def acm_sgc_weight_gradient(g, gwa, gwb, w):
+    """dW = [Y^T d_low | X^T d_high - Y^T d_high | X^T d_ident] into g from gwa = Y^T [d_low | -d_high] and gwb = X^T [d_high | d_ident]
+    (channels of w columns; [F, .] matrices, or [J, F, .] stacks of them)"""
+    g[..., :w].copy_(gwa[..., :w])
+    torch.add(gwa[..., w:], gwb[..., :w], out=g[..., w:2 * w])
+    g[..., 2 * w:].copy_(gwb[..., w:])
 
 
 class XentEvalBatch:

@@ -4,6 +4,7 @@ import time
 import torch
 
 from ._rt import capture_graphs, snapshot
+from .train import acm_operand_gradient, acm_sgc_weight_gradient
 
 
 class TrainBatch:
@@ -214,13 +215,6 @@ class TrainBatch:
                         bwd_spmm(self.dg1, self.t1),
                         ops.GemmBatch([(xt[jobs[j].seed], self.dxw[j], self.w0.grad[j], None) for j in range(J)])]  # dW0 = X^T d(X W0)
 
-    @staticmethod
-    def _acm_operand_gradient(d_pair, t_pair, d_full, width):
-        """d(M W) = [A_hat^T dP_L | dP_H - A_hat^T dP_H | dP_I] from d_pair = [dP_L | dP_H] and t_pair = A_hat^T d_pair (the kernel has
-        written dP_I into the third block of d_full already)"""
-        d_full[..., :width].copy_(t_pair[..., :width])
-        torch.sub(d_pair[..., width:], t_pair[..., width:], out=d_full[..., width:2 * width])
-
     def _acm_backward(self):
         """the backward launches behind dlogits for the logits of the last _forward()"""
         c, h = self.c, self.h
@@ -229,21 +223,18 @@ class TrainBatch:
             torch.neg(self.dxb[..., :c], out=self.dya[..., c:])  # d(high_agg) = -d_high
             self.bwd[0].launch()
             self.bwd[1].launch()
-            g = self.w.grad  # dW = [Y^T d_low | X^T d_high - Y^T d_high | X^T d_ident]
-            g[..., :c].copy_(self.gwa[..., :c])
-            torch.add(self.gwa[..., c:], self.gwb[..., :c], out=g[..., c:2 * c])
-            g[..., 2 * c:].copy_(self.gwb[..., c:])
+            acm_sgc_weight_gradient(self.w.grad, self.gwa, self.gwb, c)
             return
         self.mix[1].launch_backward()
         self.bwd[0].launch()
-        self._acm_operand_gradient(self.dg2, self.t2, self.dhw, c)
+        acm_operand_gradient(self.dg2, self.t2, self.dhw, c)
         self.bwd[1].launch()
         self.w1t.copy_(self.w1.data.transpose(1, 2))
         self.bwd[2].launch()
         self._mask_hidden_gradient()
         self.mix[0].launch_backward()
         self.bwd[3].launch()
-        self._acm_operand_gradient(self.dg1, self.t1, self.dxw, h)
+        acm_operand_gradient(self.dg1, self.t1, self.dxw, h)
         self.bwd[4].launch()
 
     # -- one epoch ---------------------------------------------------------------------------------------------
