@@ -1279,6 +1279,82 @@ int wdg_adam_batched_f32(const wdg_adam_job *jobs_dev, int32_t n_jobs, int32_t m
 /* replaces: nothing of its own - the per-job refusals of the optimiser step above (gnns_on_syn.py:109-154), on the host's table */
 int wdg_adam_check_jobs(const wdg_adam_job *jobs_host, int32_t n_jobs);
 
+/*
+ * Keep the selected model of a stacked run: copy, of every tensor of a table, exactly the segments of the replicas whose best epoch
+ * is the CURRENT step, in one launch - the parameters and the logits of a replica at its best validation epoch stay behind in `dst`
+ * while the run goes on, with no host in the epoch.  A job is one TENSOR (wdg_adam_batched_f32's convention), not one replica.
+ * replaces: the bookkeeping of the training loops behind the accuracy tables gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249 (the
+ *           loop itself lives upstream of the reference, where it keeps the selected model) - what wdg_xent_eval_batched_f32 cites.
+ * The definition, for element (i, j) of a job:
+ *   s = (i / seg_rows) * ceil(cols / seg_cols) + j / seg_cols     (integer divisions: wdg_adam_batched_f32's rule; the last segment of
+ *                                                                  a row or of the tensor may be ragged)
+ *   r = s % reps                                                  (the channel-major ACM weights [F, 3 R w] are one job: 3 R segments)
+ *   t = *step_dev, read from DEVICE memory when the kernel runs
+ *   dst[i][j] = src[i][j]   iff   best[3 r] >= 0 && best[3 r + 2] == t
+ * The copy is of the 32-bit word: NaN payloads and the sign of zero survive.  Every other element of dst is neither read nor
+ * written, and the src elements of unselected segments are not loaded; nothing outside columns 0 .. cols - 1 of a row is touched.
+ * PRECONDITION: the launch comes after the WDG_XENT_EVAL call of the same step and before the step word advances.  That call writes
+ * best[r][2] = *step_dev exactly for the replicas whose validation hits improved; every step recorded earlier is smaller, and the
+ * first selection always improves on -1 - so "best[r][2] == t" means "replica r was selected in this step".
+ * Access width, per job: 16-byte accesses when src and dst are 16-byte aligned and seg_cols, ld_src and ld_dst are multiples of 4
+ * (four adjacent columns then share a segment); word by word otherwise and at a ragged right edge.  Both paths move the same bits.
+ * No LDS, no atomics: an element depends on its own source word, its replica's two numbers and t; a job's result does not depend on
+ * the table it is in, and two launches from the same inputs give the same bits.
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, a NULL step_dev, negative counts, more than 65535
+ * jobs (a job per grid z), more than 64 * 65535 columns (a tile per grid y).  These come FIRST, in this order of precedence: a NULL
+ * step_dev is refused even when n_jobs == 0 (wdg_adam_batched_f32's order); only then n_jobs == 0: WDG_OK, nothing is launched; a NULL
+ * table is looked at after that (n_jobs > 0 only).  The table
+ * lives in device memory, so what is wrong inside a job - seg_rows, seg_cols or reps below 1, ld_src or ld_dst below cols, a NULL
+ * pointer, src and dst that overlap (their byte ranges intersect, unless both have one leading dimension and their column ranges
+ * are disjoint inside it: column ranges of one wider matrix) - makes the kernel SKIP the job, and wdg_keep_best_check_jobs applies
+ * the same predicate to the HOST copy of the table (ops.KeepBestBatch calls it before it uploads; no HIP call either).  A job of 0
+ * rows or 0 columns is skipped; rows beyond max_rows (the table's largest) are left untouched, and so is a job of more than max_cols
+ * columns.  No two jobs may share an element of a dst.
+ */
+typedef struct wdg_keep_job {
+    const float *src; float *dst; /* [rows, cols], leading dimensions ld_src / ld_dst */
+    const int32_t *best;      /* [reps, 3], wdg_xent_job.best */
+    int64_t ld_src, ld_dst;
+    int32_t rows, cols, seg_rows, seg_cols, reps, reserved;
+} wdg_keep_job;
+int wdg_keep_best_batched_f32(const wdg_keep_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
+                              const int32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the conditional copy above (gnns_on_syn.py:109-154), on the host's table */
+int wdg_keep_best_check_jobs(const wdg_keep_job *jobs_host, int32_t n_jobs);
+
+/*
+ * Predictions and confusion counts of many models whose logits are STACKED along the feature axis (wdg_xent_eval_batched_f32's
+ * layout: replica r's classes are columns r cs .. r cs + C - 1 of one [n, R cs] matrix), per replica and per part of its split.
+ * replaces: the accuracy of utils/util_funcs.py:393 taken apart by class - the per-class view of the models the accuracy tables
+ *           gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249 train (the loop itself lives upstream of the reference).
+ * The definition, for row i and replica r of a job, with z_k = logits[i][r cs + k], k = 0 .. C - 1 (tests/_confusion_ref.py restates it):
+ *   pred = the first k with z_k == max_k z_k - exactly WDG_XENT_EVAL's prediction; a NaN among the z's gives no prediction.
+ *   pred[i][r] = pred, or 255 for none (where the job has a pred matrix) - for EVERY row, whatever its split code and label.
+ *   if s = split[i][r] is in 1 .. 3 and y = labels[i] is in 0 .. C - 1:   counts[r][s - 1][y][pred, or C for none] += 1
+ *   a row with split code 0 (or above 3) or a label out of range is not counted.
+ * The counts are ADDED to what `counts` holds (the front end zeroes its pool before the launch).  They are integers: counted per
+ * workgroup in LDS, then one integer add per workgroup and non-zero counter.  No floating-point atomics: two runs are bit-identical,
+ * and a replica's counts do not depend on which other replicas or jobs are in the table.  The padding columns C .. cs - 1 of the
+ * logits are never read; nothing beyond column R cs of a row is read.
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs (a job per
+ * grid z).  max_cols names the table's largest C: more than 16 classes is WDG_ERR_UNSUPPORTED.  n_jobs == 0: WDG_OK, nothing is
+ * launched.  A job with n == 0 or R == 0 is skipped, and so is one whose own C lies outside 1 .. 16, whose cs < C, whose ld_logits
+ * is below R cs or whose logits, labels, split or counts pointer is NULL; wdg_confusion_check_jobs refuses such a job (other than
+ * an empty one) on the HOST copy of the table.  Rows beyond max_rows (the table's largest n) are left untouched.
+ */
+typedef struct wdg_confusion_job {
+    const float *logits;      /* [n, R*cs] fp32, leading dimension ld_logits */
+    const int32_t *labels;    /* [n], shared by the replicas */
+    const uint8_t *split;     /* [n, R] row-major: 0 unused, 1 train, 2 validation, 3 test */
+    int32_t *counts;          /* [R, 3, C, C+1] in/out: part (train, validation, test), true class, predicted class (C: none) */
+    uint8_t *pred;            /* [n, R] or NULL: the prediction, 255 for none */
+    int64_t ld_logits;
+    int32_t n, R, C, cs;
+} wdg_confusion_job;
+int wdg_confusion_batched_i32(const wdg_confusion_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the confusion counts above (utils/util_funcs.py:393), on the host's table */
+int wdg_confusion_check_jobs(const wdg_confusion_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,10 @@ SIGNATURES = {
     "wdg_xent_eval_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "wdg_adam_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
     "wdg_adam_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_keep_best_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "wdg_keep_best_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_confusion_batched_i32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_confusion_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -320,6 +324,18 @@ class AdamJob(ctypes.Structure):
     """mirror of `wdg_adam_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("p", "g", "m", "v", "hyper")] + \
                [("ld", c_int64), ("ld_s", c_int64), ("rows", c_int32), ("cols", c_int32), ("seg_rows", c_int32), ("seg_cols", c_int32)]
+
+
+class KeepJob(ctypes.Structure):
+    """mirror of `wdg_keep_job` (include/wdg.h)"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("best", c_void_p), ("ld_src", c_int64), ("ld_dst", c_int64)] + \
+               [(name, c_int32) for name in ("rows", "cols", "seg_rows", "seg_cols", "reps", "reserved")]
+
+
+class ConfusionJob(ctypes.Structure):
+    """mirror of `wdg_confusion_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("logits", "labels", "split", "counts", "pred")] + \
+               [("ld_logits", c_int64), ("n", c_int32), ("R", c_int32), ("C", c_int32), ("cs", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

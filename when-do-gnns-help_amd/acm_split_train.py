@@ -64,11 +64,11 @@ class AcmSplitTrainBatch(SplitTrainBatch):
     MAX_HIDDEN = AcmMixBatch.MAX_COLS
 
     def __init__(self, adj, x, labels, masks, kind="acm_gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
-                 dropout_seed=None, replica_ids=None):
+                 dropout_seed=None, replica_ids=None, *, keep_best=False):
         who = "AcmSplitTrainBatch"
         if kind not in self.KINDS:
             raise ValueError(f"{who}: unknown model kind {kind!r} (one of {self.KINDS}; {SplitTrainBatch.KINDS} are SplitTrainBatch's)")
-        self.kind, self.optimizer, self.two_layer = kind, "torch", kind == "acm_gcn"
+        self.kind, self.optimizer, self.two_layer, self.keep_best = kind, "torch", kind == "acm_gcn", bool(keep_best)
         if any(np.ndim(v) > 0 for v in (lr, weight_decay, dropout)):
             raise ValueError(f"{who}: one lr, one weight_decay and one dropout for all replicas expected")
         self.dropout = float(dropout)
@@ -165,6 +165,17 @@ class AcmSplitTrainBatch(SplitTrainBatch):
 
     _class_stride = staticmethod(class_stride)
 
+    def _segments(self, tensors):
+        """SplitTrainBatch._segments for the channel-major layout (segment s belongs to replica s % R):
+            w, w0 [F, 3 R w]: seg_rows = F, seg_cols = cs | hidden - 3 R column blocks, block (c, r) = segment c R + r
+            att* [R, 3, w] as [3 R, w]: seg_rows = 3;   wmix* [R, 3, 3] as [R, 9]: a row;   w1 [R, hidden, 3 cs] as [R hidden, 3 cs]: seg_rows = hidden"""
+        R, f, h, cs = self.R, self.f, self.h, self.cs
+        layer = lambda w, att, wmix, width: [(w, f, width), (att.view(3 * R, width), 3, width), (wmix.view(R, 9), 1, 9)]  # noqa: E731
+        if not self.two_layer:
+            return layer(*tensors, cs)
+        w0, att0, wmix0, w1, att1, wmix1 = tensors
+        return layer(w0, att0, wmix0, h) + [(w1.view(R * h, 3 * cs), h, 3 * cs), (att1.view(3 * R, cs), 3, cs), (wmix1.view(R, 9), 1, 9)]
+
     def set_hyper(self, lr, weight_decay):
         raise ValueError("AcmSplitTrainBatch.set_hyper: the run steps with torch's Adam (one rate per tensor)")
 
@@ -217,16 +228,16 @@ class AcmSplitTrainBatch(SplitTrainBatch):
         """[W_L | W_H | W_I] of replica r ([F, 3 cols], a copy: the stacked matrix is channel-major)"""
         return t.view(t.shape[0], 3, self.R, width)[:, :, r, :cols].reshape(t.shape[0], 3 * cols)
 
-    def weights_of(self, r, grad=False):
-        """replica r's parameters (or their gradients) without the padding columns, in the order of its model's parameters:
+    def weights_of(self, r, grad=False, kept=False):
+        """replica r's parameters (or their gradients; kept=True: their kept copies) without the padding columns, in the order of its model's parameters:
         (weight, att, wmix) or (w0, att0, wmix0, w1, att1, wmix1); the weight matrices are copies, [W_L | W_H | W_I]"""
         c, cs, h = self.c, self.cs, self.h
-        pick = (lambda p: p.grad) if grad else (lambda p: p.data)
         if not self.two_layer:
-            return self._first_layer_block(pick(self.w), r, cs, c), pick(self.att)[r, :, :c], pick(self.wmix)[r]
-        w1 = pick(self.w1)[r].view(h, 3, cs)[:, :, :c].reshape(h, 3 * c)
-        return (self._first_layer_block(pick(self.w0), r, h, h), pick(self.att0)[r], pick(self.wmix0)[r],
-                w1, pick(self.att1)[r, :, :c], pick(self.wmix1)[r])
+            w, att, wmix = self._tensors(grad, kept)
+            return self._first_layer_block(w, r, cs, c), att[r, :, :c], wmix[r]
+        w0, att0, wmix0, w1, att1, wmix1 = self._tensors(grad, kept)
+        return (self._first_layer_block(w0, r, h, h), att0[r], wmix0[r],
+                w1[r].view(h, 3, cs)[:, :, :c].reshape(h, 3 * c), att1[r, :, :c], wmix1[r])
 
     def _empty_model(self, models, p, rng):
         """replica_model()'s module: a models.ACMGCN2 / ACMSGC1"""

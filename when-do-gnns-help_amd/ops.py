@@ -17,7 +17,9 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         AcmMixPackedBatch (the same mix for stacked class-width layers: 1, 2 or 4 lanes per replica),
                         XentEvalBatch (cross-entropy gradient, hits and model selection of many models with stacked logits),
                         AdamBatch (the Adam step of a stacked run's parameter tensors in one launch: a learning rate and a weight
-                        decay per replica in device memory, the step count read from the run's step word)
+                        decay per replica in device memory, the step count read from the run's step word),
+                        KeepBestBatch (the copy of every replica's parameters and logits at its best epoch, selected on the device),
+                        ConfusionBatch (predictions and per-split confusion counts of stacked logits)
   split_train.py        SplitTrainBatch (all splits of ONE graph trained as a single stacked run; reached as ops.SplitTrainBatch;
                         optimizer="device": per-replica lr / weight_decay / dropout), grid_search (a hyperparameter grid over all
                         splits as stacked chunks), select_settings
@@ -47,11 +49,11 @@ from .stats import (  # noqa: F401
 from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
-from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, DropoutBatch, HeadTrainBatch, XentEvalBatch, XENT_EVAL, XENT_GRAD  # noqa: F401
+from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, ConfusionBatch, DropoutBatch, HeadTrainBatch, KeepBestBatch, XentEvalBatch, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .synth import regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, expand_features, feature_image_floats, FeatureExpand, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
     deflation_enabled, EdgeGramBatch, GnbBatch, GramBatch, kr_split_sizes, KrBatch, KrSets, PropagatedGram, RowRepBatch, SvmBatch, _KR_JOB_DTYPE,
 )
-from .split_train import grid_search, masks_from_indices, random_masks, select_settings, SplitTrainBatch  # noqa: E402,F401  (last: it builds on the modules above)
+from .split_train import classification_report, grid_search, masks_from_indices, prediction_overlap, random_masks, select_settings, SplitTrainBatch  # noqa: E402,F401  (last: it builds on the modules above)
 from .acm_split_train import AcmSplitTrainBatch  # noqa: E402,F401

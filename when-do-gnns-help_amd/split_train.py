@@ -29,7 +29,7 @@ from ._lib import require_gpu
 from ._rt import _dev, capture_graphs, snapshot
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
-from .train import XENT_EVAL, XENT_GRAD, AdamBatch, DropoutBatch, XentEvalBatch, dropout_constants
+from .train import XENT_EVAL, XENT_GRAD, AdamBatch, ConfusionBatch, DropoutBatch, KeepBestBatch, XentEvalBatch, dropout_constants
 
 MAX_CLASSES = XentEvalBatch.MAX_C
 
@@ -133,18 +133,23 @@ class SplitTrainBatch:
     refused - a torch parameter group has one rate per tensor.  With a dropout sequence the replicas are grouped by drop probability,
     ascending, one DropoutBatch per group (self.drops); self.dropout is then the largest of them.
     replica_ids: R non-negative integers that stand for r in replica_seed(seed, r) and as the dropout stream (default: range(R)).
-    Replicas with one id start from the same weights and, with one drop probability, draw the same masks."""
+    Replicas with one id start from the same weights and, with one drop probability, draw the same masks.
+
+    keep_best=True: the run also owns kept_params (one tensor per entry of self.params, of its shape) and kept_logits
+    [n, R cs], zeros at first, and every epoch's evaluation is followed by one ops.KeepBestBatch launch that copies, on the device,
+    the parameter blocks and the logits of exactly the replicas whose best epoch is this one.  best_weights_of(r), best_logits_of(r),
+    best_model(r), predictions() and confusion() read them; the parameters, `best` and run()'s dictionary are what they are without it."""
 
     KINDS = ("sgc", "gcn", "mlp1", "mlp2")
     OPTIMIZERS = ("torch", "device")
 
     def __init__(self, adj, x, labels, masks, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
-                 dropout_seed=None, *, optimizer="torch", replica_ids=None):
+                 dropout_seed=None, *, optimizer="torch", replica_ids=None, keep_best=False):
         if kind not in self.KINDS:
             raise ValueError(f"SplitTrainBatch: unknown model kind {kind!r} (one of {self.KINDS}; the ACM kinds are sweep.TrainBatch's)")
         if optimizer not in self.OPTIMIZERS:
             raise ValueError(f"SplitTrainBatch: unknown optimizer {optimizer!r} (one of {self.OPTIMIZERS})")
-        self.kind, self.optimizer = kind, optimizer
+        self.kind, self.optimizer, self.keep_best = kind, optimizer, bool(keep_best)
         self.two_layer = kind in ("gcn", "mlp2")
         per_replica = {name: np.ndim(val) > 0 for name, val in (("lr", lr), ("weight_decay", weight_decay), ("dropout", dropout))}
         if optimizer != "device" and any(per_replica.values()):
@@ -251,15 +256,32 @@ class SplitTrainBatch:
         if self.optimizer == "torch":
             self.opt, self.adam = torch.optim.Adam(self.params, lr=self.lr, weight_decay=self.weight_decay, capturable=True, fused=True), None
         else:
-            # ops.AdamBatch: one job per parameter tensor, a replica = a segment (a column block of w0 / w, a row block of w1)
-            R, f, h, cs = self.R, self.f, self.h, self.cs
+            # ops.AdamBatch: one job per parameter tensor, a replica = a segment (_segments() states them)
             hyper = np.stack([self.lrs, self.weight_decays], 1).astype(np.float32)
-            if self.two_layer:
-                entries = [(self.w0.data, self.w0.grad, f, h, hyper), (self.w1.data.view(R * h, cs), self.w1.grad.view(R * h, cs), h, cs, hyper)]
-            else:
-                entries = [(self.w.data, self.w.grad, f, cs, hyper)]
-            self.opt, self.adam = None, AdamBatch(entries)
+            grads = self._segments([p.grad for p in self.params])
+            self.opt, self.adam = None, AdamBatch([(p, g, seg_rows, seg_cols, hyper) for (p, seg_rows, seg_cols), (g, _, _) in
+                                                   zip(self._segments([p.data for p in self.params]), grads)])
+        self.kept_params = self.kept_logits = self.keeper = self._confusion = None
+        if self.keep_best:
+            # the selected model: zeros until a replica has a best epoch; one job per parameter tensor plus one for the logits
+            self.kept_params = [torch.zeros_like(p.data) for p in self.params]
+            self.kept_logits = torch.zeros_like(self.logits)
+            kept = self._segments(self.kept_params)
+            entries = [(p, k, seg_rows, seg_cols, self.R, self.best) for (p, seg_rows, seg_cols), (k, _, _) in
+                       zip(self._segments([p.data for p in self.params]), kept)]
+            self.keeper = KeepBestBatch(entries + [(self.logits, self.kept_logits, max(self.n, 1), self.cs, self.R, self.best)])
         self.graph = None
+
+    def _segments(self, tensors):
+        """the segment description of the stacked parameters, stated once: `tensors` - one per entry of self.params and of its shape
+        (the parameters' data, their gradients, the kept copies) -> [(2-D view, seg_rows, seg_cols)], where element (i, j) of a view
+        belongs to segment (i // seg_rows) * ceil(cols / seg_cols) + j // seg_cols and segment s to replica s % R:
+        a replica = a column block of w0 / w, a row block of w1 [R hidden, cs]"""
+        R, f, h, cs = self.R, self.f, self.h, self.cs
+        if self.two_layer:
+            w0, w1 = tensors
+            return [(w0, f, h), (w1.view(R * h, cs), h, cs)]
+        return [(tensors[0], f, cs)]
 
     def _stage_splits(self, labels_np, masks, counts, dev):
         """what the loss kernel reads of the splits, and the run's step word, on the device"""
@@ -358,6 +380,8 @@ class SplitTrainBatch:
     def eval_step(self):
         self.forward(train=False)
         self.xent.launch(XENT_EVAL, self.step)
+        if self.keeper is not None:
+            self.keeper.launch(self.step)  # (after the selection of this step, before the word advances)
         self.step.add_(1)
 
     def epoch(self):
@@ -369,7 +393,8 @@ class SplitTrainBatch:
         """Capture one epoch as a hipGraph (after a warm-up whose effects are rewound); returns the replay callable."""
         # torch's Adam: the state it has is restored, the state the warm-up creates starts from zero
         state = [] if self.adam is not None else [v for st in self.opt.state.values() for v in st.values() if torch.is_tensor(v)]
-        restore = snapshot(self.params + [self.step, self.xent.best] + ([self.adam.moments] if self.adam is not None else state))
+        kept = self.kept_params + [self.kept_logits] if self.keep_best else []  # (the warm-up epochs leave no trace in them)
+        restore = snapshot(self.params + [self.step, self.xent.best] + ([self.adam.moments] if self.adam is not None else state) + kept)
 
         def warm_up():
             self.forward()
@@ -403,13 +428,20 @@ class SplitTrainBatch:
                     best_epoch=torch.from_numpy(best[:, 2].astype(np.int64)), seconds=dt, replicas_per_s=self.R / dt, epochs=epochs)
 
     # -- one replica ---------------------------------------------------------------------------------------------
-    def weights_of(self, r, grad=False):
-        """replica r's weights (or their gradients) as views without the padding columns: (W,) or (W0, W1)"""
+    def _tensors(self, grad=False, kept=False):
+        """one tensor per entry of self.params, in its order: the parameters' data, their gradients or their kept copies"""
+        if kept:
+            return list(self.kept_params)
+        return [p.grad if grad else p.data for p in self.params]
+
+    def weights_of(self, r, grad=False, kept=False):
+        """replica r's weights (or their gradients; kept=True: their kept copies) as views without the padding columns: (W,) or (W0, W1)"""
         c, cs, h = self.c, self.cs, self.h
-        pick = (lambda p: p.grad) if grad else (lambda p: p.data)
         if self.two_layer:
-            return pick(self.w0)[:, r * h:(r + 1) * h], pick(self.w1)[r, :, :c]
-        return (pick(self.w)[:, r * cs:r * cs + c],)
+            w0, w1 = self._tensors(grad, kept)
+            return w0[:, r * h:(r + 1) * h], w1[r, :, :c]
+        w, = self._tensors(grad, kept)
+        return (w[:, r * cs:r * cs + c],)
 
     def logits_of(self, r):
         return self.logits[:, r * self.cs:r * self.cs + self.c]
@@ -420,9 +452,9 @@ class SplitTrainBatch:
             return (models.GCN2 if self.kind == "gcn" else models.MLP2)(self.f, self.c, nhid=self.h, dropout=p, dropout_rng=rng)
         return (models.SGC1 if self.kind == "sgc" else models.MLP1)(self.f, self.c)
 
-    def replica_model(self, r):
+    def replica_model(self, r, kept=False):
         """the per-replica reference (a models.SGC1 / GCN2 / MLP1 / MLP2; a subclass: its own) on the device holding replica r's CURRENT
-        parameters (copies); with dropout > 0 its hidden layer draws from models.DeviceDropout(dropout_seed, stream=replica_ids[r]) with
+        parameters (copies; kept=True: the kept ones, as best_model(r) asks); with dropout > 0 its hidden layer draws from models.DeviceDropout(dropout_seed, stream=replica_ids[r]) with
         replica r's own drop probability; its step word starts at 0"""
         from . import models
         if not 0 <= r < self.R:
@@ -433,9 +465,57 @@ class SplitTrainBatch:
             model = self._empty_model(models, p, rng)
         model = model.to(self.x.device)
         with torch.no_grad():
-            for p, w in zip(model.parameters(), self.weights_of(r)):
+            for p, w in zip(model.parameters(), self.weights_of(r, kept=kept)):
                 p.copy_(w)
         return model
+
+    # -- the selected model (keep_best=True) -------------------------------------------------------------------------
+    def _kept(self, what, r=None):
+        if not self.keep_best:
+            raise ValueError(f"{type(self).__name__}.{what}: the run was built without keep_best=True")
+        if r is not None and not 0 <= r < self.R:
+            raise ValueError(f"{type(self).__name__}.{what}: replica {r} of {self.R}")
+
+    def best_weights_of(self, r):
+        """weights_of(r) of replica r's best epoch (zeros while it has none)"""
+        self._kept("best_weights_of", r)
+        return self.weights_of(r, kept=True)
+
+    def best_logits_of(self, r):
+        """logits_of(r) of replica r's best epoch: [n, C], a view of kept_logits"""
+        self._kept("best_logits_of", r)
+        return self.kept_logits[:, r * self.cs:r * self.cs + self.c]
+
+    def best_model(self, r):
+        """replica_model(r) holding the weights of replica r's best epoch"""
+        self._kept("best_model", r)
+        return self.replica_model(r, kept=True)
+
+    def _confuse(self, what):
+        """ONE ops.ConfusionBatch launch over kept_logits, now -> the table (its counts and predictions are current)"""
+        self._kept(what)
+        if self._confusion is None:
+            self._confusion = ConfusionBatch([dict(logits=self.kept_logits, labels=self.labels, split=self.split, C=self.c, cs=self.cs)])
+        self._confusion.launch()
+        return self._confusion
+
+    def confusion_and_predictions(self):
+        """-> (confusion(), predictions()) from ONE launch over kept_logits and one read-back of each (every call launches: the kept
+        logits move with every epoch that selects)"""
+        table = self._confuse("confusion_and_predictions")
+        return table.counts_of[0].cpu().numpy().astype(np.int64), np.ascontiguousarray(table.pred_of[0].cpu().numpy().T)
+
+    def predictions(self):
+        """-> uint8 [R, n] (numpy): every replica's predicted class of every node at its best epoch, 255 for none (a NaN in the row).
+        Every call launches the kernel once; confusion_and_predictions() gives both results of one launch"""
+        self._kept("predictions")
+        return self.confusion_and_predictions()[1]
+
+    def confusion(self):
+        """-> int64 [R, 3, C, C + 1] (numpy): per replica and part (train, validation, test) the rows of true class y predicted as k
+        (column C: no prediction) at the replica's best epoch.  Every call launches the kernel once"""
+        self._kept("confusion")
+        return self.confusion_and_predictions()[0]
 
 
 # -- a hyperparameter grid over the splits ------------------------------------------------------------------------------------
@@ -495,7 +575,61 @@ def select_settings(best, n_val, n_test):
                 best_mean_test_std=dev(test_all[g_best]))
 
 
-def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, seed=0, max_replicas=None, symmetric=0, capture=True):
+def classification_report(confusion):
+    """What a confusion table says per replica and split part, in numpy alone.  confusion: integer [..., 3, C, C + 1] (confusion() of a
+    stacked run, or grid_search(keep_best=True)["confusion"]): true class by predicted class, column C = no prediction, which counts
+    as wrong everywhere below.
+    -> dict(recall [..., 3, C]: hits of a class over its rows (NaN for a class without rows in that part),
+            balanced_accuracy [..., 3]: the mean recall over the classes PRESENT in the part (NaN where it is empty),
+            macro_f1 [..., 3]: the mean over the classes that occur as a label or as a prediction of F1 = 2 tp / (2 tp + fp + fn),
+            accuracy [..., 3]: hits over rows (NaN where the part is empty), support [..., 3, C]: the rows of a class)"""
+    m = np.asarray(confusion)
+    if m.ndim < 3 or m.shape[-3] != 3 or m.shape[-1] != m.shape[-2] + 1 or m.dtype.kind not in "iu":
+        raise ValueError(f"classification_report: an integer [..., 3, C, C + 1] table expected, got {m.dtype} {tuple(m.shape)}")
+    m = m.astype(np.int64)
+    c = m.shape[-2]
+    tp = np.diagonal(m[..., :c], axis1=-2, axis2=-1)  # [..., 3, C]
+    support, predicted = m.sum(-1), m[..., :c].sum(-2)
+    nan = np.float64("nan")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recall = np.where(support > 0, tp / support, nan)
+        present = support > 0
+        balanced = np.where(present.any(-1), np.where(present, recall, 0.0).sum(-1) / present.sum(-1), nan)
+        occurs = (support + predicted) > 0
+        f1 = np.where(occurs, 2 * tp / (support + predicted), 0.0)  # (2 tp + fp + fn = the class's rows + its predictions)
+        macro = np.where(occurs.any(-1), f1.sum(-1) / occurs.sum(-1), nan)
+        accuracy = np.where(support.sum(-1) > 0, tp.sum(-1) / support.sum(-1), nan)
+    return dict(recall=recall, balanced_accuracy=balanced, macro_f1=macro, accuracy=accuracy, support=support)
+
+
+def prediction_overlap(pred_a, pred_b, labels, masks):
+    """A node-level comparison of two models over every split's TEST rows.  pred_a, pred_b: integer [S, n] (predictions() of two runs
+    over the same splits; 255 = no prediction = wrong), labels [n], masks bool [S, 3, n].
+    -> (counts int64 [S, 2, 2]: counts[s, i, j] = the test rows of split s with a wrong (i = 1) or right (i = 0) and b wrong (j = 1) or right
+        (j = 0) - [0, 0] both right, [0, 1] only a, [1, 0] only b, [1, 1] neither;
+        p float64 [S]: the two-sided exact binomial p-value of the discordant pair (only a against only b at probability 1/2 - the exact
+        McNemar test, scipy.stats.binomtest; 1 where no row is discordant))"""
+    from scipy.stats import binomtest
+    labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
+    pa, pb = (np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p) for p in (pred_a, pred_b))
+    masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+    n = labels.shape[0]
+    if pa.ndim != 2 or pa.shape != pb.shape or pa.shape[1] != n or masks.dtype != np.bool_ or masks.shape != (pa.shape[0], 3, n):
+        raise ValueError("prediction_overlap: pred_a and pred_b [S, n], labels [n] and bool masks [S, 3, n] expected")
+    S = pa.shape[0]
+    counts, p = np.zeros((S, 2, 2), np.int64), np.ones(S, np.float64)
+    for s in range(S):
+        test = masks[s, 2]
+        wrong_a, wrong_b = (pa[s, test].astype(np.int64) != labels[test]), (pb[s, test].astype(np.int64) != labels[test])
+        np.add.at(counts[s], (wrong_a.astype(np.int64), wrong_b.astype(np.int64)), 1)
+        discordant = int(counts[s, 0, 1] + counts[s, 1, 0])
+        if discordant:
+            p[s] = binomtest(int(counts[s, 0, 1]), discordant, 0.5, alternative="two-sided").pvalue
+    return counts, p
+
+
+def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, seed=0, max_replicas=None, symmetric=0, capture=True, *,
+                keep_best=False):
     """A hyperparameter grid over all splits of one graph, as stacked runs.  grid: a list of G dicts with the keys lr, weight_decay and
     dropout; masks: bool [S, 3, n].  Replica (g, s) - setting g on split s - sits at position g S + s (setting-major) with
     replica_ids = s: every setting starts split s from the same weights and draws the same dropout masks (common random numbers).
@@ -507,7 +641,9 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     hold at least one setting: max_replicas < S is refused.
     -> dict(val_acc, test_acc [G, S] float64 (-1 / 0 for a replica without a best epoch), best_epoch [G, S], best [G, S, 3] int
     (validation hits, test hits, epoch), n_val, n_test [S], chunks [(g0, g1), ...], seconds, selection = select_settings(best, n_val,
-    n_test): the per-split pick, its test accuracy's mean and sample deviation, and the setting of the best mean validation accuracy)."""
+    n_test): the per-split pick, its test accuracy's mean and sample deviation, and the setting of the best mean validation accuracy).
+    keep_best=True: every chunk runs with keep_best, and the result gains confusion [G, S, 3, C, C + 1] int64 and pred [G, S, n] uint8 - of
+    every (setting, split) at its best epoch, collected chunk by chunk (the kept weights themselves go with their chunk)."""
     grid = list(grid)
     for g in grid:
         if not isinstance(g, dict) or set(g) != {"lr", "weight_decay", "dropout"}:
@@ -533,18 +669,25 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     x = _dev(x, torch.float32, dev)
     labels_dev = torch.as_tensor(labels_np.astype(np.int64))
     best = np.zeros((len(grid), S, 3), np.int64)
+    confusion, pred = [], []
     seconds = 0.0
     for g0, g1 in chunks:
         part = grid[g0:g1]
         spread = lambda key: np.repeat(np.array([float(g[key]) for g in part]), S)  # noqa: E731  (setting-major)
         kw = dict(dropout=spread("dropout")) if two_layer else {}
         stb = SplitTrainBatch(adj, x, labels_dev, np.tile(masks, (g1 - g0, 1, 1)), kind=kind, hidden=hidden, lr=spread("lr"),
-                              weight_decay=spread("weight_decay"), seed=seed, optimizer="device", replica_ids=np.tile(np.arange(S), g1 - g0), **kw)
+                              weight_decay=spread("weight_decay"), seed=seed, optimizer="device", replica_ids=np.tile(np.arange(S), g1 - g0),
+                              keep_best=keep_best, **kw)
         seconds += stb.run(epochs=epochs, capture=capture)["seconds"]
         best[g0:g1] = stb.best.cpu().numpy().reshape(g1 - g0, S, 3)
+        if keep_best:
+            conf, pr = stb.confusion_and_predictions()  # (one launch per chunk)
+            confusion.append(conf.reshape((g1 - g0, S) + (3, stb.c, stb.c + 1)))
+            pred.append(pr.reshape(g1 - g0, S, n))
         del stb
     n_val, n_test = masks[:, 1].sum(1).astype(np.int64), masks[:, 2].sum(1).astype(np.int64)
     none = best[:, :, 0] < 0
+    kept = dict(confusion=np.concatenate(confusion, 0), pred=np.concatenate(pred, 0)) if keep_best else {}
     return dict(val_acc=np.where(none, -1.0, best[:, :, 0] / n_val[None, :]), test_acc=np.where(none, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :]),
                 best_epoch=best[:, :, 2].copy(), best=best, n_val=n_val, n_test=n_test, chunks=chunks, seconds=seconds,
-                selection=select_settings(best, n_val, n_test))
+                selection=select_settings(best, n_val, n_test), **kept)

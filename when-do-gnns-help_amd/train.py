@@ -4,7 +4,9 @@ ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dro
 (ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip
 (and, for the stacked class-width layers of acm_split_train, several replicas per 16 lanes: csrc/acm_mix_packed.hip),
 and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip,
-and the Adam step of the stacked parameters with every replica's own learning rate and weight decay, csrc/adam.hip."""
+and the Adam step of the stacked parameters with every replica's own learning rate and weight decay, csrc/adam.hip,
+and the copy of every replica's parameters and logits at its best epoch, csrc/keep_best.hip, with the predictions and the confusion
+counts of stacked logits, csrc/confusion.hip."""
 import ctypes
 import math
 
@@ -17,8 +19,9 @@ from ._rt import _h2d, _ld, _ptr
 
 # the record types of the job tables: those of the ctypes mirrors of include/wdg.h (names, offsets and size; tests/test_abi*.py check
 # the mirrors against the header)
-_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE, _ACM_PACKED_JOB_DTYPE = (
-    np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob, _lib.AcmPackedJob))
+_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE, _ACM_PACKED_JOB_DTYPE, _KEEP_JOB_DTYPE, _CONFUSION_JOB_DTYPE = (
+    np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob, _lib.AcmPackedJob, _lib.KeepJob,
+                          _lib.ConfusionJob))
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
 
 
@@ -550,3 +553,121 @@ class AdamBatch:
     def reset(self):
         """the moments back to zero (the parameters and the step word are the caller's)"""
         self.moments.zero_()
+
+
+class KeepBestBatch:
+    """Job table for wdg_keep_best_batched_f32 (csrc/keep_best.hip): of every tensor of the table, the segments of the replicas whose
+    best epoch is the current step are copied from src to dst, in one launch (include/wdg.h states the rule; tests/_keep_ref.py
+    restates it in numpy).  A job is one tensor, as in AdamBatch; nothing is owned by the table but its records."""
+
+    MAX_JOBS = 65535
+
+    def __init__(self, entries):
+        """entries: list of (src, dst, seg_rows, seg_cols, reps, best) - src and dst [rows, cols] fp32 device views of one shape with
+        unit inner stride (any leading dimensions; w1 [R, hidden, cs] is passed as its [R hidden, cs] view), dst written IN PLACE;
+        element (r, c) belongs to segment (r // seg_rows) * ceil(cols / seg_cols) + c // seg_cols and to replica segment % reps;
+        best: [reps, 3] int32 device, contiguous (XentEvalBatch.best_of[i]).  Raises ValueError for other dtypes, shapes or strides,
+        src and dst that overlap, seg_rows, seg_cols or reps below 1, more than 65535 entries."""
+        self.keep = entries
+        n = self.n_jobs = len(entries)
+        if n > self.MAX_JOBS:
+            raise ValueError(f"KeepBestBatch: {n} entries; one launch takes {self.MAX_JOBS}")
+        for e in entries:
+            if len(e) != 6:
+                raise ValueError("KeepBestBatch: an entry is (src, dst, seg_rows, seg_cols, reps, best)")
+            src, dst, seg_rows, seg_cols, reps, best = e
+            _check_matrix("KeepBestBatch", "src", src)
+            _check_matrix("KeepBestBatch", "dst", dst)
+            if src.shape != dst.shape:
+                raise ValueError("KeepBestBatch: src and dst must have one shape")
+            if _views_may_overlap(src, dst):
+                raise ValueError("KeepBestBatch: src and dst overlap")
+            if int(seg_rows) < 1 or int(seg_cols) < 1 or int(reps) < 1:
+                raise ValueError(f"KeepBestBatch: segments of {seg_rows} x {seg_cols} for {reps} replicas; at least 1 x 1 and one replica expected")
+            if not isinstance(best, torch.Tensor) or best.dtype != torch.int32 or not best.is_cuda or not best.is_contiguous() or \
+                    tuple(best.shape) != (int(reps), 3):
+                raise ValueError(f"KeepBestBatch: best must be a contiguous [reps = {int(reps)}, 3] int32 device tensor")
+        dev = require_gpu()  # (after the checks that need no device)
+        col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
+        tab = np.zeros(n, _KEEP_JOB_DTYPE)
+        tab["src"], tab["dst"], tab["best"] = col(lambda e: e[0].data_ptr()), col(lambda e: e[1].data_ptr()), col(lambda e: e[5].data_ptr())
+        tab["ld_src"], tab["ld_dst"] = col(lambda e: max(_ld(e[0]), e[0].shape[1])), col(lambda e: max(_ld(e[1]), e[1].shape[1]))
+        tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
+        tab["seg_rows"], tab["seg_cols"], tab["reps"] = col(lambda e: int(e[2])), col(lambda e: int(e[3])), col(lambda e: int(e[4]))
+        self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
+        host = np.ascontiguousarray(tab)
+        check(lib.wdg_keep_best_check_jobs(ctypes.c_void_p(host.ctypes.data), n), "wdg_keep_best_check_jobs")
+        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self, step):
+        """step: a one-element int32 DEVICE tensor, read by the kernel when it runs - the word the XentEvalBatch.launch(XENT_EVAL, step)
+        before this launch recorded, not yet advanced"""
+        check(lib.wdg_keep_best_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, _step_word("KeepBestBatch.launch", step),
+                                            stream_handle()), "wdg_keep_best_batched_f32")
+
+
+class ConfusionBatch:
+    """Job table for wdg_confusion_batched_i32 (csrc/confusion.hip): the prediction of every (row, replica) of stacked logits - the first
+    maximum, XentEvalBatch's rule; 255 for a row with a NaN - and, per replica and split part, the counts of (true class, predicted
+    class or none) (include/wdg.h states both; tests/_confusion_ref.py restates them in numpy).  The table owns the counts
+    (counts_of[i]: int32 [R, 3, C, C + 1] - train, validation, test) and the predictions (pred_of[i]: uint8 [n, R])."""
+
+    MAX_C, MAX_JOBS = 16, 65535
+
+    def __init__(self, jobs):
+        """jobs: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device,
+        split [n, R] uint8 device contiguous (0 unused, 1 train, 2 validation, 3 test), C, cs (default: C).
+        Raises ValueError for other shapes, dtypes or strides, C outside 1 .. 16, cs < C, R cs beyond a row, more than 65535 jobs."""
+        self.keep = jobs
+        n_jobs = self.n_jobs = len(jobs)
+        if n_jobs > self.MAX_JOBS:
+            raise ValueError(f"ConfusionBatch: {n_jobs} jobs; one launch takes {self.MAX_JOBS}")
+        shapes = []
+        for e in jobs:
+            unknown = set(e) - {"logits", "labels", "split", "C", "cs"}
+            if unknown:
+                raise ValueError(f"ConfusionBatch: unknown keys {sorted(unknown)}")
+            split = e.get("split")
+            if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
+                raise ValueError("ConfusionBatch: split must be a contiguous [n, R] uint8 device matrix")
+            n, r = split.shape
+            c = int(e.get("C", 0))
+            cs = int(e.get("cs", c))
+            if not 1 <= c <= self.MAX_C:
+                raise ValueError(f"ConfusionBatch: {c} classes; the kernel holds 1..{self.MAX_C}")
+            if cs < c:
+                raise ValueError(f"ConfusionBatch: a replica stride of {cs} columns is narrower than its {c} classes")
+            t = e.get("logits")
+            _check_matrix("ConfusionBatch", "logits", t, (n, None))
+            if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
+                raise ValueError(f"ConfusionBatch: {r} replicas of {cs} columns do not fit a row of logits ({t.shape[1]} columns, leading dimension {_ld(t)})")
+            lab = e.get("labels")
+            if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
+                raise ValueError("ConfusionBatch: labels must be a contiguous [n] int32 device vector")
+            shapes.append((n, r, c, cs))
+        dev = require_gpu()  # (after the checks that need no device)
+        offsets = lambda lens: np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n_jobs))]).astype(np.int64)  # noqa: E731
+        coff, poff = offsets(r * 3 * c * (c + 1) for _, r, c, _ in shapes), offsets(n * r for n, r, _, _ in shapes)
+        self.counts = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int32, device=dev)
+        self.pred = torch.zeros(max(int(poff[-1]), 1), dtype=torch.uint8, device=dev)
+        self.counts_of = [self.counts[coff[i]:coff[i + 1]].view(r, 3, c, c + 1) for i, (_, r, c, _) in enumerate(shapes)]
+        self.pred_of = [self.pred[poff[i]:poff[i + 1]].view(n, r) for i, (n, r, _, _) in enumerate(shapes)]
+        tab = np.zeros(n_jobs, _CONFUSION_JOB_DTYPE)
+        for i, e in enumerate(jobs):
+            for k in ("logits", "labels", "split"):
+                tab[k][i] = e[k].data_ptr()
+            tab["ld_logits"][i] = max(_ld(e["logits"]), shapes[i][1] * shapes[i][3])
+        tab["counts"] = self.counts.data_ptr() + 4 * coff[:-1]
+        tab["pred"] = self.pred.data_ptr() + poff[:-1]
+        for k, name in enumerate(("n", "R", "C", "cs")):
+            tab[name] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
+        self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
+        host = np.ascontiguousarray(tab)
+        check(lib.wdg_confusion_check_jobs(ctypes.c_void_p(host.ctypes.data), n_jobs), "wdg_confusion_check_jobs")
+        self.table = _h2d(host.view(np.uint8), dev) if n_jobs else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self, zero=True):
+        """the predictions and the counts of every job; zero=True (the default) clears the table's counts first - the kernel ADDS"""
+        if zero:
+            self.counts.zero_()
+        check(lib.wdg_confusion_batched_i32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()), "wdg_confusion_batched_i32")
