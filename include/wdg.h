@@ -1355,6 +1355,72 @@ int wdg_confusion_batched_i32(const wdg_confusion_job *jobs_dev, int32_t n_jobs,
 /* replaces: nothing of its own - the per-job refusals of the confusion counts above (utils/util_funcs.py:393), on the host's table */
 int wdg_confusion_check_jobs(const wdg_confusion_job *jobs_host, int32_t n_jobs);
 
+/*
+ * The evaluation of a training epoch for many models whose logits are STACKED along the feature axis (wdg_xent_eval_batched_f32's
+ * layout: replica r owns columns r cs .. r cs + C - 1 of one [n, R cs] matrix), WITH the losses: per replica the mean cross-entropy
+ * and the hits of its train, validation and test rows, a row of its learning curve, its model selection by one of three rules and its
+ * patience counter - all on the device, inside a captured epoch.  A job is one graph's stacked logits (a ragged table).
+ * replaces: the accuracy of utils/util_funcs.py:393 and the loss / accuracy / early-stopping bookkeeping of the training loops behind
+ *           the accuracy tables gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249 (the loop itself lives upstream of the reference;
+ *           the selection rules are DEFINED here and are not claimed to reproduce its tables).  It stands in for the WDG_XENT_EVAL
+ *           call of wdg_xent_eval_batched_f32 where a run asks for losses, another selection rule, a patience or a learning curve.
+ * The definition of one call with the step word at s = *step_dev (read from DEVICE memory when the kernel runs), for row i and replica
+ * r of a job, z_k = logits[i][r cs + k], k = 0 .. C - 1, part p = split[i][r] - 1 in {0 train, 1 validation, 2 test} (other codes: the
+ * row is not looked at); tests/_curve_ref.py restates it in numpy.  All per-row arithmetic in fp32, in this order:
+ *     m = max_k z_k;  e_k = exp(z_k - m);  sum = e_0 + e_1 + ... + e_{C-1} (in that order);  term = log(sum) - (z_label - m)
+ *   H[r][p] = the rows whose prediction equals labels[i]; the prediction is the first k with z_k == m, and a row with a NaN among its
+ *             z's has none (WDG_XENT_EVAL's rule).
+ *   S[r][p] = the fp64 sum of the terms, each widened to fp64, IN THIS ORDER: the rows are cut into blocks of 32 (rows 32 b .. 32 b + 31);
+ *             a block's partial starts at +0.0 and takes the terms of its rows of part p in ascending row order; S starts at +0.0 and
+ *             takes the partials of the blocks 0 .. ceil(n / 32) - 1 in ascending order (blocks without a row of the part add their +0.0).
+ *             The order depends on the job's own n alone: not on R, the other jobs of the table, max_rows or which run it is.
+ *   L[r][p] = (float) (S[r][p] / n_part[r][p]), or NaN when n_part[r][p] <= 0.
+ *   A row whose label lies outside 0 .. C - 1 adds nothing to S and is no hit.  A NaN among the z's of a counted row makes its term,
+ *   and with it L[r][p], NaN.  The padding columns C .. cs - 1 are never read; nothing beyond column R cs of a row is read.
+ * Curve:      if 0 <= s < curve_rows:  curve_loss[s][r][:] = L[r][:], curve_hits[s][r][:] = H[r][:]; no other row is written.
+ * Selection:  only while state[r][1] (stopped_at) < 0; Hv = H[r][1], Lv = L[r][1]:
+ *     rule 0 (val_hits):            improved = Hv > best[r][0]
+ *     rule 1 (val_loss):            improved = Lv < best_loss[r][1]
+ *     rule 2 (val_hits_then_loss):  improved = Hv > best[r][0] || (Hv == best[r][0] && Lv < best_loss[r][1])
+ *     (a NaN makes every comparison false)
+ *     improved:   best[r] = (Hv, H[r][2], s), best_loss[r][:] = L[r][:], bad = 0;        otherwise: bad += 1
+ *     then, if patience > 0 && bad >= patience:  stopped_at = s.
+ *   A stopped replica's best, best_loss and state never change again; its curve rows are still written.  With rule 0 and patience 0,
+ *   best is what WDG_XENT_EVAL leaves.
+ * Two launches: one over the rows (the terms of a row block in LDS, then one thread per replica adds them in row order and STORES the
+ * block's partials; the hits are integer adds to `hits`), one that finishes (sums, means, curve, selection; `hits` back to zero).
+ * No floating-point atomic: two calls from the same inputs give the same bits, inside any table.
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs (a job per grid
+ * z), a NULL step_dev.  max_cols names the table's largest C: more than 16 classes is WDG_ERR_UNSUPPORTED.  n_jobs == 0: WDG_OK, nothing
+ * is launched.  The table lives in device memory, so what is wrong inside a job - a rule outside 0 .. 2, a negative patience, negative
+ * curve_rows or curve_rows > 0 without both curve buffers, C outside 1 .. 16, cs < C, ld_logits below R cs, a NULL pointer - is refused
+ * by wdg_xent_curve_check_jobs on the HOST copy of the table (ops.XentCurveBatch calls it before it uploads; no HIP call either), and
+ * both launches SKIP such a job without touching its memory.  A job with n == 0 or R == 0 is skipped; rows beyond max_rows (the
+ * table's largest n) are not looked at.
+ */
+typedef struct wdg_xent_curve_job {
+    const float *logits;      /* [n, R*cs] fp32, leading dimension ld_logits */
+    const int32_t *labels;    /* [n], shared by the replicas */
+    const uint8_t *split;     /* [n, R] row-major: 0 unused, 1 train, 2 validation, 3 test */
+    const int32_t *n_part;    /* [R, 3]: the train, validation and test rows of a replica, counted by the host */
+    int32_t *best;            /* [R, 3] in/out: wdg_xent_job.best - validation hits of the best step (-1: none yet), test hits at it, the step */
+    float *best_loss;         /* [R, 3] in/out: L[r][:] of the best step; +inf before the first */
+    int32_t *state;           /* [R, 2] in/out: bad (steps since the last improvement), stopped_at (-1: running) */
+    float *curve_loss;        /* [curve_rows, R, 3], or NULL with curve_rows == 0 */
+    int32_t *curve_hits;      /* [curve_rows, R, 3], or NULL with curve_rows == 0 */
+    int32_t *hits;            /* [R, 3] work space: zero before the first call, left zero by every call */
+    double *partials;         /* work space of wdg_xent_curve_partials_len(n, R) doubles: written before it is read, any contents */
+    int64_t ld_logits;
+    int32_t n, R, C, cs;
+    int32_t rule, patience, curve_rows, reserved;
+} wdg_xent_curve_job;
+int wdg_xent_curve_batched_f32(const wdg_xent_curve_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols,
+                               const int32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the evaluation above (gnns_on_syn.py:109-154), on the host's table */
+int wdg_xent_curve_check_jobs(const wdg_xent_curve_job *jobs_host, int32_t n_jobs);
+/* replaces: nothing of its own - the doubles of a job's `partials`: ceil(n / 32) * R * 3 (0 for an empty job) (gnns_on_syn.py:109-154) */
+int64_t wdg_xent_curve_partials_len(int32_t n, int32_t R);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,9 @@ SIGNATURES = {
     "wdg_keep_best_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_confusion_batched_i32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_confusion_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_xent_curve_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "wdg_xent_curve_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_xent_curve_partials_len": (c_int64, [c_int32, c_int32]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -336,6 +339,13 @@ class ConfusionJob(ctypes.Structure):
     """mirror of `wdg_confusion_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("logits", "labels", "split", "counts", "pred")] + \
                [("ld_logits", c_int64), ("n", c_int32), ("R", c_int32), ("C", c_int32), ("cs", c_int32)]
+
+
+class XentCurveJob(ctypes.Structure):
+    """mirror of `wdg_xent_curve_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("logits", "labels", "split", "n_part", "best", "best_loss", "state", "curve_loss", "curve_hits",
+                                              "hits", "partials")] + \
+               [("ld_logits", c_int64)] + [(name, c_int32) for name in ("n", "R", "C", "cs", "rule", "patience", "curve_rows", "reserved")]
 
 
 if not os.path.exists(LIB_PATH):

@@ -57,6 +57,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
     Stacked parameters (w = hidden or cs; block (c, r) of a first-layer weight = columns (c R + r) w .. of it):
         "acm_sgc":  w [F, 3 R cs], att [R, 3, cs], wmix [R, 3, 3]
         "acm_gcn":  w0 [F, 3 R hidden], att0 [R, 3, hidden], wmix0 [R, 3, 3], w1 [R, hidden, 3 cs], att1 [R, 3, cs], wmix1 [R, 3, 3]
+    select, patience, curve_epochs: SplitTrainBatch's.
     Raises ValueError for another kind, "acm_sgc" with dropout, more than 16 classes, hidden outside 1..256 and what SplitTrainBatch
     refuses of masks, labels and replica ids."""
 
@@ -64,11 +65,12 @@ class AcmSplitTrainBatch(SplitTrainBatch):
     MAX_HIDDEN = AcmMixBatch.MAX_COLS
 
     def __init__(self, adj, x, labels, masks, kind="acm_gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
-                 dropout_seed=None, replica_ids=None, *, keep_best=False):
+                 dropout_seed=None, replica_ids=None, *, keep_best=False, select="val_hits", patience=0, curve_epochs=0):
         who = "AcmSplitTrainBatch"
         if kind not in self.KINDS:
             raise ValueError(f"{who}: unknown model kind {kind!r} (one of {self.KINDS}; {SplitTrainBatch.KINDS} are SplitTrainBatch's)")
         self.kind, self.optimizer, self.two_layer, self.keep_best = kind, "torch", kind == "acm_gcn", bool(keep_best)
+        self._selection(who, select, patience, curve_epochs)
         if any(np.ndim(v) > 0 for v in (lr, weight_decay, dropout)):
             raise ValueError(f"{who}: one lr, one weight_decay and one dropout for all replicas expected")
         self.dropout = float(dropout)

@@ -29,7 +29,8 @@ from ._lib import require_gpu
 from ._rt import _dev, capture_graphs, snapshot
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
-from .train import XENT_EVAL, XENT_GRAD, AdamBatch, ConfusionBatch, DropoutBatch, KeepBestBatch, XentEvalBatch, dropout_constants
+from .train import (SELECT_RULES, XENT_EVAL, XENT_GRAD, AdamBatch, ConfusionBatch, DropoutBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch,
+                    dropout_constants, select_rule, whole_number)
 
 MAX_CLASSES = XentEvalBatch.MAX_C
 
@@ -138,18 +139,33 @@ class SplitTrainBatch:
     keep_best=True: the run also owns kept_params (one tensor per entry of self.params, of its shape) and kept_logits
     [n, R cs], zeros at first, and every epoch's evaluation is followed by one ops.KeepBestBatch launch that copies, on the device,
     the parameter blocks and the logits of exactly the replicas whose best epoch is this one.  best_weights_of(r), best_logits_of(r),
-    best_model(r), predictions() and confusion() read them; the parameters, `best` and run()'s dictionary are what they are without it."""
+    best_model(r), predictions() and confusion() read them; the parameters, `best` and run()'s dictionary are what they are without it.
+
+    select, patience, curve_epochs: with the defaults ("val_hits", 0, 0) nothing below exists and the epoch is what it
+    was.  Otherwise the run owns an ops.XentCurveBatch (csrc/xent_curve.hip) over the stacked logits, whose launch takes the place of
+    the evaluation launch of every epoch: it computes every replica's mean cross-entropy and hits on its train, validation and test
+    rows, writes them into row `epoch` of the learning curve (the first curve_epochs epochs), selects by `select` - "val_hits"
+    (strictly more validation hits), "val_loss" (strictly lower validation loss) or "val_hits_then_loss" (more hits, or equal hits and
+    a lower loss) - and, with patience = k > 0, stops a replica's SELECTION after k epochs in a row without an improvement.  A stopped
+    replica goes on training in the shared launches (freezing it would save nothing); its best, best_loss and kept tensors no longer
+    change.  The losses are those of the CLEAN forward pass of the epoch's evaluation, for all three parts at the same weights: with
+    dropout the train loss is NOT the loss of the training pass the gradient came from.  `best` is the curve table's (KeepBestBatch,
+    run() and grid_search read it as ever); best_loss [R, 3], stopped_at [R] and learning_curves() read the rest.  The rules are
+    defined in include/wdg.h; they are not claimed to reproduce the tables of the loops upstream of the reference."""
 
     KINDS = ("sgc", "gcn", "mlp1", "mlp2")
     OPTIMIZERS = ("torch", "device")
+    select, patience, curve_epochs, curve = SELECT_RULES[0], 0, 0, None  # (a run whose constructor never calls _selection() is a default run)
 
     def __init__(self, adj, x, labels, masks, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
-                 dropout_seed=None, *, optimizer="torch", replica_ids=None, keep_best=False):
+                 dropout_seed=None, *, optimizer="torch", replica_ids=None, keep_best=False,
+                 select="val_hits", patience=0, curve_epochs=0):
         if kind not in self.KINDS:
             raise ValueError(f"SplitTrainBatch: unknown model kind {kind!r} (one of {self.KINDS}; the ACM kinds are sweep.TrainBatch's)")
         if optimizer not in self.OPTIMIZERS:
             raise ValueError(f"SplitTrainBatch: unknown optimizer {optimizer!r} (one of {self.OPTIMIZERS})")
         self.kind, self.optimizer, self.keep_best = kind, optimizer, bool(keep_best)
+        self._selection("SplitTrainBatch", select, patience, curve_epochs)
         self.two_layer = kind in ("gcn", "mlp2")
         per_replica = {name: np.ndim(val) > 0 for name, val in (("lr", lr), ("weight_decay", weight_decay), ("dropout", dropout))}
         if optimizer != "device" and any(per_replica.values()):
@@ -240,6 +256,12 @@ class SplitTrainBatch:
         self._stage_splits(labels_np, masks, counts, dev)
         return dev
 
+    def _selection(self, who, select, patience, curve_epochs):
+        """the checks of select, patience and curve_epochs (before anything touches the device)"""
+        self.select = SELECT_RULES[select_rule(who, select)]
+        self.patience = whole_number(who, "patience", patience)
+        self.curve_epochs = whole_number(who, "curve_epochs", curve_epochs)
+
     @staticmethod
     def _class_stride(c):
         """the columns between the replicas of a class-width matrix: c rounded up to a multiple of 4"""
@@ -250,6 +272,13 @@ class SplitTrainBatch:
         self.xent = XentEvalBatch([dict(logits=self.logits, dlogits=self.dlogits, labels=self.labels, split=self.split,
                                         inv_n_train=self.inv_n_train, C=self.c, cs=self.cs)])
         self.best = self.xent.best_of[0]  # [R, 3] int32: validation hits of the best epoch (-1: none yet), test hits at it, its epoch
+        self.curve = None
+        if (self.select, self.patience, self.curve_epochs) != (SELECT_RULES[0], 0, 0):
+            # the evaluation with losses: its table owns the running best from here on
+            counts = np.stack([self.n_train, self.n_val, self.n_test], 1)
+            self.curve = XentCurveBatch([dict(logits=self.logits, labels=self.labels, split=self.split, n_part=counts, C=self.c, cs=self.cs,
+                                              select=self.select, patience=self.patience, curve_rows=self.curve_epochs)])
+            self.best = self.curve.best_of[0]
         # torch's fused Adam: its kernel forms the bias corrections 1 - beta^t in double precision.  The unfused capturable path forms
         # them in fp32 tensors - 1 - 0.999^t cancels to a relative error of 1e-5 - and twelve epochs end 9e-7 from a float64 run where
         # this form ends 1e-7 from it (measured: tests/test_gpu_split_train.py).  Both keep the step count on the device: capturable.
@@ -379,7 +408,10 @@ class SplitTrainBatch:
 
     def eval_step(self):
         self.forward(train=False)
-        self.xent.launch(XENT_EVAL, self.step)
+        if self.curve is None:
+            self.xent.launch(XENT_EVAL, self.step)
+        else:
+            self.curve.launch(self.step)  # losses, hits, the curve's row, selection and patience of this step
         if self.keeper is not None:
             self.keeper.launch(self.step)  # (after the selection of this step, before the word advances)
         self.step.add_(1)
@@ -394,7 +426,8 @@ class SplitTrainBatch:
         # torch's Adam: the state it has is restored, the state the warm-up creates starts from zero
         state = [] if self.adam is not None else [v for st in self.opt.state.values() for v in st.values() if torch.is_tensor(v)]
         kept = self.kept_params + [self.kept_logits] if self.keep_best else []  # (the warm-up epochs leave no trace in them)
-        restore = snapshot(self.params + [self.step, self.xent.best] + ([self.adam.moments] if self.adam is not None else state) + kept)
+        selection = [self.xent.best] + (self.curve.state_tensors() if self.curve is not None else [])
+        restore = snapshot(self.params + [self.step] + selection + ([self.adam.moments] if self.adam is not None else state) + kept)
 
         def warm_up():
             self.forward()
@@ -411,21 +444,68 @@ class SplitTrainBatch:
         self.graph, = capture_graphs([self.epoch], warm_up, rewind)
         return self.graph.replay
 
-    def run(self, epochs=200, capture=True):
-        """-> dict(val_acc [R], test_acc [R], best_epoch [R], seconds, replicas_per_s): `epochs` more epochs of every replica"""
+    def run(self, epochs=200, capture=True, check_every=None):
+        """-> dict(val_acc [R], test_acc [R], best_epoch [R], seconds, replicas_per_s): `epochs` more epochs of every replica.
+        With select / patience / curve_epochs the dictionary gains val_loss [R], test_loss [R] (at the best epoch; +inf while there is
+        none), stopped_at [R] (-1: not stopped) and epochs_run.  check_every = k (such a run only): the host reads stopped_at after
+        every k epochs and ends the run once EVERY replica has stopped; None (the default) reads nothing back.  A stopped replica's
+        selection is frozen, so the results are the same with or without the early exit."""
+        if check_every is not None:
+            check_every = whole_number(f"{type(self).__name__}.run", "check_every", check_every, least=1)
+            if self.curve is None:
+                raise ValueError(f"{type(self).__name__}.run: check_every needs a run built with select, patience or curve_epochs")
         step = (self.graph.replay if self.graph is not None else self.capture()) if capture else self.epoch
         self.forward()  # logits of the current weights
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(epochs):
+        done = 0
+        while done < epochs:
             step()
+            done += 1
+            if check_every is not None and done % check_every == 0 and bool((self.curve.state_of[0][:, 1] >= 0).all()):
+                break
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         best = self.best.cpu().numpy()
         none = best[:, 0] < 0
-        return dict(val_acc=torch.from_numpy(np.where(none, -1.0, best[:, 0] / self.n_val)),
-                    test_acc=torch.from_numpy(np.where(none, 0.0, best[:, 1] / np.maximum(self.n_test, 1))),
-                    best_epoch=torch.from_numpy(best[:, 2].astype(np.int64)), seconds=dt, replicas_per_s=self.R / dt, epochs=epochs)
+        out = dict(val_acc=torch.from_numpy(np.where(none, -1.0, best[:, 0] / self.n_val)),
+                   test_acc=torch.from_numpy(np.where(none, 0.0, best[:, 1] / np.maximum(self.n_test, 1))),
+                   best_epoch=torch.from_numpy(best[:, 2].astype(np.int64)), seconds=dt, replicas_per_s=self.R / dt, epochs=epochs)
+        if self.curve is not None:
+            loss = self.best_loss
+            out.update(val_loss=torch.from_numpy(loss[:, 1].copy()), test_loss=torch.from_numpy(loss[:, 2].copy()),
+                       stopped_at=torch.from_numpy(self.stopped_at), epochs_run=done)
+        return out
+
+    # -- the losses (select / patience / curve_epochs) ---------------------------------------------------------------
+    def _curved(self, what):
+        if self.curve is None:
+            raise ValueError(f"{type(self).__name__}.{what}: the run was built with the default select, patience and curve_epochs")
+        return self.curve
+
+    @property
+    def best_loss(self):
+        """float32 [R, 3] (numpy): the train, validation and test loss of every replica at its best epoch (+inf while it has none)"""
+        return self._curved("best_loss").best_loss_of[0].cpu().numpy()
+
+    @property
+    def stopped_at(self):
+        """int64 [R] (numpy): the epoch at which a replica's patience ran out, -1 while it has not"""
+        return self._curved("stopped_at").state_of[0][:, 1].cpu().numpy().astype(np.int64)
+
+    def learning_curves(self):
+        """-> dict(loss [T, R, 3] float32, hits [T, R, 3] int64, acc [T, R, 3] float64 (NaN for a part without rows)) over the parts train,
+        validation, test, for T = min(epochs done, curve_epochs): row t is the evaluation of epoch t (its clean forward pass)"""
+        pair = self._curved("learning_curves").curve_of[0]
+        T = min(int(self.step.item()), self.curve_epochs)
+        if pair is None:
+            loss, hits = np.zeros((0, self.R, 3), np.float32), np.zeros((0, self.R, 3), np.int64)
+        else:
+            loss, hits = pair[0][:T].cpu().numpy(), pair[1][:T].cpu().numpy().astype(np.int64)
+        rows = np.stack([self.n_train, self.n_val, self.n_test], 1).astype(np.float64)[None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            acc = np.where(rows > 0, hits / rows, np.nan)
+        return dict(loss=loss, hits=hits, acc=acc)
 
     # -- one replica ---------------------------------------------------------------------------------------------
     def _tensors(self, grad=False, kept=False):
@@ -543,7 +623,7 @@ def chunk_settings(n_settings, n_splits, max_replicas):
     return [(g0, min(g0 + per, n_settings)) for g0 in range(0, n_settings, per)]
 
 
-def select_settings(best, n_val, n_test):
+def select_settings(best, n_val, n_test, val_loss=None):
     """Model selection over a grid, in numpy alone.  best: int [G, S, 3] - per (setting, split) the validation hits of the best epoch
     (-1: the replica never had a best epoch), the test hits at it, its epoch; n_val, n_test: [S] row counts.
     For every split the setting with the most validation hits is picked, the LOWEST setting index among equals; a replica without a
@@ -551,7 +631,11 @@ def select_settings(best, n_val, n_test):
     -> dict(setting [S], val_acc [S], test_acc [S], best_epoch [S] at the picked setting; test_mean, test_std: mean and SAMPLE
     deviation (ddof = 1; 0 for a single split) of test_acc over the splits; mean_val_acc [G]: the settings' mean validation accuracy
     over the splits (a replica without a best epoch counts 0), best_mean_setting: its argmax (lowest index among equals), and
-    best_mean_test_mean / best_mean_test_std: that one setting's test accuracy over the splits)."""
+    best_mean_test_mean / best_mean_test_std: that one setting's test accuracy over the splits).
+    val_loss: float [G, S] (grid_search(select="val_loss")["best_loss"][:, :, 1]) - then the per-split pick is the setting with the LOWEST
+    validation loss instead, the lowest index among equals; a NaN never wins, and neither does a replica without a best epoch (a split
+    where nothing qualifies picks setting 0 with test accuracy 0).  The result gains mean_val_loss [G] (a NaN or a replica without a best
+    epoch makes its setting's mean +inf) and best_mean_loss_setting: its argmin (lowest index among equals).  None: nothing changes."""
     best = np.asarray(best)
     if best.ndim != 3 or best.shape[2] != 3 or best.shape[0] < 1 or best.shape[1] < 1 or best.dtype.kind not in "iu":
         raise ValueError(f"select_settings: an integer [G, S, 3] table expected, got {best.dtype} {tuple(best.shape)}")
@@ -562,17 +646,27 @@ def select_settings(best, n_val, n_test):
     hits = best[:, :, 0].astype(np.int64)
     pick = hits.argmax(0)  # (numpy's argmax: the first maximum = the lowest setting index; -1 loses to every count >= 0)
     cols = np.arange(S)
-    none = hits[pick, cols] < 0
+    extra = {}
+    if val_loss is not None:
+        loss = np.asarray(val_loss, np.float64)
+        if loss.shape != (G, S):
+            raise ValueError(f"select_settings: val_loss must be [G = {G}, S = {S}], got {tuple(loss.shape)}")
+        loss = np.where(np.isnan(loss) | (hits < 0), np.inf, loss)
+        pick = loss.argmin(0)  # (the first minimum = the lowest setting index)
+        pick = np.where(np.isinf(loss[pick, cols]), 0, pick)
+        mean_loss = loss.mean(1)
+        extra = dict(mean_val_loss=mean_loss, best_mean_loss_setting=int(mean_loss.argmin()))
+    none = (hits[pick, cols] < 0) if val_loss is None else np.isinf(loss[pick, cols])
     test_all = np.where(hits < 0, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :])
     val_all = np.where(hits < 0, 0.0, hits / n_val[None, :])
-    test_acc = test_all[pick, cols]
+    test_acc = np.where(none, 0.0, test_all[pick, cols])
     dev = lambda a: float(a.std(ddof=1)) if a.size > 1 else 0.0  # noqa: E731
     mean_val = val_all.mean(1)
     g_best = int(mean_val.argmax())
     return dict(setting=pick.astype(np.int64), val_acc=np.where(none, -1.0, val_all[pick, cols]), test_acc=test_acc,
                 best_epoch=best[pick, cols, 2].astype(np.int64), test_mean=float(test_acc.mean()), test_std=dev(test_acc),
                 mean_val_acc=mean_val, best_mean_setting=g_best, best_mean_test_mean=float(test_all[g_best].mean()),
-                best_mean_test_std=dev(test_all[g_best]))
+                best_mean_test_std=dev(test_all[g_best]), **extra)
 
 
 def classification_report(confusion):
@@ -629,7 +723,7 @@ def prediction_overlap(pred_a, pred_b, labels, masks):
 
 
 def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, seed=0, max_replicas=None, symmetric=0, capture=True, *,
-                keep_best=False):
+                keep_best=False, select="val_hits", patience=0, check_every=None):
     """A hyperparameter grid over all splits of one graph, as stacked runs.  grid: a list of G dicts with the keys lr, weight_decay and
     dropout; masks: bool [S, 3, n].  Replica (g, s) - setting g on split s - sits at position g S + s (setting-major) with
     replica_ids = s: every setting starts split s from the same weights and draws the same dropout masks (common random numbers).
@@ -643,7 +737,18 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     (validation hits, test hits, epoch), n_val, n_test [S], chunks [(g0, g1), ...], seconds, selection = select_settings(best, n_val,
     n_test): the per-split pick, its test accuracy's mean and sample deviation, and the setting of the best mean validation accuracy).
     keep_best=True: every chunk runs with keep_best, and the result gains confusion [G, S, 3, C, C + 1] int64 and pred [G, S, n] uint8 - of
-    every (setting, split) at its best epoch, collected chunk by chunk (the kept weights themselves go with their chunk)."""
+    every (setting, split) at its best epoch, collected chunk by chunk (the kept weights themselves go with their chunk).
+    select, patience, check_every: SplitTrainBatch's and run()'s, passed to every chunk.  With anything but the defaults the result gains
+    best_loss [G, S, 3] float32 and stopped_at [G, S], and with select="val_loss" the selection is
+    select_settings(best, n_val, n_test, val_loss=best_loss[:, :, 1])."""
+    who = "grid_search"
+    select = SELECT_RULES[select_rule(who, select)]
+    patience = whole_number(who, "patience", patience)
+    if check_every is not None:
+        check_every = whole_number(who, "check_every", check_every, least=1)
+    curved = (select, patience) != (SELECT_RULES[0], 0)
+    if check_every is not None and not curved:
+        raise ValueError("grid_search: check_every needs a select or a patience other than the defaults")
     grid = list(grid)
     for g in grid:
         if not isinstance(g, dict) or set(g) != {"lr", "weight_decay", "dropout"}:
@@ -669,6 +774,7 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     x = _dev(x, torch.float32, dev)
     labels_dev = torch.as_tensor(labels_np.astype(np.int64))
     best = np.zeros((len(grid), S, 3), np.int64)
+    best_loss, stopped_at = np.zeros((len(grid), S, 3), np.float32), np.zeros((len(grid), S), np.int64)
     confusion, pred = [], []
     seconds = 0.0
     for g0, g1 in chunks:
@@ -677,9 +783,11 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
         kw = dict(dropout=spread("dropout")) if two_layer else {}
         stb = SplitTrainBatch(adj, x, labels_dev, np.tile(masks, (g1 - g0, 1, 1)), kind=kind, hidden=hidden, lr=spread("lr"),
                               weight_decay=spread("weight_decay"), seed=seed, optimizer="device", replica_ids=np.tile(np.arange(S), g1 - g0),
-                              keep_best=keep_best, **kw)
-        seconds += stb.run(epochs=epochs, capture=capture)["seconds"]
+                              keep_best=keep_best, select=select, patience=patience, **kw)
+        seconds += stb.run(epochs=epochs, capture=capture, check_every=check_every)["seconds"]
         best[g0:g1] = stb.best.cpu().numpy().reshape(g1 - g0, S, 3)
+        if curved:
+            best_loss[g0:g1], stopped_at[g0:g1] = stb.best_loss.reshape(g1 - g0, S, 3), stb.stopped_at.reshape(g1 - g0, S)
         if keep_best:
             conf, pr = stb.confusion_and_predictions()  # (one launch per chunk)
             confusion.append(conf.reshape((g1 - g0, S) + (3, stb.c, stb.c + 1)))
@@ -688,6 +796,9 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     n_val, n_test = masks[:, 1].sum(1).astype(np.int64), masks[:, 2].sum(1).astype(np.int64)
     none = best[:, :, 0] < 0
     kept = dict(confusion=np.concatenate(confusion, 0), pred=np.concatenate(pred, 0)) if keep_best else {}
+    if curved:
+        kept.update(best_loss=best_loss, stopped_at=stopped_at)
+    by_loss = best_loss[:, :, 1] if select == "val_loss" else None
     return dict(val_acc=np.where(none, -1.0, best[:, :, 0] / n_val[None, :]), test_acc=np.where(none, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :]),
                 best_epoch=best[:, :, 2].copy(), best=best, n_val=n_val, n_test=n_test, chunks=chunks, seconds=seconds,
-                selection=select_settings(best, n_val, n_test), **kept)
+                selection=select_settings(best, n_val, n_test, val_loss=by_loss), **kept)

@@ -6,7 +6,8 @@ ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dro
 and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip,
 and the Adam step of the stacked parameters with every replica's own learning rate and weight decay, csrc/adam.hip,
 and the copy of every replica's parameters and logits at its best epoch, csrc/keep_best.hip, with the predictions and the confusion
-counts of stacked logits, csrc/confusion.hip."""
+counts of stacked logits, csrc/confusion.hip, and the evaluation with losses, a learning curve, three selection rules and a patience
+counter, csrc/xent_curve.hip."""
 import ctypes
 import math
 
@@ -19,10 +20,11 @@ from ._rt import _h2d, _ld, _ptr
 
 # the record types of the job tables: those of the ctypes mirrors of include/wdg.h (names, offsets and size; tests/test_abi*.py check
 # the mirrors against the header)
-_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE, _ACM_PACKED_JOB_DTYPE, _KEEP_JOB_DTYPE, _CONFUSION_JOB_DTYPE = (
+_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE, _ACM_PACKED_JOB_DTYPE, _KEEP_JOB_DTYPE, _CONFUSION_JOB_DTYPE, _XENT_CURVE_JOB_DTYPE = (
     np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob, _lib.AcmPackedJob, _lib.KeepJob,
-                          _lib.ConfusionJob))
+                          _lib.ConfusionJob, _lib.XentCurveJob))
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
+SELECT_RULES = ("val_hits", "val_loss", "val_hits_then_loss")  # wdg_xent_curve_job.rule = the index
 
 
 def _check_matrix(table, name, t, shape=None):
@@ -454,6 +456,143 @@ class XentEvalBatch:
         self.hits.zero_()
         self.best.zero_()
         self.best[:, 0] = -1
+
+
+def select_rule(where, select):
+    """-> wdg_xent_curve_job.rule of a rule's name (or of its number); ValueError for another"""
+    if isinstance(select, str) and select in SELECT_RULES:
+        return SELECT_RULES.index(select)
+    if isinstance(select, (int, np.integer)) and not isinstance(select, bool) and 0 <= int(select) < len(SELECT_RULES):
+        return int(select)
+    raise ValueError(f"{where}: unknown selection rule {select!r} (one of {SELECT_RULES})")
+
+
+def whole_number(where, name, value, least=0):
+    """-> int(value); ValueError unless value is an integer (no bool, no float with a fraction, no NaN) of at least `least`"""
+    ok = isinstance(value, (int, np.integer)) and not isinstance(value, bool)
+    if not ok and isinstance(value, (float, np.floating)) and float(value).is_integer():
+        ok = True
+    if not ok or int(value) < least:
+        raise ValueError(f"{where}: {name} must be an integer of at least {least}, got {value!r}")
+    return int(value)
+
+
+class XentCurveBatch:
+    """Job table for wdg_xent_curve_batched_f32 (csrc/xent_curve.hip): the evaluation of an epoch for models whose logits are stacked
+    along the feature axis (XentEvalBatch's layout) WITH the losses - per replica the mean cross-entropy and the hits of its train,
+    validation and test rows, a row of its learning curve, the model selection by one of SELECT_RULES and a patience counter, on the
+    device (include/wdg.h states every step and the order of the fp64 sum; tests/_curve_ref.py restates them in numpy).
+    The table owns best [R, 3] int32 (XentEvalBatch.best's meaning and layout: KeepBestBatch reads it), best_loss [R, 3] fp32 (+inf at
+    first), state [R, 2] int32 (bad, stopped_at; 0, -1 at first), the optional curves and the kernel's work space - one view per entry
+    in best_of, best_loss_of, state_of and curve_of (a (loss [curve_rows, R, 3] fp32, hits [curve_rows, R, 3] int32) pair, or None)."""
+
+    MAX_C, MAX_JOBS = 16, 65535
+
+    def __init__(self, entries):
+        """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device,
+        split [n, R] uint8 device contiguous (0 unused, 1 train, 2 validation, 3 test), n_part [R, 3] integers (a host array or a tensor:
+        the train, validation and test rows of every replica; it is COPIED into the table's own device memory), C, cs (default: C),
+        select (a name of SELECT_RULES or its index; default "val_hits"), patience (default 0: never stops), curve_rows (default 0).
+        Raises ValueError for other shapes, dtypes or strides, C outside 1 .. 16, cs < C, R cs beyond a row, an unknown rule, a negative
+        or non-integer patience or curve_rows, more than 65535 entries."""
+        name = "XentCurveBatch"
+        self.keep = entries
+        n_jobs = self.n_jobs = len(entries)
+        if n_jobs > self.MAX_JOBS:
+            raise ValueError(f"{name}: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
+        shapes, parts = [], []
+        for e in entries:
+            unknown = set(e) - {"logits", "labels", "split", "n_part", "C", "cs", "select", "patience", "curve_rows"}
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            rule = select_rule(name, e.get("select", "val_hits"))
+            patience = whole_number(name, "patience", e.get("patience", 0))
+            curve_rows = whole_number(name, "curve_rows", e.get("curve_rows", 0))
+            split = e.get("split")
+            if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
+                raise ValueError(f"{name}: split must be a contiguous [n, R] uint8 device matrix")
+            n, r = split.shape
+            c = int(e.get("C", 0))
+            cs = int(e.get("cs", c))
+            if not 1 <= c <= self.MAX_C:
+                raise ValueError(f"{name}: {c} classes; the kernel holds 1..{self.MAX_C}")
+            if cs < c:
+                raise ValueError(f"{name}: a replica stride of {cs} columns is narrower than its {c} classes")
+            t = e.get("logits")
+            _check_matrix(name, "logits", t, (n, None))  # (one row of split per row)
+            if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
+                raise ValueError(f"{name}: {r} replicas of {cs} columns do not fit a row of logits ({t.shape[1]} columns, leading dimension {_ld(t)})")
+            lab = e.get("labels")
+            if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
+                raise ValueError(f"{name}: labels must be a contiguous [n] int32 device vector")
+            part = e.get("n_part")
+            part = np.asarray(part.detach().cpu() if isinstance(part, torch.Tensor) else part)
+            if part.shape != (r, 3) or part.dtype.kind not in "iu" or (part < 0).any() or (part > n).any():
+                raise ValueError(f"{name}: n_part must be [R = {r}, 3] row counts (train, validation, test) in 0..n")
+            parts.append(part.astype(np.int32))
+            shapes.append((n, r, c, cs, rule, patience, curve_rows))
+        dev = require_gpu()  # (after the checks that need no device)
+        offsets = lambda lens: np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n_jobs))]).astype(np.int64)  # noqa: E731
+        off = offsets(s_[1] for s_ in shapes)
+        coff = offsets(s_[6] * s_[1] * 3 for s_ in shapes)
+        poff = offsets(int(lib.wdg_xent_curve_partials_len(s_[0], s_[1])) for s_ in shapes)
+        total = max(int(off[-1]), 1)
+        self.n_part = torch.zeros((total, 3), dtype=torch.int32, device=dev)
+        if off[-1]:
+            self.n_part[:int(off[-1])].copy_(torch.from_numpy(np.concatenate(parts, 0)))
+        self.hits = torch.zeros((total, 3), dtype=torch.int32, device=dev)
+        self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
+        self.best_loss = torch.zeros((total, 3), dtype=torch.float32, device=dev)
+        self.state = torch.zeros((total, 2), dtype=torch.int32, device=dev)
+        self.curve_loss = torch.zeros(max(int(coff[-1]), 1), dtype=torch.float32, device=dev)
+        self.curve_hits = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int32, device=dev)
+        self.partials = torch.zeros(max(int(poff[-1]), 1), dtype=torch.float64, device=dev)
+        self.best_of = [self.best[off[i]:off[i + 1]] for i in range(n_jobs)]
+        self.best_loss_of = [self.best_loss[off[i]:off[i + 1]] for i in range(n_jobs)]
+        self.state_of = [self.state[off[i]:off[i + 1]] for i in range(n_jobs)]
+        self.curve_of = [(self.curve_loss[coff[i]:coff[i + 1]].view(s_[6], s_[1], 3), self.curve_hits[coff[i]:coff[i + 1]].view(s_[6], s_[1], 3))
+                         if s_[6] else None for i, s_ in enumerate(shapes)]
+        tab = np.zeros(n_jobs, _XENT_CURVE_JOB_DTYPE)
+        for i, e in enumerate(entries):
+            for k in ("logits", "labels", "split"):
+                tab[k][i] = e[k].data_ptr()
+            tab["ld_logits"][i] = max(_ld(e["logits"]), shapes[i][1] * shapes[i][3])
+            tab["curve_loss"][i] = self.curve_loss.data_ptr() + 4 * coff[i] if shapes[i][6] else 0
+            tab["curve_hits"][i] = self.curve_hits.data_ptr() + 4 * coff[i] if shapes[i][6] else 0
+        tab["n_part"] = self.n_part.data_ptr() + 12 * off[:-1]
+        tab["hits"] = self.hits.data_ptr() + 12 * off[:-1]
+        tab["best"] = self.best.data_ptr() + 12 * off[:-1]
+        tab["best_loss"] = self.best_loss.data_ptr() + 12 * off[:-1]
+        tab["state"] = self.state.data_ptr() + 8 * off[:-1]
+        tab["partials"] = self.partials.data_ptr() + 8 * poff[:-1]
+        for k, field in enumerate(("n", "R", "C", "cs", "rule", "patience", "curve_rows")):
+            tab[field] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
+        self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
+        host = np.ascontiguousarray(tab)
+        check(lib.wdg_xent_curve_check_jobs(ctypes.c_void_p(host.ctypes.data), n_jobs), "wdg_xent_curve_check_jobs")
+        self.table = _h2d(host.view(np.uint8), dev) if n_jobs else torch.empty(0, dtype=torch.uint8)
+        self.reset()
+
+    def launch(self, step):
+        """one evaluation of every entry.  step: a one-element int32 DEVICE tensor, read by the kernel when it runs - the step recorded in
+        best and stopped_at and the row of the curve: a captured launch beside a captured `step.add_(1)` is right on every replay"""
+        check(lib.wdg_xent_curve_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, _step_word("XentCurveBatch.launch", step),
+                                             stream_handle()), "wdg_xent_curve_batched_f32")
+
+    def state_tensors(self):
+        """what a run snapshots and rewinds with its parameters: best, best_loss, state and the curves"""
+        return [self.best, self.best_loss, self.state, self.curve_loss, self.curve_hits]
+
+    def reset(self):
+        """the running best back to "none yet", the losses to +inf, nobody stopped, the curves to zero (the counters are zero between calls)"""
+        self.hits.zero_()
+        self.best.zero_()
+        self.best[:, 0] = -1
+        self.best_loss.fill_(float("inf"))
+        self.state.zero_()
+        self.state[:, 1] = -1
+        self.curve_loss.zero_()
+        self.curve_hits.zero_()
 
 
 class AdamBatch:
