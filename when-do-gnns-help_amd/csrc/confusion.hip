@@ -1,5 +1,5 @@
-// Predictions and confusion counts of many models whose logits are STACKED along the feature axis (xent_eval.hip's layout: replica r's
-// classes are columns r cs .. r cs + C - 1 of one [n, R cs] matrix): per replica and per part of its split (train, validation, test) a
+// Predictions and confusion counts of many models whose logits are STACKED along the feature axis (replica r's classes are columns
+// r cs .. r cs + C - 1 of one [n, R cs] matrix): per replica and per part of its split (train, validation, test) a
 // [C, C + 1] table of (true class, predicted class or "none"), and the prediction of every row.  include/wdg.h states the rule;
 // tests/_confusion_ref.py restates it in numpy.
 //
@@ -7,24 +7,24 @@
 //           gnns_on_syn.py:213-249 train (the loop itself lives upstream of the reference).  It stands in for an argmax, a mask per
 //           split part and a bincount per replica.
 //
-// xent_eval.hip's ownership: one thread owns one (row, replica) pair, adjacent lanes own adjacent replicas of a row; a workgroup owns
+// csrc/stacked_row.h states the layout, the ownership of a (row, replica) pair, its loads and the prediction rule.  A workgroup owns
 // CF_ROWS rows of a job and walks the replicas in chunks.  A chunk is as many replicas as CF_LDS_INTS counters hold (3 C (C + 1) per
 // replica: 10 replicas of 16 classes, 91 of 5): the workgroup counts in LDS (integer adds) and adds one integer per non-zero counter to
 // the job's `counts`.  No floating-point atomics: a sum of integers does not depend on its order.
-#include "wdg_common.h"
+#include "stacked_row.h"
 
 namespace {
 
 using namespace wdg;
 
-constexpr int CF_ROWS = 64, CF_THREADS = 256, CF_MAX_C = 16, CF_LDS_INTS = 8192;
+constexpr int CF_ROWS = 64, CF_THREADS = 256, CF_MAX_C = SR_MAX_C, CF_LDS_INTS = 8192;
 constexpr int CF_MAX_JOBS = 65535;  // gridDim.z: a job per z
 static_assert(3 * CF_MAX_C * (CF_MAX_C + 1) <= CF_LDS_INTS, "a chunk holds at least one replica");
 
 // what the kernel skips: nothing to do, a shape the registers of a thread do not hold, a row narrower than its replicas, a NULL pointer
 __host__ __device__ inline bool cf_skipped(const void *logits, const void *labels, const void *split, const void *counts, const int64_t ld,
                                            const int n, const int R, const int C, const int cs) {
-    return n <= 0 || R <= 0 || C < 1 || C > CF_MAX_C || cs < C || ld < static_cast<int64_t>(R) * cs || !logits || !labels || !split || !counts;
+    return n <= 0 || R <= 0 || sr_bad_classes(C, cs) || ld < static_cast<int64_t>(R) * cs || !logits || !labels || !split || !counts;
 }
 
 __global__ __launch_bounds__(CF_THREADS) void confusion_kernel(const wdg_confusion_job *__restrict__ jobs, const int max_rows) {
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_kernel(const wdg_confusi
     const global_ptr<uint8_t> pred_out = to_global(job->pred);
     int32_t *const counts = job->counts;
     const bool has_pred = job->pred != nullptr;
-    const bool vec_in = ((reinterpret_cast<uintptr_t>(job->logits) | static_cast<uintptr_t>(ld * 4)) & 15) == 0 && (cs & 3) == 0;
+    const bool vec_in = sr_rows16(job->logits, ld, cs);
     const int per = 3 * C * (C + 1);  // counters of a replica
     const int chunk = min(CF_LDS_INTS / per, R);
     const int t = threadIdx.x;
@@ -57,31 +57,11 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_kernel(const wdg_confusi
             const int code = split[static_cast<int64_t>(i) * R + r];
             const int lab = labels[i];
             float z[CF_MAX_C];
-            const global_ptr<const float> p = logits + static_cast<int64_t>(i) * ld + static_cast<int64_t>(r) * cs;
-#pragma unroll
-            for (int g = 0; g < CF_MAX_C / 4; ++g) {  // (the padding columns C .. cs - 1 are never read)
-                if (4 * g >= C) continue;
-                if (vec_in && 4 * g + 3 < C) {
-                    const float4 v = load_f32x4(p + 4 * g);
-                    z[4 * g] = v.x, z[4 * g + 1] = v.y, z[4 * g + 2] = v.z, z[4 * g + 3] = v.w;
-                } else {
-#pragma unroll
-                    for (int k = 4 * g; k < 4 * g + 4; ++k) z[k] = k < C ? p[k] : 0.f;
-                }
-            }
-            // the first maximum; a row with a NaN has no prediction (xent_eval.hip's rule, comparison for comparison)
-            float m = z[0];
-            int pred = 0;
-            bool nan = z[0] != z[0];
-#pragma unroll
-            for (int k = 1; k < CF_MAX_C; ++k) {
-                if (k < C) {
-                    nan = nan || z[k] != z[k];
-                    if (z[k] > m) m = z[k], pred = k;
-                }
-            }
-            if (has_pred) pred_out[static_cast<int64_t>(i) * R + r] = static_cast<uint8_t>(nan ? 255 : pred);
-            if (code >= 1 && code <= 3 && lab >= 0 && lab < C) atomicAdd(&lds[rl * per + ((code - 1) * C + lab) * (C + 1) + (nan ? C : pred)], 1);
+            sr_load(z, logits + static_cast<int64_t>(i) * ld + static_cast<int64_t>(r) * cs, C, vec_in);
+            const sr_max top = sr_first_max(z, C);
+            const int pred = top.nan ? C : top.pred;  // (C: none)
+            if (has_pred) pred_out[static_cast<int64_t>(i) * R + r] = static_cast<uint8_t>(top.nan ? 255 : pred);
+            if (code >= 1 && code <= 3 && lab >= 0 && lab < C) atomicAdd(&lds[rl * per + ((code - 1) * C + lab) * (C + 1) + pred], 1);
         }
         __syncthreads();
         for (int q = t; q < rc * per; q += CF_THREADS) {  // (the counters of consecutive replicas are consecutive in `counts` as well)

@@ -8,13 +8,13 @@
 //           It stands in for wdg_xent_eval_batched_f32's WDG_XENT_EVAL call where a run asks for losses, another selection rule, a
 //           patience or a learning curve.
 //
-// The loads are xent_eval.hip's: one thread owns one (row, replica) pair, adjacent lanes own adjacent replicas of a row.  A workgroup
+// csrc/stacked_row.h states the layout, the ownership of a (row, replica) pair, its loads and the prediction rule.  A workgroup
 // owns XC_ROWS rows of a job and walks the replicas in chunks of XC_RCHUNK: every pair leaves its fp32 loss term and a mark (its
 // part, whether it counts, whether it is a hit) in LDS; then one thread per replica walks the chunk's rows in ASCENDING order and adds
 // the widened terms of each part in fp64 - one partial per (row block, replica, part), stored, not added.  The finishing launch adds
 // a replica's partials in ascending block order, divides, writes the curve row, selects and counts patience.  No floating-point
 // atomic anywhere: the order of the sum is a function of the job's own n; the hits are integers.
-#include "wdg_common.h"
+#include "stacked_row.h"
 
 #include <cmath>
 
@@ -22,7 +22,7 @@ namespace {
 
 using namespace wdg;
 
-constexpr int XC_ROWS = 32, XC_THREADS = 256, XC_RCHUNK = 256, XC_MAX_C = 16;
+constexpr int XC_ROWS = 32, XC_THREADS = 256, XC_RCHUNK = 256, XC_MAX_C = SR_MAX_C;
 constexpr int XC_MAX_JOBS = 65535;  // gridDim.z: a job per z
 constexpr unsigned XC_COUNTS = 4, XC_HIT = 8;  // a pair's mark: its split code (1 .. 3) | the term counts | the row is a hit
 
@@ -34,7 +34,7 @@ __host__ __device__ __forceinline__ bool xc_empty(const J job) {
 }
 template <typename J>
 __host__ __device__ __forceinline__ bool xc_malformed(const J job) {
-    return job->n < 0 || job->R < 0 || job->C < 1 || job->C > XC_MAX_C || job->cs < job->C ||
+    return job->n < 0 || job->R < 0 || sr_bad_classes(job->C, job->cs) ||
            (job->n > 1 && job->ld_logits < static_cast<int64_t>(job->R) * job->cs) || job->rule < 0 || job->rule > 2 || job->patience < 0 ||
            job->curve_rows < 0 || (job->curve_rows > 0 && (job->curve_loss == nullptr || job->curve_hits == nullptr)) ||
            (job->n > 0 && job->R > 0 && (job->logits == nullptr || job->labels == nullptr || job->split == nullptr || job->n_part == nullptr ||
@@ -55,8 +55,7 @@ __global__ __launch_bounds__(XC_THREADS) void xent_curve_kernel(const wdg_xent_c
     const global_ptr<const uint8_t> split = to_global(job->split);
     const global_ptr<double> partials = to_global(job->partials);
     const int64_t ld = job->ld_logits;
-    // (uniform) 16-byte loads where the job's pointer, leading dimension and replica stride allow
-    const bool vec_in = ((reinterpret_cast<uintptr_t>(job->logits) | static_cast<uintptr_t>(ld * 4)) & 15) == 0 && (cs & 3) == 0;
+    const bool vec_in = sr_rows16(job->logits, ld, cs);
     const int t = threadIdx.x;
     for (int r0 = 0; r0 < R; r0 += XC_RCHUNK) {
         const int rc = min(XC_RCHUNK, R - r0);
@@ -69,43 +68,16 @@ __global__ __launch_bounds__(XC_THREADS) void xent_curve_kernel(const wdg_xent_c
             unsigned mark = 0;
             if (code >= 1 && code <= 3) {  // (the padding columns C .. cs - 1 are never read)
                 float z[XC_MAX_C];
-                const global_ptr<const float> p = logits + static_cast<int64_t>(i) * ld + static_cast<int64_t>(r) * cs;
-#pragma unroll
-                for (int g = 0; g < XC_MAX_C / 4; ++g) {
-                    if (4 * g >= C) continue;
-                    if (vec_in && 4 * g + 3 < C) {
-                        const float4 v = load_f32x4(p + 4 * g);
-                        z[4 * g] = v.x, z[4 * g + 1] = v.y, z[4 * g + 2] = v.z, z[4 * g + 3] = v.w;
-                    } else {
-#pragma unroll
-                        for (int k = 4 * g; k < 4 * g + 4; ++k) z[k] = k < C ? p[k] : 0.f;
-                    }
-                }
-                // the first maximum; a row with a NaN has no prediction (xent_eval.hip's rule).  m is the maximum the comparisons
-                // leave: a NaN survives below whatever they made of it - it makes its own e a NaN, and with it the sum
-                float m = z[0], zl = z[0];
-                int pred = 0;
-                bool nan = z[0] != z[0];
-#pragma unroll
-                for (int k = 1; k < XC_MAX_C; ++k) {
-                    if (k < C) {
-                        nan = nan || z[k] != z[k];
-                        if (z[k] > m) m = z[k], pred = k;
-                        if (k == lab) zl = z[k];
-                    }
-                }
+                sr_load(z, logits + static_cast<int64_t>(i) * ld + static_cast<int64_t>(r) * cs, C, vec_in);
+                const sr_max top = sr_first_max(z, C);
                 mark = code;
-                if (!nan && pred == lab) mark |= XC_HIT;
+                if (!top.nan && top.pred == lab) mark |= XC_HIT;
                 if (lab >= 0 && lab < C) {  // (a label outside 0 .. C - 1 adds nothing)
-                    float s = 0.f;
+                    float zl = z[0];  // z[lab], by compile-time indices: the array stays in registers
 #pragma unroll
-                    for (int k = 0; k < XC_MAX_C; ++k) {
-                        if (k < C) {
-                            const float e = expf(z[k] - m);
-                            s = k == 0 ? e : s + e;
-                        }
-                    }
-                    term = logf(s) - (zl - m);
+                    for (int k = 1; k < XC_MAX_C; ++k)
+                        if (k == lab) zl = z[k];
+                    term = logf(sr_exp_sum(z, C, top.m)) - (zl - top.m);
                     mark |= XC_COUNTS;
                 }
             }

@@ -7,24 +7,24 @@
 //           for the softmax / scatter / argmax / gather / where launches of sweep.TrainBatch.train_step and eval_step, which need
 //           a [J, n, c] layout and splits of equal length.
 //
-// One thread owns one (row, replica) pair; adjacent lanes own adjacent replicas of a row, so a wave reads the split codes as
-// consecutive bytes and the logits as one contiguous piece of a row.  A workgroup owns XE_ROWS rows of a job and walks the replicas
-// in chunks of XE_RCHUNK: the hits of a chunk are counted in LDS (integer adds) and one integer per workgroup and non-zero counter is
-// added to the job's `hits`.  A second launch of the same call compares, records and zeroes them.  No floating-point atomics: a pair's
-// gradient depends on its own C logits alone, and a sum of integers does not depend on its order.
-#include "wdg_common.h"
+// csrc/stacked_row.h states the layout, the ownership of a (row, replica) pair, its loads and the prediction rule.  A workgroup owns
+// XE_ROWS rows of a job and walks the replicas in chunks of XE_RCHUNK: the hits of a chunk are counted in LDS (integer adds) and one
+// integer per workgroup and non-zero counter is added to the job's `hits`.  A second launch of the same call compares, records and
+// zeroes them.  No floating-point atomics: a pair's gradient depends on its own C logits alone, and a sum of integers does not depend
+// on its order.
+#include "stacked_row.h"
 
 namespace {
 
 using namespace wdg;
 
-constexpr int XE_ROWS = 64, XE_THREADS = 256, XE_RCHUNK = 256, XE_MAX_C = 16;
+constexpr int XE_ROWS = 64, XE_THREADS = 256, XE_RCHUNK = 256, XE_MAX_C = SR_MAX_C;
 constexpr int XE_MAX_JOBS = 65535;  // gridDim.z: a job per z
 
 // what both launches skip: nothing to do, or a shape the registers of a thread do not hold (the entry refuses max_cols > 16; a job
 // that lies about its own C must still not be indexed out of bounds)
 __device__ __forceinline__ bool xe_skipped(const int n, const int R, const int C, const int cs) {
-    return n <= 0 || R <= 0 || C < 1 || C > XE_MAX_C || cs < C;
+    return n <= 0 || R <= 0 || sr_bad_classes(C, cs);
 }
 
 template <bool GRAD, bool EVAL>
@@ -42,8 +42,7 @@ __global__ __launch_bounds__(XE_THREADS) void xent_eval_kernel(const wdg_xent_jo
     const global_ptr<const float> inv_n_train = to_global(job->inv_n_train);
     const int64_t ld = job->ld_logits, ldd = job->ld_dlogits;
     // (uniform) 16-byte accesses where the job's pointers, leading dimensions and replica stride allow
-    const bool vec_in = ((reinterpret_cast<uintptr_t>(job->logits) | static_cast<uintptr_t>(ld * 4)) & 15) == 0 && (cs & 3) == 0;
-    const bool vec_out = GRAD && ((reinterpret_cast<uintptr_t>(job->dlogits) | static_cast<uintptr_t>(ldd * 4)) & 15) == 0 && (cs & 3) == 0;
+    const bool vec_in = sr_rows16(job->logits, ld, cs), vec_out = GRAD && sr_rows16(job->dlogits, ldd, cs);
     const int t = threadIdx.x;
     for (int r0 = 0; r0 < R; r0 += XE_RCHUNK) {
         const int rc = min(XE_RCHUNK, R - r0);
@@ -59,52 +58,17 @@ __global__ __launch_bounds__(XE_THREADS) void xent_eval_kernel(const wdg_xent_jo
             const bool train = GRAD && code == 1, scored = EVAL && (code == 2 || code == 3);
             const int lab = labels[i];
             float z[XE_MAX_C];
-            if (train || scored) {  // (the padding columns C .. cs - 1 are never read)
-                const global_ptr<const float> p = logits + static_cast<int64_t>(i) * ld + static_cast<int64_t>(r) * cs;
-#pragma unroll
-                for (int g = 0; g < XE_MAX_C / 4; ++g) {
-                    if (4 * g >= C) continue;
-                    if (vec_in && 4 * g + 3 < C) {
-                        const float4 v = load_f32x4(p + 4 * g);
-                        z[4 * g] = v.x, z[4 * g + 1] = v.y, z[4 * g + 2] = v.z, z[4 * g + 3] = v.w;
-                    } else {
-#pragma unroll
-                        for (int k = 4 * g; k < 4 * g + 4; ++k) z[k] = k < C ? p[k] : 0.f;
-                    }
-                }
-            }
+            if (train || scored) sr_load(z, logits + static_cast<int64_t>(i) * ld + static_cast<int64_t>(r) * cs, C, vec_in);
             if (scored) {
-                // the first maximum; a row with a NaN has no prediction
-                float m = z[0];
-                int pred = 0;
-                bool nan = z[0] != z[0];
-#pragma unroll
-                for (int k = 1; k < XE_MAX_C; ++k) {
-                    if (k < C) {
-                        nan = nan || z[k] != z[k];
-                        if (z[k] > m) m = z[k], pred = k;
-                    }
-                }
-                if (!nan && pred == lab) atomicAdd(&counts[(code == 3 ? XE_RCHUNK : 0) + rl], 1);
+                const sr_max top = sr_first_max(z, C);
+                if (!top.nan && top.pred == lab) atomicAdd(&counts[(code == 3 ? XE_RCHUNK : 0) + rl], 1);
             }
             if (GRAD) {
                 float o[XE_MAX_C];
 #pragma unroll
                 for (int k = 0; k < XE_MAX_C; ++k) o[k] = 0.f;
                 if (train) {
-                    // m = max z (a NaN survives below whatever the comparisons made of it: it makes its own e a NaN, and with it s)
-                    float m = z[0];
-#pragma unroll
-                    for (int k = 1; k < XE_MAX_C; ++k)
-                        if (k < C && z[k] > m) m = z[k];
-                    float s = 0.f;
-#pragma unroll
-                    for (int k = 0; k < XE_MAX_C; ++k) {
-                        if (k < C) {
-                            z[k] = expf(z[k] - m);
-                            s = k == 0 ? z[0] : s + z[k];
-                        }
-                    }
+                    const float s = sr_exp_sum(z, C, sr_first_max(z, C).m);  // (a NaN among the logits makes s a NaN)
                     const float inv = inv_n_train[r];
 #pragma unroll
                     for (int k = 0; k < XE_MAX_C; ++k)

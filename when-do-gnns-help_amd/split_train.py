@@ -35,6 +35,23 @@ from .train import (SELECT_RULES, XENT_EVAL, XENT_GRAD, AdamBatch, ConfusionBatc
 MAX_CLASSES = XentEvalBatch.MAX_C
 
 
+def _host(a):
+    """a tensor (host or device) or anything array-like -> a numpy array"""
+    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
+
+
+def _default_selection(select, patience, curve_epochs=0):
+    """whether a run evaluates with csrc/xent_eval.hip alone: no losses, no patience, no learning curve"""
+    return (select, patience, curve_epochs) == (SELECT_RULES[0], 0, 0)
+
+
+def _accuracies(best, n_val, n_test):
+    """best int [..., S, 3] (validation hits of the best epoch, -1: none; test hits at it; its epoch), n_val, n_test [S]
+    -> (val_acc, test_acc) float64 [..., S]: -1 and 0 for a replica without a best epoch"""
+    none = best[..., 0] < 0
+    return np.where(none, -1.0, best[..., 0] / n_val), np.where(none, 0.0, best[..., 1] / np.maximum(n_test, 1))
+
+
 def masks_from_indices(n, splits):
     """splits: a list of (train, valid, test) index arrays, one triple per replica -> bool [R, 3, n]"""
     masks = np.zeros((len(splits), 3, n), bool)
@@ -53,7 +70,7 @@ def random_masks(labels, R, seed, train_frac=0.6):
     """R draws of utils.util_funcs.random_disassortative_splits (class-balanced train rows, 20 % validation, the rest test) from
     torch's CPU generator seeded with `seed` (the caller's generator state is put back) -> bool [R, 3, n]"""
     from .utils.util_funcs import random_disassortative_splits
-    labels = torch.as_tensor(np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)).long()
+    labels = torch.as_tensor(_host(labels)).long()
     c = int(labels.max()) + 1
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(int(seed))
@@ -76,9 +93,9 @@ def xavier(fan_in, fan_out, gen):
 # the checks of a stacked run's labels, masks and replica ids (`who` names the class in the messages: acm_split_train shares them)
 def _labels_and_masks(who, labels, masks):
     """-> (labels int64 [n], masks bool [R, 3, n]) as numpy arrays"""
-    labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
+    labels_np = _host(labels).reshape(-1).astype(np.int64)
     n = labels_np.shape[0]
-    masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+    masks = _host(masks)
     if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[2] != n or masks.shape[0] < 1:
         raise ValueError(f"{who}: masks must be a bool array [R, 3, n = {n}], got {masks.dtype} {tuple(masks.shape)}")
     return labels_np, masks
@@ -273,7 +290,7 @@ class SplitTrainBatch:
                                         inv_n_train=self.inv_n_train, C=self.c, cs=self.cs)])
         self.best = self.xent.best_of[0]  # [R, 3] int32: validation hits of the best epoch (-1: none yet), test hits at it, its epoch
         self.curve = None
-        if (self.select, self.patience, self.curve_epochs) != (SELECT_RULES[0], 0, 0):
+        if not _default_selection(self.select, self.patience, self.curve_epochs):
             # the evaluation with losses: its table owns the running best from here on
             counts = np.stack([self.n_train, self.n_val, self.n_test], 1)
             self.curve = XentCurveBatch([dict(logits=self.logits, labels=self.labels, split=self.split, n_part=counts, C=self.c, cs=self.cs,
@@ -467,9 +484,8 @@ class SplitTrainBatch:
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         best = self.best.cpu().numpy()
-        none = best[:, 0] < 0
-        out = dict(val_acc=torch.from_numpy(np.where(none, -1.0, best[:, 0] / self.n_val)),
-                   test_acc=torch.from_numpy(np.where(none, 0.0, best[:, 1] / np.maximum(self.n_test, 1))),
+        val_acc, test_acc = _accuracies(best, self.n_val, self.n_test)
+        out = dict(val_acc=torch.from_numpy(val_acc), test_acc=torch.from_numpy(test_acc),
                    best_epoch=torch.from_numpy(best[:, 2].astype(np.int64)), seconds=dt, replicas_per_s=self.R / dt, epochs=epochs)
         if self.curve is not None:
             loss = self.best_loss
@@ -704,9 +720,8 @@ def prediction_overlap(pred_a, pred_b, labels, masks):
         p float64 [S]: the two-sided exact binomial p-value of the discordant pair (only a against only b at probability 1/2 - the exact
         McNemar test, scipy.stats.binomtest; 1 where no row is discordant))"""
     from scipy.stats import binomtest
-    labels = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
-    pa, pb = (np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p) for p in (pred_a, pred_b))
-    masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+    labels = _host(labels).reshape(-1).astype(np.int64)
+    pa, pb, masks = _host(pred_a), _host(pred_b), _host(masks)
     n = labels.shape[0]
     if pa.ndim != 2 or pa.shape != pb.shape or pa.shape[1] != n or masks.dtype != np.bool_ or masks.shape != (pa.shape[0], 3, n):
         raise ValueError("prediction_overlap: pred_a and pred_b [S, n], labels [n] and bool masks [S, 3, n] expected")
@@ -746,7 +761,7 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     patience = whole_number(who, "patience", patience)
     if check_every is not None:
         check_every = whole_number(who, "check_every", check_every, least=1)
-    curved = (select, patience) != (SELECT_RULES[0], 0)
+    curved = not _default_selection(select, patience)
     if check_every is not None and not curved:
         raise ValueError("grid_search: check_every needs a select or a patience other than the defaults")
     grid = list(grid)
@@ -755,14 +770,14 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
             raise ValueError("grid_search: every setting is a dict with exactly the keys lr, weight_decay and dropout")
     if kind not in SplitTrainBatch.KINDS:
         raise ValueError(f"grid_search: unknown model kind {kind!r} (one of {SplitTrainBatch.KINDS})")
-    masks = np.asarray(masks.cpu() if isinstance(masks, torch.Tensor) else masks)
+    masks = _host(masks)
     if masks.dtype != np.bool_ or masks.ndim != 3 or masks.shape[1] != 3 or masks.shape[0] < 1:
         raise ValueError(f"grid_search: masks must be a bool array [S, 3, n], got {masks.dtype} {tuple(masks.shape)}")
     S, n = masks.shape[0], masks.shape[2]
     two_layer = kind in ("gcn", "mlp2")
     if not two_layer and any(float(g["dropout"]) != 0.0 for g in grid):
         raise ValueError(f"grid_search: kind {kind!r} has no hidden layer to drop units of: every setting's dropout must be 0")
-    labels_np = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
+    labels_np = _host(labels).reshape(-1)
     cs = SplitTrainBatch._class_stride(int(labels_np.max()) + 1 if labels_np.size else 1)
     if max_replicas is None:
         max_replicas = default_max_replicas(n, int(hidden) if two_layer else cs, kind, S)
@@ -794,11 +809,11 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
             pred.append(pr.reshape(g1 - g0, S, n))
         del stb
     n_val, n_test = masks[:, 1].sum(1).astype(np.int64), masks[:, 2].sum(1).astype(np.int64)
-    none = best[:, :, 0] < 0
+    val_acc, test_acc = _accuracies(best, n_val, n_test)
     kept = dict(confusion=np.concatenate(confusion, 0), pred=np.concatenate(pred, 0)) if keep_best else {}
     if curved:
         kept.update(best_loss=best_loss, stopped_at=stopped_at)
     by_loss = best_loss[:, :, 1] if select == "val_loss" else None
-    return dict(val_acc=np.where(none, -1.0, best[:, :, 0] / n_val[None, :]), test_acc=np.where(none, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :]),
+    return dict(val_acc=val_acc, test_acc=test_acc,
                 best_epoch=best[:, :, 2].copy(), best=best, n_val=n_val, n_test=n_test, chunks=chunks, seconds=seconds,
                 selection=select_settings(best, n_val, n_test, val_loss=by_loss), **kept)

@@ -1,13 +1,15 @@
-"""Training on the device: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the
-models of gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249) inside one launch of csrc/head_train.hip, and the hidden layer's
-ReLU + dropout of many two-layer models (GCN-2, MLP-2) in one launch of csrc/dropout.hip, and the channel mix of many ACM layers
-(ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel weighted per node) with its backward pass, csrc/acm_mix.hip
-(and, for the stacked class-width layers of acm_split_train, several replicas per 16 lanes: csrc/acm_mix_packed.hip),
-and the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits, csrc/xent_eval.hip,
-and the Adam step of the stacked parameters with every replica's own learning rate and weight decay, csrc/adam.hip,
-and the copy of every replica's parameters and logits at its best epoch, csrc/keep_best.hip, with the predictions and the confusion
-counts of stacked logits, csrc/confusion.hip, and the evaluation with losses, a learning curve, three selection rules and a patience
-counter, csrc/xent_curve.hip."""
+"""Training on the device: the job tables of the training kernels, one launch per table.
+- csrc/head_train.hip: every epoch of many multinomial logistic heads (SGC-1 on the cached A_hat X, MLP-1 on X: the models of
+  gnns_on_syn.py:109-154 and gnns_on_syn.py:213-249)
+- csrc/dropout.hip: the hidden layer's ReLU + dropout of many two-layer models (GCN-2, MLP-2)
+- csrc/acm_mix.hip: the channel mix of many ACM layers (ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel
+  weighted per node) with its backward pass
+- csrc/acm_mix_packed.hip: the same for the stacked class-width layers of acm_split_train, several replicas per 16 lanes
+- csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
+- csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
+- csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
+- csrc/confusion.hip: the predictions and the confusion counts of stacked logits
+- csrc/xent_curve.hip: the evaluation with losses, a learning curve, three selection rules and a patience counter"""
 import ctypes
 import math
 
@@ -20,9 +22,15 @@ from ._rt import _h2d, _ld, _ptr
 
 # the record types of the job tables: those of the ctypes mirrors of include/wdg.h (names, offsets and size; tests/test_abi*.py check
 # the mirrors against the header)
-_HEAD_JOB_DTYPE, _DROPOUT_JOB_DTYPE, _ACM_JOB_DTYPE, _XENT_JOB_DTYPE, _ADAM_JOB_DTYPE, _ACM_PACKED_JOB_DTYPE, _KEEP_JOB_DTYPE, _CONFUSION_JOB_DTYPE, _XENT_CURVE_JOB_DTYPE = (
-    np.dtype(s) for s in (_lib.HeadTrainJob, _lib.DropoutJob, _lib.AcmMixJob, _lib.XentJob, _lib.AdamJob, _lib.AcmPackedJob, _lib.KeepJob,
-                          _lib.ConfusionJob, _lib.XentCurveJob))
+_HEAD_JOB_DTYPE = np.dtype(_lib.HeadTrainJob)
+_DROPOUT_JOB_DTYPE = np.dtype(_lib.DropoutJob)
+_ACM_JOB_DTYPE = np.dtype(_lib.AcmMixJob)
+_ACM_PACKED_JOB_DTYPE = np.dtype(_lib.AcmPackedJob)
+_XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
+_ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
+_KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
+_CONFUSION_JOB_DTYPE = np.dtype(_lib.ConfusionJob)
+_XENT_CURVE_JOB_DTYPE = np.dtype(_lib.XentCurveJob)
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
 SELECT_RULES = ("val_hits", "val_loss", "val_hits_then_loss")  # wdg_xent_curve_job.rule = the index
 
@@ -43,6 +51,20 @@ def _step_word(where, step):
     if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
         raise ValueError(f"{where}: a one-element int32 device tensor expected as the step word")
     return _ptr(step)
+
+
+def _offsets(lens, n):
+    """the lengths of n consecutive blocks -> int64 [n + 1]: where each starts, and the end of the last"""
+    return np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n))]).astype(np.int64)
+
+
+def _upload(tab, n, dev, check_jobs=None):
+    """the device copy of a table of n records (an empty tensor for none) - after the host-side check of the records, where the
+    kernel has one (check_jobs: its name in lib)"""
+    host = np.ascontiguousarray(tab)
+    if check_jobs is not None:
+        check(getattr(lib, check_jobs)(ctypes.c_void_p(host.ctypes.data), n), check_jobs)
+    return _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
 
 
 class HeadTrainBatch:
@@ -78,8 +100,7 @@ class HeadTrainBatch:
                 raise ValueError("HeadTrainBatch: one label per row of M")
             if tuple(w.shape) != (mat.shape[1], c) or w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
                 raise ValueError("HeadTrainBatch: W must be a contiguous [F, C] fp32 device matrix")
-        sizes = np.fromiter((p_[5].numel() for p_ in problems), np.int64, n)
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        offs = _offsets((p_[5].numel() for p_ in problems), n)
         self._moments = torch.zeros((2, max(int(offs[-1]), 1)), dtype=torch.float32, device=dev)
         self.m = [self._moments[0, offs[i]:offs[i + 1]].view(problems[i][5].shape) for i in range(n)]
         self.v = [self._moments[1, offs[i]:offs[i + 1]].view(problems[i][5].shape) for i in range(n)]
@@ -98,7 +119,7 @@ class HeadTrainBatch:
         tab["F"], tab["C"] = col(lambda p_: p_[0].shape[1]), np.asarray(classes, np.int64)
         self.max_f, self.max_c = int(tab["F"].max(initial=1)), int(tab["C"].max(initial=1))
         self.bytes_per_epoch = int(sum((p_[2].shape[0] + p_[3].shape[0] + p_[4].shape[0]) * p_[0].shape[1] * 4 for p_ in problems))
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n, dev)
         self.best = self.best[:n]
 
     def launch(self, epochs, step0=0):
@@ -155,7 +176,7 @@ class DropoutBatch:
         tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
         tab["stream"] = col(lambda e: int(e[2]))
         self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n, dev)
 
     def launch(self, step):
         """step: a one-element int32 DEVICE tensor whose bits are the uint32 step - the kernel reads it when it runs, so a captured
@@ -185,7 +206,7 @@ class _AcmMixTable:
     """What the job tables of the two channel-mix kernels share: the activation flags, the key checks, the "all six gradient tensors or
     none" rule, the overlap check, the pointer / leading-dimension fill, aux and the partial sums of the parameter gradients (owned by
     the table, one slice per entry) and the two launches.  A subclass states its record type and entry points, its keys and, in
-    _shape(), its shape rules; _check_alignment() and _check_jobs() are there for the kernel that has such rules."""
+    _shape(), its shape rules; _check_alignment() and _CHECK_JOBS are there for the kernel that has such rules."""
 
     MAX_JOBS, TILE = 65535, 64
     _MATS = ("low", "high", "high_agg", "ident", "out", "d_out", "d_low", "d_high", "d_ident")
@@ -194,6 +215,7 @@ class _AcmMixTable:
     _OUTPUTS = ("out", "out_t", "d_low", "d_high", "d_ident", "d_att", "d_wmix")
     # of a subclass: _DTYPE, _FORWARD, _BACKWARD (the record type and the entry points), _EXTRA (its keys besides _MATS and _VECS),
     # _REQUIRED (in the order of the message)
+    _CHECK_JOBS = None  # (the kernel without a host-side check of its records)
 
     def __init__(self, entries, relu):
         name = type(self).__name__
@@ -237,8 +259,7 @@ class _AcmMixTable:
                         raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
             shapes.append((fields, width, aux_shape, -(-rows // self.TILE) * part_len))
         dev = require_gpu()  # (after the checks that need no device)
-        offsets = lambda lens: np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n))]).astype(np.int64)  # noqa: E731
-        aux_off, part_off = offsets(int(np.prod(s_[2])) for s_ in shapes), offsets(s_[3] for s_ in shapes)
+        aux_off, part_off = _offsets((int(np.prod(s_[2])) for s_ in shapes), n), _offsets((s_[3] for s_ in shapes), n)
         self.aux = torch.zeros(max(int(aux_off[-1]), 1), dtype=torch.float32, device=dev)
         self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
         tab = np.zeros(n, self._DTYPE)
@@ -258,15 +279,10 @@ class _AcmMixTable:
         self.max_rows = int(tab["rows"].max(initial=0))
         self._widest = max((s_[1] for s_ in shapes), default=0)
         self.aux_of = [self.aux[aux_off[i]:aux_off[i + 1]].view(shapes[i][2]) for i in range(n)]
-        host = np.ascontiguousarray(tab)
-        self._check_jobs(host)
-        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n, dev, self._CHECK_JOBS)
 
     def _check_alignment(self, k, t, rows):
         """(the kernel that takes any alignment)"""
-
-    def _check_jobs(self, host):
-        """(the kernel without a host-side check of its records)"""
 
     def launch(self):
         """out (and out_t, aux) of every entry"""
@@ -319,6 +335,7 @@ class AcmMixPackedBatch(_AcmMixTable):
     STRIDES = (4, 8, 16)
     _DTYPE, _FORWARD, _BACKWARD = _ACM_PACKED_JOB_DTYPE, "wdg_acm_mix_packed_f32", "wdg_acm_mix_packed_backward_f32"
     _EXTRA, _REQUIRED = ("cols",), ("cols", "low", "high", "ident", "att", "wmix", "out")
+    _CHECK_JOBS = "wdg_acm_mix_packed_check_jobs"
 
     def __init__(self, entries, relu):
         """entries: list of dicts - cols (int), att [reps, 3, stride] and wmix [reps, 3, 3] or [reps, 9] (fp32 device, contiguous: reps
@@ -350,9 +367,6 @@ class AcmMixPackedBatch(_AcmMixTable):
         if k in ("att", "d_att") and t.data_ptr() % 16:
             raise ValueError(f"AcmMixPackedBatch: {k} must start at a 16-byte boundary")
 
-    def _check_jobs(self, host):
-        check(lib.wdg_acm_mix_packed_check_jobs(ctypes.c_void_p(host.ctypes.data), self.n_jobs), "wdg_acm_mix_packed_check_jobs")
-
 
 def acm_operand_gradient(d_pair, t_pair, d_full, width):
     """d(M W) = [A_hat^T dP_L | dP_H - A_hat^T dP_H | dP_I] from d_pair = [dP_L | dP_H] and t_pair = A_hat^T d_pair (the kernel has
@@ -369,6 +383,41 @@ def acm_sgc_weight_gradient(g, gwa, gwb, w):
     g[..., 2 * w:].copy_(gwb[..., w:])
 
 
+_STACKED_MAX_C = 16  # SR_MAX_C of csrc/stacked_row.h
+
+
+def _stacked_logits_entry(table, e, keys, mats, own=lambda e: ()):
+    """The checks that every table over STACKED logits (csrc/stacked_row.h: replica r owns columns r cs .. r cs + C - 1 of a row) makes
+    of an entry e, in the order they are reported: no key outside `keys`; own(e) - the table's checks of its own settings; split a
+    contiguous [n, R] uint8 device matrix; C in 1..16 and cs >= C; every matrix of `mats` (only "logits" is required) [n, >= R cs]
+    fp32 on the device; labels a contiguous [n] int32 device vector.  -> (n, R, C, cs) + own(e)"""
+    unknown = set(e) - set(keys)
+    if unknown:
+        raise ValueError(f"{table}: unknown keys {sorted(unknown)}")
+    settings = tuple(own(e))
+    split = e.get("split")
+    if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
+        raise ValueError(f"{table}: split must be a contiguous [n, R] uint8 device matrix")
+    n, r = split.shape
+    c = int(e.get("C", 0))
+    cs = int(e.get("cs", c))
+    if not 1 <= c <= _STACKED_MAX_C:
+        raise ValueError(f"{table}: {c} classes; the kernel holds 1..{_STACKED_MAX_C}")
+    if cs < c:
+        raise ValueError(f"{table}: a replica stride of {cs} columns is narrower than its {c} classes")
+    for name in mats:
+        t = e.get(name)
+        if t is None and name != "logits":
+            continue
+        _check_matrix(table, name, t, (n, None))  # (one row of split per row)
+        if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
+            raise ValueError(f"{table}: {r} replicas of {cs} columns do not fit a row of {name} ({t.shape[1]} columns, leading dimension {_ld(t)})")
+    lab = e.get("labels")
+    if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
+        raise ValueError(f"{table}: labels must be a contiguous [n] int32 device vector")
+    return (n, r, c, cs) + settings
+
+
 class XentEvalBatch:
     """Job table for wdg_xent_eval_batched_f32 (csrc/xent_eval.hip): the tail of an epoch for models whose logits are stacked along
     the feature axis - replica r of an entry owns columns r cs .. r cs + C - 1 of its [n, R cs] logits.  launch(XENT_GRAD) writes the
@@ -376,7 +425,7 @@ class XentEvalBatch:
     replica's validation and test hits and keeps the best (include/wdg.h states both; tests/_xent_ref.py restates them in numpy).
     The table owns self.hits and self.best (one [R, 2] / [R, 3] int32 view per entry in hits_of / best_of)."""
 
-    MAX_C, MAX_JOBS = 16, 65535
+    MAX_C, MAX_JOBS = _STACKED_MAX_C, 65535
 
     def __init__(self, entries):
         """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), dlogits the same or
@@ -387,39 +436,17 @@ class XentEvalBatch:
         n_jobs = self.n_jobs = len(entries)
         if n_jobs > self.MAX_JOBS:
             raise ValueError(f"XentEvalBatch: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
-        self.has_grad = n_jobs > 0
+        self.has_grad = n_jobs > 0 and all(e.get("dlogits") is not None for e in entries)
         shapes = []
         for e in entries:
-            unknown = set(e) - {"logits", "dlogits", "labels", "split", "inv_n_train", "C", "cs"}
-            if unknown:
-                raise ValueError(f"XentEvalBatch: unknown keys {sorted(unknown)}")
-            split = e.get("split")
-            if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
-                raise ValueError("XentEvalBatch: split must be a contiguous [n, R] uint8 device matrix")
-            n, r = split.shape
-            c = int(e.get("C", 0))
-            cs = int(e.get("cs", c))
-            if not 1 <= c <= self.MAX_C:
-                raise ValueError(f"XentEvalBatch: {c} classes; the kernel holds 1..{self.MAX_C}")
-            if cs < c:
-                raise ValueError(f"XentEvalBatch: a replica stride of {cs} columns is narrower than its {c} classes")
-            for name in ("logits", "dlogits"):
-                t = e.get(name)
-                if t is None and name == "dlogits":
-                    self.has_grad = False
-                    continue
-                _check_matrix("XentEvalBatch", name, t, (n, None))  # (one row of split per row)
-                if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
-                    raise ValueError(f"XentEvalBatch: {r} replicas of {cs} columns do not fit a row of {name} ({t.shape[1]} columns, leading dimension {_ld(t)})")
-            lab, inv = e.get("labels"), e.get("inv_n_train")
-            if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
-                raise ValueError("XentEvalBatch: labels must be a contiguous [n] int32 device vector")
-            if not isinstance(inv, torch.Tensor) or inv.dtype != torch.float32 or not inv.is_cuda or not inv.is_contiguous() or tuple(inv.shape) != (r,):
+            shapes.append(_stacked_logits_entry("XentEvalBatch", e, ("logits", "dlogits", "labels", "split", "inv_n_train", "C", "cs"),
+                                                ("logits", "dlogits")))
+            inv = e.get("inv_n_train")
+            if not isinstance(inv, torch.Tensor) or inv.dtype != torch.float32 or not inv.is_cuda or not inv.is_contiguous() or \
+                    tuple(inv.shape) != (shapes[-1][1],):
                 raise ValueError("XentEvalBatch: inv_n_train must be a contiguous [R] fp32 device vector")
-            shapes.append((n, r, c, cs))
         dev = require_gpu()  # (after the checks that need no device)
-        reps = np.fromiter((s_[1] for s_ in shapes), np.int64, n_jobs)
-        off = np.concatenate([[0], np.cumsum(reps)]).astype(np.int64)
+        off = _offsets((s_[1] for s_ in shapes), n_jobs)
         total = max(int(off[-1]), 1)
         self.hits = torch.zeros((total, 2), dtype=torch.int32, device=dev)
         self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
@@ -437,7 +464,7 @@ class XentEvalBatch:
         for k, name in enumerate(("n", "R", "C", "cs")):
             tab[name] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
         self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
-        self.table = _h2d(tab.view(np.uint8), dev) if n_jobs else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n_jobs, dev)
 
     def launch(self, flags, step=None):
         """flags: XENT_GRAD, XENT_EVAL or both.  step (needed with XENT_EVAL): a one-element int32 DEVICE tensor - the kernel reads it
@@ -486,7 +513,7 @@ class XentCurveBatch:
     first), state [R, 2] int32 (bad, stopped_at; 0, -1 at first), the optional curves and the kernel's work space - one view per entry
     in best_of, best_loss_of, state_of and curve_of (a (loss [curve_rows, R, 3] fp32, hits [curve_rows, R, 3] int32) pair, or None)."""
 
-    MAX_C, MAX_JOBS = 16, 65535
+    MAX_C, MAX_JOBS = _STACKED_MAX_C, 65535
 
     def __init__(self, entries):
         """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device,
@@ -501,41 +528,22 @@ class XentCurveBatch:
         if n_jobs > self.MAX_JOBS:
             raise ValueError(f"{name}: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
         shapes, parts = [], []
+        settings = lambda e: (select_rule(name, e.get("select", "val_hits")), whole_number(name, "patience", e.get("patience", 0)),  # noqa: E731
+                              whole_number(name, "curve_rows", e.get("curve_rows", 0)))
         for e in entries:
-            unknown = set(e) - {"logits", "labels", "split", "n_part", "C", "cs", "select", "patience", "curve_rows"}
-            if unknown:
-                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
-            rule = select_rule(name, e.get("select", "val_hits"))
-            patience = whole_number(name, "patience", e.get("patience", 0))
-            curve_rows = whole_number(name, "curve_rows", e.get("curve_rows", 0))
-            split = e.get("split")
-            if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
-                raise ValueError(f"{name}: split must be a contiguous [n, R] uint8 device matrix")
-            n, r = split.shape
-            c = int(e.get("C", 0))
-            cs = int(e.get("cs", c))
-            if not 1 <= c <= self.MAX_C:
-                raise ValueError(f"{name}: {c} classes; the kernel holds 1..{self.MAX_C}")
-            if cs < c:
-                raise ValueError(f"{name}: a replica stride of {cs} columns is narrower than its {c} classes")
-            t = e.get("logits")
-            _check_matrix(name, "logits", t, (n, None))  # (one row of split per row)
-            if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
-                raise ValueError(f"{name}: {r} replicas of {cs} columns do not fit a row of logits ({t.shape[1]} columns, leading dimension {_ld(t)})")
-            lab = e.get("labels")
-            if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
-                raise ValueError(f"{name}: labels must be a contiguous [n] int32 device vector")
+            shape = _stacked_logits_entry(name, e, ("logits", "labels", "split", "n_part", "C", "cs", "select", "patience", "curve_rows"),
+                                          ("logits",), own=settings)
+            n, r = shape[:2]
             part = e.get("n_part")
             part = np.asarray(part.detach().cpu() if isinstance(part, torch.Tensor) else part)
             if part.shape != (r, 3) or part.dtype.kind not in "iu" or (part < 0).any() or (part > n).any():
                 raise ValueError(f"{name}: n_part must be [R = {r}, 3] row counts (train, validation, test) in 0..n")
             parts.append(part.astype(np.int32))
-            shapes.append((n, r, c, cs, rule, patience, curve_rows))
+            shapes.append(shape)  # (n, R, C, cs, rule, patience, curve_rows)
         dev = require_gpu()  # (after the checks that need no device)
-        offsets = lambda lens: np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n_jobs))]).astype(np.int64)  # noqa: E731
-        off = offsets(s_[1] for s_ in shapes)
-        coff = offsets(s_[6] * s_[1] * 3 for s_ in shapes)
-        poff = offsets(int(lib.wdg_xent_curve_partials_len(s_[0], s_[1])) for s_ in shapes)
+        off = _offsets((s_[1] for s_ in shapes), n_jobs)
+        coff = _offsets((s_[6] * s_[1] * 3 for s_ in shapes), n_jobs)
+        poff = _offsets((int(lib.wdg_xent_curve_partials_len(s_[0], s_[1])) for s_ in shapes), n_jobs)
         total = max(int(off[-1]), 1)
         self.n_part = torch.zeros((total, 3), dtype=torch.int32, device=dev)
         if off[-1]:
@@ -568,9 +576,7 @@ class XentCurveBatch:
         for k, field in enumerate(("n", "R", "C", "cs", "rule", "patience", "curve_rows")):
             tab[field] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
         self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
-        host = np.ascontiguousarray(tab)
-        check(lib.wdg_xent_curve_check_jobs(ctypes.c_void_p(host.ctypes.data), n_jobs), "wdg_xent_curve_check_jobs")
-        self.table = _h2d(host.view(np.uint8), dev) if n_jobs else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n_jobs, dev, "wdg_xent_curve_check_jobs")
         self.reset()
 
     def launch(self, step):
@@ -641,13 +647,12 @@ class AdamBatch:
             self.segments.append(segs)
         dev = require_gpu()  # (after the checks that need no device)
         # the moments: every tensor's block starts at a multiple of four floats (16-byte accesses where its width allows)
-        sizes = np.fromiter((-(-e[0].numel() // 4) * 4 for e in entries), np.int64, n)
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        offs = _offsets((-(-e[0].numel() // 4) * 4 for e in entries), n)
         total = max(int(offs[-1]), 4)
         self.moments = torch.zeros((2, total), dtype=torch.float32, device=dev)
         self.m = [self.moments[0, offs[i]:offs[i] + entries[i][0].numel()].view(entries[i][0].shape) for i in range(n)]
         self.v = [self.moments[1, offs[i]:offs[i] + entries[i][0].numel()].view(entries[i][0].shape) for i in range(n)]
-        hoff = np.concatenate([[0], np.cumsum(self.segments)]).astype(np.int64)
+        hoff = _offsets(self.segments, n)
         self.hyper = torch.zeros((max(int(hoff[-1]), 1), 2), dtype=torch.float32, device=dev)
         if hoff[-1]:
             self.hyper[:int(hoff[-1])].copy_(torch.from_numpy(np.concatenate(hypers, 0)))
@@ -662,9 +667,7 @@ class AdamBatch:
         tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
         tab["seg_rows"], tab["seg_cols"] = col(lambda e: int(e[2])), col(lambda e: int(e[3]))
         self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
-        host = np.ascontiguousarray(tab)
-        check(lib.wdg_adam_check_jobs(ctypes.c_void_p(host.ctypes.data), n), "wdg_adam_check_jobs")
-        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n, dev, "wdg_adam_check_jobs")
 
     def launch(self, step):
         """one Adam step, t = step + 1.  step: a one-element int32 DEVICE tensor, read by the kernel when it runs (the word DropoutBatch
@@ -734,9 +737,7 @@ class KeepBestBatch:
         tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
         tab["seg_rows"], tab["seg_cols"], tab["reps"] = col(lambda e: int(e[2])), col(lambda e: int(e[3])), col(lambda e: int(e[4]))
         self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
-        host = np.ascontiguousarray(tab)
-        check(lib.wdg_keep_best_check_jobs(ctypes.c_void_p(host.ctypes.data), n), "wdg_keep_best_check_jobs")
-        self.table = _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n, dev, "wdg_keep_best_check_jobs")
 
     def launch(self, step):
         """step: a one-element int32 DEVICE tensor, read by the kernel when it runs - the word the XentEvalBatch.launch(XENT_EVAL, step)
@@ -751,7 +752,7 @@ class ConfusionBatch:
     class or none) (include/wdg.h states both; tests/_confusion_ref.py restates them in numpy).  The table owns the counts
     (counts_of[i]: int32 [R, 3, C, C + 1] - train, validation, test) and the predictions (pred_of[i]: uint8 [n, R])."""
 
-    MAX_C, MAX_JOBS = 16, 65535
+    MAX_C, MAX_JOBS = _STACKED_MAX_C, 65535
 
     def __init__(self, jobs):
         """jobs: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device,
@@ -761,32 +762,9 @@ class ConfusionBatch:
         n_jobs = self.n_jobs = len(jobs)
         if n_jobs > self.MAX_JOBS:
             raise ValueError(f"ConfusionBatch: {n_jobs} jobs; one launch takes {self.MAX_JOBS}")
-        shapes = []
-        for e in jobs:
-            unknown = set(e) - {"logits", "labels", "split", "C", "cs"}
-            if unknown:
-                raise ValueError(f"ConfusionBatch: unknown keys {sorted(unknown)}")
-            split = e.get("split")
-            if not isinstance(split, torch.Tensor) or split.dim() != 2 or split.dtype != torch.uint8 or not split.is_cuda or not split.is_contiguous():
-                raise ValueError("ConfusionBatch: split must be a contiguous [n, R] uint8 device matrix")
-            n, r = split.shape
-            c = int(e.get("C", 0))
-            cs = int(e.get("cs", c))
-            if not 1 <= c <= self.MAX_C:
-                raise ValueError(f"ConfusionBatch: {c} classes; the kernel holds 1..{self.MAX_C}")
-            if cs < c:
-                raise ValueError(f"ConfusionBatch: a replica stride of {cs} columns is narrower than its {c} classes")
-            t = e.get("logits")
-            _check_matrix("ConfusionBatch", "logits", t, (n, None))
-            if r * cs > t.shape[1] or (n > 1 and r * cs > _ld(t)):
-                raise ValueError(f"ConfusionBatch: {r} replicas of {cs} columns do not fit a row of logits ({t.shape[1]} columns, leading dimension {_ld(t)})")
-            lab = e.get("labels")
-            if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or not lab.is_cuda or not lab.is_contiguous() or tuple(lab.shape) != (n,):
-                raise ValueError("ConfusionBatch: labels must be a contiguous [n] int32 device vector")
-            shapes.append((n, r, c, cs))
+        shapes = [_stacked_logits_entry("ConfusionBatch", e, ("logits", "labels", "split", "C", "cs"), ("logits",)) for e in jobs]
         dev = require_gpu()  # (after the checks that need no device)
-        offsets = lambda lens: np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n_jobs))]).astype(np.int64)  # noqa: E731
-        coff, poff = offsets(r * 3 * c * (c + 1) for _, r, c, _ in shapes), offsets(n * r for n, r, _, _ in shapes)
+        coff, poff = _offsets((r * 3 * c * (c + 1) for _, r, c, _ in shapes), n_jobs), _offsets((n * r for n, r, _, _ in shapes), n_jobs)
         self.counts = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int32, device=dev)
         self.pred = torch.zeros(max(int(poff[-1]), 1), dtype=torch.uint8, device=dev)
         self.counts_of = [self.counts[coff[i]:coff[i + 1]].view(r, 3, c, c + 1) for i, (_, r, c, _) in enumerate(shapes)]
@@ -801,9 +779,7 @@ class ConfusionBatch:
         for k, name in enumerate(("n", "R", "C", "cs")):
             tab[name] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
         self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
-        host = np.ascontiguousarray(tab)
-        check(lib.wdg_confusion_check_jobs(ctypes.c_void_p(host.ctypes.data), n_jobs), "wdg_confusion_check_jobs")
-        self.table = _h2d(host.view(np.uint8), dev) if n_jobs else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, n_jobs, dev, "wdg_confusion_check_jobs")
 
     def launch(self, zero=True):
         """the predictions and the counts of every job; zero=True (the default) clears the table's counts first - the kernel ADDS"""
