@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Line-level host time of SweepBatch.__init__ and of KrPlan's construction inside the whole sweep (dev tool; sys.settrace on those
 frames)."""
+import linecache
 import os
 import sys
 import time
@@ -25,8 +26,10 @@ sweep.whole_sweep_rank(pairs, graph_of, feats, 1, 0)
 torch.cuda.synchronize()
 acc = defaultdict(float)
 last = {}
-targets = {f.__code__ for f in (sweep.SweepBatch.__init__, sweep.KrPlan.__init__, sweep.KrPlan._build_grams, sweep.KrPlan._group_jobs,
-                                 sweep.KrPlan._draw_sets, sweep.KrPlan._regression_table)}
+SB = sweep.SweepBatch  # (sweep_batch.py: the constructor and its stages; KrPlan's are in kr_plan.py - a line is named with its file)
+targets = {f.__code__ for f in (SB.__init__, SB._plan_columns, SB._host_graphs, SB._feature_blocks, SB._with_label_block, SB._finish_graphs,
+                                 SB._upload_labels, SB._layout_y, SB._aggregation_tables, SB._gcn_tables, sweep.KrPlan.__init__,
+                                 sweep.KrPlan._build_grams, sweep.KrPlan._group_jobs, sweep.KrPlan._draw_sets, sweep.KrPlan._regression_table)}
 
 
 def tracer(frame, event, arg):
@@ -37,14 +40,14 @@ def tracer(frame, event, arg):
         now = time.perf_counter()
         key = id(frame)
         if key in last:
-            code, line, t0 = last[key]
-            acc[(code, line)] += now - t0
+            path, code, line, t0 = last[key]
+            acc[(path, code, line)] += now - t0
         if event == "return":
             last.pop(key, None)
         else:
-            last[key] = (frame.f_code.co_name, frame.f_lineno, time.perf_counter())
+            last[key] = (frame.f_code.co_filename, frame.f_code.co_name, frame.f_lineno, time.perf_counter())
         return local
-    last[id(frame)] = (frame.f_code.co_name, frame.f_lineno, time.perf_counter())
+    last[id(frame)] = (frame.f_code.co_filename, frame.f_code.co_name, frame.f_lineno, time.perf_counter())
     return local
 
 
@@ -57,6 +60,5 @@ sweep.whole_sweep_rank(pairs, graph_of, feats, W, R)
 torch.cuda.synchronize()
 sys.settrace(None)
 print(f"traced pass: {(time.perf_counter() - t0) * 1e3:.0f} ms")
-src = open(sweep.__file__).read().splitlines()
-for (code, line), t in sorted(acc.items(), key=lambda kv: -kv[1])[:40]:
-    print(f"{t * 1e3:8.1f} ms  {code}:{line}  {src[line - 1].strip()[:110]}")
+for (path, code, line), t in sorted(acc.items(), key=lambda kv: -kv[1])[:40]:
+    print(f"{t * 1e3:8.1f} ms  {os.path.basename(path)}:{code}:{line}  {linecache.getline(path, line).strip()[:110]}")

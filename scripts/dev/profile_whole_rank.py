@@ -44,5 +44,5 @@ st.sort_stats("cumulative").print_stats(45)
 st.sort_stats("tottime").print_stats(30)
 if os.environ.get("WDG_PROF_CALLEES"):
     st.sort_stats("cumulative")
-    for pat in ("sweep.py:.*(__init__)", "_build_grams", "_group_jobs", "_draw_sets", "_regression_table", "rebind_features", "kernel_regression.py:.*(__init__)", "aggregate.py:.*(__init__)"):
+    for pat in ("sweep_batch.py:.*(__init__)", "kr_plan.py:.*(__init__)", "_build_grams", "_group_jobs", "_draw_sets", "_regression_table", "rebind_features", "kernel_regression.py:.*(__init__)", "aggregate.py:.*(__init__)"):
         st.print_callees(pat)

@@ -43,7 +43,7 @@ def dense_run():
 
 @pytest.mark.parametrize("depth", [2, 1])
 def test_compact_bases_equal_dense_bases(dense_run, depth, monkeypatch):
-    from wdg_amd import ops, sweep
+    from wdg_amd import ops, sweep_batch
     from wdg_amd.ops import SparseFeatures
     monkeypatch.delenv("WDG_GRAM_ROUTE", raising=False)
     shards, bases, want = dense_run
@@ -54,12 +54,12 @@ def test_compact_bases_equal_dense_bases(dense_run, depth, monkeypatch):
         for s_ in feats:
             assert feats[s_].kind == "csr" and feats[s_].shape == dense[s_].shape
     lens, dense_uploads = [], []
-    orig_expand, orig_upload = ops.expand_features, sweep._upload_features
+    orig_expand, orig_upload = ops.expand_features, sweep_batch._upload_features
     monkeypatch.setattr(ops, "expand_features", lambda feats, outs=None: (lens.append(len(list(feats))), orig_expand(feats, outs))[1])
-    monkeypatch.setattr(sweep, "_upload_features", lambda host: (dense_uploads.append(1), orig_upload(host))[1])
+    monkeypatch.setattr(sweep_batch, "_upload_features", lambda host: (dense_uploads.append(1), orig_upload(host))[1])
     got = _rows(shards, compact, depth)
     monkeypatch.setattr(ops, "expand_features", orig_expand)
-    monkeypatch.setattr(sweep, "_upload_features", orig_upload)
+    monkeypatch.setattr(sweep_batch, "_upload_features", orig_upload)
     for key in want:
         assert got[key].shape == (len(shards[key[0]][0]), 9)
         assert torch.equal(torch.nan_to_num(got[key], nan=-7.0), torch.nan_to_num(want[key], nan=-7.0)), key
