@@ -1421,6 +1421,71 @@ int wdg_xent_curve_check_jobs(const wdg_xent_curve_job *jobs_host, int32_t n_job
 /* replaces: nothing of its own - the doubles of a job's `partials`: ceil(n / 32) * R * 3 (0 for an empty job) (gnns_on_syn.py:109-154) */
 int64_t wdg_xent_curve_partials_len(int32_t n, int32_t R);
 
+/*
+ * The exact ROC-AUC of many BINARY models whose logits are STACKED along the feature axis (wdg_xent_job's layout: replica r owns
+ * columns r cs and r cs + 1 of one [n, R cs] matrix; the job carries no C, it is 2), per replica and per part of its split, as two
+ * integers - with a model selection on the validation AUC, a patience counter and a curve row, all on the device, inside a captured
+ * epoch.  A job is one graph's stacked logits (a ragged table).
+ * replaces: nothing the reference computes - its only score is the accuracy of utils/util_funcs.py:393, while five of the seven large
+ *           data sets its command line accepts (homophily_tests.py:30) are binary and two of the loaders beside them, load_yelpchi_dataset
+ *           (utils/datasets.py:82) and load_genius (utils/datasets.py:197), give labels of roughly 85/15 and 80/20, which upstream scores
+ *           by ROC-AUC.  It stands in for a copy of the logits to the host and sklearn.metrics.roc_auc_score per replica and epoch.
+ * The definition of one call with the step word at s = *step_dev (read from DEVICE memory when the kernel runs); tests/_auc_ref.py
+ * restates it in numpy.  For row i and replica r:
+ *   score  d = z_1 - z_0 = logits[i][r cs + 1] - logits[i][r cs]: ONE fp32 subtraction, no exponential.
+ *   part   p = split[i][r] - 1 in {0 train, 1 validation, 2 test}; a row with another code is not looked at.
+ *   pos(r, p) = the rows of the part with labels[i] == 1, neg(r, p) = those with labels[i] == 0; rows with any other label are not looked at.
+ *   pairs[r][p] = |pos| |neg|
+ *   u2[r][p]    = sum over i in pos, j in neg of (2 [d_j < d_i] + [d_j == d_i])          both int64; AUC = u2 / (2 pairs), the caller's
+ *                 division (NaN when pairs == 0).
+ *   The comparisons are IEEE's: -0.0 == +0.0, -inf < every finite number < +inf, inf == inf.  A NaN d (inf - inf included) among the
+ *   rows of pos or neg makes u2[r][p] = -1; pairs still counts the row.
+ * Curve:      if 0 <= s < curve_rows:  curve_u2[s][r][:] = u2[r][:]; no other row is written.
+ * Selection:  only when select == 1 and while state[r][1] (stopped_at) < 0:
+ *     improved = u2[r][1] >= 0 && u2[r][1] > best_u2[r][1]        (strict: the earliest of equal steps wins; best_u2 starts at -1)
+ *     improved:   best_u2[r][:] = u2[r][:], best[r] = (0, 0, s), bad = 0;        otherwise: bad += 1
+ *     then, if patience > 0 && bad >= patience:  stopped_at = s.
+ *   `best` [R, 3] int32 starts at (-1, 0, 0) and keeps the meaning wdg_keep_best_batched_f32 reads: best[3 r] >= 0 && best[3 r + 2] == t.
+ * The route (csrc/auc.hip) sorts nothing: a key = the monotone uint32 image of d (-0 mapped to +0 first); an integer histogram of
+ * bin = key >> (32 - bins_log2) per (r, p, class); a scan per replica that adds the pairs ACROSS bins, 2 pos[b] (negatives in lower
+ * bins), and turns the counts into offsets; a scatter of the keys into bin-contiguous arrays through an integer cursor per bin (the
+ * order inside a bin is arbitrary and no count depends on it); the pairs INSIDE a bin counted against tiles of its negatives in LDS
+ * (a bin larger than the tile loops over tiles); a finishing launch.  Every sum is a sum of integers (integer atomics); there is no
+ * floating-point atomic: two calls from the same inputs give the same bits, and a replica's numbers do not depend on the table it is
+ * in, on max_rows or on bins_log2.  bins_log2 only moves work between the scan (bins) and the in-bin count (rows of a bin, squared):
+ * all scores equal puts a part into ONE bin, and the call then costs |pos| |neg| comparisons - quadratic in the part's rows.
+ * Five launches on `stream`; the last one leaves the work space as it found it (zero where zero is asked for), so a captured call
+ * replays without a memset of its own.
+ * Refused before any HIP call (WDG_ERR_INVALID), in this order: negative counts, a NULL step_dev, more than 65535 jobs (a job per grid
+ * z), a NULL table with n_jobs > 0.  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is launched.  The table lives in device memory, so
+ * what is wrong inside a job - cs < 2, ld_logits below R cs (with n > 1), bins_log2 outside 1 .. 16, select outside 0 .. 1, a negative
+ * patience or curve_rows, curve_rows > 0 without curve_u2, a negative n or R, a NULL pointer or a work space that is not 8-byte
+ * aligned - is refused by wdg_auc_check_jobs on the HOST copy of the table (ops.AucBatch calls it before it uploads; no HIP call
+ * either), and every launch SKIPS such a job without touching its memory.  A job with n == 0 or R == 0 is skipped; rows beyond
+ * max_rows (the table's largest n) are not looked at.
+ */
+typedef struct wdg_auc_job {
+    const float *logits;      /* [n, R*cs] fp32, leading dimension ld_logits; columns r cs and r cs + 1 are read */
+    const int32_t *labels;    /* [n], shared by the replicas */
+    const uint8_t *split;     /* [n, R] row-major: 0 unused, 1 train, 2 validation, 3 test */
+    int64_t *u2;              /* [R, 3] out */
+    int64_t *pairs;           /* [R, 3] out */
+    int64_t *best_u2;         /* [R, 3] in/out: u2[r][:] of the best step; -1 before the first */
+    int32_t *best;            /* [R, 3] in/out: (0, 0, the best step); (-1, 0, 0) before the first */
+    int32_t *state;           /* [R, 2] in/out: bad (steps since the last improvement), stopped_at (-1: running) */
+    int64_t *curve_u2;        /* [curve_rows, R, 3], or NULL with curve_rows == 0 */
+    void *work;               /* wdg_auc_workspace_bytes(n, R, bins_log2) bytes, 8-byte aligned: ZERO before the first call, left zero by every call */
+    int64_t ld_logits;
+    int32_t n, R, cs, bins_log2;
+    int32_t select, patience, curve_rows, reserved;
+} wdg_auc_job;
+int wdg_auc_batched_i64(const wdg_auc_job *jobs_dev, int32_t n_jobs, int32_t max_rows, const int32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the AUC above (utils/util_funcs.py:393), on the host's table */
+int wdg_auc_check_jobs(const wdg_auc_job *jobs_host, int32_t n_jobs);
+/* replaces: nothing of its own - the bytes of a job's `work` (utils/util_funcs.py:393): with B = 2^bins_log2, 72 R of sums and counts,
+ *           36 R B of bin counters and bin starts, 4 n R of keys; 0 for an empty job, -1 for bins_log2 outside 1 .. 16 */
+int64_t wdg_auc_workspace_bytes(int32_t n, int32_t R, int32_t bins_log2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,7 +57,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
     Stacked parameters (w = hidden or cs; block (c, r) of a first-layer weight = columns (c R + r) w .. of it):
         "acm_sgc":  w [F, 3 R cs], att [R, 3, cs], wmix [R, 3, 3]
         "acm_gcn":  w0 [F, 3 R hidden], att0 [R, 3, hidden], wmix0 [R, 3, 3], w1 [R, hidden, 3 cs], att1 [R, 3, cs], wmix1 [R, 3, 3]
-    select, patience, curve_epochs: SplitTrainBatch's.
+    select, patience, curve_epochs: SplitTrainBatch's (select="val_auc": DESIGN 4.22).
     Raises ValueError for another kind, "acm_sgc" with dropout, more than 16 classes, hidden outside 1..256 and what SplitTrainBatch
     refuses of masks, labels and replica ids."""
 

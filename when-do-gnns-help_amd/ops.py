@@ -21,6 +21,7 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         KeepBestBatch (the copy of every replica's parameters and logits at its best epoch, selected on the device),
                         ConfusionBatch (predictions and per-split confusion counts of stacked logits),
                         XentCurveBatch (the evaluation with losses: a learning curve, selection on validation loss, patience)
+                        AucBatch (the exact ROC-AUC of stacked binary logits: selection on the validation AUC, patience, a curve)
   split_train.py        SplitTrainBatch (all splits of ONE graph trained as a single stacked run; reached as ops.SplitTrainBatch;
                         optimizer="device": per-replica lr / weight_decay / dropout), grid_search (a hyperparameter grid over all
                         splits as stacked chunks), select_settings
@@ -50,7 +51,7 @@ from .stats import (  # noqa: F401
 from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
-from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, ConfusionBatch, DropoutBatch, HeadTrainBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
+from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, HeadTrainBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .synth import regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, expand_features, feature_image_floats, FeatureExpand, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401

@@ -29,7 +29,7 @@ from ._lib import require_gpu
 from ._rt import _dev, capture_graphs, snapshot
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
-from .train import (SELECT_RULES, XENT_EVAL, XENT_GRAD, AdamBatch, ConfusionBatch, DropoutBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch,
+from .train import (AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch,
                     dropout_constants, select_rule, whole_number)
 
 MAX_CLASSES = XentEvalBatch.MAX_C
@@ -43,6 +43,21 @@ def _host(a):
 def _default_selection(select, patience, curve_epochs=0):
     """whether a run evaluates with csrc/xent_eval.hip alone: no losses, no patience, no learning curve"""
     return (select, patience, curve_epochs) == (SELECT_RULES[0], 0, 0)
+
+
+def _rule(who, select):
+    """-> the name of a selection rule: AUC_RULE, or one of SELECT_RULES (by name or index); ValueError for another"""
+    return AUC_RULE if isinstance(select, str) and select == AUC_RULE else SELECT_RULES[select_rule(who, select)]
+
+
+def _binary_validation(who, labels_np, masks):
+    """what select="val_auc" asks of the labels: two classes, and both among every replica's validation rows"""
+    if labels_np.size and int(labels_np.max()) > 1:
+        raise ValueError(f"{who}: select='val_auc' scores binary labels; these have {int(labels_np.max()) + 1} classes")
+    for r in range(masks.shape[0]):
+        val = labels_np[masks[r, 1]]
+        if not ((val == 0).any() and (val == 1).any()):
+            raise ValueError(f"{who}: select='val_auc': the validation rows of replica {r} lack one of the two classes")
 
 
 def _accuracies(best, n_val, n_test):
@@ -168,11 +183,19 @@ class SplitTrainBatch:
     change.  The losses are those of the CLEAN forward pass of the epoch's evaluation, for all three parts at the same weights: with
     dropout the train loss is NOT the loss of the training pass the gradient came from.  `best` is the curve table's (KeepBestBatch,
     run() and grid_search read it as ever); best_loss [R, 3], stopped_at [R] and learning_curves() read the rest.  The rules are
-    defined in include/wdg.h; they are not claimed to reproduce the tables of the loops upstream of the reference."""
+    defined in include/wdg.h; they are not claimed to reproduce the tables of the loops upstream of the reference.
+
+    select="val_auc" (binary labels with both classes among every replica's validation rows, else ValueError): the run owns
+    an ops.AucBatch (csrc/auc.hip) whose launch FOLLOWS the epoch's evaluation and selects on the exact validation ROC-AUC of the score
+    z_1 - z_0 - strictly larger wins, the earliest epoch among equals.  The evaluation launch stays as a recorder with patience 0 (its
+    table: best_by_hits; the XentCurveBatch only with curve_epochs > 0); `best`, `patience`, stopped_at and KeepBestBatch are the AUC
+    table's, whose best is (0, 0, epoch): run() reports val_auc, test_auc and best_epoch at the selected epoch and NaN accuracies - with
+    keep_best=True confusion() gives the accuracy at the selected epoch.  learning_curves() gains auc [T, R, 3]."""
 
     KINDS = ("sgc", "gcn", "mlp1", "mlp2")
     OPTIMIZERS = ("torch", "device")
     select, patience, curve_epochs, curve = SELECT_RULES[0], 0, 0, None  # (a run whose constructor never calls _selection() is a default run)
+    auc = best_by_hits = _roc = _roc_kept = None
 
     def __init__(self, adj, x, labels, masks, kind="gcn", hidden=64, lr=0.01, weight_decay=5e-4, symmetric=0, seed=0, dropout=0.0,
                  dropout_seed=None, *, optimizer="torch", replica_ids=None, keep_best=False,
@@ -259,6 +282,8 @@ class SplitTrainBatch:
         self.lrs, self.weight_decays, self.dropouts = spread(lr, "lr"), spread(weight_decay, "weight_decay"), spread(dropout, "dropout")
         self.replica_ids = _replica_ids(who, replica_ids, R)
         c, counts = _classes_and_counts(who, labels_np, masks)
+        if self.select == AUC_RULE:
+            _binary_validation(who, labels_np, masks)
         dev = require_gpu()  # (after the checks that need no device)
         from . import models
         self.adj = adj if isinstance(adj, models.NormAdj) or (adj is None and not needs_graph) else models.NormAdj(adj, symmetric=symmetric)
@@ -275,7 +300,7 @@ class SplitTrainBatch:
 
     def _selection(self, who, select, patience, curve_epochs):
         """the checks of select, patience and curve_epochs (before anything touches the device)"""
-        self.select = SELECT_RULES[select_rule(who, select)]
+        self.select = _rule(who, select)
         self.patience = whole_number(who, "patience", patience)
         self.curve_epochs = whole_number(who, "curve_epochs", curve_epochs)
 
@@ -289,13 +314,22 @@ class SplitTrainBatch:
         self.xent = XentEvalBatch([dict(logits=self.logits, dlogits=self.dlogits, labels=self.labels, split=self.split,
                                         inv_n_train=self.inv_n_train, C=self.c, cs=self.cs)])
         self.best = self.xent.best_of[0]  # [R, 3] int32: validation hits of the best epoch (-1: none yet), test hits at it, its epoch
-        self.curve = None
-        if not _default_selection(self.select, self.patience, self.curve_epochs):
+        self.curve = self.auc = self.best_by_hits = self._roc = self._roc_kept = None
+        by_auc = self.select == AUC_RULE
+        # (a run that selects on the AUC evaluates as a default run would - a recorder by hits without patience - and selects afterwards)
+        select, patience = (SELECT_RULES[0], 0) if by_auc else (self.select, self.patience)
+        if not _default_selection(select, patience, self.curve_epochs):
             # the evaluation with losses: its table owns the running best from here on
             counts = np.stack([self.n_train, self.n_val, self.n_test], 1)
             self.curve = XentCurveBatch([dict(logits=self.logits, labels=self.labels, split=self.split, n_part=counts, C=self.c, cs=self.cs,
-                                              select=self.select, patience=self.patience, curve_rows=self.curve_epochs)])
+                                              select=select, patience=patience, curve_rows=self.curve_epochs)])
             self.best = self.curve.best_of[0]
+        if by_auc:
+            # the selection on the validation AUC: its table owns the running best, the evaluation's is kept beside it
+            self.best_by_hits = self.best
+            self.auc = AucBatch([dict(logits=self.logits, labels=self.labels, split=self.split, cs=self.cs, select=1, patience=self.patience,
+                                      curve_rows=self.curve_epochs)])
+            self.best = self.auc.best_of[0]
         # torch's fused Adam: its kernel forms the bias corrections 1 - beta^t in double precision.  The unfused capturable path forms
         # them in fp32 tensors - 1 - 0.999^t cancels to a relative error of 1e-5 - and twelve epochs end 9e-7 from a float64 run where
         # this form ends 1e-7 from it (measured: tests/test_gpu_split_train.py).  Both keep the step count on the device: capturable.
@@ -429,6 +463,8 @@ class SplitTrainBatch:
             self.xent.launch(XENT_EVAL, self.step)
         else:
             self.curve.launch(self.step)  # losses, hits, the curve's row, selection and patience of this step
+        if self.auc is not None:
+            self.auc.launch(self.step)  # the AUC integers, their curve row, the selection on them and its patience
         if self.keeper is not None:
             self.keeper.launch(self.step)  # (after the selection of this step, before the word advances)
         self.step.add_(1)
@@ -443,7 +479,8 @@ class SplitTrainBatch:
         # torch's Adam: the state it has is restored, the state the warm-up creates starts from zero
         state = [] if self.adam is not None else [v for st in self.opt.state.values() for v in st.values() if torch.is_tensor(v)]
         kept = self.kept_params + [self.kept_logits] if self.keep_best else []  # (the warm-up epochs leave no trace in them)
-        selection = [self.xent.best] + (self.curve.state_tensors() if self.curve is not None else [])
+        selection = [self.xent.best] + (self.curve.state_tensors() if self.curve is not None else []) + \
+                    (self.auc.state_tensors() if self.auc is not None else [])
         restore = snapshot(self.params + [self.step] + selection + ([self.adam.moments] if self.adam is not None else state) + kept)
 
         def warm_up():
@@ -469,7 +506,7 @@ class SplitTrainBatch:
         selection is frozen, so the results are the same with or without the early exit."""
         if check_every is not None:
             check_every = whole_number(f"{type(self).__name__}.run", "check_every", check_every, least=1)
-            if self.curve is None:
+            if self.curve is None and self.auc is None:
                 raise ValueError(f"{type(self).__name__}.run: check_every needs a run built with select, patience or curve_epochs")
         step = (self.graph.replay if self.graph is not None else self.capture()) if capture else self.epoch
         self.forward()  # logits of the current weights
@@ -479,7 +516,7 @@ class SplitTrainBatch:
         while done < epochs:
             step()
             done += 1
-            if check_every is not None and done % check_every == 0 and bool((self.curve.state_of[0][:, 1] >= 0).all()):
+            if check_every is not None and done % check_every == 0 and bool((self._selector().state_of[0][:, 1] >= 0).all()):
                 break
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -487,13 +524,23 @@ class SplitTrainBatch:
         val_acc, test_acc = _accuracies(best, self.n_val, self.n_test)
         out = dict(val_acc=torch.from_numpy(val_acc), test_acc=torch.from_numpy(test_acc),
                    best_epoch=torch.from_numpy(best[:, 2].astype(np.int64)), seconds=dt, replicas_per_s=self.R / dt, epochs=epochs)
-        if self.curve is not None:
+        if self.auc is not None:
+            # (the AUC table's best is (0, 0, epoch): the hits at the selected epoch are not counted - confusion() of a keep_best run has them)
+            score = self.auc.best_auc()
+            nan = torch.full((self.R,), float("nan"), dtype=torch.float64)
+            out.update(val_acc=nan, test_acc=nan.clone(), val_auc=torch.from_numpy(score[:, 1].copy()), test_auc=torch.from_numpy(score[:, 2].copy()),
+                       stopped_at=torch.from_numpy(self.stopped_at), epochs_run=done)
+        elif self.curve is not None:
             loss = self.best_loss
             out.update(val_loss=torch.from_numpy(loss[:, 1].copy()), test_loss=torch.from_numpy(loss[:, 2].copy()),
                        stopped_at=torch.from_numpy(self.stopped_at), epochs_run=done)
         return out
 
     # -- the losses (select / patience / curve_epochs) ---------------------------------------------------------------
+    def _selector(self):
+        """the table whose state (bad, stopped_at) counts this run's patience: the AUC's, else the evaluation's"""
+        return self.auc if self.auc is not None else self.curve
+
     def _curved(self, what):
         if self.curve is None:
             raise ValueError(f"{type(self).__name__}.{what}: the run was built with the default select, patience and curve_epochs")
@@ -507,11 +554,13 @@ class SplitTrainBatch:
     @property
     def stopped_at(self):
         """int64 [R] (numpy): the epoch at which a replica's patience ran out, -1 while it has not"""
-        return self._curved("stopped_at").state_of[0][:, 1].cpu().numpy().astype(np.int64)
+        table = self.auc if self.auc is not None else self._curved("stopped_at")
+        return table.state_of[0][:, 1].cpu().numpy().astype(np.int64)
 
     def learning_curves(self):
         """-> dict(loss [T, R, 3] float32, hits [T, R, 3] int64, acc [T, R, 3] float64 (NaN for a part without rows)) over the parts train,
-        validation, test, for T = min(epochs done, curve_epochs): row t is the evaluation of epoch t (its clean forward pass)"""
+        validation, test, for T = min(epochs done, curve_epochs): row t is the evaluation of epoch t (its clean forward pass); a run with
+        select="val_auc" adds auc [T, R, 3] float64 (NaN for a part without a positive or a negative row)"""
         pair = self._curved("learning_curves").curve_of[0]
         T = min(int(self.step.item()), self.curve_epochs)
         if pair is None:
@@ -521,7 +570,8 @@ class SplitTrainBatch:
         rows = np.stack([self.n_train, self.n_val, self.n_test], 1).astype(np.float64)[None]
         with np.errstate(divide="ignore", invalid="ignore"):
             acc = np.where(rows > 0, hits / rows, np.nan)
-        return dict(loss=loss, hits=hits, acc=acc)
+        extra = dict(auc=self.auc.curves(0, rows=T)) if self.auc is not None else {}
+        return dict(loss=loss, hits=hits, acc=acc, **extra)
 
     # -- one replica ---------------------------------------------------------------------------------------------
     def _tensors(self, grad=False, kept=False):
@@ -614,6 +664,24 @@ class SplitTrainBatch:
         return self.confusion_and_predictions()[0]
 
 
+def roc_auc(run, kept=False):
+    """-> float64 [R, 3] (numpy): the exact ROC-AUC of a stacked run's CURRENT logits (kept=True: of its kept logits, a keep_best run's) on
+    every replica's train, validation and test rows, whatever the run selects by; NaN for a part without a positive or a negative row.
+    Binary labels only (ValueError otherwise).  One ops.AucBatch with select = 0 per run and source, built on first use; every call
+    launches it once."""
+    who = "roc_auc"
+    if run.c > 2:
+        raise ValueError(f"{who}: the run has {run.c} classes; the AUC is defined for binary labels")
+    if kept and not run.keep_best:
+        raise ValueError(f"{who}: the run was built without keep_best=True")
+    name = "_roc_kept" if kept else "_roc"
+    if getattr(run, name) is None:
+        setattr(run, name, AucBatch([dict(logits=run.kept_logits if kept else run.logits, labels=run.labels, split=run.split, cs=run.cs)]))
+    table = getattr(run, name)
+    table.launch(run.step)
+    return table.auc()
+
+
 # -- a hyperparameter grid over the splits ------------------------------------------------------------------------------------
 # buffers of hidden width [n, R hidden] a stacked run holds (the class-width ones, [n, R cs], for the one-layer kinds)
 _WIDE_BUFFERS = {"gcn": 5, "mlp2": 3, "sgc": 2, "mlp1": 2}  # gcn: p, hid, hid_t, dhid, dp; mlp2: hid, hid_t, dhid; else logits, dlogits
@@ -639,7 +707,7 @@ def chunk_settings(n_settings, n_splits, max_replicas):
     return [(g0, min(g0 + per, n_settings)) for g0 in range(0, n_settings, per)]
 
 
-def select_settings(best, n_val, n_test, val_loss=None):
+def select_settings(best, n_val, n_test, val_loss=None, val_u2=None):
     """Model selection over a grid, in numpy alone.  best: int [G, S, 3] - per (setting, split) the validation hits of the best epoch
     (-1: the replica never had a best epoch), the test hits at it, its epoch; n_val, n_test: [S] row counts.
     For every split the setting with the most validation hits is picked, the LOWEST setting index among equals; a replica without a
@@ -651,7 +719,12 @@ def select_settings(best, n_val, n_test, val_loss=None):
     val_loss: float [G, S] (grid_search(select="val_loss")["best_loss"][:, :, 1]) - then the per-split pick is the setting with the LOWEST
     validation loss instead, the lowest index among equals; a NaN never wins, and neither does a replica without a best epoch (a split
     where nothing qualifies picks setting 0 with test accuracy 0).  The result gains mean_val_loss [G] (a NaN or a replica without a best
-    epoch makes its setting's mean +inf) and best_mean_loss_setting: its argmin (lowest index among equals).  None: nothing changes."""
+    epoch makes its setting's mean +inf) and best_mean_loss_setting: its argmin (lowest index among equals).  None: nothing changes.
+    val_u2: int [G, S] (grid_search(select="val_auc")["best_u2"][:, :, 1]: the validation AUC of the selected epoch as an integer, -1 for
+    a replica that never selected; a split's validation pairs are the same for all its settings, so the integers compare directly) -
+    then the per-split pick is the setting with the LARGEST integer, the lowest index among equals (a split where no setting ever
+    selected picks setting 0), and the result gains selected [S] (bool: the pick has a selected epoch).  The accuracies of such a
+    table are what its `best` holds.  None: nothing changes.  val_loss and val_u2 together are refused."""
     best = np.asarray(best)
     if best.ndim != 3 or best.shape[2] != 3 or best.shape[0] < 1 or best.shape[1] < 1 or best.dtype.kind not in "iu":
         raise ValueError(f"select_settings: an integer [G, S, 3] table expected, got {best.dtype} {tuple(best.shape)}")
@@ -672,6 +745,15 @@ def select_settings(best, n_val, n_test, val_loss=None):
         pick = np.where(np.isinf(loss[pick, cols]), 0, pick)
         mean_loss = loss.mean(1)
         extra = dict(mean_val_loss=mean_loss, best_mean_loss_setting=int(mean_loss.argmin()))
+    if val_u2 is not None:
+        if val_loss is not None:
+            raise ValueError("select_settings: either val_loss or val_u2")
+        u2 = np.asarray(val_u2)
+        if u2.shape != (G, S) or u2.dtype.kind not in "iu":
+            raise ValueError(f"select_settings: val_u2 must be an integer [G = {G}, S = {S}] table, got {u2.dtype} {tuple(u2.shape)}")
+        u2 = np.where(hits < 0, -1, u2.astype(np.int64))
+        pick = u2.argmax(0)  # (the first maximum = the lowest setting index; all -1: setting 0)
+        extra = dict(selected=u2[pick, cols] >= 0)
     none = (hits[pick, cols] < 0) if val_loss is None else np.isinf(loss[pick, cols])
     test_all = np.where(hits < 0, 0.0, best[:, :, 1] / np.maximum(n_test, 1)[None, :])
     val_all = np.where(hits < 0, 0.0, hits / n_val[None, :])
@@ -755,13 +837,17 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     every (setting, split) at its best epoch, collected chunk by chunk (the kept weights themselves go with their chunk).
     select, patience, check_every: SplitTrainBatch's and run()'s, passed to every chunk.  With anything but the defaults the result gains
     best_loss [G, S, 3] float32 and stopped_at [G, S], and with select="val_loss" the selection is
-    select_settings(best, n_val, n_test, val_loss=best_loss[:, :, 1])."""
+    select_settings(best, n_val, n_test, val_loss=best_loss[:, :, 1]).
+    select="val_auc" (binary labels, both classes among every split's validation rows): the result gains best_u2 [G, S, 3] and pairs
+    [S, 3] int64, val_auc and test_auc [G, S] (at the selected epoch) and stopped_at instead, val_acc and test_acc are NaN, and the
+    selection is select_settings(best, n_val, n_test, val_u2=best_u2[:, :, 1])."""
     who = "grid_search"
-    select = SELECT_RULES[select_rule(who, select)]
+    select = _rule(who, select)
+    by_auc = select == AUC_RULE
     patience = whole_number(who, "patience", patience)
     if check_every is not None:
         check_every = whole_number(who, "check_every", check_every, least=1)
-    curved = not _default_selection(select, patience)
+    curved = by_auc or not _default_selection(select, patience)
     if check_every is not None and not curved:
         raise ValueError("grid_search: check_every needs a select or a patience other than the defaults")
     grid = list(grid)
@@ -778,6 +864,8 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     if not two_layer and any(float(g["dropout"]) != 0.0 for g in grid):
         raise ValueError(f"grid_search: kind {kind!r} has no hidden layer to drop units of: every setting's dropout must be 0")
     labels_np = _host(labels).reshape(-1)
+    if by_auc:
+        _binary_validation(who, labels_np.astype(np.int64), masks)
     cs = SplitTrainBatch._class_stride(int(labels_np.max()) + 1 if labels_np.size else 1)
     if max_replicas is None:
         max_replicas = default_max_replicas(n, int(hidden) if two_layer else cs, kind, S)
@@ -790,6 +878,7 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     labels_dev = torch.as_tensor(labels_np.astype(np.int64))
     best = np.zeros((len(grid), S, 3), np.int64)
     best_loss, stopped_at = np.zeros((len(grid), S, 3), np.float32), np.zeros((len(grid), S), np.int64)
+    best_u2, pairs = np.full((len(grid), S, 3), -1, np.int64), np.zeros((S, 3), np.int64)
     confusion, pred = [], []
     seconds = 0.0
     for g0, g1 in chunks:
@@ -801,7 +890,10 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
                               keep_best=keep_best, select=select, patience=patience, **kw)
         seconds += stb.run(epochs=epochs, capture=capture, check_every=check_every)["seconds"]
         best[g0:g1] = stb.best.cpu().numpy().reshape(g1 - g0, S, 3)
-        if curved:
+        if by_auc:
+            best_u2[g0:g1], stopped_at[g0:g1] = stb.auc.best_u2_of[0].cpu().numpy().reshape(g1 - g0, S, 3), stb.stopped_at.reshape(g1 - g0, S)
+            pairs = stb.auc.pairs_of[0][:S].cpu().numpy()  # (a split's pairs: the same for every setting)
+        elif curved:
             best_loss[g0:g1], stopped_at[g0:g1] = stb.best_loss.reshape(g1 - g0, S, 3), stb.stopped_at.reshape(g1 - g0, S)
         if keep_best:
             conf, pr = stb.confusion_and_predictions()  # (one launch per chunk)
@@ -811,9 +903,14 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     n_val, n_test = masks[:, 1].sum(1).astype(np.int64), masks[:, 2].sum(1).astype(np.int64)
     val_acc, test_acc = _accuracies(best, n_val, n_test)
     kept = dict(confusion=np.concatenate(confusion, 0), pred=np.concatenate(pred, 0)) if keep_best else {}
-    if curved:
+    if by_auc:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            score = np.where((pairs[None] > 0) & (best_u2 >= 0), best_u2 / (2.0 * pairs[None]), np.nan)
+        val_acc, test_acc = np.full_like(val_acc, np.nan), np.full_like(test_acc, np.nan)
+        kept.update(best_u2=best_u2, pairs=pairs, val_auc=score[:, :, 1], test_auc=score[:, :, 2], stopped_at=stopped_at)
+    elif curved:
         kept.update(best_loss=best_loss, stopped_at=stopped_at)
     by_loss = best_loss[:, :, 1] if select == "val_loss" else None
     return dict(val_acc=val_acc, test_acc=test_acc,
                 best_epoch=best[:, :, 2].copy(), best=best, n_val=n_val, n_test=n_test, chunks=chunks, seconds=seconds,
-                selection=select_settings(best, n_val, n_test, val_loss=by_loss), **kept)
+                selection=select_settings(best, n_val, n_test, val_loss=by_loss, val_u2=best_u2[:, :, 1] if by_auc else None), **kept)

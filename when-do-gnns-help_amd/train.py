@@ -9,7 +9,8 @@
 - csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
 - csrc/confusion.hip: the predictions and the confusion counts of stacked logits
-- csrc/xent_curve.hip: the evaluation with losses, a learning curve, three selection rules and a patience counter"""
+- csrc/xent_curve.hip: the evaluation with losses, a learning curve, three selection rules and a patience counter
+- csrc/auc.hip: the exact ROC-AUC of stacked binary logits, the selection on it, its patience counter and its curve"""
 import ctypes
 import math
 
@@ -31,8 +32,11 @@ _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
 _KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
 _CONFUSION_JOB_DTYPE = np.dtype(_lib.ConfusionJob)
 _XENT_CURVE_JOB_DTYPE = np.dtype(_lib.XentCurveJob)
+_AUC_JOB_DTYPE = np.dtype(_lib.AucJob)
 XENT_GRAD, XENT_EVAL = 1, 2  # WDG_XENT_GRAD, WDG_XENT_EVAL of include/wdg.h
 SELECT_RULES = ("val_hits", "val_loss", "val_hits_then_loss")  # wdg_xent_curve_job.rule = the index
+AUC_RULE = "val_auc"  # no rule of wdg_xent_curve_job: the selection of wdg_auc_job (csrc/auc.hip), beside the evaluation's
+AUC_BINS_LOG2 = 12  # AucBatch's default: sign, exponent and three mantissa bits of the score
 
 
 def _check_matrix(table, name, t, shape=None):
@@ -599,6 +603,117 @@ class XentCurveBatch:
         self.state[:, 1] = -1
         self.curve_loss.zero_()
         self.curve_hits.zero_()
+
+
+class AucBatch:
+    """Job table for wdg_auc_batched_i64 (csrc/auc.hip): the exact ROC-AUC of BINARY models whose logits are stacked along the feature
+    axis (XentEvalBatch's layout; the score of a row is z_1 - z_0), per replica and part of its split, as two integers - u2 and pairs,
+    AUC = u2 / (2 pairs) - with the selection on the validation AUC, a patience counter and a curve row, on the device (include/wdg.h
+    states every step; tests/_auc_ref.py restates them in numpy).  The table owns u2, pairs, best_u2 [R, 3] int64 (-1 at first), best
+    [R, 3] int32 (XentEvalBatch.best's layout, (-1, 0, 0) at first: KeepBestBatch reads it), state [R, 2] int32 (bad, stopped_at; 0, -1
+    at first), the optional curve and the kernel's work space - one view per entry in u2_of, pairs_of, best_u2_of, best_of, state_of
+    and curve_of ([curve_rows, R, 3] int64, or None)."""
+
+    MAX_JOBS = 65535
+
+    def __init__(self, entries):
+        """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device
+        (rows with a label other than 0 or 1 are not looked at), split [n, R] uint8 device contiguous (0 unused, 1 train, 2 validation,
+        3 test), cs (default 2), select (0, the default: score only; 1: select on the validation AUC), patience (default 0: never stops),
+        curve_rows (default 0), bins_log2 (default AUC_BINS_LOG2; 1 .. 16: it moves work, never a result).
+        Raises ValueError for other shapes, dtypes or strides, cs < 2, R cs beyond a row, a select, patience, curve_rows or bins_log2
+        outside the definition, more than 65535 entries."""
+        name = "AucBatch"
+        self.keep = entries
+        n_jobs = self.n_jobs = len(entries)
+        if n_jobs > self.MAX_JOBS:
+            raise ValueError(f"{name}: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
+        shapes = []
+        for e in entries:
+            if int(e.get("cs", 2)) < 2:
+                raise ValueError(f"{name}: a replica stride of {e.get('cs')} columns; a binary model has 2")
+            settings = lambda e: (whole_number(name, "select", e.get("select", 0)), whole_number(name, "patience", e.get("patience", 0)),  # noqa: E731
+                                  whole_number(name, "curve_rows", e.get("curve_rows", 0)), whole_number(name, "bins_log2", e.get("bins_log2", AUC_BINS_LOG2), 1))
+            shape = _stacked_logits_entry(name, dict(e, C=2, cs=int(e.get("cs", 2))), ("logits", "labels", "split", "C", "cs", "select", "patience",
+                                                                                       "curve_rows", "bins_log2"), ("logits",), own=settings)
+            if shape[4] > 1 or shape[7] > 16:
+                raise ValueError(f"{name}: select {shape[4]} and bins_log2 {shape[7]}; 0 or 1 and 1 .. 16 expected")
+            shapes.append(shape)  # (n, R, 2, cs, select, patience, curve_rows, bins_log2)
+        dev = require_gpu()  # (after the checks that need no device)
+        off = _offsets((s_[1] for s_ in shapes), n_jobs)
+        coff = _offsets((s_[6] * s_[1] * 3 for s_ in shapes), n_jobs)
+        woff = _offsets((int(lib.wdg_auc_workspace_bytes(s_[0], s_[1], s_[7])) // 8 + 1 for s_ in shapes), n_jobs)  # (in 8-byte words)
+        total = max(int(off[-1]), 1)
+        self.u2, self.pairs, self.best_u2 = (torch.zeros((total, 3), dtype=torch.int64, device=dev) for _ in range(3))
+        self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
+        self.state = torch.zeros((total, 2), dtype=torch.int32, device=dev)
+        self.curve = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int64, device=dev)
+        self.work = torch.zeros(max(int(woff[-1]), 1), dtype=torch.int64, device=dev)  # (zero before the first call; every call leaves it so)
+        for field in ("u2", "pairs", "best_u2", "best", "state"):
+            setattr(self, field + "_of", [getattr(self, field)[off[i]:off[i + 1]] for i in range(n_jobs)])
+        self.curve_of = [self.curve[coff[i]:coff[i + 1]].view(s_[6], s_[1], 3) if s_[6] else None for i, s_ in enumerate(shapes)]
+        tab = np.zeros(n_jobs, _AUC_JOB_DTYPE)
+        for i, e in enumerate(entries):
+            for k in ("logits", "labels", "split"):
+                tab[k][i] = e[k].data_ptr()
+            tab["ld_logits"][i] = max(_ld(e["logits"]), shapes[i][1] * shapes[i][3])
+            tab["curve_u2"][i] = self.curve.data_ptr() + 8 * coff[i] if shapes[i][6] else 0
+        for field in ("u2", "pairs", "best_u2"):
+            tab[field] = getattr(self, field).data_ptr() + 24 * off[:-1]
+        tab["best"] = self.best.data_ptr() + 12 * off[:-1]
+        tab["state"] = self.state.data_ptr() + 8 * off[:-1]
+        tab["work"] = self.work.data_ptr() + 8 * woff[:-1]
+        for k, field in ((0, "n"), (1, "R"), (3, "cs"), (4, "select"), (5, "patience"), (6, "curve_rows"), (7, "bins_log2")):
+            tab[field] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
+        self.max_rows = int(tab["n"].max(initial=0))
+        self.table = _upload(tab, n_jobs, dev, "wdg_auc_check_jobs")
+        self.reset()
+
+    def launch(self, step):
+        """the AUC integers of every entry, and - for the entries with select = 1 - their selection at this step.  step: a one-element
+        int32 DEVICE tensor, read by the kernel when it runs: a captured launch beside a captured `step.add_(1)` is right on every replay"""
+        check(lib.wdg_auc_batched_i64(_ptr(self.table), self.n_jobs, self.max_rows, _step_word("AucBatch.launch", step), stream_handle()),
+              "wdg_auc_batched_i64")
+
+    @staticmethod
+    def _ratio(u2, pairs):
+        u2, pairs = u2.cpu().numpy().astype(np.float64), pairs.cpu().numpy().astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where((pairs > 0) & (u2 >= 0), u2 / (2.0 * pairs), np.nan)
+
+    def auc(self, entry=0):
+        """float64 [R, 3] (numpy): the AUC of the last launch on the train, validation and test rows; NaN for a part without a positive
+        or without a negative row, or with a NaN score"""
+        return self._ratio(self.u2_of[entry], self.pairs_of[entry])
+
+    def best_auc(self, entry=0):
+        """float64 [R, 3] (numpy): the AUC at the selected step (NaN while there is none; the parts' pairs never change between steps)"""
+        return self._ratio(self.best_u2_of[entry], self.pairs_of[entry])
+
+    def stopped_at(self, entry=0):
+        """int64 [R] (numpy): the step at which a replica's patience ran out, -1 while it has not"""
+        return self.state_of[entry][:, 1].cpu().numpy().astype(np.int64)
+
+    def curves(self, entry=0, rows=None):
+        """float64 [rows, R, 3] (numpy): the AUC of the first `rows` (default: all) curve rows of an entry"""
+        cur = self.curve_of[entry]
+        if cur is None:
+            return np.zeros((0, self.pairs_of[entry].shape[0], 3))
+        cur = cur if rows is None else cur[:rows]
+        return self._ratio(cur, self.pairs_of[entry][None].expand_as(cur))
+
+    def state_tensors(self):
+        """what a run snapshots and rewinds with its parameters: best, best_u2, state and the curve"""
+        return [self.best, self.best_u2, self.state, self.curve]
+
+    def reset(self):
+        """the running best back to "none yet", nobody stopped, the curve to zero (the work space is zero between calls)"""
+        self.best.zero_()
+        self.best[:, 0] = -1
+        self.best_u2.fill_(-1)
+        self.state.zero_()
+        self.state[:, 1] = -1
+        self.curve.zero_()
 
 
 class AdamBatch:
