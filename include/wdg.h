@@ -1486,6 +1486,66 @@ int wdg_auc_check_jobs(const wdg_auc_job *jobs_host, int32_t n_jobs);
  *           36 R B of bin counters and bin starts, 4 n R of keys; 0 for an empty job, -1 for bins_log2 outside 1 .. 16 */
 int64_t wdg_auc_workspace_bytes(int32_t n, int32_t R, int32_t bins_log2);
 
+/*
+ * Y = S W for a SPARSE S and a dense W, a table of products per launch: the first layer of a stacked run on a bag-of-words feature
+ * matrix, X [W0_1 | ... | W0_R], and its weight gradient X^T dP, without the dense X (sparse_features.DeviceFeatures).
+ * replaces: th.FloatTensor(features) / .todense() utils/util_funcs.py:339 - the densification in front of the first torch call - for
+ *           the two products that read X: the job keeps S as the CSR it is on disk.
+ * A job: S is CSR - rowptr int32 [n_rows + 1], col int32 sorted ascending and unique inside a row, val fp32 or NULL (= every stored
+ * value is 1.0) - with n_cols columns; W [n_cols, m] fp32 with leading dimension ldw, Y [n_rows, m] fp32 with leading dimension ldy.
+ * The definition (tests/_sparse_dense_ref.py restates it in numpy, bit for bit):
+ *   Y[i][j] = the chain   acc = +0;  for e = rowptr[i] .. rowptr[i + 1] - 1 ascending:  acc = fmaf(val[e], W[col[e]][j], acc)
+ *   - one correctly rounded fma per stored entry, the SAME chain for a row of any length: no row is split over lanes or waves, no
+ *   partial sums are added, there is no atomic (csrc/sparse_dense.hip is compiled with contraction off and writes the fma out).
+ *   wdg_gemm_f32 is this chain over every k in ascending order, and fmaf(0, w, acc) = acc for a finite w: on a W without inf / NaN
+ *   the result has the bits of wdg_gemm_f32 on the expanded S wherever that takes its single chain (wdg_gemm_splitk_plan == 1).
+ *   Every element of Y[0 : n_rows][0 : m] is written; an empty row gives +0.  Nothing outside that block is written - not the columns
+ *   m .. ldy - 1 of a wider Y.  Two launches from the same inputs give the same bits, and a job's bits do not depend on the table it
+ *   is in, on max_rows, max_m or on where its workgroups run.
+ *   m >= 1 and leading dimensions >= m of any value: 16-byte loads / stores where the pointer, the leading dimension and the four
+ *   columns of a lane allow, scalar ones elsewhere (same values, same fma).
+ *   An entry whose column lies outside [0, n_cols) is SKIPPED (no fma), never read through: the guard of wdg_features_expand_batched_f32.
+ *   order: int32 [n_rows] or NULL - the sequence in which the rows are dealt to the waves (position p works on row order[p]; NULL: p),
+ *   nothing else: a permutation with the longest rows first lets the longest chain, which bounds the launch, start first.  A position
+ *   whose entry lies outside [0, n_rows) is skipped (its row is then written by nobody).
+ * max_rows, max_m: the largest n_rows and m of the table (rows / columns beyond them are not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID), in this order: negative counts, more than 65535 jobs (a job per grid y); then
+ * n_jobs == 0, max_rows == 0 or max_m == 0 is WDG_OK with nothing launched; then a NULL table.  The table lives in device memory: what
+ * is wrong inside a job - a negative n_rows, n_cols or m, a leading dimension below m, a NULL rowptr or Y, a NULL col or W with
+ * n_cols > 0, a reserved word that is not 0 - is refused by wdg_sparse_dense_check_jobs on the HOST copy of the table
+ * (sparse_features.SparseDenseBatch calls it before it uploads), and the launch leaves such a job untouched.  A job with n_rows == 0
+ * or m == 0 is skipped.
+ */
+typedef struct wdg_sparse_dense_job {
+    const int32_t *rowptr;  /* [n_rows + 1] */
+    const int32_t *col;     /* [nnz], sorted and unique inside a row */
+    const float *val;       /* [nnz] or NULL = 1.0 */
+    const int32_t *order;   /* [n_rows] or NULL: the sequence in which rows are dealt */
+    const float *W;         /* [n_cols, m], leading dimension ldw */
+    float *Y;               /* [n_rows, m], leading dimension ldy */
+    int64_t ldw, ldy;
+    int32_t n_rows, n_cols, m, reserved;
+} wdg_sparse_dense_job;
+int wdg_sparse_dense_batched_f32(const wdg_sparse_dense_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_m, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the sparse product above (utils/util_funcs.py:339), on the host's table */
+int wdg_sparse_dense_check_jobs(const wdg_sparse_dense_job *jobs_host, int32_t n_jobs);
+/*
+ * The stored values of a CSR feature matrix under preprocess_features' row scaling, once, in CSR order and in the order of its
+ * transposed layout - what the two sparse products above read as `val`.
+ * replaces: preprocess_features utils/util_funcs.py:39-46 (normalise WDG_FEAT_NORM_SUM) and f.normalize homophily_tests.py:94
+ *           (WDG_FEAT_NORM_ABS) on the stored entries instead of on the dense matrix of utils/util_funcs.py:339.
+ * val_scaled[e] = what wdg_features_expand_batched_f32 writes at entry e's position under the same `normalise`, bit for bit: the two
+ * kernels share the row sum's order and the scale (csrc/feat_scale.h) - the fp64 sum over the row's entries (an entry whose column is
+ * outside [0, n_feat) left out), s = (float)sum, WDG_FEAT_NORM_SUM: r = 1.0f / s, inf -> 0, y = r * x; WDG_FEAT_NORM_ABS: the sum over
+ * |x|, y = x / fmaxf(s, 1e-12f); WDG_FEAT_NORM_NONE: y = x.  val NULL = every stored value is 1.0.
+ * t_src int32 [nnz] or NULL: entry e of the transposed layout is CSR entry t_src[e]; t_val_scaled[e] = val_scaled[t_src[e]] (+0 for
+ * a t_src[e] outside [0, nnz)).  t_src and t_val_scaled are both given or both NULL.  Two launches on `stream`.
+ * Refused before any HIP call: negative counts, a normalise that is none of WDG_FEAT_NORM_*; then n_rows == 0 or nnz == 0 is WDG_OK
+ * with nothing launched; then a NULL rowptr, col or val_scaled, and t_src without t_val_scaled or the reverse.
+ */
+int wdg_feat_scaled_values_f32(const int32_t *rowptr, const int32_t *col, const float *val, int32_t n_rows, int32_t n_feat, int normalise,
+                               const int32_t *t_src, int32_t nnz, float *val_scaled, float *t_val_scaled, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,9 @@ SIGNATURES = {
     "wdg_auc_batched_i64": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "wdg_auc_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_auc_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "wdg_sparse_dense_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_sparse_dense_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_feat_scaled_values_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -355,6 +358,12 @@ class AucJob(ctypes.Structure):
     """mirror of `wdg_auc_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("logits", "labels", "split", "u2", "pairs", "best_u2", "best", "state", "curve_u2", "work")] + \
                [("ld_logits", c_int64)] + [(name, c_int32) for name in ("n", "R", "cs", "bins_log2", "select", "patience", "curve_rows", "reserved")]
+
+
+class SparseDenseJob(ctypes.Structure):
+    """mirror of `wdg_sparse_dense_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "val", "order", "W", "Y")] + [("ldw", c_int64), ("ldy", c_int64)] + \
+               [(name, c_int32) for name in ("n_rows", "n_cols", "m", "reserved")]
 
 
 if not os.path.exists(LIB_PATH):

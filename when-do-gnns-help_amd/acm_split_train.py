@@ -49,7 +49,8 @@ class AcmSplitTrainBatch(SplitTrainBatch):
         kind "acm_gcn":  two ACM layers, dropout(relu(.)) between them                             (models.ACMGCN2)
     bias-free; the per-replica reference is replica_model(r).  The arguments, the epoch (gradient of the train loss -> torch's fused
     Adam with the L2 term in the gradient -> a clean forward pass -> evaluation and model selection), run / capture / epoch and the
-    result dictionary are SplitTrainBatch's with optimizer="torch": one lr, one weight_decay, one dropout.  dropout applies to
+    result dictionary are SplitTrainBatch's with optimizer="torch" (x may be sparse, as there: "acm_gcn" then runs X W0 and X^T d(X W0) on
+    csrc/sparse_dense.hip and holds no dense x; "acm_sgc" expands the matrix once and keeps it): one lr, one weight_decay, one dropout.  dropout applies to
     "acm_gcn"; replica r draws the masks of models.DeviceDropout(dropout_seed, stream=replica_ids[r]).
     Replica r is initialised from a CPU generator seeded by replica_seed(seed, replica_ids[r]) in DESIGN 4.16's draw order, layer 1
     before layer 2: it does not depend on R.  The padding columns of the class-width weights and attention vectors start at zero and
@@ -86,7 +87,10 @@ class AcmSplitTrainBatch(SplitTrainBatch):
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
         wc, wh = R * cs, R * h  # a channel's columns of a class-width / hidden-width layer
         self.logits, self.dlogits = z(n, wc), z(n, wc)
-        self.xt = x.t().contiguous()
+        if x is None and not self.two_layer:
+            # (a sparse x, "acm_sgc": every epoch multiplies the DENSE pair [Y | X] - the matrix is expanded once and kept)
+            x = self.x = self.feats.dense()
+        self.xt = x.t().contiguous() if x is not None else None
 
         def parameters(*tensors):
             out = [torch.nn.Parameter(t) for t in tensors]
@@ -117,6 +121,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
                                                d_low=self.dya[:, :wc], d_high=self.dxb[:, :wc], d_ident=self.dxb[:, wc:],
                                                d_att=self.att.grad, d_wmix=self.wmix.grad)], relu=False)
             self.drop, self.drops = None, []
+            self._first_layer(None, None, None)
         else:
             w0, att0, wmix0 = z(f, 3 * wh), z(R, 3, h), z(R, 3, 3)
             w1, att1, wmix1 = z(R, h, 3 * cs), z(R, 3, cs), z(R, 3, 3)
@@ -163,6 +168,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
                 self.relu = DropoutBatch(units, 0.0, self.dropout_seed)  # p = 0: a plain ReLU plus the transposed copy
                 self.drops = [self.relu]
             self.drop, self.hid_scale = self.drops[0], None
+            self._first_layer(self.w0, self.xw, self.dxw)
         self._epilogue()  # (optimizer "torch": the fused Adam, for SplitTrainBatch's reason)
 
     _class_stride = staticmethod(class_stride)
@@ -191,7 +197,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
                 self.mix.launch()
                 return
             wh, wc = self.R * self.h, self.R * self.cs
-            gemm(self.x, self.w0.data, out=self.xw)             # X [W0_L | W0_H | W0_I], every replica
+            self._x_times(self.x, self.w0.data, self.xw)        # X [W0_L | W0_H | W0_I], every replica
             self._aggregate(self.xw[:, :2 * wh], self.ag1)      # A_hat of the first two channels
             self.mix0.launch()                                  # layer 1's mix, a job per replica
             for unit in (self.drops if (train or self.dropout == 0) else [self.relu]):
@@ -223,7 +229,7 @@ class AcmSplitTrainBatch(SplitTrainBatch):
             self.mix0.launch_backward()
             self._aggregate_t(self.dg1, self.t1)
             acm_operand_gradient(self.dg1, self.t1, self.dxw, wh)
-            gemm(self.xt, self.dxw, out=self.w0.grad)           # dW0 = X^T d(X W0)
+            self._xt_times(self.xt, self.dxw, self.w0.grad)     # dW0 = X^T d(X W0)
 
     # -- one replica ---------------------------------------------------------------------------------------------
     def _first_layer_block(self, t, r, width, cols):

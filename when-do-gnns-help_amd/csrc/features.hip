@@ -30,6 +30,7 @@
 // compare equal), and NaN where the sum is not finite.
 #include <climits>
 
+#include "feat_scale.h"
 #include "wdg_common.h"
 
 namespace {
@@ -58,23 +59,7 @@ __device__ __forceinline__ void store_positions(global_ptr<float> dst, int q, in
     }
 }
 
-// the row's scale from its fp64 sum, exactly as row_l1_kernel: sum -> y = r * x, r = 1 / s (inf -> 0); abs -> y = x / max(s, 1e-12)
-struct RowScale {
-    int mode;
-    float f;
-    __device__ __forceinline__ RowScale(int mode_, double sum) : mode(mode_), f(1.f) {
-        const float s = static_cast<float>(sum);
-        if (mode == WDG_FEAT_NORM_SUM) {
-            f = 1.0f / s;
-            if (isinf(f)) f = 0.f;
-        } else if (mode == WDG_FEAT_NORM_ABS) {
-            f = fmaxf(s, 1e-12f);
-        }
-    }
-    __device__ __forceinline__ float operator()(float x) const {
-        return mode == WDG_FEAT_NORM_SUM ? f * x : mode == WDG_FEAT_NORM_ABS ? x / f : x;
-    }
-};
+// (RowScale and the row sum's order: csrc/feat_scale.h, shared with sparse_dense.hip)
 
 __global__ __launch_bounds__(64 * kFeatRows) void features_expand_kernel(const wdg_feat_job *__restrict__ jobs) {
     __shared__ __attribute__((aligned(16))) float images[kFeatRows][kFeatImage];
@@ -125,15 +110,7 @@ __global__ __launch_bounds__(64 * kFeatRows) void features_expand_kernel(const w
     const global_ptr<const int32_t> rowptr = to_global(job->rowptr), col = to_global(job->col);
     const global_ptr<const float> val = to_global(job->val);
     const int beg = rowptr[row], end = rowptr[row + 1];
-    double sum = 0.0;
-    if (mode != WDG_FEAT_NORM_NONE) {
-        for (int e = beg + lane; e < end; e += 64) {
-            if (static_cast<unsigned>(col[e]) >= static_cast<unsigned>(F)) continue;
-            const float x = val ? val[e] : 1.f;
-            sum += static_cast<double>(mode == WDG_FEAT_NORM_ABS ? fabsf(x) : x);
-        }
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    }
+    const double sum = feat_csr_row_sum(col, val, beg, end, F, mode, lane);
     const RowScale scale(mode, sum);
     float *img = images[wave];
     int cursor = beg;  // the first entry no window has taken yet (wave-uniform)

@@ -28,7 +28,9 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
   acm_split_train.py    AcmSplitTrainBatch (all splits of ONE graph trained as a single stacked run of ACM-SGC-1 / ACM-GCN-2 models, in a
                         channel-major layout; reached as ops.AcmSplitTrainBatch)
   train_batch.py        TrainBatch (one model per graph of a shard, trained for all graphs at once; reached as sweep.TrainBatch)
-  sparse_features.py    SparseFeatures (compact feature matrices on the host), expand_features / FeatureExpand (one launch for a list of them)
+  sparse_features.py    SparseFeatures (compact feature matrices on the host), expand_features / FeatureExpand (one launch for a list of them),
+                        DeviceFeatures (a feature matrix on the device as CSR + its transposed index: matmul / t_matmul, the sparse first layer
+                        of the stacked trainers), SparseDenseBatch (a table of such products)
   kernel_regression.py  GramBatch, PropagatedGram, RowRepBatch, EdgeGramBatch, KrSets, KrBatch, GnbBatch, SvmBatch
 (module-level switches - aggregate.ABLATE_BITS, aggregate.NARROW_MIN_ENTRIES - are set on the module that owns them)."""
 from ._lib import check, lib, require_gpu, stream_handle  # noqa: F401
@@ -53,7 +55,7 @@ from .gemm import (  # noqa: F401
 )
 from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, HeadTrainBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .synth import regular_graph_device, sample_feature_rows  # noqa: F401
-from .sparse_features import as_compact, expand_features, feature_image_floats, FeatureExpand, SparseFeatures  # noqa: F401
+from .sparse_features import as_compact, DeviceFeatures, expand_features, feature_image_floats, FeatureExpand, SparseDenseBatch, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
     deflation_enabled, EdgeGramBatch, GnbBatch, GramBatch, kr_split_sizes, KrBatch, KrSets, PropagatedGram, RowRepBatch, SvmBatch, _KR_JOB_DTYPE,
 )

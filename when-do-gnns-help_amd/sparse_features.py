@@ -266,3 +266,216 @@ def feature_image_floats():
     """the floats of one LDS row image of the expand kernel's CSR path (a wider row is written in several windows)"""
     from ._lib import lib
     return int(lib.wdg_features_image_floats())
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The sparse first layer (csrc/sparse_dense.hip; DESIGN 4.23): X w and X^T d from the compact matrix, bit for bit what ops.gemm gives
+# on the expanded one wherever that takes its single fma chain.
+def csr_of(sf):
+    """a SparseFeatures of either kind -> (rowptr int32 [n + 1], col int32 [nnz], val fp32 [nnz] or None) on the host: a `bits`
+    matrix is turned into CSR here (its set bits, row-major: sorted and unique; every value is 1)"""
+    if sf.kind == "csr":
+        return sf.rowptr, sf.col, sf.val
+    n, f = sf.shape
+    n_words = (f + 31) // 32
+    bits = np.unpackbits(np.ascontiguousarray(sf.words[:, :n_words]).view(np.uint8).reshape(n, 4 * n_words), axis=1, bitorder="little")[:, :f]
+    rows, col = np.nonzero(bits)
+    rowptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=rowptr[1:])
+    return rowptr.astype(np.int32), col.astype(np.int32), None
+
+
+def transposed_index(rowptr, col, n_feat):
+    """the column-major index of a CSR matrix, by a stable sort: -> (t_rowptr int32 [F + 1], t_col int32 [nnz]: the ROWS of a
+    column's entries, ascending, t_src int32 [nnz]: entry e of the transposed layout is CSR entry t_src[e])"""
+    n = rowptr.shape[0] - 1
+    rows = np.repeat(np.arange(n, dtype=np.int32), np.diff(rowptr))
+    t_src = np.argsort(col, kind="stable").astype(np.int32)
+    t_rowptr = np.zeros(n_feat + 1, np.int64)
+    np.cumsum(np.bincount(col, minlength=n_feat), out=t_rowptr[1:])
+    return t_rowptr.astype(np.int32), rows[t_src], t_src
+
+
+def deal_order(rowptr):
+    """the sequence in which the sparse product deals rows: longest first, equal lengths in row order (a stable sort) -> int32 [n]"""
+    return np.argsort(-np.diff(rowptr).astype(np.int64), kind="stable").astype(np.int32)
+
+
+class DeviceFeatures:
+    """A [n, F] feature matrix on the DEVICE as the CSR it is on disk plus its transposed index - no dense copy - for the two products
+    of a first layer: matmul(w) = X w and t_matmul(d) = X^T d (wdg_sparse_dense_batched_f32).
+
+    x: a SparseFeatures (either kind; its `normalise` is applied to the stored values once, by wdg_feat_scaled_values_f32, with
+    features.hip's arithmetic), a scipy sparse matrix, or (rowptr, col, val | None, shape) CSR arrays; normalise=...: overrides the
+    matrix's own.  The transposed index and both dealing orders (longest row first) are built on the host with numpy; everything
+    goes up in ONE pooled upload through the ring, then comes the preparation launch.
+    Element (i, j) of either product is one fp32 fma chain over the stored entries in ascending order from +0: the bits of
+    ops.gemm(dense(), w) / ops.gemm(dense().t().contiguous(), d) wherever gemm takes its single chain (wdg_gemm_splitk_plan == 1) and
+    the dense operand holds no inf / NaN."""
+
+    PLANS_KEPT = 8  # job tables matmul / t_matmul keep for (w, out) pairs
+
+    def __init__(self, x, normalise=...):
+        import torch
+
+        from ._lib import check, lib, require_gpu, stream_handle
+        from ._rt import _h2d, _ptr
+        if isinstance(x, DeviceFeatures):
+            raise TypeError("DeviceFeatures: already on the device")
+        if isinstance(x, tuple) and len(x) == 4:
+            x = SparseFeatures.from_csr(*x)
+        sf = as_compact(x)
+        if sf is None:
+            raise TypeError(f"DeviceFeatures: a SparseFeatures, a scipy sparse matrix or (rowptr, col, val, shape) expected, not {type(x).__name__}")
+        self.normalise = sf.normalise if normalise is ... else _check_normalise(normalise)
+        self.shape = sf.shape
+        n, f = sf.shape
+        rowptr, col, val = csr_of(sf)
+        t_rowptr, t_col, t_src = transposed_index(rowptr, col, f)
+        self.nnz = int(col.shape[0])
+        self.longest_row = int(np.diff(rowptr).max(initial=0))
+        self.longest_col = int(np.diff(t_rowptr).max(initial=0))
+        dev = require_gpu()
+        arrays = dict(rowptr=rowptr, col=col, order=deal_order(rowptr), t_rowptr=t_rowptr, t_col=t_col, t_order=deal_order(t_rowptr), t_src=t_src)
+        plain = self.normalise is None
+        if val is not None:
+            arrays["val"] = val
+            if plain:
+                arrays["t_val"] = val[t_src]
+        # one pooled upload: every array is made of 4-byte items; each starts on a 16-byte boundary of the pool
+        pieces, at, cursor = [], {}, 0
+        for name, a in arrays.items():
+            a = np.ascontiguousarray(a).reshape(-1)
+            pieces.append(a.view(np.int32))
+            at[name] = (cursor, a.size)
+            cursor += a.size + (-a.size % 4)
+            if -a.size % 4:
+                pieces.append(np.zeros(-a.size % 4, np.int32))
+        self.uploaded_bytes = 4 * cursor
+        self.pool = _h2d(np.concatenate(pieces), dev)
+        part = lambda name: self.pool[at[name][0]:at[name][0] + at[name][1]] if name in at else None  # noqa: E731
+        for name in ("rowptr", "col", "order", "t_rowptr", "t_col", "t_order", "t_src"):
+            setattr(self, name, part(name))
+        as_f32 = lambda t: None if t is None else t.view(torch.float32)  # noqa: E731
+        if plain:
+            self.val, self.t_val = as_f32(part("val")), as_f32(part("t_val"))  # (None: every stored value is 1)
+        else:
+            self.val, self.t_val = (torch.empty(self.nnz, dtype=torch.float32, device=dev) for _ in range(2))
+            check(lib.wdg_feat_scaled_values_f32(_ptr(self.rowptr), _ptr(self.col), _ptr(part("val")), n, f, NORMALISE[self.normalise], _ptr(self.t_src),
+                                                 self.nnz, _ptr(self.val), _ptr(self.t_val), stream_handle()), "wdg_feat_scaled_values_f32")
+        self._source, self._plans = sf.with_normalise(self.normalise), {}
+
+    device = property(lambda self: self.pool.device)
+
+    def _csr(self, transposed):
+        """(rowptr, col, val, order, rows, cols) of X or of X^T"""
+        n, f = self.shape
+        return (self.t_rowptr, self.t_col, self.t_val, self.t_order, f, n) if transposed else (self.rowptr, self.col, self.val, self.order, n, f)
+
+    def _product(self, transposed, w, out):
+        import torch
+        rows, cols = (self.shape[1], self.shape[0]) if transposed else self.shape
+        who = "DeviceFeatures.t_matmul" if transposed else "DeviceFeatures.matmul"
+        if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.shape[0] == cols and w.stride(1) == 1):
+            raise ValueError(f"{who}: an fp32 device matrix [{cols}, m] with unit inner stride expected")
+        if out is None:  # a fresh result: a table of its own, not kept (nothing could launch it again)
+            out = torch.empty((rows, w.shape[1]), dtype=torch.float32, device=w.device)
+            SparseDenseBatch([(self, transposed, w, out)]).launch()
+            return out
+        # the tables of the last PLANS_KEPT (w, out) pairs, by address and shape: a table holds addresses, not the tensors, so dropping
+        # w or out frees them, and a pair that comes back finds its table
+        key = (bool(transposed), w.data_ptr(), tuple(w.shape), w.stride(0), out.data_ptr(), tuple(out.shape), out.stride(0))
+        table = self._plans.pop(key, None)
+        if table is None:
+            table = SparseDenseBatch([(self, transposed, w, out)], keep=False)
+            while len(self._plans) >= self.PLANS_KEPT:
+                self._plans.pop(next(iter(self._plans)))  # (the least recently used)
+        self._plans[key] = table
+        table.launch()
+        return out
+
+    def matmul(self, w, out=None):
+        """X w: w [F, m] fp32 on the device -> [n, m] (out: a preallocated target, any leading dimension >= m).  One launch.  With `out`
+        the job table of the (w, out) pair is built at its first call and kept, so a
+        later call allocates and synchronises nothing and records into a captured epoch; without it the result and its table are new.
+        The tables of the PLANS_KEPT most recently used pairs are kept, by address: they hold no reference to w or out.  Code that
+        replays a captured launch for longer than that should own its table - a SparseDenseBatch, as the stacked trainers do."""
+        return self._product(False, w, out)
+
+    def t_matmul(self, d, out=None):
+        """X^T d: d [n, m] fp32 on the device -> [F, m]; as matmul"""
+        return self._product(True, d, out)
+
+    def dense(self):
+        """expand_features' result for this matrix (a fresh [n, F] fp32 device tensor), on demand"""
+        return expand_features([self._source])[0]
+
+
+class SparseDenseBatch:
+    """Job table for wdg_sparse_dense_batched_f32: entries (DeviceFeatures, transposed, W, Y) - Y = X W, or X^T W with transposed - one
+    launch.  W [cols, m] and Y [rows, m] are fp32 device matrices with unit inner stride and any leading dimension >= m."""
+
+    MAX_JOBS = 65535
+
+    def __init__(self, entries, keep=True):
+        """keep: hold the entries' tensors for as long as the table lives (False: the caller keeps them alive while it launches)"""
+        import torch
+
+        from ._lib import SparseDenseJob, require_gpu
+        from ._rt import _ld
+        who = "SparseDenseBatch"
+        if len(entries) > self.MAX_JOBS:
+            raise ValueError(f"{who}: {len(entries)} entries; one launch takes {self.MAX_JOBS}")
+        tab = np.zeros(len(entries), np.dtype(SparseDenseJob))
+        for i, (feats, transposed, w, y) in enumerate(entries):
+            if not isinstance(feats, DeviceFeatures):
+                raise TypeError(f"{who}: entry {i}: a DeviceFeatures expected, not {type(feats).__name__}")
+            rowptr, col, val, order, rows, cols = feats._csr(bool(transposed))
+            for name, t, r in (("W", w, cols), ("Y", y, rows)):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == r and t.stride(1) == 1):
+                    raise ValueError(f"{who}: entry {i}: {name} must be an fp32 device matrix of {r} rows with unit inner stride")
+            if w.shape[1] != y.shape[1]:
+                raise ValueError(f"{who}: entry {i}: W has {w.shape[1]} columns, Y has {y.shape[1]}")
+            m = int(w.shape[1])
+            for name, t in (("rowptr", rowptr), ("col", col), ("val", val), ("order", order), ("W", w), ("Y", y)):
+                tab[name][i] = 0 if t is None or t.numel() == 0 else t.data_ptr()
+            if col.numel() == 0:
+                tab["col"][i] = rowptr.data_ptr()  # (a matrix without entries: any address will do, no row reads it)
+            tab["ldw"][i], tab["ldy"][i] = max(_ld(w), m), max(_ld(y), m)
+            tab["n_rows"][i], tab["n_cols"][i], tab["m"][i] = rows, cols, m
+        self.keep = entries if keep else None
+        self.n_jobs = len(entries)
+        self.max_rows, self.max_m = int(tab["n_rows"].max(initial=0)), int(tab["m"].max(initial=0))
+        self.table = self._upload(tab, require_gpu())
+
+    @staticmethod
+    def _upload(tab, dev):
+        import ctypes
+
+        import torch
+
+        from ._lib import check, lib
+        from ._rt import _h2d
+        host = np.ascontiguousarray(tab)
+        check(lib.wdg_sparse_dense_check_jobs(ctypes.c_void_p(host.ctypes.data), len(host)), "wdg_sparse_dense_check_jobs")
+        return _h2d(host.view(np.uint8), dev) if len(host) else torch.empty(0, dtype=torch.uint8)
+
+    def launch(self):
+        from ._lib import check, lib, stream_handle
+        from ._rt import _ptr
+        check(lib.wdg_sparse_dense_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_m, stream_handle()), "wdg_sparse_dense_batched_f32")
+
+
+def sparse_operand(who, x, n):
+    """what a stacked trainer takes as `x`, decided on the host before the device is touched: True for a DeviceFeatures, a
+    SparseFeatures or a scipy sparse matrix of n rows (ValueError for another row count), False for a dense array or tensor;
+    TypeError for an object that is no matrix at all (None, a string, a mapping, a torch tensor in a sparse layout)"""
+    if isinstance(x, (DeviceFeatures, SparseFeatures)) or (hasattr(x, "tocsr") and hasattr(x, "nnz")):
+        shape = tuple(int(v) for v in x.shape)
+        if len(shape) != 2 or shape[0] != n:
+            raise ValueError(f"{who}: x must be [n = {n}, F], got a sparse matrix of shape {shape}")
+        return True
+    if x is None or isinstance(x, (str, bytes, dict, set)) or (hasattr(x, "layout") and hasattr(x, "is_sparse") and (x.is_sparse or "Sparse" in str(x.layout))):
+        raise TypeError(f"{who}: x must be a dense [n, F] array or tensor, an ops.SparseFeatures, a scipy sparse matrix or an ops.DeviceFeatures, "
+                        f"not {type(x).__name__}" + (" in a sparse torch layout" if hasattr(x, "layout") else ""))
+    return False

@@ -29,6 +29,7 @@ from ._lib import require_gpu
 from ._rt import _dev, capture_graphs, snapshot
 from .aggregate import spmm
 from .gemm import GemmBatch, gemm
+from .sparse_features import DeviceFeatures, SparseDenseBatch, sparse_operand
 from .train import (AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch,
                     dropout_constants, select_rule, whole_number)
 
@@ -156,7 +157,10 @@ class SplitTrainBatch:
     step word: what models.DeviceDropout(dropout_seed, stream=r) draws.
 
     adj: whatever models.NormAdj takes, or a NormAdj (then `symmetric` is the NormAdj's own); None for the MLP kinds.
-    x [n, F] fp32 (host or device), labels [n] integers, masks bool [R, 3, n] (train, validation, test; sizes may differ between
+    x [n, F] fp32 (host or device) - or sparse: an ops.SparseFeatures, a scipy sparse matrix or an ops.DeviceFeatures: the
+    matrix then stays CSR on the device, X W0 / X W and X^T dP / X^T dlogits are launches of csrc/sparse_dense.hip whose bits are the
+    dense products' wherever those take their single fma chain, self.x and self.xt are None and self.feats is the DeviceFeatures
+    ("sgc" expands it once for Y = A_hat X and drops the expansion) -, labels [n] integers, masks bool [R, 3, n] (train, validation, test; sizes may differ between
     replicas, classes may be unbalanced).  Raises ValueError for a replica without a train or a validation row, overlapping sets, a
     split row whose label lies outside 0 .. C - 1, more than 16 classes, dropout with a kind that has no hidden layer.
 
@@ -233,10 +237,11 @@ class SplitTrainBatch:
             self.w0, self.w1 = torch.nn.Parameter(w0), torch.nn.Parameter(w1)
             self.w0.grad, self.w1.grad = torch.zeros_like(w0), torch.zeros_like(w1)
             self.params = [self.w0, self.w1]
-            self.xt = x.t().contiguous()  # for dW0 = X^T dP
+            self.xt = x.t().contiguous() if x is not None else None  # for dW0 = X^T dP (a sparse x: the transposed index of self.feats)
             self.hid, self.hid_t, self.dhid, self.w1t = z(n, R * h), z(R * h, n), z(n, R * h), z(R, cs, h)
             if kind == "gcn":
                 self.p, self.z, self.dz, self.dp = z(n, R * h), z(n, R * cs), z(n, R * cs), z(n, R * h)
+            self._first_layer(self.w0, self.p if kind == "gcn" else self.hid, self.dp if kind == "gcn" else self.dhid)
             head_out = self.z if kind == "gcn" else self.logits     # Z_r = H_r W1_r: aggregated afterwards ("gcn") or the logits ("mlp2")
             head_grad = self.dz if kind == "gcn" else self.dlogits  # dZ_r
             self.head = GemmBatch([(blk(self.hid, r, h), self.w1.data[r], blk(head_out, r, cs), None) for r in range(R)])
@@ -266,10 +271,13 @@ class SplitTrainBatch:
             self.drop, self.drops = None, []
             if kind == "sgc":
                 a = self.adj
-                self.y = spmm(a.graph, x, row_scale=a.row_scale, col_scale=a.col_scale)  # Y = A_hat X, once
+                # (a sparse x is expanded for this one aggregation and the expansion dropped: Y is dense whatever X was)
+                self.y = spmm(a.graph, x if x is not None else self.feats.dense(), row_scale=a.row_scale, col_scale=a.col_scale)  # Y = A_hat X, once
+                self._first_layer(None, None, None)
             else:
                 self.y = x
-            self.yt = self.y.t().contiguous()  # for dW = Y^T dlogits
+                self._first_layer(self.w, self.logits, self.dlogits)
+            self.yt = self.y.t().contiguous() if self.y is not None else None  # for dW = Y^T dlogits
         self._epilogue()
 
     # -- the constructor's steps that every stacked run shares (acm_split_train.AcmSplitTrainBatch builds its own layout between them) --
@@ -284,19 +292,49 @@ class SplitTrainBatch:
         c, counts = _classes_and_counts(who, labels_np, masks)
         if self.select == AUC_RULE:
             _binary_validation(who, labels_np, masks)
+        sparse = sparse_operand(who, x, n)  # (a sparse x of another row count, or an object that is no matrix at all: refused here)
         dev = require_gpu()  # (after the checks that need no device)
         from . import models
         self.adj = adj if isinstance(adj, models.NormAdj) or (adj is None and not needs_graph) else models.NormAdj(adj, symmetric=symmetric)
         if needs_graph and self.adj.n != n:
             raise ValueError(f"{who}: the graph has {self.adj.n} nodes, labels has {n}")
-        x = _dev(x, torch.float32, dev)
-        if x.dim() != 2 or x.shape[0] != n:
-            raise ValueError(f"{who}: x must be [n = {n}, F]")
-        self.x, self.n, self.R, self.c, self.cs, self.f, self.h = x, n, R, c, self._class_stride(c), x.shape[1], int(hidden)
+        # a sparse x: the matrix stays CSR on the device and self.x is None; a dense array takes the path it always took
+        self.feats = (x if isinstance(x, DeviceFeatures) else DeviceFeatures(x)) if sparse else None
+        if sparse:
+            self.xt = None  # (no kind holds a dense x^T then; the one-layer kinds never had the attribute)
+        else:
+            x = _dev(x, torch.float32, dev)
+            if x.dim() != 2 or x.shape[0] != n:
+                raise ValueError(f"{who}: x must be [n = {n}, F]")
+        self.x, self.n, self.R, self.c, self.cs, self.h = (None if sparse else x), n, R, c, self._class_stride(c), int(hidden)
+        self.f = int(self.feats.shape[1] if sparse else x.shape[1])
         self.lr, self.weight_decay, self.seed = lr, weight_decay, int(seed)
         self.dropout_seed = self.seed if dropout_seed is None else int(dropout_seed)
         self._stage_splits(labels_np, masks, counts, dev)
         return dev
+
+    def _first_layer(self, weight, product, product_grad):
+        """the two products that read x, for a run built from sparse features: X weight -> product and X^T product_grad -> weight.grad
+        as one-job tables of wdg_sparse_dense_batched_f32, built here and launched by forward() / _backward() in place of the dense
+        gemm calls; None for a dense x, and for a kind whose epochs do not read x (weight None)"""
+        sparse = self.feats is not None and weight is not None
+        # (the run owns its tables, and they own nothing but this run's tensors: dropping the run frees them, whoever keeps self.feats)
+        self.x_product = SparseDenseBatch([(self.feats, False, weight.data, product)]) if sparse else None
+        self.xt_product = SparseDenseBatch([(self.feats, True, product_grad, weight.grad)]) if sparse else None
+
+    def _x_times(self, dense, w, out):
+        """X w into out (`dense`: the dense operand of a run built from a dense x)"""
+        if self.x_product is None:
+            gemm(dense, w, out=out)
+        else:
+            self.x_product.launch()
+
+    def _xt_times(self, dense_t, d, out):
+        """X^T d into out"""
+        if self.xt_product is None:
+            gemm(dense_t, d, out=out)
+        else:
+            self.xt_product.launch()
 
     def _selection(self, who, select, patience, curve_epochs):
         """the checks of select, patience and curve_epochs (before anything touches the device)"""
@@ -404,18 +442,18 @@ class SplitTrainBatch:
         word.  The hidden layer's launch also leaves hid^T in hid_t, which the backward pass reads."""
         with torch.no_grad():
             if not self.two_layer:
-                gemm(self.y, self.w.data, out=self.logits)
+                self._x_times(self.y, self.w.data, self.logits)
                 return
             units = self.drops if (train or self.dropout == 0) else [self.relu]
             if self.kind == "gcn":
-                gemm(self.x, self.w0.data, out=self.p)     # P = X [W0_1 | ... | W0_R]
+                self._x_times(self.x, self.w0.data, self.p)  # P = X [W0_1 | ... | W0_R]
                 self._aggregate(self.p, self.hid)           # A_hat P
                 for unit in units:
                     unit.launch(self.step)                  # relu (+ dropout), hid^T
                 self.head.launch()                          # Z_r = H_r W1_r
                 self._aggregate(self.z, self.logits)        # logits = A_hat Z
             else:
-                gemm(self.x, self.w0.data, out=self.hid)
+                self._x_times(self.x, self.w0.data, self.hid)
                 for unit in units:
                     unit.launch(self.step)
                 self.head.launch()
@@ -424,7 +462,7 @@ class SplitTrainBatch:
         """the weight gradients behind self.dlogits, for the forward pass that produced self.logits"""
         with torch.no_grad():
             if not self.two_layer:
-                gemm(self.yt, self.dlogits, out=self.w.grad)  # dW = Y^T dlogits
+                self._xt_times(self.yt, self.dlogits, self.w.grad)  # dW = Y^T dlogits
                 return
             if self.kind == "gcn":
                 self._aggregate_t(self.dlogits, self.dz)      # dZ = A_hat^T dlogits
@@ -436,9 +474,9 @@ class SplitTrainBatch:
             self.dhid.copy_(torch.where(self.hid > 0, self.dhid * scale, 0.0))
             if self.kind == "gcn":
                 self._aggregate_t(self.dhid, self.dp)         # dP = A_hat^T dH
-                gemm(self.xt, self.dp, out=self.w0.grad)      # dW0 = X^T dP
+                self._xt_times(self.xt, self.dp, self.w0.grad)  # dW0 = X^T dP
             else:
-                gemm(self.xt, self.dhid, out=self.w0.grad)
+                self._xt_times(self.xt, self.dhid, self.w0.grad)
 
     def gradients(self):
         """the gradients of every replica's mean train loss at the current weights into the parameters' .grad (no weight decay, no
@@ -609,7 +647,7 @@ class SplitTrainBatch:
         with torch.random.fork_rng(devices=[]):  # (the constructor draws an initialisation that is overwritten below)
             rng = models.DeviceDropout(self.dropout_seed, stream=int(self.replica_ids[r])) if self.two_layer and p > 0 else None
             model = self._empty_model(models, p, rng)
-        model = model.to(self.x.device)
+        model = model.to(self.logits.device)
         with torch.no_grad():
             for p, w in zip(model.parameters(), self.weights_of(r, kept=kept)):
                 p.copy_(w)
@@ -870,11 +908,15 @@ def grid_search(adj, x, labels, masks, grid, kind="gcn", hidden=64, epochs=200, 
     if max_replicas is None:
         max_replicas = default_max_replicas(n, int(hidden) if two_layer else cs, kind, S)
     chunks = chunk_settings(len(grid), S, max_replicas)
+    sparse = sparse_operand(who, x, n)
     dev = require_gpu()  # (after the checks that need no device)
     from . import models
     if kind in ("sgc", "gcn") and not isinstance(adj, models.NormAdj):
         adj = models.NormAdj(adj, symmetric=symmetric)
-    x = _dev(x, torch.float32, dev)
+    if sparse:
+        x = x if isinstance(x, DeviceFeatures) else DeviceFeatures(x)  # one device copy of the compact matrix serves all chunks
+    else:
+        x = _dev(x, torch.float32, dev)
     labels_dev = torch.as_tensor(labels_np.astype(np.int64))
     best = np.zeros((len(grid), S, 3), np.int64)
     best_loss, stopped_at = np.zeros((len(grid), S, 3), np.float32), np.zeros((len(grid), S), np.int64)
