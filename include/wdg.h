@@ -1083,6 +1083,95 @@ int wdg_synth_feature_rows(const int32_t *base_labels, int32_t n_base, int32_t n
                            void *workspace, size_t workspace_bytes, wdg_stream_t stream);
 
 /*
+ * Graphs of the CSBM-H model, generated on the device: classes of ANY sizes, each with an out-degree d[c] and a number k[c] of
+ * same-class neighbours of its own (the model's h d_c with h d_c an integer) - the two ablation axes of the reference's command
+ * line, csbm-h.py:428-442 (n0 : n1 and d0, d1), which wdg_synth_regular_batched (equal classes, one k, one d) cannot draw.
+ * replaces: nothing the reference computes on a graph - csbm-h.py:174-175,187-191 draws the aggregated features from their closed-form
+ *           law (csbm-h.py:46-56); this generator makes the graphs on which that law can be measured.
+ *
+ * The definition, for a graph of C = n_classes contiguous classes in order (class c = rows [s_c, s_c + class_size[c]), n = the sum):
+ *   key(i, j) is EXACTLY wdg_synth_regular_batched's: word j & 3 of Philox4x32-10 with counter {i, j >> 2, 0, 0}, key {seed low, high};
+ *   row i of class c holds
+ *     - the k[c] columns j of its class block, j != i, with the smallest (key(i, j), j), and
+ *     - the d[c] - k[c] columns j outside the block with the smallest (key(i, j), j),
+ *     - with WDG_SYNTH_SELF_LOOPS also column i,
+ *   written ascending; every stored value is 1; labels[i] = c; rowptr = the prefix sum of the rows' lengths D_c = d[c] (+ 1 with loops).
+ * With equal class sizes and equal k, d the output is wdg_synth_regular_batched's bit for bit (one row routine: csrc/synth_row.h).
+ * k[c] = 0 and d[c] = k[c] are allowed.  All jobs go in one launch; the table is given twice, as to the regular generator.
+ * Refused on the HOST copy of the table, before any launch (WDG_ERR_INVALID): a null table with n_jobs > 0, more than 65535 jobs,
+ * n_classes outside 1 .. 16, a class of no nodes, n outside 1 .. 16384, k[c] outside 0 .. class_size[c] - 1, d[c] < k[c],
+ * d[c] - k[c] > n - class_size[c], unknown flags, a null output.  n_jobs == 0: nothing.
+ */
+#define WDG_SYNTH_MAX_CLASSES 16
+typedef struct wdg_synth_classes_job {
+    int32_t *rowptr;        /* out [n + 1] */
+    int32_t *col;           /* out [sum_c class_size[c] D_c] */
+    float *val;             /* out, as col: ones */
+    int32_t *labels;        /* out [n] */
+    uint64_t seed;
+    int32_t n_classes, flags;
+    int32_t class_size[WDG_SYNTH_MAX_CLASSES], k[WDG_SYNTH_MAX_CLASSES], d[WDG_SYNTH_MAX_CLASSES];
+} wdg_synth_classes_job;
+int wdg_synth_classes_batched(const wdg_synth_classes_job *jobs_host, const wdg_synth_classes_job *jobs_dev, int32_t n_jobs,
+                              wdg_stream_t stream);
+
+/*
+ * Gaussian class features, drawn on the device: x[i][f] = mean[labels[i]][f] + sd[labels[i]] z(i, f) with z standard normal -
+ * the node features of the CSBM-H model, N(mu_c, sigma_c I) with sd = sqrt(sigma_c) (the reference's sigma is a VARIANCE).
+ * replaces: np.random.multivariate_normal(mu, sigma * np.eye(2), n), csbm-h.py:174-175 (same distribution, a documented stream).
+ *
+ * The definition: the Philox4x32-10 block with counter {i, q, 0, 0} and key {seed low, seed high} serves features 4q .. 4q + 3 of
+ * row i; its words (w0, w1) and (w2, w3) are two Box-Muller pairs:
+ *   u1 = ((w >> 8) + 1) 2^-24 in (0, 1],  u2 = (w' >> 8) 2^-24 in [0, 1)   (both exact in fp32),
+ *   r = sqrtf(-2 logf(u1)),  z_a = r cospif(2 u2),  z_b = r sinpif(2 u2)   (features 4q, 4q + 1 from (w0, w1); 4q + 2, 4q + 3 from (w2, w3)),
+ *   x = fmaf(sd[c], z, mean[c][f])
+ * with the accurate library functions (the unit is compiled without fast-math).  |z| <= sqrt(48 ln 2) = 5.77.  sd = 0 gives the mean
+ * exactly.  A label outside [0, n_classes) writes NaN.  Callers give the stream a seed of its own (not the graph's).
+ * Refused on the HOST copy of the table, before any launch (WDG_ERR_INVALID): a null table with n_jobs > 0, more than 65535 jobs,
+ * n < 0, F outside 1 .. 16, n_classes outside 1 .. 16, ldx < F, a null pointer in a job with n > 0.  n_jobs == 0: nothing.
+ */
+#define WDG_GAUSS_MAX_F 16
+typedef struct wdg_gauss_job {
+    float *x;               /* out [n, F], row i at x + i ldx */
+    const int32_t *labels;  /* [n] */
+    const float *mean;      /* [n_classes, F] */
+    const float *sd;        /* [n_classes] */
+    int64_t ldx;
+    uint64_t seed;
+    int32_t n, F, n_classes, reserved;
+} wdg_gauss_job;
+int wdg_gauss_features_batched_f32(const wdg_gauss_job *jobs_host, const wdg_gauss_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream);
+
+/*
+ * The errors the Bayes rule of two isotropic Gaussian classes makes on three feature sets of a graph: t = 0 the features x, t = 1
+ * the aggregated features h (the caller's A_rw x), t = 2 the high-pass features x - h.  Per job, counts[t][true][predicted] (int32
+ * [3, 2, 2]) over the rows whose label is 0 or 1 (other rows are not counted).
+ * replaces: the evaluation the reference only has in closed form - chi2comb_error, csbm-h.py:9-37, and PBE, csbm-h.py:40-60.
+ *
+ * Arithmetic: the high-pass row is ONE fp32 subtraction x[i][f] - h[i][f]; everything after it is fp64, every multiply and add its
+ * own rounded operation (the unit is compiled with contraction off):
+ *   s_c = sum over f ascending of (z_f - mean[t][c][f])^2   (from +0),   g_c = bias[t][c] - inv2v[t][c] * s_c,
+ * class 0 is predicted iff g_0 > g_1 - so a NaN predicts 1.  The HOST forms bias = ln n_c - (F / 2) ln v_c and inv2v = 1 / (2 v_c).
+ * A workgroup per job; counts are integer adds in registers and LDS and one plain store per entry: no atomic, nothing to clear
+ * beforehand, bit-identical from run to run.
+ * Refused on the HOST copy of the table, before any launch (WDG_ERR_INVALID): a null table with n_jobs > 0, more than 65535 jobs,
+ * n < 0, F outside 1 .. 16, ldx or ldh < F, a null counts, a null x, h or labels in a job with n > 0.  n_jobs == 0: nothing.
+ */
+#define WDG_QDA_MAX_F 16
+typedef struct wdg_qda_job {
+    const float *x;         /* [n, F] */
+    const float *h;         /* [n, F] */
+    const int32_t *labels;  /* [n] */
+    int32_t *counts;        /* out [3, 2, 2]: [set][true][predicted] */
+    int64_t ldx, ldh;
+    int32_t n, F;
+    double mean[3][2][WDG_QDA_MAX_F];
+    double inv2v[3][2];
+    double bias[3][2];
+} wdg_qda_job;
+int wdg_qda_errors_batched_i32(const wdg_qda_job *jobs_host, const wdg_qda_job *jobs_dev, int32_t n_jobs, wdg_stream_t stream);
+
+/*
  * The channel mix of an ACM layer (adaptive channel mixing: a low-pass, a high-pass and an identity channel weighted per node)
  * for many models in one launch, and its backward pass.  The reference's loader returns the high-pass operator g_high = I - A_hat
  * beside the low-pass one and its accuracy tables name "mf-" models, but it ships no model code: the layer is DEFINED here

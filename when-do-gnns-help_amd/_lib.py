@@ -184,6 +184,9 @@ SIGNATURES = {
     "wdg_sparse_dense_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_feat_scaled_values_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "wdg_synth_classes_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "wdg_gauss_features_batched_f32": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "wdg_qda_errors_batched_i32": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
@@ -270,6 +273,25 @@ class SynthJob(ctypes.Structure):
     _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("val", c_void_p), ("labels", c_void_p), ("rowptr_union", c_void_p),
                 ("seed", ctypes.c_uint64), ("n", c_int32), ("n_classes", c_int32), ("k", c_int32), ("d", c_int32), ("flags", c_int32),
                 ("nnz_base", c_int32)]
+
+
+class SynthClassesJob(ctypes.Structure):
+    """mirror of `wdg_synth_classes_job` (include/wdg.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("val", c_void_p), ("labels", c_void_p), ("seed", ctypes.c_uint64),
+                ("n_classes", c_int32), ("flags", c_int32), ("class_size", c_int32 * 16), ("k", c_int32 * 16), ("d", c_int32 * 16)]
+
+
+class GaussJob(ctypes.Structure):
+    """mirror of `wdg_gauss_job` (include/wdg.h)"""
+    _fields_ = [("x", c_void_p), ("labels", c_void_p), ("mean", c_void_p), ("sd", c_void_p), ("ldx", c_int64), ("seed", ctypes.c_uint64),
+                ("n", c_int32), ("F", c_int32), ("n_classes", c_int32), ("reserved", c_int32)]
+
+
+class QdaJob(ctypes.Structure):
+    """mirror of `wdg_qda_job` (include/wdg.h)"""
+    _fields_ = [("x", c_void_p), ("h", c_void_p), ("labels", c_void_p), ("counts", c_void_p), ("ldx", c_int64), ("ldh", c_int64),
+                ("n", c_int32), ("F", c_int32), ("mean", ctypes.c_double * 16 * 2 * 3), ("inv2v", ctypes.c_double * 2 * 3),
+                ("bias", ctypes.c_double * 2 * 3)]
 
 
 class LasJob(ctypes.Structure):

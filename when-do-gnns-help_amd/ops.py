@@ -8,7 +8,11 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         (capture_graphs, snapshot: TrainBatch, SplitTrainBatch and models.train_eval_graphed call it)
   graphs.py             CsrGraph (+ its one-time plans), GraphBatch (a shard's graphs in one build, or GENERATED on the device:
                         GraphBatch.generated), normalisations
-  synth.py              regular_graph_device, sample_feature_rows (the device generators; the numpy generators live there too)
+  synth.py              regular_graph_device, sample_feature_rows (the device generators; the numpy generators live there too),
+                        class_graphs_device / ClassGraphBatch (classes of any sizes, a k and a d per class), gauss_features_device /
+                        GaussFeatureBatch (Gaussian class features)
+  csbmh.py              the CSBM-H closed forms (host, fp64), QdaBatch (the Bayes rule's error counts on x, A_rw x and x - A_rw x) and
+                        empirical (the curves measured on sampled graphs); reached as wdg_amd.csbmh, not re-exported here
   aggregate.py          spmm, SpmmBatch (the quad-row kernel's tape and its cost cut), spmm_plan
   stats.py              edge / label statistics, LAS, per-edge cosine, their job tables
   gemm.py               gemm, gemm_skinny, GemmBatch, Mlp2Batch
@@ -54,7 +58,7 @@ from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
 from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, HeadTrainBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
-from .synth import regular_graph_device, sample_feature_rows  # noqa: F401
+from .synth import class_graphs_device, ClassGraphBatch, gauss_features_device, GaussFeatureBatch, regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, DeviceFeatures, expand_features, feature_image_floats, FeatureExpand, SparseDenseBatch, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
     deflation_enabled, EdgeGramBatch, GnbBatch, GramBatch, kr_split_sizes, KrBatch, KrSets, PropagatedGram, RowRepBatch, SvmBatch, _KR_JOB_DTYPE,

@@ -9,7 +9,9 @@ verified on those files, is restated here so that benchmarks and tests need no d
   * `data_synthesis/800` is k=2, `data_synthesis/4000` is k=10 (the directory name is k * 400, synthetic_plot.py:22);
   * features: dense fp32 [N,F], ~10 % non-zeros, rows L1-normalised (pubmed-sample statistics).
 Host-side numpy (numpy PCG64 seeded by (seed, h)); the graphs are inputs, not part of the timed hot path.
-regular_graph_device / sample_feature_rows at the end draw the same family, and the rows behind its features, on the device.
+regular_graph_device / sample_feature_rows at the end draw the same family, and the rows behind its features, on the device;
+class_graphs_device / gauss_features_device draw the CSBM-H model's graphs (classes of any sizes, a degree and a same-class count per
+class) and its Gaussian class features (csbm-h.py:174-175).
 """
 import numpy as np
 
@@ -139,3 +141,111 @@ def sample_feature_rows(base_labels_dev, n, n_classes, seed):
         if (counts == 0).any():
             raise ValueError(f"sample_feature_rows: class {int(np.flatnonzero(counts == 0)[0])} has no base rows")
     return out
+
+
+class ClassGraphBatch:
+    """Graphs of classes of ANY sizes, each class with a same-class count k[c] and an out-degree d[c] of its own, drawn on the device
+    (wdg_synth_classes_batched; the definition is in include/wdg.h) - all jobs in one launch, on one pooled allocation.
+    specs: list of (class_sizes, k, d, seed) with up to 16 classes; seed: 64 bits, used as is.
+    .graphs: list of (CsrGraph, labels int32 [n]) - views of the pool, rows sorted by column, every value 1; written by launch()."""
+
+    def __init__(self, specs, self_loops=False):
+        import ctypes
+
+        import torch
+
+        from . import _lib, ops
+        dev = ops.require_gpu()
+        loops = 1 if self_loops else 0
+        self.host = (_lib.SynthClassesJob * max(len(specs), 1))()
+        sizes = []
+        for g, (cls, k, d, seed) in enumerate(specs):
+            cls, k, d = [int(v) for v in cls], [int(v) for v in k], [int(v) for v in d]
+            if not (1 <= len(cls) <= 16 and len(k) == len(cls) and len(d) == len(cls)):
+                raise ValueError(f"class_graphs_device: graph {g}: 1 .. 16 classes with a size, a k and a d each")
+            n, nnz = sum(cls), sum(m * (dc + loops) for m, dc in zip(cls, d))
+            sizes.append((n, nnz))
+            j = self.host[g]
+            j.n_classes, j.flags, j.seed = len(cls), loops, int(seed) & 0xFFFFFFFFFFFFFFFF
+            for c in range(len(cls)):
+                j.class_size[c], j.k[c], j.d[c] = cls[c], k[c], d[c]
+        words = sum(2 * n + 1 + 2 * nnz for n, nnz in sizes)  # per graph: rowptr [n + 1], labels [n], col [nnz], val [nnz]
+        if words >= (1 << 31):
+            raise ValueError("class_graphs_device: more than 2^31 words in one pool")
+        self.pool = torch.zeros(max(words, 1), dtype=torch.int32, device=dev)
+        self.graphs, at = [], 0
+        for g, (n, nnz) in enumerate(sizes):
+            rowptr, labels = self.pool[at:at + n + 1], self.pool[at + n + 1:at + 2 * n + 1]
+            col, val = self.pool[at + 2 * n + 1:at + 2 * n + 1 + nnz], self.pool[at + 2 * n + 1 + nnz:at + 2 * n + 1 + 2 * nnz].view(torch.float32)
+            j = self.host[g]
+            base = self.pool.data_ptr() + 4 * at
+            j.rowptr, j.labels, j.col, j.val = base, base + 4 * (n + 1), base + 4 * (2 * n + 1), base + 4 * (2 * n + 1 + nnz)
+            graph = ops.CsrGraph(rowptr, col, val, n, n)
+            graph._unit_values = True  # (the generator writes ones)
+            self.graphs.append((graph, labels))
+            at += 2 * n + 1 + 2 * nnz
+        self.labels = [lab for _g, lab in self.graphs]
+        self.n_jobs = len(specs)
+        self._cast = ctypes.cast(self.host, ctypes.c_void_p)
+        self.table = ops._table(self.host) if specs else None
+
+    def launch(self):
+        """the one launch, on the current stream (counter-based: again = the same bits into the same arrays)"""
+        from . import ops
+        ops.check(ops.lib.wdg_synth_classes_batched(self._cast, ops._ptr(self.table), self.n_jobs, ops.stream_handle()),
+                  "wdg_synth_classes_batched")
+        return self.graphs
+
+
+def class_graphs_device(specs, self_loops=False):
+    """-> list of (CsrGraph, labels): ClassGraphBatch(specs, self_loops), launched"""
+    return ClassGraphBatch(specs, self_loops).launch()
+
+
+class GaussFeatureBatch:
+    """Gaussian class features drawn on the device (wdg_gauss_features_batched_f32; the definition is in include/wdg.h): job g's
+    x[i] = mean[labels[i]] + sd[labels[i]] z, one launch for all jobs, one pooled [sum n, ld] matrix (padding columns are zero).
+    labels: list of int32 device tensors; mean [C, F], sd [C] (standard deviations) shared by the jobs; seeds: one per job - give the
+    features a seed of their own, not the graph's.  .x: list of [n, F] views, written by launch()."""
+
+    def __init__(self, labels, mean, sd, seeds, ld=None):
+        import ctypes
+
+        import torch
+
+        from . import _lib, ops
+        dev = ops.require_gpu()
+        mean, sd = np.ascontiguousarray(mean, np.float32), np.ascontiguousarray(sd, np.float32).reshape(-1)
+        if mean.ndim != 2 or sd.shape[0] != mean.shape[0] or len(seeds) != len(labels):
+            raise ValueError("gauss_features_device: mean [C, F], sd [C] and a seed per job expected")
+        C, F = mean.shape
+        ld = F if ld is None else int(ld)
+        if ld < F:
+            raise ValueError(f"gauss_features_device: ld = {ld} below F = {F}")
+        self.mean, self.sd = ops._h2d(mean, dev), ops._h2d(sd, dev)
+        ns = [int(lab.shape[0]) for lab in labels]
+        self.pool = torch.zeros((max(sum(ns), 1), ld), dtype=torch.float32, device=dev)
+        self.host = (_lib.GaussJob * max(len(labels), 1))()
+        self.x, at = [], 0
+        for g, (lab, n, seed) in enumerate(zip(labels, ns, seeds)):
+            if lab.dtype != torch.int32 or not lab.is_contiguous():
+                raise ValueError(f"gauss_features_device: job {g}: contiguous int32 labels expected")
+            j = self.host[g]
+            j.x, j.labels, j.mean, j.sd = self.pool.data_ptr() + 4 * at * ld, lab.data_ptr() if n else 0, self.mean.data_ptr(), self.sd.data_ptr()
+            j.ldx, j.seed, j.n, j.F, j.n_classes, j.reserved = ld, int(seed) & 0xFFFFFFFFFFFFFFFF, n, F, C, 0
+            self.x.append(self.pool[at:at + n, :F])
+            at += n
+        self.keep, self.n_jobs = labels, len(labels)
+        self._cast = ctypes.cast(self.host, ctypes.c_void_p)
+        self.table = ops._table(self.host) if labels else None
+
+    def launch(self):
+        from . import ops
+        ops.check(ops.lib.wdg_gauss_features_batched_f32(self._cast, ops._ptr(self.table), self.n_jobs, ops.stream_handle()),
+                  "wdg_gauss_features_batched_f32")
+        return self.x
+
+
+def gauss_features_device(labels, mean, sd, seeds, ld=None):
+    """-> list of fp32 [n, F] device matrices: GaussFeatureBatch(labels, mean, sd, seeds, ld), launched"""
+    return GaussFeatureBatch(labels, mean, sd, seeds, ld).launch()
