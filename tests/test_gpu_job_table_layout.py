@@ -1,0 +1,37 @@
+"""The bytes of the training job tables are pinned: scripts/describe_job_tables.py builds the ten tables of train.py and SparseDenseBatch
+at small shapes and describes every record, every owned buffer (as built, and after reset()), every per-job view and state_tensors();
+tests/golden/job_table_layout.json is that description at the commit BEFORE the tables moved onto job_table.JobTable."""
+import importlib.util
+import json
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# what the base gives the tables that had no reset() / state_tensors() of their own when the fixture was written (so the fixture is silent
+# about them): reset() puts back what the constructor left, and a run rewinds XentEvalBatch.best and AdamBatch.moments - what
+# SplitTrainBatch.capture() listed by hand
+NEW_STATE = {"XentEvalBatch": ["best"], "AdamBatch": ["moments"]}
+
+
+@pytest.fixture(scope="module")
+def described():
+    spec = importlib.util.spec_from_file_location("describe_job_tables", os.path.join(ROOT, "scripts", "describe_job_tables.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return json.loads(json.dumps(mod.describe_all()))  # (through JSON: tuples and lists compare alike)
+
+
+@pytest.mark.gpu
+def test_every_table_is_laid_out_as_in_the_fixture(described):
+    with open(os.path.join(ROOT, "tests", "golden", "job_table_layout.json")) as f:
+        want = json.load(f)
+    assert sorted(described) == sorted(want)
+    for label, got in described.items():
+        kind = label.split(" ")[0]
+        if "buffers_after_reset" not in want[label] and "buffers_after_reset" in got:
+            assert got.pop("buffers_after_reset") == got["buffers"], label
+        if "state_tensors" not in want[label] and "state_tensors" in got:
+            assert got.pop("state_tensors") == NEW_STATE.get(kind, []), label
+        assert got == want[label], label

@@ -423,6 +423,7 @@ class SparseDenseBatch:
 
         from ._lib import SparseDenseJob, require_gpu
         from ._rt import _ld
+        from .job_table import _upload
         who = "SparseDenseBatch"
         if len(entries) > self.MAX_JOBS:
             raise ValueError(f"{who}: {len(entries)} entries; one launch takes {self.MAX_JOBS}")
@@ -446,19 +447,7 @@ class SparseDenseBatch:
         self.keep = entries if keep else None
         self.n_jobs = len(entries)
         self.max_rows, self.max_m = int(tab["n_rows"].max(initial=0)), int(tab["m"].max(initial=0))
-        self.table = self._upload(tab, require_gpu())
-
-    @staticmethod
-    def _upload(tab, dev):
-        import ctypes
-
-        import torch
-
-        from ._lib import check, lib
-        from ._rt import _h2d
-        host = np.ascontiguousarray(tab)
-        check(lib.wdg_sparse_dense_check_jobs(ctypes.c_void_p(host.ctypes.data), len(host)), "wdg_sparse_dense_check_jobs")
-        return _h2d(host.view(np.uint8), dev) if len(host) else torch.empty(0, dtype=torch.uint8)
+        self.table = _upload(tab, self.n_jobs, require_gpu(), "wdg_sparse_dense_check_jobs")
 
     def launch(self):
         from ._lib import check, lib, stream_handle

@@ -517,9 +517,8 @@ class SplitTrainBatch:
         # torch's Adam: the state it has is restored, the state the warm-up creates starts from zero
         state = [] if self.adam is not None else [v for st in self.opt.state.values() for v in st.values() if torch.is_tensor(v)]
         kept = self.kept_params + [self.kept_logits] if self.keep_best else []  # (the warm-up epochs leave no trace in them)
-        selection = [self.xent.best] + (self.curve.state_tensors() if self.curve is not None else []) + \
-                    (self.auc.state_tensors() if self.auc is not None else [])
-        restore = snapshot(self.params + [self.step] + selection + ([self.adam.moments] if self.adam is not None else state) + kept)
+        owned = [t for table in (self.xent, self.curve, self.auc, self.adam) if table is not None for t in table.state_tensors()]
+        restore = snapshot(self.params + [self.step] + owned + state + kept)
 
         def warm_up():
             self.forward()

@@ -10,16 +10,18 @@
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
 - csrc/confusion.hip: the predictions and the confusion counts of stacked logits
 - csrc/xent_curve.hip: the evaluation with losses, a learning curve, three selection rules and a patience counter
-- csrc/auc.hip: the exact ROC-AUC of stacked binary logits, the selection on it, its patience counter and its curve"""
-import ctypes
+- csrc/auc.hip: the exact ROC-AUC of stacked binary logits, the selection on it, its patience counter and its curve
+Every table is a job_table.JobTable: what a table is, what it owns and the sequence of its constructor are stated there; a class here
+states its kernel's contract, its checks and its records."""
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, require_gpu, stream_handle
-from ._rt import _h2d, _ld, _ptr
+from ._lib import lib
+from ._rt import _ld, _ptr
+from .job_table import JobTable, StackedLogitsTable, _check_matrix, _check_pair, _offsets, _step_word, _upload, _views_may_overlap  # noqa: F401
 
 # the record types of the job tables: those of the ctypes mirrors of include/wdg.h (names, offsets and size; tests/test_abi*.py check
 # the mirrors against the header)
@@ -39,39 +41,7 @@ AUC_RULE = "val_auc"  # no rule of wdg_xent_curve_job: the selection of wdg_auc_
 AUC_BINS_LOG2 = 12  # AucBatch's default: sign, exponent and three mantissa bits of the score
 
 
-def _check_matrix(table, name, t, shape=None):
-    """ValueError (naming the table and the operand) unless t is a 2-D fp32 device matrix - of `shape`, where one is given (None = any
-    size in that dimension) - whose rows are contiguous and do not overlap; any leading dimension"""
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (
-            shape is not None and any(want is not None and want != got for want, got in zip(shape, t.shape))):
-        what = "2-D" if shape is None else "[" + ", ".join("any" if d is None else str(d) for d in shape) + "]"
-        raise ValueError(f"{table}: {name} must be a {what} fp32 device matrix")
-    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError(f"{table}: the rows of {name} must be contiguous (unit inner stride) and must not overlap")
-
-
-def _step_word(where, step):
-    """-> the pointer of a launch's step word: a one-element int32 DEVICE tensor, read by the kernel when it runs"""
-    if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
-        raise ValueError(f"{where}: a one-element int32 device tensor expected as the step word")
-    return _ptr(step)
-
-
-def _offsets(lens, n):
-    """the lengths of n consecutive blocks -> int64 [n + 1]: where each starts, and the end of the last"""
-    return np.concatenate([[0], np.cumsum(np.fromiter(lens, np.int64, n))]).astype(np.int64)
-
-
-def _upload(tab, n, dev, check_jobs=None):
-    """the device copy of a table of n records (an empty tensor for none) - after the host-side check of the records, where the
-    kernel has one (check_jobs: its name in lib)"""
-    host = np.ascontiguousarray(tab)
-    if check_jobs is not None:
-        check(getattr(lib, check_jobs)(ctypes.c_void_p(host.ctypes.data), n), check_jobs)
-    return _h2d(host.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
-
-
-class HeadTrainBatch:
+class HeadTrainBatch(JobTable):
     """Job table for wdg_head_train_batched_f32: one logistic head logits = M W per problem, trained by full-batch Adam on the
     cross-entropy of its train rows with model selection on its validation hits - a workgroup per problem, all epochs of a
     launch inside it (the arithmetic of sweep.TrainBatch's "sgc" / "mlp1" epoch; csrc/head_train.hip)."""
@@ -84,9 +54,7 @@ class HeadTrainBatch:
         The Adam moments (self.m[i], self.v[i]: zeros) and self.best [n_problems, 3] int32 (validation hits of the best epoch, -1 =
         none yet; test hits at it; its epoch) are the table's own: launch(a) then launch(b, step0=a) is launch(a + b), bit for bit.
         Raises for what the kernel does not hold: F outside 1..4096, C outside 1..8, no train or no validation row."""
-        dev = require_gpu()
-        self.keep = problems
-        n = self.n_jobs = len(problems)
+        n = self._open(problems)
         classes = [int(n_classes)] * n if np.ndim(n_classes) == 0 else [int(c) for c in n_classes]
         if len(classes) != n:
             raise ValueError("HeadTrainBatch: one class count per problem")
@@ -104,39 +72,23 @@ class HeadTrainBatch:
                 raise ValueError("HeadTrainBatch: one label per row of M")
             if tuple(w.shape) != (mat.shape[1], c) or w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
                 raise ValueError("HeadTrainBatch: W must be a contiguous [F, C] fp32 device matrix")
-        offs = _offsets((p_[5].numel() for p_ in problems), n)
-        self._moments = torch.zeros((2, max(int(offs[-1]), 1)), dtype=torch.float32, device=dev)
-        self.m = [self._moments[0, offs[i]:offs[i + 1]].view(problems[i][5].shape) for i in range(n)]
-        self.v = [self._moments[1, offs[i]:offs[i + 1]].view(problems[i][5].shape) for i in range(n)]
-        self.best = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=dev)
-        self.best[:, 0] = -1
-        col = lambda f: np.fromiter((f(p_) for p_ in problems), np.int64, n)  # noqa: E731
-        tab = np.zeros(n, _HEAD_JOB_DTYPE)
-        tab["M"], tab["ldm"] = col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0]))
-        for k, name in enumerate(("labels", "train", "val", "test"), 1):
-            tab[name] = col(lambda p_: p_[k].data_ptr())
-        tab["W"] = col(lambda p_: p_[5].data_ptr())
-        tab["m"] = self._moments.data_ptr() + 4 * offs[:-1]
-        tab["v"] = self._moments.data_ptr() + 4 * (offs[:-1] + self._moments.shape[1])
-        tab["best"] = self.best.data_ptr() + 12 * np.arange(n, dtype=np.int64)
-        tab["n_train"], tab["n_val"], tab["n_test"] = (col(lambda p_: p_[k].shape[0]) for k in (2, 3, 4))
-        tab["F"], tab["C"] = col(lambda p_: p_[0].shape[1]), np.asarray(classes, np.int64)
+        tab = self._records(_HEAD_JOB_DTYPE)
+        for k, field in enumerate(("M", "labels", "train", "val", "test", "W")):
+            self._point(tab, field, [p_[k] for p_ in problems], ld="ldm" if field == "M" else None)
+        tab["m"], tab["v"] = self._own("_moments", [p_[5].numel() for p_ in problems], torch.float32, shapes=[p_[5].shape for p_ in problems],
+                                       planes=("m", "v"))
+        tab["best"] = self._own("best", [1] * n, torch.int32, unit=(3,), init=(-1, 0, 0), of=None)
+        tab["n_train"], tab["n_val"], tab["n_test"] = ([p_[k].shape[0] for p_ in problems] for k in (2, 3, 4))
+        tab["F"], tab["C"] = [p_[0].shape[1] for p_ in problems], classes
         self.max_f, self.max_c = int(tab["F"].max(initial=1)), int(tab["C"].max(initial=1))
         self.bytes_per_epoch = int(sum((p_[2].shape[0] + p_[3].shape[0] + p_[4].shape[0]) * p_[0].shape[1] * 4 for p_ in problems))
-        self.table = _upload(tab, n, dev)
-        self.best = self.best[:n]
+        self._close(tab)
+        self.best = self.best[:n]  # (no row where there is no problem)
 
     def launch(self, epochs, step0=0):
         """`epochs` more epochs of every problem; step0 = the Adam steps the table's moments have taken already"""
-        check(lib.wdg_head_train_batched_f32(_ptr(self.table), self.n_jobs, self.max_f, self.max_c, int(epochs), int(step0), self.lr,
-                                             self.weight_decay, self.betas[0], self.betas[1], self.eps, stream_handle()),
-              "wdg_head_train_batched_f32")
-
-    def reset(self):
-        """the moments and the running best back to their initial state (the weights are the caller's)"""
-        self._moments.zero_()
-        self.best.zero_()
-        self.best[:, 0] = -1
+        self._launch("wdg_head_train_batched_f32", self.max_f, self.max_c, int(epochs), int(step0), self.lr, self.weight_decay, self.betas[0],
+                     self.betas[1], self.eps)
 
 
 def dropout_constants(p):
@@ -148,7 +100,7 @@ def dropout_constants(p):
     return int(math.floor(p * 4294967296.0)), float(np.float32(1.0 / (1.0 - p)))
 
 
-class DropoutBatch:
+class DropoutBatch(JobTable):
     """Job table for wdg_relu_dropout_batched_f32 (csrc/dropout.hip): h <- dropout(relu(h)) IN PLACE for every entry, and its
     transpose into ht where one is given, in one launch.  The mask of element (r, c) is a function of (seed, the entry's stream,
     the step word, r, c) alone (include/wdg.h states it; tests/_dropout_ref.py restates it in numpy): nothing is stored, and the
@@ -163,50 +115,29 @@ class DropoutBatch:
         self.seed = int(seed)
         if not 0 <= self.seed < 1 << 32:
             raise ValueError(f"DropoutBatch: a seed of 32 bits expected, got {seed!r}")
-        dev = require_gpu()
-        self.keep = entries
-        n = self.n_jobs = len(entries)
+        self._open(entries)
         for h, ht, stream in entries:
             _check_matrix("DropoutBatch", "h", h)
             if ht is not None:
                 _check_matrix("DropoutBatch", "ht", ht, (h.shape[1], h.shape[0]))
             if not 0 <= int(stream) < 1 << 32:
                 raise ValueError(f"DropoutBatch: a stream of 32 bits expected, got {stream!r}")
-        col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
-        tab = np.zeros(n, _DROPOUT_JOB_DTYPE)
-        tab["h"], tab["ld"] = col(lambda e: e[0].data_ptr()), col(lambda e: _ld(e[0]))
-        tab["ht"] = col(lambda e: 0 if e[1] is None else e[1].data_ptr())
-        tab["ld_t"] = col(lambda e: 0 if e[1] is None else _ld(e[1]))
-        tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
-        tab["stream"] = col(lambda e: int(e[2]))
+        tab = self._records(_DROPOUT_JOB_DTYPE)
+        self._point(tab, "h", [e[0] for e in entries], ld="ld")
+        self._point(tab, "ht", [e[1] for e in entries], ld="ld_t")
+        tab["rows"], tab["cols"] = [e[0].shape[0] for e in entries], [e[0].shape[1] for e in entries]
+        tab["stream"] = [int(e[2]) for e in entries]
         self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
-        self.table = _upload(tab, n, dev)
+        self._close(tab)
 
     def launch(self, step):
         """step: a one-element int32 DEVICE tensor whose bits are the uint32 step - the kernel reads it when it runs, so a captured
         launch followed by a captured `step.add_(1)` draws a fresh mask on every replay"""
-        check(lib.wdg_relu_dropout_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.threshold, self.scale,
-                                               self.seed, _step_word("DropoutBatch.launch", step), stream_handle()), "wdg_relu_dropout_batched_f32")
+        self._launch("wdg_relu_dropout_batched_f32", self.max_rows, self.max_cols, self.threshold, self.scale, self.seed,
+                     _step_word("DropoutBatch.launch", step))
 
 
-def _views_may_overlap(a, b):
-    """whether two 2-D views with unit inner stride may share a byte.  Exact when their byte spans are disjoint and for views of
-    one row pitch (column slices of one wider matrix: they share nothing when their column ranges are disjoint inside the pitch);
-    other views whose spans intersect are reported as overlapping."""
-    def span(t):
-        r, c = t.shape
-        return t.data_ptr(), ((r - 1) * t.stride(0) + c) * 4 if r and c else 0
-    (pa, na), (pb, nb) = span(a), span(b)
-    if na == 0 or nb == 0 or pa + na <= pb or pb + nb <= pa:
-        return False
-    if a.shape[0] > 1 and b.shape[0] > 1 and a.stride(0) == b.stride(0):
-        pitch, wa, wb = a.stride(0) * 4, a.shape[1] * 4, b.shape[1] * 4
-        delta = (pb - pa) % pitch
-        return delta < wa or delta + wb > pitch
-    return True
-
-
-class _AcmMixTable:
+class _AcmMixTable(JobTable):
     """What the job tables of the two channel-mix kernels share: the activation flags, the key checks, the "all six gradient tensors or
     none" rule, the overlap check, the pointer / leading-dimension fill, aux and the partial sums of the parameter gradients (owned by
     the table, one slice per entry) and the two launches.  A subclass states its record type and entry points, its keys and, in
@@ -223,10 +154,7 @@ class _AcmMixTable:
 
     def __init__(self, entries, relu):
         name = type(self).__name__
-        self.keep = entries
-        n = self.n_jobs = len(entries)
-        if n > self.MAX_JOBS:
-            raise ValueError(f"{name}: {n} entries; one launch takes {self.MAX_JOBS}")
+        n = self._open(entries)
         flags = [bool(relu)] * n if np.ndim(relu) == 0 else [bool(f) for f in relu]
         if len(flags) != n:
             raise ValueError(f"{name}: one activation flag per entry")
@@ -262,41 +190,33 @@ class _AcmMixTable:
                     if (ka in self._OUTPUTS or kb in self._OUTPUTS) and _views_may_overlap(ta, tb):
                         raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
             shapes.append((fields, width, aux_shape, -(-rows // self.TILE) * part_len))
-        dev = require_gpu()  # (after the checks that need no device)
-        aux_off, part_off = _offsets((int(np.prod(s_[2])) for s_ in shapes), n), _offsets((s_[3] for s_ in shapes), n)
-        self.aux = torch.zeros(max(int(aux_off[-1]), 1), dtype=torch.float32, device=dev)
-        self.partials = torch.zeros(max(int(part_off[-1]), 1), dtype=torch.float32, device=dev) if self.has_backward else None
-        tab = np.zeros(n, self._DTYPE)
-        for i, e in enumerate(entries):
-            for k in self._MATS + self._VECS + ("out_t",):
-                if k in self._DTYPE.names:
-                    t = e.get(k)
-                    tab[k][i] = 0 if t is None else t.data_ptr()
-                    if "ld_" + k in self._DTYPE.names:
-                        tab["ld_" + k][i] = 0 if t is None else _ld(t)
-            for k, v in shapes[i][0].items():
-                tab[k][i] = v
-        tab["aux"] = self.aux.data_ptr() + 4 * aux_off[:-1]
+        tab = self._records(self._DTYPE)
+        for k in self._MATS + self._VECS + ("out_t",):
+            if k in self._DTYPE.names:
+                self._point(tab, k, [e.get(k) for e in entries], ld="ld_" + k if "ld_" + k in self._DTYPE.names else None)
+        for k in (shapes[0][0] if n else ()):
+            tab[k] = [s_[0][k] for s_ in shapes]
+        tab["aux"] = self._own("aux", [math.prod(s_[2]) for s_ in shapes], torch.float32, shapes=[s_[2] for s_ in shapes])
+        self.partials = None
         if self.has_backward:
-            tab["partials"] = self.partials.data_ptr() + 4 * part_off[:-1]
-        tab["flags"] = np.asarray(flags, np.int64)
+            tab["partials"] = self._own("partials", [s_[3] for s_ in shapes], torch.float32, of=None)
+        tab["flags"] = flags
         self.max_rows = int(tab["rows"].max(initial=0))
         self._widest = max((s_[1] for s_ in shapes), default=0)
-        self.aux_of = [self.aux[aux_off[i]:aux_off[i + 1]].view(shapes[i][2]) for i in range(n)]
-        self.table = _upload(tab, n, dev, self._CHECK_JOBS)
+        self._close(tab, self._CHECK_JOBS)
 
     def _check_alignment(self, k, t, rows):
         """(the kernel that takes any alignment)"""
 
     def launch(self):
         """out (and out_t, aux) of every entry"""
-        check(getattr(lib, self._FORWARD)(_ptr(self.table), self.n_jobs, self.max_rows, self._widest, stream_handle()), self._FORWARD)
+        self._launch(self._FORWARD, self.max_rows, self._widest)
 
     def launch_backward(self):
         """d_low, d_high, d_ident, d_att, d_wmix of every entry from d_out, the inputs and the aux of the last launch()"""
         if not self.has_backward and self.n_jobs:
             raise ValueError(f"{type(self).__name__}.launch_backward: the table was built without gradient tensors")
-        check(getattr(lib, self._BACKWARD)(_ptr(self.table), self.n_jobs, self.max_rows, self._widest, stream_handle()), self._BACKWARD)
+        self._launch(self._BACKWARD, self.max_rows, self._widest)
 
 
 class AcmMixBatch(_AcmMixTable):
@@ -422,24 +342,21 @@ def _stacked_logits_entry(table, e, keys, mats, own=lambda e: ()):
     return (n, r, c, cs) + settings
 
 
-class XentEvalBatch:
+class XentEvalBatch(StackedLogitsTable):
     """Job table for wdg_xent_eval_batched_f32 (csrc/xent_eval.hip): the tail of an epoch for models whose logits are stacked along
     the feature axis - replica r of an entry owns columns r cs .. r cs + C - 1 of its [n, R cs] logits.  launch(XENT_GRAD) writes the
     cross-entropy gradient of every replica's train rows (+0 elsewhere and in the padding columns); launch(XENT_EVAL) counts every
     replica's validation and test hits and keeps the best (include/wdg.h states both; tests/_xent_ref.py restates them in numpy).
     The table owns self.hits and self.best (one [R, 2] / [R, 3] int32 view per entry in hits_of / best_of)."""
 
-    MAX_C, MAX_JOBS = _STACKED_MAX_C, 65535
+    MAX_C = _STACKED_MAX_C
 
     def __init__(self, entries):
         """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), dlogits the same or
         None (then launch(XENT_GRAD) is refused), labels [n] int32 device, split [n, R] uint8 device contiguous (0 unused, 1 train,
         2 validation, 3 test), inv_n_train [R] fp32 device, C, cs (default: C).  R is split's second dimension.
         Raises ValueError for other shapes, dtypes or strides, C outside 1 .. 16, cs < C, R cs beyond a row, more than 65535 entries."""
-        self.keep = entries
-        n_jobs = self.n_jobs = len(entries)
-        if n_jobs > self.MAX_JOBS:
-            raise ValueError(f"XentEvalBatch: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
+        n_jobs = self._open(entries)
         self.has_grad = n_jobs > 0 and all(e.get("dlogits") is not None for e in entries)
         shapes = []
         for e in entries:
@@ -449,26 +366,12 @@ class XentEvalBatch:
             if not isinstance(inv, torch.Tensor) or inv.dtype != torch.float32 or not inv.is_cuda or not inv.is_contiguous() or \
                     tuple(inv.shape) != (shapes[-1][1],):
                 raise ValueError("XentEvalBatch: inv_n_train must be a contiguous [R] fp32 device vector")
-        dev = require_gpu()  # (after the checks that need no device)
-        off = _offsets((s_[1] for s_ in shapes), n_jobs)
-        total = max(int(off[-1]), 1)
-        self.hits = torch.zeros((total, 2), dtype=torch.int32, device=dev)
-        self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
-        self.best[:, 0] = -1
-        self.hits_of = [self.hits[off[i]:off[i + 1]] for i in range(n_jobs)]
-        self.best_of = [self.best[off[i]:off[i + 1]] for i in range(n_jobs)]
-        tab = np.zeros(n_jobs, _XENT_JOB_DTYPE)
-        for i, e in enumerate(entries):
-            for k in ("logits", "dlogits", "labels", "split", "inv_n_train"):
-                tab[k][i] = 0 if e.get(k) is None else e[k].data_ptr()
-            tab["ld_logits"][i] = _ld(e["logits"])
-            tab["ld_dlogits"][i] = 0 if e.get("dlogits") is None else _ld(e["dlogits"])
-        tab["hits"] = self.hits.data_ptr() + 8 * off[:-1]
-        tab["best"] = self.best.data_ptr() + 12 * off[:-1]
-        for k, name in enumerate(("n", "R", "C", "cs")):
-            tab[name] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
-        self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
-        self.table = _upload(tab, n_jobs, dev)
+        tab = self._stacked_records(_XENT_JOB_DTYPE, entries, shapes)
+        self._point(tab, "dlogits", [e.get("dlogits") for e in entries], ld="ld_dlogits")
+        self._point(tab, "inv_n_train", [e["inv_n_train"] for e in entries])
+        tab["hits"] = self._own_per_replica("hits", torch.int32, 2)
+        tab["best"] = self._own_per_replica("best", torch.int32, 3, init=(-1, 0, 0), state=True)
+        self._close(tab)
 
     def launch(self, flags, step=None):
         """flags: XENT_GRAD, XENT_EVAL or both.  step (needed with XENT_EVAL): a one-element int32 DEVICE tensor - the kernel reads it
@@ -479,14 +382,7 @@ class XentEvalBatch:
         if flags & XENT_GRAD and not self.has_grad and self.n_jobs:
             raise ValueError("XentEvalBatch.launch: the table was built without dlogits")
         word = _step_word("XentEvalBatch.launch", step) if flags & XENT_EVAL else _ptr(None)
-        check(lib.wdg_xent_eval_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, flags, word, stream_handle()),
-              "wdg_xent_eval_batched_f32")
-
-    def reset(self):
-        """the running best back to "none yet" (the counters are zero between calls)"""
-        self.hits.zero_()
-        self.best.zero_()
-        self.best[:, 0] = -1
+        self._launch("wdg_xent_eval_batched_f32", self.max_rows, self.max_cols, flags, word)
 
 
 def select_rule(where, select):
@@ -508,7 +404,7 @@ def whole_number(where, name, value, least=0):
     return int(value)
 
 
-class XentCurveBatch:
+class XentCurveBatch(StackedLogitsTable):
     """Job table for wdg_xent_curve_batched_f32 (csrc/xent_curve.hip): the evaluation of an epoch for models whose logits are stacked
     along the feature axis (XentEvalBatch's layout) WITH the losses - per replica the mean cross-entropy and the hits of its train,
     validation and test rows, a row of its learning curve, the model selection by one of SELECT_RULES and a patience counter, on the
@@ -517,7 +413,7 @@ class XentCurveBatch:
     first), state [R, 2] int32 (bad, stopped_at; 0, -1 at first), the optional curves and the kernel's work space - one view per entry
     in best_of, best_loss_of, state_of and curve_of (a (loss [curve_rows, R, 3] fp32, hits [curve_rows, R, 3] int32) pair, or None)."""
 
-    MAX_C, MAX_JOBS = _STACKED_MAX_C, 65535
+    MAX_C = _STACKED_MAX_C
 
     def __init__(self, entries):
         """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device,
@@ -527,10 +423,7 @@ class XentCurveBatch:
         Raises ValueError for other shapes, dtypes or strides, C outside 1 .. 16, cs < C, R cs beyond a row, an unknown rule, a negative
         or non-integer patience or curve_rows, more than 65535 entries."""
         name = "XentCurveBatch"
-        self.keep = entries
-        n_jobs = self.n_jobs = len(entries)
-        if n_jobs > self.MAX_JOBS:
-            raise ValueError(f"{name}: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
+        self._open(entries)
         shapes, parts = [], []
         settings = lambda e: (select_rule(name, e.get("select", "val_hits")), whole_number(name, "patience", e.get("patience", 0)),  # noqa: E731
                               whole_number(name, "curve_rows", e.get("curve_rows", 0)))
@@ -544,68 +437,30 @@ class XentCurveBatch:
                 raise ValueError(f"{name}: n_part must be [R = {r}, 3] row counts (train, validation, test) in 0..n")
             parts.append(part.astype(np.int32))
             shapes.append(shape)  # (n, R, C, cs, rule, patience, curve_rows)
-        dev = require_gpu()  # (after the checks that need no device)
-        off = _offsets((s_[1] for s_ in shapes), n_jobs)
-        coff = _offsets((s_[6] * s_[1] * 3 for s_ in shapes), n_jobs)
-        poff = _offsets((int(lib.wdg_xent_curve_partials_len(s_[0], s_[1])) for s_ in shapes), n_jobs)
-        total = max(int(off[-1]), 1)
-        self.n_part = torch.zeros((total, 3), dtype=torch.int32, device=dev)
-        if off[-1]:
-            self.n_part[:int(off[-1])].copy_(torch.from_numpy(np.concatenate(parts, 0)))
-        self.hits = torch.zeros((total, 3), dtype=torch.int32, device=dev)
-        self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
-        self.best_loss = torch.zeros((total, 3), dtype=torch.float32, device=dev)
-        self.state = torch.zeros((total, 2), dtype=torch.int32, device=dev)
-        self.curve_loss = torch.zeros(max(int(coff[-1]), 1), dtype=torch.float32, device=dev)
-        self.curve_hits = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int32, device=dev)
-        self.partials = torch.zeros(max(int(poff[-1]), 1), dtype=torch.float64, device=dev)
-        self.best_of = [self.best[off[i]:off[i + 1]] for i in range(n_jobs)]
-        self.best_loss_of = [self.best_loss[off[i]:off[i + 1]] for i in range(n_jobs)]
-        self.state_of = [self.state[off[i]:off[i + 1]] for i in range(n_jobs)]
-        self.curve_of = [(self.curve_loss[coff[i]:coff[i + 1]].view(s_[6], s_[1], 3), self.curve_hits[coff[i]:coff[i + 1]].view(s_[6], s_[1], 3))
-                         if s_[6] else None for i, s_ in enumerate(shapes)]
-        tab = np.zeros(n_jobs, _XENT_CURVE_JOB_DTYPE)
-        for i, e in enumerate(entries):
-            for k in ("logits", "labels", "split"):
-                tab[k][i] = e[k].data_ptr()
-            tab["ld_logits"][i] = max(_ld(e["logits"]), shapes[i][1] * shapes[i][3])
-            tab["curve_loss"][i] = self.curve_loss.data_ptr() + 4 * coff[i] if shapes[i][6] else 0
-            tab["curve_hits"][i] = self.curve_hits.data_ptr() + 4 * coff[i] if shapes[i][6] else 0
-        tab["n_part"] = self.n_part.data_ptr() + 12 * off[:-1]
-        tab["hits"] = self.hits.data_ptr() + 12 * off[:-1]
-        tab["best"] = self.best.data_ptr() + 12 * off[:-1]
-        tab["best_loss"] = self.best_loss.data_ptr() + 12 * off[:-1]
-        tab["state"] = self.state.data_ptr() + 8 * off[:-1]
-        tab["partials"] = self.partials.data_ptr() + 8 * poff[:-1]
-        for k, field in enumerate(("n", "R", "C", "cs", "rule", "patience", "curve_rows")):
-            tab[field] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
-        self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
-        self.table = _upload(tab, n_jobs, dev, "wdg_xent_curve_check_jobs")
-        self.reset()
+        tab = self._stacked_records(_XENT_CURVE_JOB_DTYPE, entries, shapes)
+        tab["n_part"] = self._own_per_replica("n_part", torch.int32, 3, of=None, reset=False)
+        if parts:
+            self.n_part[:int(self._replicas.sum())].copy_(torch.from_numpy(np.concatenate(parts, 0)))
+        tab["hits"] = self._own_per_replica("hits", torch.int32, 3, of=None)
+        tab["best"] = self._own_per_replica("best", torch.int32, 3, init=(-1, 0, 0), state=True)
+        tab["best_loss"] = self._own_per_replica("best_loss", torch.float32, 3, init=float("inf"), state=True)
+        tab["state"] = self._own_per_replica("state", torch.int32, 2, init=(0, -1), state=True)
+        tab["curve_loss"] = self._own_curve("curve_loss", torch.float32, [s_[6] for s_ in shapes], of="_curve_loss_of")
+        tab["curve_hits"] = self._own_curve("curve_hits", torch.int32, [s_[6] for s_ in shapes], of="_curve_hits_of")
+        self.curve_of = [None if loss is None else (loss, hits) for loss, hits in zip(self._curve_loss_of, self._curve_hits_of)]
+        tab["partials"] = self._own("partials", [int(lib.wdg_xent_curve_partials_len(s_[0], s_[1])) for s_ in shapes], torch.float64, of=None,
+                                    reset=False)  # (the kernel's work space)
+        for k, field in enumerate(("rule", "patience", "curve_rows"), 4):
+            tab[field] = [s_[k] for s_ in shapes]
+        self._close(tab, "wdg_xent_curve_check_jobs")
 
     def launch(self, step):
         """one evaluation of every entry.  step: a one-element int32 DEVICE tensor, read by the kernel when it runs - the step recorded in
         best and stopped_at and the row of the curve: a captured launch beside a captured `step.add_(1)` is right on every replay"""
-        check(lib.wdg_xent_curve_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, _step_word("XentCurveBatch.launch", step),
-                                             stream_handle()), "wdg_xent_curve_batched_f32")
-
-    def state_tensors(self):
-        """what a run snapshots and rewinds with its parameters: best, best_loss, state and the curves"""
-        return [self.best, self.best_loss, self.state, self.curve_loss, self.curve_hits]
-
-    def reset(self):
-        """the running best back to "none yet", the losses to +inf, nobody stopped, the curves to zero (the counters are zero between calls)"""
-        self.hits.zero_()
-        self.best.zero_()
-        self.best[:, 0] = -1
-        self.best_loss.fill_(float("inf"))
-        self.state.zero_()
-        self.state[:, 1] = -1
-        self.curve_loss.zero_()
-        self.curve_hits.zero_()
+        self._launch("wdg_xent_curve_batched_f32", self.max_rows, self.max_cols, _step_word("XentCurveBatch.launch", step))
 
 
-class AucBatch:
+class AucBatch(StackedLogitsTable):
     """Job table for wdg_auc_batched_i64 (csrc/auc.hip): the exact ROC-AUC of BINARY models whose logits are stacked along the feature
     axis (XentEvalBatch's layout; the score of a row is z_1 - z_0), per replica and part of its split, as two integers - u2 and pairs,
     AUC = u2 / (2 pairs) - with the selection on the validation AUC, a patience counter and a curve row, on the device (include/wdg.h
@@ -613,8 +468,6 @@ class AucBatch:
     [R, 3] int32 (XentEvalBatch.best's layout, (-1, 0, 0) at first: KeepBestBatch reads it), state [R, 2] int32 (bad, stopped_at; 0, -1
     at first), the optional curve and the kernel's work space - one view per entry in u2_of, pairs_of, best_u2_of, best_of, state_of
     and curve_of ([curve_rows, R, 3] int64, or None)."""
-
-    MAX_JOBS = 65535
 
     def __init__(self, entries):
         """entries: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device
@@ -624,10 +477,7 @@ class AucBatch:
         Raises ValueError for other shapes, dtypes or strides, cs < 2, R cs beyond a row, a select, patience, curve_rows or bins_log2
         outside the definition, more than 65535 entries."""
         name = "AucBatch"
-        self.keep = entries
-        n_jobs = self.n_jobs = len(entries)
-        if n_jobs > self.MAX_JOBS:
-            raise ValueError(f"{name}: {n_jobs} entries; one launch takes {self.MAX_JOBS}")
+        self._open(entries)
         shapes = []
         for e in entries:
             if int(e.get("cs", 2)) < 2:
@@ -639,41 +489,24 @@ class AucBatch:
             if shape[4] > 1 or shape[7] > 16:
                 raise ValueError(f"{name}: select {shape[4]} and bins_log2 {shape[7]}; 0 or 1 and 1 .. 16 expected")
             shapes.append(shape)  # (n, R, 2, cs, select, patience, curve_rows, bins_log2)
-        dev = require_gpu()  # (after the checks that need no device)
-        off = _offsets((s_[1] for s_ in shapes), n_jobs)
-        coff = _offsets((s_[6] * s_[1] * 3 for s_ in shapes), n_jobs)
-        woff = _offsets((int(lib.wdg_auc_workspace_bytes(s_[0], s_[1], s_[7])) // 8 + 1 for s_ in shapes), n_jobs)  # (in 8-byte words)
-        total = max(int(off[-1]), 1)
-        self.u2, self.pairs, self.best_u2 = (torch.zeros((total, 3), dtype=torch.int64, device=dev) for _ in range(3))
-        self.best = torch.zeros((total, 3), dtype=torch.int32, device=dev)
-        self.state = torch.zeros((total, 2), dtype=torch.int32, device=dev)
-        self.curve = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int64, device=dev)
-        self.work = torch.zeros(max(int(woff[-1]), 1), dtype=torch.int64, device=dev)  # (zero before the first call; every call leaves it so)
-        for field in ("u2", "pairs", "best_u2", "best", "state"):
-            setattr(self, field + "_of", [getattr(self, field)[off[i]:off[i + 1]] for i in range(n_jobs)])
-        self.curve_of = [self.curve[coff[i]:coff[i + 1]].view(s_[6], s_[1], 3) if s_[6] else None for i, s_ in enumerate(shapes)]
-        tab = np.zeros(n_jobs, _AUC_JOB_DTYPE)
-        for i, e in enumerate(entries):
-            for k in ("logits", "labels", "split"):
-                tab[k][i] = e[k].data_ptr()
-            tab["ld_logits"][i] = max(_ld(e["logits"]), shapes[i][1] * shapes[i][3])
-            tab["curve_u2"][i] = self.curve.data_ptr() + 8 * coff[i] if shapes[i][6] else 0
-        for field in ("u2", "pairs", "best_u2"):
-            tab[field] = getattr(self, field).data_ptr() + 24 * off[:-1]
-        tab["best"] = self.best.data_ptr() + 12 * off[:-1]
-        tab["state"] = self.state.data_ptr() + 8 * off[:-1]
-        tab["work"] = self.work.data_ptr() + 8 * woff[:-1]
-        for k, field in ((0, "n"), (1, "R"), (3, "cs"), (4, "select"), (5, "patience"), (6, "curve_rows"), (7, "bins_log2")):
-            tab[field] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
-        self.max_rows = int(tab["n"].max(initial=0))
-        self.table = _upload(tab, n_jobs, dev, "wdg_auc_check_jobs")
-        self.reset()
+        tab = self._stacked_records(_AUC_JOB_DTYPE, entries, shapes)
+        tab["u2"] = self._own_per_replica("u2", torch.int64, 3, reset=False)
+        tab["pairs"] = self._own_per_replica("pairs", torch.int64, 3, reset=False)
+        tab["best"] = self._own_per_replica("best", torch.int32, 3, init=(-1, 0, 0), state=True)
+        tab["best_u2"] = self._own_per_replica("best_u2", torch.int64, 3, init=-1, state=True)
+        tab["state"] = self._own_per_replica("state", torch.int32, 2, init=(0, -1), state=True)
+        tab["curve_u2"] = self._own_curve("curve", torch.int64, [s_[6] for s_ in shapes])
+        # the work space in 8-byte words (zero before the first call; every call leaves it so)
+        tab["work"] = self._own("work", [int(lib.wdg_auc_workspace_bytes(s_[0], s_[1], s_[7])) // 8 + 1 for s_ in shapes], torch.int64, of=None,
+                                reset=False)
+        for k, field in enumerate(("select", "patience", "curve_rows", "bins_log2"), 4):
+            tab[field] = [s_[k] for s_ in shapes]
+        self._close(tab, "wdg_auc_check_jobs")
 
     def launch(self, step):
         """the AUC integers of every entry, and - for the entries with select = 1 - their selection at this step.  step: a one-element
         int32 DEVICE tensor, read by the kernel when it runs: a captured launch beside a captured `step.add_(1)` is right on every replay"""
-        check(lib.wdg_auc_batched_i64(_ptr(self.table), self.n_jobs, self.max_rows, _step_word("AucBatch.launch", step), stream_handle()),
-              "wdg_auc_batched_i64")
+        self._launch("wdg_auc_batched_i64", self.max_rows, _step_word("AucBatch.launch", step))
 
     @staticmethod
     def _ratio(u2, pairs):
@@ -702,21 +535,8 @@ class AucBatch:
         cur = cur if rows is None else cur[:rows]
         return self._ratio(cur, self.pairs_of[entry][None].expand_as(cur))
 
-    def state_tensors(self):
-        """what a run snapshots and rewinds with its parameters: best, best_u2, state and the curve"""
-        return [self.best, self.best_u2, self.state, self.curve]
 
-    def reset(self):
-        """the running best back to "none yet", nobody stopped, the curve to zero (the work space is zero between calls)"""
-        self.best.zero_()
-        self.best[:, 0] = -1
-        self.best_u2.fill_(-1)
-        self.state.zero_()
-        self.state[:, 1] = -1
-        self.curve.zero_()
-
-
-class AdamBatch:
+class AdamBatch(JobTable):
     """Job table for wdg_adam_batched_f32 (csrc/adam.hip): the Adam step (the L2 term in the gradient, torch.optim.Adam's rule) of every
     parameter tensor of a stacked run in one launch, with the learning rate and the weight decay of every SEGMENT of a tensor - a
     replica's column or row block - in device memory (include/wdg.h states the arithmetic and the segment rule; tests/_adam_ref.py
@@ -735,21 +555,13 @@ class AdamBatch:
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         if not all(0.0 <= b < 1.0 for b in self.betas) or self.eps != self.eps:
             raise ValueError(f"AdamBatch: betas in [0, 1) and an eps that is a number expected, got {betas!r}, {eps!r}")
-        self.keep = entries
-        n = self.n_jobs = len(entries)
-        if n > self.MAX_JOBS:
-            raise ValueError(f"AdamBatch: {n} entries; one launch takes {self.MAX_JOBS}")
+        self._open(entries)
         hypers, self.segments = [], []
         for e in entries:
             if len(e) != 5:
                 raise ValueError("AdamBatch: an entry is (param, grad, seg_rows, seg_cols, hyper)")
             p, g, seg_rows, seg_cols, hyper = e
-            _check_matrix("AdamBatch", "param", p)
-            _check_matrix("AdamBatch", "grad", g)
-            if p.shape != g.shape or (p.shape[0] > 1 and _ld(p) != _ld(g)):
-                raise ValueError("AdamBatch: param and grad must have one shape and one leading dimension")
-            if _views_may_overlap(p, g):
-                raise ValueError("AdamBatch: param and grad overlap")
+            _check_pair("AdamBatch", "param", p, "grad", g, one_ld=True)
             rows, cols = p.shape
             seg_rows, seg_cols = int(seg_rows), int(seg_cols)
             if rows and cols and (seg_rows < 1 or seg_cols < 1):
@@ -760,35 +572,26 @@ class AdamBatch:
                 raise ValueError(f"AdamBatch: hyper must be [segments = {segs}, 2] (lr, weight_decay), got {tuple(h.shape)}")
             hypers.append(h)
             self.segments.append(segs)
-        dev = require_gpu()  # (after the checks that need no device)
+        tab = self._records(_ADAM_JOB_DTYPE)
+        params = [e[0] for e in entries]
+        self._point(tab, "p", params, ld="ld", cols=[p.shape[1] for p in params])
+        self._point(tab, "g", [e[1] for e in entries])
         # the moments: every tensor's block starts at a multiple of four floats (16-byte accesses where its width allows)
-        offs = _offsets((-(-e[0].numel() // 4) * 4 for e in entries), n)
-        total = max(int(offs[-1]), 4)
-        self.moments = torch.zeros((2, total), dtype=torch.float32, device=dev)
-        self.m = [self.moments[0, offs[i]:offs[i] + entries[i][0].numel()].view(entries[i][0].shape) for i in range(n)]
-        self.v = [self.moments[1, offs[i]:offs[i] + entries[i][0].numel()].view(entries[i][0].shape) for i in range(n)]
-        hoff = _offsets(self.segments, n)
-        self.hyper = torch.zeros((max(int(hoff[-1]), 1), 2), dtype=torch.float32, device=dev)
-        if hoff[-1]:
-            self.hyper[:int(hoff[-1])].copy_(torch.from_numpy(np.concatenate(hypers, 0)))
-        self.hyper_of = [self.hyper[hoff[i]:hoff[i + 1]] for i in range(n)]
-        col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
-        tab = np.zeros(n, _ADAM_JOB_DTYPE)
-        tab["p"], tab["g"], tab["ld"] = col(lambda e: e[0].data_ptr()), col(lambda e: e[1].data_ptr()), col(lambda e: max(_ld(e[0]), e[0].shape[1]))
-        tab["m"] = self.moments.data_ptr() + 4 * offs[:-1]
-        tab["v"] = self.moments.data_ptr() + 4 * (offs[:-1] + total)
-        tab["hyper"] = self.hyper.data_ptr() + 8 * hoff[:-1]
-        tab["ld_s"] = col(lambda e: e[0].shape[1])
-        tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
-        tab["seg_rows"], tab["seg_cols"] = col(lambda e: int(e[2])), col(lambda e: int(e[3]))
+        tab["m"], tab["v"] = self._own("moments", [p.numel() for p in params], torch.float32, shapes=[p.shape for p in params], align=4,
+                                       planes=("m", "v"), state=True)
+        tab["hyper"] = self._own("hyper", self.segments, torch.float32, unit=(2,), reset=False)
+        if hypers:
+            self.hyper[:sum(self.segments)].copy_(torch.from_numpy(np.concatenate(hypers, 0)))
+        tab["rows"], tab["cols"] = [p.shape[0] for p in params], [p.shape[1] for p in params]
+        tab["ld_s"] = tab["cols"]
+        tab["seg_rows"], tab["seg_cols"] = [int(e[2]) for e in entries], [int(e[3]) for e in entries]
         self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
-        self.table = _upload(tab, n, dev, "wdg_adam_check_jobs")
+        self._close(tab, "wdg_adam_check_jobs")
 
     def launch(self, step):
         """one Adam step, t = step + 1.  step: a one-element int32 DEVICE tensor, read by the kernel when it runs (the word DropoutBatch
         and XentEvalBatch read): a captured launch beside a captured `step.add_(1)` takes the right step on every replay"""
-        check(lib.wdg_adam_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, self.betas[0], self.betas[1], self.eps,
-                                       _step_word("AdamBatch.launch", step), stream_handle()), "wdg_adam_batched_f32")
+        self._launch("wdg_adam_batched_f32", self.max_rows, self.max_cols, self.betas[0], self.betas[1], self.eps, _step_word("AdamBatch.launch", step))
 
     def set_hyper(self, lr, weight_decay, entry=None):
         """rewrite the device table IN PLACE (the captured launch reads it on its next replay: a rate changes between replays without a
@@ -807,12 +610,8 @@ class AdamBatch:
             if segs:
                 self.hyper_of[i].copy_(torch.from_numpy(np.stack(cols, 1)))
 
-    def reset(self):
-        """the moments back to zero (the parameters and the step word are the caller's)"""
-        self.moments.zero_()
 
-
-class KeepBestBatch:
+class KeepBestBatch(JobTable):
     """Job table for wdg_keep_best_batched_f32 (csrc/keep_best.hip): of every tensor of the table, the segments of the replicas whose
     best epoch is the current step are copied from src to dst, in one launch (include/wdg.h states the rule; tests/_keep_ref.py
     restates it in numpy).  A job is one tensor, as in AdamBatch; nothing is owned by the table but its records."""
@@ -825,79 +624,54 @@ class KeepBestBatch:
         element (r, c) belongs to segment (r // seg_rows) * ceil(cols / seg_cols) + c // seg_cols and to replica segment % reps;
         best: [reps, 3] int32 device, contiguous (XentEvalBatch.best_of[i]).  Raises ValueError for other dtypes, shapes or strides,
         src and dst that overlap, seg_rows, seg_cols or reps below 1, more than 65535 entries."""
-        self.keep = entries
-        n = self.n_jobs = len(entries)
-        if n > self.MAX_JOBS:
-            raise ValueError(f"KeepBestBatch: {n} entries; one launch takes {self.MAX_JOBS}")
+        self._open(entries)
         for e in entries:
             if len(e) != 6:
                 raise ValueError("KeepBestBatch: an entry is (src, dst, seg_rows, seg_cols, reps, best)")
             src, dst, seg_rows, seg_cols, reps, best = e
-            _check_matrix("KeepBestBatch", "src", src)
-            _check_matrix("KeepBestBatch", "dst", dst)
-            if src.shape != dst.shape:
-                raise ValueError("KeepBestBatch: src and dst must have one shape")
-            if _views_may_overlap(src, dst):
-                raise ValueError("KeepBestBatch: src and dst overlap")
+            _check_pair("KeepBestBatch", "src", src, "dst", dst)
             if int(seg_rows) < 1 or int(seg_cols) < 1 or int(reps) < 1:
                 raise ValueError(f"KeepBestBatch: segments of {seg_rows} x {seg_cols} for {reps} replicas; at least 1 x 1 and one replica expected")
             if not isinstance(best, torch.Tensor) or best.dtype != torch.int32 or not best.is_cuda or not best.is_contiguous() or \
                     tuple(best.shape) != (int(reps), 3):
                 raise ValueError(f"KeepBestBatch: best must be a contiguous [reps = {int(reps)}, 3] int32 device tensor")
-        dev = require_gpu()  # (after the checks that need no device)
-        col = lambda f: np.fromiter((f(e) for e in entries), np.int64, n)  # noqa: E731
-        tab = np.zeros(n, _KEEP_JOB_DTYPE)
-        tab["src"], tab["dst"], tab["best"] = col(lambda e: e[0].data_ptr()), col(lambda e: e[1].data_ptr()), col(lambda e: e[5].data_ptr())
-        tab["ld_src"], tab["ld_dst"] = col(lambda e: max(_ld(e[0]), e[0].shape[1])), col(lambda e: max(_ld(e[1]), e[1].shape[1]))
-        tab["rows"], tab["cols"] = col(lambda e: e[0].shape[0]), col(lambda e: e[0].shape[1])
-        tab["seg_rows"], tab["seg_cols"], tab["reps"] = col(lambda e: int(e[2])), col(lambda e: int(e[3])), col(lambda e: int(e[4]))
+        tab = self._records(_KEEP_JOB_DTYPE)
+        cols = [e[0].shape[1] for e in entries]
+        self._point(tab, "src", [e[0] for e in entries], ld="ld_src", cols=cols)
+        self._point(tab, "dst", [e[1] for e in entries], ld="ld_dst", cols=cols)
+        self._point(tab, "best", [e[5] for e in entries])
+        tab["rows"], tab["cols"] = [e[0].shape[0] for e in entries], cols
+        tab["seg_rows"], tab["seg_cols"], tab["reps"] = ([int(e[k]) for e in entries] for k in (2, 3, 4))
         self.max_rows, self.max_cols = int(tab["rows"].max(initial=0)), int(tab["cols"].max(initial=0))
-        self.table = _upload(tab, n, dev, "wdg_keep_best_check_jobs")
+        self._close(tab, "wdg_keep_best_check_jobs")
 
     def launch(self, step):
         """step: a one-element int32 DEVICE tensor, read by the kernel when it runs - the word the XentEvalBatch.launch(XENT_EVAL, step)
         before this launch recorded, not yet advanced"""
-        check(lib.wdg_keep_best_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, _step_word("KeepBestBatch.launch", step),
-                                            stream_handle()), "wdg_keep_best_batched_f32")
+        self._launch("wdg_keep_best_batched_f32", self.max_rows, self.max_cols, _step_word("KeepBestBatch.launch", step))
 
 
-class ConfusionBatch:
+class ConfusionBatch(StackedLogitsTable):
     """Job table for wdg_confusion_batched_i32 (csrc/confusion.hip): the prediction of every (row, replica) of stacked logits - the first
     maximum, XentEvalBatch's rule; 255 for a row with a NaN - and, per replica and split part, the counts of (true class, predicted
     class or none) (include/wdg.h states both; tests/_confusion_ref.py restates them in numpy).  The table owns the counts
     (counts_of[i]: int32 [R, 3, C, C + 1] - train, validation, test) and the predictions (pred_of[i]: uint8 [n, R])."""
 
-    MAX_C, MAX_JOBS = _STACKED_MAX_C, 65535
+    MAX_C, _JOBS = _STACKED_MAX_C, "jobs"
 
     def __init__(self, jobs):
         """jobs: list of dicts - logits [n, >= R cs] fp32 device (unit inner stride, any leading dimension), labels [n] int32 device,
         split [n, R] uint8 device contiguous (0 unused, 1 train, 2 validation, 3 test), C, cs (default: C).
         Raises ValueError for other shapes, dtypes or strides, C outside 1 .. 16, cs < C, R cs beyond a row, more than 65535 jobs."""
-        self.keep = jobs
-        n_jobs = self.n_jobs = len(jobs)
-        if n_jobs > self.MAX_JOBS:
-            raise ValueError(f"ConfusionBatch: {n_jobs} jobs; one launch takes {self.MAX_JOBS}")
+        self._open(jobs)
         shapes = [_stacked_logits_entry("ConfusionBatch", e, ("logits", "labels", "split", "C", "cs"), ("logits",)) for e in jobs]
-        dev = require_gpu()  # (after the checks that need no device)
-        coff, poff = _offsets((r * 3 * c * (c + 1) for _, r, c, _ in shapes), n_jobs), _offsets((n * r for n, r, _, _ in shapes), n_jobs)
-        self.counts = torch.zeros(max(int(coff[-1]), 1), dtype=torch.int32, device=dev)
-        self.pred = torch.zeros(max(int(poff[-1]), 1), dtype=torch.uint8, device=dev)
-        self.counts_of = [self.counts[coff[i]:coff[i + 1]].view(r, 3, c, c + 1) for i, (_, r, c, _) in enumerate(shapes)]
-        self.pred_of = [self.pred[poff[i]:poff[i + 1]].view(n, r) for i, (n, r, _, _) in enumerate(shapes)]
-        tab = np.zeros(n_jobs, _CONFUSION_JOB_DTYPE)
-        for i, e in enumerate(jobs):
-            for k in ("logits", "labels", "split"):
-                tab[k][i] = e[k].data_ptr()
-            tab["ld_logits"][i] = max(_ld(e["logits"]), shapes[i][1] * shapes[i][3])
-        tab["counts"] = self.counts.data_ptr() + 4 * coff[:-1]
-        tab["pred"] = self.pred.data_ptr() + poff[:-1]
-        for k, name in enumerate(("n", "R", "C", "cs")):
-            tab[name] = np.fromiter((s_[k] for s_ in shapes), np.int64, n_jobs)
-        self.max_rows, self.max_cols = int(tab["n"].max(initial=0)), int(tab["C"].max(initial=0))
-        self.table = _upload(tab, n_jobs, dev, "wdg_confusion_check_jobs")
+        tab = self._stacked_records(_CONFUSION_JOB_DTYPE, jobs, shapes)
+        tab["counts"] = self._own("counts", [r * 3 * c * (c + 1) for _, r, c, _ in shapes], torch.int32, shapes=[(r, 3, c, c + 1) for _, r, c, _ in shapes])
+        tab["pred"] = self._own("pred", [n * r for n, r, _, _ in shapes], torch.uint8, shapes=[(n, r) for n, r, _, _ in shapes])
+        self._close(tab, "wdg_confusion_check_jobs")
 
     def launch(self, zero=True):
         """the predictions and the counts of every job; zero=True (the default) clears the table's counts first - the kernel ADDS"""
         if zero:
             self.counts.zero_()
-        check(lib.wdg_confusion_batched_i32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_cols, stream_handle()), "wdg_confusion_batched_i32")
+        self._launch("wdg_confusion_batched_i32", self.max_rows, self.max_cols)
