@@ -1635,6 +1635,87 @@ int wdg_sparse_dense_check_jobs(const wdg_sparse_dense_job *jobs_host, int32_t n
 int wdg_feat_scaled_values_f32(const int32_t *rowptr, const int32_t *col, const float *val, int32_t n_rows, int32_t n_feat, int normalise,
                                const int32_t *t_src, int32_t nnz, float *val_scaled, float *t_val_scaled, wdg_stream_t stream);
 
+/*
+ * Graph attention for many graphs in one launch, and its backward pass: a weight per stored entry, learnt, where every other
+ * aggregation of this library takes weights fixed before the launch.  The reference ships no model code: the layer is DEFINED here
+ *  and is not claimed to reproduce an upstream table.
+ * replaces: the fixed weights of normalize_tensor, utils/util_funcs.py:365-381, in the aggregation, for the attention baseline that
+ *           stands beside the GCN / SGC tables of gnns_on_syn.py:1-154 (models that live upstream of the reference).
+ * A job: a square CSR PATTERN of n rows - rowptr int32 [n + 1], col int32 [nnz], columns strictly ascending inside a row; stored
+ * values and scales are ignored -, heads in 1..8 of width w >= 1 with heads w <= 256, H [n, heads w], S [n, 2 heads] (S[:, h] the
+ * row's own score, S[:, heads + h] its score as a neighbour: the caller's product S = H blockdiag(a_dst, a_src)), slope >= 0.
+ * The definition, for row i, head h and the row's stored entries p in ascending order, j = col[p]:
+ *   pre_p = S[i, h] + S[j, heads + h]          e_p = pre_p > 0 ? pre_p : slope * pre_p
+ *   m = max_p e_p          q_p = expf(e_p - m)          Z = sum_p q_p          alpha_p = q_p / Z   (a correctly rounded division)
+ *   out[i, h w + k] = sum_p alpha_p H[j, h w + k]     ONE fmaf chain from +0 over ascending p: acc = fmaf(alpha_p, H[j, .], acc)
+ *   alpha[p, h] = alpha_p                              [nnz, heads] contiguous: kept for the backward pass and for the caller
+ * The backward pass, g = d_out[i, :]:
+ *   dalpha_p = sum_k g[h w + k] H[j, h w + k]          ONE fmaf chain from +0 over ascending k
+ *   c = sum_p alpha_p dalpha_p                         t_p = dalpha_p - c     u_p = alpha_p * t_p
+ *   dpre_p = u_p * (pre_p > 0 ? 1 : slope)  -> d_pre[p, h] (workspace [nnz, heads])          d_S[i, h] = sum_p dpre_p
+ * and, over the TRANSPOSED pattern (t_rowptr, t_col; entry q of row j has source row i = t_col[q] and is forward entry p = t_pos[q]):
+ *   d_H[j, h w + k] = sum_q alpha[p, h] d_out[i, h w + k]     ONE fmaf chain from +0 over ascending q
+ *   d_S[j, heads + h] = sum_q d_pre[p, h]
+ * The order of the other sums is fixed too.  A sum over a row's entries - Z, c, d_S[i, h], d_S[j, heads + h] - numbers the entries
+ * 0, 1, ... from the row's first: lane l of 64 adds the entries l, l + 64, l + 128, ... in ascending order from +0 (c: acc =
+ * fmaf(alpha_p, dalpha_p, acc); the others: acc = acc + term), and the 64 lane sums are then added by a butterfly over lane distances
+ * 32, 16, 8, 4, 2, 1, each step v = v + v[lane ^ distance].  The maximum is taken with fmaxf - it skips a NaN - and its value does not
+ * depend on an order.  There are no floating-point atomics.  csrc/gat.hip is compiled with contraction off and writes every fmaf out.
+ * An empty row writes out = +0 (and +0 gradients) and no alpha.  A NaN stays a NaN: one in row j of H reaches out[i, :] of exactly
+ * the rows i that store j, one in d_out[i, :] reaches d_H[j, :] of exactly the columns j that row i stores.  An element depends on
+ * its row, or its transposed row, alone, and a job on the job alone: a job answers in a table what it answers alone, and head h of
+ * a job has the bits of a one-head job on that head's column slices (every matrix has its own leading dimension: slices are passed
+ * in place).  Outputs must not overlap inputs or each other.  16-byte accesses where a matrix's pointer and leading dimension allow,
+ * scalar ones elsewhere: the same values.
+ * Guards: an entry whose column lies outside [0, n) - or whose t_pos lies outside [0, nnz) - is skipped, never read through; a row
+ * whose extent lies outside [0, nnz] is left untouched, and so is a job outside the limits.
+ * max_rows: the table's largest n (rows beyond it are not worked on).  wdg_gat_backward_batched_f32 is two launches: the row pass,
+ * then the pass over the transposed pattern; it reads the alpha of the last forward launch.
+ * Refused before any launch (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs (a job per grid
+ * z).  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is launched.  The table lives in device memory: what is wrong inside a job - heads
+ * outside 1..8, w < 1, heads w > 256, a slope that is negative or a NaN, flags other than 0, a negative n or nnz, a NULL rowptr, H, S or
+ * out, a NULL col or alpha with nnz > 0, a leading dimension below the row, the backward pointers (d_out, d_H, d_S, t_rowptr; d_pre,
+ * t_col, t_pos with nnz > 0) given in part - is refused by wdg_gat_check_jobs on the HOST copy of the table (train.GatBatch calls it
+ * before it uploads).  A job with n == 0 is skipped.
+ */
+#define WDG_GAT_MAX_HEADS 8
+#define WDG_GAT_MAX_COLS 256
+typedef struct wdg_gat_job {
+    const int32_t *rowptr;    /* [n + 1] */
+    const int32_t *col;       /* [nnz], strictly ascending inside a row */
+    const int32_t *t_rowptr;  /* [n + 1]: the transposed pattern (backward), or NULL */
+    const int32_t *t_col;     /* [nnz] */
+    const int32_t *t_pos;     /* [nnz]: the forward entry of every transposed entry (wdg_csr_transpose_positions) */
+    const float *H;           /* [n, heads w] */
+    const float *S;           /* [n, 2 heads] */
+    float *out;               /* forward out [n, heads w] */
+    float *alpha;             /* [nnz, heads]: forward out, backward in */
+    const float *d_out;       /* backward in [n, heads w] */
+    float *d_H;               /* backward out [n, heads w] */
+    float *d_S;               /* backward out [n, 2 heads] */
+    float *d_pre;             /* backward workspace [nnz, heads] */
+    int64_t ld_h, ld_s, ld_out, ld_d_out, ld_d_h, ld_d_s;
+    int32_t n, heads, w, flags; /* flags: 0 (none is defined) */
+    float slope;
+    int32_t nnz;              /* rowptr[n]: the extent of col, alpha and d_pre */
+} wdg_gat_job;
+int wdg_gat_forward_batched_f32(const wdg_gat_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+/* replaces: nothing of its own - the backward pass of the layer above (utils/util_funcs.py:365-381) */
+int wdg_gat_backward_batched_f32(const wdg_gat_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the layer above (utils/util_funcs.py:365-381), on the host's table */
+int wdg_gat_check_jobs(const wdg_gat_job *jobs_host, int32_t n_jobs);
+/*
+ * t_pos of wdg_gat_job: for every entry q of the transposed CSR (row j, t_col[q] = i) the position p of the forward entry (i, j),
+ * found by binary search in forward row i; -1 where there is none.
+ * replaces: nothing of the reference - torch autograd transposes the dense A_hat of utils/util_funcs.py:365-381 by itself.
+ * bad_dev: one int32 word in device memory, cleared and then COUNTED into: the transposed entries without a match, and the rows
+ * of either pattern whose columns are not strictly ascending inside [0, n) or whose extent is not inside the pattern.  A non-zero
+ * count marks a pattern with duplicates or unsorted rows, or two patterns that are not each other's transpose (together with equal
+ * entry counts, zero proves the bijection).  Refused before any HIP call: a negative n, a NULL count word, NULL row pointers.
+ */
+int wdg_csr_transpose_positions(const int32_t *rowptr, const int32_t *col, const int32_t *t_rowptr, const int32_t *t_col, int32_t n,
+                                int32_t *t_pos, int32_t *bad_dev, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,10 @@ SIGNATURES = {
     "wdg_synth_classes_batched": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "wdg_gauss_features_batched_f32": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "wdg_qda_errors_batched_i32": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "wdg_gat_forward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_gat_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_gat_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
@@ -386,6 +390,13 @@ class SparseDenseJob(ctypes.Structure):
     """mirror of `wdg_sparse_dense_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "val", "order", "W", "Y")] + [("ldw", c_int64), ("ldy", c_int64)] + \
                [(name, c_int32) for name in ("n_rows", "n_cols", "m", "reserved")]
+
+
+class GatJob(ctypes.Structure):
+    """mirror of `wdg_gat_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "t_rowptr", "t_col", "t_pos", "H", "S", "out", "alpha", "d_out", "d_H", "d_S", "d_pre")] + \
+               [(name, c_int64) for name in ("ld_h", "ld_s", "ld_out", "ld_d_out", "ld_d_h", "ld_d_s")] + \
+               [(name, c_int32) for name in ("n", "heads", "w", "flags")] + [("slope", ctypes.c_float), ("nnz", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

@@ -242,6 +242,26 @@ class CsrGraph:
         g.n_cols = self.n_rows
         return g
 
+    def transpose_positions(self, g_t):
+        """-> t_pos int32 [nnz]: for every entry q of g_t = self.transpose() the position of the matching entry of self
+        (wdg_csr_transpose_positions: binary search in the forward row).  ValueError when the kernel's count word is not zero: it counts
+        what marks a pattern the attention kernels refuse - transposed entries without a match, rows of either pattern whose columns
+        are not strictly ascending (duplicates, unsorted rows).  One host read-back (the count): a one-time plan, not inside a capture."""
+        if (g_t.n_rows, g_t.n_cols, g_t.nnz) != (self.n_cols, self.n_rows, self.nnz) or self.n_rows != self.n_cols:
+            raise ValueError(f"transpose_positions: a square pattern and its transpose expected, got {self.n_rows} x {self.n_cols} with {self.nnz} "
+                             f"entries and {g_t.n_rows} x {g_t.n_cols} with {g_t.nnz}")
+        dev = self.device
+        t_pos = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        nz = self.nnz > 0
+        check(lib.wdg_csr_transpose_positions(_ptr(self.rowptr), _ptr(self.col if nz else None), _ptr(g_t.rowptr), _ptr(g_t.col if nz else None), self.n_rows,
+                                              _ptr(t_pos if nz else None), _ptr(bad), stream_handle()), "wdg_csr_transpose_positions")
+        count = int(bad.item())
+        if count:
+            raise ValueError(f"transpose_positions: {count} entries without a match or rows whose columns are not strictly ascending - a pattern "
+                             "with duplicates or unsorted rows, or not the transpose of this graph")
+        return t_pos
+
     def to_torch_sparse(self):
         idx = torch.stack([self.row_indices(), self.col.to(torch.int64)])
         val = self.val if self.val is not None else torch.ones(self.nnz, device=self.device)

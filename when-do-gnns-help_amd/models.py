@@ -17,6 +17,10 @@ in the middle of the homophily range: every layer mixes a low-pass channel A_hat
 the g_high its loader returns, utils/util_funcs.py:198-204 - and an identity channel M W_I with per-node weights.  The mix and its
 backward pass run on csrc/acm_mix.hip; the layer is defined by this project (the reference names "mf-" models in
 gnns_on_syn.py:58-104 and gnns_on_syn.py:159-206 but ships none) and is not claimed to reproduce those tables.
+
+GAT-1 / GAT-2 (`GAT1`, `GAT2`) replace the fixed weights of the aggregation (normalize_tensor, utils/util_funcs.py:365-381)
+by a softmax weight per stored entry: out_i = sum_j alpha_ij H_j on csrc/gat.hip, forward and backward; the scores are a product on
+csrc/gemm.hip.  Defined by this project as well, as the attention baseline beside the tables of gnns_on_syn.py:1-154.
 """
 import torch
 
@@ -35,9 +39,21 @@ class NormAdj:
         self.graph, self.graph_t = g, g.transpose()
         self.row_scale, self.col_scale = d, (d if symmetric else None)
         self.n = g.n_rows
+        self._attention = None
 
     def matmul(self, x):
         return _Aggregate.apply(x, self)
+
+    def attention_plan(self):
+        """what the attention kernels need of the pattern, built on first use and kept: dict(graph, graph_t, t_pos) - t_pos ties
+        every entry of the transposed CSR to its forward entry (CsrGraph.transpose_positions).  ValueError for a graph that is not
+        square, or whose pattern the kernel's count word refuses (duplicates, unsorted rows)."""
+        if self._attention is None:
+            g, gt = self.graph, self.graph_t
+            if g.n_rows != g.n_cols:
+                raise ValueError(f"attention needs a square pattern, got {g.n_rows} x {g.n_cols}")
+            self._attention = dict(graph=g, graph_t=gt, t_pos=g.transpose_positions(gt))
+        return self._attention
 
 
 class _Aggregate(torch.autograd.Function):
@@ -333,6 +349,134 @@ class ACMGCN2(torch.nn.Module):
         else:
             h = torch.nn.functional.dropout(torch.relu(o), self.dropout, self.training)
         return self._layer(adj, h, self.w1, self.att1, self.wmix1, self.nclass, self._mix1)
+
+
+class _GatLayer:
+    """One attention layer Att_heads(H; a) on a one-job ops.GatBatch: work buffers and the table over them per (graph, rows, heads, w),
+    built on first use - before any capture - so that a captured forward / backward addresses the same memory on every replay.
+    As for _AcmMixer the buffers (alpha among them) hold ONE forward pass, the latest: `version` counts forward passes on the host, and
+    an eager backward pass that finds another forward pass in between runs its own again from the saved operands.  Inside a captured
+    region a backward pass must follow its own forward pass there (models.train_eval_graphed)."""
+
+    def __init__(self, heads, slope):
+        self.heads, self.slope = int(heads), float(slope)
+        self._tables, self._index = {}, None
+        self.version = 0
+
+    def table(self, adj, rows, cols, dev):
+        plan = adj.attention_plan()
+        key = (id(plan), rows, cols)
+        if key not in self._tables:
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            b = dict(h=z(rows, cols), s=z(rows, 2 * self.heads), out=z(rows, cols), d_out=z(rows, cols), d_h=z(rows, cols), d_s=z(rows, 2 * self.heads))
+            self._tables[key] = (b, ops.GatBatch([dict(plan, heads=self.heads, **b)], self.slope), plan)  # (plan: kept alive with its id)
+        return self._tables[key][:2]
+
+    def run(self, h, s, adj):
+        b, table = self.table(adj, h.shape[0], h.shape[1], h.device)
+        b["h"].copy_(h)
+        b["s"].copy_(s)
+        table.launch()
+        self.version += 1
+        return b, table
+
+    def operand(self, att):
+        """blockdiag(a_dst, a_src) [heads w, 2 heads] of att [2, heads, w]: element (h w + k, h) = a_dst[h, k], (h w + k, heads + h) =
+        a_src[h, k] - an index_put into zeros, so the gradient of the operand reaches att by the same indices"""
+        _, heads, w = att.shape
+        if self._index is None or self._index[0].device != att.device:
+            rows = torch.arange(heads * w, device=att.device).repeat(2)
+            cols = torch.arange(2 * heads, device=att.device).repeat_interleave(w)
+            self._index = (rows, cols)
+        return torch.zeros((heads * w, 2 * heads), dtype=att.dtype, device=att.device).index_put(self._index, att.reshape(-1))
+
+    def __call__(self, adj, h, att):
+        """h [n, heads w] -> Att(h; att) [n, heads w]; the scores are a product on the GEMM: autograd carries d_S back into h and att"""
+        s = _Linear.apply(h, self.operand(att), False)
+        return _GatAggregate.apply(h, s, adj, self)
+
+    def alpha(self, adj, rows, cols, dev):
+        """[nnz, heads]: the attention weights of the latest forward pass on this graph, in the order of adj.graph's entries"""
+        return self.table(adj, rows, cols, dev)[1].alpha_of[0].clone()
+
+
+class _GatAggregate(torch.autograd.Function):
+    """out_i = sum_j alpha_ij H_j (include/wdg.h: wdg_gat_forward_batched_f32) and its backward pass, both on csrc/gat.hip"""
+
+    @staticmethod
+    def forward(ctx, h, s, adj, layer):
+        b, _ = layer.run(h, s, adj)
+        ctx.save_for_backward(h, s)
+        ctx.adj, ctx.layer, ctx.version = adj, layer, layer.version
+        return b["out"].clone()
+
+    @staticmethod
+    def backward(ctx, gy):
+        layer = ctx.layer
+        if layer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
+            b, table = layer.run(*ctx.saved_tensors, ctx.adj)
+        else:
+            b, table = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
+        b["d_out"].copy_(gy)
+        table.launch_backward()
+        return b["d_h"].clone(), b["d_s"].clone(), None, None
+
+
+def _gat_parameters(nfeat, heads, w):
+    """the parameters of one attention layer in the documented draw order: W (xavier_uniform, [nfeat, heads w]), then a_dst and a_src
+    ([heads, w] each, uniform in +- 1 / sqrt(w)) -> (weight, att [2, heads, w] = [a_dst, a_src])"""
+    if not 1 <= heads <= ops.GatBatch.MAX_HEADS or w < 1 or heads * w > ops.GatBatch.MAX_COLS:
+        raise ValueError(f"an attention layer of {heads} heads of width {w}: the kernel holds 1..{ops.GatBatch.MAX_HEADS} heads and "
+                         f"heads * w <= {ops.GatBatch.MAX_COLS}")
+    weight = torch.nn.init.xavier_uniform_(torch.empty(nfeat, heads * w))
+    att = (torch.rand(2, heads, w) * 2 - 1) / w ** 0.5
+    return torch.nn.Parameter(weight), torch.nn.Parameter(att)
+
+
+class GAT1(torch.nn.Module):
+    """GAT-1: logits = Att_1(X W; a) - one attention layer of one head of width C, bias-free, on the pattern of
+    NormAdj(adj, add_self_loops=True) (its scales are not used: the weights are the softmax's); DESIGN 4.25."""
+
+    def __init__(self, nfeat, nclass, slope=0.2):
+        super().__init__()
+        self.weight, self.att = _gat_parameters(nfeat, 1, nclass)
+        self._att = _GatLayer(1, slope)
+
+    def forward(self, adj, x):
+        return self._att(adj, _Linear.apply(x, self.weight, False), self.att)
+
+
+class GAT2(torch.nn.Module):
+    """GAT-2: hidden = relu_dropout(Att_heads(X W0; a0)) with heads * nhid columns, logits = Att_1(hidden W1; a1); bias-free, feature
+    dropout only (GCN2's two routes: dropout_rng None - torch's - or a DeviceDropout); no dropout on alpha.  DESIGN 4.25."""
+
+    def __init__(self, nfeat, nclass, heads=8, nhid=8, dropout=0.5, dropout_rng=None, slope=0.2):
+        super().__init__()
+        self.w0, self.att0 = _gat_parameters(nfeat, heads, nhid)
+        self.w1, self.att1 = _gat_parameters(heads * nhid, 1, nclass)
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._att0, self._att1 = _GatLayer(heads, slope), _GatLayer(1, slope)
+
+    def forward(self, adj, x):
+        o = self._att0(adj, _Linear.apply(x, self.w0, False), self.att0)
+        if self.dropout_rng is not None:
+            h = self.dropout_rng.relu_dropout(o, self.dropout, self.training)
+        else:
+            h = torch.nn.functional.dropout(torch.relu(o), self.dropout, self.training)
+        return self._att1(adj, _Linear.apply(h, self.w1, False), self.att1)
+
+    def attention(self, adj, x):
+        """-> (alpha of layer 1 [nnz, heads], alpha of layer 2 [nnz, 1]) of an evaluation forward pass on (adj, x), run here (the
+        model's mode is put back): the weights of adj.graph's stored entries, in their order"""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                self(adj, x)
+        finally:
+            self.train(was_training)
+        n, dev = x.shape[0], self.w0.device
+        return self._att0.alpha(adj, n, self.w0.shape[1], dev), self._att1.alpha(adj, n, self.w1.shape[1], dev)
 
 
 def graphed_inference(model, adj, x, **forward_kwargs):

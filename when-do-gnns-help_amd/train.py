@@ -5,6 +5,7 @@
 - csrc/acm_mix.hip: the channel mix of many ACM layers (ACM-SGC-1, ACM-GCN-2: a low-pass, a high-pass and an identity channel
   weighted per node) with its backward pass
 - csrc/acm_mix_packed.hip: the same for the stacked class-width layers of acm_split_train, several replicas per 16 lanes
+- csrc/gat.hip: the graph-attention layer of many graphs (GAT-1, GAT-2: a softmax weight per stored entry) with its backward pass
 - csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
 - csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
@@ -29,6 +30,7 @@ _HEAD_JOB_DTYPE = np.dtype(_lib.HeadTrainJob)
 _DROPOUT_JOB_DTYPE = np.dtype(_lib.DropoutJob)
 _ACM_JOB_DTYPE = np.dtype(_lib.AcmMixJob)
 _ACM_PACKED_JOB_DTYPE = np.dtype(_lib.AcmPackedJob)
+_GAT_JOB_DTYPE = np.dtype(_lib.GatJob)
 _XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
 _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
 _KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
@@ -290,6 +292,112 @@ class AcmMixPackedBatch(_AcmMixTable):
             raise ValueError(f"AcmMixPackedBatch: {k} must start at a 16-byte boundary and have a leading dimension that is a multiple of 4")
         if k in ("att", "d_att") and t.data_ptr() % 16:
             raise ValueError(f"AcmMixPackedBatch: {k} must start at a 16-byte boundary")
+
+
+class GatBatch(JobTable):
+    """Job table for wdg_gat_forward_batched_f32 / wdg_gat_backward_batched_f32 (csrc/gat.hip): one graph-attention layer per entry -
+    out[i, h w + k] = sum_p alpha[p, h] H[col[p], h w + k] over row i's stored entries, alpha the softmax over the row of
+    leaky_relu(S[i, h] + S[col[p], heads + h]) (include/wdg.h states it and every sum's order; tests/_gat_ref.py restates it in numpy) -
+    and its backward pass, a whole table per launch.  The table owns alpha (alpha_of[i]: [nnz, heads], written forward, read backward
+    and by the caller) and the backward pass's workspace d_pre."""
+
+    MAX_JOBS, MAX_HEADS, MAX_COLS = 65535, 8, 256
+    _KEYS = ("graph", "graph_t", "t_pos", "h", "s", "out", "heads", "d_out", "d_h", "d_s")
+    _BACKWARD = ("graph_t", "t_pos", "d_out", "d_h", "d_s")
+
+    def __init__(self, entries, slope=0.2):
+        """entries: list of dicts - graph: a square CsrGraph (its pattern is used; columns strictly ascending inside a row), heads (int,
+           default 1), h [n, heads w] and s [n, 2 heads] fp32 (unit inner stride, any leading dimension: column slices of a wider
+           matrix are fine), out [n, heads w];
+           and, for launch_backward(): graph_t (graph.transpose()), t_pos (graph.transpose_positions(graph_t): int32 [nnz]), d_out and
+           d_h [n, heads w], d_s [n, 2 heads] - all five or none (models.NormAdj.attention_plan() has the first three).
+           slope: the negative slope of the leaky ReLU, for every entry (one number, or one per entry), >= 0.
+        Raises ValueError for heads outside 1..8, heads w outside 1..256, other dtypes, shapes or strides, a graph that is not square,
+        a negative or NaN slope, more than 65535 entries, an output that overlaps an input or another output of its entry."""
+        name = "GatBatch"
+        n_jobs = self._open(entries)
+        slopes = [float(slope)] * n_jobs if np.ndim(slope) == 0 else [float(v) for v in slope]
+        if len(slopes) != n_jobs:
+            raise ValueError(f"{name}: one slope per entry")
+        if not all(v >= 0.0 for v in slopes):  # (a NaN fails the comparison)
+            raise ValueError(f"{name}: a slope >= 0 expected, got {slope!r}")
+        self.slopes, self.has_backward = slopes, n_jobs > 0
+        shapes = []
+        for e in entries:
+            unknown = set(e) - set(self._KEYS)
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            g, heads = e.get("graph"), int(e.get("heads", 1))
+            if g is None or any(e.get(k) is None for k in ("h", "s", "out")):
+                raise ValueError(f"{name}: graph, h, s and out are required")
+            if g.n_rows != g.n_cols:
+                raise ValueError(f"{name}: a square pattern expected, got {g.n_rows} x {g.n_cols}")
+            if not 1 <= heads <= self.MAX_HEADS:
+                raise ValueError(f"{name}: {heads} heads; the kernel holds 1..{self.MAX_HEADS}")
+            cols = e["h"].shape[1] if isinstance(e["h"], torch.Tensor) and e["h"].dim() == 2 else -1
+            if not 1 <= cols <= self.MAX_COLS or cols % heads:
+                raise ValueError(f"{name}: {cols} columns for {heads} heads; the kernel holds heads * w in 1..{self.MAX_COLS}")
+            given = [k for k in self._BACKWARD if e.get(k) is not None]
+            if given and len(given) != len(self._BACKWARD):
+                raise ValueError(f"{name}: graph_t, t_pos, d_out, d_h and d_s come together or not at all")
+            self.has_backward = self.has_backward and bool(given)
+            n = g.n_rows
+            mats = {k: e[k] for k in ("h", "s", "out", "d_out", "d_h", "d_s") if e.get(k) is not None}
+            for k, t in mats.items():
+                self._matrix(k, t, (n, 2 * heads if k in ("s", "d_s") else cols))
+            if given:
+                gt, t_pos = e["graph_t"], e["t_pos"]
+                if (gt.n_rows, gt.n_cols, gt.nnz) != (n, n, g.nnz):
+                    raise ValueError(f"{name}: graph_t must be the transposed pattern: {n} x {n} with {g.nnz} entries")
+                if not isinstance(t_pos, torch.Tensor) or t_pos.dtype != torch.int32 or tuple(t_pos.shape) != (g.nnz,) or not t_pos.is_contiguous():
+                    raise ValueError(f"{name}: t_pos must be a contiguous [nnz = {g.nnz}] int32 tensor")
+            named = list(mats.items())
+            for i, (ka, ta) in enumerate(named):
+                for kb, tb in named[i + 1:]:
+                    if (ka in ("out", "d_h", "d_s") or kb in ("out", "d_h", "d_s")) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
+            shapes.append((n, heads, cols // heads, g.nnz))
+        tab = self._records(_GAT_JOB_DTYPE)
+        for e in entries:
+            tensors = [e[k] for k in ("h", "s", "out", "d_out", "d_h", "d_s", "t_pos") if e.get(k) is not None]
+            tensors += [t for g in (e["graph"], e.get("graph_t")) if g is not None for t in (g.rowptr, g.col)]
+            if any(t.device != self._dev for t in tensors):
+                raise ValueError(f"{name}: every tensor of an entry must live on the device {self._dev}")
+        nnz_heads = [s_[3] * s_[1] for s_ in shapes]
+        alpha_shapes = [(s_[3], s_[1]) for s_ in shapes]
+        tab["alpha"] = self._own("alpha", nnz_heads, torch.float32, shapes=alpha_shapes)
+        self.d_pre = None
+        if self.has_backward:
+            tab["d_pre"] = self._own("d_pre", nnz_heads, torch.float32, of=None)
+        for field, key, part in (("rowptr", "graph", "rowptr"), ("col", "graph", "col"), ("t_rowptr", "graph_t", "rowptr"), ("t_col", "graph_t", "col")):
+            self._point(tab, field, [None if e.get(key) is None else getattr(e[key], part) for e in entries])
+        self._point(tab, "t_pos", [e.get("t_pos") for e in entries])
+        for field, key, ld in (("H", "h", "ld_h"), ("S", "s", "ld_s"), ("out", "out", "ld_out"), ("d_out", "d_out", "ld_d_out"), ("d_H", "d_h", "ld_d_h"),
+                               ("d_S", "d_s", "ld_d_s")):
+            self._point(tab, field, [e.get(key) for e in entries], ld=ld)
+        for k, field in enumerate(("n", "heads", "w", "nnz")):
+            tab[field] = [s_[k] for s_ in shapes]
+        tab["slope"] = slopes
+        self.max_rows = int(tab["n"].max(initial=0))
+        self._close(tab, "wdg_gat_check_jobs")
+
+    @staticmethod
+    def _matrix(name, t, shape):
+        """job_table._check_matrix without its device test: that one comes after require_gpu()"""
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"GatBatch: {name} must be a {list(shape)} fp32 matrix")
+        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"GatBatch: the rows of {name} must be contiguous (unit inner stride) and must not overlap")
+
+    def launch(self):
+        """out and alpha of every entry"""
+        self._launch("wdg_gat_forward_batched_f32", self.max_rows)
+
+    def launch_backward(self):
+        """d_h and d_s of every entry from d_out, h, s and the alpha of the last launch()"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError("GatBatch.launch_backward: the table was built without gradient tensors")
+        self._launch("wdg_gat_backward_batched_f32", self.max_rows)
 
 
 def acm_operand_gradient(d_pair, t_pair, d_full, width):
