@@ -1716,6 +1716,60 @@ int wdg_gat_check_jobs(const wdg_gat_job *jobs_host, int32_t n_jobs);
 int wdg_csr_transpose_positions(const int32_t *rowptr, const int32_t *col, const int32_t *t_rowptr, const int32_t *t_col, int32_t n,
                                 int32_t *t_pos, int32_t *bad_dev, wdg_stream_t stream);
 
+/*
+ * The attention SCORES of many stacked layers in one launch, and their backward pass: S = H blockdiag(a_dst, a_src) without the
+ * operand - of a stacked run's [R heads w, 2 R heads] one part in R is not zero - and without a transposed copy of H for its gradient.
+ * replaces: the product that forms wdg_gat_job's S for the layer above (utils/util_funcs.py:365-381), for all replicas of a stacked run.
+ * A job: n rows, G groups of w columns each, a block size `heads` in 1..8; H [n, G w], S [n, 2 G], att [2, G w] (plane 0 = a_dst,
+ * plane 1 = a_src, [G, w] each; ld_att floats lie between the planes), and for the backward pass d_S [n, 2 G], d_H [n, G w],
+ * d_att [2, G w] (ld_d_att between its planes) and a workspace `partial` of wdg_gat_scores_partial_len(n, G, w) floats at a 16-byte
+ * boundary.  Every matrix has its own leading dimension and unit inner stride: column slices are passed in place.
+ * Score columns: the groups are cut into consecutive blocks of `heads`; the last block may be shorter.  Block b = g / heads holds
+ * hb = min(heads, G - heads b) groups, and its group g has   dst(g) = 2 heads b + (g - heads b)   and   src(g) = dst(g) + hb:  a block's
+ * dst scores, then its src scores - the S a wdg_gat_job of hb heads reads as the column slice 2 heads b .. 2 heads b + 2 hb.
+ * The arithmetic (csrc/gat_scores.hip is compiled with contraction off and writes every fmaf out; tests/_gat_scores_ref.py restates it):
+ *   forward    S[i, dst(g)] = ONE fmaf chain from +0 over ascending k:  acc = fmaf(H[i, g w + k], a_dst[g, k], acc);  S[i, src(g)]: a_src
+ *   backward   d_H[i, g w + k] = fmaf(d_S[i, src(g)], a_src[g, k], fmaf(d_S[i, dst(g)], a_dst[g, k], d_H[i, g w + k]))
+ *              - d_H is ADDED to: the attention kernel's d_H is there already -;
+ *              the rows are cut into blocks of WDG_GAT_SCORES_ROW_BLOCK from row 0; per block b and element (p, g, k),
+ *              partial[b, p, g w + k] = ONE chain from +0 over the block's rows ascending: acc = fmaf(d_S[i, p ? src(g) : dst(g)], H[i, g w + k], acc),
+ *              and d_att[p, g w + k] = the blocks' sums added in ascending b from +0: acc = acc + partial[b, p, g w + k].
+ * No floating-point atomics; an element depends on its row (forward, d_H) or its column (d_att) of its job alone: a job has the same bits
+ * alone and in any table, and a second launch repeats the first (given d_H as it was).  A NaN in H[i, g w + k] reaches S[i, dst(g)],
+ * S[i, src(g)] and d_att[:, g w + k], nothing else.  16-byte accesses where every pointer and leading dimension of a pass and w allow - one
+ * decision per job -, scalar ones elsewhere: the same values.  Outputs must not overlap inputs or each other.
+ * Limits: heads in 1..WDG_GAT_SCORES_MAX_HEADS, w in 1..WDG_GAT_SCORES_MAX_W, G w < 2^31, at most 65535 jobs (a job per grid z).
+ * max_rows / max_groups / max_cols: the table's largest n, G and G w (what lies beyond them is not worked on).  The backward entry is two
+ * launches: d_H and the partial sums, then the sums of the blocks.
+ * Refused before any launch (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs.  n_jobs == 0 or a
+ * zero maximum: WDG_OK, nothing is launched.  The table lives in device memory: what is wrong inside a job - heads outside 1..8, w outside
+ * 1..256, a negative n or G, G w >= 2^31, NULL H, S or att with n > 0 and G > 0, a leading dimension below its row (ld_h, ld_d_h < G w;
+ * ld_s, ld_d_s < 2 G; ld_att, ld_d_att < G w), the backward pointers (d_S, d_H, d_att, partial) given in part, a workspace that is not
+ * 16-byte aligned - is refused by wdg_gat_scores_check_jobs on the HOST copy of the table (train.GatScoresBatch calls it before it
+ * uploads).  A job with n == 0 or G == 0 is skipped: it touches nothing, d_att included; the kernels leave a job outside the limits untouched.
+ */
+#define WDG_GAT_SCORES_MAX_HEADS 8
+#define WDG_GAT_SCORES_MAX_W 256
+#define WDG_GAT_SCORES_ROW_BLOCK 32
+typedef struct wdg_gat_scores_job {
+    const float *H;      /* [n, G w] */
+    float *S;            /* forward out [n, 2 G] */
+    const float *att;    /* [2, G w]: a_dst, a_src */
+    const float *d_S;    /* backward in [n, 2 G], or NULL (then d_H, d_att and partial are NULL too) */
+    float *d_H;          /* backward in / out [n, G w]: added to */
+    float *d_att;        /* backward out [2, G w] */
+    float *partial;      /* backward workspace [ceil(n / WDG_GAT_SCORES_ROW_BLOCK), 2, G w] */
+    int64_t ld_h, ld_s, ld_att, ld_d_s, ld_d_h, ld_d_att;
+    int32_t n, G, w, heads;
+} wdg_gat_scores_job;
+int wdg_gat_scores_forward_batched_f32(const wdg_gat_scores_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_groups, wdg_stream_t stream);
+/* replaces: nothing of its own - the backward pass of the scores above (utils/util_funcs.py:365-381) */
+int wdg_gat_scores_backward_batched_f32(const wdg_gat_scores_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the scores above (utils/util_funcs.py:365-381), on the host's table */
+int wdg_gat_scores_check_jobs(const wdg_gat_scores_job *jobs_host, int32_t n_jobs);
+/* the floats of a job's workspace: ceil(n / WDG_GAT_SCORES_ROW_BLOCK) * 2 * G * w; 0 for a negative argument */
+int64_t wdg_gat_scores_partial_len(int32_t n, int32_t G, int32_t w);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,10 @@ SIGNATURES = {
     "wdg_gat_forward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_gat_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_gat_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_gat_scores_forward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_gat_scores_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_gat_scores_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_gat_scores_partial_len": (c_int64, [c_int32, c_int32, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -397,6 +401,13 @@ class GatJob(ctypes.Structure):
     _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "t_rowptr", "t_col", "t_pos", "H", "S", "out", "alpha", "d_out", "d_H", "d_S", "d_pre")] + \
                [(name, c_int64) for name in ("ld_h", "ld_s", "ld_out", "ld_d_out", "ld_d_h", "ld_d_s")] + \
                [(name, c_int32) for name in ("n", "heads", "w", "flags")] + [("slope", ctypes.c_float), ("nnz", c_int32)]
+
+
+class GatScoresJob(ctypes.Structure):
+    """mirror of `wdg_gat_scores_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("H", "S", "att", "d_S", "d_H", "d_att", "partial")] + \
+               [(name, c_int64) for name in ("ld_h", "ld_s", "ld_att", "ld_d_s", "ld_d_h", "ld_d_att")] + \
+               [(name, c_int32) for name in ("n", "G", "w", "heads")]
 
 
 if not os.path.exists(LIB_PATH):

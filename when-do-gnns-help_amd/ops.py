@@ -22,6 +22,8 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         dropout of many hidden layers in one launch), AcmMixBatch (the channel mix of many ACM layers, forward and backward),
                         AcmMixPackedBatch (the same mix for stacked class-width layers: 1, 2 or 4 lanes per replica),
                         GatBatch (the graph-attention layer of many graphs, forward and backward: a softmax weight per stored entry),
+                        GatScoresBatch (the scores of stacked attention layers, S = H blockdiag(a_dst, a_src) without the operand, forward and
+                        backward with a parameter gradient summed in a stated order),
                         XentEvalBatch (cross-entropy gradient, hits and model selection of many models with stacked logits),
                         AdamBatch (the Adam step of a stacked run's parameter tensors in one launch: a learning rate and a weight
                         decay per replica in device memory, the step count read from the run's step word),
@@ -34,6 +36,9 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         splits as stacked chunks), select_settings
   acm_split_train.py    AcmSplitTrainBatch (all splits of ONE graph trained as a single stacked run of ACM-SGC-1 / ACM-GCN-2 models, in a
                         channel-major layout; reached as ops.AcmSplitTrainBatch)
+  gat_split_train.py    GatSplitTrainBatch (all splits of ONE graph trained as a single stacked run of GAT-1 / GAT-2 models: the replicas'
+                        layers are column-slice jobs of GatBatch, their scores one GatScoresBatch job per layer; reached as
+                        ops.GatSplitTrainBatch)
   train_batch.py        TrainBatch (one model per graph of a shard, trained for all graphs at once; reached as sweep.TrainBatch)
   sparse_features.py    SparseFeatures (compact feature matrices on the host), expand_features / FeatureExpand (one launch for a list of them),
                         DeviceFeatures (a feature matrix on the device as CSR + its transposed index: matmul / t_matmul, the sparse first layer
@@ -60,7 +65,7 @@ from .stats import (  # noqa: F401
 from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
-from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, GatBatch, HeadTrainBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
+from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, GatBatch, GatScoresBatch, HeadTrainBatch, KeepBestBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .synth import class_graphs_device, ClassGraphBatch, gauss_features_device, GaussFeatureBatch, regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, DeviceFeatures, expand_features, feature_image_floats, FeatureExpand, SparseDenseBatch, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
@@ -68,3 +73,4 @@ from .kernel_regression import (  # noqa: F401
 )
 from .split_train import classification_report, grid_search, masks_from_indices, prediction_overlap, random_masks, select_settings, SplitTrainBatch  # noqa: E402,F401  (last: it builds on the modules above)
 from .acm_split_train import AcmSplitTrainBatch  # noqa: E402,F401
+from .gat_split_train import GatSplitTrainBatch  # noqa: E402,F401

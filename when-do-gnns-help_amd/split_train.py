@@ -148,7 +148,8 @@ class SplitTrainBatch:
         kind "gcn":  logits_r = A_hat relu(A_hat (X W0_r)) W1_r
         kind "mlp1": logits_r = X W_r                                kind "mlp2": logits_r = relu(X W0_r) W1_r
     bias-free, as in sweep.TrainBatch; the per-replica reference is replica_model(r): a models.SGC1 / GCN2 / MLP1 / MLP2.
-    (The ACM kinds "acm_sgc" / "acm_gcn" are stacked over the splits by acm_split_train.AcmSplitTrainBatch, in a layout of their own.)
+    (The ACM kinds "acm_sgc" / "acm_gcn" are stacked over the splits by acm_split_train.AcmSplitTrainBatch, in a layout of their own; the
+    attention kinds "gat1" / "gat2" by gat_split_train.GatSplitTrainBatch.)
 
     An epoch has the meaning of TrainBatch's: gradient of the train loss -> Adam (the L2 term in the gradient) -> a clean forward pass
     -> evaluation and model selection; a step word in device memory advances at its end.  Without dropout the clean forward pass is

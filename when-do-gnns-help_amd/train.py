@@ -6,6 +6,7 @@
   weighted per node) with its backward pass
 - csrc/acm_mix_packed.hip: the same for the stacked class-width layers of acm_split_train, several replicas per 16 lanes
 - csrc/gat.hip: the graph-attention layer of many graphs (GAT-1, GAT-2: a softmax weight per stored entry) with its backward pass
+- csrc/gat_scores.hip: the scores of stacked attention layers, S = H blockdiag(a_dst, a_src) without the operand, with their backward pass
 - csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
 - csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
@@ -31,6 +32,7 @@ _DROPOUT_JOB_DTYPE = np.dtype(_lib.DropoutJob)
 _ACM_JOB_DTYPE = np.dtype(_lib.AcmMixJob)
 _ACM_PACKED_JOB_DTYPE = np.dtype(_lib.AcmPackedJob)
 _GAT_JOB_DTYPE = np.dtype(_lib.GatJob)
+_GAT_SCORES_JOB_DTYPE = np.dtype(_lib.GatScoresJob)
 _XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
 _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
 _KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
@@ -382,12 +384,12 @@ class GatBatch(JobTable):
         self._close(tab, "wdg_gat_check_jobs")
 
     @staticmethod
-    def _matrix(name, t, shape):
+    def _matrix(name, t, shape, table="GatBatch"):
         """job_table._check_matrix without its device test: that one comes after require_gpu()"""
         if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
-            raise ValueError(f"GatBatch: {name} must be a {list(shape)} fp32 matrix")
+            raise ValueError(f"{table}: {name} must be a {list(shape)} fp32 matrix")
         if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise ValueError(f"GatBatch: the rows of {name} must be contiguous (unit inner stride) and must not overlap")
+            raise ValueError(f"{table}: the rows of {name} must be contiguous (unit inner stride) and must not overlap")
 
     def launch(self):
         """out and alpha of every entry"""
@@ -398,6 +400,95 @@ class GatBatch(JobTable):
         if not self.has_backward and self.n_jobs:
             raise ValueError("GatBatch.launch_backward: the table was built without gradient tensors")
         self._launch("wdg_gat_backward_batched_f32", self.max_rows)
+
+
+class GatScoresBatch(JobTable):
+    """Job table for wdg_gat_scores_forward_batched_f32 / wdg_gat_scores_backward_batched_f32 (csrc/gat_scores.hip): the attention scores
+    of G groups of w columns per entry - S[i, dst(g)] = sum_k H[i, g w + k] a_dst[g, k], S[i, src(g)] the same with a_src, the columns
+    laid out in blocks of `heads` groups as the GatBatch jobs of those blocks read them (include/wdg.h states the layout, the chains and
+    the order of every sum; tests/_gat_scores_ref.py restates them in numpy) - and their backward pass: d_h is ADDED to (the attention
+    kernel's d_H is there already), d_att is written from partial sums over blocks of ROW_BLOCK rows that the table owns."""
+
+    MAX_JOBS, MAX_HEADS, MAX_W, ROW_BLOCK = 65535, 8, 256, 32
+    _KEYS = ("h", "s", "att", "heads", "d_s", "d_h", "d_att")
+    _BACKWARD = ("d_s", "d_h", "d_att")
+
+    def __init__(self, entries):
+        """entries: list of dicts - h [n, G w] and s [n, 2 G] fp32 (unit inner stride, any leading dimension: column slices of a wider
+           matrix are fine), att [2, G, w] fp32 (a_dst, a_src; each plane contiguous), heads (int, default 1): the block size of the
+           score columns;
+           and, for launch_backward(): d_s [n, 2 G], d_h [n, G w], d_att [2, G, w] - all three or none.
+        Raises ValueError for heads outside 1..8, w outside 1..256, other dtypes, shapes or strides, more than 65535 entries, the backward
+        tensors given in part, an output that overlaps an input or another output of its entry."""
+        name = "GatScoresBatch"
+        n_jobs = self._open(entries)
+        self.has_backward = n_jobs > 0
+        shapes = []
+        for e in entries:
+            unknown = set(e) - set(self._KEYS)
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            if any(e.get(k) is None for k in ("h", "s", "att")):
+                raise ValueError(f"{name}: h, s and att are required")
+            heads = int(e.get("heads", 1))
+            if not 1 <= heads <= self.MAX_HEADS:
+                raise ValueError(f"{name}: a block of {heads} heads; the kernel holds 1..{self.MAX_HEADS}")
+            given = [k for k in self._BACKWARD if e.get(k) is not None]
+            if given and len(given) != len(self._BACKWARD):
+                raise ValueError(f"{name}: d_s, d_h and d_att come together or not at all")
+            self.has_backward = self.has_backward and bool(given)
+            att = e["att"]
+            if not isinstance(att, torch.Tensor) or att.dim() != 3 or att.shape[0] != 2 or att.dtype != torch.float32:
+                raise ValueError(f"{name}: att must be a [2, G, w] fp32 tensor")
+            G, w = int(att.shape[1]), int(att.shape[2])
+            if not 1 <= w <= self.MAX_W:
+                raise ValueError(f"{name}: groups of {w} columns; the kernel holds 1..{self.MAX_W}")
+            if G * w >= 1 << 31:
+                raise ValueError(f"{name}: {G * w} columns; the kernel holds fewer than 2^31")
+            n = e["h"].shape[0] if isinstance(e["h"], torch.Tensor) and e["h"].dim() == 2 else -1
+            mats = {k: e[k] for k in ("h", "s", "d_s", "d_h") if e.get(k) is not None}
+            for k, t in mats.items():
+                GatBatch._matrix(k, t, (n, 2 * G if k in ("s", "d_s") else G * w), name)
+            for k in ("att", "d_att"):
+                t = e.get(k)
+                if t is None:
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (2, G, w):
+                    raise ValueError(f"{name}: {k} must be a [2, {G}, {w}] fp32 tensor")
+                if G and not t[0].is_contiguous():
+                    raise ValueError(f"{name}: the planes of {k} must be contiguous")
+                mats[k] = t.as_strided((2, G * w), (max(t.stride(0), G * w), 1))  # [2, G w]: what the kernel addresses
+            named = list(mats.items())
+            for i, (ka, ta) in enumerate(named):
+                for kb, tb in named[i + 1:]:
+                    if (ka in ("s", "d_h", "d_att") or kb in ("s", "d_h", "d_att")) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
+            shapes.append((n, G, w, heads, mats))
+        tab = self._records(_GAT_SCORES_JOB_DTYPE)
+        for s_ in shapes:
+            if any(t.device != self._dev for t in s_[4].values()):
+                raise ValueError(f"{name}: every tensor of an entry must live on the device {self._dev}")
+        if self.has_backward:
+            tab["partial"] = self._own("partial", [-(-s_[0] // self.ROW_BLOCK) * 2 * s_[1] * s_[2] for s_ in shapes], torch.float32, of=None, align=4)
+        for field, key, ld in (("H", "h", "ld_h"), ("S", "s", "ld_s"), ("att", "att", "ld_att"), ("d_S", "d_s", "ld_d_s"), ("d_H", "d_h", "ld_d_h"),
+                               ("d_att", "d_att", "ld_d_att")):
+            self._point(tab, field, [s_[4].get(key) for s_ in shapes], ld=ld)
+        for k, field in enumerate(("n", "G", "w", "heads")):
+            tab[field] = [s_[k] for s_ in shapes]
+        self.max_rows = int(tab["n"].max(initial=0))
+        self.max_groups = int(tab["G"].max(initial=0))
+        self.max_cols = int((tab["G"].astype(np.int64) * tab["w"]).max(initial=0))
+        self._close(tab, "wdg_gat_scores_check_jobs")
+
+    def launch(self):
+        """s of every entry"""
+        self._launch("wdg_gat_scores_forward_batched_f32", self.max_rows, self.max_groups)
+
+    def launch_backward(self):
+        """d_h += and d_att = of every entry, from d_s, h and att"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError("GatScoresBatch.launch_backward: the table was built without gradient tensors")
+        self._launch("wdg_gat_scores_backward_batched_f32", self.max_rows, self.max_cols)
 
 
 def acm_operand_gradient(d_pair, t_pair, d_full, width):
