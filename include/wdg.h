@@ -944,6 +944,10 @@ int wdg_kernel_regress_large_windows_batched_f32(const wdg_kr_job *jobs_dev, int
  * is written to train_out + s train_stride / val_out + s val_stride (sum of train_per_class / of sample - train entries each).
  * Grid block b serves set b - first_set of the job with first_set <= b < first_set + n_sets (jobs ascending in first_set).
  * Limits: n <= 16 000 nodes, n_classes <= 64.  Labels outside [0, n_classes) are never drawn.
+ * A class with fewer members than train_per_class[c] / sample_per_class[c] gives what it has.  A set that comes out shorter than
+ * its stride for either reason leaves the remaining entries of its row UNTOUCHED (neither zeroed nor marked): the sums above are
+ * then upper bounds of the set's length, and a caller who needs the length fills the outputs with a marker before the launch.
+ * Nothing is ever written past a row's stride.
  */
 typedef struct wdg_kr_sample_job {
     const int32_t *labels;            /* [n] */

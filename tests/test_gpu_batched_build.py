@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from _kr_sets_ref import host_sets as _host_sets  # the definition of include/wdg.h in numpy (held by tests/test_kr_sets_ref.py)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -78,35 +80,6 @@ def test_sweep_batch_builds_agree_bitwise():
 
 
 # ---------------------------------------------------------------------------------------------- the device sampler
-def _philox4x32_10(c0, c1, k0, k1):
-    """numpy restatement of the documented generator (include/wdg.h): first output word of Philox4x32-10, counter {c0, c1, 0, 0}"""
-    c0, c1 = np.asarray(c0, np.uint64), np.asarray(c1, np.uint64) + np.zeros_like(np.asarray(c0, np.uint64))
-    c2, c3 = np.zeros_like(c0), np.zeros_like(c0)
-    k0, k1 = np.uint64(k0), np.uint64(k1)
-    m32 = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        n0, n2 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & m32, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & m32
-        c1, c3, c0, c2 = p1 & m32, p0 & m32, n0, n2
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
-    return c0
-
-
-def _host_sets(labels, s_c, t_c, seed, epochs):
-    n = len(labels)
-    out = []
-    for e in range(epochs):
-        key = _philox4x32_10(np.arange(n), e, seed & 0xFFFFFFFF, seed >> 32)
-        order = np.lexsort((np.arange(n), key, labels))  # by (class, key, node)
-        train, val = [], []
-        for c in range(len(s_c)):
-            members = order[labels[order] == c]
-            train += list(members[:t_c[c]])
-            val += list(members[t_c[c]:s_c[c]])
-        out.append((np.sort(train), np.sort(val)))
-    return out
-
-
 def test_device_node_sets_follow_the_documented_generator():
     from wdg_amd import ops
     rng = np.random.default_rng(5)

@@ -9,6 +9,7 @@ import torch
 
 from _golden import REAL, SYN, dense_features, load
 from _gram_ref import arccos_map32
+from _row_rep_ref import rep_numpy as _rep_numpy  # the dictionary over the rows' bytes (held by tests/test_row_rep_ref.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -1764,13 +1765,6 @@ def test_spmm_narrow_batched_table(ops, oracle, f, ld):
 
 
 # ------------------------------------------------------------------------------------------- row representatives / deflation
-def _rep_numpy(rows_bytes):
-    first, rep = {}, []
-    for i, b in enumerate(rows_bytes):
-        rep.append(first.setdefault(b, i))
-    return np.asarray(rep, np.int32)
-
-
 def test_row_representatives_of_dense_tiled_and_csr_rows():
     """wdg_row_rep_batched: rep[i] = the smallest row bit-identical to row i (+0 == -0, a NaN row equals nothing), for row-major and
     tiled dense matrices and for the rows of a scaled CSR pattern - against a dictionary over the rows' bytes"""

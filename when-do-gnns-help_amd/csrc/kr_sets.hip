@@ -31,8 +31,8 @@ constexpr int KS_MAX_CLASSES = 64;
 // the few nodes of those two boundary bins (counted against the other members of the same class and bin, by a wave per such
 // node) - every other node is classified by its bin alone.  256 threads and ~25 KB of LDS per set instead of a 1024-thread
 // comparator network over 64-bit keys with ~90 barriers: several workgroups share a CU, so the launch also runs well BESIDE the
-// Gram kernels it is queued next to (a sort held whole CUs).  tests/test_gpu_batched_build.py compares the device's sets with a
-// numpy restatement of the definition.
+// Gram kernels it is queued next to (a sort held whole CUs).  tests/test_gpu_kr_sets.py compares the device's sets with a
+// numpy restatement of the definition (tests/_kr_sets_ref.py), at every bin layout and with more boundary members than the list holds.
 constexpr int KSEL_THREADS = 256, KSEL_WAVES = KSEL_THREADS / 64, KSEL_LIST = 1024;
 __device__ __forceinline__ unsigned long long ksel_composite(unsigned cls, unsigned key, int node) {
     return (static_cast<unsigned long long>(cls) << 56) | (static_cast<unsigned long long>(key) << 24) | static_cast<unsigned long long>(node);

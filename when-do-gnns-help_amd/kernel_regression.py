@@ -249,7 +249,12 @@ class KrSets:
     """Job table for wdg_kr_sample_sets: the (train, validation) node sets of every epoch of many (graph, classifier) pairs,
     drawn on the device in one launch (Philox4x32-10 keyed per pair; include/wdg.h documents the generator).
     self.train [pairs, epochs, n_train], self.val [pairs, epochs, n_val] int32, ascending ids; pairs whose graphs differ in
-    class sizes are padded to the widest (self.n_train / self.n_val hold the true lengths)."""
+    class sizes are padded to the widest (self.n_train / self.n_val hold the true lengths).
+    A set that comes out SHORTER than its stride - labels outside [0, n_classes), or hand-given sizes above a class's count: a
+    class gives what it has - leaves the remaining entries untouched: launch() writes a set's true length and nothing behind it,
+    and n_train / n_val (the sums of t_c and of s_c - t_c) are then upper bounds.  Sizes from kr_split_sizes over labels inside
+    the range never ask for more than a class has; a caller with other sizes fills train / val with a marker of its own before
+    launch() and reads each set up to it (the tensors come from torch.empty when every pair has the same sizes)."""
 
     def __init__(self, entries, epochs, out=None):
         """entries: list of (labels int32 device [n], s_c, t_c (kr_split_sizes), seed int)
@@ -261,11 +266,11 @@ class KrSets:
         n = self.n_pairs
         sums = {}
         for _l, s_, t, _seed in entries:
-            if id(t) not in sums:
-                sums[id(t)] = (int(np.sum(t)), int(np.sum(s_)) - int(np.sum(t)), len(s_))
-        self.n_train = np.fromiter((sums[id(e[2])][0] for e in entries), np.int64, n)
-        self.n_val = np.fromiter((sums[id(e[2])][1] for e in entries), np.int64, n)
-        n_cls = np.fromiter((sums[id(e[2])][2] for e in entries), np.int64, n)
+            if (id(s_), id(t)) not in sums:
+                sums[(id(s_), id(t))] = (int(np.sum(t)), int(np.sum(s_)) - int(np.sum(t)), len(s_))
+        self.n_train = np.fromiter((sums[(id(e[1]), id(e[2]))][0] for e in entries), np.int64, n)
+        self.n_val = np.fromiter((sums[(id(e[1]), id(e[2]))][1] for e in entries), np.int64, n)
+        n_cls = np.fromiter((sums[(id(e[1]), id(e[2]))][2] for e in entries), np.int64, n)
         if n and int(n_cls.max()) > 64:
             raise ValueError("KrSets: more than 64 classes")
         self.train_stride, self.val_stride = int(self.n_train.max(initial=0)), int(self.n_val.max(initial=0))
