@@ -105,6 +105,9 @@ int wdg_csr_split_blockdiag(const int32_t *rowptr, int32_t *col, const float *va
  * Dense [N,M] fp32 -> CSR of its non-zeros (the "plot" flavour hands dense adjacencies around).
  * replaces: `A.nonzero()`, `A.to_sparse().coalesce()`, `(adj > 0)` utils/homophily_plot.py:48,85,133,151.
  * Two calls: count (fills rowptr), then fill (needs col/val of rowptr[N] entries).
+ * An entry is stored when it compares != 0: -0.0 is dropped; NaN, inf and subnormals are kept, bit for bit.  Columns M .. lda - 1 are
+ * never read.  A matrix without rows or without columns has no storage: A may be NULL when N == 0 or M == 0, and the count call
+ * itself then returns the empty pattern (rowptr = N + 1 zeros) - the wrappers need no case of their own.
  */
 int wdg_dense_to_csr_count(const float *A, int64_t lda, int32_t N, int32_t M, int32_t *rowptr, void *workspace,
                            size_t workspace_bytes, wdg_stream_t stream);
@@ -121,12 +124,17 @@ size_t wdg_scan_workspace_bytes(int64_t n);
 /*
  * Row sums / counts and the normalisation coefficient d_i (1/rowsum or rowsum^-1/2; inf -> 0; in the
  * F64 path rowsum==0 -> 1).  Any of rowsum / cnt / dinv_f32 / dinv_f64 may be NULL.
+ * The row sum is an fp64 sum; rowsum is its fp32 rounding.  F32: 1.0f / s or 1.0f / sqrtf(s) on s = (float)sum, dinv_f64 the same
+ * number; F64: 1.0 / sum or 1.0 / sqrt(sum) (two correctly rounded operations: within a last bit of pow(sum, -0.5)), dinv_f32 its
+ * fp32 rounding.  A NaN entry or, for SYM, a negative sum makes that row's coefficient NaN and no other's.
  * replaces: the degree part of normalize, normalize_tensor, row_normalized_adjacency,
  *           sys_normalized_adjacency (utils/util_funcs.py:31-33,367-370,376-377,386,421-424).
  */
 int wdg_degree_norm(const int32_t *rowptr, const float *val, int32_t N, int mode, int prec, float *rowsum,
                     int32_t *cnt, float *dinv_f32, double *dinv_f64, wdg_stream_t stream);
-/* Materialise A_hat's values exactly as the reference would: out[p] = d_i * val[p] (* d_col[p] for SYM). */
+/* Materialise A_hat's values exactly as the reference would: out[p] = d_i * val[p] (* d_col[p] for SYM).
+ * SYM reads dinv[col[p]] from the N row coefficients: every column must be < N, i.e. the pattern square.  The call does not know the
+ * column count and cannot check it: graphs.normalise_values refuses a pattern of another shape before it launches. */
 int wdg_normalise_values(const int32_t *rowptr, const int32_t *col, const float *val, int32_t N, int mode, int prec,
                          const float *dinv_f32, const double *dinv_f64, float *out, wdg_stream_t stream);
 /*

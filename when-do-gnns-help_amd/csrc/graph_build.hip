@@ -794,9 +794,13 @@ int wdg_csr_split_blockdiag(const int32_t *rowptr, int32_t *col, const float *va
 int wdg_dense_to_csr_count(const float *A, int64_t lda, int32_t N, int32_t M, int32_t *rowptr, void *workspace,
                            size_t workspace_bytes, wdg_stream_t stream) {
     WDG_REQUIRE(N >= 0 && M >= 0 && rowptr, "dense_to_csr_count: bad arguments");
-    WDG_REQUIRE(N == 0 || (A && lda >= M), "dense_to_csr_count: bad matrix");
+    WDG_REQUIRE(N == 0 || M == 0 || (A && lda >= M), "dense_to_csr_count: bad matrix");
     if (!workspace || workspace_bytes < wdg_scan_workspace_bytes(N)) return fail(WDG_ERR_WORKSPACE, "dense_to_csr: workspace too small");
     hipStream_t st = as_stream(stream);
+    if (M == 0) {  // a matrix without columns has no storage (A may be NULL): N empty rows, nothing to read
+        hipMemsetAsync(rowptr, 0, sizeof(int32_t) * (static_cast<size_t>(N) + 1), st);
+        return check_launch("dense_to_csr_count");
+    }
     void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
     if (N > 0) hipLaunchKernelGGL(dense_count, dim3(wave_rows_grid(N)), dim3(256), 0, st, A, lda, N, M, rowptr);
     return exclusive_scan(rowptr, N, rowptr, nullptr, ws, st);

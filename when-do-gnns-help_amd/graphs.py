@@ -237,10 +237,11 @@ class CsrGraph:
         return CsrGraph.from_coo(self.row_indices(), self.col, self.n_rows, self.val, flags)
 
     def transpose(self):
-        """A^T as CSR (the backward pass of a directed graph needs it)."""
-        g = CsrGraph.from_coo(self.col, self.row_indices(), self.n_cols, self.val, 0)
-        g.n_cols = self.n_rows
-        return g
+        """A^T as CSR (the backward pass of a directed graph needs it).  Any shape: the COO builder takes ONE node
+        count, so a tall pattern is built with n_rows nodes and the n_rows - n_cols empty rows at its end are cut off again."""
+        n = max(self.n_rows, self.n_cols)
+        g = CsrGraph.from_coo(self.col, self.row_indices(), n, self.val, 0)
+        return CsrGraph(g.rowptr[:self.n_cols + 1], g.col, g.val, self.n_cols, self.n_rows)
 
     def transpose_positions(self, g_t):
         """-> t_pos int32 [nnz]: for every entry q of g_t = self.transpose() the position of the matching entry of self
@@ -601,9 +602,21 @@ def degree_norm(g, mode=NORM_RW, prec=PREC_F32, use_values=True):
     return out
 
 
-def normalise_values(g, mode=NORM_RW, prec=PREC_F32):
-    """A_hat's stored values as the reference materialises them (D^-1 A or D^-1/2 A D^-1/2) -> new CsrGraph."""
+def normalise_values(g, mode=NORM_RW, prec=PREC_F32, zero_sum_rows=False):
+    """A_hat's stored values as the reference materialises them (D^-1 A or D^-1/2 A D^-1/2) -> new CsrGraph.
+
+    NORM_SYM scales entry (i, j) by d_i and d_j, both row coefficients: the pattern must be square (ValueError otherwise - the
+    kernel would read d[col] past the n_rows coefficients).  zero_sum_rows: a row whose sum is 0 gets coefficient 0 whatever the
+    path's own rule says (F64 keeps such a row as it is, sklearn's rule) - the `1 / rowsum; inf -> 0` of the reference's
+    normalize / preprocess_features, which zeroes a row whose entries cancel."""
+    if mode == NORM_SYM and g.n_rows != g.n_cols:
+        raise ValueError(f"normalise_values: NORM_SYM needs a square pattern (one coefficient per row, used for rows and columns), got "
+                         f"{g.n_rows} x {g.n_cols}")
     d = degree_norm(g, mode, prec)
+    if zero_sum_rows:
+        zero = d["rowsum"] == 0
+        d["dinv"].masked_fill_(zero, 0.0)
+        d["dinv64"].masked_fill_(zero, 0.0)
     out = torch.empty(g.nnz, dtype=torch.float32, device=g.device)
     if g.nnz == 0:  # nothing stored: nothing to scale (empty tensors have no device pointer to hand over)
         return g.with_values(out)

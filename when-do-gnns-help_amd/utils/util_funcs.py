@@ -27,11 +27,15 @@ def _csr_to_scipy(g, dtype=np.float64):
 
 # ------------------------------------------------------------------------------------------- row scaling
 def normalize(mx):
-    """Row-normalise: diag(1/rowsum) mx, inf -> 0.  reference: utils/util_funcs.py:29-36."""
+    """Row-normalise: diag(1/rowsum) mx, inf -> 0.  reference: utils/util_funcs.py:29-36.
+
+    A row whose sum is 0 comes back all zero - a row without entries and a row whose entries cancel alike (1 / 0 = inf -> 0 is the
+    row's coefficient), on every input kind.  (row_normalized_adjacency is the other rule: sklearn leaves a zero row as it is.)"""
     if _is_scipy(mx):
         # any shape (feature matrices are N x F): the CSR arrays are uploaded as they are - the COO builder is for square
-        # adjacencies; coefficients in fp64 like scipy's, stored values are the fp32 roundings (device values are fp32)
-        g = ops.normalise_values(CsrGraph.from_scipy_csr(mx), ops.NORM_RW, ops.PREC_F64)
+        # adjacencies; coefficients in fp64 like scipy's, stored values are the fp32 roundings (device values are fp32);
+        # zero_sum_rows: the F64 / RW coefficient of a zero row sum is sklearn's 1, this function's is 0
+        g = ops.normalise_values(CsrGraph.from_scipy_csr(mx), ops.NORM_RW, ops.PREC_F64, zero_sum_rows=True)
         return _csr_to_scipy(g, mx.dtype)
     if isinstance(mx, torch.Tensor):
         return ops.row_l1_normalise(mx)
