@@ -1782,6 +1782,82 @@ int wdg_gat_scores_check_jobs(const wdg_gat_scores_job *jobs_host, int32_t n_job
 /* the floats of a job's workspace: ceil(n / WDG_GAT_SCORES_ROW_BLOCK) * 2 * G * w; 0 for a negative argument */
 int64_t wdg_gat_scores_partial_len(int32_t n, int32_t G, int32_t w);
 
+/*
+ * Signed attention for many graphs in one launch, and its backward pass (the layer of FAGCN: Bo et al., "Beyond Low-frequency
+ * Information in Graph Convolutional Networks"): a weight per stored entry that is learnt and may be NEGATIVE - tanh where
+ * wdg_gat_job has the softmax, so an edge can subtract a neighbour -, times the fixed factored scales of the normalised adjacency.
+ * The reference ships no model code: the layer is DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: the fixed weights of normalize_tensor, utils/util_funcs.py:365-381, in the aggregation, by signed learnt ones, for the
+ *           high-pass baseline that stands beside the GCN / SGC tables of gnns_on_syn.py:1-154 (models that live upstream of the reference).
+ * A job: the square CSR PATTERN of wdg_gat_job - rowptr int32 [n + 1], col int32 [nnz], columns strictly ascending inside a row; stored
+ * values are ignored -, heads in 1..8 of width w >= 1 with heads w <= 256, H [n, heads w], S [n, 2 heads] (S[:, h] the row's own
+ * score, S[:, heads + h] its score as a neighbour), row_scale [n] or NULL and col_scale [n] or NULL (NULL = 1: the two vectors of a
+ * factored A_hat = diag(r) A diag(c)), an optional residual res [n, heads w] with the scalar eps (NULL = none; eps is then not read).
+ * The definition, for row i, head h and the row's stored entries p in ascending order, j = col[p]:
+ *   pre_p  = S[i, h] + S[j, heads + h]          t_p = tanhf(pre_p)
+ *   coef_p = row_scale[i] * col_scale[j]        ONE fp32 product; a NULL factor is left out, both NULL: 1
+ *   a_p    = t_p * coef_p  -> alpha[p, h]       [nnz, heads] contiguous: the SIGNED weight that is applied, kept for the backward pass
+ *   chain  = sum_p a_p H[j, h w + k]            ONE fmaf chain from +0 over ascending p: acc = fmaf(a_p, H[j, .], acc)
+ *   out[i, h w + k] = fmaf(eps, res[i, h w + k], chain)          (no residual: out = chain)
+ * The backward pass, g = d_out[i, :]:
+ *   dalpha_p = sum_k g[h w + k] H[j, h w + k]   ONE fmaf chain from +0 over ascending k
+ *   u_p      = fmaf(-t_p, t_p, 1.0f)            t_p recomputed from S by the forward's expression: the same bits
+ *   dpre_p   = (dalpha_p * coef_p) * u_p  -> d_pre[p, h] (workspace [nnz, heads])          d_S[i, h] = sum_p dpre_p
+ * and, over the TRANSPOSED pattern (t_rowptr, t_col; entry q of row j has source row i = t_col[q] and is forward entry p = t_pos[q]):
+ *   d_H[j, h w + k] = sum_q alpha[p, h] d_out[i, h w + k]     ONE fmaf chain from +0 over ascending q
+ *   d_S[j, heads + h] = sum_q d_pre[p, h]
+ * The residual's gradient, eps * d_out, is the caller's: the kernels do not write it.  d_S[i, h] and d_S[j, heads + h] are summed in
+ * the order wdg_gat_job states for its sums over a row's entries: lane l of 64 adds the entries l, l + 64, ... in ascending order from
+ * +0 (acc = acc + term), then the butterfly over lane distances 32, 16, 8, 4, 2, 1.  There are no floating-point atomics;
+ * csrc/signed_att.hip is compiled with contraction off and writes every fmaf out.  tanhf is the device library's: its error in ulps is
+ * measured, not assumed (tests/test_gpu_signed_att.py); where it returns +-1 exactly - large |pre| - u_p is exactly 0.
+ * An empty row writes out = fmaf(eps, res, +0) - +0 without a residual - and +0 gradients, and no alpha.  A NaN stays a NaN: one in
+ * row j of H reaches out[i, :] of exactly the rows i that store j, one in d_out[i, :] reaches d_H[j, :] of exactly the columns j that
+ * row i stores.  An element depends on its row, or its transposed row, alone, and a job on the job alone: a job answers in a table
+ * what it answers alone, and head h of a job has the bits of a one-head job on that head's column slices (every matrix has its own
+ * leading dimension: slices are passed in place).  Outputs must not overlap inputs or each other.  16-byte accesses where a
+ * matrix's pointer and leading dimension allow, scalar ones elsewhere: the same values.
+ * Guards: an entry whose column lies outside [0, n) - or whose t_pos lies outside [0, nnz) - is skipped, never read through (its
+ * alpha and d_pre are written +0); a row whose extent lies outside [0, nnz] is left untouched, and so is a job outside the limits.
+ * max_rows: the table's largest n (rows beyond it are not worked on).  wdg_signed_att_backward_batched_f32 is two launches: the row
+ * pass, then the pass over the transposed pattern; it reads the alpha of the last forward launch.
+ * Refused before any launch (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs (a job per grid
+ * z).  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is launched.  The table lives in device memory: what is wrong inside a job - heads
+ * outside 1..8, w < 1, heads w > 256, an eps that is infinite or a NaN, flags other than 0, a negative n or nnz, a NULL rowptr, H, S or
+ * out, a NULL col or alpha with nnz > 0, a leading dimension below the row (ld_res with res given), the backward pointers (d_out, d_H,
+ * d_S, t_rowptr; d_pre, t_col, t_pos with nnz > 0) given in part - is refused by wdg_signed_att_check_jobs on the HOST copy of the
+ * table (train.SignedAttBatch calls it before it uploads).  A job with n == 0 is skipped.
+ */
+#define WDG_SIGNED_ATT_MAX_HEADS 8
+#define WDG_SIGNED_ATT_MAX_COLS 256
+typedef struct wdg_signed_att_job {
+    const int32_t *rowptr;    /* [n + 1] */
+    const int32_t *col;       /* [nnz], strictly ascending inside a row */
+    const int32_t *t_rowptr;  /* [n + 1]: the transposed pattern (backward), or NULL */
+    const int32_t *t_col;     /* [nnz] */
+    const int32_t *t_pos;     /* [nnz]: the forward entry of every transposed entry (wdg_csr_transpose_positions) */
+    const float *H;           /* [n, heads w] */
+    const float *S;           /* [n, 2 heads] */
+    float *out;               /* forward out [n, heads w] */
+    float *alpha;             /* [nnz, heads]: forward out, backward in */
+    const float *d_out;       /* backward in [n, heads w] */
+    float *d_H;               /* backward out [n, heads w] */
+    float *d_S;               /* backward out [n, 2 heads] */
+    float *d_pre;             /* backward workspace [nnz, heads] */
+    const float *row_scale;   /* [n], or NULL = 1 */
+    const float *col_scale;   /* [n], or NULL = 1 */
+    const float *res;         /* [n, heads w]: the residual, or NULL = none */
+    int64_t ld_h, ld_s, ld_out, ld_d_out, ld_d_h, ld_d_s, ld_res;
+    int32_t n, heads, w, flags; /* flags: 0 (none is defined) */
+    float eps;                /* the residual's factor */
+    int32_t nnz;              /* rowptr[n]: the extent of col, alpha and d_pre */
+} wdg_signed_att_job;
+int wdg_signed_att_forward_batched_f32(const wdg_signed_att_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+/* replaces: nothing of its own - the backward pass of the layer above (utils/util_funcs.py:365-381) */
+int wdg_signed_att_backward_batched_f32(const wdg_signed_att_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the layer above (utils/util_funcs.py:365-381), on the host's table */
+int wdg_signed_att_check_jobs(const wdg_signed_att_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

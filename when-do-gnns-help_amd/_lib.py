@@ -194,6 +194,9 @@ SIGNATURES = {
     "wdg_gat_scores_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_gat_scores_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_gat_scores_partial_len": (c_int64, [c_int32, c_int32, c_int32]),
+    "wdg_signed_att_forward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_signed_att_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_signed_att_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -408,6 +411,14 @@ class GatScoresJob(ctypes.Structure):
     _fields_ = [(name, c_void_p) for name in ("H", "S", "att", "d_S", "d_H", "d_att", "partial")] + \
                [(name, c_int64) for name in ("ld_h", "ld_s", "ld_att", "ld_d_s", "ld_d_h", "ld_d_att")] + \
                [(name, c_int32) for name in ("n", "G", "w", "heads")]
+
+
+class SignedAttJob(ctypes.Structure):
+    """mirror of `wdg_signed_att_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "t_rowptr", "t_col", "t_pos", "H", "S", "out", "alpha", "d_out", "d_H", "d_S", "d_pre",
+                                              "row_scale", "col_scale", "res")] + \
+               [(name, c_int64) for name in ("ld_h", "ld_s", "ld_out", "ld_d_out", "ld_d_h", "ld_d_s", "ld_res")] + \
+               [(name, c_int32) for name in ("n", "heads", "w", "flags")] + [("eps", ctypes.c_float), ("nnz", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

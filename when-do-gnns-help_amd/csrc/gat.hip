@@ -23,146 +23,19 @@
 // decision.  The first form of this file left one wait behind every load and ran at 1.5 - 1.8 times these times.
 // Guards: an entry whose column (or whose t_pos) lies outside the job is skipped - never read through -, a row whose extent lies outside
 // [0, nnz] and a job outside the limits are left untouched.
-#include <cmath>
-#include <cstdint>
-
-#include "wdg_common.h"
-
-#pragma clang fp contract(off)  // every fused multiply-add of the definition is written as fmaf; nothing else may be fused
+#include "gat_lanes.h"
 
 namespace {
 
-using namespace wdg;
+using namespace wdg_gt;
 
-constexpr int GT_WAVES = 4;                  // rows per workgroup
-constexpr int GT_HEADS = WDG_GAT_MAX_HEADS;  // the unrolled head loops and the LDS stage's row
-constexpr int GT_MAX_JOBS = 65535;           // gridDim.z
-#ifndef WDG_GAT_DEPTH
-#define WDG_GAT_DEPTH 8
-#endif
-constexpr int GT_DEPTH = WDG_GAT_DEPTH;      // row loads in flight before the first fmaf of a batch (a divisor of 64; DESIGN 4.25 has the A/B)
-
-// the wave's sum in the STATED order: partner lanes 32, 16, 8, 4, 2, 1 apart, each step adding a pair both ways (every lane ends with
-// the same bits)
-__device__ __forceinline__ float gt_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    return v;
-}
 // the wave's maximum; fmaxf skips a NaN, and the value of a maximum does not depend on the order
 __device__ __forceinline__ float gt_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-// what one lane of a wave wrote to the wave's LDS region is read by another: LDS operations of a wave execute in order, so only the
-// compiler has to keep them in place
-__device__ __forceinline__ void gt_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool gt_aligned16(const float *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
 __device__ __forceinline__ float gt_leaky(const float pre, const float slope) { return pre > 0.f ? pre : slope * pre; }
-
-// the lane's four columns c0 .. c0 + 3 of the job's heads * w, and the head of each
-struct gt_lane_cols {
-    int c0, live;  // live: how many of the four exist (0 .. 4)
-    int hk[4];
-};
-__device__ __forceinline__ gt_lane_cols gt_columns(const int lane, const int heads, const int w) {
-    gt_lane_cols lc;
-    lc.c0 = 4 * lane;
-    lc.live = max(0, min(4, heads * w - lc.c0));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) lc.hk[k] = min((lc.c0 + k) / w, heads - 1);
-    return lc;
-}
-// VEC is the WAVE's decision (pointer and leading dimension 16-byte aligned, heads w a multiple of 4: every lane that has columns has
-// four): no per-lane branch sits between a load and its use, so the loads of a batch stay in flight together.  Without VEC a lane
-// reads its `live` columns one by one; the address of a column it does not have is clamped to its last one (the value is never stored).
-template <bool VEC>
-__device__ __forceinline__ void gt_load4(const global_ptr<const float> p, const int live, float (&x)[4]) {
-    if (VEC) {
-        const float4 in = load_f32x4(p);
-        x[0] = in.x, x[1] = in.y, x[2] = in.z, x[3] = in.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = p[min(k, live - 1)];
-    }
-}
-__device__ __forceinline__ void gt_store4(const global_ptr<float> p, const bool vec, const int live, const float (&x)[4]) {
-    if (vec) {
-        store_f32x4(p, make_float4(x[0], x[1], x[2], x[3]));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < live) p[k] = x[k];
-    }
-}
-__device__ __forceinline__ bool gt_wave_vec(const float *p, const int64_t ld, const int cols) { return gt_aligned16(p, ld) && (cols & 3) == 0; }
-
-// D consecutive entries d0 .. d0 + D - 1 of the chunk the wave holds: all D row loads, then the D x 4 fmafs in entry order -
-// acc[k] = fmaf(weight of the entry for the column's head, X[source row][c0 + k], acc[k]).  src: lane d holds the source row of entry
-// d, or -1 for an entry that is skipped (its load goes to row 0 and its fmaf is not applied); stage: the wave's [64][GT_HEADS]
-// weights.  EVERY lane is active at the readlanes; a lane without columns only skips the loads and the fmafs.
-template <int D, bool VEC>
-__device__ __forceinline__ void gt_batch(const global_ptr<const float> x_base, const int64_t ld, const gt_lane_cols &lc, const bool one_head, const int src,
-                                         const int d0, const float *stage, float (&acc)[4]) {
-    int r[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) r[d] = __builtin_amdgcn_readlane(src, d0 + d);
-    if (lc.live > 0) {
-        float x[D][4];
-#pragma unroll
-        for (int d = 0; d < D; ++d) gt_load4<VEC>(x_base + static_cast<int64_t>(max(r[d], 0)) * ld + lc.c0, lc.live, x[d]);
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const bool ok = r[d] >= 0;  // (uniform)
-            const float *a = stage + (d0 + d) * GT_HEADS;
-            if (one_head) {
-                const float a0 = a[lc.hk[0]];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = ok ? fmaf(a0, x[d][k], acc[k]) : acc[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] = ok ? fmaf(a[lc.hk[k]], x[d][k], acc[k]) : acc[k];
-            }
-        }
-    }
-}
-// the chains of the lane's four columns over the `cnt` entries of a chunk, in entry order: batches of GT_DEPTH, a shorter tail in
-// batches of 8, 4, 2, 1
-template <bool VEC>
-__device__ __forceinline__ void gt_chains(const global_ptr<const float> x_base, const int64_t ld, const gt_lane_cols &lc, const bool one_head, const int src,
-                                          const int cnt, const float *stage, float (&acc)[4]) {
-    int d0 = 0;
-    for (; d0 + GT_DEPTH <= cnt; d0 += GT_DEPTH) gt_batch<GT_DEPTH, VEC>(x_base, ld, lc, one_head, src, d0, stage, acc);
-    if (GT_DEPTH > 8 && d0 + 8 <= cnt) gt_batch<8, VEC>(x_base, ld, lc, one_head, src, d0, stage, acc), d0 += 8;
-    if (GT_DEPTH > 4 && d0 + 4 <= cnt) gt_batch<4, VEC>(x_base, ld, lc, one_head, src, d0, stage, acc), d0 += 4;
-    if (GT_DEPTH > 2 && d0 + 2 <= cnt) gt_batch<2, VEC>(x_base, ld, lc, one_head, src, d0, stage, acc), d0 += 2;
-    if (d0 + 1 <= cnt) gt_batch<1, VEC>(x_base, ld, lc, one_head, src, d0, stage, acc);
-}
-
-// what every kernel reads of a job first (wave-uniform): false = the job is outside the limits and is left untouched
-struct gt_shape {
-    int n, heads, w, cols, nnz;
-};
-__device__ __forceinline__ bool gt_job_shape(const desc_ptr<wdg_gat_job> job, const int max_rows, gt_shape &s) {
-    s.n = min(job->n, max_rows), s.heads = job->heads, s.w = job->w, s.nnz = job->nnz;
-    s.cols = s.heads * s.w;
-    return s.heads >= 1 && s.heads <= GT_HEADS && s.w >= 1 && s.cols <= WDG_GAT_MAX_COLS && s.nnz >= 0 && job->n >= 0;
-}
-// the extent of row `row` of a CSR: false = it lies outside [0, nnz] (the row is left untouched)
-__device__ __forceinline__ bool gt_extent(const int32_t *rowptr_, const int row, const int nnz, int &beg, int &end) {
-    const global_ptr<const int32_t> rowptr = to_global(rowptr_);
-    beg = __builtin_amdgcn_readfirstlane(rowptr[row]);
-    end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-    return beg >= 0 && beg <= end && end <= nnz;
-}
 
 __global__ __launch_bounds__(64 * GT_WAVES) void gat_forward_kernel(const wdg_gat_job *__restrict__ jobs, const int max_rows) {
     __shared__ float stage_all[GT_WAVES][64 * GT_HEADS];
@@ -252,11 +125,6 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_forward_kernel(const wdg_ga
         gt_store4(to_global(job->out) + static_cast<int64_t>(i) * job->ld_out + lc.c0, gt_wave_vec(job->out, job->ld_out, s.cols), lc.live, acc);
 }
 
-__device__ __forceinline__ bool gt_has_backward(const desc_ptr<wdg_gat_job> job, const int nnz) {
-    return job->rowptr && job->t_rowptr && job->H && job->S && job->d_out && job->d_H && job->d_S &&
-           (nnz == 0 || (job->col && job->t_col && job->t_pos && job->alpha && job->d_pre));
-}
-
 // the row pass: d_pre[p, h] and d_S[i, h]
 __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_rows_kernel(const wdg_gat_job *__restrict__ jobs, const int max_rows) {
     __shared__ __attribute__((aligned(16))) float g_all[GT_WAVES][WDG_GAT_MAX_COLS];
@@ -275,19 +143,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_rows_kernel(const 
     const global_ptr<float> d_pre = to_global(job->d_pre);
     const int64_t ld_s = job->ld_s, ld_h = job->ld_h;
     float *g = g_all[wave];
-    {  // g = d_out[i, :] into LDS, +0 past the job's columns
-        const gt_lane_cols lc = gt_columns(lane, heads, w);
-        float x[4] = {0.f, 0.f, 0.f, 0.f};
-        const global_ptr<const float> gi = to_global(job->d_out) + static_cast<int64_t>(i) * job->ld_d_out + lc.c0;
-        if (lc.live > 0) {
-            if (gt_wave_vec(job->d_out, job->ld_d_out, cols))
-                gt_load4<true>(gi, lc.live, x);
-            else
-                gt_load4<false>(gi, lc.live, x);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g[4 * lane + k] = k < lc.live ? x[k] : 0.f;
-    }
+    gt_stage_d_out(job, s, i, lane, g);  // g = d_out[i, :] into LDS, +0 past the job's columns
     gt_wave_sync();
     // dalpha[p, h] = one fmaf chain over k ascending from +0, parked in d_pre[]: a lane per entry reads its neighbour's row
     const bool vec_h = gt_wave_vec(job->H, ld_h, cols);
@@ -377,7 +233,9 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_rows_kernel(const 
         }
 }
 
-// the pass over the transposed pattern: d_H[j, :] and d_S[j, heads + h]
+// the pass over the transposed pattern: d_H[j, :] and d_S[j, heads + h].  signed_att.hip runs the same pass as gt_transposed_row of
+// gat_lanes.h; here it stays written out: called through that function the compiler ends at 82 registers instead of 80 - five waves
+// per SIMD instead of six - and this kernel is to compile to the code it had.  A change to one is a change to the other.
 __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_cols_kernel(const wdg_gat_job *__restrict__ jobs, const int max_rows) {
     __shared__ float stage_all[GT_WAVES][64 * GT_HEADS];
     const desc_ptr<wdg_gat_job> job = (desc_ptr<wdg_gat_job>)(jobs + blockIdx.z);
@@ -480,12 +338,7 @@ __global__ __launch_bounds__(256) void csr_transpose_positions_kernel(const int3
     if (count) atomicAdd(bad, count);
 }
 
-int gt_check(const char *what, const wdg_gat_job *jobs, int32_t n_jobs, int32_t max_rows) {
-    WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= GT_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, GT_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
-}
+int gt_check(const char *what, const wdg_gat_job *jobs, int32_t n_jobs, int32_t max_rows) { return gt_check_table(what, jobs, n_jobs, max_rows); }
 
 }  // namespace
 

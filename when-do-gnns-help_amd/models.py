@@ -21,6 +21,11 @@ gnns_on_syn.py:58-104 and gnns_on_syn.py:159-206 but ships none) and is not clai
 GAT-1 / GAT-2 (`GAT1`, `GAT2`) replace the fixed weights of the aggregation (normalize_tensor, utils/util_funcs.py:365-381)
 by a softmax weight per stored entry: out_i = sum_j alpha_ij H_j on csrc/gat.hip, forward and backward; the scores are a product on
 csrc/gemm.hip.  Defined by this project as well, as the attention baseline beside the tables of gnns_on_syn.py:1-154.
+
+FAGCN-1 / FAGCN-2 (`FAGCN1`, `FAGCN2`) take the other standard answer to a low-pass average: a weight learnt per stored entry
+that may be NEGATIVE - tanh of the score where GAT has the softmax, times the fixed scales of the NormAdj they are given (Bo et al.,
+"Beyond Low-frequency Information in Graph Convolutional Networks") - plus eps times a residual, on csrc/signed_att.hip, forward and
+backward; the scores are the same product on csrc/gemm.hip.  Defined by this project as well.
 """
 import torch
 
@@ -477,6 +482,128 @@ class GAT2(torch.nn.Module):
             self.train(was_training)
         n, dev = x.shape[0], self.w0.device
         return self._att0.alpha(adj, n, self.w0.shape[1], dev), self._att1.alpha(adj, n, self.w1.shape[1], dev)
+
+
+class _SignedAttLayer(_GatLayer):
+    """One signed-attention layer eps R + FA(H; a) on a one-job ops.SignedAttBatch, with the pattern AND the two scale vectors of the
+    NormAdj it is given: _GatLayer's buffers, table per (graph, rows, cols) built on first use - before any capture -, `version` rule and
+    score operand; the residual R has a buffer of its own (R may be H itself: the kernel's operands do not overlap)."""
+
+    def __init__(self, heads, eps):
+        super().__init__(heads, 0.0)
+        self.eps = float(eps)
+
+    def table(self, adj, rows, cols, dev):
+        plan = adj.attention_plan()
+        key = (id(plan), rows, cols)
+        if key not in self._tables:
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            b = dict(h=z(rows, cols), s=z(rows, 2 * self.heads), res=z(rows, cols), out=z(rows, cols), d_out=z(rows, cols), d_h=z(rows, cols),
+                     d_s=z(rows, 2 * self.heads))
+            entry = dict(plan, heads=self.heads, row_scale=adj.row_scale, col_scale=adj.col_scale, **b)
+            self._tables[key] = (b, ops.SignedAttBatch([entry], self.eps), plan, adj)  # (plan, adj: kept alive with the id and the scales)
+        return self._tables[key][:2]
+
+    def run(self, h, s, res, adj):
+        b, table = self.table(adj, h.shape[0], h.shape[1], h.device)
+        b["h"].copy_(h)
+        b["s"].copy_(s)
+        b["res"].copy_(res)
+        table.launch()
+        self.version += 1
+        return b, table
+
+    def __call__(self, adj, h, att, res):
+        """h, res [n, heads w] -> eps res + FA(h; att) [n, heads w]; the scores are a product on the GEMM, as in _GatLayer"""
+        s = _Linear.apply(h, self.operand(att), False)
+        return _SignedAttAggregate.apply(h, s, res, adj, self)
+
+
+class _SignedAttAggregate(torch.autograd.Function):
+    """out_i = eps res_i + sum_j a_ij H_j (include/wdg.h: wdg_signed_att_forward_batched_f32) and its backward pass, both on
+    csrc/signed_att.hip; the residual's gradient eps d_out is formed here (the kernels do not write it)"""
+
+    @staticmethod
+    def forward(ctx, h, s, res, adj, layer):
+        b, _ = layer.run(h, s, res, adj)
+        ctx.save_for_backward(h, s, res)
+        ctx.adj, ctx.layer, ctx.version = adj, layer, layer.version
+        return b["out"].clone()
+
+    @staticmethod
+    def backward(ctx, gy):
+        layer = ctx.layer
+        if layer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
+            b, table = layer.run(*ctx.saved_tensors, ctx.adj)
+        else:
+            b, table = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
+        b["d_out"].copy_(gy)
+        table.launch_backward()
+        return b["d_h"].clone(), b["d_s"].clone(), (gy * layer.eps if ctx.needs_input_grad[2] else None), None, None
+
+
+def _signed_weights_of(model, layers, adj, x, cols):
+    """the alpha of every layer of `layers` after an evaluation forward pass of `model` on (adj, x), run here (the mode is put back)"""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            model(adj, x)
+    finally:
+        model.train(was_training)
+    return tuple(layer.alpha(adj, x.shape[0], cols, x.device) for layer in layers)
+
+
+class FAGCN1(torch.nn.Module):
+    """FAGCN-1: Z = X W, logits = eps Z + FA_1(Z; a) - one signed-attention layer of one head of width C, bias-free, on the pattern and
+    the scales of the NormAdj it is given (recommended: NormAdj(adj, symmetric=1, add_self_loops=False) - the paper's d_i^-1/2 d_j^-1/2
+    without self loops: eps Z is the node's own share); DESIGN 4.27.  Parameters in the draw order of _gat_parameters: W, then a."""
+
+    def __init__(self, nfeat, nclass, eps=0.3):
+        super().__init__()
+        self.weight, self.att = _gat_parameters(nfeat, 1, nclass)
+        self._att = _SignedAttLayer(1, eps)
+
+    def forward(self, adj, x):
+        z = _Linear.apply(x, self.weight, False)
+        return self._att(adj, z, self.att, z)
+
+    def signed_weights(self, adj, x):
+        """-> (alpha [nnz, 1],): the signed weights of adj.graph's stored entries, in their order, of an evaluation forward pass"""
+        return _signed_weights_of(self, [self._att], adj, x, self.weight.shape[1])
+
+
+class FAGCN2(torch.nn.Module):
+    """FAGCN-2: H0 = relu_dropout(X W0), H_l = eps H0 + FA_1(H_{l-1}; a_l) for l = 1..layers, logits = H_L W1; bias-free, one head of
+    width nhid, feature dropout only (GCN2's two routes: dropout_rng None - torch's - or a DeviceDropout); no dropout on the weights, eps
+    is not learnt.  DESIGN 4.27.  Parameters are drawn in this order: W0 (xavier_uniform, [nfeat, nhid]), then a_1 .. a_layers
+    ([2, 1, nhid] = [a_dst, a_src] each, uniform in +- 1 / sqrt(nhid): _gat_parameters' rule), then W1 (xavier_uniform, [nhid, nclass])."""
+
+    def __init__(self, nfeat, nclass, nhid=64, layers=2, eps=0.3, dropout=0.5, dropout_rng=None):
+        super().__init__()
+        if layers < 1:
+            raise ValueError(f"FAGCN2: {layers} layers; at least one expected")
+        self.w0, first = _gat_parameters(nfeat, 1, nhid)
+        rest = [torch.nn.Parameter((torch.rand(2, 1, nhid) * 2 - 1) / nhid ** 0.5) for _ in range(layers - 1)]
+        self.att = torch.nn.ParameterList([first] + rest)
+        self.w1 = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nhid, nclass)))
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._att = [_SignedAttLayer(1, eps) for _ in range(layers)]
+
+    def forward(self, adj, x):
+        if self.dropout_rng is not None:
+            h0 = self.dropout_rng.relu_dropout(_Linear.apply(x, self.w0, False), self.dropout, self.training)
+        else:
+            h0 = torch.nn.functional.dropout(_Linear.apply(x, self.w0, True), self.dropout, self.training)
+        h = h0
+        for layer, att in zip(self._att, self.att):
+            h = layer(adj, h, att, h0)
+        return _Linear.apply(h, self.w1, False)
+
+    def signed_weights(self, adj, x):
+        """-> (alpha of layer 1, ..., alpha of layer L), [nnz, 1] each, of an evaluation forward pass on (adj, x), run here (the model's
+        mode is put back): the signed weights of adj.graph's stored entries, in their order"""
+        return _signed_weights_of(self, self._att, adj, x, self.w0.shape[1])
 
 
 def graphed_inference(model, adj, x, **forward_kwargs):

@@ -7,6 +7,8 @@
 - csrc/acm_mix_packed.hip: the same for the stacked class-width layers of acm_split_train, several replicas per 16 lanes
 - csrc/gat.hip: the graph-attention layer of many graphs (GAT-1, GAT-2: a softmax weight per stored entry) with its backward pass
 - csrc/gat_scores.hip: the scores of stacked attention layers, S = H blockdiag(a_dst, a_src) without the operand, with their backward pass
+- csrc/signed_att.hip: the signed-attention layer of many graphs (FAGCN-1, FAGCN-2: a tanh weight per stored entry, times the fixed scales)
+  with its backward pass
 - csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
 - csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
@@ -33,6 +35,7 @@ _ACM_JOB_DTYPE = np.dtype(_lib.AcmMixJob)
 _ACM_PACKED_JOB_DTYPE = np.dtype(_lib.AcmPackedJob)
 _GAT_JOB_DTYPE = np.dtype(_lib.GatJob)
 _GAT_SCORES_JOB_DTYPE = np.dtype(_lib.GatScoresJob)
+_SIGNED_ATT_JOB_DTYPE = np.dtype(_lib.SignedAttJob)
 _XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
 _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
 _KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
@@ -306,6 +309,9 @@ class GatBatch(JobTable):
     MAX_JOBS, MAX_HEADS, MAX_COLS = 65535, 8, 256
     _KEYS = ("graph", "graph_t", "t_pos", "h", "s", "out", "heads", "d_out", "d_h", "d_s")
     _BACKWARD = ("graph_t", "t_pos", "d_out", "d_h", "d_s")
+    _VECTORS = ()   # further operands of an entry, optional: [n] vectors ...
+    _INPUTS = ()    # ... and [n, heads w] matrices the kernel only reads (SignedAttBatch has both kinds)
+    _RECORD, _ENTRIES = _GAT_JOB_DTYPE, ("wdg_gat_forward_batched_f32", "wdg_gat_backward_batched_f32", "wdg_gat_check_jobs")
 
     def __init__(self, entries, slope=0.2):
         """entries: list of dicts - graph: a square CsrGraph (its pattern is used; columns strictly ascending inside a row), heads (int,
@@ -323,7 +329,17 @@ class GatBatch(JobTable):
             raise ValueError(f"{name}: one slope per entry")
         if not all(v >= 0.0 for v in slopes):  # (a NaN fails the comparison)
             raise ValueError(f"{name}: a slope >= 0 expected, got {slope!r}")
-        self.slopes, self.has_backward = slopes, n_jobs > 0
+        self.slopes = slopes
+        tab = self._attention_records(entries)
+        tab["slope"] = slopes
+        self._close(tab, self._ENTRIES[2])
+
+    def _attention_records(self, entries):
+        """what the attention tables (this one and SignedAttBatch) share, after _open and the checks of the table's own settings: the
+        checks of the entries - none needs a device -, then the device, the records with everything an attention job of either
+        kind has, and the table's own alpha and d_pre -> the records"""
+        name, n_jobs = type(self).__name__, self.n_jobs
+        self.has_backward = n_jobs > 0
         shapes = []
         for e in entries:
             unknown = set(e) - set(self._KEYS)
@@ -344,9 +360,13 @@ class GatBatch(JobTable):
                 raise ValueError(f"{name}: graph_t, t_pos, d_out, d_h and d_s come together or not at all")
             self.has_backward = self.has_backward and bool(given)
             n = g.n_rows
-            mats = {k: e[k] for k in ("h", "s", "out", "d_out", "d_h", "d_s") if e.get(k) is not None}
+            mats = {k: e[k] for k in ("h", "s", "out", "d_out", "d_h", "d_s") + self._INPUTS if e.get(k) is not None}
             for k, t in mats.items():
-                self._matrix(k, t, (n, 2 * heads if k in ("s", "d_s") else cols))
+                self._matrix(k, t, (n, 2 * heads if k in ("s", "d_s") else cols), name)
+            for k in self._VECTORS:
+                t = e.get(k)
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+                    raise ValueError(f"{name}: {k} must be a contiguous [n = {n}] fp32 vector")
             if given:
                 gt, t_pos = e["graph_t"], e["t_pos"]
                 if (gt.n_rows, gt.n_cols, gt.nnz) != (n, n, g.nnz):
@@ -359,9 +379,9 @@ class GatBatch(JobTable):
                     if (ka in ("out", "d_h", "d_s") or kb in ("out", "d_h", "d_s")) and _views_may_overlap(ta, tb):
                         raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
             shapes.append((n, heads, cols // heads, g.nnz))
-        tab = self._records(_GAT_JOB_DTYPE)
+        tab = self._records(self._RECORD)
         for e in entries:
-            tensors = [e[k] for k in ("h", "s", "out", "d_out", "d_h", "d_s", "t_pos") if e.get(k) is not None]
+            tensors = [e[k] for k in ("h", "s", "out", "d_out", "d_h", "d_s", "t_pos") + self._INPUTS + self._VECTORS if e.get(k) is not None]
             tensors += [t for g in (e["graph"], e.get("graph_t")) if g is not None for t in (g.rowptr, g.col)]
             if any(t.device != self._dev for t in tensors):
                 raise ValueError(f"{name}: every tensor of an entry must live on the device {self._dev}")
@@ -379,9 +399,8 @@ class GatBatch(JobTable):
             self._point(tab, field, [e.get(key) for e in entries], ld=ld)
         for k, field in enumerate(("n", "heads", "w", "nnz")):
             tab[field] = [s_[k] for s_ in shapes]
-        tab["slope"] = slopes
         self.max_rows = int(tab["n"].max(initial=0))
-        self._close(tab, "wdg_gat_check_jobs")
+        return tab
 
     @staticmethod
     def _matrix(name, t, shape, table="GatBatch"):
@@ -393,13 +412,48 @@ class GatBatch(JobTable):
 
     def launch(self):
         """out and alpha of every entry"""
-        self._launch("wdg_gat_forward_batched_f32", self.max_rows)
+        self._launch(self._ENTRIES[0], self.max_rows)
 
     def launch_backward(self):
         """d_h and d_s of every entry from d_out, h, s and the alpha of the last launch()"""
         if not self.has_backward and self.n_jobs:
-            raise ValueError("GatBatch.launch_backward: the table was built without gradient tensors")
-        self._launch("wdg_gat_backward_batched_f32", self.max_rows)
+            raise ValueError(f"{type(self).__name__}.launch_backward: the table was built without gradient tensors")
+        self._launch(self._ENTRIES[1], self.max_rows)
+
+
+class SignedAttBatch(GatBatch):
+    """Job table for wdg_signed_att_forward_batched_f32 / wdg_signed_att_backward_batched_f32 (csrc/signed_att.hip): one signed-attention
+    (FAGCN) layer per entry - out[i, h w + k] = eps res[i, h w + k] + sum_p alpha[p, h] H[col[p], h w + k] over row i's stored entries,
+    alpha[p, h] = tanh(S[i, h] + S[col[p], heads + h]) row_scale[i] col_scale[col[p]]: a weight that may be negative (include/wdg.h
+    states it and every sum's order; tests/_signed_att_ref.py restates it in numpy) - and its backward pass, a whole table per launch.
+    An attention table like GatBatch: the same entries, checks and own buffers (alpha_of[i]: the SIGNED weights that were applied)."""
+
+    _KEYS = GatBatch._KEYS + ("row_scale", "col_scale", "res")
+    _VECTORS, _INPUTS = ("row_scale", "col_scale"), ("res",)
+    _RECORD = _SIGNED_ATT_JOB_DTYPE
+    _ENTRIES = ("wdg_signed_att_forward_batched_f32", "wdg_signed_att_backward_batched_f32", "wdg_signed_att_check_jobs")
+
+    def __init__(self, entries, eps=0.0):
+        """entries: GatBatch's - graph, heads, h, s, out and, for launch_backward(), graph_t, t_pos, d_out, d_h, d_s all together or not
+           at all - and, each optional: row_scale and col_scale (contiguous [n] fp32: the two vectors a models.NormAdj holds; None = 1),
+           res [n, heads w] (the residual; None = none).
+           eps: the residual's factor, for every entry (one number, or one per entry), finite.  The residual's gradient, eps * d_out, is
+           the caller's.
+        Raises ValueError for what GatBatch refuses, and for an eps that is infinite or a NaN."""
+        name = "SignedAttBatch"
+        n_jobs = self._open(entries)
+        epss = [float(eps)] * n_jobs if np.ndim(eps) == 0 else [float(v) for v in eps]
+        if len(epss) != n_jobs:
+            raise ValueError(f"{name}: one eps per entry")
+        if not all(math.isfinite(v) for v in epss):
+            raise ValueError(f"{name}: a finite eps expected, got {eps!r}")
+        self.eps = epss
+        tab = self._attention_records(entries)
+        for k in self._VECTORS:
+            self._point(tab, k, [e.get(k) for e in entries])
+        self._point(tab, "res", [e.get("res") for e in entries], ld="ld_res")
+        tab["eps"] = epss
+        self._close(tab, self._ENTRIES[2])
 
 
 class GatScoresBatch(JobTable):
