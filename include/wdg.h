@@ -1858,6 +1858,87 @@ int wdg_signed_att_backward_batched_f32(const wdg_signed_att_job *jobs_dev, int3
 /* replaces: nothing of its own - the per-job refusals of the layer above (utils/util_funcs.py:365-381), on the host's table */
 int wdg_signed_att_check_jobs(const wdg_signed_att_job *jobs_host, int32_t n_jobs);
 
+/*
+ * A polynomial graph filter of many graphs in one launch (the propagation of GPR-GNN: Chien et al., "Adaptive Universal Generalized
+ * PageRank Graph Neural Network"; with frozen coefficients, APPNP): out = sum_{k = 0..K} gamma_k A_hat^k v at class width, all K hops
+ * of a few columns inside ONE workgroup, T_k and T_{k+1} of those columns in LDS.  The reference ships no model code: the filter is
+ * DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: the ONE fixed aggregation of normalize_tensor / the SGC and GCN tables (utils/util_funcs.py:365-381, gnns_on_syn.py:1-154)
+ *           by K of them with a learnt weight per hop, for the baseline that stands beside those tables.
+ * A job: the square CSR pattern rowptr int32 [n + 1], col int32 [nnz], its values val [nnz] or NULL (NULL = 1: a binary adjacency),
+ * row_scale [n] or NULL and col_scale [n] or NULL (NULL = 1: the two vectors of a factored A_hat = diag(r) A diag(c)), v and out
+ * [n, cols] with unit inner stride and leading dimensions ld_v, ld_out (column slices of wider matrices are passed in place), order K in 0..64, gamma [K + 1, n_seg] in
+ * DEVICE memory with leading dimension ld_gamma, seg_cols >= 1 with cols = n_seg * seg_cols: segment s is the columns
+ * s seg_cols .. (s + 1) seg_cols - 1 and has the coefficients gamma[:, s].  Optionally - both or neither - u [n, cols] (ld_u) and
+ * dots [K + 1, n_seg] (ld_dots), with the workspace partials (wdg_poly_filter_partials_len doubles).  group_cols in {1, 2, 4}.
+ * The definition, for column c of segment s, row i with the stored entries p = beg .. end - 1, j = col[p]:
+ *   T_0 = v
+ *   a row of at most WDG_POLY_FILTER_LONG_ROW entries has L = WDG_POLY_FILTER_TEAM = 4 lanes, a longer one L = 64.  Lane l of the L
+ *   adds the entries beg + l, beg + l + L, ... in ascending order in ONE fmaf chain from +0: acc = fmaf(coef_p, T_k[j, c], acc), coef_p = val[p] * col_scale[j] -
+ *   ONE fp32 product; a NULL factor is 1.0f and the product then exact -;
+ *   then the butterfly acc = acc + (the acc of lane l ^ d) over the lane distances d = L/2, L/4, ..., 1; then
+ *   T_{k+1}[i, c] = row_scale[i] * sum (a NULL row_scale: 1.0f - the product is exact).  An empty row gives row_scale[i] * +0.
+ *   out[i, c] = gamma[0, s] * v[i, c], then for k = 1..K in ascending order out[i, c] = fmaf(gamma[k, s], T_k[i, c], out[i, c]).
+ *   dots[k, s] = sum over the rows and the segment's columns of T_k[i, c] * u[i, c]: every product formed in fp64 (exact); per column
+ *   and per block of WDG_POLY_FILTER_DOT_ROWS consecutive rows one fp64 sum from +0 over ascending rows; a column's blocks added in
+ *   ascending order from +0; the segment's columns added in ascending order from +0; rounded to fp32 ONCE.
+ * So the order of every chain and sum is a function of the row's length and of compile-time constants alone - never of the table, of
+ * group_cols or of the columns that share a workgroup.  What follows, and what tests/test_gpu_poly_filter.py checks: a job has the same
+ * bits alone and inside any table; a column has the same bits for group_cols 1, 2 and 4 and the bits of a one-segment job on its column
+ * slice (dots: a segment's); order 0 gives exactly gamma[0, s] * v; columns outside a view are never written; all-zero input gives a
+ * zero - +0 in every bit unless EVERY coefficient of the segment is negative: gamma[0, s] * +0 is then -0 and stays -0.
+ * T_k is not exposed; a job whose gamma[:, s] is the unit vector e_k returns exactly T_k in segment s (fmaf(1, T_k, +-0)), which is how
+ * the tests compare dots for EQUAL BITS with the numpy restatement (tests/_poly_filter_ref.py).
+ * No floating-point atomic anywhere; csrc/poly_filter.hip is compiled with contraction off and writes every fmaf out.
+ * Shape: grid (column groups, jobs), 1024 threads.  A group is up to group_cols consecutive columns of ONE segment (seg_cols 5 with
+ * group_cols 4: groups of 4 and 1); its workgroup holds T_k and T_{k+1} in 2 * n * group_cols * 4 bytes of LDS for all K hops -
+ * gathers come from LDS, indices and scales from global memory on every hop, workgroup barriers between hops, no grid-wide
+ * synchronisation.  Every team of 4 lanes (wave, for the long rows) owns the same rows on every hop and accumulates out where it lives.
+ * Limit: 2 * n * group_cols * 4 <= WDG_POLY_FILTER_LDS_BYTES (160 KiB less 256 bytes kept free, as csrc/spmm.hip keeps them; the
+ * kernel has no other scratch): n <= wdg_poly_filter_max_rows(group_cols) = 20448, 10224, 5112.
+ * max_groups: the table's largest count of column groups (n_seg * ceil(seg_cols / group_cols)); max_floats: its largest
+ * n * group_cols, which sizes the launch's LDS - the launch geometry cannot be read out of a table in device memory.  A job beyond
+ * either is left untouched, and so is one that is malformed.  An entry whose column lies outside [0, n) is skipped, never read
+ * through; a row whose extent lies outside [0, nnz] counts as empty.
+ * wdg_poly_filter_batched_f32 is one launch, and a second small one (a workgroup per job and k adds the partials) when
+ * max_dot_rows != 0: the largest order + 1 of the jobs that have dots (0: none has).  Refused before any launch (WDG_ERR_INVALID): a
+ * NULL table with n_jobs > 0, negative counts, more than 65535 jobs, max_floats beyond the limit, max_dot_rows beyond 65.  n_jobs == 0:
+ * WDG_OK, nothing is launched; max_groups == 0 or max_floats == 0: the filter's launch is left out (the dots of empty jobs are still written).  What
+ * is wrong inside a job - order outside 0..64, seg_cols < 1 or cols no multiple of it, u without dots or dots without u or either
+ * without partials, group_cols not in {1, 2, 4}, a negative n, nnz or cols, a NULL rowptr, v, out or gamma, a NULL col with nnz > 0,
+ * a leading dimension below its row - is refused by wdg_poly_filter_check_jobs on the HOST copy of the table (train.PolyFilterBatch
+ * calls it before it uploads), and so is n over the limit of its group_cols, as WDG_ERR_UNSUPPORTED with the limit in the message.  A job with
+ * n == 0 or cols == 0 is skipped (its dots are written +0).
+ */
+#define WDG_POLY_FILTER_MAX_ORDER 64
+#define WDG_POLY_FILTER_TEAM 4
+#define WDG_POLY_FILTER_LONG_ROW 128
+#define WDG_POLY_FILTER_DOT_ROWS 32
+#define WDG_POLY_FILTER_LDS_BYTES (160 * 1024 - 256)
+typedef struct wdg_poly_filter_job {
+    const int32_t *rowptr;    /* [n + 1] */
+    const int32_t *col;       /* [nnz] */
+    const float *val;         /* [nnz], or NULL = 1 */
+    const float *row_scale;   /* [n], or NULL = 1 */
+    const float *col_scale;   /* [n], or NULL = 1 */
+    const float *v;           /* [n, cols] */
+    float *out;               /* [n, cols] */
+    const float *gamma;       /* [order + 1, n_seg], device memory */
+    const float *u;           /* [n, cols], or NULL: no dots */
+    float *dots;              /* [order + 1, n_seg], or NULL */
+    double *partials;         /* workspace of wdg_poly_filter_partials_len doubles, with dots */
+    int64_t ld_v, ld_out, ld_gamma, ld_u, ld_dots;
+    int32_t n, nnz, cols, seg_cols, order, group_cols;
+} wdg_poly_filter_job;
+int wdg_poly_filter_batched_f32(const wdg_poly_filter_job *jobs_dev, int32_t n_jobs, int32_t max_groups, int32_t max_floats, int32_t max_dot_rows,
+                                wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the filter above (utils/util_funcs.py:365-381), on the host's table */
+int wdg_poly_filter_check_jobs(const wdg_poly_filter_job *jobs_host, int32_t n_jobs);
+/* the largest n of a job with this group_cols (host only); 0 for a group_cols outside {1, 2, 4} */
+int32_t wdg_poly_filter_max_rows(int32_t group_cols);
+/* the doubles of a job's workspace: (order + 1) * cols * (ceil(n / WDG_POLY_FILTER_DOT_ROWS) + 1); 0 for a negative argument */
+int64_t wdg_poly_filter_partials_len(int32_t n, int32_t cols, int32_t order);
+
 #ifdef __cplusplus
 }
 #endif

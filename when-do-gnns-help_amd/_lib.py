@@ -197,6 +197,10 @@ SIGNATURES = {
     "wdg_signed_att_forward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_signed_att_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_signed_att_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_poly_filter_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_poly_filter_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_poly_filter_max_rows": (c_int32, [c_int32]),
+    "wdg_poly_filter_partials_len": (c_int64, [c_int32, c_int32, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -419,6 +423,13 @@ class SignedAttJob(ctypes.Structure):
                                               "row_scale", "col_scale", "res")] + \
                [(name, c_int64) for name in ("ld_h", "ld_s", "ld_out", "ld_d_out", "ld_d_h", "ld_d_s", "ld_res")] + \
                [(name, c_int32) for name in ("n", "heads", "w", "flags")] + [("eps", ctypes.c_float), ("nnz", c_int32)]
+
+
+class PolyFilterJob(ctypes.Structure):
+    """mirror of `wdg_poly_filter_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "val", "row_scale", "col_scale", "v", "out", "gamma", "u", "dots", "partials")] + \
+               [(name, c_int64) for name in ("ld_v", "ld_out", "ld_gamma", "ld_u", "ld_dots")] + \
+               [(name, c_int32) for name in ("n", "nnz", "cols", "seg_cols", "order", "group_cols")]
 
 
 if not os.path.exists(LIB_PATH):

@@ -26,6 +26,11 @@ FAGCN-1 / FAGCN-2 (`FAGCN1`, `FAGCN2`) take the other standard answ
 that may be NEGATIVE - tanh of the score where GAT has the softmax, times the fixed scales of the NormAdj they are given (Bo et al.,
 "Beyond Low-frequency Information in Graph Convolutional Networks") - plus eps times a residual, on csrc/signed_att.hip, forward and
 backward; the scores are the same product on csrc/gemm.hip.  Defined by this project as well.
+
+GPR-GNN-1 / GPR-GNN-2 (`GPRGNN1`, `GPRGNN2`) put a learnt polynomial of the fixed aggregation behind the transform:
+logits = sum_k gamma_k A_hat^k H0 with K + 1 coefficients that may turn negative (Chien et al., "Adaptive Universal Generalized PageRank
+Graph Neural Network"; frozen coefficients: APPNP) - all K hops in one launch of csrc/poly_filter.hip, the backward pass one more launch
+of the same kernel on the transposed pattern.  Defined by this project as well.
 """
 import torch
 
@@ -604,6 +609,142 @@ class FAGCN2(torch.nn.Module):
         """-> (alpha of layer 1, ..., alpha of layer L), [nnz, 1] each, of an evaluation forward pass on (adj, x), run here (the model's
         mode is put back): the signed weights of adj.graph's stored entries, in their order"""
         return _signed_weights_of(self, self._att, adj, x, self.w0.shape[1])
+
+
+def ppr_coefficients(K, alpha):
+    """The personalised-PageRank coefficients GPR-GNN starts from and APPNP keeps: gamma_k = alpha (1 - alpha)^k for k < K and
+    gamma_K = (1 - alpha)^K - they sum to 1 -> a float32 tensor [K + 1]"""
+    if K < 0 or not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"ppr_coefficients: K >= 0 and alpha in [0, 1] expected, got K = {K}, alpha = {alpha}")
+    k = torch.arange(K + 1, dtype=torch.float64)
+    g = alpha * (1.0 - alpha) ** k
+    g[K] = (1.0 - alpha) ** K
+    return g.to(torch.float32)
+
+
+class _PolyFilterLayer:
+    """The filter F(H0; gamma) = sum_k gamma_k A_hat^k H0 on two one-job ops.PolyFilterBatch tables over work buffers, per (graph, rows,
+    cols), built on first use - before any capture.  The forward table runs the pattern with the NormAdj's scales; the backward table is
+    ONE more job of the same kernel on graph_t with the two scales swapped, v = d_out and u = H0: its out is d_H0 and its dots are
+    d_gamma, because d_gamma_k = <d_out, A_hat^k H0> = <(A_hat^T)^k d_out, H0>.  _GatLayer's `version` rule: the buffers hold the
+    operands of the latest forward pass, and an eager backward pass that finds another one in between puts its own back first.
+    max_rows: the largest graph that takes the fused route (None: what one column of the kernel holds); a larger one, or fused=False,
+    runs hop by hop - K _Aggregate steps and torch adds, autograd's backward."""
+
+    def __init__(self, order, fused=True, max_rows=None):
+        if not 0 <= order <= ops.PolyFilterBatch.MAX_ORDER:
+            raise ValueError(f"a polynomial filter of order {order}: the kernel runs 0..{ops.PolyFilterBatch.MAX_ORDER} hops")
+        self.order, self.fused, self.max_rows = int(order), bool(fused), max_rows
+        self._tables = {}
+        self.version = 0
+
+    def is_fused(self, rows):
+        limit = ops.PolyFilterBatch.max_rows(1) if self.max_rows is None else min(int(self.max_rows), ops.PolyFilterBatch.max_rows(1))
+        return self.fused and rows <= limit
+
+    def table(self, adj, rows, cols, dev):
+        key = (id(adj), rows, cols)
+        if key not in self._tables:
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            b = dict(h=z(rows, cols), out=z(rows, cols), gamma=z(self.order + 1, 1), d_out=z(rows, cols), d_h=z(rows, cols), d_gamma=z(self.order + 1, 1))
+            fwd = ops.PolyFilterBatch([dict(graph=adj.graph, row_scale=adj.row_scale, col_scale=adj.col_scale, v=b["h"], out=b["out"], gamma=b["gamma"],
+                                            order=self.order)])
+            bwd = ops.PolyFilterBatch([dict(graph=adj.graph_t, row_scale=adj.col_scale, col_scale=adj.row_scale, v=b["d_out"], out=b["d_h"],
+                                            gamma=b["gamma"], order=self.order, u=b["h"], dots=b["d_gamma"])])  # (R A C)^T = C A^T R
+            self._tables[key] = (b, fwd, bwd, adj)  # (adj: kept alive with its id and its scales)
+        return self._tables[key][:3]
+
+    def stage(self, h, gamma, adj):
+        b, fwd, bwd = self.table(adj, h.shape[0], h.shape[1], h.device)
+        b["h"].copy_(h)
+        b["gamma"].copy_(gamma.reshape(-1, 1))
+        self.version += 1
+        return b, fwd, bwd
+
+    def __call__(self, adj, h, gamma):
+        if self.is_fused(h.shape[0]):
+            return _PolyFilter.apply(h, gamma, adj, self)
+        t, out = h, gamma[0] * h
+        for k in range(1, self.order + 1):
+            t = adj.matmul(t)
+            out = out + gamma[k] * t
+        return out
+
+
+class _PolyFilter(torch.autograd.Function):
+    """out = sum_k gamma_k A_hat^k H0 (include/wdg.h: wdg_poly_filter_batched_f32) and its backward pass, both on csrc/poly_filter.hip"""
+
+    @staticmethod
+    def forward(ctx, h, gamma, adj, layer):
+        b, fwd, _ = layer.stage(h, gamma, adj)
+        fwd.launch()
+        ctx.save_for_backward(h, gamma)
+        ctx.adj, ctx.layer, ctx.version = adj, layer, layer.version
+        return b["out"].clone()
+
+    @staticmethod
+    def backward(ctx, gy):
+        layer = ctx.layer
+        if layer.version != ctx.version:  # another forward pass has overwritten H0 and gamma since: put them back
+            b, _, bwd = layer.stage(*ctx.saved_tensors, ctx.adj)
+        else:
+            b, _, bwd = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
+        b["d_out"].copy_(gy)
+        bwd.launch()
+        return b["d_h"].clone(), (b["d_gamma"].reshape(-1).clone() if ctx.needs_input_grad[1] else None), None, None
+
+
+class _GPRBase(torch.nn.Module):
+    def _init_filter(self, order, alpha, learn, fused, fused_max_rows):
+        gamma = ppr_coefficients(order, alpha)
+        if learn:
+            self.gamma = torch.nn.Parameter(gamma)
+        else:
+            self.register_buffer("gamma", gamma)  # (frozen: no parameter, so no optimizer and no weight decay touches it)
+        self._filter = _PolyFilterLayer(order, fused, fused_max_rows)
+
+    def filter_coefficients(self):
+        """-> the current gamma [order + 1] as a host numpy array: the learnt filter, to be read off"""
+        return self.gamma.detach().cpu().numpy().copy()
+
+
+class GPRGNN1(_GPRBase):
+    """GPR-GNN-1: logits = F(X W; gamma), F(H0; gamma) = sum_{k = 0..order} gamma_k A_hat^k H0 - a learnt polynomial graph filter at class
+    width (Chien et al., "Adaptive Universal Generalized PageRank Graph Neural Network"); bias-free; DESIGN 4.28.  The coefficients may
+    become negative, so the model can turn itself into a high-pass or band-pass filter.  learn=False freezes gamma at
+    ppr_coefficients(order, alpha): that model is APPNP.  Recommended graph: NormAdj(adj, symmetric=1) with self loops; any NormAdj works.
+    fused=True: all hops in one launch of csrc/poly_filter.hip, forward and backward; fused=False, or a graph of more rows than the
+    kernel holds in LDS at one column (fused_max_rows lowers that limit), runs K aggregations hop by hop.
+    Parameters are drawn in this order: W (xavier_uniform, [nfeat, nclass]), then gamma (deterministic)."""
+
+    def __init__(self, nfeat, nclass, order=10, alpha=0.1, learn=True, fused=True, fused_max_rows=None):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nfeat, nclass)))
+        self._init_filter(order, alpha, learn, fused, fused_max_rows)
+
+    def forward(self, adj, x):
+        return self._filter(adj, _Linear.apply(x, self.weight, False), self.gamma)
+
+
+class GPRGNN2(_GPRBase):
+    """GPR-GNN-2: logits = F(relu_dropout(X W0) W1; gamma) with GPRGNN1's filter F; bias-free, feature dropout only (GCN2's two routes:
+    dropout_rng None - torch's - or a DeviceDropout), no dropout between the hops.  learn=False freezes gamma: APPNP.  DESIGN 4.28.
+    Parameters are drawn in this order: W0 (xavier_uniform, [nfeat, nhid]), W1 (xavier_uniform, [nhid, nclass]), then gamma
+    (deterministic)."""
+
+    def __init__(self, nfeat, nclass, nhid=64, order=10, alpha=0.1, dropout=0.5, dropout_rng=None, learn=True, fused=True, fused_max_rows=None):
+        super().__init__()
+        self.w0 = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nfeat, nhid)))
+        self.w1 = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nhid, nclass)))
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._init_filter(order, alpha, learn, fused, fused_max_rows)
+
+    def forward(self, adj, x):
+        if self.dropout_rng is not None:
+            h = self.dropout_rng.relu_dropout(_Linear.apply(x, self.w0, False), self.dropout, self.training)
+        else:
+            h = torch.nn.functional.dropout(_Linear.apply(x, self.w0, True), self.dropout, self.training)
+        return self._filter(adj, _Linear.apply(h, self.w1, False), self.gamma)
 
 
 def graphed_inference(model, adj, x, **forward_kwargs):

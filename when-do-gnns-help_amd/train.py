@@ -9,6 +9,8 @@
 - csrc/gat_scores.hip: the scores of stacked attention layers, S = H blockdiag(a_dst, a_src) without the operand, with their backward pass
 - csrc/signed_att.hip: the signed-attention layer of many graphs (FAGCN-1, FAGCN-2: a tanh weight per stored entry, times the fixed scales)
   with its backward pass
+- csrc/poly_filter.hip: the polynomial graph filter of many graphs (GPR-GNN-1, GPR-GNN-2; APPNP): all K hops of sum_k gamma_k A_hat^k v in one launch,
+  with the dot products that are the coefficients' gradient
 - csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
 - csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
@@ -36,6 +38,7 @@ _ACM_PACKED_JOB_DTYPE = np.dtype(_lib.AcmPackedJob)
 _GAT_JOB_DTYPE = np.dtype(_lib.GatJob)
 _GAT_SCORES_JOB_DTYPE = np.dtype(_lib.GatScoresJob)
 _SIGNED_ATT_JOB_DTYPE = np.dtype(_lib.SignedAttJob)
+_POLY_FILTER_JOB_DTYPE = np.dtype(_lib.PolyFilterJob)
 _XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
 _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
 _KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
@@ -543,6 +546,121 @@ class GatScoresBatch(JobTable):
         if not self.has_backward and self.n_jobs:
             raise ValueError("GatScoresBatch.launch_backward: the table was built without gradient tensors")
         self._launch("wdg_gat_scores_backward_batched_f32", self.max_rows, self.max_cols)
+
+
+class PolyFilterBatch(JobTable):
+    """Job table for wdg_poly_filter_batched_f32 (csrc/poly_filter.hip): one polynomial graph filter per entry,
+    out = sum_{k = 0..K} gamma[k, seg] A_hat^k v with A_hat = diag(row_scale) A diag(col_scale), A the graph with its stored values, all K hops in one
+    launch - a workgroup keeps T_k and T_{k+1} of up to `group` columns in LDS -, and optionally dots[k, seg] = <A_hat^k v, u> over the
+    segment's columns (include/wdg.h states the arithmetic and every sum's order; tests/_poly_filter_ref.py restates it in numpy).  On
+    the transposed pattern with the two scales swapped, v = d_out and u = H0, out is the gradient of H0 and dots that of gamma."""
+
+    MAX_JOBS, MAX_ORDER, GROUPS, DOT_ROWS, TEAM, LONG_ROW = 65535, 64, (4, 2, 1), 32, 4, 128
+    _KEYS = ("graph", "v", "out", "gamma", "order", "row_scale", "col_scale", "seg_cols", "u", "dots", "group")
+
+    @staticmethod
+    def max_rows(group):
+        """the largest graph a workgroup holds twice in LDS at `group` columns (20448, 10224, 5112 for 1, 2, 4; 0 for another width)"""
+        return int(lib.wdg_poly_filter_max_rows(int(group)))
+
+    @classmethod
+    def default_group(cls, n):
+        """the default `group` of an entry: the LARGEST of 4, 2, 1 whose row limit holds n rows (fewer launches' worth of index reads
+        per column); None where even one column does not fit"""
+        return next((g for g in cls.GROUPS if n <= cls.max_rows(g)), None)
+
+    def __init__(self, entries):
+        """entries: list of dicts - graph: a square CsrGraph (its pattern and its values; a graph whose values are all 1 is run without
+           them: the same bits), v and out [n, cols] fp32 (unit inner stride, any
+           leading dimension: column slices of a wider matrix are fine), order K (int, 0..64), gamma [K + 1, n_seg] fp32 on the device
+           (unit inner stride), and, each optional: row_scale and col_scale (contiguous [n] fp32: the two vectors a models.NormAdj
+           holds; None = 1), seg_cols (default: cols - all columns form one segment; cols = n_seg * seg_cols), u [n, cols] together
+           with dots [K + 1, n_seg] (fp32 out), group (1, 2 or 4 columns per workgroup; default: the largest of 4, 2, 1 whose row
+           limit - max_rows(group) - holds the graph).
+        Raises ValueError for unknown keys, an order outside 0..64, cols no multiple of seg_cols, u without dots or dots without u, a
+        group outside {1, 2, 4}, a graph over the row limit of its group, other dtypes, shapes or strides, more than 65535 entries, an
+        output (out, dots) that overlaps an input or another output of its entry."""
+        name = "PolyFilterBatch"
+        self._open(entries)
+        shapes = []
+        for e in entries:
+            unknown = set(e) - set(self._KEYS)
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            if any(e.get(k) is None for k in ("graph", "v", "out", "gamma", "order")):
+                raise ValueError(f"{name}: graph, v, out, gamma and order are required")
+            g = e["graph"]
+            if g.n_rows != g.n_cols:
+                raise ValueError(f"{name}: a square graph expected, got {g.n_rows} x {g.n_cols}")
+            n, order = g.n_rows, int(e["order"])
+            if not 0 <= order <= self.MAX_ORDER:
+                raise ValueError(f"{name}: order {order}; the kernel runs 0..{self.MAX_ORDER} hops")
+            v = e["v"]
+            if not isinstance(v, torch.Tensor) or v.dim() != 2:
+                raise ValueError(f"{name}: v must be a [{n}, cols] fp32 matrix")
+            cols = int(v.shape[1])
+            seg_cols = int(e["seg_cols"]) if e.get("seg_cols") is not None else max(cols, 1)
+            if seg_cols < 1 or cols % seg_cols:
+                raise ValueError(f"{name}: {cols} columns in segments of {seg_cols}; a multiple expected")
+            n_seg = cols // seg_cols
+            if (e.get("u") is None) != (e.get("dots") is None):
+                raise ValueError(f"{name}: u and dots come together or not at all")
+            group = e.get("group")
+            if group is None:
+                group = self.default_group(n)
+                if group is None:
+                    raise ValueError(f"{name}: a graph of {n} rows; one column of at most {self.max_rows(1)} rows fits twice in a workgroup's LDS")
+            group = int(group)
+            if group not in self.GROUPS:
+                raise ValueError(f"{name}: group {group}; 1, 2 or 4 columns per workgroup expected")
+            if n > self.max_rows(group):
+                raise ValueError(f"{name}: a graph of {n} rows at group {group}; at most {self.max_rows(group)} rows fit twice in a workgroup's LDS")
+            mats = {k: e[k] for k in ("v", "out", "u") if e.get(k) is not None}
+            for k, t in mats.items():
+                GatBatch._matrix(k, t, (n, cols), name)
+            for k in ("gamma", "dots"):
+                if e.get(k) is not None:
+                    GatBatch._matrix(k, e[k], (order + 1, n_seg), name)
+                    mats[k] = e[k]
+            for k in ("row_scale", "col_scale"):
+                t = e.get(k)
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous()):
+                    raise ValueError(f"{name}: {k} must be a contiguous [n = {n}] fp32 vector")
+            named = list(mats.items())
+            for i, (ka, ta) in enumerate(named):
+                for kb, tb in named[i + 1:]:
+                    if (ka in ("out", "dots") or kb in ("out", "dots")) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
+            shapes.append((n, g.nnz, cols, seg_cols, order, group))
+        tab = self._records(_POLY_FILTER_JOB_DTYPE)
+        for e in entries:
+            tensors = [e[k] for k in ("v", "out", "u", "gamma", "dots", "row_scale", "col_scale") if e.get(k) is not None]
+            tensors += [t for t in (e["graph"].rowptr, e["graph"].col, e["graph"].val) if t is not None]
+            if any(t.device != self._dev for t in tensors):
+                raise ValueError(f"{name}: every tensor of an entry must live on the device {self._dev}")
+        has_dots = [e.get("dots") is not None for e in entries]
+        lens = [int(lib.wdg_poly_filter_partials_len(s_[0], s_[2], s_[4])) if d else 0 for s_, d in zip(shapes, has_dots)]
+        if any(has_dots):
+            ptr = self._own("partials", lens, torch.float64, of=None, reset=False)
+            tab["partials"] = np.where(has_dots, ptr, 0)
+        self._point(tab, "rowptr", [e["graph"].rowptr for e in entries])
+        self._point(tab, "col", [e["graph"].col for e in entries])
+        self._point(tab, "val", [None if e["graph"].unit_values else e["graph"].val for e in entries])  # (checked once per graph, here: before any capture)
+        for k in ("row_scale", "col_scale"):
+            self._point(tab, k, [e.get(k) for e in entries])
+        for key in ("v", "out", "gamma", "u", "dots"):
+            self._point(tab, key, [e.get(key) for e in entries], ld="ld_" + key)
+        for k, field in enumerate(("n", "nnz", "cols", "seg_cols", "order", "group_cols")):
+            tab[field] = [s_[k] for s_ in shapes]
+        self.groups = [s_[5] for s_ in shapes]
+        self.max_groups = max((s_[2] // s_[3] * -(-s_[3] // s_[5]) for s_ in shapes), default=0)
+        self.max_floats = max((s_[0] * s_[5] for s_ in shapes), default=0)
+        self.max_dot_rows = max((s_[4] + 1 for s_, d in zip(shapes, has_dots) if d), default=0)
+        self._close(tab, "wdg_poly_filter_check_jobs")
+
+    def launch(self):
+        """out - and dots, where an entry has them - of every entry"""
+        self._launch("wdg_poly_filter_batched_f32", self.max_groups, self.max_floats, self.max_dot_rows)
 
 
 def acm_operand_gradient(d_pair, t_pair, d_full, width):
