@@ -1939,6 +1939,61 @@ int32_t wdg_poly_filter_max_rows(int32_t group_cols);
 /* the doubles of a job's workspace: (order + 1) * cols * (ceil(n / WDG_POLY_FILTER_DOT_ROWS) + 1); 0 for a negative argument */
 int64_t wdg_poly_filter_partials_len(int32_t n, int32_t cols, int32_t order);
 
+/*
+ * The strict two-hop neighbourhood of many graphs (the second aggregation pattern of H2GCN: Zhu et al., "Beyond Homophily in Graph
+ * Neural Networks"), built on the device for a table of jobs in two launches.  The reference computes no pattern product: the
+ * result is DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: nothing of its own - the aggregations of normalize_tensor (utils/util_funcs.py:365-381) run on the pattern they are handed;
+ *           this builds a second pattern for them.
+ * A job: a square CSR pattern A, rowptr int32 [n + 1] and col int32 [rowptr[n]] - inside a row in ANY order, duplicates allowed, no
+ * values read.  With B[i, j] = (A stores (i, j) and i != j) - the diagonal of A is ignored as if it were not stored - the result is
+ * the CSR pattern T of
+ *   R[i, j] = exists k with B[i, k] and B[k, j]                           (so k != i and k != j: reached in exactly two steps)
+ *   flags == 0:                            T[i, j] = R[i, j] and not B[i, j] and j != i        (the strict two-hop neighbourhood)
+ *   flags & WDG_TWO_HOP_KEEP_ONE_HOP (1):  A's off-diagonal entries are not removed: T[i, j] = (R[i, j] or B[i, j]) ... - every j within
+ *                                          two hops of i
+ *   flags & WDG_TWO_HOP_KEEP_SELF (2):     ... the diagonal is not removed: T[i, i] = R[i, i] (i has an out-neighbour that points back)
+ * Row i is built from OUT-neighbours of OUT-neighbours: on a directed graph T is in general not symmetric.  out_rowptr [n + 1] starts
+ * at 0 for every job; the columns of a row of out_col come out strictly ascending and without duplicates whatever the input's order;
+ * no values are written (a CsrGraph with val = NULL: every stored value is 1).  The results are the same bits on every run and do not
+ * depend on the other jobs of the table or on max_rows.
+ * wdg_csr_two_hop_count_batched: every row's count, out_rowptr (an exclusive scan per job) and *total = out_rowptr[n] as int64 - or
+ *   -1 when any stored index of the job lies outside [0, n): such an index is skipped, it never addresses the bitmap (the front end
+ *   raises IndexError, as for wdg_coo_to_csr_i32's negative count).  A total above 2^31 - 1 is written as it is; out_rowptr has then wrapped
+ *   and the caller must not go on to the fill pass.  Two kernels on the stream.  out_col is not read.
+ * wdg_csr_two_hop_fill_batched: out_col[out_rowptr[i] .. out_rowptr[i + 1]) = the set bits of row i in ascending order, nothing past a
+ *   row's end; a job whose out_col is NULL is skipped.  The bitmap of a row is REBUILT here: no workspace is kept between the passes.
+ * Shape: WDG_TWO_HOP_WAVES waves per workgroup, a wave per row at a time with a bitmap of n bits in its slice of LDS, bits set with LDS
+ * atomics; no floating point, no global atomic.  max_rows: the table's largest n - it sizes the launch's LDS
+ * (WDG_TWO_HOP_WAVES * 4 * ceil(max_rows / 32) bytes) and grid; a job with n > max_rows is left untouched, and so is a malformed one.
+ * Limit: WDG_TWO_HOP_WAVES bitmaps in WDG_TWO_HOP_LDS_BYTES (160 KiB less 256 bytes kept free): n <= wdg_csr_two_hop_max_rows() =
+ * WDG_TWO_HOP_MAX_ROWS = 163 584.
+ * Refused before any launch, by both launches (WDG_ERR_INVALID): a NULL table with n_jobs > 0, a negative n_jobs or max_rows, more than
+ * 65535 jobs; max_rows over the limit: WDG_ERR_UNSUPPORTED with the limit in the message.  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is
+ * launched (so a table of nothing but n == 0 jobs has nothing written: the caller zeroes out_rowptr[0] and total; in a table that
+ * launches, an n == 0 job gets out_rowptr[0] = 0 and total = 0).  What is wrong inside a job - a negative n, a flag bit other than 1 and
+ * 2, a NULL out_rowptr or total, a NULL rowptr with n > 0 - is refused by wdg_csr_two_hop_check_jobs on the HOST copy of the table
+ * (graphs.TwoHopBatch calls it before it uploads), and so is n over the limit, as WDG_ERR_UNSUPPORTED with the limit in the message.  A NULL
+ * col is a pattern without entries.  rowptr is trusted: the job carries no entry count to hold it against.
+ */
+#define WDG_TWO_HOP_KEEP_ONE_HOP 1
+#define WDG_TWO_HOP_KEEP_SELF 2
+#define WDG_TWO_HOP_WAVES 8
+#define WDG_TWO_HOP_LDS_BYTES (160 * 1024 - 256)
+#define WDG_TWO_HOP_MAX_ROWS (WDG_TWO_HOP_LDS_BYTES / (4 * WDG_TWO_HOP_WAVES) * 32)
+typedef struct wdg_two_hop_job {
+    const int32_t *rowptr;    /* A: n x n, [n + 1] */
+    const int32_t *col;       /* [rowptr[n]]: any order inside a row, duplicates allowed; NULL: no entries */
+    int32_t n, flags;
+    int32_t *out_rowptr;      /* [n + 1], written by the count pass */
+    int32_t *out_col;         /* [out_rowptr[n]], written by the fill pass; may be NULL for the count pass */
+    int64_t *total;           /* entries of T, or -1 for an index out of range */
+} wdg_two_hop_job;
+int32_t wdg_csr_two_hop_max_rows(void);
+int wdg_csr_two_hop_check_jobs(const wdg_two_hop_job *jobs_host, int32_t n_jobs);
+int wdg_csr_two_hop_count_batched(const wdg_two_hop_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+int wdg_csr_two_hop_fill_batched(const wdg_two_hop_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

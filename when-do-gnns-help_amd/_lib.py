@@ -201,6 +201,10 @@ SIGNATURES = {
     "wdg_poly_filter_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_poly_filter_max_rows": (c_int32, [c_int32]),
     "wdg_poly_filter_partials_len": (c_int64, [c_int32, c_int32, c_int32]),
+    "wdg_csr_two_hop_max_rows": (c_int32, []),
+    "wdg_csr_two_hop_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_csr_two_hop_count_batched": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_csr_two_hop_fill_batched": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -430,6 +434,12 @@ class PolyFilterJob(ctypes.Structure):
     _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "val", "row_scale", "col_scale", "v", "out", "gamma", "u", "dots", "partials")] + \
                [(name, c_int64) for name in ("ld_v", "ld_out", "ld_gamma", "ld_u", "ld_dots")] + \
                [(name, c_int32) for name in ("n", "nnz", "cols", "seg_cols", "order", "group_cols")]
+
+
+class TwoHopJob(ctypes.Structure):
+    """mirror of `wdg_two_hop_job` (include/wdg.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("n", c_int32), ("flags", c_int32), ("out_rowptr", c_void_p), ("out_col", c_void_p),
+                ("total", c_void_p)]
 
 
 if not os.path.exists(LIB_PATH):

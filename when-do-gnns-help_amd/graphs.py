@@ -1,5 +1,6 @@
 """Device-resident graphs: the CSR container with its one-time plans (SELL-16 copy, band plan, narrow pack), the batched build of a
-sweep shard's graphs (one block-diagonal COO -> CSR build, one host read-back) and the degree normalisations.  Every function is
+sweep shard's graphs (one block-diagonal COO -> CSR build, one host read-back), the strict two-hop neighbourhoods of a list of graphs
+(TwoHopBatch: two launches, one host read-back) and the degree normalisations.  Every function is
 a call into the C ABI (include/wdg.h); nothing computes on the CPU."""
 import ctypes
 import os
@@ -271,6 +272,10 @@ class CsrGraph:
         # running the COO -> CSR build again (the tensor is a view of the same pattern; .coalesce() / arithmetic drop the tag)
         t._wdg_csr = self
         return t
+
+    def two_hop(self, flags=0):
+        """the strict two-hop neighbourhood of this graph as a CsrGraph without values: `two_hop(self, flags)`"""
+        return two_hop(self, flags)
 
     def with_values(self, val):  # (neither SELL copy is shared: both hold values)
         return CsrGraph(self.rowptr, self.col, val, self.n_rows, self.n_cols)  # SELL copy (holds values) not shared
@@ -587,6 +592,98 @@ class GraphBatch:
                                   _ptr(out["cnt"]), _ptr(out["dinv"]), _ptr(out["dinv64"]), stream_handle()), "wdg_degree_norm")
         p = self.node_ptr_host
         return [{k: v[int(p[g_]):int(p[g_ + 1])] for k, v in out.items()} for g_ in range(len(self.graphs))]
+
+
+# ------------------------------------------------------------------------------------------- two-hop neighbourhoods
+TWO_HOP_KEEP_ONE_HOP, TWO_HOP_KEEP_SELF = 1, 2  # WDG_TWO_HOP_* of include/wdg.h
+
+
+def two_hop_totals(totals):
+    """the totals wdg_csr_two_hop_count_batched wrote (any sequence of integers, one per job) -> list of int.  IndexError for a -1 (the
+    job stores an index outside its graph), OverflowError for a total above 2^31 - 1 (the row pointers are int32)."""
+    out = [int(t) for t in totals]
+    for g_, t in enumerate(out):
+        if t < 0:
+            raise IndexError(f"two_hop: graph {g_} stores a column index out of range for its node count")
+        if t > (1 << 31) - 1:
+            raise OverflowError(f"two_hop: graph {g_} has {t} two-hop entries; a CSR pattern with int32 row pointers holds at most {(1 << 31) - 1}")
+    return out
+
+
+class TwoHopBatch:
+    """The strict two-hop neighbourhoods T = (A . A > 0) \\ (A u I) of a list of square CsrGraphs as ONE job table
+    (wdg_csr_two_hop_count_batched / _fill_batched, csrc/two_hop.hip; include/wdg.h defines the result): row i of T holds the nodes
+    reached from i in exactly two steps that are neither i nor stored in row i - OUT-neighbours of OUT-neighbours, so T of a directed
+    graph is in general not symmetric.  The diagonal of A counts as not stored; values are not read; rows may be unsorted and hold
+    duplicates.  flags: TWO_HOP_KEEP_ONE_HOP (1: A's off-diagonal entries stay - everything within two hops), TWO_HOP_KEEP_SELF (2: the
+    diagonal stays where a neighbour points back).
+    launch() -> list of CsrGraph(out_rowptr, out_col, None, n, n): no values, so the aggregation kernels skip the value stream; rows
+    strictly ascending - what the SpMM plans, transpose_positions and the attention plans expect.
+    A one-time plan like ensure_quad and transpose_positions: launch() reads the totals back (ONE host sync for the whole list) and
+    allocates, so it must not be called inside a stream capture."""
+
+    MAX_JOBS = 65535
+
+    @staticmethod
+    def max_rows():
+        return int(lib.wdg_csr_two_hop_max_rows())
+
+    def __init__(self, graphs, flags=0):
+        graphs, flags = list(graphs), int(flags)
+        if flags & ~(TWO_HOP_KEEP_ONE_HOP | TWO_HOP_KEEP_SELF):
+            raise ValueError(f"TwoHopBatch: flags = {flags} (TWO_HOP_KEEP_ONE_HOP = 1 and TWO_HOP_KEEP_SELF = 2 are defined)")
+        if len(graphs) > self.MAX_JOBS:
+            raise ValueError(f"TwoHopBatch: {len(graphs)} graphs; one launch takes {self.MAX_JOBS}")
+        limit = self.max_rows()
+        for g_, g in enumerate(graphs):
+            if g.n_rows != g.n_cols:
+                raise ValueError(f"TwoHopBatch: graph {g_} is {g.n_rows} x {g.n_cols}; a square pattern expected")
+            if g.n_rows > limit:
+                raise ValueError(f"TwoHopBatch: graph {g_} has {g.n_rows} rows; a wave's bitmap holds at most {limit} columns in LDS")
+        dev = require_gpu()
+        self.graphs, self.flags, self.G = graphs, flags, len(graphs)
+        self.ns = [g.n_rows for g in graphs]
+        self.max_n = max(self.ns, default=0)
+        # every graph's row pointers in one pool (a slice per graph, 256-byte aligned like an allocation of its own) and the totals;
+        # zeros: a table of nothing but empty graphs launches nothing
+        off = np.concatenate([[0], np.cumsum([(n + 1 + 63) // 64 * 64 for n in self.ns])]).astype(np.int64)
+        self._rowptr_off = off
+        self.rowptr_pool = torch.zeros(int(off[-1]), dtype=torch.int32, device=dev)
+        self.totals = torch.zeros(max(self.G, 1), dtype=torch.int64, device=dev)
+        self.jobs = (_lib.TwoHopJob * max(self.G, 1))()
+        for g_, g in enumerate(graphs):
+            job = self.jobs[g_]
+            job.rowptr, job.col = g.rowptr.data_ptr(), g.col.data_ptr() if g.nnz else 0
+            job.n, job.flags = g.n_rows, flags
+            job.out_rowptr, job.out_col = self.rowptr_pool.data_ptr() + 4 * int(off[g_]), 0
+            job.total = self.totals.data_ptr() + 8 * g_
+        check(lib.wdg_csr_two_hop_check_jobs(ctypes.cast(self.jobs, c_void_p), self.G), "wdg_csr_two_hop_check_jobs")
+
+    def launch(self):
+        """count pass, the ONE read-back of all totals (IndexError / OverflowError: two_hop_totals), fill pass -> list of CsrGraph"""
+        G, st = self.G, stream_handle()
+        dev = self.rowptr_pool.device
+        if G == 0:
+            return []
+        table = _table((_lib.TwoHopJob * G)(*self.jobs[:G]))
+        check(lib.wdg_csr_two_hop_count_batched(_ptr(table), G, self.max_n, st), "wdg_csr_two_hop_count_batched")
+        totals = two_hop_totals(self.totals[:G].cpu().tolist())  # the one host sync of the build
+        base = np.concatenate([[0], np.cumsum([(t + 63) // 64 * 64 for t in totals])]).astype(np.int64)
+        col_pool = torch.empty(int(base[-1]), dtype=torch.int32, device=dev)
+        for g_ in range(G):
+            self.jobs[g_].out_col = col_pool.data_ptr() + 4 * int(base[g_]) if totals[g_] else 0
+        table2 = _table((_lib.TwoHopJob * G)(*self.jobs[:G]))
+        check(lib.wdg_csr_two_hop_fill_batched(_ptr(table2), G, self.max_n, st), "wdg_csr_two_hop_fill_batched")
+        self._keep = (table, table2)  # (alive until the launches that read them have run)
+        off = self._rowptr_off
+        return [CsrGraph(self.rowptr_pool[int(off[g_]):int(off[g_]) + self.ns[g_] + 1], col_pool[int(base[g_]):int(base[g_]) + totals[g_]], None,
+                         self.ns[g_], self.ns[g_]) for g_ in range(G)]
+
+
+def two_hop(g, flags=0):
+    """The strict two-hop neighbourhood of ONE graph (TwoHopBatch of a one-entry list): a CsrGraph without values.  A one-time plan with
+    a host read-back - not inside a stream capture."""
+    return TwoHopBatch([g], flags).launch()[0]
 
 
 # ------------------------------------------------------------------------------------------- normalisation

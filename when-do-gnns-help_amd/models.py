@@ -31,6 +31,11 @@ GPR-GNN-1 / GPR-GNN-2 (`GPRGNN1`, `GPRGNN2`) put a learnt polynomia
 logits = sum_k gamma_k A_hat^k H0 with K + 1 coefficients that may turn negative (Chien et al., "Adaptive Universal Generalized PageRank
 Graph Neural Network"; frozen coefficients: APPNP) - all K hops in one launch of csrc/poly_filter.hip, the backward pass one more launch
 of the same kernel on the transposed pattern.  Defined by this project as well.
+
+H2GCN-1 / H2GCN-2 (`H2GCN1`, `H2GCN2`) aggregate SEPARATELY over the one-hop neighbourhood and over the strict two-hop
+neighbourhood - the nodes reached in exactly two steps that are neither the node nor one of its neighbours - without self loops, and
+keep every round's representation for the classifier (Zhu et al., "Beyond Homophily in Graph Neural Networks").  The second pattern is
+built once on csrc/two_hop.hip (`TwoHopAdj`); the aggregations are the existing ones.  Defined by this project as well.
 """
 import torch
 
@@ -745,6 +750,73 @@ class GPRGNN2(_GPRBase):
         else:
             h = torch.nn.functional.dropout(_Linear.apply(x, self.w0, True), self.dropout, self.training)
         return self._filter(adj, _Linear.apply(h, self.w1, False), self.gamma)
+
+
+class TwoHopAdj:
+    """The two fixed aggregations of H2GCN over one graph, both WITHOUT self loops:
+        .one = NormAdj(A without its diagonal, symmetric, add_self_loops=False)
+        .two = NormAdj(ops.two_hop(A without its diagonal), symmetric, add_self_loops=False)   - the strict two-hop neighbourhood
+    .graph: the one-hop graph (train_eval / train_eval_graphed read adj.graph.device), .n: the node count.  A row without entries -
+    an isolated node; a node whose two-hop set is empty, as in a clique - has scale 0 (degree_norm's guard) and aggregates to 0.
+    Building it runs the two-hop build, a one-time plan with a host read-back: not inside a stream capture."""
+
+    def __init__(self, adj, symmetric=1):
+        g = CsrGraph.from_any(adj).rebuild(ops.COO_DROP_SELF_LOOPS)
+        self.one = NormAdj(g, symmetric, add_self_loops=False)
+        self.two = NormAdj(ops.two_hop(g), symmetric, add_self_loops=False)
+        self.graph, self.n = self.one.graph, g.n_rows
+
+
+class _H2GCN(torch.nn.Module):
+    """R0 = relu(X W_e); R_k = [A1_hat R_{k-1} | A2_hat R_{k-1}] for k = 1..rounds (width nhid 2^k); R = [R0 | ... | R_K];
+    logits = dropout(R) W_c.  Bias-free.  Every entry of R is >= 0 (a ReLU output, then sums with the non-negative weights of a
+    TwoHopAdj), so relu_dropout(R) of a DeviceDropout IS dropout(R)."""
+
+    def __init__(self, rounds, nfeat, nclass, nhid, dropout, dropout_rng):
+        super().__init__()
+        self.rounds = rounds
+        self.w_e = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nfeat, nhid)))
+        self.w_c = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nhid * (2 ** (rounds + 1) - 1), nclass)))
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+
+    def representation(self, adj, x):
+        """-> R [n, nhid (2^(rounds + 1) - 1)] before dropout"""
+        if not isinstance(adj, TwoHopAdj):
+            raise TypeError(f"{type(self).__name__} aggregates over two patterns: a models.TwoHopAdj expected, got {type(adj).__name__}")
+        r = _Linear.apply(x, self.w_e, True)
+        reps = [r]
+        for _ in range(self.rounds):
+            r = torch.cat([adj.one.matmul(r), adj.two.matmul(r)], 1)
+            reps.append(r)
+        return torch.cat(reps, 1)
+
+    def forward(self, adj, x):
+        r = self.representation(adj, x)
+        if self.dropout_rng is not None:
+            r = self.dropout_rng.relu_dropout(r, self.dropout, self.training)
+        else:
+            r = torch.nn.functional.dropout(r, self.dropout, self.training)
+        return _Linear.apply(r, self.w_c, False)
+
+
+class H2GCN1(_H2GCN):
+    """H2GCN-1: one round - logits = dropout([R0 | A1_hat R0 | A2_hat R0]) W_c with R0 = relu(X W_e) (Zhu et al., "Beyond Homophily in
+    Graph Neural Networks": ego and neighbour embeddings kept apart, the higher-order neighbourhood aggregated on its own, the
+    intermediate representations combined); bias-free; DESIGN 4.29.  adj: a TwoHopAdj (recommended: symmetric=1).
+    dropout_rng: None - torch's dropout - or a DeviceDropout (csrc/dropout.hip: R >= 0, so its ReLU changes nothing); the kernel takes
+    any width this model has (its limit is rows * ceil(cols / 4) < 2^32).
+    Parameters are drawn in this order: W_e (xavier_uniform, [nfeat, nhid]), then W_c (xavier_uniform, [3 nhid, nclass])."""
+
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
+        super().__init__(1, nfeat, nclass, nhid, dropout, dropout_rng)
+
+
+class H2GCN2(_H2GCN):
+    """H2GCN-2: two rounds - R1 = [A1_hat R0 | A2_hat R0], R2 = [A1_hat R1 | A2_hat R1], logits = dropout([R0 | R1 | R2]) W_c; otherwise
+    H2GCN1.  Parameters are drawn in this order: W_e (xavier_uniform, [nfeat, nhid]), then W_c (xavier_uniform, [7 nhid, nclass])."""
+
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
+        super().__init__(2, nfeat, nclass, nhid, dropout, dropout_rng)
 
 
 def graphed_inference(model, adj, x, **forward_kwargs):
