@@ -435,6 +435,11 @@ int wdg_debug_clock(uint64_t *out_dev, wdg_stream_t stream);
  *   totals[4]=|P'| (non-loop)  [5]=matches among P'
  *   row_nnz[u]=|P_u|  row_nnz_noself[u]=|P'_u|  row_match_noself[u]=#{v in P'_u : y_v==y_u}
  *   compat[i*C+j]=#{(u,v) in P' : y_u=i, y_v=j, both>=0}   classdeg[c]=sum_{y_u=c}(|P_u|-1)
+ * Labels outside [0, C): "y_u == y_v" compares the stored int32 values whatever they are (two labels of -1 match, two of C match),
+ * and totals[2] / totals[3] ask only for the sign - a label >= C counts there like any other non-negative one.  compat and classdeg
+ * hold the classes [0, C) alone: an entry with either label outside [0, C) is in no cell of compat, a row whose label is outside
+ * [0, C) is in no element of classdeg (a negative label and one >= C are the same to them).  A row without entries adds -1 to
+ * classdeg of its class.  C = 0: compat and classdeg are not touched and may be NULL.
  * All outputs are exact integers (bit-exact parity).  Any per-row output may be NULL.
  * replaces: utils/homophily_metrics.py:50-56 (edge), :73-78 (node), :89-101 (compat), :127-145
  *           (class_distribution); dense twins utils/homophily_plot.py:48-51,85-99,111-122,151-170.
@@ -453,7 +458,9 @@ typedef struct wdg_stats_job {
     int32_t *row_nnz, *row_nnz_noself, *row_match_noself; /* [N] each, may be NULL */
     int32_t n_rows, n_classes;
 } wdg_stats_job;
-/* Batched form: outputs must be zeroed by the caller (one memset over a pooled buffer). */
+/* Batched form: outputs must be zeroed by the caller (one memset over a pooled buffer) - totals, compat and classdeg are ADDED to
+ * (a second launch without the memset doubles them), the per-row arrays are written.  Jobs may differ in n_rows (0 included) and in
+ * n_classes; max_rows / max_classes are the largest of the table.  n_jobs == 0 or max_rows == 0: nothing is launched or written. */
 int wdg_edge_label_stats_batched(const wdg_stats_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_classes,
                                  wdg_stream_t stream);
 
@@ -465,6 +472,12 @@ int wdg_edge_label_stats_batched(const wdg_stats_job *jobs_dev, int32_t n_jobs, 
  * replaces: the tails of edge_homophily / node_homophily / our_measure / adjusted_homo / label_informativeness / similarity as
  *           synthetic_plot.py:94-106 calls them (utils/homophily_plot.py:43-160): fp32 arithmetic on integer counters, NaN class
  *           terms skipped, zeros -> 1e-8.  Deterministic (fixed summation order).  1 <= C <= 32.
+ * Degenerate jobs get what IEEE arithmetic gives these formulas, and leave the other jobs of the table alone:
+ *   totals[4] == 0 (no non-loop entry; totals[5] is 0 then): edge = 0 / 0 = NaN, and with it adjusted homophily;
+ *   no non-empty row: node = 0 / 0 = NaN;
+ *   classdeg all zero: p = 0 / 0 = NaN (a NaN is not the zero that 1e-8 stands in for): adjusted homophily and label informativeness NaN;
+ *   C == 1: class homophily divides by C - 1 = 0 (NaN for a zero sum, +inf for a positive one); p = 1, so adjusted homophily is
+ *           (edge - 1) / 0 = -inf (NaN when edge == 1) and label informativeness 2 - 0 / 0 = NaN.
  */
 int wdg_sweep_scalars_f32(const int64_t *totals, const int32_t *rows, const int64_t *compat, const int64_t *classdeg,
                           const int64_t *las_counts, const float *las_n, const float *class_prop, int32_t n_jobs, int32_t max_rows,

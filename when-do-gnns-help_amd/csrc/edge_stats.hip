@@ -6,7 +6,7 @@
 //           :97-101 (per-class scatter_add loop), :129-145 (unique counts and the O(C^2) torch.where loops);
 //           dense twins in utils/homophily_plot.py:48-51,85-99,111-122,151-170.
 //
-// Layout: a group of GL lanes owns one row (GL picked from the mean row length), lanes stride over the row's
+// Layout: a group of GL = 16 lanes owns one row (the 3..100-entry rows of every reference dataset), lanes stride over the row's
 // column indices (coalesced within the row), gather labels (4 B, L2-resident), and count.  Group counts are
 // combined with xor-shuffles, workgroup counts in LDS (C x C histogram privatised per workgroup), and one 64-bit
 // atomic per non-zero histogram cell per workgroup reaches HBM.
@@ -20,8 +20,8 @@ using u64 = unsigned long long;
 constexpr int THREADS = 256;
 constexpr int MAX_LDS_CLASSES = 64;  // C x C int32 histogram in LDS up to 16 KiB
 constexpr int PASSES = 8;            // row tiles per workgroup
+constexpr int GL = 16;               // lanes per row
 
-template <int GL>
 __global__ __launch_bounds__(THREADS) void edge_stats_kernel(const wdg_stats_job *__restrict__ jobs,
                                                              const wdg_stats_job inline_job, int tiles_per_job, int lds_classes) {
     constexpr int ROWS_PER_PASS = THREADS / GL;
@@ -115,23 +115,15 @@ __global__ __launch_bounds__(THREADS) void edge_stats_kernel(const wdg_stats_job
     }
 }
 
-int launch(const wdg_stats_job *jobs, const wdg_stats_job &inl, int n_jobs, int max_rows, int max_classes, int gl,
-           hipStream_t st) {
+int launch(const wdg_stats_job *jobs, const wdg_stats_job &inl, int n_jobs, int max_rows, int max_classes, hipStream_t st) {
     if (n_jobs == 0 || max_rows == 0) return WDG_OK;
     const int lds_classes = std::min(std::max(max_classes, 1), MAX_LDS_CLASSES);  // jobs with more classes: global atomics
     const size_t lds = static_cast<size_t>(lds_classes) * 8 + static_cast<size_t>(lds_classes) * lds_classes * 4;
-#define WDG_STATS_CASE(G)                                                                                     \
-    if (gl == G) {                                                                                            \
-        const int tiles = static_cast<int>(ceil_div(max_rows, (THREADS / G) * PASSES));                       \
-        const int64_t blocks = static_cast<int64_t>(tiles) * n_jobs;                                          \
-        if (blocks > 0x7fffffffLL) return fail(WDG_ERR_UNSUPPORTED, "edge_label_stats: grid too large");      \
-        hipLaunchKernelGGL(edge_stats_kernel<G>, dim3(static_cast<unsigned>(blocks)), dim3(THREADS), lds, st, jobs, inl, \
-                           tiles, lds_classes);                                                               \
-        return check_launch("edge_stats_kernel");                                                             \
-    }
-    WDG_STATS_CASE(4) WDG_STATS_CASE(16) WDG_STATS_CASE(64)
-#undef WDG_STATS_CASE
-    return fail(WDG_ERR_UNSUPPORTED, "edge_label_stats: bad group width");
+    const int tiles = static_cast<int>(ceil_div(max_rows, (THREADS / GL) * PASSES));
+    const int64_t blocks = static_cast<int64_t>(tiles) * n_jobs;
+    if (blocks > 0x7fffffffLL) return fail(WDG_ERR_UNSUPPORTED, "edge_label_stats: grid too large");
+    hipLaunchKernelGGL(edge_stats_kernel, dim3(static_cast<unsigned>(blocks)), dim3(THREADS), lds, st, jobs, inl, tiles, lds_classes);
+    return check_launch("edge_stats_kernel");
 }
 
 // ---- the sweep step's six scalars from the counters, one launch for a whole shard (sweep.SweepBatch.results).  The formulas of
@@ -245,16 +237,14 @@ int wdg_edge_label_stats(const int32_t *rowptr, const int32_t *col, const int32_
     j.totals = totals; j.compat = compat; j.classdeg = classdeg;
     j.row_nnz = row_nnz; j.row_nnz_noself = row_nnz_noself; j.row_match_noself = row_match_noself;
     j.n_rows = N; j.n_classes = C;
-    // group width from the mean row length is a host-side guess the caller can refine through the batched API;
-    // 16 lanes/row suits the 3..100-entry rows of every reference dataset.
-    return launch(nullptr, j, 1, N, C, 16, st);
+    return launch(nullptr, j, 1, N, C, st);
 }
 
 int wdg_edge_label_stats_batched(const wdg_stats_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_classes,
                                  wdg_stream_t stream) {
     WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0 && max_classes >= 0, "edge_label_stats_batched: negative size");
     WDG_REQUIRE(n_jobs == 0 || jobs_dev, "edge_label_stats_batched: null job table");
-    return launch(jobs_dev, wdg_stats_job{}, n_jobs, max_rows, max_classes, 16, as_stream(stream));
+    return launch(jobs_dev, wdg_stats_job{}, n_jobs, max_rows, max_classes, as_stream(stream));
 }
 
 int wdg_sweep_scalars_f32(const int64_t *totals, const int32_t *rows, const int64_t *compat, const int64_t *classdeg,
