@@ -2007,6 +2007,60 @@ int wdg_csr_two_hop_check_jobs(const wdg_two_hop_job *jobs_host, int32_t n_jobs)
 int wdg_csr_two_hop_count_batched(const wdg_two_hop_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
 int wdg_csr_two_hop_fill_batched(const wdg_two_hop_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
 
+/*
+ * The k best columns of every row of many dense fp32 matrices in ONE launch: the selection a k-nearest-neighbour FEATURE graph needs
+ * (AM-GCN, SimP-GCN, the "kNN-GCN" rows of comparison tables) once the similarity matrix X X^T exists.  The reference builds no such
+ * graph: the result is DEFINED here and is not claimed to reproduce an upstream table.
+ * stands next to: the dense cosine matrix of generalized_edge_homophily, utils/homophily_metrics.py:167 - its rows are what this ranks
+ *                 (and utils/homophily_metrics.py:168, sim[isnan] = 0, is what a column scale of 0 for an all-zero row restates).
+ * A job: scores fp32 [rows, cols] with leading dimension ld >= cols, col_scale fp32 [cols] or NULL, row0, k in 1 .. WDG_TOPK_MAX_K, flags.
+ *   key(r, j) = scores[r, j] * col_scale[j]          ONE fp32 product, rounded once; col_scale NULL: the score itself
+ *   eligible(r, j): key is not a NaN, and - with WDG_TOPK_EXCLUDE_SELF (1) - j != row0 + r   (row r's own node is column row0 + r,
+ *                   compared in 64 bits; where it lies outside 0 .. cols - 1 nothing is excluded)
+ *   j ranks before j'  iff  key_j > key_j'  or  (key_j == key_j' and j < j')         -0 == +0; +-inf are ordinary values
+ *   out_len[r] = min(k, number of eligible j)
+ *   out_col[r, 0 .. len - 1]: the first len columns of the ranking in rank order - with WDG_TOPK_SORT_COLUMNS (2) the same set in
+ *                   ascending column order
+ *   out_key[r, s] (where out_key is not NULL): the key of out_col[r, s] as computed above (a -0 product stays -0)
+ *   slots len .. k - 1: out_col = -1, out_key = +0.  Nothing beyond slot k - 1 of a row is written (ld_out may exceed k).
+ * The ranking is a total order: the output is a pure function of the job's input - the same bits on every launch, alone or in any
+ * table, and a panel of rows of a matrix (row0 = the panel's first row) gives the rows the whole matrix gives.  No atomic of any kind.
+ * Shape: a wave owns a row at a time; lane l holds the rank-l candidate as a 64-bit word (the monotone uint32 image of the key above
+ * the complemented column); the row is streamed in chunks of 64 columns, a chunk is merged (bitonic sort + bitonic merge over
+ * cross-lane moves) only when one of its words beats the current k-th.  No LDS, no scratch.  Grid: (blocks of rows, jobs); max_rows -
+ * the table's largest `rows` - sizes the grid only: rows are strided over, so a job with more rows than max_rows is still completed.
+ * Refused before any launch (WDG_ERR_INVALID, with a message): a NULL table with n_jobs > 0, a negative n_jobs or max_rows, more than
+ * 65535 jobs.  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is launched.  What is wrong inside a job is refused by
+ * wdg_topk_rows_check_jobs on the HOST copy of the table (graphs.TopkRowsBatch calls it before it uploads): k outside
+ * 1 .. WDG_TOPK_MAX_K, negative rows or cols, ld < cols, ld_out < k, NULL scores with rows * cols > 0, NULL out_col or out_len, a flag
+ * bit other than 1 and 2; the kernel skips such a job.  rows == 0: nothing to write; cols == 0: every row has length 0.
+ *
+ * wdg_row_rnorm_f32: out[i] = 1 / ||x_i|| for x fp32 [n, F] with leading dimension ld >= F, and 0 where the row is all zero (a row
+ * whose squares overflow gives 1 / inf = 0 as well).  Its arithmetic, a wave per row: lane l's partial s_l = fmaf(v, v, s_l) over
+ * v = x[i, f], f = l, l + 64, ... ascending, from s_l = +0; the 64 partials are added by the butterfly s = s + shuffle_xor(s, o),
+ * o = 32, 16, 8, 4, 2, 1 (every lane ends with the same sum); out[i] = s == 0 ? 0 : 1.0f / sqrtf(s), the square root and the
+ * division each correctly rounded.  Every term is >= 0, so s carries at most ceil(F / 64) + 6 roundings: the relative error of out[i]
+ * is at most ((ceil(F / 64) + 6) / 2 + 2) 2^-24 to first order.  Refused: a negative n or F, ld < F, NULL x with n F > 0, NULL out
+ * with n > 0.  n == 0: nothing is launched.  F == 0: zeros.
+ */
+#define WDG_TOPK_EXCLUDE_SELF 1
+#define WDG_TOPK_SORT_COLUMNS 2
+#define WDG_TOPK_MAX_K 64
+typedef struct wdg_topk_job {
+    const float *scores;      /* [rows, cols], leading dimension ld */
+    const float *col_scale;   /* [cols] or NULL */
+    int32_t *out_col;         /* [rows, k], leading dimension ld_out */
+    float *out_key;           /* as out_col, or NULL */
+    int32_t *out_len;         /* [rows] */
+    int64_t ld, ld_out;
+    int32_t rows, cols;
+    int32_t row0, k;
+    int32_t flags, reserved;  /* reserved: not read */
+} wdg_topk_job;
+int wdg_topk_rows_check_jobs(const wdg_topk_job *jobs_host, int32_t n_jobs);
+int wdg_topk_rows_batched_f32(const wdg_topk_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
+int wdg_row_rnorm_f32(const float *x, int64_t ld, int32_t n, int32_t F, float *out, wdg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

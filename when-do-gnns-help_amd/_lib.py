@@ -205,6 +205,9 @@ SIGNATURES = {
     "wdg_csr_two_hop_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_two_hop_count_batched": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_csr_two_hop_fill_batched": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_topk_rows_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_topk_rows_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
+    "wdg_row_rnorm_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -440,6 +443,13 @@ class TwoHopJob(ctypes.Structure):
     """mirror of `wdg_two_hop_job` (include/wdg.h)"""
     _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("n", c_int32), ("flags", c_int32), ("out_rowptr", c_void_p), ("out_col", c_void_p),
                 ("total", c_void_p)]
+
+
+class TopkJob(ctypes.Structure):
+    """mirror of `wdg_topk_job` (include/wdg.h)"""
+    _fields_ = [("scores", c_void_p), ("col_scale", c_void_p), ("out_col", c_void_p), ("out_key", c_void_p), ("out_len", c_void_p),
+                ("ld", c_int64), ("ld_out", c_int64), ("rows", c_int32), ("cols", c_int32), ("row0", c_int32), ("k", c_int32),
+                ("flags", c_int32), ("reserved", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

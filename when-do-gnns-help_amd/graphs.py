@@ -1,6 +1,7 @@
 """Device-resident graphs: the CSR container with its one-time plans (SELL-16 copy, band plan, narrow pack), the batched build of a
 sweep shard's graphs (one block-diagonal COO -> CSR build, one host read-back), the strict two-hop neighbourhoods of a list of graphs
-(TwoHopBatch: two launches, one host read-back) and the degree normalisations.  Every function is
+(TwoHopBatch: two launches, one host read-back), the row top-k selection and the kNN feature graphs built on it (TopkRowsBatch,
+knn_graph, knn_graphs) and the degree normalisations.  Every function is
 a call into the C ABI (include/wdg.h); nothing computes on the CPU."""
 import ctypes
 import os
@@ -684,6 +685,246 @@ def two_hop(g, flags=0):
     """The strict two-hop neighbourhood of ONE graph (TwoHopBatch of a one-entry list): a CsrGraph without values.  A one-time plan with
     a host read-back - not inside a stream capture."""
     return TwoHopBatch([g], flags).launch()[0]
+
+
+# ------------------------------------------------------------------------------------------- row top-k and kNN feature graphs
+TOPK_EXCLUDE_SELF, TOPK_SORT_COLUMNS, TOPK_MAX_K = 1, 2, 64  # WDG_TOPK_* of include/wdg.h
+KNN_PANEL_BYTES = 256 << 20   # knn_graph: the default panel of similarities is at most this large
+KNN_BATCH_BYTES = 1 << 30     # knn_graphs: the similarity matrices of one chunk of the list are at most this large together
+
+
+def _byte_range(t):
+    """[first, last) byte a tensor of up to two dimensions touches; an empty tensor touches nothing"""
+    if t.numel() == 0:
+        return (0, 0)
+    last = sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1
+    return (t.data_ptr(), t.data_ptr() + last * t.element_size())
+
+
+class TopkRowsBatch:
+    """The k best columns of every row of a LIST of dense fp32 matrices as ONE job table (wdg_topk_rows_batched_f32,
+    csrc/topk_rows.hip; include/wdg.h defines the result): key = scores[r, j] * col_scale[j] (one rounded product), NaN keys are
+    not eligible, larger keys rank first and equal keys (-0 == +0) by the lower column - a total order, so the output is the same
+    bits on every launch, alone or in any table, and for a panel of rows of a matrix (`row0`) what the whole matrix gives.
+    entries: dicts with
+        scores        fp32 [rows, cols] device tensor, unit inner stride (a row pitch above cols is fine)
+        k             1 .. 64
+        col_scale     fp32 [cols] device tensor, optional
+        row0          the column that is row 0's own node (default 0); only read with exclude_self
+        exclude_self  row r's own column row0 + r is not eligible (default False)
+        sort_columns  a row's columns ascending instead of in rank order (default False)
+        keys          also write the keys (default False)
+        out_col / out_key / out_len   optional: int32 [rows, k] / fp32 [rows, k] (unit inner stride, any row pitch) / int32 [rows]
+                      device tensors of the caller's that the job writes instead of the batch's own (a panel of a larger result)
+    -> self.out_col[i] int32 [rows, k], self.out_key[i] fp32 [rows, k] or None, self.out_len[i] int32 [rows]; slots past a row's
+    length hold -1 / +0.  launch() is ONE kernel launch for the whole table and may be captured.  Unknown keys, wrong dtypes,
+    non-unit inner strides, wrong shapes and outputs that overlap an input or each other raise ValueError before a device is
+    asked for."""
+
+    MAX_JOBS = 65535
+    KEYS = {"scores": None, "k": None, "col_scale": None, "row0": 0, "exclude_self": False, "sort_columns": False, "keys": False,
+            "out_col": None, "out_key": None, "out_len": None}
+
+    @staticmethod
+    def _matrix(t, what, dtype, shape):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"TopkRowsBatch: {what} must be a {dtype} tensor")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"TopkRowsBatch: {what} has shape {tuple(t.shape)}; {tuple(shape)} expected")
+        if t.numel() == 0:  # (nothing of it is read or written; torch reports arbitrary strides for it)
+            return t
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise ValueError(f"TopkRowsBatch: {what} must have unit inner stride")
+        if t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+            raise ValueError(f"TopkRowsBatch: the rows of {what} overlap (row stride {t.stride(0)} below {t.shape[1]} columns)")
+        return t
+
+    def __init__(self, entries):
+        entries = [dict(e) for e in entries]
+        if len(entries) > self.MAX_JOBS:
+            raise ValueError(f"TopkRowsBatch: {len(entries)} jobs; one launch takes {self.MAX_JOBS}")
+        for i, e in enumerate(entries):
+            unknown = sorted(set(e) - set(self.KEYS))
+            if unknown:
+                raise ValueError(f"TopkRowsBatch: entry {i} has unknown keys {unknown}; known: {sorted(self.KEYS)}")
+            if "scores" not in e or "k" not in e:
+                raise ValueError(f"TopkRowsBatch: entry {i} needs `scores` and `k`")
+            for name, default in self.KEYS.items():
+                e.setdefault(name, default)
+            s, k = e["scores"], int(e["k"])
+            if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or s.dim() != 2:
+                raise ValueError(f"TopkRowsBatch: entry {i}: scores must be a two-dimensional torch.float32 tensor")
+            rows, cols = s.shape
+            self._matrix(s, f"entry {i}: scores", torch.float32, (rows, cols))
+            if not 1 <= k <= TOPK_MAX_K:
+                raise ValueError(f"TopkRowsBatch: entry {i} has k = {k}; 1 .. {TOPK_MAX_K} are supported")
+            if not -(1 << 31) <= int(e["row0"]) < (1 << 31):
+                raise ValueError(f"TopkRowsBatch: entry {i} has row0 = {e['row0']} outside int32")
+            if e["col_scale"] is not None:
+                self._matrix(e["col_scale"], f"entry {i}: col_scale", torch.float32, (cols,))
+            if e["out_col"] is not None:
+                self._matrix(e["out_col"], f"entry {i}: out_col", torch.int32, (rows, k))
+            if e["out_key"] is not None:
+                self._matrix(e["out_key"], f"entry {i}: out_key", torch.float32, (rows, k))
+            if e["out_len"] is not None:
+                self._matrix(e["out_len"], f"entry {i}: out_len", torch.int32, (rows,))
+            e["k"] = k
+        # outputs of the caller's against every input and against each other (the batch's own are fresh allocations)
+        ins = [(i, n_, _byte_range(e[n_])) for i, e in enumerate(entries) for n_ in ("scores", "col_scale") if e[n_] is not None]
+        outs = [(i, n_, _byte_range(e[n_])) for i, e in enumerate(entries) for n_ in ("out_col", "out_key", "out_len") if e[n_] is not None]
+        for a, (i, n_, (lo, hi)) in enumerate(outs):
+            for j, m_, (lo2, hi2) in ins + outs[a + 1:]:
+                if lo < hi2 and lo2 < hi:
+                    raise ValueError(f"TopkRowsBatch: {n_} of entry {i} overlaps {m_} of entry {j}")
+        dev = require_gpu()
+        for i, e in enumerate(entries):
+            for n_ in ("scores", "col_scale", "out_col", "out_key", "out_len"):
+                if e[n_] is not None and e[n_].device != dev:
+                    raise ValueError(f"TopkRowsBatch: entry {i}: {n_} lives on {e[n_].device}, the current device is {dev}")
+        self.entries, self.G = entries, len(entries)
+        self.max_rows = max([e["scores"].shape[0] for e in entries], default=0)
+        self.out_col, self.out_key, self.out_len = [], [], []
+        self.jobs = (_lib.TopkJob * max(self.G, 1))()
+        for job, e in zip(self.jobs, entries):
+            s, k = e["scores"], e["k"]
+            rows, cols = s.shape
+            oc = e["out_col"] if e["out_col"] is not None else torch.empty((rows, k), dtype=torch.int32, device=dev)
+            ol = e["out_len"] if e["out_len"] is not None else torch.empty(rows, dtype=torch.int32, device=dev)
+            ok = e["out_key"] if e["out_key"] is not None else (torch.empty((rows, k), dtype=torch.float32, device=dev) if e["keys"] else None)
+            if ok is not None and _ld(ok) != _ld(oc):
+                raise ValueError("TopkRowsBatch: out_col and out_key of an entry share ONE leading dimension")
+            self.out_col.append(oc), self.out_key.append(ok), self.out_len.append(ol)
+            job.scores, job.col_scale = s.data_ptr() if s.numel() else 0, 0 if e["col_scale"] is None else e["col_scale"].data_ptr()
+            job.out_col, job.out_key, job.out_len = oc.data_ptr(), 0 if ok is None else ok.data_ptr(), ol.data_ptr()
+            job.ld, job.ld_out = max(_ld(s), cols), max(_ld(oc), k)
+            job.rows, job.cols, job.row0, job.k = rows, cols, int(e["row0"]), k
+            job.flags = (TOPK_EXCLUDE_SELF if e["exclude_self"] else 0) | (TOPK_SORT_COLUMNS if e["sort_columns"] else 0)
+            if rows == 0:  # (an empty allocation has no address: nothing of it is written)
+                job.out_col = job.out_col or 256
+                job.out_len = job.out_len or 256
+        check(lib.wdg_topk_rows_check_jobs(ctypes.cast(self.jobs, c_void_p), self.G), "wdg_topk_rows_check_jobs")
+        self.table = _table((_lib.TopkJob * self.G)(*self.jobs[:self.G]))
+
+    def launch(self):
+        check(lib.wdg_topk_rows_batched_f32(_ptr(self.table), self.G, self.max_rows, stream_handle()), "wdg_topk_rows_batched_f32")
+        return self
+
+
+def row_rnorm(x):
+    """1 / ||x_i|| of every row of a dense fp32 device matrix (unit inner stride), 0 for an all-zero row: wdg_row_rnorm_f32, whose
+    arithmetic include/wdg.h writes out -> fp32 [n]"""
+    dev = require_gpu()
+    if x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1) or x.device != dev:
+        raise ValueError("row_rnorm: a two-dimensional fp32 matrix with unit inner stride on the current device expected")
+    n, f = x.shape
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    check(lib.wdg_row_rnorm_f32(_ptr(x) if x.numel() else c_void_p(0), max(_ld(x), f) if n else f, n, f, _ptr(out) if n else c_void_p(0), stream_handle()),
+          "wdg_row_rnorm_f32")
+    return out
+
+
+def _knn_arguments(x, k, metric, mode):
+    from .sparse_features import SparseFeatures
+    if isinstance(x, SparseFeatures):
+        raise ValueError("knn_graph: a SparseFeatures is not taken; the similarities are a dense product - pass ops.expand_features(x)")
+    if metric not in ("cosine", "dot"):
+        raise ValueError(f"knn_graph: metric = {metric!r}; 'cosine' and 'dot' are defined")
+    if mode not in ("union", "directed"):
+        raise ValueError(f"knn_graph: mode = {mode!r}; 'union' and 'directed' are defined")
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"knn_graph: k = {k}; 1 .. {TOPK_MAX_K} are supported")
+    if len(x.shape) != 2:
+        raise ValueError("knn_graph: a dense [n, F] feature matrix expected")
+    return int(k)
+
+
+def _knn_finish(out_col, out_len, n, k, mode):
+    """the selection of n rows (out_col [n, k] ascending with -1 padding, out_len [n]) -> CsrGraph without values.  directed: the row
+    pointers are the cumulative sum of out_len on the device, ONE read-back of the total, the columns compacted on the device;
+    union: A u A^T through the device COO build (its own read-back of the merged count)."""
+    dev = out_col.device
+    rowptr64 = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(out_len, 0, out=rowptr64[1:])
+    total = int(rowptr64[-1].item()) if n else 0  # the one host sync of the directed build (n k < 2^31: rows * 64 entries at most)
+    if total > (1 << 31) - 1:
+        raise OverflowError(f"knn_graph: {total} entries; a CSR pattern with int32 row pointers holds at most {(1 << 31) - 1}")
+    rows = torch.repeat_interleave(torch.arange(n, device=dev), out_len.to(torch.int64), output_size=total)
+    slot = torch.arange(total, device=dev) - rowptr64[rows]
+    col = out_col[rows, slot].contiguous() if total else torch.empty(0, dtype=torch.int32, device=dev)
+    if mode == "directed":
+        return CsrGraph(rowptr64.to(torch.int32), col, None, n, n)
+    g = CsrGraph.from_coo(rows, col, n, None, COO_SYMMETRISE | COO_BINARISE)
+    return CsrGraph(g.rowptr, g.col, None, n, n)
+
+
+def knn_graph(x, k, metric="cosine", mode="union", panel_rows=None):
+    """The k-nearest-neighbour graph of the rows of a dense feature matrix x fp32 [n, F] (host or device) as a CsrGraph without
+    values, rows strictly ascending, never a diagonal entry - the FEATURE graph that AM-GCN, SimP-GCN and "kNN-GCN" baselines set
+    beside the given one; every consumer of a CsrGraph (NormAdj, ops.spmm, ops.edge_label_stats: the homophily of the feature graph)
+    takes it as it is.
+    metric: "dot" ranks row i's columns by <x_i, x_j>; "cosine" by <x_i, x_j> / ||x_j|| - within a row the same order as the cosine
+            (the factor 1 / ||x_i|| is the row's own) - with 1 / ||x_j|| from wdg_row_rnorm_f32 as the selection's column scale; an
+            all-zero x_j scores 0, as the reference's sim[isnan] = 0 (utils/homophily_metrics.py:168).
+    The similarities come panel_rows rows at a time from the exact-fp32 GEMM (ops.gemm(..., transb=True)); every panel is one top-k
+    job with row0 = its first row, so the memory is panel_rows * n floats, not n^2 (default: the largest panel of at most 256 MiB),
+    and - the ranking being a total order - the result does not depend on panel_rows.  Ties go to the lower column.
+    mode: "directed" - row i holds i's min(k, n - 1) best other nodes (fewer where a key is NaN); "union" - A u A^T, symmetric, built
+          from that by CsrGraph.from_coo(..., COO_SYMMETRISE | COO_BINARISE).
+    A one-time plan like two_hop: it reads totals back to the host and allocates, so it must NOT run inside a stream capture.
+    Not taken: a SparseFeatures (ops.expand_features first), k > 64, other metrics."""
+    k = _knn_arguments(x, k, metric, mode)
+    dev = require_gpu()
+    x = _dev(x, torch.float32, dev)
+    n = x.shape[0]
+    if panel_rows is None:
+        panel_rows = max(1, KNN_PANEL_BYTES // (4 * max(n, 1)))
+    panel_rows = max(1, min(int(panel_rows), max(n, 1)))
+    scale = row_rnorm(x) if metric == "cosine" else None
+    out_col = torch.empty((n, k), dtype=torch.int32, device=dev)
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    panel = torch.empty((panel_rows, n), dtype=torch.float32, device=dev)
+    batches = []  # (the job tables live until the read-back below, which follows every launch on the stream)
+    for p0 in range(0, n, panel_rows):
+        p1 = min(n, p0 + panel_rows)
+        scores = _gemm_transb(x[p0:p1], x, panel[:p1 - p0])
+        batches.append(TopkRowsBatch([dict(scores=scores, k=k, col_scale=scale, row0=p0, exclude_self=True, sort_columns=True,
+                                           out_col=out_col[p0:p1], out_len=out_len[p0:p1])]).launch())
+    return _knn_finish(out_col, out_len, n, k, mode)
+
+
+def _gemm_transb(a, b, out):
+    """out = a @ b^T on the exact-fp32 GEMM (ops.gemm(a, b, transb=True, out=out); imported late: gemm.py builds on this module)"""
+    from .gemm import gemm
+    return gemm(a, b, transb=True, out=out)
+
+
+def knn_graphs(xs, k, metric="cosine", mode="union", budget_bytes=None):
+    """The kNN graphs of a LIST of dense feature matrices (a shard) -> list of CsrGraph, each as knn_graph(x, k, metric, mode) defines
+    it.  The similarity matrices of all graphs of a chunk come from ONE GramBatch(linear=True, arccos=False) and are selected in ONE
+    TopkRowsBatch launch; the list is cut into chunks whose matrices take at most budget_bytes together (default 1 GiB; a single
+    matrix above the budget is a chunk of its own).  GramBatch leaves G / 2 - an exact halving, every comparison stays as it is - and its products are within rounding of the GEMM's, not its bits:
+    where two keys of a row differ by less than that, a graph may differ from knn_graph's in those entries (with integer features
+    both are exact).  One-time plan with host read-backs: not inside a stream capture."""
+    from .kernel_regression import GramBatch
+    xs = list(xs)
+    k = [_knn_arguments(x, k, metric, mode) for x in xs][0] if xs else int(k)
+    dev = require_gpu()
+    xs = [_dev(x, torch.float32, dev) for x in xs]
+    budget = KNN_BATCH_BYTES if budget_bytes is None else int(budget_bytes)
+    out, i = [], 0
+    while i < len(xs):
+        j, used = i, 0
+        while j < len(xs) and (j == i or used + 4 * xs[j].shape[0] ** 2 <= budget):
+            used += 4 * xs[j].shape[0] ** 2
+            j += 1
+        chunk = xs[i:j]
+        gram = GramBatch(chunk, linear=True, arccos=False)
+        gram.launch()
+        batch = TopkRowsBatch([dict(scores=s, k=k, col_scale=row_rnorm(x) if metric == "cosine" else None, exclude_self=True, sort_columns=True)
+                               for x, s in zip(chunk, gram.k_linear)]).launch()
+        out += [_knn_finish(oc, ol, x.shape[0], k, mode) for x, oc, ol in zip(chunk, batch.out_col, batch.out_len)]
+        i = j
+    return out
 
 
 # ------------------------------------------------------------------------------------------- normalisation

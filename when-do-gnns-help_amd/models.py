@@ -36,6 +36,8 @@ H2GCN-1 / H2GCN-2 (`H2GCN1`, `H2GCN2`) aggregate SEPARATELY over th
 neighbourhood - the nodes reached in exactly two steps that are neither the node nor one of its neighbours - without self loops, and
 keep every round's representation for the classifier (Zhu et al., "Beyond Homophily in Graph Neural Networks").  The second pattern is
 built once on csrc/two_hop.hip (`TwoHopAdj`); the aggregations are the existing ones.  Defined by this project as well.
+`KnnAdj` puts the k-nearest-neighbour graph of the FEATURES in the second pattern's place (the feature channel of AM-GCN /
+SimP-GCN), built once on csrc/topk_rows.hip; H2GCN1 / H2GCN2 take it as they take a TwoHopAdj.
 """
 import torch
 
@@ -764,6 +766,26 @@ class TwoHopAdj:
         g = CsrGraph.from_any(adj).rebuild(ops.COO_DROP_SELF_LOOPS)
         self.one = NormAdj(g, symmetric, add_self_loops=False)
         self.two = NormAdj(ops.two_hop(g), symmetric, add_self_loops=False)
+        self.graph, self.n = self.one.graph, g.n_rows
+
+
+class KnnAdj(TwoHopAdj):
+    """A structure channel beside a FEATURE channel, in TwoHopAdj's shape (so H2GCN1 / H2GCN2 run on it unchanged), both WITHOUT self
+    loops:
+        .one = NormAdj(A without its diagonal, symmetric, add_self_loops=False)                 - what TwoHopAdj builds
+        .two = NormAdj(ops.knn_graph(x, k, metric, "union"), symmetric, add_self_loops=False)   - the kNN graph of the features
+    .knn: that graph as a CsrGraph (ops.edge_label_stats(adj.knn, labels): its homophily), .graph, .n as TwoHopAdj's.  The
+    two-channel design of AM-GCN / SimP-GCN on this project's aggregations; a node without neighbours in a pattern aggregates to 0
+    there.  Building it runs knn_graph, a one-time plan with host read-backs: not inside a stream capture.  The plain baseline needs
+    nothing of this: GCN2 on NormAdj(ops.knn_graph(x, k))."""
+
+    def __init__(self, adj, x, k=10, metric="cosine", symmetric=1):
+        g = CsrGraph.from_any(adj).rebuild(ops.COO_DROP_SELF_LOOPS)
+        if g.n_rows != g.n_cols or len(x.shape) != 2 or x.shape[0] != g.n_rows:
+            raise ValueError(f"KnnAdj: a square graph and a feature row per node expected, got {g.n_rows} x {g.n_cols} and x of shape {tuple(x.shape)}")
+        self.one = NormAdj(g, symmetric, add_self_loops=False)
+        self.knn = ops.knn_graph(x, k, metric, "union")
+        self.two = NormAdj(self.knn, symmetric, add_self_loops=False)
         self.graph, self.n = self.one.graph, g.n_rows
 
 

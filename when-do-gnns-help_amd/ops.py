@@ -8,7 +8,8 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         (capture_graphs, snapshot: TrainBatch, SplitTrainBatch and models.train_eval_graphed call it)
   graphs.py             CsrGraph (+ its one-time plans), GraphBatch (a shard's graphs in one build, or GENERATED on the device:
                         GraphBatch.generated), TwoHopBatch / two_hop (the strict two-hop neighbourhoods of a list of graphs as CsrGraphs:
-                        two launches and one read-back), normalisations
+                        two launches and one read-back), TopkRowsBatch / knn_graph / knn_graphs (the k best columns of every row of a
+                        table of dense matrices in one launch; kNN feature graphs as CsrGraphs), normalisations
   synth.py              regular_graph_device, sample_feature_rows (the device generators; the numpy generators live there too),
                         class_graphs_device / ClassGraphBatch (classes of any sizes, a k and a d per class), gauss_features_device /
                         GaussFeatureBatch (Gaussian class features)
@@ -57,8 +58,9 @@ from ._rt import (  # noqa: F401
     SPMM_HALF_SLAB, SPMM_SMALL_OFFSETS, Tiled, Transposed, _dev, _h2d, _H2D_MAX_BYTES, _ld, _PinnedArena, _ptr, _table,
 )
 from .graphs import (  # noqa: F401
-    CsrGraph, degree_norm, GraphBatch, normalise_values, quad_disabled, row_l1_normalise, two_hop, two_hop_totals, TwoHopBatch,
-    TWO_HOP_KEEP_ONE_HOP, TWO_HOP_KEEP_SELF, unpack_bits, _host_pack_coo,
+    CsrGraph, degree_norm, GraphBatch, knn_graph, knn_graphs, normalise_values, quad_disabled, row_l1_normalise, row_rnorm, TopkRowsBatch,
+    TOPK_EXCLUDE_SELF, TOPK_MAX_K, TOPK_SORT_COLUMNS, two_hop, two_hop_totals, TwoHopBatch, TWO_HOP_KEEP_ONE_HOP, TWO_HOP_KEEP_SELF,
+    unpack_bits, _host_pack_coo,
 )
 from .aggregate import (  # noqa: F401
     QUAD_MULTI_ITEM_SU, spmm, spmm_plan, SpmmBatch, _dma_ok, _fill_job, _QUAD_COST_NS,
