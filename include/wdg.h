@@ -197,6 +197,9 @@ int wdg_features_expand_batched_f32(const wdg_feat_job *jobs_dev, int32_t n_jobs
  * One aggregation problem:  Y[i,:] = row_scale[i] * sum_p val[p] * col_scale[col[p]] * X[col[p],:]
  * (val / row_scale / col_scale may each be NULL = 1).  rw: row_scale = d;  sym: row_scale = col_scale = d;
  * explicit A_hat: val only.  X is [n_cols, F] row-major with leading dimension ldx (elements), Y [n_rows, F].
+ * The sum runs over the STORED entries p of row i: every entry point takes a row's entries in any order and adds a column that is
+ * stored several times once per copy (the order only decides the rounding; tests/test_gpu_spmm_edges.py holds every kernel to it) -
+ * with ONE condition, on an optional plan: a SELL-16 copy of more than one column block is built from rows in ascending column order.
  * replaces: torch.spmm / torch.mm(adj, X) - utils/homophily_metrics.py:192,199,200,234,235,299,315;
  *           utils/homophily_plot.py:196,246,320,336.
  */
@@ -303,6 +306,9 @@ int wdg_spmm_plan(int32_t n_jobs, int32_t max_rows, int32_t max_cols, int32_t n_
  * block: q_ext 2 (n_blocks M + 1) ints, q_rows 16 M ints; the pair {chunk count, entries per block | WDG_SELL16_CONT if
  * split} is stored behind the entries AND at pair index n_blocks M, where the caller reads it back to size q_col / q_val:
  * 256 entries per chunk PLUS two chunks of slack that the kernel may read but never uses; then fill.  One-time per graph.
+ * Graphs of SEVERAL column blocks (more than 5056 columns): both calls cut a row at the block boundaries by binary search, so every
+ * row's columns must ascend (equal neighbours allowed); rows of one-block graphs may be stored in any order.  CsrGraph.ensure_quad
+ * checks it and leaves other graphs to the CSR and band kernels.
  */
 int32_t wdg_sell16_block_cols(int32_t n_cols);
 /* Bytes of a slab row the copy's offsets are scaled by: 64 (16 features of X per workgroup), or 32 for graphs of 2529 .. 5056
@@ -392,7 +398,8 @@ int wdg_spmm_narrow_bf16(const wdg_spmm_job *job_host, const int32_t *part_ptr, 
 /*
  * Many graphs with at most 8 features each in one launch (the sweep's logits aggregation A_hat Z with C classes): plain CSR,
  * 16 lanes per row, sources read IN PLACE - every job's X must be 16-byte aligned with ldx a multiple of 4 and >= 4 (>= 8
- * when the job has more than 4 features: a source row is read as one or two float4).  flags: WDG_SPMM_ANY_VAL,
+ * for EVERY job of a table with max_feat > 4, a job of fewer features included: the launch picks its width from max_feat and
+ * then reads two float4 of every source row of every job, else one).  flags: WDG_SPMM_ANY_VAL,
  * WDG_SPMM_ANY_COL_SCALE.  Sums in a fixed order (lane layout + fixed butterfly).
  */
 int wdg_spmm_narrow_batched_f32(const wdg_spmm_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat, int flags,

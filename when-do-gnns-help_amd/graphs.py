@@ -36,7 +36,10 @@ class CsrGraph:
     """Device-resident CSR adjacency: int32 rowptr[n_rows+1], int32 col[nnz], optional fp32 val[nnz].
 
     The layout every kernel consumes: row-major sorted, duplicates already merged - what the
-    reference gets from `.coalesce()` on a torch COO tensor, with 4-byte instead of 8-byte indices.
+    reference gets from `.coalesce()` on a torch COO tensor, with 4-byte instead of 8-byte indices.  That is what the builders
+    below hand out (COO_KEEP_DUPLICATES excepted).  The aggregation itself sums a row's STORED entries, in any order and a repeated
+    column once per copy (include/wdg.h at wdg_spmm_job; tests/test_gpu_spmm_edges.py); kernels that search a row - the attention
+    layers, transpose_positions - say so where they are declared.
     """
 
     def __init__(self, rowptr, col, val, n_rows, n_cols):
@@ -47,6 +50,7 @@ class CsrGraph:
         self.narrow_ws = None  # packed-source workspace of the narrow kernel (one per graph: calls on one stream)
         self.narrow_parts = None  # {parts: split positions of every row} when the packed sources exceed an XCD's L2
         self._unit_values = None if val is not None else True  # every stored value == 1 (checked once, on first use)
+        self._rows_ascending = None  # no row stores a column below the one before it (checked once, on first use)
 
     @property
     def unit_values(self):
@@ -56,6 +60,22 @@ class CsrGraph:
         if self._unit_values is None:
             self._unit_values = bool((self.val == 1).all().item()) if self.val.numel() else True
         return self._unit_values
+
+    @property
+    def rows_ascending(self):
+        """True when no row stores a column below the one before it (equal neighbours - duplicates - are fine).  Every builder of this
+        package hands out such rows; a caller's own arrays and COO_KEEP_DUPLICATES graphs need not be.  The products sum a row's stored
+        entries in any order, but the SELL-16 build of a graph with SEVERAL column blocks cuts every row at the block boundaries by
+        binary search (csrc/sell16.hip) and needs it.  One reduction + host read-back per graph, on first use (like unit_values)."""
+        if self._rows_ascending is None:
+            if self.nnz < 2:
+                self._rows_ascending = True
+            else:
+                down = self.col[1:] < self.col[:-1]
+                first = self.rowptr[1:-1].to(torch.int64)  # (a step down INTO the first entry of a row is none)
+                down[first[(first > 0) & (first < self.nnz)] - 1] = False
+                self._rows_ascending = not bool(down.any().item())
+        return self._rows_ascending
 
     QUAD_SLAB_COLS = 2528  # columns of X the quad-row kernel holds in LDS at once (one column block)
 
@@ -100,7 +120,9 @@ class CsrGraph:
 
     def ensure_quad(self, max_padding=4.0):
         """Build the SELL-16 copy (wdg_csr_to_sell16_*) that the quad-row SpMM consumes.  One-time per graph; False for
-        graphs of more than 4 column blocks (10 112 columns) or whose slices would pad too much (the decision is kept)."""
+        graphs of more than 4 column blocks (10 112 columns), for graphs of several column blocks whose rows are not stored in
+        ascending column order (the build cuts such rows wrongly: the CSR and band kernels take them) or whose slices would pad
+        too much (the decision is kept)."""
         if self.quad is not None:
             return self.quad is not False
         if quad_disabled() or self.n_rows == 0 or self.nnz == 0:
@@ -108,7 +130,7 @@ class CsrGraph:
             return False
         block_cols = lib.wdg_sell16_block_cols(self.n_cols)
         n_blocks = (max(self.n_cols, 1) + block_cols - 1) // block_cols
-        if n_blocks > self.QUAD_MAX_BLOCKS:
+        if n_blocks > self.QUAD_MAX_BLOCKS or (n_blocks > 1 and not self.rows_ascending):
             self.quad = False
             return False
         dev = self.device
