@@ -156,6 +156,49 @@ def _dropout_rngs(model):
     return [m.dropout_rng for m in model.modules() if getattr(m, "dropout_rng", None) is not None]
 
 
+class _HiddenDropout:
+    """The hidden layer's ReLU + dropout of a model that holds `dropout` and `dropout_rng` - None: torch's dropout (its own generator) -
+    or a DeviceDropout: csrc/dropout.hip, masks reproducible from (seed, stream, step).  Three routes, which differ in where the ReLU
+    is on torch's side; they are not one, because a ReLU more or less is another autograd graph and another captured launch."""
+
+    def _torch_dropout(self, h):
+        return torch.nn.functional.dropout(h, self.dropout, self.training)
+
+    def _relu_dropout(self, pre):
+        """of a kernel layer's pre-activation: torch.relu, then dropout"""
+        if self.dropout_rng is not None:
+            return self.dropout_rng.relu_dropout(pre, self.dropout, self.training)
+        return self._torch_dropout(torch.relu(pre))
+
+    def _relu_dropout_of_product(self, x, w):
+        """of the pre-activation x @ w: on torch's route the ReLU is the GEMM's epilogue"""
+        if self.dropout_rng is not None:
+            return self.dropout_rng.relu_dropout(_Linear.apply(x, w, False), self.dropout, self.training)
+        return self._torch_dropout(_Linear.apply(x, w, True))
+
+    def _dropout_of_nonnegative(self, r):
+        """of r >= 0: the kernel's ReLU changes nothing, torch's route has none"""
+        if self.dropout_rng is not None:
+            return self.dropout_rng.relu_dropout(r, self.dropout, self.training)
+        return self._torch_dropout(r)
+
+
+def _xavier(a, b):
+    return torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(a, b)))
+
+
+def _eval_forward(model, adj, x):
+    """an evaluation forward pass of `model` on (adj, x) without gradients, for what it leaves in the layers' tables; the model's mode
+    is put back"""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            model(adj, x)
+    finally:
+        model.train(was_training)
+
+
 class SGC1(torch.nn.Module):
     """logits = (A_hat X) W.  Training caches A_hat X (loop invariant: one wide aggregation for the whole run) and learns W on it;
     a forward pass WITHOUT that cache in eval mode (one-shot inference on a graph: BASELINE configs[0], [3], [4]) takes the
@@ -165,8 +208,7 @@ class SGC1(torch.nn.Module):
 
     def __init__(self, nfeat, nclass):
         super().__init__()
-        self.weight = torch.nn.Parameter(torch.empty(nfeat, nclass))
-        torch.nn.init.xavier_uniform_(self.weight)
+        self.weight = _xavier(nfeat, nclass)
         self._cache = None
 
     def aggregate_once(self, adj, x):
@@ -189,24 +231,17 @@ class SGC1(torch.nn.Module):
         return _Linear.apply(self.aggregate_once(adj, x), self.weight, False)
 
 
-class GCN2(torch.nn.Module):
+class GCN2(_HiddenDropout, torch.nn.Module):
     """dropout_rng: None - torch's dropout (its own generator) - or a DeviceDropout: the hidden layer's ReLU + dropout on
     csrc/dropout.hip, masks reproducible from (seed, stream, step)"""
 
     def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
         super().__init__()
-        self.w0 = torch.nn.Parameter(torch.empty(nfeat, nhid))
-        self.w1 = torch.nn.Parameter(torch.empty(nhid, nclass))
-        torch.nn.init.xavier_uniform_(self.w0)
-        torch.nn.init.xavier_uniform_(self.w1)
+        self.w0, self.w1 = _xavier(nfeat, nhid), _xavier(nhid, nclass)
         self.dropout, self.dropout_rng = dropout, dropout_rng
 
     def forward(self, adj, x):
-        if self.dropout_rng is not None:
-            h = self.dropout_rng.relu_dropout(adj.matmul(_Linear.apply(x, self.w0, False)), self.dropout, self.training)
-        else:
-            h = torch.relu(adj.matmul(_Linear.apply(x, self.w0, False)))
-            h = torch.nn.functional.dropout(h, self.dropout, self.training)
+        h = self._relu_dropout(adj.matmul(_Linear.apply(x, self.w0, False)))
         return adj.matmul(_Linear.apply(h, self.w1, False))
 
 
@@ -216,95 +251,114 @@ class MLP1(torch.nn.Module):
 
     def __init__(self, nfeat, nclass):
         super().__init__()
-        self.weight = torch.nn.Parameter(torch.empty(nfeat, nclass))
-        torch.nn.init.xavier_uniform_(self.weight)
+        self.weight = _xavier(nfeat, nclass)
 
     def forward(self, adj, x):
         return _Linear.apply(x, self.weight, False)
 
 
-class MLP2(torch.nn.Module):
+class MLP2(_HiddenDropout, torch.nn.Module):
     """logits = relu(X W0) W1: GCN-2 without its two aggregations, bias-free like it; `adj` is accepted and ignored.
     dropout_rng: as for GCN2."""
 
     def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
         super().__init__()
-        self.w0 = torch.nn.Parameter(torch.empty(nfeat, nhid))
-        self.w1 = torch.nn.Parameter(torch.empty(nhid, nclass))
-        torch.nn.init.xavier_uniform_(self.w0)
-        torch.nn.init.xavier_uniform_(self.w1)
+        self.w0, self.w1 = _xavier(nfeat, nhid), _xavier(nhid, nclass)
         self.dropout, self.dropout_rng = dropout, dropout_rng
 
     def forward(self, adj, x):
-        if self.dropout_rng is not None:
-            h = self.dropout_rng.relu_dropout(_Linear.apply(x, self.w0, False), self.dropout, self.training)
-        else:
-            h = _Linear.apply(x, self.w0, True)
-            h = torch.nn.functional.dropout(h, self.dropout, self.training)
-        return _Linear.apply(h, self.w1, False)
+        return _Linear.apply(self._relu_dropout_of_product(x, self.w0), self.w1, False)
 
 
-class _AcmMixer:
-    """The channel mix of one ACM layer on a one-job ops.AcmMixBatch: work buffers and the table over them per (rows, cols), built on
-    first use - before any capture - so that a captured forward / backward addresses the same memory on every replay.
-    What it requires: the buffers (aux among them) hold ONE forward pass, the latest.  A backward pass must either follow its own
-    forward pass with no other forward pass of this layer between them, or run eagerly: `version` counts forward passes on the host
-    and an eager backward pass that finds another forward pass in between runs its own again from the saved operands.  The counter
-    does not advance while a hipGraph replays, so inside a captured region a backward pass must follow its own forward pass there
-    (models.train_eval_graphed: forward, backward, Adam in one graph, the evaluation forward in another)."""
+class _OneJobLayer:
+    """A layer whose forward and backward pass are one launch each over a ONE-job ops table: work buffers and the table(s) over them per
+    (what keyed_on names, rows, cols), built on first use - before any capture - so that a captured forward / backward addresses the same
+    memory on every replay.
+    What it requires: the buffers (with what the forward launch leaves for the backward launch: aux, alpha) hold ONE forward pass, the
+    latest.  A backward pass must either follow its own forward pass with no other forward pass of this layer between them, or run
+    eagerly: `version` counts forward passes on the host and an eager backward pass that finds another forward pass in between runs
+    its own again from the saved operands.  The counter does not advance while a hipGraph replays, so inside a captured region a
+    backward pass must follow its own forward pass there (models.train_eval_graphed: forward, backward, Adam in one graph, the
+    evaluation forward in another).
+    A concrete layer states: `operands` - the buffers a forward pass fills, in the order of its tensor arguments and of the copies;
+    keyed_on(adj) - the objects whose id() is in the key, kept alive with the entry; build(adj, rows, cols, z) -> (buffers, the forward
+    table, the backward launch); gradients(b, gy, needs) - one per operand; and `restore_launches` - whether a stale backward pass has to
+    run the forward launch again, or only to put the operands back."""
 
-    def __init__(self, relu):
-        self.relu = bool(relu)
+    operands, restore_launches = (), True
+
+    def __init__(self):
         self._tables = {}
-        self.version = 0  # forward passes so far: a backward pass whose forward is not the latest one runs it again (aux is the table's)
+        self.version = 0  # forward passes so far: a backward pass whose forward is not the latest one puts its own operands back
 
-    def table(self, rows, cols, dev):
-        key = (rows, cols)
+    def table(self, adj, rows, cols, dev):
+        keep = self.keyed_on(adj)
+        key = (*map(id, keep), rows, cols)
         if key not in self._tables:
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
-            b = dict(inp=z(4, rows, cols), att=z(3, cols), wmix=z(3, 3), out=z(rows, cols), d_out=z(rows, cols), d=z(3, rows, cols),
-                     d_att=z(3, cols), d_wmix=z(3, 3))
-            entry = dict(low=b["inp"][0], high=b["inp"][1], high_agg=b["inp"][2], ident=b["inp"][3], att=b["att"], wmix=b["wmix"], out=b["out"],
-                         d_out=b["d_out"], d_low=b["d"][0], d_high=b["d"][1], d_ident=b["d"][2], d_att=b["d_att"], d_wmix=b["d_wmix"])
-            self._tables[key] = (b, ops.AcmMixBatch([entry], self.relu))
-        return self._tables[key]
+            self._tables[key] = (*self.build(adj, rows, cols, z), keep)
+        return self._tables[key][:3]
 
-    def run(self, inputs):
-        low, high, high_agg, ident, att, wmix = inputs
-        b, table = self.table(low.shape[0], low.shape[1], low.device)
-        for i, t in enumerate((low, high, high_agg, ident)):
-            b["inp"][i].copy_(t)
-        b["att"].copy_(att)
-        b["wmix"].copy_(wmix)
-        table.launch()
+    def stage(self, adj, operands, launch):
+        b, forward, backward = self.table(adj, operands[0].shape[0], operands[0].shape[1], operands[0].device)
+        for name, t in zip(self.operands, operands):
+            b[name].copy_(t)
+        if launch:
+            forward.launch()
         self.version += 1
-        return b, table
-
-    def __call__(self, low, high, high_agg, ident, att, wmix):
-        return _AcmMix.apply(low, high, high_agg, ident, att, wmix, self)
+        return b, backward
 
 
-class _AcmMix(torch.autograd.Function):
-    """out = 3 sum_c alpha_c H_c (include/wdg.h: wdg_acm_mix_batched_f32) and its backward pass, both on csrc/acm_mix.hip"""
+class _OneJob(torch.autograd.Function):
+    """out = layer(operands) and its backward pass, a launch each on the layer's one-job table (include/wdg.h states the arithmetic)"""
 
     @staticmethod
-    def forward(ctx, low, high, high_agg, ident, att, wmix, mixer):
-        b, _ = mixer.run((low, high, high_agg, ident, att, wmix))
-        ctx.save_for_backward(low, high, high_agg, ident, att, wmix)
-        ctx.mixer, ctx.version = mixer, mixer.version
+    def forward(ctx, layer, adj, *operands):
+        b, _ = layer.stage(adj, operands, True)
+        ctx.save_for_backward(*operands)
+        ctx.layer, ctx.adj, ctx.version = layer, adj, layer.version
         return b["out"].clone()
 
     @staticmethod
     def backward(ctx, gy):
-        mixer = ctx.mixer
-        if mixer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
-            b, table = mixer.run(ctx.saved_tensors)
+        layer = ctx.layer
+        if layer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
+            b, backward = layer.stage(ctx.adj, ctx.saved_tensors, layer.restore_launches)
         else:
-            b, table = mixer.table(gy.shape[0], gy.shape[1], gy.device)
+            b, _, backward = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
         b["d_out"].copy_(gy)
-        table.launch_backward()
+        backward()
+        return (None, None, *layer.gradients(b, gy, ctx.needs_input_grad[2:]))  # (needs: per operand, past layer and adj)
+
+
+class _AcmMixer(_OneJobLayer):
+    """The channel mix of one ACM layer, out = 3 sum_c alpha_c H_c (include/wdg.h: wdg_acm_mix_batched_f32), and its backward pass, both
+    on csrc/acm_mix.hip through a one-job ops.AcmMixBatch per (rows, cols); no graph.  A stale backward pass runs the forward launch
+    again: aux is the table's."""
+
+    operands = ("low", "high", "high_agg", "ident", "att", "wmix")
+
+    def __init__(self, relu):
+        super().__init__()
+        self.relu = bool(relu)
+
+    def keyed_on(self, adj):
+        return ()
+
+    def build(self, adj, rows, cols, z):
+        inp, att, wmix, out, d_out, d, d_att, d_wmix = (z(4, rows, cols), z(3, cols), z(3, 3), z(rows, cols), z(rows, cols), z(3, rows, cols),
+                                                        z(3, cols), z(3, 3))
+        entry = dict(low=inp[0], high=inp[1], high_agg=inp[2], ident=inp[3], att=att, wmix=wmix, out=out, d_out=d_out, d_low=d[0],
+                     d_high=d[1], d_ident=d[2], d_att=d_att, d_wmix=d_wmix)
+        table = ops.AcmMixBatch([entry], self.relu)
+        return dict(entry, d=d), table, table.launch_backward
+
+    def gradients(self, b, gy, needs):
         d = b["d"].clone()
-        return d[0], d[1], -d[1], d[2], b["d_att"].clone(), b["d_wmix"].clone(), None
+        return d[0], d[1], -d[1], d[2], b["d_att"].clone(), b["d_wmix"].clone()
+
+    def __call__(self, low, high, high_agg, ident, att, wmix):
+        return _OneJob.apply(self, None, low, high, high_agg, ident, att, wmix)
 
 
 def _acm_parameters(nfeat, width):
@@ -313,7 +367,7 @@ def _acm_parameters(nfeat, width):
     (weight [nfeat, 3 width] = [W_L | W_H | W_I], att, wmix)"""
     if not 1 <= width <= ops.AcmMixBatch.MAX_COLS:
         raise ValueError(f"an ACM layer of width {width}: the mix kernel holds 1..{ops.AcmMixBatch.MAX_COLS} (256) columns")
-    ws = [torch.nn.init.xavier_uniform_(torch.empty(nfeat, width)) for _ in range(3)]
+    ws = [_xavier(nfeat, width).detach() for _ in range(3)]
     att = (torch.rand(3, width) * 2 - 1) / width ** 0.5
     wmix = (torch.rand(3, 3) * 2 - 1) / 3 ** 0.5
     return torch.nn.Parameter(torch.cat(ws, 1)), torch.nn.Parameter(att), torch.nn.Parameter(wmix)
@@ -340,7 +394,7 @@ class ACMSGC1(torch.nn.Module):
         return self._mix(ya[:, :c], xb[:, :c], ya[:, c:], xb[:, c:], self.att, self.wmix)
 
 
-class ACMGCN2(torch.nn.Module):
+class ACMGCN2(_HiddenDropout, torch.nn.Module):
     """ACM-GCN-2: layer 1 (F -> nhid, activation on) -> dropout(relu(.)) -> layer 2 (nhid -> C, no activation); bias-free, A_hat the
     random-walk normalisation as for GCN2.  A layer is one product M [W_L | W_H | W_I], one aggregation of its first two
     column blocks and the mix.  dropout_rng: as for GCN2 (layer 1's output is non-negative: relu + dropout apply as they stand)."""
@@ -361,41 +415,31 @@ class ACMGCN2(torch.nn.Module):
 
     def forward(self, adj, x):
         o = self._layer(adj, x, self.w0, self.att0, self.wmix0, self.nhid, self._mix0)
-        if self.dropout_rng is not None:
-            h = self.dropout_rng.relu_dropout(o, self.dropout, self.training)
-        else:
-            h = torch.nn.functional.dropout(torch.relu(o), self.dropout, self.training)
-        return self._layer(adj, h, self.w1, self.att1, self.wmix1, self.nclass, self._mix1)
+        return self._layer(adj, self._relu_dropout(o), self.w1, self.att1, self.wmix1, self.nclass, self._mix1)
 
 
-class _GatLayer:
-    """One attention layer Att_heads(H; a) on a one-job ops.GatBatch: work buffers and the table over them per (graph, rows, heads, w),
-    built on first use - before any capture - so that a captured forward / backward addresses the same memory on every replay.
-    As for _AcmMixer the buffers (alpha among them) hold ONE forward pass, the latest: `version` counts forward passes on the host, and
-    an eager backward pass that finds another forward pass in between runs its own again from the saved operands.  Inside a captured
-    region a backward pass must follow its own forward pass there (models.train_eval_graphed)."""
+class _GatLayer(_OneJobLayer):
+    """One attention layer Att_heads(H; a), out_i = sum_j alpha_ij H_j (include/wdg.h: wdg_gat_forward_batched_f32), and its backward
+    pass, both on csrc/gat.hip through a one-job ops.GatBatch per (graph, rows, heads w).  A stale backward pass runs the forward launch
+    again: alpha is the table's."""
+
+    operands = ("h", "s")
 
     def __init__(self, heads, slope):
+        super().__init__()
         self.heads, self.slope = int(heads), float(slope)
-        self._tables, self._index = {}, None
-        self.version = 0
+        self._index = None
 
-    def table(self, adj, rows, cols, dev):
-        plan = adj.attention_plan()
-        key = (id(plan), rows, cols)
-        if key not in self._tables:
-            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
-            b = dict(h=z(rows, cols), s=z(rows, 2 * self.heads), out=z(rows, cols), d_out=z(rows, cols), d_h=z(rows, cols), d_s=z(rows, 2 * self.heads))
-            self._tables[key] = (b, ops.GatBatch([dict(plan, heads=self.heads, **b)], self.slope), plan)  # (plan: kept alive with its id)
-        return self._tables[key][:2]
+    def keyed_on(self, adj):
+        return (adj.attention_plan(),)
 
-    def run(self, h, s, adj):
-        b, table = self.table(adj, h.shape[0], h.shape[1], h.device)
-        b["h"].copy_(h)
-        b["s"].copy_(s)
-        table.launch()
-        self.version += 1
-        return b, table
+    def build(self, adj, rows, cols, z):
+        b = dict(h=z(rows, cols), s=z(rows, 2 * self.heads), out=z(rows, cols), d_out=z(rows, cols), d_h=z(rows, cols), d_s=z(rows, 2 * self.heads))
+        table = ops.GatBatch([dict(adj.attention_plan(), heads=self.heads, **b)], self.slope)
+        return b, table, table.launch_backward
+
+    def gradients(self, b, gy, needs):
+        return b["d_h"].clone(), b["d_s"].clone()
 
     def operand(self, att):
         """blockdiag(a_dst, a_src) [heads w, 2 heads] of att [2, heads, w]: element (h w + k, h) = a_dst[h, k], (h w + k, heads + h) =
@@ -409,34 +453,11 @@ class _GatLayer:
 
     def __call__(self, adj, h, att):
         """h [n, heads w] -> Att(h; att) [n, heads w]; the scores are a product on the GEMM: autograd carries d_S back into h and att"""
-        s = _Linear.apply(h, self.operand(att), False)
-        return _GatAggregate.apply(h, s, adj, self)
+        return _OneJob.apply(self, adj, h, _Linear.apply(h, self.operand(att), False))
 
     def alpha(self, adj, rows, cols, dev):
         """[nnz, heads]: the attention weights of the latest forward pass on this graph, in the order of adj.graph's entries"""
         return self.table(adj, rows, cols, dev)[1].alpha_of[0].clone()
-
-
-class _GatAggregate(torch.autograd.Function):
-    """out_i = sum_j alpha_ij H_j (include/wdg.h: wdg_gat_forward_batched_f32) and its backward pass, both on csrc/gat.hip"""
-
-    @staticmethod
-    def forward(ctx, h, s, adj, layer):
-        b, _ = layer.run(h, s, adj)
-        ctx.save_for_backward(h, s)
-        ctx.adj, ctx.layer, ctx.version = adj, layer, layer.version
-        return b["out"].clone()
-
-    @staticmethod
-    def backward(ctx, gy):
-        layer = ctx.layer
-        if layer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
-            b, table = layer.run(*ctx.saved_tensors, ctx.adj)
-        else:
-            b, table = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
-        b["d_out"].copy_(gy)
-        table.launch_backward()
-        return b["d_h"].clone(), b["d_s"].clone(), None, None
 
 
 def _gat_parameters(nfeat, heads, w):
@@ -445,9 +466,7 @@ def _gat_parameters(nfeat, heads, w):
     if not 1 <= heads <= ops.GatBatch.MAX_HEADS or w < 1 or heads * w > ops.GatBatch.MAX_COLS:
         raise ValueError(f"an attention layer of {heads} heads of width {w}: the kernel holds 1..{ops.GatBatch.MAX_HEADS} heads and "
                          f"heads * w <= {ops.GatBatch.MAX_COLS}")
-    weight = torch.nn.init.xavier_uniform_(torch.empty(nfeat, heads * w))
-    att = (torch.rand(2, heads, w) * 2 - 1) / w ** 0.5
-    return torch.nn.Parameter(weight), torch.nn.Parameter(att)
+    return _xavier(nfeat, heads * w), torch.nn.Parameter((torch.rand(2, heads, w) * 2 - 1) / w ** 0.5)
 
 
 class GAT1(torch.nn.Module):
@@ -463,7 +482,7 @@ class GAT1(torch.nn.Module):
         return self._att(adj, _Linear.apply(x, self.weight, False), self.att)
 
 
-class GAT2(torch.nn.Module):
+class GAT2(_HiddenDropout, torch.nn.Module):
     """GAT-2: hidden = relu_dropout(Att_heads(X W0; a0)) with heads * nhid columns, logits = Att_1(hidden W1; a1); bias-free, feature
     dropout only (GCN2's two routes: dropout_rng None - torch's - or a DeviceDropout); no dropout on alpha.  DESIGN 4.25."""
 
@@ -476,93 +495,49 @@ class GAT2(torch.nn.Module):
 
     def forward(self, adj, x):
         o = self._att0(adj, _Linear.apply(x, self.w0, False), self.att0)
-        if self.dropout_rng is not None:
-            h = self.dropout_rng.relu_dropout(o, self.dropout, self.training)
-        else:
-            h = torch.nn.functional.dropout(torch.relu(o), self.dropout, self.training)
-        return self._att1(adj, _Linear.apply(h, self.w1, False), self.att1)
+        return self._att1(adj, _Linear.apply(self._relu_dropout(o), self.w1, False), self.att1)
 
     def attention(self, adj, x):
         """-> (alpha of layer 1 [nnz, heads], alpha of layer 2 [nnz, 1]) of an evaluation forward pass on (adj, x), run here (the
         model's mode is put back): the weights of adj.graph's stored entries, in their order"""
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                self(adj, x)
-        finally:
-            self.train(was_training)
+        _eval_forward(self, adj, x)
         n, dev = x.shape[0], self.w0.device
         return self._att0.alpha(adj, n, self.w0.shape[1], dev), self._att1.alpha(adj, n, self.w1.shape[1], dev)
 
 
 class _SignedAttLayer(_GatLayer):
-    """One signed-attention layer eps R + FA(H; a) on a one-job ops.SignedAttBatch, with the pattern AND the two scale vectors of the
-    NormAdj it is given: _GatLayer's buffers, table per (graph, rows, cols) built on first use - before any capture -, `version` rule and
-    score operand; the residual R has a buffer of its own (R may be H itself: the kernel's operands do not overlap)."""
+    """One signed-attention layer out_i = eps R_i + sum_j a_ij H_j (include/wdg.h: wdg_signed_att_forward_batched_f32) and its backward
+    pass, both on csrc/signed_att.hip through a one-job ops.SignedAttBatch, with the pattern AND the two scale vectors of the NormAdj it
+    is given: _GatLayer's buffers, key and score operand; the residual R has a buffer of its own (R may be H itself: the kernel's
+    operands do not overlap) and its gradient eps d_out is formed here (the kernels do not write it)."""
+
+    operands = ("h", "s", "res")
 
     def __init__(self, heads, eps):
         super().__init__(heads, 0.0)
         self.eps = float(eps)
 
-    def table(self, adj, rows, cols, dev):
-        plan = adj.attention_plan()
-        key = (id(plan), rows, cols)
-        if key not in self._tables:
-            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
-            b = dict(h=z(rows, cols), s=z(rows, 2 * self.heads), res=z(rows, cols), out=z(rows, cols), d_out=z(rows, cols), d_h=z(rows, cols),
-                     d_s=z(rows, 2 * self.heads))
-            entry = dict(plan, heads=self.heads, row_scale=adj.row_scale, col_scale=adj.col_scale, **b)
-            self._tables[key] = (b, ops.SignedAttBatch([entry], self.eps), plan, adj)  # (plan, adj: kept alive with the id and the scales)
-        return self._tables[key][:2]
+    def keyed_on(self, adj):
+        return (adj.attention_plan(), adj)  # (adj: for its scales)
 
-    def run(self, h, s, res, adj):
-        b, table = self.table(adj, h.shape[0], h.shape[1], h.device)
-        b["h"].copy_(h)
-        b["s"].copy_(s)
-        b["res"].copy_(res)
-        table.launch()
-        self.version += 1
-        return b, table
+    def build(self, adj, rows, cols, z):
+        b = dict(h=z(rows, cols), s=z(rows, 2 * self.heads), res=z(rows, cols), out=z(rows, cols), d_out=z(rows, cols), d_h=z(rows, cols),
+                 d_s=z(rows, 2 * self.heads))
+        entry = dict(adj.attention_plan(), heads=self.heads, row_scale=adj.row_scale, col_scale=adj.col_scale, **b)
+        table = ops.SignedAttBatch([entry], self.eps)
+        return b, table, table.launch_backward
+
+    def gradients(self, b, gy, needs):
+        return b["d_h"].clone(), b["d_s"].clone(), (gy * self.eps if needs[2] else None)
 
     def __call__(self, adj, h, att, res):
         """h, res [n, heads w] -> eps res + FA(h; att) [n, heads w]; the scores are a product on the GEMM, as in _GatLayer"""
-        s = _Linear.apply(h, self.operand(att), False)
-        return _SignedAttAggregate.apply(h, s, res, adj, self)
-
-
-class _SignedAttAggregate(torch.autograd.Function):
-    """out_i = eps res_i + sum_j a_ij H_j (include/wdg.h: wdg_signed_att_forward_batched_f32) and its backward pass, both on
-    csrc/signed_att.hip; the residual's gradient eps d_out is formed here (the kernels do not write it)"""
-
-    @staticmethod
-    def forward(ctx, h, s, res, adj, layer):
-        b, _ = layer.run(h, s, res, adj)
-        ctx.save_for_backward(h, s, res)
-        ctx.adj, ctx.layer, ctx.version = adj, layer, layer.version
-        return b["out"].clone()
-
-    @staticmethod
-    def backward(ctx, gy):
-        layer = ctx.layer
-        if layer.version != ctx.version:  # another forward pass has overwritten the table's buffers since: restore them
-            b, table = layer.run(*ctx.saved_tensors, ctx.adj)
-        else:
-            b, table = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
-        b["d_out"].copy_(gy)
-        table.launch_backward()
-        return b["d_h"].clone(), b["d_s"].clone(), (gy * layer.eps if ctx.needs_input_grad[2] else None), None, None
+        return _OneJob.apply(self, adj, h, _Linear.apply(h, self.operand(att), False), res)
 
 
 def _signed_weights_of(model, layers, adj, x, cols):
-    """the alpha of every layer of `layers` after an evaluation forward pass of `model` on (adj, x), run here (the mode is put back)"""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            model(adj, x)
-    finally:
-        model.train(was_training)
+    """the alpha of every layer of `layers` after an evaluation forward pass of `model` on (adj, x)"""
+    _eval_forward(model, adj, x)
     return tuple(layer.alpha(adj, x.shape[0], cols, x.device) for layer in layers)
 
 
@@ -585,7 +560,7 @@ class FAGCN1(torch.nn.Module):
         return _signed_weights_of(self, [self._att], adj, x, self.weight.shape[1])
 
 
-class FAGCN2(torch.nn.Module):
+class FAGCN2(_HiddenDropout, torch.nn.Module):
     """FAGCN-2: H0 = relu_dropout(X W0), H_l = eps H0 + FA_1(H_{l-1}; a_l) for l = 1..layers, logits = H_L W1; bias-free, one head of
     width nhid, feature dropout only (GCN2's two routes: dropout_rng None - torch's - or a DeviceDropout); no dropout on the weights, eps
     is not learnt.  DESIGN 4.27.  Parameters are drawn in this order: W0 (xavier_uniform, [nfeat, nhid]), then a_1 .. a_layers
@@ -598,16 +573,12 @@ class FAGCN2(torch.nn.Module):
         self.w0, first = _gat_parameters(nfeat, 1, nhid)
         rest = [torch.nn.Parameter((torch.rand(2, 1, nhid) * 2 - 1) / nhid ** 0.5) for _ in range(layers - 1)]
         self.att = torch.nn.ParameterList([first] + rest)
-        self.w1 = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nhid, nclass)))
+        self.w1 = _xavier(nhid, nclass)
         self.dropout, self.dropout_rng = dropout, dropout_rng
         self._att = [_SignedAttLayer(1, eps) for _ in range(layers)]
 
     def forward(self, adj, x):
-        if self.dropout_rng is not None:
-            h0 = self.dropout_rng.relu_dropout(_Linear.apply(x, self.w0, False), self.dropout, self.training)
-        else:
-            h0 = torch.nn.functional.dropout(_Linear.apply(x, self.w0, True), self.dropout, self.training)
-        h = h0
+        h = h0 = self._relu_dropout_of_product(x, self.w0)
         for layer, att in zip(self._att, self.att):
             h = layer(adj, h, att, h0)
         return _Linear.apply(h, self.w1, False)
@@ -629,76 +600,49 @@ def ppr_coefficients(K, alpha):
     return g.to(torch.float32)
 
 
-class _PolyFilterLayer:
-    """The filter F(H0; gamma) = sum_k gamma_k A_hat^k H0 on two one-job ops.PolyFilterBatch tables over work buffers, per (graph, rows,
-    cols), built on first use - before any capture.  The forward table runs the pattern with the NormAdj's scales; the backward table is
-    ONE more job of the same kernel on graph_t with the two scales swapped, v = d_out and u = H0: its out is d_H0 and its dots are
-    d_gamma, because d_gamma_k = <d_out, A_hat^k H0> = <(A_hat^T)^k d_out, H0>.  _GatLayer's `version` rule: the buffers hold the
-    operands of the latest forward pass, and an eager backward pass that finds another one in between puts its own back first.
+class _PolyFilterLayer(_OneJobLayer):
+    """The filter F(H0; gamma) = sum_k gamma_k A_hat^k H0 (include/wdg.h: wdg_poly_filter_batched_f32) and its backward pass, both on
+    csrc/poly_filter.hip through two one-job ops.PolyFilterBatch tables per (graph, rows, cols).  The forward table runs the pattern with
+    the NormAdj's scales; the backward table is ONE more job of the same kernel on graph_t with the two scales swapped, v = d_out and
+    u = H0: its out is d_H0 and its dots are d_gamma, because d_gamma_k = <d_out, A_hat^k H0> = <(A_hat^T)^k d_out, H0>.  So a stale
+    backward pass only puts H0 and gamma back: the backward job reads nothing the forward launch wrote.
     max_rows: the largest graph that takes the fused route (None: what one column of the kernel holds); a larger one, or fused=False,
     runs hop by hop - K _Aggregate steps and torch adds, autograd's backward."""
+
+    operands, restore_launches = ("h", "gamma"), False
 
     def __init__(self, order, fused=True, max_rows=None):
         if not 0 <= order <= ops.PolyFilterBatch.MAX_ORDER:
             raise ValueError(f"a polynomial filter of order {order}: the kernel runs 0..{ops.PolyFilterBatch.MAX_ORDER} hops")
+        super().__init__()
         self.order, self.fused, self.max_rows = int(order), bool(fused), max_rows
-        self._tables = {}
-        self.version = 0
 
     def is_fused(self, rows):
         limit = ops.PolyFilterBatch.max_rows(1) if self.max_rows is None else min(int(self.max_rows), ops.PolyFilterBatch.max_rows(1))
         return self.fused and rows <= limit
 
-    def table(self, adj, rows, cols, dev):
-        key = (id(adj), rows, cols)
-        if key not in self._tables:
-            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
-            b = dict(h=z(rows, cols), out=z(rows, cols), gamma=z(self.order + 1, 1), d_out=z(rows, cols), d_h=z(rows, cols), d_gamma=z(self.order + 1, 1))
-            fwd = ops.PolyFilterBatch([dict(graph=adj.graph, row_scale=adj.row_scale, col_scale=adj.col_scale, v=b["h"], out=b["out"], gamma=b["gamma"],
-                                            order=self.order)])
-            bwd = ops.PolyFilterBatch([dict(graph=adj.graph_t, row_scale=adj.col_scale, col_scale=adj.row_scale, v=b["d_out"], out=b["d_h"],
-                                            gamma=b["gamma"], order=self.order, u=b["h"], dots=b["d_gamma"])])  # (R A C)^T = C A^T R
-            self._tables[key] = (b, fwd, bwd, adj)  # (adj: kept alive with its id and its scales)
-        return self._tables[key][:3]
+    def keyed_on(self, adj):
+        return (adj,)  # (for its scales as well)
 
-    def stage(self, h, gamma, adj):
-        b, fwd, bwd = self.table(adj, h.shape[0], h.shape[1], h.device)
-        b["h"].copy_(h)
-        b["gamma"].copy_(gamma.reshape(-1, 1))
-        self.version += 1
-        return b, fwd, bwd
+    def build(self, adj, rows, cols, z):
+        h, out, gamma, d_out, d_h, d_gamma = z(rows, cols), z(rows, cols), z(self.order + 1, 1), z(rows, cols), z(rows, cols), z(self.order + 1, 1)
+        fwd = ops.PolyFilterBatch([dict(graph=adj.graph, row_scale=adj.row_scale, col_scale=adj.col_scale, v=h, out=out, gamma=gamma,
+                                        order=self.order)])
+        bwd = ops.PolyFilterBatch([dict(graph=adj.graph_t, row_scale=adj.col_scale, col_scale=adj.row_scale, v=d_out, out=d_h, gamma=gamma,
+                                        order=self.order, u=h, dots=d_gamma)])  # (R A C)^T = C A^T R
+        return dict(h=h, out=out, gamma=gamma.reshape(-1), d_out=d_out, d_h=d_h, d_gamma=d_gamma.reshape(-1)), fwd, bwd.launch
+
+    def gradients(self, b, gy, needs):
+        return b["d_h"].clone(), (b["d_gamma"].clone() if needs[1] else None)
 
     def __call__(self, adj, h, gamma):
         if self.is_fused(h.shape[0]):
-            return _PolyFilter.apply(h, gamma, adj, self)
+            return _OneJob.apply(self, adj, h, gamma)
         t, out = h, gamma[0] * h
         for k in range(1, self.order + 1):
             t = adj.matmul(t)
             out = out + gamma[k] * t
         return out
-
-
-class _PolyFilter(torch.autograd.Function):
-    """out = sum_k gamma_k A_hat^k H0 (include/wdg.h: wdg_poly_filter_batched_f32) and its backward pass, both on csrc/poly_filter.hip"""
-
-    @staticmethod
-    def forward(ctx, h, gamma, adj, layer):
-        b, fwd, _ = layer.stage(h, gamma, adj)
-        fwd.launch()
-        ctx.save_for_backward(h, gamma)
-        ctx.adj, ctx.layer, ctx.version = adj, layer, layer.version
-        return b["out"].clone()
-
-    @staticmethod
-    def backward(ctx, gy):
-        layer = ctx.layer
-        if layer.version != ctx.version:  # another forward pass has overwritten H0 and gamma since: put them back
-            b, _, bwd = layer.stage(*ctx.saved_tensors, ctx.adj)
-        else:
-            b, _, bwd = layer.table(ctx.adj, gy.shape[0], gy.shape[1], gy.device)
-        b["d_out"].copy_(gy)
-        bwd.launch()
-        return b["d_h"].clone(), (b["d_gamma"].reshape(-1).clone() if ctx.needs_input_grad[1] else None), None, None
 
 
 class _GPRBase(torch.nn.Module):
@@ -726,14 +670,14 @@ class GPRGNN1(_GPRBase):
 
     def __init__(self, nfeat, nclass, order=10, alpha=0.1, learn=True, fused=True, fused_max_rows=None):
         super().__init__()
-        self.weight = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nfeat, nclass)))
+        self.weight = _xavier(nfeat, nclass)
         self._init_filter(order, alpha, learn, fused, fused_max_rows)
 
     def forward(self, adj, x):
         return self._filter(adj, _Linear.apply(x, self.weight, False), self.gamma)
 
 
-class GPRGNN2(_GPRBase):
+class GPRGNN2(_HiddenDropout, _GPRBase):
     """GPR-GNN-2: logits = F(relu_dropout(X W0) W1; gamma) with GPRGNN1's filter F; bias-free, feature dropout only (GCN2's two routes:
     dropout_rng None - torch's - or a DeviceDropout), no dropout between the hops.  learn=False freezes gamma: APPNP.  DESIGN 4.28.
     Parameters are drawn in this order: W0 (xavier_uniform, [nfeat, nhid]), W1 (xavier_uniform, [nhid, nclass]), then gamma
@@ -741,16 +685,12 @@ class GPRGNN2(_GPRBase):
 
     def __init__(self, nfeat, nclass, nhid=64, order=10, alpha=0.1, dropout=0.5, dropout_rng=None, learn=True, fused=True, fused_max_rows=None):
         super().__init__()
-        self.w0 = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nfeat, nhid)))
-        self.w1 = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nhid, nclass)))
+        self.w0, self.w1 = _xavier(nfeat, nhid), _xavier(nhid, nclass)
         self.dropout, self.dropout_rng = dropout, dropout_rng
         self._init_filter(order, alpha, learn, fused, fused_max_rows)
 
     def forward(self, adj, x):
-        if self.dropout_rng is not None:
-            h = self.dropout_rng.relu_dropout(_Linear.apply(x, self.w0, False), self.dropout, self.training)
-        else:
-            h = torch.nn.functional.dropout(_Linear.apply(x, self.w0, True), self.dropout, self.training)
+        h = self._relu_dropout_of_product(x, self.w0)
         return self._filter(adj, _Linear.apply(h, self.w1, False), self.gamma)
 
 
@@ -763,9 +703,16 @@ class TwoHopAdj:
     Building it runs the two-hop build, a one-time plan with a host read-back: not inside a stream capture."""
 
     def __init__(self, adj, symmetric=1):
-        g = CsrGraph.from_any(adj).rebuild(ops.COO_DROP_SELF_LOOPS)
+        self._channels(self._without_diagonal(adj), symmetric, ops.two_hop)
+
+    @staticmethod
+    def _without_diagonal(adj):
+        return CsrGraph.from_any(adj).rebuild(ops.COO_DROP_SELF_LOOPS)
+
+    def _channels(self, g, symmetric, second):
+        """.one over g, then .two over second(g); .graph, .n"""
         self.one = NormAdj(g, symmetric, add_self_loops=False)
-        self.two = NormAdj(ops.two_hop(g), symmetric, add_self_loops=False)
+        self.two = NormAdj(second(g), symmetric, add_self_loops=False)
         self.graph, self.n = self.one.graph, g.n_rows
 
 
@@ -780,16 +727,18 @@ class KnnAdj(TwoHopAdj):
     nothing of this: GCN2 on NormAdj(ops.knn_graph(x, k))."""
 
     def __init__(self, adj, x, k=10, metric="cosine", symmetric=1):
-        g = CsrGraph.from_any(adj).rebuild(ops.COO_DROP_SELF_LOOPS)
+        g = self._without_diagonal(adj)
         if g.n_rows != g.n_cols or len(x.shape) != 2 or x.shape[0] != g.n_rows:
             raise ValueError(f"KnnAdj: a square graph and a feature row per node expected, got {g.n_rows} x {g.n_cols} and x of shape {tuple(x.shape)}")
-        self.one = NormAdj(g, symmetric, add_self_loops=False)
-        self.knn = ops.knn_graph(x, k, metric, "union")
-        self.two = NormAdj(self.knn, symmetric, add_self_loops=False)
-        self.graph, self.n = self.one.graph, g.n_rows
+
+        def knn(_):
+            self.knn = ops.knn_graph(x, k, metric, "union")
+            return self.knn
+
+        self._channels(g, symmetric, knn)
 
 
-class _H2GCN(torch.nn.Module):
+class _H2GCN(_HiddenDropout, torch.nn.Module):
     """R0 = relu(X W_e); R_k = [A1_hat R_{k-1} | A2_hat R_{k-1}] for k = 1..rounds (width nhid 2^k); R = [R0 | ... | R_K];
     logits = dropout(R) W_c.  Bias-free.  Every entry of R is >= 0 (a ReLU output, then sums with the non-negative weights of a
     TwoHopAdj), so relu_dropout(R) of a DeviceDropout IS dropout(R)."""
@@ -797,8 +746,7 @@ class _H2GCN(torch.nn.Module):
     def __init__(self, rounds, nfeat, nclass, nhid, dropout, dropout_rng):
         super().__init__()
         self.rounds = rounds
-        self.w_e = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nfeat, nhid)))
-        self.w_c = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(nhid * (2 ** (rounds + 1) - 1), nclass)))
+        self.w_e, self.w_c = _xavier(nfeat, nhid), _xavier(nhid * (2 ** (rounds + 1) - 1), nclass)
         self.dropout, self.dropout_rng = dropout, dropout_rng
 
     def representation(self, adj, x):
@@ -813,12 +761,7 @@ class _H2GCN(torch.nn.Module):
         return torch.cat(reps, 1)
 
     def forward(self, adj, x):
-        r = self.representation(adj, x)
-        if self.dropout_rng is not None:
-            r = self.dropout_rng.relu_dropout(r, self.dropout, self.training)
-        else:
-            r = torch.nn.functional.dropout(r, self.dropout, self.training)
-        return _Linear.apply(r, self.w_c, False)
+        return _Linear.apply(self._dropout_of_nonnegative(self.representation(adj, x)), self.w_c, False)
 
 
 class H2GCN1(_H2GCN):
