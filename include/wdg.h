@@ -648,6 +648,9 @@ int wdg_las_batched_f32(const wdg_las_job *jobs_dev, int32_t n_jobs, int32_t max
  * The reference has no X.W (its models live upstream, gnns_on_syn.py:1-249 holds only results);
  * this is the build-defined SGC-1 / GCN-2 transform of SURVEY.md 7.3 (K10), and the Gram products of
  * utils/homophily_metrics.py:234-235,246 (B = A^T via transb).
+ * K = 0 is the empty sum: act(bias), or act(0) without a bias, is stored into all of C; A and B may be NULL then and are never
+ * dereferenced.  WDG_ACT_RELU in this and the following GEMM entry points turns negative values into 0 and keeps a NaN a NaN
+ * (torch.relu's rule, not fmaxf's); the hidden activation of the fused two-layer transform below is fmaxf(v, 0).
  */
 int wdg_gemm_f32(const float *A, int64_t lda, const float *B, int64_t ldb, int transb, const float *bias, int act,
                  float *C, int64_t ldc, int32_t M, int32_t N, int32_t K, wdg_stream_t stream);
@@ -657,9 +660,14 @@ int wdg_gemm_f32(const float *A, int64_t lda, const float *B, int64_t ldb, int t
  * B in LDS for shorter rows) instead of 128-row MFMA tiles.  Summation order: per lane k = l, l + L, ... ascending (L lanes per
  * row), then a fixed butterfly over the row's lanes - bitwise
  * reproducible, within fp32 rounding of wdg_gemm_f32's k-ordered chain (not bit-identical to it).  B is [K, N] (no transb).
+ * K = 0 is the empty sum: act(bias), or act(0) without a bias, is stored into all of C; A and B may be NULL then and are never
+ * dereferenced.
  */
 int wdg_gemm_skinny_f32(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, int act, float *C,
                         int64_t ldc, int32_t M, int32_t N, int32_t K, wdg_stream_t stream);
+/* L of the above, the lanes that share a row of K entries: 1 (K <= 16), 4 (K <= 128), 16 (K <= 512) or 64 (a wave per row).  The
+ * launcher asks this very function (a host entry point: no device needed). */
+int32_t wdg_gemm_skinny_lanes(int32_t K);
 
 /* Many independent products in one launch (every graph of a sweep batch with its own weights); B is [K,N]. */
 typedef struct wdg_gemm_job {
@@ -679,6 +687,8 @@ int wdg_gemm_batched_f32(const wdg_gemm_job *jobs_dev, int32_t n_jobs, int32_t m
  * (wdg_gemm_splitk_workspace_bytes), and a second launch adds the partials in split order, then bias and activation.  Each
  * partial is the k-ordered fma chain of its range and the ranges are added in order: bitwise reproducible, but NOT the single
  * chain of wdg_gemm_f32 - the two agree to fp32 rounding.  Replaces the same `x @ W` as wdg_gemm_f32.
+ * K < 16 splits (K = 0 among them) is wdg_gemm_f32's single chain, workspace unused; with K = 0 act(bias), or act(0) without a
+ * bias, is stored into all of C, A and B may be NULL and are never dereferenced.
  */
 int32_t wdg_gemm_splitk_plan(int32_t M, int32_t N, int32_t K);
 size_t wdg_gemm_splitk_workspace_bytes(int32_t M, int32_t N, int32_t splits);
@@ -692,6 +702,9 @@ int wdg_gemm_splitk_f32(const float *A, int64_t lda, const float *B, int64_t ldb
 #define WDG_GEMM_A_VEC4 1u
 int wdg_gemm_batched_flags_f32(const wdg_gemm_job *jobs_dev, int32_t n_jobs, int32_t max_M, int32_t max_N,
                                int32_t max_K, uint32_t flags, wdg_stream_t stream);
+/* 1 when a launch of these sizes whose operands keep the WDG_GEMM_A_VEC4 promise takes the B-resident kernel (wdg_gemm_f32 with
+ * n_jobs = 1, or a table with the flag), 0 when it takes the tile kernel; reads WDG_GEMM_TILE / WDG_GEMM_RESIDENT as the launch does */
+int wdg_gemm_resident_eligible(int32_t n_jobs, int32_t max_M, int32_t max_N, int32_t K);
 
 /* Fused two-layer feature transform Z = act(A W0 + b0) W1 + b1 for every graph of a batch in one launch and one pass
  * over A (hidden width H <= 64, C <= 8 outputs, K <= 512): the build-defined GCN-2 feature path relu(Y W0) W1 (SURVEY

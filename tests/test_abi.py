@@ -47,6 +47,8 @@ def test_host_side_queries_need_no_gpu():
     assert L.lib.wdg_spmm_plan(1, 2000, 2000, 500, 0, ctypes.byref(slab), ctypes.byref(thr)) == 0  # LDS slab family
     assert slab.value in (4, 8, 16, 32) and thr.value in (512, 1024)
     assert L.lib.wdg_spmm_plan(1, 200000, 200000, 7, 0, ctypes.byref(slab), ctypes.byref(thr)) == 1  # row gather
+    assert [L.lib.wdg_gemm_skinny_lanes(k) for k in (0, 16, 17, 128, 129, 512, 513)] == [1, 1, 4, 4, 16, 16, 64]  # lanes per row of the skinny product
+    assert L.lib.wdg_gemm_resident_eligible(1, 4096, 64, 6) == 0 and L.lib.wdg_gemm_resident_eligible(1, 4096, 65, 64) == 0  # K % 4, N > 64: the tile kernel
 
 
 def test_argument_refusals_need_no_gpu():

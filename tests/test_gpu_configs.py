@@ -131,8 +131,10 @@ def test_c5_twitch_scale(oracle):
 
 @pytest.mark.parametrize("m,n,k,pad", [(2708, 7, 1433, 0), (5201, 5, 2089, 3), (1, 1, 1, 0), (9, 8, 4100, 0), (1000, 2, 7, 1), (17, 3, 2048, 0)])
 def test_skinny_gemm_against_the_oracle(oracle, m, n, k, pad):
-    """wdg_gemm_skinny_f32 (N <= 8: the SGC-1 head): any K (chunks of 2048 through LDS), unaligned rows (lda = K + pad), bias +
-    relu, ragged last row group; fp32 within 1e-5 of the oracle's k-ordered product, bitwise reproducible"""
+    """wdg_gemm_skinny_f32 (N <= 8: the SGC-1 head): any K (these K reach the one-lane kernel, K <= 16, and the wave per row,
+    K > 512; B passes through LDS only for K <= 512, in one piece; the 4- and 16-lane kernels and every boundary are
+    tests/test_gpu_gemm_edges.py's), unaligned rows (lda = K + pad), bias + relu, ragged last row group; fp32 within 1e-5 of the
+    oracle's k-ordered product, bitwise reproducible"""
     from wdg_amd import ops
     rng = np.random.default_rng(m + 3 * n + k)
     store = rng.standard_normal((m, k + pad)).astype(np.float32)

@@ -27,6 +27,10 @@ using namespace wdg;
 constexpr int BM = 128, BK = 16, THREADS = 256;
 constexpr int LDA_S = BK + 1;  // As[m][k], odd stride -> lanes m=0..31 hit distinct banks
 
+// WDG_ACT_RELU of the GEMM epilogues: negative values become 0 and a NaN STAYS a NaN, as torch.relu has it (fmaxf(v, 0) returns 0
+// for a NaN: a diverged product would come out of the activation looking finite)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
 // One launch serves a single problem (descriptor by value) or a table of independent problems (blockIdx.z = job):
 // the sweep transforms every graph's features with that graph's own weights in one go.
 // Epilogue of one 32-row x (NT x 32)-column tile held in MFMA accumulators.  C/D map of a 32x32 tile: col = lane & 31,
@@ -57,7 +61,7 @@ __device__ __forceinline__ void tile_store(const f32x16 (&acc)[NT], float (&bv)[
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float v = acc[t][r] + bv[t];
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = relu_keep_nan(v);
             if (full || row0 + (r & 3) + 8 * (r >> 2) + 4 * lk < M) *p = v;
             p += ((r & 3) == 3) ? 5 * ldc : ldc;
             if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // at most four store addresses live at a time
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(const float *__restric
     float v = P[static_cast<int64_t>(m) * ldp + n];
     for (int z = 1; z < splits; ++z) v += P[(static_cast<int64_t>(z) * M + m) * ldp + n];
     if (bias) v += bias[n];
-    if (act == WDG_ACT_RELU) v = fmaxf(v, 0.f);
+    if (act == WDG_ACT_RELU) v = relu_keep_nan(v);
     C[static_cast<int64_t>(m) * ldc + n] = v;
 }
 
@@ -706,8 +710,9 @@ int launch_bres(const wdg_gemm_job *jobs, const wdg_gemm_job &inl, int n_jobs, i
 // ------------------------------------------------------------------------------------------------ skinny products (N <= 8)
 // C[M, N] = act(A[M, K] B[K, N] + bias) for a classifier-sized N (the SGC-1 head X W: Cora 2708 x 1433 x 7).  The product is a
 // read of A: 4 M K bytes against 2 M K N flops - nothing for the matrix pipe, and the 128 x 32 tiles of the MFMA kernels put
-// 22 workgroups on 256 CUs for Cora (57 us for 15.5 MB).  Here B sits in LDS ([K][8] floats, staged per workgroup in chunks
-// of <= 2048 rows), sixteen lanes own a row of A and split its K (every load instruction reads 64 contiguous bytes of each of
+// 22 workgroups on 256 CUs for Cora (57 us for 15.5 MB).  Here B sits in LDS ([K][8] floats, staged once per workgroup: the
+// launcher sends K <= 512 here, so the kernel's loop over chunks of 2048 rows takes one trip - a second trip is unreachable
+// and untested), sixteen lanes own a row of A and split its K (every load instruction reads 64 contiguous bytes of each of
 // the wave's four rows), each lane keeps the N running sums of its k's, and a four-step butterfly adds the sixteen lanes.
 // Summation order: per lane k ascending (k = l + LPR t), then the butterfly - fixed, so results are bitwise reproducible;
 // NOT the k-ordered chain of wdg_gemm_f32 (a separate entry point: callers that need that chain keep wdg_gemm_f32).
@@ -740,7 +745,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_wave_kernel(const float *__re
 #pragma unroll
         for (int c = 0; c < NCOLS; ++c) {
             const float v = acc[c] + (bias ? bias[c] : 0.f);
-            out[c] = act == WDG_ACT_RELU ? fmaxf(v, 0.f) : v;
+            out[c] = act == WDG_ACT_RELU ? relu_keep_nan(v) : v;
         }
     }
 }
@@ -786,7 +791,7 @@ __global__ __launch_bounds__(SK_THREADS) void gemm_skinny_kernel(const float *__
         for (int c = 0; c < SK_N; ++c) {
             if (c >= N) break;
             const float v = acc[c] + (bias ? bias[c] : 0.f);
-            out[c] = act == WDG_ACT_RELU ? fmaxf(v, 0.f) : v;
+            out[c] = act == WDG_ACT_RELU ? relu_keep_nan(v) : v;
         }
     }
 }
@@ -799,7 +804,7 @@ int wdg_gemm_f32(const float *A, int64_t lda, const float *B, int64_t ldb, int t
                  float *C, int64_t ldc, int32_t M, int32_t N, int32_t K, wdg_stream_t stream) {
     WDG_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
     if (M == 0 || N == 0) return WDG_OK;
-    WDG_REQUIRE(A && B && C, "gemm: null matrix");
+    WDG_REQUIRE(C && (K == 0 || (A && B)), "gemm: null matrix");  // (K = 0: act(bias) into all of C, A and B never dereferenced)
     WDG_REQUIRE(lda >= K && ldc >= N && ldb >= (transb ? K : N), "gemm: leading dimension too small");
     WDG_REQUIRE(act == WDG_ACT_NONE || act == WDG_ACT_RELU, "gemm: bad activation");
     hipStream_t st = wdg::as_stream(stream);
@@ -875,22 +880,25 @@ int wdg_gemm_splitk_f32(const float *A, int64_t lda, const float *B, int64_t ldb
     return wdg::check_launch("gemm_splitk");
 }
 
+int32_t wdg_gemm_skinny_lanes(int32_t K) { return K <= 16 ? 1 : K <= 128 ? 4 : K <= 512 ? 16 : 64; }
+
 int wdg_gemm_skinny_f32(const float *A, int64_t lda, const float *B, int64_t ldb, const float *bias, int act, float *C, int64_t ldc,
                         int32_t M, int32_t N, int32_t K, wdg_stream_t stream) {
     WDG_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_skinny: negative size");
     WDG_REQUIRE(N <= SK_N, "gemm_skinny: more than 8 columns (wdg_gemm_f32 takes those)");
     if (M == 0 || N == 0) return WDG_OK;
-    WDG_REQUIRE(A && B && C, "gemm_skinny: null matrix");
+    WDG_REQUIRE(C && (K == 0 || (A && B)), "gemm_skinny: null matrix");  // (K = 0: act(bias) into all of C, A and B never dereferenced)
     WDG_REQUIRE(lda >= K && ldc >= N && ldb >= N, "gemm_skinny: leading dimension too small");
     WDG_REQUIRE(act == WDG_ACT_NONE || act == WDG_ACT_RELU, "gemm_skinny: bad activation");
     hipStream_t st = wdg::as_stream(stream);
-    if (K <= 16)
+    const int lanes = wdg_gemm_skinny_lanes(K);
+    if (lanes == 1)
         hipLaunchKernelGGL(gemm_skinny_kernel<1>, dim3(static_cast<unsigned>(wdg::ceil_div(M, SK_THREADS))), dim3(SK_THREADS), 0, st, A, lda,
                            B, ldb, bias, act, C, ldc, M, N, K);
-    else if (K <= 128)
+    else if (lanes == 4)
         hipLaunchKernelGGL(gemm_skinny_kernel<4>, dim3(static_cast<unsigned>(wdg::ceil_div(M, SK_THREADS / 4))), dim3(SK_THREADS), 0, st, A,
                            lda, B, ldb, bias, act, C, ldc, M, N, K);
-    else if (K <= 512)
+    else if (lanes == 16)
         hipLaunchKernelGGL(gemm_skinny_kernel<16>, dim3(static_cast<unsigned>(wdg::ceil_div(M, SK_THREADS / 16))), dim3(SK_THREADS), 0, st, A,
                            lda, B, ldb, bias, act, C, ldc, M, N, K);
     else {  // a wave per row: enough lanes that every lane's handful of loads is in flight at once (Cora: 23 per lane)
@@ -926,6 +934,8 @@ int wdg_gemm_batched_flags_f32(const wdg_gemm_job *jobs_dev, int32_t n_jobs, int
     else hipLaunchKernelGGL((gemm_f32_kernel<1, false>), grid, dim3(THREADS), 0, wdg::as_stream(stream), jobs_dev, wdg_gemm_job{});
     return wdg::check_launch("gemm_f32_kernel (batched)");
 }
+
+int wdg_gemm_resident_eligible(int32_t n_jobs, int32_t max_M, int32_t max_N, int32_t K) { return bres_shape_ok(n_jobs, max_M, max_N, K) ? 1 : 0; }
 
 int wdg_gemm_batched_f32(const wdg_gemm_job *jobs_dev, int32_t n_jobs, int32_t max_M, int32_t max_N,
                          wdg_stream_t stream) {

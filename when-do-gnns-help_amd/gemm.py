@@ -106,11 +106,22 @@ class Mlp2Batch:
 
 
 # ------------------------------------------------------------------------------------------- GEMM
+def _rows(t, dev):
+    """a matrix operand as the kernels take it: an fp32 device matrix whose rows are contiguous is passed AS IT IS, with its own
+    leading dimension (a column slice of a wider buffer is read in place, its padding never touched); anything else as _dev's
+    contiguous copy"""
+    if isinstance(t, torch.Tensor) and t.dim() == 2 and t.dtype == torch.float32 and t.device == dev and \
+            (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= max(t.shape[1], 1)):
+        return t
+    return _dev(t, torch.float32, dev)
+
+
 def gemm(a, b, bias=None, relu=False, transb=False, out=None):
     """act(A @ B + bias) (or A @ B^T with transb) in exact fp32 on the MFMA pipe (wdg_gemm_f32; products with few output tiles
-    and K >= 1024 as partial products over ranges of K, wdg_gemm_splitk_f32: same arithmetic per range, ranges added in order)."""
+    and K >= 1024 as partial products over ranges of K, wdg_gemm_splitk_f32: same arithmetic per range, ranges added in order).
+    K = 0 (A [M, 0], B [0, N]) is the empty sum: act(bias), or act(0) without a bias."""
     dev = require_gpu()
-    a, b, bias = _dev(a, torch.float32, dev), _dev(b, torch.float32, dev), _dev(bias, torch.float32, dev)
+    a, b, bias = _rows(a, dev), _rows(b, dev), _dev(bias, torch.float32, dev)
     m, k = a.shape
     n = b.shape[0] if transb else b.shape[1]
     if (b.shape[1] if transb else b.shape[0]) != k:
@@ -132,9 +143,9 @@ def gemm(a, b, bias=None, relu=False, transb=False, out=None):
 def gemm_skinny(a, b, bias=None, relu=False, out=None):
     """act(A @ B + bias) for B of <= 8 columns (a classifier head) on wdg_gemm_skinny_f32: the rows of A spread over the whole
     chip, K split over 16 lanes per row.  Within fp32 rounding of gemm() (whose k-ordered chain it does not reproduce bit for
-    bit); wider B: gemm()."""
+    bit); wider B: gemm().  K = 0 is the empty sum, as in gemm()."""
     dev = require_gpu()
-    a, b, bias = _dev(a, torch.float32, dev), _dev(b, torch.float32, dev), _dev(bias, torch.float32, dev)
+    a, b, bias = _rows(a, dev), _rows(b, dev), _dev(bias, torch.float32, dev)
     m, k = a.shape
     n = b.shape[1]
     if b.shape[0] != k:
