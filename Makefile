@@ -4,9 +4,9 @@ CSRC     := $(PKG)/csrc
 HIPCC    ?= /opt/rocm/bin/hipcc
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-value $(if $(STAMPS),-DWDG_STAMPS,) $(if $(DEPTH),-DWDG_PREFETCH_DEPTH=$(DEPTH),) $(EXTRA)
 SRCS     := $(wildcard $(CSRC)/*.hip)
-# link order: the units of the opt-in keep_best, learning-curve, AUC, sparse-first-layer, CSBM-H (synth_classes, qda), attention (gat, gat_scores) signed-attention (signed_att), polynomial-filter (poly_filter), two-hop pattern (two_hop) and row top-k (topk_rows) paths go LAST, so that every other kernel keeps the place in the library it had before
+# link order: the units of the opt-in keep_best, learning-curve, AUC, sparse-first-layer, CSBM-H (synth_classes, qda), attention (gat, gat_scores) signed-attention (signed_att), polynomial-filter (poly_filter), two-hop pattern (two_hop), row top-k (topk_rows) and GCNII layer (gcnii) paths go LAST, so that every other kernel keeps the place in the library it had before
 # they existed (the default paths are timed against the parent commit's build: DESIGN 4.20, 4.21)
-LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $(CSRC)/auc.hip $(CSRC)/sparse_dense.hip $(CSRC)/synth_classes.hip $(CSRC)/qda.hip $(CSRC)/gat.hip $(CSRC)/gat_scores.hip $(CSRC)/signed_att.hip $(CSRC)/poly_filter.hip $(CSRC)/two_hop.hip $(CSRC)/topk_rows.hip
+LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $(CSRC)/auc.hip $(CSRC)/sparse_dense.hip $(CSRC)/synth_classes.hip $(CSRC)/qda.hip $(CSRC)/gat.hip $(CSRC)/gat_scores.hip $(CSRC)/signed_att.hip $(CSRC)/poly_filter.hip $(CSRC)/two_hop.hip $(CSRC)/topk_rows.hip $(CSRC)/gcnii.hip
 SRCS     := $(filter-out $(LAST),$(SRCS)) $(LAST)
 LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and
@@ -37,6 +37,8 @@ FLAGS_signed_att := -ffp-contract=off
 FLAGS_poly_filter := -ffp-contract=off
 # topk_rows.hip's key is ONE rounded product and its row norm an fmaf chain written out in include/wdg.h: nothing else is fused (the source says so as well)
 FLAGS_topk_rows := -ffp-contract=off
+# gcnii.hip's layer and its backward pass are stated operation by operation in include/wdg.h and restated in numpy bit for bit: every fmaf is written out, nothing else is fused
+FLAGS_gcnii := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB      := $(PKG)/lib/libwdg_hip.so
 

@@ -2081,6 +2081,85 @@ int wdg_topk_rows_check_jobs(const wdg_topk_job *jobs_host, int32_t n_jobs);
 int wdg_topk_rows_batched_f32(const wdg_topk_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream);
 int wdg_row_rnorm_f32(const float *x, int64_t ld, int32_t n, int32_t F, float *out, wdg_stream_t stream);
 
+/*
+ * One GCNII layer behind its aggregation, for many layers / graphs in ONE launch, and its backward pass (Chen, Wei, Huang, Ding, Li:
+ * "Simple and Deep Graph Convolutional Networks", ICML 2020): the initial residual, the identity mapping, the ReLU and the dropout of
+ *   H_l = relu_dropout((1 - beta) S + beta S W),   S = (1 - alpha) P + alpha H0,   P = A_hat H_{l-1} (the caller's aggregation)
+ * as one pass over the rows instead of a combine, a product, a combine and an activation.  The reference ships no model code: the layer is
+ * DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: nothing of the reference - it stands behind the aggregation with the fixed weights of normalize_tensor,
+ *           utils/util_funcs.py:365-381, whose result is this layer's P.
+ * A job: n rows, w columns (1 <= w <= WDG_GCNII_MAX_W); P [n, w], H0 [n, w], W [w, w] (row k, column c), alpha, beta, a generator
+ * stream; outputs out [n, w] and S [n, w] - S may be NULL (inference: nothing reads it again).  For the backward pass d_out [n, w],
+ * d_P [n, w], d_H0 [n, w], d_W [w, w] and a workspace `partial` of wdg_gcnii_partial_len(n, w) floats at a 16-byte boundary; the
+ * backward pass reads S, W and - with act == 1 - out.  Every matrix has its own leading dimension and unit inner stride.
+ * The arithmetic (csrc/gcnii.hip is compiled with contraction off and writes every fmaf out; tests/_gcnii_ref.py restates it), with
+ * a1 = 1.0f - alpha and b1 = 1.0f - beta:
+ *   forward    S[i, k] = fmaf(alpha, H0[i, k], a1 * P[i, k])
+ *              T[i, c] = ONE fmaf chain from +0 over ascending k:  acc = fmaf(S[i, k], W[k, c], acc)
+ *              Z[i, c] = fmaf(beta, T[i, c], b1 * S[i, c])
+ *              out[i, c] = Z[i, c] when the launch's act is 0; when act is 1, what wdg_relu_dropout_batched_f32 makes of Z[i, c]:
+ *                g = i * ceil(w / 4) + (c >> 2), the four words of Philox4x32-10 with counter {g, *step_dev, 0, 0} and key
+ *                {seed, jobs[j].stream}, kept = word[c & 3] >= drop_threshold, out = Z * scale (ONE multiply) if kept and Z > 0; Z itself
+ *                if Z is a NaN; +0.0f otherwise.  drop_threshold, scale, seed and step_dev are launch arguments as there; (0, 1.0f) is a
+ *                plain ReLU (no word is drawn: every word is >= 0).
+ *   backward   dZ[i, c] = act ? (out[i, c] > 0 ? d_out[i, c] * scale : +0.0f) : d_out[i, c]
+ *              U[i, k] = ONE fmaf chain from +0 over ascending c:  acc = fmaf(dZ[i, c], W[k, c], acc)
+ *              dS[i, k] = fmaf(beta, U[i, k], b1 * dZ[i, k])
+ *              d_P[i, k] = a1 * dS[i, k]
+ *              d_H0[i, k] = fmaf(alpha, dS[i, k], d_H0[i, k])   - d_H0 is ADDED to: the layers of a model accumulate into one tensor,
+ *                in the order they are launched -
+ *              the rows are cut into blocks of WDG_GCNII_ROW_BLOCK from row 0; per block b and element (k, c),
+ *              partial[b, k, c] = ONE chain from +0 over the block's rows ascending:  acc = fmaf(S[i, k], dZ[i, c], acc)
+ *   weight     d_W[k, c] = beta * (the blocks' sums added in ascending b from +0: acc = acc + partial[b, k, c])   (ONE multiply)
+ *              - an entry of its own, so that a model calls it ONCE after the backward launches of all its layers, with L jobs.
+ * No floating-point atomics; an element depends on its own row of its own job (S, out, d_P, d_H0) or its own (k, c) of its own job (d_W):
+ * a job has the same bits alone and in any table, and a second launch repeats the first (given d_H0 as it was).  A NaN in P[i, k]
+ * reaches row i of S and out, and row k of d_W, nothing else.  16-byte accesses where every pointer, leading dimension and w of a job
+ * allow - one decision per job and pass -, scalar ones elsewhere: the same values.  Outputs must not overlap inputs or each other.
+ * Limits: w in 1..WDG_GCNII_MAX_W, at most 65535 jobs (a job per grid z).  max_rows / max_w: the table's largest n and w (what lies
+ * beyond them is not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID): a NULL table with n_jobs > 0, negative counts, more than 65535 jobs, max_w above
+ * WDG_GCNII_MAX_W, an act other than 0 and 1, a NULL step_dev with act == 1, a scale that is not a number, max_rows * ceil(max_w / 4)
+ * >= 2^32 (g is a 32-bit counter word).  n_jobs == 0 or a zero maximum: WDG_OK, nothing is launched.  The table lives in device memory:
+ * what is wrong inside a job - w outside 1..128, a negative n, NULL P, H0, W or out with n > 0, a leading dimension below its row, the
+ * backward pointers (d_out, d_P, d_H0, d_W, partial) given in part or without S, a workspace that is not 16-byte aligned - is refused by
+ * wdg_gcnii_check_jobs on the HOST copy of the table (train.GcniiBatch calls it before it uploads).  A job with n == 0 is skipped: it
+ * touches nothing, d_W included; the kernels leave a job outside the limits untouched.
+ */
+#define WDG_GCNII_MAX_W 128
+#define WDG_GCNII_ROW_BLOCK 32
+typedef struct wdg_gcnii_job {
+    const float *P;      /* [n, w]: A_hat H_{l-1} */
+    const float *H0;     /* [n, w] */
+    const float *W;      /* [w, w]: row k, column c */
+    float *out;          /* forward out [n, w]; read by the backward pass when act == 1 */
+    float *S;            /* forward out [n, w], or NULL (inference); read by the backward pass */
+    const float *d_out;  /* backward in [n, w], or NULL (then d_P, d_H0, d_W and partial are NULL too) */
+    float *d_P;          /* backward out [n, w] */
+    float *d_H0;         /* backward in / out [n, w]: added to */
+    float *d_W;          /* weight-gradient out [w, w] */
+    float *partial;      /* backward workspace [ceil(n / WDG_GCNII_ROW_BLOCK), w, w] */
+    int64_t ld_p, ld_h0, ld_w, ld_out, ld_s, ld_d_out, ld_d_p, ld_d_h0, ld_d_w;
+    int32_t n, w;
+    float alpha, beta;
+    uint32_t stream;     /* generator stream of this job */
+    uint32_t reserved;   /* not read */
+} wdg_gcnii_job;
+int wdg_gcnii_forward_batched_f32(const wdg_gcnii_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_w, int32_t act,
+                                  uint32_t drop_threshold, float scale, uint32_t seed, const uint32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the backward pass of the layer above (behind the aggregation of utils/util_funcs.py:365-381):
+ *           dZ, d_P, d_H0 += and the blocks' partial sums, one launch */
+int wdg_gcnii_backward_batched_f32(const wdg_gcnii_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_w, int32_t act, float scale,
+                                   wdg_stream_t stream);
+/* replaces: nothing of its own - d_W of the layer above (behind the aggregation of utils/util_funcs.py:365-381) from the partial sums
+ *           the backward launches left, one launch for all the layers of a model */
+int wdg_gcnii_weight_grad_batched_f32(const wdg_gcnii_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_w, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the layer above (utils/util_funcs.py:365-381), on the host's table */
+int wdg_gcnii_check_jobs(const wdg_gcnii_job *jobs_host, int32_t n_jobs);
+/* the floats of a job's workspace: ceil(n / WDG_GCNII_ROW_BLOCK) * w * w; 0 for a negative argument */
+int64_t wdg_gcnii_partial_len(int32_t n, int32_t w);
+
 #ifdef __cplusplus
 }
 #endif

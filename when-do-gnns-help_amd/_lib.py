@@ -210,6 +210,11 @@ SIGNATURES = {
     "wdg_topk_rows_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_topk_rows_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
     "wdg_row_rnorm_f32": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "wdg_gcnii_forward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, ctypes.c_float, c_uint32, c_void_p, c_void_p]),
+    "wdg_gcnii_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_void_p]),
+    "wdg_gcnii_weight_grad_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_gcnii_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_gcnii_partial_len": (c_int64, [c_int32, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -452,6 +457,13 @@ class TopkJob(ctypes.Structure):
     _fields_ = [("scores", c_void_p), ("col_scale", c_void_p), ("out_col", c_void_p), ("out_key", c_void_p), ("out_len", c_void_p),
                 ("ld", c_int64), ("ld_out", c_int64), ("rows", c_int32), ("cols", c_int32), ("row0", c_int32), ("k", c_int32),
                 ("flags", c_int32), ("reserved", c_int32)]
+
+
+class GcniiJob(ctypes.Structure):
+    """mirror of `wdg_gcnii_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("P", "H0", "W", "out", "S", "d_out", "d_P", "d_H0", "d_W", "partial")] + \
+               [(name, c_int64) for name in ("ld_p", "ld_h0", "ld_w", "ld_out", "ld_s", "ld_d_out", "ld_d_p", "ld_d_h0", "ld_d_w")] + \
+               [("n", c_int32), ("w", c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("stream", c_uint32), ("reserved", c_uint32)]
 
 
 if not os.path.exists(LIB_PATH):

@@ -38,7 +38,14 @@ keep every round's representation for the classifier (Zhu et al., "Beyond Homoph
 built once on csrc/two_hop.hip (`TwoHopAdj`); the aggregations are the existing ones.  Defined by this project as well.
 `KnnAdj` puts the k-nearest-neighbour graph of the FEATURES in the second pattern's place (the feature channel of AM-GCN /
 SimP-GCN), built once on csrc/topk_rows.hip; H2GCN1 / H2GCN2 take it as they take a TwoHopAdj.
+
+GCNII (`GCNII`) is the DEEP model with a residual to the un-aggregated representation: every layer mixes alpha H0 into its
+aggregation and passes the result through (1 - beta_l) I + beta_l W_l (Chen et al., "Simple and Deep Graph Convolutional Networks") - the
+residual, the identity mapping, the ReLU and the dropout behind an aggregation are ONE launch of csrc/gcnii.hip, forward and backward, and
+the weight gradients of all layers one more.  Defined by this project as well.
 """
+import math
+
 import torch
 
 from . import ops
@@ -692,6 +699,153 @@ class GPRGNN2(_HiddenDropout, _GPRBase):
     def forward(self, adj, x):
         h = self._relu_dropout_of_product(x, self.w0)
         return self._filter(adj, _Linear.apply(h, self.w1, False), self.gamma)
+
+
+class _GcniiStack:
+    """The L layers of one GCNII model behind their aggregations, H_l = relu_dropout((1 - beta_l) S + beta_l S W_l) with
+    S = (1 - alpha) A_hat H_{l-1} + alpha H0 (include/wdg.h: wdg_gcnii_forward_batched_f32), as ONE ops.GcniiBatch of L jobs per
+    (rows, cols): a layer's forward and backward pass are one launch each on its job, the weight gradients of all layers ONE launch, and
+    the kernel accumulates d_H0 over the layers.  The work buffers - H0, the weights, one P, every layer's S and out, the gradients - and
+    the tables over them are built on first use, before any capture, so that a captured pass addresses the same memory on every replay.
+    Two tables: the training table keeps every layer's S and out for the backward pass; the inference table passes S = NULL and lets
+    the layers' outputs alternate between two buffers.
+    What it requires (as _OneJobLayer does): the training buffers hold ONE forward pass, the latest; a backward pass that finds another
+    training forward pass between itself and its own raises - the step word its masks were drawn at may have moved on."""
+
+    def __init__(self, alpha, betas, rng):
+        self.alpha, self.betas, self.rng = float(alpha), [float(b) for b in betas], rng
+        self._tables, self._word = {}, None
+        self.version = 0  # training forward passes so far
+
+    def _entries(self, b, outs, s_of):
+        base = self.rng.stream if self.rng is not None else 0
+        return [dict(p=b["p"], h0=b["h0"], w=b["w"][l], out=outs(l), s=s_of(l), alpha=self.alpha, beta=beta, stream=(base + l + 1) & 0xFFFFFFFF)
+                for l, beta in enumerate(self.betas)]
+
+    def word(self, dev):
+        """the step word the epilogues read: the DeviceDropout's, as H0's call left it; without one a word of the stack's own (a plain
+        ReLU draws nothing, the entry still wants an address)"""
+        if self.rng is not None:
+            return self.rng.step
+        if self._word is None:
+            self._word = torch.zeros(1, dtype=torch.int32, device=dev)
+        return self._word
+
+    def table(self, training, rows, cols, dev, masks=False):
+        key = (bool(training), rows, cols, dev)
+        if key not in self._tables:
+            L = len(self.betas)
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            seed = self.rng.seed if self.rng is not None else 0
+            b = dict(h0=z(rows, cols), w=z(L, cols, cols), p=z(rows, cols))
+            if training:
+                b.update(out=z(L, rows, cols), s=z(L, rows, cols), d_out=z(rows, cols), d_p=z(rows, cols), d_h0=z(rows, cols), d_w=z(L, cols, cols))
+                entries = self._entries(b, lambda l: b["out"][l], lambda l: b["s"][l])
+                entries = [dict(e, d_out=b["d_out"], d_p=b["d_p"], d_h0=b["d_h0"], d_w=b["d_w"][l]) for l, e in enumerate(entries)]
+            else:
+                b.update(out=z(2, rows, cols))
+                entries = self._entries(b, lambda l: b["out"][l & 1], lambda l: None)
+            self._tables[key] = (b, ops.GcniiBatch(entries, 0.0, seed))
+        b, table = self._tables[key]
+        if masks and "mask" not in b:
+            b["mask"] = torch.zeros_like(b["out"])
+        return b, table
+
+    def forward(self, training, adj, h0, weights, p_dev, p_torch):
+        """-> H_L (a view of the stack's buffers).  p_dev: the drop probability of the kernel's epilogue (0: a plain ReLU); p_torch: that
+        of torch's dropout behind it (the route without a DeviceDropout)"""
+        b, table = self.table(training, h0.shape[0], h0.shape[1], h0.device, masks=training and p_torch > 0)
+        b["h0"].copy_(h0)
+        torch.stack(list(weights), out=b["w"])
+        word, h = self.word(h0.device), b["h0"]
+        for l in range(len(self.betas)):
+            ops.spmm(adj.graph, h, row_scale=adj.row_scale, col_scale=adj.col_scale, out=b["p"])
+            table.launch(word, first=l, count=1, p=p_dev)
+            h = b["out"][l] if training else b["out"][l & 1]
+            if p_torch > 0 and training:
+                h = h * b["mask"][l].bernoulli_(1.0 - p_torch).mul_(1.0 / (1.0 - p_torch))
+            elif p_torch > 0:
+                h = torch.nn.functional.dropout(h, p_torch, True)
+        if training:
+            self.version += 1
+        return h
+
+
+class _GcniiLayers(torch.autograd.Function):
+    """H_L = the L layers of a _GcniiStack applied to H0, and their backward pass - ONE function over the whole stack, so that d_H0 is
+    accumulated by the kernel and d_W of all layers comes from one launch; the aggregations between the layers are ops.spmm forward
+    and _Aggregate's backward pass."""
+
+    @staticmethod
+    def forward(ctx, stack, adj, p_dev, p_torch, h0, *weights):
+        h = stack.forward(True, adj, h0, weights, p_dev, p_torch)
+        ctx.stack, ctx.adj, ctx.p_dev, ctx.p_torch, ctx.version = stack, adj, p_dev, p_torch, stack.version
+        ctx.shape = (h0.shape[0], h0.shape[1], h0.device)
+        return h.clone()
+
+    @staticmethod
+    def backward(ctx, gy):
+        stack = ctx.stack
+        if stack.version != ctx.version:
+            raise RuntimeError("GCNII: another training forward pass of this model has run since the one this backward pass belongs to; "
+                               "its buffers hold one forward pass, the latest")
+        b, table = stack.table(True, *ctx.shape)
+        b["d_h0"].zero_()
+        d = gy
+        for l in reversed(range(len(stack.betas))):
+            if ctx.p_torch > 0:
+                torch.mul(d, b["mask"][l], out=b["d_out"])
+            else:
+                b["d_out"].copy_(d)
+            table.launch_backward(first=l, count=1, p=ctx.p_dev)
+            d = _Aggregate.backward(ctx, b["d_p"])[0]  # (reads ctx.adj alone)
+        table.launch_weight_grad()
+        return (None, None, None, None, b["d_h0"] + d, *b["d_w"].clone().unbind(0))
+
+
+class GCNII(_HiddenDropout, torch.nn.Module):
+    """GCNII (Chen, Wei, Huang, Ding, Li: "Simple and Deep Graph Convolutional Networks", ICML 2020): a DEEP model with a residual to the
+    un-aggregated representation and an identity mapping in every layer -
+        H0 = relu_dropout(X W_in),
+        H_l = relu_dropout((1 - beta_l) S_l + beta_l S_l W_l),  S_l = (1 - alpha) A_hat H_{l-1} + alpha H0,  l = 1..layers,
+        logits = H_L W_out,
+    beta_l = log(theta / l + 1), computed in fp64 and rounded once; bias-free; alpha is not learnt; one weight per layer (not GCNII*).
+    H0 is both the first input and the residual of every layer.  The aggregation is ops.spmm; everything behind it is ONE launch of
+    csrc/gcnii.hip per layer, forward and backward; nhid <= 128.  Recommended graph: NormAdj(adj, symmetric=1).
+    Dropout (GCN2's two routes): with a DeviceDropout, in training and with dropout > 0, layer l's epilogue draws stream
+    dropout_rng.stream + l at the step word as H0's call left it - nothing else advances the word, so a captured epoch draws fresh masks
+    per replay; with dropout_rng=None the kernel applies the plain ReLU and torch's dropout follows.
+    Parameters are drawn in this order: W_in ([nfeat, nhid]), W_1 .. W_L ([nhid, nhid]), W_out ([nhid, nclass]), all xavier_uniform."""
+
+    def __init__(self, nfeat, nclass, nhid=64, layers=8, alpha=0.1, theta=0.5, dropout=0.5, dropout_rng=None):
+        super().__init__()
+        if layers < 1:
+            raise ValueError(f"GCNII: {layers} layers; at least one expected")
+        if not 1 <= nhid <= ops.GcniiBatch.MAX_W:
+            raise ValueError(f"GCNII: a hidden width of {nhid}; the layer kernel holds 1..{ops.GcniiBatch.MAX_W}")
+        if not 0.0 <= alpha <= 1.0 or not theta >= 0.0:
+            raise ValueError(f"GCNII: alpha in [0, 1] and theta >= 0 expected, got alpha = {alpha}, theta = {theta}")
+        self.w_in = _xavier(nfeat, nhid)
+        self.weights = torch.nn.ParameterList([_xavier(nhid, nhid) for _ in range(layers)])
+        self.w_out = _xavier(nhid, nclass)
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._beta = torch.tensor([math.log(float(theta) / l + 1.0) for l in range(1, layers + 1)], dtype=torch.float64).to(torch.float32)
+        self._stack = _GcniiStack(alpha, self._beta.tolist(), dropout_rng)
+
+    def filter_strength(self):
+        """-> beta_1 .. beta_L as a host float32 numpy array: how much of each layer goes through its weight"""
+        return self._beta.numpy().copy()
+
+    def forward(self, adj, x):
+        h0 = self._relu_dropout_of_product(x, self.w_in)
+        drops = self.training and self.dropout > 0
+        p_dev = float(self.dropout) if drops and self.dropout_rng is not None else 0.0
+        p_torch = float(self.dropout) if drops and self.dropout_rng is None else 0.0
+        if torch.is_grad_enabled() and (h0.requires_grad or any(w.requires_grad for w in self.weights)):
+            h = _GcniiLayers.apply(self._stack, adj, p_dev, p_torch, h0, *self.weights)
+        else:
+            h = self._stack.forward(False, adj, h0, [w.detach() for w in self.weights], p_dev, p_torch).clone()
+        return _Linear.apply(h, self.w_out, False)
 
 
 class TwoHopAdj:

@@ -30,6 +30,8 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         times the fixed scales, an optional residual),
                         PolyFilterBatch (the polynomial graph filter sum_k gamma_k A_hat^k v of many graphs, all hops in one launch, with
                         the dot products that are the coefficients' gradient),
+                        GcniiBatch (the GCNII layer behind its aggregation for many layers / graphs in one launch: initial residual, identity
+                        mapping, ReLU + counter-based dropout, with a backward pass and a weight gradient summed in a stated order),
                         XentEvalBatch (cross-entropy gradient, hits and model selection of many models with stacked logits),
                         AdamBatch (the Adam step of a stacked run's parameter tensors in one launch: a learning rate and a weight
                         decay per replica in device memory, the step count read from the run's step word),
@@ -72,7 +74,7 @@ from .stats import (  # noqa: F401
 from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
-from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, GatBatch, GatScoresBatch, HeadTrainBatch, KeepBestBatch, PolyFilterBatch, SignedAttBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
+from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, GatBatch, GatScoresBatch, GcniiBatch, HeadTrainBatch, KeepBestBatch, PolyFilterBatch, SignedAttBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .synth import class_graphs_device, ClassGraphBatch, gauss_features_device, GaussFeatureBatch, regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, DeviceFeatures, expand_features, feature_image_floats, FeatureExpand, SparseDenseBatch, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401

@@ -11,6 +11,8 @@
   with its backward pass
 - csrc/poly_filter.hip: the polynomial graph filter of many graphs (GPR-GNN-1, GPR-GNN-2; APPNP): all K hops of sum_k gamma_k A_hat^k v in one launch,
   with the dot products that are the coefficients' gradient
+- csrc/gcnii.hip: the GCNII layer behind its aggregation (GCNII: initial residual + identity mapping + ReLU + dropout in one launch) with its
+  backward pass and the weight gradient of all the layers of a model in one launch
 - csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
 - csrc/adam.hip: the Adam step of the stacked parameters with every replica's own learning rate and weight decay
 - csrc/keep_best.hip: the copy of every replica's parameters and logits at its best epoch
@@ -19,6 +21,7 @@
 - csrc/auc.hip: the exact ROC-AUC of stacked binary logits, the selection on it, its patience counter and its curve
 Every table is a job_table.JobTable: what a table is, what it owns and the sequence of its constructor are stated there; a class here
 states its kernel's contract, its checks and its records."""
+import ctypes
 import math
 
 import numpy as np
@@ -39,6 +42,7 @@ _GAT_JOB_DTYPE = np.dtype(_lib.GatJob)
 _GAT_SCORES_JOB_DTYPE = np.dtype(_lib.GatScoresJob)
 _SIGNED_ATT_JOB_DTYPE = np.dtype(_lib.SignedAttJob)
 _POLY_FILTER_JOB_DTYPE = np.dtype(_lib.PolyFilterJob)
+_GCNII_JOB_DTYPE = np.dtype(_lib.GcniiJob)
 _XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
 _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
 _KEEP_JOB_DTYPE = np.dtype(_lib.KeepJob)
@@ -546,6 +550,109 @@ class GatScoresBatch(JobTable):
         if not self.has_backward and self.n_jobs:
             raise ValueError("GatScoresBatch.launch_backward: the table was built without gradient tensors")
         self._launch("wdg_gat_scores_backward_batched_f32", self.max_rows, self.max_cols)
+
+
+class GcniiBatch(JobTable):
+    """Job table for wdg_gcnii_forward_batched_f32 / wdg_gcnii_backward_batched_f32 / wdg_gcnii_weight_grad_batched_f32 (csrc/gcnii.hip):
+    one GCNII layer behind its aggregation per entry - s = (1 - alpha) p + alpha h0, z = (1 - beta) s + beta s w, out = z or, with act,
+    relu_dropout(z) with DropoutBatch's masks (include/wdg.h states every operation and every sum's order; tests/_gcnii_ref.py restates
+    them in numpy) - and its backward pass: d_p is written, d_h0 is ADDED to (the layers of a model accumulate into one tensor), d_w comes
+    from partial sums over blocks of ROW_BLOCK rows that the table owns, by a launch of its own: once for all the layers of a model.
+    Every launch takes a range of the table (first, count): the layers of one model are one table and run one after the other."""
+
+    MAX_JOBS, MAX_W, ROW_BLOCK = 65535, 128, 32
+    _KEYS = ("p", "h0", "w", "out", "s", "alpha", "beta", "stream", "d_out", "d_p", "d_h0", "d_w")
+    _BACKWARD = ("d_out", "d_p", "d_h0", "d_w")
+
+    def __init__(self, entries, p=0.0, seed=0, act=True):
+        """entries: list of dicts - p, h0 and out [n, w] fp32, w [w, w] fp32 (unit inner stride, any leading dimension), alpha and beta
+           (floats), s [n, w] or None (inference: not written), stream (the entry's generator stream, 0 .. 2^32 - 1, default 0);
+           and, for launch_backward() / launch_weight_grad(): d_out, d_p, d_h0 [n, w] and d_w [w, w] - all four or none, and s with them.
+        p: the drop probability in [0, 1) of the epilogue, seed: 0 .. 2^32 - 1 (DropoutBatch's); act=False: out = z, no ReLU.
+        Raises ValueError for w outside 1..128, other dtypes, shapes or strides, more than 65535 entries, the backward tensors given in
+        part or without s, an output that overlaps an input or another output of its entry."""
+        name = "GcniiBatch"
+        self.p, self.act, self.seed = float(p), bool(act), int(seed)
+        self.threshold, self.scale = dropout_constants(p)
+        if not 0 <= self.seed < 1 << 32:
+            raise ValueError(f"{name}: a seed of 32 bits expected, got {seed!r}")
+        n_jobs = self._open(entries)
+        self.has_backward = n_jobs > 0
+        shapes = []
+        for e in entries:
+            unknown = set(e) - set(self._KEYS)
+            if unknown:
+                raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+            if any(e.get(k) is None for k in ("p", "h0", "w", "out", "alpha", "beta")):
+                raise ValueError(f"{name}: p, h0, w, out, alpha and beta are required")
+            given = [k for k in self._BACKWARD if e.get(k) is not None]
+            if given and (len(given) != len(self._BACKWARD) or e.get("s") is None):
+                raise ValueError(f"{name}: d_out, d_p, d_h0 and d_w come together, with s, or not at all")
+            self.has_backward = self.has_backward and bool(given)
+            if not 0 <= int(e.get("stream", 0)) < 1 << 32:
+                raise ValueError(f"{name}: a stream of 32 bits expected, got {e.get('stream')!r}")
+            wm = e["w"]
+            width = int(wm.shape[1]) if isinstance(wm, torch.Tensor) and wm.dim() == 2 else -1
+            if not 1 <= width <= self.MAX_W:
+                raise ValueError(f"{name}: a layer of {width} columns; the kernel holds 1..{self.MAX_W}")
+            n = e["p"].shape[0] if isinstance(e["p"], torch.Tensor) and e["p"].dim() == 2 else -1
+            mats = {k: e[k] for k in ("p", "h0", "w", "out", "s", "d_out", "d_p", "d_h0", "d_w") if e.get(k) is not None}
+            for k, t in mats.items():
+                GatBatch._matrix(k, t, (width, width) if k in ("w", "d_w") else (n, width), name)
+            if n * (-(-width // 4)) >= 1 << 32:
+                raise ValueError(f"{name}: {n} rows of {width} columns hold 2^32 or more groups of four columns")
+            named = list(mats.items())
+            for i, (ka, ta) in enumerate(named):
+                for kb, tb in named[i + 1:]:
+                    if (ka in ("out", "s", "d_p", "d_h0", "d_w") or kb in ("out", "s", "d_p", "d_h0", "d_w")) and _views_may_overlap(ta, tb):
+                        raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
+            shapes.append((n, width, mats))
+        tab = self._records(_GCNII_JOB_DTYPE)
+        for s_ in shapes:
+            if any(t.device != self._dev for t in s_[2].values()):
+                raise ValueError(f"{name}: every tensor of an entry must live on the device {self._dev}")
+        if self.has_backward:
+            tab["partial"] = self._own("partial", [-(-s_[0] // self.ROW_BLOCK) * s_[1] * s_[1] for s_ in shapes], torch.float32, align=4)
+        for field, key, ld in (("P", "p", "ld_p"), ("H0", "h0", "ld_h0"), ("W", "w", "ld_w"), ("out", "out", "ld_out"), ("S", "s", "ld_s"),
+                               ("d_out", "d_out", "ld_d_out"), ("d_P", "d_p", "ld_d_p"), ("d_H0", "d_h0", "ld_d_h0"), ("d_W", "d_w", "ld_d_w")):
+            self._point(tab, field, [s_[2].get(key) for s_ in shapes], ld=ld)
+        tab["n"], tab["w"] = [s_[0] for s_ in shapes], [s_[1] for s_ in shapes]
+        tab["alpha"], tab["beta"] = [float(e["alpha"]) for e in entries], [float(e["beta"]) for e in entries]
+        tab["stream"] = [int(e.get("stream", 0)) for e in entries]
+        self.max_rows, self.max_w = int(tab["n"].max(initial=0)), int(tab["w"].max(initial=0))
+        self._close(tab, "wdg_gcnii_check_jobs")
+
+    def _range(self, entry_point, first, count, *args):
+        """lib.<entry_point>(the records first .. first + count - 1, count, the table's largest n and w, *args, stream)"""
+        count = self.n_jobs - first if count is None else count
+        if not (0 <= first and 0 <= count and first + count <= self.n_jobs):
+            raise ValueError(f"GcniiBatch: entries {first} .. {first + count - 1} of {self.n_jobs}")
+        table = ctypes.c_void_p(self.table.data_ptr() + first * _GCNII_JOB_DTYPE.itemsize if count else 0)
+        _lib.check(getattr(lib, entry_point)(table, count, self.max_rows, self.max_w, *args, _lib.stream_handle()), entry_point)
+
+    def _epilogue(self, p):
+        return (self.threshold, self.scale) if p is None else dropout_constants(p)
+
+    def launch(self, step=None, first=0, count=None, p=None):
+        """out (and s) of the entries first .. first + count - 1 (default: all).  step: with act, a one-element int32 DEVICE tensor
+        whose bits are the uint32 step word - DropoutBatch.launch's; p: another drop probability than the table's for this launch
+        (0: a plain ReLU)"""
+        threshold, scale = self._epilogue(p)
+        word = _step_word("GcniiBatch.launch", step) if self.act else ctypes.c_void_p(0)
+        self._range("wdg_gcnii_forward_batched_f32", first, count, int(self.act), threshold, scale, self.seed, word)
+
+    def launch_backward(self, first=0, count=None, p=None):
+        """d_p =, d_h0 += and the blocks' partial sums of the entries first .. first + count - 1, from d_out, s, w and - with act - the out
+        of the last launch(); p: the drop probability of THAT launch where it was not the table's"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError("GcniiBatch.launch_backward: the table was built without gradient tensors")
+        self._range("wdg_gcnii_backward_batched_f32", first, count, int(self.act), self._epilogue(p)[1])
+
+    def launch_weight_grad(self, first=0, count=None):
+        """d_w of the entries first .. first + count - 1 from the partial sums their launch_backward() left"""
+        if not self.has_backward and self.n_jobs:
+            raise ValueError("GcniiBatch.launch_weight_grad: the table was built without gradient tensors")
+        self._range("wdg_gcnii_weight_grad_batched_f32", first, count)
 
 
 class PolyFilterBatch(JobTable):
