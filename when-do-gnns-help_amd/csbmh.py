@@ -24,12 +24,13 @@ has ONE non-central chi-square term and no Gaussian term, i.e. exactly this.  Wh
 error is a normal CDF: class 0 Phi(-(b.m0 + c) / (|b| sqrt(v0))), class 1 Phi((b.m1 + c) / (|b| sqrt(v1))).
 """
 import argparse
-import ctypes
 import json
 import sys
 import time
 
 import numpy as np
+
+from .job_table import JobTable
 
 SETS = ("x", "h", "h_high")
 KEYS = ("pbe", "ngjd", "dist", "ratio", "nswd", "nshd")
@@ -145,7 +146,7 @@ def rule_constants(n0, n1, mu0, mu1, sigma0, sigma1, d0, d1, h):
 
 
 # ------------------------------------------------------------------------------------------------ measured on the device
-class QdaBatch:
+class QdaBatch(JobTable):
     """Job table of wdg_qda_errors_batched_i32: per job the [3, 2, 2] error counts [set][true][predicted] of the Bayes rule on x, h
     and x - h.  jobs: list of (x [n, F], h [n, F], labels int32 [n], (mean [3, 2, F], inv2v [3, 2], bias [3, 2])) - fp32 device
     tensors with unit inner stride and fp64 host constants.  .counts: int32 [J, 3, 2, 2] on the device, written by launch()."""
@@ -153,35 +154,27 @@ class QdaBatch:
     def __init__(self, jobs):
         import torch
 
-        from . import _lib, ops
-        dev = ops.require_gpu()
-        self.keep = jobs
-        self.counts = torch.zeros((len(jobs), 3, 2, 2), dtype=torch.int32, device=dev)
-        self.host = (_lib.QdaJob * max(len(jobs), 1))()
-        for g, (x, h, labels, (mean, inv2v, bias)) in enumerate(jobs):
-            j = self.host[g]
+        from . import _lib
+        n_jobs = self._open(jobs)
+        for g, (x, h, labels, (mean, _inv2v, _bias)) in enumerate(jobs):
             n, F = int(x.shape[0]), int(x.shape[1])
             if tuple(h.shape) != (n, F) or int(labels.shape[0]) != n or x.dtype != torch.float32 or h.dtype != torch.float32 or \
                     labels.dtype != torch.int32 or (F > 1 and (x.stride(1) != 1 or h.stride(1) != 1)):
                 raise ValueError(f"QdaBatch: job {g}: x and h fp32 [n, F] with unit inner stride and int32 labels [n] expected")
-            mean = np.asarray(mean, np.float64)
-            if mean.shape != (3, 2, F) or F > 16:
-                raise ValueError(f"QdaBatch: job {g}: mean of shape {mean.shape} for F = {F} (at most 16 features)")
-            j.x, j.h, j.labels = x.data_ptr(), h.data_ptr(), labels.data_ptr()
-            j.counts = self.counts.data_ptr() + 48 * g
-            j.ldx, j.ldh, j.n, j.F = ops._ld(x), ops._ld(h), n, F
-            for t in range(3):
-                for c in range(2):
-                    j.inv2v[t][c], j.bias[t][c] = float(np.asarray(inv2v)[t, c]), float(np.asarray(bias)[t, c])
-                    for f in range(F):
-                        j.mean[t][c][f] = float(mean[t, c, f])
-        self.n_jobs = len(jobs)
-        self.table = ops._table(self.host) if jobs else None
+            if np.shape(mean) != (3, 2, F) or F > 16:
+                raise ValueError(f"QdaBatch: job {g}: mean of shape {np.shape(mean)} for F = {F} (at most 16 features)")
+        tab = self._records(np.dtype(_lib.QdaJob))
+        self._point(tab, "x", [j[0] for j in jobs], ld="ldx")
+        self._point(tab, "h", [j[1] for j in jobs], ld="ldh")
+        self._point(tab, "labels", [j[2] for j in jobs])
+        tab["counts"] = self._own("counts", np.ones(n_jobs, np.int64), torch.int32, unit=(3, 2, 2), of=None, floor=0)
+        tab["n"], tab["F"] = [int(j[0].shape[0]) for j in jobs], [int(j[0].shape[1]) for j in jobs]
+        for g, (x, _h, _labels, (mean, inv2v, bias)) in enumerate(jobs):
+            tab["mean"][g, :, :, :x.shape[1]], tab["inv2v"][g], tab["bias"][g] = mean, inv2v, bias
+        self._close(tab, host=True)
 
     def launch(self):
-        from . import ops
-        ops.check(ops.lib.wdg_qda_errors_batched_i32(ctypes.cast(self.host, ctypes.c_void_p), ops._ptr(self.table), self.n_jobs,
-                                                     ops.stream_handle()), "wdg_qda_errors_batched_i32")
+        self._launch("wdg_qda_errors_batched_i32", host=True)
         return self.counts
 
 

@@ -9,43 +9,46 @@ import torch
 from . import _lib
 from ._lib import c_void_p, check, lib, require_gpu, stream_handle
 from ._rt import *  # noqa: F401,F403  (the flag values of include/wdg.h)
-from ._rt import _dev, _h2d, _ld, _ptr, _table
+from ._rt import _dev, _ld, _ptr
+from .job_table import JobTable
 
 
-class GemmBatch:
+_GEMM_JOB, _MLP2_JOB = np.dtype(_lib.GemmJob), np.dtype(_lib.Mlp2Job)
+
+
+def _members(entries, width):
+    """the entries' members, one list per position (`width` empty lists for no entries)"""
+    return [list(m) for m in zip(*entries)] if entries else [[] for _ in range(width)]
+
+
+class GemmBatch(JobTable):
     """Job table for wdg_gemm_batched_f32: C_i = act(A_i @ B_i + bias_i), one launch."""
 
     def __init__(self, entries, relu=False):
         """entries: list of (A [M,K], B [K,N], C [M,N], bias|None) fp32 device tensors (unit inner stride)."""
-        dev = require_gpu()
-        self.keep = entries
-        arr = (_lib.GemmJob * len(entries))()
-        self.max_m = self.max_n = self.max_k = 0
-        self.flops = 0
-        self.flags = GEMM_A_VEC4  # cleared by the first job whose A is not 16-byte aligned with lda % 4 == K % 4 == 0
-        for job, (a, b, c, bias) in zip(arr, entries):
-            m, k = a.shape
-            n = b.shape[1]
-            if b.shape[0] != k or tuple(c.shape) != (m, n) or any(t.stride(1) != 1 or t.dtype != torch.float32 for t in (a, b, c)):
+        self._open(entries)
+        for a, b, c, _bias in entries:
+            if b.shape[0] != a.shape[1] or tuple(c.shape) != (a.shape[0], b.shape[1]) or \
+                    any(t.stride(1) != 1 or t.dtype != torch.float32 for t in (a, b, c)):
                 raise ValueError("GemmBatch: shape / layout mismatch")
-            job.A, job.B, job.C = a.data_ptr(), b.data_ptr(), c.data_ptr()
-            job.bias = 0 if bias is None else bias.data_ptr()
-            job.lda, job.ldb, job.ldc = _ld(a), _ld(b), _ld(c)
-            job.M, job.N, job.K, job.act = m, n, k, (ACT_RELU if relu else ACT_NONE)
-            self.max_m, self.max_n, self.max_k = max(self.max_m, m), max(self.max_n, n), max(self.max_k, k)
-            if a.data_ptr() % 16 or job.lda % 4 or k % 4:
-                self.flags = 0
-            self.flops += 2 * m * n * k
-        self.n_jobs = len(entries)
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8) if len(entries) else torch.empty(0, dtype=torch.uint8)
-        self.table = _h2d(host, dev) if len(entries) else host
+        tab = self._records(_GEMM_JOB)
+        a_, b_, c_, bias_ = _members(entries, 4)
+        for field, ts, ld in (("A", a_, "lda"), ("B", b_, "ldb"), ("C", c_, "ldc"), ("bias", bias_, None)):
+            self._point(tab, field, ts, ld=ld)
+        dims = np.array([(a.shape[0], b.shape[1], a.shape[1]) for a, b in zip(a_, b_)], np.int64).reshape(-1, 3)
+        tab["M"], tab["N"], tab["K"] = dims.T
+        tab["act"] = ACT_RELU if relu else ACT_NONE
+        self.max_m, self.max_n, self.max_k = (int(v) for v in dims.max(axis=0, initial=0))
+        self.flops = int(2 * dims.prod(axis=1).sum())
+        # GEMM_A_VEC4 unless a job's A is not 16-byte aligned with lda % 4 == K % 4 == 0
+        self.flags = 0 if ((tab["A"] % 16 != 0) | (tab["lda"] % 4 != 0) | (tab["K"] % 4 != 0)).any() else GEMM_A_VEC4
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_gemm_batched_flags_f32(_ptr(self.table), self.n_jobs, self.max_m, self.max_n, self.max_k, self.flags,
-                                             stream_handle()), "wdg_gemm_batched_flags_f32")
+        self._launch("wdg_gemm_batched_flags_f32", self.max_m, self.max_n, self.max_k, self.flags)
 
 
-class Mlp2Batch:
+class Mlp2Batch(JobTable):
     """Job table for wdg_mlp2_batched_f32: Z_i = act(A_i W0_i + b0_i) W1_i + b1_i, one launch, one pass over A_i, the hidden
     layer never stored.  `eligible(entries)` says whether the fused kernel takes the shapes (else: two GemmBatch)."""
 
@@ -73,36 +76,30 @@ class Mlp2Batch:
 
     def __init__(self, entries, relu=True):
         """entries: list of (A [M,K], W0 [K,H], b0 [H]|None, W1 [H,C], b1 [C]|None, Z [M,C]) fp32 device tensors."""
-        dev = require_gpu()
+        self._open(entries)
         if not self.eligible(entries):
             raise ValueError("Mlp2Batch: needs H <= 64, C <= 8, K <= 512, K % 4 == 0, 16-byte aligned rows of A")
-        self.keep = entries
-        arr = (_lib.Mlp2Job * len(entries))()
-        self.max_m = self.max_k = self.max_h = self.max_c = 0
-        self.flops = 0
-        for job, (a, w0, b0, w1, b1, z) in zip(arr, entries):
-            (m, k), h, c = a.shape, w0.shape[1], w1.shape[1]
-            if w0.shape[0] != k or w1.shape[0] != h or tuple(z.shape) != (m, c) or \
+        for a, w0, _b0, w1, _b1, z in entries:
+            if w0.shape[0] != a.shape[1] or w1.shape[0] != w0.shape[1] or tuple(z.shape) != (a.shape[0], w1.shape[1]) or \
                     any(t.stride(1) != 1 or t.dtype != torch.float32 for t in (w0, w1, z) + (() if isinstance(a, Tiled) else (a,))):
                 raise ValueError("Mlp2Batch: shape / layout mismatch")
-            job.A, job.W0, job.W1, job.Z = a.data_ptr(), w0.data_ptr(), w1.data_ptr(), z.data_ptr()
-            job.b0 = 0 if b0 is None else b0.data_ptr()
-            job.b1 = 0 if b1 is None else b1.data_ptr()
-            job.lda, job.ldw0, job.ldw1, job.ldz = (a.ld if isinstance(a, Tiled) else _ld(a)), _ld(w0), _ld(w1), _ld(z)
-            job.a_group_stride = a.group_stride if isinstance(a, Tiled) else 0
-            job.M, job.K, job.H, job.C, job.act = m, k, h, c, (ACT_RELU if relu else ACT_NONE)
-            self.max_m, self.max_k = max(self.max_m, m), max(self.max_k, k)
-            self.max_h, self.max_c = max(self.max_h, h), max(self.max_c, c)
-            self.flops += 2 * m * h * (k + c)
-        self.n_jobs = len(entries)
-        self.table = _h2d(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8), dev)
+        tab = self._records(_MLP2_JOB)
+        a_, w0_, b0_, w1_, b1_, z_ = _members(entries, 6)
+        for field, ts, ld in (("A", a_, "lda"), ("W0", w0_, "ldw0"), ("W1", w1_, "ldw1"), ("Z", z_, "ldz"), ("b0", b0_, None), ("b1", b1_, None)):
+            self._point(tab, field, ts, ld=ld)
+        tab["a_group_stride"] = [a.group_stride if isinstance(a, Tiled) else 0 for a in a_]
+        dims = np.array([(a.shape[0], a.shape[1], w0.shape[1], w1.shape[1]) for a, w0, w1 in zip(a_, w0_, w1_)], np.int64).reshape(-1, 4)
+        tab["M"], tab["K"], tab["H"], tab["C"] = dims.T
+        tab["act"] = ACT_RELU if relu else ACT_NONE
+        self.max_m, self.max_k, self.max_h, self.max_c = (int(v) for v in dims.max(axis=0))
+        self.flops = int((2 * dims[:, 0] * dims[:, 2] * (dims[:, 1] + dims[:, 3])).sum())
+        self._close(tab)
         # the kernel is chosen HERE, with the table, and named at every launch (1 = WDG_KERNEL_SPLIT, 2 = WDG_KERNEL_CHAIN,
         # 4 = WDG_OPERAND_TILED): the environment may change between build and launch, the table's layout does not
-        self.flags = (1 if self.split_kernel() else 2) | (4 if any(isinstance(e[0], Tiled) for e in entries) else 0)
+        self.flags = (1 if self.split_kernel() else 2) | (4 if any(isinstance(a, Tiled) for a in a_) else 0)
 
     def launch(self):
-        check(lib.wdg_mlp2_batched_flags_f32(_ptr(self.table), self.n_jobs, self.max_m, self.max_k, self.max_h, self.max_c, self.flags,
-                                             stream_handle()), "wdg_mlp2_batched_flags_f32")
+        self._launch("wdg_mlp2_batched_flags_f32", self.max_m, self.max_k, self.max_h, self.max_c, self.flags)
 
 
 # ------------------------------------------------------------------------------------------- GEMM

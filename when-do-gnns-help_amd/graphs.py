@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import c_void_p, check, lib, require_gpu, stream_handle
 from ._rt import *  # noqa: F401,F403  (the flag values of include/wdg.h)
 from ._rt import _arena_take, _dev, _h2d, _H2D_MAX_BYTES, _ld, _ptr, _table
+from .job_table import JobTable, block_offsets, unit_bytes
 
 
 def quad_disabled():
@@ -619,6 +620,7 @@ class GraphBatch:
 
 # ------------------------------------------------------------------------------------------- two-hop neighbourhoods
 TWO_HOP_KEEP_ONE_HOP, TWO_HOP_KEEP_SELF = 1, 2  # WDG_TWO_HOP_* of include/wdg.h
+_TWO_HOP_JOB, _TOPK_JOB = np.dtype(_lib.TwoHopJob), np.dtype(_lib.TopkJob)
 
 
 def two_hop_totals(totals):
@@ -633,7 +635,7 @@ def two_hop_totals(totals):
     return out
 
 
-class TwoHopBatch:
+class TwoHopBatch(JobTable):
     """The strict two-hop neighbourhoods T = (A . A > 0) \\ (A u I) of a list of square CsrGraphs as ONE job table
     (wdg_csr_two_hop_count_batched / _fill_batched, csrc/two_hop.hip; include/wdg.h defines the result): row i of T holds the nodes
     reached from i in exactly two steps that are neither i nor stored in row i - OUT-neighbours of OUT-neighbours, so T of a directed
@@ -646,6 +648,7 @@ class TwoHopBatch:
     allocates, so it must not be called inside a stream capture."""
 
     MAX_JOBS = 65535
+    _JOBS = "graphs"
 
     @staticmethod
     def max_rows():
@@ -655,52 +658,41 @@ class TwoHopBatch:
         graphs, flags = list(graphs), int(flags)
         if flags & ~(TWO_HOP_KEEP_ONE_HOP | TWO_HOP_KEEP_SELF):
             raise ValueError(f"TwoHopBatch: flags = {flags} (TWO_HOP_KEEP_ONE_HOP = 1 and TWO_HOP_KEEP_SELF = 2 are defined)")
-        if len(graphs) > self.MAX_JOBS:
-            raise ValueError(f"TwoHopBatch: {len(graphs)} graphs; one launch takes {self.MAX_JOBS}")
+        self.G = self._open(graphs)
         limit = self.max_rows()
         for g_, g in enumerate(graphs):
             if g.n_rows != g.n_cols:
                 raise ValueError(f"TwoHopBatch: graph {g_} is {g.n_rows} x {g.n_cols}; a square pattern expected")
             if g.n_rows > limit:
                 raise ValueError(f"TwoHopBatch: graph {g_} has {g.n_rows} rows; a wave's bitmap holds at most {limit} columns in LDS")
-        dev = require_gpu()
-        self.graphs, self.flags, self.G = graphs, flags, len(graphs)
+        tab = self._records(_TWO_HOP_JOB)
+        self.graphs, self.flags = graphs, flags
         self.ns = [g.n_rows for g in graphs]
         self.max_n = max(self.ns, default=0)
         # every graph's row pointers in one pool (a slice per graph, 256-byte aligned like an allocation of its own) and the totals;
         # zeros: a table of nothing but empty graphs launches nothing
-        off = np.concatenate([[0], np.cumsum([(n + 1 + 63) // 64 * 64 for n in self.ns])]).astype(np.int64)
-        self._rowptr_off = off
-        self.rowptr_pool = torch.zeros(int(off[-1]), dtype=torch.int32, device=dev)
-        self.totals = torch.zeros(max(self.G, 1), dtype=torch.int64, device=dev)
-        self.jobs = (_lib.TwoHopJob * max(self.G, 1))()
-        for g_, g in enumerate(graphs):
-            job = self.jobs[g_]
-            job.rowptr, job.col = g.rowptr.data_ptr(), g.col.data_ptr() if g.nnz else 0
-            job.n, job.flags = g.n_rows, flags
-            job.out_rowptr, job.out_col = self.rowptr_pool.data_ptr() + 4 * int(off[g_]), 0
-            job.total = self.totals.data_ptr() + 8 * g_
-        check(lib.wdg_csr_two_hop_check_jobs(ctypes.cast(self.jobs, c_void_p), self.G), "wdg_csr_two_hop_check_jobs")
+        tab["out_rowptr"] = self._own("rowptr_pool", [n + 1 for n in self.ns], torch.int32, of="_rowptr_of", align=64, floor=0)
+        tab["total"] = self._own("totals", np.ones(self.G, np.int64), torch.int64, of=None)
+        self._point(tab, "rowptr", [g.rowptr for g in graphs])
+        self._point(tab, "col", [g.col if g.nnz else None for g in graphs])
+        tab["n"], tab["flags"] = self.ns, flags
+        self._close(tab, "wdg_csr_two_hop_check_jobs", host=True)  # (the count pass's table; out_col comes with the fill pass's)
 
     def launch(self):
         """count pass, the ONE read-back of all totals (IndexError / OverflowError: two_hop_totals), fill pass -> list of CsrGraph"""
-        G, st = self.G, stream_handle()
-        dev = self.rowptr_pool.device
-        if G == 0:
+        if self.G == 0:
             return []
-        table = _table((_lib.TwoHopJob * G)(*self.jobs[:G]))
-        check(lib.wdg_csr_two_hop_count_batched(_ptr(table), G, self.max_n, st), "wdg_csr_two_hop_count_batched")
-        totals = two_hop_totals(self.totals[:G].cpu().tolist())  # the one host sync of the build
-        base = np.concatenate([[0], np.cumsum([(t + 63) // 64 * 64 for t in totals])]).astype(np.int64)
-        col_pool = torch.empty(int(base[-1]), dtype=torch.int32, device=dev)
-        for g_ in range(G):
-            self.jobs[g_].out_col = col_pool.data_ptr() + 4 * int(base[g_]) if totals[g_] else 0
-        table2 = _table((_lib.TwoHopJob * G)(*self.jobs[:G]))
-        check(lib.wdg_csr_two_hop_fill_batched(_ptr(table2), G, self.max_n, st), "wdg_csr_two_hop_fill_batched")
-        self._keep = (table, table2)  # (alive until the launches that read them have run)
-        off = self._rowptr_off
-        return [CsrGraph(self.rowptr_pool[int(off[g_]):int(off[g_]) + self.ns[g_] + 1], col_pool[int(base[g_]):int(base[g_]) + totals[g_]], None,
-                         self.ns[g_], self.ns[g_]) for g_ in range(G)]
+        counted = self.table
+        self._launch("wdg_csr_two_hop_count_batched", self.max_n)
+        totals = two_hop_totals(self.totals[:self.G].cpu().tolist())  # the one host sync of the build
+        # (the columns are this launch's result, not the table's: a pool of their own, in 64-word slices like the row pointers)
+        base, _ = block_offsets(totals, align=64)
+        col_pool = torch.empty(int(base[-1]), dtype=torch.int32, device=self._dev)
+        self.host["out_col"] = np.where(np.asarray(totals) > 0, col_pool.data_ptr() + unit_bytes(torch.int32) * base[:-1], 0)
+        self._close(self.host, host=True)
+        self._launch("wdg_csr_two_hop_fill_batched", self.max_n)
+        self._keep = (counted, self.table)  # (alive until the launches that read them have run)
+        return [CsrGraph(rowptr, col_pool[at:at + t], None, n, n) for rowptr, at, t, n in zip(self._rowptr_of, base.tolist(), totals, self.ns)]
 
 
 def two_hop(g, flags=0):
@@ -723,7 +715,7 @@ def _byte_range(t):
     return (t.data_ptr(), t.data_ptr() + last * t.element_size())
 
 
-class TopkRowsBatch:
+class TopkRowsBatch(JobTable):
     """The k best columns of every row of a LIST of dense fp32 matrices as ONE job table (wdg_topk_rows_batched_f32,
     csrc/topk_rows.hip; include/wdg.h defines the result): key = scores[r, j] * col_scale[j] (one rounded product), NaN keys are
     not eligible, larger keys rank first and equal keys (-0 == +0) by the lower column - a total order, so the output is the same
@@ -744,6 +736,7 @@ class TopkRowsBatch:
     asked for."""
 
     MAX_JOBS = 65535
+    _JOBS = "jobs"
     KEYS = {"scores": None, "k": None, "col_scale": None, "row0": 0, "exclude_self": False, "sort_columns": False, "keys": False,
             "out_col": None, "out_key": None, "out_len": None}
 
@@ -762,9 +755,8 @@ class TopkRowsBatch:
         return t
 
     def __init__(self, entries):
-        entries = [dict(e) for e in entries]
-        if len(entries) > self.MAX_JOBS:
-            raise ValueError(f"TopkRowsBatch: {len(entries)} jobs; one launch takes {self.MAX_JOBS}")
+        self.G = self._open(entries)
+        entries = self.keep = [dict(e) for e in entries]
         for i, e in enumerate(entries):
             unknown = sorted(set(e) - set(self.KEYS))
             if unknown:
@@ -798,37 +790,39 @@ class TopkRowsBatch:
             for j, m_, (lo2, hi2) in ins + outs[a + 1:]:
                 if lo < hi2 and lo2 < hi:
                     raise ValueError(f"TopkRowsBatch: {n_} of entry {i} overlaps {m_} of entry {j}")
-        dev = require_gpu()
+        tab = self._records(_TOPK_JOB)
+        dev = self._dev
         for i, e in enumerate(entries):
             for n_ in ("scores", "col_scale", "out_col", "out_key", "out_len"):
                 if e[n_] is not None and e[n_].device != dev:
                     raise ValueError(f"TopkRowsBatch: entry {i}: {n_} lives on {e[n_].device}, the current device is {dev}")
-        self.entries, self.G = entries, len(entries)
+        self.entries = entries
         self.max_rows = max([e["scores"].shape[0] for e in entries], default=0)
         self.out_col, self.out_key, self.out_len = [], [], []
-        self.jobs = (_lib.TopkJob * max(self.G, 1))()
-        for job, e in zip(self.jobs, entries):
-            s, k = e["scores"], e["k"]
-            rows, cols = s.shape
+        for e in entries:
+            (rows, _cols), k = e["scores"].shape, e["k"]
             oc = e["out_col"] if e["out_col"] is not None else torch.empty((rows, k), dtype=torch.int32, device=dev)
             ol = e["out_len"] if e["out_len"] is not None else torch.empty(rows, dtype=torch.int32, device=dev)
             ok = e["out_key"] if e["out_key"] is not None else (torch.empty((rows, k), dtype=torch.float32, device=dev) if e["keys"] else None)
             if ok is not None and _ld(ok) != _ld(oc):
                 raise ValueError("TopkRowsBatch: out_col and out_key of an entry share ONE leading dimension")
             self.out_col.append(oc), self.out_key.append(ok), self.out_len.append(ol)
-            job.scores, job.col_scale = s.data_ptr() if s.numel() else 0, 0 if e["col_scale"] is None else e["col_scale"].data_ptr()
-            job.out_col, job.out_key, job.out_len = oc.data_ptr(), 0 if ok is None else ok.data_ptr(), ol.data_ptr()
-            job.ld, job.ld_out = max(_ld(s), cols), max(_ld(oc), k)
-            job.rows, job.cols, job.row0, job.k = rows, cols, int(e["row0"]), k
-            job.flags = (TOPK_EXCLUDE_SELF if e["exclude_self"] else 0) | (TOPK_SORT_COLUMNS if e["sort_columns"] else 0)
-            if rows == 0:  # (an empty allocation has no address: nothing of it is written)
-                job.out_col = job.out_col or 256
-                job.out_len = job.out_len or 256
-        check(lib.wdg_topk_rows_check_jobs(ctypes.cast(self.jobs, c_void_p), self.G), "wdg_topk_rows_check_jobs")
-        self.table = _table((_lib.TopkJob * self.G)(*self.jobs[:self.G]))
+        scores = [e["scores"] for e in entries]
+        tab["rows"], tab["cols"] = np.array([tuple(s.shape) for s in scores], np.int64).reshape(-1, 2).T
+        tab["k"], tab["row0"] = [e["k"] for e in entries], [int(e["row0"]) for e in entries]
+        tab["flags"] = [(TOPK_EXCLUDE_SELF if e["exclude_self"] else 0) | (TOPK_SORT_COLUMNS if e["sort_columns"] else 0) for e in entries]
+        self._point(tab, "scores", [s if s.numel() else None for s in scores])
+        tab["ld"] = [max(_ld(s), s.shape[1]) for s in scores]
+        self._point(tab, "col_scale", [e["col_scale"] for e in entries])
+        self._point(tab, "out_col", self.out_col, ld="ld_out", cols=tab["k"])
+        self._point(tab, "out_key", self.out_key)
+        self._point(tab, "out_len", self.out_len)
+        for field in ("out_col", "out_len"):  # (an empty allocation has no address: nothing of it is written)
+            tab[field][(tab["rows"] == 0) & (tab[field] == 0)] = 256
+        self._close(tab, "wdg_topk_rows_check_jobs")
 
     def launch(self):
-        check(lib.wdg_topk_rows_batched_f32(_ptr(self.table), self.G, self.max_rows, stream_handle()), "wdg_topk_rows_batched_f32")
+        self._launch("wdg_topk_rows_batched_f32", self.max_rows)
         return self
 
 

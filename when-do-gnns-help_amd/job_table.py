@@ -1,7 +1,7 @@
-"""What the job tables of the training kernels (train.py) share: a table is one array of fixed-size records (the ctypes mirrors of
-include/wdg.h in _lib.py) on the device, one record per job, that a kernel reads in one launch.  A record points at the caller's tensors
-and at buffers the table OWNS: one tensor per kind of buffer for all jobs, a block per job, with an initial pattern that reset() puts
-back and - for the buffers a run rewinds with its parameters - a place in state_tensors().
+"""What the job tables share: a table is one array of fixed-size records (the ctypes mirrors of include/wdg.h in _lib.py) on the device,
+one record per job, that a kernel reads in one launch.  A record points at the caller's tensors and at buffers the table OWNS: one tensor
+per kind of buffer for all jobs, a block per job, with an initial pattern that reset() puts back (or none: a workspace) and - for the
+buffers a run rewinds with its parameters - a place in state_tensors().
 
 JobTable is the sequence a constructor walks through, as methods it calls in order - no hooks:
     n = self._open(entries)            keep, n_jobs, the limit of one launch (before any check of an entry)
@@ -13,21 +13,35 @@ JobTable is the sequence a constructor walks through, as methods it calls in ord
 and launch() is self._launch("wdg_...", the arguments between n_jobs and the stream).  StackedLogitsTable adds what the four tables over
 stacked logits (csrc/stacked_row.h) fill alike.
 
-Not on this base (yet): GemmBatch, Mlp2Batch and SpmmBatch - the sweep step's hot tables, built from ctypes arrays - and the tables of
-kernel_regression.py, stats.py, synth.py and csbmh.py.  sparse_features.SparseDenseBatch shares _upload only."""
+On this base: the tables of train.py, kernel_regression.py (RowRepBatch, GramBatch, EdgeGramBatch, KrSets, KrBatch, GnbBatch, SvmBatch),
+stats.py, gemm.py, synth.py and csbmh.py, sparse_features.SparseDenseBatch and graphs.TwoHopBatch / TopkRowsBatch; their bytes are
+pinned by tests/golden/job_table_layout.json and job_table_layout_sweep.json (scripts/describe_job_tables.py), their host cost by
+profiles/job_table_timing.json and job_table_sweep_timing.json (scripts/time_job_tables.py).
+Not on it: aggregate.SpmmBatch - its records come from _fill_job, which the single-graph calls share through ctypes.byref, and it carries
+the segment plan - and the graph build (GraphBatch), FeatureExpand, DeviceFeatures, PropagatedGram: _rt._table uploads their ctypes arrays."""
 import ctypes
 import math
 
 import numpy as np
-import torch
 
-from ._lib import check, lib, require_gpu, stream_handle
-from ._rt import _h2d, _ld, _ptr
+# torch, the binding (_lib: importing it loads the library) and the plumbing (_rt) are bound to these names by _load(), when a table is
+# opened or an entry checked: importing this module loads nothing, so the modules of host code that also define a table (csbmh.py,
+# synth.py, sparse_features.py) import with numpy alone, as sweep_jobs needs them on a launcher (tests/test_sweep_modules.py)
+torch = check = lib = require_gpu = stream_handle = _h2d = _ld = _ptr = None
+
+
+def _load():
+    global torch, check, lib, require_gpu, stream_handle, _h2d, _ld, _ptr
+    if lib is None:
+        import torch
+        from ._lib import check, lib, require_gpu, stream_handle
+        from ._rt import _h2d, _ld, _ptr
 
 
 def _check_matrix(table, name, t, shape=None):
     """ValueError (naming the table and the operand) unless t is a 2-D fp32 device matrix - of `shape`, where one is given (None = any
     size in that dimension) - whose rows are contiguous and do not overlap; any leading dimension"""
+    _load()
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (
             shape is not None and any(want is not None and want != got for want, got in zip(shape, t.shape))):
         what = "2-D" if shape is None else "[" + ", ".join("any" if d is None else str(d) for d in shape) + "]"
@@ -38,6 +52,7 @@ def _check_matrix(table, name, t, shape=None):
 
 def _step_word(where, step):
     """-> the pointer of a launch's step word: a one-element int32 DEVICE tensor, read by the kernel when it runs"""
+    _load()
     if not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1 or not step.is_cuda:
         raise ValueError(f"{where}: a one-element int32 device tensor expected as the step word")
     return _ptr(step)
@@ -51,6 +66,7 @@ def _offsets(lens, n):
 def _upload(tab, n, dev, check_jobs=None):
     """the device copy of a table of n records (an empty tensor for none) - after the host-side check of the records, where the
     kernel has one (check_jobs: its name in lib)"""
+    _load()
     host = np.ascontiguousarray(tab)
     if check_jobs is not None:
         check(getattr(lib, check_jobs)(ctypes.c_void_p(host.ctypes.data), n), check_jobs)
@@ -107,9 +123,11 @@ class JobTable:
     MAX_JOBS = None  # (no limit)
     _JOBS = "entries"  # what the table's messages call its jobs
 
-    def _open(self, entries):
-        """keep, n_jobs and the limit of one launch -> n_jobs"""
-        self.keep, self.n_jobs, self._owned = entries, len(entries), []
+    def _open(self, entries, n=None):
+        """keep, n_jobs and the limit of one launch -> n_jobs (n: the count of a table given as columns - KrBatch.from_arrays - whose
+        `entries` is only what it keeps alive)"""
+        _load()
+        self.keep, self.n_jobs, self._owned = entries, len(entries) if n is None else int(n), []
         if self.MAX_JOBS is not None and self.n_jobs > self.MAX_JOBS:
             raise ValueError(f"{type(self).__name__}: {self.n_jobs} {self._JOBS}; one launch takes {self.MAX_JOBS}")
         return self.n_jobs
@@ -119,9 +137,11 @@ class JobTable:
         self._dev = require_gpu()
         return np.zeros(self.n_jobs, dtype)
 
-    def _own(self, name, counts, dtype, unit=(), init=0, shapes=None, of=..., align=1, planes=None, reset=True, state=False):
+    def _own(self, name, counts, dtype, unit=(), init=0, shapes=None, of=..., align=1, planes=None, reset=True, state=False, floor=None):
         """One buffer of the table's own: ONE tensor self.<name> of [units of all jobs] + unit elements, a block of counts[i] units per
-        job (block_offsets), every row set to `init` - a number, or the pattern of a unit such as (-1, 0, 0).
+        job (block_offsets), every row set to `init` - a number, or the pattern of a unit such as (-1, 0, 0); None: left UNINITIALISED
+        (a workspace, an output the kernel writes whole: no fill is enqueued, and reset() leaves it alone).  floor: the least number of
+        units to allocate instead of block_offsets' `align` - 256 for a pool of workspace bytes, 0 for a buffer that is EMPTY without jobs.
         -> the int64 column of the blocks' addresses.
         The jobs' views go to self.<of> (default <name>_of; None: no list): [counts[i]] + unit, or shapes[i] where shapes are given - a
         job whose shape is None gets None as its view and a NULL address.  planes = (names): the tensor is [len(planes), units] and a job
@@ -129,8 +149,12 @@ class JobTable:
         reset / state: whether reset() puts `init` back, whether state_tensors() lists the buffer (in the order of the _own calls)."""
         n = self.n_jobs
         off, total = block_offsets(counts, align)
+        if floor is not None:
+            total = max(int(off[-1]), floor)
         size = ((len(planes),) if planes else ()) + (total,) + tuple(unit)
-        if isinstance(init, tuple) or init == 0:
+        if init is None:
+            t = torch.empty(size, dtype=dtype, device=self._dev)
+        elif isinstance(init, tuple) or init == 0:
             t = torch.zeros(size, dtype=dtype, device=self._dev)
             if init != 0:
                 self._set(t, init, fresh=True)
@@ -175,19 +199,25 @@ class JobTable:
         elif ld is not None:
             tab[ld] = np.fromiter((0 if t is None else max(_ld(t), c) for t, c in zip(tensors, cols)), np.int64, n)
 
-    def _close(self, tab, check_jobs=None):
-        """the host-side check of the records, where the kernel has one, and the upload"""
+    def _close(self, tab, check_jobs=None, host=False):
+        """the host-side check of the records, where the kernel has one, and the upload.  host: the records stay, as self.host - for a
+        launcher that takes them beside the device table (_launch(host=True): ClassGraphBatch, GaussFeatureBatch, QdaBatch; the table
+        of no jobs is then None), or a launch() that uploads them again (TwoHopBatch)"""
         self.table = _upload(tab, self.n_jobs, self._dev, check_jobs)
+        if host:
+            self.host, self.table = np.ascontiguousarray(tab), self.table if self.n_jobs else None
 
-    def _launch(self, entry_point, *args):
-        """lib.<entry_point>(table, n_jobs, *args, stream)"""
-        check(getattr(lib, entry_point)(_ptr(self.table), self.n_jobs, *args, stream_handle()), entry_point)
+    def _launch(self, entry_point, *args, host=False):
+        """lib.<entry_point>(table, n_jobs, *args, stream) - host: the kept host records go in front of the table"""
+        head = (ctypes.c_void_p(self.host.ctypes.data),) if host else ()
+        check(getattr(lib, entry_point)(*head, _ptr(self.table), self.n_jobs, *args, stream_handle()), entry_point)
 
     def reset(self):
         """the table's own state back to what the constructor left (what is the caller's - parameters, step words - is not touched, nor
-        are the settings copied into the table)"""
+        are the settings copied into the table).  For the training tables, whose runs rewind; the other tables own outputs that every
+        launch writes anew - some in tensors of their own making (StatsBatch.counters, KrBatch's window buffers) - and nobody resets them"""
         for name, init, reset, _ in self._owned:
-            if reset:
+            if reset and init is not None:
                 self._set(getattr(self, name), init)
 
     def state_tensors(self):

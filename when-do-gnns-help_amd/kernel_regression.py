@@ -9,6 +9,7 @@ from . import _lib
 from ._lib import c_void_p, check, lib, require_gpu, stream_handle
 from ._rt import *  # noqa: F401,F403  (the flag values of include/wdg.h)
 from ._rt import _dev, _h2d, _ld, _ptr, _table
+from .job_table import JobTable, _upload, unit_bytes
 
 
 # ------------------------------------------------------------------------------------------- kernel-regression metric
@@ -17,50 +18,51 @@ def deflation_enabled():
     return os.environ.get("WDG_KR_DEFLATE", "1") not in ("0", "")
 
 
-class RowRepBatch:
+_ROW_REP_JOB, _GRAM_JOB, _EDGE_GRAM_JOB = np.dtype(_lib.RowRepJob), np.dtype(_lib.GramJob), np.dtype(_lib.EdgeGramJob)
+
+
+class RowRepBatch(JobTable):
     """Job table for wdg_row_rep_batched: per matrix the map row -> smallest bit-identical row (`rep[i]`, int32 [n]) - what the
     kernel-regression solver deflates duplicate nodes with (KrBatch(rep=...); csrc/row_rep.hip)."""
 
     def __init__(self, dense=None, csr=None, out=None):
         """dense: list of A [n, F] fp32 device tensors (or ops.Tiled) - or csr: list of (CsrGraph, row_scale | None, use_values)
         out: another RowRepBatch over matrices of the same row counts whose `rep` tensors this one fills"""
-        dev = require_gpu()
         if (dense is None) == (csr is None):
             raise ValueError("RowRepBatch: dense or csr")
         self.source = 0 if dense is not None else 1
-        items = dense if dense is not None else csr
-        self.keep = items
+        self._open(dense if dense is not None else csr)
         ns = [int(a.shape[0]) for a in dense] if dense is not None else [int(g.n_rows) for g, _rs, _uv in csr]
-        self.n_jobs, self.max_n = len(ns), max(ns, default=0)
-        off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        self.max_n = max(ns, default=0)
+        if out is not None and [int(r.shape[0]) for r in out.rep] != ns:
+            raise ValueError("RowRepBatch(out=...): the other batch's maps have other lengths")
+        if any(a.dtype != torch.float32 or a.stride(1) != 1 for a in dense or ()):
+            raise ValueError("RowRepBatch: A must be fp32 with unit inner stride")
+        tab = self._records(_ROW_REP_JOB)
         if out is not None:
-            if [int(r.shape[0]) for r in out.rep] != ns:
-                raise ValueError("RowRepBatch(out=...): the other batch's maps have other lengths")
             self.rep = out.rep
+            self._point(tab, "rep_out", self.rep)
         else:
-            pool = torch.empty(int(off[-1]), dtype=torch.int32, device=dev)
-            self.rep = [pool[int(off[i]):int(off[i + 1])] for i in range(len(ns))]
-        self.hash_ws = torch.empty(max(int(off[-1]), 1), dtype=torch.int64, device=dev)
-        arr = (_lib.RowRepJob * self.n_jobs)()
-        for i, (job, it) in enumerate(zip(arr, items)):
-            job.rep_out, job.hash_ws, job.n = self.rep[i].data_ptr(), self.hash_ws.data_ptr() + 8 * int(off[i]), ns[i]
-            if dense is not None:
-                if it.dtype != torch.float32 or it.stride(1) != 1:
-                    raise ValueError("RowRepBatch: A must be fp32 with unit inner stride")
-                job.A, job.lda, job.F = it.data_ptr(), _ld(it), int(it.shape[1])
-                job.a_group_stride = it.group_stride if isinstance(it, Tiled) else 0
-            else:
-                g, rs, use_values = it
-                job.rowptr, job.col = g.rowptr.data_ptr(), g.col.data_ptr()
-                job.val = g.val.data_ptr() if (use_values and g.val is not None and not getattr(g, "unit_values", False)) else 0
-                job.row_scale = 0 if rs is None else rs.data_ptr()
-        self.table = _table(arr)
+            tab["rep_out"] = self._own("_pool", ns, torch.int32, init=None, of="rep", floor=0)
+        tab["hash_ws"] = self._own("hash_ws", ns, torch.int64, init=None, of=None)
+        tab["n"] = ns
+        if dense is not None:
+            self._point(tab, "A", dense, ld="lda")
+            tab["F"] = [int(a.shape[1]) for a in dense]
+            tab["a_group_stride"] = [a.group_stride if isinstance(a, Tiled) else 0 for a in dense]
+        else:
+            for field in ("rowptr", "col"):
+                self._point(tab, field, [getattr(g, field) for g, _rs, _uv in csr])
+            self._point(tab, "val", [g.val if (use_values and g.val is not None and not getattr(g, "unit_values", False)) else None
+                                     for g, _rs, use_values in csr])
+            self._point(tab, "row_scale", [rs for _g, rs, _uv in csr])
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_row_rep_batched(_ptr(self.table), self.n_jobs, self.max_n, self.source, stream_handle()), "wdg_row_rep_batched")
+        self._launch("wdg_row_rep_batched", self.max_n, self.source)
 
 
-class GramBatch:
+class GramBatch(JobTable):
     """Job table for wdg_gram_map_batched_f32: K = map(A A^T) of every A of a batch (all nodes), linear and / or arc-cosine."""
 
     def __init__(self, mats, linear=True, arccos=True, out=None):
@@ -68,38 +70,40 @@ class GramBatch:
         features - when the split-operand kernels run: `tiled_ok()`) -> self.k_linear[i], self.k_arccos[i] ([n, n] or None)
         out: another GramBatch over matrices of the same row counts whose output buffers this one writes (a sweep's next feature
         base on the same graphs: every table that holds those addresses stays valid)"""
-        dev = require_gpu()
-        self.keep = mats
-        self.n_jobs = len(mats)
-        self.max_n = max([a.shape[0] for a in mats], default=0)
+        n = self._open(mats)
+        rows = [a.shape[0] for a in mats]
+        self.max_n = max(rows, default=0)
+        if out is not None and (rows != [k.shape[0] for k in out.norm2] or (linear and out.k_linear[:1] == [None])
+                                or (arccos and out.k_arccos[:1] == [None])):
+            raise ValueError("GramBatch(out=...): the other batch's outputs have other shapes")
+        tiled = [isinstance(a, Tiled) for a in mats]
+        if any(a.dtype != torch.float32 or a.stride(1) != 1 for a in mats):
+            raise ValueError("GramBatch: A must be fp32 with unit inner stride")
+        if any(tiled) and not self.tiled_ok():
+            raise ValueError("GramBatch: a tiled A needs the split-operand kernels (WDG_GRAM_SPLIT=0 is set)")
+        tab = self._records(_GRAM_JOB)
         if out is not None:
-            if [a.shape[0] for a in mats] != [k.shape[0] for k in out.norm2] or (linear and out.k_linear[:1] == [None]) or (arccos and out.k_arccos[:1] == [None]):
-                raise ValueError("GramBatch(out=...): the other batch's outputs have other shapes")
-            self.norm2, self.k_linear, self.k_arccos = out.norm2, out.k_linear if linear else [None] * len(mats), out.k_arccos if arccos else [None] * len(mats)
+            self.norm2, self.k_linear, self.k_arccos = out.norm2, out.k_linear if linear else [None] * n, out.k_arccos if arccos else [None] * n
         else:
             # (one allocation per matrix: 16-MB blocks come back from torch's caching allocator in microseconds; one 1-GB block per
             # output kind - tried in round 5 - is returned to the driver between shards and costs 5 ms per allocation)
-            self.norm2 = [torch.empty(a.shape[0], dtype=torch.float32, device=dev) for a in mats]
-            self.k_linear = [torch.empty((a.shape[0], a.shape[0]), dtype=torch.float32, device=dev) if linear else None for a in mats]
-            self.k_arccos = [torch.empty((a.shape[0], a.shape[0]), dtype=torch.float32, device=dev) if arccos else None for a in mats]
-        arr = (_lib.GramJob * self.n_jobs)()
-        for job, a, n2, kl, ka in zip(arr, mats, self.norm2, self.k_linear, self.k_arccos):
-            if a.dtype != torch.float32 or a.stride(1) != 1:
-                raise ValueError("GramBatch: A must be fp32 with unit inner stride")
-            if isinstance(a, Tiled) and not self.tiled_ok():
-                raise ValueError("GramBatch: a tiled A needs the split-operand kernels (WDG_GRAM_SPLIT=0 is set)")
-            job.a_group_stride = a.group_stride if isinstance(a, Tiled) else 0
-            job.A, job.norm2 = a.data_ptr(), n2.data_ptr()
-            job.K_linear = 0 if kl is None else kl.data_ptr()
-            job.K_arccos = 0 if ka is None else ka.data_ptr()
-            job.lda, job.ldk, job.n, job.F = _ld(a), a.shape[0], a.shape[0], a.shape[1]
-        self.table = _table(arr)
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self._dev)  # noqa: E731
+            self.norm2 = [new(r) for r in rows]
+            self.k_linear = [new(r, r) if linear else None for r in rows]
+            self.k_arccos = [new(r, r) if arccos else None for r in rows]
+        self._point(tab, "A", mats, ld="lda")
+        for field, ts in (("norm2", self.norm2), ("K_linear", self.k_linear), ("K_arccos", self.k_arccos)):
+            self._point(tab, field, ts)
+        tab["a_group_stride"] = [a.group_stride if t else 0 for a, t in zip(mats, tiled)]
+        tab["ldk"] = tab["n"] = rows
+        tab["F"] = [a.shape[1] for a in mats]
+        self._close(tab)
         # the kernel family is chosen with the table and named at every launch (1 = WDG_KERNEL_SPLIT, 2 = WDG_KERNEL_CHAIN,
         # 4 = WDG_OPERAND_TILED): see Mlp2Batch
-        self.flags = (1 if self.tiled_ok() else 2) | (4 if any(isinstance(a, Tiled) for a in mats) else 0)
+        self.flags = (1 if self.tiled_ok() else 2) | (4 if any(tiled) else 0)
         # rep[i]: row -> smallest bit-identical row of A_i (launch() fills it beside the Gram): the solver's deflation maps
         self.row_rep = (RowRepBatch(dense=mats, out=getattr(out, "row_rep", None)) if (deflation_enabled() and mats) else None)
-        self.rep = self.row_rep.rep if self.row_rep is not None else [None] * len(mats)
+        self.rep = self.row_rep.rep if self.row_rep is not None else [None] * n
 
     @staticmethod
     def tiled_ok():
@@ -111,8 +115,7 @@ class GramBatch:
             return False
 
     def launch(self):
-        check(lib.wdg_gram_map_batched_flags_f32(_ptr(self.table), self.n_jobs, self.max_n, self.flags, stream_handle()),
-              "wdg_gram_map_batched_flags_f32")
+        self._launch("wdg_gram_map_batched_flags_f32", self.max_n, self.flags)
         if self.row_rep is not None:
             self.row_rep.launch()
 
@@ -198,29 +201,27 @@ class PropagatedGram:
             self.row_rep.launch()
 
 
-class EdgeGramBatch:
+class EdgeGramBatch(JobTable):
     """Job table for wdg_edge_gram_mean_batched_f32: mean edge cosine (generalized edge homophily) of many graphs from the Grams
     of their feature matrices."""
 
     def __init__(self, problems):
         """problems: list of (CsrGraph, K_linear [n, n], norm2 [n]) -> self.mean [n_problems] fp64 after launch()"""
-        dev = require_gpu()
-        self.keep = problems
-        self.n_jobs = len(problems)
+        n = self._open(problems)
         self.max_rows = max([p[0].n_rows for p in problems], default=0)
-        self.mean = torch.zeros(max(self.n_jobs, 1), dtype=torch.float64, device=dev)
-        self.ws_bytes = lib.wdg_edge_gram_workspace_bytes(self.n_jobs, self.max_rows)
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-        arr = (_lib.EdgeGramJob * self.n_jobs)()
-        for i, (job, (g, k, n2)) in enumerate(zip(arr, problems)):
-            job.rowptr, job.col, job.K_linear, job.norm2 = g.rowptr.data_ptr(), g.col.data_ptr(), k.data_ptr(), n2.data_ptr()
-            job.mean_out = self.mean.data_ptr() + 8 * i
-            job.ldk, job.n_rows = _ld(k), g.n_rows
-        self.table = _table(arr)
+        tab = self._records(_EDGE_GRAM_JOB)
+        tab["mean_out"] = self._own("mean", np.ones(n, np.int64), torch.float64, of=None)
+        self.ws_bytes = lib.wdg_edge_gram_workspace_bytes(n, self.max_rows)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self._dev)
+        for field in ("rowptr", "col"):
+            self._point(tab, field, [getattr(g, field) for g, _k, _n2 in problems])
+        self._point(tab, "K_linear", [k for _g, k, _n2 in problems], ld="ldk")
+        self._point(tab, "norm2", [n2 for _g, _k, n2 in problems])
+        tab["n_rows"] = [g.n_rows for g, _k, _n2 in problems]
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_edge_gram_mean_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, _ptr(self.ws), self.ws_bytes,
-                                                 stream_handle()), "wdg_edge_gram_mean_batched_f32")
+        self._launch("wdg_edge_gram_mean_batched_f32", self.max_rows, _ptr(self.ws), self.ws_bytes)
 
 
 def kr_split_sizes(labels, sample_max):
@@ -245,7 +246,7 @@ def kr_split_sizes(labels, sample_max):
 _KR_SAMPLE_DTYPE = np.dtype(_lib.KrSampleJob)  # the record type of the ctypes mirror: its names, offsets and size
 
 
-class KrSets:
+class KrSets(JobTable):
     """Job table for wdg_kr_sample_sets: the (train, validation) node sets of every epoch of many (graph, classifier) pairs,
     drawn on the device in one launch (Philox4x32-10 keyed per pair; include/wdg.h documents the generator).
     self.train [pairs, epochs, n_train], self.val [pairs, epochs, n_val] int32, ascending ids; pairs whose graphs differ in
@@ -259,57 +260,46 @@ class KrSets:
     def __init__(self, entries, epochs, out=None):
         """entries: list of (labels int32 device [n], s_c, t_c (kr_split_sizes), seed int)
         out: another KrSets of the same shape whose train / val tensors this one fills (other seeds for the same label vectors)"""
-        dev = require_gpu()
-        self.keep = entries
-        self.n_pairs, self.epochs = len(entries), int(epochs)
-        # (the table by column arithmetic: entries that share a label vector - the jobs of a sweep - share its per-class arrays)
-        n = self.n_pairs
-        sums = {}
+        n = self.n_pairs = self._open(entries)
+        self.epochs = int(epochs)
+        # entries that share a label vector - the jobs of a sweep - share its per-class arrays: one [s_c | t_c] block per distinct
+        # pair of arrays (by identity), and its sums
+        blocks, parts, at = {}, [], 0
         for _l, s_, t, _seed in entries:
-            if (id(s_), id(t)) not in sums:
-                sums[(id(s_), id(t))] = (int(np.sum(t)), int(np.sum(s_)) - int(np.sum(t)), len(s_))
-        self.n_train = np.fromiter((sums[(id(e[1]), id(e[2]))][0] for e in entries), np.int64, n)
-        self.n_val = np.fromiter((sums[(id(e[1]), id(e[2]))][1] for e in entries), np.int64, n)
-        n_cls = np.fromiter((sums[(id(e[1]), id(e[2]))][2] for e in entries), np.int64, n)
+            if (id(s_), id(t)) not in blocks:
+                blocks[(id(s_), id(t))] = (at, int(np.sum(t)), int(np.sum(s_)) - int(np.sum(t)), len(s_))
+                parts += [np.asarray(s_, np.int32), np.asarray(t, np.int32)]
+                at += 2 * len(s_)
+        off_of, self.n_train, self.n_val, n_cls = np.array([blocks[(id(e[1]), id(e[2]))] for e in entries], np.int64).reshape(-1, 4).T
         if n and int(n_cls.max()) > 64:
             raise ValueError("KrSets: more than 64 classes")
         self.train_stride, self.val_stride = int(self.n_train.max(initial=0)), int(self.n_val.max(initial=0))
         ts, vs = max(self.train_stride, 1), max(self.val_stride, 1)
-        # (zeros only where sets are padded to a common stride: the kernel writes every entry of a set)
-        alloc = torch.zeros if (n and (int(self.n_train.min()) != ts or int(self.n_val.min()) != vs)) else torch.empty
-        if out is not None:
-            if tuple(out.train.shape) != (n, self.epochs, ts) or tuple(out.val.shape) != (n, self.epochs, vs):
-                raise ValueError("KrSets(out=...): the other table's sets have another shape")
-            self.train, self.val = out.train, out.val
-        else:
-            self.train = alloc((n, self.epochs, ts), dtype=torch.int32, device=dev)
-            self.val = alloc((n, self.epochs, vs), dtype=torch.int32, device=dev)
+        if out is not None and (tuple(out.train.shape) != (n, self.epochs, ts) or tuple(out.val.shape) != (n, self.epochs, vs)):
+            raise ValueError("KrSets(out=...): the other table's sets have another shape")
         self.max_n = max([int(e[0].shape[0]) for e in entries], default=0)
-        tables, off_of, parts, off = {}, np.zeros(n, np.int64), [], 0
-        for i, (_l, s_, t, _seed) in enumerate(entries):  # one [s_c | t_c] block per distinct pair of arrays
-            key = (id(s_), id(t))
-            if key not in tables:
-                tables[key] = off
-                parts += [np.asarray(s_, np.int32), np.asarray(t, np.int32)]
-                off += 2 * len(s_)
-            off_of[i] = tables[key]
-        self.class_tables = _h2d(np.concatenate(parts) if parts else np.zeros(0, np.int32), dev)
-        tab = np.zeros(n, _KR_SAMPLE_DTYPE)
+        tab = self._records(_KR_SAMPLE_DTYPE)
+        # (zeros only where sets are padded to a common stride: the kernel writes every entry of a set)
+        init = 0 if (n and (int(self.n_train.min()) != ts or int(self.n_val.min()) != vs)) else None
         idx = np.arange(n, dtype=np.int64)
-        tab["labels"] = np.fromiter((e[0].data_ptr() for e in entries), np.int64, n)
-        tab["sample_per_class"] = self.class_tables.data_ptr() + 4 * off_of
-        tab["train_per_class"] = self.class_tables.data_ptr() + 4 * (off_of + n_cls)
-        tab["train_out"] = self.train.data_ptr() + 4 * idx * self.epochs * ts
-        tab["val_out"] = self.val.data_ptr() + 4 * idx * self.epochs * vs
+        for name, width in (("train", ts), ("val", vs)):
+            if out is not None:
+                setattr(self, name, getattr(out, name))
+                tab[name + "_out"] = getattr(out, name).data_ptr() + unit_bytes(torch.int32, (self.epochs, width)) * idx
+            else:
+                tab[name + "_out"] = self._own(name, np.ones(n, np.int64), torch.int32, unit=(self.epochs, width), init=init, of=None, floor=0)
+        self.class_tables = _h2d(np.concatenate(parts) if parts else np.zeros(0, np.int32), self._dev)
+        self._point(tab, "labels", [e[0] for e in entries])
+        tab["sample_per_class"] = self.class_tables.data_ptr() + unit_bytes(torch.int32) * off_of
+        tab["train_per_class"] = self.class_tables.data_ptr() + unit_bytes(torch.int32) * (off_of + n_cls)
         tab["seed"] = np.fromiter((int(e[3]) & 0xFFFFFFFFFFFFFFFF for e in entries), np.uint64, n)
-        tab["n"] = np.fromiter((int(e[0].shape[0]) for e in entries), np.int64, n)
+        tab["n"] = [int(e[0].shape[0]) for e in entries]
         tab["n_classes"], tab["n_sets"], tab["first_set"] = n_cls, self.epochs, idx * self.epochs
         tab["train_stride"], tab["val_stride"] = ts, vs
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_kr_sample_sets(_ptr(self.table), self.n_pairs, self.n_pairs * self.epochs, self.max_n, stream_handle()),
-              "wdg_kr_sample_sets")
+        self._launch("wdg_kr_sample_sets", self.n_pairs * self.epochs, self.max_n)
 
 
 _KR_JOB_DTYPE = np.dtype(_lib.KrJob)
@@ -364,7 +354,7 @@ def release_kr_large_scratch():
     _KR_LARGE_SCRATCH.clear()
 
 
-class KrBatch:
+class KrBatch(JobTable):
     """Job table for the batched kernel-regression solvers: many (kernel, train rows, validation rows) problems in one launch -
     wdg_kernel_regress_batched_f32 (train blocks of up to 320 rows, register-resident) or, for a table that holds a larger block,
     wdg_kernel_regress_large_batched_f32 (up to 1024 rows, the factor in device memory)."""
@@ -389,13 +379,14 @@ class KrBatch:
         -> self.correct [n_problems] int32 after launch().  Shapes the chosen solver does not hold (more than 8 classes, more than
         320 / 1024 or fewer than 1 train rows) raise here: the kernel would answer them with the sentinel -1, and an accuracy of
         -1 / n_val fed to the t-test is a silently wrong p-value (callers with such label sets take the host path)."""
-        self.keep = problems
-        n = len(problems)
-        col = lambda f: np.fromiter((f(p_) for p_ in problems), np.int64, n)  # noqa: E731
-        self._build(col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0])), col(lambda p_: p_[1].data_ptr()),
-                    col(lambda p_: p_[2].data_ptr()), col(lambda p_: p_[3].data_ptr()), col(lambda p_: p_[1].shape[0]),
-                    col(lambda p_: p_[2].shape[0]), n_classes,
-                    col(lambda p_: p_[4].data_ptr() if len(p_) > 4 and p_[4] is not None else 0), route=route, class_windows=class_windows)
+        self._open(problems)
+        dims = np.array([(_ld(p_[0]), p_[1].shape[0], p_[2].shape[0]) for p_ in problems], np.int64).reshape(-1, 3)
+
+        def point(tab):
+            for k, field in enumerate(("K", "train", "val", "labels")):
+                self._point(tab, field, [p_[k] for p_ in problems])
+            self._point(tab, "rep", [p_[4] if len(p_) > 4 else None for p_ in problems])
+        self._build(*dims.T, n_classes, point, route, class_windows)
 
     @classmethod
     def from_arrays(cls, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, keep=None, rep_ptr=None, route="auto",
@@ -403,14 +394,16 @@ class KrBatch:
         """the same table from per-problem numpy columns (device addresses and sizes): a sweep shard's 20 000 problems are
         described by arithmetic on a few base pointers, not by 20 000 tensor objects"""
         self = cls.__new__(cls)
-        self.keep = keep
-        self._build(*(np.asarray(a, np.int64) for a in (k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val)), n_classes,
-                    None if rep_ptr is None else np.asarray(rep_ptr, np.int64), route=route, class_windows=class_windows)
+        self._open(keep, n=len(k_ptr))
+
+        def point(tab):
+            tab["K"], tab["train"], tab["val"], tab["labels"], tab["rep"] = k_ptr, train_ptr, val_ptr, labels_ptr, 0 if rep_ptr is None else rep_ptr
+        self._build(*(np.asarray(a, np.int64) for a in (ldk, n_train, n_val)), n_classes, point, route, class_windows)
         return self
 
-    def _build(self, k_ptr, ldk, train_ptr, val_ptr, labels_ptr, n_train, n_val, n_classes, rep_ptr=None, route="auto", class_windows=False):
-        dev = require_gpu()
-        n = self.n_jobs = int(k_ptr.shape[0])
+    def _build(self, ldk, n_train, n_val, n_classes, point, route, class_windows):
+        """point(tab): fills the columns K, train, val, labels and rep of the records"""
+        n = self.n_jobs
         if route not in self.ROUTES:
             raise ValueError(f"KrBatch: unknown route {route!r} (one of {', '.join(self.ROUTES)})")
         max_classes = self.MAX_CLASSES_WINDOWED if class_windows else self.MAX_CLASSES
@@ -426,21 +419,20 @@ class KrBatch:
                              + ("" if self.large else f" (route {route!r}; the large solver holds 1..{self.MAX_TRAIN_LARGE})"))
         if n and int(ldk.max()) >= 65536:  # (the solver's prediction gathers address a kernel matrix by 32-bit element offsets)
             raise ValueError(f"KrBatch: kernel matrices of leading dimension {int(ldk.max())}, the solver addresses up to 65 535")
-        self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        self.flags = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)  # bit 0: ridge refactorisation, 1: deflated, 2: rows dropped
+        tab = self._records(_KR_JOB_DTYPE)
+        dev = self._dev
+        point(tab)
+        tab["correct_out"] = self._own("correct", np.ones(n, np.int64), torch.int32, of=None)
+        tab["flags_out"] = self._own("flags", np.ones(n, np.int64), torch.int32, of=None)  # bit 0: ridge refactorisation, 1: deflated, 2: rows dropped
         self.n_val = _h2d(n_val.astype(np.float32), dev)
-        tab = np.zeros(n, _KR_JOB_DTYPE)
-        tab["K"], tab["train"], tab["val"], tab["labels"] = k_ptr, train_ptr, val_ptr, labels_ptr
-        tab["correct_out"] = self.correct.data_ptr() + 4 * np.arange(n, dtype=np.int64)
-        tab["flags_out"] = self.flags.data_ptr() + 4 * np.arange(n, dtype=np.int64)
         tab["ldk"], tab["n_train"], tab["n_val"], tab["n_classes"] = ldk, n_train, n_val, int(n_classes)
         # row representatives -> the deflating entry point: a workspace for EVERY problem of the table (problems without maps: identity)
         self.ws = None
-        tab["rep"] = 0 if rep_ptr is None else rep_ptr
         if n and bool((tab["rep"] != 0).any()):
             per = int(lib.wdg_kr_large_workspace_bytes(int(n_train.max()), int(n_val.max())) if self.large
                       else lib.wdg_kr_deflate_workspace_bytes(int(n_val.max())))
-            self.ws = torch.empty(n * n_win * per, dtype=torch.uint8, device=dev)  # (windowed: a workspace per window job)
+            # (a line of the class: windowed, there is a workspace per WINDOW job, and kr_class_window_tables hands them out)
+            self.ws = torch.empty(n * n_win * per, dtype=torch.uint8, device=dev)
             tab["ws"] = self.ws.data_ptr() + per * np.arange(n, dtype=np.int64)
         # (large) the factor storage belongs to the launch, not to the table: CUs x 2.1 MiB shared, in stream order, by the tables
         # launched on one stream - taken here for the stream that is current now, and by launch() for the one current then
@@ -455,8 +447,8 @@ class KrBatch:
             tab, comb = kr_class_window_tables(tab, n_classes, self.rows.data_ptr(), row_stride, self.win_correct.data_ptr(),
                                                self.win_flags.data_ptr(), 0 if self.ws is None else self.ws.data_ptr(),
                                                0 if self.ws is None else per)
-            self.combine_table = _h2d(comb.view(np.uint8), dev)
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+            self.combine_table = _upload(comb, n, dev)
+        self._close(tab)
 
     def launch(self):
         if self.windowed and self.n_jobs:
@@ -472,13 +464,11 @@ class KrBatch:
         elif self.large:
             if self.n_jobs:
                 self.scratch = _kr_large_scratch(self.correct.device)
-            check(lib.wdg_kernel_regress_large_batched_f32(_ptr(self.table), self.n_jobs, _ptr(self.scratch),
-                                                           self.scratch.numel() if self.n_jobs else 0, stream_handle()),
-                  "wdg_kernel_regress_large_batched_f32")
+            self._launch("wdg_kernel_regress_large_batched_f32", _ptr(self.scratch), self.scratch.numel() if self.n_jobs else 0)
         elif self.ws is not None:
-            check(lib.wdg_kernel_regress_deflated_batched_f32(_ptr(self.table), self.n_jobs, stream_handle()), "wdg_kernel_regress_deflated_batched_f32")
+            self._launch("wdg_kernel_regress_deflated_batched_f32")
         else:
-            check(lib.wdg_kernel_regress_batched_f32(_ptr(self.table), self.n_jobs, stream_handle()), "wdg_kernel_regress_batched_f32")
+            self._launch("wdg_kernel_regress_batched_f32")
 
     def ridged(self):
         """[n_problems] bool: the train block was rank deficient in fp32 and was solved with the rounding-level ridge"""
@@ -501,16 +491,6 @@ class KrBatch:
 
 
 # ------------------------------------------------------------------------------------------- what the GNB and SVM tables share
-def _pooled(counts, dtype, dev, fill=None, width=None, floor=1):
-    """One allocation for every job's `counts[i]` rows (of `width` elements each, when given) -> (pool, the jobs' views of it, the
-    views' device addresses [n] int64).  fill None: uninitialised; the pool holds at least `floor` rows (a table without jobs)."""
-    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    shape = (max(int(off[-1]), floor),) + (() if width is None else (width,))
-    pool = torch.empty(shape, dtype=dtype, device=dev) if fill is None else torch.full(shape, fill, dtype=dtype, device=dev)
-    views = [pool[int(off[i]):int(off[i + 1])] for i in range(len(counts))]
-    return pool, views, pool.data_ptr() + pool.element_size() * (width or 1) * off[:-1]
-
-
 def _host_hit_rate(correct, n_val):
     """[n_problems] float32 (host): hits / validation rows, as `torch.mean(pred.eq(labels[idx_val]).float())` gives them
     (utils/homophily_metrics.py:311-312, :328-329); NaN for a problem without validation rows"""
@@ -523,7 +503,7 @@ def _host_hit_rate(correct, n_val):
 _GNB_JOB_DTYPE = np.dtype(_lib.GnbJob)
 
 
-class GnbBatch:
+class GnbBatch(JobTable):
     """Job table for wdg_gnb_batched_f32: many (feature matrix, train rows, validation rows) Gaussian-naive-Bayes problems in one call -
     the GNB branch of classifier_based_performance_metric (utils/homophily_metrics.py:296-312), scikit-learn's arithmetic (csrc/gnb.hip)."""
 
@@ -534,9 +514,7 @@ class GnbBatch:
         the statistics are summed over the train rows IN THE ORDER GIVEN (the reference's boolean masks: ascending ids).
         -> self.correct [n_problems] int32 after launch(); want_pred: self.pred[i] int32 [nv] too.
         Raises for what scikit-learn raises for or the kernel does not hold: no train rows, no features, more than 16 classes."""
-        dev = require_gpu()
-        self.keep = problems
-        n = self.n_jobs = len(problems)
+        n = self._open(problems)
         self.n_classes = int(n_classes)
         if n and not 1 <= self.n_classes <= self.MAX_CLASSES:
             raise ValueError(f"GnbBatch: {n_classes} classes, the kernel holds 1..{self.MAX_CLASSES}")
@@ -549,26 +527,23 @@ class GnbBatch:
                 raise ValueError("GnbBatch: a problem needs at least one train row and one feature")
             if lab.shape[0] != x.shape[0]:
                 raise ValueError("GnbBatch: one label per row of X")
-        col = lambda f: np.fromiter((f(p_) for p_ in problems), np.int64, n)  # noqa: E731
-        feats, n_val = col(lambda p_: p_[0].shape[1]), col(lambda p_: p_[2].shape[0])
-        self.max_feat, self.max_val = int(feats.max(initial=0)), int(n_val.max(initial=0))
-        self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        self.n_val = n_val
-        self.ws, _, ws_ptr = _pooled([int(lib.wdg_gnb_workspace_bytes(int(f), self.n_classes)) for f in feats], torch.uint8, dev, floor=256)
+        feats, n_train, n_val = np.array([(x.shape[1], tr.shape[0], va.shape[0]) for x, tr, va, _lab in problems], np.int64).reshape(-1, 3).T
+        self.max_feat, self.max_val, self.n_val = int(feats.max(initial=0)), int(n_val.max(initial=0)), n_val
+        tab = self._records(_GNB_JOB_DTYPE)
+        self._point(tab, "X", [p_[0] for p_ in problems], ld="ldx")
+        for k, field in enumerate(("train", "val", "labels"), 1):
+            self._point(tab, field, [p_[k] for p_ in problems])
+        tab["correct"] = self._own("correct", np.ones(n, np.int64), torch.int32, of=None)
+        tab["ws"] = self._own("ws", [int(lib.wdg_gnb_workspace_bytes(int(f), self.n_classes)) for f in feats], torch.uint8, init=None,
+                              of=None, floor=256)
         self.pred = None
-        tab = np.zeros(n, _GNB_JOB_DTYPE)
-        tab["X"], tab["ldx"] = col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0]))
-        tab["train"], tab["val"], tab["labels"] = col(lambda p_: p_[1].data_ptr()), col(lambda p_: p_[2].data_ptr()), col(lambda p_: p_[3].data_ptr())
-        tab["ws"] = ws_ptr
-        tab["correct"] = self.correct.data_ptr() + 4 * np.arange(n, dtype=np.int64)
         if want_pred:
-            _, self.pred, tab["pred"] = _pooled(n_val, torch.int32, dev, fill=-1)
-        tab["n_train"], tab["n_val"], tab["F"], tab["n_classes"] = col(lambda p_: p_[1].shape[0]), n_val, feats, self.n_classes
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+            tab["pred"] = self._own("_pred", n_val, torch.int32, init=-1, of="pred")
+        tab["n_train"], tab["n_val"], tab["F"], tab["n_classes"] = n_train, n_val, feats, self.n_classes
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_gnb_batched_f32(_ptr(self.table), self.n_jobs, self.max_feat, self.max_val, self.n_classes, stream_handle()),
-              "wdg_gnb_batched_f32")
+        self._launch("wdg_gnb_batched_f32", self.max_feat, self.max_val, self.n_classes)
 
     def accuracy(self):
         """[n_problems] float32 (host): hits / validation rows (_host_hit_rate)"""
@@ -579,7 +554,7 @@ class GnbBatch:
 _SVM_JOB_DTYPE = np.dtype(_lib.SvmJob)
 
 
-class SvmBatch:
+class SvmBatch(JobTable):
     """Job table for wdg_svm_batched_f32: many (Gram, train rows, validation rows) one-vs-one C-SVC problems in one call - the svm_rbf /
     svm_poly / svm_linear branches of classifier_based_performance_metric (utils/homophily_metrics.py:313-333), libsvm's arithmetic as
     scikit-learn calls it (csrc/svm.hip; tests/_svm_ref.py restates it)."""
@@ -600,9 +575,7 @@ class SvmBatch:
         (the pairs of the PRESENT classes first, in libsvm's order; a positive value votes for the lower class).
         Raises ValueError for what the kernel does not hold: more than 16 classes, more than 1024 train rows, no train rows, another
         dtype than fp32."""
-        dev = require_gpu()
-        self.keep = problems
-        n = self.n_jobs = len(problems)
+        n = self._open(problems)
         self.n_classes = int(n_classes)
         if kernel not in self.KERNELS:
             raise ValueError(f"SvmBatch: unknown kernel {kernel!r}")
@@ -628,34 +601,30 @@ class SvmBatch:
                 raise ValueError(f"SvmBatch: {tr.shape[0]} train rows, the solver holds 1..{self.MAX_TRAIN}")
             if lab.shape[0] != g.shape[0] or int(feat) < 1:
                 raise ValueError("SvmBatch: one label per row of the Gram and at least one feature")
-        col = lambda f: np.fromiter((f(p_) for p_ in problems), np.int64, n)  # noqa: E731
-        n_train, n_val = col(lambda p_: p_[3].shape[0]), col(lambda p_: p_[4].shape[0])
+        n_train, n_val, feats = np.array([(p_[3].shape[0], p_[4].shape[0], int(p_[6])) for p_ in problems], np.int64).reshape(-1, 3).T
         self.max_train, self.max_val, self.n_val = int(n_train.max(initial=0)), int(n_val.max(initial=0)), n_val
         self.n_pairs = self.n_classes * (self.n_classes - 1) // 2
-        self.correct = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        self.info = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
-        self.ws, _, ws_ptr = _pooled([int(lib.wdg_svm_workspace_bytes(int(t), self.n_classes)) for t in n_train], torch.uint8, dev, floor=256)
+        tab = self._records(_SVM_JOB_DTYPE)
+        self._point(tab, "G_half", [p_[0] for p_ in problems], ld="ldk")
+        for k, field in enumerate(("norm2", "row_sum", "train", "val", "labels"), 1):
+            self._point(tab, field, [p_[k] for p_ in problems])
+        tab["correct"] = self._own("correct", np.ones(n, np.int64), torch.int32, of=None)
+        tab["info"] = self._own("info", np.ones(n, np.int64), torch.int32, unit=(4,), of=None)
+        tab["ws"] = self._own("ws", [int(lib.wdg_svm_workspace_bytes(int(t), self.n_classes)) for t in n_train], torch.uint8, init=None,
+                              of=None, floor=256)
         self.pred = self.dec = None
-        tab = np.zeros(n, _SVM_JOB_DTYPE)
-        tab["G_half"], tab["ldk"] = col(lambda p_: p_[0].data_ptr()), col(lambda p_: _ld(p_[0]))
-        tab["norm2"], tab["row_sum"] = col(lambda p_: p_[1].data_ptr()), col(lambda p_: 0 if p_[2] is None else p_[2].data_ptr())
-        tab["train"], tab["val"], tab["labels"] = col(lambda p_: p_[3].data_ptr()), col(lambda p_: p_[4].data_ptr()), col(lambda p_: p_[5].data_ptr())
-        tab["ws"] = ws_ptr
-        tab["correct"] = self.correct.data_ptr() + 4 * np.arange(n, dtype=np.int64)
-        tab["info"] = self.info.data_ptr() + 16 * np.arange(n, dtype=np.int64)
         if want_pred:
-            _, self.pred, tab["pred"] = _pooled(n_val, torch.int32, dev, fill=-1)
+            tab["pred"] = self._own("_pred", n_val, torch.int32, init=-1, of="pred")
         if want_dec:
-            _, self.dec, tab["dec"] = _pooled(n_val, torch.float64, dev, fill=0.0, width=max(self.n_pairs, 1))
+            tab["dec"] = self._own("_dec", n_val, torch.float64, unit=(max(self.n_pairs, 1),), of="dec")
         tab["C"], tab["gamma"] = float(C), 0.0 if scale else float(gamma)
         tab["kernel"], tab["degree"] = self.KERNELS[kernel], int(degree)
         tab["max_iter"] = np.minimum(1000 * n_train, 2 ** 31 - 1) if max_iter is None else int(max_iter)
-        tab["n_train"], tab["n_val"], tab["n_classes"], tab["F"] = n_train, n_val, self.n_classes, col(lambda p_: int(p_[6]))
-        self.table = _h2d(tab.view(np.uint8), dev) if n else torch.empty(0, dtype=torch.uint8)
+        tab["n_train"], tab["n_val"], tab["n_classes"], tab["F"] = n_train, n_val, self.n_classes, feats
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_svm_batched_f32(_ptr(self.table), self.n_jobs, self.max_train, self.max_val, self.n_classes, stream_handle()),
-              "wdg_svm_batched_f32")
+        self._launch("wdg_svm_batched_f32", self.max_train, self.max_val, self.n_classes)
 
     def flags(self):
         """[n_problems] int32 (host): bit 0 a pair stopped at max_iter, bit 1 fewer than two classes among the train rows"""

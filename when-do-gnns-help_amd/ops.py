@@ -18,8 +18,9 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
   aggregate.py          spmm, SpmmBatch (the quad-row kernel's tape and its cost cut), spmm_plan
   stats.py              edge / label statistics, LAS, per-edge cosine, their job tables
   gemm.py               gemm, gemm_skinny, GemmBatch, Mlp2Batch
-  job_table.py          JobTable, StackedLogitsTable: what the job tables of train.py share - the limit of one launch, the buffers a table
-                        owns (offsets, byte strides, initial patterns, reset(), state_tensors()), the pointer fill, the upload, the launch
+  job_table.py          JobTable, StackedLogitsTable: what the job tables share (all but SpmmBatch, PropagatedGram and the builds) - the limit of one
+                        launch, the buffers a table owns (offsets, byte strides, initial patterns, reset(), state_tensors()), the pointer
+                        fill, the upload, the launch
   train.py              HeadTrainBatch (every epoch of many logistic heads in one launch), DropoutBatch (ReLU + counter-based
                         dropout of many hidden layers in one launch), AcmMixBatch (the channel mix of many ACM layers, forward and backward),
                         AcmMixPackedBatch (the same mix for stacked class-width layers: 1, 2 or 4 lanes per replica),

@@ -13,6 +13,7 @@ the row."""
 import numpy as np
 
 from . import graph_io
+from .job_table import JobTable
 
 KINDS = ("csr", "bits")
 NORMALISE = {None: 0, "sum": 1, "abs": 2}  # WDG_FEAT_NORM_* of include/wdg.h
@@ -411,7 +412,7 @@ class DeviceFeatures:
         return expand_features([self._source])[0]
 
 
-class SparseDenseBatch:
+class SparseDenseBatch(JobTable):
     """Job table for wdg_sparse_dense_batched_f32: entries (DeviceFeatures, transposed, W, Y) - Y = X W, or X^T W with transposed - one
     launch.  W [cols, m] and Y [rows, m] are fp32 device matrices with unit inner stride and any leading dimension >= m."""
 
@@ -421,38 +422,39 @@ class SparseDenseBatch:
         """keep: hold the entries' tensors for as long as the table lives (False: the caller keeps them alive while it launches)"""
         import torch
 
-        from ._lib import SparseDenseJob, require_gpu
+        from ._lib import SparseDenseJob
         from ._rt import _ld
-        from .job_table import _upload
         who = "SparseDenseBatch"
-        if len(entries) > self.MAX_JOBS:
-            raise ValueError(f"{who}: {len(entries)} entries; one launch takes {self.MAX_JOBS}")
-        tab = np.zeros(len(entries), np.dtype(SparseDenseJob))
+        self._open(entries)
+        csr = []
         for i, (feats, transposed, w, y) in enumerate(entries):
             if not isinstance(feats, DeviceFeatures):
                 raise TypeError(f"{who}: entry {i}: a DeviceFeatures expected, not {type(feats).__name__}")
-            rowptr, col, val, order, rows, cols = feats._csr(bool(transposed))
-            for name, t, r in (("W", w, cols), ("Y", y, rows)):
+            csr.append(feats._csr(bool(transposed)))
+            for name, t, r in (("W", w, csr[i][5]), ("Y", y, csr[i][4])):
                 if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == r and t.stride(1) == 1):
                     raise ValueError(f"{who}: entry {i}: {name} must be an fp32 device matrix of {r} rows with unit inner stride")
             if w.shape[1] != y.shape[1]:
                 raise ValueError(f"{who}: entry {i}: W has {w.shape[1]} columns, Y has {y.shape[1]}")
-            m = int(w.shape[1])
-            for name, t in (("rowptr", rowptr), ("col", col), ("val", val), ("order", order), ("W", w), ("Y", y)):
-                tab[name][i] = 0 if t is None or t.numel() == 0 else t.data_ptr()
-            if col.numel() == 0:
-                tab["col"][i] = rowptr.data_ptr()  # (a matrix without entries: any address will do, no row reads it)
-            tab["ldw"][i], tab["ldy"][i] = max(_ld(w), m), max(_ld(y), m)
-            tab["n_rows"][i], tab["n_cols"][i], tab["m"][i] = rows, cols, m
-        self.keep = entries if keep else None
-        self.n_jobs = len(entries)
+        tab = self._records(np.dtype(SparseDenseJob))
+        stored = lambda t: None if t is None or t.numel() == 0 else t  # noqa: E731  (nothing of an empty array is read: NULL)
+        for k, name in enumerate(("rowptr", "col", "val", "order")):
+            self._point(tab, name, [stored(c[k]) for c in csr])
+        empty = [c[1].numel() == 0 for c in csr]
+        if any(empty):  # (a matrix without entries: any address will do for col, no row reads it)
+            tab["col"][empty] = [c[0].data_ptr() for c, e in zip(csr, empty) if e]
+        tab["m"] = [int(w.shape[1]) for _f, _t, w, _y in entries]
+        for name, ld, mats in (("W", "ldw", [e[2] for e in entries]), ("Y", "ldy", [e[3] for e in entries])):
+            self._point(tab, name, [stored(t) for t in mats])
+            tab[ld] = [max(_ld(t), int(t.shape[1])) for t in mats]  # (of an empty matrix too)
+        tab["n_rows"], tab["n_cols"] = [c[4] for c in csr], [c[5] for c in csr]
+        if not keep:
+            self.keep = None
         self.max_rows, self.max_m = int(tab["n_rows"].max(initial=0)), int(tab["m"].max(initial=0))
-        self.table = _upload(tab, self.n_jobs, require_gpu(), "wdg_sparse_dense_check_jobs")
+        self._close(tab, "wdg_sparse_dense_check_jobs")
 
     def launch(self):
-        from ._lib import check, lib, stream_handle
-        from ._rt import _ptr
-        check(lib.wdg_sparse_dense_batched_f32(_ptr(self.table), self.n_jobs, self.max_rows, self.max_m, stream_handle()), "wdg_sparse_dense_batched_f32")
+        self._launch("wdg_sparse_dense_batched_f32", self.max_rows, self.max_m)
 
 
 def sparse_operand(who, x, n):

@@ -1,7 +1,6 @@
 """Edge / label statistics, LAS and the per-edge cosine (reference: utils/homophily_plot.py:43-231 and
 utils/homophily_metrics.py:164-187): one pass over the pattern per graph, or job tables for a sweep shard."""
-import ctypes
-import os
+import math
 
 import numpy as np
 import torch
@@ -9,7 +8,8 @@ import torch
 from . import _lib
 from ._lib import c_void_p, check, lib, require_gpu, stream_handle
 from ._rt import *  # noqa: F401,F403  (the flag values of include/wdg.h)
-from ._rt import _dev, _h2d, _ld, _ptr, _table
+from ._rt import _dev, _h2d, _ld, _ptr
+from .job_table import JobTable, block_offsets, unit_bytes
 from ._lib import StatsJob
 
 
@@ -36,38 +36,36 @@ def edge_label_stats(g, labels, n_classes=None, per_row=True):
     return st
 
 
-class StatsBatch:
+_STATS_JOB, _LAS_JOB = np.dtype(StatsJob), np.dtype(_lib.LasJob)
+
+
+class StatsBatch(JobTable):
     """Job table for wdg_edge_label_stats_batched; outputs live in pooled tensors zeroed by one memset."""
 
     def __init__(self, graphs, labels_list, n_classes):
-        dev = require_gpu()
-        self.n_jobs, self.c = len(graphs), int(n_classes)
-        c = self.c
-        # one pool, three views: a launch zeroes the counters with a single memset
-        self.counters = torch.zeros(self.n_jobs * (6 + c * c + c), dtype=torch.int64, device=dev)
-        self.totals = self.counters[:self.n_jobs * 6].view(self.n_jobs, 6)
-        self.compat = self.counters[self.n_jobs * 6:self.n_jobs * (6 + c * c)].view(self.n_jobs, c, c)
-        self.classdeg = self.counters[self.n_jobs * (6 + c * c):].view(self.n_jobs, c)
+        n = self._open(graphs)
+        self.c = c = int(n_classes)
         self.max_rows = max([g.n_rows for g in graphs], default=0)
-        self.rows = torch.zeros((self.n_jobs, 3, max(self.max_rows, 1)), dtype=torch.int32, device=dev)
-        self.labels = [_dev(l, torch.int32, dev) for l in labels_list]
-        self.keep = graphs
-        # the table by column arithmetic (a structured array with the descriptor's layout): the outputs are slices of pools at
-        # regular strides, so only the graphs' own pointers are read one by one
-        tab = np.zeros(self.n_jobs, np.dtype(StatsJob))
-        idx = np.arange(self.n_jobs, dtype=np.int64)
-        tab["rowptr"] = [g.rowptr.data_ptr() for g in graphs]
-        tab["col"] = [g.col.data_ptr() for g in graphs]
-        tab["labels"] = [l.data_ptr() for l in self.labels]
-        tab["totals"] = self.totals.data_ptr() + 8 * 6 * idx
-        tab["compat"] = self.compat.data_ptr() + 8 * c * c * idx
-        tab["classdeg"] = self.classdeg.data_ptr() + 8 * c * idx
-        row_stride = 4 * self.rows.shape[2]
-        for k, name in enumerate(("row_nnz", "row_nnz_noself", "row_match_noself")):
-            tab[name] = self.rows.data_ptr() + row_stride * (3 * idx + k)
+        tab = self._records(_STATS_JOB)
+        self.labels = [_dev(l, torch.int32, self._dev) for l in labels_list]
+        for field in ("rowptr", "col"):
+            self._point(tab, field, [getattr(g, field) for g in graphs])
+        self._point(tab, "labels", self.labels)
+        # one pool, three views: a launch zeroes the counters with a single memset
+        self.counters = torch.zeros(n * (6 + c * c + c), dtype=torch.int64, device=self._dev)
+        at, idx = 0, np.arange(n, dtype=np.int64)
+        for field, unit in (("totals", (6,)), ("compat", (c, c)), ("classdeg", (c,))):
+            view = self.counters[at:at + n * math.prod(unit)].view((n,) + unit)
+            setattr(self, field, view)
+            tab[field] = view.data_ptr() + unit_bytes(torch.int64, unit) * idx
+            at += view.numel()
+        width = max(self.max_rows, 1)
+        rows = self._own("rows", np.ones(n, np.int64), torch.int32, unit=(3, width), of=None, floor=0)
+        for k, field in enumerate(("row_nnz", "row_nnz_noself", "row_match_noself")):
+            tab[field] = rows + k * unit_bytes(torch.int32, (width,))
         tab["n_rows"] = [g.n_rows for g in graphs]
         tab["n_classes"] = c
-        self.table = _h2d(tab.view(np.uint8), dev) if self.n_jobs else torch.empty(0, dtype=torch.uint8)
+        self._close(tab)
 
     def zero(self):
         """the counters must be zero when the kernel starts (launch() does it; callers that want the memset off a
@@ -77,11 +75,10 @@ class StatsBatch:
     def launch(self, zero=True):
         if zero:
             self.counters.zero_()
-        check(lib.wdg_edge_label_stats_batched(_ptr(self.table), self.n_jobs, self.max_rows, self.c, stream_handle()),
-              "wdg_edge_label_stats_batched")
+        self._launch("wdg_edge_label_stats_batched", self.max_rows, self.c)
 
 
-class LasBatch:
+class LasBatch(JobTable):
     """Job table for wdg_las_batched_f32: soft / hard LAS counts of many graphs in one launch (3 kernels)."""
 
     def __init__(self, entries, n_classes, counts=None, row_scales=None):
@@ -90,37 +87,31 @@ class LasBatch:
         batch's integer counters from H = D^-1 (A + I) onehot(labels) - every node's neighbour-class counts ride in H already -
         instead of a second pass over the edges (include/wdg.h, wdg_las_job.counts; needs the fused one-workgroup path:
         self.derives_counts tells whether it applies)."""
-        dev = require_gpu()
-        self.keep = (entries, counts, row_scales)
-        self.n_jobs, self.c = len(entries), int(n_classes)
-        self.counts = torch.zeros((self.n_jobs, 2), dtype=torch.int64, device=dev)
-        self.n = _h2d(np.array([h.shape[0] for h, _ in entries], np.float32), dev)
-        sizes = [lib.wdg_las_workspace_bytes(h.shape[0], h.shape[1], self.c) for h, _ in entries]
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self.ws = torch.empty(int(offs[-1]) + 256, dtype=torch.uint8, device=dev)
-        tab = np.zeros(self.n_jobs, np.dtype(_lib.LasJob))
-        idx = np.arange(self.n_jobs, dtype=np.int64)
-        tab["H"] = [h.data_ptr() for h, _ in entries]
-        tab["labels"] = [lab.data_ptr() for _, lab in entries]
-        tab["count_out"] = self.counts.data_ptr() + 16 * idx
+        n = self._open(entries)
+        self.keep, self.c = (entries, counts, row_scales), int(n_classes)
+        dims = np.array([tuple(h.shape) for h, _ in entries], np.int64).reshape(-1, 2)
+        self.max_n, self.max_f = (int(v) for v in dims.max(axis=0, initial=0))
+        tab = self._records(_LAS_JOB)
+        self._point(tab, "H", [h for h, _ in entries], ld="ldh")
+        self._point(tab, "labels", [lab for _, lab in entries])
+        tab["count_out"] = self._own("counts", np.ones(n, np.int64), torch.int64, unit=(2,), of=None, floor=0)
+        self.n = _h2d(dims[:, 0].astype(np.float32), self._dev)
+        # (the blocks of the workspace, and 256 spare bytes behind the last)
+        offs, _ = block_offsets([lib.wdg_las_workspace_bytes(int(rows), int(f), self.c) for rows, f in dims])
+        self.ws = torch.empty(int(offs[-1]) + 256, dtype=torch.uint8, device=self._dev)
         tab["workspace"] = self.ws.data_ptr() + offs[:-1]
-        tab["ldh"] = [_ld(h) for h, _ in entries]
-        tab["n"] = [h.shape[0] for h, _ in entries]
-        tab["F"] = [h.shape[1] for h, _ in entries]
+        tab["n"], tab["F"] = dims.T
         tab["C"] = self.c
-        self.max_n = int(tab["n"].max()) if self.n_jobs else 0
-        self.max_f = int(tab["F"].max()) if self.n_jobs else 0
-        self.derives_counts = bool(counts is not None and row_scales is not None and self.n_jobs and counts.n_jobs == self.n_jobs
+        self.derives_counts = bool(counts is not None and row_scales is not None and n and counts.n_jobs == n
                                    and all(h.shape[1] == self.c for h, _ in entries)
                                    and lib.wdg_las_fused_eligible(self.max_n, self.max_f, self.c))
         if self.derives_counts:
-            tab["counts"] = counts.table.data_ptr() + ctypes.sizeof(StatsJob) * idx
-            tab["row_scale"] = [r.data_ptr() for r in row_scales]
-        self.table = _h2d(tab.view(np.uint8), dev) if self.n_jobs else torch.empty(0, dtype=torch.uint8)
+            tab["counts"] = counts.table.data_ptr() + _STATS_JOB.itemsize * np.arange(n, dtype=np.int64)
+            self._point(tab, "row_scale", row_scales)
+        self._close(tab)
 
     def launch(self):
-        check(lib.wdg_las_batched_f32(_ptr(self.table), self.n_jobs, self.max_n, self.max_f, self.c, stream_handle()),
-              "wdg_las_batched_f32")
+        self._launch("wdg_las_batched_f32", self.max_n, self.max_f, self.c)
 
 
 # ------------------------------------------------------------------------------------------- per-edge cosine

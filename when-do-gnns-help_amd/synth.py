@@ -15,6 +15,8 @@ class) and its Gaussian class features (csbm-h.py:174-175).
 """
 import numpy as np
 
+from .job_table import JobTable, unit_bytes
+
 # the 30 levels of synthetic_plot.py:19-20 and the 10-level subset used by BASELINE configs[1]/[2]
 H_LEVELS_30 = [0.05, 0.1, 0.15, 0.16, 0.165, 0.17, 0.175, 0.18, 0.185, 0.19, 0.195, 0.2, 0.21, 0.22, 0.23, 0.24,
                0.25, 0.3, 0.35, 0.4, 0.45, 0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9]
@@ -143,57 +145,49 @@ def sample_feature_rows(base_labels_dev, n, n_classes, seed):
     return out
 
 
-class ClassGraphBatch:
+class ClassGraphBatch(JobTable):
     """Graphs of classes of ANY sizes, each class with a same-class count k[c] and an out-degree d[c] of its own, drawn on the device
     (wdg_synth_classes_batched; the definition is in include/wdg.h) - all jobs in one launch, on one pooled allocation.
     specs: list of (class_sizes, k, d, seed) with up to 16 classes; seed: 64 bits, used as is.
     .graphs: list of (CsrGraph, labels int32 [n]) - views of the pool, rows sorted by column, every value 1; written by launch()."""
 
     def __init__(self, specs, self_loops=False):
-        import ctypes
-
         import torch
 
         from . import _lib, ops
-        dev = ops.require_gpu()
+        n_jobs = self._open(specs)
         loops = 1 if self_loops else 0
-        self.host = (_lib.SynthClassesJob * max(len(specs), 1))()
-        sizes = []
-        for g, (cls, k, d, seed) in enumerate(specs):
+        classes = []
+        for g, (cls, k, d, _seed) in enumerate(specs):
             cls, k, d = [int(v) for v in cls], [int(v) for v in k], [int(v) for v in d]
             if not (1 <= len(cls) <= 16 and len(k) == len(cls) and len(d) == len(cls)):
                 raise ValueError(f"class_graphs_device: graph {g}: 1 .. 16 classes with a size, a k and a d each")
-            n, nnz = sum(cls), sum(m * (dc + loops) for m, dc in zip(cls, d))
-            sizes.append((n, nnz))
-            j = self.host[g]
-            j.n_classes, j.flags, j.seed = len(cls), loops, int(seed) & 0xFFFFFFFFFFFFFFFF
-            for c in range(len(cls)):
-                j.class_size[c], j.k[c], j.d[c] = cls[c], k[c], d[c]
-        words = sum(2 * n + 1 + 2 * nnz for n, nnz in sizes)  # per graph: rowptr [n + 1], labels [n], col [nnz], val [nnz]
-        if words >= (1 << 31):
+            classes.append((cls, k, d))
+        ns = np.array([sum(cls) for cls, _k, _d in classes], np.int64)
+        nnz = np.array([sum(m * (dc + loops) for m, dc in zip(cls, d)) for cls, _k, d in classes], np.int64)
+        words = 2 * ns + 1 + 2 * nnz  # per graph: rowptr [n + 1], labels [n], col [nnz], val [nnz]
+        if int(words.sum()) >= (1 << 31):
             raise ValueError("class_graphs_device: more than 2^31 words in one pool")
-        self.pool = torch.zeros(max(words, 1), dtype=torch.int32, device=dev)
-        self.graphs, at = [], 0
-        for g, (n, nnz) in enumerate(sizes):
-            rowptr, labels = self.pool[at:at + n + 1], self.pool[at + n + 1:at + 2 * n + 1]
-            col, val = self.pool[at + 2 * n + 1:at + 2 * n + 1 + nnz], self.pool[at + 2 * n + 1 + nnz:at + 2 * n + 1 + 2 * nnz].view(torch.float32)
-            j = self.host[g]
-            base = self.pool.data_ptr() + 4 * at
-            j.rowptr, j.labels, j.col, j.val = base, base + 4 * (n + 1), base + 4 * (2 * n + 1), base + 4 * (2 * n + 1 + nnz)
+        tab = self._records(np.dtype(_lib.SynthClassesJob))
+        for g, (cls, k, d) in enumerate(classes):
+            tab["class_size"][g, :len(cls)], tab["k"][g, :len(cls)], tab["d"][g, :len(cls)] = cls, k, d
+        tab["n_classes"], tab["flags"] = [len(cls) for cls, _k, _d in classes], loops
+        tab["seed"] = np.fromiter((int(spec[3]) & 0xFFFFFFFFFFFFFFFF for spec in specs), np.uint64, n_jobs)
+        word = unit_bytes(torch.int32)
+        base = self._own("pool", words, torch.int32, of="_blocks")
+        tab["rowptr"], tab["labels"], tab["col"], tab["val"] = (base + word * at for at in (0, ns + 1, 2 * ns + 1, 2 * ns + 1 + nnz))
+        self.graphs = []
+        for block, n, z in zip(self._blocks, ns.tolist(), nnz.tolist()):
+            rowptr, labels, col, val = block[:n + 1], block[n + 1:2 * n + 1], block[2 * n + 1:2 * n + 1 + z], block[2 * n + 1 + z:].view(torch.float32)
             graph = ops.CsrGraph(rowptr, col, val, n, n)
             graph._unit_values = True  # (the generator writes ones)
             self.graphs.append((graph, labels))
-            at += 2 * n + 1 + 2 * nnz
         self.labels = [lab for _g, lab in self.graphs]
-        self.n_jobs = len(specs)
-        self._cast = ctypes.cast(self.host, ctypes.c_void_p)
-        self.table = ops._table(self.host) if specs else None
+        self._close(tab, host=True)
 
     def launch(self):
         """the one launch, on the current stream (counter-based: again = the same bits into the same arrays)"""
-        from . import ops
-        ops.check(ops.lib.wdg_synth_classes_batched(self._cast, ops._ptr(self.table), self.n_jobs, ops.stream_handle()),
-                  "wdg_synth_classes_batched")
+        self._launch("wdg_synth_classes_batched", host=True)
         return self.graphs
 
 
@@ -202,19 +196,17 @@ def class_graphs_device(specs, self_loops=False):
     return ClassGraphBatch(specs, self_loops).launch()
 
 
-class GaussFeatureBatch:
+class GaussFeatureBatch(JobTable):
     """Gaussian class features drawn on the device (wdg_gauss_features_batched_f32; the definition is in include/wdg.h): job g's
     x[i] = mean[labels[i]] + sd[labels[i]] z, one launch for all jobs, one pooled [sum n, ld] matrix (padding columns are zero).
     labels: list of int32 device tensors; mean [C, F], sd [C] (standard deviations) shared by the jobs; seeds: one per job - give the
     features a seed of their own, not the graph's.  .x: list of [n, F] views, written by launch()."""
 
     def __init__(self, labels, mean, sd, seeds, ld=None):
-        import ctypes
-
         import torch
 
         from . import _lib, ops
-        dev = ops.require_gpu()
+        n_jobs = self._open(labels)
         mean, sd = np.ascontiguousarray(mean, np.float32), np.ascontiguousarray(sd, np.float32).reshape(-1)
         if mean.ndim != 2 or sd.shape[0] != mean.shape[0] or len(seeds) != len(labels):
             raise ValueError("gauss_features_device: mean [C, F], sd [C] and a seed per job expected")
@@ -222,27 +214,22 @@ class GaussFeatureBatch:
         ld = F if ld is None else int(ld)
         if ld < F:
             raise ValueError(f"gauss_features_device: ld = {ld} below F = {F}")
-        self.mean, self.sd = ops._h2d(mean, dev), ops._h2d(sd, dev)
-        ns = [int(lab.shape[0]) for lab in labels]
-        self.pool = torch.zeros((max(sum(ns), 1), ld), dtype=torch.float32, device=dev)
-        self.host = (_lib.GaussJob * max(len(labels), 1))()
-        self.x, at = [], 0
-        for g, (lab, n, seed) in enumerate(zip(labels, ns, seeds)):
+        for g, lab in enumerate(labels):
             if lab.dtype != torch.int32 or not lab.is_contiguous():
                 raise ValueError(f"gauss_features_device: job {g}: contiguous int32 labels expected")
-            j = self.host[g]
-            j.x, j.labels, j.mean, j.sd = self.pool.data_ptr() + 4 * at * ld, lab.data_ptr() if n else 0, self.mean.data_ptr(), self.sd.data_ptr()
-            j.ldx, j.seed, j.n, j.F, j.n_classes, j.reserved = ld, int(seed) & 0xFFFFFFFFFFFFFFFF, n, F, C, 0
-            self.x.append(self.pool[at:at + n, :F])
-            at += n
-        self.keep, self.n_jobs = labels, len(labels)
-        self._cast = ctypes.cast(self.host, ctypes.c_void_p)
-        self.table = ops._table(self.host) if labels else None
+        tab = self._records(np.dtype(_lib.GaussJob))
+        self.mean, self.sd = ops._h2d(mean, self._dev), ops._h2d(sd, self._dev)
+        ns = [int(lab.shape[0]) for lab in labels]
+        tab["x"] = self._own("pool", ns, torch.float32, unit=(ld,), of="_rows")
+        self.x = [rows[:, :F] for rows in self._rows]
+        self._point(tab, "labels", [lab if n else None for lab, n in zip(labels, ns)])
+        tab["mean"], tab["sd"] = self.mean.data_ptr(), self.sd.data_ptr()
+        tab["seed"] = np.fromiter((int(seed) & 0xFFFFFFFFFFFFFFFF for seed in seeds), np.uint64, n_jobs)
+        tab["ldx"], tab["n"], tab["F"], tab["n_classes"] = ld, ns, F, C
+        self._close(tab, host=True)
 
     def launch(self):
-        from . import ops
-        ops.check(ops.lib.wdg_gauss_features_batched_f32(self._cast, ops._ptr(self.table), self.n_jobs, ops.stream_handle()),
-                  "wdg_gauss_features_batched_f32")
+        self._launch("wdg_gauss_features_batched_f32", host=True)
         return self.x
 
 
