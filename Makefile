@@ -4,9 +4,9 @@ CSRC     := $(PKG)/csrc
 HIPCC    ?= /opt/rocm/bin/hipcc
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function -Wno-unused-value $(if $(STAMPS),-DWDG_STAMPS,) $(if $(DEPTH),-DWDG_PREFETCH_DEPTH=$(DEPTH),) $(EXTRA)
 SRCS     := $(wildcard $(CSRC)/*.hip)
-# link order: the units of the opt-in keep_best, learning-curve, AUC, sparse-first-layer, CSBM-H (synth_classes, qda), attention (gat, gat_scores) signed-attention (signed_att), polynomial-filter (poly_filter), two-hop pattern (two_hop), row top-k (topk_rows) and GCNII layer (gcnii) paths go LAST, so that every other kernel keeps the place in the library it had before
+# link order: the units of the opt-in keep_best, learning-curve, AUC, sparse-first-layer, CSBM-H (synth_classes, qda), attention (gat, gat_scores) signed-attention (signed_att), polynomial-filter (poly_filter), two-hop pattern (two_hop), row top-k (topk_rows), GCNII layer (gcnii) and DropEdge (drop_edge) paths go LAST, so that every other kernel keeps the place in the library it had before
 # they existed (the default paths are timed against the parent commit's build: DESIGN 4.20, 4.21)
-LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $(CSRC)/auc.hip $(CSRC)/sparse_dense.hip $(CSRC)/synth_classes.hip $(CSRC)/qda.hip $(CSRC)/gat.hip $(CSRC)/gat_scores.hip $(CSRC)/signed_att.hip $(CSRC)/poly_filter.hip $(CSRC)/two_hop.hip $(CSRC)/topk_rows.hip $(CSRC)/gcnii.hip
+LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $(CSRC)/auc.hip $(CSRC)/sparse_dense.hip $(CSRC)/synth_classes.hip $(CSRC)/qda.hip $(CSRC)/gat.hip $(CSRC)/gat_scores.hip $(CSRC)/signed_att.hip $(CSRC)/poly_filter.hip $(CSRC)/two_hop.hip $(CSRC)/topk_rows.hip $(CSRC)/gcnii.hip $(CSRC)/drop_edge.hip
 SRCS     := $(filter-out $(LAST),$(SRCS)) $(LAST)
 LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and
@@ -39,6 +39,8 @@ FLAGS_poly_filter := -ffp-contract=off
 FLAGS_topk_rows := -ffp-contract=off
 # gcnii.hip's layer and its backward pass are stated operation by operation in include/wdg.h and restated in numpy bit for bit: every fmaf is written out, nothing else is fused
 FLAGS_gcnii := -ffp-contract=off
+# drop_edge.hip's aggregation is ONE fmaf chain per element, stated in include/wdg.h and restated in numpy bit for bit: the fmaf is written out, nothing else is fused
+FLAGS_drop_edge := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB      := $(PKG)/lib/libwdg_hip.so
 

@@ -2160,6 +2160,113 @@ int wdg_gcnii_check_jobs(const wdg_gcnii_job *jobs_host, int32_t n_jobs);
 /* the floats of a job's workspace: ceil(n / WDG_GCNII_ROW_BLOCK) * w * w; 0 for a negative argument */
 int64_t wdg_gcnii_partial_len(int32_t n, int32_t w);
 
+/*
+ * DropEdge (Rong, Huang, Xu, Huang: "DropEdge: Towards Deep Graph Convolutional Networks on Node Classification", ICLR 2020): a fresh
+ * random subset of a pattern's stored entries per training step, renormalised, for a table of patterns in ONE launch.  The pass writes
+ * the thinned PATTERN, not a mask: the aggregations behind it (wdg_spmm_thinned_batched_f32) do not depend on the step and draw nothing.
+ * A graph appears in the table twice - its forward pattern and its transposed pattern (WDG_DROP_EDGE_TRANSPOSED) - and both keep the same
+ * edges, because an entry's fate is a function of its FORWARD coordinates, not of its position in an array: no position map is read.
+ * The reference ships no model code: the pass is DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: nothing of the reference - it restates the degree part of its normalisation on the KEPT entries: normalize,
+ *           utils/util_funcs.py:29-36 (WDG_NORM_RW), and normalize_tensor, utils/util_funcs.py:365-380 (the symmetric form) - for the
+ *           models that stand beside the tables of gnns_on_syn.py:9-53.
+ * A job: a CSR pattern of n rows and n_cols columns - rowptr int32 [n + 1], col int32 [nnz], rows in any order, duplicates allowed -
+ * and the outputs kept_col int32 [nnz], kept_len int32 [n], scale fp32 [n] or NULL.  The definition (tests/_drop_edge_ref.py restates it
+ * in numpy), Philox4x32-10 being the generator of wdg_relu_dropout_batched_f32 with counter {c0, c1, 0, 0} and key {k0, k1}:
+ *   step key     (k0, k1) = output words 0 and 1 of Philox4x32-10 with counter {*step_dev, jobs[j].stream, 0, 0} and key
+ *                {seed, 0x45444745} - once per launch and job
+ *   coordinates  of the stored column j of row i: the FORWARD coordinates are (i, j), or (j, i) with WDG_DROP_EDGE_TRANSPOSED; the pair
+ *                (a, b) is the forward coordinates, or (min, max) of them with WDG_DROP_EDGE_TIED: both directions of an undirected
+ *                edge then share one fate (DropEdge as the paper draws it for symmetric graphs; untied is for directed graphs)
+ *   kept         when 0 <= j < n_cols and either WDG_DROP_EDGE_KEEP_DIAGONAL is set and i == j (the self loop of A + I is never
+ *                dropped) or word 0 of Philox4x32-10 with counter {a, b, 0, 0} and key {k0, k1} is >= drop_threshold.
+ *                A column stored twice is kept or dropped together; a column outside [0, n_cols) is never kept.
+ *   per row i    the kept columns, in stored order, go to kept_col[rowptr[i] .. rowptr[i] + kept_len[i] - 1]; the rest of the row's extent
+ *                is filled with -1; kept_len[i] = their count c; where scale != NULL, scale[i] = the F32 path of wdg_degree_norm on c:
+ *                1.0f / (float)c (WDG_NORM_RW) or, with WDG_DROP_EDGE_NORM_SYM, 1.0f / sqrtf((float)c) (WDG_NORM_SYM); inf -> 0.
+ *                At drop_threshold 0 on a unit-valued pattern this is wdg_degree_norm's dinv_f32, bit for bit.
+ *                A row whose extent lies outside [0, nnz] is left untouched (kept_col, kept_len and scale).
+ * The host passes drop_threshold = (uint32_t) floor(p * 2^32), computed in fp64, for a drop probability 0 <= p < 1, as for
+ * wdg_relu_dropout_batched_f32; p = 0 keeps every entry with a column inside the pattern.  *step_dev is read from DEVICE memory by the
+ * kernel: a captured hipGraph that holds this launch and an increment of the word draws a fresh subset on every replay.
+ * Integer arithmetic plus one scale per row; no LDS, no atomics; a job has the same bytes alone and in any table.  A wave per row, 64
+ * entries per step: there is NO multi-wave path for a hub row (squirrel's longest row is 30 steps of one wave).
+ * max_rows: the table's largest n (rows beyond it are not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID): negative counts, more than 65535 jobs (a job per grid y), a NULL table with
+ * n_jobs > 0, a NULL step_dev.  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is launched.  The table lives in device memory: what is
+ * wrong inside a job - a negative n, n_cols or nnz, unknown flag bits, a reserved word that is not 0, a NULL rowptr or kept_len with
+ * n > 0, a NULL col or kept_col with nnz > 0, a kept_col that overlaps col (the pass does not run in place) - is refused by
+ * wdg_drop_edge_check_jobs on the HOST copy of the table (drop_edge.DropEdgeBatch calls it before it uploads), and the launch leaves such
+ * a job untouched.  A job with n == 0 is skipped.
+ */
+#define WDG_DROP_EDGE_TIED 1          /* (a, b) = (min, max) of the forward coordinates */
+#define WDG_DROP_EDGE_TRANSPOSED 2    /* the job's pattern is the transposed one: the forward coordinates of (i, j) are (j, i) */
+#define WDG_DROP_EDGE_KEEP_DIAGONAL 4 /* an entry with i == j is never dropped */
+#define WDG_DROP_EDGE_NORM_SYM 8      /* the norm mode: scale = c^-1/2 (WDG_NORM_SYM); not set: 1 / c (WDG_NORM_RW) */
+typedef struct wdg_drop_edge_job {
+    const int32_t *rowptr;  /* [n + 1] */
+    const int32_t *col;     /* [nnz] */
+    int32_t *kept_col;      /* out [nnz]: per row the kept columns in stored order, then -1 */
+    int32_t *kept_len;      /* out [n] */
+    float *scale;           /* out [n], or NULL */
+    int32_t n, n_cols, nnz;
+    uint32_t stream;        /* generator stream of this job: the forward and the transposed job of a graph carry the same */
+    int32_t flags;          /* WDG_DROP_EDGE_* */
+    int32_t reserved;       /* must be 0 */
+} wdg_drop_edge_job;
+int wdg_drop_edge_thin_batched(const wdg_drop_edge_job *jobs_dev, int32_t n_jobs, int32_t max_rows, uint32_t drop_threshold, uint32_t seed,
+                               const uint32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the thinning pass above (utils/util_funcs.py:29-36, 365-380), on the host's table */
+int wdg_drop_edge_check_jobs(const wdg_drop_edge_job *jobs_host, int32_t n_jobs);
+
+/*
+ * Y = diag(row_scale) A_k diag(col_scale) X over a THINNED pattern A_k as wdg_drop_edge_thin_batched leaves it, a table of products per
+ * launch.  The backward pass is the same entry on the transposed job's thinned pattern with the two scales swapped:
+ * (R A_k C)^T = C A_k^T R.
+ * replaces: nothing of the reference - the product with the normalised adjacency of normalize, utils/util_funcs.py:29-36, and
+ *           normalize_tensor, utils/util_funcs.py:365-380, kept factored and restricted to the entries a step keeps, under the models
+ *           that stand beside the tables of gnns_on_syn.py:9-53.
+ * A job: rowptr int32 [n_rows + 1] - the FULL pattern's, whose extents hold the thinned rows -, kept_col int32 [nnz], kept_len int32
+ * [n_rows], row_scale fp32 [n_rows] or NULL, col_scale fp32 [n_cols] or NULL, X [n_cols, n_feat] fp32 with leading dimension ldx,
+ * Y [n_rows, n_feat] fp32 with leading dimension ldy.  The definition (tests/_drop_edge_ref.py restates it in numpy, bit for bit):
+ *   Y[i, f] = row_scale[i] * acc (ONE multiply; a NULL row_scale: no multiply), with acc = +0 and then, for
+ *   q = rowptr[i] .. rowptr[i] + min(kept_len[i], rowptr[i + 1] - rowptr[i]) - 1 in that order:
+ *     j = kept_col[q]; an entry with j outside [0, n_cols) - which includes -1 - is SKIPPED (no fmaf), never read through;
+ *     acc = fmaf(col_scale ? col_scale[j] : 1.0f, X[j, f], acc)
+ *   - one correctly rounded fmaf per kept entry, ONE chain per output element in the stated order whatever the row's length: no row is
+ *   split over lanes or waves, no partial sums are added, there is no atomic (csrc/drop_edge.hip is compiled with contraction off and
+ *   writes the fmaf out).  A row with no kept entry stores row_scale[i] * +0.  A row whose extent lies outside [0, nnz] is left
+ *   untouched.  Every other element of Y[0 : n_rows][0 : n_feat] is written and nothing outside that block.  A job has the same bits
+ *   alone and in any table, and a column has the same bits whatever the width of the job it is in.
+ *   Leading dimensions >= n_feat of any value: 16-byte loads / stores where the pointer, the leading dimension and n_feat (a multiple of
+ *   4) allow - the wave's decision, one for X and one for Y -, element-wise ones elsewhere (same values, same fmaf).  X and Y must not
+ *   overlap.
+ * A wave per row and per panel of 256 columns (a panel per grid y): n_feat up to 256 * 65535.  max_rows, max_feat: the table's largest
+ * n_rows and n_feat (rows / columns beyond them are not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID): negative counts, more than 65535 jobs (a job per grid z), a NULL table with
+ * n_jobs > 0, max_feat above 256 * 65535.  n_jobs == 0, max_rows == 0 or max_feat == 0: WDG_OK, nothing is launched.  What is wrong inside
+ * a job - a negative n_rows, n_cols, n_feat or nnz, a reserved word that is not 0, a leading dimension below n_feat, a NULL rowptr,
+ * kept_len or Y, a NULL kept_col or X with nnz > 0 and n_cols > 0, X == Y - is refused by wdg_spmm_thinned_check_jobs on the HOST copy of
+ * the table (drop_edge.ThinnedSpmmBatch calls it before it uploads), and the launch leaves such a job untouched.  A job with
+ * n_rows == 0 or n_feat == 0 is skipped.
+ */
+typedef struct wdg_thinned_spmm_job {
+    const int32_t *rowptr;    /* [n_rows + 1]: the full pattern's */
+    const int32_t *kept_col;  /* [nnz]: wdg_drop_edge_job.kept_col */
+    const int32_t *kept_len;  /* [n_rows] */
+    const float *row_scale;   /* [n_rows] or NULL */
+    const float *col_scale;   /* [n_cols] or NULL */
+    const float *X;           /* [n_cols, n_feat], leading dimension ldx */
+    float *Y;                 /* [n_rows, n_feat], leading dimension ldy */
+    int64_t ldx, ldy;
+    int32_t n_rows, n_cols, n_feat, nnz;
+    int32_t reserved;         /* must be 0 */
+} wdg_thinned_spmm_job;
+int wdg_spmm_thinned_batched_f32(const wdg_thinned_spmm_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the thinned aggregation above (utils/util_funcs.py:29-36, 365-380), on the
+ *           host's table */
+int wdg_spmm_thinned_check_jobs(const wdg_thinned_spmm_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,10 @@ SIGNATURES = {
     "wdg_gcnii_weight_grad_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_gcnii_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_gcnii_partial_len": (c_int64, [c_int32, c_int32]),
+    "wdg_drop_edge_thin_batched": (c_int, [c_void_p, c_int32, c_int32, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "wdg_drop_edge_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_spmm_thinned_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_spmm_thinned_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -464,6 +468,18 @@ class GcniiJob(ctypes.Structure):
     _fields_ = [(name, c_void_p) for name in ("P", "H0", "W", "out", "S", "d_out", "d_P", "d_H0", "d_W", "partial")] + \
                [(name, c_int64) for name in ("ld_p", "ld_h0", "ld_w", "ld_out", "ld_s", "ld_d_out", "ld_d_p", "ld_d_h0", "ld_d_w")] + \
                [("n", c_int32), ("w", c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("stream", c_uint32), ("reserved", c_uint32)]
+
+
+class DropEdgeJob(ctypes.Structure):
+    """mirror of `wdg_drop_edge_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_col", "kept_len", "scale")] + \
+               [("n", c_int32), ("n_cols", c_int32), ("nnz", c_int32), ("stream", c_uint32), ("flags", c_int32), ("reserved", c_int32)]
+
+
+class ThinnedSpmmJob(ctypes.Structure):
+    """mirror of `wdg_thinned_spmm_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "kept_col", "kept_len", "row_scale", "col_scale", "X", "Y")] + \
+               [("ldx", c_int64), ("ldy", c_int64)] + [(name, c_int32) for name in ("n_rows", "n_cols", "n_feat", "nnz", "reserved")]
 
 
 if not os.path.exists(LIB_PATH):

@@ -43,6 +43,11 @@ GCNII (`GCNII`) is the DEEP model with a residual to the un-aggrega
 aggregation and passes the result through (1 - beta_l) I + beta_l W_l (Chen et al., "Simple and Deep Graph Convolutional Networks") - the
 residual, the identity mapping, the ReLU and the dropout behind an aggregation are ONE launch of csrc/gcnii.hip, forward and backward, and
 the weight gradients of all layers one more.  Defined by this project as well.
+
+DropEdge (`DropEdgeAdj`) regularises from the graph side: every training step aggregates over a fresh random subset of the
+stored entries, renormalised, and evaluation over the full graph (Rong et al., "DropEdge: Towards Deep Graph Convolutional Networks on
+Node Classification").  The subset is drawn on csrc/drop_edge.hip and written as a thinned pattern; the aggregation over it and its
+backward pass run on the same unit.  It serves the models that aggregate through NormAdj.matmul / aggregate / aggregate_t.
 """
 import math
 
@@ -68,6 +73,14 @@ class NormAdj:
     def matmul(self, x):
         return _Aggregate.apply(x, self)
 
+    def aggregate(self, x, out=None):
+        """A_hat x without autograd (into `out`, where one is given): what _Aggregate's forward pass and the GCNII stack launch"""
+        return ops.spmm(self.graph, x, row_scale=self.row_scale, col_scale=self.col_scale, out=out)
+
+    def aggregate_t(self, g):
+        """A_hat^T g without autograd: the backward pass of `aggregate` - (R A C)^T = C A^T R"""
+        return ops.spmm(self.graph_t, g, row_scale=self.col_scale, col_scale=self.row_scale)
+
     def attention_plan(self):
         """what the attention kernels need of the pattern, built on first use and kept: dict(graph, graph_t, t_pos) - t_pos ties
         every entry of the transposed CSR to its forward entry (CsrGraph.transpose_positions).  ValueError for a graph that is not
@@ -84,12 +97,11 @@ class _Aggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, adj):
         ctx.adj = adj
-        return ops.spmm(adj.graph, x, row_scale=adj.row_scale, col_scale=adj.col_scale)
+        return adj.aggregate(x)
 
     @staticmethod
     def backward(ctx, gy):
-        a = ctx.adj  # (R A C)^T = C A^T R
-        return ops.spmm(a.graph_t, gy.contiguous(), row_scale=a.col_scale, col_scale=a.row_scale), None
+        return ctx.adj.aggregate_t(gy.contiguous()), None
 
 
 class _Linear(torch.autograd.Function):
@@ -759,7 +771,7 @@ class _GcniiStack:
         torch.stack(list(weights), out=b["w"])
         word, h = self.word(h0.device), b["h0"]
         for l in range(len(self.betas)):
-            ops.spmm(adj.graph, h, row_scale=adj.row_scale, col_scale=adj.col_scale, out=b["p"])
+            adj.aggregate(h, out=b["p"])
             table.launch(word, first=l, count=1, p=p_dev)
             h = b["out"][l] if training else b["out"][l & 1]
             if p_torch > 0 and training:
@@ -798,7 +810,7 @@ class _GcniiLayers(torch.autograd.Function):
             else:
                 b["d_out"].copy_(d)
             table.launch_backward(first=l, count=1, p=ctx.p_dev)
-            d = _Aggregate.backward(ctx, b["d_p"])[0]  # (reads ctx.adj alone)
+            d = ctx.adj.aggregate_t(b["d_p"])
         table.launch_weight_grad()
         return (None, None, None, None, b["d_h0"] + d, *b["d_w"].clone().unbind(0))
 
@@ -938,6 +950,98 @@ class H2GCN2(_H2GCN):
         super().__init__(2, nfeat, nclass, nhid, dropout, dropout_rng)
 
 
+_DROP_EDGE_SERVED = ("a thinned view of a DropEdgeAdj has no stored pattern to read: it serves the models that aggregate through matmul / "
+                     "aggregate / aggregate_t - GCN2, ACMGCN2, GPRGNN1 / GPRGNN2 with fused=False, GCNII")
+
+
+class _ThinnedAdj:
+    """What DropEdgeAdj.resample() returns: A_hat_kept of the LATEST draw, as the models see an adjacency - .n, .matmul(x),
+    .aggregate(x, out=None), .aggregate_t(g), all three on wdg_spmm_thinned_batched_f32 (the backward pass is the transposed
+    pattern's job with the scales swapped).  It holds no pattern of its own: the owner's buffers hold one draw, the latest, so a
+    backward pass must precede the next resample() - one that does not raises.  Whatever reads a stored pattern gets a TypeError."""
+
+    def __init__(self, owner, draw):
+        self._owner, self._draw, self.n = owner, draw, owner.n
+
+    def matmul(self, x):
+        return _Aggregate.apply(x, self)
+
+    def aggregate(self, x, out=None):
+        return self._owner._product(False, self._draw, x, out)
+
+    def aggregate_t(self, g):
+        return self._owner._product(True, self._draw, g, None)
+
+    def attention_plan(self):
+        raise TypeError("attention_plan: " + _DROP_EDGE_SERVED)
+
+    def _no_pattern(self):
+        raise TypeError(_DROP_EDGE_SERVED)
+
+    graph = graph_t = row_scale = col_scale = property(_no_pattern)
+
+
+class DropEdgeAdj:
+    """DropEdge (Rong et al., ICLR 2020) over one graph: .full - the plain NormAdj(adj, symmetric, add_self_loops), what evaluation and
+    graphed_inference run on - and resample(), which draws a fresh random subset of the stored entries on the device
+    (ops.DropEdgeBatch, csrc/drop_edge.hip: drop probability p, generator (seed, stream), a step word of this object's own),
+    renormalises it - the scales of .full's normalisation on the KEPT counts - and returns the thinned view every layer of that
+    training step aggregates over (one mask per step).  A self loop that add_self_loops put there is never dropped.
+    tied: both directions of an edge share one fate; None: tied when the pattern equals its transpose.
+    .graph and .n are .full's (the training loops read adj.graph.device).  The tables and buffers are built on first use - before any
+    capture: train_eval_graphed's warm-up does that - and hold ONE draw, the latest."""
+
+    def __init__(self, adj, p, seed, stream=0, symmetric=0, add_self_loops=True, tied=None):
+        ops.dropout_constants(p)
+        if not 0 <= int(seed) < 1 << 32 or not 0 <= int(stream) < 1 << 32:
+            raise ValueError(f"DropEdgeAdj: a seed and a stream of 32 bits expected, got {seed!r} and {stream!r}")
+        self.p, self.seed, self.stream, self.symmetric, self.keep_diagonal = float(p), int(seed), int(stream), bool(symmetric), bool(add_self_loops)
+        self.full = NormAdj(adj, symmetric, add_self_loops)
+        g, gt = self.full.graph, self.full.graph_t
+        self.graph, self.n = g, self.full.n
+        if tied is None:
+            tied = g.n_rows == g.n_cols and torch.equal(g.rowptr, gt.rowptr) and torch.equal(g.col, gt.col)
+        elif tied and g.n_rows != g.n_cols:
+            raise ValueError(f"DropEdgeAdj: tied needs a square pattern, got {g.n_rows} x {g.n_cols}")
+        self.tied = bool(tied)
+        self.step = torch.zeros(1, dtype=torch.int32, device=g.device)
+        self.draws = 0  # resample() calls so far, on the host: a view whose draw is not the latest refuses its backward pass
+        self._batch, self._products = None, {}
+
+    def batch(self):
+        """the one-entry ops.DropEdgeBatch over .full's two patterns, built on first use (kept_graph(0), kept_counts() of the latest draw)"""
+        if self._batch is None:
+            self._batch = ops.DropEdgeBatch([dict(graph=self.full.graph, graph_t=self.full.graph_t, stream=self.stream, tied=self.tied,
+                                                  keep_diagonal=self.keep_diagonal, norm=ops.NORM_SYM if self.symmetric else ops.NORM_RW)],
+                                            self.p, self.seed)
+        return self._batch
+
+    def resample(self):
+        """thin both patterns at the current step word, advance the word on the device -> the thinned view of this draw"""
+        self.batch().launch(self.step)
+        self.step.add_(1)
+        self.draws += 1
+        return _ThinnedAdj(self, self.draws)
+
+    def _product(self, transposed, draw, x, out):
+        """A_hat_kept x, or A_hat_kept^T x: a one-job ops.ThinnedSpmmBatch and its two buffers per (direction, width), built on first use"""
+        if draw != self.draws:
+            raise RuntimeError("DropEdgeAdj: another resample() has run since the one this pass belongs to; the thinned pattern holds one "
+                               "draw, the latest - a backward pass must precede the next resample()")
+        key = (bool(transposed), int(x.shape[1]))
+        if key not in self._products:
+            b = self.batch()
+            pat, s = (b.thinned_t(0) if transposed else b.thinned(0)), b.thinned(0).scale  # (the scale of A_kept's ROW counts, both ways)
+            row, col = (s, s if self.symmetric else None) if not transposed else (s if self.symmetric else None, s)  # (R A C)^T = C A^T R
+            xb = torch.zeros((pat.n_cols, key[1]), dtype=torch.float32, device=s.device)
+            yb = torch.zeros((pat.n_rows, key[1]), dtype=torch.float32, device=s.device)
+            self._products[key] = (xb, yb, ops.ThinnedSpmmBatch([dict(pattern=pat, x=xb, y=yb, row_scale=row, col_scale=col)]))
+        xb, yb, table = self._products[key]
+        xb.copy_(x)
+        table.launch()
+        return yb.clone() if out is None else out.copy_(yb)
+
+
 def graphed_inference(model, adj, x, **forward_kwargs):
     """One-shot inference `model(adj, x)` (eval mode, no gradients) captured as ONE hipGraph -> (replay, logits).
 
@@ -948,6 +1052,7 @@ def graphed_inference(model, adj, x, **forward_kwargs):
     their addresses: same tensors, new values are fine); everything the forward builds lazily - SELL / band copies of the
     graph, narrow-kernel tables - is built by two eager runs before the capture."""
     model.eval()
+    adj = adj.full if isinstance(adj, DropEdgeAdj) else adj  # (inference runs on the full graph)
     with torch.no_grad():
         for _ in range(2):
             model(adj, x, **forward_kwargs)
@@ -972,16 +1077,18 @@ def train_eval(model, adj, x, labels, masks=None, epochs=200, lr=0.01, weight_de
     tr, va, te = (m.to(dev) for m in masks)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     best = dict(val_acc=-1.0, test_acc=0.0, epoch=0)
+    thins = isinstance(adj, DropEdgeAdj)  # (a fresh subset of the edges per training step; evaluation on the full graph)
+    full = adj.full if thins else adj
     for ep in range(epochs):
         model.train()
         opt.zero_grad()
-        out = torch.log_softmax(model(adj, x), 1)
+        out = torch.log_softmax(model(adj.resample() if thins else adj, x), 1)
         loss = torch.nn.functional.nll_loss(out[tr], labels[tr])
         loss.backward()
         opt.step()
         model.eval()
         with torch.no_grad():
-            out = model(adj, x)
+            out = model(full, x)
             v, t = float(accuracy(labels[va], out[va])), float(accuracy(labels[te], out[te]))
         if v > best["val_acc"]:
             best = dict(val_acc=v, test_acc=t, epoch=ep)
@@ -1010,11 +1117,13 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
     best_test = torch.zeros((), device=dev)
     best_epoch = torch.zeros((), dtype=torch.int64, device=dev)
     epoch = torch.zeros((), dtype=torch.int64, device=dev)
+    thins = isinstance(adj, DropEdgeAdj)  # (a fresh subset of the edges per training step - per replay; evaluation on the full graph)
+    full = adj.full if thins else adj
 
     def train_step():
         model.train()
         opt.zero_grad(set_to_none=False)
-        out = torch.log_softmax(model(adj, x), 1)
+        out = torch.log_softmax(model(adj.resample() if thins else adj, x), 1)
         loss = torch.nn.functional.nll_loss(out.index_select(0, tr), y_tr)
         loss.backward()
         opt.step()
@@ -1022,7 +1131,7 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
     def eval_step():
         model.eval()
         with torch.no_grad():
-            pred = model(adj, x).argmax(1)
+            pred = model(full, x).argmax(1)
             v = (pred.index_select(0, va) == y_va).float().mean()
             t = (pred.index_select(0, te) == y_te).float().mean()
             better = v > best_val
@@ -1035,8 +1144,8 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
         p.grad = torch.zeros_like(p)
     g_train = g_eval = None
     if capture:
-        # (DeviceDropout: the warm-up's masks are drawn again)
-        restore = snapshot(list(model.parameters()) + [r.step for r in _dropout_rngs(model)])
+        # (DeviceDropout, DropEdgeAdj: the warm-up's masks and subsets are drawn again)
+        restore = snapshot(list(model.parameters()) + [r.step for r in _dropout_rngs(model)] + ([adj.step] if thins else []))
 
         def warm_up():
             for _ in range(2):
