@@ -7,6 +7,8 @@ SRCS     := $(wildcard $(CSRC)/*.hip)
 # link order: the units of the opt-in keep_best, learning-curve, AUC, sparse-first-layer, CSBM-H (synth_classes, qda), attention (gat, gat_scores) signed-attention (signed_att), polynomial-filter (poly_filter), two-hop pattern (two_hop), row top-k (topk_rows), GCNII layer (gcnii) and DropEdge (drop_edge) paths go LAST, so that every other kernel keeps the place in the library it had before
 # they existed (the default paths are timed against the parent commit's build: DESIGN 4.20, 4.21)
 LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $(CSRC)/auc.hip $(CSRC)/sparse_dense.hip $(CSRC)/synth_classes.hip $(CSRC)/qda.hip $(CSRC)/gat.hip $(CSRC)/gat_scores.hip $(CSRC)/signed_att.hip $(CSRC)/poly_filter.hip $(CSRC)/two_hop.hip $(CSRC)/topk_rows.hip $(CSRC)/gcnii.hip $(CSRC)/drop_edge.hip
+# ... and behind them the neighbour sampler (neighbor_sample), on a line of its own: the list above ends where tests/test_abi_drop_edge.py reads it
+LAST     += $(CSRC)/neighbor_sample.hip
 SRCS     := $(filter-out $(LAST),$(SRCS)) $(LAST)
 LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and

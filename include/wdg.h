@@ -2267,6 +2267,79 @@ int wdg_spmm_thinned_batched_f32(const wdg_thinned_spmm_job *jobs_dev, int32_t n
  *           host's table */
 int wdg_spmm_thinned_check_jobs(const wdg_thinned_spmm_job *jobs_host, int32_t n_jobs);
 
+/*
+ * GraphSAGE's neighbour sampling (Hamilton, Ying, Leskovec: "Inductive Representation Learning on Large Graphs", NeurIPS 2017): per
+ * training step EXACTLY `fanout` of every row's eligible entries, uniformly and without replacement, for a table of patterns.  Like
+ * wdg_drop_edge_thin_batched the pass writes a thinned PATTERN (kept_col, kept_len, scale) that wdg_spmm_thinned_batched_f32 aggregates
+ * over, and a graph appears in the table twice - its forward pattern and its transposed pattern (WDG_NEIGHBOR_SAMPLE_TRANSPOSED) -, both
+ * keeping the same edges.  "s of this row's entries" is an order statistic of the row, not a function of the entry: what makes it
+ * recomputable from the transposed side without a position map is ONE 64-bit word per forward row, the threshold tau.
+ * The reference ships no model code: the pass is DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: nothing of the reference - its loaders only carry the switch (sage_data, utils/util_funcs.py:207, 342); the pass restates the
+ *           degree part of its normalisation on the KEPT entries: normalize, utils/util_funcs.py:29-36 (WDG_NORM_RW), and
+ *           normalize_tensor, utils/util_funcs.py:365-380 (the symmetric form) - for the models that stand beside the tables of
+ *           gnns_on_syn.py:9-53.
+ * A job: a CSR pattern of n rows and n_cols columns - rowptr int32 [n + 1], col int32 [nnz], rows in any order, duplicates allowed -, the
+ * outputs kept_col int32 [nnz], kept_len int32 [n], scale fp32 [n] or NULL, and tau uint64: on a forward job an OUTPUT [n], on a
+ * transposed job the forward job's tau, an INPUT [n_cols].  The definition (tests/_neighbor_sample_ref.py restates it in numpy),
+ * Philox4x32-10 being the generator of wdg_drop_edge_thin_batched with counter {c0, c1, 0, 0} and key {k0, k1}:
+ *   step key     (k0, k1) = output words 0 and 1 of Philox4x32-10 with counter {*step_dev, jobs[j].stream, 0, 0} and key
+ *                {seed, 0x53414745} ("SAGE": equal seeds give draws unrelated to DropEdge's) - once per launch and job
+ *   key          of the stored column j of row i, with FORWARD coordinates (fi, fj) = (i, j), or (j, i) with
+ *                WDG_NEIGHBOR_SAMPLE_TRANSPOSED: key = ((uint64_t) word 0 of Philox4x32-10 with counter {fi, fj, 0, 0} and key
+ *                {k0, k1}) << 32 | (uint32_t) fj.  A total order within a forward row; a column stored twice shares one key.
+ *   eligible     (forward job) the stored entries of row i with 0 <= j < n_cols, minus the protected diagonal: an entry with i == j
+ *                under WDG_NEIGHBOR_SAMPLE_KEEP_DIAGONAL
+ *   tau[i]       (forward job) the fanout-th smallest key over the eligible entries of row i, counted with multiplicity;
+ *                2^64 - 1 when there are fewer than fanout
+ *   kept         when 0 <= j < n_cols and either the entry is a protected diagonal entry or key <= tau[fi] - tau[i] on a forward
+ *                job, tau[j] on a transposed one (read only for a valid j).  A duplicate-free row with e eligible entries keeps
+ *                exactly min(fanout, e) of them, a uniformly random subset; copies of the threshold column are kept with it; a tie
+ *                between different columns (probability 2^-32 per pair) goes to the lower column.  A protected diagonal entry is kept
+ *                and is not counted against the fan-out.
+ *   per row i    as wdg_drop_edge_thin_batched: the kept columns, in stored order, go to kept_col[rowptr[i] .. rowptr[i] + kept_len[i] - 1];
+ *                the rest of the row's extent is filled with -1; kept_len[i] = their count c; where scale != NULL, scale[i] =
+ *                1.0f / (float)c or, with WDG_NEIGHBOR_SAMPLE_NORM_SYM, 1.0f / sqrtf((float)c); inf -> 0.
+ *                A row whose extent lies outside [0, nnz] is left untouched (kept_col, kept_len, scale and tau).
+ * There is no tied form - a fan-out is a property of the receiving row -: the flag bit of value 1 (WDG_DROP_EDGE_TIED's) is refused.
+ * phase 0 works the jobs WITHOUT WDG_NEIGHBOR_SAMPLE_TRANSPOSED: it selects, writes tau and thins in the same pass over the row.
+ * phase 1 works the jobs WITH it: it thins by tau alone, and must follow phase 0 of the same step in stream order; a forward-only user
+ * skips it.  Each phase leaves the other's jobs untouched.  *step_dev is read from DEVICE memory by the kernel: a captured hipGraph that
+ * holds both launches and an increment of the word draws a fresh sample on every replay.
+ * The result is a pure function of (pattern, fanout, flags, seed, stream, step): a job has the same bytes alone and in any table,
+ * whatever algorithm computes it.  Integer arithmetic plus one scale per row; no LDS, no atomics.  A wave per row, 64 entries per step:
+ * there is NO multi-wave path for a hub row.  Phase 0 bounds every forward row at fanout kept entries (plus a protected diagonal and
+ * copies of the threshold column); the rows of the transposed pattern are NOT bounded.
+ * max_rows: the table's largest n (rows beyond it are not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID): negative counts, more than 65535 jobs (a job per grid y), a NULL table with
+ * n_jobs > 0, a phase other than 0 and 1, a NULL step_dev.  n_jobs == 0 or max_rows == 0: WDG_OK, nothing is launched.  The table lives
+ * in device memory: what is wrong inside a job - a negative n, n_cols or nnz, the flag bit of value 1, unknown flag bits, a fanout
+ * outside 1 .. 64 on a forward job (a transposed job's is not read), a NULL rowptr or kept_len with n > 0, a NULL tau (a transposed job
+ * without entries needs none), a NULL col or kept_col with nnz > 0, a kept_col that overlaps col (the pass does not run in place) - is
+ * refused by wdg_neighbor_sample_check_jobs on the HOST copy of the table (neighbor_sample.NeighborSampleBatch calls it before it
+ * uploads), and the launch leaves such a job untouched.  A job with n == 0 is skipped.
+ */
+#define WDG_NEIGHBOR_SAMPLE_TRANSPOSED 2    /* the job's pattern is the transposed one: the forward coordinates of (i, j) are (j, i) */
+#define WDG_NEIGHBOR_SAMPLE_KEEP_DIAGONAL 4 /* an entry with i == j is always kept and does not count against the fan-out */
+#define WDG_NEIGHBOR_SAMPLE_NORM_SYM 8      /* the norm mode: scale = c^-1/2 (WDG_NORM_SYM); not set: 1 / c (WDG_NORM_RW) */
+#define WDG_NEIGHBOR_SAMPLE_MAX_FANOUT 64
+typedef struct wdg_neighbor_sample_job {
+    const int32_t *rowptr;  /* [n + 1] */
+    const int32_t *col;     /* [nnz] */
+    int32_t *kept_col;      /* out [nnz]: per row the kept columns in stored order, then -1 */
+    int32_t *kept_len;      /* out [n] */
+    float *scale;           /* out [n], or NULL */
+    uint64_t *tau;          /* forward job: out [n]; transposed job: in [n_cols], the forward job's */
+    int32_t n, n_cols, nnz;
+    uint32_t stream;        /* generator stream of this job: the forward and the transposed job of a graph carry the same */
+    int32_t flags;          /* WDG_NEIGHBOR_SAMPLE_* */
+    int32_t fanout;         /* 1 .. 64 on a forward job; not read on a transposed one */
+} wdg_neighbor_sample_job;
+int wdg_neighbor_sample_batched(const wdg_neighbor_sample_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t phase, uint32_t seed,
+                                const uint32_t *step_dev, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the sampling pass above (utils/util_funcs.py:29-36, 365-380), on the host's table */
+int wdg_neighbor_sample_check_jobs(const wdg_neighbor_sample_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

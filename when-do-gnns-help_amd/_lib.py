@@ -219,6 +219,8 @@ SIGNATURES = {
     "wdg_drop_edge_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_spmm_thinned_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_spmm_thinned_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_neighbor_sample_batched": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
+    "wdg_neighbor_sample_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -480,6 +482,12 @@ class ThinnedSpmmJob(ctypes.Structure):
     """mirror of `wdg_thinned_spmm_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("rowptr", "kept_col", "kept_len", "row_scale", "col_scale", "X", "Y")] + \
                [("ldx", c_int64), ("ldy", c_int64)] + [(name, c_int32) for name in ("n_rows", "n_cols", "n_feat", "nnz", "reserved")]
+
+
+class NeighborSampleJob(ctypes.Structure):
+    """mirror of `wdg_neighbor_sample_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_col", "kept_len", "scale", "tau")] + \
+               [("n", c_int32), ("n_cols", c_int32), ("nnz", c_int32), ("stream", c_uint32), ("flags", c_int32), ("fanout", c_int32)]
 
 
 if not os.path.exists(LIB_PATH):

@@ -5,7 +5,8 @@
   ThinnedPattern     what a launch leaves for one pattern: the full pattern's rowptr and the table's kept_col / kept_len / scale blocks
   ThinnedSpmmBatch   Y = diag(row_scale) A_k diag(col_scale) X over such patterns, a table of products in one launch; the backward pass is
                      the transposed pattern's job with the two scales swapped
-Both tables are job_table.JobTables; models.DropEdgeAdj puts them under the training loops."""
+  ThinningTable      what DropEdgeBatch shares with neighbor_sample.NeighborSampleBatch, which writes the same thinned patterns
+All are job_table.JobTables; models.DropEdgeAdj puts them under the training loops."""
 import numpy as np
 
 from . import _lib
@@ -28,47 +29,41 @@ class ThinnedPattern:
         self.n_rows, self.n_cols, self.nnz = int(n_rows), int(n_cols), int(kept_col.shape[0])
 
 
-class DropEdgeBatch(JobTable):
-    """Job table for wdg_drop_edge_thin_batched: TWO jobs per entry - the graph's forward pattern and its transposed pattern, which keep
-    the same edges because an entry's fate is a function of its forward coordinates - thinned in ONE launch.  The table owns the
-    kept_col, kept_len and scale blocks of both patterns; nothing is drawn on the host and no mask is stored."""
+class ThinningTable(JobTable):
+    """What the tables that write thinned patterns share (DropEdgeBatch, neighbor_sample.NeighborSampleBatch): TWO jobs per entry - the
+    graph's forward pattern and its transposed pattern -, the checks of an entry's graph, graph_t, stream and norm, the record fields both
+    job structs have (rowptr, col, kept_col, kept_len, scale, n, n_cols, nnz, stream), the kept_col / kept_len / scale blocks the table owns
+    and the views of what a launch left."""
 
     MAX_JOBS = 65535
     _JOBS = "jobs (two per entry)"
-    _KEYS = ("graph", "graph_t", "stream", "tied", "keep_diagonal", "norm")
 
-    def __init__(self, entries, p, seed):
-        """entries: dicts of graph (a CsrGraph; its values are not read), graph_t (its transpose, or None: built here), stream (the
-        entry's generator stream, 0 .. 2^32 - 1; default 0), tied (both directions of an edge share one fate: a square pattern;
-        default False), keep_diagonal (an entry (i, i) is never dropped; default False), norm (ops.NORM_RW - scale = 1 / count -,
-        ops.NORM_SYM - count^-1/2 -, or None: no scale; default NORM_RW).  p: drop probability in [0, 1).  seed: 0 .. 2^32 - 1."""
-        who = "DropEdgeBatch"
-        self.p, self.seed = float(p), int(seed)
-        self.threshold = dropout_constants(p)[0]
-        if not 0 <= self.seed < 1 << 32:
-            raise ValueError(f"{who}: a seed of 32 bits expected, got {seed!r}")
-        self._open(entries, n=2 * len(entries))
-        flags = []
-        for i, e in enumerate(entries):
-            if not isinstance(e, dict) or "graph" not in e or set(e) - set(self._KEYS):
-                raise ValueError(f"{who}: entry {i}: a dict with `graph` and any of {self._KEYS[1:]} expected"
-                                 + (f", unknown keys {sorted(set(e) - set(self._KEYS))}" if isinstance(e, dict) else ""))
-            g, gt = e["graph"], e.get("graph_t")
-            if not isinstance(g, CsrGraph) or not (gt is None or isinstance(gt, CsrGraph)):
-                raise TypeError(f"{who}: entry {i}: graph (and graph_t, where given) must be a CsrGraph")
-            if gt is not None and (gt.n_rows, gt.n_cols, gt.nnz) != (g.n_cols, g.n_rows, g.nnz):
-                raise ValueError(f"{who}: entry {i}: graph_t is {gt.n_rows} x {gt.n_cols} with {gt.nnz} entries: not the transpose of a "
-                                 f"{g.n_rows} x {g.n_cols} pattern with {g.nnz}")
-            if e.get("tied") and g.n_rows != g.n_cols:
-                raise ValueError(f"{who}: entry {i}: tied needs a square pattern, got {g.n_rows} x {g.n_cols}")
-            if not 0 <= int(e.get("stream", 0)) < 1 << 32:
-                raise ValueError(f"{who}: entry {i}: a stream of 32 bits expected, got {e.get('stream')!r}")
-            norm = e.get("norm", NORM_RW)
-            if norm not in (None, NORM_RW, NORM_SYM):
-                raise ValueError(f"{who}: entry {i}: norm must be ops.NORM_RW, ops.NORM_SYM or None, got {norm!r}")
-            flags.append((DROP_EDGE_TIED if e.get("tied") else 0) | (DROP_EDGE_KEEP_DIAGONAL if e.get("keep_diagonal") else 0)
-                         | (DROP_EDGE_NORM_SYM if norm == NORM_SYM else 0))
-        tab = self._records(_DROP_EDGE_JOB_DTYPE)
+    def _check_graphs(self, i, e):
+        """the checks of entry i's keys, graph and graph_t (none needs a device)"""
+        who = type(self).__name__
+        if not isinstance(e, dict) or "graph" not in e or set(e) - set(self._KEYS):
+            raise ValueError(f"{who}: entry {i}: a dict with `graph` and any of {self._KEYS[1:]} expected"
+                             + (f", unknown keys {sorted(set(e) - set(self._KEYS))}" if isinstance(e, dict) else ""))
+        g, gt = e["graph"], e.get("graph_t")
+        if not isinstance(g, CsrGraph) or not (gt is None or isinstance(gt, CsrGraph)):
+            raise TypeError(f"{who}: entry {i}: graph (and graph_t, where given) must be a CsrGraph")
+        if gt is not None and (gt.n_rows, gt.n_cols, gt.nnz) != (g.n_cols, g.n_rows, g.nnz):
+            raise ValueError(f"{who}: entry {i}: graph_t is {gt.n_rows} x {gt.n_cols} with {gt.nnz} entries: not the transpose of a "
+                             f"{g.n_rows} x {g.n_cols} pattern with {g.nnz}")
+
+    def _check_stream_and_norm(self, i, e):
+        """the checks of entry i's stream and norm -> its norm"""
+        who = type(self).__name__
+        if not 0 <= int(e.get("stream", 0)) < 1 << 32:
+            raise ValueError(f"{who}: entry {i}: a stream of 32 bits expected, got {e.get('stream')!r}")
+        norm = e.get("norm", NORM_RW)
+        if norm not in (None, NORM_RW, NORM_SYM):
+            raise ValueError(f"{who}: entry {i}: norm must be ops.NORM_RW, ops.NORM_SYM or None, got {norm!r}")
+        return norm
+
+    def _thinning_records(self, dtype, entries):
+        """the device and the records with the fields both job structs have; the owned blocks; max_rows"""
+        tab = self._records(dtype)
         self._patterns = []  # forward, transposed, forward, ... : job 2 i and 2 i + 1 of entry i
         for e in entries:
             self._patterns += [e["graph"], e["graph_t"] if e.get("graph_t") is not None else e["graph"].transpose()]
@@ -85,15 +80,9 @@ class DropEdgeBatch(JobTable):
         tab["scale"] = np.where(scaled, self._own("scale", rows, torch.float32, reset=False), 0)
         tab["n"], tab["n_cols"], tab["nnz"] = rows, [g.n_cols for g in pats], nnz
         tab["stream"] = [int(e.get("stream", 0)) for e in entries for _ in (0, 1)]
-        tab["flags"] = [f | t for f in flags for t in (0, DROP_EDGE_TRANSPOSED)]
         self._scaled = scaled
         self.max_rows = int(tab["n"].max(initial=0))
-        self._close(tab, "wdg_drop_edge_check_jobs")
-
-    def launch(self, step):
-        """step: a one-element int32 DEVICE tensor whose bits are the uint32 step - the kernel reads it when it runs, so a captured
-        launch followed by a captured `step.add_(1)` draws a fresh subset on every replay"""
-        self._launch("wdg_drop_edge_thin_batched", self.max_rows, self.threshold, self.seed, _step_word("DropEdgeBatch.launch", step))
+        return tab
 
     def _view(self, job):
         g = self._patterns[job]
@@ -123,6 +112,43 @@ class DropEdgeBatch(JobTable):
         if not self.keep:
             return torch.zeros(0, dtype=torch.int64, device=self._dev)
         return torch.stack([self.kept_len_of[2 * i].sum() for i in range(len(self.keep))])
+
+
+class DropEdgeBatch(ThinningTable):
+    """Job table for wdg_drop_edge_thin_batched: TWO jobs per entry - the graph's forward pattern and its transposed pattern, which keep
+    the same edges because an entry's fate is a function of its forward coordinates - thinned in ONE launch.  The table owns the
+    kept_col, kept_len and scale blocks of both patterns; nothing is drawn on the host and no mask is stored."""
+
+    _KEYS = ("graph", "graph_t", "stream", "tied", "keep_diagonal", "norm")
+
+    def __init__(self, entries, p, seed):
+        """entries: dicts of graph (a CsrGraph; its values are not read), graph_t (its transpose, or None: built here), stream (the
+        entry's generator stream, 0 .. 2^32 - 1; default 0), tied (both directions of an edge share one fate: a square pattern;
+        default False), keep_diagonal (an entry (i, i) is never dropped; default False), norm (ops.NORM_RW - scale = 1 / count -,
+        ops.NORM_SYM - count^-1/2 -, or None: no scale; default NORM_RW).  p: drop probability in [0, 1).  seed: 0 .. 2^32 - 1."""
+        who = "DropEdgeBatch"
+        self.p, self.seed = float(p), int(seed)
+        self.threshold = dropout_constants(p)[0]
+        if not 0 <= self.seed < 1 << 32:
+            raise ValueError(f"{who}: a seed of 32 bits expected, got {seed!r}")
+        self._open(entries, n=2 * len(entries))
+        flags = []
+        for i, e in enumerate(entries):
+            self._check_graphs(i, e)
+            g = e["graph"]
+            if e.get("tied") and g.n_rows != g.n_cols:
+                raise ValueError(f"{who}: entry {i}: tied needs a square pattern, got {g.n_rows} x {g.n_cols}")
+            norm = self._check_stream_and_norm(i, e)
+            flags.append((DROP_EDGE_TIED if e.get("tied") else 0) | (DROP_EDGE_KEEP_DIAGONAL if e.get("keep_diagonal") else 0)
+                         | (DROP_EDGE_NORM_SYM if norm == NORM_SYM else 0))
+        tab = self._thinning_records(_DROP_EDGE_JOB_DTYPE, entries)
+        tab["flags"] = [f | t for f in flags for t in (0, DROP_EDGE_TRANSPOSED)]
+        self._close(tab, "wdg_drop_edge_check_jobs")
+
+    def launch(self, step):
+        """step: a one-element int32 DEVICE tensor whose bits are the uint32 step - the kernel reads it when it runs, so a captured
+        launch followed by a captured `step.add_(1)` draws a fresh subset on every replay"""
+        self._launch("wdg_drop_edge_thin_batched", self.max_rows, self.threshold, self.seed, _step_word("DropEdgeBatch.launch", step))
 
 
 class ThinnedSpmmBatch(JobTable):

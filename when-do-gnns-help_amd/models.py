@@ -48,6 +48,12 @@ DropEdge (`DropEdgeAdj`) regularises from the graph side: every tra
 stored entries, renormalised, and evaluation over the full graph (Rong et al., "DropEdge: Towards Deep Graph Convolutional Networks on
 Node Classification").  The subset is drawn on csrc/drop_edge.hip and written as a thinned pattern; the aggregation over it and its
 backward pass run on the same unit.  It serves the models that aggregate through NormAdj.matmul / aggregate / aggregate_t.
+
+GraphSAGE (`SAGE1`, `SAGE2`, `NeighborSampleAdj`) is the mean aggregator over a fixed-size random sample of every node's
+neighbours, with the node's own representation kept APART from the aggregate (Hamilton, Ying, Leskovec, "Inductive Representation
+Learning on Large Graphs") - the ego / neighbour separation H2GCN's paper credits for its standing under heterophily.  The sample -
+exactly `fanout` of a row's entries per training step - is drawn on csrc/neighbor_sample.hip and written as the thinned pattern of
+DropEdge's aggregation; evaluation runs on the full neighbourhood.  Defined by this project as well.
 """
 import math
 
@@ -950,12 +956,47 @@ class H2GCN2(_H2GCN):
         super().__init__(2, nfeat, nclass, nhid, dropout, dropout_rng)
 
 
+class SAGE1(torch.nn.Module):
+    """GraphSAGE-1 (mean aggregator), bias-free: P = X w with w [nfeat, 2 C], logits = P[:, :C] + A_s P[:, C:] - the node's own
+    transform and the transform of its neighbourhood mean are separate columns of ONE product, and the aggregation runs at class width
+    (A_s (X W_n) = (A_s X) W_n).  A_s = adj.matmul: a NeighborSampleAdj's view (the sampled mean), a plain NormAdj (the full-neighbourhood
+    mean) or a DropEdgeAdj's view; give the adjacency add_self_loops=False, the model holds the self path.  A node with no kept
+    neighbour aggregates +0.  w is ONE xavier_uniform draw of [nfeat, 2 C]."""
+
+    def __init__(self, nfeat, nclass):
+        super().__init__()
+        self.w = _xavier(nfeat, 2 * nclass)
+        self.nclass = nclass
+
+    def forward(self, adj, x):
+        p = _Linear.apply(x, self.w, False)
+        return p[:, :self.nclass] + adj.matmul(p[:, self.nclass:].contiguous())
+
+
+class SAGE2(_HiddenDropout, torch.nn.Module):
+    """GraphSAGE-2: P0 = X w0 (w0 [nfeat, 2 nhid]), H = dropout(relu(P0[:, :nhid] + A_s P0[:, nhid:])), P1 = H w1 (w1 [nhid, 2 C]),
+    logits = P1[:, :C] + A_s P1[:, C:]; otherwise SAGE1.  Parameters are drawn in this order: w0, then w1 (xavier_uniform each).
+    dropout_rng: as for GCN2."""
+
+    def __init__(self, nfeat, nclass, nhid=64, dropout=0.5, dropout_rng=None):
+        super().__init__()
+        self.w0, self.w1 = _xavier(nfeat, 2 * nhid), _xavier(nhid, 2 * nclass)
+        self.nhid, self.nclass = nhid, nclass
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+
+    def forward(self, adj, x):
+        p0 = _Linear.apply(x, self.w0, False)
+        h = self._relu_dropout(p0[:, :self.nhid] + adj.matmul(p0[:, self.nhid:].contiguous()))
+        p1 = _Linear.apply(h, self.w1, False)
+        return p1[:, :self.nclass] + adj.matmul(p1[:, self.nclass:].contiguous())
+
+
 _DROP_EDGE_SERVED = ("a thinned view of a DropEdgeAdj has no stored pattern to read: it serves the models that aggregate through matmul / "
-                     "aggregate / aggregate_t - GCN2, ACMGCN2, GPRGNN1 / GPRGNN2 with fused=False, GCNII")
+                     "aggregate / aggregate_t - GCN2, ACMGCN2, GPRGNN1 / GPRGNN2 with fused=False, GCNII, SAGE1 / SAGE2")
 
 
 class _ThinnedAdj:
-    """What DropEdgeAdj.resample() returns: A_hat_kept of the LATEST draw, as the models see an adjacency - .n, .matmul(x),
+    """What DropEdgeAdj.resample() / NeighborSampleAdj.resample() return: A_hat_kept of the LATEST draw, as the models see an adjacency - .n, .matmul(x),
     .aggregate(x, out=None), .aggregate_t(g), all three on wdg_spmm_thinned_batched_f32 (the backward pass is the transposed
     pattern's job with the scales swapped).  It holds no pattern of its own: the owner's buffers hold one draw, the latest, so a
     backward pass must precede the next resample() - one that does not raises.  Whatever reads a stored pattern gets a TypeError."""
@@ -981,40 +1022,22 @@ class _ThinnedAdj:
     graph = graph_t = row_scale = col_scale = property(_no_pattern)
 
 
-class DropEdgeAdj:
-    """DropEdge (Rong et al., ICLR 2020) over one graph: .full - the plain NormAdj(adj, symmetric, add_self_loops), what evaluation and
-    graphed_inference run on - and resample(), which draws a fresh random subset of the stored entries on the device
-    (ops.DropEdgeBatch, csrc/drop_edge.hip: drop probability p, generator (seed, stream), a step word of this object's own),
-    renormalises it - the scales of .full's normalisation on the KEPT counts - and returns the thinned view every layer of that
-    training step aggregates over (one mask per step; DESIGN 4.32).  A self loop that add_self_loops put there is never dropped.
-    tied: both directions of an edge share one fate; None: tied when the pattern equals its transpose.
-    .graph and .n are .full's (the training loops read adj.graph.device).  The tables and buffers are built on first use - before any
-    capture: train_eval_graphed's warm-up does that - and hold ONE draw, the latest."""
+class _ResampledAdj:
+    """What DropEdgeAdj and NeighborSampleAdj share: .full - the plain NormAdj, what evaluation and graphed_inference run on -, a step
+    word of the object's own on the device, resample() - one launch of the subclass's batch() at the current step word, the word
+    advanced on the device -> the thinned view every layer of that training step aggregates over -, and the one-job aggregation tables
+    over the batch's thinned patterns.  The tables and buffers are built on first use - before any capture: train_eval_graphed's
+    warm-up does that - and hold ONE draw, the latest.  A subclass states batch()."""
 
-    def __init__(self, adj, p, seed, stream=0, symmetric=0, add_self_loops=True, tied=None):
-        ops.dropout_constants(p)
+    def _setup(self, adj, seed, stream, symmetric, add_self_loops):
         if not 0 <= int(seed) < 1 << 32 or not 0 <= int(stream) < 1 << 32:
-            raise ValueError(f"DropEdgeAdj: a seed and a stream of 32 bits expected, got {seed!r} and {stream!r}")
-        self.p, self.seed, self.stream, self.symmetric, self.keep_diagonal = float(p), int(seed), int(stream), bool(symmetric), bool(add_self_loops)
+            raise ValueError(f"{type(self).__name__}: a seed and a stream of 32 bits expected, got {seed!r} and {stream!r}")
+        self.seed, self.stream, self.symmetric, self.keep_diagonal = int(seed), int(stream), bool(symmetric), bool(add_self_loops)
         self.full = NormAdj(adj, symmetric, add_self_loops)
-        g, gt = self.full.graph, self.full.graph_t
-        self.graph, self.n = g, self.full.n
-        if tied is None:
-            tied = g.n_rows == g.n_cols and torch.equal(g.rowptr, gt.rowptr) and torch.equal(g.col, gt.col)
-        elif tied and g.n_rows != g.n_cols:
-            raise ValueError(f"DropEdgeAdj: tied needs a square pattern, got {g.n_rows} x {g.n_cols}")
-        self.tied = bool(tied)
-        self.step = torch.zeros(1, dtype=torch.int32, device=g.device)
+        self.graph, self.n = self.full.graph, self.full.n
+        self.step = torch.zeros(1, dtype=torch.int32, device=self.graph.device)
         self.draws = 0  # resample() calls so far, on the host: a view whose draw is not the latest refuses its backward pass
         self._batch, self._products = None, {}
-
-    def batch(self):
-        """the one-entry ops.DropEdgeBatch over .full's two patterns, built on first use (kept_graph(0), kept_counts() of the latest draw)"""
-        if self._batch is None:
-            self._batch = ops.DropEdgeBatch([dict(graph=self.full.graph, graph_t=self.full.graph_t, stream=self.stream, tied=self.tied,
-                                                  keep_diagonal=self.keep_diagonal, norm=ops.NORM_SYM if self.symmetric else ops.NORM_RW)],
-                                            self.p, self.seed)
-        return self._batch
 
     def resample(self):
         """thin both patterns at the current step word, advance the word on the device -> the thinned view of this draw"""
@@ -1026,7 +1049,7 @@ class DropEdgeAdj:
     def _product(self, transposed, draw, x, out):
         """A_hat_kept x, or A_hat_kept^T x: a one-job ops.ThinnedSpmmBatch and its two buffers per (direction, width), built on first use"""
         if draw != self.draws:
-            raise RuntimeError("DropEdgeAdj: another resample() has run since the one this pass belongs to; the thinned pattern holds one "
+            raise RuntimeError(f"{type(self).__name__}: another resample() has run since the one this pass belongs to; the thinned pattern holds one "
                                "draw, the latest - a backward pass must precede the next resample()")
         key = (bool(transposed), int(x.shape[1]))
         if key not in self._products:
@@ -1042,6 +1065,59 @@ class DropEdgeAdj:
         return yb.clone() if out is None else out.copy_(yb)
 
 
+class DropEdgeAdj(_ResampledAdj):
+    """DropEdge (Rong et al., ICLR 2020) over one graph: .full - the plain NormAdj(adj, symmetric, add_self_loops), what evaluation and
+    graphed_inference run on - and resample(), which draws a fresh random subset of the stored entries on the device
+    (ops.DropEdgeBatch, csrc/drop_edge.hip: drop probability p, generator (seed, stream), a step word of this object's own),
+    renormalises it - the scales of .full's normalisation on the KEPT counts - and returns the thinned view every layer of that
+    training step aggregates over (one mask per step; DESIGN 4.32).  A self loop that add_self_loops put there is never dropped.
+    tied: both directions of an edge share one fate; None: tied when the pattern equals its transpose.
+    .graph and .n are .full's (the training loops read adj.graph.device).  The tables and buffers are built on first use - before any
+    capture: train_eval_graphed's warm-up does that - and hold ONE draw, the latest."""
+
+    def __init__(self, adj, p, seed, stream=0, symmetric=0, add_self_loops=True, tied=None):
+        ops.dropout_constants(p)
+        self._setup(adj, seed, stream, symmetric, add_self_loops)
+        self.p = float(p)
+        g, gt = self.full.graph, self.full.graph_t
+        if tied is None:
+            tied = g.n_rows == g.n_cols and torch.equal(g.rowptr, gt.rowptr) and torch.equal(g.col, gt.col)
+        elif tied and g.n_rows != g.n_cols:
+            raise ValueError(f"DropEdgeAdj: tied needs a square pattern, got {g.n_rows} x {g.n_cols}")
+        self.tied = bool(tied)
+
+    def batch(self):
+        """the one-entry ops.DropEdgeBatch over .full's two patterns, built on first use (kept_graph(0), kept_counts() of the latest draw)"""
+        if self._batch is None:
+            self._batch = ops.DropEdgeBatch([dict(graph=self.full.graph, graph_t=self.full.graph_t, stream=self.stream, tied=self.tied,
+                                                  keep_diagonal=self.keep_diagonal, norm=ops.NORM_SYM if self.symmetric else ops.NORM_RW)],
+                                            self.p, self.seed)
+        return self._batch
+
+
+class NeighborSampleAdj(_ResampledAdj):
+    """GraphSAGE's neighbour sampling (Hamilton et al., NeurIPS 2017) over one graph, with DropEdgeAdj's interface: .full - the plain
+    NormAdj(adj, symmetric, add_self_loops): the full-neighbourhood mean, what evaluation and graphed_inference run on - and
+    resample(), which keeps EXACTLY `fanout` of every row's stored entries, uniformly and without replacement, on the device
+    (ops.NeighborSampleBatch, csrc/neighbor_sample.hip: generator (seed, stream), a step word of this object's own), renormalises - the
+    scales of .full's normalisation on the KEPT counts: the sampled mean - and returns the thinned view every layer of that training
+    step aggregates over (one sample per step).  A self loop that add_self_loops put there is always kept and does not
+    count against the fan-out; the default leaves the node's own representation to the model (SAGE1 / SAGE2 keep it apart)."""
+
+    def __init__(self, adj, fanout, seed, stream=0, symmetric=0, add_self_loops=False):
+        from .neighbor_sample import check_fanout
+        self.fanout = check_fanout("NeighborSampleAdj", fanout)
+        self._setup(adj, seed, stream, symmetric, add_self_loops)
+
+    def batch(self):
+        """the one-entry ops.NeighborSampleBatch over .full's two patterns, built on first use (kept_graph(0), kept_counts() of the latest draw)"""
+        if self._batch is None:
+            self._batch = ops.NeighborSampleBatch([dict(graph=self.full.graph, graph_t=self.full.graph_t, stream=self.stream,
+                                                        keep_diagonal=self.keep_diagonal, norm=ops.NORM_SYM if self.symmetric else ops.NORM_RW)],
+                                                  self.fanout, self.seed)
+        return self._batch
+
+
 def graphed_inference(model, adj, x, **forward_kwargs):
     """One-shot inference `model(adj, x)` (eval mode, no gradients) captured as ONE hipGraph -> (replay, logits).
 
@@ -1052,7 +1128,7 @@ def graphed_inference(model, adj, x, **forward_kwargs):
     their addresses: same tensors, new values are fine); everything the forward builds lazily - SELL / band copies of the
     graph, narrow-kernel tables - is built by two eager runs before the capture."""
     model.eval()
-    adj = adj.full if isinstance(adj, DropEdgeAdj) else adj  # (inference runs on the full graph)
+    adj = adj.full if isinstance(adj, _ResampledAdj) else adj  # (inference runs on the full graph)
     with torch.no_grad():
         for _ in range(2):
             model(adj, x, **forward_kwargs)
@@ -1077,7 +1153,7 @@ def train_eval(model, adj, x, labels, masks=None, epochs=200, lr=0.01, weight_de
     tr, va, te = (m.to(dev) for m in masks)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     best = dict(val_acc=-1.0, test_acc=0.0, epoch=0)
-    thins = isinstance(adj, DropEdgeAdj)  # (a fresh subset of the edges per training step; evaluation on the full graph)
+    thins = isinstance(adj, _ResampledAdj)  # (a fresh subset of the edges per training step; evaluation on the full graph)
     full = adj.full if thins else adj
     for ep in range(epochs):
         model.train()
@@ -1117,7 +1193,7 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
     best_test = torch.zeros((), device=dev)
     best_epoch = torch.zeros((), dtype=torch.int64, device=dev)
     epoch = torch.zeros((), dtype=torch.int64, device=dev)
-    thins = isinstance(adj, DropEdgeAdj)  # (a fresh subset of the edges per training step - per replay; evaluation on the full graph)
+    thins = isinstance(adj, _ResampledAdj)  # (a fresh subset of the edges per training step - per replay; evaluation on the full graph)
     full = adj.full if thins else adj
 
     def train_step():
@@ -1144,7 +1220,7 @@ def train_eval_graphed(model, adj, x, labels, masks=None, epochs=200, lr=0.01, w
         p.grad = torch.zeros_like(p)
     g_train = g_eval = None
     if capture:
-        # (DeviceDropout, DropEdgeAdj: the warm-up's masks and subsets are drawn again)
+        # (DeviceDropout, DropEdgeAdj, NeighborSampleAdj: the warm-up's masks and subsets are drawn again)
         restore = snapshot(list(model.parameters()) + [r.step for r in _dropout_rngs(model)] + ([adj.step] if thins else []))
 
         def warm_up():
