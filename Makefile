@@ -9,6 +9,8 @@ SRCS     := $(wildcard $(CSRC)/*.hip)
 LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $(CSRC)/auc.hip $(CSRC)/sparse_dense.hip $(CSRC)/synth_classes.hip $(CSRC)/qda.hip $(CSRC)/gat.hip $(CSRC)/gat_scores.hip $(CSRC)/signed_att.hip $(CSRC)/poly_filter.hip $(CSRC)/two_hop.hip $(CSRC)/topk_rows.hip $(CSRC)/gcnii.hip $(CSRC)/drop_edge.hip
 # ... and behind them the neighbour sampler (neighbor_sample), on a line of its own: the list above ends where tests/test_abi_drop_edge.py reads it
 LAST     += $(CSRC)/neighbor_sample.hip
+# ... and behind it the neighbour maximum (neighbor_max), again on a line of its own
+LAST     += $(CSRC)/neighbor_max.hip
 SRCS     := $(filter-out $(LAST),$(SRCS)) $(LAST)
 LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and
@@ -43,6 +45,8 @@ FLAGS_topk_rows := -ffp-contract=off
 FLAGS_gcnii := -ffp-contract=off
 # drop_edge.hip's aggregation is ONE fmaf chain per element, stated in include/wdg.h and restated in numpy bit for bit: the fmaf is written out, nothing else is fused
 FLAGS_drop_edge := -ffp-contract=off
+# neighbor_max.hip's backward pass is ONE fp32 add chain per element, stated in include/wdg.h and restated in numpy bit for bit: nothing is fused (the source says so as well)
+FLAGS_neighbor_max := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB      := $(PKG)/lib/libwdg_hip.so
 

@@ -2340,6 +2340,111 @@ int wdg_neighbor_sample_batched(const wdg_neighbor_sample_job *jobs_dev, int32_t
 /* replaces: nothing of its own - the per-job refusals of the sampling pass above (utils/util_funcs.py:29-36, 365-380), on the host's table */
 int wdg_neighbor_sample_check_jobs(const wdg_neighbor_sample_job *jobs_host, int32_t n_jobs);
 
+/*
+ * The neighbour MAXIMUM: Y[i, f] = the greatest X[j, f] over the stored neighbours j of row i, and which j it was - the pooling aggregator
+ * of GraphSAGE (Hamilton, Ying, Leskovec, NeurIPS 2017) and the building block of PNA-style multi-aggregators -, for a table of patterns
+ * in ONE launch.  Every other aggregation of this library is a weighted sum; this one is not a low-pass average at all.
+ * The reference ships no model code: the operator is DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: nothing of the reference - it stands where the product with the normalised adjacency of normalize, utils/util_funcs.py:29-36,
+ *           and normalize_tensor, utils/util_funcs.py:365-380, stands in the other models, beside the tables of gnns_on_syn.py:9-53.
+ * A job: rowptr int32 [n_rows + 1], col int32 [nnz], kept_len int32 [n_rows] or NULL, X [n_cols, n_feat] fp32 with leading dimension
+ * ldx, Y [n_rows, n_feat] fp32 with leading dimension ldy, arg int32 [n_rows, n_feat] with leading dimension lda, or NULL (evaluation:
+ * not written).  kept_len == NULL: every row's whole extent (a plain CSR pattern); otherwise col is a thinned pattern's kept_col and
+ * the row's length is min(kept_len[i], rowptr[i + 1] - rowptr[i]), as in wdg_spmm_thinned_batched_f32.  The definition
+ * (tests/_neighbor_max_ref.py restates it in numpy), for row i and column f:
+ *   eligible     the row's first `len` stored entries q whose j = col[q] lies in [0, n_cols); the others - -1 included - are SKIPPED,
+ *                never read through
+ *   the order    a NaN above everything; otherwise the larger X[j, f], with -0 == +0; among equals (two NaNs are equals) the LOWER j -
+ *                the tie convention of wdg_topk_rows_batched_f32.  With WDG_NEIGHBOR_MAX_MIN "larger" reads "smaller"; a NaN still
+ *                wins and a tie still goes to the lower j.  A TOTAL order on the pairs (X[j, f], j): copies of one j are one pair.
+ *   Y[i, f]      the winner's X[j, f] - its BITS, copied: no arithmetic touches a value (a NaN keeps its payload, a zero its sign)
+ *   arg[i, f]    the winner's j
+ *   A row with no eligible entry stores +0 and -1.  A row whose extent lies outside [0, nnz] is left untouched (Y and arg).  Every
+ *   other element of Y / arg [0 : n_rows][0 : n_feat] is written and nothing outside that block.
+ * The winner is a function of the SET of eligible entries, so the result has the same bits for any stored order of a row, with
+ * duplicates, alone or in any table, and for a column at any job width - whatever walks the row: a wave per row and per panel of 256
+ * columns (four per lane), and the lanes that hold no columns take SHARES of the row's entries - at n_feat <= 16 four lanes cover the
+ * columns and sixteen entries are in flight per step -; the shares are merged across lanes at the end under the same order, carrying
+ * (value, j).  That is bit-safe because the maximum of a total order is associative and commutative; no sum of this library is.
+ * There is no multi-wave path for a hub row.  No LDS, no atomics.  16-byte loads / stores where the pointer, the leading dimension and
+ * n_feat (a multiple of 4) allow - the wave's decision, one each for X, Y and arg.  X must not overlap Y or arg.
+ * max_rows, max_feat: the table's largest n_rows and n_feat (rows / columns beyond them are not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID): negative counts, more than 65535 jobs (a job per grid z), a NULL table with
+ * n_jobs > 0, max_feat above 256 * 65535.  n_jobs == 0, max_rows == 0 or max_feat == 0: WDG_OK, nothing is launched.  What is wrong inside
+ * a job - a negative n_rows, n_cols, n_feat or nnz, unknown flag bits, a reserved word that is not 0, a leading dimension below n_feat (lda:
+ * where arg is given), a NULL
+ * rowptr or Y, a NULL col or X with nnz > 0 and n_cols > 0, X == Y - is refused by wdg_neighbor_max_check_jobs on the HOST copy of the
+ * table (neighbor_max.NeighborMaxBatch calls it before it uploads), and the launch leaves such a job untouched.  A job with
+ * n_rows == 0 or n_feat == 0 is skipped.
+ */
+#define WDG_NEIGHBOR_MAX_MIN 1 /* the neighbour MINIMUM: "larger" reads "smaller"; NaN and ties as before */
+typedef struct wdg_neighbor_max_job {
+    const int32_t *rowptr;    /* [n_rows + 1] */
+    const int32_t *col;       /* [nnz]: a CSR pattern's col, or a thinned pattern's kept_col */
+    const int32_t *kept_len;  /* [n_rows], or NULL: every row's whole extent */
+    const float *X;           /* [n_cols, n_feat], leading dimension ldx */
+    float *Y;                 /* out [n_rows, n_feat], leading dimension ldy */
+    int32_t *arg;             /* out [n_rows, n_feat], leading dimension lda, or NULL */
+    int64_t ldx, ldy, lda;
+    int32_t n_rows, n_cols, n_feat, nnz;
+    int32_t flags;            /* WDG_NEIGHBOR_MAX_* */
+    int32_t reserved;         /* must be 0 */
+} wdg_neighbor_max_job;
+int wdg_neighbor_max_batched_f32(const wdg_neighbor_max_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the neighbour maximum above (utils/util_funcs.py:29-36, 365-380), on the
+ *           host's table */
+int wdg_neighbor_max_check_jobs(const wdg_neighbor_max_job *jobs_host, int32_t n_jobs);
+
+/*
+ * The backward pass of the neighbour maximum: d_X[j, f] = the sum of d_Y[i, f] over the rows i whose winner in column f was j.  A job on
+ * the TRANSPOSED pattern, plain or thinned, which holds the same edges: a gather with one add chain per element, not a scatter.
+ * replaces: nothing of the reference - the transposed product that stands behind normalize, utils/util_funcs.py:29-36, and
+ *           normalize_tensor, utils/util_funcs.py:365-380, in the other models' backward passes (gnns_on_syn.py:9-53 holds their tables).
+ * A job: rowptr int32 [n_rows + 1], col int32 [nnz], kept_len int32 [n_rows] or NULL - of the transposed pattern, as above -,
+ * G [n_src, n_feat] fp32 with leading dimension ldg (the forward pass's d_Y), arg int32 [n_src, n_feat] with leading dimension lda (the
+ * forward pass's), D [n_rows, n_feat] fp32 with leading dimension ldd (d_X).  The definition (tests/_neighbor_max_ref.py restates it in
+ * numpy, bit for bit), for transposed row j and column f:
+ *   acc = +0; last = none; then for q = rowptr[j] .. rowptr[j] + len - 1 in that order, len as above:
+ *     i = col[q]; an entry with i outside [0, n_src) - which includes -1 - is SKIPPED, never read through;
+ *     an entry whose i equals `last`, the i of the previous entry that was not out of range, is SKIPPED too (the duplicate rule);
+ *     otherwise last = i and, if arg[i, f] == j: acc = acc + G[i, f]   (one rounded fp32 add; no add where arg differs)
+ *   D[j, f] = acc
+ *   - ONE add chain per output element in stored order whatever the row's length: no chain is split over lanes or waves, no partial
+ *   sums are added, there is no atomic (csrc/neighbor_max.hip is compiled with contraction off).  A sum depends on its order: unlike the
+ *   forward pass, this chain cannot be shared out - only the LOADS of a row's entries are, over the lanes that hold no columns; every
+ *   term then goes to the one lane that adds it, in entry order - and there is NO multi-wave path for a hub row of the transposed
+ *   pattern.
+ *   The duplicate rule: an edge stored twice is ONE pair of the forward pass's set and routes its gradient once.  CsrGraph.transpose()
+ *   MERGES duplicates (it builds through wdg_coo_to_csr_i32 without WDG_COO_KEEP_DUPLICATES: rows sorted by column, copies summed into
+ *   one entry), a transpose built with WDG_COO_KEEP_DUPLICATES sorts every row and so leaves copies adjacent, and the thinning passes
+ *   (wdg_drop_edge_thin_batched, wdg_neighbor_sample_batched) keep or drop all copies of a column together and compact in stored
+ *   order: adjacent copies stay adjacent.  A pattern whose duplicates are NOT adjacent counts them per occurrence.
+ *   A row whose extent lies outside [0, nnz] is left untouched.  A job has the same bits alone and in any table, and a column has the
+ *   same bits whatever the width of the job it is in.  D must not overlap G or arg.
+ * A wave per row and per panel of 256 columns, 16-byte accesses as above (one decision each for G, arg and D).
+ * Refused before any HIP call (WDG_ERR_INVALID): as above.  What is wrong inside a job - a negative n_rows, n_src, n_feat or nnz, a
+ * reserved word that is not 0, a leading dimension below n_feat, a NULL rowptr or D, a NULL col, G or arg with nnz > 0 and n_src > 0,
+ * G == D - is refused by wdg_neighbor_max_backward_check_jobs on the HOST copy of the table (neighbor_max.NeighborMaxBackwardBatch calls
+ * it before it uploads), and the launch leaves such a job untouched.  A job with n_rows == 0 or n_feat == 0 is skipped.
+ */
+typedef struct wdg_neighbor_max_backward_job {
+    const int32_t *rowptr;    /* [n_rows + 1]: the TRANSPOSED pattern's */
+    const int32_t *col;       /* [nnz] */
+    const int32_t *kept_len;  /* [n_rows], or NULL */
+    const float *G;           /* [n_src, n_feat], leading dimension ldg: d_Y */
+    const int32_t *arg;       /* [n_src, n_feat], leading dimension lda: the forward pass's */
+    float *D;                 /* out [n_rows, n_feat], leading dimension ldd: d_X */
+    int64_t ldg, lda, ldd;
+    int32_t n_rows, n_src, n_feat, nnz;
+    int32_t reserved;         /* must be 0 */
+    int32_t reserved2;        /* must be 0 */
+} wdg_neighbor_max_backward_job;
+int wdg_neighbor_max_backward_batched_f32(const wdg_neighbor_max_backward_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat,
+                                          wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the backward pass above (utils/util_funcs.py:29-36, 365-380), on the host's
+ *           table */
+int wdg_neighbor_max_backward_check_jobs(const wdg_neighbor_max_backward_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,10 @@ SIGNATURES = {
     "wdg_spmm_thinned_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_neighbor_sample_batched": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_uint32, c_void_p, c_void_p]),
     "wdg_neighbor_sample_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_neighbor_max_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_neighbor_max_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_neighbor_max_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_neighbor_max_backward_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -488,6 +492,18 @@ class NeighborSampleJob(ctypes.Structure):
     """mirror of `wdg_neighbor_sample_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_col", "kept_len", "scale", "tau")] + \
                [("n", c_int32), ("n_cols", c_int32), ("nnz", c_int32), ("stream", c_uint32), ("flags", c_int32), ("fanout", c_int32)]
+
+
+class NeighborMaxJob(ctypes.Structure):
+    """mirror of `wdg_neighbor_max_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_len", "X", "Y", "arg")] + [(name, c_int64) for name in ("ldx", "ldy", "lda")] + \
+               [(name, c_int32) for name in ("n_rows", "n_cols", "n_feat", "nnz", "flags", "reserved")]
+
+
+class NeighborMaxBackwardJob(ctypes.Structure):
+    """mirror of `wdg_neighbor_max_backward_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_len", "G", "arg", "D")] + [(name, c_int64) for name in ("ldg", "lda", "ldd")] + \
+               [(name, c_int32) for name in ("n_rows", "n_src", "n_feat", "nnz", "reserved", "reserved2")]
 
 
 if not os.path.exists(LIB_PATH):

@@ -54,6 +54,12 @@ neighbours, with the node's own representation kept APART from the aggregate (Ha
 Learning on Large Graphs") - the ego / neighbour separation H2GCN's paper credits for its standing under heterophily.  The sample -
 exactly `fanout` of a row's entries per training step - is drawn on csrc/neighbor_sample.hip and written as the thinned pattern of
 DropEdge's aggregation; evaluation runs on the full neighbourhood.  Defined by this project as well.
+
+GraphSAGE's POOLING aggregator (`SAGEPool1`, `SAGEPool2`) replaces the neighbourhood mean by a per-column MAXIMUM over the
+neighbours of a ReLU transform - the one aggregation here that is not a weighted sum.  `adj.neighbor_max(x)` runs on
+csrc/neighbor_max.hip, forward (it keeps which neighbour won) and backward (one job on the transposed pattern), over a NormAdj's stored
+pattern and over the thinned views of NeighborSampleAdj / DropEdgeAdj alike.  Defined by this project as well (the paper's layer
+without its bias).
 """
 import math
 
@@ -74,7 +80,7 @@ class NormAdj:
         self.graph, self.graph_t = g, g.transpose()
         self.row_scale, self.col_scale = d, (d if symmetric else None)
         self.n = g.n_rows
-        self._attention = None
+        self._attention, self._max_tables = None, {}
 
     def matmul(self, x):
         return _Aggregate.apply(x, self)
@@ -86,6 +92,16 @@ class NormAdj:
     def aggregate_t(self, g):
         """A_hat^T g without autograd: the backward pass of `aggregate` - (R A C)^T = C A^T R"""
         return ops.spmm(self.graph_t, g, row_scale=self.col_scale, col_scale=self.row_scale)
+
+    def neighbor_max(self, x):
+        """[n, F] -> per column the maximum of x over every row's stored neighbours (+0 for a row without one), with autograd: the
+        gradient goes to the neighbour that won (csrc/neighbor_max.hip; the scales are not read: a maximum has no weights)"""
+        return _NeighborMax.apply(x, self)
+
+    def _max_pass(self, backward, x, arg):
+        """the forward job (-> y, arg; arg None when no gradient is wanted) or the backward job on graph_t (x = d_y -> d_x): a one-job
+        table and its buffers per (direction, width, with arg), built on first use"""
+        return _max_pass(self._max_tables, self.graph, self.graph_t, backward, x, arg)
 
     def attention_plan(self):
         """what the attention kernels need of the pattern, built on first use and kept: dict(graph, graph_t, t_pos) - t_pos ties
@@ -108,6 +124,55 @@ class _Aggregate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         return ctx.adj.aggregate_t(gy.contiguous()), None
+
+
+def _max_pass(tables, pattern, pattern_t, backward, x, arg):
+    """What NormAdj._max_pass and _ResampledAdj._max_pass share: the one-job ops.NeighborMaxBatch / NeighborMaxBackwardBatch and its
+    buffers per (direction, width, with arg) in `tables`, built on first use (as _ResampledAdj._product's).  Forward: x and whether arg
+    is wanted (True / False: evaluation writes none) -> (y, arg or None); backward: x = d_y and the forward pass's arg -> d_x."""
+    key = (bool(backward), int(x.shape[1]), backward or bool(arg))
+    if key not in tables:
+        dev, f = x.device, key[1]
+        if backward:
+            gb = torch.zeros((pattern_t.n_cols, f), dtype=torch.float32, device=dev)
+            ab = torch.full((pattern_t.n_cols, f), -1, dtype=torch.int32, device=dev)
+            db = torch.zeros((pattern_t.n_rows, f), dtype=torch.float32, device=dev)
+            tables[key] = (gb, ab, db, ops.NeighborMaxBackwardBatch([dict(pattern=pattern_t, g=gb, arg=ab, d=db)]))
+        else:
+            xb = torch.zeros((pattern.n_cols, f), dtype=torch.float32, device=dev)
+            yb = torch.zeros((pattern.n_rows, f), dtype=torch.float32, device=dev)
+            ab = torch.full((pattern.n_rows, f), -1, dtype=torch.int32, device=dev) if key[2] else None
+            tables[key] = (xb, yb, ab, ops.NeighborMaxBatch([dict(pattern=pattern, x=xb, y=yb, arg=ab)]))
+    if backward:
+        gb, ab, db, table = tables[key]
+        gb.copy_(x)
+        ab.copy_(arg)
+        table.launch()
+        return db.clone()
+    xb, yb, ab, table = tables[key]
+    xb.copy_(x)
+    table.launch()
+    return yb.clone(), (ab.clone() if key[2] else None)
+
+
+class _NeighborMax(torch.autograd.Function):
+    """y = adj.neighbor_max(x): the forward pass keeps arg - which neighbour won every (row, column) -, the backward pass is ONE job on
+    the transposed pattern that sums every d_y into the winner's row (a tie routed to the lower j, never split).  adj: a NormAdj or a
+    thinned view, whose backward pass must precede the next resample() - the same refusal as the thinned aggregation's."""
+
+    @staticmethod
+    def forward(ctx, x, adj):
+        want = ctx.needs_input_grad[0]
+        y, arg = adj._max_pass(False, x, want)
+        ctx.adj = adj
+        if want:
+            ctx.save_for_backward(arg)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (arg,) = ctx.saved_tensors
+        return ctx.adj._max_pass(True, gy.contiguous(), arg), None
 
 
 class _Linear(torch.autograd.Function):
@@ -991,8 +1056,51 @@ class SAGE2(_HiddenDropout, torch.nn.Module):
         return p1[:, :self.nclass] + adj.matmul(p1[:, self.nclass:].contiguous())
 
 
+class _PoolLayer:
+    """The layer SAGEPool1 / SAGEPool2 share: Q = relu(M w_p), out = M w_s + neighbor_max(Q) w_n.  Q >= 0, so the +0 a node without
+    neighbours pools is the maximum over nothing; no gradient passes through it."""
+
+    @staticmethod
+    def _pool(adj, m, w_p, w_s, w_n):
+        q = _Linear.apply(m, w_p, True)
+        return _Linear.apply(m, w_s, False) + _Linear.apply(adj.neighbor_max(q), w_n, False)
+
+
+class SAGEPool1(_PoolLayer, torch.nn.Module):
+    """GraphSAGE-1 with the POOLING aggregator (Hamilton et al.'s, without its bias), bias-free: Q = relu(X w_p) with w_p [nfeat, npool],
+    logits = X w_s + neighbor_max(Q) w_n - per column of Q the maximum over the node's neighbours (adj.neighbor_max: a NormAdj's stored
+    pattern, or the sample / subset of a NeighborSampleAdj's / DropEdgeAdj's view; the scales are not read).  Give the adjacency
+    add_self_loops=False, as for SAGE1: the model holds the self path.  Parameters are drawn in this order: w_p [nfeat, npool], w_s
+    [nfeat, C], w_n [npool, C] (xavier_uniform each)."""
+
+    def __init__(self, nfeat, nclass, npool=64):
+        super().__init__()
+        self.w_p, self.w_s, self.w_n = _xavier(nfeat, npool), _xavier(nfeat, nclass), _xavier(npool, nclass)
+
+    def forward(self, adj, x):
+        return self._pool(adj, x, self.w_p, self.w_s, self.w_n)
+
+
+class SAGEPool2(_PoolLayer, _HiddenDropout, torch.nn.Module):
+    """GraphSAGE-2 with the pooling aggregator: SAGEPool1's layer twice - H = dropout(relu(X w_s0 + neighbor_max(relu(X w_p0)) w_n0)),
+    logits = H w_s1 + neighbor_max(relu(H w_p1)) w_n1 -, with _HiddenDropout's ReLU + dropout between.  Parameters are drawn in this
+    order: w_p0 [nfeat, npool], w_s0 [nfeat, nhid], w_n0 [npool, nhid], w_p1 [nhid, npool], w_s1 [nhid, C], w_n1 [npool, C]
+    (xavier_uniform each).  dropout_rng: as for GCN2."""
+
+    def __init__(self, nfeat, nclass, nhid=64, npool=64, dropout=0.5, dropout_rng=None):
+        super().__init__()
+        self.w_p0, self.w_s0, self.w_n0 = _xavier(nfeat, npool), _xavier(nfeat, nhid), _xavier(npool, nhid)
+        self.w_p1, self.w_s1, self.w_n1 = _xavier(nhid, npool), _xavier(nhid, nclass), _xavier(npool, nclass)
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+
+    def forward(self, adj, x):
+        h = self._relu_dropout(self._pool(adj, x, self.w_p0, self.w_s0, self.w_n0))
+        return self._pool(adj, h, self.w_p1, self.w_s1, self.w_n1)
+
+
 _DROP_EDGE_SERVED = ("a thinned view of a DropEdgeAdj has no stored pattern to read: it serves the models that aggregate through matmul / "
-                     "aggregate / aggregate_t - GCN2, ACMGCN2, GPRGNN1 / GPRGNN2 with fused=False, GCNII, SAGE1 / SAGE2")
+                     "aggregate / aggregate_t - GCN2, ACMGCN2, GPRGNN1 / GPRGNN2 with fused=False, GCNII, SAGE1 / SAGE2"
+                     " - or pool through neighbor_max - SAGEPool1 / SAGEPool2")
 
 
 class _ThinnedAdj:
@@ -1012,6 +1120,13 @@ class _ThinnedAdj:
 
     def aggregate_t(self, g):
         return self._owner._product(True, self._draw, g, None)
+
+    def neighbor_max(self, x):
+        """NormAdj.neighbor_max over the kept entries of this draw"""
+        return _NeighborMax.apply(x, self)
+
+    def _max_pass(self, backward, x, arg):
+        return self._owner._max_pass(backward, self._draw, x, arg)
 
     def attention_plan(self):
         raise TypeError("attention_plan: " + _DROP_EDGE_SERVED)
@@ -1037,7 +1152,7 @@ class _ResampledAdj:
         self.graph, self.n = self.full.graph, self.full.n
         self.step = torch.zeros(1, dtype=torch.int32, device=self.graph.device)
         self.draws = 0  # resample() calls so far, on the host: a view whose draw is not the latest refuses its backward pass
-        self._batch, self._products = None, {}
+        self._batch, self._products, self._max_tables = None, {}, {}
 
     def resample(self):
         """thin both patterns at the current step word, advance the word on the device -> the thinned view of this draw"""
@@ -1046,11 +1161,14 @@ class _ResampledAdj:
         self.draws += 1
         return _ThinnedAdj(self, self.draws)
 
-    def _product(self, transposed, draw, x, out):
-        """A_hat_kept x, or A_hat_kept^T x: a one-job ops.ThinnedSpmmBatch and its two buffers per (direction, width), built on first use"""
+    def _refuse_stale(self, draw):
         if draw != self.draws:
             raise RuntimeError(f"{type(self).__name__}: another resample() has run since the one this pass belongs to; the thinned pattern holds one "
                                "draw, the latest - a backward pass must precede the next resample()")
+
+    def _product(self, transposed, draw, x, out):
+        """A_hat_kept x, or A_hat_kept^T x: a one-job ops.ThinnedSpmmBatch and its two buffers per (direction, width), built on first use"""
+        self._refuse_stale(draw)
         key = (bool(transposed), int(x.shape[1]))
         if key not in self._products:
             b = self.batch()
@@ -1063,6 +1181,13 @@ class _ResampledAdj:
         xb.copy_(x)
         table.launch()
         return yb.clone() if out is None else out.copy_(yb)
+
+    def _max_pass(self, backward, draw, x, arg):
+        """the neighbour maximum over the kept entries, or its backward pass on the thinned transposed pattern (_max_pass above): the
+        tables hold the addresses of the batch's blocks, so every draw is reduced over without a rebuild"""
+        self._refuse_stale(draw)
+        b = self.batch()
+        return _max_pass(self._max_tables, b.thinned(0), b.thinned_t(0), backward, x, arg)
 
 
 class DropEdgeAdj(_ResampledAdj):
