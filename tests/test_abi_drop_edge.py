@@ -225,6 +225,10 @@ def test_header_and_source_state_what_they_owe():
     assert "replaces:" in source and "utils/util_funcs.py:29-36" in source and "utils/util_funcs.py:365-380" in source and "gnns_on_syn.py:9-53" in source
     assert "#pragma clang fp contract(off)" in source and '#include "philox.h"' in source
     code = re.sub(r"//[^\n]*", "", source)
-    assert "atomic" not in code.lower() and "__shared__" not in code and "gat_lanes.h" not in code  # (no atomics, no LDS, the chains restated)
+    assert '#include "wave_rows.h"' in code and "gat_lanes.h" not in code  # (the row helpers shared, the chains restated)
+    shared = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "when-do-gnns-help_amd", "csrc", "wave_rows.h")).read())  # the helpers the unit takes from there
+    assert "gat_lanes.h" not in shared
+    for text in (code, shared):
+        assert "atomic" not in text.lower() and "__shared__" not in text  # (no atomics, no LDS)
     make = open(os.path.join(ROOT, "Makefile")).read()
     assert "FLAGS_drop_edge := -ffp-contract=off" in make and re.search(r"^LAST\s*:=.*gcnii\.hip \$\(CSRC\)/drop_edge\.hip$", make, re.M)

@@ -224,5 +224,7 @@ def test_header_and_source_state_what_they_owe():
     source = open(os.path.join(ROOT, "when-do-gnns-help_amd", "csrc", "gcnii.hip")).read()
     assert "replaces:" in source and "utils/util_funcs.py:365-381" in source and "#pragma clang fp contract(off)" in source
     assert '#include "philox.h"' in source and "atomic" not in source.replace("No atomics", "")
+    shared = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "when-do-gnns-help_amd", "csrc", "wave_rows.h")).read())  # the helpers the unit takes from there
+    assert '#include "wave_rows.h"' in source and "atomic" not in shared.lower()
     make = open(os.path.join(ROOT, "Makefile")).read()
     assert "FLAGS_gcnii := -ffp-contract=off" in make and re.search(r"^LAST\s*:=.*gcnii\.hip", make, re.M)

@@ -189,7 +189,10 @@ def test_header_source_and_makefile_state_what_they_owe():
     assert "replaces:" in source and "utils/util_funcs.py:29-36" in source and "utils/util_funcs.py:365-380" in source and "gnns_on_syn.py:9-53" in source
     assert "#pragma clang fp contract(off)" in source
     code = re.sub(r"//[^\n]*", "", source)
-    assert "atomic" not in code.lower() and "__shared__" not in code and "fmaf" not in code  # (no atomics, no LDS, a plain add chain)
+    assert '#include "wave_rows.h"' in code
+    shared = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "when-do-gnns-help_amd", "csrc", "wave_rows.h")).read())  # the helpers the unit takes from there
+    for text in (code, shared):
+        assert "atomic" not in text.lower() and "__shared__" not in text and "fmaf" not in text  # (no atomics, no LDS, a plain add chain)
     make = open(os.path.join(ROOT, "Makefile")).read()
     assert "FLAGS_neighbor_max := -ffp-contract=off" in make
     last = re.findall(r"^LAST\s*\+=\s*(.*)$", make, re.M)

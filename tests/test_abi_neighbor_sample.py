@@ -195,7 +195,10 @@ def test_header_and_source_state_what_they_owe():
     assert "replaces:" in source and "utils/util_funcs.py:29-36" in source and "utils/util_funcs.py:365-380" in source and "gnns_on_syn.py:9-53" in source
     assert '#include "philox.h"' in source and "0x53414745u" in source
     code = re.sub(r"//[^\n]*", "", source)
-    assert "atomic" not in code.lower() and "__shared__" not in code and "topk_rows" not in code  # (no atomics, no LDS, the helpers restated)
+    assert '#include "wave_rows.h"' in code and "topk_rows" not in code  # (the row helpers shared, the candidate set restated)
+    shared = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "when-do-gnns-help_amd", "csrc", "wave_rows.h")).read())  # the helpers the unit takes from there
+    for text in (code, shared):
+        assert "atomic" not in text.lower() and "__shared__" not in text  # (no atomics, no LDS)
     make = open(os.path.join(ROOT, "Makefile")).read()
     assert re.search(r"^LAST\s*\+=\s*\$\(CSRC\)/neighbor_sample\.hip$", make, re.M)
     assert make.index("neighbor_sample.hip") > make.index("drop_edge.hip") and make.index("LAST     +=") < make.index("SRCS     := $(filter-out")

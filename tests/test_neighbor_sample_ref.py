@@ -119,3 +119,24 @@ def test_the_kept_subset_is_uniform(d, s):
     kc, kl, _, _ = R.sample([0] * 6 + [d], cols, d + 2, 0, s, 7, 3, 11)
     key = R.keys(np.full(d, 5), cols, 7, 3, 11)
     assert kl[5] == s and np.array_equal(kc[:s], cols[key <= np.sort(key)[s - 1]])
+
+
+@pytest.mark.parametrize("diagonal", [0, R.KEEP_DIAGONAL])
+@pytest.mark.parametrize("norm", [0, R.NORM_SYM])
+def test_both_restatements_leave_one_thinned_layout_where_nothing_is_dropped(norm, diagonal):
+    """the CPU twin of tests/test_gpu_thinned_layout.py: DropEdge at p = 0 and the sampler at a fan-out no row reaches write the same
+    kept_col, kept_len and scale - the full pattern - for the forward and for the transposed pattern (whose row 0 spans three chunks)"""
+    import _drop_edge_ref as D
+    import _thinned_layout as L
+    rowptr, col, t_rowptr, t_col = L.graph()
+    flags = norm | diagonal
+    assert (D.KEEP_DIAGONAL, D.NORM_SYM, D.TRANSPOSED) == (R.KEEP_DIAGONAL, R.NORM_SYM, R.TRANSPOSED)
+    kc, kl, sc, tau = R.sample(rowptr, col, L.N, flags, L.FANOUT, SEED, STREAM, 1)
+    assert (tau == R.NOTHING).all()  # nothing is drawn
+    fwd = D.thin(rowptr, col, L.N, flags, 0.0, SEED, STREAM, 1)
+    bwd = D.thin(t_rowptr, t_col, L.N, flags | D.TRANSPOSED, 0.0, SEED, STREAM, 1)
+    for got, want, rp, c in (((kc, kl, sc), fwd, rowptr, col),
+                             (R.thin_transposed(t_rowptr, t_col, L.N, flags | R.TRANSPOSED, tau, SEED, STREAM, 1), bwd, t_rowptr, t_col)):
+        for a, b in zip(got, want):
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+        assert np.array_equal(want[0], c) and np.array_equal(want[1], np.diff(rp)) and want[2].tobytes() == R.scale_of(np.diff(rp), flags).tobytes()

@@ -75,9 +75,8 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_kernel(const wdg_confusi
 }  // namespace
 
 extern "C" int wdg_confusion_batched_i32(const wdg_confusion_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_cols, wdg_stream_t stream) {
-    WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0 && max_cols >= 0, "confusion_batched: negative count");
-    WDG_REQUIRE(n_jobs <= CF_MAX_JOBS, "confusion_batched: %d jobs; one launch takes %d", n_jobs, CF_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs_dev != nullptr, "confusion_batched: null job table");
+    WDG_REQUIRE(max_rows >= 0 && max_cols >= 0, "confusion_batched: negative count");
+    if (const int rc = wdg::check_job_table("confusion_batched", jobs_dev, n_jobs, CF_MAX_JOBS)) return rc;
     if (max_cols > CF_MAX_C) return wdg::fail(WDG_ERR_UNSUPPORTED, "confusion_batched: %d classes; the kernel holds %d", max_cols, CF_MAX_C);
     if (n_jobs == 0 || max_rows == 0) return WDG_OK;
     hipLaunchKernelGGL(confusion_kernel, dim3(static_cast<unsigned>(wdg::ceil_div(max_rows, CF_ROWS)), 1, static_cast<unsigned>(n_jobs)), dim3(CF_THREADS), 0,

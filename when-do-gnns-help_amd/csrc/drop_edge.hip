@@ -21,10 +21,12 @@
 // lane draws its entry's word, a ballot and the lane's prefix count (mbcnt) give the compacted position, the kept columns are
 // stored in stored order, then the wave fills the rest of the row's extent with -1 and lane 0 writes the length and the scale.
 // Integer arithmetic plus one division (and a square root) per row.  No LDS, no atomics, no scratch.  There is NO multi-wave path
-// for a hub row: squirrel's longest row (1904 entries) is 30 chunks on one wave.
+// for a hub row: squirrel's longest row (1904 entries) is 30 chunks on one wave.  The row's extent, the chunk's compaction and the
+// row's tail are csrc/wave_rows.h's, which csrc/neighbor_sample.hip writes the same layout with; the aggregation reads it through
+// thinned_row_len there, as csrc/neighbor_max.hip does.
 // Aggregation: a WAVE owns a row and a PANEL of 256 columns (grid y); lane l holds the four columns 256 panel + 4 l .. + 3, so an
 // entry costs the wave one row piece of X (a 16-byte load per lane where the job's pointer, leading dimension and width allow -
-// the wave's decision, as in csrc/gat_lanes.h - element-wise loads elsewhere: same values, same fmaf).  The kept columns and their
+// the wave's decision, csrc/wave_rows.h - element-wise loads elsewhere: same values, same fmaf).  The kept columns and their
 // column scales are read 64 at a time, one per lane, and handed out with v_readlane; TS_DEPTH row loads are in flight before the
 // first fmaf of a batch, a shorter tail goes in batches of 4, 2, 1 (gt_chains' schedule, restated here: those chains read an
 // entry's weight per head from an LDS stage, these carry ONE scale per entry in a register, and gat_lanes.h is left as it is).
@@ -32,6 +34,7 @@
 #include <cstdint>
 
 #include "philox.h"
+#include "wave_rows.h"
 #include "wdg_common.h"
 
 #pragma clang fp contract(off)  // the chain's fmaf is written out; nothing else may be fused
@@ -41,19 +44,11 @@ namespace {
 using namespace wdg;
 
 constexpr int DE_WAVES = 4;          // rows per workgroup, both kernels
-constexpr int DE_MAX_JOBS = 65535;   // a job per grid y (thinning) / grid z (aggregation)
 constexpr int TS_PANEL = 256;        // columns of Y per wave: four per lane
 constexpr int TS_MAX_PANELS = 65535; // gridDim.y
 constexpr int TS_DEPTH = 8;          // row loads in flight before the first fmaf of a batch
 constexpr unsigned DE_KEY_TAG = 0x45444745u;  // "EDGE": the second key word of the step key
 constexpr int DE_KNOWN_FLAGS = WDG_DROP_EDGE_TIED | WDG_DROP_EDGE_TRANSPOSED | WDG_DROP_EDGE_KEEP_DIAGONAL | WDG_DROP_EDGE_NORM_SYM;
-
-// the extent of row `row`: false = it lies outside [0, nnz] (the row is left untouched)
-__device__ __forceinline__ bool de_extent(const global_ptr<const int32_t> rowptr, const int row, const int nnz, int &beg, int &end) {
-    beg = __builtin_amdgcn_readfirstlane(rowptr[row]);
-    end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-    return beg >= 0 && beg <= end && end <= nnz;
-}
 
 __global__ __launch_bounds__(64 * DE_WAVES) void drop_edge_thin_kernel(const wdg_drop_edge_job *__restrict__ jobs, const int max_rows,
                                                                        const unsigned drop_threshold, const unsigned seed,
@@ -68,7 +63,7 @@ __global__ __launch_bounds__(64 * DE_WAVES) void drop_edge_thin_kernel(const wdg
         (nnz > 0 && (!job->col || !job->kept_col || job->kept_col == job->col)))
         return;
     int beg, end;
-    if (!de_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
+    if (!row_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
     const global_ptr<const int32_t> col = to_global(job->col);
     const global_ptr<int32_t> kept_col = to_global(job->kept_col);
 
@@ -86,38 +81,9 @@ __global__ __launch_bounds__(64 * DE_WAVES) void drop_edge_thin_kernel(const wdg
         const unsigned a = tied ? min(fi, fj) : fi, b = tied ? max(fi, fj) : fj;
         const unsigned word = philox4x32_10(a, b, k0, k1);
         const bool keep = valid && ((diagonal && j == row) || word >= drop_threshold);
-        const unsigned long long votes = __ballot(keep);
-        const int before = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(votes >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(votes), 0u));
-        if (keep) kept_col[beg + kept + before] = j;  // (beg + kept + before < e0 + lane + 1 <= end: inside the row's extent)
-        kept += __popcll(votes);
+        thinned_row_keep(kept_col, beg, kept, keep, j);
     }
-    for (int q = beg + kept + lane; q < end; q += 64) kept_col[q] = -1;
-    if (lane == 0) {
-        to_global(job->kept_len)[row] = kept;
-        if (job->scale) {
-            const float c = static_cast<float>(kept);
-            float d = (flags & WDG_DROP_EDGE_NORM_SYM) ? 1.0f / sqrtf(c) : 1.0f / c;  // the F32 path of wdg_degree_norm on the count
-            if (isinf(d)) d = 0.f;
-            to_global(job->scale)[row] = d;
-        }
-    }
-}
-
-__device__ __forceinline__ bool ts_aligned16(const float *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
-// VEC is the WAVE's decision (pointer and leading dimension 16-byte aligned, n_feat a multiple of 4: every lane that has columns has
-// four): no per-lane branch sits between a load and its use.  Without VEC a lane reads its `live` columns one by one; the address of
-// a column it does not have is clamped to its last one (the value is never stored).
-template <bool VEC>
-__device__ __forceinline__ void ts_load4(const global_ptr<const float> p, const int live, float (&x)[4]) {
-    if (VEC) {
-        const float4 in = load_f32x4(p);
-        x[0] = in.x, x[1] = in.y, x[2] = in.z, x[3] = in.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = p[min(k, live - 1)];
-    }
+    thinned_row_finish(job, kept_col, row, beg, end, kept, lane, flags & WDG_DROP_EDGE_NORM_SYM);
 }
 
 // D consecutive entries d0 .. d0 + D - 1 of the chunk the wave holds: all D row loads, then the D x 4 fmafs in entry order.  src: lane
@@ -136,7 +102,7 @@ __device__ __forceinline__ void ts_batch(const global_ptr<const float> x_lane, c
     if (live > 0) {
         float x[D][4];
 #pragma unroll
-        for (int d = 0; d < D; ++d) ts_load4<VEC>(x_lane + static_cast<int64_t>(max(r[d], 0)) * ld, live, x[d]);
+        for (int d = 0; d < D; ++d) load4<VEC>(x_lane + static_cast<int64_t>(max(r[d], 0)) * ld, live, x[d]);
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const bool ok = r[d] >= 0;  // (uniform)
@@ -173,14 +139,14 @@ __global__ __launch_bounds__(64 * DE_WAVES) void spmm_thinned_kernel(const wdg_t
     // a job outside the contract is left untouched (wdg_spmm_thinned_check_jobs refuses it on the host)
     if (n_cols < 0 || nnz < 0 || job->reserved != 0 || job->ldx < n_feat || job->ldy < n_feat || !job->rowptr || !job->kept_len || !job->Y) return;
     int beg, end;
-    if (!de_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
-    int len = min(__builtin_amdgcn_readfirstlane(to_global(job->kept_len)[row]), end - beg);
+    if (!row_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
+    int len = thinned_row_len(job->kept_len, row, beg, end);
     if (n_cols == 0 || !job->kept_col || !job->X) len = 0;  // (nothing to gather from: every entry is skipped)
 
     const int c0 = panel0 + 4 * lane, live = max(0, min(4, n_feat - c0));
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     const global_ptr<const float> x_lane = to_global(job->X) + c0;
-    if ((n_feat & 3) == 0 && ts_aligned16(job->X, job->ldx))
+    if ((n_feat & 3) == 0 && aligned16(job->X, job->ldx))
         ts_row<true>(x_lane, job->ldx, live, to_global(job->kept_col), to_global(job->col_scale), beg, len, n_cols, lane, acc);
     else
         ts_row<false>(x_lane, job->ldx, live, to_global(job->kept_col), to_global(job->col_scale), beg, len, n_cols, lane, acc);
@@ -191,21 +157,13 @@ __global__ __launch_bounds__(64 * DE_WAVES) void spmm_thinned_kernel(const wdg_t
         for (int k = 0; k < 4; ++k) acc[k] = rs * acc[k];  // ONE multiply
     }
     const global_ptr<float> y = to_global(job->Y) + static_cast<int64_t>(row) * job->ldy + c0;
-    if ((n_feat & 3) == 0 && ts_aligned16(job->Y, job->ldy)) {
+    if ((n_feat & 3) == 0 && aligned16(job->Y, job->ldy)) {
         store_f32x4(y, make_float4(acc[0], acc[1], acc[2], acc[3]));
-    } else {
+    } else {  // (store4 of wave_rows.h, written out: through the call the compiler lays this kernel's blocks out differently)
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < live) y[k] = acc[k];
     }
-}
-
-// the table-level refusals of the launch entries and of the host predicates (what = the entry's name in the message)
-int de_check_table(const char *what, const void *jobs, int32_t n_jobs) {
-    WDG_REQUIRE(n_jobs >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= DE_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, DE_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
 }
 
 }  // namespace
@@ -213,7 +171,7 @@ int de_check_table(const char *what, const void *jobs, int32_t n_jobs) {
 extern "C" int wdg_drop_edge_thin_batched(const wdg_drop_edge_job *jobs_dev, int32_t n_jobs, int32_t max_rows, uint32_t drop_threshold,
                                           uint32_t seed, const uint32_t *step_dev, wdg_stream_t stream) {
     WDG_REQUIRE(max_rows >= 0, "drop_edge_thin_batched: negative count");
-    if (const int rc = de_check_table("drop_edge_thin_batched", jobs_dev, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("drop_edge_thin_batched", jobs_dev, n_jobs)) return rc;
     WDG_REQUIRE(step_dev != nullptr, "drop_edge_thin_batched: null step word");
     if (n_jobs == 0 || max_rows == 0) return WDG_OK;
     hipLaunchKernelGGL(drop_edge_thin_kernel, dim3(static_cast<unsigned>(wdg::ceil_div(max_rows, DE_WAVES)), static_cast<unsigned>(n_jobs)),
@@ -224,7 +182,7 @@ extern "C" int wdg_drop_edge_thin_batched(const wdg_drop_edge_job *jobs_dev, int
 // The per-job part of the contract, for a table the caller still holds on the host (drop_edge.DropEdgeBatch calls this on the table it
 // is about to upload).
 extern "C" int wdg_drop_edge_check_jobs(const wdg_drop_edge_job *jobs_host, int32_t n_jobs) {
-    if (const int rc = de_check_table("drop_edge_check_jobs", jobs_host, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("drop_edge_check_jobs", jobs_host, n_jobs)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_drop_edge_job &j = jobs_host[i];
         WDG_REQUIRE(j.n >= 0 && j.n_cols >= 0 && j.nnz >= 0, "drop_edge_check_jobs: job %d has a negative shape", i);
@@ -243,7 +201,7 @@ extern "C" int wdg_drop_edge_check_jobs(const wdg_drop_edge_job *jobs_host, int3
 extern "C" int wdg_spmm_thinned_batched_f32(const wdg_thinned_spmm_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat,
                                             wdg_stream_t stream) {
     WDG_REQUIRE(max_rows >= 0 && max_feat >= 0, "spmm_thinned_batched: negative count");
-    if (const int rc = de_check_table("spmm_thinned_batched", jobs_dev, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("spmm_thinned_batched", jobs_dev, n_jobs)) return rc;
     WDG_REQUIRE(wdg::ceil_div(max_feat, TS_PANEL) <= TS_MAX_PANELS, "spmm_thinned_batched: %d columns; one launch takes %d", max_feat,
                 TS_PANEL * TS_MAX_PANELS);
     if (n_jobs == 0 || max_rows == 0 || max_feat == 0) return WDG_OK;
@@ -255,7 +213,7 @@ extern "C" int wdg_spmm_thinned_batched_f32(const wdg_thinned_spmm_job *jobs_dev
 }
 
 extern "C" int wdg_spmm_thinned_check_jobs(const wdg_thinned_spmm_job *jobs_host, int32_t n_jobs) {
-    if (const int rc = de_check_table("spmm_thinned_check_jobs", jobs_host, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("spmm_thinned_check_jobs", jobs_host, n_jobs)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_thinned_spmm_job &j = jobs_host[i];
         WDG_REQUIRE(j.n_rows >= 0 && j.n_cols >= 0 && j.n_feat >= 0 && j.nnz >= 0, "spmm_thinned_check_jobs: job %d has a negative shape", i);

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_forward_kernel(const wdg_ga
     const int i = blockIdx.x * GT_WAVES + wave;
     if (i >= s.n || !job->rowptr || !job->H || !job->S || !job->out || (s.nnz > 0 && (!job->col || !job->alpha))) return;  // (wave-uniform)
     int beg, end;
-    if (!gt_extent(job->rowptr, i, s.nnz, beg, end)) return;
+    if (!row_extent(to_global(job->rowptr), i, s.nnz, beg, end)) return;
     const int heads = s.heads, n = job->n;
     const float slope = job->slope;
     const global_ptr<const int32_t> col = to_global(job->col);
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_rows_kernel(const 
     const int i = blockIdx.x * GT_WAVES + wave;
     if (i >= s.n || !gt_has_backward(job, s.nnz)) return;  // (wave-uniform)
     int beg, end;
-    if (!gt_extent(job->rowptr, i, s.nnz, beg, end)) return;
+    if (!row_extent(to_global(job->rowptr), i, s.nnz, beg, end)) return;
     const int heads = s.heads, w = s.w, cols = s.cols, n = job->n;
     const float slope = job->slope;
     const global_ptr<const int32_t> col = to_global(job->col);
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_rows_kernel(const 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (vec_h) {
-                    gt_load4<true>(row + min(c + 4 * u, cols - 4), 4, x[u]);
+                    load4<true>(row + min(c + 4 * u, cols - 4), 4, x[u]);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) x[u][k] = row[min(c + 4 * u + k, cols - 1)];
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void gat_backward_cols_kernel(const 
     const int j = blockIdx.x * GT_WAVES + wave;
     if (j >= s.n || !gt_has_backward(job, s.nnz)) return;  // (wave-uniform)
     int beg, end;
-    if (!gt_extent(job->t_rowptr, j, s.nnz, beg, end)) return;
+    if (!row_extent(to_global(job->t_rowptr), j, s.nnz, beg, end)) return;
     const int heads = s.heads, n = job->n;
     const global_ptr<const int32_t> t_col = to_global(job->t_col), t_pos = to_global(job->t_pos);
     const global_ptr<const float> alpha = to_global(const_cast<const float *>(job->alpha)), d_pre = to_global(const_cast<const float *>(job->d_pre));

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "wave_rows.h"
 #include "wdg_common.h"
 
 #pragma clang fp contract(off)  // every fused multiply-add of the definitions is written as fmaf; nothing else may be fused
@@ -16,7 +17,6 @@ using namespace wdg;
 
 constexpr int GT_WAVES = 4;                  // rows per workgroup
 constexpr int GT_HEADS = WDG_GAT_MAX_HEADS;  // the unrolled head loops and the LDS stage's row
-constexpr int GT_MAX_JOBS = 65535;           // gridDim.z
 #ifndef WDG_GAT_DEPTH
 #define WDG_GAT_DEPTH 8
 #endif
@@ -37,10 +37,6 @@ __device__ __forceinline__ void gt_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ bool gt_aligned16(const float *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
-
 // the lane's four columns c0 .. c0 + 3 of the job's heads * w, and the head of each
 struct gt_lane_cols {
     int c0, live;  // live: how many of the four exist (0 .. 4)
@@ -54,19 +50,9 @@ __device__ __forceinline__ gt_lane_cols gt_columns(const int lane, const int hea
     for (int k = 0; k < 4; ++k) lc.hk[k] = min((lc.c0 + k) / w, heads - 1);
     return lc;
 }
-// VEC is the WAVE's decision (pointer and leading dimension 16-byte aligned, heads w a multiple of 4: every lane that has columns has
-// four): no per-lane branch sits between a load and its use, so the loads of a batch stay in flight together.  Without VEC a lane
-// reads its `live` columns one by one; the address of a column it does not have is clamped to its last one (the value is never stored).
-template <bool VEC>
-__device__ __forceinline__ void gt_load4(const global_ptr<const float> p, const int live, float (&x)[4]) {
-    if (VEC) {
-        const float4 in = load_f32x4(p);
-        x[0] = in.x, x[1] = in.y, x[2] = in.z, x[3] = in.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = p[min(k, live - 1)];
-    }
-}
+// VEC of load4 (wave_rows.h) is the WAVE's decision here - gt_wave_vec: pointer and leading dimension 16-byte aligned, heads w a
+// multiple of 4 -, so the loads of a batch stay in flight together.  The store takes the decision at RUN time and stays written out:
+// as a dispatch to store4<true / false> the compiler inverts the callers' branch on it.
 __device__ __forceinline__ void gt_store4(const global_ptr<float> p, const bool vec, const int live, const float (&x)[4]) {
     if (vec) {
         store_f32x4(p, make_float4(x[0], x[1], x[2], x[3]));
@@ -76,7 +62,7 @@ __device__ __forceinline__ void gt_store4(const global_ptr<float> p, const bool 
             if (k < live) p[k] = x[k];
     }
 }
-__device__ __forceinline__ bool gt_wave_vec(const float *p, const int64_t ld, const int cols) { return gt_aligned16(p, ld) && (cols & 3) == 0; }
+__device__ __forceinline__ bool gt_wave_vec(const float *p, const int64_t ld, const int cols) { return aligned16(p, ld) && (cols & 3) == 0; }
 
 // D consecutive entries d0 .. d0 + D - 1 of the chunk the wave holds: all D row loads, then the D x 4 fmafs in entry order -
 // acc[k] = fmaf(weight of the entry for the column's head, X[source row][c0 + k], acc[k]).  src: lane d holds the source row of entry
@@ -91,7 +77,7 @@ __device__ __forceinline__ void gt_batch(const global_ptr<const float> x_base, c
     if (lc.live > 0) {
         float x[D][4];
 #pragma unroll
-        for (int d = 0; d < D; ++d) gt_load4<VEC>(x_base + static_cast<int64_t>(max(r[d], 0)) * ld + lc.c0, lc.live, x[d]);
+        for (int d = 0; d < D; ++d) load4<VEC>(x_base + static_cast<int64_t>(max(r[d], 0)) * ld + lc.c0, lc.live, x[d]);
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const bool ok = r[d] >= 0;  // (uniform)
@@ -131,13 +117,6 @@ __device__ __forceinline__ bool gt_job_shape(const desc_ptr<J> job, const int ma
     s.cols = s.heads * s.w;
     return s.heads >= 1 && s.heads <= GT_HEADS && s.w >= 1 && s.cols <= WDG_GAT_MAX_COLS && s.nnz >= 0 && job->n >= 0;
 }
-// the extent of row `row` of a CSR: false = it lies outside [0, nnz] (the row is left untouched)
-__device__ __forceinline__ bool gt_extent(const int32_t *rowptr_, const int row, const int nnz, int &beg, int &end) {
-    const global_ptr<const int32_t> rowptr = to_global(rowptr_);
-    beg = __builtin_amdgcn_readfirstlane(rowptr[row]);
-    end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-    return beg >= 0 && beg <= end && end <= nnz;
-}
 
 template <typename J>
 __device__ __forceinline__ bool gt_has_backward(const desc_ptr<J> job, const int nnz) {
@@ -153,9 +132,9 @@ __device__ __forceinline__ void gt_stage_d_out(const desc_ptr<J> job, const gt_s
     const global_ptr<const float> gi = to_global(job->d_out) + static_cast<int64_t>(i) * job->ld_d_out + lc.c0;
     if (lc.live > 0) {
         if (gt_wave_vec(job->d_out, job->ld_d_out, s.cols))
-            gt_load4<true>(gi, lc.live, x);
+            load4<true>(gi, lc.live, x);
         else
-            gt_load4<false>(gi, lc.live, x);
+            load4<false>(gi, lc.live, x);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) g[4 * lane + k] = k < lc.live ? x[k] : 0.f;
@@ -216,10 +195,8 @@ __device__ __forceinline__ void gt_transposed_row(const desc_ptr<J> job, const g
 
 // the table-level refusals of the launch entries and of the host predicates (what = the entry's name in the message)
 inline int gt_check_table(const char *what, const void *jobs, int32_t n_jobs, int32_t max_rows) {
-    WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= GT_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, GT_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
+    WDG_REQUIRE(max_rows >= 0, "%s: negative count", what);
+    return check_job_table(what, jobs, n_jobs);
 }
 
 }  // namespace wdg_gt

@@ -19,6 +19,7 @@
 // per-lane branch sits between a load and its use.
 #include <cstdint>
 
+#include "wave_rows.h"
 #include "wdg_common.h"
 
 #pragma clang fp contract(off)  // every fused multiply-add of the definition is written as fmaf; nothing else may be fused
@@ -31,12 +32,8 @@ constexpr int GS_THREADS = 256;
 constexpr int GS_ROWS = WDG_GAT_SCORES_ROW_BLOCK;  // rows per workgroup of either pass; the backward pass's block of partial sums
 constexpr int GS_REG_W = 16;                       // the widest group whose attention vectors a forward thread keeps in registers
 constexpr int GS_DEPTH = 4;                        // backward: rows whose loads are in flight together (a divisor of GS_ROWS)
-constexpr int GS_MAX_JOBS = 65535;                 // gridDim.z
 static_assert(GS_ROWS % GS_DEPTH == 0, "a block of rows is a whole number of batches");
 
-__device__ __forceinline__ bool gs_aligned16(const void *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
 __device__ __forceinline__ bool gs_in_limits(const int n, const int G, const int w, const int heads) {
     return n > 0 && G > 0 && heads >= 1 && heads <= WDG_GAT_SCORES_MAX_HEADS && w >= 1 && w <= WDG_GAT_SCORES_MAX_W &&
            static_cast<int64_t>(G) * w <= INT32_MAX;
@@ -135,7 +132,7 @@ __global__ __launch_bounds__(GS_THREADS) void gat_scores_forward_kernel(const wd
     const int n = j->n, G = j->G, w = j->w, heads = j->heads;
     if (!gs_in_limits(n, G, w, heads) || !j->H || !j->S || !j->att) return;
     if (static_cast<int64_t>(blockIdx.x) * GS_ROWS >= n) return;
-    const bool vec = (w & 3) == 0 && gs_aligned16(j->H, j->ld_h) && gs_aligned16(j->att, j->ld_att);
+    const bool vec = (w & 3) == 0 && aligned16(j->H, j->ld_h) && aligned16(j->att, j->ld_att);
     if (vec)
         gs_forward_job<true>(j, n, G, w, heads);
     else
@@ -143,27 +140,6 @@ __global__ __launch_bounds__(GS_THREADS) void gat_scores_forward_kernel(const wd
 }
 
 // --------------------------------------------------------------------------------------------------------------- backward
-template <bool VEC>
-__device__ __forceinline__ void gs_load4(const global_ptr<const float> p, const int live, float (&x)[4]) {
-    if (VEC) {
-        const float4 v = load_f32x4(p);
-        x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = p[min(k, live - 1)];  // (a column the thread does not have: its last one, never stored)
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void gs_store4(const global_ptr<float> p, const int live, const float (&x)[4]) {
-    if (VEC) {
-        store_f32x4(p, make_float4(x[0], x[1], x[2], x[3]));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < live) p[k] = x[k];
-    }
-}
-
 // VEC: w is a multiple of 4, so the thread's four columns lie in ONE group and read one pair of scores per row; else every column has
 // its own pair.
 template <bool VEC>
@@ -185,15 +161,15 @@ __device__ __forceinline__ void gs_backward_job(const desc_ptr<wdg_gat_scores_jo
     const global_ptr<float> d_H = to_global(j->d_H) + c0;
     const int64_t ld_h = j->ld_h, ld_d_h = j->ld_d_h, ld_d_s = j->ld_d_s;
     float a_d[4], a_s[4], acc_d[4] = {0.f, 0.f, 0.f, 0.f}, acc_s[4] = {0.f, 0.f, 0.f, 0.f};
-    gs_load4<VEC>(att, live, a_d);
-    gs_load4<VEC>(att + j->ld_att, live, a_s);
+    load4<VEC>(att, live, a_d);
+    load4<VEC>(att + j->ld_att, live, a_s);
     for (int r = r0; r < r1; r += GS_DEPTH) {
         float x[GS_DEPTH][4], dh[GS_DEPTH][4], sd[GS_DEPTH][NS], ss[GS_DEPTH][NS];
 #pragma unroll
         for (int u = 0; u < GS_DEPTH; ++u) {  // all the loads of the batch (a row past the block's end: the last one again, not used)
             const int64_t row = min(r + u, r1 - 1);
-            gs_load4<VEC>(H + row * ld_h, live, x[u]);
-            gs_load4<VEC>(d_H + row * ld_d_h, live, dh[u]);
+            load4<VEC>(H + row * ld_h, live, x[u]);
+            load4<VEC>(d_H + row * ld_d_h, live, dh[u]);
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 sd[u][k] = d_S[row * ld_d_s + c_dst[k]];
@@ -211,12 +187,12 @@ __device__ __forceinline__ void gs_backward_job(const desc_ptr<wdg_gat_scores_jo
                 acc_s[k] = fmaf(s, x[u][k], acc_s[k]);
                 out[k] = fmaf(s, a_s[k], fmaf(d, a_d[k], dh[u][k]));
             }
-            gs_store4<VEC>(d_H + (r + u) * ld_d_h, live, out);
+            store4<VEC>(d_H + (r + u) * ld_d_h, live, out);
         }
     }
     const global_ptr<float> part = to_global(j->partial) + static_cast<int64_t>(blockIdx.x) * 2 * cols + c0;
-    gs_store4<VEC>(part, live, acc_d);
-    gs_store4<VEC>(part + cols, live, acc_s);
+    store4<VEC>(part, live, acc_d);
+    store4<VEC>(part + cols, live, acc_s);
 }
 
 __device__ __forceinline__ bool gs_has_backward(const desc_ptr<wdg_gat_scores_job> j) {
@@ -228,8 +204,8 @@ __global__ __launch_bounds__(GS_THREADS) void gat_scores_backward_kernel(const w
     const int n = j->n, G = j->G, w = j->w, heads = j->heads;
     if (!gs_in_limits(n, G, w, heads) || !gs_has_backward(j)) return;
     if (static_cast<int64_t>(blockIdx.x) * GS_ROWS >= n) return;
-    const bool vec = (w & 3) == 0 && gs_aligned16(j->H, j->ld_h) && gs_aligned16(j->d_H, j->ld_d_h) && gs_aligned16(j->att, j->ld_att) &&
-                     gs_aligned16(j->partial, 0);
+    const bool vec = (w & 3) == 0 && aligned16(j->H, j->ld_h) && aligned16(j->d_H, j->ld_d_h) && aligned16(j->att, j->ld_att) &&
+                     aligned16(j->partial, 0);
     if (vec)
         gs_backward_job<true>(j, n, G, w, heads);
     else
@@ -255,10 +231,8 @@ __global__ __launch_bounds__(GS_THREADS) void gat_scores_sum_blocks_kernel(const
 }
 
 int gs_check(const char *what, const wdg_gat_scores_job *jobs, int32_t n_jobs, int32_t max_rows, int32_t max_other) {
-    WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0 && max_other >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= GS_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, GS_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
+    WDG_REQUIRE(max_rows >= 0 && max_other >= 0, "%s: negative count", what);
+    return wdg::check_job_table(what, jobs, n_jobs);
 }
 
 }  // namespace

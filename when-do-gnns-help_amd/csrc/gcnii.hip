@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "philox.h"
+#include "wave_rows.h"
 #include "wdg_common.h"
 
 #pragma clang fp contract(off)  // every fused multiply-add of the definition is written as fmaf; nothing else may be fused
@@ -35,33 +36,7 @@ constexpr int GC_ROWS = WDG_GCNII_ROW_BLOCK;  // rows per workgroup of either pa
 constexpr int GC_LD = WDG_GCNII_MAX_W + 4;    // the LDS tiles' row pitch in floats: a multiple of 4 (16-byte reads), not of 32
 constexpr int GC_MAX_JOBS = 65535;            // gridDim.z
 
-__device__ __forceinline__ bool gc_aligned16(const void *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
 __device__ __forceinline__ bool gc_in_limits(const int n, const int w) { return n > 0 && w >= 1 && w <= WDG_GCNII_MAX_W; }
-
-// four adjacent floats at p, of which `live` (1..4) exist: 16 bytes at once, or one by one (a float the thread does not have: its last
-// one again, never stored)
-template <bool VEC>
-__device__ __forceinline__ void gc_load4(const global_ptr<const float> p, const int live, float (&x)[4]) {
-    if (VEC) {
-        const float4 v = load_f32x4(p);
-        x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = p[min(k, live - 1)];
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void gc_store4(const global_ptr<float> p, const int live, const float (&x)[4]) {
-    if (VEC) {
-        store_f32x4(p, make_float4(x[0], x[1], x[2], x[3]));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < live) p[k] = x[k];
-    }
-}
 
 // the contract of wdg_relu_dropout_batched_f32 for one element (csrc/dropout.hip's dr_value, word for word)
 __device__ __forceinline__ float gc_relu_dropout(const float h, const unsigned word, const unsigned drop_threshold, const float scale) {
@@ -82,11 +57,11 @@ __device__ __forceinline__ void gc_stage_s(const desc_ptr<wdg_gcnii_job> j, cons
         const int rl = e / quads, c = 4 * (e - rl * quads), live = min(4, w - c);
         const int64_t r = r0 + rl;
         float p[4], h[4], s[4];
-        gc_load4<VEC>(P + r * ld_p + c, live, p);
-        gc_load4<VEC>(H0 + r * ld_h0 + c, live, h);
+        load4<VEC>(P + r * ld_p + c, live, p);
+        load4<VEC>(H0 + r * ld_h0 + c, live, h);
 #pragma unroll
         for (int k = 0; k < 4; ++k) s[k] = fmaf(alpha, h[k], a1 * p[k]);
-        if (j->S) gc_store4<VEC>(S + r * ld_s + c, live, s);
+        if (j->S) store4<VEC>(S + r * ld_s + c, live, s);
 #pragma unroll
         for (int k = 0; k < 4; ++k) tile[rl][c + k] = k < live ? s[k] : 0.f;
     }
@@ -114,7 +89,7 @@ __device__ __forceinline__ void gc_forward_job(const desc_ptr<wdg_gcnii_job> j, 
 #pragma unroll 4
     for (int k = 0; k < w; ++k) {
         float wk[4];
-        gc_load4<VEC>(W + k * ld_w, live, wk);
+        load4<VEC>(W + k * ld_w, live, wk);
 #pragma unroll
         for (int u = 0; u < RPT; ++u) {
             const float s = tile[min(rg + u * GROUPS, GC_ROWS - 1)][k];  // (a row past the block's end: never stored)
@@ -140,7 +115,7 @@ __device__ __forceinline__ void gc_forward_job(const desc_ptr<wdg_gcnii_job> j, 
 #pragma unroll
             for (int q = 0; q < 4; ++q) z[q] = gc_relu_dropout(z[q], pw.w[q], drop_threshold, scale);
         }
-        gc_store4<VEC>(out + static_cast<int64_t>(r) * ld_out + c, live, z);
+        store4<VEC>(out + static_cast<int64_t>(r) * ld_out + c, live, z);
     }
 }
 
@@ -164,8 +139,8 @@ __global__ __launch_bounds__(GC_THREADS) void gcnii_forward_kernel(const wdg_gcn
     const int n = j->n, w = j->w;
     if (!gc_in_limits(n, w) || !j->P || !j->H0 || !j->W || !j->out) return;  // (uniform: before the barrier)
     if (static_cast<int64_t>(blockIdx.x) * GC_ROWS >= n) return;
-    const bool vec = (w & 3) == 0 && gc_aligned16(j->P, j->ld_p) && gc_aligned16(j->H0, j->ld_h0) && gc_aligned16(j->W, j->ld_w) &&
-                     gc_aligned16(j->out, j->ld_out) && gc_aligned16(j->S, j->ld_s);
+    const bool vec = (w & 3) == 0 && aligned16(j->P, j->ld_p) && aligned16(j->H0, j->ld_h0) && aligned16(j->W, j->ld_w) &&
+                     aligned16(j->out, j->ld_out) && aligned16(j->S, j->ld_s);
     if (vec)
         gc_forward_width<true>(j, n, w, act, drop_threshold, scale, seed, step_dev, tile);
     else
@@ -188,9 +163,9 @@ __device__ __forceinline__ void gc_backward_job(const desc_ptr<wdg_gcnii_job> j,
             const int rl = e / quads, c = 4 * (e - rl * quads), live = min(4, w - c);
             const int64_t r = r0 + rl;
             float s[4], g[4], o[4] = {1.f, 1.f, 1.f, 1.f};
-            gc_load4<VEC>(S + r * ld_s + c, live, s);
-            gc_load4<VEC>(d_out + r * ld_d_out + c, live, g);
-            if (act != 0) gc_load4<VEC>(out + r * ld_out + c, live, o);
+            load4<VEC>(S + r * ld_s + c, live, s);
+            load4<VEC>(d_out + r * ld_d_out + c, live, g);
+            if (act != 0) load4<VEC>(out + r * ld_out + c, live, o);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float dz = act != 0 ? (o[k] > 0.f ? g[k] * scale : 0.f) : g[k];
@@ -217,7 +192,7 @@ __device__ __forceinline__ void gc_backward_job(const desc_ptr<wdg_gcnii_job> j,
             const int lc = min(4, w - c);
             float wk[4][4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) gc_load4<VEC>(Wk[q] + c, lc, wk[q]);
+            for (int q = 0; q < 4; ++q) load4<VEC>(Wk[q] + c, lc, wk[q]);
 #pragma unroll
             for (int u = 0; u < RPT; ++u) {
                 const float *dz = dz_tile[min(rg + u * GROUPS, GC_ROWS - 1)] + c;
@@ -237,15 +212,15 @@ __device__ __forceinline__ void gc_backward_job(const desc_ptr<wdg_gcnii_job> j,
             const int64_t r = r0 + rl;
             if (r >= r1) break;
             float h[4], dp[4];
-            gc_load4<VEC>(d_H0 + r * ld_d_h0 + q4, live, h);
+            load4<VEC>(d_H0 + r * ld_d_h0 + q4, live, h);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float ds = fmaf(beta, acc[u][q], b1 * dz_tile[rl][q4 + q]);
                 dp[q] = a1 * ds;
                 h[q] = fmaf(alpha, ds, h[q]);
             }
-            gc_store4<VEC>(d_P + r * ld_d_p + q4, live, dp);
-            gc_store4<VEC>(d_H0 + r * ld_d_h0 + q4, live, h);
+            store4<VEC>(d_P + r * ld_d_p + q4, live, dp);
+            store4<VEC>(d_H0 + r * ld_d_h0 + q4, live, h);
         }
     }
     // the block's partial sums: columns q4 .. q4 + 3 of rows k = kg KPT .. of partial[b]
@@ -272,7 +247,7 @@ __device__ __forceinline__ void gc_backward_job(const desc_ptr<wdg_gcnii_job> j,
 #pragma unroll
     for (int u = 0; u < KPT; ++u) {
         if (k0 + u >= w) break;
-        gc_store4<VEC>(part + static_cast<int64_t>(k0 + u) * w, live, acc[u]);
+        store4<VEC>(part + static_cast<int64_t>(k0 + u) * w, live, acc[u]);
     }
 }
 
@@ -300,9 +275,9 @@ __global__ __launch_bounds__(GC_THREADS) void gcnii_backward_kernel(const wdg_gc
     const int n = j->n, w = j->w;
     if (!gc_in_limits(n, w) || !gc_has_backward(j)) return;  // (uniform: before the barrier)
     if (static_cast<int64_t>(blockIdx.x) * GC_ROWS >= n) return;
-    const bool vec = (w & 3) == 0 && gc_aligned16(j->S, j->ld_s) && gc_aligned16(j->W, j->ld_w) && gc_aligned16(j->out, j->ld_out) &&
-                     gc_aligned16(j->d_out, j->ld_d_out) && gc_aligned16(j->d_P, j->ld_d_p) && gc_aligned16(j->d_H0, j->ld_d_h0) &&
-                     gc_aligned16(j->partial, 0);
+    const bool vec = (w & 3) == 0 && aligned16(j->S, j->ld_s) && aligned16(j->W, j->ld_w) && aligned16(j->out, j->ld_out) &&
+                     aligned16(j->d_out, j->ld_d_out) && aligned16(j->d_P, j->ld_d_p) && aligned16(j->d_H0, j->ld_d_h0) &&
+                     aligned16(j->partial, 0);
     if (vec)
         gc_backward_width<true>(j, n, w, act, scale, s_tile, dz_tile);
     else

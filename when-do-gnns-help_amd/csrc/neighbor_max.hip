@@ -29,6 +29,7 @@
 // No LDS, no atomics, no scratch.
 #include <cstdint>
 
+#include "wave_rows.h"
 #include "wdg_common.h"
 
 #pragma clang fp contract(off)  // the backward chain is restated bit for bit: nothing may be fused
@@ -38,45 +39,10 @@ namespace {
 using namespace wdg;
 
 constexpr int NM_WAVES = 4;           // rows per workgroup, both kernels
-constexpr int NM_MAX_JOBS = 65535;    // a job per grid z
 constexpr int NM_PANEL = 256;         // columns per wave: four per lane
 constexpr int NM_MAX_PANELS = 65535;  // gridDim.y
 constexpr int NB_DEPTH = 8;           // backward: row loads in flight before the first add of a batch
 constexpr int NM_KNOWN_FLAGS = WDG_NEIGHBOR_MAX_MIN;
-
-// the extent of row `row`: false = it lies outside [0, nnz] (the row is left untouched)
-__device__ __forceinline__ bool nm_extent(const global_ptr<const int32_t> rowptr, const int row, const int nnz, int &beg, int &end) {
-    beg = __builtin_amdgcn_readfirstlane(rowptr[row]);
-    end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-    return beg >= 0 && beg <= end && end <= nnz;
-}
-__device__ __forceinline__ bool nm_aligned16(const void *p, const int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(ld * 4)) & 15) == 0;
-}
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-
-// four consecutive 32-bit words of a row: one 16-byte load (VEC: the wave's decision) or the lane's `live` words one by one, the
-// address of a word it does not have clamped to its last one (that value is never stored)
-template <bool VEC>
-__device__ __forceinline__ void nm_load4(const global_ptr<const uint32_t> p, const int live, uint32_t (&x)[4]) {
-    if (VEC) {
-        const i32x4_t in = *(global_ptr<const i32x4_t>)p;
-        x[0] = in.x, x[1] = in.y, x[2] = in.z, x[3] = in.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = p[min(k, live - 1)];
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void nm_store4(const global_ptr<uint32_t> p, const int live, const uint32_t (&x)[4]) {
-    if (VEC) {
-        *(global_ptr<i32x4_t>)p = i32x4_t{static_cast<int>(x[0]), static_cast<int>(x[1]), static_cast<int>(x[2]), static_cast<int>(x[3])};
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < live) p[k] = x[k];
-    }
-}
 
 // the image of a value under the order: greater = wins.  A NaN: 0xffffffff; -0 and +0 share an image; every other image lies in
 // [0x007fffff, 0xff800000], for the maximum and (complemented) for the minimum alike - never 0, the word of "no entry yet"
@@ -107,7 +73,7 @@ __device__ __forceinline__ void nm_step(const global_ptr<const uint32_t> x_lane,
     if (live > 0) {
         uint32_t x[U][4];
 #pragma unroll
-        for (int u = 0; u < U; ++u) nm_load4<VEC>(x_lane + static_cast<int64_t>(max(j[u], 0)) * ld, live, x[u]);
+        for (int u = 0; u < U; ++u) load4<VEC>(x_lane + static_cast<int64_t>(max(j[u], 0)) * ld, live, x[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t tie = ~static_cast<uint32_t>(j[u]);  // the lower j is the greater word
@@ -146,9 +112,8 @@ __global__ __launch_bounds__(64 * NM_WAVES) void neighbor_max_kernel(const wdg_n
         (job->arg && job->lda < n_feat) || !job->rowptr || !job->Y)
         return;
     int beg, end;
-    if (!nm_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
-    int len = end - beg;
-    if (job->kept_len) len = min(__builtin_amdgcn_readfirstlane(to_global(job->kept_len)[row]), len);
+    if (!row_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
+    int len = thinned_row_len(job->kept_len, row, beg, end);
     if (n_cols == 0 || !job->col || !job->X) len = 0;  // (nothing to look at: every entry is skipped)
 
     // the lanes the panel's columns need, rounded up to a power of two: P; the S = 64 / P shares of the row's entries
@@ -167,7 +132,7 @@ __global__ __launch_bounds__(64 * NM_WAVES) void neighbor_max_kernel(const wdg_n
     uint32_t bits[4] = {0, 0, 0, 0};
     const global_ptr<const uint32_t> x_lane = (global_ptr<const uint32_t>)to_global(job->X) + c0;
     const global_ptr<const int32_t> col = to_global(job->col) + beg;
-    const bool vec = (n_feat & 3) == 0 && nm_aligned16(job->X, job->ldx);
+    const bool vec = (n_feat & 3) == 0 && aligned16(job->X, job->ldx);
     if (vec) nm_share<true>(x_lane, job->ldx, live, col, len, n_cols, s, S, minimum, best, bits);
     else nm_share<false>(x_lane, job->ldx, live, col, len, n_cols, s, S, minimum, best, bits);
     // the shares of one column group sit P lanes apart: merged under the same order (EVERY lane is active here)
@@ -189,12 +154,12 @@ __global__ __launch_bounds__(64 * NM_WAVES) void neighbor_max_kernel(const wdg_n
         bits[k] = best[k] ? bits[k] : 0u;                                  // ... its bits, or +0
     }
     const global_ptr<uint32_t> y = (global_ptr<uint32_t>)to_global(job->Y) + static_cast<int64_t>(row) * job->ldy + c0;
-    if ((n_feat & 3) == 0 && nm_aligned16(job->Y, job->ldy)) nm_store4<true>(y, live, bits);
-    else nm_store4<false>(y, live, bits);
+    if ((n_feat & 3) == 0 && aligned16(job->Y, job->ldy)) store4<true>(y, live, bits);
+    else store4<false>(y, live, bits);
     if (job->arg) {
         const global_ptr<uint32_t> a = (global_ptr<uint32_t>)to_global(job->arg) + static_cast<int64_t>(row) * job->lda + c0;
-        if ((n_feat & 3) == 0 && nm_aligned16(job->arg, job->lda)) nm_store4<true>(a, live, who);
-        else nm_store4<false>(a, live, who);
+        if ((n_feat & 3) == 0 && aligned16(job->arg, job->lda)) store4<true>(a, live, who);
+        else store4<false>(a, live, who);
     }
 }
 
@@ -219,8 +184,8 @@ __device__ __forceinline__ void nb_batch(const global_ptr<const uint32_t> g_lane
         uint32_t a[D][4], g[D][4];
 #pragma unroll
         for (int u = 0; u < D; ++u) {
-            nm_load4<VEC_A>(a_lane + static_cast<int64_t>(max(r[u], 0)) * lda, live, a[u]);
-            nm_load4<VEC_G>(g_lane + static_cast<int64_t>(max(r[u], 0)) * ldg, live, g[u]);
+            load4<VEC_A>(a_lane + static_cast<int64_t>(max(r[u], 0)) * lda, live, a[u]);
+            load4<VEC_G>(g_lane + static_cast<int64_t>(max(r[u], 0)) * ldg, live, g[u]);
         }
 #pragma unroll
         for (int u = 0; u < D; ++u)
@@ -282,9 +247,8 @@ __global__ __launch_bounds__(64 * NM_WAVES) void neighbor_max_backward_kernel(co
         !job->rowptr || !job->D)
         return;
     int beg, end;
-    if (!nm_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
-    int len = end - beg;
-    if (job->kept_len) len = min(__builtin_amdgcn_readfirstlane(to_global(job->kept_len)[row]), len);
+    if (!row_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
+    int len = thinned_row_len(job->kept_len, row, beg, end);
     if (n_src == 0 || !job->col || !job->G || !job->arg) len = 0;  // (nothing to gather from: every entry is skipped)
 
     // the forward pass's lane groups: P lanes hold the panel's columns, share t of the S = 64 / P requests every S-th entry's pieces
@@ -296,7 +260,7 @@ __global__ __launch_bounds__(64 * NM_WAVES) void neighbor_max_backward_kernel(co
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     const global_ptr<const uint32_t> g_lane = (global_ptr<const uint32_t>)to_global(job->G) + c0, a_lane = (global_ptr<const uint32_t>)to_global(job->arg) + c0;
     const global_ptr<const int32_t> col = to_global(job->col) + beg;
-    const bool vg = (n_feat & 3) == 0 && nm_aligned16(job->G, job->ldg), va = (n_feat & 3) == 0 && nm_aligned16(job->arg, job->lda);
+    const bool vg = (n_feat & 3) == 0 && aligned16(job->G, job->ldg), va = (n_feat & 3) == 0 && aligned16(job->arg, job->lda);
     const uint32_t me = static_cast<uint32_t>(row);
     if (vg && va) nb_row<true, true>(g_lane, job->ldg, a_lane, job->lda, live, col, len, n_src, lane, me, c, s, P, S, acc);
     else if (vg) nb_row<true, false>(g_lane, job->ldg, a_lane, job->lda, live, col, len, n_src, lane, me, c, s, P, S, acc);
@@ -305,21 +269,14 @@ __global__ __launch_bounds__(64 * NM_WAVES) void neighbor_max_backward_kernel(co
     if (s != 0 || live == 0) return;
     const uint32_t out[4] = {__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]), __float_as_uint(acc[3])};
     const global_ptr<uint32_t> d = (global_ptr<uint32_t>)to_global(job->D) + static_cast<int64_t>(row) * job->ldd + c0;
-    if ((n_feat & 3) == 0 && nm_aligned16(job->D, job->ldd)) nm_store4<true>(d, live, out);
-    else nm_store4<false>(d, live, out);
+    if ((n_feat & 3) == 0 && aligned16(job->D, job->ldd)) store4<true>(d, live, out);
+    else store4<false>(d, live, out);
 }
 
-// the table-level refusals of the launch entries and of the host predicates (what = the entry's name in the message)
-int nm_check_table(const char *what, const void *jobs, int32_t n_jobs) {
-    WDG_REQUIRE(n_jobs >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= NM_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, NM_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
-}
-// ... and of the counts both launch entries take -> the grid, or nothing to launch
+// the refusals of the counts both launch entries take -> the grid, or nothing to launch
 int nm_check_counts(const char *what, const void *jobs, int32_t n_jobs, int32_t max_rows, int32_t max_feat) {
     WDG_REQUIRE(max_rows >= 0 && max_feat >= 0, "%s: negative count", what);
-    if (const int rc = nm_check_table(what, jobs, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table(what, jobs, n_jobs)) return rc;
     WDG_REQUIRE(wdg::ceil_div(max_feat, NM_PANEL) <= NM_MAX_PANELS, "%s: %d columns; one launch takes %d", what, max_feat, NM_PANEL * NM_MAX_PANELS);
     return WDG_OK;
 }
@@ -340,7 +297,7 @@ extern "C" int wdg_neighbor_max_batched_f32(const wdg_neighbor_max_job *jobs_dev
 // The per-job part of the contract, for a table the caller still holds on the host (neighbor_max.NeighborMaxBatch calls this on the
 // table it is about to upload).
 extern "C" int wdg_neighbor_max_check_jobs(const wdg_neighbor_max_job *jobs_host, int32_t n_jobs) {
-    if (const int rc = nm_check_table("neighbor_max_check_jobs", jobs_host, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("neighbor_max_check_jobs", jobs_host, n_jobs)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_neighbor_max_job &j = jobs_host[i];
         WDG_REQUIRE(j.n_rows >= 0 && j.n_cols >= 0 && j.n_feat >= 0 && j.nnz >= 0, "neighbor_max_check_jobs: job %d has a negative shape", i);
@@ -365,7 +322,7 @@ extern "C" int wdg_neighbor_max_backward_batched_f32(const wdg_neighbor_max_back
 }
 
 extern "C" int wdg_neighbor_max_backward_check_jobs(const wdg_neighbor_max_backward_job *jobs_host, int32_t n_jobs) {
-    if (const int rc = nm_check_table("neighbor_max_backward_check_jobs", jobs_host, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("neighbor_max_backward_check_jobs", jobs_host, n_jobs)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_neighbor_max_backward_job &j = jobs_host[i];
         WDG_REQUIRE(j.n_rows >= 0 && j.n_src >= 0 && j.n_feat >= 0 && j.nnz >= 0, "neighbor_max_backward_check_jobs: job %d has a negative shape", i);

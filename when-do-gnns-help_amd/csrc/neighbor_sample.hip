@@ -22,13 +22,14 @@
 // far as a 64-bit word (2^64 - 1 = nothing; the candidate set of csrc/topk_rows.hip, restated ascending).  A chunk is looked at only
 // when a ballot finds a key below the current fanout-th; up to NS_INSERT_MAX entrants are inserted one by one (a scalar lane read, a
 // ballot for the rank, one lane shift), more are sorted (bitonic) and merged.  Both routes leave ranks 0 .. fanout - 1 exact, so which
-// one ran cannot show.  A second pass over the chunks recomputes each key, compares with tau and compacts (ballot + mbcnt, as
-// drop_edge_thin_kernel).  There is NO multi-wave path for a hub row.
+// one ran cannot show.  A second pass over the chunks recomputes each key, compares with tau and compacts (ballot + mbcnt:
+// csrc/wave_rows.h's thinned row, the one drop_edge_thin_kernel writes).  There is NO multi-wave path for a hub row.
 // Phase 1: the same compaction pass over the transposed pattern with tau read per entry.
 #include <cmath>
 #include <cstdint>
 
 #include "philox.h"
+#include "wave_rows.h"
 #include "wdg_common.h"
 
 namespace {
@@ -36,7 +37,6 @@ namespace {
 using namespace wdg;
 
 constexpr int NS_WAVES = 4;         // rows per workgroup
-constexpr int NS_MAX_JOBS = 65535;  // a job per grid y
 constexpr int NS_INSERT_MAX = 8;    // up to this many entrants of a chunk are inserted one by one; more: sort + merge
 constexpr unsigned NS_KEY_TAG = 0x53414745u;  // "SAGE": the second key word of the step key
 constexpr int NS_KNOWN_FLAGS = WDG_NEIGHBOR_SAMPLE_TRANSPOSED | WDG_NEIGHBOR_SAMPLE_KEEP_DIAGONAL | WDG_NEIGHBOR_SAMPLE_NORM_SYM;
@@ -51,12 +51,6 @@ __host__ __device__ __forceinline__ bool ns_malformed(const J job) {
            (forward && (job->fanout < 1 || job->fanout > WDG_NEIGHBOR_SAMPLE_MAX_FANOUT)) ||
            (job->n > 0 && (!job->rowptr || !job->kept_len || (forward && !job->tau))) ||
            (job->n > 0 && job->nnz > 0 && (!job->col || !job->kept_col || job->kept_col == job->col || !job->tau));
-}
-
-__device__ __forceinline__ bool ns_extent(const global_ptr<const int32_t> rowptr, const int row, const int nnz, int &beg, int &end) {
-    beg = __builtin_amdgcn_readfirstlane(rowptr[row]);
-    end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-    return beg >= 0 && beg <= end && end <= nnz;
 }
 
 // the key of the entry with FORWARD coordinates (i, j)
@@ -123,21 +117,9 @@ __device__ __forceinline__ void ns_compact(const desc_ptr<wdg_neighbor_sample_jo
             const uint64_t t = valid ? tau[j] : 0ull;
             keep = valid && ((diagonal && j == row) || ns_key(static_cast<unsigned>(j), static_cast<unsigned>(row), k0, k1) <= t);
         }
-        const unsigned long long votes = __ballot(keep);
-        const int before = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(votes >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(votes), 0u));
-        if (keep) kept_col[beg + kept + before] = j;  // (beg + kept + before < e0 + lane + 1 <= end: inside the row's extent)
-        kept += __popcll(votes);
+        thinned_row_keep(kept_col, beg, kept, keep, j);
     }
-    for (int q = beg + kept + lane; q < end; q += 64) kept_col[q] = -1;
-    if (lane == 0) {
-        to_global(job->kept_len)[row] = kept;
-        if (job->scale) {
-            const float c = static_cast<float>(kept);
-            float d = (flags & WDG_NEIGHBOR_SAMPLE_NORM_SYM) ? 1.0f / sqrtf(c) : 1.0f / c;  // the F32 path of wdg_degree_norm on the count
-            if (isinf(d)) d = 0.f;
-            to_global(job->scale)[row] = d;
-        }
-    }
+    thinned_row_finish(job, kept_col, row, beg, end, kept, lane, flags & WDG_NEIGHBOR_SAMPLE_NORM_SYM);
 }
 
 template <bool FORWARD>
@@ -151,7 +133,7 @@ __global__ __launch_bounds__(64 * NS_WAVES) void neighbor_sample_kernel(const wd
     if (row >= min(job->n, max_rows)) return;  // (wave-uniform, like everything up to the chunk loops)
     if (ns_malformed(job)) return;             // a job outside the contract is left untouched (the host predicate refuses it)
     int beg, end;
-    if (!ns_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
+    if (!row_extent(to_global(job->rowptr), row, nnz, beg, end)) return;
 
     const philox_words key = philox4x32_10_words(*step_dev, job->stream, seed, NS_KEY_TAG);  // the step key: uniform
     const unsigned k0 = key.w[0], k1 = key.w[1];
@@ -190,19 +172,12 @@ __global__ __launch_bounds__(64 * NS_WAVES) void neighbor_sample_kernel(const wd
     ns_compact<FORWARD>(job, row, beg, end, lane, k0, k1, kth);
 }
 
-int ns_check_table(const char *what, const void *jobs, int32_t n_jobs) {
-    WDG_REQUIRE(n_jobs >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= NS_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, NS_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
-}
-
 }  // namespace
 
 extern "C" int wdg_neighbor_sample_batched(const wdg_neighbor_sample_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t phase, uint32_t seed,
                                            const uint32_t *step_dev, wdg_stream_t stream) {
     WDG_REQUIRE(max_rows >= 0, "neighbor_sample_batched: negative count");
-    if (const int rc = ns_check_table("neighbor_sample_batched", jobs_dev, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("neighbor_sample_batched", jobs_dev, n_jobs)) return rc;
     WDG_REQUIRE(phase == 0 || phase == 1, "neighbor_sample_batched: unknown phase %d; 0 (select and thin the forward jobs) and 1 (thin the transposed jobs) are defined", phase);
     WDG_REQUIRE(step_dev != nullptr, "neighbor_sample_batched: null step word");
     if (n_jobs == 0 || max_rows == 0) return WDG_OK;
@@ -218,7 +193,7 @@ extern "C" int wdg_neighbor_sample_batched(const wdg_neighbor_sample_job *jobs_d
 // The per-job part of the contract, for a table the caller still holds on the host (neighbor_sample.NeighborSampleBatch calls this on the
 // table it is about to upload).
 extern "C" int wdg_neighbor_sample_check_jobs(const wdg_neighbor_sample_job *jobs_host, int32_t n_jobs) {
-    if (const int rc = ns_check_table("neighbor_sample_check_jobs", jobs_host, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("neighbor_sample_check_jobs", jobs_host, n_jobs)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_neighbor_sample_job &j = jobs_host[i];
         const bool forward = !(j.flags & WDG_NEIGHBOR_SAMPLE_TRANSPOSED);

@@ -293,9 +293,7 @@ extern "C" int64_t wdg_poly_filter_partials_len(int32_t n, int32_t cols, int32_t
 
 // The per-job part of the contract, on the table the caller still holds on the host (train.PolyFilterBatch calls this before it uploads).
 extern "C" int wdg_poly_filter_check_jobs(const wdg_poly_filter_job *jobs_host, int32_t n_jobs) {
-    WDG_REQUIRE(n_jobs >= 0, "poly_filter_check_jobs: negative count");
-    WDG_REQUIRE(n_jobs <= PF_MAX_JOBS, "poly_filter_check_jobs: %d jobs; one launch takes %d", n_jobs, PF_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs_host != nullptr, "poly_filter_check_jobs: null job table");
+    if (const int rc = wdg::check_job_table("poly_filter_check_jobs", jobs_host, n_jobs, PF_MAX_JOBS)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_poly_filter_job &j = jobs_host[i];
         WDG_REQUIRE(j.n >= 0 && j.nnz >= 0 && j.cols >= 0, "poly_filter_check_jobs: job %d has a negative shape", i);
@@ -325,9 +323,8 @@ extern "C" int wdg_poly_filter_check_jobs(const wdg_poly_filter_job *jobs_host, 
 
 extern "C" int wdg_poly_filter_batched_f32(const wdg_poly_filter_job *jobs_dev, int32_t n_jobs, int32_t max_groups, int32_t max_floats, int32_t max_dot_rows,
                                            wdg_stream_t stream) {
-    WDG_REQUIRE(n_jobs >= 0 && max_groups >= 0 && max_floats >= 0 && max_dot_rows >= 0, "poly_filter_batched: negative count");
-    WDG_REQUIRE(n_jobs <= PF_MAX_JOBS, "poly_filter_batched: %d jobs; one launch takes %d", n_jobs, PF_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs_dev != nullptr, "poly_filter_batched: null job table");
+    WDG_REQUIRE(max_groups >= 0 && max_floats >= 0 && max_dot_rows >= 0, "poly_filter_batched: negative count");
+    if (const int rc = wdg::check_job_table("poly_filter_batched", jobs_dev, n_jobs, PF_MAX_JOBS)) return rc;
     WDG_REQUIRE(max_dot_rows <= WDG_POLY_FILTER_MAX_ORDER + 1, "poly_filter_batched: %d rows of dots; an order has at most %d", max_dot_rows,
                 WDG_POLY_FILTER_MAX_ORDER + 1);
     WDG_REQUIRE(static_cast<int64_t>(max_floats) * 8 <= WDG_POLY_FILTER_LDS_BYTES, "poly_filter_batched: %d floats per image; two of them must fit in %d bytes of LDS",

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void signed_att_forward_kernel(const
     const int i = blockIdx.x * GT_WAVES + wave;
     if (i >= s.n || !job->rowptr || !job->H || !job->S || !job->out || (s.nnz > 0 && (!job->col || !job->alpha))) return;  // (wave-uniform)
     int beg, end;
-    if (!gt_extent(job->rowptr, i, s.nnz, beg, end)) return;
+    if (!row_extent(to_global(job->rowptr), i, s.nnz, beg, end)) return;
     const int heads = s.heads, n = job->n;
     const global_ptr<const int32_t> col = to_global(job->col);
     const global_ptr<const float> S = to_global(job->S), H = to_global(job->H), col_scale = to_global(job->col_scale);
@@ -88,9 +88,9 @@ __global__ __launch_bounds__(64 * GT_WAVES) void signed_att_forward_kernel(const
             const global_ptr<const float> ri = to_global(job->res) + static_cast<int64_t>(i) * job->ld_res + lc.c0;
             float r[4];
             if (gt_wave_vec(job->res, job->ld_res, s.cols))
-                gt_load4<true>(ri, lc.live, r);
+                load4<true>(ri, lc.live, r);
             else
-                gt_load4<false>(ri, lc.live, r);
+                load4<false>(ri, lc.live, r);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = fmaf(eps, r[k], acc[k]);
         }
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void signed_att_backward_rows_kernel
     const int i = blockIdx.x * GT_WAVES + wave;
     if (i >= s.n || !gt_has_backward(job, s.nnz)) return;  // (wave-uniform)
     int beg, end;
-    if (!gt_extent(job->rowptr, i, s.nnz, beg, end)) return;
+    if (!row_extent(to_global(job->rowptr), i, s.nnz, beg, end)) return;
     const int heads = s.heads, w = s.w, cols = s.cols, n = job->n;
     const global_ptr<const int32_t> col = to_global(job->col);
     const global_ptr<const float> S = to_global(job->S), H = to_global(job->H), col_scale = to_global(job->col_scale);
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void signed_att_backward_rows_kernel
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (vec_h) {
-                    gt_load4<true>(row + min(c + 4 * u, cols - 4), 4, x[u]);
+                    load4<true>(row + min(c + 4 * u, cols - 4), 4, x[u]);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) x[u][k] = row[min(c + 4 * u + k, cols - 1)];
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64 * GT_WAVES) void signed_att_backward_cols_kernel
     const int j = blockIdx.x * GT_WAVES + wave;
     if (j >= s.n || !gt_has_backward(job, s.nnz)) return;  // (wave-uniform)
     int beg, end;
-    if (!gt_extent(job->t_rowptr, j, s.nnz, beg, end)) return;
+    if (!row_extent(to_global(job->t_rowptr), j, s.nnz, beg, end)) return;
     gt_transposed_row(job, s, j, beg, end, lane, stage_all[wave]);
 }
 

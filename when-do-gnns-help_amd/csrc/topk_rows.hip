@@ -182,20 +182,13 @@ __global__ __launch_bounds__(TK_THREADS) void row_rnorm_kernel(const float *__re
     }
 }
 
-int tk_table_checks(const char *what, const wdg_topk_job *jobs, int32_t n_jobs) {
-    WDG_REQUIRE(n_jobs >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= TK_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, TK_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
-    return WDG_OK;
-}
-
 unsigned tk_groups(const int64_t rows) { return static_cast<unsigned>(std::min<int64_t>(wdg::ceil_div(rows, TK_WAVES), TK_MAX_GROUPS)); }
 
 }  // namespace
 
 // The per-job part of the contract, on the table the caller still holds on the host (graphs.TopkRowsBatch calls this before it uploads).
 extern "C" int wdg_topk_rows_check_jobs(const wdg_topk_job *jobs_host, int32_t n_jobs) {
-    if (const int rc = tk_table_checks("topk_rows_check_jobs", jobs_host, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("topk_rows_check_jobs", jobs_host, n_jobs, TK_MAX_JOBS)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_topk_job &j = jobs_host[i];
         WDG_REQUIRE(j.k >= 1 && j.k <= WDG_TOPK_MAX_K, "topk_rows_check_jobs: job %d has k = %d; 1 .. %d are supported", i, j.k, WDG_TOPK_MAX_K);
@@ -212,7 +205,7 @@ extern "C" int wdg_topk_rows_check_jobs(const wdg_topk_job *jobs_host, int32_t n
 }
 
 extern "C" int wdg_topk_rows_batched_f32(const wdg_topk_job *jobs_dev, int32_t n_jobs, int32_t max_rows, wdg_stream_t stream) {
-    if (const int rc = tk_table_checks("topk_rows_batched_f32", jobs_dev, n_jobs)) return rc;
+    if (const int rc = wdg::check_job_table("topk_rows_batched_f32", jobs_dev, n_jobs, TK_MAX_JOBS)) return rc;
     WDG_REQUIRE(max_rows >= 0, "topk_rows_batched_f32: negative max_rows");
     if (n_jobs == 0 || max_rows == 0) return WDG_OK;
     hipLaunchKernelGGL(topk_rows_kernel, dim3(tk_groups(max_rows), static_cast<unsigned>(n_jobs)), dim3(TK_THREADS), 0, wdg::as_stream(stream), jobs_dev);

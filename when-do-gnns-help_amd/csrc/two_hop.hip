@@ -196,9 +196,8 @@ __global__ __launch_bounds__(TH_THREADS) void two_hop_fill_kernel(const wdg_two_
 }
 
 int th_launch_checks(const char *what, const wdg_two_hop_job *jobs_dev, int32_t n_jobs, int32_t max_rows) {
-    WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0, "%s: negative count", what);
-    WDG_REQUIRE(n_jobs <= TH_MAX_JOBS, "%s: %d jobs; one launch takes %d", what, n_jobs, TH_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs_dev != nullptr, "%s: null job table", what);
+    WDG_REQUIRE(max_rows >= 0, "%s: negative count", what);
+    if (const int rc = wdg::check_job_table(what, jobs_dev, n_jobs, TH_MAX_JOBS)) return rc;
     if (max_rows > WDG_TWO_HOP_MAX_ROWS)
         return wdg::fail(WDG_ERR_UNSUPPORTED, "%s: %d rows; a wave's bitmap holds at most %d columns in LDS", what, max_rows, WDG_TWO_HOP_MAX_ROWS);
     return WDG_OK;
@@ -223,9 +222,7 @@ extern "C" int32_t wdg_csr_two_hop_max_rows(void) { return WDG_TWO_HOP_MAX_ROWS;
 
 // The per-job part of the contract, on the table the caller still holds on the host (graphs.TwoHopBatch calls this before it uploads).
 extern "C" int wdg_csr_two_hop_check_jobs(const wdg_two_hop_job *jobs_host, int32_t n_jobs) {
-    WDG_REQUIRE(n_jobs >= 0, "csr_two_hop_check_jobs: negative count");
-    WDG_REQUIRE(n_jobs <= TH_MAX_JOBS, "csr_two_hop_check_jobs: %d jobs; one launch takes %d", n_jobs, TH_MAX_JOBS);
-    WDG_REQUIRE(n_jobs == 0 || jobs_host != nullptr, "csr_two_hop_check_jobs: null job table");
+    if (const int rc = wdg::check_job_table("csr_two_hop_check_jobs", jobs_host, n_jobs, TH_MAX_JOBS)) return rc;
     for (int32_t i = 0; i < n_jobs; ++i) {
         const wdg_two_hop_job &j = jobs_host[i];
         WDG_REQUIRE(j.n >= 0, "csr_two_hop_check_jobs: job %d has a negative n", i);

@@ -94,3 +94,14 @@ __device__ __forceinline__ void store_f32x4(global_ptr<float> p, const float4 &a
     do {                                                        \
         if (!(cond)) return wdg::fail(WDG_ERR_INVALID, __VA_ARGS__); \
     } while (0)
+
+namespace wdg {
+// The table-level refusals of a batched entry and of its host predicate, in this order (what = the entry's name in the message;
+// max_jobs: a job per grid y or z).  A unit's other counts stay in the unit, in front of or behind the call.
+inline int check_job_table(const char *what, const void *jobs, int32_t n_jobs, int32_t max_jobs = 65535) {
+    WDG_REQUIRE(n_jobs >= 0, "%s: negative count", what);
+    WDG_REQUIRE(n_jobs <= max_jobs, "%s: %d jobs; one launch takes %d", what, n_jobs, max_jobs);
+    WDG_REQUIRE(n_jobs == 0 || jobs != nullptr, "%s: null job table", what);
+    return WDG_OK;
+}
+}  // namespace wdg
