@@ -400,10 +400,18 @@ int wdg_spmm_narrow_bf16(const wdg_spmm_job *job_host, const int32_t *part_ptr, 
  * 16 lanes per row, sources read IN PLACE - every job's X must be 16-byte aligned with ldx a multiple of 4 and >= 4 (>= 8
  * for EVERY job of a table with max_feat > 4, a job of fewer features included: the launch picks its width from max_feat and
  * then reads two float4 of every source row of every job, else one).  flags: WDG_SPMM_ANY_VAL,
- * WDG_SPMM_ANY_COL_SCALE.  Sums in a fixed order (lane layout + fixed butterfly).
+ * WDG_SPMM_ANY_COL_SCALE, WDG_NARROW_SLAB_OK.  Sums in a fixed order (lane layout + fixed butterfly).
+ * WDG_NARROW_SLAB_OK (the entry cannot see n_cols: it is in the device table) promises that EVERY job is pattern-only (no values, no
+ * column scale) and that its sources fit one LDS slab: n_cols x (max_feat > 4 ? 32 : 16) bytes <= WDG_NARROW_SLAB_BYTES.  Such a
+ * table runs on a kernel whose workgroups copy their job's source rows into LDS and gather from there - the same sums in the same
+ * order, bit for bit (WDG_NARROW_SLAB=0 in the environment: the in-place kernel; a table flagged by mistake gets wrong numbers).
+ * wdg_spmm_narrow_slab_launches: how many launches of this process took the slab kernel (tests ask which kernel ran).
  */
+#define WDG_NARROW_SLAB_OK 64
+#define WDG_NARROW_SLAB_BYTES (72 * 1024) /* two slabs fit the 160 KB of a CU's LDS */
 int wdg_spmm_narrow_batched_f32(const wdg_spmm_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat, int flags,
                                 wdg_stream_t stream);
+int64_t wdg_spmm_narrow_slab_launches(void);
 
 /*
  * The batched aggregation on the quad-row kernel (every job carries its SELL-16 copy).  The caller lays the jobs'

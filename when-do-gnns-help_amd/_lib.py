@@ -104,6 +104,7 @@ SIGNATURES = {
     "wdg_spmm_narrow_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wdg_spmm_narrow_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wdg_spmm_narrow_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int, c_void_p]),
+    "wdg_spmm_narrow_slab_launches": (c_int64, []),
     "wdg_spmm_quad_batched_clocked_f32": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int, c_void_p,
                                                   c_void_p]),
     "wdg_spmm_quad_workgroups": (c_int32, [c_int32, c_int32, c_int]),

@@ -17,6 +17,7 @@ ABLATE_BITS = 0  # diagnostics: scripts/dev/ablate_*.py set this to wdg_spmm_job
 
 
 # ------------------------------------------------------------------------------------------- aggregation
+SPMM_NARROW_SLAB_OK, NARROW_SLAB_BYTES = 64, 72 * 1024  # WDG_NARROW_SLAB_OK, WDG_NARROW_SLAB_BYTES of include/wdg.h
 NARROW_MIN_ENTRIES = int(os.environ.get("WDG_NARROW_MIN_ENTRIES", 1 << 15))  # below: the general families (round 2: 2^18 - chameleon's
 # 65 019 entries then took the gather kernel for its C = 5 logits aggregation: 85 us against the narrow kernel's 20)
 
@@ -343,6 +344,8 @@ class SpmmBatch:
         self.flags = (SPMM_ANY_VAL if any_val else 0) | (SPMM_DMA_OK if dma_ok else 0)
         if any(e[4] is not None for e in entries):
             self.flags |= SPMM_ANY_COL_SCALE
+        if self.narrow and not self.flags & (SPMM_ANY_VAL | SPMM_ANY_COL_SCALE) and self.max_cols * (32 if self.max_feat > 4 else 16) <= NARROW_SLAB_BYTES:
+            self.flags |= SPMM_NARROW_SLAB_OK  # pattern-only jobs whose source rows fit an LDS slab: gathered from LDS, the same bits
         if self.quad:
             if all(_y_span(e[2], e[0].n_rows) < (1 << 30) and e[0].quad["chunks"] < (1 << 22) - 2 and e[0].quad["split"] for e in entries):
                 self.flags |= SPMM_SMALL_OFFSETS

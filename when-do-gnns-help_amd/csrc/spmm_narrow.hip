@@ -15,6 +15,8 @@
 //     not keep, so after log2 G steps lane 2f holds feature f's total - 8 + 4 + 2 + 1 cross-lane moves per row instead
 //     of 8 log2 G - and the lanes store the row's F floats.  The order of the sums is fixed by the lane layout.
 #include <algorithm>
+#include <atomic>
+#include <cstdlib>
 
 #include "wdg_common.h"
 
@@ -287,7 +289,155 @@ __global__ __launch_bounds__(N_THREADS) void spmm_narrow_batched_kernel(const wd
     if (live && !(lane & 1) && feat < F) to_global(job->Y)[static_cast<int64_t>(row) * job->ldy + feat] = total * (rs ? rs[row] : 1.f);
 }
 
+// ---- the same table, pattern-only jobs whose sources fit WDG_NARROW_SLAB_BYTES (the sweep's logits: 2000 x 32 B = 64 KB): a workgroup
+//      takes a contiguous row range of one job and copies the job's source rows - their first one or two float4, `ldx` apart - into
+//      LDS first, so a stored entry costs LDS reads instead of an L2 request.  Order of a workgroup's memory operations: the bounds
+//      of all its rows, the copy's loads, the first SLAB_AHEAD indices per lane of every pass (they wait for the bounds only: the
+//      copy's loads stay in flight behind them), the copy's LDS writes, one barrier, the row scales, the gathers.  A row's sum is
+//      spmm_narrow_batched_kernel's operation for operation: lane s of 16 adds the entries b + s, b + s + 16, ... to +0.f in that
+//      order (low float4, high float4), narrow_reduce16, the row scale, the same store.
+constexpr int SLAB_THREADS = 1024;  // one workgroup per CU (the 76 registers a lane's loads in flight take leave room for 16 waves, not 32):
+                                    // 10.6 us on the sweep's table against 13.3 us for two workgroups of 512 threads per CU
+constexpr int SLAB_WAVES = 4;       // waves per SIMD the registers allow
+constexpr int SLAB_ROWS = 512;      // rows whose bounds and first indices a workgroup holds in registers at once; longer ranges repeat
+constexpr int SLAB_AHEAD = 5;       // indices per lane requested before the barrier: rows of <= 80 entries; longer rows go on in a loop
+constexpr int SLAB_PIECES = WDG_NARROW_SLAB_BYTES / 16;
+
+// Every load in front of the barrier is issued by every lane, without a branch: a lane with nothing to load reads a valid word
+// instead (its range's last row, the copy's last piece, rowptr[0]) and drops it.  Loads that a branch may skip would make the count
+// of outstanding loads unknown to the compiler, and each wait would then have to be for all of them.
+template <bool WIDE, int THREADS, bool FIRST>
+__device__ __forceinline__ void narrow_slab_rows(desc_ptr<wdg_spmm_job> job, f32x4_t *slab, int r0, int row_end) {
+    constexpr int RPP = THREADS / 16, PASSES = SLAB_ROWS / RPP, STAGE = (SLAB_PIECES + THREADS - 1) / THREADS, LDQ = WIDE ? 2 : 1;
+    const global_ptr<const int32_t> rowptr = to_global(job->rowptr), col = to_global(job->col);
+    const global_ptr<const float> rs = to_global(job->row_scale);
+    const int tid = threadIdx.x, lane = tid & 63, sub = tid & 15;
+    const global_ptr<const int32_t> col_or_valid = col ? col : rowptr;  // (a job without entries may have no col: index 0 of rowptr)
+    int b[PASSES], left[PASSES], idx[PASSES][SLAB_AHEAD];  // left: the row's entries from this lane's first on (<= 0: none)
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        const int valid_row = std::min(r0 + p * RPP + (tid >> 4), row_end - 1);
+        b[p] = rowptr[valid_row], left[p] = rowptr[valid_row + 1];
+    }
+    f32x4_t piece[STAGE];
+    int n_pieces = 0;
+    // in LDS the low float4s of all source rows come first, the high ones behind them: a lane's 16 bytes then fall into one of 16
+    // bank windows by its column, not one of 8
+    const int n_cols = job->n_cols, hi_at = std::min(n_cols, SLAB_PIECES / 2);
+    if (FIRST) {
+        // (a table flagged by mistake computes nonsense, inside its LDS; a job without columns has no X: its own descriptor is read)
+        n_pieces = std::min(n_cols * LDQ, SLAB_PIECES);
+        const global_ptr<const f32x4_t> X = n_pieces > 0 ? (global_ptr<const f32x4_t>)to_global(static_cast<const float *>(job->X))
+                                                         : (global_ptr<const f32x4_t>)job;
+        const int64_t ldq = job->ldx / 4;
+#pragma unroll
+        for (int u = 0; u < STAGE; ++u) {
+            const int q = std::max(std::min(tid + u * THREADS, n_pieces - 1), 0);
+            piece[u] = WIDE ? X[ldq * (q >> 1) + (q & 1)] : X[ldq * q];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (the compiler's own order puts the copy's LDS writes, and with them its wait, in front of the index loads)
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        left[p] = r0 + p * RPP + (tid >> 4) < row_end ? left[p] - b[p] - sub : 0;
+#pragma unroll
+        for (int u = 0; u < SLAB_AHEAD; ++u) idx[p][u] = col_or_valid[16 * u < left[p] ? b[p] + sub + 16 * u : 0];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (FIRST) {
+#pragma unroll
+        for (int u = 0; u < STAGE; ++u) {  // (lanes past the last piece write it once more)
+            const int q = std::max(std::min(tid + u * THREADS, n_pieces - 1), 0);
+            slab[WIDE ? (q >> 1) + (q & 1) * hi_at : q] = piece[u];
+        }
+        __syncthreads();
+    }
+    float scale[PASSES];  // (requested here, where the copy's registers are free again; read after a row's butterfly)
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        const float v = (rs ? rs : (global_ptr<const float>)rowptr)[std::min(r0 + p * RPP + (tid >> 4), row_end - 1)];
+        scale[p] = rs ? v : 1.f;
+    }
+    const int F = job->n_feat, feat = (lane >> 1) & 7;
+    const global_ptr<float> Y = to_global(job->Y);
+    const int64_t ldy = job->ldy;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        if (r0 + p * RPP >= row_end) break;  // (uniform)
+        Acc8 a;
+#pragma unroll
+        for (int f = 0; f < 8; ++f) a.v[f] = 0.f;
+#pragma unroll
+        for (int u = 0; u < SLAB_AHEAD; ++u) {
+            if (16 * u < left[p]) {  // (a wave whose four rows all end before this entry skips it)
+                const int c = idx[p][u];
+                const f32x4_t lo = slab[c], hi = WIDE ? slab[hi_at + c] : lo;
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    a.v[f] = a.v[f] + lo[f];
+                    if (WIDE) a.v[4 + f] = a.v[4 + f] + hi[f];
+                }
+            }
+        }
+        for (int k = b[p] + sub + 16 * SLAB_AHEAD; k < b[p] + sub + left[p]; k += 16) {
+            const int c = col[k];
+            const f32x4_t lo = slab[c], hi = WIDE ? slab[hi_at + c] : lo;
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                a.v[f] = a.v[f] + lo[f];
+                if (WIDE) a.v[4 + f] = a.v[4 + f] + hi[f];
+            }
+        }
+        const float total = narrow_reduce16(a, lane);
+        const int row = r0 + p * RPP + (tid >> 4);
+        if (row < row_end && !(lane & 1) && feat < F) Y[static_cast<int64_t>(row) * ldy + feat] = total * scale[p];
+    }
+}
+
+template <bool WIDE, int THREADS>
+__global__ __launch_bounds__(THREADS, SLAB_WAVES) void spmm_narrow_slab_batched_kernel(const wdg_spmm_job *__restrict__ jobs, int parts, int rows_per_wg,
+                                                                           int n_items) {
+    extern __shared__ f32x4_t narrow_slab[];
+    const int64_t item = xcd_contiguous_item(blockIdx.x, n_items);  // (the parts of a job copy the same sources: one L2)
+    if (item >= n_items) return;
+    const desc_ptr<wdg_spmm_job> job = (desc_ptr<wdg_spmm_job>)(jobs + item / parts);
+    const int64_t first = (item % parts) * rows_per_wg;
+    const int N = job->n_rows;
+    if (first >= N) return;  // (uniform: jobs smaller than the launch bound)
+    const int r0 = static_cast<int>(first), row_end = static_cast<int>(std::min<int64_t>(N, first + rows_per_wg));
+    narrow_slab_rows<WIDE, THREADS, true>(job, narrow_slab, r0, row_end);
+    for (int r = r0 + SLAB_ROWS; r < row_end; r += SLAB_ROWS) narrow_slab_rows<WIDE, THREADS, false>(job, narrow_slab, r, row_end);
+}
+
 constexpr int64_t N_PART_BYTES = 3 << 20;  // 3 MiB of packed sources per part: what an XCD's 4-MiB L2 keeps beside the streams (168 114 columns: 2 parts 133 us, 1 part 151, 4 parts 141)
+
+
+std::atomic<int64_t> slab_launches{0};
+
+// The slab kernel's geometry: every workgroup resident at once where the table allows it.  A CU holds as many workgroups as slabs fit
+// its LDS (two) and as its registers allow (one of 1024 threads); the rows of a job are cut into as many parts as that gives every
+// job (the sweep's 50 jobs of 2000 rows on 256 CUs: 5 parts of 400).
+template <bool WIDE>
+int narrow_slab_launch(const wdg_spmm_job *jobs_dev, int n_jobs, int max_rows, hipStream_t st) {
+    constexpr int THREADS = SLAB_THREADS;
+    const void *kernel = reinterpret_cast<const void *>(spmm_narrow_slab_batched_kernel<WIDE, THREADS>);
+    static thread_local int configured_dev = -1;
+    if (configured_dev != wdg::current_device()) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WDG_NARROW_SLAB_BYTES) != hipSuccess)
+            return wdg::fail(WDG_ERR_LAUNCH, "spmm_narrow_batched: cannot raise the dynamic LDS limit");
+        configured_dev = wdg::current_device();
+    }
+    const int64_t slots = static_cast<int64_t>(std::max(wdg_device_cus(), 8)) * std::min(kLdsBytes / WDG_NARROW_SLAB_BYTES, SLAB_WAVES * 256 / THREADS);
+    const int64_t want_parts = std::max<int64_t>(1, slots / n_jobs);
+    const int rows_per_wg = static_cast<int>(std::max<int64_t>(wdg::ceil_div(max_rows, want_parts), THREADS / 16));
+    const int parts = static_cast<int>(wdg::ceil_div(max_rows, rows_per_wg));
+    const int64_t n_items = static_cast<int64_t>(n_jobs) * parts;
+    WDG_REQUIRE(wdg::xcd_grid_size(n_items) < (1ll << 31), "spmm_narrow_batched: grid too large");
+    hipLaunchKernelGGL((spmm_narrow_slab_batched_kernel<WIDE, THREADS>), dim3(static_cast<unsigned>(wdg::xcd_grid_size(n_items))), dim3(THREADS),
+                       WDG_NARROW_SLAB_BYTES, st, jobs_dev, parts, rows_per_wg, static_cast<int>(n_items));
+    slab_launches.fetch_add(1, std::memory_order_relaxed);
+    return wdg::check_launch("spmm_narrow_slab_batched_kernel");
+}
 
 }  // namespace
 
@@ -388,12 +538,20 @@ int wdg_spmm_narrow_bf16(const wdg_spmm_job *job_host, const int32_t *part_ptr, 
     return narrow_launch(job_host, true, part_ptr, workspace, workspace_bytes, stream);
 }
 
+int64_t wdg_spmm_narrow_slab_launches(void) { return slab_launches.load(std::memory_order_relaxed); }
+
 int wdg_spmm_narrow_batched_f32(const wdg_spmm_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat, int flags,
                                 wdg_stream_t stream) {
     WDG_REQUIRE(n_jobs >= 0 && max_rows >= 0 && max_feat >= 0, "spmm_narrow_batched: negative size");
     if (n_jobs == 0 || max_rows == 0 || max_feat == 0) return WDG_OK;
     WDG_REQUIRE(jobs_dev != nullptr, "spmm_narrow_batched: null job table");
     if (max_feat > 8) return wdg::fail(WDG_ERR_UNSUPPORTED, "spmm_narrow_batched: more than 8 features");
+    if ((flags & WDG_NARROW_SLAB_OK) && !(flags & (WDG_SPMM_ANY_VAL | WDG_SPMM_ANY_COL_SCALE))) {
+        const char *s = getenv("WDG_NARROW_SLAB");
+        if (!(s && s[0] == '0' && s[1] == 0))
+            return max_feat > 4 ? narrow_slab_launch<true>(jobs_dev, n_jobs, max_rows, wdg::as_stream(stream))
+                                : narrow_slab_launch<false>(jobs_dev, n_jobs, max_rows, wdg::as_stream(stream));
+    }
     const int blocks_per_job = static_cast<int>(wdg::ceil_div(max_rows, 16));
     WDG_REQUIRE(static_cast<int64_t>(blocks_per_job) * n_jobs < (1ll << 31), "spmm_narrow_batched: grid too large");
     const dim3 grid(static_cast<unsigned>(blocks_per_job) * n_jobs);
