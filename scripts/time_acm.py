@@ -19,29 +19,12 @@ document next to --out and the parent joins them.  (`device` in the document is 
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _shard_batch, _time_arms, best_of, flags, run_step, run_steps, write  # noqa: E402
+
 GROUPS = {"acm": ("acm_sgc", "acm_gcn"), "base": ("sgc", "gcn")}
-
-
-def best_of(fn, runs):
-    """one warm-up, then the fastest of `runs` calls of fn() -> seconds"""
-    fn()
-    return min(fn() for _ in range(runs))
-
-
-def _shard_batch():
-    import torch
-    from wdg_amd import sweep, synth
-    jobs = sweep.make_jobs(synth.H_LEVELS_10_K10, range(5), k=10, n_nodes=2000)
-    sb = sweep.SweepBatch(jobs, n_feat=500, gcn_hidden=0)
-    for s_ in sb.x:
-        lab = synth.regular_graph(2000, 5, 10, 0.5, s_)[2]
-        sb.x[s_].copy_(torch.from_numpy(synth.features(2000, 500, s_, labels=lab)))
-    return jobs, sb
 
 
 def step_shard(a):
@@ -99,29 +82,21 @@ def step_kernel(a):
         arms = {"wdg_acm_mix_batched_f32 (1 launch)": batch.launch, "wdg_acm_mix_backward_batched_f32 (2 launches)": batch.launch_backward,
                 "kernels, forward + backward": lambda: (batch.launch(), batch.launch_backward()),
                 "torch forward": torch_forward, "torch forward + backward": torch_both}
-        times = {k: [] for k in arms}
-        for rnd in range(a.kernel_rounds + 1):  # (round 0 warms up)
-            for name, fn in arms.items():
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                t0.record()
-                for _ in range(a.kernel_iters):
-                    fn()
-                t1.record()
-                torch.cuda.synchronize()
-                if rnd:
-                    times[name].append(t0.elapsed_time(t1) / a.kernel_iters * 1e3)
+        times = _time_arms(arms, a.kernel_rounds, a.kernel_iters)
         mb = J * n * w * 4 / 1e6
         key = f"width {w}, activation {'on' if relu else 'off'}"
         out[key] = {"bytes": f"forward: 4 reads of {mb:.1f} MB, out and out_t of {mb:.1f} MB each, aux {J * n * 32 / 1e6:.1f} MB; "
                              f"backward: 5 reads and 3 writes of {mb:.1f} MB, aux"}
-        for name, ts in times.items():
-            out[key][name] = {"median_us": statistics.median(ts), "min_us": min(ts), "max_us": max(ts)}
+        for name, summary in times.items():
+            out[key][name] = summary
             print(json.dumps({key: {name: out[key][name]}}), flush=True)
     return out
 
 
-def main():
+STEP_FNS = {"shard": step_shard, "kernel": step_kernel}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=200)
@@ -131,40 +106,24 @@ def main():
     ap.add_argument("--group", choices=sorted(GROUPS), help="(with --step shard) the kinds the step times")
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "acm_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    """acm, base, acm, base - one process each -, then the kernel"""
+    return [Step(f"shard {group} {i}", "shard", 300, ("--group", group)) for i in (1, 2) for group in ("acm", "base")] + [Step("kernel", "kernel", 240)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"shard": step_shard, "kernel": step_kernel}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    # (name in the document, step, group, seconds its child may take)
-    steps = [("shard acm 1", "shard", "acm", 300), ("shard base 1", "shard", "base", 300), ("shard acm 2", "shard", "acm", 300),
-             ("shard base 2", "shard", "base", 300), ("kernel", "kernel", None, 240)]
-    doc = {"order": [s[0] for s in steps]}
-    for i, (name, step, group, limit) in enumerate(steps):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part,
-               "--runs", str(a.runs), "--epochs", str(a.epochs), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        if group:
-            cmd += ["--group", group]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):  # (a step that failed after writing: nothing is left beside --out)
-                os.remove(part)
-            sys.exit(f"step {name!r} ended with status {rc}: stopping")
-        doc[name] = json.load(open(part))
-        os.remove(part)
+        return run_step(a, STEP_FNS)
+    parts = run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "kernel_rounds", "kernel_iters"), a.out)
+    doc = dict({"order": [key for key, _ in parts]}, **dict(parts))
     best = lambda group, kind: min(doc[f"shard {group} {i}"][kind]["ms_per_epoch"] for i in (1, 2))  # noqa: E731
     doc["ms per captured epoch, best of each side's two processes"] = {k: best(g, k) for g, kinds in GROUPS.items() for k in kinds}
     doc["acm over base"] = {"acm_sgc / sgc": best("acm", "acm_sgc") / best("base", "sgc"), "acm_gcn / gcn": best("acm", "acm_gcn") / best("base", "gcn")}
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    write(a.out, doc)
 
 
 if __name__ == "__main__":

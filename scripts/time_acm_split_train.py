@@ -18,24 +18,13 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _cora, _time_arms, flags, run_step, run_steps, write  # noqa: E402
+
 KINDS = ("acm_sgc", "acm_gcn")
 R, HIDDEN = 10, 64
-
-
-def _cora():
-    import numpy as np
-    import torch
-    g = dict(np.load(os.path.join(ROOT, "tests", "golden", "real_cora.npz")))
-    n, f = int(g["n_nodes"]), int(g["n_feat"])
-    x = np.zeros((n, f), np.float32)
-    x[np.repeat(np.arange(n), np.diff(g["feat_indptr"])), g["feat_indices"]] = g["featn_data"]
-    adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([g["adj_row"], g["adj_col"]]).astype(np.int64)), torch.from_numpy(g["adj_val"]), (n, n))
-    return adj, torch.from_numpy(x), g["labels"].astype(np.int64)
 
 
 def step_epoch(a):
@@ -109,19 +98,7 @@ def step_kernel(a):
         same = all(bool((sl(po["out"], r) == sl(so["out"], r)).all()) for r in range(reps))
         res = {"operand MB": n * w * 4 / 1e6, "forward outputs equal elementwise": same}
         for direction, pair in arms.items():
-            times = {k: [] for k in pair}
-            for rd in range(a.kernel_rounds + 1):  # (round 0 warms up)
-                for name, fn in pair.items():
-                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    t0.record()
-                    for _ in range(a.kernel_iters):
-                        fn()
-                    t1.record()
-                    torch.cuda.synchronize()
-                    if rd:
-                        times[name].append(t0.elapsed_time(t1) / a.kernel_iters * 1e3)
-            res[direction] = {name: {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)} for name, t in times.items()}
+            res[direction] = _time_arms(pair, a.kernel_rounds, a.kernel_iters)
             med = [res[direction][k]["median_us"] for k in pair]
             res[direction]["packed over R jobs"] = med[0] / med[1]
         out[f"R = {reps}"] = res
@@ -132,7 +109,10 @@ def step_kernel(a):
     return out
 
 
-def main():
+STEP_FNS = {"epoch": step_epoch, "kernel": step_kernel}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=100)
@@ -141,32 +121,18 @@ def main():
     ap.add_argument("--step", choices=["epoch", "kernel"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "acm_split_train_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("kernel", "kernel", 180), Step("epoch", "epoch", 420)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"epoch": step_epoch, "kernel": step_kernel}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for i, (step, limit) in enumerate((("kernel", 180), ("epoch", 420))):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--runs", str(a.runs),
-               "--epochs", str(a.epochs), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "kernel_rounds", "kernel_iters"), a.out)))
 
 
 if __name__ == "__main__":

@@ -25,44 +25,12 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _arm_rounds, _cora, _epoch_rounds, _ms_per_epoch, _summary, flags, run_step, run_steps, write  # noqa: E402
+
 HIDDEN = 64
-
-
-def _cora(tree):
-    import numpy as np
-    import torch
-    g = dict(np.load(os.path.join(tree, "tests", "golden", "real_cora.npz")))
-    n, f = int(g["n_nodes"]), int(g["n_feat"])
-    x = np.zeros((n, f), np.float32)
-    x[np.repeat(np.arange(n), np.diff(g["feat_indptr"])), g["feat_indices"]] = g["featn_data"]
-    adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([g["adj_row"], g["adj_col"]]).astype(np.int64)), torch.from_numpy(g["adj_val"]), (n, n))
-    return adj, torch.from_numpy(x), g["labels"].astype(np.int64)
-
-
-def _rounds(arms, rounds, iters):
-    """{name: callable} -> {name: [us per call]}: interleaved rounds (round 0 warms up), events around `iters` back-to-back calls"""
-    import torch
-    times = {k: [] for k in arms}
-    for rd in range(rounds + 1):
-        for arm, fn in arms.items():
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0.record()
-            for _ in range(iters):
-                fn()
-            t1.record()
-            torch.cuda.synchronize()
-            if rd:
-                times[arm].append(t0.elapsed_time(t1) / iters * 1e3)
-    return times
-
-
-def _summary(t):
-    return {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)}
 
 
 def step_kernel(a):
@@ -102,12 +70,12 @@ def step_kernel(a):
     torch.cuda.synchronize()
     same = bool(np.array_equal(table.u2_of[0].cpu().numpy(), want_u2) and np.array_equal(table.pairs_of[0].cpu().numpy(), want_pairs))
     same_comp = bool(np.array_equal(out_u2.cpu().numpy(), want_u2))
-    times = _rounds({"AucBatch.launch": lambda: table.launch(step), "torch.sort + midranks": composition}, a.kernel_rounds, a.kernel_iters)
+    times = _arm_rounds({"AucBatch.launch": lambda: table.launch(step), "torch.sort + midranks": composition}, a.kernel_rounds, a.kernel_iters)
     out = {"workload": f"n = {n}, R = {R}, 50/25/25 splits, 20 % positives, normal margins; bins_log2 = {train.AUC_BINS_LOG2}; "
                        f"{a.kernel_rounds} interleaved rounds of {a.kernel_iters} back-to-back calls, device time from events; us per call",
            "the launch equals the restatement": same, "the composition equals the restatement": same_comp}
     for arm, t in times.items():
-        out[arm] = _summary(t)
+        out[arm] = _summary(t, "us")
     k, c = out["AucBatch.launch"], out["torch.sort + midranks"]
     out["gate"] = {"rule": "the launch's median <= the composition's median", "launch median_us": k["median_us"],
                    "composition median_us": c["median_us"], "passed": same and same_comp and k["median_us"] <= c["median_us"]}
@@ -117,17 +85,11 @@ def step_kernel(a):
     tied = ops.AucBatch([dict(logits=ties, labels=lab_d, split=split_d, cs=cs)])
     tied.launch(step)
     torch.cuda.synchronize()
-    t = _rounds({"all ties": lambda: tied.launch(step)}, 3, 2)["all ties"]
-    out["all ties"] = dict(_summary(t), **{"u2 == pairs": bool(torch.equal(tied.u2, tied.pairs)),
+    t = _arm_rounds({"all ties": lambda: tied.launch(step)}, 3, 2)["all ties"]
+    out["all ties"] = dict(_summary(t, "us"), **{"u2 == pairs": bool(torch.equal(tied.u2, tied.pairs)),
                                            "comparisons per launch": int(want_pairs.sum())})
     print(json.dumps({"all ties": out["all ties"]}), flush=True)
     return out
-
-
-def _ms_per_epoch(stb, a):
-    stb.run(epochs=a.epochs, capture=True)
-    rounds = [stb.run(epochs=a.epochs, capture=True)["seconds"] / a.epochs * 1e3 for _ in range(a.runs)]
-    return {"median_ms": statistics.median(rounds), "min_ms": min(rounds), "max_ms": max(rounds), "rounds_ms": rounds}
 
 
 def step_switch(a):
@@ -141,12 +103,7 @@ def step_switch(a):
     perms = [rng.permutation(n) for _ in range(10)]
     masks = split_train.masks_from_indices(n, [(p[:int(0.6 * n)], p[int(0.6 * n):int(0.8 * n)], p[int(0.8 * n):]) for p in perms])
     arms = {sel: split_train.SplitTrainBatch(adj, x, labels, masks, kind="sgc", seed=1, select=sel) for sel in ("val_hits", "val_auc")}
-    for stb in arms.values():
-        stb.run(epochs=a.epochs, capture=True)
-    rounds = {sel: [] for sel in arms}
-    for _ in range(a.runs):
-        for sel, stb in arms.items():
-            rounds[sel].append(stb.run(epochs=a.epochs, capture=True)["seconds"] / a.epochs * 1e3)
+    rounds = _epoch_rounds({sel: (lambda rnd, stb=stb: stb.run(epochs=a.epochs, capture=True)) for sel, stb in arms.items()}, a.runs, a.epochs, warmup=1)
     off, on = statistics.median(rounds["val_hits"]), statistics.median(rounds["val_auc"])
     out = {"workload": f"captured 'sgc' epochs of ten replicas on the Cora fixture's graph, labels = (class 2 against the rest: {labels.mean():.3f} positives); per "
                        f"arm the median of {a.runs} rounds of {a.epochs} epochs, alternating round by round after a warm-up round; ms per epoch",
@@ -168,7 +125,10 @@ def step_default(a):
     return out
 
 
-def main():
+STEP_FNS = {"kernel": step_kernel, "switch": step_switch, "default": step_default}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=100)
@@ -180,32 +140,19 @@ def main():
     ap.add_argument("--tree", default=ROOT, help="(with --step) the checkout whose package is imported")
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "auc_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    trees = ([os.path.abspath(a.parent), ROOT] if a.parent else [ROOT]) * a.processes  # parent, new, parent, new, ...
+    return [Step("kernel", "kernel", 300, tree=ROOT), Step("switch", "switch", 240, tree=ROOT)] + [Step("default", "default", 240, tree=tree) for tree in trees]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, os.path.abspath(a.tree))
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"kernel": step_kernel, "switch": step_switch, "default": step_default}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    steps = [("kernel", ROOT, 300), ("switch", ROOT, 240)]
-    for tree in ([a.parent, ROOT] if a.parent else [ROOT]) * a.processes:
-        steps.append(("default", os.path.abspath(tree), 240))
-    parts = []
-    for i, (step, tree, limit) in enumerate(steps):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--tree", tree, "--part", part, "--runs", str(a.runs),
-               "--epochs", str(a.epochs), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        parts.append((step, json.load(open(part))))
-        os.remove(part)
+        return run_step(a, STEP_FNS, a.tree)
+    parts = run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "kernel_rounds", "kernel_iters"), a.out)
     doc = {"kernel": parts[0][1], "switch": parts[1][1]}
     runs = [p for s, p in parts if s == "default"]
     default = {"workload": f"Cora fixture, ten splits, 'gcn', hidden {HIDDEN}, default select; per process the median of {a.runs} rounds of {a.epochs} captured "
@@ -218,9 +165,7 @@ def main():
                                 "parent_ms": old, "new_ms": new, "bound_ms": bound, "passed": statistics.median(new) <= bound,
                                 "new over parent": statistics.median(new) / statistics.median(old)}
     doc["default"] = default
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    write(a.out, doc)
     failed = ([] if doc["kernel"]["gate"]["passed"] else ["the kernel gate"]) + \
              (["the default-path yardstick"] if a.parent and not default["yardstick"]["passed"] else [])
     for what in failed:

@@ -10,7 +10,7 @@ the accuracy of GCN-2 and GCNII-8 under it.  None of the shapes is required to w
                 step: torch.rand over the stored entries, CsrGraph.with_values(mask), ops.degree_norm(use_values=True), ops.spmm with the
                 values (per graph; its forward half only - the backward half would gather the mask through transpose_positions).
             The arms alternate inside every round; device time from events around --iters back-to-back calls after a warm-up round; median,
-            minimum and maximum over the rounds (the method of scripts/time_gat.py).
+            minimum and maximum over the rounds (the method of scripts/_timing.py).
   epochs    the captured models.train_eval_graphed epoch (training step + evaluation) of models.GCN2 and of models.GCNII (L = 8, 32), hidden
             64, on Cora's topology with 128 generated features and 7 generated classes: models.DropEdgeAdj(p = 0.5) against the plain
             models.NormAdj, seconds / epochs of 200 replays, the two alternating, three rounds.
@@ -25,28 +25,23 @@ that fails: nothing more runs on the device after a step that faults, aborts or 
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, Step, _accuracy_sweep, _cora_coo, _fixture_graph, _generated_features, _shard, _time_arms, _time_epochs, flags, run_step, run_steps, write  # noqa: E402
 
 P, W, SEED = 0.5, 64, 1
+LIMITS = {"kernels": 240, "epochs": 240, "accuracy": 420}
 
 
-def _fixture_graph(name):
-    import numpy as np
+def _looped(name):
     from wdg_amd import ops
-    z = _golden(name)
-    return ops.CsrGraph.from_coo(z["adj_row"].astype(np.int64), z["adj_col"].astype(np.int64), int(z["n_nodes"]), None, ops.COO_ADD_SELF_LOOPS | ops.COO_BINARISE)
+    return [_fixture_graph(name, ops.COO_ADD_SELF_LOOPS)]
 
 
-def _shard():
-    from wdg_amd import ops, synth
-    specs = [(2000, 5, 10, synth.out_degree(10, 0.2), seed) for seed in range(50)]
-    return [g.rebuild(ops.COO_ADD_SELF_LOOPS) for g in ops.GraphBatch.generated(specs, flags=0, quad=False).graphs]
+def _looped_shard():
+    from wdg_amd import ops
+    return [g.rebuild(ops.COO_ADD_SELF_LOOPS) for g in _shard()]
 
 
 def _topology_case(graphs, widths, a, iters):
@@ -88,74 +83,55 @@ def _topology_case(graphs, widths, a, iters):
 def step_kernels(a):
     out = {"workload": f"{a.rounds} interleaved rounds of {a.iters} back-to-back calls (the shard: a fifth of that) after a warm-up round, device time from "
                        "events; us per call"}
-    for name, graphs, widths, iters in (("cora", lambda: [_fixture_graph("real_cora")], (64, 7), a.iters),
-                                        ("shard of 50 graphs (N = 2000, k = 10, h = 0.2)", _shard, (64, 7), max(1, a.iters // 5)),
-                                        ("squirrel (the hub case)", lambda: [_fixture_graph("topo_squirrel")], (5,), a.iters)):
+    for name, graphs, widths, iters in (("cora", lambda: _looped("real_cora"), (64, 7), a.iters),
+                                        ("shard of 50 graphs (N = 2000, k = 10, h = 0.2)", _looped_shard, (64, 7), max(1, a.iters // 5)),
+                                        ("squirrel (the hub case)", lambda: _looped("topo_squirrel"), (5,), a.iters)):
         out[name] = _topology_case(graphs(), widths, a, iters)
         print(json.dumps({name: out[name]}), flush=True)
     return out
 
 
-def _cora_coo():
-    import numpy as np
-    import torch
-    cora = _golden("real_cora")
-    n = int(cora["n_nodes"])
-    return torch.sparse_coo_tensor(torch.from_numpy(np.vstack([cora["adj_row"], cora["adj_col"]]).astype(np.int64)), torch.ones(len(cora["adj_row"])), (n, n)), n
-
-
 def step_epochs(a):
     import torch
-    from wdg_amd import models, synth
+    from wdg_amd import models
     coo, n = _cora_coo()
-    lab = (torch.arange(n) % 7).numpy()
-    x, labels = torch.from_numpy(synth.features(n, 128, 0, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
+    x, labels = _generated_features(n, 7)
     out = {"workload": "models.train_eval_graphed(capture=True), 200 epochs on Cora's topology (symmetric scales), 128 generated features, 7 generated "
                        "classes, hidden 64, dropout 0.5 with a DeviceDropout: ms per epoch (training step + evaluation, two graph replays), three "
                        "alternating rounds"}
     makers = {"GCN2": lambda: models.GCN2(128, 7, W, 0.5, models.DeviceDropout(1, 0)), "GCNII, L = 8": lambda: models.GCNII(128, 7, W, 8, dropout_rng=models.DeviceDropout(1, 0)),
               "GCNII, L = 32": lambda: models.GCNII(128, 7, W, 32, dropout_rng=models.DeviceDropout(1, 0))}
     for name, mk in makers.items():
-        times = {"DropEdgeAdj(p = 0.5)": [], "NormAdj": []}
-        for _ in range(3):
-            for arm in times:
-                adj = models.DropEdgeAdj(coo, P, SEED, symmetric=1) if arm != "NormAdj" else models.NormAdj(coo, symmetric=1)
+        def arm(mk_adj):
+            def run(rnd):
+                adj = mk_adj()
                 torch.manual_seed(0)
-                res = models.train_eval_graphed(mk(), adj, x, labels, epochs=200, lr=0.01, capture=True)
-                times[arm].append(res["seconds"] / 200 * 1e3)
-        out[name] = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in times.items()}
+                return models.train_eval_graphed(mk(), adj, x, labels, epochs=200, lr=0.01, capture=True)
+            return run
+
+        out[name] = _time_epochs({"DropEdgeAdj(p = 0.5)": arm(lambda: models.DropEdgeAdj(coo, P, SEED, symmetric=1)),
+                                  "NormAdj": arm(lambda: models.NormAdj(coo, symmetric=1))}, 3, 200)
         print(json.dumps({name: out[name]}), flush=True)
     return out
 
 
 def step_accuracy(a):
-    import numpy as np
-    import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; validation "
                        "and test accuracy at the selected epoch, seeds 0 - 4; p = 0 is the plain NormAdj; untuned"}
-    makers = (("GCN2 (hidden 64)", lambda: models.GCN2(f, c), 0), ("GCNII (hidden 64, 8 layers, alpha 0.1, theta 0.5)", lambda: models.GCNII(f, c), 1))
-    for h in (0.2, 0.5, 0.9):
-        accs = {(name, p): ([], []) for name, _, _ in makers for p in (0.0, 0.3, 0.5)}
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
-            for name, mk, sym in makers:
-                for p in (0.0, 0.3, 0.5):
-                    adj = models.DropEdgeAdj(coo, p, SEED, stream=seed, symmetric=sym) if p else models.NormAdj(coo, symmetric=sym)
-                    torch.manual_seed(seed)
-                    res = models.train_eval_graphed(mk(), adj, x, labels, epochs=80, lr=0.05, capture=True)
-                    accs[(name, p)][0].append(res["val_acc"])
-                    accs[(name, p)][1].append(res["test_acc"])
-        out[f"h = {h}"] = {f"{name}, p = {p}": {"val_mean": float(np.mean(v)), "test_mean": float(np.mean(t)), "val": [round(float(q), 4) for q in v],
-                                                "test": [round(float(q), 4) for q in t]} for (name, p), (v, t) in accs.items()}
-        print(json.dumps({f"h = {h}": out[f"h = {h}"]}), flush=True)
+
+    def adj_at(p, sym):
+        return lambda coo, seed: models.DropEdgeAdj(coo, p, SEED, stream=seed, symmetric=sym) if p else models.NormAdj(coo, symmetric=sym)
+
+    out.update(_accuracy_sweep([(f"{name}, p = {p}", mk, adj_at(p, sym)) for name, mk, sym in (
+        ("GCN2 (hidden 64)", models.GCN2, 0), ("GCNII (hidden 64, 8 layers, alpha 0.1, theta 0.5)", models.GCNII, 1)) for p in (0.0, 0.3, 0.5)]))
     return out
 
 
-def main():
+STEP_FNS = {"kernels": step_kernels, "epochs": step_epochs, "accuracy": step_accuracy}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
@@ -163,37 +139,18 @@ def main():
     ap.add_argument("--step", choices=["kernels", "epochs", "accuracy"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "drop_edge_timing.json"))
-    a = ap.parse_args()
-    steps = {"kernels": step_kernels, "epochs": step_epochs, "accuracy": step_accuracy}
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step(step, step, LIMITS[step]) for step in a.steps.split(",")]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = steps[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    limits = {"kernels": 240, "epochs": 240, "accuracy": 420}
-    doc = {}
-    for step in a.steps.split(","):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limits[step]), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            with open(a.out, "w") as f:  # (what the earlier steps measured stays)
-                json.dump(dict(doc, **{step: f"not measured: the step ended with status {rc}"}), f, indent=1)
-                f.write("\n")
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters"), a.out)))
 
 
 if __name__ == "__main__":

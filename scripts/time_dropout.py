@@ -18,29 +18,12 @@ document next to --out and the parent joins them.  (`device` in the document is 
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _shard_batch, _summary, best_of, flags, run_step, run_steps, write  # noqa: E402
+
 KINDS = ("gcn", "mlp2")
-
-
-def best_of(fn, runs):
-    """one warm-up, then the fastest of `runs` calls of fn() -> seconds"""
-    fn()
-    return min(fn() for _ in range(runs))
-
-
-def _shard_batch():
-    import torch
-    from wdg_amd import sweep, synth
-    jobs = sweep.make_jobs(synth.H_LEVELS_10_K10, range(5), k=10, n_nodes=2000)
-    sb = sweep.SweepBatch(jobs, n_feat=500, gcn_hidden=0)
-    for s_ in sb.x:
-        lab = synth.regular_graph(2000, 5, 10, 0.5, s_)[2]
-        sb.x[s_].copy_(torch.from_numpy(synth.features(2000, 500, s_, labels=lab)))
-    return jobs, sb
 
 
 def step_shard(a):
@@ -94,12 +77,15 @@ def step_kernel(a):
     out = {"workload": f"{J} hidden layers of {n} x {hid} fp32 ({mb:.1f} MB read, {2 * mb:.1f} MB written with the transposed output), "
                        f"{a.kernel_rounds} interleaved rounds of {a.kernel_iters} back-to-back calls, device time from events; us per call"}
     for name, t in times.items():
-        out[name] = {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)}
+        out[name] = _summary(t, "us")
         print(json.dumps({name: out[name]}), flush=True)
     return out
 
 
-def main():
+STEP_FNS = {"shard": step_shard, "kernel": step_kernel}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=200)
@@ -111,45 +97,29 @@ def main():
     ap.add_argument("--parent", action="store_true", help="(with --step shard) --root is the parent commit: no dropout argument")
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dropout_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    """new, parent, new, parent - one process each, the parent's only with --parent-root -, then the kernel"""
+    new = lambda i: Step(f"shard new {i}", "shard", 420, tree=ROOT)  # noqa: E731
+    old = lambda i: Step(f"shard parent {i}", "shard", 420, ("--parent",), a.parent_root)  # noqa: E731
+    return ([new(1), old(1), new(2), old(2)] if a.parent_root else [new(1)]) + [Step("kernel", "kernel", 300, tree=ROOT)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, os.path.abspath(a.root))
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"shard": step_shard, "kernel": step_kernel}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    # (name in the document, step, checkout, seconds its child may take)
-    steps = [("shard new 1", "shard", ROOT, 420)]
-    if a.parent_root:
-        steps += [("shard parent 1", "shard", a.parent_root, 420), ("shard new 2", "shard", ROOT, 420), ("shard parent 2", "shard", a.parent_root, 420)]
-    steps.append(("kernel", "kernel", ROOT, 300))
-    doc = {"order": [s[0] for s in steps]}
-    for i, (name, step, root, limit) in enumerate(steps):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--root", root, "--part", part,
-               "--runs", str(a.runs), "--epochs", str(a.epochs), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        if root != ROOT:
-            cmd.append("--parent")
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):  # (a step that failed after writing: nothing is left beside --out)
-                os.remove(part)
-            sys.exit(f"step {name!r} ended with status {rc}: stopping")
-        doc[name] = json.load(open(part))
-        os.remove(part)
+        return run_step(a, STEP_FNS, a.root)
+    parts = run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "kernel_rounds", "kernel_iters"), a.out, tree_flag="--root")
+    doc = dict({"order": [key for key, _ in parts]}, **dict(parts))
     if a.parent_root:  # the unchanged path, new over parent: the best of each side's two processes
         doc["dropout=0.0 new over parent"] = {
             kind: min(doc[f"shard new {i}"][kind]["dropout=0.0"]["ms_per_epoch"] for i in (1, 2))
             / min(doc[f"shard parent {i}"][kind]["dropout=0.0"]["ms_per_epoch"] for i in (1, 2)) for kind in KINDS}
     doc["dropout=0.5 over dropout=0.0"] = {kind: doc["shard new 1"][kind]["dropout=0.5"]["ms_per_epoch"] / doc["shard new 1"][kind]["dropout=0.0"]["ms_per_epoch"]
                                            for kind in KINDS}
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    write(a.out, doc)
 
 
 if __name__ == "__main__":

@@ -20,22 +20,12 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _accuracy_sweep, _cora_problem, _golden, _plan, _time_arms, _time_epochs, flags, run_step, run_steps, write  # noqa: E402
+
 SLOPE = 0.2
-
-
-def _golden(name):
-    import numpy as np
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", name + ".npz")))
-
-
-def _plan(g):
-    gt = g.transpose()
-    return dict(graph=g, graph_t=gt, t_pos=g.transpose_positions(gt))
 
 
 def torch_layer(rows, col, n, h, s, heads):
@@ -48,23 +38,6 @@ def torch_layer(rows, col, n, h, s, heads):
     z = torch.zeros((n, heads), device=h.device).index_add_(0, rows, q)
     alpha = q / z[rows]
     return torch.zeros((n, heads, w), device=h.device).index_add_(0, rows, alpha[:, :, None] * h.view(n, heads, w)[col]).view(n, heads * w)
-
-
-def _time_arms(arms, rounds, iters):
-    import torch
-    times = {k: [] for k in arms}
-    for rnd in range(rounds + 1):  # (round 0 warms up)
-        for name, fn in arms.items():
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0.record()
-            for _ in range(iters):
-                fn()
-            t1.record()
-            torch.cuda.synchronize()
-            if rnd:
-                times[name].append(t0.elapsed_time(t1) / iters * 1e3)
-    return {k: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for k, v in times.items()}
 
 
 def _layer_case(graphs, heads, w, a):
@@ -128,60 +101,38 @@ def step_layers(a):
     return out
 
 
-def _cora_problem():
-    import numpy as np
-    import torch
-    from wdg_amd import models
-    g = _golden("real_cora")
-    n, f = int(g["n_nodes"]), int(g["n_feat"])
-    x = np.zeros((n, f), np.float32)
-    x[np.repeat(np.arange(n), np.diff(g["feat_indptr"])), g["feat_indices"]] = g["featn_data"]
-    adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([g["adj_row"], g["adj_col"]]).astype(np.int64)), torch.from_numpy(g["adj_val"]), (n, n))
-    return models.NormAdj(adj), torch.from_numpy(x).cuda(), torch.from_numpy(g["labels"].astype(np.int64)), f, int(g["labels"].max()) + 1
-
-
 def step_epoch(a):
     import torch
     from wdg_amd import models
     adj, x, labels, f, c = _cora_problem()
     makers = {"GAT2 (8 x 8)": lambda: models.GAT2(f, c, dropout_rng=models.DeviceDropout(3)), "GCN2 (hidden 64)": lambda: models.GCN2(f, c, dropout_rng=models.DeviceDropout(3))}
-    times = {k: [] for k in makers}
-    for rnd in range(a.epoch_rounds + 1):  # (round 0 warms up)
-        for name, mk in makers.items():
+
+    def arm(mk):
+        def run(rnd):
             torch.manual_seed(rnd)
-            res = models.train_eval_graphed(mk(), adj, x, labels, epochs=a.epochs, capture=True)
-            if rnd:
-                times[name].append(res["seconds"] / a.epochs * 1e3)
+            return models.train_eval_graphed(mk(), adj, x, labels, epochs=a.epochs, capture=True)
+        return run
+
     out = {"workload": f"Cora (n = 2708, F = 1433, C = 7), models.train_eval_graphed(capture=True), {a.epochs} epochs, wall clock around the epoch loop "
                        f"with the device drained before and after; {a.epoch_rounds} rounds, the two models alternating; ms per epoch"}
-    for k, v in times.items():
-        out[k] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)}
+    out.update(_time_epochs({k: arm(mk) for k, mk in makers.items()}, a.epoch_rounds, a.epochs, warmup=1))  # (round 0 warms up)
     print(json.dumps(out), flush=True)
     return out
 
 
 def step_accuracy(a):
-    import numpy as np
-    import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
+    adj = lambda coo, seed: models.NormAdj(coo, symmetric=0)  # noqa: E731
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; the "
                        "validation accuracy at the selected epoch, seeds 0 - 4"}
-    for h in (0.2, 0.5, 0.9):
-        accs = {"GAT2 (8 x 8)": [], "GCN2 (hidden 64)": [], "MLP2 (hidden 64)": []}
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            adj = models.NormAdj(torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n)), symmetric=0)
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
-            for name, mk in (("GAT2 (8 x 8)", lambda: models.GAT2(f, c)), ("GCN2 (hidden 64)", lambda: models.GCN2(f, c)), ("MLP2 (hidden 64)", lambda: models.MLP2(f, c))):
-                torch.manual_seed(seed)
-                accs[name].append(models.train_eval_graphed(mk(), adj, x, labels, epochs=80, lr=0.05, capture=True)["val_acc"])
-        out[f"h = {h}"] = {k: {"mean": float(np.mean(v)), "values": [round(float(t), 4) for t in v]} for k, v in accs.items()}
-        print(json.dumps({f"h = {h}": out[f"h = {h}"]}), flush=True)
+    out.update(_accuracy_sweep((("GAT2 (8 x 8)", models.GAT2, adj), ("GCN2 (hidden 64)", models.GCN2, adj), ("MLP2 (hidden 64)", models.MLP2, adj)), test=False))
     return out
 
 
-def main():
+STEP_FNS = {"layers": step_layers, "epoch": step_epoch, "accuracy": step_accuracy}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
@@ -190,32 +141,18 @@ def main():
     ap.add_argument("--step", choices=["layers", "epoch", "accuracy"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gat_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("layers", "layers", 300), Step("epoch", "epoch", 240), Step("accuracy", "accuracy", 420)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"layers": step_layers, "epoch": step_epoch, "accuracy": step_accuracy}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("layers", 300), ("epoch", 240), ("accuracy", 420)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters), "--epochs", str(a.epochs), "--epoch-rounds", str(a.epoch_rounds)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters", "epochs", "epoch_rounds"), a.out)))
 
 
 if __name__ == "__main__":

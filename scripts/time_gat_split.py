@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the stacked GAT runs of gat_split_train.GatSplitTrainBatch and the score kernel of csrc/gat_scores.hip, by
-scripts/time_gat.py's method: interleaved rounds with the arms alternating, median and spread over the rounds.
+scripts/_timing.py's method: interleaved rounds with the arms alternating, median and spread over the rounds.
 
   epoch     the Cora fixture (tests/golden/real_cora.npz: n = 2708, F = 1433, C = 7), ten random 60/20/20 splits, dropout 0.5: the captured
             epoch of ALL ten replicas of "gat2" (8 x 8) beside ten per-split models.train_eval_graphed(capture=True) runs of models.GAT2 -
@@ -18,17 +18,10 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from time_gat import _cora_problem, _time_arms  # noqa: E402
-
-
-def _summary(values, unit):
-    return {f"median_{unit}": statistics.median(values), f"min_{unit}": min(values), f"max_{unit}": max(values)}
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _cora_problem, _summary, _time_arms, flags, run_step, run_steps, write  # noqa: E402
 
 
 def step_epoch(a):
@@ -111,7 +104,10 @@ def step_scores(a):
     return out
 
 
-def main():
+STEP_FNS = {"epoch": step_epoch, "scores": step_scores}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
@@ -120,32 +116,18 @@ def main():
     ap.add_argument("--step", choices=["epoch", "scores"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gat_split_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("scores", "scores", 200), Step("epoch", "epoch", 360)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"epoch": step_epoch, "scores": step_scores}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("scores", 200), ("epoch", 360)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters), "--epochs", str(a.epochs), "--epoch-rounds", str(a.epoch_rounds)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters", "epochs", "epoch_rounds"), a.out)))
 
 
 if __name__ == "__main__":

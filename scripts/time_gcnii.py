@@ -11,7 +11,7 @@ graphs beside GCN-2 and MLP-2 and the largest error / derived bound of every out
             w = 64) as ONE table of 50 jobs, forward and backward, behind 50 ops.spmm calls in both arms - the composition: one torch.lerp
             over the concatenated rows, 50 ops.gemm (a weight per graph), one torch.lerp, one DropoutBatch of 50 entries; its backward
             pass is not composed (not measured).  The arms alternate inside every round; device time from events around --iters
-            back-to-back calls; median, minimum and maximum over the rounds (the method of scripts/time_gat.py).
+            back-to-back calls; median, minimum and maximum over the rounds (the method of scripts/_timing.py).
   epochs    the captured models.train_eval_graphed epoch (training step + evaluation) of models.GCNII and of the composed model, on Cora's
             topology with 128 generated features and 7 generated classes, L = 8 and L = 32, hidden 64: seconds / epochs of 200 replays,
             the two models alternating, three rounds.
@@ -27,13 +27,10 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, Step, _accuracy_sweep, _cora_coo, _generated_features, _time_arms, _time_epochs, flags, run_step, run_steps, write  # noqa: E402
 
 ALPHA, THETA, P, W = 0.1, 0.5, 0.5, 64
 
@@ -67,12 +64,8 @@ def composed_model():
 
 
 def _cora_adj():
-    import torch
     from wdg_amd import models
-    cora = _golden("real_cora")
-    n = int(cora["n_nodes"])
-    import numpy as np
-    coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([cora["adj_row"], cora["adj_col"]]).astype(np.int64)), torch.ones(len(cora["adj_row"])), (n, n))
+    coo, n = _cora_coo()
     return models.NormAdj(coo, symmetric=1), n
 
 
@@ -189,51 +182,32 @@ def step_layers(a):
 
 def step_epochs(a):
     import torch
-    from wdg_amd import models, synth
+    from wdg_amd import models
     adj, n = _cora_adj()
-    lab = (torch.arange(n) % 7).numpy()
-    x, labels = torch.from_numpy(synth.features(n, 128, 0, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
+    x, labels = _generated_features(n, 7)
     out = {"workload": "models.train_eval_graphed(capture=True), 200 epochs on Cora's topology, 128 generated features, 7 generated classes, hidden 64, "
                        "dropout 0.5 with a DeviceDropout: ms per epoch (training step + evaluation, two graph replays), three alternating rounds"}
-    Composed = composed_model()
     for layers in (8, 32):
-        times = {"models.GCNII": [], "composed": []}
-        for _ in range(3):
-            for name, mk in (("models.GCNII", models.GCNII), ("composed", Composed)):
+        def arm(mk):
+            def run(rnd):
                 torch.manual_seed(0)
                 model = mk(128, 7, W, layers, ALPHA, THETA, P, models.DeviceDropout(1, 0))
                 torch.manual_seed(0)
-                res = models.train_eval_graphed(model, adj, x, labels, epochs=200, lr=0.01, capture=True)
-                times[name].append(res["seconds"] / 200 * 1e3)
-        out[f"L = {layers}"] = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in times.items()}
+                return models.train_eval_graphed(model, adj, x, labels, epochs=200, lr=0.01, capture=True)
+            return run
+
+        out[f"L = {layers}"] = _time_epochs({"models.GCNII": arm(models.GCNII), "composed": arm(composed_model())}, 3, 200)
         print(json.dumps({f"L = {layers}": out[f"L = {layers}"]}), flush=True)
     return out
 
 
 def step_accuracy(a):
-    import numpy as np
-    import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; validation "
                        "and test accuracy at the selected epoch, seeds 0 - 4"}
-    for h in (0.2, 0.5, 0.9):
-        makers = (("GCNII (hidden 64, 8 layers, alpha 0.1, theta 0.5)", lambda: models.GCNII(f, c), True), ("GCN2 (hidden 64)", lambda: models.GCN2(f, c), False),
-                  ("MLP2 (hidden 64)", lambda: models.MLP2(f, c), False))
-        accs = {name: ([], []) for name, _, _ in makers}
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
-            adj, adj_sym = models.NormAdj(coo, symmetric=0), models.NormAdj(coo, symmetric=1)
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
-            for name, mk, sym in makers:
-                torch.manual_seed(seed)
-                res = models.train_eval_graphed(mk(), adj_sym if sym else adj, x, labels, epochs=80, lr=0.05, capture=True)
-                accs[name][0].append(res["val_acc"])
-                accs[name][1].append(res["test_acc"])
-        out[f"h = {h}"] = {k: {"val_mean": float(np.mean(v)), "test_mean": float(np.mean(t)), "val": [round(float(q), 4) for q in v],
-                               "test": [round(float(q), 4) for q in t]} for k, (v, t) in accs.items()}
-        print(json.dumps({f"h = {h}": out[f"h = {h}"]}), flush=True)
+    adj = lambda coo, seed: models.NormAdj(coo, symmetric=0)  # noqa: E731
+    out.update(_accuracy_sweep((("GCNII (hidden 64, 8 layers, alpha 0.1, theta 0.5)", models.GCNII, lambda coo, seed: models.NormAdj(coo, symmetric=1)),
+                                ("GCN2 (hidden 64)", models.GCN2, adj), ("MLP2 (hidden 64)", models.MLP2, adj))))
     return out
 
 
@@ -272,40 +246,28 @@ def step_errors(a):
             "largest error / derived bound": {k: round(v, 4) for k, v in worst.items()}}
 
 
-def main():
+STEP_FNS = {"layers": step_layers, "epochs": step_epochs, "accuracy": step_accuracy, "errors": step_errors}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--step", choices=["layers", "epochs", "accuracy", "errors"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gcnii_timing.json"))
-    a = ap.parse_args()
-    steps = {"layers": step_layers, "epochs": step_epochs, "accuracy": step_accuracy, "errors": step_errors}
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("errors", "errors", 120), Step("layers", "layers", 240), Step("epochs", "epochs", 240), Step("accuracy", "accuracy", 300)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = steps[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("errors", 120), ("layers", 240), ("epochs", 240), ("accuracy", 300)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters"), a.out)))
 
 
 if __name__ == "__main__":

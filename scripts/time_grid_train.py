@@ -19,25 +19,14 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _cora, _time_arms, flags, run_step, run_steps, write  # noqa: E402
+
 S, HIDDEN, KIND = 10, 64, "gcn"
 GRID = [dict(lr=lr, weight_decay=wd, dropout=dr) for lr in (0.002, 0.01, 0.05) for wd in (5e-4, 5e-3) for dr in (0.0, 0.5)]
 GATE = 1.04  # the grid's time over the successive runs' summed time: the README's spread between boxes
-
-
-def _cora():
-    import numpy as np
-    import torch
-    g = dict(np.load(os.path.join(ROOT, "tests", "golden", "real_cora.npz")))
-    n, f = int(g["n_nodes"]), int(g["n_feat"])
-    x = np.zeros((n, f), np.float32)
-    x[np.repeat(np.arange(n), np.diff(g["feat_indptr"])), g["feat_indices"]] = g["featn_data"]
-    adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([g["adj_row"], g["adj_col"]]).astype(np.int64)), torch.from_numpy(g["adj_val"]), (n, n))
-    return adj, torch.from_numpy(x), g["labels"].astype(np.int64)
 
 
 def _problem():
@@ -133,29 +122,20 @@ def step_adam(a):
     opt = torch.optim.Adam(params, lr=0.01, weight_decay=5e-4, capturable=True, fused=True)
     arms = {"torch.optim.Adam(fused=True, capturable=True).step(): one lr, one weight_decay": opt.step,
             "ops.AdamBatch.launch: lr and weight_decay per replica": lambda: batch.launch(step)}
-    times = {k: [] for k in arms}
-    for rnd in range(a.kernel_rounds + 1):  # (round 0 warms up)
-        for name, fn in arms.items():
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            t0.record()
-            for _ in range(a.kernel_iters):
-                fn()
-            t1.record()
-            torch.cuda.synchronize()
-            if rnd:
-                times[name].append(t0.elapsed_time(t1) / a.kernel_iters * 1e3)
+    times = _time_arms(arms, a.kernel_rounds, a.kernel_iters)
     elements = w0.numel() + w1.numel()
     out = {"workload": f"w0 [{f}, {r * h}] and w1 [{r * h}, {cs}] of {r} replicas ({elements} elements, {28 * elements} bytes moved per step); "
                        f"{a.kernel_rounds} interleaved rounds of {a.kernel_iters} back-to-back eager calls, device time from events; us per call"}
     for name, t in times.items():
-        med = statistics.median(t)
-        out[name] = {"median_us": med, "min_us": min(t), "max_us": max(t), "GB/s at the median": 28 * elements / med / 1e3}
+        out[name] = dict(t, **{"GB/s at the median": 28 * elements / t["median_us"] / 1e3})
         print(json.dumps({name: out[name]}), flush=True)
     return out
 
 
-def main():
+STEP_FNS = {"grid": step_grid, "stages": step_stages, "adam": step_adam}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=100)
@@ -165,32 +145,18 @@ def main():
     ap.add_argument("--step", choices=["grid", "stages", "adam"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grid_train_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("grid", "grid", 420), Step("stages", "stages", 180), Step("adam", "adam", 180)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"grid": step_grid, "stages": step_stages, "adam": step_adam}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for i, (step, limit) in enumerate((("grid", 420), ("stages", 180), ("adam", 180))):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--runs", str(a.runs),
-               "--epochs", str(a.epochs), "--stage-iters", str(a.stage_iters), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "stage_iters", "kernel_rounds", "kernel_iters"), a.out)))
 
 
 if __name__ == "__main__":

@@ -15,32 +15,20 @@ first that fails (`step_a && step_b`); a child writes its part of the document n
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _shard_batch, best_of, flags, run_step, run_steps, write  # noqa: E402
 
 STEPS = (("shard", 600), ("table", 600))  # (name, seconds its child may take)
 BASES = (("cora", 1433), ("citeseer", 3703), ("pubmed", 500), ("chameleon", 2325), ("squirrel", 2089), ("film", 932))  # sweep.BaseSweep.REFERENCE_BASES
 
 
-def best_of(fn, runs):
-    """one warm-up, then the fastest of `runs` calls of fn() -> seconds"""
-    fn()
-    return min(fn() for _ in range(runs))
-
-
 def step_shard(a):
-    import torch
-    from wdg_amd import sweep, synth
-    jobs = sweep.make_jobs(synth.H_LEVELS_10_K10, range(5), k=10, n_nodes=2000)
-    sb = sweep.SweepBatch(jobs, n_feat=500, gcn_hidden=0)
-    for s_ in sb.x:
-        lab = synth.regular_graph(2000, 5, 10, 0.5, s_)[2]
-        sb.x[s_].copy_(torch.from_numpy(synth.features(2000, 500, s_, labels=lab)))
-    out = {"workload": f"{len(jobs)} graphs, N = 2000, F = 500, k = 10, {a.epochs} epochs, best of {a.runs} after a warm-up; seconds of the epoch loop"}
+    from wdg_amd import sweep
+    jobs, sb = _shard_batch()
+    out ={"workload": f"{len(jobs)} graphs, N = 2000, F = 500, k = 10, {a.epochs} epochs, best of {a.runs} after a warm-up; seconds of the epoch loop"}
     for kind in ("sgc", "mlp1", "mlp2"):
         tb = sweep.TrainBatch(sb, kind=kind, hidden=64, seed=1)
         tb.run(epochs=3, capture=True)
@@ -103,37 +91,31 @@ def step_table(a):
     return out
 
 
-def main():
+STEP_FNS = {"shard": step_shard, "table": step_table}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=200)
     ap.add_argument("--table-graphs", type=int, default=280)
     ap.add_argument("--table-chunk", type=int, default=10)
     ap.add_argument("--step", choices=[s for s, _ in STEPS])
+    ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "head_train_timing.json"))
-    a = ap.parse_args()
-    part = lambda name: f"{a.out}.{name}.part"  # noqa: E731
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step(name, name, limit) for name, limit in STEPS]
+
+
+def main():
+    a = parse()
     if a.step:
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"shard": step_shard, "table": step_table}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(part(a.step), "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {"timer": "wall clock around the epoch loop, the device drained before and after"}
-    for name, limit in STEPS:  # each step in a fresh process under its own time limit; the first failure ends the run
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name, "--runs", str(a.runs), "--epochs", str(a.epochs),
-               "--table-graphs", str(a.table_graphs), "--table-chunk", str(a.table_chunk), "--out", a.out]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            sys.exit(f"step {name} ended with status {rc}: stopping")
-        doc[name] = json.load(open(part(name)))
-        os.remove(part(name))
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    parts = run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "table_graphs", "table_chunk"), a.out)
+    write(a.out, dict({"timer": "wall clock around the epoch loop, the device drained before and after"}, **dict(parts)))
 
 
 if __name__ == "__main__":

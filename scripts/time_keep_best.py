@@ -27,36 +27,19 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _arm_rounds, _cora, _epoch_rounds, _ms_per_epoch, _summary, flags, run_step, run_steps, write  # noqa: E402
+
 KINDS = ("gcn", "acm_gcn")
 HIDDEN = 64
-
-
-def _cora(tree):
-    import numpy as np
-    import torch
-    g = dict(np.load(os.path.join(tree, "tests", "golden", "real_cora.npz")))
-    n, f = int(g["n_nodes"]), int(g["n_feat"])
-    x = np.zeros((n, f), np.float32)
-    x[np.repeat(np.arange(n), np.diff(g["feat_indptr"])), g["feat_indices"]] = g["featn_data"]
-    adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([g["adj_row"], g["adj_col"]]).astype(np.int64)), torch.from_numpy(g["adj_val"]), (n, n))
-    return adj, torch.from_numpy(x), g["labels"].astype(np.int64)
 
 
 def _trainer(kind, adj, x, labels, masks, **kw):
     from wdg_amd import acm_split_train, split_train
     cls = acm_split_train.AcmSplitTrainBatch if kind.startswith("acm") else split_train.SplitTrainBatch
     return cls(adj, x, labels, masks, kind=kind, hidden=HIDDEN, seed=1, **kw)
-
-
-def _ms_per_epoch(stb, a):
-    """the median over a.runs rounds of a.epochs captured epochs, after one warm-up round (which captures)"""
-    stb.run(epochs=a.epochs, capture=True)
-    rounds = [stb.run(epochs=a.epochs, capture=True)["seconds"] / a.epochs * 1e3 for _ in range(a.runs)]
-    return {"median_ms": statistics.median(rounds), "min_ms": min(rounds), "max_ms": max(rounds), "rounds_ms": rounds}
 
 
 def step_kernel(a):
@@ -77,23 +60,11 @@ def step_kernel(a):
         dst.zero_()
         batch.launch(step)
         same = bool(torch.equal(dst, torch.where(column_mask, src, torch.zeros_like(src))))
-        times = {k: [] for k in arms}
-        for rd in range(a.kernel_rounds + 1):  # (round 0 warms up)
-            for arm, fn in arms.items():
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                t0.record()
-                for _ in range(a.kernel_iters):
-                    fn()
-                t1.record()
-                torch.cuda.synchronize()
-                if rd:
-                    times[arm].append(t0.elapsed_time(t1) / a.kernel_iters * 1e3)
         moved = int(chosen.sum()) * h * f * 8
         res = {"selected replicas": int(chosen.sum()), "kernel equals the composition": same, "bytes the kernel moves": moved}
-        for arm, t in times.items():
-            med = statistics.median(t)
-            res[arm] = {"median_us": med, "min_us": min(t), "max_us": max(t), "TB/s of the kernel's bytes": moved / med / 1e6}
+        for arm, t in _arm_rounds(arms, a.kernel_rounds, a.kernel_iters).items():
+            res[arm] = _summary(t, "us")
+            res[arm]["TB/s of the kernel's bytes"] = moved / res[arm]["median_us"] / 1e6
         out[name] = res
         print(json.dumps({name: res}), flush=True)
     k, c = out["all"]["keep_best kernel"], out["all"]["torch.where + copy_"]
@@ -130,12 +101,7 @@ def step_optin(a):
         ids = np.tile(np.arange(10), reps // 10)
         for kind in KINDS:
             arms = {keep: _trainer(kind, adj, x, labels, masks, replica_ids=ids, keep_best=keep) for keep in (False, True)}
-            for stb in arms.values():
-                stb.run(epochs=a.epochs, capture=True)
-            rounds = {keep: [] for keep in arms}
-            for _ in range(a.runs):
-                for keep, stb in arms.items():
-                    rounds[keep].append(stb.run(epochs=a.epochs, capture=True)["seconds"] / a.epochs * 1e3)
+            rounds = _epoch_rounds({keep: (lambda rnd, stb=stb: stb.run(epochs=a.epochs, capture=True)) for keep, stb in arms.items()}, a.runs, a.epochs, warmup=1)
             off, on = statistics.median(rounds[False]), statistics.median(rounds[True])
             kept = sum(k.numel() for k in arms[True].kept_params) + arms[True].kept_logits.numel()
             res = {"keep_best=False median_ms": off, "keep_best=True median_ms": on, "added us per epoch": (on - off) * 1e3, "on over off": on / off,
@@ -146,7 +112,10 @@ def step_optin(a):
     return out
 
 
-def main():
+STEP_FNS = {"kernel": step_kernel, "default": step_default, "optin": step_optin}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=100)
@@ -158,33 +127,19 @@ def main():
     ap.add_argument("--tree", default=ROOT, help="(with --step) the checkout whose package is imported")
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "keep_best_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    trees = ([os.path.abspath(a.parent), ROOT] if a.parent else [ROOT]) * a.processes  # parent, new, parent, new, ...
+    return [Step("kernel", "kernel", 240, tree=ROOT)] + [Step("default", "default", 300, tree=tree) for tree in trees] + [Step("optin", "optin", 600, tree=ROOT)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, os.path.abspath(a.tree))
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"kernel": step_kernel, "default": step_default, "optin": step_optin}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    steps = [("kernel", ROOT, 240)]
-    for tree in ([a.parent, ROOT] if a.parent else [ROOT]) * a.processes:
-        steps.append(("default", os.path.abspath(tree), 300))
-    steps.append(("optin", ROOT, 600))
-    parts = []
-    for i, (step, tree, limit) in enumerate(steps):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--tree", tree, "--part", part, "--runs", str(a.runs),
-               "--epochs", str(a.epochs), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        parts.append((step, json.load(open(part))))
-        os.remove(part)
+        return run_step(a, STEP_FNS, a.tree)
+    parts = run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "kernel_rounds", "kernel_iters"), a.out)
     doc = {"kernel": parts[0][1], "optin": parts[-1][1]}
     runs = [p for s, p in parts if s == "default"]
     default = {"workload": f"Cora fixture, ten splits, hidden {HIDDEN}, keep_best off; per process the median of {a.runs} rounds of {a.epochs} captured epochs "
@@ -198,9 +153,7 @@ def main():
             default["yardstick"][kind] = {"parent_ms": old, "new_ms": new, "bound_ms": bound, "passed": statistics.median(new) <= bound,
                                           "new over parent": statistics.median(new) / statistics.median(old)}
     doc["default"] = default
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    write(a.out, doc)
     failed = ([] if doc["kernel"]["gate"]["passed"] else ["the kernel gate"]) + [f"the default-path yardstick of {kind!r}" for kind in KINDS
                                                                                 if a.parent and not default["yardstick"][kind]["passed"]]
     for what in failed:

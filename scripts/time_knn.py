@@ -5,7 +5,7 @@ and scikit-learn's kneighbors_graph on the host where it imports - and records, 
 the kNN graph beside the given graph's and the accuracy of GCN-2 on the kNN graph and of H2GCN-1 on a KnnAdj beside MLP-2, GCN-2 and
 H2GCN-1 on a TwoHopAdj.
 
-  select    the method of scripts/time_gat.py: interleaved rounds, the arms alternating inside a round, device time from events around
+  select    the method of scripts/_timing.py: interleaved rounds, the arms alternating inside a round, device time from events around
             --iters back-to-back calls, median / minimum / maximum.  Shapes, k = 10, self excluded, columns ascending:
               cora        the selection alone on the 2 708^2 similarity matrix of tests/golden/real_cora.npz's features with the cosine
                           column scale; the same matrix with every row ASCENDING (the worst case: every chunk of 64 columns is merged)
@@ -29,14 +29,11 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, SWEEP_C, SWEEP_F, SWEEP_H, Step, _golden, _summary, _sweep_problems, _sweep_train, _time_arms, flags, run_step, run_steps, write  # noqa: E402
 
 K = 10
 
@@ -130,7 +127,7 @@ def _wall(fn, rounds):
         torch.cuda.synchronize()
         if rnd:
             times.append((time.perf_counter() - t0) * 1e6)
-    return {"median_us": statistics.median(times), "min_us": min(times), "max_us": max(times)}
+    return _summary(times, "us")
 
 
 def step_graphs(a):
@@ -161,7 +158,7 @@ def step_graphs(a):
                 t0 = time.perf_counter()
                 kneighbors_graph(x, K, metric="cosine", mode="connectivity", include_self=False)
                 times.append((time.perf_counter() - t0) * 1e6)
-            out[f"{name}: sklearn kneighbors_graph(metric='cosine') on the host"] = {"median_us": statistics.median(times), "min_us": min(times), "max_us": max(times)}
+            out[f"{name}: sklearn kneighbors_graph(metric='cosine') on the host"] = _summary(times, "us")
             print(json.dumps({name: times}), flush=True)
     except ImportError as e:
         out["sklearn"] = f"arm left out: scikit-learn does not import here ({e})"
@@ -171,18 +168,14 @@ def step_graphs(a):
 def step_behaviour(a):
     import numpy as np
     import torch
-    from wdg_amd import models, ops, synth
-    n, f, c = 2000, 128, 5
-    out = {"workload": f"N = 2000, F = 128, signal 0.5, k = 10 (graph), kNN k = {K} cosine union, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 "
+    from wdg_amd import models, ops
+    out ={"workload": f"N = 2000, F = 128, signal 0.5, k = 10 (graph), kNN k = {K} cosine union, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 "
                        "splits; validation and test accuracy at the selected epoch, seeds 0 - 4; hidden 64; symmetric normalisation"}
     kinds = ("MLP2", "GCN2", "H2GCN1 on TwoHopAdj", "GCN2 on the kNN graph", "H2GCN1 on KnnAdj")
-    for h in (0.2, 0.5, 0.9):
+    for h in SWEEP_H:
         res = {k: {"val": [], "test": []} for k in kinds}
         homo = {"given": [], "knn": []}
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
+        for seed, coo, x, labels in _sweep_problems(h):
             adj, adj2, adjk = models.NormAdj(coo, symmetric=1), models.TwoHopAdj(coo, symmetric=1), models.KnnAdj(coo, x, k=K, symmetric=1)
             for name, g in (("given", adjk.one.graph), ("knn", adjk.knn)):
                 t = ops.edge_label_stats(g, labels.cuda(), per_row=False)["totals"].cpu().tolist()
@@ -190,8 +183,7 @@ def step_behaviour(a):
             for kind, cls, model_adj in (("MLP2", "MLP2", adj), ("GCN2", "GCN2", adj), ("H2GCN1 on TwoHopAdj", "H2GCN1", adj2),
                                          ("GCN2 on the kNN graph", "GCN2", models.NormAdj(adjk.knn, symmetric=1)), ("H2GCN1 on KnnAdj", "H2GCN1", adjk)):
                 torch.manual_seed(seed)
-                model = getattr(models, cls)(f, c)
-                r = models.train_eval_graphed(model, model_adj, x, labels, epochs=80, lr=0.05, capture=True)
+                r = _sweep_train(getattr(models, cls)(SWEEP_F, SWEEP_C), model_adj, x, labels)
                 res[kind]["val"].append(round(r["val_acc"], 4))
                 res[kind]["test"].append(round(r["test_acc"], 4))
         doc = {k: {"val mean": float(np.mean(v["val"])), "test mean": float(np.mean(v["test"])), "val": v["val"], "test": v["test"]} for k, v in res.items()}
@@ -202,7 +194,10 @@ def step_behaviour(a):
     return out
 
 
-def main():
+STEP_FNS = {"select": step_select, "graphs": step_graphs, "behaviour": step_behaviour}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
@@ -210,32 +205,18 @@ def main():
     ap.add_argument("--step", choices=["select", "graphs", "behaviour"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "knn_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("select", "select", 300), Step("graphs", "graphs", 420), Step("behaviour", "behaviour", 420)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"select": step_select, "graphs": step_graphs, "behaviour": step_behaviour}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("select", 300), ("graphs", 420), ("behaviour", 420)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters), "--host-rounds", str(a.host_rounds)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-        with open(a.out, "w") as f:  # (written after every step: a later step's failure keeps the earlier steps' numbers)
-            json.dump(doc, f, indent=1)
-            f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters", "host_rounds"), a.out)))
 
 
 if __name__ == "__main__":

@@ -25,37 +25,13 @@ that fails: nothing more runs on the device after a step that faults, aborts or 
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, Step, _accuracy_sweep, _fixture_coo, _fixture_graph, _generated_features, _shard, _time_arms, _time_epochs, flags, run_step, run_steps, write  # noqa: E402
 
 P, W, SEED, FANOUTS = 0.5, 64, 1, (5, 10, 25)
-
-
-def _fixture_graph(name):
-    import numpy as np
-    from wdg_amd import ops
-    z = _golden(name)
-    return ops.CsrGraph.from_coo(z["adj_row"].astype(np.int64), z["adj_col"].astype(np.int64), int(z["n_nodes"]), None, ops.COO_BINARISE)
-
-
-def _fixture_coo(name):
-    import numpy as np
-    import torch
-    z = _golden(name)
-    n = int(z["n_nodes"])
-    idx = np.unique(np.vstack([z["adj_row"], z["adj_col"]]).astype(np.int64), axis=1)
-    return torch.sparse_coo_tensor(torch.from_numpy(idx), torch.ones(idx.shape[1]), (n, n)), n
-
-
-def _shard():
-    from wdg_amd import ops, synth
-    specs = [(2000, 5, 10, synth.out_degree(10, 0.2), seed) for seed in range(50)]
-    return ops.GraphBatch.generated(specs, flags=0, quad=False).graphs
+LIMITS = {"kernels": 240, "aggregation": 120, "epochs": 240, "accuracy": 420}
 
 
 def _topology_case(graphs, a, iters):
@@ -98,9 +74,9 @@ def _topology_case(graphs, a, iters):
 def step_kernels(a):
     out = {"workload": f"{a.rounds} interleaved rounds of {a.iters} back-to-back calls (the shard: a fifth of that) after a warm-up round, device time from "
                        "events; us per call"}
-    for name, graphs, iters in (("cora", lambda: [_fixture_graph("real_cora")], a.iters),
+    for name, graphs, iters in (("cora", lambda: [_fixture_graph("real_cora", 0)], a.iters),
                                 ("shard of 50 graphs (N = 2000, k = 10, h = 0.2), one table", _shard, max(1, a.iters // 5)),
-                                ("squirrel (the hub case)", lambda: [_fixture_graph("topo_squirrel")], a.iters)):
+                                ("squirrel (the hub case)", lambda: [_fixture_graph("topo_squirrel", 0)], a.iters)):
         out[name] = _topology_case(graphs(), a, iters)
         print(json.dumps({name: out[name]}), flush=True)
     return out
@@ -109,7 +85,7 @@ def step_kernels(a):
 def step_aggregation(a):
     import torch
     from wdg_amd import ops
-    g = _fixture_graph("topo_squirrel")
+    g = _fixture_graph("topo_squirrel", 0)
     gt = g.transpose()
     word = torch.zeros(1, dtype=torch.int32, device="cuda")
     entry = [dict(graph=g, graph_t=gt)]
@@ -138,57 +114,44 @@ def step_aggregation(a):
 
 def step_epochs(a):
     import torch
-    from wdg_amd import models, synth
+    from wdg_amd import models
     out = {"workload": "models.train_eval_graphed(capture=True), 200 epochs of models.SAGE2 (hidden 64, dropout 0.5 with a DeviceDropout) on the topology "
                        "(random-walk scale, no self loops), 128 generated features: ms per epoch (training step + evaluation, two graph replays), three "
                        "alternating rounds"}
     for name, fixture, c in (("cora", "real_cora", 7), ("squirrel", "topo_squirrel", 5)):
         coo, n = _fixture_coo(fixture)
-        lab = (torch.arange(n) % c).numpy()
-        x, labels = torch.from_numpy(synth.features(n, 128, 0, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
-        times = {"NeighborSampleAdj(fan-out 25)": [], "NormAdj": []}
-        for _ in range(3):
-            for arm in times:
-                adj = models.NeighborSampleAdj(coo, 25, SEED) if arm != "NormAdj" else models.NormAdj(coo, add_self_loops=False)
+        x, labels = _generated_features(n, c)
+
+        def arm(mk_adj):
+            def run(rnd):
+                adj = mk_adj()
                 torch.manual_seed(0)
-                res = models.train_eval_graphed(models.SAGE2(128, c, W, 0.5, models.DeviceDropout(1, 0)), adj, x, labels, epochs=200, lr=0.01, capture=True)
-                times[arm].append(res["seconds"] / 200 * 1e3)
-        out[name] = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in times.items()}
+                return models.train_eval_graphed(models.SAGE2(128, c, W, 0.5, models.DeviceDropout(1, 0)), adj, x, labels, epochs=200, lr=0.01, capture=True)
+            return run
+
+        out[name] = _time_epochs({"NeighborSampleAdj(fan-out 25)": arm(lambda: models.NeighborSampleAdj(coo, 25, SEED)),
+                                  "NormAdj": arm(lambda: models.NormAdj(coo, add_self_loops=False))}, 3, 200)
         print(json.dumps({name: out[name]}), flush=True)
     return out
 
 
 def step_accuracy(a):
-    import numpy as np
-    import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; validation "
                        "and test accuracy at the selected epoch, seeds 0 - 4; SAGE2 evaluates on the full neighbourhood whatever it trained on; untuned"}
-    sage = lambda: models.SAGE2(f, c)  # noqa: E731
-    arms = (("SAGE2 (hidden 64), trained on samples of fan-out 5", sage, lambda coo, seed: models.NeighborSampleAdj(coo, 5, SEED, stream=seed)),
-            ("SAGE2 (hidden 64), trained on samples of fan-out 25", sage, lambda coo, seed: models.NeighborSampleAdj(coo, 25, SEED, stream=seed)),
-            ("SAGE2 (hidden 64), trained on the full neighbourhood", sage, lambda coo, seed: models.NormAdj(coo, add_self_loops=False)),
-            ("GCN2 (hidden 64)", lambda: models.GCN2(f, c), lambda coo, seed: models.NormAdj(coo)),
-            ("MLP2 (hidden 64)", lambda: models.MLP2(f, c), lambda coo, seed: models.NormAdj(coo)))
-    for h in (0.2, 0.5, 0.9):
-        accs = {name: ([], []) for name, _, _ in arms}
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
-            for name, mk, mk_adj in arms:
-                torch.manual_seed(seed)
-                res = models.train_eval_graphed(mk(), mk_adj(coo, seed), x, labels, epochs=80, lr=0.05, capture=True)
-                accs[name][0].append(res["val_acc"])
-                accs[name][1].append(res["test_acc"])
-        out[f"h = {h}"] = {name: {"val_mean": float(np.mean(v)), "test_mean": float(np.mean(t)), "val": [round(float(q), 4) for q in v],
-                                  "test": [round(float(q), 4) for q in t]} for name, (v, t) in accs.items()}
-        print(json.dumps({f"h = {h}": out[f"h = {h}"]}), flush=True)
+    out.update(_accuracy_sweep((
+        ("SAGE2 (hidden 64), trained on samples of fan-out 5", models.SAGE2, lambda coo, seed: models.NeighborSampleAdj(coo, 5, SEED, stream=seed)),
+        ("SAGE2 (hidden 64), trained on samples of fan-out 25", models.SAGE2, lambda coo, seed: models.NeighborSampleAdj(coo, 25, SEED, stream=seed)),
+        ("SAGE2 (hidden 64), trained on the full neighbourhood", models.SAGE2, lambda coo, seed: models.NormAdj(coo, add_self_loops=False)),
+        ("GCN2 (hidden 64)", models.GCN2, lambda coo, seed: models.NormAdj(coo)),
+        ("MLP2 (hidden 64)", models.MLP2, lambda coo, seed: models.NormAdj(coo)))))
     return out
 
 
-def main():
+STEP_FNS = {"kernels": step_kernels, "aggregation": step_aggregation, "epochs": step_epochs, "accuracy": step_accuracy}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
@@ -196,37 +159,18 @@ def main():
     ap.add_argument("--step", choices=["kernels", "aggregation", "epochs", "accuracy"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "neighbor_sample_timing.json"))
-    a = ap.parse_args()
-    steps = {"kernels": step_kernels, "aggregation": step_aggregation, "epochs": step_epochs, "accuracy": step_accuracy}
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step(step, step, LIMITS[step]) for step in a.steps.split(",")]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = steps[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    limits = {"kernels": 240, "aggregation": 120, "epochs": 240, "accuracy": 420}
-    doc = {}
-    for step in a.steps.split(","):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limits[step]), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            with open(a.out, "w") as f:  # (what the earlier steps measured stays)
-                json.dump(dict(doc, **{step: f"not measured: the step ended with status {rc}"}), f, indent=1)
-                f.write("\n")
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters"), a.out)))
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ synthetic graphs of the 4.25 / 4.27 tables.
             at 5 columns; ONE table of a 50-graph shard (N = 2000, k = 10, ten homophily levels x five seeds) at 8 columns; ONE job
             of 120 segments of 8 columns on Cora (what a stacked run over 120 replicas would launch).  The arms alternate inside every
             round; device time from events around --iters back-to-back calls; median, minimum and maximum over the rounds (the method
-            of scripts/time_gat.py).
+            of scripts/_timing.py).
   accuracy  N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, h in 0.2, 0.5, 0.9, seeds 0 - 4: the validation accuracy at
             the selected epoch of GPRGNN2 (hidden 64, order 10, alpha 0.1, dropout 0.5; NormAdj(symmetric=1)) and its gamma after the
             last epoch - on the graphs, features and seeds of scripts/time_gat.py, whose table (profiles/gat_timing.json) has GAT2,
@@ -23,12 +23,10 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, SWEEP_C, SWEEP_F, SWEEP_H, Step, _golden, _sweep_problems, _sweep_train, _time_arms, flags, run_step, run_steps, write  # noqa: E402
 
 ORDER = 10
 
@@ -112,20 +110,16 @@ def step_filters(a):
 def step_accuracy(a):
     import numpy as np
     import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; the "
                        "validation accuracy at the selected epoch, seeds 0 - 4; gamma after the last epoch (not the selected one)"}
-    for h in (0.2, 0.5, 0.9):
+    for h in SWEEP_H:
         accs, gammas = [], []
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
+        for seed, coo, x, labels in _sweep_problems(h):
             adj = models.NormAdj(coo, symmetric=1)
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
             torch.manual_seed(seed)
-            model = models.GPRGNN2(f, c)
-            accs.append(models.train_eval_graphed(model, adj, x, labels, epochs=80, lr=0.05, capture=True)["val_acc"])
+            model = models.GPRGNN2(SWEEP_F, SWEEP_C)
+            accs.append(_sweep_train(model, adj, x, labels)["val_acc"])
             gammas.append(model.filter_coefficients())
         out[f"h = {h}"] = {"GPRGNN2 (hidden 64, order 10, alpha 0.1)": {"mean": float(np.mean(accs)), "values": [round(float(t), 4) for t in accs]},
                            "gamma, mean over the seeds": [round(float(t), 4) for t in np.mean(gammas, 0)],
@@ -134,39 +128,28 @@ def step_accuracy(a):
     return out
 
 
-def main():
+STEP_FNS = {"filters": step_filters, "accuracy": step_accuracy}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--step", choices=["filters", "accuracy"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poly_filter_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("filters", "filters", 300), Step("accuracy", "accuracy", 300)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"filters": step_filters, "accuracy": step_accuracy}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("filters", 300), ("accuracy", 300)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters"), a.out)))
 
 
 if __name__ == "__main__":

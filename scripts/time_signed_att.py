@@ -8,7 +8,7 @@ kernel); and - for DESIGN 4.27, not a timing - FAGCN-2 validation accuracy on th
             squirrel's topology (tests/golden/topo_squirrel.npz: rows of up to ~2 000 entries on ONE wave each) at 1 x 5, and ONE table of
             a 50-graph shard (N = 2000, k = 10, ten homophily levels x five seeds, 1 x 64; torch: the same layer on the block-diagonal
             union; spmm: 50 calls).  Both scales and a residual with eps = 0.3.  The arms alternate inside every round; device time from
-            events around --iters back-to-back calls; median, minimum and maximum over the rounds (the method of scripts/time_gat.py).
+            events around --iters back-to-back calls; median, minimum and maximum over the rounds (the method of scripts/_timing.py).
   accuracy  N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, h in 0.2, 0.5, 0.9, seeds 0 - 4: the validation accuracy at
             the selected epoch of FAGCN2 (hidden 64, 2 layers, eps 0.3; NormAdj(symmetric=1, add_self_loops=False)), dropout 0.5 - on
             the graphs, features and seeds of scripts/time_gat.py, whose table (profiles/gat_timing.json) has GAT2, GCN2 and MLP2; MLP2
@@ -21,12 +21,10 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _plan, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, SWEEP_C, SWEEP_F, SWEEP_H, Step, _golden, _plan, _sweep_problems, _sweep_train, _time_arms, flags, run_step, run_steps, write  # noqa: E402
 
 EPS = 0.3
 
@@ -110,22 +108,18 @@ def step_layers(a):
 def step_accuracy(a):
     import numpy as np
     import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; the "
                        "validation accuracy at the selected epoch, seeds 0 - 4"}
-    for h in (0.2, 0.5, 0.9):
-        makers = (("FAGCN2 (hidden 64, 2 layers, eps 0.3)", lambda: models.FAGCN2(f, c), True), ("MLP2 (hidden 64)", lambda: models.MLP2(f, c), False))
+    for h in SWEEP_H:
+        makers = (("FAGCN2 (hidden 64, 2 layers, eps 0.3)", models.FAGCN2, True), ("MLP2 (hidden 64)", models.MLP2, False))
         accs, shares = {name: [] for name, _, _ in makers}, []
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
+        for seed, coo, x, labels in _sweep_problems(h):
             adj, adj_sym = models.NormAdj(coo, symmetric=0), models.NormAdj(coo, symmetric=1, add_self_loops=False)
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
             for name, mk, signed in makers:
                 torch.manual_seed(seed)
-                model = mk()
-                accs[name].append(models.train_eval_graphed(model, adj_sym if signed else adj, x, labels, epochs=80, lr=0.05, capture=True)["val_acc"])
+                model = mk(SWEEP_F, SWEEP_C)
+                accs[name].append(_sweep_train(model, adj_sym if signed else adj, x, labels)["val_acc"])
                 if signed:  # (the weights at the LAST epoch, not the selected one)
                     shares.append([round(float((w_ < 0).float().mean()), 4) for w_ in model.signed_weights(adj_sym, x)])
         out[f"h = {h}"] = {k: {"mean": float(np.mean(v)), "values": [round(float(t), 4) for t in v]} for k, v in accs.items()}
@@ -134,39 +128,28 @@ def step_accuracy(a):
     return out
 
 
-def main():
+STEP_FNS = {"layers": step_layers, "accuracy": step_accuracy}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--step", choices=["layers", "accuracy"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "signed_att_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("layers", "layers", 300), Step("accuracy", "accuracy", 480)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"layers": step_layers, "accuracy": step_accuracy}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("layers", 300), ("accuracy", 480)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters"), a.out)))
 
 
 if __name__ == "__main__":

@@ -25,14 +25,11 @@ first that fails: nothing more runs on the device after a step that faults, abor
 import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from time_gat import _golden, _time_arms  # noqa: E402  (the method, stated once)
+from _timing import ROOT, SWEEP_C, SWEEP_F, SWEEP_H, Step, _golden, _summary, _sweep_problems, _sweep_train, _time_arms, flags, run_step, run_steps, write  # noqa: E402
 
 
 def _cases():
@@ -83,7 +80,7 @@ def _wall(fn, rounds):
         torch.cuda.synchronize()
         if rnd:
             times.append((time.perf_counter() - t0) * 1e6)
-    return {"median_us": statistics.median(times), "min_us": min(times), "max_us": max(times)}
+    return _summary(times, "us")
 
 
 def step_build(a):
@@ -107,7 +104,7 @@ def step_build(a):
             t0 = time.perf_counter()
             want = [_scipy_two_hop(b) for b in host]
             times.append((time.perf_counter() - t0) * 1e6)
-        res["scipy on the host, 1 thread: (B @ B > 0) - B - I"] = {"median_us": statistics.median(times), "min_us": min(times), "max_us": max(times)}
+        res["scipy on the host, 1 thread: (B @ B > 0) - B - I"] = _summary(times, "us")
         res["equal to scipy (rowptr and col of every graph)"] = bool(all(
             np.array_equal(t.rowptr.cpu().numpy(), w.indptr) and np.array_equal(t.col.cpu().numpy(), w.indices) for t, w in zip(two, want)))
         res["rows, one-hop entries, two-hop entries, longest one-hop row, longest two-hop row"] = [
@@ -149,21 +146,16 @@ def step_torch(a):
 def step_accuracy(a):
     import numpy as np
     import torch
-    from wdg_amd import models, synth
-    n, f, c = 2000, 128, 5
+    from wdg_amd import models
     out = {"workload": "N = 2000, F = 128, signal 0.5, k = 10, 80 epochs, lr 0.05, weight decay 5e-4, dropout 0.5, random 60/20/20 splits; validation and "
                        "test accuracy at the selected epoch, seeds 0 - 4; hidden 64; symmetric normalisation (GCN2 with self loops, H2GCN2 without)"}
-    for h in (0.2, 0.5, 0.9):
+    for h in SWEEP_H:
         res = {k: {"val": [], "test": []} for k in ("H2GCN2", "GCN2", "MLP2")}
-        for seed in range(5):
-            src, dst, lab = synth.regular_graph(n, c, 10, h, seed)
-            coo = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([src, dst])), torch.ones(src.shape[0]), (n, n))
+        for seed, coo, x, labels in _sweep_problems(h):
             adj, adj2 = models.NormAdj(coo, symmetric=1), models.TwoHopAdj(coo, symmetric=1)
-            x, labels = torch.from_numpy(synth.features(n, f, seed, labels=lab, signal=0.5)).cuda(), torch.from_numpy(lab)
             for kind, model_adj in (("H2GCN2", adj2), ("GCN2", adj), ("MLP2", adj)):
                 torch.manual_seed(seed)
-                model = getattr(models, kind)(f, c)
-                r = models.train_eval_graphed(model, model_adj, x, labels, epochs=80, lr=0.05, capture=True)
+                r = _sweep_train(getattr(models, kind)(SWEEP_F, SWEEP_C), model_adj, x, labels)
                 res[kind]["val"].append(round(r["val_acc"], 4))
                 res[kind]["test"].append(round(r["test_acc"], 4))
         out[f"h = {h}"] = {k: {"val mean": float(np.mean(v["val"])), "test mean": float(np.mean(v["test"])), "val": v["val"], "test": v["test"]} for k, v in res.items()}
@@ -171,7 +163,10 @@ def step_accuracy(a):
     return out
 
 
-def main():
+STEP_FNS = {"build": step_build, "torch": step_torch, "accuracy": step_accuracy}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
@@ -179,32 +174,18 @@ def main():
     ap.add_argument("--step", choices=["build", "torch", "accuracy"])
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "two_hop_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    return [Step("build", "build", 420), Step("accuracy", "accuracy", 420), Step("torch", "torch", 240)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, ROOT)
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"build": step_build, "torch": step_torch, "accuracy": step_accuracy}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    doc = {}
-    for step, limit in (("build", 420), ("accuracy", 420), ("torch", 240)):  # each in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--part", part, "--rounds", str(a.rounds),
-               "--iters", str(a.iters), "--host-rounds", str(a.host_rounds)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        doc[step] = json.load(open(part))
-        os.remove(part)
-        with open(a.out, "w") as f:  # (written after every step: a later step's failure keeps the earlier steps' numbers)
-            json.dump(doc, f, indent=1)
-            f.write("\n")
+        return run_step(a, STEP_FNS)
+    write(a.out, dict(run_steps(__file__, invocations(a), flags(a, "rounds", "iters", "host_rounds"), a.out)))
 
 
 if __name__ == "__main__":

@@ -26,23 +26,13 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import ROOT, Step, _cora, _epoch_rounds, _ms_per_epoch, _time_arms, flags, run_step, run_steps, write  # noqa: E402
+
 HIDDEN, REPLICAS = 64, (10, 120)
 FEATURE = dict(select="val_loss", patience=40, curve_epochs=200)
-
-
-def _cora(tree):
-    import numpy as np
-    import torch
-    g = dict(np.load(os.path.join(tree, "tests", "golden", "real_cora.npz")))
-    n, f = int(g["n_nodes"]), int(g["n_feat"])
-    x = np.zeros((n, f), np.float32)
-    x[np.repeat(np.arange(n), np.diff(g["feat_indptr"])), g["feat_indices"]] = g["featn_data"]
-    adj = torch.sparse_coo_tensor(torch.from_numpy(np.vstack([g["adj_row"], g["adj_col"]]).astype(np.int64)), torch.from_numpy(g["adj_val"]), (n, n))
-    return adj, torch.from_numpy(x), g["labels"].astype(np.int64)
 
 
 def _trainers(a, reps_list, arms):
@@ -56,10 +46,6 @@ def _trainers(a, reps_list, arms):
         masks, ids = np.tile(ten, (reps // 10, 1, 1)), np.tile(np.arange(10), reps // 10)
         yield reps, {name: split_train.SplitTrainBatch(adj, x, labels, masks, kind="gcn", hidden=HIDDEN, seed=1, replica_ids=ids, **kw)
                      for name, kw in arms.items()}
-
-
-def _summary(rounds):
-    return {"median_ms": statistics.median(rounds), "min_ms": min(rounds), "max_ms": max(rounds), "rounds_ms": rounds}
 
 
 def step_kernel(a):
@@ -83,22 +69,10 @@ def step_kernel(a):
         plain = ops.XentEvalBatch([dict(logits=logits, dlogits=torch.zeros_like(logits), labels=lab, split=codes,
                                         inv_n_train=torch.from_numpy((1.0 / counts[:, 0]).astype(np.float32)).cuda(), C=c, cs=cs)])
         arms = {"xent_curve (rows + finish)": lambda: curve.launch(step), "xent_eval EVAL (rows + select)": lambda: plain.launch(ops.XENT_EVAL, step)}
-        times = {k: [] for k in arms}
-        for rd in range(a.kernel_rounds + 1):  # (round 0 warms up)
-            for arm, fn in arms.items():
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                t0.record()
-                for _ in range(a.kernel_iters):
-                    fn()
-                t1.record()
-                torch.cuda.synchronize()
-                if rd:
-                    times[arm].append(t0.elapsed_time(t1) / a.kernel_iters * 1e3)
+        times = _time_arms(arms, a.kernel_rounds, a.kernel_iters)
         same = bool(torch.equal(curve.curve_of[0][1][5, :, 1:], plain.best_of[0][:, :2]))  # (one evaluation: its hits are the best)
         res = {"validation and test hits equal": same, "logits MB": n * reps * cs * 4 / 1e6}
-        for arm, t in times.items():
-            res[arm] = {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)}
+        res.update(times)
         out[f"R = {reps}"] = res
         print(json.dumps({f"R = {reps}": res}), flush=True)
     return out
@@ -108,11 +82,9 @@ def step_default(a):
     """(runs in this tree or, through --tree, in the parent's: the constructor is called as the parent takes it)"""
     out = {"tree": "parent" if os.path.abspath(a.tree) != ROOT else "new"}
     for reps, arms in _trainers(a, REPLICAS, {"default": {}}):
-        stb = arms["default"]
-        stb.run(epochs=a.epochs, capture=True)  # (the warm-up round captures)
-        out[f"R = {reps}"] = _summary([stb.run(epochs=a.epochs, capture=True)["seconds"] / a.epochs * 1e3 for _ in range(a.runs)])
+        out[f"R = {reps}"] = _ms_per_epoch(arms["default"], a)
         print(json.dumps({out["tree"]: {f"R = {reps}": out[f"R = {reps}"]}}), flush=True)
-        del stb, arms
+        del arms
     return out
 
 
@@ -120,12 +92,7 @@ def step_optin(a):
     out = {"workload": f"captured \"gcn\" epochs of the Cora fixture, hidden {HIDDEN}, dropout 0; per arm the median of {a.runs} rounds of {a.epochs} epochs, "
                        f"the arms alternating round by round in one process after a warm-up round each; ms per epoch of all replicas; feature = {FEATURE}"}
     for reps, arms in _trainers(a, REPLICAS, {"default": {}, "feature": FEATURE}):
-        for stb in arms.values():
-            stb.run(epochs=a.epochs, capture=True)
-        rounds = {name: [] for name in arms}
-        for _ in range(a.runs):
-            for name, stb in arms.items():
-                rounds[name].append(stb.run(epochs=a.epochs, capture=True)["seconds"] / a.epochs * 1e3)
+        rounds = _epoch_rounds({name: (lambda rnd, stb=stb: stb.run(epochs=a.epochs, capture=True)) for name, stb in arms.items()}, a.runs, a.epochs, warmup=1)
         off, on = statistics.median(rounds["default"]), statistics.median(rounds["feature"])
         res = {"default median_ms": off, "feature median_ms": on, "added us per epoch": (on - off) * 1e3, "feature over default": on / off,
                "rounds_ms default": rounds["default"], "rounds_ms feature": rounds["feature"]}
@@ -135,7 +102,10 @@ def step_optin(a):
     return out
 
 
-def main():
+STEP_FNS = {"kernel": step_kernel, "default": step_default, "optin": step_optin}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=100)
@@ -147,33 +117,19 @@ def main():
     ap.add_argument("--tree", default=ROOT, help="(with --step) the checkout whose package is imported")
     ap.add_argument("--part", help="(with --step) where the step writes its part of the document")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "xent_curve_timing.json"))
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def invocations(a):
+    trees = ([os.path.abspath(a.parent), ROOT] if a.parent else [ROOT]) * a.processes  # parent, new, parent, new, ...
+    return [Step("kernel", "kernel", 240, tree=ROOT)] + [Step("default", "default", 300, tree=tree) for tree in trees] + [Step("optin", "optin", 600, tree=ROOT)]
+
+
+def main():
+    a = parse()
     if a.step:
-        sys.path.insert(0, os.path.abspath(a.tree))
-        import torch
-        assert torch.cuda.is_available(), "needs a HIP device"
-        doc = {"kernel": step_kernel, "default": step_default, "optin": step_optin}[a.step](a)
-        doc["device"] = torch.cuda.get_device_name(0)
-        with open(a.part, "w") as f:
-            json.dump(doc, f)
-        return
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    steps = [("kernel", ROOT, 240)]
-    for tree in ([a.parent, ROOT] if a.parent else [ROOT]) * a.processes:
-        steps.append(("default", os.path.abspath(tree), 300))
-    steps.append(("optin", ROOT, 600))
-    parts = []
-    for i, (step, tree, limit) in enumerate(steps):  # each step in a fresh process under its own time limit; the first failure ends the run
-        part = f"{a.out}.{i}.part"
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--tree", tree, "--part", part, "--runs", str(a.runs),
-               "--epochs", str(a.epochs), "--kernel-rounds", str(a.kernel_rounds), "--kernel-iters", str(a.kernel_iters)]
-        rc = subprocess.call(cmd)
-        if rc != 0:
-            if os.path.exists(part):
-                os.remove(part)
-            sys.exit(f"step {step!r} ended with status {rc}: stopping")
-        parts.append((step, json.load(open(part))))
-        os.remove(part)
+        return run_step(a, STEP_FNS, a.tree)
+    parts = run_steps(__file__, invocations(a), flags(a, "runs", "epochs", "kernel_rounds", "kernel_iters"), a.out)
     doc = {"kernel": parts[0][1], "optin": parts[-1][1]}
     runs = [p for s, p in parts if s == "default"]
     default = {"workload": f"Cora fixture, \"gcn\", hidden {HIDDEN}, the defaults (no curve table); per process the median of {a.runs} rounds of {a.epochs} "
@@ -188,9 +144,7 @@ def main():
             default["yardstick"][key] = {"parent_ms": old, "new_ms": new, "bound_ms": bound, "passed": statistics.median(new) <= bound,
                                          "new over parent": statistics.median(new) / statistics.median(old)}
     doc["default"] = default
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    write(a.out, doc)
     failed = [f"the default-path yardstick at {key}" for key in (f"R = {reps}" for reps in REPLICAS) if a.parent and not default["yardstick"][key]["passed"]]
     for what in failed:
         print(f"NOT MET: {what} (see {a.out})", flush=True)
