@@ -11,7 +11,9 @@ LAST     := $(CSRC)/keep_best.hip $(CSRC)/confusion.hip $(CSRC)/xent_curve.hip $
 LAST     += $(CSRC)/neighbor_sample.hip
 # ... and behind it the neighbour maximum (neighbor_max), again on a line of its own
 LAST     += $(CSRC)/neighbor_max.hip
-SRCS     := $(filter-out $(LAST),$(SRCS)) $(LAST)
+# ... and behind every one of them the recurrence filter (recur_filter), in a list of its own: the lines above end where tests/test_abi_neighbor_max.py reads them
+AFTER    := $(CSRC)/recur_filter.hip
+SRCS     := $(filter-out $(LAST) $(AFTER),$(SRCS)) $(LAST) $(AFTER)
 LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and
 # nothing else) must unroll completely (their register indices and branch conditions are compile-time only then) - with the
@@ -39,6 +41,8 @@ FLAGS_gat_scores := -ffp-contract=off
 FLAGS_signed_att := -ffp-contract=off
 # poly_filter.hip's chains, butterflies and fp64 sums are stated operation by operation in include/wdg.h: every fmaf is written out, nothing else is fused
 FLAGS_poly_filter := -ffp-contract=off
+# recur_filter.hip's hop is poly_filter.hip's row sum (csrc/filter_rows.h) and the recurrence's fmafs, stated in include/wdg.h: every fmaf is written out, nothing else is fused
+FLAGS_recur_filter := -ffp-contract=off
 # topk_rows.hip's key is ONE rounded product and its row norm an fmaf chain written out in include/wdg.h: nothing else is fused (the source says so as well)
 FLAGS_topk_rows := -ffp-contract=off
 # gcnii.hip's layer and its backward pass are stated operation by operation in include/wdg.h and restated in numpy bit for bit: every fmaf is written out, nothing else is fused

@@ -1981,6 +1981,63 @@ int32_t wdg_poly_filter_max_rows(int32_t group_cols);
 int64_t wdg_poly_filter_partials_len(int32_t n, int32_t cols, int32_t order);
 
 /*
+ * A graph filter in a basis of ORTHOGONAL polynomials, of many graphs in one launch (the propagation of ChebNet / ChebNetII: He, Wei,
+ * Wen, "Convolutional Neural Networks on Graphs with Chebyshev Approximation, Revisited"; of JacobiConv: Wang, Zhang, "How Powerful
+ * are Spectral Graph Neural Networks"): out = sum_{k = 0..K} gamma_k T_k with the three-term recurrence every such basis obeys,
+ *   T_{k+1} = a_k A_hat T_k + b_k T_k + c_k T_{k-1},
+ * all K hops of a few columns inside ONE workgroup.  The reference ships no model code: the filter is DEFINED here and
+ * is not claimed to reproduce an upstream table.
+ * replaces: the ONE fixed aggregation of normalize_tensor / the SGC and GCN tables (utils/util_funcs.py:365-381, gnns_on_syn.py:1-154)
+ *           by K of them combined through a three-term recurrence, for the spectral baselines that stand beside those tables.
+ * A job: every member of wdg_poly_filter_job with the same meaning, and recur fp32 [order, 3] in DEVICE memory with leading dimension
+ * ld_recur >= 3: row k is (a_k, b_k, c_k), shared by all segments of the job.  recur may be NULL only when order == 0.
+ * The definition, for column c of segment s and row i: let P[i, c] be EXACTLY the polynomial filter's hop of T_k stated above - the
+ * lane chains (fmaf chains from +0 over the entries beg + l, beg + l + L, ...; coef_p = val[p] * col_scale[j] ONE rounded product),
+ * the butterfly over the distances L/2 .. 1, then ONE product with row_scale[i].  Then
+ *   T_0 = v
+ *   T_1[i, c] = fmaf(a_0, P, b_0 * T_0[i, c])                                      c_0 is not read
+ *   T_{k+1}[i, c] = fmaf(a_k, P, fmaf(b_k, T_k[i, c], c_k * T_{k-1}[i, c]))        for k >= 1
+ *   out[i, c] = gamma[0, s] * v[i, c], then for k = 1..K in ascending order out[i, c] = fmaf(gamma[k, s], T_k[i, c], out[i, c])
+ *   dots[k, s]: the polynomial filter's fp64 order, unchanged, applied to this kernel's T_k.
+ * With the table (1, 0, 0) in every row the result compares == with the polynomial filter's on finite inputs (fmaf(1, P, 0 * T) = P up
+ * to the sign of a zero).  Everything the polynomial filter's comment says about orders, tables, group_cols, segments and views holds
+ * here: a job has the same bits alone and inside any table, a column the same bits for group_cols 1, 2 and 4 and the bits of a
+ * one-segment job on its slice, order 0 gives exactly gamma[0, s] * v, columns outside a view are never written; a job whose
+ * gamma[:, s] is the unit vector e_k returns exactly T_k.  Because T_k = p_k(A_hat) v, the backward pass is one more job: on the
+ * transposed pattern with the two scales swapped and the SAME table, v = d_out and u = H0 give out = d_H0 and dots = d_gamma.
+ * No floating-point atomic anywhere; csrc/recur_filter.hip is compiled with contraction off and writes every fmaf out.
+ * Shape and limits: the polynomial filter's launch - grid (column groups, jobs), 1024 threads, teams of WDG_POLY_FILTER_TEAM lanes, a
+ * wave for rows of more than WDG_POLY_FILTER_LONG_ROW entries, the two images of 2 * n * group_cols * 4 bytes of LDS.  During hop k
+ * the image that takes T_{k+1} still holds T_{k-1}; row i of it is read and written by row i's owner alone, which reads T_k[i, :] and
+ * T_{k-1}[i, :] with the row's other loads, before its first store: NO LDS beyond the polynomial filter's, so the row limits are
+ * wdg_poly_filter_max_rows(group_cols) = 20448, 10224, 5112 and the workspace is wdg_poly_filter_partials_len doubles.
+ * max_groups, max_floats, max_dot_rows and the refusals before any launch: as for wdg_poly_filter_batched_f32.  What is wrong inside
+ * a job - everything wdg_poly_filter_check_jobs refuses, and a NULL recur or ld_recur < 3 with order > 0 - is refused by
+ * wdg_recur_filter_check_jobs on the HOST copy of the table (train.RecurFilterBatch calls it before it uploads); both launches skip
+ * such a job.
+ */
+typedef struct wdg_recur_filter_job {
+    const int32_t *rowptr;    /* [n + 1] */
+    const int32_t *col;       /* [nnz] */
+    const float *val;         /* [nnz], or NULL = 1 */
+    const float *row_scale;   /* [n], or NULL = 1 */
+    const float *col_scale;   /* [n], or NULL = 1 */
+    const float *v;           /* [n, cols] */
+    float *out;               /* [n, cols] */
+    const float *gamma;       /* [order + 1, n_seg], device memory */
+    const float *u;           /* [n, cols], or NULL: no dots */
+    float *dots;              /* [order + 1, n_seg], or NULL */
+    double *partials;         /* workspace of wdg_poly_filter_partials_len doubles, with dots */
+    const float *recur;       /* [order, 3]: row k = (a_k, b_k, c_k), device memory; NULL only with order == 0 */
+    int64_t ld_v, ld_out, ld_gamma, ld_u, ld_dots, ld_recur;
+    int32_t n, nnz, cols, seg_cols, order, group_cols;
+} wdg_recur_filter_job;
+int wdg_recur_filter_batched_f32(const wdg_recur_filter_job *jobs_dev, int32_t n_jobs, int32_t max_groups, int32_t max_floats, int32_t max_dot_rows,
+                                 wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the filter above (utils/util_funcs.py:365-381), on the host's table */
+int wdg_recur_filter_check_jobs(const wdg_recur_filter_job *jobs_host, int32_t n_jobs);
+
+/*
  * The strict two-hop neighbourhood of many graphs (the second aggregation pattern of H2GCN: Zhu et al., "Beyond Homophily in Graph
  * Neural Networks"), built on the device for a table of jobs in two launches.  The reference computes no pattern product: the
  * result is DEFINED here and is not claimed to reproduce an upstream table.

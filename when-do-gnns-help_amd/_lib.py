@@ -204,6 +204,8 @@ SIGNATURES = {
     "wdg_poly_filter_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_poly_filter_max_rows": (c_int32, [c_int32]),
     "wdg_poly_filter_partials_len": (c_int64, [c_int32, c_int32, c_int32]),
+    "wdg_recur_filter_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_recur_filter_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_two_hop_max_rows": (c_int32, []),
     "wdg_csr_two_hop_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_two_hop_count_batched": (c_int, [c_void_p, c_int32, c_int32, c_void_p]),
@@ -454,6 +456,13 @@ class PolyFilterJob(ctypes.Structure):
     """mirror of `wdg_poly_filter_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "val", "row_scale", "col_scale", "v", "out", "gamma", "u", "dots", "partials")] + \
                [(name, c_int64) for name in ("ld_v", "ld_out", "ld_gamma", "ld_u", "ld_dots")] + \
+               [(name, c_int32) for name in ("n", "nnz", "cols", "seg_cols", "order", "group_cols")]
+
+
+class RecurFilterJob(ctypes.Structure):
+    """mirror of `wdg_recur_filter_job` (include/wdg.h): PolyFilterJob's members, the recurrence table and its leading dimension"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "val", "row_scale", "col_scale", "v", "out", "gamma", "u", "dots", "partials", "recur")] + \
+               [(name, c_int64) for name in ("ld_v", "ld_out", "ld_gamma", "ld_u", "ld_dots", "ld_recur")] + \
                [(name, c_int32) for name in ("n", "nnz", "cols", "seg_cols", "order", "group_cols")]
 
 

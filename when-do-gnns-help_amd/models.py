@@ -60,9 +60,17 @@ neighbours of a ReLU transform - the one aggregation here that is not a weighted
 csrc/neighbor_max.hip, forward (it keeps which neighbour won) and backward (one job on the transposed pattern), over a NormAdj's stored
 pattern and over the thinned views of NeighborSampleAdj / DropEdgeAdj alike.  Defined by this project as well (the paper's layer
 without its bias).
+
+ChebNetII-1 / -2 and JacobiConv-1 / -2 (`ChebNetII1`, `ChebNetII2`, `JacobiConv1`, `JacobiConv2`) are GPR-GNN's filter in an
+ORTHOGONAL polynomial basis - Chebyshev polynomials of -A_hat with coefficients reparametrised by Chebyshev interpolation (He, Wei, Wen,
+"Convolutional Neural Networks on Graphs with Chebyshev Approximation, Revisited"), Jacobi polynomials of A_hat with a filter per class
+column (Wang, Zhang, "How Powerful are Spectral Graph Neural Networks") - whose three-term recurrence (`recurrence_table`) runs all K hops
+in one launch of csrc/recur_filter.hip, in the LDS the monomial filter uses; the backward pass is one more launch of the same kernel on the
+transposed pattern.  Defined by this project as well.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import ops
@@ -778,6 +786,226 @@ class GPRGNN2(_HiddenDropout, _GPRBase):
         self.w0, self.w1 = _xavier(nfeat, nhid), _xavier(nhid, nclass)
         self.dropout, self.dropout_rng = dropout, dropout_rng
         self._init_filter(order, alpha, learn, fused, fused_max_rows)
+
+    def forward(self, adj, x):
+        h = self._relu_dropout_of_product(x, self.w0)
+        return self._filter(adj, _Linear.apply(h, self.w1, False), self.gamma)
+
+
+BASES = ("monomial", "chebyshev", "jacobi", "legendre")
+
+
+def recurrence_table(basis, order, alpha=1.0, beta=1.0):
+    """The three-term recurrence of a polynomial basis as ops.RecurFilterBatch takes it -> a float64 array [order, 3] whose row k - 1
+    holds the (a, b, c) that make T_k = a A_hat T_{k-1} + b T_{k-1} + c T_{k-2} (T_0 = 1; the c of row 0 is 0 and is not read).
+      "monomial"   T_k = A_hat^k: (1, 0, 0) - the filter of GPR-GNN
+      "chebyshev"  T_k(x) of the first kind in x = -A_hat (L - I for the symmetric normalisation without self loops): (-1, 0, 0), then
+                   (-2, 0, -1)
+      "jacobi"     P_k^(alpha, beta)(x) in x = A_hat, alpha, beta > -1: row 0 is ((alpha + beta + 2) / 2, (alpha - beta) / 2, 0); for
+                   k >= 2 with s = 2 k + alpha + beta: a = s (s - 1) / (2 k (k + alpha + beta)),
+                   b = (s - 1) (alpha^2 - beta^2) / (2 k (k + alpha + beta) (s - 2)),
+                   c = -(k + alpha - 1) (k + beta - 1) s / (k (k + alpha + beta) (s - 2))
+      "legendre"   jacobi with alpha = beta = 0 (the arguments are not read)"""
+    if basis not in BASES:
+        raise ValueError(f"recurrence_table: basis {basis!r}; one of {BASES} expected")
+    if order < 0:
+        raise ValueError(f"recurrence_table: order {order}; a count of hops expected")
+    tab = np.zeros((order, 3), np.float64)
+    if basis == "monomial":
+        tab[:, 0] = 1.0
+    elif basis == "chebyshev":
+        tab[:, 0], tab[1:, 2] = -2.0, -1.0
+        tab[:1, 0] = -1.0
+    else:
+        al, be = (0.0, 0.0) if basis == "legendre" else (float(alpha), float(beta))
+        if not (al > -1.0 and be > -1.0):
+            raise ValueError(f"recurrence_table: Jacobi polynomials need alpha, beta > -1, got {alpha}, {beta}")
+        tab[:1] = ((al + be + 2.0) / 2.0, (al - be) / 2.0, 0.0)
+        for k in range(2, order + 1):
+            s = 2.0 * k + al + be
+            den = k * (k + al + be) * (s - 2.0)
+            # (s - 2 = 0 only for k = 1; k + alpha + beta > 0 from k = 2 on)
+            tab[k - 1] = (s * (s - 1.0) * (s - 2.0) / (2.0 * den), (s - 1.0) * (al * al - be * be) / (2.0 * den), -(k + al - 1.0) * (k + be - 1.0) * s / den)
+    return tab
+
+
+def chebyshev_interpolation_map(order):
+    """ChebNetII's fixed map from the filter's values at the Chebyshev nodes to its Chebyshev coefficients -> float64 [K + 1, K + 1]:
+    gamma = M theta with M[k, j] = (2 / (K + 1)) T_k(x_j), row 0 halved, x_j = cos((j + 1/2) pi / (K + 1)): then
+    sum_k gamma_k T_k(x_j) = theta_j, and for theta_j = h(x_j) with h a polynomial of degree <= K the sum IS h."""
+    K = int(order)
+    j = np.arange(K + 1, dtype=np.float64)
+    m = (2.0 / (K + 1)) * np.cos(np.outer(j, (j + 0.5) * np.pi / (K + 1)))  # T_k(cos t) = cos(k t)
+    m[0] *= 0.5
+    return m
+
+
+def chebyshev_nodes(order):
+    """x_j = cos((j + 1/2) pi / (K + 1)), j = 0..K -> float64 [K + 1]"""
+    return np.cos((np.arange(order + 1, dtype=np.float64) + 0.5) * np.pi / (order + 1))
+
+
+class _RecurFilterLayer(_OneJobLayer):
+    """The filter F(H0; gamma) = sum_k gamma_k T_k, T_{k+1} = a_k A_hat T_k + b_k T_k + c_k T_{k-1} (include/wdg.h:
+    wdg_recur_filter_batched_f32) and its backward pass, both on csrc/recur_filter.hip through two one-job ops.RecurFilterBatch tables per
+    (graph, rows, cols) - _PolyFilterLayer's sibling.  T_k = p_k(A_hat) H0, so the backward table is ONE more job of the same kernel on
+    graph_t with the two scales swapped and the same recurrence table, v = d_out and u = H0: its out is d_H0 and its dots are d_gamma.
+    gamma is [order + 1, n_seg]: per_channel - a column of coefficients per column of H0 (seg_cols = 1) - or one segment.
+    max_rows: the largest graph that takes the fused route (None: what one column of the kernel holds); a larger one, or fused=False,
+    runs hop by hop on adj.matmul and torch operations with autograd's backward - the route a DropEdgeAdj / NeighborSampleAdj view
+    takes (on the fused route it has no stored pattern to hand over: a TypeError, as for GPRGNN1 / GPRGNN2)."""
+
+    operands, restore_launches = ("h", "gamma"), False
+
+    def __init__(self, table, per_channel=False, fused=True, max_rows=None):
+        table = np.asarray(table, np.float64)
+        if table.ndim != 2 or table.shape[1] != 3 or not np.isfinite(table).all():
+            raise ValueError("a recurrence table is a finite [order, 3] array of (a, b, c)")
+        if not 0 <= table.shape[0] <= ops.RecurFilterBatch.MAX_ORDER:
+            raise ValueError(f"a recurrence filter of order {table.shape[0]}: the kernel runs 0..{ops.RecurFilterBatch.MAX_ORDER} hops")
+        super().__init__()
+        self.recur, self.order, self.per_channel, self.fused, self.max_rows = table, table.shape[0], bool(per_channel), bool(fused), max_rows
+
+    def is_fused(self, rows):
+        limit = ops.RecurFilterBatch.max_rows(1) if self.max_rows is None else min(int(self.max_rows), ops.RecurFilterBatch.max_rows(1))
+        return self.fused and rows <= limit
+
+    def keyed_on(self, adj):
+        return (adj,)  # (for its scales as well)
+
+    def build(self, adj, rows, cols, z):
+        n_seg = cols if self.per_channel else 1
+        h, out, d_out, d_h = z(rows, cols), z(rows, cols), z(rows, cols), z(rows, cols)
+        gamma, d_gamma = z(self.order + 1, n_seg), z(self.order + 1, n_seg)
+        recur = torch.from_numpy(self.recur.astype(np.float32)).to(h.device) if self.order else None
+        shared = dict(gamma=gamma, order=self.order, seg_cols=cols // n_seg, recur=recur)
+        fwd = ops.RecurFilterBatch([dict(shared, graph=adj.graph, row_scale=adj.row_scale, col_scale=adj.col_scale, v=h, out=out)])
+        bwd = ops.RecurFilterBatch([dict(shared, graph=adj.graph_t, row_scale=adj.col_scale, col_scale=adj.row_scale, v=d_out, out=d_h, u=h,
+                                         dots=d_gamma)])  # (R A C)^T = C A^T R
+        return dict(h=h, out=out, gamma=gamma, d_out=d_out, d_h=d_h, d_gamma=d_gamma), fwd, bwd.launch
+
+    def gradients(self, b, gy, needs):
+        return b["d_h"].clone(), (b["d_gamma"].clone() if needs[1] else None)
+
+    def __call__(self, adj, h, gamma):
+        """h [n, cols], gamma [order + 1, n_seg] -> F(h; gamma) [n, cols]"""
+        if gamma.shape != (self.order + 1, h.shape[1] if self.per_channel else 1):
+            raise ValueError(f"a filter of order {self.order} over {h.shape[1]} columns{' per channel' if self.per_channel else ''}: gamma of shape "
+                             f"{tuple(gamma.shape)}")
+        if self.is_fused(h.shape[0]):
+            return _OneJob.apply(self, adj, h, gamma)
+        t, t_prev, out = h, None, gamma[0] * h
+        for k in range(self.order):
+            a, b, c = (float(x) for x in self.recur[k])
+            t_next = a * adj.matmul(t)
+            if b != 0.0:
+                t_next = t_next + b * t
+            if k > 0 and c != 0.0:
+                t_next = t_next + c * t_prev
+            t_prev, t = t, t_next
+            out = out + gamma[k + 1] * t
+        return out
+
+
+class _ChebNetIIBase(torch.nn.Module):
+    def _init_filter(self, order, fused, fused_max_rows):
+        self.order = int(order)
+        self.theta = torch.nn.Parameter(torch.ones(self.order + 1))  # (the filter's values at the Chebyshev nodes: all 1 is the identity)
+        self.register_buffer("interpolation", torch.from_numpy(chebyshev_interpolation_map(self.order)).to(torch.float32), persistent=False)
+        self._filter = _RecurFilterLayer(recurrence_table("chebyshev", self.order), False, fused, fused_max_rows)
+
+    def _gamma(self):
+        # (a product and a row sum of torch's own, no BLAS call: the same kernels eagerly and inside a captured step)
+        return (self.interpolation.to(self.theta.dtype) * torch.relu(self.theta)).sum(1, keepdim=True)
+
+    def filter_coefficients(self):
+        """-> the current Chebyshev coefficients gamma [order + 1] as a host numpy array: what the forward pass hands the filter (the map
+        is an fp32 buffer)"""
+        return self._gamma().detach().reshape(-1).cpu().numpy().copy()
+
+    def filter_response(self, x):
+        """sum_k gamma_k T_k(x) at the points x of [-1, 1] (the eigenvalues of -A_hat; x = lambda_L - 1 for the symmetric normalisation),
+        evaluated on the host in float64 from the current theta -> a float64 array of x's shape"""
+        gamma = chebyshev_interpolation_map(self.order) @ np.maximum(self.theta.detach().double().cpu().numpy(), 0.0)
+        return np.polynomial.chebyshev.chebval(np.asarray(x, np.float64), gamma)
+
+
+class ChebNetII1(_ChebNetIIBase):
+    """ChebNetII-1: logits = sum_k gamma_k T_k(-A_hat) (X W), T_k the Chebyshev polynomials of the first kind, with the coefficients
+    reparametrised by Chebyshev interpolation (He, Wei, Wen, "Convolutional Neural Networks on Graphs with Chebyshev Approximation,
+    Revisited"): theta [order + 1] - learnt, all 1 at the start: the identity filter - are the filter's values at the nodes
+    x_j = cos((j + 1/2) pi / (order + 1)) and gamma_k = (2 / (order + 1)) sum_j relu(theta_j) T_k(x_j), gamma_0 halved - a fixed
+    matrix (chebyshev_interpolation_map) that autograd carries.  Bias-free; defined by this project, not claimed to reproduce
+    an upstream table.  Recommended graph: NormAdj(adj, symmetric=1, add_self_loops=False), whose -A_hat is L - I with a spectrum in
+    [-1, 1]; any NormAdj works.  fused=True: all hops in one launch of csrc/recur_filter.hip, forward and backward; fused=False, or a
+    graph of more rows than the kernel holds in LDS at one column (fused_max_rows lowers that limit), runs hop by hop.
+    Parameters are drawn in this order: W (xavier_uniform, [nfeat, nclass]), then theta (deterministic)."""
+
+    def __init__(self, nfeat, nclass, order=10, fused=True, fused_max_rows=None):
+        super().__init__()
+        self.weight = _xavier(nfeat, nclass)
+        self._init_filter(order, fused, fused_max_rows)
+
+    def forward(self, adj, x):
+        return self._filter(adj, _Linear.apply(x, self.weight, False), self._gamma())
+
+
+class ChebNetII2(_HiddenDropout, _ChebNetIIBase):
+    """ChebNetII-2: logits = F(relu_dropout(X W0) W1) with ChebNetII1's filter F; bias-free, feature dropout only (GCN2's two routes:
+    dropout_rng None - torch's - or a DeviceDropout), no dropout between the hops.  DESIGN 4.36.
+    Parameters are drawn in this order: W0 (xavier_uniform, [nfeat, nhid]), W1 (xavier_uniform, [nhid, nclass]), then theta."""
+
+    def __init__(self, nfeat, nclass, nhid=64, order=10, dropout=0.5, dropout_rng=None, fused=True, fused_max_rows=None):
+        super().__init__()
+        self.w0, self.w1 = _xavier(nfeat, nhid), _xavier(nhid, nclass)
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._init_filter(order, fused, fused_max_rows)
+
+    def forward(self, adj, x):
+        h = self._relu_dropout_of_product(x, self.w0)
+        return self._filter(adj, _Linear.apply(h, self.w1, False), self._gamma())
+
+
+class _JacobiBase(torch.nn.Module):
+    def _init_filter(self, nclass, order, alpha, beta, ppr_alpha, per_channel, fused, fused_max_rows):
+        start = ppr_coefficients(order, ppr_alpha).unsqueeze(1)
+        self.gamma = torch.nn.Parameter(start.repeat(1, nclass if per_channel else 1).contiguous())
+        self._filter = _RecurFilterLayer(recurrence_table("jacobi", order, alpha, beta), per_channel, fused, fused_max_rows)
+
+    def filter_coefficients(self):
+        """-> the current gamma [order + 1, nclass] (per_channel) or [order + 1, 1] as a host numpy array"""
+        return self.gamma.detach().cpu().numpy().copy()
+
+
+class JacobiConv1(_JacobiBase):
+    """JacobiConv-1: logits = sum_k gamma_k P_k^(alpha, beta)(A_hat) (X W), P_k the Jacobi polynomials (alpha = beta = 0: Legendre) -
+    Wang, Zhang, "How Powerful are Spectral Graph Neural Networks", WITHOUT the paper's tanh reparametrisation of the coefficients;
+    alpha and beta are fixed.  per_channel=True (the default): gamma is [order + 1, nclass], a filter of its own per class column -
+    in the kernel a segment per column; per_channel=False: one filter, gamma [order + 1, 1].  gamma starts at
+    ppr_coefficients(order, ppr_alpha) in every column.  Bias-free; defined by this project, not claimed to reproduce an
+    upstream table.  Recommended graph: NormAdj(adj, symmetric=1, add_self_loops=False); any NormAdj works.  fused / fused_max_rows:
+    as for ChebNetII1.  Parameters are drawn in this order: W (xavier_uniform, [nfeat, nclass]), then gamma (deterministic)."""
+
+    def __init__(self, nfeat, nclass, order=10, alpha=1.0, beta=1.0, ppr_alpha=0.1, per_channel=True, fused=True, fused_max_rows=None):
+        super().__init__()
+        self.weight = _xavier(nfeat, nclass)
+        self._init_filter(nclass, order, alpha, beta, ppr_alpha, per_channel, fused, fused_max_rows)
+
+    def forward(self, adj, x):
+        return self._filter(adj, _Linear.apply(x, self.weight, False), self.gamma)
+
+
+class JacobiConv2(_HiddenDropout, _JacobiBase):
+    """JacobiConv-2: logits = F(relu_dropout(X W0) W1) with JacobiConv1's filter F; bias-free, feature dropout only (GCN2's two routes:
+    dropout_rng None - torch's - or a DeviceDropout), no dropout between the hops.  DESIGN 4.36.
+    Parameters are drawn in this order: W0 (xavier_uniform, [nfeat, nhid]), W1 (xavier_uniform, [nhid, nclass]), then gamma."""
+
+    def __init__(self, nfeat, nclass, nhid=64, order=10, alpha=1.0, beta=1.0, ppr_alpha=0.1, dropout=0.5, dropout_rng=None, per_channel=True, fused=True,
+                 fused_max_rows=None):
+        super().__init__()
+        self.w0, self.w1 = _xavier(nfeat, nhid), _xavier(nhid, nclass)
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+        self._init_filter(nclass, order, alpha, beta, ppr_alpha, per_channel, fused, fused_max_rows)
 
     def forward(self, adj, x):
         h = self._relu_dropout_of_product(x, self.w0)

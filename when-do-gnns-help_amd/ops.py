@@ -31,6 +31,8 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         times the fixed scales, an optional residual),
                         PolyFilterBatch (the polynomial graph filter sum_k gamma_k A_hat^k v of many graphs, all hops in one launch, with
                         the dot products that are the coefficients' gradient),
+                        RecurFilterBatch (the same filter in a basis with a three-term recurrence - Chebyshev, Jacobi, Legendre - sum_k gamma_k T_k,
+                        T_{k+1} = a_k A_hat T_k + b_k T_k + c_k T_{k-1}, all hops in one launch at the polynomial filter's row limits),
                         GcniiBatch (the GCNII layer behind its aggregation for many layers / graphs in one launch: initial residual, identity
                         mapping, ReLU + counter-based dropout, with a backward pass and a weight gradient summed in a stated order),
                         XentEvalBatch (cross-entropy gradient, hits and model selection of many models with stacked logits),
@@ -82,7 +84,7 @@ from .stats import (  # noqa: F401
 from .gemm import (  # noqa: F401
     gemm, gemm_skinny, GemmBatch, Mlp2Batch,
 )
-from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, GatBatch, GatScoresBatch, GcniiBatch, HeadTrainBatch, KeepBestBatch, PolyFilterBatch, SignedAttBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
+from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch, AucBatch, ConfusionBatch, DropoutBatch, GatBatch, GatScoresBatch, GcniiBatch, HeadTrainBatch, KeepBestBatch, PolyFilterBatch, RecurFilterBatch, SignedAttBatch, XentCurveBatch, XentEvalBatch, AUC_RULE, SELECT_RULES, XENT_EVAL, XENT_GRAD  # noqa: F401
 from .drop_edge import DropEdgeBatch, ThinnedPattern, ThinnedSpmmBatch, DROP_EDGE_KEEP_DIAGONAL, DROP_EDGE_NORM_SYM, DROP_EDGE_TIED, DROP_EDGE_TRANSPOSED  # noqa: F401
 from .neighbor_sample import NeighborSampleBatch, NEIGHBOR_SAMPLE_KEEP_DIAGONAL, NEIGHBOR_SAMPLE_NORM_SYM, NEIGHBOR_SAMPLE_TRANSPOSED  # noqa: F401
 from .neighbor_max import neighbor_max, NeighborMaxBackwardBatch, NeighborMaxBatch, NEIGHBOR_MAX_MIN  # noqa: F401

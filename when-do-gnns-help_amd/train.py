@@ -11,6 +11,8 @@
   with its backward pass
 - csrc/poly_filter.hip: the polynomial graph filter of many graphs (GPR-GNN-1, GPR-GNN-2; APPNP): all K hops of sum_k gamma_k A_hat^k v in one launch,
   with the dot products that are the coefficients' gradient
+- csrc/recur_filter.hip: the same filter in a basis with a three-term recurrence (ChebNetII-1 / -2, JacobiConv-1 / -2): all K hops of
+  sum_k gamma_k T_k, T_{k+1} = a_k A_hat T_k + b_k T_k + c_k T_{k-1}, in one launch and in the polynomial filter's LDS
 - csrc/gcnii.hip: the GCNII layer behind its aggregation (GCNII: initial residual + identity mapping + ReLU + dropout in one launch) with its
   backward pass and the weight gradient of all the layers of a model in one launch
 - csrc/xent_eval.hip: the tail of an epoch - cross-entropy gradient, hits, model selection - of many models with stacked logits
@@ -42,6 +44,7 @@ _GAT_JOB_DTYPE = np.dtype(_lib.GatJob)
 _GAT_SCORES_JOB_DTYPE = np.dtype(_lib.GatScoresJob)
 _SIGNED_ATT_JOB_DTYPE = np.dtype(_lib.SignedAttJob)
 _POLY_FILTER_JOB_DTYPE = np.dtype(_lib.PolyFilterJob)
+_RECUR_FILTER_JOB_DTYPE = np.dtype(_lib.RecurFilterJob)
 _GCNII_JOB_DTYPE = np.dtype(_lib.GcniiJob)
 _XENT_JOB_DTYPE = np.dtype(_lib.XentJob)
 _ADAM_JOB_DTYPE = np.dtype(_lib.AdamJob)
@@ -664,6 +667,8 @@ class PolyFilterBatch(JobTable):
 
     MAX_JOBS, MAX_ORDER, GROUPS, DOT_ROWS, TEAM, LONG_ROW = 65535, 64, (4, 2, 1), 32, 4, 128
     _KEYS = ("graph", "v", "out", "gamma", "order", "row_scale", "col_scale", "seg_cols", "u", "dots", "group")
+    _RECORD, _CHECK, _ENTRY = _POLY_FILTER_JOB_DTYPE, "wdg_poly_filter_check_jobs", "wdg_poly_filter_batched_f32"
+    _REQUIRED, _DEVICE_INPUTS = ("graph", "v", "out", "gamma", "order"), ("v", "out", "u", "gamma", "dots", "row_scale", "col_scale")
 
     @staticmethod
     def max_rows(group):
@@ -687,15 +692,15 @@ class PolyFilterBatch(JobTable):
         Raises ValueError for unknown keys, an order outside 0..64, cols no multiple of seg_cols, u without dots or dots without u, a
         group outside {1, 2, 4}, a graph over the row limit of its group, other dtypes, shapes or strides, more than 65535 entries, an
         output (out, dots) that overlaps an input or another output of its entry."""
-        name = "PolyFilterBatch"
+        name = type(self).__name__
         self._open(entries)
         shapes = []
         for e in entries:
             unknown = set(e) - set(self._KEYS)
             if unknown:
                 raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
-            if any(e.get(k) is None for k in ("graph", "v", "out", "gamma", "order")):
-                raise ValueError(f"{name}: graph, v, out, gamma and order are required")
+            if any(e.get(k) is None for k in self._REQUIRED):
+                raise ValueError(f"{name}: {', '.join(self._REQUIRED[:-1])} and {self._REQUIRED[-1]} are required")
             g = e["graph"]
             if g.n_rows != g.n_cols:
                 raise ValueError(f"{name}: a square graph expected, got {g.n_rows} x {g.n_cols}")
@@ -729,6 +734,7 @@ class PolyFilterBatch(JobTable):
                 if e.get(k) is not None:
                     GatBatch._matrix(k, e[k], (order + 1, n_seg), name)
                     mats[k] = e[k]
+            self._more_operands(e, order, mats)
             for k in ("row_scale", "col_scale"):
                 t = e.get(k)
                 if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous()):
@@ -739,9 +745,9 @@ class PolyFilterBatch(JobTable):
                     if (ka in ("out", "dots") or kb in ("out", "dots")) and _views_may_overlap(ta, tb):
                         raise ValueError(f"{name}: {ka} and {kb} overlap; an output must not overlap an input or another output")
             shapes.append((n, g.nnz, cols, seg_cols, order, group))
-        tab = self._records(_POLY_FILTER_JOB_DTYPE)
+        tab = self._records(self._RECORD)
         for e in entries:
-            tensors = [e[k] for k in ("v", "out", "u", "gamma", "dots", "row_scale", "col_scale") if e.get(k) is not None]
+            tensors = [e[k] for k in self._DEVICE_INPUTS if e.get(k) is not None]
             tensors += [t for t in (e["graph"].rowptr, e["graph"].col, e["graph"].val) if t is not None]
             if any(t.device != self._dev for t in tensors):
                 raise ValueError(f"{name}: every tensor of an entry must live on the device {self._dev}")
@@ -763,11 +769,44 @@ class PolyFilterBatch(JobTable):
         self.max_groups = max((s_[2] // s_[3] * -(-s_[3] // s_[5]) for s_ in shapes), default=0)
         self.max_floats = max((s_[0] * s_[5] for s_ in shapes), default=0)
         self.max_dot_rows = max((s_[4] + 1 for s_, d in zip(shapes, has_dots) if d), default=0)
-        self._close(tab, "wdg_poly_filter_check_jobs")
+        self._more_fields(tab, entries)
+        self._close(tab, self._CHECK)
+
+    def _more_operands(self, e, order, mats):
+        """what a subclass's entry holds beyond these: checked, and added to `mats` - the operands an output must not overlap"""
+
+    def _more_fields(self, tab, entries):
+        """... and their fields of the records"""
 
     def launch(self):
         """out - and dots, where an entry has them - of every entry"""
-        self._launch("wdg_poly_filter_batched_f32", self.max_groups, self.max_floats, self.max_dot_rows)
+        self._launch(self._ENTRY, self.max_groups, self.max_floats, self.max_dot_rows)
+
+
+class RecurFilterBatch(PolyFilterBatch):
+    """Job table for wdg_recur_filter_batched_f32 (csrc/recur_filter.hip): PolyFilterBatch's filter in a basis with a three-term
+    recurrence, out = sum_{k = 0..K} gamma[k, seg] T_k with T_0 = v, T_{k+1} = a_k A_hat T_k + b_k T_k + c_k T_{k-1} - all K hops in one
+    launch and no LDS beyond PolyFilterBatch's: the same row limits, max_rows and default_group -, and optionally dots[k, seg] = <T_k, u>
+    (include/wdg.h states the arithmetic; tests/_recur_filter_ref.py restates it in numpy).  An entry is PolyFilterBatch's and `recur`:
+    an [order, 3] fp32 device matrix with unit inner stride whose row k is (a_k, b_k, c_k) - models.recurrence_table builds the
+    Chebyshev, Jacobi and Legendre ones; required unless order == 0.  The backward pass of a job is one more job: the transposed pattern
+    with the two scales swapped and the same table, v = d_out and u = H0."""
+
+    _KEYS = PolyFilterBatch._KEYS + ("recur",)
+    _RECORD, _CHECK, _ENTRY = _RECUR_FILTER_JOB_DTYPE, "wdg_recur_filter_check_jobs", "wdg_recur_filter_batched_f32"
+    _DEVICE_INPUTS = PolyFilterBatch._DEVICE_INPUTS + ("recur",)
+
+    def _more_operands(self, e, order, mats):
+        if e.get("recur") is None:
+            if order > 0:
+                raise ValueError(f"RecurFilterBatch: order {order} without recur; an [{order}, 3] fp32 matrix of (a_k, b_k, c_k) expected")
+            return
+        GatBatch._matrix("recur", e["recur"], (order, 3), "RecurFilterBatch")
+        if order > 0:
+            mats["recur"] = e["recur"]
+
+    def _more_fields(self, tab, entries):
+        self._point(tab, "recur", [e.get("recur") if int(e["order"]) > 0 else None for e in entries], ld="ld_recur")
 
 
 def acm_operand_gradient(d_pair, t_pair, d_full, width):
