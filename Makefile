@@ -13,6 +13,8 @@ LAST     += $(CSRC)/neighbor_sample.hip
 LAST     += $(CSRC)/neighbor_max.hip
 # ... and behind every one of them the recurrence filter (recur_filter), in a list of its own: the lines above end where tests/test_abi_neighbor_max.py reads them
 AFTER    := $(CSRC)/recur_filter.hip
+# ... and behind that the neighbour moments (neighbor_moments), on a line of its own: the line above ends where tests/test_abi_recur_filter.py reads it
+AFTER    += $(CSRC)/neighbor_moments.hip
 SRCS     := $(filter-out $(LAST) $(AFTER),$(SRCS)) $(LAST) $(AFTER)
 LINKFLAGS := --offload-arch=gfx950 -shared -fPIC
 # per-file flags: the 32 steps of kernel_reg.hip's in-wave substitution (the solver's k2_factor_invert; the file holds the solver and
@@ -51,6 +53,8 @@ FLAGS_gcnii := -ffp-contract=off
 FLAGS_drop_edge := -ffp-contract=off
 # neighbor_max.hip's backward pass is ONE fp32 add chain per element, stated in include/wdg.h and restated in numpy bit for bit: nothing is fused (the source says so as well)
 FLAGS_neighbor_max := -ffp-contract=off
+# neighbor_moments.hip's position chains, its centred second pass and its backward pass are stated operation by operation in include/wdg.h and restated in numpy bit for bit: every fmaf is written out, nothing else is fused
+FLAGS_neighbor_moments := -ffp-contract=off
 OBJS     := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB      := $(PKG)/lib/libwdg_hip.so
 

@@ -2510,6 +2510,140 @@ int wdg_neighbor_max_backward_batched_f32(const wdg_neighbor_max_backward_job *j
  *           table */
 int wdg_neighbor_max_backward_check_jobs(const wdg_neighbor_max_backward_job *jobs_host, int32_t n_jobs);
 
+/*
+ * The neighbour MOMENTS: per row and column the mean, the standard deviation, the maximum and the minimum of X over the row's stored
+ * neighbours, which neighbours the extremes were, and the neighbour count - the four aggregators of PNA (Corso, Cavalleri, Beaini, Lio,
+ * Velickovic, NeurIPS 2020) in ONE walk over the row, for a table of patterns in ONE launch.  The standard deviation is the CENTRED
+ * one - a second pass over the same values with the mean taken off -, not E[x^2] - E[x]^2, which in fp32 loses everything once a
+ * column's mean is large against its spread.
+ * The reference ships no model code: the operator is DEFINED here and is not claimed to reproduce an upstream table.
+ * replaces: nothing of the reference - it stands where the product with the normalised adjacency of normalize, utils/util_funcs.py:29-36,
+ *           and normalize_tensor, utils/util_funcs.py:365-380, stands in the other models, beside the tables of gnns_on_syn.py:9-53.
+ * A job: the pattern as in wdg_neighbor_max_job - rowptr int32 [n_rows + 1], col int32 [nnz], kept_len int32 [n_rows] or NULL (a plain
+ * CSR pattern; otherwise col is a thinned pattern's kept_col and a row's length is min(kept_len[i], rowptr[i + 1] - rowptr[i])) -,
+ * X [n_cols, n_feat] fp32 with leading dimension ldx, the results mean, std, mx, mn, each [n_rows, n_feat] fp32 with a leading dimension
+ * of its own (the four may be column slices of one [n_rows, 4 n_feat] matrix), arg_max and arg_min, int32 [n_rows, n_feat] with leading
+ * dimensions of their own, cnt int32 [n_rows], and eps.  A NULL mean, std, mx, mn, arg_max or arg_min is not wanted and not written
+ * (std needs the mean internally either way); cnt is always written.  The definition (tests/_neighbor_moments_ref.py restates it in
+ * numpy), for row i and column f:
+ *   positions    the row's first `len` stored entries sit at positions e = 0 .. len - 1; j = col[rowptr[i] + e].  An entry whose j lies
+ *                outside [0, n_cols) - which includes -1 - is SKIPPED, never read through.  c = the number of entries NOT skipped:
+ *                copies of a column count per occurrence, in c and in the sums, as in every sum of this library.  cnt[i] = c.
+ *   s1           FOUR CHAINS BY POSITION: chain k is acc = acc + X[j, f] from +0 over the entries not skipped with e % 4 == k, in stored
+ *                order; s1 = (c0 + c1) + (c2 + c3)
+ *   mean[i, f]   s1 / (float)c
+ *   s2           the same four chains with d = X[j, f] - mean[i, f]; acc = fmaf(d, d, acc)
+ *   std[i, f]    var = s2 / (float)c; sqrtf(var + eps)
+ *                - one rounded fp32 operation each, the fmaf written out, nothing else fused (csrc/neighbor_moments.hip is compiled with
+ *                contraction off); the division and sqrtf are the correctly rounded ones.  Where a result is a NaN its payload is not
+ *                part of the contract.
+ *   mx, arg_max  EXACTLY the Y and arg of wdg_neighbor_max_batched_f32 on the same pattern and X: the total order - a NaN above
+ *                everything, -0 == +0, a tie to the lower j -, the winner's BITS copied, the SET of the entries not skipped (copies of
+ *                one j are one pair)
+ *   mn, arg_min  the same with WDG_NEIGHBOR_MAX_MIN
+ *   c == 0       mean = std = mx = mn = +0, arg_max = arg_min = -1.  A row whose extent lies outside [0, nnz] is left untouched (cnt
+ *                too).  Every other element of the wanted blocks [0 : n_rows][0 : n_feat] is written and nothing outside them.
+ * The chains BY POSITION are the point: a column's bits depend neither on the job's width nor on how many lanes share the row - a job
+ * has the same bits alone and in any table, a column the same bits at any job width -, a wide job has four independent adds per column,
+ * and a narrow one work for four lane groups: a wave per row and per panel of 256 columns (four per lane); of the lane groups that hold
+ * no columns up to three more take whole chains (at n_feat <= 16 four lanes cover the columns and four shares walk the row).  The
+ * extremes are merged across the shares under the order, the chain sums by the tree above.  A row of one step stays in registers for the
+ * second pass, a longer one is read twice.  There is NO multi-wave path for a hub row.  No LDS, no atomics.  16-byte loads / stores where
+ * the pointer, the leading dimension and n_feat (a multiple of 4) allow - the wave's decision, one for X and one per result.
+ * No two of X and the results may overlap.
+ * max_rows, max_feat: the table's largest n_rows and n_feat (rows / columns beyond them are not worked on).
+ * Refused before any HIP call (WDG_ERR_INVALID): negative counts, more than 65535 jobs (a job per grid z), a NULL table with
+ * n_jobs > 0, max_feat above 256 * 65535.  n_jobs == 0, max_rows == 0 or max_feat == 0: WDG_OK, nothing is launched.  What is wrong inside
+ * a job - a negative n_rows, n_cols, n_feat or nnz, flag bits (none is defined), a reserved word that is not 0, an eps that is negative or
+ * not finite, a leading dimension below n_feat (of a result: where it is given), a NULL rowptr or cnt, a NULL col or X with nnz > 0 and
+ * n_cols > 0, two of X and the results at one address - is refused by wdg_neighbor_moments_check_jobs on the HOST copy of the table
+ * (neighbor_moments.NeighborMomentsBatch calls it before it uploads), and the launch leaves such a job untouched.  A job with
+ * n_rows == 0 or n_feat == 0 is skipped.
+ */
+typedef struct wdg_neighbor_moments_job {
+    const int32_t *rowptr;    /* [n_rows + 1] */
+    const int32_t *col;       /* [nnz]: a CSR pattern's col, or a thinned pattern's kept_col */
+    const int32_t *kept_len;  /* [n_rows], or NULL: every row's whole extent */
+    const float *X;           /* [n_cols, n_feat], leading dimension ldx */
+    float *mean;              /* out [n_rows, n_feat], leading dimension ld_mean, or NULL */
+    float *std;               /* out, ld_std, or NULL */
+    float *mx;                /* out, ld_mx, or NULL */
+    float *mn;                /* out, ld_mn, or NULL */
+    int32_t *arg_max;         /* out [n_rows, n_feat], ld_amax, or NULL */
+    int32_t *arg_min;         /* out, ld_amin, or NULL */
+    int32_t *cnt;             /* out [n_rows] */
+    int64_t ldx, ld_mean, ld_std, ld_mx, ld_mn, ld_amax, ld_amin;
+    int32_t n_rows, n_cols, n_feat, nnz;
+    float eps;                /* >= 0, finite */
+    int32_t flags;            /* must be 0 */
+    int32_t reserved;         /* must be 0 */
+    int32_t reserved2;        /* must be 0 */
+} wdg_neighbor_moments_job;
+int wdg_neighbor_moments_batched_f32(const wdg_neighbor_moments_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_feat,
+                                     wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the neighbour moments above (utils/util_funcs.py:29-36, 365-380), on the
+ *           host's table */
+int wdg_neighbor_moments_check_jobs(const wdg_neighbor_moments_job *jobs_host, int32_t n_jobs);
+
+/*
+ * The backward pass of the neighbour moments: d_X from the gradients of the four statistics, TWO launches inside one entry, no atomics.
+ * replaces: nothing of the reference - the transposed product that stands behind normalize, utils/util_funcs.py:29-36, and
+ *           normalize_tensor, utils/util_funcs.py:365-380, in the other models' backward passes (gnns_on_syn.py:9-53 holds their tables).
+ * A job: rowptr, col, kept_len of the TRANSPOSED pattern, plain or thinned (n_rows rows - the forward pass's columns - over n_src
+ * sources - the forward pass's rows); X [n_rows, n_feat] (the forward pass's X); g_mean, g_std, g_max, g_min [n_src, n_feat] fp32 (the
+ * gradients of the four statistics: a NULL one reads as +0); mean, std, arg_max, arg_min [n_src, n_feat] and cnt [n_src] (the forward
+ * pass's); A and B [n_src, n_feat] fp32 with leading dimension ldw, a WORKSPACE the table owns; D [n_rows, n_feat] fp32 with leading
+ * dimension ldd (d_X).  Every matrix has a leading dimension of its own.
+ * Launch 1, per forward row i and column f (c = cnt[i]):
+ *   c == 0: A[i, f] = B[i, f] = +0.  Otherwise B = g_std[i, f] / ((float)c * std[i, f]) (+0 where g_std is NULL) and
+ *   A = fmaf(-B, mean[i, f], g_mean[i, f] / (float)c).
+ * Launch 2, per transposed row j and column f, over the row's first `len` entries at positions e, i = col[q]; an entry with i outside
+ * [0, n_src) is SKIPPED:
+ *   SA, SB       four chains by position each, as in the forward pass, over A[i, f] and B[i, f] of the entries not skipped (copies count
+ *                per occurrence, as they did in the forward sums)
+ *   RM, Rm       four chains by position each over g_max[i, f] where arg_max[i, f] == j, and over g_min[i, f] where arg_min[i, f] == j,
+ *                under the duplicate rule of wdg_neighbor_max_backward_batched_f32: an entry whose i equals the i of the previous
+ *                entry that was not skipped routes nothing (one add per routed term, none elsewhere)
+ *   every group of four chains is merged (c0 + c1) + (c2 + c3);  D[j, f] = fmaf(X[j, f], SB, (SA + RM) + Rm)
+ * - the gradient of mean / sqrt(mean((x - m)^2) + eps) / amax / amin; one rounded operation each, the fmaf written out.  A row of the
+ * transposed pattern whose extent lies outside [0, nnz] is left untouched.  A job has the same bits alone and in any table, a column the
+ * same bits at any job width.  NO multi-wave path for a hub row.  No LDS, no atomics.  May any two operands alias?  None: D, A and B must
+ * not overlap each other or anything the job reads.
+ * max_rows, max_src, max_feat: the table's largest n_rows, n_src and n_feat.
+ * Refused before any HIP call (WDG_ERR_INVALID): as above (max_src counts as a count).  What is wrong inside a job - a negative shape,
+ * flag bits, a reserved word that is not 0, a leading dimension below n_feat, a NULL rowptr, X, D, A, B or cnt, a NULL col with nnz > 0 and
+ * n_src > 0, a g_mean without mean, a g_std without mean and std, a g_max or g_min without its arg, D, A or B at the address of another
+ * operand - is refused by wdg_neighbor_moments_backward_check_jobs on the HOST copy of the table
+ * (neighbor_moments.NeighborMomentsBackwardBatch calls it before it uploads), and the launches leave such a job untouched.
+ */
+typedef struct wdg_neighbor_moments_backward_job {
+    const int32_t *rowptr;    /* [n_rows + 1]: the TRANSPOSED pattern's */
+    const int32_t *col;       /* [nnz] */
+    const int32_t *kept_len;  /* [n_rows], or NULL */
+    const float *X;           /* [n_rows, n_feat], ldx: the forward pass's X */
+    const float *g_mean;      /* [n_src, n_feat], ld_gmean, or NULL: +0 */
+    const float *g_std;       /* ld_gstd, or NULL */
+    const float *g_max;       /* ld_gmax, or NULL */
+    const float *g_min;       /* ld_gmin, or NULL */
+    const float *mean;        /* [n_src, n_feat], ld_mean: the forward pass's */
+    const float *std;         /* ld_std */
+    const int32_t *arg_max;   /* ld_amax */
+    const int32_t *arg_min;   /* ld_amin */
+    const int32_t *cnt;       /* [n_src] */
+    float *A;                 /* workspace [n_src, n_feat], ldw */
+    float *B;                 /* workspace [n_src, n_feat], ldw */
+    float *D;                 /* out [n_rows, n_feat], ldd: d_X */
+    int64_t ldx, ld_gmean, ld_gstd, ld_gmax, ld_gmin, ld_mean, ld_std, ld_amax, ld_amin, ldw, ldd;
+    int32_t n_rows, n_src, n_feat, nnz;
+    int32_t flags;            /* must be 0 */
+    int32_t reserved;         /* must be 0 */
+} wdg_neighbor_moments_backward_job;
+int wdg_neighbor_moments_backward_batched_f32(const wdg_neighbor_moments_backward_job *jobs_dev, int32_t n_jobs, int32_t max_rows, int32_t max_src,
+                                              int32_t max_feat, wdg_stream_t stream);
+/* replaces: nothing of its own - the per-job refusals of the backward pass above (utils/util_funcs.py:29-36, 365-380), on the host's
+ *           table */
+int wdg_neighbor_moments_backward_check_jobs(const wdg_neighbor_moments_backward_job *jobs_host, int32_t n_jobs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,10 @@ SIGNATURES = {
     "wdg_neighbor_max_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_neighbor_max_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "wdg_neighbor_max_backward_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_neighbor_moments_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_neighbor_moments_check_jobs": (c_int, [c_void_p, c_int32]),
+    "wdg_neighbor_moments_backward_batched_f32": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "wdg_neighbor_moments_backward_check_jobs": (c_int, [c_void_p, c_int32]),
     "wdg_csr_transpose_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "wdg_synth_feature_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, ctypes.c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -514,6 +518,22 @@ class NeighborMaxBackwardJob(ctypes.Structure):
     """mirror of `wdg_neighbor_max_backward_job` (include/wdg.h)"""
     _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_len", "G", "arg", "D")] + [(name, c_int64) for name in ("ldg", "lda", "ldd")] + \
                [(name, c_int32) for name in ("n_rows", "n_src", "n_feat", "nnz", "reserved", "reserved2")]
+
+
+class NeighborMomentsJob(ctypes.Structure):
+    """mirror of `wdg_neighbor_moments_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_len", "X", "mean", "std", "mx", "mn", "arg_max", "arg_min", "cnt")] + \
+               [(name, c_int64) for name in ("ldx", "ld_mean", "ld_std", "ld_mx", "ld_mn", "ld_amax", "ld_amin")] + \
+               [(name, c_int32) for name in ("n_rows", "n_cols", "n_feat", "nnz")] + [("eps", ctypes.c_float)] + \
+               [(name, c_int32) for name in ("flags", "reserved", "reserved2")]
+
+
+class NeighborMomentsBackwardJob(ctypes.Structure):
+    """mirror of `wdg_neighbor_moments_backward_job` (include/wdg.h)"""
+    _fields_ = [(name, c_void_p) for name in ("rowptr", "col", "kept_len", "X", "g_mean", "g_std", "g_max", "g_min", "mean", "std", "arg_max", "arg_min",
+                                              "cnt", "A", "B", "D")] + \
+               [(name, c_int64) for name in ("ldx", "ld_gmean", "ld_gstd", "ld_gmax", "ld_gmin", "ld_mean", "ld_std", "ld_amax", "ld_amin", "ldw", "ldd")] + \
+               [(name, c_int32) for name in ("n_rows", "n_src", "n_feat", "nnz", "flags", "reserved")]
 
 
 if not os.path.exists(LIB_PATH):

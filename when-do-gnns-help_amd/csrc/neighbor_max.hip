@@ -29,6 +29,7 @@
 // No LDS, no atomics, no scratch.
 #include <cstdint>
 
+#include "neighbor_order.h"
 #include "wave_rows.h"
 #include "wdg_common.h"
 
@@ -44,19 +45,7 @@ constexpr int NM_MAX_PANELS = 65535;  // gridDim.y
 constexpr int NB_DEPTH = 8;           // backward: row loads in flight before the first add of a batch
 constexpr int NM_KNOWN_FLAGS = WDG_NEIGHBOR_MAX_MIN;
 
-// the image of a value under the order: greater = wins.  A NaN: 0xffffffff; -0 and +0 share an image; every other image lies in
-// [0x007fffff, 0xff800000], for the maximum and (complemented) for the minimum alike - never 0, the word of "no entry yet"
-__device__ __forceinline__ uint32_t nm_key(uint32_t b, const bool minimum) {
-    const uint32_t a = b & 0x7fffffffu;
-    if (a > 0x7f800000u) return 0xffffffffu;
-    if (a == 0) b = 0;
-    const uint32_t m = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return minimum ? ~m : m;
-}
-__device__ __forceinline__ uint64_t nm_shfl_xor64(const uint64_t w, const int off) {
-    const uint32_t lo = __shfl_xor(static_cast<int>(static_cast<uint32_t>(w)), off), hi = __shfl_xor(static_cast<int>(static_cast<uint32_t>(w >> 32)), off);
-    return static_cast<uint64_t>(hi) << 32 | lo;
-}
+// (the order itself - nm_key, the image of a value, and nm_shfl_xor64, a lane's word across lanes - is csrc/neighbor_order.h's)
 
 // one step of the lane's share: the U entries e0 + u S + s (those below len), all requested before the first compare
 template <bool VEC, int U>

@@ -1,7 +1,7 @@
 // What the wave-per-row kernels share, stated once: a row's extent, the 16-byte decision, four adjacent words of a row, and the THINNED
 // ROW - the layout that drop_edge.hip and neighbor_sample.hip write and that drop_edge.hip's aggregation and neighbor_max.hip read
 // (include/wdg.h, at wdg_drop_edge_thin_batched, DEFINES it; this header only implements it).  Users: drop_edge.hip,
-// neighbor_sample.hip, neighbor_max.hip, gcnii.hip, gat_scores.hip and gat_lanes.h (gat.hip, signed_att.hip).
+// neighbor_sample.hip, neighbor_max.hip, neighbor_moments.hip, gcnii.hip, gat_scores.hip and gat_lanes.h (gat.hip, signed_att.hip).
 //
 // No LDS, no atomics, no fused multiply-add, and no floating-point expression that could contract - only the ONE division (or 1 / sqrtf)
 // of a row's scale: the header means the same in a unit compiled with contraction off and in one compiled without.

@@ -67,6 +67,13 @@ ORTHOGONAL polynomial basis - Chebyshev polynomials of -A_hat with coefficients 
 column (Wang, Zhang, "How Powerful are Spectral Graph Neural Networks") - whose three-term recurrence (`recurrence_table`) runs all K hops
 in one launch of csrc/recur_filter.hip, in the LDS the monomial filter uses; the backward pass is one more launch of the same kernel on the
 transposed pattern.  Defined by this project as well.
+
+PNA-1 / -2 (`PNA1`, `PNA2`, `pna_delta`) aggregate a transform of the neighbours four ways at once - mean, standard
+deviation, maximum, minimum - under three degree scalers (Corso, Cavalleri, Beaini, Lio, Velickovic, "Principal Neighbourhood Aggregation
+for Graph Nets"): the SPREAD of a neighbourhood is the statistic that says "my neighbours disagree".  `adj.neighbor_moments(x)` runs on
+csrc/neighbor_moments.hip - one walk over a row for all four, the deviation centred, one autograd function whose backward pass is one
+entry on the transposed pattern - over a NormAdj's stored pattern and over the thinned views alike.  Defined by this project as well (the
+paper's layer without towers, edge features, biases and normalisation).
 """
 import math
 
@@ -88,7 +95,7 @@ class NormAdj:
         self.graph, self.graph_t = g, g.transpose()
         self.row_scale, self.col_scale = d, (d if symmetric else None)
         self.n = g.n_rows
-        self._attention, self._max_tables = None, {}
+        self._attention, self._max_tables, self._moments_tables = None, {}, {}
 
     def matmul(self, x):
         return _Aggregate.apply(x, self)
@@ -110,6 +117,17 @@ class NormAdj:
         """the forward job (-> y, arg; arg None when no gradient is wanted) or the backward job on graph_t (x = d_y -> d_x): a one-job
         table and its buffers per (direction, width, with arg), built on first use"""
         return _max_pass(self._max_tables, self.graph, self.graph_t, backward, x, arg)
+
+    def neighbor_moments(self, x, eps=1e-5):
+        """[n, F] -> (agg [n, 4 F] = [mean | std | max | min] of x over every row's stored neighbours, cnt int32 [n]: how many there
+        were), with autograd through agg - ONE function, whose backward pass is one entry on graph_t (csrc/neighbor_moments.hip; the
+        scales are not read).  A row without neighbours gets +0 four times and passes no gradient."""
+        return _NeighborMoments.apply(x, self, float(eps))
+
+    def _moments_pass(self, backward, x, eps, more):
+        """the forward job (-> agg, cnt, arg_max, arg_min; the args None when no gradient is wanted) or the backward entry on graph_t
+        (-> d_x): a one-job table and its buffers per (direction, width, ...), built on first use"""
+        return _moments_pass(self._moments_tables, self.graph, self.graph_t, backward, x, eps, more)
 
     def attention_plan(self):
         """what the attention kernels need of the pattern, built on first use and kept: dict(graph, graph_t, t_pos) - t_pos ties
@@ -181,6 +199,68 @@ class _NeighborMax(torch.autograd.Function):
     def backward(ctx, gy):
         (arg,) = ctx.saved_tensors
         return ctx.adj._max_pass(True, gy.contiguous(), arg), None
+
+
+def _moments_pass(tables, pattern, pattern_t, backward, x, eps, more):
+    """What NormAdj._moments_pass and _ResampledAdj._moments_pass share: the one-job ops.NeighborMomentsBatch /
+    NeighborMomentsBackwardBatch and its buffers in `tables`, built on first use - before any capture.  Forward: x, eps and more =
+    whether the args are wanted (evaluation writes none) -> (agg, cnt, arg_max or None, arg_min or None); backward: x = the forward
+    pass's x, more = (d_agg, agg, cnt, arg_max, arg_min) -> d_x."""
+    f, dev = int(x.shape[1]), x.device
+    part = lambda t, q: t[:, q * f:(q + 1) * f]  # noqa: E731
+    if backward:
+        key = (True, f)
+        if key not in tables:
+            n_src, n = pattern_t.n_cols, pattern_t.n_rows
+            b = dict(x=torch.zeros((n, f), dtype=torch.float32, device=dev), g=torch.zeros((n_src, 4 * f), dtype=torch.float32, device=dev),
+                     agg=torch.ones((n_src, 4 * f), dtype=torch.float32, device=dev), cnt=torch.zeros(n_src, dtype=torch.int32, device=dev),
+                     arg_max=torch.full((n_src, f), -1, dtype=torch.int32, device=dev), arg_min=torch.full((n_src, f), -1, dtype=torch.int32, device=dev),
+                     d=torch.zeros((n, f), dtype=torch.float32, device=dev))
+            b["table"] = ops.NeighborMomentsBackwardBatch([dict(
+                pattern=pattern_t, x=b["x"], d=b["d"], cnt=b["cnt"], g_mean=part(b["g"], 0), g_std=part(b["g"], 1), g_max=part(b["g"], 2),
+                g_min=part(b["g"], 3), mean=part(b["agg"], 0), std=part(b["agg"], 1), arg_max=b["arg_max"], arg_min=b["arg_min"])])
+            tables[key] = b
+        b = tables[key]
+        for name, t in zip(("x", "g", "agg", "cnt", "arg_max", "arg_min"), (x,) + tuple(more)):
+            b[name].copy_(t)
+        b["table"].launch()
+        return b["d"].clone()
+    key = (False, f, float(eps), bool(more))
+    if key not in tables:
+        n, n_cols = pattern.n_rows, pattern.n_cols
+        b = dict(x=torch.zeros((n_cols, f), dtype=torch.float32, device=dev), agg=torch.zeros((n, 4 * f), dtype=torch.float32, device=dev),
+                 cnt=torch.zeros(n, dtype=torch.int32, device=dev))
+        for name in ("arg_max", "arg_min"):
+            b[name] = torch.full((n, f), -1, dtype=torch.int32, device=dev) if more else None
+        b["table"] = ops.NeighborMomentsBatch([dict(pattern=pattern, x=b["x"], cnt=b["cnt"], mean=part(b["agg"], 0), std=part(b["agg"], 1),
+                                                    max=part(b["agg"], 2), min=part(b["agg"], 3), arg_max=b["arg_max"], arg_min=b["arg_min"], eps=key[2])])
+        tables[key] = b
+    b = tables[key]
+    b["x"].copy_(x)
+    b["table"].launch()
+    return b["agg"].clone(), b["cnt"].clone(), (b["arg_max"].clone() if more else None), (b["arg_min"].clone() if more else None)
+
+
+class _NeighborMoments(torch.autograd.Function):
+    """agg, cnt = adj.neighbor_moments(x): the forward pass keeps x, agg (its mean and std), cnt and the two args - nothing under
+    no_grad -, the backward pass is ONE entry on the transposed pattern (csrc/neighbor_moments.hip: an elementwise launch, then the
+    gather).  cnt carries no gradient.  adj: a NormAdj or a thinned view, whose backward pass must precede the next resample() - the
+    same refusal as _NeighborMax's."""
+
+    @staticmethod
+    def forward(ctx, x, adj, eps):
+        want = ctx.needs_input_grad[0]
+        agg, cnt, arg_max, arg_min = adj._moments_pass(False, x, eps, want)
+        ctx.adj = adj
+        ctx.mark_non_differentiable(cnt)
+        if want:
+            ctx.save_for_backward(x, agg, cnt, arg_max, arg_min)
+        return agg, cnt
+
+    @staticmethod
+    def backward(ctx, g_agg, _):
+        x, agg, cnt, arg_max, arg_min = ctx.saved_tensors
+        return ctx.adj._moments_pass(True, x, None, (g_agg.contiguous(), agg, cnt, arg_max, arg_min)), None, None
 
 
 class _Linear(torch.autograd.Function):
@@ -1326,9 +1406,72 @@ class SAGEPool2(_PoolLayer, _HiddenDropout, torch.nn.Module):
         return self._pool(adj, h, self.w_p1, self.w_s1, self.w_n1)
 
 
+def pna_delta(adj):
+    """PNA's delta of a graph: the mean over the nodes of log(c_i + 1), c_i the node's stored neighbours on the FULL pattern (adj: a
+    NormAdj, a NeighborSampleAdj or a DropEdgeAdj - its .graph), in fp64 on the host"""
+    rowptr = adj.graph.rowptr.cpu().numpy().astype(np.int64)
+    return float(np.log(np.diff(rowptr) + 1.0).mean())
+
+
+class _PnaLayer:
+    """The layer PNA1 / PNA2 share: P = M w_pre, AGG, cnt = neighbor_moments(P), T = AGG w_post with w_post [4 nagg, 3 out],
+    out = M w_self + T[:, :out] + amp * T[:, out : 2 out] + att * T[:, 2 out :] - the identity, amplification and attenuation scalers
+    amp_i = log(c_i + 1) / delta, att_i = delta / log(c_i + 1) (0 where c_i = 0), formed by torch operations from the kernel's cnt
+    inside the step: the draw's own counts on a sampled view.  No gradient flows to them."""
+
+    @staticmethod
+    def _check_delta(delta):
+        if not isinstance(delta, (int, float)) or isinstance(delta, bool) or not math.isfinite(delta) or delta <= 0:
+            raise ValueError(f"PNA: delta must be a finite number > 0 (models.pna_delta(adj)), got {delta!r}")
+        return float(delta)
+
+    @staticmethod
+    def _pna(adj, m, w_pre, w_self, w_post, delta, eps=1e-5):
+        out = w_self.shape[1]
+        agg, cnt = adj.neighbor_moments(_Linear.apply(m, w_pre, False), eps)
+        t = _Linear.apply(agg, w_post, False)
+        with torch.no_grad():
+            lg = torch.log(cnt.to(torch.float32) + 1.0)[:, None]
+            amp, att = lg / delta, torch.where(lg > 0, delta / lg, torch.zeros_like(lg))
+        return _Linear.apply(m, w_self, False) + t[:, :out] + amp * t[:, out:2 * out] + att * t[:, 2 * out:]
+
+
+class PNA1(_PnaLayer, torch.nn.Module):
+    """PNA-1 (Corso et al., NeurIPS 2020: the mean, std, max and min aggregators under the identity, amplification and attenuation
+    scalers; without towers, edge features, biases and post-layer normalisation), one layer: logits = _PnaLayer's out at class width.
+    delta: models.pna_delta(adj).  Give the adjacency add_self_loops=False, as for SAGE1: the model holds the self path.  adj: a
+    NormAdj's stored pattern, or the sample / subset of a NeighborSampleAdj's / DropEdgeAdj's view.  Parameters are drawn in this order:
+    w_pre [nfeat, nagg], w_self [nfeat, C], w_post [4 nagg, 3 C] (xavier_uniform each)."""
+
+    def __init__(self, nfeat, nclass, delta, nagg=64):
+        super().__init__()
+        self.delta = self._check_delta(delta)
+        self.w_pre, self.w_self, self.w_post = _xavier(nfeat, nagg), _xavier(nfeat, nclass), _xavier(4 * nagg, 3 * nclass)
+
+    def forward(self, adj, x):
+        return self._pna(adj, x, self.w_pre, self.w_self, self.w_post, self.delta)
+
+
+class PNA2(_PnaLayer, _HiddenDropout, torch.nn.Module):
+    """PNA-2: PNA1's layer twice with _HiddenDropout's ReLU + dropout between.  Parameters are drawn in this order: w_pre0 [nfeat, nagg],
+    w_self0 [nfeat, nhid], w_post0 [4 nagg, 3 nhid], w_pre1 [nhid, nagg], w_self1 [nhid, C], w_post1 [4 nagg, 3 C] (xavier_uniform
+    each).  dropout_rng: as for GCN2."""
+
+    def __init__(self, nfeat, nclass, delta, nhid=64, nagg=64, dropout=0.5, dropout_rng=None):
+        super().__init__()
+        self.delta = self._check_delta(delta)
+        self.w_pre0, self.w_self0, self.w_post0 = _xavier(nfeat, nagg), _xavier(nfeat, nhid), _xavier(4 * nagg, 3 * nhid)
+        self.w_pre1, self.w_self1, self.w_post1 = _xavier(nhid, nagg), _xavier(nhid, nclass), _xavier(4 * nagg, 3 * nclass)
+        self.dropout, self.dropout_rng = dropout, dropout_rng
+
+    def forward(self, adj, x):
+        h = self._relu_dropout(self._pna(adj, x, self.w_pre0, self.w_self0, self.w_post0, self.delta))
+        return self._pna(adj, h, self.w_pre1, self.w_self1, self.w_post1, self.delta)
+
+
 _DROP_EDGE_SERVED = ("a thinned view of a DropEdgeAdj has no stored pattern to read: it serves the models that aggregate through matmul / "
                      "aggregate / aggregate_t - GCN2, ACMGCN2, GPRGNN1 / GPRGNN2 with fused=False, GCNII, SAGE1 / SAGE2"
-                     " - or pool through neighbor_max - SAGEPool1 / SAGEPool2")
+                     " - or pool through neighbor_max - SAGEPool1 / SAGEPool2 - or aggregate through neighbor_moments - PNA1 / PNA2")
 
 
 class _ThinnedAdj:
@@ -1356,6 +1499,13 @@ class _ThinnedAdj:
     def _max_pass(self, backward, x, arg):
         return self._owner._max_pass(backward, self._draw, x, arg)
 
+    def neighbor_moments(self, x, eps=1e-5):
+        """NormAdj.neighbor_moments over the kept entries of this draw: cnt is the draw's own count"""
+        return _NeighborMoments.apply(x, self, float(eps))
+
+    def _moments_pass(self, backward, x, eps, more):
+        return self._owner._moments_pass(backward, self._draw, x, eps, more)
+
     def attention_plan(self):
         raise TypeError("attention_plan: " + _DROP_EDGE_SERVED)
 
@@ -1380,7 +1530,7 @@ class _ResampledAdj:
         self.graph, self.n = self.full.graph, self.full.n
         self.step = torch.zeros(1, dtype=torch.int32, device=self.graph.device)
         self.draws = 0  # resample() calls so far, on the host: a view whose draw is not the latest refuses its backward pass
-        self._batch, self._products, self._max_tables = None, {}, {}
+        self._batch, self._products, self._max_tables, self._moments_tables = None, {}, {}, {}
 
     def resample(self):
         """thin both patterns at the current step word, advance the word on the device -> the thinned view of this draw"""
@@ -1416,6 +1566,14 @@ class _ResampledAdj:
         self._refuse_stale(draw)
         b = self.batch()
         return _max_pass(self._max_tables, b.thinned(0), b.thinned_t(0), backward, x, arg)
+
+
+    def _moments_pass(self, backward, draw, x, eps, more):
+        """the neighbour moments over the kept entries, or their backward entry on the thinned transposed pattern (_moments_pass above),
+        through tables that hold the addresses of the batch's blocks"""
+        self._refuse_stale(draw)
+        b = self.batch()
+        return _moments_pass(self._moments_tables, b.thinned(0), b.thinned_t(0), backward, x, eps, more)
 
 
 class DropEdgeAdj(_ResampledAdj):

@@ -49,6 +49,10 @@ This module is the one namespace callers use (`from wdg_amd import ops`); the co
                         the same thinned patterns - the transposed one recomputed from one threshold word per forward row)
   neighbor_max.py       NeighborMaxBatch (the per-column maximum over every row's stored neighbours and which neighbour it was, over plain and
                         thinned patterns), NeighborMaxBackwardBatch (its backward pass: a job on the transposed pattern), neighbor_max
+  neighbor_moments.py   NeighborMomentsBatch (PNA's four aggregators in one walk: per column the mean, the centred standard deviation, the
+                        maximum and the minimum over every row's stored neighbours, the winners and the neighbour count, over plain and
+                        thinned patterns), NeighborMomentsBackwardBatch (its backward pass: an elementwise launch and a job on the
+                        transposed pattern inside one entry), neighbor_moments
   split_train.py        SplitTrainBatch (all splits of ONE graph trained as a single stacked run; reached as ops.SplitTrainBatch;
                         optimizer="device": per-replica lr / weight_decay / dropout), grid_search (a hyperparameter grid over all
                         splits as stacked chunks), select_settings
@@ -88,6 +92,7 @@ from .train import dropout_constants, AcmMixBatch, AcmMixPackedBatch, AdamBatch,
 from .drop_edge import DropEdgeBatch, ThinnedPattern, ThinnedSpmmBatch, DROP_EDGE_KEEP_DIAGONAL, DROP_EDGE_NORM_SYM, DROP_EDGE_TIED, DROP_EDGE_TRANSPOSED  # noqa: F401
 from .neighbor_sample import NeighborSampleBatch, NEIGHBOR_SAMPLE_KEEP_DIAGONAL, NEIGHBOR_SAMPLE_NORM_SYM, NEIGHBOR_SAMPLE_TRANSPOSED  # noqa: F401
 from .neighbor_max import neighbor_max, NeighborMaxBackwardBatch, NeighborMaxBatch, NEIGHBOR_MAX_MIN  # noqa: F401
+from .neighbor_moments import neighbor_moments, NeighborMomentsBackwardBatch, NeighborMomentsBatch  # noqa: F401
 from .synth import class_graphs_device, ClassGraphBatch, gauss_features_device, GaussFeatureBatch, regular_graph_device, sample_feature_rows  # noqa: F401
 from .sparse_features import as_compact, DeviceFeatures, expand_features, feature_image_floats, FeatureExpand, SparseDenseBatch, SparseFeatures  # noqa: F401
 from .kernel_regression import (  # noqa: F401
